@@ -2,7 +2,7 @@
 (README.md:71-73 rows; BASELINE.json metric), measured the way WIS measures `infer_speedup`
 (main.py:576,756-760): realtime multiple = audio_ms / infer_ms.
 
-    python bench.py [--gpus N --steps K --warmup W] [--model large --beam 5 --clip 3sec --batch 1]
+    python bench.py [--gpus N --steps K --warmup W] [--model large --beam 5 --clip 3sec --batch 1] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 A "step" is one pass of the hot path (log-mel -> encoder -> cross-K/V -> prefill -> beam-search decode ->
@@ -61,17 +61,8 @@ def cpu_baseline(size, weights, pcm, beam, fixed_new, audio_ms):
     torch.set_num_threads(enc_t)
     a = W.arch(size)
     ref = WhisperRef(weights, a["d_model"], a["n_layers"], a["n_heads"])
-    # log-mel: the reference's own wis/audio.py when its tree is present (the build container), else the oracle's numpy restatement
-    # of it (the GPU box has no /root/reference)
+    # log-mel: the oracle's numpy restatement of the reference's wis/audio.py (pinned to it by tests/golden/logmel_*.npz)
     mel_fn, mel_src = (lambda x: audio_ref.log_mel_spectrogram(audio_ref.pad_or_trim(x))), "oracle/audio_ref.py (numpy restatement of wis/audio.py)"
-    if os.path.exists("/root/reference/wis/audio.py"):
-        try:
-            sys.path.insert(0, "/root/reference")
-            from wis.audio import log_mel_spectrogram as ref_mel, pad_or_trim as ref_pad
-            ref_mel(ref_pad(pcm))          # first call builds the window / filter tensors
-            mel_fn, mel_src = (lambda x: ref_mel(ref_pad(x)).numpy()), "the reference's wis/audio.py (torch CPU)"
-        except Exception as e:      # noqa: BLE001
-            log(f"reference wis/audio.py not usable ({e}); timing the oracle's log-mel")
     t0 = time.perf_counter()
     mel = np.asarray(mel_fn(pcm), np.float32)
     t1 = time.perf_counter()
@@ -94,10 +85,9 @@ def cpu_baseline(size, weights, pcm, beam, fixed_new, audio_ms):
     t3 = time.perf_counter()
     enc_s, dec_s = t2e - t0, t3 - t2
     total = enc_s + dec_s
-    # (round-5 review item 7: `kind` says which log-mel the host timed - "port" alone only where the reference's own wis/audio.py ran)
-    kind = "port" if mel_src.startswith("the reference") else "port (log-mel: numpy oracle)"
-    return {"value": round(audio_ms / 1000.0 / total, 4), "unit": "x realtime", "cores": max(enc_t, best_t), "kind": kind,
-            "logmel_timed": mel_src,          # which log-mel ran on the host: the reference's own module only where /root/reference exists (not on the GPU box)
+    # (round-5 review item 7: `kind` says which log-mel the host timed)
+    return {"value": round(audio_ms / 1000.0 / total, 4), "unit": "x realtime", "cores": max(enc_t, best_t), "kind": "port (log-mel: numpy oracle)",
+            "logmel_timed": mel_src,
             "sample": (f"torch-fp32 oracle (KV-cached), the whole utterance measured: log-mel {1e3 * (t1 - t0):.0f} ms [{mel_src}] + encoder {1e3 * (t2e - t1):.0f} ms on {enc_t} host "
                        f"threads (best of 16/32/64/{cores} on a probe GEMM) + cross-KV, prefill and all {fixed_new + 1} beam-{beam} steps {1e3 * dec_s:.0f} ms on {best_t} threads "
                        f"(best of 8/16/32/{cores} on one step), {len(ids)} tokens = {total:.2f} s per utterance. Stand-in for the CT2 int8 CPU path (not installable offline); "
@@ -426,7 +416,7 @@ def natural_eot(lib, a, weights, dev, pcm, beam, audio_ms, make_step, timed, las
     rows = {}
     try:
         for B in (1, batch):
-            st_nat, (_k, lens) = make_step(h, pcm, beam, B, 0, _lib.WIS_IN_PCM_DEV)
+            st_nat, (_k, lens, _ids, _scores) = make_step(h, pcm, beam, B, 0, _lib.WIS_IN_PCM_DEV)
             l_nat = timed(st_nat, 20 if B == 1 else 10, 3)
             tm = last_timing(h)
             ran, needed, n_tok = int(tm["decode_steps"]), int(tm["decode_steps_needed"]), int(lens[0])
@@ -460,7 +450,11 @@ def main():
     ap.add_argument("--no-extras", action="store_true", help="skip the other BASELINE configurations, the batch-8 line, the boundary variants and the REST load replay")
     ap.add_argument("--rest-clients", type=int, default=64)
     ap.add_argument("--no-batched", action="store_true", help="N > 1 only: skip the 8-utterances-per-device-batch leg (BASELINE configs[3]) after the headline")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the last timed step returned (rank 0) as DIR/<name>.npy: "
+                    "sequences_ids (float64, -1 past each length), lengths (float64), scores (float32)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     rank = int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -558,7 +552,7 @@ def main():
             _lib.check(lib.wis_generate(h, src, B, prompt.ctypes.data_as(C.POINTER(C.c_int32)), len(PROMPT), C.byref(opts),
                                         ids.ctypes.data_as(C.POINTER(C.c_int32)), lens.ctypes.data_as(C.POINTER(C.c_int32)),
                                         scores.ctypes.data_as(C.POINTER(C.c_float))))
-        return step, (keep, lens)
+        return step, (keep, lens, ids, scores)
 
     def timed(step, n, warm):
         for _ in range(warm):
@@ -578,7 +572,7 @@ def main():
     pcm, audio_ms, clip_path = clip_pcm(args.clip)
     B = args.batch
     fixed_new = FIXED_NEW.get(args.clip, 16)
-    step, (d_pcm, lens) = make_step(handle, pcm, args.beam, B, fixed_new, _lib.WIS_IN_PCM_DEV)      # inputs resident in HBM before the timed region
+    step, (d_pcm, lens, ids, scores) = make_step(handle, pcm, args.beam, B, fixed_new, _lib.WIS_IN_PCM_DEV)      # inputs resident in HBM before the timed region
 
     def fence():
         if use_dist:
@@ -604,13 +598,22 @@ def main():
         t = torch.tensor([elapsed], dtype=torch.float64, device=f"cuda:{dev}")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if rank == 0 and args.dump_outputs:
+        # the headline path's results of its last timed step, as a caller of wis_generate receives them; inputs (seeded weights, the
+        # committed clip) are the same on every run, so two builds can be compared array by array
+        n = int(lens.max())
+        seq = np.where(np.arange(n)[None, :] < lens[:, None], ids[:, :n], -1).astype(np.float64)
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        for name, arr in (("sequences_ids", seq), ("lengths", lens.astype(np.float64)), ("scores", scores.astype(np.float32))):
+            np.save(os.path.join(args.dump_outputs, name + ".npy"), arr)
+        log(f"outputs of the last timed step written to {args.dump_outputs}")
 
     # ---- N > 1: BASELINE configs[3] (64 concurrent 3.84 s utterances over 8 GPUs = 8 per device batch per GPU, client/jmeter-asr.jmx:53-90).
     # The headline above stays one utterance per step per GPU (`value`); this second timed region runs device batches of 8 on every rank,
     # same barrier / max-over-ranks timing, so the driver's N = 1, 2, 4, 8 runs also carry the BATCHED-throughput scaling north_star asks for.
     batched = None
     if batched_B:
-        stepB, (_keepB, lensB) = make_step(handle, pcm, args.beam, batched_B, fixed_new, _lib.WIS_IN_PCM_DEV)
+        stepB, (_keepB, lensB, _idsB, _scoresB) = make_step(handle, pcm, args.beam, batched_B, fixed_new, _lib.WIS_IN_PCM_DEV)
         kB = max(4, min(args.steps, 12))
         for _ in range(2):
             stepB()

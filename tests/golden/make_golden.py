@@ -18,6 +18,10 @@ What it pins:
                               windows of 0/1/2 tokens and windows shorter than the overlap), evaluated by the reference's own
                               code under its pinned numpy's comparison semantics (np123_shim.py).  `--lcs-only` rewrites just
                               this file.
+  * lcs_fuzz.json           — the reference's `find_longest_common_sequence` on the 3 000 seeded random windows of
+                              tests/test_lcs_fuzz.py (`_cases(3000, 2024)`), under np123_shim.py; per case also whether the
+                              installed numpy evaluates the reference natively to the same ids (null: it raises).  `--lcs-fuzz-only`
+                              rewrites just this file.
 The decoder used to read the FLAC clips here is this repo's own C decoder, verified by MD5.
 """
 import ctypes
@@ -51,7 +55,36 @@ def decode(path):
     return np.ctypeslib.as_array(p, shape=(n.value,)).copy()
 
 
+def lcs_fuzz():
+    import hashlib
+    import wis.audio as ref_audio
+    sys.path.insert(0, HERE)
+    sys.path.insert(0, ROOT)
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    from np123_shim import numpy_1_23_semantics
+    from test_lcs_fuzz import FUZZ_N, FUZZ_SEED, Tok, _cases
+    cases = list(_cases(FUZZ_N, FUZZ_SEED))
+    want, native = [], []
+    for lists in cases:
+        seqs = [(l, (1, 0, 0)) for l in lists]
+        with numpy_1_23_semantics(ref_audio):
+            w = [int(v) for v in ref_audio.find_longest_common_sequence(seqs, Tok)]
+        try:
+            raw = [int(v) for v in ref_audio.find_longest_common_sequence(seqs, Tok)]
+        except ValueError:
+            raw = None
+        want.append(w)
+        native.append(None if raw is None else raw == w)
+    out = {"n": FUZZ_N, "seed": FUZZ_SEED, "cases_sha256": hashlib.sha256(json.dumps(cases).encode()).hexdigest(), "want": want, "native": native}
+    with open(os.path.join(HERE, "lcs_fuzz.json"), "w") as f:
+        json.dump(out, f, separators=(",", ":"))
+    print("lcs_fuzz:", len(want), "cases,", sum(1 for v in native if v), "evaluated natively")
+
+
 def main():
+    if "--lcs-fuzz-only" in sys.argv:
+        lcs_fuzz()
+        return
     from wis.audio import chunk_iter, find_longest_common_sequence, log_mel_spectrogram, pad_or_trim  # the reference
     sys.path.insert(0, HERE)
     lcs_only = "--lcs-only" in sys.argv      # regenerate chunker_lcs.json only (the npz fixtures stay byte-identical)
@@ -124,6 +157,7 @@ def main():
     with open(os.path.join(HERE, "chunker_lcs.json"), "w") as f:
         json.dump(cases, f)
     print("lcs outs:", [c["out"] if isinstance(c["out"], str) else len(c["out"]) for c in cases["lcs"]])
+    lcs_fuzz()
 
 
 if __name__ == "__main__":

@@ -5,7 +5,7 @@ leaves the fp64 reference by more than 0.05 (tile index, column within the tile,
     WIS_FRAG_NB=2 python tools/debug_frag2.py        # DBG48=1: four launches at 48 rows instead
 """
 import sys, os, numpy as np
-sys.path.insert(0, os.path.join(os.environ.get("GRAFT_REPO_ROOT", "/root/repo"), "willow-inference-server_amd"))
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "willow-inference-server_amd"))
 from wis_hip import _lib
 from wis_hip._lib import DevBuf, check
 lib = _lib.load()

@@ -9,7 +9,7 @@ import threading
 
 import numpy as np
 
-ROOT = os.environ.get("GRAFT_REPO_ROOT", os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "willow-inference-server_amd"))
 from wis_hip import _lib, ctranslate2 as ct2          # noqa: E402
 
