@@ -2,7 +2,7 @@
 (README.md:71-73 rows; BASELINE.json metric), measured the way WIS measures `infer_speedup`
 (main.py:576,756-760): realtime multiple = audio_ms / infer_ms.
 
-    python bench.py [--gpus N --steps K --warmup W] [--model large --beam 5 --clip 3sec --batch 1] [--dump-outputs DIR]
+    python bench.py [--gpus N --steps K --warmup W] [--model large --beam 5 --clip 3sec --batch 1] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 A "step" is one pass of the hot path (log-mel -> encoder -> cross-K/V -> prefill -> beam-search decode ->
@@ -12,6 +12,11 @@ checkpoint exists offline); decode length follows the measurement convention of 
 tokens for the 3.84 s clip, EOT masked until S then forced).  With N > 1 every rank owns one GPU and its
 own utterance stream (weak scaling, no data-path collective); weights are generated on rank 0 and
 broadcast once over RCCL/xGMI.  Rank 0 prints ONE JSON line.
+
+A plain run sets up, warms up, times the steps, writes `--dump-outputs` and prints the line; nothing else.  `--full` adds
+everything else the line can carry, after the timed steps: the roofline tap, the CPU baseline, the other BASELINE
+configurations, the boundary variants, concurrency, REST load and streaming rows, the natural-EOT row and, with N > 1, the
+batched leg.  The `--no-*` switches trim a `--full` run.
 """
 import argparse
 import ctypes as C
@@ -443,9 +448,11 @@ def main():
     ap.add_argument("--batch", type=int, default=1)
     ap.add_argument("--compute-type", default="float16", choices=["float16", "int8_float16"],
                     help="decoder weight storage; the headline number is float16 (int8_float16 mirrors the reference's GPU default)")
+    ap.add_argument("--full", action="store_true", help="after the headline, measure everything else the line can carry (see the module docstring); "
+                    "off: only the headline")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-roofline", action="store_true")
-    ap.add_argument("--natural-eot", action="store_true", help="run the natural-EOT row even with --no-extras")
+    ap.add_argument("--natural-eot", action="store_true", help="run the natural-EOT row even with --no-extras (needs --full)")
     ap.add_argument("--no-natural-eot", action="store_true", help="skip the natural-EOT row (a second large-v2 replica on EOT-ramp weights)")
     ap.add_argument("--no-extras", action="store_true", help="skip the other BASELINE configurations, the batch-8 line, the boundary variants and the REST load replay")
     ap.add_argument("--rest-clients", type=int, default=64)
@@ -455,6 +462,8 @@ def main():
     args = ap.parse_args()
     if args.steps < 1:
         ap.error("--steps must be at least 1")
+    if args.natural_eot and not args.full:
+        ap.error("--natural-eot needs --full")
 
     rank = int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -492,6 +501,8 @@ def main():
     a = W.arch(args.model)
     batched_B = 8 if ((world > 1 or os.environ.get("WIS_BENCH_FORCE_BATCHED")) and args.batch == 1 and not args.no_batched and not dry) else 0      # N > 1: BASELINE configs[3]'s 8 utterances per GPU measured after the headline
     max_batch = max(args.batch, 16 if extras else 1, batched_B)
+    if not args.full:       # (the handle keeps the size the other legs want, so that the timed steps run on the same handle with or without --full)
+        extras, batched_B = False, 0
     t0 = time.perf_counter()
     weights = None
     if not use_dist:
@@ -634,7 +645,7 @@ def main():
                    "ms_per_device_batch": round(1e3 * elB / kB, 3)}
 
     roofline = None
-    if rank == 0 and not args.no_roofline:
+    if rank == 0 and args.full and not args.no_roofline:
         # dominant kernel: the decoder's weight-streaming skinny GEMM (gemv_kernel): one decode step's weight stream
         ms = C.c_float(); nl = C.c_int(); nb = C.c_double()
         passes = 5
@@ -767,7 +778,7 @@ def main():
         except Exception as e:
             extra["streaming"] = {"failed": repr(e)}
 
-    if rank == 0 and (extras or args.natural_eot) and not args.no_natural_eot and not dry and args.model == "large" and args.compute_type == "float16":
+    if rank == 0 and args.full and (extras or args.natural_eot) and not args.no_natural_eot and not dry and args.model == "large" and args.compute_type == "float16":
         try:
             if weights is None:
                 weights = W.synthetic_weights(args.model, seed=1234)
@@ -776,7 +787,7 @@ def main():
             extra["natural_eot"] = {"failed": repr(e)}
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and args.full and world == 1 and not args.no_cpu_baseline:
         if weights is None:
             weights = W.synthetic_weights(args.model, seed=1234)
         try:

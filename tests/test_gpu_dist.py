@@ -34,7 +34,7 @@ def _json_line(stdout):
 
 
 def test_bench_distributed_branch_on_one_gpu_matches_the_plain_run():
-    args = ["--gpus", "1", "--steps", "6", "--warmup", "2", "--model", "base", "--beam", "5", "--no-extras", "--no-cpu-baseline"]
+    args = ["--gpus", "1", "--steps", "6", "--warmup", "2", "--model", "base", "--beam", "5", "--full", "--no-extras", "--no-cpu-baseline"]
     env = dict(os.environ, MASTER_ADDR="127.0.0.1", HSA_ENABLE_IPC_MODE_LEGACY="0", WIS_BENCH_FORCE_BATCHED="1")      # (the N > 1 line's batched leg, on the one rank there is)
     env.pop("WIS_DIST_BACKEND", None)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1",

@@ -5,11 +5,11 @@
 #   lab [M ...]     tools/bin/gemm_lab at the given row counts (default 1500 3000 12000), stamps off, weights from HBM
 #   tests <expr>    pytest -m gpu -k <expr> (quote the expression); "tests all" = the whole GPU suite
 #   smoke           __graft_entry__.smoke()
-#   bench<N> [ENV=VAL ...]   bench.py at N utterances per device batch (no extras, no CPU baseline); extra words are
+#   bench<N> [ENV=VAL ...]   bench.py --full at N utterances per device batch (roofline; no extras, no CPU baseline); extra words are
 #                   environment assignments for that run and become part of the output name
-#   eot             bench.py --natural-eot: the search that ends on EOT against the fixed-length call of the same number of passes
+#   eot             bench.py --full --natural-eot: the search that ends on EOT against the fixed-length call of the same number of passes
 #   stream          bench.py's streaming rows alone (large-v2, 30sec.flac)
-#   benchfull       the default bench.py line (what the driver runs)
+#   benchfull       the bench.py --full line (the headline and everything else it carries)
 #   prof<N> [ENV=VAL ...]   rocprofv3 --kernel-trace --stats of the eager bench at N utterances per device batch -> kernel_stats_b*.txt (+ by-grid table)
 #   frag2 [iters]   tools/bin/frag2_lab in its three flag variants (as the library / -fno-slp-vectorize / accumulators in AGPRs): the two-n-tile
 #                   skinny GEMM against the shipped kernel, bit for bit, with LDS dump + hardware ids of a failing workgroup -> frag2_*.txt
@@ -23,7 +23,7 @@ R=$GRAFT_REPO_ROOT
 run_bench() {   # $1 = batch, rest = env assignments
   local B=$1; shift
   local name="bench_b${B}"; for kv in "$@"; do name="${name}_${kv//[^A-Za-z0-9=]/}"; done
-  env "$@" timeout 600 python bench.py --steps 20 --warmup 3 --batch "$B" --no-cpu-baseline --no-extras > "$O/$name.json" 2> "$O/$name.err"
+  env "$@" timeout 600 python bench.py --full --steps 20 --warmup 3 --batch "$B" --no-cpu-baseline --no-extras > "$O/$name.json" 2> "$O/$name.err"
   python - "$O/$name.json" <<'PY'
 import json, sys
 try:
@@ -51,7 +51,7 @@ while [ $# -gt 0 ]; do
       run_bench "$B" "${envs[@]}" ;;
     eot)      # eot [ENV=VAL ...]: the natural-EOT row; extra words are environment assignments (part of the output name)
       envs=(); name="bench_eot"; while [ $# -gt 0 ] && [[ $1 == *=* ]]; do envs+=("$1"); name="${name}_${1//[^A-Za-z0-9=]/}"; shift; done
-      env "${envs[@]}" timeout 600 python bench.py --steps 20 --warmup 3 --no-cpu-baseline --no-extras --no-roofline --natural-eot > "$O/$name.json" 2> "$O/$name.err"
+      env "${envs[@]}" timeout 600 python bench.py --full --steps 20 --warmup 3 --no-cpu-baseline --no-extras --no-roofline --natural-eot > "$O/$name.json" 2> "$O/$name.err"
       grep "eot-trace" "$O/$name.err" | tail -24
       python - "$O/$name.json" <<'PY'
 import json, sys
@@ -82,10 +82,10 @@ h = ct2.create_handle(a, arena, index, 0, max_batch=8, max_beam=5)
 print(json.dumps(bench.streaming_bench(h, a, 0, os.path.join("tests", "golden", "clips", "30sec.flac"))))
 PY
       python -c "import json,sys; d=json.load(open('$O/stream.json')); print({k:v for k,v in d.items() if k!='noise_64s'})" || tail -5 "$O/stream.err" ;;
-    benchfull) timeout 900 python bench.py > "$O/bench_default.json" 2> "$O/bench_default.err"; tail -c 600 "$O/bench_default.json" ;;
+    benchfull) timeout 900 python bench.py --full > "$O/bench_default.json" 2> "$O/bench_default.err"; tail -c 600 "$O/bench_default.json" ;;
     prof[0-9]*)
       B=${step#prof}; while [ $# -gt 0 ] && [[ $1 == *=* ]]; do export "$1"; B="$B"; PSUF="${PSUF}_${1//[^A-Za-z0-9=]/}"; shift; done
-      ( cd /tmp && export TMPDIR=/tmp && WIS_NO_GRAPH=1 timeout 600 rocprofv3 --kernel-trace --stats -d "$O/prof_b$B" -o "b$B" -- python "$R/bench.py" --steps 5 --warmup 2 --batch "$B" --no-cpu-baseline --no-extras > "$O/bench_eager_b$B.log" 2>&1 )
+      ( cd /tmp && export TMPDIR=/tmp && WIS_NO_GRAPH=1 timeout 600 rocprofv3 --kernel-trace --stats -d "$O/prof_b$B" -o "b$B" -- python "$R/bench.py" --full --steps 5 --warmup 2 --batch "$B" --no-cpu-baseline --no-extras > "$O/bench_eager_b$B.log" 2>&1 )
       DB=$(find "$O/prof_b$B" -name "*.db" | head -1)
       python tools/prof_summary.py "$DB" 45 > "$O/kernel_stats_b$B$PSUF.txt" 2>&1
       python tools/prof_summary.py "$DB" 45 --by-grid > "$O/kernels_by_grid_b$B$PSUF.txt" 2>&1

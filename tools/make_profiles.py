@@ -6,7 +6,7 @@
   r03_pmc_decode.json                               HBM traffic (FETCH_SIZE x 2 + WRITE_SIZE) of the decoder kernels at 1 and 8 utterances
   r03_pmc_encoder_sq.md                             SQ counters of the encoder kernels at 8 utterances (MFMA busy, wait shares, LDS conflicts)
   r03_gemm_lab.md                                   tools/gemm_lab: the encoder GEMM loop variants incl. the 8-phase kernel and its ablations
-  r03_bench_large_beam5.json                        the default bench.py line
+  r03_bench_large_beam5.json                        the bench.py --full line
 """
 import argparse
 import json
@@ -66,7 +66,7 @@ def kernel_stats(tag):
             return "\n".join(out)
         st, gr = readable(st), (readable(gr) if gr else gr)
         out = (f"# rocprofv3 --kernel-trace --stats, round {int(RND[1:])}, Whisper large-v2 beam 5, 3.84 s clip, {what}\n\n"
-               f"Command (GPU box, `bash tools/gpu_session.sh prof{B}`): `WIS_NO_GRAPH=1 rocprofv3 --kernel-trace --stats -- python bench.py --steps 5 --warmup 2 --batch {B} --no-cpu-baseline --no-extras`\n"
+               f"Command (GPU box, `bash tools/gpu_session.sh prof{B}`): `WIS_NO_GRAPH=1 rocprofv3 --kernel-trace --stats -- python bench.py --full --steps 5 --warmup 2 --batch {B} --no-cpu-baseline --no-extras`\n"
                "(eager launches: rocprofv3 cannot follow a HIP-graph capture; 7 generate calls + the roofline tap's passes over the decoder weight stream + the one-time weight conversion kernels).\n"
                "Aggregated from the rocpd sqlite output (`kernels` view) by `tools/prof_summary.py`.  Durations of kernels in a dependent chain INCLUDE the boundary before them\n"
                "(start(k+1) = end(k) in the trace), so the column sums to the wall time of the chain.\n\n" + TEMPLATE_NOTE + "\n\n```\n" + st + "```\n")
