@@ -306,6 +306,43 @@ int wis_op_dec_cross_attn(int device, const float* q, const void* kx_f16, const 
 int wis_op_dec_cross_attn_folded(int device, const float* q_raw, const float* xres, const float* qcs, const float* qb,
                                  const void* kx_f16, const void* vt_f16, void* out_f16, int B, int R, int H, int T, int chunks);
 
+/* ---- speaker verification (replaces the reference's WavLMForXVector embedder, main.py:306-316 / do_sv 797-879): one handle = the
+ * WavLM-base-plus-sv x-vector model on one GPU.  Input: mono 16 kHz f32 PCM in host memory, already through the reference's
+ * preprocessing (sox gain + trim, the feature extractor's zero-mean / unit-variance normalisation: wis_hip/sv.py); output: the
+ * 512-float embedding (`.embeddings`, un-normalised) in host memory.  Cosine scoring against the enrolled speakers stays on the host.
+ * A handle runs one call at a time (the Python wrapper holds a lock). */
+typedef struct wis_sv wis_sv_t;
+typedef struct {
+  int32_t conv_dim;                 /* 512: every feature-encoder layer */
+  int32_t n_conv_layers;            /* 7 */
+  int32_t conv_kernel[8], conv_stride[8];     /* 10,3,3,3,3,2,2 / 5,2,2,2,2,2,2 */
+  int32_t hidden_size, n_heads, n_layers, intermediate_size;      /* 768, 12, 12, 3072 */
+  int32_t num_conv_pos_embeddings, num_conv_pos_embedding_groups; /* 128, 16 */
+  int32_t num_buckets, max_bucket_distance;                       /* 320, 800 */
+  int32_t n_tdnn;                   /* 5 */
+  int32_t tdnn_dim[8], tdnn_kernel[8], tdnn_dilation[8];          /* 512,512,512,512,1500 / 5,3,3,1,1 / 1,2,3,1,1 */
+  int32_t xvector_output_dim;       /* 512 */
+  int64_t max_samples;              /* longest input a call may pass; buffers are sized for it at creation (0 => 160000 = 10 s) */
+} wis_sv_config_t;
+/* tensors: Hugging Face state-dict names of WavLMForXVector ("wavlm.encoder.layers.0.attention.q_proj.weight", "tdnn.0.kernel.weight",
+ * "layer_weights", ...), with two layout conventions the Python loader applies: the feature-encoder conv weights are stored
+ * [out][k][in] (the order the channels-last GEMM reads its im2col rows in), and the positional conv's weight norm is folded into
+ * "wavlm.encoder.pos_conv_embed.conv.weight" as [out][k][in / groups].  Any other architecture: WIS_E_UNSUPPORTED. */
+int    wis_sv_create(const wis_sv_config_t* cfg, const void* arena, size_t arena_bytes, int arena_on_device,
+                     const wis_tensor_t* tensors, int n_tensors, int device, wis_sv_t** out);
+void   wis_sv_destroy(wis_sv_t* sv);
+size_t wis_sv_device_bytes(const wis_sv_t* sv);
+/* emb: [512] f32.  n > max_samples: WIS_E_STATE; audio too short to leave two frames after the TDNN layers: WIS_E_ARG. */
+int    wis_sv_embed(wis_sv_t* sv, const float* pcm, int64_t n, float* emb);
+/* host only (no device needed): the relative-position buckets of HF WavLMAttention._relative_positions_bucket for the n distances
+ * first, first + 1, ... (key position - query position) -> out[n] */
+int    wis_sv_rel_buckets(int num_buckets, int max_distance, int first, int n, int32_t* out);
+/* parity tap (tests): runs the forward pass on `pcm` and copies out, as f32 row-major [rows][cols]:
+ * tap 0 = feature-encoder output [T][512]; tap 1 = hidden state `layer` [T][768] (0 = encoder input after the positional conv and
+ * LayerNorm, l = output of layer l, HF hidden_states[l]); tap 2 = output of the last TDNN layer after its ReLU [T - 14][1500]. */
+int    wis_debug_sv_taps(wis_sv_t* sv, const float* pcm, int64_t n, int tap, int layer, float* out, int64_t cap_floats,
+                         int32_t* rows, int32_t* cols);
+
 #ifdef __cplusplus
 }
 #endif

@@ -2184,3 +2184,6 @@ int wis_op_dec_cross_attn_folded(int device, const float* q_raw, const float* xr
 }
 
 }  // extern "C"
+
+// speaker verification (wis_sv_*): its kernels and driver, in this translation unit
+#include "sv.hip"

@@ -51,6 +51,14 @@ class Timing(C.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_}
 
 
+class SvConfig(C.Structure):
+    _fields_ = [("conv_dim", C.c_int32), ("n_conv_layers", C.c_int32), ("conv_kernel", C.c_int32 * 8), ("conv_stride", C.c_int32 * 8),
+                ("hidden_size", C.c_int32), ("n_heads", C.c_int32), ("n_layers", C.c_int32), ("intermediate_size", C.c_int32),
+                ("num_conv_pos_embeddings", C.c_int32), ("num_conv_pos_embedding_groups", C.c_int32), ("num_buckets", C.c_int32),
+                ("max_bucket_distance", C.c_int32), ("n_tdnn", C.c_int32), ("tdnn_dim", C.c_int32 * 8), ("tdnn_kernel", C.c_int32 * 8),
+                ("tdnn_dilation", C.c_int32 * 8), ("xvector_output_dim", C.c_int32), ("max_samples", C.c_int64)]
+
+
 # every symbol include/wis_hip.h declares: (name, restype, argtypes)
 _vp, _i, _sz, _i64 = C.c_void_p, C.c_int, C.c_size_t, C.c_int64
 _fp = C.POINTER(C.c_float)
@@ -104,6 +112,12 @@ SYMBOLS = [
     ("wis_op_dec_self_attn", _i, [_i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i]),
     ("wis_op_dec_cross_attn", _i, [_i, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i]),
     ("wis_op_dec_cross_attn_folded", _i, [_i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i]),
+    ("wis_sv_create", _i, [C.POINTER(SvConfig), _vp, _sz, _i, C.POINTER(Tensor), _i, _i, C.POINTER(_vp)]),
+    ("wis_sv_destroy", None, [_vp]),
+    ("wis_sv_device_bytes", _sz, [_vp]),
+    ("wis_sv_embed", _i, [_vp, _vp, _i64, _fp]),
+    ("wis_sv_rel_buckets", _i, [_i, _i, _i, _i, C.POINTER(C.c_int32)]),
+    ("wis_debug_sv_taps", _i, [_vp, _vp, _i64, _i, _i, _fp, _i64, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
 ]
 
 _lib = None

@@ -11,7 +11,10 @@ audio"}`).  Differences, all deliberate:
     its single worker inside `do_whisper` (main.py:1205, 1338);
   * audio containers: WAV, FLAC and raw PCM are decoded natively (csrc/audio_io.c); other codecs need PyAV, which the
     reference uses (`audio_to_wav`, main.py:108-120) and this image does not have -> HTTP 400 "Invalid audio";
-  * speaker verification (`voice_auth`) is a different model family and out of scope -> HTTP 400.
+  * speaker verification (`voice_auth=true`, main.py:1324-1360) is served when `support_sv` is set (wis_hip/sv.py, the WavLM x-vector
+    embedder in csrc/sv.hip): it runs on the thread pool before Whisper, answers 406 "Unauthorized voice" when no enrolled speaker
+    reaches `sv_threshold`, else adds `voice_auth` and `speaker_status` to the (stats) JSON.  Without `support_sv` (the default) a
+    `voice_auth` request is answered HTTP 400, where the reference would fail inside `do_sv`.
 WebRTC (`/api/rtc/asr`), TTS, nginx auth and the static sites are not re-hosted (out of scope).
 
     python -m wis_hip.server --host 0.0.0.0 --port 19000        (or: uvicorn --factory wis_hip.server:create_app ...)
@@ -28,7 +31,7 @@ from email.policy import HTTP
 
 from fastapi import FastAPI, Request
 from fastapi.middleware.cors import CORSMiddleware
-from fastapi.responses import JSONResponse
+from fastapi.responses import JSONResponse, PlainTextResponse
 
 from .settings import get_api_settings
 from .whisper import InvalidAudio, WhisperModels, check_language, do_whisper
@@ -106,9 +109,12 @@ def _as_bool(v, default):
     return str(v).strip().lower() in ("1", "true", "yes", "on")
 
 
-def create_app(models=None, settings=None, max_workers=None):
+def create_app(models=None, settings=None, max_workers=None, sv=None):
+    """sv: the speaker verifier (an object with `embed(pcm)`, e.g. wis_hip.sv.SpeakerVerifier); None = created on first use from
+    `sv_model_path` when `support_sv` is set"""
     s = settings or (models.settings if models is not None else get_api_settings())
-    state = {"models": models}
+    state = {"models": models, "sv": sv}
+    sv_lock = __import__("threading").Lock()
     # enough threads that a full device batch per GPU replica can be waiting in the micro-batcher at once
     pool = ThreadPoolExecutor(max_workers=max_workers or 8 * max(1, s.max_batch), thread_name_prefix="wis-req")
 
@@ -156,6 +162,18 @@ def create_app(models=None, settings=None, max_workers=None):
     def bad(msg):
         return JSONResponse(content={"error": msg}, status_code=400)
 
+    def get_sv():
+        with sv_lock:
+            if state["sv"] is None:
+                from .sv import SpeakerVerifier
+                state["sv"] = SpeakerVerifier(s.sv_model_path)
+            return state["sv"]
+
+    async def run_sv(audio_file):
+        from .sv import do_sv
+        loop = asyncio.get_running_loop()
+        return await loop.run_in_executor(pool, lambda: do_sv(audio_file, s.sv_threshold, get_sv(), s.sv_speakers_dir))
+
     @app.get("/api/ping")
     async def ping():
         return JSONResponse(content={"message": "pong"})
@@ -192,8 +210,8 @@ def create_app(models=None, settings=None, max_workers=None):
         save_audio, stats, voice_auth = _as_bool(q.get("save_audio"), False), _as_bool(q.get("stats"), False), _as_bool(q.get("voice_auth"), False)
         if p["force_language"] and not check_language(p["force_language"]):
             return bad("Invalid force_language")
-        if voice_auth:
-            return bad("voice_auth (speaker verification) is not part of this build")
+        if voice_auth and not s.support_sv:
+            return bad("voice_auth (speaker verification) is disabled (support_sv)")
         h = request.headers
         sample_rate, bits, channel = h.get("x-audio-sample-rate", "").lower(), h.get("x-audio-bits", "").lower(), h.get("x-audio-channel", "").lower()
         codec = h.get("x-audio-codec", "").lower()
@@ -213,6 +231,18 @@ def create_app(models=None, settings=None, max_workers=None):
                 os.makedirs(os.path.dirname(path) or ".", exist_ok=True)
                 with open(path, "wb") as f:
                     f.write(audio_file.getbuffer())
+            sv_results, speaker_status = None, None
+            if voice_auth:       # main.py:1324-1336: before Whisper; stats forced on
+                stats = True
+                try:
+                    sv_results = await run_sv(audio_file)
+                except ValueError as e:     # undecodable audio -> 400 "Invalid audio" below
+                    raise InvalidAudio(str(e)) from e
+                if not sv_results:
+                    logger.debug("WILLOW: Unknown or unauthorized voice - returning HTTP 406")
+                    return PlainTextResponse("Unauthorized voice", status_code=406)
+                audio_file.seek(0)
+                speaker_status = f"I heard {list(sv_results.keys())[0]} say:"
             res = await run_whisper(audio_file, p)
         except InvalidAudio as e:
             logger.debug("WILLOW: %s - returning HTTP 400", e)
@@ -226,6 +256,9 @@ def create_app(models=None, settings=None, max_workers=None):
             out = {"language": language, "text": text}
         if translation:
             out["translation"] = translation
+        if voice_auth:
+            out["voice_auth"] = sv_results
+            out["speaker_status"] = speaker_status
         return JSONResponse(content=out)
 
     app.state.wis = state

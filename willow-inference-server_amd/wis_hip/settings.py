@@ -74,6 +74,11 @@ class APISettings:
     # measurement convention for seeded synthetic weights, which never emit EOT: decode exactly this many tokens
     # (EOT masked until then, then forced).  0 = off: the product default, natural termination
     fixed_new_tokens: int = 0
+    # --- speaker verification (`voice_auth`, support_sv): not reference fields, the reference hard-codes both paths (main.py:308-312,
+    # 839).  The model directory is a Hugging Face WavLMForXVector checkpoint (or "synthetic:wavlm-base-plus-sv[:SEED]"); the speakers
+    # directory holds one NAME.npy embedding per enrolled speaker (python -m wis_hip.sv enroll NAME AUDIO)
+    sv_model_path: str = "./models/microsoft-wavlm-base-plus-sv"
+    sv_speakers_dir: str = "speakers/voice_auth"
     # "float16" or "int8_float16" (the reference picks int8_float16 on GPUs, main.py:242: here it quantises the decoder weights)
     compute_type: str = "float16"
 
