@@ -148,6 +148,16 @@ typedef struct {
   int32_t queue_depth;      /* searches that end on EOT: decode steps kept enqueued beyond the last one the host has seen
                                complete (the host polls a progress record the device writes to mapped host memory after every
                                step - no stream round trip); 0 => 2: one step running, one queued, over-run <= 1 step */
+  int32_t timestamps;       /* 1: Whisper's timestamp rules every step (openai-whisper ApplyTimestampRules, what CTranslate2 applies
+                               when the prompt lacks <|notimestamps|>): no <|notimestamps|>, timestamps in pairs except before EOT,
+                               never decreasing, the first step a timestamp, text masked when the timestamps' total probability beats
+                               every text token.  Order: suppress_default, suppress_blank, these rules, fixed_new_tokens (EOT masked
+                               before the rules' decision; its forced EOT overrides them) - the order is restated, not pinned against
+                               CTranslate2.  0: off (today's search).  wis_generate / wis_debug_search; drafts answer WIS_E_UNSUPPORTED */
+  int32_t max_initial_timestamp_index;   /* timestamps: the first timestamp is at most <|0.00|> + this (CTranslate2 default 50);
+                                            < 0: no cap */
+  int32_t no_speech_prob;   /* 1: keep P(<|nospeech|>) of the softmax over the raw logits at <|startoftranscript|> per utterance
+                               (wis_last_no_speech_prob) */
 } wis_gen_opts_t;
 
 /* out_ids: [B][max_new] (max_new = resolved max_new_tokens), out_len: [B], out_score: [B]
@@ -186,6 +196,11 @@ int wis_generate_draft_beam(wis_model_t* m, const float* input, const int32_t* p
 /* The trajectory of utterance b of the LAST generate call on this handle (any of the three forms; beam_size k of that call): tok / org
  * [cap_steps][k], *n_steps = steps recorded (the step that ended the search leaves no live set).  Synchronises the handle's stream. */
 int wis_last_trajectory(wis_model_t* m, int b, int32_t* tok, int32_t* org, int cap_steps, int32_t* n_steps);
+
+/* no_speech_prob of the first B utterances of the LAST wis_generate on this handle, which must have set opts->no_speech_prob
+ * (otherwise WIS_E_STATE): softmax(logits at the <|startoftranscript|> prompt position)[cfg.no_speech] over the whole vocabulary,
+ * no logits processor applied (openai-whisper probs_at_sot).  Synchronises the handle's stream. */
+int wis_last_no_speech_prob(wis_model_t* m, int B, float* out);
 
 /* ---- a14: language detection (replaces whisper_model.detect_language(features),
  * main.py:637-643): probabilities over cfg.lang_ids, [B][n_lang]. */

@@ -2485,11 +2485,15 @@ __device__ __forceinline__ bool better(float av, int ai, float bv, int bi) { ret
 __device__ __forceinline__ bool better_b(float av, int ai, float bv, int bi) { return (av > bv) | ((av == bv) & (ai < bi)); }
 __device__ __forceinline__ void take_better(float& v, int& i, float ov, int oi) { const bool t = better_b(ov, oi, v, i); v = t ? ov : v; i = t ? oi : i; }
 
+// TS: the timestamp form - three more [lo, hi) ranges of the row are masked, as ts_rules_kernel left them for the row in ts_desc
+// (the plain form takes ts_desc = nullptr and compiles to what it was before the template parameter existed)
+template <bool TS>
 __global__ __launch_bounds__(256) void logit_stats_kernel(const float* __restrict__ logits, const float* __restrict__ bias_all,
                                                           const float* __restrict__ bias_begin, const int* __restrict__ step_u,
                                                           float* __restrict__ st_max, float* __restrict__ st_sum,
                                                           float* __restrict__ st_val, int* __restrict__ st_idx, SampleCfg cfg,
-                                                          int lr_b, int lr_j, int lr_off, unsigned long long* prof, const int* __restrict__ rowmap) {
+                                                          int lr_b, int lr_j, int lr_off, unsigned long long* prof, const int* __restrict__ rowmap,
+                                                          const int* __restrict__ ts_desc) {
   constexpr int PT = 16;   // values per lane: supports n_vocab <= 64 * 64 * 16
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int sc = blockIdx.x * 4 + wave, m = blockIdx.y, b = m / cfg.beam;
@@ -2511,6 +2515,11 @@ __global__ __launch_bounds__(256) void logit_stats_kernel(const float* __restric
   // by select - a guarded `if (nidx < hi) { load }` per value compiled into sixteen branches with a wait each: 15k cycles)
   float vals[PT]; u64 keys[PT];
   float lv[PT], la[PT], lb[PT];
+  int r0l = 0, r0h = 0, r1l = 0, r1h = 0, r2l = 0, r2h = 0;
+  if constexpr (TS) {
+    const int* dsc = ts_desc + m * TS_DESC_INTS;
+    r0l = dsc[0]; r0h = dsc[1]; r1l = dsc[2]; r1h = dsc[3]; r2l = dsc[4]; r2h = dsc[5];
+  }
 #pragma unroll
   for (int i = 0; i < PT; ++i) {
     const int nidx = lo + lane + 64 * i;
@@ -2523,7 +2532,8 @@ __global__ __launch_bounds__(256) void logit_stats_kernel(const float* __restric
     const int nidx = lo + lane + 64 * i;
     float v = lv[i] + la[i];
     v = first ? v + lb[i] : v;
-    const bool dead = (nidx >= hi) | (mask_eot & (nidx == cfg.eot)) | (force_eot & (nidx != cfg.eot));
+    bool dead = (nidx >= hi) | (mask_eot & (nidx == cfg.eot)) | (force_eot & (nidx != cfg.eot));
+    if constexpr (TS) dead = dead | ((nidx >= r0l) & (nidx < r0h)) | ((nidx >= r1l) & (nidx < r1h)) | ((nidx >= r2l) & (nidx < r2h));
     v = dead ? -INFINITY : v;
     vals[i] = v; keys[i] = nidx < hi ? sel_key(v, nidx) : 0ull; mx = fmaxf(mx, v);
   }
@@ -2562,10 +2572,129 @@ __global__ __launch_bounds__(256) void logit_stats_kernel(const float* __restric
 }
 int launch_logit_stats(hipStream_t st, const float* logits, const float* bias_all, const float* bias_begin, const int* step_u,
                        float* st_max, float* st_sum, float* st_val, int* st_idx, int B, const SampleCfg& cfg, int lr_b, int lr_j, int lr_off,
-                       unsigned long long* prof, const int* rowmap) {
+                       unsigned long long* prof, const int* rowmap, const int* ts_desc) {
   if (cdiv(cfg.n_vocab, STAT_SUB) > 16 * 64) { set_error("logit_stats: vocab too large"); return WIS_E_UNSUPPORTED; }
-  hipLaunchKernelGGL(logit_stats_kernel, dim3(STAT_SUB / 4, B * cfg.beam), dim3(256), 0, st, logits, bias_all, bias_begin, step_u,
-                     st_max, st_sum, st_val, st_idx, cfg, lr_b, lr_j, lr_off, prof, rowmap);
+  if (ts_desc) hipLaunchKernelGGL(logit_stats_kernel<true>, dim3(STAT_SUB / 4, B * cfg.beam), dim3(256), 0, st, logits, bias_all, bias_begin, step_u,
+                                  st_max, st_sum, st_val, st_idx, cfg, lr_b, lr_j, lr_off, prof, rowmap, ts_desc);
+  else hipLaunchKernelGGL(logit_stats_kernel<false>, dim3(STAT_SUB / 4, B * cfg.beam), dim3(256), 0, st, logits, bias_all, bias_begin, step_u,
+                          st_max, st_sum, st_val, st_idx, cfg, lr_b, lr_j, lr_off, prof, rowmap, nullptr);
+  return WIS_OK;
+}
+
+// =======================================================================================
+// Whisper's timestamp rules (openai-whisper ApplyTimestampRules, restated by CTranslate2 4.1.0 for prompts without <|notimestamps|>),
+// the pre-pass of the timestamp form of the sampling tail.  grid B*beam (one workgroup per live row), block 256.  The row's generated
+// history is bs.alive[m][0 .. step_u[b]); every rule masks a RANGE of ids, so what the pass leaves for logit_stats_kernel<true> is three
+// [lo, hi) ranges per row (ts_desc, TS_DESC_INTS ints: ranges, then the decision flag and the step it was taken at):
+//   range 0: <|notimestamps|> - or [0, tb) once the decision below masks the text, or at the first step
+//   range 1: last token a timestamp: [tb, V) after a pair (or as the only token), else [0, eot) (text, EOT stays allowed);
+//            first step: (tb + max_initial_timestamp_index, V)
+//   range 2: timestamps may not decrease: [tb, t_last), t_last = the last timestamp when it opened a segment, else the last + 1
+// Decision: over the row after bias_all / bias_begin / mask_eot and ranges 0-2, logsumexp(allowed timestamp logits) > max(allowed text
+// logits) masks the text (the log-softmax normaliser is common to both sides; an all-masked side is -inf; strict).  force_eot (the
+// measurement convention's last step) overrides every rule: nothing is masked here and logit_stats_kernel keeps EOT alone.
+__device__ __forceinline__ float block_max_256(float v, float* red) {
+  v = wave_max(v);
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  __syncthreads();
+  if (lane == 0) red[wave] = v;
+  __syncthreads();
+  return fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
+}
+__device__ __forceinline__ float block_sum_256(float v, float* red) {
+  v = wave_sum(v);
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  __syncthreads();
+  if (lane == 0) red[wave] = v;
+  __syncthreads();
+  return (red[0] + red[1]) + (red[2] + red[3]);
+}
+__global__ __launch_bounds__(256) void ts_rules_kernel(const float* __restrict__ logits, const float* __restrict__ bias_all,
+                                                       const float* __restrict__ bias_begin, const int* __restrict__ step_u,
+                                                       const int* __restrict__ alive, SampleCfg cfg, int no_ts, int max_init,
+                                                       int lr_b, int lr_j, int lr_off, int* __restrict__ ts_desc) {
+  __shared__ float red[4];
+  const int tid = threadIdx.x, m = blockIdx.x, b = m / cfg.beam, jb = m - b * cfg.beam;
+  const int V = cfg.n_vocab, tb = no_ts + 1;
+  int step = step_u[b];
+  step = step < cfg.max_new ? step : cfg.max_new;
+  const bool force_eot = cfg.fixed_new > 0 && step >= cfg.fixed_new;
+  int* dsc = ts_desc + m * TS_DESC_INTS;
+  if (force_eot) {
+    if (tid < TS_DESC_INTS) dsc[tid] = (tid == 7) ? step : 0;
+    return;
+  }
+  const bool first = (step == 0) && cfg.suppress_blank;
+  const bool mask_eot = cfg.fixed_new > 0 && step < cfg.fixed_new;
+  int r0l = no_ts, r0h = no_ts + 1, r1l = 0, r1h = 0, r2l = 0, r2h = 0;
+  if (step == 0) {
+    r0l = 0; r0h = tb;
+    if (max_init >= 0 && tb + max_init + 1 < V) { r1l = tb + max_init + 1; r1h = V; }
+  } else {
+    // history: the position of the last timestamp (block maximum of the positions that hold one; max_new <= 256 = one token per thread)
+    const int* hist = alive + (size_t)m * cfg.max_new;
+    const int tk = tid < step ? hist[tid] : -1;
+    const float lastpos = block_max_256(tk >= tb ? (float)tid : -1.f, red);
+    const int last = hist[step - 1];
+    const bool last_ts = last >= tb;
+    const bool pen_ts = step < 2 || hist[step - 2] >= tb;
+    if (last_ts) { if (pen_ts) { r1l = tb; r1h = V; } else { r1l = 0; r1h = cfg.eot; } }
+    if (lastpos >= 0.f) {
+      const int t_ts = hist[(int)lastpos];
+      const int t_last = (last_ts && !pen_ts) ? t_ts : t_ts + 1;
+      r2l = tb; r2h = t_last;
+    }
+  }
+  // the decision, over the row as every earlier processor left it
+  const float* row = logits + (size_t)(b * lr_b + jb * lr_j + lr_off) * cfg.n_vocab_pad;
+  auto value = [&](int i) -> float {
+    float v = row[i] + (bias_all ? bias_all[i] : 0.f);
+    v = first ? v + bias_begin[i] : v;
+    const bool dead = (mask_eot & (i == cfg.eot)) | ((i >= r0l) & (i < r0h)) | ((i >= r1l) & (i < r1h)) | ((i >= r2l) & (i < r2h));
+    return dead ? -INFINITY : v;
+  };
+  float tmx = -INFINITY;
+  for (int i = tid; i < tb; i += 256) tmx = fmaxf(tmx, value(i));
+  float smx = -INFINITY;
+  for (int i = tb + tid; i < V; i += 256) smx = fmaxf(smx, value(i));
+  tmx = block_max_256(tmx, red);
+  smx = block_max_256(smx, red);
+  float ssum = 0.f;
+  if (smx > -INFINITY)
+    for (int i = tb + tid; i < V; i += 256) ssum += expf(value(i) - smx);
+  ssum = block_sum_256(ssum, red);
+  const float lse = smx > -INFINITY ? smx + logf(ssum) : -INFINITY;
+  const bool ts_wins = lse > tmx;
+  if (ts_wins) { r0l = 0; r0h = tb; }
+  if (tid == 0) {
+    dsc[0] = r0l; dsc[1] = r0h; dsc[2] = r1l; dsc[3] = r1h; dsc[4] = r2l; dsc[5] = r2h; dsc[6] = ts_wins ? 1 : 0; dsc[7] = step;
+  }
+}
+int launch_ts_rules(hipStream_t st, const float* logits, const float* bias_all, const float* bias_begin, const BeamState& bs, int B,
+                    const SampleCfg& cfg, int no_ts, int max_init, int lr_b, int lr_j, int lr_off, int* ts_desc) {
+  if (cfg.max_new > 256 || no_ts + 1 >= cfg.n_vocab) { set_error("ts_rules: config out of range"); return WIS_E_UNSUPPORTED; }
+  hipLaunchKernelGGL(ts_rules_kernel, dim3(B * cfg.beam), dim3(256), 0, st, logits, bias_all, bias_begin, bs.step_u, bs.alive, cfg, no_ts, max_init,
+                     lr_b, lr_j, lr_off, ts_desc);
+  return WIS_OK;
+}
+
+// no_speech_prob (openai-whisper probs_at_sot, CTranslate2 return_no_speech_prob): softmax over the full vocabulary of the raw logits of
+// the decoder row that read <|startoftranscript|>, at <|nospeech|>.  grid B, block 256; row of utterance b = logits + (b * rs + r0) * ld
+__global__ __launch_bounds__(256) void no_speech_kernel(const float* __restrict__ logits, int ld, int rs, int r0, int V, int ns, float* __restrict__ out) {
+  __shared__ float red[4];
+  const int b = blockIdx.x, tid = threadIdx.x;
+  const float* row = logits + (size_t)(b * rs + r0) * ld;
+  float mx = -INFINITY;
+  for (int i = tid; i < V; i += 256) mx = fmaxf(mx, row[i]);
+  mx = block_max_256(mx, red);
+  float s = 0.f;
+  for (int i = tid; i < V; i += 256) s += expf(row[i] - mx);
+  s = block_sum_256(s, red);
+  if (tid == 0) out[b] = expf(row[ns] - mx) / s;
+}
+int launch_no_speech(hipStream_t st, const float* logits, int ld, int B, int rs, int r0, int V, int ns, float* out) {
+  if (ns < 0 || ns >= V) { set_error("no_speech: token %d outside the vocabulary", ns); return WIS_E_ARG; }
+  hipLaunchKernelGGL(no_speech_kernel, dim3(B), dim3(256), 0, st, logits, ld, rs, r0, V, ns, out);
   return WIS_OK;
 }
 

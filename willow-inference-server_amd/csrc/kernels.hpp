@@ -151,7 +151,17 @@ constexpr int STAT_SUB = 64;      // sub-chunks per logits row (one wave each): 
 int launch_logit_stats(hipStream_t st, const float* logits, const float* bias_all, const float* bias_begin, const int* step_u,
                        float* st_max, float* st_sum, float* st_val, int* st_idx, int B, const SampleCfg& cfg,
                        int lr_b, int lr_j, int lr_off, unsigned long long* prof = nullptr,    // logits row of (b, j) = b*lr_b + j*lr_j + lr_off
-                       const int* rowmap = nullptr);      // ... or b*lr_b + rowmap[j]*lr_j + lr_off (device table: draft verification of a beam search)
+                       const int* rowmap = nullptr,       // ... or b*lr_b + rowmap[j]*lr_j + lr_off (device table: draft verification of a beam search)
+                       const int* ts_desc = nullptr);     // timestamp form: the ranges launch_ts_rules left per row are masked too
+// Whisper's timestamp rules for prompts without <|notimestamps|> (dec_kernels.hip ts_rules_kernel): per live row, the masked ranges
+// of the step (+ the decision flag, the step) -> ts_desc [B*beam][TS_DESC_INTS]; rows as launch_logit_stats reads them.
+// max_init < 0: no cap on the first timestamp
+constexpr int TS_DESC_INTS = 8;
+struct BeamState;
+int launch_ts_rules(hipStream_t st, const float* logits, const float* bias_all, const float* bias_begin, const BeamState& bs, int B,
+                    const SampleCfg& cfg, int no_ts, int max_init, int lr_b, int lr_j, int lr_off, int* ts_desc);
+// probability of <|nospeech|> under the full-vocabulary softmax of each utterance's <|startoftranscript|> row (b * rs + r0)
+int launch_no_speech(hipStream_t st, const float* logits, int ld, int B, int rs, int r0, int V, int ns, float* out);
 struct BeamState {
   int* step_u;      // [B] generated-token count so far
   int* done;        // [B]

@@ -115,6 +115,7 @@ struct DecLayerW {
 
 struct GraphKey {
   int B, beam, P, max_new, fixed_new, suppress_blank, suppress_default, early_exit, spin, sa_nb; float lp, patience;
+  int timestamps, max_init;      // the timestamp form of the step (ts_rules_kernel ahead of logit_stats_kernel<true>) and its first-timestamp cap
   bool operator<(const GraphKey& o) const { return memcmp(this, &o, sizeof(GraphKey)) < 0; }
 };
 
@@ -164,6 +165,9 @@ struct wis_model {
   RowMeta rm; BeamState bs;
   RowMeta rm_win;               // row metadata of a draft-verification window (wis_generate_draft_beam): the search's own rows (rm, written by beam_step_kernel) stay untouched
   float *st_max, *st_sum, *st_val; int* st_idx;
+  int* ts_desc = nullptr;       // timestamp rules: masked ranges per live row [MAX_ROWS][TS_DESC_INTS] (ts_rules_kernel -> logit_stats_kernel<true>)
+  float* d_nsp = nullptr;       // no_speech_prob per utterance of the last wis_generate that asked for it
+  int nsp_B = 0;                // ... its batch size; 0: the last call did not ask (wis_last_no_speech_prob answers WIS_E_STATE)
   float* d_in; int64_t* d_nsamp; float* d_probs;
   int* vstep = nullptr; int* pick_tok = nullptr; float* pick_lp = nullptr;      // wis_generate_draft: per-row step index, picked token / log-probability of the teacher-forced rows
   int* d_draft = nullptr; int* d_anc = nullptr; int* d_vstate = nullptr; int* d_base = nullptr;        // wis_generate_draft_beam: the draft trajectory [256][MAX_R][2], the window rows' ancestor slots [MAX_ROWS][32], {steps verified}
@@ -525,6 +529,7 @@ int alloc_buffers(wis_model* m) {
   WIS_RET(dalloc(m, &m->bs.out_ids, (size_t)Bm * max_new)); WIS_RET(dalloc(m, &m->bs.out_len, Bm)); WIS_RET(dalloc(m, &m->bs.out_score, Bm));
   WIS_RET(dalloc(m, &m->st_max, (size_t)MAX_ROWS * STAT_SUB)); WIS_RET(dalloc(m, &m->st_sum, (size_t)MAX_ROWS * STAT_SUB));
   WIS_RET(dalloc(m, &m->st_val, (size_t)MAX_ROWS * STAT_SUB * MAX_CAND)); WIS_RET(dalloc(m, &m->st_idx, (size_t)MAX_ROWS * STAT_SUB * MAX_CAND));
+  WIS_RET(dalloc(m, &m->ts_desc, (size_t)MAX_ROWS * TS_DESC_INTS)); WIS_RET(dalloc(m, &m->d_nsp, (size_t)MAX_ROWS));
   WIS_RET(dalloc(m, &m->d_in, (size_t)Bm * WIS_N_SAMPLES));
   WIS_RET(dalloc(m, &m->d_nsamp, Bm));
   WIS_RET(dalloc(m, &m->lm_logspec, (size_t)Bm * WIS_N_MELS * WIS_N_FRAMES));
@@ -1120,6 +1125,7 @@ static int generate_impl(wis_model_t* m, const float* input, int B, const int32_
                  const int32_t* draft = nullptr, int n_draft = 0, int* accepted = nullptr, const int32_t* draft_org = nullptr) {
   *retry = false;
   if (accepted) *accepted = 0;
+  m->nsp_B = 0;
   WIS_HIP_CHECK(hipSetDevice(m->device));
   SpinClaim claim(m, B);
   const wis_config_t& c = m->cfg;
@@ -1147,6 +1153,16 @@ static int generate_impl(wis_model_t* m, const float* input, int B, const int32_
   const bool beam_draft = drafting && draft_org != nullptr;
   if (drafting && B != 1) { set_error("wis_generate_draft: one utterance per call (got B = %d)", B); return WIS_E_UNSUPPORTED; }
   if (drafting && !beam_draft && beam != 1) { set_error("wis_generate_draft: beam_size 1 (a beam search is drafted by its trajectory: wis_generate_draft_beam)"); return WIS_E_UNSUPPORTED; }
+  // Whisper's timestamp rules (prompts without <|notimestamps|>): a pre-pass ahead of the sampling statistics of every step
+  const bool ts = o->timestamps != 0;
+  const int ts_max_init = o->max_initial_timestamp_index < 0 ? -1 : o->max_initial_timestamp_index;
+  if (ts && draft != nullptr) { set_error("timestamps: not available for drafted decodes (wis_generate_draft / wis_generate_draft_beam)"); return WIS_E_UNSUPPORTED; }
+  int sot_row = -1;      // no_speech_prob: the prompt row that reads <|startoftranscript|> (the same in every utterance of the batch)
+  if (o->no_speech_prob && !drafting) {
+    for (int i = 0; i < P; ++i) if (prompt[i] == c.sot) { sot_row = i; break; }
+    for (int b = 1; b < B && sot_row >= 0; ++b) if (prompt[b * P + sot_row] != c.sot) sot_row = -1;
+    if (sot_row < 0) { set_error("no_speech_prob: the prompts hold no common <|startoftranscript|> position"); return WIS_E_ARG; }
+  }
   if (beam_draft && (beam < 2 || n_draft > 256)) { set_error("wis_generate_draft_beam: beam_size >= 2 and at most 256 draft steps (got %d, %d)", beam, n_draft); return WIS_E_ARG; }
   if (drafting) for (int i = 0; i < n_draft * (beam_draft ? beam : 1); ++i) if (draft[i] < 0 || draft[i] >= c.n_vocab) { set_error("draft token %d out of range", draft[i]); return WIS_E_ARG; }
   if (beam_draft) for (int i = 0; i < n_draft * beam; ++i) if (draft_org[i] < 0 || draft_org[i] >= beam) { set_error("draft origin %d outside [0, beam_size)", draft_org[i]); return WIS_E_ARG; }
@@ -1200,7 +1216,11 @@ static int generate_impl(wis_model_t* m, const float* input, int B, const int32_
   std::vector<int> spec_gen; float spec_cum = 0.f; int spec_len = 0;
   if (!drafting) {
     WIS_RET(dec_forward(m, B * P, P, B, true, beam, 0));
-    WIS_RET(launch_logit_stats(st, m->logits, bias_all, m->bias_begin, m->bs.step_u, m->st_max, m->st_sum, m->st_val, m->st_idx, B, sc, P, 0, P - 1, WIS_TAPS ? m->d_prof + (size_t)m->cfg.n_dec_layers * 8 * 16 + 16 : nullptr));
+    // every prompt row has its logits after this pass: the <|startoftranscript|> row's are what no_speech_prob reads (raw, no processors)
+    if (sot_row >= 0) WIS_RET(launch_no_speech(st, m->logits, m->n_vocab_pad, B, P, sot_row, c.n_vocab, c.no_speech, m->d_nsp));
+    if (ts) WIS_RET(launch_ts_rules(st, m->logits, bias_all, m->bias_begin, m->bs, B, sc, c.no_timestamps, ts_max_init, P, 0, P - 1, m->ts_desc));
+    WIS_RET(launch_logit_stats(st, m->logits, bias_all, m->bias_begin, m->bs.step_u, m->st_max, m->st_sum, m->st_val, m->st_idx, B, sc, P, 0, P - 1, WIS_TAPS ? m->d_prof + (size_t)m->cfg.n_dec_layers * 8 * 16 + 16 : nullptr,
+                               nullptr, ts ? m->ts_desc : nullptr));
     WIS_RET(launch_beam_step(st, m->st_max, m->st_sum, m->st_val, m->st_idx, m->bs, m->rm, B, P, ctx, sc, WIS_TAPS ? m->d_prof + (size_t)m->cfg.n_dec_layers * 8 * 16 : nullptr));
     WIS_RET(launch_kv_reorder(st, m->kc_all, m->vc_all, m->kv_layer_stride, c.n_dec_layers, m->bs, B, beam, P, ctx, c.d_model));
   } else if (beam_draft) {
@@ -1372,7 +1392,9 @@ static int generate_impl(wis_model_t* m, const float* input, int B, const int32_
 
   auto one_step = [&]() -> int {
     WIS_RET(dec_forward(m, Mrows, beam, B, true, beam, 1));
-    WIS_RET(launch_logit_stats(st, m->logits, bias_all, m->bias_begin, m->bs.step_u, m->st_max, m->st_sum, m->st_val, m->st_idx, B, sc, beam, 1, 0, WIS_TAPS ? m->d_prof + (size_t)m->cfg.n_dec_layers * 8 * 16 + 16 : nullptr));
+    if (ts) WIS_RET(launch_ts_rules(st, m->logits, bias_all, m->bias_begin, m->bs, B, sc, c.no_timestamps, ts_max_init, beam, 1, 0, m->ts_desc));
+    WIS_RET(launch_logit_stats(st, m->logits, bias_all, m->bias_begin, m->bs.step_u, m->st_max, m->st_sum, m->st_val, m->st_idx, B, sc, beam, 1, 0, WIS_TAPS ? m->d_prof + (size_t)m->cfg.n_dec_layers * 8 * 16 + 16 : nullptr,
+                               nullptr, ts ? m->ts_desc : nullptr));
     WIS_RET(launch_beam_step(st, m->st_max, m->st_sum, m->st_val, m->st_idx, m->bs, m->rm, B, P, ctx, sc, WIS_TAPS ? m->d_prof + (size_t)m->cfg.n_dec_layers * 8 * 16 : nullptr));
     WIS_RET(launch_kv_reorder(st, m->kc_all, m->vc_all, m->kv_layer_stride, c.n_dec_layers, m->bs, B, beam, P, ctx, c.d_model));
     return WIS_OK;
@@ -1388,6 +1410,7 @@ static int generate_impl(wis_model_t* m, const float* input, int B, const int32_
     key.B = B; key.beam = beam; key.P = P; key.max_new = max_new; key.fixed_new = sc.fixed_new; key.suppress_blank = sc.suppress_blank;
     key.suppress_default = o->suppress_default; key.early_exit = sc.allow_early_exit; key.lp = sc.length_penalty; key.patience = patience; key.spin = (m->spin_now ? 1 : 0) | (sa_fuse_enabled() ? 2 : 0);
     key.sa_nb = nb;
+    key.timestamps = ts ? 1 : 0; key.max_init = ts ? ts_max_init : 0;
     auto it = m->graphs.find(key);
     if (it != m->graphs.end()) { *out = it->second; return WIS_OK; }
     hipGraph_t graph = nullptr; hipGraphExec_t ge = nullptr;
@@ -1541,6 +1564,7 @@ static int generate_impl(wis_model_t* m, const float* input, int B, const int32_
   m->timing.decode_steps = steps;             // steps enqueued (the merged prefill + first step included)
   m->timing.decode_steps_needed = needed;     // steps after which every utterance had finished: steps - needed = over-run
   if (steps > needed) { claim.defer(st); m->overrun_left = true; }      // an over-run step is still queued: its combiners keep their share of the spin budget until it has run
+  if (sot_row >= 0) m->nsp_B = B;
   return WIS_OK;
 }
 
@@ -1562,6 +1586,7 @@ int wis_generate(wis_model_t* m, const float* input, int B, const int32_t* promp
 int wis_generate_draft(wis_model_t* m, const float* input, const int32_t* prompt, int P, const wis_gen_opts_t* o,
                        const int32_t* draft, int n_draft, int32_t* out_ids, int32_t* out_len, float* out_score, int32_t* accepted) {
   if (!m || !input || !prompt || !o || !out_ids || !out_len || (n_draft > 0 && !draft) || n_draft < 0) { set_error("wis_generate_draft: bad argument"); return WIS_E_ARG; }
+  if (o->timestamps) { set_error("wis_generate_draft: timestamps are not available for drafted decodes"); return WIS_E_UNSUPPORTED; }
   WIS_ENTER(m, "wis_generate_draft")
   bool retry = false;
   int acc = 0;
@@ -1577,6 +1602,7 @@ int wis_generate_draft(wis_model_t* m, const float* input, const int32_t* prompt
 int wis_generate_draft_beam(wis_model_t* m, const float* input, const int32_t* prompt, int P, const wis_gen_opts_t* o,
                             const int32_t* draft_tok, const int32_t* draft_org, int n_steps, int32_t* out_ids, int32_t* out_len, float* out_score, int32_t* accepted_steps) {
   if (!m || !input || !prompt || !o || !out_ids || !out_len || n_steps < 0 || (n_steps > 0 && (!draft_tok || !draft_org))) { set_error("wis_generate_draft_beam: bad argument"); return WIS_E_ARG; }
+  if (o->timestamps) { set_error("wis_generate_draft_beam: timestamps are not available for drafted decodes"); return WIS_E_UNSUPPORTED; }
   WIS_ENTER(m, "wis_generate_draft_beam")
   bool retry = false;
   int acc = 0;
@@ -1586,6 +1612,17 @@ int wis_generate_draft_beam(wis_model_t* m, const float* input, const int32_t* p
     if (attempt == 1) { set_error("wis_generate_draft_beam: hand-off flag raised without the granule path"); return WIS_E_STATE; }
   }
   if (accepted_steps) *accepted_steps = acc;
+  return WIS_OK;
+}
+
+int wis_last_no_speech_prob(wis_model_t* m, int B, float* out) {
+  if (!m || !out || B < 1) { set_error("wis_last_no_speech_prob: bad argument"); return WIS_E_ARG; }
+  WIS_ENTER(m, "wis_last_no_speech_prob")
+  if (m->nsp_B == 0) { set_error("wis_last_no_speech_prob: the last wis_generate on this handle did not ask for no_speech_prob"); return WIS_E_STATE; }
+  if (B > m->nsp_B) { set_error("wis_last_no_speech_prob: %d utterances asked, the last call had %d", B, m->nsp_B); return WIS_E_ARG; }
+  WIS_HIP_CHECK(hipSetDevice(m->device));
+  WIS_HIP_CHECK(hipMemcpyAsync(out, m->d_nsp, (size_t)B * 4, hipMemcpyDeviceToHost, m->st));
+  WIS_HIP_CHECK(hipStreamSynchronize(m->st));
   return WIS_OK;
 }
 
@@ -1624,11 +1661,15 @@ int wis_debug_search(wis_model_t* m, const float* logits, int n_steps, int B, co
   float patience;
   const SampleCfg sc = make_sample_cfg(m, o, beam, max_new, &patience);
   const float* bias_all = o->suppress_default ? m->bias_all : nullptr;
+  const bool ts = o->timestamps != 0;
+  const int ts_max_init = o->max_initial_timestamp_index < 0 ? -1 : o->max_initial_timestamp_index;
   std::vector<int> done(B, 0), fin(B, -1), par(Mrows);
   for (int s = 0; s < max_new; ++s) {
     WIS_HIP_CHECK(hipMemcpy2DAsync(m->logits, (size_t)m->n_vocab_pad * 4, logits + (size_t)s * Mrows * V, (size_t)V * 4, (size_t)V * 4, Mrows, hipMemcpyHostToDevice, st));
     // step 0 samples every beam of an utterance from ONE row (wis_generate: the last prompt row; here row b*beam), later steps row b*beam + j
-    WIS_RET(launch_logit_stats(st, m->logits, bias_all, m->bias_begin, m->bs.step_u, m->st_max, m->st_sum, m->st_val, m->st_idx, B, sc, beam, s == 0 ? 0 : 1, 0));
+    if (ts) WIS_RET(launch_ts_rules(st, m->logits, bias_all, m->bias_begin, m->bs, B, sc, c.no_timestamps, ts_max_init, beam, s == 0 ? 0 : 1, 0, m->ts_desc));
+    WIS_RET(launch_logit_stats(st, m->logits, bias_all, m->bias_begin, m->bs.step_u, m->st_max, m->st_sum, m->st_val, m->st_idx, B, sc, beam, s == 0 ? 0 : 1, 0, nullptr, nullptr,
+                               ts ? m->ts_desc : nullptr));
     WIS_RET(launch_beam_step(st, m->st_max, m->st_sum, m->st_val, m->st_idx, m->bs, m->rm, B, P, c.n_text_ctx, sc));
     WIS_HIP_CHECK(hipMemcpyAsync(done.data(), m->bs.done, (size_t)B * 4, hipMemcpyDeviceToHost, st));
     WIS_HIP_CHECK(hipMemcpyAsync(par.data(), m->bs.parent, (size_t)Mrows * 4, hipMemcpyDeviceToHost, st));

@@ -40,7 +40,8 @@ class Tensor(C.Structure):
 class GenOpts(C.Structure):
     _fields_ = [("input_kind", C.c_int32), ("beam_size", C.c_int32), ("max_new_tokens", C.c_int32), ("length_penalty", C.c_float),
                 ("patience", C.c_float), ("suppress_blank", C.c_int32), ("suppress_default", C.c_int32),
-                ("fixed_new_tokens", C.c_int32), ("queue_depth", C.c_int32)]
+                ("fixed_new_tokens", C.c_int32), ("queue_depth", C.c_int32), ("timestamps", C.c_int32), ("max_initial_timestamp_index", C.c_int32),
+                ("no_speech_prob", C.c_int32)]
 
 
 class Timing(C.Structure):
@@ -87,6 +88,7 @@ SYMBOLS = [
     ("wis_generate_draft_beam", _i, [_vp, _vp, C.POINTER(C.c_int32), _i, C.POINTER(GenOpts), C.POINTER(C.c_int32), C.POINTER(C.c_int32), _i, C.POINTER(C.c_int32),
                                      C.POINTER(C.c_int32), _fp, C.POINTER(C.c_int32)]),
     ("wis_last_trajectory", _i, [_vp, _i, C.POINTER(C.c_int32), C.POINTER(C.c_int32), _i, C.POINTER(C.c_int32)]),
+    ("wis_last_no_speech_prob", _i, [_vp, _i, _fp]),
     ("wis_detect_language", _i, [_vp, _vp, _i, _i, _fp]),
     ("wis_debug_encode", _i, [_vp, _vp, _i, _i, _fp]),
     ("wis_debug_logits", _i, [_vp, _vp, _i, _i, C.POINTER(C.c_int32), _i, _fp]),

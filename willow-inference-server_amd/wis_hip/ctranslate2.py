@@ -172,13 +172,20 @@ def _last_trajectory(r, b, beam):
     return tok[:n.value].copy(), org[:n.value].copy()
 
 
-def _generate_chunk(r, mel, prompts, P, beam, max_new, lp, patience, suppress_blank, suppress_default, fixed_new, kind, device_ptr=None, draft=None, want_traj=False):
+def _generate_chunk(r, mel, prompts, P, beam, max_new, lp, patience, suppress_blank, suppress_default, fixed_new, kind, device_ptr=None, draft=None, want_traj=False,
+                    timestamps=False, max_initial_timestamp_index=50, no_speech_prob=False):
     """mel: host ndarray [B, ...] - or, with device_ptr, just the batch size B of features already resident on r.device.
     draft (one utterance): token ids of an earlier hypothesis (beam 1: wis_generate_draft) or the trajectory (tok [n][beam], org [n][beam]) of
     an earlier beam search (wis_generate_draft_beam) - verified in multi-row passes before ordinary steps go on.
-    want_traj: every result carries `.trajectory`, what a later call takes as its draft."""
+    want_traj: every result carries `.trajectory`, what a later call takes as its draft.
+    timestamps: Whisper's timestamp rules every step (max_initial_timestamp_index None: no cap on the first timestamp);
+    no_speech_prob: every result carries P(<|nospeech|>) at <|startoftranscript|> (wis_last_no_speech_prob)."""
     B = int(mel) if device_ptr is not None else mel.shape[0]
     o = _lib.GenOpts(kind, beam, max_new, lp, patience, int(bool(suppress_blank)), int(bool(suppress_default)), int(fixed_new), 0)
+    if timestamps:
+        o.timestamps = 1
+        o.max_initial_timestamp_index = -1 if max_initial_timestamp_index is None else int(max_initial_timestamp_index)
+    o.no_speech_prob = int(bool(no_speech_prob))
     pr = np.ascontiguousarray(np.asarray(prompts, np.int32).reshape(B, P))
     ids = np.zeros((B, max_new), np.int32)
     lens = np.zeros(B, np.int32)
@@ -201,7 +208,10 @@ def _generate_chunk(r, mel, prompts, P, beam, max_new, lp, patience, suppress_bl
     else:
         _lib.check(lib.wis_generate(r.handle, src, B, pr.ctypes.data_as(i32p), P, C.byref(o), ids.ctypes.data_as(i32p), lens.ctypes.data_as(i32p),
                                     scores.ctypes.data_as(C.POINTER(C.c_float))))
-    out = [WhisperGenerationResult([ids[b, :lens[b]].tolist()], [float(scores[b])]) for b in range(B)]
+    nsp = np.zeros(B, np.float32)
+    if no_speech_prob:
+        _lib.check(lib.wis_last_no_speech_prob(r.handle, B, nsp.ctypes.data_as(C.POINTER(C.c_float))))
+    out = [WhisperGenerationResult([ids[b, :lens[b]].tolist()], [float(scores[b])], float(nsp[b])) for b in range(B)]
     if acc is not None:
         out[0].accepted_draft_tokens = int(acc.value)      # tokens (beam 1) or search steps (beam > 1) of the draft the final decode kept
     if want_traj:
@@ -216,6 +226,17 @@ MAX_BEAM = 8               # csrc/kernels.hpp MAX_R: rows per utterance (beam si
 MAX_REPLICAS_PER_DEVICE = 4   # default ceiling for inter_threads -> replicas per GPU (measured on MI355X, bench.py "concurrent_device_batches": 118 / 152 / 165 / 173 / 160 utterances/s with 1..5 batches of 8 in flight)
 MAX_PROMPT = 16            # wis_generate: prompt tokens per utterance
 MAX_HYPOTHESES = 24        # csrc/kernels.hpp MAX_HYP: finished hypotheses an utterance's search can hold
+
+
+def timestamp_prompt(prompt):
+    """True when `prompt` asks for timestamps: from <|startoftranscript|> on it holds only the start sequence's special tokens
+    (language, task; ids in [<|endoftext|>, <|notimestamps|>)) and no <|notimestamps|> - what CTranslate2 decodes under Whisper's
+    timestamp rules.  A prompt without <|startoftranscript|>, with <|notimestamps|>, or with text or timestamp tokens after its start
+    sequence (a decoder prefix) keeps the plain search the engine has always run for it."""
+    p = [int(t) for t in prompt]
+    if W.SOT not in p:
+        return False
+    return all(W.EOT <= t < W.NO_TIMESTAMPS for t in p[p.index(W.SOT):])
 
 
 def _check_patience(beam_size, patience):
@@ -240,6 +261,8 @@ def _run_batch(replica, key, rows):
     P, beam, max_new, lp, patience, suppress_blank, suppress_default, fixed_new, kind = key[:9]
     draft = key[9] if len(key) > 9 else None          # (a drafted utterance has a key of its own: it never shares a device batch)
     want_traj = bool(key[10]) if len(key) > 10 else False
+    ts, mi, nsp = key[11:14] if len(key) > 11 else (False, 50, False)      # Whisper.generate's timestamp tail
+    tsk = dict(timestamps=ts, max_initial_timestamp_index=mi, no_speech_prob=nsp) if len(key) > 11 else {}
     dr = (draft[1] if draft and len(rows) == 1 else None)
     prompts = [p for _, p in rows]
     if kind == _lib.WIS_IN_MEL_DEV:
@@ -256,11 +279,11 @@ def _run_batch(replica, key, rows):
                     _lib.check(lib.wis_dev_copy_peer(replica.device, C.c_void_p(replica.stage.ptr.value + i * _MEL_BYTES), replica.device, C.c_void_p(int(src)), _MEL_BYTES))
                 ptr = replica.stage.ptr.value
             return _generate_chunk(replica, len(rows), prompts, P, beam, max_new, lp, patience, suppress_blank, suppress_default, fixed_new, kind, device_ptr=ptr,
-                                   draft=dr, want_traj=want_traj)
+                                   draft=dr, want_traj=want_traj, **tsk)
     mel = np.ascontiguousarray(np.stack([m for m, _ in rows]))
     with replica.lock:
         return _generate_chunk(replica, mel, prompts, P, beam, max_new, lp, patience, suppress_blank, suppress_default, fixed_new, kind,
-                               draft=dr, want_traj=want_traj)
+                               draft=dr, want_traj=want_traj, **tsk)
 
 
 class Whisper:
@@ -383,7 +406,11 @@ class Whisper:
         """`draft_tokens` (one utterance, beam_size 1): the ids of an earlier hypothesis for this audio - wis_generate_draft verifies them in
         multi-row passes and decodes on behind the accepted prefix; the result is the greedy decode of THESE features either way.
         `draft_trajectory` (one utterance, beam_size > 1): `(tok, org)` as an earlier result's `.trajectory` gives it (`return_trajectory=True`) -
-        the beam search is replayed along it 16 steps per decoder pass (wis_generate_draft_beam); the result is the beam search of THESE features."""
+        the beam search is replayed along it 16 steps per decoder pass (wis_generate_draft_beam); the result is the beam search of THESE features.
+        Timestamps: a Whisper start sequence without <|notimestamps|> (<|startoftranscript|>, language, task - `timestamp_prompt`) decodes
+        under Whisper's timestamp rules (first timestamp at most <|0.00|> + max_initial_timestamp_index; None: no cap); drafts cannot be
+        combined with them.  A prompt that carries text after its start sequence (a decoder prefix) keeps the plain search.  return_no_speech_prob=True fills
+        `no_speech_prob` (P(<|nospeech|>) at <|startoftranscript|>)."""
         if num_hypotheses != 1 or repetition_penalty != 1 or no_repeat_ngram_size != 0 or sampling_topk != 1:
             raise NotImplementedError("only the decoding options WIS uses are implemented (defaults of CTranslate2 4.1.0)")
         mel = self._features(features, input_kind)
@@ -399,10 +426,21 @@ class Whisper:
         if not 1 <= P <= MAX_PROMPT:
             raise ValueError(f"prompt length {P} outside 1..{MAX_PROMPT}")
         _check_patience(beam_size, patience)
+        ts_rows = [timestamp_prompt(p) for p in prompts]
+        timestamps = any(ts_rows)
+        if timestamps and not all(ts_rows):
+            raise ValueError("prompts of one call must all ask for timestamps (a start sequence without <|notimestamps|>) or none")
+        if timestamps and (draft_tokens is not None and len(draft_tokens) or draft_trajectory is not None and len(draft_trajectory[0])):
+            raise ValueError("timestamps (a prompt without <|notimestamps|>) cannot be combined with draft_tokens / draft_trajectory")
+        if return_no_speech_prob and (draft_tokens is not None and len(draft_tokens) or draft_trajectory is not None and len(draft_trajectory[0])):
+            raise ValueError("return_no_speech_prob cannot be combined with draft_tokens / draft_trajectory")
         max_new = min(max_length // 2, max_length - P)
         key = (P, int(beam_size), max_new, float(length_penalty), float(patience), bool(suppress_blank), list(suppress_tokens) == [-1],
                int(fixed_new_tokens), int(input_kind))
         key = key + self._draft_key(B, beam_size, draft_tokens, draft_trajectory, return_trajectory)
+        if timestamps or return_no_speech_prob:      # (the tail keeps the draft slots at fixed positions: _run_batch reads key[11:14])
+            mi = None if max_initial_timestamp_index is None else int(max_initial_timestamp_index)
+            key = (key + (None, False))[:11] + (timestamps, mi if timestamps else 50, bool(return_no_speech_prob))
         rows = [(np.ascontiguousarray(mel[b]), [int(t) for t in prompts[b]]) for b in range(B)]
         return self._batcher.submit(key, rows)
 

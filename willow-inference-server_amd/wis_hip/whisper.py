@@ -7,6 +7,9 @@ including the reference's behaviours: >= long_beam_size_threshold ms switches to
 > 30 s is chunked into 22 s windows with 4 s context, decoded `concurrent_gpu_chunks` at a time and stitched with
 find_longest_common_sequence (main.py:588-611, 677-711).
 
+`timestamps=True` decodes without <|notimestamps|> (CTranslate2 then applies Whisper's timestamp rules) and attaches
+`.segments` = [{start, end, text}] (segments_from_tokens); `text` stays free of timestamp tokens.  One 30 s window only.
+
 No tokenizer files exist offline (the reference loads HF WhisperProcessor from the model dir, main.py:329-334):
 prompt ids are the fixed multilingual ids; `text` is produced by an optional tokenizer
 (`tokenizers` JSON next to the model) and otherwise is the space-joined token ids.  The returned tuple also
@@ -27,10 +30,51 @@ MODEL_SIZES = ("tiny", "base", "small", "medium", "large")
 SPECIAL_IDS = list(range(W.EOT, W.N_VOCAB))     # <|endoftext|> ... timestamps: everything >= 50257 is special
 
 
+TIMESTAMP_BEGIN = W.NO_TIMESTAMPS + 1      # <|0.00|>; timestamp token t means (t - TIMESTAMP_BEGIN) * 0.02 s
+TIME_PRECISION = 0.02
+WINDOW_S = 30.0
+
+
 class WhisperResult(tuple):
-    """6-tuple like the reference's return value, plus the raw token ids."""
+    """6-tuple like the reference's return value, plus the raw token ids (and, decoded with timestamps, the segments)."""
     tokens = None
     translation_tokens = None
+    segments = None
+
+
+def segments_from_tokens(ids, tokenizer, offset=0.0, duration=WINDOW_S):
+    """Timed segments of one decoded window, split as openai-whisper's transcribe() splits a window's tokens: two consecutive
+    timestamps close one segment and open the next; a single timestamp before the end (EOT) closes the last segment; text that
+    no timestamp closes ends at the window's `duration`.  A window with no consecutive pair is one segment from `offset` to its last
+    timestamp (or to `duration` when that is <|0.00|> or there is none).  -> [{"start", "end", "text"}], seconds + `offset`."""
+    tb = TIMESTAMP_BEGIN
+    toks = [int(t) for t in ids if int(t) != W.EOT]
+    is_ts = [t >= tb for t in toks]
+
+    def seg(start, end, piece):
+        return {"start": round(offset + start, 2), "end": round(offset + end, 2), "text": tokenizer.decode([t for t in piece if t < W.EOT]).strip()}
+
+    def at(t):
+        return (t - tb) * TIME_PRECISION
+    slices = [i + 1 for i in range(len(toks) - 1) if is_ts[i] and is_ts[i + 1]]
+    single_ending = is_ts[-2:] == [False, True]
+    out = []
+    if slices:
+        if single_ending:
+            slices.append(len(toks))
+        last = 0
+        for cur in slices:
+            piece = toks[last:cur]
+            out.append(seg(at(piece[0]), at(piece[-1]), piece))
+            last = cur
+        tail = toks[last:]
+        if any(not f for f in is_ts[last:]):
+            out.append(seg(at(tail[0]) if tail[0] >= tb else out[-1]["end"] - offset, duration, tail))
+    elif toks:
+        stamps = [t for t in toks if t >= tb]
+        end = at(stamps[-1]) if stamps and stamps[-1] != tb else duration
+        out.append(seg(0.0, end, toks))
+    return out
 
 
 def special_ids_from_tokenizer_json(path):
@@ -157,7 +201,7 @@ def chunkit(lst, num):
 
 
 def do_whisper(audio_file, model, beam_size=None, task="transcribe", detect_language=False, force_language=None, translate=False,
-               models=None, fixed_new_tokens=None):
+               models=None, fixed_new_tokens=None, timestamps=False):
     models = models or default_models()
     s = models.settings
     if fixed_new_tokens is None:
@@ -179,6 +223,8 @@ def do_whisper(audio_file, model, beam_size=None, task="transcribe", detect_lang
     audio_duration = int(pcm.shape[0] / sr * 1000)
     if audio_duration >= s.long_beam_size_threshold:
         beam_size = s.long_beam_size
+    if timestamps and audio_duration > 30 * 1000:
+        raise ValueError("timestamps are available for audio of up to 30 s (one window)")
     use_chunking = audio_duration > 30 * 1000 and s.support_chunking
     strides = []
     if use_chunking:
@@ -212,7 +258,7 @@ def do_whisper(audio_file, model, beam_size=None, task="transcribe", detect_lang
     if not check_language(language):
         raise ValueError(f"unsupported language {language!r}")
     task_id = W.TRANSLATE if task == "translate" else W.TRANSCRIBE
-    prompt = [W.SOT, _Tokenizer.language_token_id(language), task_id, W.NO_TIMESTAMPS]
+    prompt = [W.SOT, _Tokenizer.language_token_id(language), task_id] + ([] if timestamps else [W.NO_TIMESTAMPS])
 
     # STEP 3 — run the model, `concurrent_gpu_chunks` windows per generate call
     results = []
@@ -227,7 +273,12 @@ def do_whisper(audio_file, model, beam_size=None, task="transcribe", detect_lang
         tokens = [int(t) for t in tokens]
     else:
         tokens = results[0].sequences_ids[0]
-    text = tokenizer.decode(tokens).strip()
+    segments = None
+    if timestamps:
+        segments = segments_from_tokens(tokens, tokenizer, 0.0, min(audio_duration / 1000.0, WINDOW_S))
+        text = tokenizer.decode([t for t in tokens if t < TIMESTAMP_BEGIN]).strip()
+    else:
+        text = tokenizer.decode(tokens).strip()
 
     translation = None
     if translate and total_chunk_count <= s.concurrent_gpu_chunks:       # main.py:729-748 (its `len(int)` bug aside: short audio only)
@@ -244,4 +295,5 @@ def do_whisper(audio_file, model, beam_size=None, task="transcribe", detect_lang
     out = WhisperResult((language, text, infer_time_milliseconds, translation, infer_speedup, audio_duration))
     out.tokens = tokens
     out.translation_tokens = out_translation_tokens
+    out.segments = segments
     return out
