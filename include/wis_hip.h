@@ -63,6 +63,10 @@ void wis_audio_free(float* pcm);
  * pcm_on_device / mel_on_device select host or device pointers for each side. */
 int wis_logmel(int device, const float* pcm, int64_t stride, const int64_t* n_samples, int n_win,
                int pcm_on_device, float* mel_out, int mel_on_device);
+/* the same with n_mels = 80 (tiny .. large-v2; wis_logmel) or 128 (large-v3 / large-v3-turbo, librosa's Slaney bank of 128
+ * filters): mel_out [n_win][n_mels][3000].  Any other n_mels: WIS_E_UNSUPPORTED. */
+int wis_logmel_n(int device, int n_mels, const float* pcm, int64_t stride, const int64_t* n_samples, int n_win,
+                 int pcm_on_device, float* mel_out, int mel_on_device);
 
 /* ---- 8(f)3: incremental log-mel over arriving PCM (streaming / long-form sessions).  One handle = ONE 30 s window being
  * filled on one device.  Frames are local (400 samples around 160 t, wis/audio.py:96-101), so every 16-frame tile whose samples
@@ -74,6 +78,9 @@ int wis_logmel(int device, const float* pcm, int64_t stride, const int64_t* n_sa
  * A handle is used by one thread at a time; different handles are independent (own stream and buffers). */
 typedef struct wis_melstream wis_melstream_t;
 int  wis_melstream_create(int device, wis_melstream_t** out);
+/* a session for n_mels = 80 (= wis_melstream_create) or 128 bins: finish then hands back [n_mels][3000], equal bit for bit to
+ * wis_logmel_n(n_mels) of the complete window.  Any other n_mels: WIS_E_UNSUPPORTED. */
+int  wis_melstream_create_n(int device, int n_mels, wis_melstream_t** out);
 int  wis_melstream_reset(wis_melstream_t* s);
 int  wis_melstream_feed(wis_melstream_t* s, const float* pcm, int64_t n_samples);   /* host PCM, appended; beyond 480000: ignored */
 int  wis_melstream_finish(wis_melstream_t* s, float* mel_host_or_null, float** mel_dev_out);
@@ -86,10 +93,10 @@ void wis_melstream_destroy(wis_melstream_t* s);
  * GPU; the Python shim creates one per listed device_index entry. */
 typedef struct {
   int32_t d_model, n_heads, n_enc_layers, n_dec_layers;
-  int32_t n_vocab;        /* 51865 multilingual */
+  int32_t n_vocab;        /* 51865 multilingual; 51866 large-v3 */
   int32_t n_audio_ctx;    /* 1500 */
   int32_t n_text_ctx;     /* 448 */
-  int32_t n_mels;         /* 80 */
+  int32_t n_mels;         /* 80, or 128 (large-v3 / large-v3-turbo) */
   int32_t max_batch;      /* utterances (30 s windows) per device batch */
   int32_t max_beam;       /* largest beam_size that will be requested */
   int32_t eot, sot, no_timestamps, no_speech;   /* 50257, 50258, 50363, 50362 */
@@ -130,7 +137,7 @@ int  wis_model_clone(wis_model_t* parent, wis_model_t** out);
 /* ---- a7-a13: generate (replaces whisper_model.generate(features, [prompt]*B,
  * beam_size=.., return_scores=False) and results[i].sequences_ids[0], main.py:685-693,707,713;
  * decoding defaults are CTranslate2 4.1.0's because WIS passes none). */
-#define WIS_IN_MEL_HOST 0   /* f32 [B][80][3000] host   (StorageView.from_array, main.py:638,685) */
+#define WIS_IN_MEL_HOST 0   /* f32 [B][n_mels][3000] host   (StorageView.from_array, main.py:638,685) */
 #define WIS_IN_MEL_DEV  1   /* same, device memory */
 #define WIS_IN_PCM_HOST 2   /* f32 [B][480000] host: log-mel runs on the GPU, mel never leaves HBM */
 #define WIS_IN_PCM_DEV  3

@@ -176,15 +176,18 @@ int get_ctx(int device, DeviceCtx** out);
 hipStream_t ctx_stream(DeviceCtx* c);
 std::mutex& ctx_op_mutex(DeviceCtx* c);   // serialises the single-kernel taps (wis_op_*) that share ctx_stream
 
-// log-mel on `stream`: pcm (device) -> mel f32 [n_win][80][3000] (device, may be null) and/or
-// conv1 input f16 [n_win][3002][96] (device, may be null; rows 0 and 3001 and cols 80..95 zero).
-// d_logspec f32 [n_win][80][3000] and d_gmax u32 [n_win] are the caller's own scratch (never shared between in-flight calls).
+// log-mel on `stream`: pcm (device) -> mel f32 [n_win][n_mels][3000] (device, may be null) and/or
+// conv1 input f16 [n_win][3002][conv1_channels(n_mels)] (device, may be null; rows 0 and 3001 and the pad cols 80..95 zero).
+// d_logspec f32 [n_win][n_mels][3000] and d_gmax u32 [n_win] are the caller's own scratch (never shared between in-flight calls).
+// n_mels: 80 (tiny .. large-v2) or 128 (large-v3); anything else is WIS_E_UNSUPPORTED.
+bool mel_bins_supported(int n_mels);
+int conv1_channels(int n_mels);          // conv1 image row pitch: 96 for 80 bins, 128 for 128
 int logmel_device(DeviceCtx* c, hipStream_t stream, float* d_logspec, unsigned* d_gmax, const float* d_pcm, int64_t stride,
-                  const int64_t* d_nsamp, int n_win, float* d_mel, f16* d_conv_in);
+                  const int64_t* d_nsamp, int n_win, float* d_mel, f16* d_conv_in, int n_mels);
 // the two halves, for streaming sessions: log-spectrum of the 16-frame tiles [tile0, tile0 + n_tiles) of every window
 // (accumulates the running maximum into d_gmax, which the caller zeroes once per window), then clamp / scale / emit
 int logmel_frames(DeviceCtx* c, hipStream_t stream, float* d_logspec, unsigned* d_gmax, const float* d_pcm, int64_t stride,
-                  const int64_t* d_nsamp, int n_win, int tile0, int n_tiles);
-int logmel_finalize(hipStream_t stream, const float* d_logspec, const unsigned* d_gmax, int n_win, float* d_mel, f16* d_conv_in);
+                  const int64_t* d_nsamp, int n_win, int tile0, int n_tiles, int n_mels);
+int logmel_finalize(hipStream_t stream, const float* d_logspec, const unsigned* d_gmax, int n_win, float* d_mel, f16* d_conv_in, int n_mels);
 
 }  // namespace wis

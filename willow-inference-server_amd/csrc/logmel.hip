@@ -41,7 +41,10 @@ constexpr int SPAN = (FT - 1) * HOP + NFFT;          // 2800 samples per workgro
 constexpr int SKEW(int s) { return s + 2 * (s / HOP); }  // LDS bank skew (see A-operand reads)
 constexpr int SPAN_LDS = SPAN + 2 * (SPAN / HOP) + 8;
 constexpr int PSTR = NBINP + 1;          // 209: power tile row stride
-constexpr int CONV_C = 96;               // conv1 input channels padded 80 -> 96 (K = 288 = 9 x 32)
+constexpr int NMEL_MAX = 128;            // large-v3 / large-v3-turbo; the workspaces are sized for it
+// conv1 input channels: 80 bins padded to 96 (K = 288 = 9 x 32, read as 320 = 5 x 64 with zero-weighted columns);
+// 128 bins need no pad (K = 384 = 6 x 64)
+template <int NM> struct MelShape { static constexpr int CONV_C = NM == 80 ? 96 : NM; };
 
 struct DeviceCtx {
   int device = -1;
@@ -49,6 +52,8 @@ struct DeviceCtx {
   float* d_dft = nullptr;     // [NCT][25][64][4]  MFMA-B-fragment-packed DFT matrix
   float* d_filt = nullptr;    // [80][201]
   int* d_frange = nullptr;    // [80][2] first / one-past-last non-zero bin
+  float* d_filt128 = nullptr; // [128][201]: the large-v3 bank
+  int* d_frange128 = nullptr; // [128][2]
   // wis_logmel workspaces: one per in-flight call (own stream, own staging and scratch), recycled through a free list, so
   // the entry point is re-entrant: concurrent callers never share a buffer or a stream (SURVEY 8(b) conventions)
   std::mutex ws_mu;
@@ -77,8 +82,8 @@ static int ws_acquire(DeviceCtx* c, int n_win, LogmelWs** out) {
     hipFree(w->d_pcm); hipFree(w->d_nsamp); hipFree(w->d_melout); hipFree(w->d_logspec); hipFree(w->d_gmax);
     w->d_pcm = nullptr; w->d_nsamp = nullptr; w->d_melout = nullptr; w->d_logspec = nullptr; w->d_gmax = nullptr; w->cap = 0;
     if (hipMalloc(&w->d_pcm, (size_t)n_win * NSAMP * 4) != hipSuccess || hipMalloc(&w->d_nsamp, (size_t)n_win * 8) != hipSuccess ||
-        hipMalloc(&w->d_melout, (size_t)n_win * NMEL * NFRAMES * 4) != hipSuccess ||
-        hipMalloc(&w->d_logspec, (size_t)n_win * NMEL * NFRAMES * 4) != hipSuccess || hipMalloc(&w->d_gmax, (size_t)n_win * 4) != hipSuccess) {
+        hipMalloc(&w->d_melout, (size_t)n_win * NMEL_MAX * NFRAMES * 4) != hipSuccess ||
+        hipMalloc(&w->d_logspec, (size_t)n_win * NMEL_MAX * NFRAMES * 4) != hipSuccess || hipMalloc(&w->d_gmax, (size_t)n_win * 4) != hipSuccess) {
       set_error("wis_logmel: out of device memory for %d windows", n_win);
       std::lock_guard<std::mutex> lk(c->ws_mu); c->ws_free.push_back(w);     // cap = 0: the next owner re-allocates
       return WIS_E_NOMEM;
@@ -96,7 +101,7 @@ std::mutex& ctx_op_mutex(DeviceCtx* c) { return c->op_mu; }
 static std::mutex g_ctx_mu;
 static DeviceCtx* g_ctx[64] = {nullptr};
 
-// Slaney mel scale, as librosa.filters.mel(sr=16000, n_fft=400, n_mels=80) which produced
+// Slaney mel scale, as librosa.filters.mel(sr=16000, n_fft=400, n_mels=80 | 128) which produced
 // the reference asset wis/assets/mel_filters.npz (wis/audio.py:54-69); fp64 then rounded.
 static double hz_to_mel(double f) {
   const double f_sp = 200.0 / 3, min_log_hz = 1000.0, min_log_mel = min_log_hz / f_sp, logstep = log(6.4) / 27.0;
@@ -106,11 +111,11 @@ static double mel_to_hz(double m) {
   const double f_sp = 200.0 / 3, min_log_hz = 1000.0, min_log_mel = min_log_hz / f_sp, logstep = log(6.4) / 27.0;
   return m >= min_log_mel ? min_log_hz * exp(logstep * (m - min_log_mel)) : f_sp * m;
 }
-void build_mel_filters(float* out /*[80][201]*/) {
-  double melpts[NMEL + 2];
+void build_mel_filters(float* out /*[n_mels][201]*/, int n_mels) {
+  double melpts[NMEL_MAX + 2];
   const double mlo = hz_to_mel(0.0), mhi = hz_to_mel(WIS_SAMPLE_RATE / 2.0);
-  for (int i = 0; i < NMEL + 2; ++i) melpts[i] = mel_to_hz(mlo + (mhi - mlo) * i / (NMEL + 1));
-  for (int m = 0; m < NMEL; ++m) {
+  for (int i = 0; i < n_mels + 2; ++i) melpts[i] = mel_to_hz(mlo + (mhi - mlo) * i / (n_mels + 1));
+  for (int m = 0; m < n_mels; ++m) {
     const double enorm = 2.0 / (melpts[m + 2] - melpts[m]);
     for (int k = 0; k < NBIN; ++k) {
       const double f = (WIS_SAMPLE_RATE / 2.0) * k / (NBIN - 1);
@@ -151,21 +156,25 @@ int get_ctx(int device, DeviceCtx** out) {
           }
           dft[(((size_t)ct * 25 + g) * 64 + lane) * 4 + u] = v;
         }
-  std::vector<float> filt((size_t)NMEL * NBIN);
-  build_mel_filters(filt.data());
-  std::vector<int> fr(NMEL * 2);
-  for (int m = 0; m < NMEL; ++m) {
-    int lo = NBIN, hi = 0;
-    for (int k = 0; k < NBIN; ++k) if (filt[m * NBIN + k] != 0.f) { if (k < lo) lo = k; hi = k + 1; }
-    if (lo > hi) lo = hi = 0;
-    fr[2 * m] = lo; fr[2 * m + 1] = hi;
-  }
   WIS_HIP_CHECK(hipMalloc(&c->d_dft, dft.size() * 4));
-  WIS_HIP_CHECK(hipMalloc(&c->d_filt, filt.size() * 4));
-  WIS_HIP_CHECK(hipMalloc(&c->d_frange, fr.size() * 4));
   WIS_HIP_CHECK(hipMemcpy(c->d_dft, dft.data(), dft.size() * 4, hipMemcpyHostToDevice));
-  WIS_HIP_CHECK(hipMemcpy(c->d_filt, filt.data(), filt.size() * 4, hipMemcpyHostToDevice));
-  WIS_HIP_CHECK(hipMemcpy(c->d_frange, fr.data(), fr.size() * 4, hipMemcpyHostToDevice));
+  for (const int nm : {NMEL, NMEL_MAX}) {      // both filter banks: 80 (tiny .. large-v2) and 128 (large-v3)
+    std::vector<float> filt((size_t)nm * NBIN);
+    build_mel_filters(filt.data(), nm);
+    std::vector<int> fr(nm * 2);
+    for (int m = 0; m < nm; ++m) {
+      int lo = NBIN, hi = 0;
+      for (int k = 0; k < NBIN; ++k) if (filt[m * NBIN + k] != 0.f) { if (k < lo) lo = k; hi = k + 1; }
+      if (lo > hi) lo = hi = 0;
+      fr[2 * m] = lo; fr[2 * m + 1] = hi;
+    }
+    float*& df = nm == NMEL ? c->d_filt : c->d_filt128;
+    int*& dr = nm == NMEL ? c->d_frange : c->d_frange128;
+    WIS_HIP_CHECK(hipMalloc(&df, filt.size() * 4));
+    WIS_HIP_CHECK(hipMalloc(&dr, fr.size() * 4));
+    WIS_HIP_CHECK(hipMemcpy(df, filt.data(), filt.size() * 4, hipMemcpyHostToDevice));
+    WIS_HIP_CHECK(hipMemcpy(dr, fr.data(), fr.size() * 4, hipMemcpyHostToDevice));
+  }
   g_ctx[device] = c; *out = c;
   return WIS_OK;
 }
@@ -180,7 +189,8 @@ __device__ __forceinline__ float fkey_inv(unsigned k) {
   return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k);
 }
 
-// grid (188, n_win), block 256
+// grid (188, n_win), block 256; NM = mel bins (80 or 128): only the filterbank stage and the logspec layout depend on it
+template <int NM>
 __global__ __launch_bounds__(256) void logmel_stft_kernel(
     const float* __restrict__ pcm, int64_t stride, const int64_t* __restrict__ nsamp,
     const float* __restrict__ dft, const float* __restrict__ filt, const int* __restrict__ frange,
@@ -245,9 +255,9 @@ __global__ __launch_bounds__(256) void logmel_stft_kernel(
   }
   __syncthreads();
 
-  // mel filterbank (sparse rows) + log10; 80 x 16 outputs over 256 threads
+  // mel filterbank (sparse rows) + log10; NM x 16 outputs over 256 threads
   float lmax = -INFINITY;
-  for (int o = tid; o < NMEL * FT; o += 256) {
+  for (int o = tid; o < NM * FT; o += 256) {
     const int f = o & (FT - 1), m = o >> 4;
     float v = 0.f;
     if (any) {
@@ -258,7 +268,7 @@ __global__ __launch_bounds__(256) void logmel_stft_kernel(
     }
     const float lg = log10f(fmaxf(v, 1e-10f));
     if (f0 + f < NFRAMES) {
-      logspec[((size_t)w * NMEL + m) * NFRAMES + f0 + f] = lg;
+      logspec[((size_t)w * NM + m) * NFRAMES + f0 + f] = lg;
       lmax = fmaxf(lmax, lg);
     }
   }
@@ -271,18 +281,20 @@ __global__ __launch_bounds__(256) void logmel_stft_kernel(
   }
 }
 
-// grid (ceil(3000/64), n_win), block 256: clamp to max-8, scale, write f32 [80][3000] and/or
-// the conv1 input image f16 [3002][96] (row t+1 = frame t; pad rows/cols stay zero).
+// grid (ceil(3000/64), n_win), block 256: clamp to max-8, scale, write f32 [NM][3000] and/or
+// the conv1 input image f16 [3002][CONV_C] (row t+1 = frame t; pad rows/cols stay zero).
+template <int NM>
 __global__ __launch_bounds__(256) void logmel_finalize_kernel(
     const float* __restrict__ logspec, const unsigned* __restrict__ gmax,
     float* __restrict__ mel, f16* __restrict__ conv_in) {
-  __shared__ float s_t[NMEL][65];
+  constexpr int CONV_C = MelShape<NM>::CONV_C;
+  __shared__ float s_t[NM][65];
   const int tid = threadIdx.x, w = blockIdx.y, f0 = blockIdx.x * 64;
   const float floor_ = fkey_inv(gmax[w]) - 8.0f;
-  for (int o = tid; o < NMEL * 64; o += 256) {
+  for (int o = tid; o < NM * 64; o += 256) {
     const int m = o >> 6, f = o & 63;
     if (f0 + f < NFRAMES) {
-      const size_t idx = ((size_t)w * NMEL + m) * NFRAMES + f0 + f;
+      const size_t idx = ((size_t)w * NM + m) * NFRAMES + f0 + f;
       const float v = (fmaxf(logspec[idx], floor_) + 4.0f) / 4.0f;
       if (mel) mel[idx] = v;
       s_t[m][f] = v;
@@ -293,34 +305,46 @@ __global__ __launch_bounds__(256) void logmel_finalize_kernel(
   for (int o = tid; o < 64 * CONV_C; o += 256) {
     const int f = o / CONV_C, c = o - f * CONV_C;
     if (f0 + f < NFRAMES)
-      conv_in[((size_t)w * (NFRAMES + 2) + f0 + f + 1) * CONV_C + c] = (c < NMEL) ? (f16)s_t[c][f] : (f16)0.f;
+      conv_in[((size_t)w * (NFRAMES + 2) + f0 + f + 1) * CONV_C + c] = (c < NM) ? (f16)s_t[c][f] : (f16)0.f;
   }
 }
 
 // The frame tiles are independent (a frame depends on 400 samples around it); only the clamp at (global max - 8) couples a
-// window, and that is the finalize pass.  d_logspec [n_win][80][3000] / d_gmax [n_win] are the CALLER's scratch: nothing in
+// window, and that is the finalize pass.  d_logspec [n_win][n_mels][3000] / d_gmax [n_win] are the CALLER's scratch: nothing in
 // here is shared between two in-flight calls.
+bool mel_bins_supported(int n_mels) { return n_mels == NMEL || n_mels == NMEL_MAX; }
+int conv1_channels(int n_mels) { return n_mels == NMEL ? MelShape<NMEL>::CONV_C : MelShape<NMEL_MAX>::CONV_C; }
 int logmel_frames(DeviceCtx* c, hipStream_t stream, float* d_logspec, unsigned* d_gmax, const float* d_pcm, int64_t stride,
-                  const int64_t* d_nsamp, int n_win, int tile0, int n_tiles) {
+                  const int64_t* d_nsamp, int n_win, int tile0, int n_tiles, int n_mels) {
   if (n_win <= 0 || n_tiles <= 0) return WIS_OK;
   if (tile0 < 0 || tile0 + n_tiles > cdiv(NFRAMES, FT)) { set_error("logmel_frames: tiles [%d, %d) out of range", tile0, tile0 + n_tiles); return WIS_E_ARG; }
-  hipLaunchKernelGGL(logmel_stft_kernel, dim3(n_tiles, n_win), dim3(256), 0, stream,
-                     d_pcm, stride, d_nsamp, c->d_dft, c->d_filt, c->d_frange, d_logspec, d_gmax, tile0);
+  if (n_mels == NMEL)
+    hipLaunchKernelGGL(logmel_stft_kernel<NMEL>, dim3(n_tiles, n_win), dim3(256), 0, stream,
+                       d_pcm, stride, d_nsamp, c->d_dft, c->d_filt, c->d_frange, d_logspec, d_gmax, tile0);
+  else if (n_mels == NMEL_MAX)
+    hipLaunchKernelGGL(logmel_stft_kernel<NMEL_MAX>, dim3(n_tiles, n_win), dim3(256), 0, stream,
+                       d_pcm, stride, d_nsamp, c->d_dft, c->d_filt128, c->d_frange128, d_logspec, d_gmax, tile0);
+  else { set_error("logmel: %d mel bins (80 or 128)", n_mels); return WIS_E_UNSUPPORTED; }
   WIS_HIP_CHECK(hipGetLastError());
   return WIS_OK;
 }
-int logmel_finalize(hipStream_t stream, const float* d_logspec, const unsigned* d_gmax, int n_win, float* d_mel, f16* d_conv_in) {
+int logmel_finalize(hipStream_t stream, const float* d_logspec, const unsigned* d_gmax, int n_win, float* d_mel, f16* d_conv_in, int n_mels) {
   if (n_win <= 0) return WIS_OK;
-  hipLaunchKernelGGL(logmel_finalize_kernel, dim3(cdiv(NFRAMES, 64), n_win), dim3(256), 0, stream, d_logspec, d_gmax, d_mel, d_conv_in);
+  if (n_mels == NMEL)
+    hipLaunchKernelGGL(logmel_finalize_kernel<NMEL>, dim3(cdiv(NFRAMES, 64), n_win), dim3(256), 0, stream, d_logspec, d_gmax, d_mel, d_conv_in);
+  else if (n_mels == NMEL_MAX)
+    hipLaunchKernelGGL(logmel_finalize_kernel<NMEL_MAX>, dim3(cdiv(NFRAMES, 64), n_win), dim3(256), 0, stream, d_logspec, d_gmax, d_mel, d_conv_in);
+  else { set_error("logmel: %d mel bins (80 or 128)", n_mels); return WIS_E_UNSUPPORTED; }
   WIS_HIP_CHECK(hipGetLastError());
   return WIS_OK;
 }
 int logmel_device(DeviceCtx* c, hipStream_t stream, float* d_logspec, unsigned* d_gmax, const float* d_pcm, int64_t stride,
-                  const int64_t* d_nsamp, int n_win, float* d_mel, f16* d_conv_in) {
+                  const int64_t* d_nsamp, int n_win, float* d_mel, f16* d_conv_in, int n_mels) {
   if (n_win <= 0) return WIS_OK;
+  if (!mel_bins_supported(n_mels)) { set_error("logmel: %d mel bins (80 or 128)", n_mels); return WIS_E_UNSUPPORTED; }
   WIS_HIP_CHECK(hipMemsetAsync(d_gmax, 0, (size_t)n_win * 4, stream));
-  WIS_RET(logmel_frames(c, stream, d_logspec, d_gmax, d_pcm, stride, d_nsamp, n_win, 0, cdiv(NFRAMES, FT)));
-  return logmel_finalize(stream, d_logspec, d_gmax, n_win, d_mel, d_conv_in);
+  WIS_RET(logmel_frames(c, stream, d_logspec, d_gmax, d_pcm, stride, d_nsamp, n_win, 0, cdiv(NFRAMES, FT), n_mels));
+  return logmel_finalize(stream, d_logspec, d_gmax, n_win, d_mel, d_conv_in, n_mels);
 }
 
 }  // namespace wis
@@ -329,8 +353,9 @@ int logmel_device(DeviceCtx* c, hipStream_t stream, float* d_logspec, unsigned* 
 using namespace wis;
 
 // Re-entrant: every call runs on a workspace of its own (stream + staging + scratch) taken from the device's free list.
-extern "C" int wis_logmel(int device, const float* pcm, int64_t stride, const int64_t* n_samples, int n_win,
-                          int pcm_on_device, float* mel_out, int mel_on_device) {
+extern "C" int wis_logmel_n(int device, int n_mels, const float* pcm, int64_t stride, const int64_t* n_samples, int n_win,
+                            int pcm_on_device, float* mel_out, int mel_on_device) {
+  if (!mel_bins_supported(n_mels)) { set_error("wis_logmel_n: %d mel bins (80 or 128)", n_mels); return WIS_E_UNSUPPORTED; }
   if (!pcm || !n_samples || !mel_out || n_win < 0 || stride < 0) { set_error("wis_logmel: bad argument"); return WIS_E_ARG; }
   if (n_win == 0) return WIS_OK;
   DeviceCtx* c; WIS_RET(get_ctx(device, &c));
@@ -348,9 +373,9 @@ extern "C" int wis_logmel(int device, const float* pcm, int64_t stride, const in
     }
     WIS_HIP_CHECK(hipMemcpyAsync(ws->d_nsamp, ns.data(), (size_t)n_win * 8, hipMemcpyHostToDevice, st));
     float* dm = mel_on_device ? mel_out : ws->d_melout;
-    WIS_RET(logmel_device(c, st, ws->d_logspec, ws->d_gmax, dp, dstride, ws->d_nsamp, n_win, dm, nullptr));
+    WIS_RET(logmel_device(c, st, ws->d_logspec, ws->d_gmax, dp, dstride, ws->d_nsamp, n_win, dm, nullptr, n_mels));
     if (!mel_on_device)
-      WIS_HIP_CHECK(hipMemcpyAsync(mel_out, dm, (size_t)n_win * NMEL * NFRAMES * 4, hipMemcpyDeviceToHost, st));
+      WIS_HIP_CHECK(hipMemcpyAsync(mel_out, dm, (size_t)n_win * n_mels * NFRAMES * 4, hipMemcpyDeviceToHost, st));
     WIS_HIP_CHECK(hipStreamSynchronize(st));      // `ns` (pageable) and the caller's buffers are free again
     return WIS_OK;
   };
@@ -359,6 +384,10 @@ extern "C" int wis_logmel(int device, const float* pcm, int64_t stride, const in
   ws_release(c, ws);
   return rc;
 }
+extern "C" int wis_logmel(int device, const float* pcm, int64_t stride, const int64_t* n_samples, int n_win,
+                          int pcm_on_device, float* mel_out, int mel_on_device) {
+  return wis_logmel_n(device, NMEL, pcm, stride, n_samples, n_win, pcm_on_device, mel_out, mel_on_device);
+}
 
 // ---------------------------------------------------------------------------------------
 // Incremental log-mel: the window's PCM accumulates in HBM; tile j (frames 16j .. 16j+15) reads the samples
@@ -366,6 +395,7 @@ extern "C" int wis_logmel(int device, const float* pcm, int64_t stride, const in
 // it reaches the right edge of the 30 s window, where the reflection reads samples up to 479999: those tiles wait for finish.
 struct wis_melstream {
   int device = 0;
+  int n_mels = NMEL;
   DeviceCtx* ctx = nullptr;
   hipStream_t stream = nullptr;
   float* d_pcm = nullptr; int64_t* d_nsamp = nullptr; float* d_logspec = nullptr; unsigned* d_gmax = nullptr; float* d_mel = nullptr;
@@ -387,20 +417,22 @@ int tiles_final_for(int64_t n) {
 }
 }  // namespace
 
-extern "C" int wis_melstream_create(int device, wis_melstream_t** out) {
+extern "C" int wis_melstream_create_n(int device, int n_mels, wis_melstream_t** out) {
+  if (!mel_bins_supported(n_mels)) { set_error("wis_melstream_create_n: %d mel bins (80 or 128)", n_mels); return WIS_E_UNSUPPORTED; }
   if (!out) { set_error("wis_melstream_create: bad argument"); return WIS_E_ARG; }
   DeviceCtx* c; WIS_RET(get_ctx(device, &c));
   wis_melstream* s = new wis_melstream();
-  s->device = device; s->ctx = c;
+  s->device = device; s->ctx = c; s->n_mels = n_mels;
   bool ok = hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking) == hipSuccess &&
             hipMalloc(&s->d_pcm, (size_t)NSAMP * 4) == hipSuccess && hipMalloc(&s->d_nsamp, 8) == hipSuccess &&
-            hipMalloc(&s->d_logspec, (size_t)NMEL * NFRAMES * 4) == hipSuccess && hipMalloc(&s->d_gmax, 4) == hipSuccess &&
-            hipMalloc(&s->d_mel, (size_t)NMEL * NFRAMES * 4) == hipSuccess &&
+            hipMalloc(&s->d_logspec, (size_t)n_mels * NFRAMES * 4) == hipSuccess && hipMalloc(&s->d_gmax, 4) == hipSuccess &&
+            hipMalloc(&s->d_mel, (size_t)n_mels * NFRAMES * 4) == hipSuccess &&
             hipHostMalloc(reinterpret_cast<void**>(&s->h_nsamp), 64, hipHostMallocDefault) == hipSuccess;
   if (!ok) { set_error("wis_melstream_create: allocation failed"); wis_melstream_destroy(s); return WIS_E_NOMEM; }
   *out = s;
   return wis_melstream_reset(s);
 }
+extern "C" int wis_melstream_create(int device, wis_melstream_t** out) { return wis_melstream_create_n(device, NMEL, out); }
 extern "C" int wis_melstream_reset(wis_melstream_t* s) {
   if (!s) { set_error("wis_melstream_reset: bad argument"); return WIS_E_ARG; }
   WIS_HIP_CHECK(hipSetDevice(s->device));
@@ -413,7 +445,7 @@ static int melstream_run_tiles(wis_melstream* s, int upto) {
   if (upto <= s->tiles_done) return WIS_OK;
   *s->h_nsamp = s->n;                                  // the kernel treats samples >= n as zero (pad_or_trim)
   WIS_HIP_CHECK(hipMemcpyAsync(s->d_nsamp, s->h_nsamp, 8, hipMemcpyHostToDevice, s->stream));
-  WIS_RET(logmel_frames(s->ctx, s->stream, s->d_logspec, s->d_gmax, s->d_pcm, NSAMP, s->d_nsamp, 1, s->tiles_done, upto - s->tiles_done));
+  WIS_RET(logmel_frames(s->ctx, s->stream, s->d_logspec, s->d_gmax, s->d_pcm, NSAMP, s->d_nsamp, 1, s->tiles_done, upto - s->tiles_done, s->n_mels));
   WIS_HIP_CHECK(hipStreamSynchronize(s->stream));      // h_nsamp is reused by the next call; a feed is not latency critical
   s->tiles_done = upto;
   return WIS_OK;
@@ -436,10 +468,10 @@ extern "C" int wis_melstream_finish(wis_melstream_t* s, float* mel_host_or_null,
   WIS_HIP_CHECK(hipSetDevice(s->device));
   if (!s->finished) {
     WIS_RET(melstream_run_tiles(s, NTILES));           // the tail against the zero padding
-    WIS_RET(logmel_finalize(s->stream, s->d_logspec, s->d_gmax, 1, s->d_mel, nullptr));
+    WIS_RET(logmel_finalize(s->stream, s->d_logspec, s->d_gmax, 1, s->d_mel, nullptr, s->n_mels));
     s->finished = true;
   }
-  if (mel_host_or_null) WIS_HIP_CHECK(hipMemcpyAsync(mel_host_or_null, s->d_mel, (size_t)NMEL * NFRAMES * 4, hipMemcpyDeviceToHost, s->stream));
+  if (mel_host_or_null) WIS_HIP_CHECK(hipMemcpyAsync(mel_host_or_null, s->d_mel, (size_t)s->n_mels * NFRAMES * 4, hipMemcpyDeviceToHost, s->stream));
   WIS_HIP_CHECK(hipStreamSynchronize(s->stream));
   if (mel_dev_out) *mel_dev_out = s->d_mel;
   return WIS_OK;

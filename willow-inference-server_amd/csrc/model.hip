@@ -27,7 +27,6 @@
 using namespace wis;
 
 namespace wis {
-void build_mel_filters(float* out);
 
 // ---- small utility kernels -------------------------------------------------------------
 // generic convert: src (f16|f32) [rows][cols] -> dst (f16|f32) [rows][dst_ld]; rows < n_scale scaled
@@ -55,20 +54,24 @@ __global__ void conv_pack_kernel(const void* __restrict__ src, int src_f16, f16*
     dst[i] = (f16)v;
   }
 }
-// mel f32 [B][80][3000] -> conv1 input image f16 [B][3002][96]
+// mel f32 [B][NM][3000] -> conv1 input image f16 [B][3002][CC]: NM = 80 bins padded to CC = 96 channels, or 128 bins (CC = 128)
+template <int NM, int CC>
 __global__ void mel_to_image_kernel(const float* __restrict__ mel, f16* __restrict__ img) {
-  __shared__ float s_t[80][65];
+  __shared__ float s_t[NM][65];
   const int tid = threadIdx.x, w = blockIdx.y, f0 = blockIdx.x * 64;
-  for (int o = tid; o < 80 * 64; o += 256) {
+  for (int o = tid; o < NM * 64; o += 256) {
     const int m = o >> 6, f = o & 63;
-    if (f0 + f < 3000) s_t[m][f] = mel[((size_t)w * 80 + m) * 3000 + f0 + f];
+    if (f0 + f < 3000) s_t[m][f] = mel[((size_t)w * NM + m) * 3000 + f0 + f];
   }
   __syncthreads();
-  for (int o = tid; o < 64 * 96; o += 256) {
-    const int f = o / 96, c = o - f * 96;
-    if (f0 + f < 3000) img[((size_t)w * 3002 + f0 + f + 1) * 96 + c] = (c < 80) ? (f16)s_t[c][f] : (f16)0.f;
+  for (int o = tid; o < 64 * CC; o += 256) {
+    const int f = o / CC, c = o - f * CC;
+    if (f0 + f < 3000) img[((size_t)w * 3002 + f0 + f + 1) * CC + c] = (c < NM) ? (f16)s_t[c][f] : (f16)0.f;
   }
 }
+// conv1 over the [3002][C] image (C = conv1_channels(n_mels)) as one implicit-im2col GEMM: K = 3C, rounded up to whole 64-deep
+// k-tiles (80 bins: 288 -> 320, the 32 extra columns carry zero weights and read into the next row; 128 bins: 384, no pad)
+static int conv1_k(int n_mels) { return cdiv(3 * conv1_channels(n_mels), 64) * 64; }
 // dst[c][r] = src[r][c] as f16 (src f16 or f32, [rows][cols])
 __global__ void transpose_to_f16_kernel(const void* __restrict__ src, int src_f16, f16* __restrict__ dst, int rows, int cols) {
   __shared__ float t[32][33];
@@ -313,8 +316,9 @@ int load_weights(wis_model* m, const Loader& L) {
     {
       TensorSrc s;
       if ((rc = L.get("encoder/conv1/weight", d, (int64_t)c.n_mels * 3, &s))) break;
-      if ((rc = dalloc(m, &m->w_conv1, (size_t)d * 320))) break;     // K = 3*96 = 288 padded to 320 = 5 x 64
-      hipLaunchKernelGGL(conv_pack_kernel, dim3(blocks_for((int64_t)d * 320)), dim3(256), 0, m->st, s.p, s.f16, m->w_conv1, d, c.n_mels, 96, 320);
+      const int cc = conv1_channels(c.n_mels), k1 = conv1_k(c.n_mels);      // 80 bins: K = 3*96 = 288 padded to 320 = 5 x 64; 128: 384
+      if ((rc = dalloc(m, &m->w_conv1, (size_t)d * k1))) break;
+      hipLaunchKernelGGL(conv_pack_kernel, dim3(blocks_for((int64_t)d * k1)), dim3(256), 0, m->st, s.p, s.f16, m->w_conv1, d, c.n_mels, cc, k1);
       if ((rc = L.get("encoder/conv2/weight", d, (int64_t)d * 3, &s))) break;
       if ((rc = dalloc(m, &m->w_conv2, (size_t)d * 3 * d))) break;
       hipLaunchKernelGGL(conv_pack_kernel, dim3(blocks_for((int64_t)d * 3 * d)), dim3(256), 0, m->st, s.p, s.f16, m->w_conv2, d, d, d, 3 * d);
@@ -428,7 +432,8 @@ int alloc_buffers(wis_model* m) {
   const int d = c.d_model, H = c.n_heads, Bm = c.max_batch, T = c.n_audio_ctx, L = c.n_dec_layers;
   const int slots = Bm * c.max_beam, ctx = c.n_text_ctx;
   m->Tpad = cdiv(T, 64) * 64;
-  WIS_RET(dalloc(m, &m->img, (size_t)Bm * 3002 * 96 + 64));     // +64: the last window's zero-weighted over-read
+  const size_t img_elems = (size_t)Bm * 3002 * conv1_channels(c.n_mels) + 64;     // +64: the last window's zero-weighted over-read (80 bins)
+  WIS_RET(dalloc(m, &m->img, img_elems));
   WIS_RET(dalloc(m, &m->c1, (size_t)Bm * 3002 * d));
   WIS_RET(dalloc(m, &m->x, (size_t)Bm * T * d));
   WIS_RET(dalloc(m, &m->xn, (size_t)Bm * T * d));
@@ -452,7 +457,7 @@ int alloc_buffers(wis_model* m) {
     m->skbuf = nullptr;
     if (sk) WIS_RET(dalloc(m, &m->skbuf, sk));
   }
-  WIS_HIP_CHECK(hipMemsetAsync(m->img, 0, ((size_t)Bm * 3002 * 96 + 64) * 2, m->st));
+  WIS_HIP_CHECK(hipMemsetAsync(m->img, 0, img_elems * 2, m->st));
   WIS_HIP_CHECK(hipMemsetAsync(m->c1, 0, (size_t)Bm * 3002 * d * 2, m->st));
   WIS_HIP_CHECK(hipMemsetAsync(m->vt, 0, (size_t)Bm * H * 64 * m->Tpad * 2, m->st));
   m->kx.resize(L); m->vx.resize(L); m->kc.resize(L); m->vc.resize(L);
@@ -532,7 +537,7 @@ int alloc_buffers(wis_model* m) {
   WIS_RET(dalloc(m, &m->ts_desc, (size_t)MAX_ROWS * TS_DESC_INTS)); WIS_RET(dalloc(m, &m->d_nsp, (size_t)MAX_ROWS));
   WIS_RET(dalloc(m, &m->d_in, (size_t)Bm * WIS_N_SAMPLES));
   WIS_RET(dalloc(m, &m->d_nsamp, Bm));
-  WIS_RET(dalloc(m, &m->lm_logspec, (size_t)Bm * WIS_N_MELS * WIS_N_FRAMES));
+  WIS_RET(dalloc(m, &m->lm_logspec, (size_t)Bm * c.n_mels * WIS_N_FRAMES));
   WIS_RET(dalloc(m, &m->lm_gmax, Bm));
   WIS_RET(dalloc(m, &m->d_probs, (size_t)Bm * (c.n_lang > 0 ? c.n_lang : 1)));
   WIS_RET(dalloc(m, &m->d_prof, ((size_t)c.n_dec_layers * 8 + 2) * 16));   // + sampling kernels (tap builds)
@@ -563,14 +568,15 @@ int stage_input(wis_model* m, const float* input, int kind, int B, hipStream_t o
     int64_t* hn = reinterpret_cast<int64_t*>(m->h_pin);
     for (int b = 0; b < B; ++b) hn[b] = WIS_N_SAMPLES;
     WIS_HIP_CHECK(hipMemcpyAsync(m->d_nsamp, hn, (size_t)B * 8, hipMemcpyHostToDevice, st));
-    WIS_RET(logmel_device(m->ctx, st, m->lm_logspec, m->lm_gmax, dp, WIS_N_SAMPLES, m->d_nsamp, B, nullptr, m->img));
+    WIS_RET(logmel_device(m->ctx, st, m->lm_logspec, m->lm_gmax, dp, WIS_N_SAMPLES, m->d_nsamp, B, nullptr, m->img, m->cfg.n_mels));
   } else if (kind == WIS_IN_MEL_HOST || kind == WIS_IN_MEL_DEV) {
     const float* dm = input;
     if (kind == WIS_IN_MEL_HOST) {
-      WIS_HIP_CHECK(hipMemcpyAsync(m->d_in, input, (size_t)B * 80 * 3000 * 4, hipMemcpyHostToDevice, st));
+      WIS_HIP_CHECK(hipMemcpyAsync(m->d_in, input, (size_t)B * m->cfg.n_mels * 3000 * 4, hipMemcpyHostToDevice, st));      // d_in: B x 480000 floats
       dm = m->d_in;
     }
-    hipLaunchKernelGGL(mel_to_image_kernel, dim3(cdiv(3000, 64), B), dim3(256), 0, st, dm, m->img);
+    if (m->cfg.n_mels == 128) hipLaunchKernelGGL((mel_to_image_kernel<128, 128>), dim3(cdiv(3000, 64), B), dim3(256), 0, st, dm, m->img);
+    else hipLaunchKernelGGL((mel_to_image_kernel<80, 96>), dim3(cdiv(3000, 64), B), dim3(256), 0, st, dm, m->img);
   } else { set_error("bad input_kind %d", kind); return WIS_E_ARG; }
   return WIS_OK;
 }
@@ -579,8 +585,10 @@ int stage_input(wis_model* m, const float* input, int kind, int B, hipStream_t o
 int run_encoder(wis_model* m, int B, hipStream_t on = nullptr) {
   const wis_config_t& c = m->cfg; hipStream_t st = on ? on : m->st;
   const int d = c.d_model, H = c.n_heads, T = c.n_audio_ctx, M = B * T;
-  {  // conv1: implicit im2col over the [3002][96] image, K = 288 (+32 zero-weighted columns that read into the next row)
-    GemmP p; p.klen = 0; p.A = m->img; p.a_bs = (int64_t)3002 * 96; p.a_rs = 96; p.a_rpb = 3000; p.W = m->w_conv1; p.M = B * 3000; p.N = d; p.K = 320;
+  {  // conv1: implicit im2col over the [3002][C] image; 80 bins: C = 96, K = 288 (+32 zero-weighted columns that read into the next
+     // row); 128 bins: C = 128, K = 384
+    const int cc = conv1_channels(c.n_mels);
+    GemmP p; p.klen = 0; p.A = m->img; p.a_bs = (int64_t)3002 * cc; p.a_rs = cc; p.a_rpb = 3000; p.W = m->w_conv1; p.M = B * 3000; p.N = d; p.K = conv1_k(c.n_mels);
     WIS_RET(launch_gemm_conv1(st, p, m->b_conv1, m->c1, 3000));
   }
   {  // conv2 (stride 2) + GELU + positions -> fp32 residual stream
@@ -1000,9 +1008,9 @@ int wis_supported_compute_types(int device, char* out, size_t cap) {
 int wis_model_create(const wis_config_t* cfg, const void* arena, size_t arena_bytes, int arena_on_device,
                      const wis_tensor_t* tensors, int n_tensors, int device, wis_model_t** out) {
   if (!cfg || !arena || !tensors || !out || n_tensors <= 0) { set_error("wis_model_create: bad argument"); return WIS_E_ARG; }
-  if (cfg->d_model % 128 || cfg->d_model != cfg->n_heads * 64 || cfg->d_model > 2048 || cfg->n_mels != 80 || cfg->n_audio_ctx != 1500 ||
+  if (cfg->d_model % 128 || cfg->d_model != cfg->n_heads * 64 || cfg->d_model > 2048 || !mel_bins_supported(cfg->n_mels) || cfg->n_enc_layers < 1 || cfg->n_dec_layers < 1 || cfg->n_audio_ctx != 1500 ||
       cfg->n_text_ctx > 512 || cfg->max_batch < 1 || cfg->max_beam < 1 || cfg->max_beam > MAX_R || cfg->n_vocab < 1024) {
-    set_error("wis_model_create: unsupported config (d_model %% 128, head_dim 64, n_mels 80, n_audio_ctx 1500, max_beam <= %d)", MAX_R);
+    set_error("wis_model_create: unsupported config (d_model %% 128, head_dim 64, n_mels 80 or 128, n_audio_ctx 1500, max_beam <= %d)", MAX_R);
     return WIS_E_UNSUPPORTED;
   }
   DeviceCtx* ctx; WIS_RET(get_ctx(device, &ctx));

@@ -72,6 +72,8 @@ SYMBOLS = [
     ("wis_audio_free", None, [_fp]),
     ("wis_logmel", _i, [_i, _vp, _i64, C.POINTER(_i64), _i, _i, _vp, _i]),
     ("wis_melstream_create", _i, [_i, C.POINTER(_vp)]),
+    ("wis_logmel_n", _i, [_i, _i, _vp, _i64, C.POINTER(_i64), _i, _i, _vp, _i]),
+    ("wis_melstream_create_n", _i, [_i, _i, C.POINTER(_vp)]),
     ("wis_melstream_reset", _i, [_vp]),
     ("wis_melstream_feed", _i, [_vp, _vp, _i64]),
     ("wis_melstream_finish", _i, [_vp, _vp, C.POINTER(_vp)]),

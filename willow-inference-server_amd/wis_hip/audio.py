@@ -20,6 +20,7 @@ from . import _lib
 SAMPLE_RATE = 16000
 N_FFT = 400
 N_MELS = 80
+MEL_BINS = (80, 128)       # tiny .. large-v2 | large-v3, large-v3-turbo
 HOP_LENGTH = 160
 CHUNK_LENGTH = 30
 N_SAMPLES = CHUNK_LENGTH * SAMPLE_RATE
@@ -136,11 +137,12 @@ class MelFeatures:
 
 
 def log_mel_spectrogram(audio, n_mels: int = N_MELS, device=None):
-    """float32 [480000] (or [n, 480000]) -> MelFeatures wrapping float32 [80, 3000] (or [n, 80, 3000]).
+    """float32 [480000] (or [n, 480000]) -> MelFeatures wrapping float32 [n_mels, 3000] (or [n, n_mels, 3000]); n_mels 80 or 128.
     `device`: the GPU to run on (callers that own a model pass one of ITS replicas' devices, wis_hip.whisper.do_whisper); None =
     device 0 - the call never touches a GPU it was not pointed at.  Re-entrant: concurrent calls never share a stream or a
     buffer (csrc/logmel.hip)."""
-    assert n_mels == 80, f"Unsupported n_mels: {n_mels}"
+    if n_mels not in MEL_BINS:
+        raise ValueError(f"Unsupported n_mels: {n_mels} (80 or 128)")
     x = np.ascontiguousarray(np.asarray(audio, dtype=np.float32))
     single = x.ndim == 1
     if single:
@@ -150,9 +152,12 @@ def log_mel_spectrogram(audio, n_mels: int = N_MELS, device=None):
     _lib.require_gpu()
     device = 0 if device is None else int(device)
     n = x.shape[0]
-    out = np.empty((n, N_MELS, N_FRAMES), np.float32)
+    out = np.empty((n, n_mels, N_FRAMES), np.float32)
     ns = (C.c_int64 * n)(*([N_SAMPLES] * n))
-    _lib.check(_lib.load().wis_logmel(device, _lib.ptr(x), N_SAMPLES, ns, n, 0, _lib.ptr(out), 0))
+    if n_mels == N_MELS:
+        _lib.check(_lib.load().wis_logmel(device, _lib.ptr(x), N_SAMPLES, ns, n, 0, _lib.ptr(out), 0))
+    else:
+        _lib.check(_lib.load().wis_logmel_n(device, n_mels, _lib.ptr(x), N_SAMPLES, ns, n, 0, _lib.ptr(out), 0))
     return MelFeatures(out[0] if single else out)
 
 
@@ -160,25 +165,30 @@ class MelStream:
     """Incremental log-mel of ONE 30 s window on one GPU (C-ABI wis_melstream_*): `feed` PCM as it arrives - every
     16-frame tile whose samples are complete is transformed right away - and `finish` clamps / scales (the only step that needs
     the whole window).  Bit-identical to `log_mel_spectrogram(pad_or_trim(everything fed))`.  After `finish`, `device_ptr` is
-    the address of the f32 [80, 3000] features in HBM (valid until reset / close): `Whisper.generate_from_device` consumes it
-    without the features ever visiting the host."""
+    the address of the f32 [n_mels, 3000] features in HBM (valid until reset / close): `Whisper.generate_from_device` consumes it
+    without the features ever visiting the host.  n_mels: 80, or 128 for the large-v3 models."""
 
     # idle native handles per device: creating one costs five device allocations, a stream and a pinned block, destroying one as
     # many (synchronising) frees - milliseconds each, and a streaming session opens a window every 14 s of audio and closes it on the
     # latency path of stop().  close() therefore parks the handle here (reset) and the next MelStream on that GPU takes it over.
     _idle, _idle_lock, _IDLE_MAX = {}, threading.Lock(), 16
 
-    def __init__(self, device=0):
+    def __init__(self, device=0, n_mels=N_MELS):
         _lib.require_gpu()
-        self.device = int(device)
+        if n_mels not in MEL_BINS:
+            raise ValueError(f"Unsupported n_mels: {n_mels} (80 or 128)")
+        self.device, self.n_mels = int(device), int(n_mels)
         self._h = None
         with MelStream._idle_lock:
-            pool = MelStream._idle.get(self.device)
+            pool = MelStream._idle.get((self.device, self.n_mels))
             if pool:
                 self._h = pool.pop()
         if self._h is None:
             self._h = C.c_void_p()
-            _lib.check(_lib.load().wis_melstream_create(self.device, C.byref(self._h)))
+            if self.n_mels == N_MELS:
+                _lib.check(_lib.load().wis_melstream_create(self.device, C.byref(self._h)))
+            else:
+                _lib.check(_lib.load().wis_melstream_create_n(self.device, self.n_mels, C.byref(self._h)))
         self.device_ptr = None
 
     def feed(self, samples):
@@ -187,7 +197,7 @@ class MelStream:
             _lib.check(_lib.load().wis_melstream_feed(self._h, _lib.ptr(x), x.shape[0]))
 
     def finish(self, to_host=True):
-        out = np.empty((N_MELS, N_FRAMES), np.float32) if to_host else None
+        out = np.empty((self.n_mels, N_FRAMES), np.float32) if to_host else None
         dev = C.c_void_p()
         _lib.check(_lib.load().wis_melstream_finish(self._h, _lib.ptr(out) if to_host else None, C.byref(dev)))
         self.device_ptr = dev.value
@@ -214,7 +224,7 @@ class MelStream:
         try:
             if _lib.load().wis_melstream_reset(h) == 0:
                 with MelStream._idle_lock:
-                    pool = MelStream._idle.setdefault(self.device, [])
+                    pool = MelStream._idle.setdefault((self.device, self.n_mels), [])
                     if len(pool) < MelStream._IDLE_MAX:
                         pool.append(h)
                         return

@@ -1,7 +1,7 @@
 """Call-compatible stand-in for the slice of `ctranslate2` the reference uses:
 
     ctranslate2.models.Whisper(path, device=, compute_type=, inter_threads=, device_index=[..] | intra_threads=)
-    ctranslate2.StorageView.from_array(ndarray f32 [B, 80, 3000])
+    ctranslate2.StorageView.from_array(ndarray f32 [B, n_mels, 3000])   (n_mels 80, or 128 for large-v3 / large-v3-turbo)
     model.generate(features, [prompt] * B, beam_size=int, return_scores=False) -> results[i].sequences_ids[0]
     model.detect_language(features) -> [[("<|xx|>", prob), ...], ...]
     ctranslate2.get_supported_compute_types(device)
@@ -21,7 +21,6 @@ import numpy as np
 
 from . import _lib, weights as W
 from .batching import MicroBatcher
-from .languages import LANGUAGE_CODES
 
 
 def get_supported_compute_types(device="cuda", device_index=0):
@@ -60,24 +59,36 @@ class WhisperGenerationResult:
 
 
 class _Replica:
-    def __init__(self, handle, device):
+    def __init__(self, handle, device, n_mels=W.N_MELS):
         self.handle, self.device = handle, device
+        self.mel_bytes = n_mels * 3000 * 4      # one utterance's features
         self.lock = threading.Lock()
         self.inflight = 0
         self.stage = None           # device block for batches of device-resident features (lazy)
 
 
-def make_config(a, max_batch, max_beam, suppress_ids=None, suppress_begin=None, lang_ids=None, n_vocab=None, weight_bits=16):
-    sup = np.asarray(W.SUPPRESS_IDS if suppress_ids is None else suppress_ids, np.int32)
-    beg = np.asarray(W.SUPPRESS_IDS_BEGIN if suppress_begin is None else suppress_begin, np.int32)
-    lang = np.asarray(W.LANG_IDS if lang_ids is None else lang_ids, np.int32)
+def special_tokens_for(a, special=None, lang_ids=None):
+    """The model's special-id table (weights.SpecialTokens) from its vocabulary size, with the ids the checkpoint states on top."""
+    ov = dict(special or {})
+    if lang_ids is not None and "lang_ids" not in ov:
+        ov["lang_ids"] = list(lang_ids)
+    return W.special_tokens(a["n_vocab"], ov)
+
+
+def make_config(a, max_batch, max_beam, suppress_ids=None, suppress_begin=None, lang_ids=None, n_vocab=None, weight_bits=16, special=None):
+    """special: a weights.SpecialTokens (default: the table of the vocabulary a["n_vocab"]); the 51865 defaults are the module constants."""
+    st = special if isinstance(special, W.SpecialTokens) else special_tokens_for(a, special, lang_ids)
+    sup = np.asarray(st.default_suppress_ids() if suppress_ids is None else suppress_ids, np.int32)
+    beg = np.asarray([220, st.eot] if suppress_begin is None else suppress_begin, np.int32)
+    lang = np.asarray(st.lang_ids if lang_ids is None else lang_ids, np.int32)
     cfg = _lib.Config()
     cfg.d_model, cfg.n_heads = a["d_model"], a["n_heads"]
-    cfg.n_enc_layers = cfg.n_dec_layers = a["n_layers"]
+    cfg.n_enc_layers = a.get("n_enc_layers", a["n_layers"])
+    cfg.n_dec_layers = a.get("n_dec_layers", a["n_layers"])
     cfg.n_vocab = n_vocab or a["n_vocab"]
     cfg.n_audio_ctx, cfg.n_text_ctx, cfg.n_mels = a["n_audio_ctx"], a["n_text_ctx"], a["n_mels"]
     cfg.max_batch, cfg.max_beam = max_batch, max_beam
-    cfg.eot, cfg.sot, cfg.no_timestamps, cfg.no_speech = W.EOT, W.SOT, W.NO_TIMESTAMPS, W.NO_SPEECH
+    cfg.eot, cfg.sot, cfg.no_timestamps, cfg.no_speech = st.eot, st.sot, st.notimestamps, st.nospeech
     cfg.suppress_ids = sup.ctypes.data_as(C.POINTER(C.c_int32)); cfg.n_suppress = len(sup)
     cfg.suppress_ids_begin = beg.ctypes.data_as(C.POINTER(C.c_int32)); cfg.n_suppress_begin = len(beg)
     cfg.lang_ids = lang.ctypes.data_as(C.POINTER(C.c_int32)); cfg.n_lang = len(lang)
@@ -228,15 +239,17 @@ MAX_PROMPT = 16            # wis_generate: prompt tokens per utterance
 MAX_HYPOTHESES = 24        # csrc/kernels.hpp MAX_HYP: finished hypotheses an utterance's search can hold
 
 
-def timestamp_prompt(prompt):
+def timestamp_prompt(prompt, special=None):
     """True when `prompt` asks for timestamps: from <|startoftranscript|> on it holds only the start sequence's special tokens
     (language, task; ids in [<|endoftext|>, <|notimestamps|>)) and no <|notimestamps|> - what CTranslate2 decodes under Whisper's
     timestamp rules.  A prompt without <|startoftranscript|>, with <|notimestamps|>, or with text or timestamp tokens after its start
-    sequence (a decoder prefix) keeps the plain search the engine has always run for it."""
+    sequence (a decoder prefix) keeps the plain search the engine has always run for it.  special: the model's SpecialTokens
+    (default: the 51865-token vocabulary)."""
     p = [int(t) for t in prompt]
-    if W.SOT not in p:
+    sot, eot, nts = (W.SOT, W.EOT, W.NO_TIMESTAMPS) if special is None else (special.sot, special.eot, special.notimestamps)
+    if sot not in p:
         return False
-    return all(W.EOT <= t < W.NO_TIMESTAMPS for t in p[p.index(W.SOT):])
+    return all(eot <= t < nts for t in p[p.index(sot):])
 
 
 def _check_patience(beam_size, patience):
@@ -254,9 +267,6 @@ def _capacity(max_batch, key):
     return max(1, min(max_batch, MAX_DECODER_ROWS // max(beam, 1), MAX_DECODER_ROWS // max(P, 1)))
 
 
-_MEL_BYTES = 80 * 3000 * 4
-
-
 def _run_batch(replica, key, rows):
     P, beam, max_new, lp, patience, suppress_blank, suppress_default, fixed_new, kind = key[:9]
     draft = key[9] if len(key) > 9 else None          # (a drafted utterance has a key of its own: it never shares a device batch)
@@ -272,11 +282,12 @@ def _run_batch(replica, key, rows):
             if len(rows) == 1:
                 ptr = int(rows[0][0])
             else:
-                if replica.stage is None or replica.stage.nbytes < len(rows) * _MEL_BYTES:
-                    replica.stage = _lib.DevBuf(max(len(rows), 8) * _MEL_BYTES, replica.device)
+                mb = replica.mel_bytes
+                if replica.stage is None or replica.stage.nbytes < len(rows) * mb:
+                    replica.stage = _lib.DevBuf(max(len(rows), 8) * mb, replica.device)
                 lib = _lib.load()
                 for i, (src, _) in enumerate(rows):
-                    _lib.check(lib.wis_dev_copy_peer(replica.device, C.c_void_p(replica.stage.ptr.value + i * _MEL_BYTES), replica.device, C.c_void_p(int(src)), _MEL_BYTES))
+                    _lib.check(lib.wis_dev_copy_peer(replica.device, C.c_void_p(replica.stage.ptr.value + i * mb), replica.device, C.c_void_p(int(src)), mb))
                 ptr = replica.stage.ptr.value
             return _generate_chunk(replica, len(rows), prompts, P, beam, max_new, lp, patience, suppress_blank, suppress_default, fixed_new, kind, device_ptr=ptr,
                                    draft=dr, want_traj=want_traj, **tsk)
@@ -308,6 +319,7 @@ class Whisper:
         if weights is None:
             weights, arch, cfg = self._load(model_path)
         self.arch, self.decode_config = arch, cfg
+        self.special = special_tokens_for(arch, cfg.get("special"), cfg.get("lang_ids"))
         devs = list(device_index) if isinstance(device_index, (list, tuple)) else [int(device_index)]
         if not 1 <= int(max_batch) <= MAX_DECODER_ROWS:
             raise ValueError(f"max_batch={max_batch}: a device batch holds 1..{MAX_DECODER_ROWS} utterances")
@@ -315,8 +327,8 @@ class Whisper:
             raise ValueError(f"max_beam={max_beam}: the engine decodes with beam sizes 1..{MAX_BEAM}")
         arena, index = W.build_arena(weights)
         kw = dict(suppress_ids=cfg.get("suppress_ids"), suppress_begin=cfg.get("suppress_ids_begin"), lang_ids=cfg.get("lang_ids"),
-                  weight_bits=8 if self.compute_type == "int8_float16" else 16)
-        self._replicas = [_Replica(h, d) for h, d in zip(create_replicas(arch, arena, index, devs, max_batch, max_beam, **kw), devs)]
+                  weight_bits=8 if self.compute_type == "int8_float16" else 16, special=self.special)
+        self._replicas = [_Replica(h, d, arch["n_mels"]) for h, d in zip(create_replicas(arch, arena, index, devs, max_batch, max_beam, **kw), devs)]
         # CTranslate2's `inter_threads` = batches a model runs in parallel (reference main.py:341-355 passes ctranslate2_threads).  Here:
         # replicas PER GPU that share one weight copy (wis_model_clone) and run their device batches concurrently on their own
         # streams - a decode chain is latency-bound and leaves most of the chip idle, a second batch in flight fills it.  The count is
@@ -325,7 +337,7 @@ class Whisper:
         per_dev = max(1, min(int(inter_threads) if inter_threads else 1, per_dev))
         for r in list(self._replicas):
             for _ in range(per_dev - 1):
-                self._replicas.append(_Replica(clone_handle(r.handle), r.device))
+                self._replicas.append(_Replica(clone_handle(r.handle), r.device, arch["n_mels"]))
         self.max_batch, self.max_beam = max_batch, max_beam
         self._pick = threading.Lock()
         # concurrent generate() calls coalesce into device batches, one worker per GPU replica (wis_hip/batching.py)
@@ -338,7 +350,8 @@ class Whisper:
         self = cls.__new__(cls)
         self.compute_type = "float16"
         self.arch, self.decode_config = arch, decode_config or {}
-        self._replicas = [_Replica(h, d) for h, d in handles]
+        self.special = special_tokens_for(arch, self.decode_config.get("special"), self.decode_config.get("lang_ids"))
+        self._replicas = [_Replica(h, d, arch["n_mels"]) for h, d in handles]
         self.max_batch, self.max_beam = max_batch, max_beam
         self._pick = threading.Lock()
         self._batcher = MicroBatcher(self._replicas, _run_batch, lambda key: _capacity(max_batch, key))
@@ -382,8 +395,12 @@ class Whisper:
         with self._pick:
             r.inflight -= 1
 
-    @staticmethod
-    def _features(features, input_kind=_lib.WIS_IN_MEL_HOST):
+    @property
+    def n_mels(self):
+        return int((getattr(self, "arch", None) or {}).get("n_mels", W.N_MELS))
+
+    def _features(self, features, input_kind=_lib.WIS_IN_MEL_HOST):
+        nm = self.n_mels
         a = features.array if isinstance(features, StorageView) else np.asarray(features)
         if a.dtype != np.float32:
             a = a.astype(np.float32)
@@ -392,8 +409,8 @@ class Whisper:
             if a.ndim != 2 or a.shape[1] != _lib.N_SAMPLES:
                 raise ValueError(f"PCM input must be [batch, {_lib.N_SAMPLES}] float32 (pad_or_trim'ed 30 s windows), got {a.shape}")
         elif input_kind == _lib.WIS_IN_MEL_HOST:
-            if a.ndim != 3 or a.shape[1:] != (80, 3000):
-                raise ValueError(f"features must be [batch, 80, 3000] float32, got {a.shape}")
+            if a.ndim != 3 or a.shape[1:] != (nm, 3000):
+                raise ValueError(f"features must be [batch, {nm}, 3000] float32 for this model ({nm} mel bins), got {a.shape}")
         else:
             raise ValueError("the Python face takes host arrays (WIS_IN_MEL_HOST or WIS_IN_PCM_HOST)")
         return a
@@ -426,7 +443,7 @@ class Whisper:
         if not 1 <= P <= MAX_PROMPT:
             raise ValueError(f"prompt length {P} outside 1..{MAX_PROMPT}")
         _check_patience(beam_size, patience)
-        ts_rows = [timestamp_prompt(p) for p in prompts]
+        ts_rows = [timestamp_prompt(p, getattr(self, "special", None)) for p in prompts]
         timestamps = any(ts_rows)
         if timestamps and not all(ts_rows):
             raise ValueError("prompts of one call must all ask for timestamps (a start sequence without <|notimestamps|>) or none")
@@ -482,7 +499,7 @@ class Whisper:
 
     def generate_from_device(self, device, mel_device_ptr, prompt, *, beam_size=5, max_length=448, length_penalty=1, patience=1,
                              suppress_blank=True, fixed_new_tokens=0, replica=None, draft_tokens=None, draft_trajectory=None, return_trajectory=False):
-        """One utterance whose log-mel features ALREADY live in HBM on `device` (f32 [80][3000] at `mel_device_ptr`, e.g. an
+        """One utterance whose log-mel features ALREADY live in HBM on `device` (f32 [n_mels][3000] at `mel_device_ptr`, e.g. an
         audio.MelStream after finish()): WIS_IN_MEL_DEV - nothing is staged through the host.  Goes through the micro-batcher bound
         to that DEVICE: any replica of the GPU can read the features, so concurrent windows of several streaming sessions on one GPU
         coalesce into one device batch like REST requests do, whatever replica each session holds (round 4 bound a window to the
@@ -509,7 +526,7 @@ class Whisper:
     def detect_language(self, features, input_kind=_lib.WIS_IN_MEL_HOST):
         mel = self._features(features, input_kind)
         B = mel.shape[0]
-        n_lang = len(W.LANG_IDS)
+        n_lang, codes = len(self.special.lang_ids), self.special.lang_codes
         out = []
         r = self._acquire()
         try:
@@ -522,7 +539,7 @@ class Whisper:
                                                                probs.ctypes.data_as(C.POINTER(C.c_float))))
                     for row in probs:
                         order = np.argsort(-row, kind="stable")
-                        out.append([(f"<|{LANGUAGE_CODES[i]}|>", float(row[i])) for i in order])
+                        out.append([(f"<|{codes[i]}|>", float(row[i])) for i in order])
         finally:
             self._release(r)
         return out

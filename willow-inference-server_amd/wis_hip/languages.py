@@ -11,3 +11,14 @@ LANGUAGE_CODES = tuple((
 assert len(LANGUAGE_CODES) == 99 and len(set(LANGUAGE_CODES)) == 99
 # membership test target of `check_language` (same truth value as `language in LANGUAGES` of the reference)
 LANGUAGES = frozenset(LANGUAGE_CODES)
+# large-v3 / large-v3-turbo (51866 tokens) add Cantonese after <|su|>: <|yue|> = 50358
+LANGUAGE_CODES_V3 = LANGUAGE_CODES + ("yue",)
+
+
+def language_codes(n_lang):
+    """The language codes of a vocabulary with n_lang language tokens, in token-id order: 99 (tiny .. large-v2) or 100 (large-v3)."""
+    if n_lang == len(LANGUAGE_CODES_V3):
+        return LANGUAGE_CODES_V3
+    if n_lang == len(LANGUAGE_CODES):
+        return LANGUAGE_CODES
+    raise ValueError(f"{n_lang} language tokens: the multilingual Whisper vocabularies hold 99 or 100")

@@ -34,7 +34,7 @@ from fastapi.middleware.cors import CORSMiddleware
 from fastapi.responses import JSONResponse, PlainTextResponse
 
 from .settings import get_api_settings
-from .whisper import InvalidAudio, WhisperModels, check_language, do_whisper
+from .whisper import InvalidAudio, WhisperModels, check_model_language, do_whisper
 
 logger = logging.getLogger("infer")
 
@@ -185,7 +185,7 @@ def create_app(models=None, settings=None, max_workers=None, sv=None):
             p = params(request)
         except BadRequest as e:
             return bad(str(e))
-        if p["force_language"] and not check_language(p["force_language"]):
+        if p["force_language"] and not check_model_language(p["force_language"], p["model"]):
             return bad("Invalid force_language")
         try:
             data = parse_multipart(await request.body(), request.headers.get("content-type"))
@@ -211,7 +211,7 @@ def create_app(models=None, settings=None, max_workers=None, sv=None):
             return bad(str(e))
         q = request.query_params
         save_audio, stats, voice_auth = _as_bool(q.get("save_audio"), False), _as_bool(q.get("stats"), False), _as_bool(q.get("voice_auth"), False)
-        if p["force_language"] and not check_language(p["force_language"]):
+        if p["force_language"] and not check_model_language(p["force_language"], p["model"]):
             return bad("Invalid force_language")
         if voice_auth and not s.support_sv:
             return bad("voice_auth (speaker verification) is disabled (support_sv)")

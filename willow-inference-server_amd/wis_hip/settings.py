@@ -25,6 +25,9 @@ class APISettings:
     preload_whisper_model_small: bool = True
     preload_whisper_model_medium: bool = True
     preload_whisper_model_large: bool = True
+    # large-v3 / large-v3-turbo (128 mel bins, 51866 tokens): only on request - preload_all_models does not pull them in
+    preload_whisper_model_large_v3: bool = False
+    preload_whisper_model_large_v3_turbo: bool = False
     sv_memory_threshold: int = 5798205849
     support_chunking: bool = True
     chunking_memory_threshold: int = 3798205849

@@ -26,8 +26,8 @@ from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
 
-from . import audio, ctranslate2, weights as W
-from .whisper import InvalidAudio, WhisperResult, _Tokenizer, check_language, default_models
+from . import audio, ctranslate2
+from .whisper import InvalidAudio, WhisperResult, check_language, default_models, model_special_tokens
 
 _STEP = audio.chunk_len - audio.stride_left - audio.stride_right     # 14 s between window starts
 
@@ -38,9 +38,9 @@ class _IncrementalFront:
     schedule (starts 0, 14, 28, ... s).  When a window is complete only its tail tiles and the clamp are left to compute, and the
     features are already in HBM on the replica's GPU (generate_from_device: nothing is staged through the host)."""
 
-    def __init__(self, device):
-        self.device = device
-        self.short = audio.MelStream(device)
+    def __init__(self, device, n_mels=audio.N_MELS):
+        self.device, self.n_mels = device, n_mels
+        self.short = audio.MelStream(device, n_mels)
         self.windows = {}             # window start (samples) -> MelStream
         self.n = 0
 
@@ -58,7 +58,7 @@ class _IncrementalFront:
                 if start + audio.chunk_len > n0:           # window [start, start + 22 s) overlaps the new samples
                     st = self.windows.get(start)
                     if st is None:
-                        st = self.windows[start] = audio.MelStream(self.device)
+                        st = self.windows[start] = audio.MelStream(self.device, self.n_mels)
                         if n0 > start:                     # opened late (cannot happen when fed from the beginning)
                             raise RuntimeError("incremental front-end must see the recording from its first sample")
                     lo, hi = max(start, n0), min(start + audio.chunk_len, n1)
@@ -84,9 +84,10 @@ class StreamingSession:
         self.beam_size = s.beam_size if beam_size is None else beam_size
         self.detect_language, self.force_language = detect_language, force_language
         self.fixed_new_tokens = fixed_new_tokens
-        if force_language and not check_language(force_language):
-            raise ValueError(f"unsupported language {force_language!r}")
         self._whisper = self.models.get(model)
+        self._special = model_special_tokens(self._whisper)
+        if force_language and not check_language(force_language, self._special):
+            raise ValueError(f"unsupported language {force_language!r}")
         self._chunks, self._n = [], 0   # PCM as it arrived; consolidated lazily (_audio) when a window is cut, not once per frame
         self._lock = threading.Lock()
         self._pool = ThreadPoolExecutor(max_workers=2, thread_name_prefix="wis-stream")
@@ -105,7 +106,7 @@ class StreamingSession:
         self.front_windows = 0        # windows whose features came from the incremental front-end
         # the session's GPU: the least-loaded replica now, held (counted in its load) until close()
         self._replica = self._whisper.acquire_replica() if incremental else None
-        self._front = _IncrementalFront(self._replica.device) if incremental else None
+        self._front = _IncrementalFront(self._replica.device, getattr(self._whisper, "n_mels", audio.N_MELS)) if incremental else None
 
     def _audio(self):
         """Everything received so far as one array (lock held).  The chunk list collapses into that array, so the cost is paid
@@ -139,8 +140,9 @@ class StreamingSession:
 
     # ---- scheduling --------------------------------------------------------------------------------------------------
     def _prompt(self, language):
-        task_id = W.TRANSLATE if self.task == "translate" else W.TRANSCRIBE
-        return [W.SOT, _Tokenizer.language_token_id(language), task_id, W.NO_TIMESTAMPS]
+        st = self._special
+        task_id = st.translate if self.task == "translate" else st.transcribe
+        return [st.sot, st.language_token_id(language), task_id, st.notimestamps]
 
     def _detect(self, first_window):
         """What do_whisper does on `mel_features[0:1]` (main.py:637-643): language of the FIRST window only."""
@@ -152,7 +154,7 @@ class StreamingSession:
             language = res[0][0][0].strip("<|>")
         elif self.force_language:
             language = self.force_language
-        if not check_language(language):
+        if not check_language(language, self._special):
             raise ValueError(f"unsupported language {language!r}")
         return language
 

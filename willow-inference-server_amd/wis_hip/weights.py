@@ -18,18 +18,23 @@ from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
 
-# size -> (d_model, layers (enc = dec), heads); "large" is large-v2 (utils.sh:264-271)
+# size -> (d_model, encoder layers, decoder layers, heads, mel bins, vocabulary); "large" is large-v2 (utils.sh:264-271)
 ARCH = {
-    "tiny": (384, 4, 6),
-    "base": (512, 6, 8),
-    "small": (768, 12, 12),
-    "medium": (1024, 24, 16),
-    "large": (1280, 32, 20),
+    "tiny": (384, 4, 4, 6, 80, 51865),
+    "base": (512, 6, 6, 8, 80, 51865),
+    "small": (768, 12, 12, 12, 80, 51865),
+    "medium": (1024, 24, 24, 16, 80, 51865),
+    "large": (1280, 32, 32, 20, 80, 51865),
+    "large-v3": (1280, 32, 32, 20, 128, 51866),
+    "large-v3-turbo": (1280, 32, 4, 20, 128, 51866),
 }
 N_VOCAB = 51865
+N_VOCAB_EN = 51864         # the English-only (.en) models: not served
+N_VOCAB_V3 = 51866         # large-v3 / large-v3-turbo: one more language (<|yue|>), every id from <|translate|> up moves by one
 N_AUDIO_CTX = 1500
 N_TEXT_CTX = 448
 N_MELS = 80
+MEL_BINS = (80, 128)
 
 # special ids of the multilingual vocabulary
 EOT, SOT, TRANSLATE, TRANSCRIBE, NO_SPEECH, NO_TIMESTAMPS = 50257, 50258, 50358, 50359, 50362, 50363
@@ -44,22 +49,130 @@ SUPPRESS_IDS = [1, 2, 7, 8, 9, 10, 14, 25, 26, 27, 28, 29, 31, 58, 59, 60, 61, 6
 SUPPRESS_IDS_BEGIN = [220, EOT]
 
 
+class SpecialTokens:
+    """The special ids of one model's vocabulary.  openai-whisper's multilingual layout: <|endoftext|>, <|startoftranscript|>, one
+    token per language, then <|translate|>, <|transcribe|>, <|startoflm|>, <|startofprev|>, <|nospeech|>, <|notimestamps|> and the
+    timestamps from <|0.00|> (timestamp_begin) on.  n_lang = n_vocab - 51765 - 1: 99 languages for 51865 tokens (the module
+    constants above), 100 for large-v3's 51866 (<|yue|> last).  `overrides` (ids the checkpoint itself states) take priority."""
+
+    NAMES = ("eot", "sot", "translate", "transcribe", "startoflm", "startofprev", "nospeech", "notimestamps", "timestamp_begin")
+
+    def __init__(self, n_vocab, overrides=None):
+        n_vocab = int(n_vocab)
+        if n_vocab == N_VOCAB_EN:
+            raise ValueError(f"vocabulary of {n_vocab} tokens: English-only Whisper models (.en) are not supported, only the "
+                             f"multilingual vocabularies ({N_VOCAB}, {N_VOCAB_V3})")
+        from .languages import language_codes
+        # (any other size - the truncated vocabularies of small test models - keeps the 51865 layout)
+        n_lang = n_vocab - 51765 - 1 if n_vocab == N_VOCAB_V3 else len(LANG_IDS)
+        self.n_vocab = n_vocab
+        self.eot, self.sot = EOT, SOT
+        self.lang_ids = list(range(SOT + 1, SOT + 1 + n_lang))
+        self.translate = SOT + 1 + n_lang
+        self.transcribe, self.startoflm, self.startofprev = self.translate + 1, self.translate + 2, self.translate + 3
+        self.nospeech, self.notimestamps = self.translate + 4, self.translate + 5
+        self.timestamp_begin = self.notimestamps + 1
+        codes = language_codes(n_lang)
+        for k, v in (overrides or {}).items():
+            if k == "lang_ids":
+                v = sorted(int(t) for t in v)
+                if v != self.lang_ids:
+                    codes = None
+                self.lang_ids = v
+            elif k == "lang_codes":
+                codes = tuple(v)
+            elif k in self.NAMES:
+                setattr(self, k, int(v))
+            else:
+                raise KeyError(f"unknown special token {k!r}")
+            if k == "notimestamps" and "timestamp_begin" not in overrides:
+                self.timestamp_begin = self.notimestamps + 1
+        # language names in id order: the standard table when the ids are the standard ones, else what the checkpoint named
+        self.lang_codes = tuple(codes) if codes is not None and len(codes) == len(self.lang_ids) else language_codes(len(self.lang_ids))
+
+    def as_dict(self):
+        return dict({k: getattr(self, k) for k in self.NAMES}, lang_ids=list(self.lang_ids), n_vocab=self.n_vocab)
+
+    def __repr__(self):
+        return f"SpecialTokens({self.as_dict()})"
+
+    @property
+    def special_ids(self):
+        """every id from <|endoftext|> up (the id-only tokenizer's all_special_ids)"""
+        return list(range(self.eot, self.n_vocab))
+
+    def language_token_id(self, code):
+        try:
+            return self.lang_ids[self.lang_codes.index(code)]
+        except ValueError:
+            raise ValueError(f"unsupported language {code!r} for this model ({len(self.lang_ids)} languages)") from None
+
+    def default_suppress_ids(self):
+        """CT2's suppress_ids for this vocabulary: the text-token part of SUPPRESS_IDS and the special part (<|startoftranscript|>,
+        <|translate|> ... <|nospeech|>) at this vocabulary's ids.  The 51865 list is SUPPRESS_IDS itself."""
+        text = [t for t in SUPPRESS_IDS if t < EOT]
+        return text + [self.sot, self.translate, self.transcribe, self.startoflm, self.startofprev, self.nospeech]
+
+
+def special_tokens(n_vocab, overrides=None):
+    return SpecialTokens(n_vocab, overrides)
+
+
+def special_tokens_from_tokenizer_json(path):
+    """Special ids a checkpoint's tokenizer.json names (added tokens by content) -> SpecialTokens overrides."""
+    with open(path, "r", encoding="utf-8") as f:
+        tj = json.load(f)
+    by = {t["content"]: int(t["id"]) for t in tj.get("added_tokens", [])}
+    names = {"<|endoftext|>": "eot", "<|startoftranscript|>": "sot", "<|translate|>": "translate", "<|transcribe|>": "transcribe",
+             "<|startoflm|>": "startoflm", "<|startofprev|>": "startofprev", "<|nospeech|>": "nospeech", "<|nocaptions|>": "nospeech",
+             "<|notimestamps|>": "notimestamps", "<|0.00|>": "timestamp_begin"}
+    out = {names[c]: i for c, i in by.items() if c in names}
+    if "sot" in out and "translate" in out:
+        langs = sorted((i, c[2:-2]) for c, i in by.items() if out["sot"] < i < out["translate"] and c.startswith("<|") and c.endswith("|>"))
+        if langs:
+            out["lang_ids"] = [i for i, _ in langs]
+            out["lang_codes"] = [c for _, c in langs]
+    return out
+
+
+def special_overrides_from_generation_config(gen):
+    """HF generation_config.json -> SpecialTokens overrides (lang_to_id, task_to_id, no_timestamps_token_id, ...)."""
+    out = {}
+    if "lang_to_id" in gen:
+        langs = sorted((int(v), k.strip("<|>")) for k, v in gen["lang_to_id"].items())
+        out["lang_ids"] = [i for i, _ in langs]
+        out["lang_codes"] = [c for _, c in langs]
+    task = gen.get("task_to_id") or {}
+    for k in ("translate", "transcribe"):
+        if k in task:
+            out[k] = int(task[k])
+    for key, name in (("no_timestamps_token_id", "notimestamps"), ("decoder_start_token_id", "sot"), ("prev_sot_token_id", "startofprev")):
+        if gen.get(key) is not None:
+            out[name] = int(gen[key])
+    eos = gen.get("eos_token_id")
+    if isinstance(eos, int):
+        out["eot"] = eos
+    return out
+
+
 def arch(size):
     if size == "large-v2":
         size = "large"
-    d, L, H = ARCH[size]
-    return dict(size=size, d_model=d, n_layers=L, n_heads=H, n_vocab=N_VOCAB, n_audio_ctx=N_AUDIO_CTX, n_text_ctx=N_TEXT_CTX, n_mels=N_MELS)
+    d, Le, Ld, H, nm, V = ARCH[size]
+    return dict(size=size, d_model=d, n_layers=Ld, n_enc_layers=Le, n_dec_layers=Ld, n_heads=H, n_vocab=V, n_audio_ctx=N_AUDIO_CTX,
+                n_text_ctx=N_TEXT_CTX, n_mels=nm)
 
 
-def tensor_shapes(d, L, n_vocab=N_VOCAB, n_text_ctx=N_TEXT_CTX):
-    """name -> (shape, kind) in CTranslate2 WhisperSpec naming; kind in {w, b, g, beta, emb}."""
+def tensor_shapes(d, L, n_vocab=N_VOCAB, n_text_ctx=N_TEXT_CTX, n_mels=N_MELS, n_dec_layers=None):
+    """name -> (shape, kind) in CTranslate2 WhisperSpec naming; kind in {w, b, g, beta, emb}.  L: encoder layers (and decoder
+    layers unless n_dec_layers says otherwise)."""
     t = {}
-    t["encoder/conv1/weight"] = ((d, N_MELS, 3), "w")
+    t["encoder/conv1/weight"] = ((d, n_mels, 3), "w")
     t["encoder/conv1/bias"] = ((d,), "b")
     t["encoder/conv2/weight"] = ((d, d, 3), "w")
     t["encoder/conv2/bias"] = ((d,), "b")
     t["encoder/position_encodings/encodings"] = ((N_AUDIO_CTX, d), "pos")     # fixed sinusoids, float32
-    for side, n in (("encoder", L), ("decoder", L)):
+    for side, n in (("encoder", L), ("decoder", L if n_dec_layers is None else n_dec_layers)):
         for l in range(n):
             p = f"{side}/layer_{l}/"
             t[p + "self_attention/layer_norm/gamma"] = ((d,), "g")
@@ -98,12 +211,16 @@ def sinusoids(length=N_AUDIO_CTX, channels=1280):
     return np.concatenate([np.sin(t), np.cos(t)], axis=1).astype(np.float32)
 
 
-def synthetic_weights(size, seed=1234, std=0.02, emb_std=None, ln_jitter=0.0, threads=8, n_vocab=N_VOCAB):
+def _arch_shapes(a, n_vocab=None):
+    return tensor_shapes(a["d_model"], a["n_enc_layers"], a["n_vocab"] if n_vocab is None else n_vocab, N_TEXT_CTX, a["n_mels"], a["n_dec_layers"])
+
+
+def synthetic_weights(size, seed=1234, std=0.02, emb_std=None, ln_jitter=0.0, threads=8, n_vocab=None):
     """Deterministic synthetic weights (f16) for `size`; each tensor has its own stream so generation order and
-    threading do not matter.  K-projection bias is zero (Whisper's k_proj has no bias)."""
+    threading do not matter.  K-projection bias is zero (Whisper's k_proj has no bias).  n_vocab: the size's own by default."""
     a = arch(size)
-    d, L = a["d_model"], a["n_layers"]
-    shapes = tensor_shapes(d, L, n_vocab)
+    d = a["d_model"]
+    shapes = _arch_shapes(a, n_vocab)
     emb_std = std if emb_std is None else emb_std
 
     def gen(item):
@@ -146,9 +263,9 @@ def arena_layout(shapes_dtypes):
     return index, off
 
 
-def synthetic_layout(size, n_vocab=N_VOCAB):
+def synthetic_layout(size, n_vocab=None):
     a = arch(size)
-    shapes = tensor_shapes(a["d_model"], a["n_layers"], n_vocab)
+    shapes = _arch_shapes(a, n_vocab)
     return arena_layout([(n, s, np.float32 if k == "pos" else np.float16) for n, (s, k) in shapes.items()])
 
 
@@ -377,32 +494,51 @@ def load_hf_dir(path):
     if os.path.exists(gj):
         with open(gj) as f:
             gen = json.load(f)
+    a = arch_from_weights(w, hc.get("decoder_attention_heads"))
+    # special ids: the vocabulary's layout, then what the tokenizer names, then what the generation config states
+    ov = {}
+    if os.path.exists(os.path.join(path, "tokenizer.json")):
+        ov.update(special_tokens_from_tokenizer_json(os.path.join(path, "tokenizer.json")))
+    ov.update(special_overrides_from_generation_config(gen))
+    st = special_tokens(a["n_vocab"], ov)
     cfg = {}
+    if ov:
+        cfg["special"] = ov
     sup = gen.get("suppress_tokens", hc.get("suppress_tokens"))
     if sup:
         # CT2's converter adds <|translate|>, <|transcribe|> handling through the prompt; the released WIS models carry
         # them in suppress_ids - keep whatever the checkpoint says and add the two task tokens
-        cfg["suppress_ids"] = sorted(set(int(t) for t in sup) | {TRANSLATE, TRANSCRIBE})
+        cfg["suppress_ids"] = sorted(set(int(t) for t in sup) | {st.translate, st.transcribe})
     beg = gen.get("begin_suppress_tokens", hc.get("begin_suppress_tokens"))
     if beg:
         cfg["suppress_ids_begin"] = [int(t) for t in beg]
     if "lang_to_id" in gen:
         cfg["lang_ids"] = sorted(int(v) for v in gen["lang_to_id"].values())
-    return w, arch_from_weights(w, hc.get("decoder_attention_heads")), cfg
+    return w, a, cfg
+
+
+def _n_layers(w, side):
+    p = f"{side}/layer_"
+    return 1 + max(int(k.split("/")[1][len("layer_"):]) for k in w if k.startswith(p) and k.split("/")[1][len("layer_"):].isdigit())
 
 
 def arch_from_weights(w, n_heads=None):
+    """Geometry of a weight set: encoder and decoder depths are counted separately (large-v3-turbo: 32 / 4, distil-large: 32 / 2)
+    and the mel bins are read from conv1.  `n_layers` is the decoder depth."""
     d = w["decoder/embeddings/weight"].shape[1]
-    L = 1 + max(int(k.split("/")[1][len("layer_"):]) for k in w if k.startswith("decoder/layer_") and k.split("/")[1][len("layer_"):].isdigit())
+    Le, Ld = _n_layers(w, "encoder"), _n_layers(w, "decoder")
     H = n_heads or d // 64
     if d % 64 or H * 64 != d:
         raise ValueError(f"unsupported Whisper geometry d_model={d}, heads={H}: the engine is built for head_dim 64")
-    if w["encoder/conv1/weight"].shape[1] != N_MELS:
-        raise ValueError(f"{w['encoder/conv1/weight'].shape[1]} mel bins: only the 80-bin models WIS serves are supported")
-    size = next((k for k, v in ARCH.items() if v == (d, L, H)), f"custom-{d}x{L}")
-    return dict(size=size, d_model=d, n_layers=L, n_heads=H, n_vocab=int(w["decoder/embeddings/weight"].shape[0]),
+    nm = int(w["encoder/conv1/weight"].shape[1])
+    if nm not in MEL_BINS:
+        raise ValueError(f"{nm} mel bins: only the 80-bin (tiny .. large-v2) and 128-bin (large-v3) models are supported")
+    V = int(w["decoder/embeddings/weight"].shape[0])
+    special_tokens(V)                    # refuses the English-only vocabularies
+    size = next((k for k, v in ARCH.items() if v == (d, Le, Ld, H, nm, V)), f"custom-{d}x{Le}x{Ld}")
+    return dict(size=size, d_model=d, n_layers=Ld, n_enc_layers=Le, n_dec_layers=Ld, n_heads=H, n_vocab=V,
                 n_audio_ctx=int(w["encoder/position_encodings/encodings"].shape[0]),
-                n_text_ctx=int(w["decoder/position_encodings/encodings"].shape[0]), n_mels=N_MELS)
+                n_text_ctx=int(w["decoder/position_encodings/encodings"].shape[0]), n_mels=nm)
 
 
 def load_model_dir(path):
@@ -423,6 +559,15 @@ def load_model_dir(path):
             with open(cj) as f:
                 cj = json.load(f)
             cfg = {k: cj[k] for k in ("suppress_ids", "suppress_ids_begin", "lang_ids") if k in cj}
+        ov = {}
+        if os.path.exists(os.path.join(path, "tokenizer.json")):
+            ov.update(special_tokens_from_tokenizer_json(os.path.join(path, "tokenizer.json")))
+        if "lang_ids" in cfg:
+            ov["lang_ids"] = cfg["lang_ids"]
+            if len(ov.get("lang_codes", ())) != len(cfg["lang_ids"]):
+                ov.pop("lang_codes", None)
+        if ov:
+            cfg["special"] = ov
         heads = attrs.get("decoder/num_heads", attrs.get("encoder/num_heads"))
         return w, arch_from_weights(w, int(np.asarray(heads).reshape(-1)[0]) if heads is not None else None), cfg
     if os.path.exists(os.path.join(path, "model.safetensors")) or os.path.exists(os.path.join(path, "model.safetensors.index.json")):
@@ -437,8 +582,9 @@ def convert_hf_to_ct2_dir(hf_dir, out_dir):
     w, a, cfg = load_hf_dir(hf_dir)
     os.makedirs(out_dir, exist_ok=True)
     write_ct2_model_bin(os.path.join(out_dir, "model.bin"), w, aliases={"decoder/projection/weight": "decoder/embeddings/weight"})
-    full = dict(suppress_ids=cfg.get("suppress_ids", SUPPRESS_IDS), suppress_ids_begin=cfg.get("suppress_ids_begin", SUPPRESS_IDS_BEGIN),
-                lang_ids=cfg.get("lang_ids", LANG_IDS), alignment_heads=[])
+    st = special_tokens(a["n_vocab"], cfg.get("special"))
+    full = dict(suppress_ids=cfg.get("suppress_ids", st.default_suppress_ids()), suppress_ids_begin=cfg.get("suppress_ids_begin", [220, st.eot]),
+                lang_ids=cfg.get("lang_ids", st.lang_ids), alignment_heads=[])
     with open(os.path.join(out_dir, "config.json"), "w") as f:
         json.dump(full, f)
     for fn in ("tokenizer.json", "tokenizer_config.json", "preprocessor_config.json", "vocab.json", "merges.txt", "added_tokens.json",

@@ -1,6 +1,7 @@
 """The ASR orchestrator: what the reference's `do_whisper` does (main.py:554-770), on the wis_hip engine.
 
-Same call signature, same per-request selection surface (model in {tiny, base, small, medium, large}, beam_size,
+Same call signature, same per-request selection surface (model in {tiny, base, small, medium, large} - and, beyond the reference,
+large-v3 / large-v3-turbo (128 mel bins, 51866 tokens; V3_MODEL_SIZES) - beam_size,
 detect_language, force_language, translate; main.py:564-573) and the same 6-tuple result
     (language, text, infer_time_ms, translation, infer_speedup, audio_duration_ms)          (main.py:763-770)
 including the reference's behaviours: >= long_beam_size_threshold ms switches to long_beam_size (main.py:582-586),
@@ -23,10 +24,11 @@ import time
 import numpy as np
 
 from . import audio, ctranslate2, weights as W
-from .languages import LANGUAGE_CODES, LANGUAGES
+from .languages import LANGUAGE_CODES, LANGUAGE_CODES_V3, LANGUAGES
 from .settings import get_api_settings
 
 MODEL_SIZES = ("tiny", "base", "small", "medium", "large")
+V3_MODEL_SIZES = ("large-v3", "large-v3-turbo")      # served on request; preload only by their own settings (preload_whisper_model_large_v3[_turbo])
 SPECIAL_IDS = list(range(W.EOT, W.N_VOCAB))     # <|endoftext|> ... timestamps: everything >= 50257 is special
 
 
@@ -42,17 +44,24 @@ class WhisperResult(tuple):
     segments = None
 
 
-def segments_from_tokens(ids, tokenizer, offset=0.0, duration=WINDOW_S):
+def model_special_tokens(model):
+    """The special-id table of a loaded model (ctranslate2.Whisper.special); the 51865-token table for anything that has none."""
+    st = getattr(model, "special", None)
+    return st if isinstance(st, W.SpecialTokens) else W.special_tokens(W.N_VOCAB)
+
+
+def segments_from_tokens(ids, tokenizer, offset=0.0, duration=WINDOW_S, special=None):
     """Timed segments of one decoded window, split as openai-whisper's transcribe() splits a window's tokens: two consecutive
     timestamps close one segment and open the next; a single timestamp before the end (EOT) closes the last segment; text that
     no timestamp closes ends at the window's `duration`.  A window with no consecutive pair is one segment from `offset` to its last
-    timestamp (or to `duration` when that is <|0.00|> or there is none).  -> [{"start", "end", "text"}], seconds + `offset`."""
-    tb = TIMESTAMP_BEGIN
-    toks = [int(t) for t in ids if int(t) != W.EOT]
+    timestamp (or to `duration` when that is <|0.00|> or there is none).  -> [{"start", "end", "text"}], seconds + `offset`.
+    special: the model's SpecialTokens (default: the 51865-token vocabulary)."""
+    tb, eot = (TIMESTAMP_BEGIN, W.EOT) if special is None else (special.timestamp_begin, special.eot)
+    toks = [int(t) for t in ids if int(t) != eot]
     is_ts = [t >= tb for t in toks]
 
     def seg(start, end, piece):
-        return {"start": round(offset + start, 2), "end": round(offset + end, 2), "text": tokenizer.decode([t for t in piece if t < W.EOT]).strip()}
+        return {"start": round(offset + start, 2), "end": round(offset + end, 2), "text": tokenizer.decode([t for t in piece if t < eot]).strip()}
 
     def at(t):
         return (t - tb) * TIME_PRECISION
@@ -92,8 +101,10 @@ class _Tokenizer:
     # id-only form (no tokenizer files, synthetic weights): every id from <|endoftext|> up is treated as special
     all_special_ids = SPECIAL_IDS
 
-    def __init__(self, path=None):
+    def __init__(self, path=None, special_ids=None):
         self._tok = None
+        if special_ids is not None:         # id-only form of another vocabulary (large-v3: up to 51865)
+            self.all_special_ids = list(special_ids)
         if path and os.path.exists(os.path.join(path, "tokenizer.json")):
             from tokenizers import Tokenizer
             self._tok = Tokenizer.from_file(os.path.join(path, "tokenizer.json"))
@@ -134,7 +145,7 @@ class WhisperModels:
         return self.settings.whisper_model_path.format(size=size)
 
     def get(self, size):
-        if size not in MODEL_SIZES:
+        if size not in MODEL_SIZES and size not in V3_MODEL_SIZES:
             raise ValueError(f"unknown model {size!r}")
         with self._lock:
             if size not in self._models:
@@ -157,6 +168,9 @@ class WhisperModels:
                                                                 inter_threads=self.settings.ctranslate2_threads,
                                                                 device_index=self.device_index, max_batch=self.settings.max_batch,
                                                                 replicas_per_device=self.settings.replicas_per_gpu, max_beam=max_beam)
+                st = model_special_tokens(self._models[size])
+                if synthetic and st.n_vocab != W.N_VOCAB:
+                    self.tokenizers[size] = _Tokenizer(None, special_ids=st.special_ids)
                 import logging
                 logging.getLogger("wis_hip").info("whisper %s loaded: beam_size 1..%d served (max_beam), device batches of up to %d utterances, %d replica(s)",
                                                   size, max_beam, self.settings.max_batch, len(self._models[size]._replicas))
@@ -169,6 +183,9 @@ class WhisperModels:
         s = self.settings
         for size in MODEL_SIZES:
             if s.preload_all_models or getattr(s, f"preload_whisper_model_{size}"):
+                self.get(size)
+        for size in V3_MODEL_SIZES:          # (setting names spell the model's '-' as '_')
+            if getattr(s, "preload_whisper_model_" + size.replace("-", "_"), False):
                 self.get(size)
 
     def warm(self, clip):
@@ -191,8 +208,14 @@ class InvalidAudio(ValueError):
     """The container could not be decoded (the REST layer answers HTTP 400 "Invalid audio", main.py:1311-1314)."""
 
 
-def check_language(language):
-    return language in LANGUAGES
+def check_language(language, special=None):
+    """`language` names a language token of the model (special: its SpecialTokens; default the 99 of the 51865-token vocabulary)."""
+    return language in (LANGUAGES if special is None else special.lang_codes)
+
+
+def check_model_language(language, size):
+    """`language` is one of model `size`'s languages, known before the model is loaded (yue: large-v3 / large-v3-turbo only)."""
+    return language in (LANGUAGE_CODES_V3 if size in V3_MODEL_SIZES else LANGUAGES)
 
 
 def chunkit(lst, num):
@@ -208,6 +231,8 @@ def do_whisper(audio_file, model, beam_size=None, task="transcribe", detect_lang
         fixed_new_tokens = s.fixed_new_tokens
     beam_size = s.beam_size if beam_size is None else beam_size
     whisper_model = models.get(model)
+    special = model_special_tokens(whisper_model)
+    n_mels = getattr(whisper_model, "n_mels", audio.N_MELS)
     first_time_start = time.perf_counter()
 
     # STEP 1 — load audio and extract features
@@ -243,7 +268,7 @@ def do_whisper(audio_file, model, beam_size=None, task="transcribe", detect_lang
         # the reference's two-step form (main.py:606-614, 685): features to the host, then StorageView.from_array
         # (on one of the model's own GPUs - never on a device the server was not configured to use)
         dev = whisper_model._replicas[0].device if getattr(whisper_model, "_replicas", None) else None
-        features, kind = audio.log_mel_spectrogram(windows, device=dev).numpy(), ctranslate2._lib.WIS_IN_MEL_HOST
+        features, kind = audio.log_mel_spectrogram(windows, n_mels=n_mels, device=dev).numpy(), ctranslate2._lib.WIS_IN_MEL_HOST
     total_chunk_count = features.shape[0]
     tokenizer = models.tokenizer_for(model)
 
@@ -255,10 +280,10 @@ def do_whisper(audio_file, model, beam_size=None, task="transcribe", detect_lang
         language = lang_token.strip("<|>")
     elif force_language:
         language = force_language
-    if not check_language(language):
+    if not check_language(language, special):
         raise ValueError(f"unsupported language {language!r}")
-    task_id = W.TRANSLATE if task == "translate" else W.TRANSCRIBE
-    prompt = [W.SOT, _Tokenizer.language_token_id(language), task_id] + ([] if timestamps else [W.NO_TIMESTAMPS])
+    task_id = special.translate if task == "translate" else special.transcribe
+    prompt = [special.sot, special.language_token_id(language), task_id] + ([] if timestamps else [special.notimestamps])
 
     # STEP 3 — run the model, `concurrent_gpu_chunks` windows per generate call
     results = []
@@ -275,14 +300,14 @@ def do_whisper(audio_file, model, beam_size=None, task="transcribe", detect_lang
         tokens = results[0].sequences_ids[0]
     segments = None
     if timestamps:
-        segments = segments_from_tokens(tokens, tokenizer, 0.0, min(audio_duration / 1000.0, WINDOW_S))
-        text = tokenizer.decode([t for t in tokens if t < TIMESTAMP_BEGIN]).strip()
+        segments = segments_from_tokens(tokens, tokenizer, 0.0, min(audio_duration / 1000.0, WINDOW_S), special)
+        text = tokenizer.decode([t for t in tokens if t < special.timestamp_begin]).strip()
     else:
         text = tokenizer.decode(tokens).strip()
 
     translation = None
     if translate and total_chunk_count <= s.concurrent_gpu_chunks:       # main.py:729-748 (its `len(int)` bug aside: short audio only)
-        tprompt = [W.SOT, _Tokenizer.language_token_id(language), W.TRANSLATE, W.NO_TIMESTAMPS]
+        tprompt = [special.sot, special.language_token_id(language), special.translate, special.notimestamps]
         feats = ctranslate2.StorageView.from_array(np.ascontiguousarray(features))
         tres = whisper_model.generate(feats, [tprompt] * total_chunk_count, beam_size=beam_size, fixed_new_tokens=fixed_new_tokens, input_kind=kind)
         translation = tokenizer.decode(tres[0].sequences_ids[0]).strip()
