@@ -364,6 +364,26 @@ int    wis_sv_rel_buckets(int num_buckets, int max_distance, int first, int n, i
  * LayerNorm, l = output of layer l, HF hidden_states[l]); tap 2 = output of the last TDNN layer after its ReLU [T - 14][1500]. */
 int    wis_debug_sv_taps(wis_sv_t* sv, const float* pcm, int64_t n, int tap, int layer, float* out, int64_t cap_floats,
                          int32_t* rows, int32_t* cols);
+/* single-kernel taps of the speaker-verification kernels (tests): every pointer is device memory, each call launches the kernels
+ * sv_forward launches, with the same grids, on the device's op stream and synchronises.
+ * conv 0 + GroupNorm(512 groups, eps 1e-5) + GELU: pcm f32 [n], w0 f32 [512][10], gamma / beta f32 [512] -> y f16 [T0][512],
+ * T0 = (n - 10) / 5 + 1 */
+int    wis_op_sv_conv0(int device, const float* pcm, int64_t n, const float* w0, const float* gamma, const float* beta, void* y_f16);
+/* positional conv (k128, pad 64, 16 groups, last output dropped) + bias, GELU, + residual: x f32 [T][768], W f16 [768][128][48],
+ * bias f32 [768] -> out f32 [T][768] */
+int    wis_op_sv_posconv(int device, const float* x, const void* W_f16, const float* bias, float* out, int T);
+/* gated relative-position attention of 12 heads: qkv f16 [T][2304] (Q pre-scaled by 1/8 | K | V), xin f32 [T][768] (the layer input,
+ * for the gate), gw f32 [8][64], gb f32 [8], gconst f32 [12], tab f32 [12][2L - 1] (entry key - query + L - 1), L >= T -> out f16 [T][768] */
+int    wis_op_sv_attention(int device, const void* qkv_f16, const float* xin, const float* gw, const float* gb, const float* gconst,
+                           const float* tab, int L, void* out_f16, int T);
+/* LayerNorm (eps 1e-5) of x [M][d] (f16 if in_f16, else f32), d = 512 or 768 -> y16 f16, y32 f32 (optional); wmode 1: ws = wl y,
+ * 2: ws += wl y (f32 [M][d]); ws16 (optional): f16 copy of the updated ws */
+int    wis_op_sv_layernorm(int device, const void* x, int in_f16, const float* gamma, const float* beta, void* y16, float* y32,
+                           float* ws, void* ws16, float wl, int wmode, int M, int d);
+/* x-vector tail: stats [2n] = mean and unbiased std over T rows of ReLU(z[t][0 .. n - 1]) (z f32, row stride ldz >= n), then
+ * emb [512] = W_fe [512][2n] . stats + b_fe */
+int    wis_op_sv_xvector_tail(int device, const float* z, int ldz, int T, int n, const float* W_fe, const float* b_fe,
+                              float* stats, float* emb);
 
 #ifdef __cplusplus
 }

@@ -144,3 +144,104 @@ def test_willow_voice_auth_end_to_end(model, golden_dir, tmp_path):
     j = r.json()
     assert list(j["voice_auth"]) == ["alice"] and float(j["voice_auth"]["alice"]) >= 0.999
     assert j["speaker_status"] == "I heard alice say:" and "infer_time" in j and "text" in j
+
+
+# ---- a model under which the attention's own features matter --------------------------------------------------------------------
+# At HF's default init the relative-position bias and its gate barely move the output (tests/sv_ref.py sharpen()); the sharpened
+# seed-11 model makes a dropped, mirrored or mis-gated bias visible (tests/test_sv_cpu.py checks that power on HF itself).  The oracle
+# is HF in float64.
+def _sv_ref():
+    import sys
+    sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+    import sv_ref
+    return sv_ref
+
+
+SHARP_LENGTHS = (5200, 5520, 10320, 48000, 160000)            # T = 16 (the shortest accepted), 17, 32, 149, 499
+
+
+@pytest.fixture(scope="module")
+def sharp(tmp_path_factory):
+    from wis_hip import sv
+    R = _sv_ref()
+    hf = R.sharpen(sv.synthetic_model(seed=11))
+    d = tmp_path_factory.mktemp("wavlm_sharp")
+    hf.save_pretrained(str(d))
+    (d / "preprocessor_config.json").write_text('{"do_normalize": true, "sampling_rate": 16000, "feature_size": 1}')
+    eng = sv.SpeakerVerifier(str(d))
+    yield hf.double(), eng, str(d)
+    eng.close()
+
+
+@pytest.fixture(scope="module")
+def long_input(golden_dir):
+    """the 30 s golden clip through the reference's gain and normalisation, untrimmed (slices of it are the inputs below)"""
+    from wis_hip import audio, sv
+    pcm, _ = audio.load_audio(os.path.join(golden_dir, "clips", "30sec.flac"))
+    return sv.zero_mean_unit_var(sv.sox_norm_gain(pcm))
+
+
+@pytest.fixture(scope="module")
+def sharp_oracle(sharp, long_input):
+    """HF float64 of each input length, computed once"""
+    hf = sharp[0]
+    R = _sv_ref()
+    cache = {}
+
+    def get(n):
+        if n not in cache:
+            cache[n] = R.hf_forward(hf, long_input[:n])
+        return cache[n]
+    return get
+
+
+def _check_taps(eng, x, ref, what):
+    R = _sv_ref()
+    feat, hidden, tdnn, emb = ref
+    T = feat.shape[0]
+    got = eng.taps(x, 0)
+    assert got.shape == (T, 512)
+    assert R.rel_l2(got, feat) <= 2e-3 and R.worst_row(got, feat) <= 1e-2, (what, R.rel_l2(got, feat), R.worst_row(got, feat))
+    errs, rows = [], []
+    for layer in range(13):
+        g = eng.taps(x, 1, layer)
+        assert g.shape == (T, 768)
+        errs.append(R.rel_l2(g, hidden[layer]))
+        rows.append(R.worst_row(g, hidden[layer]))
+    assert max(errs) <= R.SHARP_HIDDEN_LIMIT and max(rows) <= 4 * R.SHARP_HIDDEN_LIMIT, (what, errs, rows)
+    td = eng.taps(x, 2)
+    assert td.shape == tdnn.shape == (T - 14, 1500)
+    assert R.rel_l2(td, tdnn) <= 1e-2, (what, R.rel_l2(td, tdnn))
+    e = eng.embed_input(x)
+    assert R.rel_l2(e, emb) <= 1e-2, (what, R.rel_l2(e, emb))
+    print(f"sharpened {what}: T={T} feat {R.rel_l2(got, feat):.2e}, hidden max {max(errs):.2e} (worst row {max(rows):.2e}), "
+          f"tdnn {R.rel_l2(td, tdnn):.2e}, embedding {R.rel_l2(e, emb):.2e}")
+    return e
+
+
+@pytest.mark.parametrize("n", SHARP_LENGTHS)
+def test_sharpened_taps_match_hf_float64(sharp, long_input, sharp_oracle, n):
+    _, eng, _ = sharp
+    _check_taps(eng, long_input[:n], sharp_oracle(n), f"n={n}")
+
+
+def test_sharpened_too_short(sharp, long_input):
+    from wis_hip import _lib
+    _, eng, _ = sharp
+    with pytest.raises(_lib.WisError) as e:
+        eng.embed_input(long_input[:5199])        # T = 15: one frame after the TDNN layers
+    assert e.value.code == -1
+
+
+def test_sharpened_60s_handle(sharp, long_input, sharp_oracle):
+    """a handle built for 60 s (bias table of 2 x 2999 - 1 distances, saturated past 800): bit-identical to the default handle on
+    10 s, and HF parity on 25 s (T = 1249, distances up to 1248)"""
+    from wis_hip import sv
+    _, eng, path = sharp
+    big = sv.SpeakerVerifier(path, max_samples=60 * 16000)
+    try:
+        x10 = long_input[:160000]
+        assert np.array_equal(big.embed_input(x10), eng.embed_input(x10))
+        _check_taps(big, long_input[:400000], sharp_oracle(400000), "n=400000 (60 s handle)")
+    finally:
+        big.close()

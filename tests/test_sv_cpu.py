@@ -23,13 +23,37 @@ def test_rel_buckets_equal_hf():
     from transformers import WavLMForXVector
     from wis_hip import sv
     attn = WavLMForXVector(_tiny_cfg()).wavlm.encoder.layers[0].attention
-    L = 499
+    L = 2999                       # a handle built for 60 s: distances past max_bucket_distance (800) saturate
     tab = sv.rel_buckets(-(L - 1), 2 * L - 1)
-    for T in list(range(1, 40)) + [97, 250, 498, 499]:
+    for T in list(range(1, 40)) + [97, 250, 498, 499, 800, 801, 802, 1249, 2998, 2999]:
         rel = torch.arange(T)[None, :] - torch.arange(T)[:, None]
         ref = attn._relative_positions_bucket(rel).numpy()
         got = tab[(rel + L - 1).numpy()]
         assert np.array_equal(got, ref), T
+    assert tab[0] == 159 and tab[-1] == 319              # the two saturated ends
+
+
+def test_sharpened_model_sees_every_attention_ablation():
+    """The power of tests/test_gpu_sv.py's sharpened model: each wrong variant of the gated relative-position attention
+    (tests/sv_ref.py ABLATIONS: no bias, the bias table mirrored, the gate frozen, gate_a / gate_b swapped, gru_rel_pos_const = 1)
+    applied to HF float64 must move some hidden state by at least 10x the limit the GPU test holds the engine to.  At HF's default
+    init the same ablations move them by less than the limit (the gap this model closes), so a weaker model would fail here."""
+    import sys
+    sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+    import sv_ref as R
+    from wis_hip import sv
+    hf = R.sharpen(sv.synthetic_model(seed=11)).double()
+    x = sv.preprocess(np.random.default_rng(5).standard_normal(48000).astype(np.float32) * 0.1)       # 3 s: T = 149
+    _, ref, _, emb = R.hf_forward(hf, x)
+    assert max(float(np.abs(h).max()) for h in ref) < 100          # the engine holds the hidden states' f16 copies: well inside range
+    moved = {}
+    for kind in R.ABLATIONS:
+        with R.ablated(hf, kind):
+            _, hid, _, _ = R.hf_forward(hf, x)
+        moved[kind] = max(R.rel_l2(a, b) for a, b in zip(hid, ref))
+    _, again, _, emb2 = R.hf_forward(hf, x)
+    assert np.array_equal(emb, emb2)                                # every ablation was undone
+    assert min(moved.values()) >= 10 * R.SHARP_HIDDEN_LIMIT, moved
 
 
 def test_weight_norm_fold_and_conv_layout_match_hf():

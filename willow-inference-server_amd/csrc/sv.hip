@@ -17,6 +17,7 @@
 #include <math.h>
 #include <string.h>
 
+#include <mutex>
 #include <string>
 #include <vector>
 
@@ -548,6 +549,26 @@ int sv_ln(hipStream_t st, const void* x, const float* g, const float* b, f16* y1
   return WIS_OK;
 }
 
+// the launches sv_forward shares with the wis_op_sv_* entries (tests call each kernel through these, with the production grids)
+void sv_launch_conv0(hipStream_t st, const float* pcm, const float* w0, const float* gamma, const float* beta, float* part, float* ss, f16* y, int T0) {
+  const int nch = cdiv(T0, CHUNK0);
+  hipLaunchKernelGGL(sv_conv0_stats_kernel, dim3(nch), dim3(256), 0, st, pcm, w0, part, T0);
+  hipLaunchKernelGGL(sv_conv0_norm_kernel, dim3(C0 / 256), dim3(256), 0, st, part, gamma, beta, ss, T0, nch);
+  hipLaunchKernelGGL(sv_conv0_apply_kernel, dim3(nch), dim3(256), 0, st, pcm, w0, ss, y, T0);
+}
+void sv_launch_posconv(hipStream_t st, const float* x, const f16* W, const float* bias, float* out, int T) {
+  hipLaunchKernelGGL(sv_posconv_kernel, dim3(cdiv(T, 16), PG), dim3(64), 0, st, x, W, bias, out, T);
+}
+void sv_launch_attn(hipStream_t st, const f16* qkv, const float* xin, const float* gw, const float* gb, const float* gconst, const float* tab,
+                    int L, f16* out, int T) {
+  hipLaunchKernelGGL(sv_attn_kernel, dim3(cdiv(T, 16), H), dim3(64), 0, st, qkv, xin, gw, gb, gconst, tab, L, out, T);
+}
+// statistics pooling of ReLU(z[T][ldz]) over the first n columns -> stats [2n], then emb [XV] = W_fe stats + b_fe
+void sv_launch_xvector_tail(hipStream_t st, const float* z, int ldz, int T, int n, const float* w_fe, const float* b_fe, float* stats, float* emb) {
+  hipLaunchKernelGGL(sv_stats_kernel, dim3(cdiv(n, 256)), dim3(256), 0, st, z, ldz, stats, T, n);
+  hipLaunchKernelGGL(sv_linear_kernel, dim3(cdiv(XV, 4)), dim3(256), 0, st, stats, w_fe, b_fe, emb, XV, 2 * n);
+}
+
 // the forward pass; stop_hidden >= 0: return after hidden state `stop_hidden` (0 = encoder input after the positional conv + LayerNorm,
 // l = output of layer l) is in s->h
 int sv_forward(wis_sv* s, int64_t n, int stop_hidden) {
@@ -557,10 +578,7 @@ int sv_forward(wis_sv* s, int64_t n, int stop_hidden) {
   if (T - td_reduction() < 2) { set_error("wis_sv_embed: %lld samples leave %d frames, the x-vector head needs >= %d", (long long)n, T, td_reduction() + 2); return WIS_E_ARG; }
   s->T = T; s->T_td = T - td_reduction();
   // feature encoder
-  const int nch = cdiv(T0, CHUNK0);
-  hipLaunchKernelGGL(sv_conv0_stats_kernel, dim3(nch), dim3(256), 0, st, s->pcm, s->w_conv0, s->c0part, T0);
-  hipLaunchKernelGGL(sv_conv0_norm_kernel, dim3(C0 / 256), dim3(256), 0, st, s->c0part, s->gn_g, s->gn_b, s->c0ss, T0, nch);
-  hipLaunchKernelGGL(sv_conv0_apply_kernel, dim3(nch), dim3(256), 0, st, s->pcm, s->w_conv0, s->c0ss, s->fa, T0);
+  sv_launch_conv0(st, s->pcm, s->w_conv0, s->gn_g, s->gn_b, s->c0part, s->c0ss, s->fa, T0);
   f16* src = s->fa; f16* dst = s->fb;
   int t = T0;
   for (int i = 1; i < 7; ++i) {
@@ -573,13 +591,13 @@ int sv_forward(wis_sv* s, int64_t n, int stop_hidden) {
   // feature projection, positional conv, encoder LayerNorm -> hidden state 0
   WIS_RET(sv_ln<true>(st, src, s->fp_ln_g, s->fp_ln_b, s->xn512, nullptr, nullptr, nullptr, 0.f, 0, T, C0));
   WIS_RET(launch_gemm_generic(st, gemm_plain(s->xn512, C0, s->w_fp, T, D, C0), s->b_fp, nullptr, s->x32, 4));
-  hipLaunchKernelGGL(sv_posconv_kernel, dim3(cdiv(T, 16), PG), dim3(64), 0, st, s->x32, s->w_pos, s->b_pos, s->x32b, T);
+  sv_launch_posconv(st, s->x32, s->w_pos, s->b_pos, s->x32b, T);
   WIS_RET(sv_ln<false>(st, s->x32b, s->enc_ln_g, s->enc_ln_b, s->hn, s->h, s->ws, nullptr, s->lw[0], 1, T, D));
   if (stop_hidden == 0) return WIS_OK;
   for (int l = 0; l < NL; ++l) {
     const SvLayer& w = s->L[l];
     WIS_RET(launch_gemm_generic(st, gemm_plain(s->hn, D, w.w_qkv, T, 3 * D, D), w.b_qkv, nullptr, s->qkv, 0));
-    hipLaunchKernelGGL(sv_attn_kernel, dim3(cdiv(T, 16), H), dim3(64), 0, st, s->qkv, s->h, w.gw, w.gb, w.gconst, s->tab, s->Tmax, s->ao, T);
+    sv_launch_attn(st, s->qkv, s->h, w.gw, w.gb, w.gconst, s->tab, s->Tmax, s->ao, T);
     WIS_RET(launch_gemm_generic(st, gemm_plain(s->ao, D, w.w_out, T, D, D), w.b_out, s->h, s->x32, 2 | 4));
     WIS_RET(sv_ln<false>(st, s->x32, w.ln1_g, w.ln1_b, s->hn1, s->h1, nullptr, nullptr, 0.f, 0, T, D));
     WIS_RET(launch_gemm_generic(st, gemm_plain(s->hn1, D, w.w_f1, T, FF, D), w.b_f1, nullptr, s->ff, 1));
@@ -610,8 +628,7 @@ int sv_forward(wis_sv* s, int64_t n, int stop_hidden) {
       a = s->gbuf;
     }
   }
-  hipLaunchKernelGGL(sv_stats_kernel, dim3(cdiv(TD_DIM[NTD - 1], 256)), dim3(256), 0, st, s->z, TD_LAST_PAD, s->stats, t, TD_DIM[NTD - 1]);
-  hipLaunchKernelGGL(sv_linear_kernel, dim3(cdiv(XV, 4)), dim3(256), 0, st, s->stats, s->w_fe, s->b_fe, s->emb, XV, 2 * TD_DIM[NTD - 1]);
+  sv_launch_xvector_tail(st, s->z, TD_LAST_PAD, t, TD_DIM[NTD - 1], s->w_fe, s->b_fe, s->stats, s->emb);
   return WIS_OK;
 }
 
@@ -729,6 +746,65 @@ int wis_debug_sv_taps(wis_sv_t* s, const float* pcm, int64_t n, int tap, int lay
     for (int i = 0; i < r; ++i) for (int j = 0; j < c; ++j) out[(size_t)i * c + j] = z[(size_t)i * TD_LAST_PAD + j] > 0.f ? z[(size_t)i * TD_LAST_PAD + j] : 0.f;
   }
   *rows = r; *cols = c;
+  return WIS_OK;
+}
+
+// ---- single-kernel taps (tests): device pointers in, the production launch helper on the device's op stream, synchronised --------
+int wis_op_sv_conv0(int device, const float* pcm, int64_t n, const float* w0, const float* gamma, const float* beta, void* y) {
+  if (!pcm || !w0 || !gamma || !beta || !y || n < CONV_K[0] || n > (int64_t)16000 * 60) { set_error("wis_op_sv_conv0: bad argument"); return WIS_E_ARG; }
+  DeviceCtx* c; WIS_RET(get_ctx(device, &c));
+  std::lock_guard<std::mutex> op_lock(ctx_op_mutex(c));
+  hipStream_t st = ctx_stream(c);
+  const int T0 = (int)((n - CONV_K[0]) / CONV_S[0] + 1);
+  float *part = nullptr, *ss = nullptr;
+  if (hipMalloc(reinterpret_cast<void**>(&part), (size_t)cdiv(T0, CHUNK0) * C0 * 2 * 4) != hipSuccess ||
+      hipMalloc(reinterpret_cast<void**>(&ss), (size_t)2 * C0 * 4) != hipSuccess) {
+    hipFree(part); set_error("wis_op_sv_conv0: out of device memory"); return WIS_E_NOMEM;
+  }
+  sv_launch_conv0(st, pcm, w0, gamma, beta, part, ss, reinterpret_cast<f16*>(y), T0);
+  hipError_t e = hipGetLastError();
+  if (e == hipSuccess) e = hipStreamSynchronize(st);
+  hipFree(part); hipFree(ss);
+  if (e != hipSuccess) { set_error("wis_op_sv_conv0: %s", hipGetErrorString(e)); return WIS_E_HIP; }
+  return WIS_OK;
+}
+int wis_op_sv_posconv(int device, const float* x, const void* W, const float* bias, float* out, int T) {
+  if (!x || !W || !bias || !out || T < 1) { set_error("wis_op_sv_posconv: bad argument"); return WIS_E_ARG; }
+  DeviceCtx* c; WIS_RET(get_ctx(device, &c));
+  std::lock_guard<std::mutex> op_lock(ctx_op_mutex(c));
+  sv_launch_posconv(ctx_stream(c), x, reinterpret_cast<const f16*>(W), bias, out, T);
+  WIS_HIP_CHECK(hipGetLastError());
+  WIS_HIP_CHECK(hipStreamSynchronize(ctx_stream(c)));
+  return WIS_OK;
+}
+int wis_op_sv_attention(int device, const void* qkv, const float* xin, const float* gw, const float* gb, const float* gconst, const float* tab,
+                        int L, void* out, int T) {
+  if (!qkv || !xin || !gw || !gb || !gconst || !tab || !out || T < 1 || L < T) { set_error("wis_op_sv_attention: bad argument"); return WIS_E_ARG; }
+  DeviceCtx* c; WIS_RET(get_ctx(device, &c));
+  std::lock_guard<std::mutex> op_lock(ctx_op_mutex(c));
+  sv_launch_attn(ctx_stream(c), reinterpret_cast<const f16*>(qkv), xin, gw, gb, gconst, tab, L, reinterpret_cast<f16*>(out), T);
+  WIS_HIP_CHECK(hipGetLastError());
+  WIS_HIP_CHECK(hipStreamSynchronize(ctx_stream(c)));
+  return WIS_OK;
+}
+int wis_op_sv_layernorm(int device, const void* x, int in_f16, const float* gamma, const float* beta, void* y16, float* y32, float* ws, void* ws16,
+                        float wl, int wmode, int M, int d) {
+  if (!x || !gamma || !beta || !y16 || wmode < 0 || wmode > 2 || (wmode && !ws) || M < 1) { set_error("wis_op_sv_layernorm: bad argument"); return WIS_E_ARG; }
+  DeviceCtx* c; WIS_RET(get_ctx(device, &c));
+  std::lock_guard<std::mutex> op_lock(ctx_op_mutex(c));
+  if (in_f16) WIS_RET(sv_ln<true>(ctx_stream(c), x, gamma, beta, reinterpret_cast<f16*>(y16), y32, ws, reinterpret_cast<f16*>(ws16), wl, wmode, M, d));
+  else WIS_RET(sv_ln<false>(ctx_stream(c), x, gamma, beta, reinterpret_cast<f16*>(y16), y32, ws, reinterpret_cast<f16*>(ws16), wl, wmode, M, d));
+  WIS_HIP_CHECK(hipGetLastError());
+  WIS_HIP_CHECK(hipStreamSynchronize(ctx_stream(c)));
+  return WIS_OK;
+}
+int wis_op_sv_xvector_tail(int device, const float* z, int ldz, int T, int n, const float* w_fe, const float* b_fe, float* stats, float* emb) {
+  if (!z || !w_fe || !b_fe || !stats || !emb || T < 2 || n < 1 || n > ldz) { set_error("wis_op_sv_xvector_tail: bad argument"); return WIS_E_ARG; }
+  DeviceCtx* c; WIS_RET(get_ctx(device, &c));
+  std::lock_guard<std::mutex> op_lock(ctx_op_mutex(c));
+  sv_launch_xvector_tail(ctx_stream(c), z, ldz, T, n, w_fe, b_fe, stats, emb);
+  WIS_HIP_CHECK(hipGetLastError());
+  WIS_HIP_CHECK(hipStreamSynchronize(ctx_stream(c)));
   return WIS_OK;
 }
 

@@ -122,6 +122,11 @@ SYMBOLS = [
     ("wis_sv_embed", _i, [_vp, _vp, _i64, _fp]),
     ("wis_sv_rel_buckets", _i, [_i, _i, _i, _i, C.POINTER(C.c_int32)]),
     ("wis_debug_sv_taps", _i, [_vp, _vp, _i64, _i, _i, _fp, _i64, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    ("wis_op_sv_conv0", _i, [_i, _vp, _i64, _vp, _vp, _vp, _vp]),
+    ("wis_op_sv_posconv", _i, [_i, _vp, _vp, _vp, _vp, _i]),
+    ("wis_op_sv_attention", _i, [_i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _i]),
+    ("wis_op_sv_layernorm", _i, [_i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, C.c_float, _i, _i, _i]),
+    ("wis_op_sv_xvector_tail", _i, [_i, _vp, _i, _i, _i, _vp, _vp, _vp, _vp]),
 ]
 
 _lib = None

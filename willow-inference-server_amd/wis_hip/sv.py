@@ -203,6 +203,16 @@ def sv_config(max_samples=MAX_SECONDS * SAMPLE_RATE, cfg=None):
     return c
 
 
+def frames(n):
+    """frames after the feature encoder for n samples (0: too short for a stage), as the engine counts them"""
+    t = int(n)
+    for k, s in zip(ARCH["conv_kernel"], ARCH["conv_stride"]):
+        if t < k:
+            return 0
+        t = (t - k) // s + 1
+    return t
+
+
 def rel_buckets(first, n, num_buckets=320, max_distance=800):
     """the engine's relative-position bucket table (host function of libwis_hip.so, no GPU needed)"""
     out = np.zeros(n, dtype=np.int32)
@@ -244,7 +254,7 @@ class SpeakerVerifier:
 
     def taps(self, x, tap, layer=0):
         x = np.ascontiguousarray(x, dtype=np.float32)
-        cap = 512 * 1536
+        cap = max(512 * 1536, frames(x.size) * 1536)   # the widest tap: [T - 14][1500]
         out = np.zeros(cap, dtype=np.float32)
         r, c = C.c_int32(), C.c_int32()
         with self._lock:
