@@ -224,6 +224,34 @@ int wis_debug_logits(wis_model_t* m, const float* input, int input_kind, int B,
  * concurrent requests) instead of the <= 8-row route; B*R <= 96 (MAX_ROWS) */
 int wis_debug_logits_rows(wis_model_t* m, const float* input, int input_kind, int B,
                           const int32_t* dec_in, int T, int R, float* logits);
+/* ---- word-level timestamps: cross-attention alignment + dynamic time warping (csrc/align.hip) --------------------------------
+ * The alignment heads of a handle: n (layer, head) pairs; n == 0 restores openai-whisper's default, every head of the upper half
+ * of the decoder layers (layer >= n_dec_layers / 2).  Clones made afterwards inherit them.  Not part of wis_config_t. */
+int wis_model_set_alignment_heads(wis_model_t* m, const int32_t* layer_head_pairs, int n);
+/* What CTranslate2's Whisper.align / openai-whisper's find_alignment compute.  Per utterance b the decoder is teacher-forced on
+ * start_seq[P] + [no_timestamps] + text_b + (eot is predicted, not fed); the alignment heads' softmax(q.K^T) over all n_audio_ctx
+ * keys, cropped to num_frames[b] / 2 frames, for the text_len[b] + 1 rows from the no_timestamps input on, is normalised over the
+ * token axis per head ((w - mean) / population std), median-filtered along frames (odd width <= 63, reflect padding), averaged over
+ * the heads, negated, and warped (openai-whisper dtw_cpu's recurrence and tie rules, bit for bit).
+ *   text: the utterances' tokens back to back, text_len[B]; P + 1 + text_len[b] <= n_text_ctx (else WIS_E_ARG); B <= max_batch
+ *   path_text / path_time [B][n_text_ctx + n_audio_ctx], path_len [B]: the warping path in forward order
+ *   token_probs [B][n_text_ctx]: softmax(logits over ids < eot)[text_b[i]] at the row that predicts it (entries >= text_len[b] untouched)
+ * The first call of a handle allocates the align scratch (wis_model_device_bytes grows then, not at create). */
+int wis_align(wis_model_t* m, const float* input, int input_kind, int B, const int32_t* start_seq, int P,
+              const int32_t* text, const int32_t* text_len, const int32_t* num_frames, int median_filter_width,
+              int32_t* path_text, int32_t* path_time, int32_t* path_len, float* token_probs);
+/* the matrix wis_align warps, alone: out = the utterances' dense fp32 [text_len[b] + 1][num_frames[b] / 2] matrices back to back (host) */
+int wis_debug_align_matrix(wis_model_t* m, const float* input, int input_kind, int B, const int32_t* start_seq, int P,
+                           const int32_t* text, const int32_t* text_len, const int32_t* num_frames, int median_filter_width, float* out);
+/* GPU milliseconds of the handle's last wis_align: ms[6] = encoder + cross K/V, decoder passes, matrix, DTW, and of the matrix:
+ * attention weights alone, normalise + filter alone */
+int wis_align_last_timing(wis_model_t* m, float* ms);
+/* op taps (device pointers), the launch helpers wis_align uses:
+ * wis_op_dtw: x fp32 [N][M] (N <= 511) -> text_idx / time_idx (room for N + M - 1 entries each), len[1]
+ * wis_op_align_matrix: q fp32 [n_heads_sel][T_tokens][64] finished queries, kx_f16 [n_heads_sel][8][T][8] (the cross-attention K
+ * image of those heads), softmax over T keys, cropped to `frames` -> out fp32 [T_tokens][frames] */
+int wis_op_dtw(int device, const float* x, int N, int M, int32_t* text_idx, int32_t* time_idx, int32_t* len);
+int wis_op_align_matrix(int device, const float* q, const void* kx_f16, int T_tokens, int n_heads_sel, int T, int frames, int width, float* out);
 /* the decoder pass wis_generate_draft_beam verifies a window with, alone: the tree rows of steps 1 .. n_steps of a beam trajectory (tok / org
  * [n_steps][beam]: per step the live beams' newest tokens and the beam each continued from) behind `prompt`, in ONE pass (tree self-attention by
  * ancestor table, cross-attention as row groups over the utterance's one K / V); logits [n_steps][beam][n_vocab]: row (s, j) = what a step fed

@@ -129,6 +129,23 @@ struct WeightSlabs {
   ~WeightSlabs() { hipSetDevice(device); for (void* p : slabs) hipFree(p); }
 };
 
+// word-level alignment (csrc/align.hip): the handle's alignment heads and the scratch its first wis_align allocates
+struct AlignState {
+  std::vector<int> heads;                 // (layer, head) pairs of wis_model_set_alignment_heads; empty: every head of the upper half of the decoder
+  bool ready = false;                     // the selection below matches `heads`
+  bool capture = false;                   // a wis_align decoder pass is running: dec_forward_frag hands every layer's finished cross-Q to align_capture_q
+  int nsel = 0, sel_cap = 0; size_t sel_bytes = 0;
+  std::vector<int> layer_s0;              // selected heads of layer l: [layer_s0[l], layer_s0[l + 1]) of the (layer, head)-sorted selection
+  int* d_sel_head = nullptr; long long* d_koff = nullptr;      // per selected head: its head index, the element offset of its K image in kx_all (utterance 0)
+  f16* qsel = nullptr;                    // captured queries [max_batch][nsel][n_text_ctx][64]
+  float *W = nullptr, *acc = nullptr;     // one chunk of heads' probabilities; the matrix [max_batch][tokens][n_audio_ctx]
+  unsigned* trace = nullptr; int *rev = nullptr, *path = nullptr, *d_meta = nullptr; float* probs = nullptr;
+  int cap_ub0 = 0, cap_t0 = 0, cap_P = 0, last_nmax = 0;
+  int kv_ub0 = 0;                         // first utterance of the group a wis_align decoder pass runs (dec_forward_frag offsets the cross K / V by it); 0 outside
+  hipEvent_t ev[5 + 128] = {}; int n_ev = 0;      // phase boundaries of the last call (wis_align_last_timing); ev[5..]: (weights, filter) pairs of the first 64 head chunks
+  bool ev_partial = false;                // the last call had more head chunks than event pairs: the weights / filter split is not reported
+};
+
 struct wis_model {
   wis_config_t cfg;
   int device;
@@ -195,6 +212,7 @@ struct wis_model {
   bool prof_on; bool prof_all;
   size_t enc_part_cap = 0;      // (utterance, head, query tile) triples the split-key encoder attention buffers were sized for
   std::atomic_flag busy = ATOMIC_FLAG_INIT;   // one compute call at a time per handle (BusyGuard)
+  AlignState al;
 };
 
 namespace {
@@ -722,6 +740,7 @@ static int spin_gave_up(wis_model* m, bool* gave_up) {
 // tw (draft verification at beam > 1): the M rows are nodes of ONE utterance's beam tree - self-attention by ancestor table (anc [M][aw], first
 // window position w0), cross-attention as B = M / 16 groups of R = 16 rows that all read utterance 0's K / V
 struct TreeWin { const int* anc; int w0, aw; const int* base = nullptr; };
+int align_capture_q(wis_model* m, int l, int M);      // align.hip
 constexpr int ANC_W = 32;      // ancestor-table entries per row = the most steps a window holds (beam 2 / 3: 32 steps = 64 / 96 rows)
 static int dec_forward_frag(wis_model* m, int M, int R, int B, bool want_logits, int sstride, int rmul, int chunks, const TreeWin* tw = nullptr) {
   const wis_config_t& c = m->cfg; hipStream_t st = m->st;
@@ -748,6 +767,7 @@ static int dec_forward_frag(wis_model* m, int M, int R, int B, bool want_logits,
     WIS_RET(launch_gemv_frag(st, g));
     WIS_RET(launch_dec_self_attn(st, m->dq, m->kc[l], m->vc[l], m->rm.pos, m->daoxf, M, H, d, ctx, R, sstride, rmul, nullptr, MB, tw ? tw->anc : nullptr, tw ? tw->w0 : 0, tw ? tw->aw : 0, tw ? tw->base : nullptr, m->sa_nb));
     if (fold) {
+      if (m->al.capture) { set_error("dec_forward_frag: an alignment pass needs the un-folded route (more than 8 rows per utterance)"); return WIS_E_STATE; }
       // ONE launch, three d x d problems on 3 d / 16 workgroups: x1 = x0 + Wo a + bo (residual rows + their LayerNorm partials; nobody
       // reads x1's fragment image any more, so none is written and x0's image stays valid for the other two), q_A = W'q x0 + W'q bo
       // from the layer input's image, q_B = (W'q Wo) a from the attention output's - the two k-step halves of the packed [W'q | W'q Wo]
@@ -771,8 +791,11 @@ static int dec_forward_frag(wis_model* m, int M, int R, int B, bool want_logits,
     g = base(m->dxf, w.p_cq, w.s_cq, w.b_cq, d, d, GV_LN | GV_OUT_F32);
     g.csum = w.c_cq; g.stat_in = m->dstat; g.y = m->dq;
     WIS_RET(launch_gemv_frag(st, g));
-    WIS_RET(launch_dec_cross_attn(st, m->dq, m->kx[l], m->vx[l], m->daoxf, m->part, m->counters, B, R, H, d, T, m->Tpad, chunks, nullptr, MB, nullptr, nullptr, nullptr,
+    // (wis_align decodes a batch in groups of utterances: the group's first utterance picks the K / V block the rows' b = 0 reads; 0 otherwise)
+    const size_t ku = (size_t)m->al.kv_ub0 * H * T * 64, vu = (size_t)m->al.kv_ub0 * H * 64 * m->Tpad;
+    WIS_RET(launch_dec_cross_attn(st, m->dq, m->kx[l] + ku, m->vx[l] + vu, m->daoxf, m->part, m->counters, B, R, H, d, T, m->Tpad, chunks, nullptr, MB, nullptr, nullptr, nullptr,
                                   (m->spin_now && !tw) ? m->ca_gran : nullptr, m->ca_epoch, nullptr, 0, tw ? 1 : 0));
+    if (m->al.capture) WIS_RET(align_capture_q(m, l, M));      // wis_align: m->dq holds this layer's finished cross-Q until the next layer's QKV projection
     }
     g = base(m->daoxf, w.p_cout, w.s_cout, w.b_cout, d, d, GV_RESID);
     g.y = m->dx; g.y_xf = m->dxf; g.ymb = MB; g.stat_out = m->dstat; g.prof = pr ? pr + 80 : nullptr;
@@ -810,6 +833,7 @@ int dec_forward(wis_model* m, int M, int R, int B, bool want_logits, int sstride
   static const bool no_frag = getenv("WIS_NO_FRAG") != nullptr;      // A/B switch: the round-1 batched path (LayerNorm launches + LDS-staged rows)
   if (tw) return dec_forward_frag(m, M, R, B, want_logits, sstride, rmul, chunks, tw);
   if (M > 8 && !no_frag) return dec_forward_frag(m, M, R, B, want_logits, sstride, rmul, chunks);
+  if (m->al.capture) { set_error("wis_align needs the batched-row decoder route (more than 8 rows per pass, WIS_NO_FRAG unset)"); return WIS_E_STATE; }
   // fused out-proj + cross-Q stage (load_weights: cq_fold): f16 decoder weights, <= 8 rows (the LayerNorm-fused row counts)
   const bool fold = m->cq_fold && M <= 8;
   // (r5) what the LayerNorm-folded projections (QKV, FFN1, the vocabulary) read - WIS_B1_LN = rows | f16 | partials:
@@ -1067,6 +1091,7 @@ void wis_model_destroy(wis_model_t* m) {
   if (m->h_pin) hipHostFree(m->h_pin);
   if (m->h_prog) hipHostFree(m->h_prog);
   for (int i = 0; i < 8; ++i) if (m->ev[i]) hipEventDestroy(m->ev[i]);
+  for (hipEvent_t e : m->al.ev) if (e) hipEventDestroy(e);
   if (m->st_enc) { hipStreamSynchronize(m->st_enc); hipStreamDestroy(m->st_enc); }
   if (m->ev_enc) hipEventDestroy(m->ev_enc);
   if (m->ev_ckv) hipEventDestroy(m->ev_ckv);
@@ -1090,6 +1115,7 @@ int wis_model_clone(wis_model_t* parent, wis_model_t** out) {
   m->w_ckv_all = parent->w_ckv_all; m->b_ckv_all = parent->b_ckv_all;
   m->s_proj = parent->s_proj; m->c_proj = parent->c_proj; m->b_proj = parent->b_proj; m->w8 = parent->w8; m->cq_fold = parent->cq_fold;
   m->use_graph = parent->use_graph;
+  m->al.heads = parent->al.heads;      // (the clone allocates its own align scratch on its first wis_align)
   memset(&m->timing, 0, sizeof(m->timing));
   int rc = WIS_OK;
   do {
@@ -2234,5 +2260,7 @@ int wis_op_dec_cross_attn_folded(int device, const float* q_raw, const float* xr
 
 }  // extern "C"
 
+// word-level alignment (wis_align, wis_op_dtw, wis_op_align_matrix): its kernels and driver, in this translation unit
+#include "align.hip"
 // speaker verification (wis_sv_*): its kernels and driver, in this translation unit
 #include "sv.hip"

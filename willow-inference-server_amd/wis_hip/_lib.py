@@ -95,6 +95,13 @@ SYMBOLS = [
     ("wis_debug_encode", _i, [_vp, _vp, _i, _i, _fp]),
     ("wis_debug_logits", _i, [_vp, _vp, _i, _i, C.POINTER(C.c_int32), _i, _fp]),
     ("wis_debug_logits_rows", _i, [_vp, _vp, _i, _i, C.POINTER(C.c_int32), _i, _i, _fp]),
+    ("wis_model_set_alignment_heads", _i, [_vp, C.POINTER(C.c_int32), _i]),
+    ("wis_align", _i, [_vp, _vp, _i, _i, C.POINTER(C.c_int32), _i, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), _i,
+                       C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), _fp]),
+    ("wis_debug_align_matrix", _i, [_vp, _vp, _i, _i, C.POINTER(C.c_int32), _i, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), _i, _fp]),
+    ("wis_align_last_timing", _i, [_vp, _fp]),
+    ("wis_op_dtw", _i, [_i, _vp, _i, _i, _vp, _vp, _vp]),
+    ("wis_op_align_matrix", _i, [_i, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
     ("wis_debug_tree_logits", _i, [_vp, _vp, _i, C.POINTER(C.c_int32), _i, _i, C.POINTER(C.c_int32), C.POINTER(C.c_int32), _i, _fp]),
     ("wis_debug_search", _i, [_vp, _vp, _i, _i, C.POINTER(GenOpts), C.POINTER(C.c_int32), C.POINTER(C.c_int32), _fp, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     ("wis_debug_handoff", _i, [_vp, _i, C.POINTER(_i), C.POINTER(_i)]),

@@ -58,6 +58,17 @@ class WhisperGenerationResult:
         return f"WhisperGenerationResult(sequences_ids={self.sequences_ids}, scores={self.scores})"
 
 
+class WhisperAlignmentResult:
+    """CTranslate2's `WhisperAlignmentResult`: `alignments` = [(text_index, time_index), ...] (the DTW path), `text_token_probs`."""
+
+    def __init__(self, alignments, text_token_probs):
+        self.alignments = alignments
+        self.text_token_probs = text_token_probs
+
+    def __repr__(self):
+        return f"WhisperAlignmentResult(alignments={self.alignments!r}, text_token_probs={self.text_token_probs!r})"
+
+
 class _Replica:
     def __init__(self, handle, device, n_mels=W.N_MELS):
         self.handle, self.device = handle, device
@@ -338,6 +349,7 @@ class Whisper:
         for r in list(self._replicas):
             for _ in range(per_dev - 1):
                 self._replicas.append(_Replica(clone_handle(r.handle), r.device, arch["n_mels"]))
+        self._set_alignment_heads(cfg.get("alignment_heads"))
         self.max_batch, self.max_beam = max_batch, max_beam
         self._pick = threading.Lock()
         # concurrent generate() calls coalesce into device batches, one worker per GPU replica (wis_hip/batching.py)
@@ -352,6 +364,7 @@ class Whisper:
         self.arch, self.decode_config = arch, decode_config or {}
         self.special = special_tokens_for(arch, self.decode_config.get("special"), self.decode_config.get("lang_ids"))
         self._replicas = [_Replica(h, d, arch["n_mels"]) for h, d in handles]
+        self._set_alignment_heads(self.decode_config.get("alignment_heads"))
         self.max_batch, self.max_beam = max_batch, max_beam
         self._pick = threading.Lock()
         self._batcher = MicroBatcher(self._replicas, _run_batch, lambda key: _capacity(max_batch, key))
@@ -522,6 +535,74 @@ class Whisper:
     def _generate_chunk(self, r, mel, prompts, P, beam, max_new, lp, patience, suppress_blank, suppress_default, fixed_new, kind):
         """One `wis_generate` call on replica r (the caller serialises access to r)."""
         return _generate_chunk(r, mel, prompts, P, beam, max_new, lp, patience, suppress_blank, suppress_default, fixed_new, kind)
+
+    def _set_alignment_heads(self, heads):
+        """[[layer, head], ...] from the checkpoint (config.json / generation_config.json); None or empty: every head of the upper
+        half of the decoder layers (openai-whisper's default)."""
+        pairs = np.ascontiguousarray(np.asarray(W.normalize_alignment_heads(heads), np.int32).reshape(-1, 2))
+        self.alignment_heads = pairs.tolist()
+        for r in self._replicas:
+            if r.handle:      # (a host-only stand-in has no engine handle)
+                _lib.check(_lib.load().wis_model_set_alignment_heads(r.handle, pairs.ctypes.data_as(C.POINTER(C.c_int32)), len(pairs)))
+
+    def align(self, features, start_sequence, text_tokens, num_frames, *, median_filter_width=7, input_kind=_lib.WIS_IN_MEL_HOST):
+        """CTranslate2's `Whisper.align(features, start_sequence, text_tokens, num_frames, *, median_filter_width=7)`: the text
+        tokens of every utterance are aligned with its audio frames from the cross-attention of the model's alignment heads
+        (dynamic time warping, all on the GPU: csrc/align.hip).  `start_sequence`: the prompt up to the task token (no
+        `<|notimestamps|>`: the engine adds it), one for the batch; `text_tokens`: one list per utterance (no eot); `num_frames`:
+        mel frames per utterance (an int serves the whole batch).  Returns a list of `WhisperAlignmentResult` with `.alignments`
+        [(text_index, time_index)] (time_index counts encoder frames of 20 ms; text_index == len(text) is the eot row) and
+        `.text_token_probs`.  Signature and result are restated from CTranslate2's documentation; the real library cannot be
+        installed here to pin them against.  `input_kind` is an extension of this shim (host mel windows or host PCM windows, as `generate`
+        takes them).  `features` on the device: `StorageView`s are host arrays in this shim; a device
+        pointer goes through `align_from_device`."""
+        mel = self._features(features, input_kind)
+        return self._align(mel, _lib.ptr, input_kind, mel.shape[0], start_sequence, text_tokens, num_frames, median_filter_width)
+
+    def align_from_device(self, device, mel_device_ptr, start_sequence, text_tokens, num_frames, *, median_filter_width=7, replica=None):
+        """`align` on one [n_mels][3000] fp32 window already in `device`'s memory (what generate_from_device takes)."""
+        r = replica or self.replica_on(device)
+        return self._align(None, None, _lib.WIS_IN_MEL_DEV, 1, start_sequence, text_tokens, num_frames, median_filter_width, dev=(r, mel_device_ptr))
+
+    def _align(self, mel, to_ptr, kind, B, start_sequence, text_tokens, num_frames, width, dev=None):
+        if B < 1 or len(text_tokens) != B:
+            raise ValueError(f"align: {len(text_tokens)} token lists for a batch of {B}")
+        nf = [int(num_frames)] * B if np.isscalar(num_frames) else [int(x) for x in num_frames]
+        if len(nf) != B:
+            raise ValueError(f"align: {len(nf)} num_frames for a batch of {B}")
+        start = np.ascontiguousarray(np.asarray(list(start_sequence), np.int32))
+        n_ctx, n_audio = W.N_TEXT_CTX, W.N_AUDIO_CTX
+        if int(width) < 1 or int(width) % 2 == 0 or int(width) > 63:
+            raise ValueError(f"align: median_filter_width={width} must be odd and within 1..63")
+        for t, f in zip(text_tokens, nf):
+            if len(start) + 1 + len(t) > n_ctx:
+                raise ValueError(f"align: {len(start)} start + 1 + {len(t)} text tokens exceed the decoder's {n_ctx} positions")
+            if not 2 <= f <= 2 * n_audio:
+                raise ValueError(f"align: num_frames={f} outside 2..{2 * n_audio}")
+        i32 = lambda a: a.ctypes.data_as(C.POINTER(C.c_int32))
+        out = []
+        r = dev[0] if dev else self._acquire()
+        try:
+            with r.lock:
+                for s in range(0, B, self.max_batch):
+                    toks = [list(map(int, t)) for t in text_tokens[s:s + self.max_batch]]
+                    b = len(toks)
+                    flat = np.ascontiguousarray(np.asarray([x for t in toks for x in t] or [0], np.int32))
+                    lens = np.asarray([len(t) for t in toks], np.int32)
+                    frames = np.asarray(nf[s:s + b], np.int32)
+                    cap = n_ctx + n_audio
+                    pt, pf = np.zeros((b, cap), np.int32), np.zeros((b, cap), np.int32)
+                    pl, probs = np.zeros(b, np.int32), np.zeros((b, n_ctx), np.float32)
+                    src = dev[1] if dev else to_ptr(np.ascontiguousarray(mel[s:s + b]))
+                    _lib.check(_lib.load().wis_align(r.handle, src, kind, b, i32(start), len(start), i32(flat), i32(lens), i32(frames), int(width),
+                                                     i32(pt), i32(pf), i32(pl), probs.ctypes.data_as(C.POINTER(C.c_float))))
+                    for u in range(b):
+                        n = int(pl[u])
+                        out.append(WhisperAlignmentResult(list(zip(pt[u, :n].tolist(), pf[u, :n].tolist())), probs[u, :lens[u]].tolist()))
+        finally:
+            if not dev:
+                self._release(r)
+        return out
 
     def detect_language(self, features, input_kind=_lib.WIS_IN_MEL_HOST):
         mel = self._features(features, input_kind)

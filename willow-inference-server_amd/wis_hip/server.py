@@ -152,11 +152,14 @@ def create_app(models=None, settings=None, max_workers=None, sv=None):
             raise BadRequest(f"beam_size {beam} outside 1..{s.max_beam}")
         return dict(model=model, beam_size=beam,
                     detect_language=_as_bool(q.get("detect_language"), s.detect_language), force_language=q.get("force_language") or None,
-                    translate=_as_bool(q.get("translate"), False), timestamps=_as_bool(q.get("timestamps"), False))
+                    translate=_as_bool(q.get("translate"), False), timestamps=_as_bool(q.get("timestamps"), False),
+                    word_timestamps=_as_bool(q.get("word_timestamps"), False))
 
     async def run_whisper(audio_file, p):
         loop = asyncio.get_running_loop()
         kw = {"timestamps": True} if p["timestamps"] else {}      # (segment times: one 30 s window; longer audio is a 400)
+        if p["word_timestamps"]:                                  # (word times imply segment times; no vocabulary / long audio is a 400)
+            kw = {"word_timestamps": True}
         return await loop.run_in_executor(pool, lambda: do_whisper(audio_file, p["model"], p["beam_size"], "transcribe", p["detect_language"],
                                                                    p["force_language"], p["translate"], models=get_models(), **kw))
 
@@ -199,7 +202,7 @@ def create_app(models=None, settings=None, max_workers=None, sv=None):
         out = {"infer_time": infer_time, "infer_speedup": infer_speedup, "audio_duration": audio_duration, "language": language, "text": text}
         if translation:
             out["translation"] = translation
-        if p["timestamps"]:
+        if p["timestamps"] or p["word_timestamps"]:
             out["segments"] = res.segments
         return JSONResponse(content=out)
 
@@ -259,7 +262,7 @@ def create_app(models=None, settings=None, max_workers=None, sv=None):
             out = {"language": language, "text": text}
         if translation:
             out["translation"] = translation
-        if p["timestamps"]:
+        if p["timestamps"] or p["word_timestamps"]:
             out["segments"] = res.segments
         if voice_auth:
             out["voice_auth"] = sv_results

@@ -494,6 +494,7 @@ def load_hf_dir(path):
     if os.path.exists(gj):
         with open(gj) as f:
             gen = json.load(f)
+    align_heads = normalize_alignment_heads(gen.get("alignment_heads"))
     a = arch_from_weights(w, hc.get("decoder_attention_heads"))
     # special ids: the vocabulary's layout, then what the tokenizer names, then what the generation config states
     ov = {}
@@ -514,7 +515,16 @@ def load_hf_dir(path):
         cfg["suppress_ids_begin"] = [int(t) for t in beg]
     if "lang_to_id" in gen:
         cfg["lang_ids"] = sorted(int(v) for v in gen["lang_to_id"].values())
+    if align_heads:
+        cfg["alignment_heads"] = align_heads
     return w, a, cfg
+
+
+def normalize_alignment_heads(heads):
+    """[[layer, head], ...] as sorted, de-duplicated int pairs (CTranslate2 config.json / HF generation_config.json `alignment_heads`).
+    Absent or empty means openai-whisper's default: every head of the upper half of the decoder layers."""
+    out = sorted({(int(l), int(h)) for l, h in (heads or [])})
+    return [[l, h] for l, h in out]
 
 
 def _n_layers(w, side):
@@ -559,6 +569,11 @@ def load_model_dir(path):
             with open(cj) as f:
                 cj = json.load(f)
             cfg = {k: cj[k] for k in ("suppress_ids", "suppress_ids_begin", "lang_ids") if k in cj}
+            if cj.get("alignment_heads"):
+                cfg["alignment_heads"] = normalize_alignment_heads(cj["alignment_heads"])
+        ah = np.asarray(attrs["decoder/alignment_heads"]) if "decoder/alignment_heads" in attrs else None
+        if "alignment_heads" not in cfg and ah is not None and ah.ndim == 2 and ah.shape[1] == 2 and ah.shape[0] > 0:
+            cfg["alignment_heads"] = normalize_alignment_heads(ah.tolist())      # (a model.bin that carries the pairs as an attribute)
         ov = {}
         if os.path.exists(os.path.join(path, "tokenizer.json")):
             ov.update(special_tokens_from_tokenizer_json(os.path.join(path, "tokenizer.json")))
@@ -584,7 +599,7 @@ def convert_hf_to_ct2_dir(hf_dir, out_dir):
     write_ct2_model_bin(os.path.join(out_dir, "model.bin"), w, aliases={"decoder/projection/weight": "decoder/embeddings/weight"})
     st = special_tokens(a["n_vocab"], cfg.get("special"))
     full = dict(suppress_ids=cfg.get("suppress_ids", st.default_suppress_ids()), suppress_ids_begin=cfg.get("suppress_ids_begin", [220, st.eot]),
-                lang_ids=cfg.get("lang_ids", st.lang_ids), alignment_heads=[])
+                lang_ids=cfg.get("lang_ids", st.lang_ids), alignment_heads=cfg.get("alignment_heads", []))
     with open(os.path.join(out_dir, "config.json"), "w") as f:
         json.dump(full, f)
     for fn in ("tokenizer.json", "tokenizer_config.json", "preprocessor_config.json", "vocab.json", "merges.txt", "added_tokens.json",

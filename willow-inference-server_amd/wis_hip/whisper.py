@@ -50,7 +50,7 @@ def model_special_tokens(model):
     return st if isinstance(st, W.SpecialTokens) else W.special_tokens(W.N_VOCAB)
 
 
-def segments_from_tokens(ids, tokenizer, offset=0.0, duration=WINDOW_S, special=None):
+def segments_from_tokens(ids, tokenizer, offset=0.0, duration=WINDOW_S, special=None, keep_tokens=False):
     """Timed segments of one decoded window, split as openai-whisper's transcribe() splits a window's tokens: two consecutive
     timestamps close one segment and open the next; a single timestamp before the end (EOT) closes the last segment; text that
     no timestamp closes ends at the window's `duration`.  A window with no consecutive pair is one segment from `offset` to its last
@@ -61,7 +61,10 @@ def segments_from_tokens(ids, tokenizer, offset=0.0, duration=WINDOW_S, special=
     is_ts = [t >= tb for t in toks]
 
     def seg(start, end, piece):
-        return {"start": round(offset + start, 2), "end": round(offset + end, 2), "text": tokenizer.decode([t for t in piece if t < eot]).strip()}
+        d = {"start": round(offset + start, 2), "end": round(offset + end, 2), "text": tokenizer.decode([t for t in piece if t < eot]).strip()}
+        if keep_tokens:      # (word_timestamps: the segment's text tokens, for the alignment)
+            d["tokens"] = [t for t in piece if t < eot]
+        return d
 
     def at(t):
         return (t - tb) * TIME_PRECISION
@@ -95,6 +98,96 @@ def special_ids_from_tokenizer_json(path):
     with open(path, "r", encoding="utf-8") as f:
         tj = json.load(f)
     return sorted({int(t["id"]) for t in tj.get("added_tokens", []) if t.get("special")})
+
+
+# ---- words (openai-whisper tokenizer.split_to_word_tokens + timing.merge_punctuations, restated) ---------------------------------------
+NO_SPACE_LANGUAGES = ("zh", "ja", "th", "lo", "my", "yue")
+PREPEND_PUNCTUATIONS = "\"'“¿([{-"
+APPEND_PUNCTUATIONS = "\"'.。,，!！?？:：”)]}、"
+_PUNCTUATION = "!\"#$%&'()*+,-./:;<=>?@[\\]^_`{|}~"      # string.punctuation
+
+
+def split_tokens_on_unicode(tokens, decode):
+    """Pieces that decode to whole unicode characters: a token that ends inside a multi-byte character (the decoder shows U+FFFD
+    where the full text has none) is held back until the character is complete."""
+    full, rep = decode(tokens), "\ufffd"
+    words, word_tokens, cur, off = [], [], [], 0
+    for t in tokens:
+        cur.append(int(t))
+        dec = decode(cur)
+        if rep not in dec or full[off + dec.index(rep)] == rep:
+            words.append(dec)
+            word_tokens.append(cur)
+            cur = []
+            off += len(dec)
+    return words, word_tokens
+
+
+def split_tokens_on_spaces(tokens, decode, eot):
+    subwords, subword_tokens = split_tokens_on_unicode(tokens, decode)
+    words, word_tokens = [], []
+    for sw, st in zip(subwords, subword_tokens):
+        if st[0] >= eot or sw.startswith(" ") or sw.strip() in _PUNCTUATION or not words:
+            words.append(sw)
+            word_tokens.append(list(st))
+        else:
+            words[-1] += sw
+            word_tokens[-1].extend(st)
+    return words, word_tokens
+
+
+def split_to_word_tokens(tokens, decode, language, eot):
+    """one word per unicode piece for the languages written without spaces, else pieces merged up to the next leading space"""
+    if language in NO_SPACE_LANGUAGES:
+        return split_tokens_on_unicode(tokens, decode)
+    return split_tokens_on_spaces(tokens, decode, eot)
+
+
+def merge_punctuations(words, word_tokens, prepended=PREPEND_PUNCTUATIONS, appended=APPEND_PUNCTUATIONS):
+    """opening punctuation joins the word after it, closing punctuation the word before it; returns the non-empty words"""
+    words, word_tokens = list(words), [list(t) for t in word_tokens]
+    i, j = len(words) - 2, len(words) - 1
+    while i >= 0:
+        if words[i].startswith(" ") and words[i].strip() in prepended:
+            words[j], word_tokens[j] = words[i] + words[j], word_tokens[i] + word_tokens[j]
+            words[i], word_tokens[i] = "", []
+        else:
+            j = i
+        i -= 1
+    i, j = 0, 1
+    while j < len(words):
+        if not words[i].endswith(" ") and words[j] in appended:
+            words[i], word_tokens[i] = words[i] + words[j], word_tokens[i] + word_tokens[j]
+            words[j], word_tokens[j] = "", []
+        else:
+            i = j
+        j += 1
+    keep = [k for k in range(len(words)) if word_tokens[k]]
+    return [words[k] for k in keep], [word_tokens[k] for k in keep]
+
+
+def words_from_alignment(segments, alignment, probs, tokenizer, language, special, duration):
+    """`words` of every segment ({"tokens": text tokens} as segments_from_tokens(keep_tokens=True) leaves them) from ONE alignment of the
+    window's text tokens: a word starts at the jump time of its first token and ends at the jump time of the next word's first token
+    (find_alignment: time_index / 50 at the path rows where text_index advances; the row after the last token is eot's);
+    its probability is the mean of its tokens'."""
+    jumps, last = [], -1
+    for ti, fi in alignment:
+        if ti != last:
+            jumps.append(min(fi * TIME_PRECISION, duration))
+            last = ti
+    n_text = sum(len(sg["tokens"]) for sg in segments)
+    if len(jumps) != n_text + 1:
+        raise RuntimeError(f"alignment covers {len(jumps)} rows, the text has {n_text} tokens + eot")
+    o = 0
+    for sg in segments:
+        words, word_tokens = merge_punctuations(*split_to_word_tokens(sg["tokens"], tokenizer.decode, language, special.eot))
+        sg["words"] = []
+        for w, toks in zip(words, word_tokens):
+            sg["words"].append({"word": w, "start": round(jumps[o], 2), "end": round(jumps[o + len(toks)], 2),
+                                "probability": float(np.mean(probs[o:o + len(toks)]))})
+            o += len(toks)
+    return segments
 
 
 class _Tokenizer:
@@ -224,7 +317,13 @@ def chunkit(lst, num):
 
 
 def do_whisper(audio_file, model, beam_size=None, task="transcribe", detect_language=False, force_language=None, translate=False,
-               models=None, fixed_new_tokens=None, timestamps=False):
+               models=None, fixed_new_tokens=None, timestamps=False, word_timestamps=False):
+    """word_timestamps=True implies timestamps=True: after the search the window's text tokens are aligned with the audio in one
+    `Whisper.align` call (cross-attention of the alignment heads + DTW on the GPU) and every segment gains
+    `words: [{word, start, end, probability}]`, grouped as openai-whisper's split_to_word_tokens + merge_punctuations group them.
+    Out of scope: the pause / median-duration heuristics of openai-whisper's add_word_timestamps, audio over 30 s, and `translate`
+    (the translation pass carries no words).  A model without a tokenizer vocabulary raises ValueError."""
+    timestamps = timestamps or word_timestamps
     models = models or default_models()
     s = models.settings
     if fixed_new_tokens is None:
@@ -271,6 +370,8 @@ def do_whisper(audio_file, model, beam_size=None, task="transcribe", detect_lang
         features, kind = audio.log_mel_spectrogram(windows, n_mels=n_mels, device=dev).numpy(), ctranslate2._lib.WIS_IN_MEL_HOST
     total_chunk_count = features.shape[0]
     tokenizer = models.tokenizer_for(model)
+    if word_timestamps and not getattr(tokenizer, "has_vocabulary", False):
+        raise ValueError("word_timestamps need the checkpoint's tokenizer vocabulary (tokenizer.json next to the model)")
 
     # STEP 2 — language
     language = s.language
@@ -300,7 +401,16 @@ def do_whisper(audio_file, model, beam_size=None, task="transcribe", detect_lang
         tokens = results[0].sequences_ids[0]
     segments = None
     if timestamps:
-        segments = segments_from_tokens(tokens, tokenizer, 0.0, min(audio_duration / 1000.0, WINDOW_S), special)
+        duration = min(audio_duration / 1000.0, WINDOW_S)
+        segments = segments_from_tokens(tokens, tokenizer, 0.0, duration, special, keep_tokens=word_timestamps)
+        if word_timestamps:
+            text_tokens = [t for sg in segments for t in sg["tokens"]]
+            num_frames = max(2, min(3000, -(-pcm.shape[0] // audio.HOP_LENGTH)))
+            al = whisper_model.align(ctranslate2.StorageView.from_array(np.ascontiguousarray(features[0:1])), prompt[:3], [text_tokens], [num_frames],
+                                     input_kind=kind)[0]
+            words_from_alignment(segments, al.alignments, al.text_token_probs, tokenizer, language, special, duration)
+            for sg in segments:
+                del sg["tokens"]
         text = tokenizer.decode([t for t in tokens if t < special.timestamp_begin]).strip()
     else:
         text = tokenizer.decode(tokens).strip()
