@@ -403,7 +403,7 @@ int align_run(wis_model* m, const float* input, int input_kind, int B, const int
   hipEventRecord(a.ev[1], st);
   int* dN = a.d_meta; int* dF = a.d_meta + B; int* d_tgt = a.d_meta + 3 * c.max_batch; int* d_dst = d_tgt + MAX_ROWS;
   {
-    int* h = m->h_pin + 4096;
+    int* h = m->h_pin->al_frames;
     memcpy(h, hN.data(), (size_t)B * 4); memcpy(h + B, hF.data(), (size_t)B * 4);
     WIS_HIP_CHECK(hipMemcpyAsync(a.d_meta, h, (size_t)2 * B * 4, hipMemcpyHostToDevice, st));
   }
@@ -428,10 +428,10 @@ int align_run(wis_model* m, const float* input, int input_kind, int B, const int
       for (int attempt = 0; attempt < 2; ++attempt) {      // (a pass whose granule hand-off gave up is repeated in the ticket form)
         SpinClaim claim(m, nb);
         WIS_RET(upload_rows(m, tok, pos, slot, ls));
-        int* h = m->h_pin + 8192;
-        memcpy(h, tgt.data(), (size_t)M * 4); memcpy(h + MAX_ROWS, dst.data(), (size_t)M * 4);
-        WIS_HIP_CHECK(hipMemcpyAsync(d_tgt, h, (size_t)M * 4, hipMemcpyHostToDevice, st));
-        WIS_HIP_CHECK(hipMemcpyAsync(d_dst, h + MAX_ROWS, (size_t)M * 4, hipMemcpyHostToDevice, st));
+        PinnedScratch* h = m->h_pin;
+        memcpy(h->al_tgt, tgt.data(), (size_t)M * 4); memcpy(h->al_dst, dst.data(), (size_t)M * 4);
+        WIS_HIP_CHECK(hipMemcpyAsync(d_tgt, h->al_tgt, (size_t)M * 4, hipMemcpyHostToDevice, st));
+        WIS_HIP_CHECK(hipMemcpyAsync(d_dst, h->al_dst, (size_t)M * 4, hipMemcpyHostToDevice, st));
         a.capture = true; a.kv_ub0 = ub0;      // the group's rows read the cross K / V of utterances ub0 .. ub0 + nb - 1
         const int rc = dec_forward(m, M, 16, nb, want_dtw, 1, 0);
         a.capture = false; a.kv_ub0 = 0;

@@ -2729,7 +2729,7 @@ int launch_greedy_pick(hipStream_t st, const float* st_max, const float* st_sum,
 // PSL = pool entries per thread: 16 covers beam <= 5 (5 x 64 x 10 = 3200 entries), 32 the largest beam (8 x 64 x 16)
 // End of a beam step for one workgroup (thread 0, after the workgroup's global writes are fenced): count it; the workgroup that
 // ends the step as the LAST of the grid publishes the step to the host-mapped progress block - one 8-byte system-scope release
-// store that the host polls between graph launches (model.hip generate_impl), so a search that ends on EOT is noticed without a
+// store that the host polls between graph launches (generate.hip run_paced), so a search that ends on EOT is noticed without a
 // stream round trip.  Results of finished utterances were written to the same block (and fenced at system scope) before their
 // workgroup's count, so whoever reads "done = B" in the record finds them there.
 __device__ __forceinline__ void publish_step(const BeamState& bs) {
@@ -2959,7 +2959,7 @@ int launch_beam_step(hipStream_t st, const float* st_max, const float* st_sum, c
 }
 
 // =======================================================================================
-// Draft verification at beam > 1 (model.hip generate_impl; one utterance): a window of replayed beam steps is queued WITHOUT host round trips; this
+// Draft verification at beam > 1 (generate.hip seed_beam_draft; one utterance): a window of replayed beam steps is queued WITHOUT host round trips; this
 // one-workgroup kernel behind every replayed step matches the live set the step produced (tokens + the beams they continued from, as beam_step_kernel
 // recorded them in bs.traj) with the draft's entry for that step - as SETS: two candidates whose scores tie to within the summation order of a pass may
 // swap beam slots between the draft's search and this one, which changes nothing about the search itself, so live beam j may sit in ANY slot of the draft

@@ -1,0 +1,657 @@
+// generate.hip — the generate driver (wis_generate, wis_generate_draft, wis_generate_draft_beam) as a sequence of stages.
+// Compiled as part of model.hip's translation unit (included behind the model lifecycle), like align.hip and sv.hip.
+//
+//   make_gen_ctx      every argument check, the resolved shape and sampling options of the call
+//   stage_search      search counters, prompt rows, progress block: staged before anything the encoder produces
+//   front_half        log-mel, encoder, cross-K/V (on a stream of its own while the handle is alone on the GPU)
+//   seed_*            three ways to "the search stands after `steps` passes": merged prefill, greedy draft, beam-draft windows
+//   StepGraph         the decode step as a cached HIP graph (three self-attention lengths)
+//   run_burst / run_paced      the two step loops
+//   results_*         three forms of result read-back, then the timing record
+
+// what the sampling tail reads of a call (wis_debug_search builds one for a search over given logits)
+struct SampleCtx {
+  wis_model* m; hipStream_t st;
+  int B, P, beam;
+  SampleCfg sc; const float* bias_all;
+  bool ts; int ts_max_init;      // Whisper's timestamp rules (prompts without <|notimestamps|>): a pre-pass ahead of the sampling statistics of every step
+};
+// everything a stage needs to know about the call: built once (make_gen_ctx), read-only afterwards
+struct GenCtx : SampleCtx {
+  const float* input; const int32_t* prompt; const wis_gen_opts_t* o;
+  const int32_t *draft, *draft_org; int n_draft;
+  int max_new; float patience;
+  std::chrono::steady_clock::time_point t0;      // total_ms counts from here: the shape is resolved, nothing is enqueued yet
+  int sot_row;                   // no_speech_prob: the prompt row that reads <|startoftranscript|> (the same in every utterance of the batch); -1: not asked
+  bool drafting, beam_draft;
+};
+
+// draft / n_draft: wis_generate_draft (one utterance, beam 1): the tokens of an earlier hypothesis to verify first
+// draft_org (beam > 1, wis_generate_draft_beam): draft = [n_draft][beam] tokens, draft_org = [n_draft][beam] the beam slot each continued from -
+// the trajectory of an earlier SEARCH (wis_last_trajectory)
+// None of the checks depends on device state: a refused call has enqueued nothing.
+static int make_gen_ctx(wis_model* m, const float* input, int B, const int32_t* prompt, int P, const wis_gen_opts_t* o,
+                        const int32_t* draft, int n_draft, const int32_t* draft_org, GenCtx* out) {
+  const wis_config_t& c = m->cfg;
+  GenCtx& g = *out;
+  g.m = m; g.st = m->st; g.input = input; g.prompt = prompt; g.o = o; g.draft = draft; g.draft_org = draft_org; g.n_draft = n_draft; g.B = B; g.P = P;
+  const int beam = g.beam = o->beam_size < 1 ? 1 : o->beam_size;
+  WIS_RET(check_batch(m, B, beam));
+  WIS_RET(check_patience(beam, o->patience));
+  if (P < 1 || P > 16 || B * P > MAX_ROWS) { set_error("prompt length %d unsupported (1..16, B*P <= %d)", P, MAX_ROWS); return WIS_E_UNSUPPORTED; }
+  int max_new = o->max_new_tokens > 0 ? o->max_new_tokens : std::min(c.n_text_ctx / 2, c.n_text_ctx - P);
+  if (max_new > MAX_STEPS) max_new = MAX_STEPS;
+  if (P - 1 + max_new > c.n_text_ctx) max_new = c.n_text_ctx - (P - 1);
+  g.max_new = max_new;
+  for (int i = 0; i < B * P; ++i) if (prompt[i] < 0 || prompt[i] >= c.n_vocab) { set_error("prompt token %d out of range", prompt[i]); return WIS_E_ARG; }
+  g.t0 = std::chrono::steady_clock::now();
+  g.sc = make_sample_cfg(m, o, beam, max_new, &g.patience);
+  g.bias_all = o->suppress_default ? m->bias_all : nullptr;
+  const bool drafting = g.drafting = draft != nullptr && n_draft > 0;
+  const bool beam_draft = g.beam_draft = drafting && draft_org != nullptr;
+  if (drafting && B != 1) { set_error("wis_generate_draft: one utterance per call (got B = %d)", B); return WIS_E_UNSUPPORTED; }
+  if (drafting && !beam_draft && beam != 1) { set_error("wis_generate_draft: beam_size 1 (a beam search is drafted by its trajectory: wis_generate_draft_beam)"); return WIS_E_UNSUPPORTED; }
+  g.ts = o->timestamps != 0;
+  g.ts_max_init = o->max_initial_timestamp_index < 0 ? -1 : o->max_initial_timestamp_index;
+  if (g.ts && draft != nullptr) { set_error("timestamps: not available for drafted decodes (wis_generate_draft / wis_generate_draft_beam)"); return WIS_E_UNSUPPORTED; }
+  int sot_row = -1;
+  if (o->no_speech_prob && !drafting) {
+    for (int i = 0; i < P; ++i) if (prompt[i] == c.sot) { sot_row = i; break; }
+    for (int b = 1; b < B && sot_row >= 0; ++b) if (prompt[b * P + sot_row] != c.sot) sot_row = -1;
+    if (sot_row < 0) { set_error("no_speech_prob: the prompts hold no common <|startoftranscript|> position"); return WIS_E_ARG; }
+  }
+  g.sot_row = sot_row;
+  if (beam_draft && (beam < 2 || n_draft > MAX_STEPS)) { set_error("wis_generate_draft_beam: beam_size >= 2 and at most 256 draft steps (got %d, %d)", beam, n_draft); return WIS_E_ARG; }
+  if (drafting) for (int i = 0; i < n_draft * (beam_draft ? beam : 1); ++i) if (draft[i] < 0 || draft[i] >= c.n_vocab) { set_error("draft token %d out of range", draft[i]); return WIS_E_ARG; }
+  if (beam_draft) for (int i = 0; i < n_draft * beam; ++i) if (draft_org[i] < 0 || draft_org[i] >= beam) { set_error("draft origin %d outside [0, beam_size)", draft_org[i]); return WIS_E_ARG; }
+  return WIS_OK;
+}
+
+// ---- decode state first: search counters and the prompt rows depend on nothing the encoder produces, and staged from pinned
+// memory they cost the host no wait - the whole chain log-mel -> encoder -> cross-K/V -> prefill is enqueued behind them in one go
+// (the prefill's ~230 launches are issued while the encoder runs instead of after two stream drains)
+static int stage_search(const GenCtx& g) {
+  wis_model* m = g.m; const int B = g.B, P = g.P, beam = g.beam;
+  WIS_RET(init_beam_state(m, B, beam));
+  m->last_B = B; m->last_beam = beam;
+  if (!g.drafting || g.beam_draft) {
+    std::vector<int> tok(B * P), pos(B * P), slot(B * P), ls(B * P);
+    for (int b = 0; b < B; ++b) for (int i = 0; i < P; ++i) { tok[b * P + i] = g.prompt[b * P + i]; pos[b * P + i] = i; slot[b * P + i] = b * beam; ls[b * P + i] = b * beam; }
+    WIS_RET(upload_rows(m, tok, pos, slot, ls, false));
+  }
+  // a give-up flag raised by the PREVIOUS call's over-run step (it ran after that call had returned) says nothing about this call: cleared
+  // behind that step, in stream order, before this call's first decoder pass can raise it again
+  if (m->overrun_left) { WIS_HIP_CHECK(hipMemsetAsync(m->ca_epoch, 0, 4, g.st)); m->overrun_left = false; }
+  __atomic_store_n(&m->h_prog[HP_REC], 0ull, __ATOMIC_RELAXED);      // (a record of an earlier call's over-run step may still land here: it carries that call's generation)
+  m->h_prog[HP_DONE_STEP] = 0; m->h_prog[HP_DONE_STAMP] = 0; m->h_prog[HP_STAMP0] = 0;
+  return WIS_OK;
+}
+
+// Front half on a stream of its own.  A search that ended on EOT may have left ONE over-run decode step running on `st` (run_paced): the
+// log-mel and the encoder of this call touch none of the decoder's buffers, so they start at once beside it instead of behind it;
+// the cross-K/V projection (which overwrites what that step still reads) and everything after it stay on `st`.  st_enc waits for the
+// previous call's cross-K/V projection - the last reader of the encoder's output buffer.
+// ... but only while this is the ONLY call running on the GPU.  HIP streams share a handful of hardware queues (four by default): with
+// several replicas decoding at once a second stream per handle puts one replica's encoder and another's decode chain into the same
+// queue, and the chain waits behind 100 us GEMMs - measured, 8 utterances per batch, 2 / 3 / 4 batches in flight: 130 / 151 / 145
+// utterances/s with the second stream against 165 / 178 / 165 without.  Under that load the over-run step costs next to nothing anyway
+// (the GPU is shared; the step is a thin chain).
+static int front_half(const GenCtx& g) {
+  wis_model* m = g.m; hipStream_t st = g.st; const int B = g.B;
+  static const bool one_stream = getenv("WIS_ONE_STREAM") != nullptr;      // A/B switch
+  static const bool two_streams = getenv("WIS_TWO_STREAMS") != nullptr;    // A/B switch: the second stream whatever else runs
+  const bool alone = g_active_calls[m->device & 63].load(std::memory_order_relaxed) <= 1;
+  hipStream_t se = (one_stream || !(alone || two_streams)) ? st : m->st_enc;
+  if (se != st) WIS_HIP_CHECK(hipStreamWaitEvent(se, m->ev_ckv, 0));
+  WIS_HIP_CHECK(hipEventRecord(m->ev[0], se));
+  WIS_RET(stage_input(m, g.input, g.o->input_kind, B, se));
+  WIS_HIP_CHECK(hipEventRecord(m->ev[1], se));
+  WIS_RET(run_encoder(m, B, se));
+  WIS_HIP_CHECK(hipEventRecord(m->ev[2], se));
+  if (se != st) { WIS_HIP_CHECK(hipEventRecord(m->ev_enc, se)); WIS_HIP_CHECK(hipStreamWaitEvent(st, m->ev_enc, 0)); }
+  WIS_RET(run_cross_kv(m, B));
+  WIS_HIP_CHECK(hipEventRecord(m->ev[3], st));
+  WIS_HIP_CHECK(hipEventRecord(m->ev_ckv, st));
+  return WIS_OK;
+}
+
+// The sampling tail of a decoder pass: timestamp rules -> candidate statistics -> beam step -> cache reorder.  The logits row of (b, j) is
+// b*rows.b + j*rows.j + rows.off: a step samples beam j from row b*beam + j {beam, 1, 0}, the pass that carries the prompt samples every beam from the
+// last prompt row {P, 0, P - 1}.  TAIL_TAPS: the tap build's stamp rows of the two sampling kernels (the product build carries none).
+// TAIL_NO_CACHE: a search over given logits has no cache to reorder (wis_debug_search).
+struct LogitRows { int b, j, off; };
+enum { TAIL_TAPS = 1, TAIL_NO_CACHE = 2 };
+static int sampling_tail(const SampleCtx& g, LogitRows rows, int flags) {
+  wis_model* m = g.m; hipStream_t st = g.st; const wis_config_t& c = m->cfg;
+  const int lr_b = rows.b, lr_j = rows.j, lr_off = rows.off;
+  unsigned long long* prof = (WIS_TAPS && (flags & TAIL_TAPS)) ? m->d_prof + (size_t)c.n_dec_layers * 8 * 16 : nullptr;
+  if (g.ts) WIS_RET(launch_ts_rules(st, m->logits, g.bias_all, m->bias_begin, m->bs, g.B, g.sc, c.no_timestamps, g.ts_max_init, lr_b, lr_j, lr_off, m->ts_desc));
+  WIS_RET(launch_logit_stats(st, m->logits, g.bias_all, m->bias_begin, m->bs.step_u, m->st_max, m->st_sum, m->st_val, m->st_idx, g.B, g.sc, lr_b, lr_j, lr_off, prof ? prof + 16 : nullptr,
+                             nullptr, g.ts ? m->ts_desc : nullptr));
+  WIS_RET(launch_beam_step(st, m->st_max, m->st_sum, m->st_val, m->st_idx, m->bs, m->rm, g.B, g.P, c.n_text_ctx, g.sc, prof));
+  if (!(flags & TAIL_NO_CACHE)) WIS_RET(launch_kv_reorder(st, m->kc_all, m->vc_all, m->kv_layer_stride, c.n_dec_layers, m->bs, g.B, g.beam, g.P, c.n_text_ctx, c.d_model));
+  return WIS_OK;
+}
+
+// where the search stands when the step loops take over
+struct Seed {
+  int steps = 1;              // decoder passes done: the first step runs with the prefill pass
+  bool spec_done = false;     // the draft verification already met the end of the utterance
+  bool beam_fin = false;      // ... of a beam search: the replayed beam steps finished it, results are where beam_step_kernel puts them
+  std::vector<int> spec_gen; float spec_cum = 0.f; int spec_len = 0;      // greedy draft: tokens generated by the verification, their score, the result's length
+  int accepted = 0;           // draft tokens (beam draft: steps) verified
+};
+
+// Verification passes keep to the ticket hand-off of the cross-attention: their picks are accepted on the host pass by pass, outside the
+// progress record that carries the granule form's give-up flag (advisor, round 5) - the ordinary steps behind them take the call's form again
+struct TicketScope {
+  wis_model* m; bool spin_call;
+  explicit TicketScope(wis_model* mm) : m(mm), spin_call(mm->spin_now) { m->spin_now = false; }
+  ~TicketScope() { m->spin_now = spin_call; }
+};
+
+// the progress record counts passes: `steps` of them are done when the ordinary steps resume behind a verification
+static int reseed_tick(wis_model* m, int steps) {
+  unsigned* tk = m->h_pin->reseed_tick;
+  tk[0] = (unsigned)steps; tk[1] = m->gen; tk[2] = 0; tk[3] = 0;
+  WIS_HIP_CHECK(hipMemcpyAsync(m->bs.tick, tk, 16, hipMemcpyHostToDevice, m->st));
+  return WIS_OK;
+}
+
+// a (token, origin) trajectory of n steps x k beams in BeamState::traj's layout ([step][MAX_R][2]); entries of slots >= k are left alone
+static void pack_traj(int* hd, const int32_t* tok, const int32_t* org, int n, int k) {
+  for (int s_ = 0; s_ < n; ++s_) for (int j = 0; j < k; ++j) { hd[(s_ * MAX_R + j) * 2] = tok[s_ * k + j]; hd[(s_ * MAX_R + j) * 2 + 1] = org[s_ * k + j]; }
+}
+
+// ---- prefill + FIRST decode step in one pass: all P prompt tokens of an utterance are rows (b, i) at positions i in the
+// utterance's first KV slot (causal by position); the logits of the last prompt row seed the beams (CT2 forwards
+// prompt[:-1] and then feeds prompt[-1] as the first decoder input — the same arithmetic, one weight pass instead of two)
+static int seed_prefill(const GenCtx& g) {
+  wis_model* m = g.m; const wis_config_t& c = m->cfg; const int B = g.B, P = g.P;
+  WIS_RET(dec_forward(m, B * P, P, B, true, g.beam, 0));
+  // every prompt row has its logits after this pass: the <|startoftranscript|> row's are what no_speech_prob reads (raw, no processors)
+  if (g.sot_row >= 0) WIS_RET(launch_no_speech(g.st, m->logits, m->n_vocab_pad, B, P, g.sot_row, c.n_vocab, c.no_speech, m->d_nsp));
+  return sampling_tail(g, {P, 0, P - 1}, TAIL_TAPS);
+}
+
+// The decoder rows of window steps s0 .. s0 + Rw - 1 of a beam trajectory (hd: [step][MAX_R][2] = token, origin; one utterance, k beams), step-major:
+// row (s, j) feeds the token live beam j got at step s - 1 at position P - 1 + s and keeps its K / V in slot j; ha[row][ANC_W] = the slot of the
+// row's ancestor at every window step (entry 0 doubles as the slot that holds everything before the window).  Padded to whole groups of 16 rows
+// with copies of the last row (they write the same K / V to the same place).  Returns the padded row count.
+static int fill_tree_window(const int* hd, int s0, int Rw, int k, int P, std::vector<int>& tok, std::vector<int>& pos, std::vector<int>& slot, std::vector<int>& ls, int* ha) {
+  const int Mreal = k * Rw, Mpad = cdiv(Mreal, 16) * 16;
+  tok.assign(Mpad, 0); pos.assign(Mpad, 0); slot.assign(Mpad, 0); ls.assign(Mpad, 0);
+  for (int t = 0; t < Rw; ++t) for (int j = 0; j < k; ++j) {
+    const int s_ = s0 + t, r = t * k + j;
+    tok[r] = hd[((s_ - 1) * MAX_R + j) * 2]; pos[r] = P - 1 + s_; slot[r] = j; ls[r] = j;
+    int a = j;                                    // ancestor of (s_, j) at window step sp, walking the origins back to s0
+    for (int sp = s_; sp >= s0; --sp) { ha[r * ANC_W + (sp - s0)] = a; a = hd[((sp - 1) * MAX_R + a) * 2 + 1]; }
+    for (int u = t + 1; u < ANC_W; ++u) ha[r * ANC_W + u] = ha[r * ANC_W + t];
+  }
+  for (int r = Mreal; r < Mpad; ++r) {
+    tok[r] = tok[Mreal - 1]; pos[r] = pos[Mreal - 1]; slot[r] = slot[Mreal - 1]; ls[r] = ls[Mreal - 1];
+    for (int u = 0; u < ANC_W; ++u) ha[r * ANC_W + u] = ha[(Mreal - 1) * ANC_W + u];
+  }
+  return Mpad;
+}
+
+// ---- verify the draft of a BEAM SEARCH (round 6; BASELINE configs[4] at the reference's long-audio beam, main.py:582-586).  The draft is
+// the trajectory of an earlier search over (most of) the same audio: per step s the live set it left - k tokens and the beam slot each
+// continued from.  If the search over THIS window has followed it up to step s0 - 1, the decoder rows of steps s0 .. s0 + Rw - 1 are
+// known without running those steps: row (s, j) feeds the draft's token of live beam j after step s - 1 at position P - 1 + s.  They form a
+// TREE (a beam's history is a path through earlier live sets), so the pass runs the self-attention by ancestor table (dec_self_attn_kernel
+// TREE: node (s, j) keeps its K / V in slot j, row (s, j) reads position P - 1 + s' from the slot of its ancestor at step s') and the
+// cross-attention as groups of 16 rows over the utterance's one K / V.  One weight stream then yields the logits of Rw steps x k beams;
+// the steps are REPLAYED on them by the ordinary sampling kernels (logit_stats, beam_step: search state and hypothesis list end up exactly
+// where Rw ordinary steps would leave them), each followed by draft_match_kernel: if the live set a replayed step produced is the draft's -
+// as a SET: near-tied candidates swap slots between two searches all the time, so live beam j may be any draft node as long as every beam is
+// found once; the next step reads beam j's logits from the row of its node - the next step's rows were the right ones; the first step with a
+// beam the draft does not have still stands (its own inputs were verified), parks the search (done = 2), and ordinary steps resume behind
+// it.  The cache: the pass left node (s, i)'s K / V in slot i of the draft's numbering; the matching kernel keeps every live beam's path
+// through those slots and kv_gather_kernel turns the paths into "slot j = beam j's history" once per window.  A whole window is queued
+// without a host round trip; the host looks once per window.  Exact by construction: every accepted step ran beam_step_kernel on the logits
+// of its true inputs (summed in the multi-row order, as any other batch shape of the engine).
+static int seed_beam_draft(const GenCtx& g, Seed* sd) {
+  wis_model* m = g.m; hipStream_t st = g.st; const wis_config_t& c = m->cfg; PinnedScratch* hp = m->h_pin;
+  const int P = g.P, beam = g.beam, max_new = g.max_new, ctx = c.n_text_ctx;
+  const SampleCfg& sc = g.sc;
+  const int k = beam;
+  const int nd = std::min(g.n_draft, max_new - 1);
+  int* hd = hp->draft;                                // the draft in BeamState::traj's layout ([step][MAX_R][2])
+  pack_traj(hd, g.draft, g.draft_org, nd, k);
+  int* hv = hp->vstate;                               // staging of the verification state (dec_kernels.hip draft_match_kernel: vs), read back per window
+  for (int i = 0; i < 32; ++i) hv[i] = 0;
+  for (int j = 0; j < MAX_R; ++j) { hv[DRAFT_VS_PERM + j] = j; hv[DRAFT_VS_BASE + j] = j; }
+  if (nd > 0) WIS_HIP_CHECK(hipMemcpyAsync(m->d_draft, hd, (size_t)nd * MAX_R * 2 * 4, hipMemcpyHostToDevice, st));
+  WIS_HIP_CHECK(hipMemcpyAsync(m->d_vstate, hv, 32 * 4, hipMemcpyHostToDevice, st));
+  // merged prefill + first step as in the ordinary call (a tap build stamps neither kernel here), then: is the search where the draft's step 0 says?
+  WIS_RET(dec_forward(m, P, P, 1, true, beam, 0));
+  WIS_RET(sampling_tail(g, {P, 0, P - 1}, 0));
+  WIS_RET(launch_draft_match(st, m->bs, m->d_draft, nd, k, m->d_vstate, 0));
+  const int RW = std::min(ANC_W, MAX_ROWS / k);       // steps per window: k x RW rows (beam 2 / 3: 32 steps, 5: 19, 8: 12), padded to whole groups of 16
+  const int s_last = std::min(nd, max_new - 1);       // last step a window can hold: rows from the draft's entry s - 1; step max_new - 1 ends every search
+  int* ha = hp->anc;                                  // ancestor table of the window rows, [rows][ANC_W]
+  int* hb = hp->base;                                 // ... and the slot holding each row's history before the window, [rows]
+  int* hw2 = hp->path_reset;                          // per-window reset of the path bookkeeping: vs[2] = 0, vs[16 + j] = j
+  int done_flag = 0, step_dev = 0;
+  int pinv[MAX_R];                                    // real slot of draft node i at the window's start (the matching read back at the previous sync)
+  for (int j = 0; j < MAX_R; ++j) pinv[j] = j;        // (first window: every slot holds the same prompt rows - any assignment is right)
+  for (int s0 = 1;; ) {
+    const int Rw = std::min(RW, s_last - s0 + 1);
+    if (Rw >= 1) {
+      std::vector<int> tok, pos, slot, ls;
+      const int Mpad = fill_tree_window(hd, s0, Rw, k, P, tok, pos, slot, ls, ha);
+      for (int r = 0; r < Mpad; ++r) hb[r] = pinv[ha[r * ANC_W]];      // the row's window-step-0 ancestor is draft node ha[r][0]: its earlier history sits in that node's REAL slot
+      // the window's rows go through a row table of their own: the search's table (next input rows, written by the last beam step that
+      // counted) must survive a window that turns out to sit behind a parked search (queued before the host has looked)
+      const RowMeta rm_search = m->rm;
+      m->rm = m->rm_win;
+      int rc = upload_rows(m, tok, pos, slot, ls, false, &hp->win_rows);      // (the prompt rows' staging copy may still be pending: own area; windows are a sync apart)
+      if (!rc && (hipMemcpyAsync(m->d_anc, ha, (size_t)Mpad * ANC_W * 4, hipMemcpyHostToDevice, st) != hipSuccess ||
+                  hipMemcpyAsync(m->d_base, hb, (size_t)Mpad * 4, hipMemcpyHostToDevice, st) != hipSuccess)) { set_error("draft window: ancestor table upload failed"); rc = WIS_E_HIP; }
+      TreeWin tw{m->d_anc, P - 1 + s0, ANC_W}; tw.base = m->d_base;
+      if (!rc) rc = dec_forward(m, Mpad, 16, Mpad / 16, true, 1, 0, &tw);
+      m->rm = rm_search;
+      WIS_RET(rc);
+      hw2[0] = 0; for (int j = 0; j < MAX_R; ++j) hw2[1 + j] = j;
+      WIS_HIP_CHECK(hipMemcpyAsync(m->d_vstate + 2, hw2, 4, hipMemcpyHostToDevice, st));
+      WIS_HIP_CHECK(hipMemcpyAsync(m->d_vstate + DRAFT_VS_BASE, hw2 + 1, MAX_R * 4, hipMemcpyHostToDevice, st));
+      for (int t = 0; t < Rw; ++t) {      // replay: beam j's logits come from the row of the draft node it is matched to (rowmap); no cache traffic per step
+        WIS_RET(launch_logit_stats(st, m->logits, g.bias_all, m->bias_begin, m->bs.step_u, m->st_max, m->st_sum, m->st_val, m->st_idx, 1, sc, beam, 1, t * k, nullptr, m->d_vstate + DRAFT_VS_PERM));
+        WIS_RET(launch_beam_step(st, m->st_max, m->st_sum, m->st_val, m->st_idx, m->bs, m->rm, 1, P, ctx, sc));
+        WIS_RET(launch_draft_match(st, m->bs, m->d_draft, nd, k, m->d_vstate, 1));
+      }
+      // the window's paths applied to the cache at once: slot j = live beam j's history, as ordinary steps (and the next window) expect it
+      WIS_RET(launch_kv_gather(st, m->kc_all, m->vc_all, m->kv_layer_stride, c.n_dec_layers, m->d_vstate, m->bs.done, beam, P - 1 + s0, ctx, c.d_model));
+    }
+    WIS_HIP_CHECK(hipMemcpyAsync(hv, m->d_vstate, 16 * 4, hipMemcpyDeviceToHost, st));      // steps verified, ..., the matching
+    WIS_HIP_CHECK(hipMemcpyAsync(&hp->win_done, m->bs.done, 4, hipMemcpyDeviceToHost, st));
+    WIS_HIP_CHECK(hipMemcpyAsync(&hp->win_step, m->bs.step_u, 4, hipMemcpyDeviceToHost, st));
+    WIS_HIP_CHECK(hipStreamSynchronize(st));
+    done_flag = hp->win_done; step_dev = hp->win_step;
+    if (Rw < 1 || done_flag != 0) break;
+    for (int j = 0; j < k; ++j) { const int n_ = hv[DRAFT_VS_PERM + j]; if (n_ >= 0 && n_ < k) pinv[n_] = j; }
+    s0 += Rw;
+  }
+  sd->accepted = hv[0];
+  __atomic_store_n(&m->h_prog[HP_REC], 0ull, __ATOMIC_RELAXED);      // the replayed steps' progress records count launches, not steps: the pacing loop starts from `steps`
+  if (done_flag == 1) {      // the replayed steps ended the search: hypotheses ranked, result written by beam_step_kernel
+    sd->beam_fin = true; sd->steps = step_dev + 1;
+  } else {                   // parked behind a step that stands (or nothing to verify): ordinary steps resume
+    sd->steps = step_dev;
+    if (sd->steps < 1) { set_error("wis_generate_draft_beam: verification completed no step"); return WIS_E_STATE; }
+    WIS_RET(reseed_tick(m, sd->steps));
+    WIS_HIP_CHECK(hipMemsetAsync(m->bs.done, 0, 4, st));
+  }
+  return WIS_OK;
+}
+
+// ---- verify the draft: the prompt and the draft tokens go through the decoder as teacher-forced rows, 16 positions per pass
+// (causal by position inside the utterance's KV slot, like the merged prompt pass); row i's logits are what a greedy step fed
+// seq[i] after seq[0..i-1] sees, so as long as every earlier draft token equalled the greedy pick, row P-1+g yields generated
+// token g.  The first disagreement ends the verification WITH the right token for that index (its prefix was right); the K / V
+// rows of the accepted prefix are in the cache, and the ordinary step loop continues from there.  Per pass one weight stream
+// for up to 16 tokens instead of one per token.
+static int seed_greedy_draft(const GenCtx& g, Seed* sd) {
+  wis_model* m = g.m; hipStream_t st = g.st; const wis_config_t& c = m->cfg; PinnedScratch* hp = m->h_pin;
+  const int P = g.P, max_new = g.max_new;
+  const int32_t* draft = g.draft;
+  const int nd = std::min(g.n_draft, max_new - 1);
+  std::vector<int> seq(P + nd);
+  for (int i = 0; i < P; ++i) seq[i] = g.prompt[i];
+  for (int i = 0; i < nd; ++i) seq[P + i] = draft[i];
+  // (r6) up to 96 positions per pass: more than 16 rows of one utterance go through the row-group form of the tree pass (a chain is a tree whose
+  // every ancestor sits in slot 0: dec_self_attn_kernel<TREE> with an all-zero table is "causal by position in the slot", the cross-attention
+  // takes the rows as groups of 16 over the one K / V) - the 100 rows of a 96-token draft are 2 passes (3.5 + 1.3 ms) instead of 7 x 1.35 ms.
+  // WIS_DRAFT_ROWS=16: the round-5 schedule (A/B)
+  static const int env_rows = getenv("WIS_DRAFT_ROWS") ? atoi(getenv("WIS_DRAFT_ROWS")) : 0;
+  const int R = (env_rows >= 16 && env_rows <= MAX_ROWS) ? env_rows / 16 * 16 : MAX_ROWS;
+  bool stop = false; int n_acc = 0;
+  for (int t0 = 0; t0 < P + nd && !stop; t0 += R) {
+    const int rows = std::min(R, P + nd - t0);
+    const int f = std::max(P - 1 - t0, 0), nv = rows - f;      // rows f .. rows-1 of this pass predict generated tokens
+    const int Mp = rows > 16 ? cdiv(rows, 16) * 16 : rows;      // (row groups: padded with copies of the last row - same K / V to the same place)
+    std::vector<int> tok(Mp), pos(Mp), slot(Mp, 0), ls(Mp, 0);
+    for (int i = 0; i < Mp; ++i) { const int ii = std::min(i, rows - 1); tok[i] = seq[t0 + ii]; pos[i] = t0 + ii; }
+    WIS_RET(upload_rows(m, tok, pos, slot, ls));
+    if (rows > 16) {
+      WIS_HIP_CHECK(hipMemsetAsync(m->d_anc, 0, (size_t)Mp * 16 * 4, st));
+      const TreeWin tw{m->d_anc, t0, 16};
+      WIS_RET(dec_forward(m, Mp, 16, Mp / 16, nv > 0, 1, 0, &tw));
+    } else
+    WIS_RET(dec_forward(m, rows, rows, 1, nv > 0, 1, 0));
+    if (nv <= 0) continue;
+    int* hv = hp->vstep;
+    for (int i = 0; i < nv; ++i) hv[i] = t0 + f + i - (P - 1);      // the step index of each verified row (first-step / EOT masks of logit_stats_kernel)
+    WIS_HIP_CHECK(hipMemcpyAsync(m->vstep, hv, (size_t)nv * 4, hipMemcpyHostToDevice, st));
+    WIS_RET(launch_logit_stats(st, m->logits, g.bias_all, m->bias_begin, m->vstep, m->st_max, m->st_sum, m->st_val, m->st_idx, nv, g.sc, 1, 0, f));
+    WIS_RET(launch_greedy_pick(st, m->st_max, m->st_sum, m->st_val, m->st_idx, nv, g.sc, m->pick_tok, m->pick_lp));
+    int* ht = hp->pick_tok; float* hl = hp->pick_lp;
+    WIS_HIP_CHECK(hipMemcpyAsync(ht, m->pick_tok, (size_t)nv * 4, hipMemcpyDeviceToHost, st));
+    WIS_HIP_CHECK(hipMemcpyAsync(hl, m->pick_lp, (size_t)nv * 4, hipMemcpyDeviceToHost, st));
+    WIS_HIP_CHECK(hipStreamSynchronize(st));
+    for (int i = 0; i < nv && !stop; ++i) {
+      const int gi = hv[i];
+      sd->spec_cum = hl[i] + sd->spec_cum;                 // beam_step_kernel: (logit - lse) + cum
+      sd->spec_gen.push_back(ht[i]);
+      const bool eos = ht[i] == c.eot, is_last = gi + 1 >= max_new;
+      if (eos || is_last) { sd->spec_done = true; sd->spec_len = eos ? gi : gi + 1; stop = true; }
+      else if (gi < nd && ht[i] == draft[gi]) ++n_acc;
+      else stop = true;                                  // first disagreement (or the row behind the last draft token): ht[i] is generated token gi
+    }
+  }
+  sd->accepted = n_acc;
+  const int steps = sd->steps = (int)sd->spec_gen.size();
+  if (steps < 1) { set_error("wis_generate_draft: verification produced no token"); return WIS_E_STATE; }
+  if (!sd->spec_done) {
+    // the search state a run of `steps` ordinary steps would have left: history, cumulative score, next input row, counters
+    int* hs = hp->hist;
+    for (int t = 0; t < steps; ++t) hs[t] = sd->spec_gen[t];
+    WIS_HIP_CHECK(hipMemcpyAsync(m->bs.alive, hs, (size_t)steps * 4, hipMemcpyHostToDevice, st));
+    auto& hw = hp->seed;
+    hw.step = steps; hw.tok = sd->spec_gen.back(); hw.pos = P - 1 + steps; hw.slot = 0; hw.cum = sd->spec_cum;
+    WIS_HIP_CHECK(hipMemcpyAsync(m->bs.step_u, &hw.step, 4, hipMemcpyHostToDevice, st));
+    WIS_HIP_CHECK(hipMemcpyAsync(m->rm.tok, &hw.tok, 4, hipMemcpyHostToDevice, st));
+    WIS_HIP_CHECK(hipMemcpyAsync(m->rm.pos, &hw.pos, 4, hipMemcpyHostToDevice, st));
+    WIS_HIP_CHECK(hipMemcpyAsync(m->rm.slot, &hw.slot, 4, hipMemcpyHostToDevice, st));
+    WIS_HIP_CHECK(hipMemcpyAsync(m->rm.lslot, &hw.slot, 4, hipMemcpyHostToDevice, st));
+    WIS_HIP_CHECK(hipMemcpyAsync(m->bs.cum, &hw.cum, 4, hipMemcpyHostToDevice, st));
+    WIS_RET(reseed_tick(m, steps));
+  }
+  return WIS_OK;
+}
+
+// The decode step - one decoder pass over the search's rows and its sampling tail - captured once per shape into a HIP graph and replayed.
+// The step graph comes in up to three forms that differ in ONE kernel argument set: how many 8-position blocks of its rows' K / V history the self-attention
+// asks for (dec_self_attn_kernel NB).  Every row of the pass that follows s beam steps has P + s positions - known HERE, by the step index, although the graph's
+// kernel arguments are frozen - so the pass is launched from the graph whose self-attention asks for 16 / 32 / 64 positions (WIS_SA_NB=0: always 64, A/B switch).
+struct StepGraph {
+  const GenCtx& g;
+  ~StepGraph() { g.m->sa_nb = 8; }      // (everything outside the step loops - prefill, verification windows, taps - asks for 64)
+
+  int nb_for(int passes_done) const {
+    static const bool sa_short = !(getenv("WIS_SA_NB") && atoi(getenv("WIS_SA_NB")) == 0);
+    const int len = g.P + passes_done;
+    return !sa_short ? 8 : (len <= 16 ? 2 : (len <= 32 ? 4 : 8));
+  }
+  int one_step() const {
+    WIS_RET(dec_forward(g.m, g.B * g.beam, g.beam, g.B, true, g.beam, 1));
+    return sampling_tail(g, {g.beam, 1, 0}, TAIL_TAPS);
+  }
+  int graph_for(int nb, hipGraphExec_t* out) const {
+    wis_model* m = g.m; const SampleCfg& sc = g.sc;
+    GraphKey key; memset(&key, 0, sizeof(key));
+    key.B = g.B; key.beam = g.beam; key.P = g.P; key.max_new = g.max_new; key.fixed_new = sc.fixed_new; key.suppress_blank = sc.suppress_blank;
+    key.suppress_default = g.o->suppress_default; key.early_exit = sc.allow_early_exit; key.lp = sc.length_penalty; key.patience = g.patience; key.spin = (m->spin_now ? 1 : 0) | (sa_fuse_enabled() ? 2 : 0);
+    key.sa_nb = nb;
+    key.timestamps = g.ts ? 1 : 0; key.max_init = g.ts ? g.ts_max_init : 0;
+    auto it = m->graphs.find(key);
+    if (it != m->graphs.end()) { *out = it->second; return WIS_OK; }
+    hipGraph_t graph = nullptr; hipGraphExec_t ge = nullptr;
+    WIS_HIP_CHECK(hipStreamBeginCapture(g.st, hipStreamCaptureModeThreadLocal));
+    int rc = one_step();
+    hipError_t e = hipStreamEndCapture(g.st, &graph);
+    if (rc) { if (graph) hipGraphDestroy(graph); return rc; }
+    if (e != hipSuccess) { set_error("graph capture failed: %s", hipGetErrorString(e)); return WIS_E_HIP; }
+    e = hipGraphInstantiate(&ge, graph, nullptr, nullptr, 0);
+    hipGraphDestroy(graph);
+    if (e != hipSuccess) { set_error("graph instantiate failed: %s", hipGetErrorString(e)); return WIS_E_HIP; }
+    m->graphs[key] = ge;
+    *out = ge;
+    return WIS_OK;
+  }
+  int launch_pass(int passes_done) const {      // the decoder pass + sampling that follows `passes_done` passes
+    wis_model* m = g.m;
+    m->sa_nb = nb_for(passes_done);
+    if (!m->use_graph) return one_step();
+    hipGraphExec_t ge = nullptr;
+    WIS_RET(graph_for(m->sa_nb, &ge));
+    WIS_HIP_CHECK(hipGraphLaunch(ge, g.st));
+    return WIS_OK;
+  }
+};
+
+// what a step loop leaves behind
+struct LoopResult {
+  int steps;                    // decoder passes enqueued (the seed's included)
+  int needed = 0;               // steps after which the last utterance had finished (natural termination)
+  bool gave_up = false;         // a combiner's bounded spin ran out: the results are garbage, the call is repeated
+  bool from_host = false;       // the results are in the host-mapped progress block
+  float decode_ms_dev = -1.f;   // decode time by the device clock (from_host)
+};
+// the search's progress record: {generation, steps, give-up, utterances done} - a record of another generation reads as nothing
+static void unpack_progress(const wis_model* m, int* st_, int* dn_, int* gu_) {
+  const unsigned long long r = __atomic_load_n(&m->h_prog[HP_REC], __ATOMIC_ACQUIRE);
+  if ((r >> 48) != (unsigned long long)m->gen) { *st_ = 0; *dn_ = 0; *gu_ = 0; return; }
+  *st_ = (int)((r >> 32) & 0xFFFFu); *gu_ = (int)((r >> 16) & 0xFFFFu); *dn_ = (int)(r & 0xFFFFu);
+}
+static int check_terminated(const GenCtx& g, LoopResult* lr, int dn_, int gu_) {
+  lr->gave_up = gu_ != 0;
+  if (!lr->gave_up && dn_ < g.B) { set_error("decode did not terminate within %d steps (done %d of %d)", lr->steps, dn_, g.B); return WIS_E_STATE; }
+  return WIS_OK;
+}
+
+// With the measurement convention the step count is known (fixed_new tokens + the forced EOT): every step goes out in one burst, nothing to
+// find out from the device before the last one
+static int run_burst(const GenCtx& g, const StepGraph& sg, int limit, LoopResult* lr) {
+  wis_model* m = g.m;
+  for (; lr->steps < limit; ++lr->steps) WIS_RET(sg.launch_pass(lr->steps));
+  WIS_HIP_CHECK(hipEventRecord(m->ev[5], g.st));
+  WIS_HIP_CHECK(hipStreamSynchronize(g.st));
+  int st_, dn_, gu_; unpack_progress(m, &st_, &dn_, &gu_);
+  WIS_RET(check_terminated(g, lr, dn_, gu_));
+  lr->needed = lr->steps;
+  return WIS_OK;
+}
+
+// A search that ends on EOT (every real request: the reference passes no max_length, main.py:687-693).  The host keeps `depth`
+// steps enqueued beyond the last one it has seen complete (one running, one waiting behind it: the device never idles between
+// steps) and reads the search's progress from the host-mapped record beam_step_kernel writes at the end of every step - no
+// stream drain, no copy.  When the record says every utterance has finished, at most depth - 1 further steps are in the queue;
+// they run on finished utterances (every sampling workgroup returns at its `done` test, results stay as they are) and this
+// call does not wait for them: the results are already in host memory, the next call on the handle queues behind them.
+// base_done: passes a draft verification stands for - done before the first progress record of this call.
+static int run_paced(const GenCtx& g, const StepGraph& sg, int limit, int base_done, LoopResult* lr) {
+  wis_model* m = g.m; const int B = g.B;
+  int& steps = lr->steps;
+  const auto t_dec0 = std::chrono::steady_clock::now();
+  const int depth = g.o->queue_depth > 0 ? g.o->queue_depth : 2;
+  auto t_last = std::chrono::steady_clock::now();
+  int seen = -1, st_ = 0, dn_ = 0, gu_ = 0;
+  static const bool trace = getenv("WIS_EOT_TRACE") != nullptr;      // per-step record of the pacing loop on stderr (tuning)
+  struct Tr { int step; unsigned long long dev; double host_us; int launched; };
+  std::vector<Tr> tr;
+  const auto t_loop = std::chrono::steady_clock::now();
+  for (unsigned spins = 0;; ++spins) {
+    unpack_progress(m, &st_, &dn_, &gu_);
+    if (st_ < base_done) st_ = base_done;
+    if (dn_ >= B || gu_) break;
+    if (st_ >= limit) break;                 // (cannot happen: the max_new-th step finishes every utterance)
+    if (steps < limit && steps - st_ < depth) {
+      const auto tl0 = std::chrono::steady_clock::now();
+      WIS_RET(sg.launch_pass(steps));
+      ++steps;
+      if (trace) tr.push_back({-steps, 0ull, std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - tl0).count(), steps});      // (negative step: a launch, host_us = its duration)
+      continue;
+    }
+    if (st_ != seen) {
+      seen = st_; t_last = std::chrono::steady_clock::now(); spins = 0;
+      if (trace) tr.push_back({st_, m->h_prog[HP_STAMP], std::chrono::duration<double, std::micro>(t_last - t_loop).count(), steps});
+    }
+    else if ((spins & 1023u) == 1023u) {
+      const double idle = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_last).count();
+      if (idle > 30.0) { set_error("decode made no progress for 30 s (step %d of %d enqueued)", st_, steps); return WIS_E_HIP; }
+      if (idle > 200e-6) { struct timespec ts = {0, 20000}; nanosleep(&ts, nullptr); }      // long steps (big batches): stop burning the core
+    }
+    cpu_relax();
+  }
+  if (trace) {
+    unsigned long long prev_dev = 0;
+    for (size_t i = 0; i < tr.size(); ++i) {
+      if (tr[i].step < 0) { fprintf(stderr, "[eot-trace]   launch of step %d took the host %.1f us\n", -tr[i].step, tr[i].host_us); continue; }
+      fprintf(stderr, "[eot-trace] step %d seen by the host at %.1f us (device clock +%.1f us since the previous record), %d steps enqueued\n", tr[i].step, tr[i].host_us,
+              prev_dev ? (double)(tr[i].dev - prev_dev) * 0.01 : 0.0, tr[i].launched);
+      prev_dev = tr[i].dev;
+    }
+    fprintf(stderr, "[eot-trace] done seen at %.1f us: %d of %d utterances, %d steps enqueued\n", std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t_loop).count(), dn_, B, steps);
+  }
+  WIS_RET(check_terminated(g, lr, dn_, gu_));
+  if (!lr->gave_up) {
+    lr->from_host = true;
+    lr->needed = (int)m->h_prog[HP_DONE_STEP];
+    const unsigned long long s0 = m->h_prog[HP_STAMP0], s1 = m->h_prog[HP_DONE_STAMP];
+    lr->decode_ms_dev = s1 > s0 ? (float)((double)(s1 - s0) * 1e-5) : 0.f;      // 100 MHz constant clock; from the end of the first beam step (ev[4] is one kv_reorder later)
+    if (g.drafting) lr->decode_ms_dev = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t_dec0).count();      // (no first beam step of its own: host clock)
+  }
+  return WIS_OK;
+}
+
+// ---- results: out_ids is [B][max_new] (beam_step_kernel indexes by the resolved max_new; the allocations are [.][MAX_STEPS])
+// the verification rows already contained the end of the utterance: beam_step_kernel's finalisation, on the host
+static void results_from_verification(const GenCtx& g, const Seed& sd, int32_t* out_ids, int32_t* out_len, float* out_score) {
+  float sfin = sd.spec_cum;
+  if (g.sc.length_penalty != 0.f) sfin /= powf((float)sd.spec_len, g.sc.length_penalty);
+  out_len[0] = sd.spec_len;
+  for (int t = 0; t < g.max_new; ++t) out_ids[t] = t < sd.spec_len ? sd.spec_gen[t] : 0;
+  if (out_score) out_score[0] = sfin;
+}
+// the record beam_step_kernel left in the host-mapped progress block when the last utterance finished
+static int results_from_record(const GenCtx& g, int32_t* out_ids, int32_t* out_len, float* out_score) {
+  const wis_model* m = g.m; const int max_new = g.max_new;
+  const int* hl = hp_out_len(m->h_prog); const float* hs = hp_out_score(m->h_prog); const int* hi = hp_out_ids(m->h_prog);
+  for (int b = 0; b < g.B; ++b) {
+    int n = hl[b];
+    if (n < 0 || n > max_new) { set_error("decode result of utterance %d has length %d outside [0, %d]", b, n, max_new); return WIS_E_STATE; }
+    out_len[b] = n;
+    for (int t = 0; t < max_new; ++t) out_ids[(size_t)b * max_new + t] = t < n ? hi[(size_t)b * max_new + t] : 0;
+    if (out_score) out_score[b] = hs[b];
+  }
+  return WIS_OK;
+}
+// a copy of the search's device-side result (drains the stream)
+static int results_from_device(wis_model* m, int B, int max_new, int32_t* out_ids, int32_t* out_len, float* out_score) {
+  hipStream_t st = m->st;
+  std::vector<int32_t> ids((size_t)B * MAX_STEPS);
+  std::vector<float> sc_h(B);
+  WIS_HIP_CHECK(hipMemcpyAsync(ids.data(), m->bs.out_ids, (size_t)B * MAX_STEPS * 4, hipMemcpyDeviceToHost, st));
+  WIS_HIP_CHECK(hipMemcpyAsync(out_len, m->bs.out_len, (size_t)B * 4, hipMemcpyDeviceToHost, st));
+  WIS_HIP_CHECK(hipMemcpyAsync(sc_h.data(), m->bs.out_score, (size_t)B * 4, hipMemcpyDeviceToHost, st));
+  WIS_HIP_CHECK(hipStreamSynchronize(st));
+  for (int b = 0; b < B; ++b) {
+    if (out_len[b] > max_new) out_len[b] = max_new;
+    for (int t = 0; t < max_new; ++t) out_ids[(size_t)b * max_new + t] = t < out_len[b] ? ids[(size_t)b * max_new + t] : 0;
+    if (out_score) out_score[b] = sc_h[b];
+  }
+  return WIS_OK;
+}
+
+static void record_timing(const GenCtx& g, const LoopResult& lr) {
+  wis_model* m = g.m;
+  const auto t1 = std::chrono::steady_clock::now();
+  float ms;
+  hipEventElapsedTime(&ms, m->ev[0], m->ev[1]); m->timing.logmel_ms = ms;
+  hipEventElapsedTime(&ms, m->ev[1], m->ev[2]); m->timing.encoder_ms = ms;
+  hipEventElapsedTime(&ms, m->ev[2], m->ev[3]); m->timing.crosskv_ms = ms;
+  hipEventElapsedTime(&ms, m->ev[3], m->ev[4]); m->timing.prefill_ms = ms;
+  if (lr.from_host) m->timing.decode_ms = lr.decode_ms_dev; else { hipEventElapsedTime(&ms, m->ev[4], m->ev[5]); m->timing.decode_ms = ms; }
+  m->timing.total_ms = std::chrono::duration<float, std::milli>(t1 - g.t0).count();
+  m->timing.decode_steps = lr.steps;            // steps enqueued (the merged prefill + first step included)
+  m->timing.decode_steps_needed = lr.needed;    // steps after which every utterance had finished: steps - needed = over-run
+}
+
+// accepted: draft tokens (wis_generate_draft) / steps (wis_generate_draft_beam) verified
+static int generate_impl(wis_model_t* m, const float* input, int B, const int32_t* prompt, int P,
+                 const wis_gen_opts_t* o, int32_t* out_ids, int32_t* out_len, float* out_score, bool* retry,
+                 const int32_t* draft = nullptr, int n_draft = 0, int* accepted = nullptr, const int32_t* draft_org = nullptr) {
+  *retry = false;
+  if (accepted) *accepted = 0;
+  m->nsp_B = 0;
+  WIS_HIP_CHECK(hipSetDevice(m->device));
+  SpinClaim claim(m, B);
+  GenCtx g;
+  WIS_RET(make_gen_ctx(m, input, B, prompt, P, o, draft, n_draft, draft_org, &g));
+  hipStream_t st = g.st;
+  WIS_RET(stage_search(g));
+  WIS_RET(front_half(g));
+
+  Seed sd;
+  if (!g.drafting) WIS_RET(seed_prefill(g));
+  else {
+    TicketScope ticket(m);
+    WIS_RET(g.beam_draft ? seed_beam_draft(g, &sd) : seed_greedy_draft(g, &sd));
+    if (accepted) *accepted = sd.accepted;
+  }
+  WIS_HIP_CHECK(hipEventRecord(m->ev[4], st));
+  if (sd.beam_fin) WIS_HIP_CHECK(hipEventRecord(m->ev[5], st));
+
+  const StepGraph sg{g};
+  LoopResult lr; lr.steps = sd.steps;
+  // with the measurement convention the step count is known: fixed_new tokens + the forced EOT
+  const int known = (g.sc.fixed_new > 0) ? std::min(g.max_new, g.sc.fixed_new + 1) : 0;
+  if (sd.spec_done || sd.beam_fin) lr.needed = sd.steps;
+  else if (known) WIS_RET(run_burst(g, sg, known, &lr));
+  else WIS_RET(run_paced(g, sg, g.max_new, g.drafting ? sd.steps : 0, &lr));
+  // the granule hand-off's give-up flag (a combiner's bounded spin ran out: another handle's chain held the CUs its producers needed).
+  // Not an error for the caller: the handle keeps to the ticket hand-off from now on and the call is run again (generate_with_retry).
+  if (lr.gave_up) {
+    WIS_HIP_CHECK(hipMemsetAsync(m->ca_epoch, 0, 4, st));
+    WIS_HIP_CHECK(hipStreamSynchronize(st));
+    m->spin_off = true; *retry = true; ++m->handoff_retries;
+    fprintf(stderr, "[wis_hip] device %d: decoder cross-attention granule hand-off timed out; this handle uses the ticket hand-off from now on, the call is repeated\n", m->device);
+    return WIS_OK;
+  }
+  if (sd.spec_done) { results_from_verification(g, sd, out_ids, out_len, out_score); lr.from_host = true; lr.decode_ms_dev = 0.f; }
+  else if (lr.from_host) WIS_RET(results_from_record(g, out_ids, out_len, out_score));
+  else WIS_RET(results_from_device(m, B, g.max_new, out_ids, out_len, out_score));
+  record_timing(g, lr);
+  if (lr.steps > lr.needed) { claim.defer(st); m->overrun_left = true; }      // an over-run step is still queued: its combiners keep their share of the spin budget until it has run
+  if (g.sot_row >= 0) m->nsp_B = B;
+  return WIS_OK;
+}
+
+// runs the call, and once more if the granule hand-off gave up: the second run takes the ticket hand-off (spin_off is set), which cannot time out
+static int generate_with_retry(const char* who, wis_model_t* m, const float* input, int B, const int32_t* prompt, int P, const wis_gen_opts_t* o,
+                               int32_t* out_ids, int32_t* out_len, float* out_score,
+                               const int32_t* draft = nullptr, int n_draft = 0, int* accepted = nullptr, const int32_t* draft_org = nullptr) {
+  bool retry = false;
+  for (int attempt = 0; attempt < 2; ++attempt) {
+    WIS_RET(generate_impl(m, input, B, prompt, P, o, out_ids, out_len, out_score, &retry, draft, n_draft, accepted, draft_org));
+    if (!retry) return WIS_OK;
+  }
+  set_error("%s: hand-off flag raised without the granule path", who);
+  return WIS_E_STATE;
+}
+
+extern "C" {
+
+int wis_generate(wis_model_t* m, const float* input, int B, const int32_t* prompt, int P,
+                 const wis_gen_opts_t* o, int32_t* out_ids, int32_t* out_len, float* out_score) {
+  if (!m || !input || !prompt || !o || !out_ids || !out_len) { set_error("wis_generate: bad argument"); return WIS_E_ARG; }
+  WIS_ENTER(m, "wis_generate")
+  return generate_with_retry("wis_generate", m, input, B, prompt, P, o, out_ids, out_len, out_score);
+}
+
+int wis_generate_draft(wis_model_t* m, const float* input, const int32_t* prompt, int P, const wis_gen_opts_t* o,
+                       const int32_t* draft, int n_draft, int32_t* out_ids, int32_t* out_len, float* out_score, int32_t* accepted) {
+  if (!m || !input || !prompt || !o || !out_ids || !out_len || (n_draft > 0 && !draft) || n_draft < 0) { set_error("wis_generate_draft: bad argument"); return WIS_E_ARG; }
+  if (o->timestamps) { set_error("wis_generate_draft: timestamps are not available for drafted decodes"); return WIS_E_UNSUPPORTED; }
+  WIS_ENTER(m, "wis_generate_draft")
+  int acc = 0;
+  WIS_RET(generate_with_retry("wis_generate_draft", m, input, 1, prompt, P, o, out_ids, out_len, out_score, draft, n_draft, &acc));
+  if (accepted) *accepted = acc;
+  return WIS_OK;
+}
+
+int wis_generate_draft_beam(wis_model_t* m, const float* input, const int32_t* prompt, int P, const wis_gen_opts_t* o,
+                            const int32_t* draft_tok, const int32_t* draft_org, int n_steps, int32_t* out_ids, int32_t* out_len, float* out_score, int32_t* accepted_steps) {
+  if (!m || !input || !prompt || !o || !out_ids || !out_len || n_steps < 0 || (n_steps > 0 && (!draft_tok || !draft_org))) { set_error("wis_generate_draft_beam: bad argument"); return WIS_E_ARG; }
+  if (o->timestamps) { set_error("wis_generate_draft_beam: timestamps are not available for drafted decodes"); return WIS_E_UNSUPPORTED; }
+  WIS_ENTER(m, "wis_generate_draft_beam")
+  int acc = 0;
+  WIS_RET(generate_with_retry("wis_generate_draft_beam", m, input, 1, prompt, P, o, out_ids, out_len, out_score, n_steps > 0 ? draft_tok : nullptr, n_steps, &acc,
+                              n_steps > 0 ? draft_org : nullptr));
+  if (accepted_steps) *accepted_steps = acc;
+  return WIS_OK;
+}
+
+}  // extern "C"

@@ -174,7 +174,7 @@ struct BeamState {
   int* hyp_tok;     // [B][max_hyp][max_new]
   int* all_done;    // [1] utterances finished so far
   int* out_ids; int* out_len; float* out_score;   // final result [B][max_new], [B], [B]
-  // progress of the search, published to the host without a stream round trip (model.hip generate_impl's pacing loop):
+  // progress of the search, published to the host without a stream round trip (generate.hip run_paced):
   unsigned* tick;                 // device [4]: {workgroups of beam_step_kernel that ended since init, call generation, step at which all_done reached B, -}
   const unsigned* giveup;         // word 0 of the cross-attention hand-off's epoch block (a combiner's bounded spin ran out)
   unsigned long long* host;       // device address of the HOST-mapped (fine-grained) progress block, layout HP_* below

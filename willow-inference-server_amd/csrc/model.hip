@@ -146,6 +146,38 @@ struct AlignState {
   bool ev_partial = false;                // the last call had more head chunks than event pairs: the weights / filter split is not reported
 };
 
+constexpr int ANC_W = 32;      // ancestor-table entries per row = the most steps a window holds (beam 2 / 3: 32 steps = 64 / 96 rows)
+constexpr int MAX_STEPS = 256;      // decode steps a search can take (the cap on max_new; BeamState::traj and the draft hold this many entries)
+
+// The handle's pinned host staging block.  Every area is a member of its own: a copy out of one may still be pending on the stream when
+// the host fills the next (the prompt rows against a window's rows, init_beam_state's staging against the rows'), and nothing here is
+// large enough to be worth sharing.  Extents follow the device buffers they stage (alloc_buffers).
+struct RowStage { int tok[MAX_ROWS], pos[MAX_ROWS], slot[MAX_ROWS], lslot[MAX_ROWS]; };      // upload_rows -> RowMeta
+struct PinnedScratch {
+  int64_t nsamp[MAX_ROWS];                     // stage_input: samples per utterance
+  int giveup;                                  // spin_gave_up: the give-up flag read back
+  RowStage rows, win_rows;                     // the search's rows (every caller's default); the rows of a draft-verification window
+  float beam_cum[MAX_ROWS]; unsigned beam_tick[4];      // init_beam_state
+  unsigned reseed_tick[4];                     // reseed_tick: bs.tick behind a draft verification
+  // wis_generate_draft: step index of the verified rows, their picks read back; then the search state `steps` ordinary steps would have left
+  int vstep[MAX_ROWS], pick_tok[MAX_ROWS]; float pick_lp[MAX_ROWS];
+  int hist[MAX_STEPS];
+  struct { int step, tok, pos, slot; float cum; } seed;
+  // wis_generate_draft_beam: the draft in BeamState::traj's layout, the host image of the verification state, done / step_u read back per
+  // window, the window rows' ancestor table and base slots, the per-window reset of the path bookkeeping (vs[2], then vs[DRAFT_VS_BASE + j])
+  int draft[MAX_STEPS * MAX_R * 2];
+  int vstate[DRAFT_VS_INTS]; int win_done, win_step;
+  int anc[MAX_ROWS * ANC_W], base[MAX_ROWS];
+  int path_reset[1 + MAX_R];
+  struct { int parent[MAX_R], step, done; } tree_seed;      // wis_debug_tree_logits: the search state behind the prompt pass
+  int al_frames[2 * MAX_ROWS], al_tgt[MAX_ROWS], al_dst[MAX_ROWS];      // wis_align: {tokens, frames} per utterance; target token / matrix row per pass row
+};
+static_assert(MAX_ROWS % 16 == 0, "a verification window is padded to whole groups of 16 rows: min(ANC_W, MAX_ROWS / beam) steps x beam rows must still fit MAX_ROWS");
+static_assert(sizeof(PinnedScratch::draft) == sizeof(int) * MAX_STEPS * MAX_R * 2, "the draft area holds one {token, origin} pair per step and beam slot");
+static_assert(sizeof(PinnedScratch::anc) == sizeof(int) * MAX_ROWS * ANC_W, "ANC_W ancestor slots per window row");
+// (the device buffers these two are copied to - d_draft, d_anc - are allocated by the staging areas' own extents: alloc_buffers)
+static_assert(DRAFT_VS_PERM + MAX_R <= 16 && DRAFT_VS_BASE + MAX_R <= 32 && DRAFT_VS_INTS >= 32, "the verification state's head (32 ints up, 16 back) holds the matching and the base slots");
+
 struct wis_model {
   wis_config_t cfg;
   int device;
@@ -174,7 +206,7 @@ struct wis_model {
   // decode state
   float *dx, *dq, *logits, *part; f16 *dao, *dh, *dln; unsigned* counters;
   float* dq2 = nullptr;         // batched fold: second half of the cross-attention q_raw (dec_forward_frag)
-  int sa_nb = 8;      // 8-position blocks the step's self-attention asks for per pass (generate_impl: by the step index; 8 outside the decode loop)
+  int sa_nb = 8;      // 8-position blocks the step's self-attention asks for per pass (generate.hip StepGraph: by the step index; 8 outside the step loops)
   float* gf_part = nullptr; unsigned* gf_cnt = nullptr; int gf_ksplit = 1;      // K split of the batched FFN2 skinny GEMM: slice sums, tickets (GemvP::ksplit)
   unsigned long long* ca_gran = nullptr; unsigned* ca_epoch = nullptr;      // granule hand-off of the decoder cross-attention (small grids): slots, flag + epochs
   unsigned long long* sa_gran = nullptr; unsigned* sa_epoch = nullptr;      // ... of q / k / v from the QKV projection to the self-attention fused into its launch: slots [H][8][3][64], epochs [H]
@@ -190,9 +222,9 @@ struct wis_model {
   int nsp_B = 0;                // ... its batch size; 0: the last call did not ask (wis_last_no_speech_prob answers WIS_E_STATE)
   float* d_in; int64_t* d_nsamp; float* d_probs;
   int* vstep = nullptr; int* pick_tok = nullptr; float* pick_lp = nullptr;      // wis_generate_draft: per-row step index, picked token / log-probability of the teacher-forced rows
-  int* d_draft = nullptr; int* d_anc = nullptr; int* d_vstate = nullptr; int* d_base = nullptr;        // wis_generate_draft_beam: the draft trajectory [256][MAX_R][2], the window rows' ancestor slots [MAX_ROWS][32], {steps verified}
+  int* d_draft = nullptr; int* d_anc = nullptr; int* d_vstate = nullptr; int* d_base = nullptr;        // wis_generate_draft_beam: the draft trajectory [MAX_STEPS][MAX_R][2], the window rows' ancestor slots [MAX_ROWS][ANC_W], the verification state, the rows' base slots
   float* lm_logspec = nullptr; unsigned* lm_gmax = nullptr;   // log-mel scratch of THIS replica (never shared with other callers)
-  int* h_pin;      // pinned host scratch
+  PinnedScratch* h_pin = nullptr;      // pinned host staging (one block, named areas)
   unsigned long long* h_prog = nullptr;      // host-mapped progress block of the beam search (kernels.hpp HP_*): the decode loop polls it
   unsigned gen = 0;                          // generation of the current search (records of an earlier call's over-run step are ignored)
   int last_B = 0, last_beam = 0;             // shape of the last generate call (wis_last_trajectory)
@@ -536,7 +568,7 @@ int alloc_buffers(wis_model* m) {
   WIS_RET(dalloc(m, &m->rm.tok, MAX_ROWS)); WIS_RET(dalloc(m, &m->rm.pos, MAX_ROWS));
   WIS_RET(dalloc(m, &m->rm.slot, MAX_ROWS)); WIS_RET(dalloc(m, &m->rm.lslot, MAX_ROWS));
   WIS_RET(dalloc(m, &m->rm_win.tok, MAX_ROWS)); WIS_RET(dalloc(m, &m->rm_win.pos, MAX_ROWS)); WIS_RET(dalloc(m, &m->rm_win.slot, MAX_ROWS)); WIS_RET(dalloc(m, &m->rm_win.lslot, MAX_ROWS));
-  const int max_new = 256, max_hyp = MAX_HYP;
+  const int max_new = MAX_STEPS, max_hyp = MAX_HYP;
   WIS_RET(dalloc(m, &m->bs.step_u, Bm)); WIS_RET(dalloc(m, &m->bs.done, Bm)); WIS_RET(dalloc(m, &m->bs.n_hyp, Bm));
   WIS_RET(dalloc(m, &m->bs.cum, slots));
   WIS_RET(dalloc(m, &m->bs.alive, (size_t)slots * max_new));
@@ -546,8 +578,8 @@ int alloc_buffers(wis_model* m) {
   WIS_RET(dalloc(m, &m->bs.all_done, 4));
   WIS_RET(dalloc(m, &m->bs.tick, 4));
   WIS_RET(dalloc(m, &m->vstep, MAX_ROWS)); WIS_RET(dalloc(m, &m->pick_tok, MAX_ROWS)); WIS_RET(dalloc(m, &m->pick_lp, MAX_ROWS));
-  WIS_RET(dalloc(m, &m->bs.traj, (size_t)Bm * 256 * MAX_R * 2));
-  WIS_RET(dalloc(m, &m->d_draft, (size_t)256 * MAX_R * 2)); WIS_RET(dalloc(m, &m->d_anc, (size_t)MAX_ROWS * 32)); WIS_RET(dalloc(m, &m->d_vstate, DRAFT_VS_INTS)); WIS_RET(dalloc(m, &m->d_base, MAX_ROWS));
+  WIS_RET(dalloc(m, &m->bs.traj, (size_t)Bm * MAX_STEPS * MAX_R * 2));
+  WIS_RET(dalloc(m, &m->d_draft, sizeof(PinnedScratch::draft) / sizeof(int))); WIS_RET(dalloc(m, &m->d_anc, sizeof(PinnedScratch::anc) / sizeof(int))); WIS_RET(dalloc(m, &m->d_vstate, DRAFT_VS_INTS)); WIS_RET(dalloc(m, &m->d_base, MAX_ROWS));
   WIS_HIP_CHECK(hipMemsetAsync(m->bs.tick, 0, 16, m->st));
   WIS_RET(dalloc(m, &m->bs.out_ids, (size_t)Bm * max_new)); WIS_RET(dalloc(m, &m->bs.out_len, Bm)); WIS_RET(dalloc(m, &m->bs.out_score, Bm));
   WIS_RET(dalloc(m, &m->st_max, (size_t)MAX_ROWS * STAT_SUB)); WIS_RET(dalloc(m, &m->st_sum, (size_t)MAX_ROWS * STAT_SUB));
@@ -559,7 +591,7 @@ int alloc_buffers(wis_model* m) {
   WIS_RET(dalloc(m, &m->lm_gmax, Bm));
   WIS_RET(dalloc(m, &m->d_probs, (size_t)Bm * (c.n_lang > 0 ? c.n_lang : 1)));
   WIS_RET(dalloc(m, &m->d_prof, ((size_t)c.n_dec_layers * 8 + 2) * 16));   // + sampling kernels (tap builds)
-  WIS_HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&m->h_pin), 65536, hipHostMallocDefault));
+  WIS_HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&m->h_pin), sizeof(PinnedScratch), hipHostMallocDefault));
   // fine-grained (coherent) host memory mapped into the device: beam_step_kernel's system-scope stores land here while the
   // stream is still running
   WIS_HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&m->h_prog), HP_BYTES, hipHostMallocMapped | hipHostMallocCoherent));
@@ -583,7 +615,7 @@ int stage_input(wis_model* m, const float* input, int kind, int B, hipStream_t o
       WIS_HIP_CHECK(hipMemcpyAsync(m->d_in, input, (size_t)B * WIS_N_SAMPLES * 4, hipMemcpyHostToDevice, st));
       dp = m->d_in;
     }
-    int64_t* hn = reinterpret_cast<int64_t*>(m->h_pin);
+    int64_t* hn = m->h_pin->nsamp;
     for (int b = 0; b < B; ++b) hn[b] = WIS_N_SAMPLES;
     WIS_HIP_CHECK(hipMemcpyAsync(m->d_nsamp, hn, (size_t)B * 8, hipMemcpyHostToDevice, st));
     WIS_RET(logmel_device(m->ctx, st, m->lm_logspec, m->lm_gmax, dp, WIS_N_SAMPLES, m->d_nsamp, B, nullptr, m->img, m->cfg.n_mels));
@@ -720,7 +752,7 @@ struct SpinClaim {
 };
 // reads and clears the give-up flag (word 0 of the epoch block); true = a combiner gave up: results of the pass are garbage
 static int spin_gave_up(wis_model* m, bool* gave_up) {
-  int* h = m->h_pin + 2;
+  int* h = &m->h_pin->giveup;
   WIS_HIP_CHECK(hipMemcpyAsync(h, m->ca_epoch, 4, hipMemcpyDeviceToHost, m->st));
   WIS_HIP_CHECK(hipStreamSynchronize(m->st));
   *gave_up = *h != 0;
@@ -741,7 +773,6 @@ static int spin_gave_up(wis_model* m, bool* gave_up) {
 // window position w0), cross-attention as B = M / 16 groups of R = 16 rows that all read utterance 0's K / V
 struct TreeWin { const int* anc; int w0, aw; const int* base = nullptr; };
 int align_capture_q(wis_model* m, int l, int M);      // align.hip
-constexpr int ANC_W = 32;      // ancestor-table entries per row = the most steps a window holds (beam 2 / 3: 32 steps = 64 / 96 rows)
 static int dec_forward_frag(wis_model* m, int M, int R, int B, bool want_logits, int sstride, int rmul, int chunks, const TreeWin* tw = nullptr) {
   const wis_config_t& c = m->cfg; hipStream_t st = m->st;
   const int d = c.d_model, H = c.n_heads, T = c.n_audio_ctx, ctx = c.n_text_ctx, MB = cdiv(M, 16);
@@ -933,10 +964,10 @@ int dec_forward(wis_model* m, int M, int R, int B, bool want_logits, int sstride
 static int init_beam_state(wis_model* m, int B, int beam) {
   hipStream_t st = m->st;
   const int Mrows = B * beam;
-  // staged in pinned memory of its own (h_pin + 2048 ..): the copies run when the stream gets there, nothing waits for them here
-  float* cum = reinterpret_cast<float*>(m->h_pin + 2048);
+  // staged in pinned memory of its own (PinnedScratch::beam_cum / beam_tick): the copies run when the stream gets there, nothing waits for them here
+  float* cum = m->h_pin->beam_cum;
   for (int r = 0; r < Mrows; ++r) cum[r] = (r % beam == 0) ? 0.f : -INFINITY;
-  unsigned* tk = reinterpret_cast<unsigned*>(m->h_pin + 2048 + MAX_ROWS);
+  unsigned* tk = m->h_pin->beam_tick;
   m->gen = (m->gen % 0xFFFFu) + 1u;      // 1 .. 65535: never the 0 of a cleared record
   tk[0] = 0; tk[1] = m->gen; tk[2] = 0; tk[3] = 0;
   WIS_HIP_CHECK(hipMemcpyAsync(m->bs.cum, cum, (size_t)Mrows * 4, hipMemcpyHostToDevice, st));
@@ -979,14 +1010,14 @@ static int check_patience(int beam, float patience) {
   return WIS_OK;
 }
 
-int upload_rows(wis_model* m, const std::vector<int>& tok, const std::vector<int>& pos, const std::vector<int>& slot, const std::vector<int>& lslot, bool wait = true, int stage = 1024) {
+int upload_rows(wis_model* m, const std::vector<int>& tok, const std::vector<int>& pos, const std::vector<int>& slot, const std::vector<int>& lslot, bool wait = true, RowStage* stage = nullptr) {
   const size_t n = tok.size();
-  int* h = m->h_pin + stage;      // (a caller that uploads twice without a wait in between passes a second staging area)
-  memcpy(h, tok.data(), n * 4); memcpy(h + MAX_ROWS, pos.data(), n * 4); memcpy(h + 2 * MAX_ROWS, slot.data(), n * 4); memcpy(h + 3 * MAX_ROWS, lslot.data(), n * 4);
-  WIS_HIP_CHECK(hipMemcpyAsync(m->rm.tok, h, n * 4, hipMemcpyHostToDevice, m->st));
-  WIS_HIP_CHECK(hipMemcpyAsync(m->rm.pos, h + MAX_ROWS, n * 4, hipMemcpyHostToDevice, m->st));
-  WIS_HIP_CHECK(hipMemcpyAsync(m->rm.slot, h + 2 * MAX_ROWS, n * 4, hipMemcpyHostToDevice, m->st));
-  WIS_HIP_CHECK(hipMemcpyAsync(m->rm.lslot, h + 3 * MAX_ROWS, n * 4, hipMemcpyHostToDevice, m->st));
+  RowStage* h = stage ? stage : &m->h_pin->rows;      // (a caller that uploads twice without a wait in between passes a second staging area)
+  memcpy(h->tok, tok.data(), n * 4); memcpy(h->pos, pos.data(), n * 4); memcpy(h->slot, slot.data(), n * 4); memcpy(h->lslot, lslot.data(), n * 4);
+  WIS_HIP_CHECK(hipMemcpyAsync(m->rm.tok, h->tok, n * 4, hipMemcpyHostToDevice, m->st));
+  WIS_HIP_CHECK(hipMemcpyAsync(m->rm.pos, h->pos, n * 4, hipMemcpyHostToDevice, m->st));
+  WIS_HIP_CHECK(hipMemcpyAsync(m->rm.slot, h->slot, n * 4, hipMemcpyHostToDevice, m->st));
+  WIS_HIP_CHECK(hipMemcpyAsync(m->rm.lslot, h->lslot, n * 4, hipMemcpyHostToDevice, m->st));
   // the pinned staging area is reused by the next upload: make sure the copies are done (wis_generate uploads once per call and
   // drains its stream before it returns or re-enters, so it does not wait here)
   if (wait) WIS_HIP_CHECK(hipStreamSynchronize(m->st));
@@ -1004,7 +1035,7 @@ int check_batch(wis_model* m, int B, int beam) {
 // replica from one worker thread).  A second thread entering the same handle is refused with WIS_E_STATE instead of silently
 // corrupting the first call's state - SURVEY 8(b) asks for thread safety at the boundary: concurrency comes from replicas and the
 // micro-batcher, never from two calls inside one replica.
-static std::atomic<int> g_active_calls[64];      // compute calls running per device (all handles): generate_impl's stream choice
+static std::atomic<int> g_active_calls[64];      // compute calls running per device (all handles): front_half's stream choice (generate.hip)
 struct BusyGuard {
   wis_model* m; bool ok;
   explicit BusyGuard(wis_model* mm) : m(mm), ok(!mm->busy.test_and_set(std::memory_order_acquire)) { if (ok) g_active_calls[m->device & 63].fetch_add(1, std::memory_order_relaxed); }
@@ -1128,526 +1159,11 @@ int wis_model_clone(wis_model_t* parent, wis_model_t** out) {
   return WIS_OK;
 }
 
-}  // extern "C" (reopened below: the generate driver is a static helper)
+}  // extern "C" (reopened below: the generate driver is made of static helpers)
 
-// The decoder rows of window steps s0 .. s0 + Rw - 1 of a beam trajectory (hd: [step][MAX_R][2] = token, origin; one utterance, k beams), step-major:
-// row (s, j) feeds the token live beam j got at step s - 1 at position P - 1 + s and keeps its K / V in slot j; ha[row][ANC_W] = the slot of the
-// row's ancestor at every window step (entry 0 doubles as the slot that holds everything before the window).  Padded to whole groups of 16 rows
-// with copies of the last row (they write the same K / V to the same place).  Returns the padded row count.
-static int fill_tree_window(const int* hd, int s0, int Rw, int k, int P, std::vector<int>& tok, std::vector<int>& pos, std::vector<int>& slot, std::vector<int>& ls, int* ha) {
-  const int Mreal = k * Rw, Mpad = cdiv(Mreal, 16) * 16;
-  tok.assign(Mpad, 0); pos.assign(Mpad, 0); slot.assign(Mpad, 0); ls.assign(Mpad, 0);
-  for (int t = 0; t < Rw; ++t) for (int j = 0; j < k; ++j) {
-    const int s_ = s0 + t, r = t * k + j;
-    tok[r] = hd[((s_ - 1) * MAX_R + j) * 2]; pos[r] = P - 1 + s_; slot[r] = j; ls[r] = j;
-    int a = j;                                    // ancestor of (s_, j) at window step sp, walking the origins back to s0
-    for (int sp = s_; sp >= s0; --sp) { ha[r * ANC_W + (sp - s0)] = a; a = hd[((sp - 1) * MAX_R + a) * 2 + 1]; }
-    for (int u = t + 1; u < ANC_W; ++u) ha[r * ANC_W + u] = ha[r * ANC_W + t];
-  }
-  for (int r = Mreal; r < Mpad; ++r) {
-    tok[r] = tok[Mreal - 1]; pos[r] = pos[Mreal - 1]; slot[r] = slot[Mreal - 1]; ls[r] = ls[Mreal - 1];
-    for (int u = 0; u < ANC_W; ++u) ha[r * ANC_W + u] = ha[(Mreal - 1) * ANC_W + u];
-  }
-  return Mpad;
-}
-
-// draft / n_draft / accepted: wis_generate_draft (one utterance, beam 1): the tokens of an earlier hypothesis to verify first
-// draft_org (beam > 1, wis_generate_draft_beam): draft = [n_draft][beam] tokens, draft_org = [n_draft][beam] the beam slot each continued from -
-// the trajectory of an earlier SEARCH (wis_last_trajectory); accepted = steps verified
-static int generate_impl(wis_model_t* m, const float* input, int B, const int32_t* prompt, int P,
-                 const wis_gen_opts_t* o, int32_t* out_ids, int32_t* out_len, float* out_score, bool* retry,
-                 const int32_t* draft = nullptr, int n_draft = 0, int* accepted = nullptr, const int32_t* draft_org = nullptr) {
-  *retry = false;
-  if (accepted) *accepted = 0;
-  m->nsp_B = 0;
-  WIS_HIP_CHECK(hipSetDevice(m->device));
-  SpinClaim claim(m, B);
-  const wis_config_t& c = m->cfg;
-  const int beam = o->beam_size < 1 ? 1 : o->beam_size;
-  WIS_RET(check_batch(m, B, beam));
-  WIS_RET(check_patience(beam, o->patience));
-  if (P < 1 || P > 16 || B * P > MAX_ROWS) { set_error("prompt length %d unsupported (1..16, B*P <= %d)", P, MAX_ROWS); return WIS_E_UNSUPPORTED; }
-  int max_new = o->max_new_tokens > 0 ? o->max_new_tokens : std::min(c.n_text_ctx / 2, c.n_text_ctx - P);
-  if (max_new > 256) max_new = 256;
-  if (P - 1 + max_new > c.n_text_ctx) max_new = c.n_text_ctx - (P - 1);
-  for (int i = 0; i < B * P; ++i) if (prompt[i] < 0 || prompt[i] >= c.n_vocab) { set_error("prompt token %d out of range", prompt[i]); return WIS_E_ARG; }
-  hipStream_t st = m->st;
-  const int ctx = c.n_text_ctx;
-  auto t0 = std::chrono::steady_clock::now();
-
-  // ---- decode state first: search counters and the prompt rows depend on nothing the encoder produces, and staged from pinned
-  // memory they cost the host no wait - the whole chain log-mel -> encoder -> cross-K/V -> prefill is enqueued behind them in one go
-  // (the prefill's ~230 launches are issued while the encoder runs instead of after two stream drains)
-  const int Mrows = B * beam;
-  WIS_RET(init_beam_state(m, B, beam));
-  float patience;
-  const SampleCfg sc = make_sample_cfg(m, o, beam, max_new, &patience);
-  const float* bias_all = o->suppress_default ? m->bias_all : nullptr;
-  const bool drafting = draft != nullptr && n_draft > 0;
-  const bool beam_draft = drafting && draft_org != nullptr;
-  if (drafting && B != 1) { set_error("wis_generate_draft: one utterance per call (got B = %d)", B); return WIS_E_UNSUPPORTED; }
-  if (drafting && !beam_draft && beam != 1) { set_error("wis_generate_draft: beam_size 1 (a beam search is drafted by its trajectory: wis_generate_draft_beam)"); return WIS_E_UNSUPPORTED; }
-  // Whisper's timestamp rules (prompts without <|notimestamps|>): a pre-pass ahead of the sampling statistics of every step
-  const bool ts = o->timestamps != 0;
-  const int ts_max_init = o->max_initial_timestamp_index < 0 ? -1 : o->max_initial_timestamp_index;
-  if (ts && draft != nullptr) { set_error("timestamps: not available for drafted decodes (wis_generate_draft / wis_generate_draft_beam)"); return WIS_E_UNSUPPORTED; }
-  int sot_row = -1;      // no_speech_prob: the prompt row that reads <|startoftranscript|> (the same in every utterance of the batch)
-  if (o->no_speech_prob && !drafting) {
-    for (int i = 0; i < P; ++i) if (prompt[i] == c.sot) { sot_row = i; break; }
-    for (int b = 1; b < B && sot_row >= 0; ++b) if (prompt[b * P + sot_row] != c.sot) sot_row = -1;
-    if (sot_row < 0) { set_error("no_speech_prob: the prompts hold no common <|startoftranscript|> position"); return WIS_E_ARG; }
-  }
-  if (beam_draft && (beam < 2 || n_draft > 256)) { set_error("wis_generate_draft_beam: beam_size >= 2 and at most 256 draft steps (got %d, %d)", beam, n_draft); return WIS_E_ARG; }
-  if (drafting) for (int i = 0; i < n_draft * (beam_draft ? beam : 1); ++i) if (draft[i] < 0 || draft[i] >= c.n_vocab) { set_error("draft token %d out of range", draft[i]); return WIS_E_ARG; }
-  if (beam_draft) for (int i = 0; i < n_draft * beam; ++i) if (draft_org[i] < 0 || draft_org[i] >= beam) { set_error("draft origin %d outside [0, beam_size)", draft_org[i]); return WIS_E_ARG; }
-  m->last_B = B; m->last_beam = beam;
-  // Verification passes keep to the ticket hand-off of the cross-attention: their picks are accepted on the host pass by pass, outside the
-  // progress record that carries the granule form's give-up flag (advisor, round 5) - the ordinary steps behind them take the call's form again
-  const bool spin_call = m->spin_now;
-  if (drafting) m->spin_now = false;
-  if (!drafting || beam_draft) {
-    std::vector<int> tok(B * P), pos(B * P), slot(B * P), ls(B * P);
-    for (int b = 0; b < B; ++b) for (int i = 0; i < P; ++i) { tok[b * P + i] = prompt[b * P + i]; pos[b * P + i] = i; slot[b * P + i] = b * beam; ls[b * P + i] = b * beam; }
-    WIS_RET(upload_rows(m, tok, pos, slot, ls, false));
-  }
-  const unsigned long long gen = m->gen;
-  // a give-up flag raised by the PREVIOUS call's over-run step (it ran after that call had returned) says nothing about this call: cleared
-  // behind that step, in stream order, before this call's first decoder pass can raise it again
-  if (m->overrun_left) { WIS_HIP_CHECK(hipMemsetAsync(m->ca_epoch, 0, 4, st)); m->overrun_left = false; }
-  __atomic_store_n(&m->h_prog[HP_REC], 0ull, __ATOMIC_RELAXED);      // (a record of an earlier call's over-run step may still land here: it carries that call's generation)
-  m->h_prog[HP_DONE_STEP] = 0; m->h_prog[HP_DONE_STAMP] = 0; m->h_prog[HP_STAMP0] = 0;
-
-  // Front half on a stream of its own.  A search that ended on EOT may have left ONE over-run decode step running on `st` (below): the
-  // log-mel and the encoder of this call touch none of the decoder's buffers, so they start at once beside it instead of behind it;
-  // the cross-K/V projection (which overwrites what that step still reads) and everything after it stay on `st`.  st_enc waits for the
-  // previous call's cross-K/V projection - the last reader of the encoder's output buffer.
-  // ... but only while this is the ONLY call running on the GPU.  HIP streams share a handful of hardware queues (four by default): with
-  // several replicas decoding at once a second stream per handle puts one replica's encoder and another's decode chain into the same
-  // queue, and the chain waits behind 100 us GEMMs - measured, 8 utterances per batch, 2 / 3 / 4 batches in flight: 130 / 151 / 145
-  // utterances/s with the second stream against 165 / 178 / 165 without.  Under that load the over-run step costs next to nothing anyway
-  // (the GPU is shared; the step is a thin chain).
-  static const bool one_stream = getenv("WIS_ONE_STREAM") != nullptr;      // A/B switch
-  static const bool two_streams = getenv("WIS_TWO_STREAMS") != nullptr;    // A/B switch: the second stream whatever else runs
-  const bool alone = g_active_calls[m->device & 63].load(std::memory_order_relaxed) <= 1;
-  hipStream_t se = (one_stream || !(alone || two_streams)) ? st : m->st_enc;
-  if (se != st) WIS_HIP_CHECK(hipStreamWaitEvent(se, m->ev_ckv, 0));
-  WIS_HIP_CHECK(hipEventRecord(m->ev[0], se));
-  WIS_RET(stage_input(m, input, o->input_kind, B, se));
-  WIS_HIP_CHECK(hipEventRecord(m->ev[1], se));
-  WIS_RET(run_encoder(m, B, se));
-  WIS_HIP_CHECK(hipEventRecord(m->ev[2], se));
-  if (se != st) { WIS_HIP_CHECK(hipEventRecord(m->ev_enc, se)); WIS_HIP_CHECK(hipStreamWaitEvent(st, m->ev_enc, 0)); }
-  WIS_RET(run_cross_kv(m, B));
-  WIS_HIP_CHECK(hipEventRecord(m->ev[3], st));
-  WIS_HIP_CHECK(hipEventRecord(m->ev_ckv, st));
-
-  // ---- prefill + FIRST decode step in one pass: all P prompt tokens of an utterance are rows (b, i) at positions i in the
-  // utterance's first KV slot (causal by position); the logits of the last prompt row seed the beams (CT2 forwards
-  // prompt[:-1] and then feeds prompt[-1] as the first decoder input — the same arithmetic, one weight pass instead of two)
-  int steps = 1;            // decoder passes done: the first step runs with the prefill pass
-  bool spec_done = false;   // the draft verification already met the end of the utterance
-  bool beam_fin = false;    // ... of a beam search: the replayed beam steps finished it, results are where beam_step_kernel puts them
-  std::vector<int> spec_gen; float spec_cum = 0.f; int spec_len = 0;
-  if (!drafting) {
-    WIS_RET(dec_forward(m, B * P, P, B, true, beam, 0));
-    // every prompt row has its logits after this pass: the <|startoftranscript|> row's are what no_speech_prob reads (raw, no processors)
-    if (sot_row >= 0) WIS_RET(launch_no_speech(st, m->logits, m->n_vocab_pad, B, P, sot_row, c.n_vocab, c.no_speech, m->d_nsp));
-    if (ts) WIS_RET(launch_ts_rules(st, m->logits, bias_all, m->bias_begin, m->bs, B, sc, c.no_timestamps, ts_max_init, P, 0, P - 1, m->ts_desc));
-    WIS_RET(launch_logit_stats(st, m->logits, bias_all, m->bias_begin, m->bs.step_u, m->st_max, m->st_sum, m->st_val, m->st_idx, B, sc, P, 0, P - 1, WIS_TAPS ? m->d_prof + (size_t)m->cfg.n_dec_layers * 8 * 16 + 16 : nullptr,
-                               nullptr, ts ? m->ts_desc : nullptr));
-    WIS_RET(launch_beam_step(st, m->st_max, m->st_sum, m->st_val, m->st_idx, m->bs, m->rm, B, P, ctx, sc, WIS_TAPS ? m->d_prof + (size_t)m->cfg.n_dec_layers * 8 * 16 : nullptr));
-    WIS_RET(launch_kv_reorder(st, m->kc_all, m->vc_all, m->kv_layer_stride, c.n_dec_layers, m->bs, B, beam, P, ctx, c.d_model));
-  } else if (beam_draft) {
-    // ---- verify the draft of a BEAM SEARCH (round 6; BASELINE configs[4] at the reference's long-audio beam, main.py:582-586).  The draft is
-    // the trajectory of an earlier search over (most of) the same audio: per step s the live set it left - k tokens and the beam slot each
-    // continued from.  If the search over THIS window has followed it up to step s0 - 1, the decoder rows of steps s0 .. s0 + Rw - 1 are
-    // known without running those steps: row (s, j) feeds the draft's token of live beam j after step s - 1 at position P - 1 + s.  They form a
-    // TREE (a beam's history is a path through earlier live sets), so the pass runs the self-attention by ancestor table (dec_self_attn_kernel
-    // TREE: node (s, j) keeps its K / V in slot j, row (s, j) reads position P - 1 + s' from the slot of its ancestor at step s') and the
-    // cross-attention as groups of 16 rows over the utterance's one K / V.  One weight stream then yields the logits of Rw steps x k beams;
-    // the steps are REPLAYED on them by the ordinary sampling kernels (logit_stats, beam_step: search state and hypothesis list end up exactly
-    // where Rw ordinary steps would leave them), each followed by draft_match_kernel: if the live set a replayed step produced is the draft's -
-    // as a SET: near-tied candidates swap slots between two searches all the time, so live beam j may be any draft node as long as every beam is
-    // found once; the next step reads beam j's logits from the row of its node - the next step's rows were the right ones; the first step with a
-    // beam the draft does not have still stands (its own inputs were verified), parks the search (done = 2), and ordinary steps resume behind
-    // it.  The cache: the pass left node (s, i)'s K / V in slot i of the draft's numbering; the matching kernel keeps every live beam's path
-    // through those slots and kv_gather_kernel turns the paths into "slot j = beam j's history" once per window.  A whole window is queued
-    // without a host round trip; the host looks once per window.  Exact by construction: every accepted step ran beam_step_kernel on the logits
-    // of its true inputs (summed in the multi-row order, as any other batch shape of the engine).
-    const int k = beam;
-    const int nd = std::min(n_draft, max_new - 1);
-    int* hd = m->h_pin + 8192;                         // the draft in BeamState::traj's layout ([step][MAX_R][2])
-    for (int s_ = 0; s_ < nd; ++s_) for (int j = 0; j < k; ++j) { hd[(s_ * MAX_R + j) * 2] = draft[s_ * k + j]; hd[(s_ * MAX_R + j) * 2 + 1] = draft_org[s_ * k + j]; }
-    int* hv = m->h_pin + 12288;                        // staging of the verification state (dec_kernels.hip draft_match_kernel: vs), read back per window
-    for (int i = 0; i < 32; ++i) hv[i] = 0;
-    for (int j = 0; j < MAX_R; ++j) { hv[DRAFT_VS_PERM + j] = j; hv[DRAFT_VS_BASE + j] = j; }
-    if (nd > 0) WIS_HIP_CHECK(hipMemcpyAsync(m->d_draft, hd, (size_t)nd * MAX_R * 2 * 4, hipMemcpyHostToDevice, st));
-    WIS_HIP_CHECK(hipMemcpyAsync(m->d_vstate, hv, 32 * 4, hipMemcpyHostToDevice, st));
-    // merged prefill + first step as in the ordinary call, then: is the search where the draft's step 0 says?
-    WIS_RET(dec_forward(m, P, P, 1, true, beam, 0));
-    WIS_RET(launch_logit_stats(st, m->logits, bias_all, m->bias_begin, m->bs.step_u, m->st_max, m->st_sum, m->st_val, m->st_idx, 1, sc, P, 0, P - 1));
-    WIS_RET(launch_beam_step(st, m->st_max, m->st_sum, m->st_val, m->st_idx, m->bs, m->rm, 1, P, ctx, sc));
-    WIS_RET(launch_kv_reorder(st, m->kc_all, m->vc_all, m->kv_layer_stride, c.n_dec_layers, m->bs, 1, beam, P, ctx, c.d_model));
-    WIS_RET(launch_draft_match(st, m->bs, m->d_draft, nd, k, m->d_vstate, 0));
-    const int RW = std::min(ANC_W, MAX_ROWS / k);       // steps per window: k x RW rows (beam 2 / 3: 32 steps, 5: 19, 8: 12), padded to whole groups of 16
-    const int s_last = std::min(nd, max_new - 1);       // last step a window can hold: rows from the draft's entry s - 1; step max_new - 1 ends every search
-    int* ha = m->h_pin + 12352;                         // ancestor table of the window rows, [rows][ANC_W] (.. 15424; the rows' staging follows at 15488)
-    int* hb = m->h_pin + 15872;                         // ... and the slot holding each row's history before the window, [rows] (.. 15968)
-    int* hw2 = m->h_pin + 16000;                        // per-window reset of the path bookkeeping: vs[2] = 0, vs[16 + j] = j
-    int done_flag = 0, step_dev = 0;
-    int pinv[MAX_R];                                    // real slot of draft node i at the window's start (the matching read back at the previous sync)
-    for (int j = 0; j < MAX_R; ++j) pinv[j] = j;        // (first window: every slot holds the same prompt rows - any assignment is right)
-    for (int s0 = 1;; ) {
-      const int Rw = std::min(RW, s_last - s0 + 1);
-      if (Rw >= 1) {
-        std::vector<int> tok, pos, slot, ls;
-        const int Mpad = fill_tree_window(hd, s0, Rw, k, P, tok, pos, slot, ls, ha);
-        for (int r = 0; r < Mpad; ++r) hb[r] = pinv[ha[r * ANC_W]];      // the row's window-step-0 ancestor is draft node ha[r][0]: its earlier history sits in that node's REAL slot
-        // the window's rows go through a row table of their own: the search's table (next input rows, written by the last beam step that
-        // counted) must survive a window that turns out to sit behind a parked search (queued before the host has looked)
-        const RowMeta rm_search = m->rm;
-        m->rm = m->rm_win;
-        int rc = upload_rows(m, tok, pos, slot, ls, false, 15488);      // (the prompt rows' staging copy may still be pending: own area; windows are a sync apart)
-        if (!rc && (hipMemcpyAsync(m->d_anc, ha, (size_t)Mpad * ANC_W * 4, hipMemcpyHostToDevice, st) != hipSuccess ||
-                    hipMemcpyAsync(m->d_base, hb, (size_t)Mpad * 4, hipMemcpyHostToDevice, st) != hipSuccess)) { set_error("draft window: ancestor table upload failed"); rc = WIS_E_HIP; }
-        TreeWin tw{m->d_anc, P - 1 + s0, ANC_W}; tw.base = m->d_base;
-        if (!rc) rc = dec_forward(m, Mpad, 16, Mpad / 16, true, 1, 0, &tw);
-        m->rm = rm_search;
-        WIS_RET(rc);
-        hw2[0] = 0; for (int j = 0; j < MAX_R; ++j) hw2[1 + j] = j;
-        WIS_HIP_CHECK(hipMemcpyAsync(m->d_vstate + 2, hw2, 4, hipMemcpyHostToDevice, st));
-        WIS_HIP_CHECK(hipMemcpyAsync(m->d_vstate + DRAFT_VS_BASE, hw2 + 1, MAX_R * 4, hipMemcpyHostToDevice, st));
-        for (int t = 0; t < Rw; ++t) {      // replay: beam j's logits come from the row of the draft node it is matched to (rowmap); no cache traffic per step
-          WIS_RET(launch_logit_stats(st, m->logits, bias_all, m->bias_begin, m->bs.step_u, m->st_max, m->st_sum, m->st_val, m->st_idx, 1, sc, beam, 1, t * k, nullptr, m->d_vstate + DRAFT_VS_PERM));
-          WIS_RET(launch_beam_step(st, m->st_max, m->st_sum, m->st_val, m->st_idx, m->bs, m->rm, 1, P, ctx, sc));
-          WIS_RET(launch_draft_match(st, m->bs, m->d_draft, nd, k, m->d_vstate, 1));
-        }
-        // the window's paths applied to the cache at once: slot j = live beam j's history, as ordinary steps (and the next window) expect it
-        WIS_RET(launch_kv_gather(st, m->kc_all, m->vc_all, m->kv_layer_stride, c.n_dec_layers, m->d_vstate, m->bs.done, beam, P - 1 + s0, ctx, c.d_model));
-      }
-      WIS_HIP_CHECK(hipMemcpyAsync(hv, m->d_vstate, 16 * 4, hipMemcpyDeviceToHost, st));      // steps verified, ..., the matching
-      WIS_HIP_CHECK(hipMemcpyAsync(hv + 24, m->bs.done, 4, hipMemcpyDeviceToHost, st));
-      WIS_HIP_CHECK(hipMemcpyAsync(hv + 25, m->bs.step_u, 4, hipMemcpyDeviceToHost, st));
-      WIS_HIP_CHECK(hipStreamSynchronize(st));
-      done_flag = hv[24]; step_dev = hv[25];
-      if (Rw < 1 || done_flag != 0) break;
-      for (int j = 0; j < k; ++j) { const int n_ = hv[DRAFT_VS_PERM + j]; if (n_ >= 0 && n_ < k) pinv[n_] = j; }
-      s0 += Rw;
-    }
-    if (accepted) *accepted = hv[0];
-    __atomic_store_n(&m->h_prog[HP_REC], 0ull, __ATOMIC_RELAXED);      // the replayed steps' progress records count launches, not steps: the pacing loop starts from `steps`
-    if (done_flag == 1) {      // the replayed steps ended the search: hypotheses ranked, result written by beam_step_kernel
-      beam_fin = true; steps = step_dev + 1;
-    } else {                   // parked behind a step that stands (or nothing to verify): ordinary steps resume
-      steps = step_dev;
-      if (steps < 1) { set_error("wis_generate_draft_beam: verification completed no step"); return WIS_E_STATE; }
-      int* hw = m->h_pin + 4096 + 512;
-      unsigned* tk = reinterpret_cast<unsigned*>(hw);
-      tk[0] = (unsigned)steps; tk[1] = m->gen; tk[2] = 0; tk[3] = 0;
-      WIS_HIP_CHECK(hipMemcpyAsync(m->bs.tick, tk, 16, hipMemcpyHostToDevice, st));
-      WIS_HIP_CHECK(hipMemsetAsync(m->bs.done, 0, 4, st));
-    }
-  } else {
-    // ---- verify the draft: the prompt and the draft tokens go through the decoder as teacher-forced rows, 16 positions per pass
-    // (causal by position inside the utterance's KV slot, like the merged prompt pass); row i's logits are what a greedy step fed
-    // seq[i] after seq[0..i-1] sees, so as long as every earlier draft token equalled the greedy pick, row P-1+g yields generated
-    // token g.  The first disagreement ends the verification WITH the right token for that index (its prefix was right); the K / V
-    // rows of the accepted prefix are in the cache, and the ordinary step loop continues from there.  Per pass one weight stream
-    // for up to 16 tokens instead of one per token.
-    const int nd = std::min(n_draft, max_new - 1);
-    std::vector<int> seq(P + nd);
-    for (int i = 0; i < P; ++i) seq[i] = prompt[i];
-    for (int i = 0; i < nd; ++i) seq[P + i] = draft[i];
-    // (r6) up to 96 positions per pass: more than 16 rows of one utterance go through the row-group form of the tree pass (a chain is a tree whose
-    // every ancestor sits in slot 0: dec_self_attn_kernel<TREE> with an all-zero table is "causal by position in the slot", the cross-attention
-    // takes the rows as groups of 16 over the one K / V) - the 100 rows of a 96-token draft are 2 passes (3.5 + 1.3 ms) instead of 7 x 1.35 ms.
-    // WIS_DRAFT_ROWS=16: the round-5 schedule (A/B)
-    static const int env_rows = getenv("WIS_DRAFT_ROWS") ? atoi(getenv("WIS_DRAFT_ROWS")) : 0;
-    const int R = (env_rows >= 16 && env_rows <= MAX_ROWS) ? env_rows / 16 * 16 : MAX_ROWS;
-    bool stop = false; int n_acc = 0;
-    for (int t0 = 0; t0 < P + nd && !stop; t0 += R) {
-      const int rows = std::min(R, P + nd - t0);
-      const int f = std::max(P - 1 - t0, 0), nv = rows - f;      // rows f .. rows-1 of this pass predict generated tokens
-      const int Mp = rows > 16 ? cdiv(rows, 16) * 16 : rows;      // (row groups: padded with copies of the last row - same K / V to the same place)
-      std::vector<int> tok(Mp), pos(Mp), slot(Mp, 0), ls(Mp, 0);
-      for (int i = 0; i < Mp; ++i) { const int ii = std::min(i, rows - 1); tok[i] = seq[t0 + ii]; pos[i] = t0 + ii; }
-      WIS_RET(upload_rows(m, tok, pos, slot, ls));
-      if (rows > 16) {
-        WIS_HIP_CHECK(hipMemsetAsync(m->d_anc, 0, (size_t)Mp * 16 * 4, st));
-        const TreeWin tw{m->d_anc, t0, 16};
-        WIS_RET(dec_forward(m, Mp, 16, Mp / 16, nv > 0, 1, 0, &tw));
-      } else
-      WIS_RET(dec_forward(m, rows, rows, 1, nv > 0, 1, 0));
-      if (nv <= 0) continue;
-      int* hv = m->h_pin + 4096;
-      for (int i = 0; i < nv; ++i) hv[i] = t0 + f + i - (P - 1);      // the step index of each verified row (first-step / EOT masks of logit_stats_kernel)
-      WIS_HIP_CHECK(hipMemcpyAsync(m->vstep, hv, (size_t)nv * 4, hipMemcpyHostToDevice, st));
-      WIS_RET(launch_logit_stats(st, m->logits, bias_all, m->bias_begin, m->vstep, m->st_max, m->st_sum, m->st_val, m->st_idx, nv, sc, 1, 0, f));
-      WIS_RET(launch_greedy_pick(st, m->st_max, m->st_sum, m->st_val, m->st_idx, nv, sc, m->pick_tok, m->pick_lp));
-      int* ht = m->h_pin + 4096 + MAX_ROWS; float* hl = reinterpret_cast<float*>(m->h_pin + 4096 + 2 * MAX_ROWS);
-      WIS_HIP_CHECK(hipMemcpyAsync(ht, m->pick_tok, (size_t)nv * 4, hipMemcpyDeviceToHost, st));
-      WIS_HIP_CHECK(hipMemcpyAsync(hl, m->pick_lp, (size_t)nv * 4, hipMemcpyDeviceToHost, st));
-      WIS_HIP_CHECK(hipStreamSynchronize(st));
-      for (int i = 0; i < nv && !stop; ++i) {
-        const int g = hv[i];
-        spec_cum = hl[i] + spec_cum;                       // beam_step_kernel: (logit - lse) + cum
-        spec_gen.push_back(ht[i]);
-        const bool eos = ht[i] == c.eot, is_last = g + 1 >= max_new;
-        if (eos || is_last) { spec_done = true; spec_len = eos ? g : g + 1; stop = true; }
-        else if (g < nd && ht[i] == draft[g]) ++n_acc;
-        else stop = true;                                  // first disagreement (or the row behind the last draft token): ht[i] is generated token g
-      }
-    }
-    if (accepted) *accepted = n_acc;
-    steps = (int)spec_gen.size();
-    if (steps < 1) { set_error("wis_generate_draft: verification produced no token"); return WIS_E_STATE; }
-    if (!spec_done) {
-      // the search state a run of `steps` ordinary steps would have left: history, cumulative score, next input row, counters
-      int* hs = m->h_pin + 4096;
-      for (int t = 0; t < steps; ++t) hs[t] = spec_gen[t];
-      WIS_HIP_CHECK(hipMemcpyAsync(m->bs.alive, hs, (size_t)steps * 4, hipMemcpyHostToDevice, st));
-      int* hw = m->h_pin + 4096 + 512;
-      hw[0] = steps; hw[1] = spec_gen.back(); hw[2] = P - 1 + steps; hw[3] = 0;
-      memcpy(hw + 4, &spec_cum, 4);
-      WIS_HIP_CHECK(hipMemcpyAsync(m->bs.step_u, hw, 4, hipMemcpyHostToDevice, st));
-      WIS_HIP_CHECK(hipMemcpyAsync(m->rm.tok, hw + 1, 4, hipMemcpyHostToDevice, st));
-      WIS_HIP_CHECK(hipMemcpyAsync(m->rm.pos, hw + 2, 4, hipMemcpyHostToDevice, st));
-      WIS_HIP_CHECK(hipMemcpyAsync(m->rm.slot, hw + 3, 4, hipMemcpyHostToDevice, st));
-      WIS_HIP_CHECK(hipMemcpyAsync(m->rm.lslot, hw + 3, 4, hipMemcpyHostToDevice, st));
-      WIS_HIP_CHECK(hipMemcpyAsync(m->bs.cum, hw + 4, 4, hipMemcpyHostToDevice, st));
-      unsigned* tk = reinterpret_cast<unsigned*>(hw + 8);
-      tk[0] = (unsigned)steps; tk[1] = m->gen; tk[2] = 0; tk[3] = 0;      // the progress record counts passes: `steps` of them are done
-      WIS_HIP_CHECK(hipMemcpyAsync(m->bs.tick, tk, 16, hipMemcpyHostToDevice, st));
-    }
-  }
-  m->spin_now = spin_call;
-  WIS_HIP_CHECK(hipEventRecord(m->ev[4], st));
-  if (beam_fin) WIS_HIP_CHECK(hipEventRecord(m->ev[5], st));
-
-  auto one_step = [&]() -> int {
-    WIS_RET(dec_forward(m, Mrows, beam, B, true, beam, 1));
-    if (ts) WIS_RET(launch_ts_rules(st, m->logits, bias_all, m->bias_begin, m->bs, B, sc, c.no_timestamps, ts_max_init, beam, 1, 0, m->ts_desc));
-    WIS_RET(launch_logit_stats(st, m->logits, bias_all, m->bias_begin, m->bs.step_u, m->st_max, m->st_sum, m->st_val, m->st_idx, B, sc, beam, 1, 0, WIS_TAPS ? m->d_prof + (size_t)m->cfg.n_dec_layers * 8 * 16 + 16 : nullptr,
-                               nullptr, ts ? m->ts_desc : nullptr));
-    WIS_RET(launch_beam_step(st, m->st_max, m->st_sum, m->st_val, m->st_idx, m->bs, m->rm, B, P, ctx, sc, WIS_TAPS ? m->d_prof + (size_t)m->cfg.n_dec_layers * 8 * 16 : nullptr));
-    WIS_RET(launch_kv_reorder(st, m->kc_all, m->vc_all, m->kv_layer_stride, c.n_dec_layers, m->bs, B, beam, P, ctx, c.d_model));
-    return WIS_OK;
-  };
-  // The step graph comes in up to three forms that differ in ONE kernel argument set: how many 8-position blocks of its rows' K / V history the self-attention
-  // asks for (dec_self_attn_kernel NB).  Every row of the pass that follows s beam steps has P + s positions - known HERE, by the step index, although the graph's
-  // kernel arguments are frozen - so the pass is launched from the graph whose self-attention asks for 16 / 32 / 64 positions (WIS_SA_NB=0: always 64, A/B switch).
-  static const bool sa_short = !(getenv("WIS_SA_NB") && atoi(getenv("WIS_SA_NB")) == 0);
-  auto nb_for = [&](int passes_done) { const int len = P + passes_done; return !sa_short ? 8 : (len <= 16 ? 2 : (len <= 32 ? 4 : 8)); };
-  struct NbReset { wis_model* m; ~NbReset() { m->sa_nb = 8; } } nb_reset{m};      // (everything outside this loop - prefill, verification windows, taps - asks for 64)
-  auto graph_for = [&](int nb, hipGraphExec_t* out) -> int {
-    GraphKey key; memset(&key, 0, sizeof(key));
-    key.B = B; key.beam = beam; key.P = P; key.max_new = max_new; key.fixed_new = sc.fixed_new; key.suppress_blank = sc.suppress_blank;
-    key.suppress_default = o->suppress_default; key.early_exit = sc.allow_early_exit; key.lp = sc.length_penalty; key.patience = patience; key.spin = (m->spin_now ? 1 : 0) | (sa_fuse_enabled() ? 2 : 0);
-    key.sa_nb = nb;
-    key.timestamps = ts ? 1 : 0; key.max_init = ts ? ts_max_init : 0;
-    auto it = m->graphs.find(key);
-    if (it != m->graphs.end()) { *out = it->second; return WIS_OK; }
-    hipGraph_t graph = nullptr; hipGraphExec_t ge = nullptr;
-    WIS_HIP_CHECK(hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal));
-    int rc = one_step();
-    hipError_t e = hipStreamEndCapture(st, &graph);
-    if (rc) { if (graph) hipGraphDestroy(graph); return rc; }
-    if (e != hipSuccess) { set_error("graph capture failed: %s", hipGetErrorString(e)); return WIS_E_HIP; }
-    e = hipGraphInstantiate(&ge, graph, nullptr, nullptr, 0);
-    hipGraphDestroy(graph);
-    if (e != hipSuccess) { set_error("graph instantiate failed: %s", hipGetErrorString(e)); return WIS_E_HIP; }
-    m->graphs[key] = ge;
-    *out = ge;
-    return WIS_OK;
-  };
-  auto launch_pass = [&](int passes_done) -> int {      // the decoder pass + sampling that follows `passes_done` passes
-    m->sa_nb = nb_for(passes_done);
-    if (!m->use_graph) return one_step();
-    hipGraphExec_t ge = nullptr;
-    WIS_RET(graph_for(m->sa_nb, &ge));
-    WIS_HIP_CHECK(hipGraphLaunch(ge, st));
-    return WIS_OK;
-  };
-  int needed = 0;           // steps after which the last utterance had finished (natural termination)
-  bool gave_up = false, from_host = false;
-  float decode_ms_dev = -1.f;
-  // with the measurement convention the step count is known: fixed_new tokens + the forced EOT
-  const int known = (sc.fixed_new > 0) ? std::min(max_new, sc.fixed_new + 1) : 0;
-  const int limit = known ? known : max_new;
-  auto unpack = [&](unsigned long long r, int* st_, int* dn_, int* gu_) {
-    if ((r >> 48) != gen) { *st_ = 0; *dn_ = 0; *gu_ = 0; return; }
-    *st_ = (int)((r >> 32) & 0xFFFFu); *gu_ = (int)((r >> 16) & 0xFFFFu); *dn_ = (int)(r & 0xFFFFu);
-  };
-  const int base_done = drafting ? steps : 0;      // passes the draft verification stands for: done before the first progress record of this call
-  const auto t_dec0 = std::chrono::steady_clock::now();
-  if (spec_done || beam_fin) {
-    needed = steps;
-  } else if (known) {
-    // every step goes out in one burst: nothing to find out from the device before the last one
-    for (; steps < limit; ++steps) WIS_RET(launch_pass(steps));
-    WIS_HIP_CHECK(hipEventRecord(m->ev[5], st));
-    WIS_HIP_CHECK(hipStreamSynchronize(st));
-    int st_, dn_, gu_; unpack(__atomic_load_n(&m->h_prog[HP_REC], __ATOMIC_ACQUIRE), &st_, &dn_, &gu_);
-    gave_up = gu_ != 0;
-    if (!gave_up && dn_ < B) { set_error("decode did not terminate within %d steps (done %d of %d)", steps, dn_, B); return WIS_E_STATE; }
-    needed = steps;
-  } else {
-    // A search that ends on EOT (every real request: the reference passes no max_length, main.py:687-693).  The host keeps `depth`
-    // steps enqueued beyond the last one it has seen complete (one running, one waiting behind it: the device never idles between
-    // steps) and reads the search's progress from the host-mapped record beam_step_kernel writes at the end of every step - no
-    // stream drain, no copy.  When the record says every utterance has finished, at most depth - 1 further steps are in the queue;
-    // they run on finished utterances (every sampling workgroup returns at its `done` test, results stay as they are) and this
-    // call does not wait for them: the results are already in host memory, the next call on the handle queues behind them.
-    const int depth = o->queue_depth > 0 ? o->queue_depth : 2;
-    auto t_last = std::chrono::steady_clock::now();
-    int seen = -1, st_ = 0, dn_ = 0, gu_ = 0;
-    static const bool trace = getenv("WIS_EOT_TRACE") != nullptr;      // per-step record of the pacing loop on stderr (tuning)
-    struct Tr { int step; unsigned long long dev; double host_us; int launched; };
-    std::vector<Tr> tr;
-    const auto t_loop = std::chrono::steady_clock::now();
-    for (unsigned spins = 0;; ++spins) {
-      unpack(__atomic_load_n(&m->h_prog[HP_REC], __ATOMIC_ACQUIRE), &st_, &dn_, &gu_);
-      if (st_ < base_done) st_ = base_done;
-      if (dn_ >= B || gu_) break;
-      if (st_ >= limit) break;                 // (cannot happen: the max_new-th step finishes every utterance)
-      if (steps < limit && steps - st_ < depth) {
-        const auto tl0 = std::chrono::steady_clock::now();
-        WIS_RET(launch_pass(steps));
-        ++steps;
-        if (trace) tr.push_back({-steps, 0ull, std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - tl0).count(), steps});      // (negative step: a launch, host_us = its duration)
-        continue;
-      }
-      if (st_ != seen) {
-        seen = st_; t_last = std::chrono::steady_clock::now(); spins = 0;
-        if (trace) tr.push_back({st_, m->h_prog[HP_STAMP], std::chrono::duration<double, std::micro>(t_last - t_loop).count(), steps});
-      }
-      else if ((spins & 1023u) == 1023u) {
-        const double idle = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_last).count();
-        if (idle > 30.0) { set_error("decode made no progress for 30 s (step %d of %d enqueued)", st_, steps); return WIS_E_HIP; }
-        if (idle > 200e-6) { struct timespec ts = {0, 20000}; nanosleep(&ts, nullptr); }      // long steps (big batches): stop burning the core
-      }
-      cpu_relax();
-    }
-    if (trace) {
-      unsigned long long prev_dev = 0;
-      for (size_t i = 0; i < tr.size(); ++i) {
-        if (tr[i].step < 0) { fprintf(stderr, "[eot-trace]   launch of step %d took the host %.1f us\n", -tr[i].step, tr[i].host_us); continue; }
-        fprintf(stderr, "[eot-trace] step %d seen by the host at %.1f us (device clock +%.1f us since the previous record), %d steps enqueued\n", tr[i].step, tr[i].host_us,
-                prev_dev ? (double)(tr[i].dev - prev_dev) * 0.01 : 0.0, tr[i].launched);
-        prev_dev = tr[i].dev;
-      }
-      fprintf(stderr, "[eot-trace] done seen at %.1f us: %d of %d utterances, %d steps enqueued\n", std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t_loop).count(), dn_, B, steps);
-    }
-    gave_up = gu_ != 0;
-    if (!gave_up && dn_ < B) { set_error("decode did not terminate within %d steps (done %d of %d)", steps, dn_, B); return WIS_E_STATE; }
-    if (!gave_up) {
-      from_host = true;
-      needed = (int)m->h_prog[HP_DONE_STEP];
-      const unsigned long long s0 = m->h_prog[HP_STAMP0], s1 = m->h_prog[HP_DONE_STAMP];
-      decode_ms_dev = s1 > s0 ? (float)((double)(s1 - s0) * 1e-5) : 0.f;      // 100 MHz constant clock; from the end of the first beam step (ev[4] is one kv_reorder later)
-      if (drafting) decode_ms_dev = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t_dec0).count();      // (no first beam step of its own: host clock)
-    }
-  }
-  // the granule hand-off's give-up flag (a combiner's bounded spin ran out: another handle's chain held the CUs its producers needed).
-  // Not an error for the caller: the handle keeps to the ticket hand-off from now on and the call is run again (wis_generate).
-  if (gave_up) {
-    WIS_HIP_CHECK(hipMemsetAsync(m->ca_epoch, 0, 4, st));
-    WIS_HIP_CHECK(hipStreamSynchronize(st));
-    m->spin_off = true; *retry = true; ++m->handoff_retries;
-    fprintf(stderr, "[wis_hip] device %d: decoder cross-attention granule hand-off timed out; this handle uses the ticket hand-off from now on, the call is repeated\n", m->device);
-    return WIS_OK;
-  }
-  // results: out_ids is [B][max_new] (beam_step_kernel indexes by the resolved max_new; the allocations are [.][256])
-  if (spec_done) {      // the verification rows already contained the end of the utterance: beam_step_kernel's finalisation, on the host
-    float sfin = spec_cum;
-    if (sc.length_penalty != 0.f) sfin /= powf((float)spec_len, sc.length_penalty);
-    out_len[0] = spec_len;
-    for (int t = 0; t < max_new; ++t) out_ids[t] = t < spec_len ? spec_gen[t] : 0;
-    if (out_score) out_score[0] = sfin;
-    from_host = true; decode_ms_dev = 0.f;
-  } else if (from_host) {
-    const int* hl = hp_out_len(m->h_prog); const float* hs = hp_out_score(m->h_prog); const int* hi = hp_out_ids(m->h_prog);
-    for (int b = 0; b < B; ++b) {
-      int n = hl[b];
-      if (n < 0 || n > max_new) { set_error("decode result of utterance %d has length %d outside [0, %d]", b, n, max_new); return WIS_E_STATE; }
-      out_len[b] = n;
-      for (int t = 0; t < max_new; ++t) out_ids[(size_t)b * max_new + t] = t < n ? hi[(size_t)b * max_new + t] : 0;
-      if (out_score) out_score[b] = hs[b];
-    }
-  } else {
-    std::vector<int32_t> ids((size_t)B * 256);
-    WIS_HIP_CHECK(hipMemcpyAsync(ids.data(), m->bs.out_ids, (size_t)B * 256 * 4, hipMemcpyDeviceToHost, st));
-    WIS_HIP_CHECK(hipMemcpyAsync(out_len, m->bs.out_len, (size_t)B * 4, hipMemcpyDeviceToHost, st));
-    std::vector<float> sc_h(B);
-    WIS_HIP_CHECK(hipMemcpyAsync(sc_h.data(), m->bs.out_score, (size_t)B * 4, hipMemcpyDeviceToHost, st));
-    WIS_HIP_CHECK(hipStreamSynchronize(st));
-    for (int b = 0; b < B; ++b) {
-      if (out_len[b] > max_new) out_len[b] = max_new;
-      for (int t = 0; t < max_new; ++t) out_ids[(size_t)b * max_new + t] = t < out_len[b] ? ids[(size_t)b * max_new + t] : 0;
-      if (out_score) out_score[b] = sc_h[b];
-    }
-  }
-  auto t1 = std::chrono::steady_clock::now();
-  float ms;
-  hipEventElapsedTime(&ms, m->ev[0], m->ev[1]); m->timing.logmel_ms = ms;
-  hipEventElapsedTime(&ms, m->ev[1], m->ev[2]); m->timing.encoder_ms = ms;
-  hipEventElapsedTime(&ms, m->ev[2], m->ev[3]); m->timing.crosskv_ms = ms;
-  hipEventElapsedTime(&ms, m->ev[3], m->ev[4]); m->timing.prefill_ms = ms;
-  if (from_host) m->timing.decode_ms = decode_ms_dev; else { hipEventElapsedTime(&ms, m->ev[4], m->ev[5]); m->timing.decode_ms = ms; }
-  m->timing.total_ms = std::chrono::duration<float, std::milli>(t1 - t0).count();
-  m->timing.decode_steps = steps;             // steps enqueued (the merged prefill + first step included)
-  m->timing.decode_steps_needed = needed;     // steps after which every utterance had finished: steps - needed = over-run
-  if (steps > needed) { claim.defer(st); m->overrun_left = true; }      // an over-run step is still queued: its combiners keep their share of the spin budget until it has run
-  if (sot_row >= 0) m->nsp_B = B;
-  return WIS_OK;
-}
+#include "generate.hip"      // the generate driver and its three entry points
 
 extern "C" {
-
-int wis_generate(wis_model_t* m, const float* input, int B, const int32_t* prompt, int P,
-                 const wis_gen_opts_t* o, int32_t* out_ids, int32_t* out_len, float* out_score) {
-  if (!m || !input || !prompt || !o || !out_ids || !out_len) { set_error("wis_generate: bad argument"); return WIS_E_ARG; }
-  WIS_ENTER(m, "wis_generate")
-  bool retry = false;
-  WIS_RET(generate_impl(m, input, B, prompt, P, o, out_ids, out_len, out_score, &retry));
-  if (retry) {      // once: the second run takes the ticket hand-off (spin_off is set), which cannot time out
-    WIS_RET(generate_impl(m, input, B, prompt, P, o, out_ids, out_len, out_score, &retry));
-    if (retry) { set_error("wis_generate: hand-off flag raised without the granule path"); return WIS_E_STATE; }
-  }
-  return WIS_OK;
-}
-
-int wis_generate_draft(wis_model_t* m, const float* input, const int32_t* prompt, int P, const wis_gen_opts_t* o,
-                       const int32_t* draft, int n_draft, int32_t* out_ids, int32_t* out_len, float* out_score, int32_t* accepted) {
-  if (!m || !input || !prompt || !o || !out_ids || !out_len || (n_draft > 0 && !draft) || n_draft < 0) { set_error("wis_generate_draft: bad argument"); return WIS_E_ARG; }
-  if (o->timestamps) { set_error("wis_generate_draft: timestamps are not available for drafted decodes"); return WIS_E_UNSUPPORTED; }
-  WIS_ENTER(m, "wis_generate_draft")
-  bool retry = false;
-  int acc = 0;
-  WIS_RET(generate_impl(m, input, 1, prompt, P, o, out_ids, out_len, out_score, &retry, draft, n_draft, &acc));
-  if (retry) {
-    WIS_RET(generate_impl(m, input, 1, prompt, P, o, out_ids, out_len, out_score, &retry, draft, n_draft, &acc));
-    if (retry) { set_error("wis_generate_draft: hand-off flag raised without the granule path"); return WIS_E_STATE; }
-  }
-  if (accepted) *accepted = acc;
-  return WIS_OK;
-}
-
-int wis_generate_draft_beam(wis_model_t* m, const float* input, const int32_t* prompt, int P, const wis_gen_opts_t* o,
-                            const int32_t* draft_tok, const int32_t* draft_org, int n_steps, int32_t* out_ids, int32_t* out_len, float* out_score, int32_t* accepted_steps) {
-  if (!m || !input || !prompt || !o || !out_ids || !out_len || n_steps < 0 || (n_steps > 0 && (!draft_tok || !draft_org))) { set_error("wis_generate_draft_beam: bad argument"); return WIS_E_ARG; }
-  if (o->timestamps) { set_error("wis_generate_draft_beam: timestamps are not available for drafted decodes"); return WIS_E_UNSUPPORTED; }
-  WIS_ENTER(m, "wis_generate_draft_beam")
-  bool retry = false;
-  int acc = 0;
-  for (int attempt = 0; attempt < 2; ++attempt) {
-    WIS_RET(generate_impl(m, input, 1, prompt, P, o, out_ids, out_len, out_score, &retry, n_steps > 0 ? draft_tok : nullptr, n_steps, &acc, n_steps > 0 ? draft_org : nullptr));
-    if (!retry) break;
-    if (attempt == 1) { set_error("wis_generate_draft_beam: hand-off flag raised without the granule path"); return WIS_E_STATE; }
-  }
-  if (accepted_steps) *accepted_steps = acc;
-  return WIS_OK;
-}
 
 int wis_last_no_speech_prob(wis_model_t* m, int B, float* out) {
   if (!m || !out || B < 1) { set_error("wis_last_no_speech_prob: bad argument"); return WIS_E_ARG; }
@@ -1669,10 +1185,10 @@ int wis_last_trajectory(wis_model_t* m, int b, int32_t* tok, int32_t* org, int c
   int n = 0;
   WIS_HIP_CHECK(hipMemcpyAsync(&n, m->bs.step_u + b, 4, hipMemcpyDeviceToHost, m->st));
   WIS_HIP_CHECK(hipStreamSynchronize(m->st));
-  if (n < 0 || n > 256) { set_error("wis_last_trajectory: step counter %d out of range", n); return WIS_E_STATE; }
+  if (n < 0 || n > MAX_STEPS) { set_error("wis_last_trajectory: step counter %d out of range", n); return WIS_E_STATE; }
   if (n > cap_steps) n = cap_steps;
   std::vector<int> raw((size_t)n * MAX_R * 2);
-  if (n) WIS_HIP_CHECK(hipMemcpy(raw.data(), m->bs.traj + (size_t)b * 256 * MAX_R * 2, raw.size() * 4, hipMemcpyDeviceToHost));
+  if (n) WIS_HIP_CHECK(hipMemcpy(raw.data(), m->bs.traj + (size_t)b * MAX_STEPS * MAX_R * 2, raw.size() * 4, hipMemcpyDeviceToHost));
   for (int s = 0; s < n; ++s) for (int j = 0; j < k; ++j) { tok[s * k + j] = raw[((size_t)s * MAX_R + j) * 2]; org[s * k + j] = raw[((size_t)s * MAX_R + j) * 2 + 1]; }
   *n_steps = n;
   return WIS_OK;
@@ -1680,31 +1196,30 @@ int wis_last_trajectory(wis_model_t* m, int b, int32_t* tok, int32_t* org, int c
 
 int wis_debug_search(wis_model_t* m, const float* logits, int n_steps, int B, const wis_gen_opts_t* o,
                      int32_t* out_ids, int32_t* out_len, float* out_score, int32_t* out_finish_step, int32_t* out_parent) {
-  if (!m || !logits || !o || !out_ids || !out_len || n_steps < 1 || n_steps > 256) { set_error("wis_debug_search: bad argument"); return WIS_E_ARG; }
+  if (!m || !logits || !o || !out_ids || !out_len || n_steps < 1 || n_steps > MAX_STEPS) { set_error("wis_debug_search: bad argument"); return WIS_E_ARG; }
   WIS_ENTER(m, "wis_debug_search")
   WIS_HIP_CHECK(hipSetDevice(m->device));
   const wis_config_t& c = m->cfg;
   const int beam = o->beam_size < 1 ? 1 : o->beam_size;
   WIS_RET(check_batch(m, B, beam));
   WIS_RET(check_patience(beam, o->patience));
-  const int max_new = o->max_new_tokens > 0 ? std::min(o->max_new_tokens, 256) : n_steps;
+  const int max_new = o->max_new_tokens > 0 ? std::min(o->max_new_tokens, MAX_STEPS) : n_steps;
   if (max_new > n_steps) { set_error("wis_debug_search: %d steps of logits for max_new_tokens %d", n_steps, max_new); return WIS_E_ARG; }
   hipStream_t st = m->st;
-  const int Mrows = B * beam, V = c.n_vocab, P = 1;
+  const int Mrows = B * beam, V = c.n_vocab;
   WIS_RET(init_beam_state(m, B, beam));
   float patience;
-  const SampleCfg sc = make_sample_cfg(m, o, beam, max_new, &patience);
-  const float* bias_all = o->suppress_default ? m->bias_all : nullptr;
-  const bool ts = o->timestamps != 0;
-  const int ts_max_init = o->max_initial_timestamp_index < 0 ? -1 : o->max_initial_timestamp_index;
+  SampleCtx g;      // a search over given logits: a one-token prompt
+  g.m = m; g.st = st; g.B = B; g.P = 1; g.beam = beam;
+  g.sc = make_sample_cfg(m, o, beam, max_new, &patience);
+  g.bias_all = o->suppress_default ? m->bias_all : nullptr;
+  g.ts = o->timestamps != 0;
+  g.ts_max_init = o->max_initial_timestamp_index < 0 ? -1 : o->max_initial_timestamp_index;
   std::vector<int> done(B, 0), fin(B, -1), par(Mrows);
   for (int s = 0; s < max_new; ++s) {
     WIS_HIP_CHECK(hipMemcpy2DAsync(m->logits, (size_t)m->n_vocab_pad * 4, logits + (size_t)s * Mrows * V, (size_t)V * 4, (size_t)V * 4, Mrows, hipMemcpyHostToDevice, st));
     // step 0 samples every beam of an utterance from ONE row (wis_generate: the last prompt row; here row b*beam), later steps row b*beam + j
-    if (ts) WIS_RET(launch_ts_rules(st, m->logits, bias_all, m->bias_begin, m->bs, B, sc, c.no_timestamps, ts_max_init, beam, s == 0 ? 0 : 1, 0, m->ts_desc));
-    WIS_RET(launch_logit_stats(st, m->logits, bias_all, m->bias_begin, m->bs.step_u, m->st_max, m->st_sum, m->st_val, m->st_idx, B, sc, beam, s == 0 ? 0 : 1, 0, nullptr, nullptr,
-                               ts ? m->ts_desc : nullptr));
-    WIS_RET(launch_beam_step(st, m->st_max, m->st_sum, m->st_val, m->st_idx, m->bs, m->rm, B, P, c.n_text_ctx, sc));
+    WIS_RET(sampling_tail(g, {beam, s == 0 ? 0 : 1, 0}, TAIL_NO_CACHE));
     WIS_HIP_CHECK(hipMemcpyAsync(done.data(), m->bs.done, (size_t)B * 4, hipMemcpyDeviceToHost, st));
     WIS_HIP_CHECK(hipMemcpyAsync(par.data(), m->bs.parent, (size_t)Mrows * 4, hipMemcpyDeviceToHost, st));
     WIS_HIP_CHECK(hipStreamSynchronize(st));
@@ -1714,18 +1229,8 @@ int wis_debug_search(wis_model_t* m, const float* logits, int n_steps, int B, co
     if (all) break;
   }
   for (int b = 0; b < B; ++b) if (fin[b] < 0) { set_error("wis_debug_search: utterance %d did not finish within %d steps", b, max_new); return WIS_E_STATE; }
-  std::vector<int32_t> ids((size_t)B * 256);
-  std::vector<float> sc_h(B);
-  WIS_HIP_CHECK(hipMemcpyAsync(ids.data(), m->bs.out_ids, (size_t)B * 256 * 4, hipMemcpyDeviceToHost, st));
-  WIS_HIP_CHECK(hipMemcpyAsync(out_len, m->bs.out_len, (size_t)B * 4, hipMemcpyDeviceToHost, st));
-  WIS_HIP_CHECK(hipMemcpyAsync(sc_h.data(), m->bs.out_score, (size_t)B * 4, hipMemcpyDeviceToHost, st));
-  WIS_HIP_CHECK(hipStreamSynchronize(st));
-  for (int b = 0; b < B; ++b) {
-    if (out_len[b] > max_new) out_len[b] = max_new;
-    for (int t = 0; t < max_new; ++t) out_ids[(size_t)b * max_new + t] = t < out_len[b] ? ids[(size_t)b * max_new + t] : 0;
-    if (out_score) out_score[b] = sc_h[b];
-    if (out_finish_step) out_finish_step[b] = fin[b];
-  }
+  WIS_RET(results_from_device(m, B, max_new, out_ids, out_len, out_score));
+  if (out_finish_step) for (int b = 0; b < B; ++b) out_finish_step[b] = fin[b];
   return WIS_OK;
 }
 
@@ -1872,20 +1377,20 @@ int wis_debug_tree_logits(wis_model_t* m, const float* input, int input_kind, co
   for (int i = 0; i < P; ++i) { ptok[i] = prompt[i]; ppos[i] = i; }
   WIS_RET(upload_rows(m, ptok, ppos, pslot, pls));
   WIS_RET(dec_forward(m, P, P, 1, false, beam, 0));
-  int* hs = m->h_pin + 4096;
-  for (int j = 0; j < MAX_R; ++j) hs[j] = 0;
-  hs[8] = 1; hs[9] = 0;
-  WIS_HIP_CHECK(hipMemcpyAsync(m->bs.parent, hs, (size_t)k * 4, hipMemcpyHostToDevice, st));
-  WIS_HIP_CHECK(hipMemcpyAsync(m->bs.step_u, hs + 8, 4, hipMemcpyHostToDevice, st));
-  WIS_HIP_CHECK(hipMemcpyAsync(m->bs.done, hs + 9, 4, hipMemcpyHostToDevice, st));
+  auto& hs = m->h_pin->tree_seed;
+  for (int j = 0; j < MAX_R; ++j) hs.parent[j] = 0;
+  hs.step = 1; hs.done = 0;
+  WIS_HIP_CHECK(hipMemcpyAsync(m->bs.parent, hs.parent, (size_t)k * 4, hipMemcpyHostToDevice, st));
+  WIS_HIP_CHECK(hipMemcpyAsync(m->bs.step_u, &hs.step, 4, hipMemcpyHostToDevice, st));
+  WIS_HIP_CHECK(hipMemcpyAsync(m->bs.done, &hs.done, 4, hipMemcpyHostToDevice, st));
   WIS_RET(launch_kv_reorder(st, m->kc_all, m->vc_all, m->kv_layer_stride, c.n_dec_layers, m->bs, 1, beam, P, c.n_text_ctx, c.d_model));
   // one window: steps 1 .. n_steps, rows from trajectory entries 0 .. n_steps - 1
   std::vector<int> hd((size_t)n_steps * MAX_R * 2, 0);
-  for (int s_ = 0; s_ < n_steps; ++s_) for (int j = 0; j < k; ++j) { hd[(s_ * MAX_R + j) * 2] = tok[s_ * k + j]; hd[(s_ * MAX_R + j) * 2 + 1] = org[s_ * k + j]; }
+  pack_traj(hd.data(), tok, org, n_steps, k);
   std::vector<int> wt, wp, wsl, wls;
-  int* ha = m->h_pin + 12352;
+  int* ha = m->h_pin->anc;
   const int Mpad = fill_tree_window(hd.data(), 1, n_steps, k, P, wt, wp, wsl, wls, ha);
-  WIS_RET(upload_rows(m, wt, wp, wsl, wls, false, 15488));
+  WIS_RET(upload_rows(m, wt, wp, wsl, wls, false, &m->h_pin->win_rows));
   WIS_HIP_CHECK(hipMemcpyAsync(m->d_anc, ha, (size_t)Mpad * ANC_W * 4, hipMemcpyHostToDevice, st));
   const TreeWin tw{m->d_anc, P, ANC_W};
   WIS_RET(dec_forward(m, Mpad, 16, Mpad / 16, true, 1, 0, &tw));
