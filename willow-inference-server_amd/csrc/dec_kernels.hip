@@ -20,8 +20,6 @@
 //    pass over the logits (16 chunks per row), the beam bookkeeping runs on device (one wave per
 //    utterance) so the host never sees logits and a whole step replays as one HIP graph.
 #include <string.h>
-#include <atomic>
-#include <mutex>
 #include "common.hpp"
 #include "kernels.hpp"
 
@@ -182,7 +180,8 @@ int launch_pack_gemv(hipStream_t st, const f16* W, f16* Wp, int N, int Npad, int
 }
 
 // 8-byte {tag, value} granules: one relaxed agent-scope (write-through) store each, "the data is the flag" (guide G16 form R2) - the hand-off of the
-// decoder cross-attention's chunk partials (dec_cross_attn_kernel SPIN) and of q / k / v from the QKV projection to the self-attention fused into its launch
+// decoder cross-attention's chunk partials (dec_cross_attn_kernel SPIN).  Lesson of the three in-launch hand-offs that were tried for the step's other
+// stages and lost (retired experiments): an in-launch hand-off is two fabric round trips (granule store -> L2 -> poll), like a kernel boundary.
 typedef unsigned long long gran_t;
 __device__ __forceinline__ void st_gran(gran_t* p, unsigned tag, float v) {
   __hip_atomic_store(p, ((gran_t)tag << 32) | (gran_t)__float_as_uint(v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -190,120 +189,9 @@ __device__ __forceinline__ void st_gran(gran_t* p, unsigned tag, float v) {
 __device__ __forceinline__ gran_t ld_gran(const gran_t* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 constexpr unsigned CA_SPIN_LIMIT = 1u << 17;      // sweeps before the combiner gives up (~0.1 s)
 
-// ---- self-attention FUSED into the QKV projection's launch (round 6; round-5 review item 4a) -----------------------------------------
-// The one-utterance decode step ran  QKV projection -> [kernel boundary] -> dec_self_attn_kernel  per layer: a 1.6 us dispatch boundary plus a 5 us
-// kernel whose only inputs from the projection are 64 floats of q and one new K / V row per (row, head).  Now the projection's launch carries
-// H extra workgroups behind its n-tiles - one per head, dispatched after every producer tile of the launch - that run dec_self_attn_kernel's
-// arithmetic (same lane mapping, same order: bit-identical results): each wave owns rows w and w + 4, requests the row's K / V HISTORY from the
-// cache at once (it was written by earlier steps: nothing to wait for), then polls the 192 granules the projection's epilogue publishes for its
-// (row, head) - q[64], k[64], v[64] of the CURRENT position, tagged with the head's epoch + 1 - and finishes.  The boundary, the kernel's own
-// start-up and its history round trip are gone from the chain; what is left behind the last projection tile is one L2 round trip and the softmax.
-// Hand-off rules as in dec_cross_attn_kernel's granule form: producers store and leave (no drain, no ticket); the head's consumer advances the
-// epoch word at the end of the launch (tags only grow: graph replays stay valid, nothing is reset); a consumer's spin is bounded and raises the
-// cross-attention's give-up flag word (the host repeats the call with both hand-offs in their kernel-boundary forms); consumers are dispatched
-// behind their producers, so they can never hold a slot a producer of the same launch still needs.
-// Only for decode rows that own their KV slot (rmul = 1: the ordinary step; prefill rows of one slot read each other's rows of the same launch).
-__device__ __forceinline__ void sa_consume(const GemvP& p, const int h, char* smem) {
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, pl = lane >> 3, c = lane & 7;
-  const int M = p.M, d = p.d, ctx = p.ctx;
-  float* shq = reinterpret_cast<float*>(smem) + wave * 512;                  // per wave: q f32 [64] | k f16 [64] | v f16 [64] | red f32 [4][64]
-  f16* shk = reinterpret_cast<f16*>(shq + 64); f16* shv = shk + 64; float* red = shq + 128;
-  const unsigned tag = __hip_atomic_load(p.sa_epoch + h, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) + 1u;
-  const int hoff = h * 64 + 8 * c;
-  for (int m = wave; m < M; m += 4) {
-    const int ls = (m / p.sa_rpu) * p.sa_sstride + (m % p.sa_rpu);
-    const int len = p.pos[m] + 1;
-    const f16* krow = p.kc + (size_t)ls * ctx * d + hoff;
-    const f16* vrow = p.vc + (size_t)ls * ctx * d + hoff;
-    u32x4 kr[8], vr[8];
-#pragma unroll
-    for (int i = 0; i < 8; ++i) kr[i] = *reinterpret_cast<const u32x4*>(krow + (size_t)(8 * i + pl) * d);      // history (position len - 1 is replaced below)
-#pragma unroll
-    for (int i = 0; i < 8; ++i) vr[i] = *reinterpret_cast<const u32x4*>(vrow + (size_t)(8 * i + pl) * d);
-    // the current position's q / k / v: lane owns element `lane` of each
-    const gran_t* g = p.sa_gran + ((size_t)(h * 8 + m) * 3) * 64 + lane;
-    gran_t gq, gk, gv;
-    for (unsigned spins = 0;; ++spins) {
-      gq = ld_gran(g); gk = ld_gran(g + 64); gv = ld_gran(g + 128);
-      const bool ok = ((unsigned)(gq >> 32) == tag) & ((unsigned)(gk >> 32) == tag) & ((unsigned)(gv >> 32) == tag);
-      if (__ballot(!ok) == 0ull) break;
-      if (spins > CA_SPIN_LIMIT) { if (lane == 0) atomicOr(p.sa_flag, 1u); break; }      // the give-up flag word of the cross-attention hand-off: one host protocol for both
-      __builtin_amdgcn_s_sleep(1);
-    }
-    shq[lane] = __uint_as_float((unsigned)gq); shk[lane] = (f16)__uint_as_float((unsigned)gk); shv[lane] = (f16)__uint_as_float((unsigned)gv);
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    float qv[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) qv[j] = shq[8 * c + j];
-    const u32x4 kcur = *reinterpret_cast<const u32x4*>(shk + 8 * c), vcur = *reinterpret_cast<const u32x4*>(shv + 8 * c);
-    float m_run = -INFINITY, l_run = 0.f;
-    float acc[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) acc[j] = 0.f;
-    int p0 = 0;
-    do {
-      if (p0 > 0) {
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-          const int pp = p0 + 8 * i + pl, pc = pp < len ? pp : len - 1;
-          kr[i] = *reinterpret_cast<const u32x4*>(krow + (size_t)pc * d);
-          vr[i] = *reinterpret_cast<const u32x4*>(vrow + (size_t)pc * d);
-        }
-      }
-#pragma unroll
-      for (int i = 0; i < 8; ++i) { const bool cur = p0 + 8 * i + pl == len - 1; kr[i] = cur ? kcur : kr[i]; vr[i] = cur ? vcur : vr[i]; }
-      float sc[8]; float mx = -INFINITY;
-#pragma unroll
-      for (int i = 0; i < 8; ++i) {
-        const int pp = p0 + 8 * i + pl;
-        float dot = 0.f;
-        if (pp < len) {
-          const f16x8 kv = *reinterpret_cast<const f16x8*>(&kr[i]);
-#pragma unroll
-          for (int j = 0; j < 8; ++j) dot = fmaf((float)kv[j], qv[j], dot);
-        }
-        dot += dpp_f<0xB1>(dot); dot += dpp_f<0x4E>(dot); dot += dpp_f<0x141>(dot);
-        sc[i] = (pp < len) ? dot : -INFINITY;
-        mx = fmaxf(mx, sc[i]);
-      }
-      mx = wave_max(mx);
-      const float m_new = fmaxf(m_run, mx);
-      const float alpha = __expf(m_run - m_new);
-      float lsum = 0.f;
-#pragma unroll
-      for (int j = 0; j < 8; ++j) acc[j] *= alpha;
-#pragma unroll
-      for (int i = 0; i < 8; ++i) {
-        const float pw = __expf(sc[i] - m_new);
-        lsum += pw;
-        if (p0 + 8 * i + pl < len) {
-          const f16x8 vv = *reinterpret_cast<const f16x8*>(&vr[i]);
-#pragma unroll
-          for (int j = 0; j < 8; ++j) acc[j] = fmaf(pw, (float)vv[j], acc[j]);
-        }
-      }
-      l_run = l_run * alpha + wave_sum(lsum) * 0.125f;
-      m_run = m_new;
-      p0 += 64;
-    } while (p0 < len);
-#pragma unroll
-    for (int j = 0; j < 8; ++j) acc[j] += dpp_f<0x128>(acc[j]);
-    if ((lane & 8) == 0) {
-#pragma unroll
-      for (int j = 0; j < 8; ++j) red[(lane >> 4) * 64 + 8 * c + j] = acc[j];
-    }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    const float o = (red[lane] + red[64 + lane]) + (red[128 + lane] + red[192 + lane]);
-    p.sa_out[(size_t)m * d + h * 64 + lane] = (f16)(o / l_run);
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier();      // (the LDS row is reused by this wave's next row)
-  }
-  __syncthreads();
-  if (tid == 0) __hip_atomic_store(p.sa_epoch + h, tag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);      // the next launch's epoch
-}
-
 // =======================================================================================
 // Skinny GEMM.  grid = Npad/16 workgroups of 4 waves; wave w streams the k-steps of its quarter of
-// every staged K-chunk.  Dynamic LDS: xs f16 [M][KC+8] | red f32 [4][MB][64][4] | stats f32 [48][2] | sred f32 [4][8]
+// every staged K-chunk.  Dynamic LDS: xs f16 [M][KC+8] | red f32 [4][64][4] | stats f32 [MAX_ROWS][2] (unused) | sred f32 [4][8]
 //
 // Memory-latency structure (one dependent round trip): the activation loads (L2-hot, written by the
 // previous kernel) are issued FIRST, then a 16-deep prefetch of this wave's weight fragments (HBM);
@@ -312,20 +200,17 @@ __device__ __forceinline__ void sa_consume(const GemvP& p, const int h, char* sm
 // SC (template): compile-time k-steps per wave (K / 128) for the common single-chunk shapes {3,4,6,8,10} so the prefetch and
 // the MFMA loop are straight-line code (every runtime `u < S` guard would be a scalar branch around one load); SC = 0 is the
 // generic ring of 16 fragments with refill.
-
-// WIS_EP_EARLY (build flag, default 0): request the epilogue operands (bias, folded column sums, row scales, residual / KV-cache
-// slot) right BEHIND the weight prefetch instead of after the last MFMA (vmcnt retires in order, so they cannot delay the
-// activations or a weight fragment).  Measured on MI355X (round 2, build.py --variant, tools/run_r2c.sh): 33.12 vs 32.82 ms per
-// utterance at B = 1, 97.8 vs 97.7 ms at B = 8 - no gain: the epilogue round trip is already hidden behind the cross-wave
-// reduction, and the extra 15-18 live VGPRs cost as much as they save.  The late form stays the product default.
-#ifndef WIS_EP_EARLY
-#define WIS_EP_EARLY 0
-#endif
+// Two A/B builds of this body found no gain and are gone: requesting the epilogue operands right behind the weight prefetch instead of after the last
+// MFMA (33.12 vs 32.82 ms per utterance: the round trip is already hidden behind the cross-wave reduction, and 15-18 more live VGPRs cost what it saves),
+// and fetching the rows' LayerNorm shifts with one vector load per row instead of through the scalar cache (the round-2..4 form: five of a wave's 25 requests).
+// MB (16-row blocks) is 1 at every call site - more than 16 rows take launch_gemv_frag.  The `MB > 1` arms below (30-piece register staging, multi-chunk
+// `more`, per-block accumulators) are dead at compile time; they and the parameter stay because without them hipcc allocates the registers of the MODE 1
+// kernels differently, and this body is kept instruction for instruction.
 // MODE 0: generic staging from global; 1: fast LayerNorm prologue from registers; 2: fast f16 activations from registers
 // NT (r5; MB = 1, single chunk, compile-time SC only): n-tiles per workgroup.  2: waves 0-1 own tile 2 nt, waves 2-3 tile 2 nt + 1, half of
 // K each (SC = K / 64 fragments per wave, all requested up front) - half as many workgroups stage the activation rows, each with twice
 // the weight bytes in flight: N = 4d of the one-utterance step is 160 workgroups (one per CU) instead of 320 on 256 CUs.
-template <int MB, int MODE, int SC, int RM, bool W8, int NT = 1, bool SA = false>
+template <int MB, int MODE, int SC, int RM, bool W8, int NT = 1>
 __device__ __forceinline__ void gemv_body(const GemvP& p, const int KC, const int nt, char* smem) {
   static_assert(NT == 1 || (NT == 2 && MB == 1 && SC > 0), "two-tile workgroups: <= 16 rows, every fragment prefetched");
   typedef typename WFrag<W8>::T WT;
@@ -367,9 +252,6 @@ __device__ __forceinline__ void gemv_body(const GemvP& p, const int KC, const in
   unsigned long long* pf = (nt == 0 && tid == 0) ? p.prof : nullptr;
   if (tid == 0) tl_begin(p.prof);
   stamp(pf, 0);
-  // fused self-attention (sa_consume): this tile's head and the tag its granules carry (requested with everything else)
-  unsigned sa_tag = 0;
-  if (SA) { const int nh = rows * nt, sec = nh / p.d; sa_tag = __hip_atomic_load(p.sa_epoch + ((nh - sec * p.d) >> 6), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) + 1u; }
   if (x16) {
     const u32x4* x8 = reinterpret_cast<const u32x4*>(p.x);
     const int k8n16 = K >> 3, t8 = tid < k8n16 ? tid : k8n16 - 1;      // (clamped address: threads >= K / 8 load a valid chunk and drop it)
@@ -391,15 +273,10 @@ __device__ __forceinline__ void gemv_body(const GemvP& p, const int KC, const in
 #pragma unroll
     // (the shifts are uniform over the workgroup: fetched through the SCALAR cache - as vector loads they were five of a wave's 25 requests
     // on the CU's address path, the unit the start of these kernels is bound by)
-#ifdef WIS_CSHIFT_VLOAD      // (A/B build: the round-2..4 form, one vector load per row)
-    for (int r = 0; r < RMAX; ++r) { const int rr = r < M ? r : M - 1; cshift[r] = reinterpret_cast<const float*>(p.x)[(size_t)rr * K]; }
-#else
     for (int r = 0; r < RMAX; ++r) { const int rr = r < M ? r : M - 1; cshift[r] = uniform_load_issue_f32(reinterpret_cast<const float*>(p.x) + (size_t)rr * K); }
-#endif
   }
   // f16 activations (attention / FFN hidden output of the previous kernel): same idea, up to 13 x 16 B per thread
-  // (MB >= 2: up to 48 rows x 1280 columns per chunk = 30 x 16 B per thread; K larger than the chunk is walked chunk by
-  // chunk, the next chunk's activations are fetched into registers while the matrix cores work on the current one)
+  // (single chunk: the launcher selects this mode only when KC == K)
   constexpr bool fastx = MODE == 2;
   constexpr int NXH = fastx ? (MB == 1 ? 13 : 30) : 1;
   u32x4 xh[NXH];
@@ -440,29 +317,14 @@ __device__ __forceinline__ void gemv_body(const GemvP& p, const int KC, const in
   const bool ep_ok = ep_act && ep_m < M && ep_n < p.N && 4 * (lane >> 4) < rows;
   float4 ep_bias = make_float4(0.f, 0.f, 0.f, 0.f), ep_cs = ep_bias, ep_res = ep_bias, ep_sc = make_float4(1.f, 1.f, 1.f, 1.f);
   int ep_slot = 0, ep_pos = 0;
-  // GV_LNP (f16 rows + per-16-column (sum, M2) partials of the rows in stat_in): mean / rstd merged Chan-style about the first
-  // tile's mean by the four lanes of a row, a quarter of the K / 16 pairs each - gemv_frag_body's form.  The consumer then needs
-  // neither the fp32 rows (a third of the load instructions of a LayerNorm-folded launch were those) nor a pass over them.
-  const bool lnp = fastx && (p.flags & GV_LNP);
-  constexpr int LNQ = 20;                     // pairs per lane: K / 64 <= 20 (K <= 1280); larger K takes the loop form
-  float2 lnp_pr[LNQ]; float lnp_c = 0.f;
 #define WIS_EP_LOADS()                                                                                              \
-  if (lnp && ep_act) {                                                                                              \
-    const int mm = ep_m < M ? ep_m : M - 1, nq = K >> 6;                                                            \
-    const float2* row = reinterpret_cast<const float2*>(p.stat_in) + (size_t)mm * (K >> 4);                         \
-    const float2* sp = row + (size_t)(lane >> 4) * nq;                                                              \
-    lnp_c = row[0].x * 0.0625f;                                                                                     \
-    _Pragma("unroll") for (int i = 0; i < LNQ; ++i) lnp_pr[i] = sp[i < nq ? i : nq - 1];                            \
-  }                                                                                                                 \
   if (ep_ok) {                                                                                                      \
     if (p.bias) ep_bias = *reinterpret_cast<const float4*>(p.bias + ep_n);                                          \
-    if (fast || lnp) ep_cs = *reinterpret_cast<const float4*>(p.csum + ep_n);                                       \
+    if (fast) ep_cs = *reinterpret_cast<const float4*>(p.csum + ep_n);                                              \
     if (W8) ep_sc = *reinterpret_cast<const float4*>(p.wscale + ep_n);                                              \
     if (p.flags & GV_QKV) { if (ep_n >= p.d) { ep_slot = p.slot[ep_m]; ep_pos = p.pos[ep_m]; } }                    \
     else if (p.flags & GV_RESID) ep_res = *reinterpret_cast<const float4*>(reinterpret_cast<const float*>(p.y) + (size_t)ep_m * p.N + ep_n); \
   }
-  constexpr bool ep_early = WIS_EP_EARLY && MB == 1 && SC > 0;    // single chunk, every weight fragment already requested
-  if (ep_early) { WIS_EP_LOADS() }
   stamp(pf, 1);
   float sa[RMAX], sb[RMAX];
   if (x16) {
@@ -484,11 +346,9 @@ __device__ __forceinline__ void gemv_body(const GemvP& p, const int KC, const in
     stamp(pf, 2);
   } else
   if (fast) {
-#ifndef WIS_CSHIFT_VLOAD
     uniform_load_wait();      // the rows' shifts (requested with the activation rows, long landed)
 #pragma unroll
     for (int r = 0; r < RMAX; ++r) uniform_load_landed(cshift[r]);
-#endif
 #pragma unroll
     for (int r = 0; r < RMAX; ++r) {
       const int rr = r < M ? r : M - 1;       // clamped rows rewrite row M-1 with identical values (benign)
@@ -523,7 +383,7 @@ __device__ __forceinline__ void gemv_body(const GemvP& p, const int KC, const in
   const int c8n = KC / 8;
   for (int kc0 = 0; kc0 < K; kc0 += KC) {
     const WT* wq = wp4 + (size_t)(kc0 / 32 + ksl0) * wstep;
-    const bool more = MB > 1 && kc0 + KC < K;     // multi-chunk register staging exists for the batched row counts only
+    const bool more = MB > 1 && kc0 + KC < K;     // (dead: MB == 1)
     if (kc0 > 0 && SC == 0) {
 #pragma unroll
       for (int u = 0; u < GV_PF; ++u) if (u < S && wact) wf[u] = __builtin_nontemporal_load(wq + (size_t)u * wstep);
@@ -582,9 +442,9 @@ __device__ __forceinline__ void gemv_body(const GemvP& p, const int KC, const in
     }
   }
   stamp(pf, 4);
-  // (late form: requested NOW - every weight fragment has been consumed, so they cannot hold up the in-order vmcnt queue - and
+  // (requested NOW - every weight fragment has been consumed, so they cannot hold up the in-order vmcnt queue - and
   // covered by the reductions and the barrier below; requested BEFORE the activations they delayed them and cost more than they saved)
-  if (!ep_early) { WIS_EP_LOADS() }
+  WIS_EP_LOADS()
 #undef WIS_EP_LOADS
   if (fast) {   // LayerNorm statistics of the folded form: reduced here, behind the MFMAs, published with the accumulators
 #pragma unroll
@@ -615,21 +475,8 @@ __device__ __forceinline__ void gemv_body(const GemvP& p, const int KC, const in
     }
     const int m = ep_m, n = ep_n;
     float4 rsum = make_float4(0.f, 0.f, 0.f, 0.f);      // the residual row values this lane stored (statistics partials below)
-    float lnp_mu = 0.f, lnp_rs = 1.f;
-    if (lnp) {      // whole wave: ((q0 + q1) + (q2 + q3)) of the row's four quarter sums on every lane
-      const int nq = K >> 6;
-      float t1 = 0.f, t2 = 0.f;
-#pragma unroll
-      for (int i = 0; i < LNQ; ++i) if (i < nq) { const float dm = lnp_pr[i].x * 0.0625f - lnp_c; t1 += dm; t2 += lnp_pr[i].y + 16.0f * dm * dm; }
-      t1 += __shfl_xor(t1, 16); t2 += __shfl_xor(t2, 16);
-      t1 += __shfl_xor(t1, 32); t2 += __shfl_xor(t2, 32);
-      const float invK = 1.0f / (float)K, dmu = t1 * 16.0f * invK;
-      lnp_mu = lnp_c + dmu;
-      lnp_rs = 1.0f / sqrtf(fmaxf(t2 * invK - dmu * dmu, 0.f) + 1e-5f);
-    }
     if (ep_ok) {
       if (W8) { s.x *= ep_sc.x; s.y *= ep_sc.y; s.z *= ep_sc.z; s.w *= ep_sc.w; }
-      if (lnp) { s.x = lnp_rs * (s.x - lnp_mu * ep_cs.x); s.y = lnp_rs * (s.y - lnp_mu * ep_cs.y); s.z = lnp_rs * (s.z - lnp_mu * ep_cs.z); s.w = lnp_rs * (s.w - lnp_mu * ep_cs.w); }
       if (fast) {   // y = rs * (W' x - mu * c) [+ b' below]
         const int r = m < RMAX ? m : RMAX - 1;
         const float invK = 1.0f / (float)K;
@@ -645,13 +492,8 @@ __device__ __forceinline__ void gemv_body(const GemvP& p, const int KC, const in
       s.x += ep_bias.x; s.y += ep_bias.y; s.z += ep_bias.z; s.w += ep_bias.w;
       if (p.flags & GV_QKV) {
         const int d = p.d;
-        if (SA) {      // q / k / v of the current position to the head's consumer workgroup of this launch: four granules per lane
-          const int sec = n / d, hn = n - sec * d;
-          gran_t* gp = p.sa_gran + (((size_t)((hn >> 6) * 8 + m) * 3) + sec) * 64 + (hn & 63);
-          st_gran(gp, sa_tag, s.x); st_gran(gp + 1, sa_tag, s.y); st_gran(gp + 2, sa_tag, s.z); st_gran(gp + 3, sa_tag, s.w);
-        }
         if (n < d) {
-          if (!SA) *reinterpret_cast<float4*>(p.q + (size_t)m * d + n) = s;
+          *reinterpret_cast<float4*>(p.q + (size_t)m * d + n) = s;
         } else {
           const bool isk = n < 2 * d;
           f16* dst = (isk ? p.kc : p.vc) + ((size_t)ep_slot * p.ctx + ep_pos) * d + (n - (isk ? d : 2 * d));
@@ -700,65 +542,24 @@ __device__ __forceinline__ void gemv_body(const GemvP& p, const int KC, const in
 #define WIS_GV_LEAD(q) (q).x, (q).x2, (q).Wp, (q).M, (q).N, (q).K, (q).xsplit
 #define WIS_GV_LEAD_DECL(s) const void* s##x, const void* s##x2, const f16* s##Wp, int s##M, int s##N, int s##K, int s##xsplit
 #define WIS_GV_LEAD_APPLY(q, s) (q).x = s##x; (q).x2 = s##x2; (q).Wp = s##Wp; (q).M = s##M; (q).N = s##N; (q).K = s##K; (q).xsplit = s##xsplit
-template <int MB, int MODE, int SC, int RM, bool W8, int NT = 1, bool SA = false>
+template <int MB, int MODE, int SC, int RM, bool W8, int NT = 1>
 __global__ __launch_bounds__(256) void gemv_kernel(WIS_GV_LEAD_DECL(l_), int KC, GemvP p) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   WIS_GV_LEAD_APPLY(p, l_);
-  if (SA && (int)blockIdx.x >= p.sa_first) { sa_consume(p, (int)blockIdx.x - p.sa_first, smem); return; }      // the heads' self-attention workgroups, behind the n-tiles
-  gemv_body<MB, MODE, SC, RM, W8, NT, SA>(p, KC, blockIdx.x, smem);
+  gemv_body<MB, MODE, SC, RM, W8, NT>(p, KC, blockIdx.x, smem);
 }
 // Two skinny GEMMs in ONE launch (workgroups [0, nA) run problem A, the rest problem B; both f16-activation, single-chunk,
 // <= 16 rows): the decoder's attention output projection together with the cross-attention query projection folded THROUGH it
 // (model.hip fused_out_cq): one dependent stage instead of two.
-// (r6, WIS_CA_PREFETCH=1) L2 prefetch riders: the launch leaves 96 of 256 CUs idle, the cross-attention that follows it starts with a 7.7 MB K / V stream
-// from HBM.  Workgroup nA + nB + i of this launch touches exactly what workgroup i of the cross-attention will load (key chunk c = i % chunks of head
-// h = i / chunks: 32 KB of K fragments, 32 KB of V^T rows) and leaves; with the round-robin placement of linear workgroup ids over the 8 XCDs both land on
-// XCD i % 8, i.e. in the L2 the consumer reads through.
-struct DualPf { const f16* k; const f16* v; int T, Tpad, chunks, CL, n; };
 template <int SCA, int SCB>
 __global__ __launch_bounds__(256) void gemv_dual_kernel(int nA, int M, const void* ax, const f16* aWp, const void* bx, const void* bx2, const f16* bWp, int bxsplit,
-                                                        GemvP pa, GemvP pb, DualPf pf) {
+                                                        GemvP pa, GemvP pb) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  if (pf.n && (int)blockIdx.x >= pf.n) {
-    const int i = (int)blockIdx.x - pf.n, c = i % pf.chunks, h = i / pf.chunks, tid = threadIdx.x;
-    const int klo = c * pf.CL;
-    const f16* kb = pf.k + (size_t)h * 8 * pf.T * 8;
-    const f16* vb = pf.v + (size_t)h * 64 * pf.Tpad;
-    u32x4 sink = {0u, 0u, 0u, 0u};
-#pragma unroll
-    for (int u = 0; u < 8; ++u) {      // K: 8 planes x CL keys x 16 B
-      int key = klo + tid; if (key > pf.T - 1) key = pf.T - 1;
-      const u32x4 v = *reinterpret_cast<const u32x4*>(kb + ((size_t)u * pf.T + key) * 8);
-      sink[0] ^= v[0]; sink[1] ^= v[1]; sink[2] ^= v[2]; sink[3] ^= v[3];
-    }
-#pragma unroll
-    for (int u = 0; u < 8; ++u) {      // V^T: 64 rows x CL keys x 2 B = 64 x 32 pieces of 16 B
-      const int piece = tid + 256 * u, row = piece >> 5, col = piece & 31;
-      const u32x4 v = *reinterpret_cast<const u32x4*>(vb + (size_t)row * pf.Tpad + klo + 8 * col);
-      sink[0] ^= v[0]; sink[1] ^= v[1]; sink[2] ^= v[2]; sink[3] ^= v[3];
-    }
-    asm volatile("" :: "v"(sink[0]), "v"(sink[1]), "v"(sink[2]), "v"(sink[3]));
-    return;
-  }
   // (K of either problem is the instantiation's: SC k-steps of 32 per wave, four waves)
   if ((int)blockIdx.x < nA) { pa.x = ax; pa.x2 = nullptr; pa.Wp = aWp; pa.M = M; pa.K = SCA * 128; gemv_body<1, 2, SCA, 1, false>(pa, SCA * 128, blockIdx.x, smem); }
   else { pb.x = bx; pb.x2 = bx2; pb.Wp = bWp; pb.M = M; pb.K = SCB * 128; pb.xsplit = bxsplit; gemv_body<1, 2, SCB, 1, false>(pb, SCB * 128, (int)blockIdx.x - nA, smem); }
 }
-// per-device launch state of the skinny GEMM (several replica worker threads may launch on different GPUs at once): the dynamic-LDS
-// ceiling of each device, queried once, and the lock under which the per-instantiation attribute is raised
-static std::mutex g_gemv_dev_mu;
-static std::atomic<size_t> g_gemv_lds_max[64];
-static size_t gemv_lds_limit(int dev) {
-  size_t v = g_gemv_lds_max[dev & 63].load(std::memory_order_acquire);
-  if (!v) {
-    int a = 0;
-    if (hipDeviceGetAttribute(&a, hipDeviceAttributeMaxSharedMemoryPerBlock, dev) != hipSuccess || a < 65536) a = 65536;
-    v = (size_t)a;
-    g_gemv_lds_max[dev & 63].store(v, std::memory_order_release);
-  }
-  return v;
-}
-int launch_gemv_dual(hipStream_t st, const GemvP& pa, const GemvP& pb, const f16* pf_k, const f16* pf_v, int pf_T, int pf_Tpad, int pf_chunks, int pf_H) {
+int launch_gemv_dual(hipStream_t st, const GemvP& pa, const GemvP& pb) {
   if (pa.M != pb.M || pa.M < 1 || pa.M > 16 || pa.x2 || pa.wscale || pb.wscale || (pa.flags & (GV_LN | GV_QKV)) || (pb.flags & (GV_LN | GV_QKV))) { set_error("gemv_dual: unsupported pair"); return WIS_E_UNSUPPORTED; }
   if (pa.M * (pa.K / 8) > 13 * 256 || pb.M * (pb.K / 8) > 13 * 256 || pa.K % 128 || pb.K % 128) { set_error("gemv_dual: rows do not fit the register staging (M=%d K=%d/%d)", pa.M, pa.K, pb.K); return WIS_E_UNSUPPORTED; }
   const int sa = pa.K / 128, sb = pb.K / 128;
@@ -767,35 +568,23 @@ int launch_gemv_dual(hipStream_t st, const GemvP& pa, const GemvP& pb, const f16
   const size_t lds = (((size_t)pa.M * (Kmax + 8) * 2 + 15) & ~(size_t)15) + aux;
   if (lds > 65536) { set_error("gemv_dual: LDS"); return WIS_E_UNSUPPORTED; }
   const int nA = cdiv(pa.N, 16), nB = cdiv(pb.N, 16);
-  DualPf pf; memset(&pf, 0, sizeof(pf));
-  if (pf_k && pf_v && pf_chunks > 0) {
-    const int CL = cdiv(cdiv(pf_T, pf_chunks), 32) * 32, used = cdiv(pf_T, CL);
-    if (CL == 256 && (nA + nB) % 8 == 0) { pf.k = pf_k; pf.v = pf_v; pf.T = pf_T; pf.Tpad = pf_Tpad; pf.chunks = used; pf.CL = CL; pf.n = nA + nB; }
-  }
-  dim3 grid(nA + nB + (pf.n ? pf.chunks * pf_H : 0)), block(256);
+  dim3 grid(nA + nB), block(256);
   GemvP a = pa, b = pb; a.rows = 16; b.rows = 16;
-  if (sa == 10 && sb == 20) hipLaunchKernelGGL((gemv_dual_kernel<10, 20>), grid, block, lds, st, nA, a.M, a.x, a.Wp, b.x, b.x2, b.Wp, b.xsplit, a, b, pf);
-  else if (sa == 8 && sb == 16) hipLaunchKernelGGL((gemv_dual_kernel<8, 16>), grid, block, lds, st, nA, a.M, a.x, a.Wp, b.x, b.x2, b.Wp, b.xsplit, a, b, pf);
-  else if (sa == 6 && sb == 12) hipLaunchKernelGGL((gemv_dual_kernel<6, 12>), grid, block, lds, st, nA, a.M, a.x, a.Wp, b.x, b.x2, b.Wp, b.xsplit, a, b, pf);
-  else if (sa == 4 && sb == 8) hipLaunchKernelGGL((gemv_dual_kernel<4, 8>), grid, block, lds, st, nA, a.M, a.x, a.Wp, b.x, b.x2, b.Wp, b.xsplit, a, b, pf);
-  else if (sa == 3 && sb == 6) hipLaunchKernelGGL((gemv_dual_kernel<3, 6>), grid, block, lds, st, nA, a.M, a.x, a.Wp, b.x, b.x2, b.Wp, b.xsplit, a, b, pf);
+  if (sa == 10 && sb == 20) hipLaunchKernelGGL((gemv_dual_kernel<10, 20>), grid, block, lds, st, nA, a.M, a.x, a.Wp, b.x, b.x2, b.Wp, b.xsplit, a, b);
+  else if (sa == 8 && sb == 16) hipLaunchKernelGGL((gemv_dual_kernel<8, 16>), grid, block, lds, st, nA, a.M, a.x, a.Wp, b.x, b.x2, b.Wp, b.xsplit, a, b);
+  else if (sa == 6 && sb == 12) hipLaunchKernelGGL((gemv_dual_kernel<6, 12>), grid, block, lds, st, nA, a.M, a.x, a.Wp, b.x, b.x2, b.Wp, b.xsplit, a, b);
+  else if (sa == 4 && sb == 8) hipLaunchKernelGGL((gemv_dual_kernel<4, 8>), grid, block, lds, st, nA, a.M, a.x, a.Wp, b.x, b.x2, b.Wp, b.xsplit, a, b);
+  else if (sa == 3 && sb == 6) hipLaunchKernelGGL((gemv_dual_kernel<3, 6>), grid, block, lds, st, nA, a.M, a.x, a.Wp, b.x, b.x2, b.Wp, b.xsplit, a, b);
   else { set_error("gemv_dual: K=%d/%d not instantiated", pa.K, pb.K); return WIS_E_UNSUPPORTED; }
   return WIS_OK;
 }
 
 int launch_gemv(hipStream_t st, const GemvP& p) {
-  if (p.M < 1 || p.M > 48 || p.K % 128 || p.N % 4) { set_error("gemv: M=%d N=%d K=%d unsupported (the LDS-staged form holds <= 48 rows; more rows take launch_gemv_frag)", p.M, p.N, p.K); return WIS_E_UNSUPPORTED; }
-  const int MB = cdiv(p.M, 16);
-  // largest K-chunk (multiple of 128 dividing K) whose f16 image of M rows fits the LDS: 64 KiB for <= 16 rows (several
-  // workgroups per CU), the whole 160 KiB CU array (minus slack) for the batched-decode row counts
-  int cur_dev = 0;
-  if (hipGetDevice(&cur_dev) != hipSuccess) cur_dev = 0;
-  const size_t lds_dev_max = gemv_lds_limit(cur_dev);
-  // (two half-size chunks so that two workgroups fit a CU were measured slower for N = 4d: 24.3 vs 19.0 us at 40 rows)
-  const size_t lds_cap = MB == 1 ? 65536 : (lds_dev_max > 155648 ? 155648 : lds_dev_max);
+  if (p.M < 1 || p.M > 16 || p.K % 128 || p.N % 4) { set_error("gemv: M=%d N=%d K=%d unsupported (the LDS-staged form holds one 16-row block; more rows take launch_gemv_frag)", p.M, p.N, p.K); return WIS_E_UNSUPPORTED; }
+  // largest K-chunk (multiple of 128 dividing K) whose f16 image of M rows fits 64 KiB of LDS (several workgroups per CU)
   int KC = p.K;
-  const size_t aux = (size_t)4 * MB * 64 * 16 + MAX_ROWS * 8 + 4 * 16 * 4 + 16;   // red + stats + sred (+ alignment)
-  while ((size_t)p.M * (KC + 8) * 2 + aux > lds_cap) {
+  const size_t aux = (size_t)4 * 64 * 16 + MAX_ROWS * 8 + 4 * 16 * 4 + 16;   // red + stats + sred (+ alignment)
+  while ((size_t)p.M * (KC + 8) * 2 + aux > 65536) {
     int next = 0;
     for (int c = KC - 128; c >= 128; c -= 128) if (p.K % c == 0) { next = c; break; }
     if (!next) { set_error("gemv: cannot chunk K=%d for M=%d", p.K, p.M); return WIS_E_UNSUPPORTED; }
@@ -808,76 +597,40 @@ int launch_gemv(hipStream_t st, const GemvP& p) {
   dim3 grid(npad / rows), block(256);
   int mode = 0;
   if (p.flags & GV_LN) {
-    // folded LayerNorm: raw fp32 rows in registers - at most 8 rows of at most 2048 columns; callers split larger row counts
-    // into layernorm_kernel (no affine) + the f16-activation path (model.hip: launch_ln_gemv)
+    // folded LayerNorm: raw fp32 rows in registers - at most 8 rows of at most 2048 columns (more rows take launch_gemv_frag)
     if (p.M > 8 || p.K > 2048 || KC != p.K || !p.csum) { set_error("gemv: fused LayerNorm needs M <= 8, K <= 2048 and the folded column sums (M=%d K=%d)", p.M, p.K); return WIS_E_UNSUPPORTED; }
   }
-  if (p.flags & GV_LNP) {
-    if ((p.flags & GV_LN) || p.M > 16 || p.K > 1280 || p.K % 64 || KC != p.K || !p.csum || !p.stat_in || p.M * (p.K / 8) > 13 * 256) {
-      set_error("gemv: the LayerNorm fold from partials needs f16 rows, column sums, partials, M <= 16, K <= 1280 (M=%d K=%d)", p.M, p.K); return WIS_E_UNSUPPORTED; }
-  }
   if (p.flags & GV_LN16) {
-    if ((p.flags & (GV_LN | GV_LNP)) || p.M > 8 || p.K > 2048 || p.K % 8 || KC != p.K || !p.csum || MB != 1) {
+    if ((p.flags & GV_LN) || p.M > 8 || p.K > 2048 || p.K % 8 || KC != p.K || !p.csum) {
       set_error("gemv: the LayerNorm fold on f16 rows needs column sums, M <= 8, K <= 2048 (M=%d K=%d)", p.M, p.K); return WIS_E_UNSUPPORTED; }
   }
-  if (MB == 1) {
-    if (KC == p.K) {
-      if (p.flags & GV_LN) mode = 1;
-      else if (p.flags & GV_LN16) mode = 3;
-      else if (!(p.flags & GV_LN) && p.M * (p.K / 8) <= 13 * 256) mode = 2;
-    }
-  } else if (!(p.flags & GV_LN) && p.M * (KC / 8) <= 30 * 256) mode = 2;       // register-staged f16 chunks (single or multi chunk)
+  if (KC == p.K) {
+    if (p.flags & GV_LN) mode = 1;
+    else if (p.flags & GV_LN16) mode = 3;
+    else if (p.M * (p.K / 8) <= 13 * 256) mode = 2;
+  }
   const int sck = KC / 128;
-  const int sc = ((KC == p.K || mode == 2) && (sck == 3 || sck == 4 || sck == 6 || sck == 8 || sck == 10)) ? sck : 0;
-#define WIS_GV1(MBv, MODEv, SCv, RMv, W8v) do { \
-    if (lds > 65536) {      /* the attribute is per device and per instantiation: set once each, under the per-device state's lock */ \
-      static std::atomic<unsigned long long> big_ok{0};      /* bit = device */ \
-      if (!((big_ok.load(std::memory_order_acquire) >> (cur_dev & 63)) & 1ull)) { \
-        std::lock_guard<std::mutex> lk(g_gemv_dev_mu); \
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(&gemv_kernel<MBv, MODEv, SCv, RMv, W8v>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_cap) != hipSuccess) { \
-          set_error("gemv: cannot raise the dynamic LDS limit to %zu bytes", lds_cap); return WIS_E_HIP; } \
-        big_ok.fetch_or(1ull << (cur_dev & 63), std::memory_order_release); } } \
-    hipLaunchKernelGGL((gemv_kernel<MBv, MODEv, SCv, RMv, W8v>), grid, block, lds, st, WIS_GV_LEAD(pp), KC, pp); } while (0)
-#define WIS_GV(MBv, MODEv, SCv, RMv) do { if (p.wscale) WIS_GV1(MBv, MODEv, SCv, RMv, true); else WIS_GV1(MBv, MODEv, SCv, RMv, false); } while (0)
-#define WIS_GV_SC(MBv, MODEv, RMv) do { switch (sc) { case 3: WIS_GV(MBv, MODEv, 3, RMv); break; case 4: WIS_GV(MBv, MODEv, 4, RMv); break; case 6: WIS_GV(MBv, MODEv, 6, RMv); break; \
-                                                      case 8: WIS_GV(MBv, MODEv, 8, RMv); break; case 10: WIS_GV(MBv, MODEv, 10, RMv); break; default: WIS_GV(MBv, MODEv, 0, RMv); } } while (0)
-  // two n-tiles per workgroup (gemv_body NT = 2): the LayerNorm-folded projections of the one-utterance step at K = 1280, 4-5 rows, f16 weights;
-  // WIS_GV_NT2 bit 0 = N >= 4096 without the KV-cache epilogue (FFN1: 320 tiles on 256 CUs left a quarter of the CUs with two workgroups;
-  // 160 two-tile workgroups: decode step 1.268 -> 1.250 ms), bit 1 = the QKV projection (240 tiles had a CU each already: 120 fat
-  // workgroups measured SLOWER, 1.292 ms - off).  Default 1.
-  static const int nt2_mask = getenv("WIS_GV_NT2") ? atoi(getenv("WIS_GV_NT2")) : 1;
-  if (MB == 1 && mode == 1 && sc == 10 && p.M > 3 && p.M <= 5 && !p.wscale && rows == 16 && p.N % 32 == 0 && !(p.flags & GV_RESID) &&
-      (((nt2_mask & 1) && !(p.flags & GV_QKV) && p.N >= 4096) || ((nt2_mask & 2) && (p.flags & GV_QKV)))) {
+  const int sc = (KC == p.K && (sck == 3 || sck == 4 || sck == 6 || sck == 8 || sck == 10)) ? sck : 0;
+#define WIS_GV1(MODEv, SCv, RMv, W8v) hipLaunchKernelGGL((gemv_kernel<1, MODEv, SCv, RMv, W8v>), grid, block, lds, st, WIS_GV_LEAD(pp), KC, pp)
+#define WIS_GV(MODEv, SCv, RMv) do { if (p.wscale) WIS_GV1(MODEv, SCv, RMv, true); else WIS_GV1(MODEv, SCv, RMv, false); } while (0)
+#define WIS_GV_SC(MODEv, RMv) do { switch (sc) { case 3: WIS_GV(MODEv, 3, RMv); break; case 4: WIS_GV(MODEv, 4, RMv); break; case 6: WIS_GV(MODEv, 6, RMv); break; \
+                                                 case 8: WIS_GV(MODEv, 8, RMv); break; case 10: WIS_GV(MODEv, 10, RMv); break; default: WIS_GV(MODEv, 0, RMv); } } while (0)
+  // two n-tiles per workgroup (gemv_body NT = 2): FFN1 of the one-utterance step (K = 1280, N >= 4096, 4-5 rows, f16 weights) - 320 tiles on 256 CUs left a
+  // quarter of the CUs with two workgroups; 160 two-tile workgroups: decode step 1.268 -> 1.250 ms.  Not the QKV projection: its 240 tiles had a CU each
+  // already, and 120 fat workgroups measured SLOWER (1.292 ms) - fatter workgroups pay only where they remove a second round.
+  if (mode == 1 && sc == 10 && p.M > 3 && p.M <= 5 && !p.wscale && rows == 16 && p.N % 32 == 0 && !(p.flags & (GV_RESID | GV_QKV)) && p.N >= 4096) {
     hipLaunchKernelGGL((gemv_kernel<1, 1, 20, 5, false, 2>), dim3(p.N / 32), block, lds, st, WIS_GV_LEAD(pp), KC, pp);
     return WIS_OK;
   }
-  if (p.sa_gran) {      // QKV projection + the heads' self-attention workgroups in one launch (sa_consume)
-    if (!(MB == 1 && mode == 1 && sc > 0 && !p.wscale && (p.flags & GV_QKV) && p.M <= 8 && p.d % 64 == 0 && p.N == 3 * p.d && p.sa_epoch && p.sa_flag && p.sa_out)) {
-      set_error("gemv: the fused self-attention needs the LayerNorm-folded f16 QKV projection of <= 8 rows (M=%d N=%d K=%d)", p.M, p.N, p.K); return WIS_E_UNSUPPORTED; }
-    pp.sa_first = (int)grid.x;
-    const dim3 gsa(grid.x + p.d / 64);
-    const size_t lds_sa = lds > 4 * 512 * 4 ? lds : 4 * 512 * 4;      // the consumer workgroups' exchange rows: 2 KiB per wave
-#define WIS_GV_SA(SCv, RMv) hipLaunchKernelGGL((gemv_kernel<1, 1, SCv, RMv, false, 1, true>), gsa, block, lds_sa, st, WIS_GV_LEAD(pp), KC, pp)
-#define WIS_GV_SA_RM(SCv) do { if (p.M <= 3) WIS_GV_SA(SCv, 3); else if (p.M <= 5) WIS_GV_SA(SCv, 5); else WIS_GV_SA(SCv, 8); } while (0)
-    switch (sc) { case 3: WIS_GV_SA_RM(3); break; case 4: WIS_GV_SA_RM(4); break; case 6: WIS_GV_SA_RM(6); break; case 8: WIS_GV_SA_RM(8); break; default: WIS_GV_SA_RM(10); }
-#undef WIS_GV_SA_RM
-#undef WIS_GV_SA
-    return WIS_OK;
-  }
-  if (MB == 1) {
-    if (mode == 1) { if (p.M <= 3) WIS_GV_SC(1, 1, 3); else if (p.M <= 5) WIS_GV_SC(1, 1, 5); else WIS_GV_SC(1, 1, 8); }
-    else if (mode == 3) { if (p.M <= 3) WIS_GV_SC(1, 3, 3); else if (p.M <= 5) WIS_GV_SC(1, 3, 5); else WIS_GV_SC(1, 3, 8); }
-    else if (mode == 2) {
-      // K = 4d of the one-utterance step (FFN2: 80 workgroups x 160 KiB of weights): EVERY fragment requested up front (40 per wave:
-      // 160 VGPRs, one workgroup per CU anyway) instead of a ring of 16 - the ring held 64 KiB in flight per CU, and 80 CUs x 64 KiB
-      // over the memory latency is what the stream ran at (WIS_FFN2_RING=1: the ring, for A/B)
-      static const bool ffn2_ring = getenv("WIS_FFN2_RING") && atoi(getenv("WIS_FFN2_RING")) != 0;
-      if (sck == 40 && KC == p.K && !p.wscale && !ffn2_ring) WIS_GV1(1, 2, 40, 1, false);
-      else WIS_GV_SC(1, 2, 1);
-    } else WIS_GV_SC(1, 0, 1);
-  }
-  else if (MB == 2) { if (mode == 2) WIS_GV_SC(2, 2, 1); else WIS_GV(2, 0, 0, 1); }
-  else { if (mode == 2) WIS_GV_SC(3, 2, 1); else WIS_GV(3, 0, 0, 1); }
+  if (mode == 1) { if (p.M <= 3) WIS_GV_SC(1, 3); else if (p.M <= 5) WIS_GV_SC(1, 5); else WIS_GV_SC(1, 8); }
+  else if (mode == 3) { if (p.M <= 3) WIS_GV_SC(3, 3); else if (p.M <= 5) WIS_GV_SC(3, 5); else WIS_GV_SC(3, 8); }
+  else if (mode == 2) {
+    // K = 4d of the one-utterance step (FFN2: 80 workgroups x 160 KiB of weights): EVERY fragment requested up front (40 per wave:
+    // 160 VGPRs, one workgroup per CU anyway) instead of a ring of 16 - the ring held 64 KiB in flight per CU, and 80 CUs x 64 KiB
+    // over the memory latency is what the stream ran at
+    if (sck == 40 && !p.wscale) WIS_GV1(2, 40, 1, false);
+    else WIS_GV_SC(2, 1);
+  } else WIS_GV_SC(0, 1);
 #undef WIS_GV_SC
 #undef WIS_GV
 #undef WIS_GV1
@@ -1460,37 +1213,8 @@ __global__ void dec_embed_kernel(const f16* __restrict__ emb, const f16* __restr
     if (xh) xh[(size_t)m * d + i] = (f16)v;          // f16 copy of the layer input (fused out-proj + cross-Q stage)
   }
 }
-// the same with the rows' LayerNorm partials (GV_LNP consumers): thread = one 16-column tile of row m
-__global__ void dec_embed_stat_kernel(const f16* __restrict__ emb, const f16* __restrict__ pos_emb, const int* __restrict__ tok,
-                                      const int* __restrict__ pos, float* __restrict__ x, f16* __restrict__ xh, float* __restrict__ stat, int d) {
-  const int m = blockIdx.x, t = threadIdx.x, nt = d >> 4;
-  if (t >= nt) return;
-  const f16x8* e = reinterpret_cast<const f16x8*>(emb + (size_t)tok[m] * d + 16 * t);
-  const f16x8* pe = reinterpret_cast<const f16x8*>(pos_emb + (size_t)pos[m] * d + 16 * t);
-  const f16x8 e0 = e[0], e1 = e[1], p0 = pe[0], p1 = pe[1];
-  float v[16];
-#pragma unroll
-  for (int i = 0; i < 8; ++i) { v[i] = (float)e0[i] + (float)p0[i]; v[8 + i] = (float)e1[i] + (float)p1[i]; }
-  float s1 = 0.f;
-#pragma unroll
-  for (int i = 0; i < 16; ++i) s1 += v[i];
-  const float ml = s1 * 0.0625f;
-  float s2 = 0.f;
-#pragma unroll
-  for (int i = 0; i < 16; ++i) { const float a = v[i] - ml; s2 += a * a; }
-  float4* xo = reinterpret_cast<float4*>(x + (size_t)m * d + 16 * t);
-#pragma unroll
-  for (int i = 0; i < 4; ++i) xo[i] = make_float4(v[4 * i], v[4 * i + 1], v[4 * i + 2], v[4 * i + 3]);
-  f16x8 h0, h1;
-#pragma unroll
-  for (int i = 0; i < 8; ++i) { h0[i] = (f16)v[i]; h1[i] = (f16)v[8 + i]; }
-  f16x8* ho = reinterpret_cast<f16x8*>(xh + (size_t)m * d + 16 * t);
-  ho[0] = h0; ho[1] = h1;
-  *reinterpret_cast<float2*>(stat + ((size_t)m * nt + t) * 2) = make_float2(s1, s2);
-}
-int launch_dec_embed(hipStream_t st, const f16* emb, const f16* pos_emb, const int* tok, const int* pos, float* x, int M, int d, f16* xh, float* stat) {
-  if (stat && xh && d % 16 == 0 && d / 16 <= 256) hipLaunchKernelGGL(dec_embed_stat_kernel, dim3(M), dim3(((d / 16 + 63) / 64) * 64), 0, st, emb, pos_emb, tok, pos, x, xh, stat, d);
-  else hipLaunchKernelGGL(dec_embed_kernel, dim3(M), dim3(256), 0, st, emb, pos_emb, tok, pos, x, xh, d);
+int launch_dec_embed(hipStream_t st, const f16* emb, const f16* pos_emb, const int* tok, const int* pos, float* x, int M, int d, f16* xh) {
+  hipLaunchKernelGGL(dec_embed_kernel, dim3(M), dim3(256), 0, st, emb, pos_emb, tok, pos, x, xh, d);
   return WIS_OK;
 }
 
@@ -2095,9 +1819,8 @@ __device__ __forceinline__ void st_gran2(gran_t* p, unsigned tag, float v0, floa
 // (Measured and not kept, round 6: the folded query finished ONCE per workgroup by the first V wave - which has nothing to ask for before the barrier - instead of by
 // every K wave for itself, 81 instead of 96 wave requests per workgroup: 1.222 / 1.219 vs 1.204 / 1.205 ms per step at one utterance - the K waves then wait for a
 // wave that started later - and 1.863 / 1.874 / 1.881 / 1.888 vs 1.880 / 1.885 / 1.883 / 1.886 at eight: nothing; sessions r6R / r6S.)
-// NKW = K waves = V waves per workgroup: 2 (256 threads, four workgroups per CU: the batched step's 960 workgroups in one round) or 4 (512 threads: the
-// one-utterance step's 120 workgroups have a CU each - twice the waves put the workgroup's 160 requests into the CU's address path in half the time, and
-// every K wave has half the scores and exponentials to take: its path - requests, query, scores, softmax - is the critical one there)
+// NKW = K waves = V waves per workgroup: 2 at every call site (256 threads, four workgroups per CU: the batched step's 960 workgroups in one round).  4 + 4 waves
+// for the one-utterance step's 120 workgroups measured 0.8 % slower per step: the CU's address path takes the same requests no faster from eight waves.
 // all-reduce over the four 16-lane rows of a lane column (lanes l, l + 16, l + 32, l + 48) with gfx950's row-swap moves: v_permlane32_swap exchanges the upper
 // half of its first operand with the lower half of its second (both = v: one register then holds the lower half's values twice, the other the upper half's),
 // v_permlane16_swap the odd rows of the first with the even rows of the second - two VALU moves instead of two ds_bpermute round trips through the LDS pipe
@@ -2443,20 +2166,17 @@ int launch_dec_cross_attn(hipStream_t st, const float* q, const f16* kx, const f
   static const int env_spin = getenv("WIS_CA_SPIN") ? atoi(getenv("WIS_CA_SPIN")) : 1;      // 0: always the ticket form (A/B switch)
   // granule hand-off: small grids only (fewer spinning combiners than CUs), the default 256-key chunking, <= 8 rows per utterance
   const bool spin = env_spin && gran && epoch && B * H <= CA_SPIN_MAX_BH && CL == 256 && used >= 2 && used <= 6 && R <= 8;
-  static const int lds_pad = getenv("WIS_CA_LDS_PAD") ? atoi(getenv("WIS_CA_LDS_PAD")) : 0;      // experiment: dynamic LDS nobody uses = fewer workgroups per CU
-  const int shm = (long)B * H * used > 512 ? lds_pad : 0;
-#define WIS_CA(TPWv, CMv, FOLDv, SPINv) hipLaunchKernelGGL((dec_cross_attn_kernel<TPWv, CMv, FOLDv, SPINv>), dim3(used, H, B), dim3(256), shm, st, q, kx, vt, xres, q2, epoch, \
+#define WIS_CA(TPWv, CMv, FOLDv, SPINv) hipLaunchKernelGGL((dec_cross_attn_kernel<TPWv, CMv, FOLDv, SPINv>), dim3(used, H, B), dim3(256), 0, st, q, kx, vt, xres, q2, epoch, \
                                                   (R | (H << 8) | (CL << 14) | (used << 24)), (d | (T << 16)), (Tpad | (kv_shared ? (1 << 30) : 0)), out, part, counters, prof, out_mb, qcs, qb, gran)
   if (xres_is_stat) {
     const bool small = (long)B * H * used <= 256;      // at most one workgroup per CU: V is requested up front (FOLD 3)
     // the role-split kernel (K waves / V waves): WIS_CA_RS=0 off (A/B switch), 1 the batched step's grids only, 2 (default) the one-utterance step's too
     static const int ca_rs = getenv("WIS_CA_RS") ? atoi(getenv("WIS_CA_RS")) : 2;
     if (ca_rs && (!small || ca_rs >= 2) && CL == 256 && used <= 6 && R <= 8 && d <= 1280) {
-#define WIS_CA_RS(SPINv, NTv, NKWv) hipLaunchKernelGGL((dec_cross_attn_rs_kernel<SPINv, NTv, NKWv>), dim3(used, H, B), dim3(128 * NKWv), 0, st, q, kx, vt, xres, q2, epoch, \
+#define WIS_CA_RS(SPINv, NTv) hipLaunchKernelGGL((dec_cross_attn_rs_kernel<SPINv, NTv, 2>), dim3(used, H, B), dim3(256), 0, st, q, kx, vt, xres, q2, epoch, \
                                                         (R | (H << 8) | (CL << 14) | (used << 24)), (d | (T << 16)), (Tpad | (kv_shared ? (1 << 30) : 0)), out, part, counters, prof, out_mb, qcs, qb, gran)
-      static const bool rs8 = getenv("WIS_CA_RS8") && atoi(getenv("WIS_CA_RS8")) != 0;      // small grids with 4 + 4 waves per workgroup: measured 0.8 % SLOWER per step than 2 + 2 (session r6G); A/B switch, off
-      if (spin) { if (small && rs8) WIS_CA_RS(true, true, 4); else if (small) WIS_CA_RS(true, true, 2); else WIS_CA_RS(true, false, 2); }
-      else { if (small && rs8) WIS_CA_RS(false, true, 4); else if (small) WIS_CA_RS(false, true, 2); else WIS_CA_RS(false, false, 2); }
+      if (spin) { if (small) WIS_CA_RS(true, true); else WIS_CA_RS(true, false); }
+      else { if (small) WIS_CA_RS(false, true); else WIS_CA_RS(false, false); }
 #undef WIS_CA_RS
       return WIS_OK;
     }

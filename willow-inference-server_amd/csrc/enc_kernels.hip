@@ -646,8 +646,9 @@ __global__ __launch_bounds__(512) void gemm_8p_kernel(WIS_GP_DECL(g_), Epi epi) 
 // the two wave rows, same swizzle, same permuted weight rows / 16-byte stores.  Per k-tile the fragment reads (16 ds_read_b128 per
 // wave = 1024 LDS cycles per CU) equal the MFMA time (32 MFMAs x 16 cycles x 2 waves per SIMD): the tile is at the LDS-bandwidth
 // balance point, which is why the batched encoder keeps the 256 x 256 tile (1536 LDS vs 2048 MFMA cycles).
-// Functors with a transposed part (the V images) run both column sets in ONE launch: workgroups >= tiles_a take `pb` and the swapped
-// MFMA operand order (a wave-uniform branch; with 64 accumulator registers both MFMA clusters fit without spills).
+// Functors with a transposed part (the V images) would run both column sets in ONE launch: workgroups >= tiles_a take `pb` and the swapped
+// MFMA operand order.  launch_gemm_8pn no longer instantiates the kernel for them (measured slower than the ping-pong tile), so `tr` is false at compile time;
+// its arms stay in the source because deleting them rescheduled the three plain instantiations (one instruction fewer), and this kernel is kept instruction for instruction.
 template <class Epi>
 __global__ __launch_bounds__(512) void gemm_8pn_kernel(GemmP pa, GemmP pb, int tiles_a, Epi epi) {
   constexpr int BM_ = 128, BN_ = 256, HALF = 128 * 64, BUF = 3 * HALF, RING = 3 * BUF;
@@ -655,7 +656,7 @@ __global__ __launch_bounds__(512) void gemm_8pn_kernel(GemmP pa, GemmP pb, int t
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wr = wave >> 2, wc = wave & 3, l15 = lane & 15, kq = lane >> 4;
-  const bool tr = Epi::HAS_T && (int)blockIdx.x >= tiles_a;
+  const bool tr = Epi::HAS_T && (int)blockIdx.x >= tiles_a;      // false at compile time: no functor with HAS_T is instantiated; every `tr` arm below, `pb` and `tiles_a` are dead (kept: see above)
   const GemmP& p = tr ? pb : pa;
   const int nmt = (p.M + BM_ - 1) / BM_, nwg = nmt * (p.N / BN_);
   const int kbeg = p.klen > 0 ? (int)blockIdx.z * p.klen : 0;
@@ -836,20 +837,15 @@ template <class Epi>
 static int launch_gemm_8pn(hipStream_t st, const GemmP& p, const Epi& epi) {
   static const bool use = !(getenv("WIS_GEMM_8PN") && atoi(getenv("WIS_GEMM_8PN")) == 0);
   const int splits = p.klen > 0 ? p.K / p.klen : 1;
-  static const bool use_t = getenv("WIS_GEMM_8PN_T") && atoi(getenv("WIS_GEMM_8PN_T")) != 0;      // functors with a transposed part: measured slower than the ping-pong tile (QKV 33.9 vs 29.8 us)
-  if (Epi::HAS_T && !use_t) return 1;
-  if (!use || p.N % 256 || (p.klen > 0 ? p.klen : p.K) / BK < 2 || p.M < 128) return 1;
-  const int tiles = cdiv(p.M, 128) * (p.N / 256) * splits;
-  if (tiles < 120 || tiles > 512) return 1;
-  GemmP a = p, b = p;
-  int tiles_a = cdiv(p.M, 128) * (p.N / 256);
-  if constexpr (Epi::HAS_T) {
-    epi.split(p.N, &a, &b);
-    if (a.N % 256 || b.N % 256 || a.n_span % 256 || b.n_span % 256) return 1;
-    tiles_a = cdiv(p.M, 128) * (a.N / 256);
+  if constexpr (Epi::HAS_T) {      // functors with a transposed part: measured slower than the ping-pong tile (QKV 33.9 vs 29.8 us); not instantiated
+    return 1;
+  } else {
+    if (!use || p.N % 256 || (p.klen > 0 ? p.klen : p.K) / BK < 2 || p.M < 128) return 1;
+    const int tiles = cdiv(p.M, 128) * (p.N / 256) * splits;
+    if (tiles < 120 || tiles > 512) return 1;
+    hipLaunchKernelGGL((gemm_8pn_kernel<Epi>), dim3(tiles / splits, 1, splits), dim3(512), 0, st, p, p, tiles / splits, epi);
+    return WIS_OK;
   }
-  hipLaunchKernelGGL((gemm_8pn_kernel<Epi>), dim3(cdiv(p.M, 128) * (p.N / 256), 1, splits), dim3(512), 0, st, a, b, tiles_a, epi);
-  return WIS_OK;
 }
 
 template <class Epi>

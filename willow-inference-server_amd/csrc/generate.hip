@@ -382,7 +382,7 @@ struct StepGraph {
     wis_model* m = g.m; const SampleCfg& sc = g.sc;
     GraphKey key; memset(&key, 0, sizeof(key));
     key.B = g.B; key.beam = g.beam; key.P = g.P; key.max_new = g.max_new; key.fixed_new = sc.fixed_new; key.suppress_blank = sc.suppress_blank;
-    key.suppress_default = g.o->suppress_default; key.early_exit = sc.allow_early_exit; key.lp = sc.length_penalty; key.patience = g.patience; key.spin = (m->spin_now ? 1 : 0) | (sa_fuse_enabled() ? 2 : 0);
+    key.suppress_default = g.o->suppress_default; key.early_exit = sc.allow_early_exit; key.lp = sc.length_penalty; key.patience = g.patience; key.spin = m->spin_now ? 1 : 0;
     key.sa_nb = nb;
     key.timestamps = g.ts ? 1 : 0; key.max_init = g.ts ? g.ts_max_init : 0;
     auto it = m->graphs.find(key);

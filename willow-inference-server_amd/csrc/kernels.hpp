@@ -52,12 +52,11 @@ struct RowMeta {
 };
 
 // skinny GEMM (decoder): y = epi(LN?(x) . Wp^T + b), Wp packed in MFMA 16x16x32 A-fragment order
-enum { GV_GELU = 1, GV_RESID = 2, GV_OUT_F32 = 4, GV_LN = 8, GV_QKV = 16,
-       GV_LNP = 32,
-       GV_LN16 = 64 };     // LayerNorm-folded projection on f16 rows, statistics taken from those rows in the kernel (<= 8 rows)      // LayerNorm-folded projection on f16 rows whose statistics arrive as per-16-column (sum, M2) partials in stat_in (<= 16 rows)
+enum { GV_GELU = 1, GV_RESID = 2, GV_OUT_F32 = 4, GV_LN = 8, GV_QKV = 16,      // (32 is free: wis_op_gemv's tap uses it for "quantise to 8 bits first")
+       GV_LN16 = 64 };     // LayerNorm-folded projection on f16 rows, statistics taken from those rows in the kernel (<= 8 rows)
 struct GemvP {
   const void* x;                 // f32 [M][K] (raw, un-normalised) when GV_LN else f16 [M][K]
-  const float* gamma; const float* beta;   // only used by the split path (model.hip launch_ln_gemv); the kernel never reads them
+  const float* gamma; const float* beta;   // unused (the affine part lives in the folded weights / bias); kept: removing them moves every later member, and the gemv kernels are kept instruction for instruction
   const float* csum;             // GV_LN: column sums of the gamma-folded weights (see fold_ln_kernel); bias then is b + W.beta
   const f16* Wp; const float* bias;
   const float* wscale;           // non-null: Wp is the 8-bit packed image, one dequantisation scale per output row
@@ -84,14 +83,10 @@ struct GemvP {
   // the weight matrix as a k-step window of a wider packed image (launch_gemv_frag / launch_gemv_frag3): wks = k-steps per n-tile of
   // the image (0: K / 32, the matrix is the whole image), wk0 = first k-step of the window
   int wks, wk0;
-  // self-attention fused into the QKV projection's launch (launch_gemv, GV_QKV at <= 8 decode rows; dec_kernels.hip sa_consume): sa_gran = 8-byte
-  // {tag, value} slots [heads][8 rows][q | k | v][64], sa_epoch = one monotonic epoch word per head, sa_flag = the give-up flag word (the cross-
-  // attention hand-off's), sa_out = attention output f16 [M][d]; slot of row m = (m / sa_rpu) * sa_sstride + m % sa_rpu; sa_first is set by the launcher
-  unsigned long long* sa_gran; unsigned* sa_epoch; unsigned* sa_flag; f16* sa_out; int sa_rpu, sa_sstride, sa_first;
 };
 int launch_gemv(hipStream_t st, const GemvP& p);
-// two f16-activation skinny GEMMs in one launch (+ optionally L2 prefetch riders for the cross-attention that follows: pf_k / pf_v = its K / V^T of utterance 0)
-int launch_gemv_dual(hipStream_t st, const GemvP& pa, const GemvP& pb, const f16* pf_k = nullptr, const f16* pf_v = nullptr, int pf_T = 0, int pf_Tpad = 0, int pf_chunks = 0, int pf_H = 0);
+// two f16-activation skinny GEMMs in one launch
+int launch_gemv_dual(hipStream_t st, const GemvP& pa, const GemvP& pb);
 // Batched decode rows (8 < M <= 96).  The skinny GEMM reads its activations as ready-made MFMA B fragments straight from L2
 // (written in that order by the producing kernel: no per-workgroup LDS staging, no staging barrier, many workgroups per CU), and
 // the pre-LN LayerNorm needs no launch of its own: every residual epilogue leaves per-16-column partial sums of the rows it
@@ -115,7 +110,7 @@ int launch_pack_gemv8(hipStream_t st, const f16* W, unsigned char* Wp, float* sc
 int launch_pack_gemv(hipStream_t st, const f16* W, f16* Wp, int N, int Npad, int K, int n_scale, float scale, int rows = 16);
 int gemv_rows_for(int N, int K);     // tile height used for an [N][K] decoder matrix
 
-int launch_dec_embed(hipStream_t st, const f16* emb, const f16* pos_emb, const int* tok, const int* pos, float* x, int M, int d, f16* xh = nullptr, float* stat = nullptr);
+int launch_dec_embed(hipStream_t st, const f16* emb, const f16* pos_emb, const int* tok, const int* pos, float* x, int M, int d, f16* xh = nullptr);
 // logical slot of row m = (m / rpu) * sstride + (m % rpu) * rmul
 // out_mb: 0 = out is row-major f16 [M][d]; > 0 = fragment image with that many 16-row blocks (batched decode)
 // anc (optional; draft verification at beam > 1, model.hip verify_beam_draft): the rows of a pass are the nodes of a beam TREE - row m reads

@@ -209,7 +209,6 @@ struct wis_model {
   int sa_nb = 8;      // 8-position blocks the step's self-attention asks for per pass (generate.hip StepGraph: by the step index; 8 outside the step loops)
   float* gf_part = nullptr; unsigned* gf_cnt = nullptr; int gf_ksplit = 1;      // K split of the batched FFN2 skinny GEMM: slice sums, tickets (GemvP::ksplit)
   unsigned long long* ca_gran = nullptr; unsigned* ca_epoch = nullptr;      // granule hand-off of the decoder cross-attention (small grids): slots, flag + epochs
-  unsigned long long* sa_gran = nullptr; unsigned* sa_epoch = nullptr;      // ... of q / k / v from the QKV projection to the self-attention fused into its launch: slots [H][8][3][64], epochs [H]
   bool spin_off = false;        // sticky: a combiner's bounded spin ran out once on this handle - it keeps to the ticket hand-off from then on
   int handoff_retries = 0;      // calls repeated because a combiner's spin ran out (wis_debug_handoff: expected to stay 0)
   bool spin_now = true;         // this call's decision (SpinClaim): dec_forward passes the granule buffers only when set
@@ -560,10 +559,6 @@ int alloc_buffers(wis_model* m) {
     WIS_RET(dalloc(m, &m->ca_epoch, (size_t)bh + 1));
     WIS_HIP_CHECK(hipMemsetAsync(m->ca_gran, 0, (size_t)bh * 6 * 8 * 66 * 8, m->st));
     WIS_HIP_CHECK(hipMemsetAsync(m->ca_epoch, 0, ((size_t)bh + 1) * 4, m->st));
-    WIS_RET(dalloc(m, &m->sa_gran, (size_t)H * 8 * 3 * 64));
-    WIS_RET(dalloc(m, &m->sa_epoch, (size_t)H));
-    WIS_HIP_CHECK(hipMemsetAsync(m->sa_gran, 0, (size_t)H * 8 * 3 * 64 * 8, m->st));
-    WIS_HIP_CHECK(hipMemsetAsync(m->sa_epoch, 0, (size_t)H * 4, m->st));
   }
   WIS_RET(dalloc(m, &m->rm.tok, MAX_ROWS)); WIS_RET(dalloc(m, &m->rm.pos, MAX_ROWS));
   WIS_RET(dalloc(m, &m->rm.slot, MAX_ROWS)); WIS_RET(dalloc(m, &m->rm.lslot, MAX_ROWS));
@@ -680,17 +675,6 @@ int run_cross_kv(wis_model* m, int B) {
   // every decoder layer's K/V projection of the encoder memory in one GEMM (weights, biases and outputs are single blocks)
   return launch_gemm_crosskv(m->st, gemm_plain(m->mem, d, m->w_ckv_all, B * T, c.n_dec_layers * 2 * d, d), m->b_ckv_all, m->kx_all, m->vx_all, d, T, m->Tpad,
                              c.n_heads, (int64_t)m->kx_lstride, (int64_t)m->vx_lstride);
-}
-
-// LayerNorm + skinny GEMM.  Up to 8 rows the LayerNorm is fused into the GEMM prologue (register resident); with more rows
-// (batched decode: B*beam up to 48) every workgroup re-normalising all rows costs more than one extra launch, so the rows are
-// normalised once by layernorm_kernel into an f16 buffer and the GEMM takes its f16-activation path.
-static int launch_ln_gemv(wis_model* m, hipStream_t st, GemvP g) {
-  if (g.M > 8 && (g.flags & GV_LN)) {   // plain normalisation (the affine part lives in the folded weights / bias), then f16 activations
-    WIS_RET(launch_layernorm(st, reinterpret_cast<const float*>(g.x), nullptr, nullptr, m->dln, g.M, g.K));
-    g.x = m->dln; g.csum = nullptr; g.flags &= ~GV_LN;
-  }
-  return launch_gemv(st, g);
 }
 
 // ---- granule hand-off of the cross-attention: when it may be used -------------------------------
@@ -847,40 +831,31 @@ static int dec_forward_frag(wis_model* m, int M, int R, int B, bool want_logits,
   return WIS_OK;
 }
 
-// WIS_SA_FUSE=1: the step's self-attention rides in the QKV projection's launch (dec_kernels.hip sa_consume).  OFF by default - built, correct (the GPU
-// suite is green with it) and measured SLOWER, same call on MI355X: decode step 1.280 against 1.250 ms, utterance 27.38 against 26.97 ms
-// (profiles/r06_sa_fuse_ab.txt).  The eager trace shows why: the fused launch averages 9.0 us where the two launches take 6.2 + 5.0, but its FLOOR
-// is 7.9 us against 3.3 + 2.3: behind the last projection tile the consumer still needs granule store -> L2 -> poll (~2 us) and the whole softmax,
-// which costs what the 1.6 us boundary + the stand-alone kernel's start cost once the graph replays them back to back - the same lesson as the
-// persistent skeleton and the flag-gated early start: an in-launch hand-off is two fabric round trips, like a kernel boundary.
-// Read per call so that a test can compare both forms in one process.
-static bool sa_fuse_enabled() { const char* e = getenv("WIS_SA_FUSE"); return e && atoi(e) != 0; }
+// The step of <= 8 rows: LDS-staged skinny GEMMs (launch_gemv) with the LayerNorm folded into their prologue; more rows and tree windows take
+// dec_forward_frag.  One launch per stage: running the self-attention inside the QKV projection's launch (granule hand-off) was built, bit-identical and
+// slower (1.280 against 1.250 ms per step) - an in-launch hand-off is two fabric round trips, like a kernel boundary (retired experiments).
 int dec_forward(wis_model* m, int M, int R, int B, bool want_logits, int sstride, int rmul, const TreeWin* tw = nullptr) {
   const wis_config_t& c = m->cfg; hipStream_t st = m->st;
   const int d = c.d_model, H = c.n_heads, T = c.n_audio_ctx, ctx = c.n_text_ctx;
   static const int env_chunks = getenv("WIS_CROSS_CHUNKS") ? atoi(getenv("WIS_CROSS_CHUNKS")) : 0;
   // 256-key chunks (6 per utterance-head): measured faster than 128-key chunks at every batch size (fewer partials to publish and combine)
   const int chunks = env_chunks ? env_chunks : 6;
-  static const bool no_frag = getenv("WIS_NO_FRAG") != nullptr;      // A/B switch: the round-1 batched path (LayerNorm launches + LDS-staged rows)
   if (tw) return dec_forward_frag(m, M, R, B, want_logits, sstride, rmul, chunks, tw);
-  if (M > 8 && !no_frag) return dec_forward_frag(m, M, R, B, want_logits, sstride, rmul, chunks);
-  if (m->al.capture) { set_error("wis_align needs the batched-row decoder route (more than 8 rows per pass, WIS_NO_FRAG unset)"); return WIS_E_STATE; }
-  // fused out-proj + cross-Q stage (load_weights: cq_fold): f16 decoder weights, <= 8 rows (the LayerNorm-fused row counts)
-  const bool fold = m->cq_fold && M <= 8;
-  // (r5) what the LayerNorm-folded projections (QKV, FFN1, the vocabulary) read - WIS_B1_LN = rows | f16 | partials:
+  if (M > 8) return dec_forward_frag(m, M, R, B, want_logits, sstride, rmul, chunks);
+  if (m->al.capture) { set_error("wis_align needs the batched-row decoder route (more than 8 rows per pass)"); return WIS_E_STATE; }
+  // fused out-proj + cross-Q stage (load_weights: cq_fold): f16 decoder weights
+  const bool fold = m->cq_fold;
+  // (r5) what the LayerNorm-folded projections (QKV, FFN1, the vocabulary) read - WIS_B1_LN = rows | f16:
   //   rows      (default) the fp32 rows (25.6 KB per workgroup at five rows), statistics in all four waves behind the weight stream: rounds 2-5
   //   f16       (off: the statistics of rounded rows cost parity at large-v2) the f16 copy of the rows (GV_LN16: 12.8 KB) that whoever produces residual rows leaves next to them (embedding, cross-
   //             attention output projection, FFN2), statistics from those same values, still in all four waves - a third of a launch's
   //             requests through the CU's address path gone, nothing added to its tail
-  //   partials  f16 rows + per-16-column (sum, M2) pairs from the producers' epilogues (GV_LNP): fewer requests still, but the merge sits in
-  //             the one epilogue wave BEHIND the reduction barrier - measured slower than `rows` (1.357 against 1.345 ms per step)
-  static const int ln_form = [] { const char* e = getenv("WIS_B1_LN"); return !e ? 0 : (!strcmp(e, "f16") ? 2 : (!strcmp(e, "partials") ? 1 : 0)); }();
+  //   (statistics from per-16-column partials of the producers' epilogues instead measured slower, 1.357 against 1.345 ms per step: the merge sits in the
+  //   one epilogue wave BEHIND the reduction barrier)
+  static const bool ln_f16 = [] { const char* e = getenv("WIS_B1_LN"); return e && !strcmp(e, "f16"); }();
   const bool ln_ok = fold && d % 64 == 0 && M * (d / 8) <= 13 * 256;
-  // (r6) the self-attention inside the QKV projection's launch (dec_kernels.hip sa_consume): decode rows that own their KV slot, f16 weights, the
-  // granule hand-off allowed for this call (it shares the cross-attention's budget and give-up protocol); WIS_SA_FUSE=0: two launches (A/B)
-  const bool sa_fuse = m->spin_now && sa_fuse_enabled() && rmul == 1 && M <= 8 && !m->w8 && d % 64 == 0 && ctx >= 64 && !m->prof_on;
-  const bool lnp = ln_ok && ln_form == 1 && d <= 1280, ln16 = ln_ok && ln_form == 2 && d <= 2048;
-  WIS_RET(launch_dec_embed(st, m->emb, m->dec_pos, m->rm.tok, m->rm.pos, m->dx, M, d, fold ? m->dxh : nullptr, lnp ? m->dstat : nullptr));
+  const bool ln16 = ln_ok && ln_f16 && d <= 2048;
+  WIS_RET(launch_dec_embed(st, m->emb, m->dec_pos, m->rm.tok, m->rm.pos, m->dx, M, d, fold ? m->dxh : nullptr));
   for (int l = 0; l < c.n_dec_layers; ++l) {
     const DecLayerW& w = m->dec[l];
     // stamp rows of this layer's 8 kernels: QKV, self-attn, out, cross-Q, cross-attn, cross-out, FFN1, FFN2
@@ -890,72 +865,59 @@ int dec_forward(wis_model* m, int M, int R, int B, bool want_logits, int sstride
     g.x = m->dx; g.csum = w.c_qkv; g.Wp = w.p_qkv; g.wscale = w.s_qkv; g.bias = w.b_qkv; g.M = M; g.N = 3 * d; g.K = d;
     g.flags = GV_LN | GV_QKV; g.q = m->dq; g.kc = m->kc[l]; g.vc = m->vc[l]; g.slot = m->rm.slot; g.pos = m->rm.pos; g.d = d; g.ctx = ctx;
     g.prof = pr;
-    if (lnp) { g.x = m->dxh; g.stat_in = m->dstat; g.flags = GV_LNP | GV_QKV; }
     if (ln16) { g.x = m->dxh; g.flags = GV_LN16 | GV_QKV; }
     g.rows = gemv_rows_for(g.N == m->n_vocab_pad ? m->cfg.n_vocab : g.N, g.K);
-    if (sa_fuse && !lnp && !ln16) { g.sa_gran = m->sa_gran; g.sa_epoch = m->sa_epoch; g.sa_flag = m->ca_epoch; g.sa_out = m->dao; g.sa_rpu = R; g.sa_sstride = sstride; }
-    WIS_RET(launch_ln_gemv(m, st, g));
-    if (!g.sa_gran) WIS_RET(launch_dec_self_attn(st, m->dq, m->kc[l], m->vc[l], m->rm.pos, m->dao, M, H, d, ctx, R, sstride, rmul, pr ? pr + 16 : nullptr, 0, nullptr, 0, 0, nullptr, m->sa_nb));
+    WIS_RET(launch_gemv(st, g));
+    WIS_RET(launch_dec_self_attn(st, m->dq, m->kc[l], m->vc[l], m->rm.pos, m->dao, M, H, d, ctx, R, sstride, rmul, pr ? pr + 16 : nullptr, 0, nullptr, 0, 0, nullptr, m->sa_nb));
     if (fold) {
       // ONE launch: x1 = x0 + Wo a + bo (tiles [0, d/16)) and q_raw = W'q x0 + (W'q Wo) a + W'q bo (the other d/16 tiles); the
       // cross-attention kernel applies the LayerNorm statistics of x1 (rs, mu) and b' to q_raw
       GemvP ga; memset(&ga, 0, sizeof(ga));
       ga.x = m->dao; ga.Wp = w.p_out; ga.bias = w.b_out; ga.y = m->dx; ga.M = M; ga.N = d; ga.K = d; ga.flags = GV_RESID; ga.prof = pr ? pr + 32 : nullptr;
       // (r5) the out-projection leaves LayerNorm partials of x1 (80 pairs per row); the cross-attention's prologue merges them instead of
-      // every one of its 120 workgroups re-reading and re-summing the five 1280-float rows (WIS_B1_STAT_ROWS=1: the round-2..4 form, A/B)
-      static const bool stat_rows = getenv("WIS_B1_STAT_ROWS") != nullptr;
-      if (!stat_rows) ga.stat_out = m->dstat;
+      // every one of its 120 workgroups re-reading and re-summing the five 1280-float rows (decode step 1.352 -> 1.330 ms)
+      ga.stat_out = m->dstat;
       GemvP gb; memset(&gb, 0, sizeof(gb));
       gb.x = m->dxh; gb.x2 = m->dao; gb.xsplit = d; gb.Wp = w.p_cqo; gb.bias = w.b_cqo; gb.y = m->dq; gb.M = M; gb.N = d; gb.K = 2 * d; gb.flags = GV_OUT_F32;
-      static const bool ca_pf = getenv("WIS_CA_PREFETCH") && atoi(getenv("WIS_CA_PREFETCH")) != 0;      // (r6 A/B: L2 prefetch riders for the cross-attention's K / V)
-      if (ca_pf && B == 1) WIS_RET(launch_gemv_dual(st, ga, gb, m->kx[l], m->vx[l], T, m->Tpad, chunks, H));
-      else
       WIS_RET(launch_gemv_dual(st, ga, gb));
-      if (!stat_rows) WIS_RET(launch_dec_cross_attn(st, m->dq, m->kx[l], m->vx[l], m->dao, m->part, m->counters, B, R, H, d, T, m->Tpad, chunks, pr ? pr + 64 : nullptr, 0,
-                                                    m->dstat, w.c_cq, w.b_cq, m->spin_now ? m->ca_gran : nullptr, m->ca_epoch, nullptr, 1));
-      else
       WIS_RET(launch_dec_cross_attn(st, m->dq, m->kx[l], m->vx[l], m->dao, m->part, m->counters, B, R, H, d, T, m->Tpad, chunks, pr ? pr + 64 : nullptr, 0,
-                                    m->dx, w.c_cq, w.b_cq, m->spin_now ? m->ca_gran : nullptr, m->ca_epoch));
+                                    m->dstat, w.c_cq, w.b_cq, m->spin_now ? m->ca_gran : nullptr, m->ca_epoch, nullptr, 1));
     } else {
     memset(&g, 0, sizeof(g));
     g.x = m->dao; g.Wp = w.p_out; g.wscale = w.s_out; g.bias = w.b_out; g.y = m->dx; g.M = M; g.N = d; g.K = d; g.flags = GV_RESID; g.prof = pr ? pr + 32 : nullptr;
     g.rows = gemv_rows_for(g.N == m->n_vocab_pad ? m->cfg.n_vocab : g.N, g.K);
-    WIS_RET(launch_ln_gemv(m, st, g));
+    WIS_RET(launch_gemv(st, g));
     // cross-attention block
     memset(&g, 0, sizeof(g));
     g.x = m->dx; g.csum = w.c_cq; g.Wp = w.p_cq; g.wscale = w.s_cq; g.bias = w.b_cq; g.y = m->dq; g.M = M; g.N = d; g.K = d; g.flags = GV_LN | GV_OUT_F32; g.prof = pr ? pr + 48 : nullptr;
     g.rows = gemv_rows_for(g.N == m->n_vocab_pad ? m->cfg.n_vocab : g.N, g.K);
-    WIS_RET(launch_ln_gemv(m, st, g));
+    WIS_RET(launch_gemv(st, g));
     WIS_RET(launch_dec_cross_attn(st, m->dq, m->kx[l], m->vx[l], m->dao, m->part, m->counters, B, R, H, d, T, m->Tpad, chunks, pr ? pr + 64 : nullptr, 0, nullptr, nullptr, nullptr,
                                   m->spin_now ? m->ca_gran : nullptr, m->ca_epoch));
     }
     memset(&g, 0, sizeof(g));
     g.x = m->dao; g.Wp = w.p_cout; g.wscale = w.s_cout; g.bias = w.b_cout; g.y = m->dx; g.M = M; g.N = d; g.K = d; g.flags = GV_RESID; g.prof = pr ? pr + 80 : nullptr;
-    if (lnp) { g.y16 = m->dln; g.stat_out = m->dstat; }      // FFN1's input: f16 rows (dln is free at <= 8 rows) + partials
-    if (ln16) g.y16 = m->dln;
+    if (ln16) g.y16 = m->dln;      // FFN1's input: f16 rows
     g.rows = gemv_rows_for(g.N == m->n_vocab_pad ? m->cfg.n_vocab : g.N, g.K);
-    WIS_RET(launch_ln_gemv(m, st, g));
+    WIS_RET(launch_gemv(st, g));
     // FFN
     memset(&g, 0, sizeof(g));
     g.x = m->dx; g.csum = w.c_f1; g.Wp = w.p_f1; g.wscale = w.s_f1; g.bias = w.b_f1; g.y = m->dh; g.M = M; g.N = 4 * d; g.K = d; g.flags = GV_LN | GV_GELU; g.prof = pr ? pr + 96 : nullptr;
-    if (lnp) { g.x = m->dln; g.stat_in = m->dstat; g.flags = GV_LNP | GV_GELU; }
     if (ln16) { g.x = m->dln; g.flags = GV_LN16 | GV_GELU; }
     g.rows = gemv_rows_for(g.N == m->n_vocab_pad ? m->cfg.n_vocab : g.N, g.K);
-    WIS_RET(launch_ln_gemv(m, st, g));
+    WIS_RET(launch_gemv(st, g));
     memset(&g, 0, sizeof(g));
     g.x = m->dh; g.Wp = w.p_f2; g.wscale = w.s_f2; g.bias = w.b_f2; g.y = m->dx; g.M = M; g.N = d; g.K = 4 * d; g.flags = GV_RESID; g.prof = pr ? pr + 112 : nullptr;
     g.y16 = fold ? m->dxh : nullptr;             // the next layer's x0 in f16
-    if (lnp) g.stat_out = m->dstat;              // ... and its LayerNorm partials (next layer's QKV / the vocabulary projection)
     g.rows = gemv_rows_for(g.N == m->n_vocab_pad ? m->cfg.n_vocab : g.N, g.K);
-    WIS_RET(launch_ln_gemv(m, st, g));
+    WIS_RET(launch_gemv(st, g));
   }
   if (want_logits) {
     GemvP g; memset(&g, 0, sizeof(g));
     g.x = m->dx; g.csum = m->c_proj; g.bias = m->b_proj; g.Wp = m->p_proj; g.wscale = m->s_proj; g.y = m->logits; g.M = M; g.N = m->n_vocab_pad; g.K = d; g.flags = GV_LN | GV_OUT_F32;
-    if (lnp) { g.x = m->dxh; g.stat_in = m->dstat; g.flags = GV_LNP | GV_OUT_F32; }
     if (ln16) { g.x = m->dxh; g.flags = GV_LN16 | GV_OUT_F32; }
     g.rows = gemv_rows_for(g.N == m->n_vocab_pad ? m->cfg.n_vocab : g.N, g.K);
-    WIS_RET(launch_ln_gemv(m, st, g));
+    WIS_RET(launch_gemv(st, g));
   }
   return WIS_OK;
 }
@@ -1489,12 +1451,10 @@ int wis_bench_weight_stream(wis_model_t* m, int M, int passes, float* total_ms, 
   WIS_HIP_CHECK(hipSetDevice(m->device));
   const int d = m->cfg.d_model; hipStream_t st = m->st;
   int launches = 0; double bytes = 0;
-  static const bool no_frag = getenv("WIS_NO_FRAG") != nullptr;
-  const bool frag = M > 8 && !no_frag;          // the route dec_forward takes at this row count
+  const bool frag = M > 8;          // the route dec_forward takes at this row count
   const int MBf = cdiv(M, 16);
-  static const int ln_form = [] { const char* e = getenv("WIS_B1_LN"); return !e ? 0 : (!strcmp(e, "f16") ? 2 : (!strcmp(e, "partials") ? 1 : 0)); }();
-  const bool ln_ok = !frag && M <= 8 && m->cq_fold && d % 64 == 0 && M * (d / 8) <= 13 * 256;      // dec_forward's choice at this row count
-  const bool lnp = ln_ok && ln_form == 1 && d <= 1280, ln16 = ln_ok && ln_form == 2 && d <= 2048;
+  static const bool ln_f16 = [] { const char* e = getenv("WIS_B1_LN"); return e && !strcmp(e, "f16"); }();
+  const bool ln16 = !frag && ln_f16 && m->cq_fold && d % 64 == 0 && M * (d / 8) <= 13 * 256 && d <= 2048;      // dec_forward's choice at this row count
   auto pass = [&](bool count) -> int {
     for (int l = 0; l < m->cfg.n_dec_layers; ++l) {
       const DecLayerW& w = m->dec[l];
@@ -1510,9 +1470,8 @@ int wis_bench_weight_stream(wis_model_t* m, int M, int passes, float* total_ms, 
         if (frag) { g.x = t.K == d ? (const void*)m->dxf : (const void*)m->dhxf; g.xmb = MBf; g.stat_in = m->dstat; WIS_RET(launch_gemv_frag(st, g)); }
         else {
           g.x = t.ln ? (const void*)m->dx : (const void*)m->dh;
-          if (t.ln && lnp) { g.x = m->dxh; g.stat_in = m->dstat; g.flags = GV_LNP | GV_OUT_F32; }      // the form dec_forward launches (f16 rows + partials)
           if (t.ln && ln16) { g.x = m->dxh; g.flags = GV_LN16 | GV_OUT_F32; }
-          WIS_RET(launch_ln_gemv(m, st, g));   // (more than 8 rows, round-1 route: LayerNorm runs as its own launch)
+          WIS_RET(launch_gemv(st, g));
         }
         if (count) { ++launches; bytes += (double)t.N * t.K * (m->w8 ? 1 : 2); }
       }
@@ -1523,9 +1482,8 @@ int wis_bench_weight_stream(wis_model_t* m, int M, int passes, float* total_ms, 
     if (frag) { g.x = m->dxf; g.xmb = MBf; g.stat_in = m->dstat; WIS_RET(launch_gemv_frag(st, g)); }
     else {
       g.x = m->dx;
-      if (lnp) { g.x = m->dxh; g.stat_in = m->dstat; g.flags = GV_LNP | GV_OUT_F32; }
       if (ln16) { g.x = m->dxh; g.flags = GV_LN16 | GV_OUT_F32; }
-      WIS_RET(launch_ln_gemv(m, st, g));
+      WIS_RET(launch_gemv(st, g));
     }
     if (count) { ++launches; bytes += (double)m->n_vocab_pad * d * (m->w8 ? 1 : 2); }
     return WIS_OK;
@@ -1537,7 +1495,7 @@ int wis_bench_weight_stream(wis_model_t* m, int M, int passes, float* total_ms, 
   }
   WIS_HIP_CHECK(hipMemsetAsync(m->dx, 0, (size_t)MAX_ROWS * d * 4, st));
   WIS_HIP_CHECK(hipMemsetAsync(m->dh, 0, (size_t)MAX_ROWS * 4 * d * 2, st));
-  if (lnp || ln16) {
+  if (ln16) {
     WIS_HIP_CHECK(hipMemsetAsync(m->dxh, 0, (size_t)MAX_ROWS * d * 2, st));
     WIS_HIP_CHECK(hipMemsetAsync(m->dstat, 0, (size_t)MAX_ROWS * (d / 16) * 2 * 4, st));
   }
@@ -1655,13 +1613,13 @@ int wis_op_gemv(int device, const void* x, const float* gamma, const float* beta
   hipStream_t st = ctx_stream(c);
   if (flags & GV_QKV) { set_error("wis_op_gemv: flag 16 is internal"); return WIS_E_ARG; }
   const int Npad = cdiv(N, gemv_rows_for(N, K)) * gemv_rows_for(N, K);
-  // (tap flags: 32 = quantise the matrix to 8 bits per weight first - NOT GV_LNP; 64 = GV_LN16: x is the F16 copy of the rows, LayerNorm folded)
+  // (tap flags: 32 = quantise the matrix to 8 bits per weight first; 64 = GV_LN16: x is the F16 copy of the rows, LayerNorm folded)
   const bool w8 = flags & 32, ln16 = (flags & GV_LN16) != 0, ln = (flags & GV_LN) || ln16;
   flags &= ~32;
   if (ln16 && ((flags & GV_LN) || M > 8 || w8)) { set_error("wis_op_gemv: flag 64 (LayerNorm fold on f16 rows): <= 8 rows, f16 weights, without flag 8"); return WIS_E_ARG; }
   if (ln && (!gamma || !beta)) { set_error("wis_op_gemv: flags 8 / 64 need gamma and beta"); return WIS_E_ARG; }
   // the same preparation the model loader does: optional LayerNorm fold into a private copy of W / bias, then packing
-  f16 *wp = nullptr, *wtmp = nullptr, *xn = nullptr, *xfr = nullptr; float *wsc = nullptr, *b2 = nullptr, *cs = nullptr, *stt = nullptr;
+  f16 *wp = nullptr, *wtmp = nullptr, *xfr = nullptr; float *wsc = nullptr, *b2 = nullptr, *cs = nullptr, *stt = nullptr;
   int rc = WIS_OK;
   do {
     if (hipMalloc(reinterpret_cast<void**>(&wp), (size_t)Npad * K * 2) != hipSuccess || hipMalloc(reinterpret_cast<void**>(&wtmp), (size_t)N * K * 2) != hipSuccess ||
@@ -1677,8 +1635,7 @@ int wis_op_gemv(int device, const void* x, const float* gamma, const float* beta
     if (w8 && ln && (rc = launch_csum8(st, wtmp, wsc, cs, N, K, 0, 1.f))) break;
     GemvP g; memset(&g, 0, sizeof(g));
     g.x = x; g.csum = ln ? cs : nullptr; g.Wp = wp; g.wscale = wsc; g.bias = (bias || ln) ? b2 : nullptr; g.y = y; g.M = M; g.N = N; g.K = K; g.flags = flags; g.rows = rows;
-    static const bool no_frag = getenv("WIS_NO_FRAG") != nullptr;
-    if (M > 8 && !no_frag) {
+    if (M > 8) {
       // the product's batched route (dec_forward_frag): activations as a fragment image, LayerNorm statistics as row partials
       const int MBf = cdiv(M, 16);
       if (hipMalloc(reinterpret_cast<void**>(&xfr), (size_t)(K / 32) * MBf * 64 * 8 * 2) != hipSuccess ||
@@ -1700,15 +1657,10 @@ int wis_op_gemv(int device, const void* x, const float* gamma, const float* beta
       hipFree(kp); hipFree(kc);
       break;
     }
-    if (ln && M > 8) {      // the round-1 split path (WIS_NO_FRAG): plain normalisation, then f16 activations against the folded weights
-      if (hipMalloc(reinterpret_cast<void**>(&xn), (size_t)M * K * 2) != hipSuccess) { set_error("wis_op_gemv: out of device memory"); rc = WIS_E_NOMEM; break; }
-      if ((rc = launch_layernorm(st, reinterpret_cast<const float*>(x), nullptr, nullptr, xn, M, K))) break;
-      g.x = xn; g.csum = nullptr; g.flags &= ~GV_LN;
-    }
     rc = launch_gemv(st, g);
   } while (0);
   hipError_t e = hipStreamSynchronize(st);
-  hipFree(wp); hipFree(wtmp); hipFree(b2); hipFree(cs); hipFree(wsc); hipFree(xn); hipFree(xfr); hipFree(stt);
+  hipFree(wp); hipFree(wtmp); hipFree(b2); hipFree(cs); hipFree(wsc); hipFree(xfr); hipFree(stt);
   if (rc) return rc;
   if (e != hipSuccess) { set_error("wis_op_gemv: %s", hipGetErrorString(e)); return WIS_E_HIP; }
   return WIS_OK;
