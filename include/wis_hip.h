@@ -356,6 +356,38 @@ int wis_op_dec_cross_attn(int device, const float* q, const void* kx_f16, const 
 int wis_op_dec_cross_attn_folded(int device, const float* q_raw, const float* xres, const float* qcs, const float* qb,
                                  const void* kx_f16, const void* vt_f16, void* out_f16, int B, int R, int H, int T, int chunks);
 
+/* ---- taps of the forms the decode step launches (tests/test_gpu_dec_step_ops.py).  They add arguments and the loader's preparation only: which
+ * kernel instantiation runs is decided by the product's own launch_* functions, as in a decode step. */
+/* cross-attention with the query folded from ROW PARTIALS (dec_forward / dec_forward_frag at <= 8 rows per utterance): q (+ q2, optional) f32 [B*R][d]
+ * the halves of q_raw, stat f32 [B*R][d/16][2] the (sum x, sum (x - tile mean)^2) pairs per 16 columns of the un-normalised rows; the kernel merges
+ * mean / rstd from them and finishes q = rstd (q + q2 - mean qcs) + qb.  R <= 8, d <= 2048.  stat = qcs = qb = q2 = NULL: the plain form (q finished).
+ * out_mb > 0: out is the MFMA fragment image of out_mb >= ceil(B R / 16) row blocks (zero-filled first; element (m, k) at
+ * (((k / 32) out_mb + m / 16) 64 + m % 16 + 16 ((k / 8) % 4)) 8 + k % 8), else f16 [B*R][d].  kv_shared = 1: every group b reads utterance 0's K / V
+ * (draft verification).  no_spin = 1: no granule hand-off buffers are passed (the ticket form), as a handle does after a give-up; they are also
+ * withheld above 192 (utterance, head) pairs.  Three launches per call on one set of tickets / epochs. */
+int wis_op_dec_cross_attn_stat(int device, const float* q, const float* q2, const float* stat, const float* qcs, const float* qb,
+                               const void* kx_f16, const void* vt_f16, void* out_f16, int B, int R, int H, int T, int chunks,
+                               int out_mb, int kv_shared, int no_spin);
+/* wis_op_dec_self_attn with the step's other choices: nb = 2 / 4 / 8 eight-position blocks per pass (the step graphs: 2 up to 16 cached positions,
+ * 4 up to 32), out_mb > 0: the fragment image as above, and the TREE form (anc != NULL; draft verification): anc i32 [M][aw] - row m reads positions
+ * < w0 from slot base[m] (base NULL: anc[m][0]) and position w0 + t from slot anc[m][min(t, aw - 1)]; rpu / sstride / rmul are unused then. */
+int wis_op_dec_self_attn_ex(int device, const float* q, const void* kc_f16, const void* vc_f16, const int32_t* pos, void* out_f16,
+                            int M, int H, int ctx, int rpu, int sstride, int rmul, int nb, int out_mb,
+                            const int32_t* anc, int w0, int aw, const int32_t* base);
+/* the self-attention QKV projection behind its LayerNorm with the scatter epilogue (GV_LN | GV_QKV), prepared as the loader prepares it (LayerNorm
+ * fold, 1/8 on the query rows, packing): x f32 [M][d], W f16 [3d][d], bias f32 [3d] -> q f32 [M][d]; row m's key / value rows go to
+ * kc / vc f16 [slots][ctx][d] at (slot[m], pos[m]).  M <= 8: the LDS-staged form; more rows: fragment image + row partials (launch_gemv_frag). */
+int wis_op_gemv_qkv(int device, const float* x, const float* gamma, const float* beta, const void* W_f16, const float* bias,
+                    const int32_t* slot, const int32_t* pos, float* q, void* kc_f16, void* vc_f16, int M, int d, int ctx);
+/* the fused stage behind the self-attention: x1 = x0 + Wo a + bo with the LayerNorm partials of x1, and q_raw = W'q x0 + (W'q Wo) a + W'q bo of the
+ * cross-attention query folded THROUGH the out-projection (W'q = (Wq o gamma) / 8; model.hip build_cq_fold, the loader's own code).
+ * a f16 [M][d], x0 f32 [M][d], Wo / Wq f16 [d][d], bo / bq / gamma / beta f32 [d] -> x1 f32 [M][d], stat f32 [M][d/16][2], qcs / qb f32 [d] (column
+ * sums and bias of the folded projection: what wis_op_dec_cross_attn_stat takes).  M <= 8 and force_frag = 0: one launch_gemv_dual, q = q_raw, q2
+ * untouched (may be NULL); otherwise launch_gemv_frag3: q = W'q x0 + W'q bo, q2 = (W'q Wo) a. */
+int wis_op_gemv_out_cq(int device, const void* a_f16, const float* x0, const void* Wo_f16, const float* bo, const void* Wq_f16, const float* bq,
+                       const float* gamma, const float* beta, float* x1, float* stat, float* q, float* q2, float* qcs, float* qb,
+                       int M, int d, int force_frag);
+
 /* ---- speaker verification (replaces the reference's WavLMForXVector embedder, main.py:306-316 / do_sv 797-879): one handle = the
  * WavLM-base-plus-sv x-vector model on one GPU.  Input: mono 16 kHz f32 PCM in host memory, already through the reference's
  * preprocessing (sox gain + trim, the feature extractor's zero-mean / unit-variance normalisation: wis_hip/sv.py); output: the

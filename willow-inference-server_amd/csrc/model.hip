@@ -344,6 +344,21 @@ int to_packed(wis_model* m, const Loader& L, const std::string& name, int N, int
   return WIS_OK;
 }
 
+// The cross-Q fold's matrix and bias (load_weights below; the wis_op_gemv_out_cq tap builds its operands with the same code): wq_gamma = f16(Wq o gamma)
+// [d][d] as fold_ln_kernel left it, wo / bo = the self-attention output projection (f16 or f32 [d][d]; fp32 [d]) ->
+//   p_cqo = packed [W'q | W'q Wo] ([d][2d], W'q = wq_gamma * qs, the product rounded to f16 like every other stored weight),  b_cqo = W'q bo.
+// fcat [d][2d], fwot [d][d], fwqo [d][d]: f16 staging of the caller.
+int build_cq_fold(hipStream_t st, const f16* wq_gamma, const void* wo, int wo_f16, const float* bo, int d, float qs, f16* fcat, f16* fwot, f16* fwqo, f16* p_cqo, float* b_cqo) {
+  hipLaunchKernelGGL(convert_kernel, dim3(blocks_for((int64_t)d * d)), dim3(256), 0, st, wq_gamma, 1, fcat, 1, (int64_t)d, (int64_t)d, (int64_t)2 * d, (int64_t)d, qs);   // left half: W'q
+  hipLaunchKernelGGL(transpose_to_f16_kernel, dim3(cdiv(d, 32), cdiv(d, 32)), dim3(256), 0, st, wo, wo_f16, fwot, d, d);
+  GemmP gp = gemm_plain(fcat, 2 * d, fwot, d, d, d);
+  WIS_RET(launch_gemm_generic(st, gp, nullptr, nullptr, fwqo, 0));                                     // W'q . Wo  (f16 inputs, fp32 accumulate)
+  hipLaunchKernelGGL(convert_kernel, dim3(blocks_for((int64_t)d * d)), dim3(256), 0, st, fwqo, 1, fcat + d, 1, (int64_t)d, (int64_t)d, (int64_t)2 * d, (int64_t)0, 1.f);   // right half
+  WIS_RET(launch_pack_gemv(st, fcat, p_cqo, d, d, 2 * d, 0, 1.f, 16));
+  hipLaunchKernelGGL(matvec_rows_kernel, dim3(d), dim3(64), 0, st, fcat, 2 * d, bo, b_cqo, d, d);
+  return WIS_OK;
+}
+
 int load_weights(wis_model* m, const Loader& L) {
   const wis_config_t& c = m->cfg;
   const int d = c.d_model, V = c.n_vocab;
@@ -446,15 +461,9 @@ int load_weights(wis_model* m, const Loader& L) {
         // in the same launch as the out-projection; mu / rs of x1 are applied by the cross-attention kernel (dec_kernels.hip).
         // tmp holds f16(Wq o gamma) (to_packed above); W'q Wo is rounded to f16 like every other stored weight.
         TensorSrc so; if ((rc = L.get(p + "self_attention/linear_1/weight", d, d, &so))) break;
-        hipLaunchKernelGGL(convert_kernel, dim3(blocks_for((int64_t)d * d)), dim3(256), 0, m->st, tmp, 1, fcat, 1, (int64_t)d, (int64_t)d, (int64_t)2 * d, (int64_t)d, qs);   // left half: W'q
-        hipLaunchKernelGGL(transpose_to_f16_kernel, dim3(cdiv(d, 32), cdiv(d, 32)), dim3(256), 0, m->st, so.p, so.f16, fwot, d, d);
-        GemmP gp = gemm_plain(fcat, 2 * d, fwot, d, d, d);
-        if ((rc = launch_gemm_generic(m->st, gp, nullptr, nullptr, fwqo, 0))) break;                                     // W'q . Wo  (f16 inputs, fp32 accumulate)
-        hipLaunchKernelGGL(convert_kernel, dim3(blocks_for((int64_t)d * d)), dim3(256), 0, m->st, fwqo, 1, fcat + d, 1, (int64_t)d, (int64_t)d, (int64_t)2 * d, (int64_t)0, 1.f);   // right half
         if ((rc = dalloc(m, &w.p_cqo, (size_t)d * 2 * d))) break;
-        if ((rc = launch_pack_gemv(m->st, fcat, w.p_cqo, d, d, 2 * d, 0, 1.f, 16))) break;
         if ((rc = dalloc(m, &w.b_cqo, (size_t)d))) break;
-        hipLaunchKernelGGL(matvec_rows_kernel, dim3(d), dim3(64), 0, m->st, fcat, 2 * d, w.b_out, w.b_cqo, d, d);
+        if ((rc = build_cq_fold(m->st, tmp, so.p, so.f16, w.b_out, d, qs, fcat, fwot, fwqo, w.p_cqo, w.b_cqo))) break;
       }
       w.w_ckv = m->w_ckv_all + (size_t)l * 2 * d * d; w.b_ckv = m->b_ckv_all + (size_t)l * 2 * d;
       if ((rc = to_f16_mat(m, L, p + "attention/linear_1/weight", 2 * d, d, &w.w_ckv))) break;
@@ -1677,15 +1686,32 @@ int wis_op_dec_self_attn(int device, const float* q, const void* kc, const void*
   WIS_HIP_CHECK(hipStreamSynchronize(ctx_stream(c)));
   return WIS_OK;
 }
+int wis_op_dec_self_attn_ex(int device, const float* q, const void* kc, const void* vc, const int32_t* pos, void* out,
+                            int M, int H, int ctx, int rpu, int sstride, int rmul, int nb, int out_mb,
+                            const int32_t* anc, int w0, int aw, const int32_t* base) {
+  DeviceCtx* c; WIS_RET(get_ctx(device, &c));
+  std::lock_guard<std::mutex> op_lock(ctx_op_mutex(c));
+  if (!q || !kc || !vc || !pos || !out || M < 1 || H < 1 || rpu < 1 || (nb != 2 && nb != 4 && nb != 8) || (out_mb && out_mb < cdiv(M, 16)) || (base && !anc)) {
+    set_error("wis_op_dec_self_attn_ex: bad argument"); return WIS_E_ARG; }
+  hipStream_t st = ctx_stream(c);
+  const int d = 64 * H;
+  if (out_mb) WIS_HIP_CHECK(hipMemsetAsync(out, 0, (size_t)(d / 32) * out_mb * 64 * 8 * 2, st));      // the fragment image's rows beyond M stay zero
+  WIS_RET(launch_dec_self_attn(st, q, reinterpret_cast<const f16*>(kc), reinterpret_cast<const f16*>(vc), pos, reinterpret_cast<f16*>(out),
+                               M, H, d, ctx, rpu, sstride, rmul, nullptr, out_mb, anc, w0, aw, base, nb));
+  WIS_HIP_CHECK(hipGetLastError());
+  WIS_HIP_CHECK(hipStreamSynchronize(st));
+  return WIS_OK;
+}
 static int op_dec_cross_attn(int device, const float* q, const float* xres, const float* qcs, const float* qb, const void* kx, const void* vt, void* out,
-                             int B, int R, int H, int T, int chunks) {
+                             int B, int R, int H, int T, int chunks, const float* q2 = nullptr, int xres_is_stat = 0, int out_mb = 0, int kv_shared = 0, bool no_spin = false) {
   DeviceCtx* c; WIS_RET(get_ctx(device, &c));
   std::lock_guard<std::mutex> op_lock(ctx_op_mutex(c));
   if (!q || !kx || !vt || !out || B < 1 || H < 1 || T < 1) { set_error("wis_op_dec_cross_attn: bad argument"); return WIS_E_ARG; }
   hipStream_t st = ctx_stream(c);
   float* part = nullptr; unsigned* counters = nullptr; unsigned long long* gran = nullptr; unsigned* epoch = nullptr;
   int rc = WIS_OK;
-  const bool small = B * H <= CA_SPIN_MAX_BH;      // the product's rule: the granule hand-off on small grids (launch_dec_cross_attn decides by chunking / rows)
+  if (out_mb && out_mb < cdiv(B * R, 16)) { set_error("wis_op_dec_cross_attn: %d row blocks for %d rows", out_mb, B * R); return WIS_E_ARG; }
+  const bool small = B * H <= CA_SPIN_MAX_BH && !no_spin;      // the product's rule: the granule hand-off on small grids (launch_dec_cross_attn decides by chunking / rows)
   if (hipMalloc(reinterpret_cast<void**>(&part), (size_t)B * H * 16 * 16 * 66 * 4) != hipSuccess ||
       hipMalloc(reinterpret_cast<void**>(&counters), (size_t)B * H * 4) != hipSuccess ||
       (small && (hipMalloc(reinterpret_cast<void**>(&gran), (size_t)B * H * 6 * 8 * 66 * 8) != hipSuccess || hipMalloc(reinterpret_cast<void**>(&epoch), ((size_t)B * H + 1) * 4) != hipSuccess))) {
@@ -1694,9 +1720,10 @@ static int op_dec_cross_attn(int device, const float* q, const float* xres, cons
   if (!rc) {
     hipMemsetAsync(counters, 0, (size_t)B * H * 4, st);
     if (small) { hipMemsetAsync(gran, 0, (size_t)B * H * 6 * 8 * 66 * 8, st); hipMemsetAsync(epoch, 0, ((size_t)B * H + 1) * 4, st); }
+    if (out_mb) hipMemsetAsync(out, 0, (size_t)(64 * H / 32) * out_mb * 64 * 8 * 2, st);      // the fragment image's rows beyond B * R stay zero
     for (int rep = 0; rep < 3 && !rc; ++rep)      // three launches: the epochs of the granule form advance from launch to launch
       rc = launch_dec_cross_attn(st, q, reinterpret_cast<const f16*>(kx), reinterpret_cast<const f16*>(vt), reinterpret_cast<f16*>(out), part, counters,
-                                 B, R, H, 64 * H, T, cdiv(T, 64) * 64, chunks, nullptr, 0, xres, qcs, qb, gran, epoch);
+                                 B, R, H, 64 * H, T, cdiv(T, 64) * 64, chunks, nullptr, out_mb, xres, qcs, qb, gran, epoch, q2, xres_is_stat, kv_shared);
     if (small && !rc) hipMemcpyAsync(&flag, epoch, 4, hipMemcpyDeviceToHost, st);
   }
   hipError_t e = hipStreamSynchronize(st);
@@ -1713,6 +1740,125 @@ int wis_op_dec_cross_attn_folded(int device, const float* q_raw, const float* xr
                                  int B, int R, int H, int T, int chunks) {
   if (!xres || !qcs || !qb) { set_error("wis_op_dec_cross_attn_folded: bad argument"); return WIS_E_ARG; }
   return op_dec_cross_attn(device, q_raw, xres, qcs, qb, kx, vt, out, B, R, H, T, chunks);
+}
+int wis_op_dec_cross_attn_stat(int device, const float* q, const float* q2, const float* stat, const float* qcs, const float* qb, const void* kx, const void* vt, void* out,
+                               int B, int R, int H, int T, int chunks, int out_mb, int kv_shared, int no_spin) {
+  if (stat ? (!qcs || !qb) : (qcs || qb || q2)) { set_error("wis_op_dec_cross_attn_stat: the fold takes partials, column sums and bias together; the plain form none of them"); return WIS_E_ARG; }
+  return op_dec_cross_attn(device, q, stat, qcs, qb, kx, vt, out, B, R, H, T, chunks, q2, stat ? 1 : 0, out_mb, kv_shared, no_spin != 0);
+}
+
+}  // extern "C"
+
+// private device scratch of a tap: freed when the tap returns
+namespace {
+struct TapScratch {
+  std::vector<void*> ptrs;
+  template <class T> bool get(T** p, size_t n_elems) {
+    void* q = nullptr;
+    if (hipMalloc(&q, n_elems * sizeof(T) ? n_elems * sizeof(T) : 16) != hipSuccess) return false;
+    ptrs.push_back(q); *p = reinterpret_cast<T*>(q); return true;
+  }
+  ~TapScratch() { for (void* q : ptrs) hipFree(q); }
+};
+}  // namespace
+
+extern "C" {
+
+int wis_op_gemv_qkv(int device, const float* x, const float* gamma, const float* beta, const void* W, const float* bias, const int32_t* slot, const int32_t* pos,
+                    float* q, void* kc, void* vc, int M, int d, int ctx) {
+  DeviceCtx* c; WIS_RET(get_ctx(device, &c));
+  std::lock_guard<std::mutex> op_lock(ctx_op_mutex(c));
+  if (!x || !gamma || !beta || !W || !bias || !slot || !pos || !q || !kc || !vc || M < 1 || M > MAX_ROWS || d < 128 || d % 128 || ctx < 1) { set_error("wis_op_gemv_qkv: bad argument"); return WIS_E_ARG; }
+  hipStream_t st = ctx_stream(c);
+  const int N = 3 * d, MB = cdiv(M, 16);
+  const float qs = 0.125f;
+  TapScratch ts;
+  f16 *wp = nullptr, *wtmp = nullptr, *xf = nullptr; float *b2 = nullptr, *cs = nullptr, *stt = nullptr;
+  if (!ts.get(&wp, (size_t)N * d) || !ts.get(&wtmp, (size_t)N * d) || !ts.get(&b2, (size_t)N) || !ts.get(&cs, (size_t)N) ||
+      (M > 8 && (!ts.get(&xf, (size_t)(d / 32) * MB * 64 * 8) || !ts.get(&stt, (size_t)M * (d / 16) * 2)))) { set_error("wis_op_gemv_qkv: out of device memory"); return WIS_E_NOMEM; }
+  int rc = WIS_OK;
+  do {
+    // what load_weights does for p_qkv / b_qkv / c_qkv: the bias's query part scaled, the LayerNorm folded, the query rows scaled by the packer
+    hipMemcpyAsync(wtmp, W, (size_t)N * d * 2, hipMemcpyDeviceToDevice, st);
+    hipLaunchKernelGGL(convert_kernel, dim3(blocks_for(N)), dim3(256), 0, st, bias, 0, b2, 0, (int64_t)N, (int64_t)1, (int64_t)1, (int64_t)d, qs);
+    hipMemsetAsync(cs, 0, (size_t)N * 4, st);
+    if ((rc = launch_fold_ln(st, wtmp, gamma, beta, b2, cs, N, d, d, qs))) break;
+    if ((rc = launch_pack_gemv(st, wtmp, wp, N, N, d, d, qs, gemv_rows_for(N, d)))) break;
+    GemvP g; memset(&g, 0, sizeof(g));
+    g.x = x; g.csum = cs; g.Wp = wp; g.bias = b2; g.M = M; g.N = N; g.K = d; g.flags = GV_LN | GV_QKV;
+    g.q = q; g.kc = reinterpret_cast<f16*>(kc); g.vc = reinterpret_cast<f16*>(vc); g.slot = slot; g.pos = pos; g.d = d; g.ctx = ctx;
+    g.rows = gemv_rows_for(N, d);
+    if (M <= 8) { rc = launch_gemv(st, g); break; }      // dec_forward
+    // dec_forward_frag: the rows as a fragment image, their LayerNorm statistics as row partials
+    hipMemsetAsync(xf, 0, (size_t)(d / 32) * MB * 64 * 8 * 2, st);
+    if ((rc = launch_xf_pack(st, x, 0, xf, stt, M, d, MB))) break;
+    g.x = xf; g.xmb = MB; g.stat_in = stt; g.rows = 16;
+    rc = launch_gemv_frag(st, g);
+  } while (0);
+  hipError_t e = hipStreamSynchronize(st);
+  if (rc) return rc;
+  if (e != hipSuccess) { set_error("wis_op_gemv_qkv: %s", hipGetErrorString(e)); return WIS_E_HIP; }
+  return WIS_OK;
+}
+
+int wis_op_gemv_out_cq(int device, const void* a, const float* x0, const void* Wo, const float* bo, const void* Wq, const float* bq, const float* gamma, const float* beta,
+                       float* x1, float* stat, float* q, float* q2, float* qcs, float* qb, int M, int d, int force_frag) {
+  DeviceCtx* c; WIS_RET(get_ctx(device, &c));
+  std::lock_guard<std::mutex> op_lock(ctx_op_mutex(c));
+  const bool frag = M > 8 || force_frag;
+  if (!a || !x0 || !Wo || !bo || !Wq || !bq || !gamma || !beta || !x1 || !stat || !q || !qcs || !qb || (frag && !q2) || M < 1 || M > MAX_ROWS || d < 128 || d % 128) {
+    set_error("wis_op_gemv_out_cq: bad argument"); return WIS_E_ARG; }
+  hipStream_t st = ctx_stream(c);
+  const int MB = cdiv(M, 16);
+  const float qs = 0.125f;
+  const size_t img = (size_t)(d / 32) * MB * 64 * 8;
+  TapScratch ts;
+  f16 *wtmp = nullptr, *fcat = nullptr, *fwot = nullptr, *fwqo = nullptr, *p_cqo = nullptr, *p_out = nullptr, *xh = nullptr, *xf = nullptr, *af = nullptr; float* b_cqo = nullptr;
+  if (!ts.get(&wtmp, (size_t)d * d) || !ts.get(&fcat, (size_t)2 * d * d) || !ts.get(&fwot, (size_t)d * d) || !ts.get(&fwqo, (size_t)d * d) || !ts.get(&p_cqo, (size_t)2 * d * d) ||
+      !ts.get(&p_out, (size_t)d * d) || !ts.get(&b_cqo, (size_t)d) || (frag ? (!ts.get(&xf, img) || !ts.get(&af, img)) : !ts.get(&xh, (size_t)M * d))) {
+    set_error("wis_op_gemv_out_cq: out of device memory"); return WIS_E_NOMEM; }
+  int rc = WIS_OK;
+  do {
+    // load_weights, decoder layer: b_cq / c_cq (the cross-Q bias scaled, the LayerNorm folded: what the cross-attention kernel takes as qb / qcs), p_out, then the fold
+    hipMemcpyAsync(wtmp, Wq, (size_t)d * d * 2, hipMemcpyDeviceToDevice, st);
+    hipLaunchKernelGGL(convert_kernel, dim3(blocks_for(d)), dim3(256), 0, st, bq, 0, qb, 0, (int64_t)d, (int64_t)1, (int64_t)1, (int64_t)d, qs);
+    hipMemsetAsync(qcs, 0, (size_t)d * 4, st);
+    if ((rc = launch_fold_ln(st, wtmp, gamma, beta, qb, qcs, d, d, d, qs))) break;
+    if ((rc = launch_pack_gemv(st, reinterpret_cast<const f16*>(Wo), p_out, d, d, d, 0, 1.f, gemv_rows_for(d, d)))) break;
+    if ((rc = build_cq_fold(st, wtmp, Wo, 1, bo, d, qs, fcat, fwot, fwqo, p_cqo, b_cqo))) break;
+    hipMemcpyAsync(x1, x0, (size_t)M * d * 4, hipMemcpyDeviceToDevice, st);      // the residual epilogue works in place
+    if (!frag) {
+      // dec_forward: one dual launch on the f16 rows (the attention output; the f16 copy of the layer input that the embedding / FFN2 epilogues leave)
+      hipLaunchKernelGGL(convert_kernel, dim3(blocks_for((int64_t)M * d)), dim3(256), 0, st, x0, 0, xh, 1, (int64_t)M, (int64_t)d, (int64_t)d, (int64_t)0, 1.f);
+      GemvP ga; memset(&ga, 0, sizeof(ga));
+      ga.x = a; ga.Wp = p_out; ga.bias = bo; ga.y = x1; ga.M = M; ga.N = d; ga.K = d; ga.flags = GV_RESID; ga.stat_out = stat;
+      GemvP gb; memset(&gb, 0, sizeof(gb));
+      gb.x = xh; gb.x2 = a; gb.xsplit = d; gb.Wp = p_cqo; gb.bias = b_cqo; gb.y = q; gb.M = M; gb.N = d; gb.K = 2 * d; gb.flags = GV_OUT_F32;
+      rc = launch_gemv_dual(st, ga, gb);
+      break;
+    }
+    // dec_forward_frag: three d x d problems on the fragment images of the layer input and the attention output
+    hipMemsetAsync(xf, 0, img * 2, st); hipMemsetAsync(af, 0, img * 2, st);
+    if ((rc = launch_xf_pack(st, x0, 0, xf, nullptr, M, d, MB))) break;
+    if ((rc = launch_xf_pack(st, a, 1, af, nullptr, M, d, MB))) break;
+    auto base = [&](const void* x, const f16* Wp, const float* bias, int flags) {
+      GemvP g; memset(&g, 0, sizeof(g));
+      g.x = x; g.Wp = Wp; g.bias = bias; g.M = M; g.N = d; g.K = d; g.flags = flags; g.xmb = MB; g.rows = 16;
+      return g;
+    };
+    GemvP g3[3];
+    g3[0] = base(af, p_out, bo, GV_RESID);
+    g3[0].y = x1; g3[0].ymb = MB; g3[0].stat_out = stat;
+    g3[1] = base(xf, p_cqo, b_cqo, GV_OUT_F32);
+    g3[1].y = q; g3[1].wks = 2 * d / 32; g3[1].wk0 = 0;
+    g3[2] = base(af, p_cqo, nullptr, GV_OUT_F32);
+    g3[2].y = q2; g3[2].wks = 2 * d / 32; g3[2].wk0 = d / 32;
+    rc = launch_gemv_frag3(st, g3, 3);
+  } while (0);
+  hipError_t e = hipStreamSynchronize(st);
+  if (rc) return rc;
+  if (e != hipSuccess) { set_error("wis_op_gemv_out_cq: %s", hipGetErrorString(e)); return WIS_E_HIP; }
+  return WIS_OK;
 }
 
 }  // extern "C"

@@ -123,6 +123,10 @@ SYMBOLS = [
     ("wis_op_dec_self_attn", _i, [_i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i]),
     ("wis_op_dec_cross_attn", _i, [_i, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i]),
     ("wis_op_dec_cross_attn_folded", _i, [_i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i]),
+    ("wis_op_dec_cross_attn_stat", _i, [_i] + [_vp] * 8 + [_i] * 8),
+    ("wis_op_dec_self_attn_ex", _i, [_i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _i, _i, _vp]),
+    ("wis_op_gemv_qkv", _i, [_i] + [_vp] * 10 + [_i] * 3),
+    ("wis_op_gemv_out_cq", _i, [_i] + [_vp] * 14 + [_i] * 3),
     ("wis_sv_create", _i, [C.POINTER(SvConfig), _vp, _sz, _i, C.POINTER(Tensor), _i, _i, C.POINTER(_vp)]),
     ("wis_sv_destroy", None, [_vp]),
     ("wis_sv_device_bytes", _sz, [_vp]),
