@@ -1350,19 +1350,17 @@ __global__ __launch_bounds__(64) void dec_self_attn_kernel(const float* __restri
   stamp(pf, 4);
   if (lane == 0) tl_end(prof);
 }
-int launch_dec_self_attn(hipStream_t st, const float* q, const f16* kc, const f16* vc, const int* pos, f16* out,
-                         int M, int H, int d, int ctx, int rpu, int sstride, int rmul, unsigned long long* prof, int out_mb,
-                         const int* anc, int w0, int aw, const int* base, int nb) {
-  if (ctx > 512 || ctx < 64) { set_error("dec_self_attn: ctx=%d outside [64, 512]", ctx); return WIS_E_UNSUPPORTED; }
-  if (anc) {
-    if (aw < 1) { set_error("dec_self_attn: ancestor table of width %d", aw); return WIS_E_ARG; }
-    hipLaunchKernelGGL((dec_self_attn_kernel<true, 8>), dim3(M, H), dim3(64), 0, st, q, kc, vc, pos, d, ctx, rpu, sstride, rmul, out, prof, out_mb, anc, w0, aw, base);
-  } else if (nb == 2)
-    hipLaunchKernelGGL((dec_self_attn_kernel<false, 2>), dim3(M, H), dim3(64), 0, st, q, kc, vc, pos, d, ctx, rpu, sstride, rmul, out, prof, out_mb, anc, w0, aw, base);
-  else if (nb == 4)
-    hipLaunchKernelGGL((dec_self_attn_kernel<false, 4>), dim3(M, H), dim3(64), 0, st, q, kc, vc, pos, d, ctx, rpu, sstride, rmul, out, prof, out_mb, anc, w0, aw, base);
-  else
-    hipLaunchKernelGGL((dec_self_attn_kernel<false, 8>), dim3(M, H), dim3(64), 0, st, q, kc, vc, pos, d, ctx, rpu, sstride, rmul, out, prof, out_mb, anc, w0, aw, base);
+int launch_dec_self_attn(hipStream_t st, const SelfAttnP& p) {
+  if (p.ctx > 512 || p.ctx < 64) { set_error("dec_self_attn: ctx=%d outside [64, 512]", p.ctx); return WIS_E_UNSUPPORTED; }
+#define WIS_SA(TREEv, NBv) hipLaunchKernelGGL((dec_self_attn_kernel<TREEv, NBv>), dim3(p.M, p.H), dim3(64), 0, st, p.q, p.kc, p.vc, p.pos, p.d, p.ctx, p.rpu, p.sstride, p.rmul, p.out, \
+                                              p.prof, p.out_mb, p.anc, p.w0, p.aw, p.base)
+  if (p.anc) {
+    if (p.aw < 1) { set_error("dec_self_attn: ancestor table of width %d", p.aw); return WIS_E_ARG; }
+    WIS_SA(true, 8);
+  } else if (p.nb == 2) WIS_SA(false, 2);
+  else if (p.nb == 4) WIS_SA(false, 4);
+  else WIS_SA(false, 8);
+#undef WIS_SA
   return WIS_OK;
 }
 
@@ -2153,10 +2151,10 @@ __global__ __launch_bounds__(128 * NKW) void dec_cross_attn_rs_kernel(const floa
   stamp(pf, 6);
 }
 
-int launch_dec_cross_attn(hipStream_t st, const float* q, const f16* kx, const f16* vt, f16* out, float* part, unsigned* counters,
-                          int B, int R, int H, int d, int T, int Tpad, int chunks, unsigned long long* prof, int out_mb,
-                          const float* xres, const float* qcs, const float* qb, unsigned long long* gran, unsigned* epoch, const float* q2, int xres_is_stat, int kv_shared) {
-  if (xres && (!qcs || !qb || R > 8 || d > (xres_is_stat ? 2048 : 1280))) { set_error("dec_cross_attn: folded query needs column sums, bias, R <= 8 and d <= 1280 (2048 from partials)"); return WIS_E_ARG; }
+int launch_dec_cross_attn(hipStream_t st, const CrossAttnP& p) {
+  const int B = p.B, R = p.R, H = p.H, d = p.d, T = p.T, Tpad = p.Tpad, chunks = p.chunks, xres_is_stat = p.xres_is_stat;
+  const float* const xres = p.xres;
+  if (xres && (!p.qcs || !p.qb || R > 8 || d > (xres_is_stat ? 2048 : 1280))) { set_error("dec_cross_attn: folded query needs column sums, bias, R <= 8 and d <= 1280 (2048 from partials)"); return WIS_E_ARG; }
   if (xres_is_stat && !xres) { set_error("dec_cross_attn: the fold from partials needs the row partials"); return WIS_E_ARG; }
   if (R < 1 || R > 16 || chunks < 1 || chunks > 16) { set_error("dec_cross_attn: R=%d chunks=%d unsupported", R, chunks); return WIS_E_UNSUPPORTED; }
   if (H > 63 || d > 65535 || T > 65535) { set_error("dec_cross_attn: H=%d d=%d T=%d beyond the packed shape arguments", H, d, T); return WIS_E_UNSUPPORTED; }
@@ -2165,16 +2163,16 @@ int launch_dec_cross_attn(hipStream_t st, const float* q, const f16* kx, const f
   const int used = cdiv(T, CL);                      // chunks that actually hold keys
   static const int env_spin = getenv("WIS_CA_SPIN") ? atoi(getenv("WIS_CA_SPIN")) : 1;      // 0: always the ticket form (A/B switch)
   // granule hand-off: small grids only (fewer spinning combiners than CUs), the default 256-key chunking, <= 8 rows per utterance
-  const bool spin = env_spin && gran && epoch && B * H <= CA_SPIN_MAX_BH && CL == 256 && used >= 2 && used <= 6 && R <= 8;
-#define WIS_CA(TPWv, CMv, FOLDv, SPINv) hipLaunchKernelGGL((dec_cross_attn_kernel<TPWv, CMv, FOLDv, SPINv>), dim3(used, H, B), dim3(256), 0, st, q, kx, vt, xres, q2, epoch, \
-                                                  (R | (H << 8) | (CL << 14) | (used << 24)), (d | (T << 16)), (Tpad | (kv_shared ? (1 << 30) : 0)), out, part, counters, prof, out_mb, qcs, qb, gran)
+  const bool spin = env_spin && p.gran && p.epoch && B * H <= CA_SPIN_MAX_BH && CL == 256 && used >= 2 && used <= 6 && R <= 8;
+#define WIS_CA(TPWv, CMv, FOLDv, SPINv) hipLaunchKernelGGL((dec_cross_attn_kernel<TPWv, CMv, FOLDv, SPINv>), dim3(used, H, B), dim3(256), 0, st, p.q, p.kx, p.vt, xres, p.q2, p.epoch, \
+                                                  (R | (H << 8) | (CL << 14) | (used << 24)), (d | (T << 16)), (Tpad | (p.kv_shared ? (1 << 30) : 0)), p.out, p.part, p.counters, p.prof, p.out_mb, p.qcs, p.qb, p.gran)
   if (xres_is_stat) {
     const bool small = (long)B * H * used <= 256;      // at most one workgroup per CU: V is requested up front (FOLD 3)
     // the role-split kernel (K waves / V waves): WIS_CA_RS=0 off (A/B switch), 1 the batched step's grids only, 2 (default) the one-utterance step's too
     static const int ca_rs = getenv("WIS_CA_RS") ? atoi(getenv("WIS_CA_RS")) : 2;
     if (ca_rs && (!small || ca_rs >= 2) && CL == 256 && used <= 6 && R <= 8 && d <= 1280) {
-#define WIS_CA_RS(SPINv, NTv) hipLaunchKernelGGL((dec_cross_attn_rs_kernel<SPINv, NTv, 2>), dim3(used, H, B), dim3(256), 0, st, q, kx, vt, xres, q2, epoch, \
-                                                        (R | (H << 8) | (CL << 14) | (used << 24)), (d | (T << 16)), (Tpad | (kv_shared ? (1 << 30) : 0)), out, part, counters, prof, out_mb, qcs, qb, gran)
+#define WIS_CA_RS(SPINv, NTv) hipLaunchKernelGGL((dec_cross_attn_rs_kernel<SPINv, NTv, 2>), dim3(used, H, B), dim3(256), 0, st, p.q, p.kx, p.vt, xres, p.q2, p.epoch, \
+                                                        (R | (H << 8) | (CL << 14) | (used << 24)), (d | (T << 16)), (Tpad | (p.kv_shared ? (1 << 30) : 0)), p.out, p.part, p.counters, p.prof, p.out_mb, p.qcs, p.qb, p.gran)
       if (spin) { if (small) WIS_CA_RS(true, true); else WIS_CA_RS(true, false); }
       else { if (small) WIS_CA_RS(false, true); else WIS_CA_RS(false, false); }
 #undef WIS_CA_RS

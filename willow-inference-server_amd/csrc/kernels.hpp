@@ -115,20 +115,29 @@ int launch_dec_embed(hipStream_t st, const f16* emb, const f16* pos_emb, const i
 // out_mb: 0 = out is row-major f16 [M][d]; > 0 = fragment image with that many 16-row blocks (batched decode)
 // anc (optional; draft verification at beam > 1, model.hip verify_beam_draft): the rows of a pass are the nodes of a beam TREE - row m reads
 // the cache rows of positions < w0 from slot anc[m * aw] and position w0 + t from slot anc[m * aw + t] (its ancestor at window step t)
-int launch_dec_self_attn(hipStream_t st, const float* q, const f16* kc, const f16* vc, const int* pos, f16* out,
-                         int M, int H, int d, int ctx, int rpu, int sstride, int rmul, unsigned long long* prof = nullptr, int out_mb = 0,
-                         const int* anc = nullptr, int w0 = 0, int aw = 0, const int* base = nullptr, int nb = 8);      // nb: 8-position blocks per pass (2 / 4 / 8; plain form only)      // base (optional): slot of the positions before w0, per row
+struct SelfAttnP {
+  const float* q = nullptr; const f16* kc = nullptr; const f16* vc = nullptr; const int* pos = nullptr; f16* out = nullptr;
+  int M = 0, H = 0, d = 0, ctx = 0, rpu = 0, sstride = 0, rmul = 0;
+  unsigned long long* prof = nullptr; int out_mb = 0; const int* anc = nullptr; int w0 = 0, aw = 0;
+  const int* base = nullptr;      // (optional): slot of the positions before w0, per row
+  int nb = 8;                     // 8-position blocks per pass (2 / 4 / 8; plain form only)
+};
+int launch_dec_self_attn(hipStream_t st, const SelfAttnP& p);
 // cross attention of R rows per utterance over the utterance's T encoder keys.
 //   q f32 [B*R][d] (pre-scaled), kx f16 [B][H][8][T][8], vt f16 [B][H][64][Tpad] (zero padded) -> out f16 [B*R][d]
 // gran / epoch (optional): the granule hand-off of small grids (dec_kernels.hip, SPIN): gran = 8-byte slots [B*H][6][8][66], epoch =
 // ONE flag word (non-zero: a combiner's bounded spin ran out) followed by [B*H] monotonic epoch words, all zero-initialised once
 constexpr int CA_SPIN_MAX_BH = 192;      // spinning combiners per launch: fewer than the chip's 256 CUs, so a producer always finds a slot (8 utterances x 20 heads = 160)
-int launch_dec_cross_attn(hipStream_t st, const float* q, const f16* kx, const f16* vt, f16* out, float* part, unsigned* counters,
-                          int B, int R, int H, int d, int T, int Tpad, int chunks, unsigned long long* prof = nullptr, int out_mb = 0,
-                          const float* xres = nullptr, const float* qcs = nullptr, const float* qb = nullptr,   // folded query: see the kernel
-                          unsigned long long* gran = nullptr, unsigned* epoch = nullptr,
-                          const float* q2 = nullptr, int xres_is_stat = 0,    // batched fold: q = q + q2; xres = row partials [B*R][d/16][2] instead of the rows
-                          int kv_shared = 0);      // 1: every row group b reads utterance 0's K / V (the B groups are rows of ONE utterance: draft verification)
+struct CrossAttnP {
+  const float* q = nullptr; const f16* kx = nullptr; const f16* vt = nullptr; f16* out = nullptr; float* part = nullptr; unsigned* counters = nullptr;
+  int B = 0, R = 0, H = 0, d = 0, T = 0, Tpad = 0, chunks = 0;
+  unsigned long long* prof = nullptr; int out_mb = 0;
+  const float* xres = nullptr; const float* qcs = nullptr; const float* qb = nullptr;   // folded query: see the kernel
+  unsigned long long* gran = nullptr; unsigned* epoch = nullptr;
+  const float* q2 = nullptr; int xres_is_stat = 0;    // batched fold: q = q + q2; xres = row partials [B*R][d/16][2] instead of the rows
+  int kv_shared = 0;      // 1: every row group b reads utterance 0's K / V (the B groups are rows of ONE utterance: draft verification)
+};
+int launch_dec_cross_attn(hipStream_t st, const CrossAttnP& p);
 
 // sampling: per-(row, chunk) masked max / sum-exp / top-2k of the logits
 struct SampleCfg {

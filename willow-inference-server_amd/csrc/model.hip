@@ -13,6 +13,7 @@
 #include <string.h>
 #include <time.h>
 #include <algorithm>
+#include <array>
 #include <atomic>
 #include <chrono>
 #include <map>
@@ -106,14 +107,22 @@ struct EncLayerW {
   f16 *w_qkv, *w_out, *w_f1, *w_f2;
   float *b_qkv, *b_out, *b_f1, *b_f2;
 };
+// One decoder projection as the step streams it (load_weights: load_proj; the taps fill one from their own scratch)
+struct DecProj {
+  const f16* Wp;          // MFMA-fragment packed matrix; the 8-bit image when `scale` is given
+  const float* scale;     // int8_float16: dequantisation scale per output row, else null
+  const float* bias;      // LayerNorm-folded projections: b + W . beta
+  const float* csum;      // column sums of the LayerNorm-folded weights (dec_kernels.hip fold_ln_kernel): non-null exactly when the projection follows a LayerNorm
+  int N, K;               // launch shape (the vocabulary projection: N = n_vocab_pad)
+  int rows;               // weight rows per workgroup tile the matrix was packed for (gemv_rows_for)
+};
 struct DecLayerW {
   float *ln1_g, *ln1_b, *ln2_g, *ln2_b, *ln3_g, *ln3_b;
-  f16 *p_qkv, *p_out, *p_cq, *p_cout, *p_f1, *p_f2;   // MFMA-fragment packed
-  f16 *w_ckv;                                        // row-major [2d][d] (encoder-side GEMM)
-  float *b_qkv, *b_out, *b_cq, *b_ckv, *b_cout, *b_f1, *b_f2;
-  float *s_qkv = nullptr, *s_out = nullptr, *s_cq = nullptr, *s_cout = nullptr, *s_f1 = nullptr, *s_f2 = nullptr;   // int8_float16: row scales
-  float *c_qkv = nullptr, *c_cq = nullptr, *c_f1 = nullptr;   // column sums of the LayerNorm-folded weights (dec_kernels.hip fold_ln_kernel)
-  f16* p_cqo = nullptr; float* b_cqo = nullptr;               // cross-Q folded THROUGH the out-projection: packed [W'q | W'q Wo] ([d][2d]) and W'q bo (fused_out_cq)
+  DecProj qkv, out, cq, cout, f1, f2;
+  DecProj cqo;                                       // cross-Q folded THROUGH the out-projection: packed [W'q | W'q Wo] ([d][2d]) and W'q bo (out_cq_dual / out_cq_frag3)
+  f16* w_ckv; float* b_ckv;                          // row-major [2d][d] (encoder-side GEMM)
+  // the six matrices a decode step streams per layer, in step order
+  std::array<const DecProj*, 6> streamed() const { return {&qkv, &out, &cq, &cout, &f1, &f2}; }
 };
 
 struct GraphKey {
@@ -191,7 +200,8 @@ struct wis_model {
   f16 *w_conv1, *w_conv2; float *b_conv1, *b_conv2, *enc_pos, *enc_ln_g, *enc_ln_b;
   std::vector<EncLayerW> enc;
   std::vector<DecLayerW> dec;
-  f16 *emb, *dec_pos, *p_proj; float *dec_ln_g, *dec_ln_b;
+  f16 *emb, *dec_pos; float *dec_ln_g, *dec_ln_b;
+  DecProj proj;                 // the tied vocabulary projection behind the final LayerNorm (N = n_vocab_pad; it has no bias of its own: bias = W . beta)
   float *bias_all, *bias_begin; int* d_lang_ids;
   int n_vocab_pad;
   // activations
@@ -234,8 +244,6 @@ struct wis_model {
   wis_timing_t timing;
   std::map<GraphKey, hipGraphExec_t> graphs;
   bool use_graph;
-  float* s_proj = nullptr;      // int8_float16: row scales of the vocabulary projection
-  float* c_proj = nullptr; float* b_proj = nullptr;   // LayerNorm-folded vocabulary projection: column sums, W . beta
   bool w8 = false;              // decoder weights stored as 8-bit packed fragments
   bool cq_fold = false;         // f16 decoder weights: the fused out-projection + cross-Q stage is available (p_cqo)
   f16* dxh = nullptr;           // f16 row-major copy of the layer input rows (written by the embedding / FFN2 epilogues)
@@ -314,33 +322,45 @@ int to_f16_mat(wis_model* m, const Loader& L, const std::string& name, int64_t r
   hipLaunchKernelGGL(convert_kernel, dim3(blocks_for(rows * cols)), dim3(256), 0, m->st, s.p, s.f16, *out, 1, rows, cols, cols, n_scale, scale);
   return WIS_OK;
 }
-// row-major source -> MFMA-fragment packed (through a temporary f16 image)
-// ln_gamma / ln_beta (device, fp32 [K]) != nullptr: the projection follows a LayerNorm - fold it (fold_ln_kernel): `bias`
-// (device fp32, >= N entries, already loaded) receives W . beta, *csum_out the column sums of the folded weights.
-int to_packed(wis_model* m, const Loader& L, const std::string& name, int N, int K, f16** out, f16* tmp, int n_scale = 0, float scale = 1.f, int* npad_out = nullptr,
-              float** scale_out = nullptr, const float* ln_gamma = nullptr, const float* ln_beta = nullptr, float* bias = nullptr, float** csum_out = nullptr) {
+// W (f16 [N][K] row-major staging) -> what the skinny GEMMs stream, on the caller's buffers (loader and op taps).  gamma given: fold that LayerNorm
+// (fold_ln_kernel rewrites W; `bias`, loaded, receives W . beta; `csum`, zeroed, the column sums).  out: the f16 fragment image - or, with scale_out, the
+// 8-bit image + row scales, the column sums retaken from what the MFMA will see; null: fold only.  Rows [0, n_scale) (the query part) are scaled by `scale`.
+int prep_projection(hipStream_t st, f16* W, int N, int Npad, int K, int n_scale, float scale, const float* gamma, const float* beta, float* bias, float* csum,
+                    void* out, float* scale_out, int rows) {
+  if (gamma) {
+    if (!bias || !csum) { set_error("prep_projection: LayerNorm folding needs a bias vector and a column-sum output"); return WIS_E_ARG; }
+    WIS_RET(launch_fold_ln(st, W, gamma, beta, bias, csum, N, K, n_scale, scale));
+  }
+  if (!out) return WIS_OK;
+  if (!scale_out) return launch_pack_gemv(st, W, static_cast<f16*>(out), N, Npad, K, n_scale, scale, rows);
+  WIS_RET(launch_pack_gemv8(st, W, static_cast<unsigned char*>(out), scale_out, N, Npad, K, n_scale, scale));
+  if (gamma) WIS_RET(launch_csum8(st, W, scale_out, csum, N, K, n_scale, scale));
+  return WIS_OK;
+}
+// checkpoint matrix -> packed projection through the f16 image `tmp` (build_cq_fold reads the folded weights there); allocations in slab order: column
+// sums, then the 8-bit image and its scales or the f16 image.  out->N is the logical N; *npad_out the packed image's rows
+int to_packed(wis_model* m, const Loader& L, const std::string& name, int N, int K, f16* tmp, int n_scale, float scale, const float* ln_gamma, const float* ln_beta,
+              float* bias, DecProj* out, int* npad_out = nullptr) {
   TensorSrc s; WIS_RET(L.get(name, N, K, &s));
   const int rows = gemv_rows_for(N, K);
   const int Npad = cdiv(N, rows) * rows;
   hipLaunchKernelGGL(convert_kernel, dim3(blocks_for((int64_t)N * K)), dim3(256), 0, m->st, s.p, s.f16, tmp, 1, (int64_t)N, (int64_t)K, (int64_t)K, (int64_t)0, 1.f);
-  if (ln_gamma) {
-    if (!bias || !csum_out) { set_error("to_packed: LayerNorm folding needs a bias vector and a column-sum output"); return WIS_E_ARG; }
-    WIS_RET(dalloc(m, csum_out, (size_t)Npad));
-    WIS_HIP_CHECK(hipMemsetAsync(*csum_out, 0, (size_t)Npad * 4, m->st));
-    WIS_RET(launch_fold_ln(m->st, tmp, ln_gamma, ln_beta, bias, *csum_out, N, K, n_scale, scale));
-  }
-  if (m->w8 && scale_out) {       // 8-bit fragments + per-row dequantisation scales (the query scaling is folded into the scales)
-    unsigned char* q8 = nullptr;
-    WIS_RET(dalloc(m, &q8, (size_t)Npad * K));
-    WIS_RET(dalloc(m, scale_out, (size_t)Npad));
-    WIS_RET(launch_pack_gemv8(m->st, tmp, q8, *scale_out, N, Npad, K, n_scale, scale));
-    if (ln_gamma) WIS_RET(launch_csum8(m->st, tmp, *scale_out, *csum_out, N, K, n_scale, scale));   // sums of what the MFMA will really see
-    *out = reinterpret_cast<f16*>(q8);
-  } else {
-    WIS_RET(dalloc(m, out, (size_t)Npad * K));
-    WIS_RET(launch_pack_gemv(m->st, tmp, *out, N, Npad, K, n_scale, scale, rows));
-  }
+  float *csum = nullptr, *wscale = nullptr; f16* wp = nullptr;
+  if (ln_gamma) { WIS_RET(dalloc(m, &csum, (size_t)Npad)); WIS_HIP_CHECK(hipMemsetAsync(csum, 0, (size_t)Npad * 4, m->st)); }
+  if (m->w8) { unsigned char* q8 = nullptr; WIS_RET(dalloc(m, &q8, (size_t)Npad * K)); WIS_RET(dalloc(m, &wscale, (size_t)Npad)); wp = reinterpret_cast<f16*>(q8); }
+  else WIS_RET(dalloc(m, &wp, (size_t)Npad * K));
+  WIS_RET(prep_projection(m->st, tmp, N, Npad, K, n_scale, scale, ln_gamma, ln_beta, bias, csum, wp, wscale, rows));
+  *out = DecProj{wp, wscale, bias, csum, N, K, rows};
   if (npad_out) *npad_out = Npad;
+  return WIS_OK;
+}
+// `name`/weight + `name`/bias of the checkpoint as a DecProj.  A LayerNorm-folded projection converts its bias first (the fold adds W . beta to it), the
+// others the matrix first: that is the order of the allocations, i.e. the slab layout (SLAB_BYTES) - keep it.
+int load_proj(wis_model* m, const Loader& L, const std::string& name, int N, int K, f16* tmp, int n_scale, float scale, const float* ln_gamma, const float* ln_beta, DecProj* out) {
+  float* bias = nullptr;
+  if (ln_gamma) WIS_RET(to_f32(m, L, name + "/bias", N, &bias, n_scale, scale));
+  WIS_RET(to_packed(m, L, name + "/weight", N, K, tmp, n_scale, scale, ln_gamma, ln_beta, bias, out));
+  if (!ln_gamma) { WIS_RET(to_f32(m, L, name + "/bias", N, &bias, n_scale, scale)); out->bias = bias; }
   return WIS_OK;
 }
 
@@ -434,9 +454,11 @@ int load_weights(wis_model* m, const Loader& L) {
     if ((rc = to_f32(m, L, "decoder/layer_norm/beta", d, &m->dec_ln_b))) break;
     // every projection that follows a LayerNorm is stored LayerNorm-folded (W o gamma, bias + W . beta, column sums): the final
     // LayerNorm into the tied vocabulary projection (which has no bias of its own) ...
-    if ((rc = dalloc(m, &m->b_proj, (size_t)V + 64))) break;
-    if (hipMemsetAsync(m->b_proj, 0, ((size_t)V + 64) * 4, m->st) != hipSuccess) { set_error("memset failed"); rc = WIS_E_HIP; break; }
-    if ((rc = to_packed(m, L, "decoder/embeddings/weight", V, d, &m->p_proj, tmp, 0, 1.f, &m->n_vocab_pad, &m->s_proj, m->dec_ln_g, m->dec_ln_b, m->b_proj, &m->c_proj))) break;
+    float* b_proj = nullptr;
+    if ((rc = dalloc(m, &b_proj, (size_t)V + 64))) break;
+    if (hipMemsetAsync(b_proj, 0, ((size_t)V + 64) * 4, m->st) != hipSuccess) { set_error("memset failed"); rc = WIS_E_HIP; break; }
+    if ((rc = to_packed(m, L, "decoder/embeddings/weight", V, d, tmp, 0, 1.f, m->dec_ln_g, m->dec_ln_b, b_proj, &m->proj, &m->n_vocab_pad))) break;
+    m->proj.N = m->n_vocab_pad;      // launched over the padded vocabulary
     m->dec.resize(c.n_dec_layers);
     if ((rc = dalloc(m, &m->w_ckv_all, (size_t)c.n_dec_layers * 2 * d * d))) break;      // one [L * 2d][d] matrix: a single GEMM projects every layer
     if ((rc = dalloc(m, &m->b_ckv_all, (size_t)c.n_dec_layers * 2 * d))) break;
@@ -445,37 +467,33 @@ int load_weights(wis_model* m, const Loader& L) {
       DecLayerW& w = m->dec[l];
       if ((rc = to_f32(m, L, p + "self_attention/layer_norm/gamma", d, &w.ln1_g))) break;
       if ((rc = to_f32(m, L, p + "self_attention/layer_norm/beta", d, &w.ln1_b))) break;
-      // ... and ln1 -> QKV, ln2 -> cross-Q, ln3 -> FFN1 of every layer (bias first: the fold adds W . beta to it)
-      if ((rc = to_f32(m, L, p + "self_attention/linear_0/bias", 3 * d, &w.b_qkv, d, qs))) break;
-      if ((rc = to_packed(m, L, p + "self_attention/linear_0/weight", 3 * d, d, &w.p_qkv, tmp, d, qs, nullptr, &w.s_qkv, w.ln1_g, w.ln1_b, w.b_qkv, &w.c_qkv))) break;
-      if ((rc = to_packed(m, L, p + "self_attention/linear_1/weight", d, d, &w.p_out, tmp, 0, 1.f, nullptr, &w.s_out))) break;
-      if ((rc = to_f32(m, L, p + "self_attention/linear_1/bias", d, &w.b_out))) break;
+      // ... and ln1 -> QKV, ln2 -> cross-Q, ln3 -> FFN1 of every layer
+      if ((rc = load_proj(m, L, p + "self_attention/linear_0", 3 * d, d, tmp, d, qs, w.ln1_g, w.ln1_b, &w.qkv))) break;
+      if ((rc = load_proj(m, L, p + "self_attention/linear_1", d, d, tmp, 0, 1.f, nullptr, nullptr, &w.out))) break;
       if ((rc = to_f32(m, L, p + "attention/layer_norm/gamma", d, &w.ln2_g))) break;
       if ((rc = to_f32(m, L, p + "attention/layer_norm/beta", d, &w.ln2_b))) break;
-      if ((rc = to_f32(m, L, p + "attention/linear_0/bias", d, &w.b_cq, d, qs))) break;
-      if ((rc = to_packed(m, L, p + "attention/linear_0/weight", d, d, &w.p_cq, tmp, d, qs, nullptr, &w.s_cq, w.ln2_g, w.ln2_b, w.b_cq, &w.c_cq))) break;
+      if ((rc = load_proj(m, L, p + "attention/linear_0", d, d, tmp, d, qs, w.ln2_g, w.ln2_b, &w.cq))) break;
       if (m->cq_fold) {
         // Cross-attention query folded through the self-attention output projection (one dependent stage less per layer):
         //   x1 = x0 + Wo a + bo,   q = rs(x1) (W'q x1 - mu(x1) c) + b'      (LayerNorm-folded form, W'q = (Wq o gamma) / 8)
         //   W'q x1 = W'q x0 + (W'q Wo) a + W'q bo  =: q_raw  - computable from the LAYER INPUT x0 and the attention output a, i.e.
         // in the same launch as the out-projection; mu / rs of x1 are applied by the cross-attention kernel (dec_kernels.hip).
-        // tmp holds f16(Wq o gamma) (to_packed above); W'q Wo is rounded to f16 like every other stored weight.
+        // tmp holds f16(Wq o gamma) (load_proj above); W'q Wo is rounded to f16 like every other stored weight.
         TensorSrc so; if ((rc = L.get(p + "self_attention/linear_1/weight", d, d, &so))) break;
-        if ((rc = dalloc(m, &w.p_cqo, (size_t)d * 2 * d))) break;
-        if ((rc = dalloc(m, &w.b_cqo, (size_t)d))) break;
-        if ((rc = build_cq_fold(m->st, tmp, so.p, so.f16, w.b_out, d, qs, fcat, fwot, fwqo, w.p_cqo, w.b_cqo))) break;
+        f16* p_cqo = nullptr; float* b_cqo = nullptr;
+        if ((rc = dalloc(m, &p_cqo, (size_t)d * 2 * d))) break;
+        if ((rc = dalloc(m, &b_cqo, (size_t)d))) break;
+        if ((rc = build_cq_fold(m->st, tmp, so.p, so.f16, w.out.bias, d, qs, fcat, fwot, fwqo, p_cqo, b_cqo))) break;
+        w.cqo = DecProj{p_cqo, nullptr, b_cqo, nullptr, d, 2 * d, 16};
       }
       w.w_ckv = m->w_ckv_all + (size_t)l * 2 * d * d; w.b_ckv = m->b_ckv_all + (size_t)l * 2 * d;
       if ((rc = to_f16_mat(m, L, p + "attention/linear_1/weight", 2 * d, d, &w.w_ckv))) break;
       if ((rc = to_f32(m, L, p + "attention/linear_1/bias", 2 * d, &w.b_ckv))) break;
-      if ((rc = to_packed(m, L, p + "attention/linear_2/weight", d, d, &w.p_cout, tmp, 0, 1.f, nullptr, &w.s_cout))) break;
-      if ((rc = to_f32(m, L, p + "attention/linear_2/bias", d, &w.b_cout))) break;
+      if ((rc = load_proj(m, L, p + "attention/linear_2", d, d, tmp, 0, 1.f, nullptr, nullptr, &w.cout))) break;
       if ((rc = to_f32(m, L, p + "ffn/layer_norm/gamma", d, &w.ln3_g))) break;
       if ((rc = to_f32(m, L, p + "ffn/layer_norm/beta", d, &w.ln3_b))) break;
-      if ((rc = to_f32(m, L, p + "ffn/linear_0/bias", 4 * d, &w.b_f1))) break;
-      if ((rc = to_packed(m, L, p + "ffn/linear_0/weight", 4 * d, d, &w.p_f1, tmp, 0, 1.f, nullptr, &w.s_f1, w.ln3_g, w.ln3_b, w.b_f1, &w.c_f1))) break;
-      if ((rc = to_packed(m, L, p + "ffn/linear_1/weight", d, 4 * d, &w.p_f2, tmp, 0, 1.f, nullptr, &w.s_f2))) break;
-      if ((rc = to_f32(m, L, p + "ffn/linear_1/bias", d, &w.b_f2))) break;
+      if ((rc = load_proj(m, L, p + "ffn/linear_0", 4 * d, d, tmp, 0, 1.f, w.ln3_g, w.ln3_b, &w.f1))) break;
+      if ((rc = load_proj(m, L, p + "ffn/linear_1", d, 4 * d, tmp, 0, 1.f, nullptr, nullptr, &w.f2))) break;
     }
   } while (0);
   hipError_t e = hipStreamSynchronize(m->st);
@@ -766,6 +784,43 @@ static int spin_gave_up(wis_model* m, bool* gave_up) {
 // window position w0), cross-attention as B = M / 16 groups of R = 16 rows that all read utterance 0's K / V
 struct TreeWin { const int* anc; int w0, aw; const int* base = nullptr; };
 int align_capture_q(wis_model* m, int l, int M);      // align.hip
+
+// ---- the step's projection stages: the ONLY places that assemble a GemvP from a projection (both forwards, the weight-stream tap, the op taps); raw
+// operand pointers, so a tap passes its own scratch; every member they do not name stays zero.  launch_gemv (<= 8 rows): x fp32 under GV_LN, else f16
+static GemvP gemv_small(const DecProj& p, const void* x, void* y, int M, int flags) {
+  GemvP g; memset(&g, 0, sizeof(g));
+  g.x = x; g.csum = p.csum; g.Wp = p.Wp; g.wscale = p.scale; g.bias = p.bias; g.y = y; g.M = M; g.N = p.N; g.K = p.K; g.flags = flags; g.rows = p.rows;
+  return g;
+}
+// launch_gemv_frag (batched rows) on the rows' fragment image; the caller adds the stage's own: output, statistics, QKV cache members, prof, FFN2's K split
+static GemvP gemv_frag(const DecProj& p, const void* xf, int M, int flags) {
+  GemvP g; memset(&g, 0, sizeof(g));
+  g.x = xf; g.csum = p.csum; g.Wp = p.Wp; g.wscale = p.scale; g.bias = p.bias; g.M = M; g.N = p.N; g.K = p.K; g.flags = flags; g.xmb = cdiv(M, 16); g.rows = 16;
+  return g;
+}
+// The fused out-projection + cross-Q stage (cq_fold; w.cqo = packed [W'q | W'q Wo], W'q bo), <= 8 rows, ONE launch_gemv_dual (which sets `rows`):
+//   ga: x1 = x0 + Wo a + bo in place, x1's LayerNorm partials to `stat` (the cross-attention's prologue merges them: decode step 1.352 -> 1.330 ms)
+//   gb: q_raw = W'q x0 + (W'q Wo) a + W'q bo from the f16 layer input xh and the attention output a; the cross-attention kernel applies rs, mu of x1 and b'
+static void out_cq_dual(const DecLayerW& w, const f16* a, const f16* xh, float* x1, float* stat, float* q, int M, GemvP* ga, GemvP* gb) {
+  const int d = w.out.K;
+  memset(ga, 0, sizeof(*ga));
+  ga->x = a; ga->Wp = w.out.Wp; ga->bias = w.out.bias; ga->y = x1; ga->M = M; ga->N = d; ga->K = d; ga->flags = GV_RESID; ga->stat_out = stat;
+  memset(gb, 0, sizeof(*gb));
+  gb->x = xh; gb->x2 = a; gb->xsplit = d; gb->Wp = w.cqo.Wp; gb->bias = w.cqo.bias; gb->y = q; gb->M = M; gb->N = d; gb->K = w.cqo.K; gb->flags = GV_OUT_F32;
+}
+// The same stage on batched rows, ONE launch_gemv_frag3 of three d x d problems: x1 = x0 + Wo a + bo (+ partials; x1's fragment image has no reader, so
+// x0's image xf stays valid), q = W'q x0 + W'q bo and q2 = (W'q Wo) a - the two k-step halves of w.cqo.  The cross-attention kernel finishes
+// q = rs (q + q2 - mu c) + b': the folded cross-Q projection as a launch of its own (6.4 us per layer at 8 utterances) is gone.
+static void out_cq_frag3(const DecLayerW& w, const f16* af, const f16* xf, float* x1, float* stat, float* q, float* q2, int M, GemvP g3[3]) {
+  const int d = w.out.K;
+  g3[0] = gemv_frag(w.out, af, M, GV_RESID);
+  g3[0].wscale = nullptr; g3[0].y = x1; g3[0].ymb = g3[0].xmb; g3[0].stat_out = stat;
+  g3[1] = gemv_frag(w.cqo, xf, M, GV_OUT_F32);
+  g3[1].K = d; g3[1].y = q; g3[1].wks = w.cqo.K / 32; g3[1].wk0 = 0;
+  g3[2] = gemv_frag(w.cqo, af, M, GV_OUT_F32);
+  g3[2].K = d; g3[2].bias = nullptr; g3[2].y = q2; g3[2].wks = w.cqo.K / 32; g3[2].wk0 = d / 32;
+}
+
 static int dec_forward_frag(wis_model* m, int M, int R, int B, bool want_logits, int sstride, int rmul, int chunks, const TreeWin* tw = nullptr) {
   const wis_config_t& c = m->cfg; hipStream_t st = m->st;
   const int d = c.d_model, H = c.n_heads, T = c.n_audio_ctx, ctx = c.n_text_ctx, MB = cdiv(M, 16);
@@ -775,69 +830,79 @@ static int dec_forward_frag(wis_model* m, int M, int R, int B, bool want_logits,
   // statistics prologue); WIS_NO_FRAG_FOLD=1 keeps the two-launch form (A/B switch)
   static const bool no_frag_fold = getenv("WIS_NO_FRAG_FOLD") != nullptr;
   const bool fold = m->cq_fold && !no_frag_fold && R <= 8;
-  auto base = [&](const void* x, const f16* Wp, const float* wscale, const float* bias, int N, int K, int flags) {
-    GemvP g; memset(&g, 0, sizeof(g));
-    g.x = x; g.Wp = Wp; g.wscale = wscale; g.bias = bias; g.M = M; g.N = N; g.K = K; g.flags = flags; g.xmb = MB; g.rows = 16;
-    return g;
-  };
+  // what every layer's attention launches share; the layer adds its caches / K, V images (and its stamp row)
+  SelfAttnP sa;
+  sa.q = m->dq; sa.pos = m->rm.pos; sa.out = m->daoxf; sa.M = M; sa.H = H; sa.d = d; sa.ctx = ctx; sa.rpu = R; sa.sstride = sstride; sa.rmul = rmul; sa.out_mb = MB; sa.nb = m->sa_nb;
+  if (tw) { sa.anc = tw->anc; sa.w0 = tw->w0; sa.aw = tw->aw; sa.base = tw->base; }
+  CrossAttnP ca;
+  ca.q = m->dq; ca.out = m->daoxf; ca.part = m->part; ca.counters = m->counters; ca.B = B; ca.R = R; ca.H = H; ca.d = d; ca.T = T; ca.Tpad = m->Tpad; ca.chunks = chunks; ca.out_mb = MB;
+  ca.epoch = m->ca_epoch;
   for (int l = 0; l < c.n_dec_layers; ++l) {
     const DecLayerW& w = m->dec[l];
     // (tap builds: stamp rows of layer 0's kernels, same row numbering as dec_forward: 0 QKV, 1 self-attn, 2 out-proj (+ q halves), 4 cross-attn,
     // 5 cross-out, 6 FFN1, 7 FFN2)
     unsigned long long* pr = (m->prof_on && l == 0) ? m->d_prof : nullptr;
-    GemvP g = base(m->dxf, w.p_qkv, w.s_qkv, w.b_qkv, 3 * d, d, GV_LN | GV_QKV);
-    g.csum = w.c_qkv; g.stat_in = m->dstat; g.q = m->dq; g.kc = m->kc[l]; g.vc = m->vc[l]; g.slot = m->rm.slot; g.pos = m->rm.pos; g.d = d; g.ctx = ctx;
+    GemvP g = gemv_frag(w.qkv, m->dxf, M, GV_LN | GV_QKV);
+    g.stat_in = m->dstat; g.q = m->dq; g.kc = m->kc[l]; g.vc = m->vc[l]; g.slot = m->rm.slot; g.pos = m->rm.pos; g.d = d; g.ctx = ctx;
     g.prof = pr;
     WIS_RET(launch_gemv_frag(st, g));
-    WIS_RET(launch_dec_self_attn(st, m->dq, m->kc[l], m->vc[l], m->rm.pos, m->daoxf, M, H, d, ctx, R, sstride, rmul, nullptr, MB, tw ? tw->anc : nullptr, tw ? tw->w0 : 0, tw ? tw->aw : 0, tw ? tw->base : nullptr, m->sa_nb));
+    sa.kc = m->kc[l]; sa.vc = m->vc[l];
+    WIS_RET(launch_dec_self_attn(st, sa));
     if (fold) {
       if (m->al.capture) { set_error("dec_forward_frag: an alignment pass needs the un-folded route (more than 8 rows per utterance)"); return WIS_E_STATE; }
-      // ONE launch, three d x d problems on 3 d / 16 workgroups: x1 = x0 + Wo a + bo (residual rows + their LayerNorm partials; nobody
-      // reads x1's fragment image any more, so none is written and x0's image stays valid for the other two), q_A = W'q x0 + W'q bo
-      // from the layer input's image, q_B = (W'q Wo) a from the attention output's - the two k-step halves of the packed [W'q | W'q Wo]
-      // matrix of the one-utterance step (load_weights: p_cqo).  The cross-attention kernel adds the halves and finishes
-      // q = rs (q_A + q_B - mu c) + b' with mu / rs merged from x1's partials: the LayerNorm-folded cross-Q projection as a launch of
-      // its own (6.4 us per layer at 8 utterances) is gone.
       GemvP g3[3];
-      g3[0] = base(m->daoxf, w.p_out, nullptr, w.b_out, d, d, GV_RESID);
-      g3[0].y = m->dx; g3[0].ymb = MB; g3[0].stat_out = m->dstat; g3[0].prof = pr ? pr + 32 : nullptr;
-      g3[1] = base(m->dxf, w.p_cqo, nullptr, w.b_cqo, d, d, GV_OUT_F32);
-      g3[1].y = m->dq; g3[1].wks = 2 * d / 32; g3[1].wk0 = 0;
-      g3[2] = base(m->daoxf, w.p_cqo, nullptr, nullptr, d, d, GV_OUT_F32);
-      g3[2].y = m->dq2; g3[2].wks = 2 * d / 32; g3[2].wk0 = d / 32;
+      out_cq_frag3(w, m->daoxf, m->dxf, m->dx, m->dstat, m->dq, m->dq2, M, g3);
+      g3[0].prof = pr ? pr + 32 : nullptr;
       WIS_RET(launch_gemv_frag3(st, g3, 3));
-      WIS_RET(launch_dec_cross_attn(st, m->dq, m->kx[l], m->vx[l], m->daoxf, m->part, m->counters, B, R, H, d, T, m->Tpad, chunks, pr ? pr + 64 : nullptr, MB, m->dstat, w.c_cq, w.b_cq,
-                                    m->spin_now ? m->ca_gran : nullptr, m->ca_epoch, m->dq2, 1));
+      CrossAttnP cf = ca;      // the batched fold: q = q + q2, statistics from x1's row partials
+      cf.kx = m->kx[l]; cf.vt = m->vx[l]; cf.prof = pr ? pr + 64 : nullptr; cf.xres = m->dstat; cf.qcs = w.cq.csum; cf.qb = w.cq.bias;
+      cf.gran = m->spin_now ? m->ca_gran : nullptr; cf.q2 = m->dq2; cf.xres_is_stat = 1;
+      WIS_RET(launch_dec_cross_attn(st, cf));
     } else {
-    g = base(m->daoxf, w.p_out, w.s_out, w.b_out, d, d, GV_RESID);
+    g = gemv_frag(w.out, m->daoxf, M, GV_RESID);
     g.y = m->dx; g.y_xf = m->dxf; g.ymb = MB; g.stat_out = m->dstat;
     WIS_RET(launch_gemv_frag(st, g));
-    g = base(m->dxf, w.p_cq, w.s_cq, w.b_cq, d, d, GV_LN | GV_OUT_F32);
-    g.csum = w.c_cq; g.stat_in = m->dstat; g.y = m->dq;
+    g = gemv_frag(w.cq, m->dxf, M, GV_LN | GV_OUT_F32);
+    g.stat_in = m->dstat; g.y = m->dq;
     WIS_RET(launch_gemv_frag(st, g));
     // (wis_align decodes a batch in groups of utterances: the group's first utterance picks the K / V block the rows' b = 0 reads; 0 otherwise)
     const size_t ku = (size_t)m->al.kv_ub0 * H * T * 64, vu = (size_t)m->al.kv_ub0 * H * 64 * m->Tpad;
-    WIS_RET(launch_dec_cross_attn(st, m->dq, m->kx[l] + ku, m->vx[l] + vu, m->daoxf, m->part, m->counters, B, R, H, d, T, m->Tpad, chunks, nullptr, MB, nullptr, nullptr, nullptr,
-                                  (m->spin_now && !tw) ? m->ca_gran : nullptr, m->ca_epoch, nullptr, 0, tw ? 1 : 0));
+    CrossAttnP cp = ca;
+    cp.kx = m->kx[l] + ku; cp.vt = m->vx[l] + vu; cp.gran = (m->spin_now && !tw) ? m->ca_gran : nullptr; cp.kv_shared = tw ? 1 : 0;
+    WIS_RET(launch_dec_cross_attn(st, cp));
     if (m->al.capture) WIS_RET(align_capture_q(m, l, M));      // wis_align: m->dq holds this layer's finished cross-Q until the next layer's QKV projection
     }
-    g = base(m->daoxf, w.p_cout, w.s_cout, w.b_cout, d, d, GV_RESID);
+    g = gemv_frag(w.cout, m->daoxf, M, GV_RESID);
     g.y = m->dx; g.y_xf = m->dxf; g.ymb = MB; g.stat_out = m->dstat; g.prof = pr ? pr + 80 : nullptr;
     WIS_RET(launch_gemv_frag(st, g));
-    g = base(m->dxf, w.p_f1, w.s_f1, w.b_f1, 4 * d, d, GV_LN | GV_GELU);
-    g.csum = w.c_f1; g.stat_in = m->dstat; g.y = m->dhxf; g.ymb = MB; g.prof = pr ? pr + 96 : nullptr;
+    g = gemv_frag(w.f1, m->dxf, M, GV_LN | GV_GELU);
+    g.stat_in = m->dstat; g.y = m->dhxf; g.ymb = MB; g.prof = pr ? pr + 96 : nullptr;
     WIS_RET(launch_gemv_frag(st, g));
-    g = base(m->dhxf, w.p_f2, w.s_f2, w.b_f2, d, 4 * d, GV_RESID);
+    g = gemv_frag(w.f2, m->dhxf, M, GV_RESID);
     g.y = m->dx; g.y_xf = m->dxf; g.ymb = MB; g.stat_out = m->dstat; g.prof = pr ? pr + 112 : nullptr;
     if (m->gf_ksplit > 1 && (4 * d / 32) % (4 * m->gf_ksplit) == 0) { g.ksplit = m->gf_ksplit; g.kpart = m->gf_part; g.kcnt = m->gf_cnt; }      // K = 4d over `ksplit` workgroups per n-tile
     WIS_RET(launch_gemv_frag(st, g));
   }
   if (want_logits) {
-    GemvP g = base(m->dxf, m->p_proj, m->s_proj, m->b_proj, m->n_vocab_pad, d, GV_LN | GV_OUT_F32);
-    g.csum = m->c_proj; g.stat_in = m->dstat; g.y = m->logits;
+    GemvP g = gemv_frag(m->proj, m->dxf, M, GV_LN | GV_OUT_F32);
+    g.stat_in = m->dstat; g.y = m->logits;
     WIS_RET(launch_gemv_frag(st, g));
   }
   return WIS_OK;
+}
+
+// The route of a pass of M rows without a tree window (dec_forward; wis_bench_weight_stream streams every matrix alone by the same choice):
+//   frag   more than 8 rows: dec_forward_frag.  The other two describe the <= 8-row step:
+//   fold   the fused out-projection + cross-Q stage (cq_fold: f16 decoder weights)
+//   ln16   WIS_B1_LN=f16 (off by default: statistics of rounded rows cost parity at large-v2): the LayerNorm-folded projections (QKV,
+//          FFN1, the vocabulary) read the f16 copy of the rows their producers leave (GV_LN16, 12.8 KB against 25.6 KB at five rows) and take the statistics
+//          from it.  (Statistics from the producers' per-16-column partials measured slower, 1.357 against 1.345 ms per step.)
+struct StepRoute { bool frag, fold, ln16; };
+static StepRoute small_route(const wis_model* m, int M) {
+  static const bool ln_f16 = [] { const char* e = getenv("WIS_B1_LN"); return e && !strcmp(e, "f16"); }();
+  const int d = m->cfg.d_model;
+  const bool frag = M > 8, ln_ok = !frag && m->cq_fold && d % 64 == 0 && M * (d / 8) <= 13 * 256;
+  return {frag, m->cq_fold, ln_ok && ln_f16 && d <= 2048};
 }
 
 // The step of <= 8 rows: LDS-staged skinny GEMMs (launch_gemv) with the LayerNorm folded into their prologue; more rows and tree windows take
@@ -849,85 +914,63 @@ int dec_forward(wis_model* m, int M, int R, int B, bool want_logits, int sstride
   static const int env_chunks = getenv("WIS_CROSS_CHUNKS") ? atoi(getenv("WIS_CROSS_CHUNKS")) : 0;
   // 256-key chunks (6 per utterance-head): measured faster than 128-key chunks at every batch size (fewer partials to publish and combine)
   const int chunks = env_chunks ? env_chunks : 6;
-  if (tw) return dec_forward_frag(m, M, R, B, want_logits, sstride, rmul, chunks, tw);
-  if (M > 8) return dec_forward_frag(m, M, R, B, want_logits, sstride, rmul, chunks);
+  const StepRoute rt = small_route(m, M);
+  if (tw || rt.frag) return dec_forward_frag(m, M, R, B, want_logits, sstride, rmul, chunks, tw);
   if (m->al.capture) { set_error("wis_align needs the batched-row decoder route (more than 8 rows per pass)"); return WIS_E_STATE; }
-  // fused out-proj + cross-Q stage (load_weights: cq_fold): f16 decoder weights
-  const bool fold = m->cq_fold;
-  // (r5) what the LayerNorm-folded projections (QKV, FFN1, the vocabulary) read - WIS_B1_LN = rows | f16:
-  //   rows      (default) the fp32 rows (25.6 KB per workgroup at five rows), statistics in all four waves behind the weight stream: rounds 2-5
-  //   f16       (off: the statistics of rounded rows cost parity at large-v2) the f16 copy of the rows (GV_LN16: 12.8 KB) that whoever produces residual rows leaves next to them (embedding, cross-
-  //             attention output projection, FFN2), statistics from those same values, still in all four waves - a third of a launch's
-  //             requests through the CU's address path gone, nothing added to its tail
-  //   (statistics from per-16-column partials of the producers' epilogues instead measured slower, 1.357 against 1.345 ms per step: the merge sits in the
-  //   one epilogue wave BEHIND the reduction barrier)
-  static const bool ln_f16 = [] { const char* e = getenv("WIS_B1_LN"); return e && !strcmp(e, "f16"); }();
-  const bool ln_ok = fold && d % 64 == 0 && M * (d / 8) <= 13 * 256;
-  const bool ln16 = ln_ok && ln_f16 && d <= 2048;
+  const bool fold = rt.fold, ln16 = rt.ln16;
+  // the LayerNorm-folded projections: the fp32 rows, or their f16 copy `x16`
+  const int ln = ln16 ? GV_LN16 : GV_LN;
+  auto ln_x = [&](const f16* x16) { return ln16 ? (const void*)x16 : (const void*)m->dx; };
   WIS_RET(launch_dec_embed(st, m->emb, m->dec_pos, m->rm.tok, m->rm.pos, m->dx, M, d, fold ? m->dxh : nullptr));
+  SelfAttnP sa;
+  sa.q = m->dq; sa.pos = m->rm.pos; sa.out = m->dao; sa.M = M; sa.H = H; sa.d = d; sa.ctx = ctx; sa.rpu = R; sa.sstride = sstride; sa.rmul = rmul; sa.nb = m->sa_nb;
+  CrossAttnP ca;
+  ca.q = m->dq; ca.out = m->dao; ca.part = m->part; ca.counters = m->counters; ca.B = B; ca.R = R; ca.H = H; ca.d = d; ca.T = T; ca.Tpad = m->Tpad; ca.chunks = chunks;
+  ca.gran = m->spin_now ? m->ca_gran : nullptr; ca.epoch = m->ca_epoch;
   for (int l = 0; l < c.n_dec_layers; ++l) {
     const DecLayerW& w = m->dec[l];
     // stamp rows of this layer's 8 kernels: QKV, self-attn, out, cross-Q, cross-attn, cross-out, FFN1, FFN2
     unsigned long long* pr = (m->prof_on && (l == 0 || m->prof_all)) ? m->d_prof + (size_t)l * 8 * 16 : nullptr;
-    GemvP g; memset(&g, 0, sizeof(g));
     // self-attention block
-    g.x = m->dx; g.csum = w.c_qkv; g.Wp = w.p_qkv; g.wscale = w.s_qkv; g.bias = w.b_qkv; g.M = M; g.N = 3 * d; g.K = d;
-    g.flags = GV_LN | GV_QKV; g.q = m->dq; g.kc = m->kc[l]; g.vc = m->vc[l]; g.slot = m->rm.slot; g.pos = m->rm.pos; g.d = d; g.ctx = ctx;
+    GemvP g = gemv_small(w.qkv, ln_x(m->dxh), nullptr, M, ln | GV_QKV);
+    g.q = m->dq; g.kc = m->kc[l]; g.vc = m->vc[l]; g.slot = m->rm.slot; g.pos = m->rm.pos; g.d = d; g.ctx = ctx;
     g.prof = pr;
-    if (ln16) { g.x = m->dxh; g.flags = GV_LN16 | GV_QKV; }
-    g.rows = gemv_rows_for(g.N == m->n_vocab_pad ? m->cfg.n_vocab : g.N, g.K);
     WIS_RET(launch_gemv(st, g));
-    WIS_RET(launch_dec_self_attn(st, m->dq, m->kc[l], m->vc[l], m->rm.pos, m->dao, M, H, d, ctx, R, sstride, rmul, pr ? pr + 16 : nullptr, 0, nullptr, 0, 0, nullptr, m->sa_nb));
+    sa.kc = m->kc[l]; sa.vc = m->vc[l]; sa.prof = pr ? pr + 16 : nullptr;
+    WIS_RET(launch_dec_self_attn(st, sa));
+    ca.kx = m->kx[l]; ca.vt = m->vx[l]; ca.prof = pr ? pr + 64 : nullptr;
     if (fold) {
-      // ONE launch: x1 = x0 + Wo a + bo (tiles [0, d/16)) and q_raw = W'q x0 + (W'q Wo) a + W'q bo (the other d/16 tiles); the
-      // cross-attention kernel applies the LayerNorm statistics of x1 (rs, mu) and b' to q_raw
-      GemvP ga; memset(&ga, 0, sizeof(ga));
-      ga.x = m->dao; ga.Wp = w.p_out; ga.bias = w.b_out; ga.y = m->dx; ga.M = M; ga.N = d; ga.K = d; ga.flags = GV_RESID; ga.prof = pr ? pr + 32 : nullptr;
-      // (r5) the out-projection leaves LayerNorm partials of x1 (80 pairs per row); the cross-attention's prologue merges them instead of
-      // every one of its 120 workgroups re-reading and re-summing the five 1280-float rows (decode step 1.352 -> 1.330 ms)
-      ga.stat_out = m->dstat;
-      GemvP gb; memset(&gb, 0, sizeof(gb));
-      gb.x = m->dxh; gb.x2 = m->dao; gb.xsplit = d; gb.Wp = w.p_cqo; gb.bias = w.b_cqo; gb.y = m->dq; gb.M = M; gb.N = d; gb.K = 2 * d; gb.flags = GV_OUT_F32;
+      GemvP ga, gb;
+      out_cq_dual(w, m->dao, m->dxh, m->dx, m->dstat, m->dq, M, &ga, &gb);
+      ga.prof = pr ? pr + 32 : nullptr;
       WIS_RET(launch_gemv_dual(st, ga, gb));
-      WIS_RET(launch_dec_cross_attn(st, m->dq, m->kx[l], m->vx[l], m->dao, m->part, m->counters, B, R, H, d, T, m->Tpad, chunks, pr ? pr + 64 : nullptr, 0,
-                                    m->dstat, w.c_cq, w.b_cq, m->spin_now ? m->ca_gran : nullptr, m->ca_epoch, nullptr, 1));
+      CrossAttnP cf = ca;      // the folded query: statistics of x1 from the out-projection's row partials
+      cf.xres = m->dstat; cf.qcs = w.cq.csum; cf.qb = w.cq.bias; cf.xres_is_stat = 1;
+      WIS_RET(launch_dec_cross_attn(st, cf));
     } else {
-    memset(&g, 0, sizeof(g));
-    g.x = m->dao; g.Wp = w.p_out; g.wscale = w.s_out; g.bias = w.b_out; g.y = m->dx; g.M = M; g.N = d; g.K = d; g.flags = GV_RESID; g.prof = pr ? pr + 32 : nullptr;
-    g.rows = gemv_rows_for(g.N == m->n_vocab_pad ? m->cfg.n_vocab : g.N, g.K);
+    g = gemv_small(w.out, m->dao, m->dx, M, GV_RESID);
+    g.prof = pr ? pr + 32 : nullptr;
     WIS_RET(launch_gemv(st, g));
     // cross-attention block
-    memset(&g, 0, sizeof(g));
-    g.x = m->dx; g.csum = w.c_cq; g.Wp = w.p_cq; g.wscale = w.s_cq; g.bias = w.b_cq; g.y = m->dq; g.M = M; g.N = d; g.K = d; g.flags = GV_LN | GV_OUT_F32; g.prof = pr ? pr + 48 : nullptr;
-    g.rows = gemv_rows_for(g.N == m->n_vocab_pad ? m->cfg.n_vocab : g.N, g.K);
+    g = gemv_small(w.cq, m->dx, m->dq, M, GV_LN | GV_OUT_F32);
+    g.prof = pr ? pr + 48 : nullptr;
     WIS_RET(launch_gemv(st, g));
-    WIS_RET(launch_dec_cross_attn(st, m->dq, m->kx[l], m->vx[l], m->dao, m->part, m->counters, B, R, H, d, T, m->Tpad, chunks, pr ? pr + 64 : nullptr, 0, nullptr, nullptr, nullptr,
-                                  m->spin_now ? m->ca_gran : nullptr, m->ca_epoch));
+    WIS_RET(launch_dec_cross_attn(st, ca));
     }
-    memset(&g, 0, sizeof(g));
-    g.x = m->dao; g.Wp = w.p_cout; g.wscale = w.s_cout; g.bias = w.b_cout; g.y = m->dx; g.M = M; g.N = d; g.K = d; g.flags = GV_RESID; g.prof = pr ? pr + 80 : nullptr;
+    g = gemv_small(w.cout, m->dao, m->dx, M, GV_RESID);
+    g.prof = pr ? pr + 80 : nullptr;
     if (ln16) g.y16 = m->dln;      // FFN1's input: f16 rows
-    g.rows = gemv_rows_for(g.N == m->n_vocab_pad ? m->cfg.n_vocab : g.N, g.K);
     WIS_RET(launch_gemv(st, g));
     // FFN
-    memset(&g, 0, sizeof(g));
-    g.x = m->dx; g.csum = w.c_f1; g.Wp = w.p_f1; g.wscale = w.s_f1; g.bias = w.b_f1; g.y = m->dh; g.M = M; g.N = 4 * d; g.K = d; g.flags = GV_LN | GV_GELU; g.prof = pr ? pr + 96 : nullptr;
-    if (ln16) { g.x = m->dln; g.flags = GV_LN16 | GV_GELU; }
-    g.rows = gemv_rows_for(g.N == m->n_vocab_pad ? m->cfg.n_vocab : g.N, g.K);
+    g = gemv_small(w.f1, ln_x(m->dln), m->dh, M, ln | GV_GELU);
+    g.prof = pr ? pr + 96 : nullptr;
     WIS_RET(launch_gemv(st, g));
-    memset(&g, 0, sizeof(g));
-    g.x = m->dh; g.Wp = w.p_f2; g.wscale = w.s_f2; g.bias = w.b_f2; g.y = m->dx; g.M = M; g.N = d; g.K = 4 * d; g.flags = GV_RESID; g.prof = pr ? pr + 112 : nullptr;
+    g = gemv_small(w.f2, m->dh, m->dx, M, GV_RESID);
+    g.prof = pr ? pr + 112 : nullptr;
     g.y16 = fold ? m->dxh : nullptr;             // the next layer's x0 in f16
-    g.rows = gemv_rows_for(g.N == m->n_vocab_pad ? m->cfg.n_vocab : g.N, g.K);
     WIS_RET(launch_gemv(st, g));
   }
-  if (want_logits) {
-    GemvP g; memset(&g, 0, sizeof(g));
-    g.x = m->dx; g.csum = m->c_proj; g.bias = m->b_proj; g.Wp = m->p_proj; g.wscale = m->s_proj; g.y = m->logits; g.M = M; g.N = m->n_vocab_pad; g.K = d; g.flags = GV_LN | GV_OUT_F32;
-    if (ln16) { g.x = m->dxh; g.flags = GV_LN16 | GV_OUT_F32; }
-    g.rows = gemv_rows_for(g.N == m->n_vocab_pad ? m->cfg.n_vocab : g.N, g.K);
-    WIS_RET(launch_gemv(st, g));
-  }
+  if (want_logits) WIS_RET(launch_gemv(st, gemv_small(m->proj, ln_x(m->dxh), m->logits, M, ln | GV_OUT_F32)));
   return WIS_OK;
 }
 
@@ -1112,10 +1155,10 @@ int wis_model_clone(wis_model_t* parent, wis_model_t** out) {
   m->w_conv1 = parent->w_conv1; m->w_conv2 = parent->w_conv2; m->b_conv1 = parent->b_conv1; m->b_conv2 = parent->b_conv2;
   m->enc_pos = parent->enc_pos; m->enc_ln_g = parent->enc_ln_g; m->enc_ln_b = parent->enc_ln_b;
   m->enc = parent->enc; m->dec = parent->dec;
-  m->emb = parent->emb; m->dec_pos = parent->dec_pos; m->p_proj = parent->p_proj; m->dec_ln_g = parent->dec_ln_g; m->dec_ln_b = parent->dec_ln_b;
+  m->emb = parent->emb; m->dec_pos = parent->dec_pos; m->proj = parent->proj; m->dec_ln_g = parent->dec_ln_g; m->dec_ln_b = parent->dec_ln_b;
   m->bias_all = parent->bias_all; m->bias_begin = parent->bias_begin; m->d_lang_ids = parent->d_lang_ids; m->n_vocab_pad = parent->n_vocab_pad;
   m->w_ckv_all = parent->w_ckv_all; m->b_ckv_all = parent->b_ckv_all;
-  m->s_proj = parent->s_proj; m->c_proj = parent->c_proj; m->b_proj = parent->b_proj; m->w8 = parent->w8; m->cq_fold = parent->cq_fold;
+  m->w8 = parent->w8; m->cq_fold = parent->cq_fold;
   m->use_graph = parent->use_graph;
   m->al.heads = parent->al.heads;      // (the clone allocates its own align scratch on its first wis_align)
   memset(&m->timing, 0, sizeof(m->timing));
@@ -1224,11 +1267,10 @@ int wis_last_timing(const wis_model_t* m, wis_timing_t* t) {
   *t = m->timing; return WIS_OK;
 }
 
-// rows (b): R = 1, every row reads its own KV slot
-static int single_row_setup(wis_model* m, int B, const std::vector<int>& tok, int pos) {
-  const int ctx = m->cfg.n_text_ctx;
-  std::vector<int> ps(B, pos), slot(B), ls(B);
-  for (int r = 0; r < B; ++r) { slot[r] = r; ls[r] = r; }
+// n rows at one position, row r in KV slot r of its own (R = 1 rows of n utterances; the tuning taps' B * beam rows of token 100)
+static int single_row_setup(wis_model* m, int n, const std::vector<int>& tok, int pos) {
+  std::vector<int> ps(n, pos), slot(n), ls(n);
+  for (int r = 0; r < n; ++r) { slot[r] = r; ls[r] = r; }
   return upload_rows(m, tok, ps, slot, ls);
 }
 
@@ -1255,613 +1297,9 @@ int wis_detect_language(wis_model_t* m, const float* input, int input_kind, int 
   return WIS_OK;
 }
 
-int wis_debug_encode(wis_model_t* m, const float* input, int input_kind, int B, float* enc_out) {
-  if (!m || !input || !enc_out) { set_error("wis_debug_encode: bad argument"); return WIS_E_ARG; }
-  WIS_ENTER(m, "wis_debug_encode")
-  WIS_HIP_CHECK(hipSetDevice(m->device));
-  WIS_RET(check_batch(m, B, 1));
-  WIS_RET(stage_input(m, input, input_kind, B));
-  WIS_RET(run_encoder(m, B));
-  const int64_t n = (int64_t)B * m->cfg.n_audio_ctx * m->cfg.d_model;
-  hipLaunchKernelGGL(f16_to_f32_kernel, dim3(blocks_for(n)), dim3(256), 0, m->st, m->mem, m->x, n);   // x is free after the encoder
-  WIS_HIP_CHECK(hipMemcpyAsync(enc_out, m->x, (size_t)n * 4, hipMemcpyDeviceToHost, m->st));
-  WIS_HIP_CHECK(hipStreamSynchronize(m->st));
-  return WIS_OK;
-}
-
-int wis_debug_logits(wis_model_t* m, const float* input, int input_kind, int B, const int32_t* dec_in, int T, float* logits) {
-  if (!m || !input || !dec_in || !logits || T < 1 || T > m->cfg.n_text_ctx) { set_error("wis_debug_logits: bad argument"); return WIS_E_ARG; }
-  WIS_ENTER(m, "wis_debug_logits")
-  WIS_HIP_CHECK(hipSetDevice(m->device));
-  WIS_RET(check_batch(m, B, 1));
-  WIS_RET(stage_input(m, input, input_kind, B));
-  WIS_RET(run_encoder(m, B));
-  WIS_RET(run_cross_kv(m, B));
-  const int V = m->cfg.n_vocab;
-  for (int t = 0; t < T; ++t) {
-    std::vector<int> tok(B);
-    for (int b = 0; b < B; ++b) tok[b] = dec_in[b * T + t];
-    for (int attempt = 0; attempt < 2; ++attempt) {      // (a pass whose granule hand-off gave up is repeated in the ticket form)
-      SpinClaim claim(m, B);
-      WIS_RET(single_row_setup(m, B, tok, t));
-      WIS_RET(dec_forward(m, B, 1, B, true, 1, 0));
-      for (int b = 0; b < B; ++b)
-        WIS_HIP_CHECK(hipMemcpyAsync(logits + ((size_t)b * T + t) * V, m->logits + (size_t)b * m->n_vocab_pad, (size_t)V * 4, hipMemcpyDeviceToHost, m->st));
-      bool gave_up = false;
-      WIS_RET(spin_gave_up(m, &gave_up));
-      if (!gave_up) break;
-    }
-  }
-  return WIS_OK;
-}
-
-int wis_debug_logits_rows(wis_model_t* m, const float* input, int input_kind, int B, const int32_t* dec_in, int T, int R, float* logits) {
-  if (!m || !input || !dec_in || !logits || T < 1 || T > m->cfg.n_text_ctx || R < 1 || R > 16) { set_error("wis_debug_logits_rows: bad argument (1 <= R <= 16)"); return WIS_E_ARG; }
-  WIS_ENTER(m, "wis_debug_logits_rows")
-  WIS_HIP_CHECK(hipSetDevice(m->device));
-  WIS_RET(check_batch(m, B, 1));
-  if (B * R > MAX_ROWS) { set_error("wis_debug_logits_rows: B*R = %d exceeds %d decoder rows per pass", B * R, MAX_ROWS); return WIS_E_STATE; }
-  WIS_RET(stage_input(m, input, input_kind, B));
-  WIS_RET(run_encoder(m, B));
-  WIS_RET(run_cross_kv(m, B));
-  const int V = m->cfg.n_vocab;
-  // teacher-forced in blocks of R positions: the rows (b, i) of a pass sit at positions t0 + i of utterance b's KV slot (causal by
-  // position, like the merged prompt pass of wis_generate), so a pass has B * R rows - with B * R > 8 it takes the batched-row
-  // route (dec_forward_frag: fragment images, partial-sum LayerNorm statistics) that wis_debug_logits' one row per utterance never
-  // reaches at small B
-  for (int t0 = 0; t0 < T; t0 += R) {
-    const int rows = std::min(R, T - t0), M = B * rows;
-    std::vector<int> tok(M), pos(M), slot(M), ls(M);
-    for (int b = 0; b < B; ++b) for (int i = 0; i < rows; ++i) { const int r = b * rows + i; tok[r] = dec_in[b * T + t0 + i]; pos[r] = t0 + i; slot[r] = b; ls[r] = b; }
-    for (int r = 0; r < M; ++r) if (tok[r] < 0 || tok[r] >= V) { set_error("wis_debug_logits_rows: token %d out of range", tok[r]); return WIS_E_ARG; }
-    for (int attempt = 0; attempt < 2; ++attempt) {      // (a pass whose granule hand-off gave up is repeated in the ticket form)
-      SpinClaim claim(m, B);
-      WIS_RET(upload_rows(m, tok, pos, slot, ls));
-      WIS_RET(dec_forward(m, M, rows, B, true, 1, 0));
-      for (int b = 0; b < B; ++b) for (int i = 0; i < rows; ++i)
-        WIS_HIP_CHECK(hipMemcpyAsync(logits + ((size_t)b * T + t0 + i) * V, m->logits + (size_t)(b * rows + i) * m->n_vocab_pad, (size_t)V * 4, hipMemcpyDeviceToHost, m->st));
-      bool gave_up = false;
-      WIS_RET(spin_gave_up(m, &gave_up));
-      if (!gave_up) break;
-    }
-  }
-  return WIS_OK;
-}
-
-int wis_debug_tree_logits(wis_model_t* m, const float* input, int input_kind, const int32_t* prompt, int P, int beam,
-                          const int32_t* tok, const int32_t* org, int n_steps, float* logits) {
-  if (!m || !input || !prompt || !tok || !org || !logits || P < 1 || P > 16 || beam < 1 || beam > MAX_R || n_steps < 1 || n_steps > std::min(32, MAX_ROWS / std::max(beam, 1))) {
-    set_error("wis_debug_tree_logits: bad argument (1 <= n_steps <= min(32, %d / beam))", MAX_ROWS); return WIS_E_ARG;
-  }
-  WIS_ENTER(m, "wis_debug_tree_logits")
-  WIS_HIP_CHECK(hipSetDevice(m->device));
-  WIS_RET(check_batch(m, 1, beam));
-  const wis_config_t& c = m->cfg; hipStream_t st = m->st;
-  const int k = beam, V = c.n_vocab;
-  for (int i = 0; i < n_steps * k; ++i) if (tok[i] < 0 || tok[i] >= V || org[i] < 0 || org[i] >= k) { set_error("wis_debug_tree_logits: token / origin out of range"); return WIS_E_ARG; }
-  WIS_RET(stage_input(m, input, input_kind, 1));
-  WIS_RET(run_encoder(m, 1));
-  WIS_RET(run_cross_kv(m, 1));
-  m->spin_now = false;
-  // the prompt: rows at positions 0 .. P-1 of slot 0, then every slot gets a copy (what the first step's kv_reorder does)
-  std::vector<int> ptok(P), ppos(P), pslot(P, 0), pls(P, 0);
-  for (int i = 0; i < P; ++i) { ptok[i] = prompt[i]; ppos[i] = i; }
-  WIS_RET(upload_rows(m, ptok, ppos, pslot, pls));
-  WIS_RET(dec_forward(m, P, P, 1, false, beam, 0));
-  auto& hs = m->h_pin->tree_seed;
-  for (int j = 0; j < MAX_R; ++j) hs.parent[j] = 0;
-  hs.step = 1; hs.done = 0;
-  WIS_HIP_CHECK(hipMemcpyAsync(m->bs.parent, hs.parent, (size_t)k * 4, hipMemcpyHostToDevice, st));
-  WIS_HIP_CHECK(hipMemcpyAsync(m->bs.step_u, &hs.step, 4, hipMemcpyHostToDevice, st));
-  WIS_HIP_CHECK(hipMemcpyAsync(m->bs.done, &hs.done, 4, hipMemcpyHostToDevice, st));
-  WIS_RET(launch_kv_reorder(st, m->kc_all, m->vc_all, m->kv_layer_stride, c.n_dec_layers, m->bs, 1, beam, P, c.n_text_ctx, c.d_model));
-  // one window: steps 1 .. n_steps, rows from trajectory entries 0 .. n_steps - 1
-  std::vector<int> hd((size_t)n_steps * MAX_R * 2, 0);
-  pack_traj(hd.data(), tok, org, n_steps, k);
-  std::vector<int> wt, wp, wsl, wls;
-  int* ha = m->h_pin->anc;
-  const int Mpad = fill_tree_window(hd.data(), 1, n_steps, k, P, wt, wp, wsl, wls, ha);
-  WIS_RET(upload_rows(m, wt, wp, wsl, wls, false, &m->h_pin->win_rows));
-  WIS_HIP_CHECK(hipMemcpyAsync(m->d_anc, ha, (size_t)Mpad * ANC_W * 4, hipMemcpyHostToDevice, st));
-  const TreeWin tw{m->d_anc, P, ANC_W};
-  WIS_RET(dec_forward(m, Mpad, 16, Mpad / 16, true, 1, 0, &tw));
-  WIS_HIP_CHECK(hipMemcpy2DAsync(logits, (size_t)V * 4, m->logits, (size_t)m->n_vocab_pad * 4, (size_t)V * 4, (size_t)n_steps * k, hipMemcpyDeviceToHost, st));
-  WIS_HIP_CHECK(hipStreamSynchronize(st));
-  return WIS_OK;
-}
-
-int wis_debug_phase_cycles(wis_model_t* m, int B, int beam, int pos, uint64_t* out) {
-  if (!m || !out) { set_error("wis_debug_phase_cycles: bad argument"); return WIS_E_ARG; }
-  if (!WIS_TAPS) { set_error("tuning taps are not compiled in (rebuild with WIS_EXTRA_HIPFLAGS=-DWIS_TAPS=1)"); return WIS_E_UNSUPPORTED; }
-  WIS_ENTER(m, "wis_debug_phase_cycles")
-  WIS_HIP_CHECK(hipSetDevice(m->device));
-  WIS_RET(check_batch(m, B, beam));
-  SpinClaim claim(m, B);      // the hand-off form wis_generate would take for this batch now (and not whatever the last call left behind)
-  const int Mrows = B * beam, ctx = m->cfg.n_text_ctx;
-  if (pos < 0 || pos >= ctx) { set_error("bad pos"); return WIS_E_ARG; }
-  WIS_HIP_CHECK(hipStreamSynchronize(m->st));
-  std::vector<int> tok(Mrows, 100), ps(Mrows, pos), slot(Mrows), ls(Mrows);
-  for (int r = 0; r < Mrows; ++r) { slot[r] = r; ls[r] = r; }
-  WIS_RET(upload_rows(m, tok, ps, slot, ls));
-  WIS_HIP_CHECK(hipMemsetAsync(m->d_prof, 0, 8 * 16 * 8, m->st));
-  WIS_RET(dec_forward(m, Mrows, beam, B, false, beam, 1));   // warm
-  m->prof_on = true;
-  int rc = dec_forward(m, Mrows, beam, B, false, beam, 1);
-  m->prof_on = false;
-  WIS_RET(rc);
-  // API order: QKV gemv, out-proj gemv, cross-attn, self-attn, FFN1 gemv, FFN2 gemv  <-  rows 0, 2, 4, 1, 6, 7
-  // (more than 8 rows - the batched-row kernels, round 6: the fourth slot carries the cross-attention output projection (row 5); the attention
-  // kernels' stamps are the one-utterance forms' and stay empty there)
-  static const int rows_small[6] = {0, 2, 4, 1, 6, 7}, rows_frag[6] = {0, 2, 4, 5, 6, 7};
-  const int* rows = Mrows > 8 ? rows_frag : rows_small;
-  for (int i = 0; i < 6; ++i)
-    WIS_HIP_CHECK(hipMemcpyAsync(out + i * 16, m->d_prof + rows[i] * 16, 16 * 8, hipMemcpyDeviceToHost, m->st));
-  bool gave_up = false;
-  WIS_RET(spin_gave_up(m, &gave_up));      // (synchronises the stream; a raised flag is consumed here, not by the next wis_generate)
-  if (gave_up) { set_error("wis_debug_phase_cycles: the granule hand-off gave up during the tap; stamps are not valid"); return WIS_E_STATE; }
-  return WIS_OK;
-}
-
-int wis_debug_sampling_cycles(wis_model_t* m, uint64_t* out) {
-  if (!m || !out) { set_error("wis_debug_sampling_cycles: bad argument"); return WIS_E_ARG; }
-  if (!WIS_TAPS) { set_error("tuning taps are not compiled in (rebuild with WIS_EXTRA_HIPFLAGS=-DWIS_TAPS=1)"); return WIS_E_UNSUPPORTED; }
-  WIS_HIP_CHECK(hipSetDevice(m->device));
-  WIS_HIP_CHECK(hipMemcpy(out, m->d_prof + (size_t)m->cfg.n_dec_layers * 8 * 16, 2 * 16 * 8, hipMemcpyDeviceToHost));
-  return WIS_OK;
-}
-
-int wis_debug_timeline(wis_model_t* m, int B, int beam, int pos, int use_graph, uint64_t* out, int n_out) {
-  if (!m || !out) { set_error("wis_debug_timeline: bad argument"); return WIS_E_ARG; }
-  if (!WIS_TAPS) { set_error("tuning taps are not compiled in (rebuild with WIS_EXTRA_HIPFLAGS=-DWIS_TAPS=1)"); return WIS_E_UNSUPPORTED; }
-  WIS_ENTER(m, "wis_debug_timeline")
-  WIS_HIP_CHECK(hipSetDevice(m->device));
-  WIS_RET(check_batch(m, B, beam));
-  SpinClaim claim(m, B);
-  const int Mrows = B * beam, ctx = m->cfg.n_text_ctx, nk = m->cfg.n_dec_layers * 8;
-  if (pos < 0 || pos >= ctx || n_out < nk) { set_error("wis_debug_timeline: bad pos / out size (need %d rows)", nk); return WIS_E_ARG; }
-  WIS_HIP_CHECK(hipStreamSynchronize(m->st));
-  std::vector<int> tok(Mrows, 100), ps(Mrows, pos), slot(Mrows), ls(Mrows);
-  for (int r = 0; r < Mrows; ++r) { slot[r] = r; ls[r] = r; }
-  WIS_RET(upload_rows(m, tok, ps, slot, ls));
-  std::vector<unsigned long long> init((size_t)nk * 16, 0ull);
-  for (int k = 0; k < nk; ++k) init[(size_t)k * 16 + 14] = ~0ull;
-  m->prof_on = true; m->prof_all = true;
-  int rc = WIS_OK;
-  hipGraph_t g = nullptr; hipGraphExec_t gx = nullptr;
-  do {
-    if (use_graph) {
-      if (hipStreamBeginCapture(m->st, hipStreamCaptureModeThreadLocal) != hipSuccess) { set_error("capture failed"); rc = WIS_E_HIP; break; }
-      rc = dec_forward(m, Mrows, beam, B, true, beam, 1);
-      if (hipStreamEndCapture(m->st, &g) != hipSuccess || rc) { if (!rc) { set_error("end capture failed"); rc = WIS_E_HIP; } break; }
-      if (hipGraphInstantiate(&gx, g, nullptr, nullptr, 0) != hipSuccess) { set_error("instantiate failed"); rc = WIS_E_HIP; break; }
-    }
-    for (int it = 0; it < 3 && !rc; ++it) {   // the last iteration is the one reported
-      if (hipMemcpyAsync(m->d_prof, init.data(), init.size() * 8, hipMemcpyHostToDevice, m->st) != hipSuccess) { rc = WIS_E_HIP; break; }
-      hipStreamSynchronize(m->st);
-      if (use_graph) { if (hipGraphLaunch(gx, m->st) != hipSuccess) { set_error("graph launch failed"); rc = WIS_E_HIP; } }
-      else rc = dec_forward(m, Mrows, beam, B, true, beam, 1);
-      hipStreamSynchronize(m->st);
-    }
-  } while (0);
-  m->prof_on = false; m->prof_all = false;
-  if (gx) hipGraphExecDestroy(gx);
-  if (g) hipGraphDestroy(g);
-  WIS_RET(rc);
-  { bool gave_up = false; WIS_RET(spin_gave_up(m, &gave_up)); if (gave_up) { set_error("wis_debug_timeline: the granule hand-off gave up during the tap"); return WIS_E_STATE; } }
-  std::vector<unsigned long long> h((size_t)nk * 16);
-  WIS_HIP_CHECK(hipMemcpy(h.data(), m->d_prof, h.size() * 8, hipMemcpyDeviceToHost));
-  for (int k = 0; k < nk; ++k) { out[2 * k] = h[(size_t)k * 16 + 14]; out[2 * k + 1] = h[(size_t)k * 16 + 15]; }
-  return WIS_OK;
-}
-
-int wis_bench_weight_stream(wis_model_t* m, int M, int passes, float* total_ms, int* launches_per_pass, double* bytes_per_pass) {
-  if (!m || M < 1 || M > MAX_ROWS || passes < 1 || !total_ms) { set_error("wis_bench_weight_stream: bad argument"); return WIS_E_ARG; }
-  WIS_ENTER(m, "wis_bench_weight_stream")
-  WIS_HIP_CHECK(hipSetDevice(m->device));
-  const int d = m->cfg.d_model; hipStream_t st = m->st;
-  int launches = 0; double bytes = 0;
-  const bool frag = M > 8;          // the route dec_forward takes at this row count
-  const int MBf = cdiv(M, 16);
-  static const bool ln_f16 = [] { const char* e = getenv("WIS_B1_LN"); return e && !strcmp(e, "f16"); }();
-  const bool ln16 = !frag && ln_f16 && m->cq_fold && d % 64 == 0 && M * (d / 8) <= 13 * 256 && d <= 2048;      // dec_forward's choice at this row count
-  auto pass = [&](bool count) -> int {
-    for (int l = 0; l < m->cfg.n_dec_layers; ++l) {
-      const DecLayerW& w = m->dec[l];
-      struct { const f16* wp; const float* sc; const float* b; const float* cs; int N, K; bool ln; } mats[6] = {
-        {w.p_qkv, w.s_qkv, w.b_qkv, w.c_qkv, 3 * d, d, true}, {w.p_out, w.s_out, w.b_out, nullptr, d, d, false},
-        {w.p_cq, w.s_cq, w.b_cq, w.c_cq, d, d, true},        {w.p_cout, w.s_cout, w.b_cout, nullptr, d, d, false},
-        {w.p_f1, w.s_f1, w.b_f1, w.c_f1, 4 * d, d, true},    {w.p_f2, w.s_f2, w.b_f2, nullptr, d, 4 * d, false}};
-      for (auto& t : mats) {
-        GemvP g; memset(&g, 0, sizeof(g));
-        g.csum = t.cs; g.Wp = t.wp; g.wscale = t.sc; g.bias = t.b;
-        g.y = m->logits; g.M = M; g.N = t.N; g.K = t.K; g.flags = (t.ln ? GV_LN : 0) | GV_OUT_F32;
-        g.rows = gemv_rows_for(g.N == m->n_vocab_pad ? m->cfg.n_vocab : g.N, g.K);
-        if (frag) { g.x = t.K == d ? (const void*)m->dxf : (const void*)m->dhxf; g.xmb = MBf; g.stat_in = m->dstat; WIS_RET(launch_gemv_frag(st, g)); }
-        else {
-          g.x = t.ln ? (const void*)m->dx : (const void*)m->dh;
-          if (t.ln && ln16) { g.x = m->dxh; g.flags = GV_LN16 | GV_OUT_F32; }
-          WIS_RET(launch_gemv(st, g));
-        }
-        if (count) { ++launches; bytes += (double)t.N * t.K * (m->w8 ? 1 : 2); }
-      }
-    }
-    GemvP g; memset(&g, 0, sizeof(g));
-    g.csum = m->c_proj; g.bias = m->b_proj; g.Wp = m->p_proj; g.wscale = m->s_proj; g.y = m->logits; g.M = M; g.N = m->n_vocab_pad; g.K = d; g.flags = GV_LN | GV_OUT_F32;
-    g.rows = gemv_rows_for(m->cfg.n_vocab, g.K);
-    if (frag) { g.x = m->dxf; g.xmb = MBf; g.stat_in = m->dstat; WIS_RET(launch_gemv_frag(st, g)); }
-    else {
-      g.x = m->dx;
-      if (ln16) { g.x = m->dxh; g.flags = GV_LN16 | GV_OUT_F32; }
-      WIS_RET(launch_gemv(st, g));
-    }
-    if (count) { ++launches; bytes += (double)m->n_vocab_pad * d * (m->w8 ? 1 : 2); }
-    return WIS_OK;
-  };
-  if (frag) {       // zero rows: fragment image of zeros (allocation state), partial sums of zeros
-    WIS_HIP_CHECK(hipMemsetAsync(m->dxf, 0, (size_t)(d / 32) * (MAX_ROWS / 16) * 64 * 8 * 2, st));
-    WIS_HIP_CHECK(hipMemsetAsync(m->dhxf, 0, (size_t)(4 * d / 32) * (MAX_ROWS / 16) * 64 * 8 * 2, st));
-    WIS_HIP_CHECK(hipMemsetAsync(m->dstat, 0, (size_t)MAX_ROWS * (d / 16) * 2 * 4, st));
-  }
-  WIS_HIP_CHECK(hipMemsetAsync(m->dx, 0, (size_t)MAX_ROWS * d * 4, st));
-  WIS_HIP_CHECK(hipMemsetAsync(m->dh, 0, (size_t)MAX_ROWS * 4 * d * 2, st));
-  if (ln16) {
-    WIS_HIP_CHECK(hipMemsetAsync(m->dxh, 0, (size_t)MAX_ROWS * d * 2, st));
-    WIS_HIP_CHECK(hipMemsetAsync(m->dstat, 0, (size_t)MAX_ROWS * (d / 16) * 2 * 4, st));
-  }
-  WIS_RET(pass(true));   // warm-up pass (also counts launches / bytes)
-  // the timed passes run the way the product runs these kernels: captured once into a HIP graph and replayed (wis_generate replays
-  // its decode step as a graph); WIS_NO_GRAPH=1 (profilers that cannot follow a capture) falls back to eager launches
-  hipGraph_t graph = nullptr; hipGraphExec_t gexec = nullptr;
-  if (m->use_graph) {
-    WIS_HIP_CHECK(hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal));
-    const int rc = pass(false);
-    const hipError_t e = hipStreamEndCapture(st, &graph);
-    if (rc || e != hipSuccess) { if (graph) hipGraphDestroy(graph); if (rc) return rc; set_error("weight-stream tap: graph capture failed: %s", hipGetErrorString(e)); return WIS_E_HIP; }
-    if (hipGraphInstantiate(&gexec, graph, nullptr, nullptr, 0) != hipSuccess) { hipGraphDestroy(graph); set_error("weight-stream tap: graph instantiate failed"); return WIS_E_HIP; }
-    hipGraphDestroy(graph);
-    if (hipGraphLaunch(gexec, st) != hipSuccess) { hipGraphExecDestroy(gexec); set_error("weight-stream tap: graph launch failed"); return WIS_E_HIP; }      // untimed first replay
-  }
-  int rc2 = WIS_OK;
-  hipError_t e2 = hipEventRecord(m->ev[6], st);
-  for (int i = 0; i < passes && !rc2 && e2 == hipSuccess; ++i) { if (gexec) e2 = hipGraphLaunch(gexec, st); else rc2 = pass(false); }
-  if (e2 == hipSuccess) e2 = hipEventRecord(m->ev[7], st);
-  if (e2 == hipSuccess) e2 = hipStreamSynchronize(st);
-  if (gexec) hipGraphExecDestroy(gexec);
-  WIS_RET(rc2);
-  WIS_HIP_CHECK(e2);
-  WIS_HIP_CHECK(hipEventElapsedTime(total_ms, m->ev[6], m->ev[7]));
-  if (launches_per_pass) *launches_per_pass = launches;
-  if (bytes_per_pass) *bytes_per_pass = bytes;
-  return WIS_OK;
-}
-
-// ---- raw device helpers + single-kernel entry points -----------------------------------
-int wis_dev_alloc(int device, size_t bytes, void** out) {
-  DeviceCtx* c; WIS_RET(get_ctx(device, &c));
-  WIS_HIP_CHECK(hipMalloc(out, bytes ? bytes : 16)); return WIS_OK;
-}
-int wis_dev_free(int device, void* p) { DeviceCtx* c; WIS_RET(get_ctx(device, &c)); WIS_HIP_CHECK(hipFree(p)); return WIS_OK; }
-int wis_dev_h2d(int device, void* dst, const void* src, size_t bytes) { DeviceCtx* c; WIS_RET(get_ctx(device, &c)); WIS_HIP_CHECK(hipMemcpy(dst, src, bytes, hipMemcpyHostToDevice)); return WIS_OK; }
-int wis_dev_d2h(int device, void* dst, const void* src, size_t bytes) { DeviceCtx* c; WIS_RET(get_ctx(device, &c)); WIS_HIP_CHECK(hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost)); return WIS_OK; }
-int wis_dev_sync(int device) { DeviceCtx* c; WIS_RET(get_ctx(device, &c)); WIS_HIP_CHECK(hipDeviceSynchronize()); return WIS_OK; }
-int wis_dev_copy_peer(int dst_device, void* dst, int src_device, const void* src, size_t bytes) {
-  if (!dst || !src) { set_error("wis_dev_copy_peer: bad argument"); return WIS_E_ARG; }
-  DeviceCtx* c; WIS_RET(get_ctx(src_device, &c)); WIS_RET(get_ctx(dst_device, &c));      // both devices exist; current = dst
-  if (src_device != dst_device) {
-    int can = 0;
-    if (hipDeviceCanAccessPeer(&can, dst_device, src_device) == hipSuccess && can) {
-      hipError_t e = hipDeviceEnablePeerAccess(src_device, 0);                            // direct xGMI path; already-enabled is fine
-      if (e != hipSuccess && e != hipErrorPeerAccessAlreadyEnabled) (void)hipGetLastError();
-    }
-  }
-  WIS_HIP_CHECK(hipMemcpyPeer(dst, dst_device, src, src_device, bytes));
-  return WIS_OK;
-}
-
-int wis_op_gemm(int device, const void* A, int lda, const void* W, const float* bias, const float* residual, void* C, int M, int N, int K, int flags) {
-  DeviceCtx* c; WIS_RET(get_ctx(device, &c));
-  std::lock_guard<std::mutex> op_lock(ctx_op_mutex(c));
-  hipStream_t st = ctx_stream(c);
-  if (flags & 8) {   // split-K = 2 path of the encoder's FFN2: requires bias, residual and fp32 output
-    if (!bias || !residual || (flags & 7) != (2 | 4)) { set_error("wis_op_gemm: split-K needs bias, residual, flags 2|4|8"); return WIS_E_ARG; }
-    float* scratch = nullptr;
-    WIS_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&scratch), (size_t)2 * M * N * 4));
-    int rc = launch_gemm_splitk_resid(st, gemm_plain(reinterpret_cast<const f16*>(A), lda, reinterpret_cast<const f16*>(W), M, N, K), 2, scratch, bias, residual,
-                                      reinterpret_cast<float*>(C));
-    hipError_t e = hipStreamSynchronize(st);
-    hipFree(scratch);
-    if (rc) return rc;
-    if (e != hipSuccess) { set_error("wis_op_gemm: %s", hipGetErrorString(e)); return WIS_E_HIP; }
-    return WIS_OK;
-  }
-  WIS_RET(launch_gemm_generic(st, gemm_plain(reinterpret_cast<const f16*>(A), lda, reinterpret_cast<const f16*>(W), M, N, K), bias, residual, C, flags));
-  WIS_HIP_CHECK(hipGetLastError());
-  WIS_HIP_CHECK(hipStreamSynchronize(st));
-  return WIS_OK;
-}
-int wis_op_layernorm(int device, const float* x, const float* gamma, const float* beta, void* y, int M, int d) {
-  DeviceCtx* c; WIS_RET(get_ctx(device, &c));
-  std::lock_guard<std::mutex> op_lock(ctx_op_mutex(c));
-  WIS_RET(launch_layernorm(ctx_stream(c), x, gamma, beta, reinterpret_cast<f16*>(y), M, d));
-  WIS_HIP_CHECK(hipGetLastError());
-  WIS_HIP_CHECK(hipStreamSynchronize(ctx_stream(c)));
-  return WIS_OK;
-}
-int wis_op_enc_attention(int device, const void* qk, const void* vt, void* out, int B, int T, int Tpad, int H) {
-  DeviceCtx* c; WIS_RET(get_ctx(device, &c));
-  std::lock_guard<std::mutex> op_lock(ctx_op_mutex(c));
-  // same rule as the encoder: the split-key form (two workgroups per query tile and head, in-launch merge) at small grids
-  hipStream_t st = ctx_stream(c);
-  float* part = nullptr; unsigned* counters = nullptr;
-  const size_t ncnt = (size_t)B * H * cdiv(T, 128);
-  int rc = WIS_OK;
-  if (hipMalloc(reinterpret_cast<void**>(&part), enc_attention_part_floats(B, T, H) * 4) != hipSuccess ||
-      hipMalloc(reinterpret_cast<void**>(&counters), ncnt * 4) != hipSuccess) { set_error("wis_op_enc_attention: out of device memory"); rc = WIS_E_NOMEM; }
-  f16* qk2 = nullptr;      // the lazy-reference loop wants log2(e) on Q as well (the engine folds it into the projection): a scaled private copy
-  if (!rc && enc_attn_lazy()) {
-    const size_t n = (size_t)B * T * 2 * H * 64;
-    if (hipMalloc(reinterpret_cast<void**>(&qk2), n * 2) != hipSuccess) { set_error("wis_op_enc_attention: out of device memory"); rc = WIS_E_NOMEM; }
-    else {
-      hipMemcpyAsync(qk2, qk, n * 2, hipMemcpyDeviceToDevice, st);
-      launch_scale_q_log2e(st, qk2, (int64_t)B * T, H * 64);
-    }
-  }
-  if (!rc) {
-    hipMemsetAsync(counters, 0, ncnt * 4, st);
-    rc = launch_enc_attention(st, qk2 ? qk2 : reinterpret_cast<const f16*>(qk), reinterpret_cast<const f16*>(vt), reinterpret_cast<f16*>(out), B, T, Tpad, H, part, counters, ncnt);
-  }
-  hipError_t e = hipStreamSynchronize(st);
-  hipFree(part); hipFree(counters); hipFree(qk2);
-  if (rc) return rc;
-  if (e != hipSuccess) { set_error("wis_op_enc_attention: %s", hipGetErrorString(e)); return WIS_E_HIP; }
-  return WIS_OK;
-}
-int wis_op_gemv(int device, const void* x, const float* gamma, const float* beta, const void* W, const float* bias, void* y, int M, int N, int K, int flags) {
-  DeviceCtx* c; WIS_RET(get_ctx(device, &c));
-  std::lock_guard<std::mutex> op_lock(ctx_op_mutex(c));
-  hipStream_t st = ctx_stream(c);
-  if (flags & GV_QKV) { set_error("wis_op_gemv: flag 16 is internal"); return WIS_E_ARG; }
-  const int Npad = cdiv(N, gemv_rows_for(N, K)) * gemv_rows_for(N, K);
-  // (tap flags: 32 = quantise the matrix to 8 bits per weight first; 64 = GV_LN16: x is the F16 copy of the rows, LayerNorm folded)
-  const bool w8 = flags & 32, ln16 = (flags & GV_LN16) != 0, ln = (flags & GV_LN) || ln16;
-  flags &= ~32;
-  if (ln16 && ((flags & GV_LN) || M > 8 || w8)) { set_error("wis_op_gemv: flag 64 (LayerNorm fold on f16 rows): <= 8 rows, f16 weights, without flag 8"); return WIS_E_ARG; }
-  if (ln && (!gamma || !beta)) { set_error("wis_op_gemv: flags 8 / 64 need gamma and beta"); return WIS_E_ARG; }
-  // the same preparation the model loader does: optional LayerNorm fold into a private copy of W / bias, then packing
-  f16 *wp = nullptr, *wtmp = nullptr, *xfr = nullptr; float *wsc = nullptr, *b2 = nullptr, *cs = nullptr, *stt = nullptr;
-  int rc = WIS_OK;
-  do {
-    if (hipMalloc(reinterpret_cast<void**>(&wp), (size_t)Npad * K * 2) != hipSuccess || hipMalloc(reinterpret_cast<void**>(&wtmp), (size_t)N * K * 2) != hipSuccess ||
-        hipMalloc(reinterpret_cast<void**>(&b2), (size_t)Npad * 4) != hipSuccess || hipMalloc(reinterpret_cast<void**>(&cs), (size_t)Npad * 4) != hipSuccess ||
-        (w8 && hipMalloc(reinterpret_cast<void**>(&wsc), (size_t)Npad * 4) != hipSuccess)) { set_error("wis_op_gemv: out of device memory"); rc = WIS_E_NOMEM; break; }
-    hipMemcpyAsync(wtmp, W, (size_t)N * K * 2, hipMemcpyDeviceToDevice, st);
-    hipMemsetAsync(b2, 0, (size_t)Npad * 4, st); hipMemsetAsync(cs, 0, (size_t)Npad * 4, st);
-    if (bias) hipMemcpyAsync(b2, bias, (size_t)N * 4, hipMemcpyDeviceToDevice, st);
-    if (ln && (rc = launch_fold_ln(st, wtmp, gamma, beta, b2, cs, N, K, 0, 1.f))) break;
-    const int rows = gemv_rows_for(N, K);
-    rc = w8 ? launch_pack_gemv8(st, wtmp, reinterpret_cast<unsigned char*>(wp), wsc, N, Npad, K, 0, 1.f) : launch_pack_gemv(st, wtmp, wp, N, Npad, K, 0, 1.f, rows);
-    if (rc) break;
-    if (w8 && ln && (rc = launch_csum8(st, wtmp, wsc, cs, N, K, 0, 1.f))) break;
-    GemvP g; memset(&g, 0, sizeof(g));
-    g.x = x; g.csum = ln ? cs : nullptr; g.Wp = wp; g.wscale = wsc; g.bias = (bias || ln) ? b2 : nullptr; g.y = y; g.M = M; g.N = N; g.K = K; g.flags = flags; g.rows = rows;
-    if (M > 8) {
-      // the product's batched route (dec_forward_frag): activations as a fragment image, LayerNorm statistics as row partials
-      const int MBf = cdiv(M, 16);
-      if (hipMalloc(reinterpret_cast<void**>(&xfr), (size_t)(K / 32) * MBf * 64 * 8 * 2) != hipSuccess ||
-          (ln && hipMalloc(reinterpret_cast<void**>(&stt), (size_t)M * (K / 16) * 2 * 4) != hipSuccess)) { set_error("wis_op_gemv: out of device memory"); rc = WIS_E_NOMEM; break; }
-      hipMemsetAsync(xfr, 0, (size_t)(K / 32) * MBf * 64 * 8 * 2, st);
-      if ((rc = launch_xf_pack(st, x, ln ? 0 : 1, xfr, ln ? stt : nullptr, M, K, MBf))) break;
-      g.x = xfr; g.xmb = MBf; g.stat_in = stt;
-      float* kp = nullptr; unsigned* kc = nullptr;
-      if (!ln && K >= 4096 && (K / 32) % 16 == 0) {      // the product's rule for the K = 4d projection: four K slices per n-tile, merged in the launch
-        const size_t nt = (size_t)cdiv(N, 16);
-        if (hipMalloc(reinterpret_cast<void**>(&kp), nt * 4 * MBf * 64 * 16) != hipSuccess || hipMalloc(reinterpret_cast<void**>(&kc), nt * 4) != hipSuccess) {
-          hipFree(kp); set_error("wis_op_gemv: out of device memory"); rc = WIS_E_NOMEM; break; }
-        hipMemsetAsync(kc, 0, nt * 4, st);
-        g.ksplit = 4; g.kpart = kp; g.kcnt = kc;
-        if (!(flags & GV_RESID)) rc = launch_gemv_frag(st, g);      // a first launch on the same tickets: they must re-arm themselves
-      }
-      if (!rc) rc = launch_gemv_frag(st, g);
-      hipStreamSynchronize(st);
-      hipFree(kp); hipFree(kc);
-      break;
-    }
-    rc = launch_gemv(st, g);
-  } while (0);
-  hipError_t e = hipStreamSynchronize(st);
-  hipFree(wp); hipFree(wtmp); hipFree(b2); hipFree(cs); hipFree(wsc); hipFree(xfr); hipFree(stt);
-  if (rc) return rc;
-  if (e != hipSuccess) { set_error("wis_op_gemv: %s", hipGetErrorString(e)); return WIS_E_HIP; }
-  return WIS_OK;
-}
-
-int wis_op_dec_self_attn(int device, const float* q, const void* kc, const void* vc, const int32_t* pos, void* out,
-                         int M, int H, int ctx, int rpu, int sstride, int rmul) {
-  DeviceCtx* c; WIS_RET(get_ctx(device, &c));
-  std::lock_guard<std::mutex> op_lock(ctx_op_mutex(c));
-  if (!q || !kc || !vc || !pos || !out || M < 1 || H < 1 || rpu < 1) { set_error("wis_op_dec_self_attn: bad argument"); return WIS_E_ARG; }
-  WIS_RET(launch_dec_self_attn(ctx_stream(c), q, reinterpret_cast<const f16*>(kc), reinterpret_cast<const f16*>(vc), pos, reinterpret_cast<f16*>(out),
-                               M, H, 64 * H, ctx, rpu, sstride, rmul));
-  WIS_HIP_CHECK(hipGetLastError());
-  WIS_HIP_CHECK(hipStreamSynchronize(ctx_stream(c)));
-  return WIS_OK;
-}
-int wis_op_dec_self_attn_ex(int device, const float* q, const void* kc, const void* vc, const int32_t* pos, void* out,
-                            int M, int H, int ctx, int rpu, int sstride, int rmul, int nb, int out_mb,
-                            const int32_t* anc, int w0, int aw, const int32_t* base) {
-  DeviceCtx* c; WIS_RET(get_ctx(device, &c));
-  std::lock_guard<std::mutex> op_lock(ctx_op_mutex(c));
-  if (!q || !kc || !vc || !pos || !out || M < 1 || H < 1 || rpu < 1 || (nb != 2 && nb != 4 && nb != 8) || (out_mb && out_mb < cdiv(M, 16)) || (base && !anc)) {
-    set_error("wis_op_dec_self_attn_ex: bad argument"); return WIS_E_ARG; }
-  hipStream_t st = ctx_stream(c);
-  const int d = 64 * H;
-  if (out_mb) WIS_HIP_CHECK(hipMemsetAsync(out, 0, (size_t)(d / 32) * out_mb * 64 * 8 * 2, st));      // the fragment image's rows beyond M stay zero
-  WIS_RET(launch_dec_self_attn(st, q, reinterpret_cast<const f16*>(kc), reinterpret_cast<const f16*>(vc), pos, reinterpret_cast<f16*>(out),
-                               M, H, d, ctx, rpu, sstride, rmul, nullptr, out_mb, anc, w0, aw, base, nb));
-  WIS_HIP_CHECK(hipGetLastError());
-  WIS_HIP_CHECK(hipStreamSynchronize(st));
-  return WIS_OK;
-}
-static int op_dec_cross_attn(int device, const float* q, const float* xres, const float* qcs, const float* qb, const void* kx, const void* vt, void* out,
-                             int B, int R, int H, int T, int chunks, const float* q2 = nullptr, int xres_is_stat = 0, int out_mb = 0, int kv_shared = 0, bool no_spin = false) {
-  DeviceCtx* c; WIS_RET(get_ctx(device, &c));
-  std::lock_guard<std::mutex> op_lock(ctx_op_mutex(c));
-  if (!q || !kx || !vt || !out || B < 1 || H < 1 || T < 1) { set_error("wis_op_dec_cross_attn: bad argument"); return WIS_E_ARG; }
-  hipStream_t st = ctx_stream(c);
-  float* part = nullptr; unsigned* counters = nullptr; unsigned long long* gran = nullptr; unsigned* epoch = nullptr;
-  int rc = WIS_OK;
-  if (out_mb && out_mb < cdiv(B * R, 16)) { set_error("wis_op_dec_cross_attn: %d row blocks for %d rows", out_mb, B * R); return WIS_E_ARG; }
-  const bool small = B * H <= CA_SPIN_MAX_BH && !no_spin;      // the product's rule: the granule hand-off on small grids (launch_dec_cross_attn decides by chunking / rows)
-  if (hipMalloc(reinterpret_cast<void**>(&part), (size_t)B * H * 16 * 16 * 66 * 4) != hipSuccess ||
-      hipMalloc(reinterpret_cast<void**>(&counters), (size_t)B * H * 4) != hipSuccess ||
-      (small && (hipMalloc(reinterpret_cast<void**>(&gran), (size_t)B * H * 6 * 8 * 66 * 8) != hipSuccess || hipMalloc(reinterpret_cast<void**>(&epoch), ((size_t)B * H + 1) * 4) != hipSuccess))) {
-    set_error("wis_op_dec_cross_attn: out of device memory"); rc = WIS_E_NOMEM; }
-  unsigned flag = 0;
-  if (!rc) {
-    hipMemsetAsync(counters, 0, (size_t)B * H * 4, st);
-    if (small) { hipMemsetAsync(gran, 0, (size_t)B * H * 6 * 8 * 66 * 8, st); hipMemsetAsync(epoch, 0, ((size_t)B * H + 1) * 4, st); }
-    if (out_mb) hipMemsetAsync(out, 0, (size_t)(64 * H / 32) * out_mb * 64 * 8 * 2, st);      // the fragment image's rows beyond B * R stay zero
-    for (int rep = 0; rep < 3 && !rc; ++rep)      // three launches: the epochs of the granule form advance from launch to launch
-      rc = launch_dec_cross_attn(st, q, reinterpret_cast<const f16*>(kx), reinterpret_cast<const f16*>(vt), reinterpret_cast<f16*>(out), part, counters,
-                                 B, R, H, 64 * H, T, cdiv(T, 64) * 64, chunks, nullptr, out_mb, xres, qcs, qb, gran, epoch, q2, xres_is_stat, kv_shared);
-    if (small && !rc) hipMemcpyAsync(&flag, epoch, 4, hipMemcpyDeviceToHost, st);
-  }
-  hipError_t e = hipStreamSynchronize(st);
-  hipFree(part); hipFree(counters); hipFree(gran); hipFree(epoch);
-  if (rc) return rc;
-  if (flag) { set_error("wis_op_dec_cross_attn: granule hand-off timed out"); return WIS_E_HIP; }
-  if (e != hipSuccess) { set_error("wis_op_dec_cross_attn: %s", hipGetErrorString(e)); return WIS_E_HIP; }
-  return WIS_OK;
-}
-int wis_op_dec_cross_attn(int device, const float* q, const void* kx, const void* vt, void* out, int B, int R, int H, int T, int chunks) {
-  return op_dec_cross_attn(device, q, nullptr, nullptr, nullptr, kx, vt, out, B, R, H, T, chunks);
-}
-int wis_op_dec_cross_attn_folded(int device, const float* q_raw, const float* xres, const float* qcs, const float* qb, const void* kx, const void* vt, void* out,
-                                 int B, int R, int H, int T, int chunks) {
-  if (!xres || !qcs || !qb) { set_error("wis_op_dec_cross_attn_folded: bad argument"); return WIS_E_ARG; }
-  return op_dec_cross_attn(device, q_raw, xres, qcs, qb, kx, vt, out, B, R, H, T, chunks);
-}
-int wis_op_dec_cross_attn_stat(int device, const float* q, const float* q2, const float* stat, const float* qcs, const float* qb, const void* kx, const void* vt, void* out,
-                               int B, int R, int H, int T, int chunks, int out_mb, int kv_shared, int no_spin) {
-  if (stat ? (!qcs || !qb) : (qcs || qb || q2)) { set_error("wis_op_dec_cross_attn_stat: the fold takes partials, column sums and bias together; the plain form none of them"); return WIS_E_ARG; }
-  return op_dec_cross_attn(device, q, stat, qcs, qb, kx, vt, out, B, R, H, T, chunks, q2, stat ? 1 : 0, out_mb, kv_shared, no_spin != 0);
-}
-
 }  // extern "C"
 
-// private device scratch of a tap: freed when the tap returns
-namespace {
-struct TapScratch {
-  std::vector<void*> ptrs;
-  template <class T> bool get(T** p, size_t n_elems) {
-    void* q = nullptr;
-    if (hipMalloc(&q, n_elems * sizeof(T) ? n_elems * sizeof(T) : 16) != hipSuccess) return false;
-    ptrs.push_back(q); *p = reinterpret_cast<T*>(q); return true;
-  }
-  ~TapScratch() { for (void* q : ptrs) hipFree(q); }
-};
-}  // namespace
-
-extern "C" {
-
-int wis_op_gemv_qkv(int device, const float* x, const float* gamma, const float* beta, const void* W, const float* bias, const int32_t* slot, const int32_t* pos,
-                    float* q, void* kc, void* vc, int M, int d, int ctx) {
-  DeviceCtx* c; WIS_RET(get_ctx(device, &c));
-  std::lock_guard<std::mutex> op_lock(ctx_op_mutex(c));
-  if (!x || !gamma || !beta || !W || !bias || !slot || !pos || !q || !kc || !vc || M < 1 || M > MAX_ROWS || d < 128 || d % 128 || ctx < 1) { set_error("wis_op_gemv_qkv: bad argument"); return WIS_E_ARG; }
-  hipStream_t st = ctx_stream(c);
-  const int N = 3 * d, MB = cdiv(M, 16);
-  const float qs = 0.125f;
-  TapScratch ts;
-  f16 *wp = nullptr, *wtmp = nullptr, *xf = nullptr; float *b2 = nullptr, *cs = nullptr, *stt = nullptr;
-  if (!ts.get(&wp, (size_t)N * d) || !ts.get(&wtmp, (size_t)N * d) || !ts.get(&b2, (size_t)N) || !ts.get(&cs, (size_t)N) ||
-      (M > 8 && (!ts.get(&xf, (size_t)(d / 32) * MB * 64 * 8) || !ts.get(&stt, (size_t)M * (d / 16) * 2)))) { set_error("wis_op_gemv_qkv: out of device memory"); return WIS_E_NOMEM; }
-  int rc = WIS_OK;
-  do {
-    // what load_weights does for p_qkv / b_qkv / c_qkv: the bias's query part scaled, the LayerNorm folded, the query rows scaled by the packer
-    hipMemcpyAsync(wtmp, W, (size_t)N * d * 2, hipMemcpyDeviceToDevice, st);
-    hipLaunchKernelGGL(convert_kernel, dim3(blocks_for(N)), dim3(256), 0, st, bias, 0, b2, 0, (int64_t)N, (int64_t)1, (int64_t)1, (int64_t)d, qs);
-    hipMemsetAsync(cs, 0, (size_t)N * 4, st);
-    if ((rc = launch_fold_ln(st, wtmp, gamma, beta, b2, cs, N, d, d, qs))) break;
-    if ((rc = launch_pack_gemv(st, wtmp, wp, N, N, d, d, qs, gemv_rows_for(N, d)))) break;
-    GemvP g; memset(&g, 0, sizeof(g));
-    g.x = x; g.csum = cs; g.Wp = wp; g.bias = b2; g.M = M; g.N = N; g.K = d; g.flags = GV_LN | GV_QKV;
-    g.q = q; g.kc = reinterpret_cast<f16*>(kc); g.vc = reinterpret_cast<f16*>(vc); g.slot = slot; g.pos = pos; g.d = d; g.ctx = ctx;
-    g.rows = gemv_rows_for(N, d);
-    if (M <= 8) { rc = launch_gemv(st, g); break; }      // dec_forward
-    // dec_forward_frag: the rows as a fragment image, their LayerNorm statistics as row partials
-    hipMemsetAsync(xf, 0, (size_t)(d / 32) * MB * 64 * 8 * 2, st);
-    if ((rc = launch_xf_pack(st, x, 0, xf, stt, M, d, MB))) break;
-    g.x = xf; g.xmb = MB; g.stat_in = stt; g.rows = 16;
-    rc = launch_gemv_frag(st, g);
-  } while (0);
-  hipError_t e = hipStreamSynchronize(st);
-  if (rc) return rc;
-  if (e != hipSuccess) { set_error("wis_op_gemv_qkv: %s", hipGetErrorString(e)); return WIS_E_HIP; }
-  return WIS_OK;
-}
-
-int wis_op_gemv_out_cq(int device, const void* a, const float* x0, const void* Wo, const float* bo, const void* Wq, const float* bq, const float* gamma, const float* beta,
-                       float* x1, float* stat, float* q, float* q2, float* qcs, float* qb, int M, int d, int force_frag) {
-  DeviceCtx* c; WIS_RET(get_ctx(device, &c));
-  std::lock_guard<std::mutex> op_lock(ctx_op_mutex(c));
-  const bool frag = M > 8 || force_frag;
-  if (!a || !x0 || !Wo || !bo || !Wq || !bq || !gamma || !beta || !x1 || !stat || !q || !qcs || !qb || (frag && !q2) || M < 1 || M > MAX_ROWS || d < 128 || d % 128) {
-    set_error("wis_op_gemv_out_cq: bad argument"); return WIS_E_ARG; }
-  hipStream_t st = ctx_stream(c);
-  const int MB = cdiv(M, 16);
-  const float qs = 0.125f;
-  const size_t img = (size_t)(d / 32) * MB * 64 * 8;
-  TapScratch ts;
-  f16 *wtmp = nullptr, *fcat = nullptr, *fwot = nullptr, *fwqo = nullptr, *p_cqo = nullptr, *p_out = nullptr, *xh = nullptr, *xf = nullptr, *af = nullptr; float* b_cqo = nullptr;
-  if (!ts.get(&wtmp, (size_t)d * d) || !ts.get(&fcat, (size_t)2 * d * d) || !ts.get(&fwot, (size_t)d * d) || !ts.get(&fwqo, (size_t)d * d) || !ts.get(&p_cqo, (size_t)2 * d * d) ||
-      !ts.get(&p_out, (size_t)d * d) || !ts.get(&b_cqo, (size_t)d) || (frag ? (!ts.get(&xf, img) || !ts.get(&af, img)) : !ts.get(&xh, (size_t)M * d))) {
-    set_error("wis_op_gemv_out_cq: out of device memory"); return WIS_E_NOMEM; }
-  int rc = WIS_OK;
-  do {
-    // load_weights, decoder layer: b_cq / c_cq (the cross-Q bias scaled, the LayerNorm folded: what the cross-attention kernel takes as qb / qcs), p_out, then the fold
-    hipMemcpyAsync(wtmp, Wq, (size_t)d * d * 2, hipMemcpyDeviceToDevice, st);
-    hipLaunchKernelGGL(convert_kernel, dim3(blocks_for(d)), dim3(256), 0, st, bq, 0, qb, 0, (int64_t)d, (int64_t)1, (int64_t)1, (int64_t)d, qs);
-    hipMemsetAsync(qcs, 0, (size_t)d * 4, st);
-    if ((rc = launch_fold_ln(st, wtmp, gamma, beta, qb, qcs, d, d, d, qs))) break;
-    if ((rc = launch_pack_gemv(st, reinterpret_cast<const f16*>(Wo), p_out, d, d, d, 0, 1.f, gemv_rows_for(d, d)))) break;
-    if ((rc = build_cq_fold(st, wtmp, Wo, 1, bo, d, qs, fcat, fwot, fwqo, p_cqo, b_cqo))) break;
-    hipMemcpyAsync(x1, x0, (size_t)M * d * 4, hipMemcpyDeviceToDevice, st);      // the residual epilogue works in place
-    if (!frag) {
-      // dec_forward: one dual launch on the f16 rows (the attention output; the f16 copy of the layer input that the embedding / FFN2 epilogues leave)
-      hipLaunchKernelGGL(convert_kernel, dim3(blocks_for((int64_t)M * d)), dim3(256), 0, st, x0, 0, xh, 1, (int64_t)M, (int64_t)d, (int64_t)d, (int64_t)0, 1.f);
-      GemvP ga; memset(&ga, 0, sizeof(ga));
-      ga.x = a; ga.Wp = p_out; ga.bias = bo; ga.y = x1; ga.M = M; ga.N = d; ga.K = d; ga.flags = GV_RESID; ga.stat_out = stat;
-      GemvP gb; memset(&gb, 0, sizeof(gb));
-      gb.x = xh; gb.x2 = a; gb.xsplit = d; gb.Wp = p_cqo; gb.bias = b_cqo; gb.y = q; gb.M = M; gb.N = d; gb.K = 2 * d; gb.flags = GV_OUT_F32;
-      rc = launch_gemv_dual(st, ga, gb);
-      break;
-    }
-    // dec_forward_frag: three d x d problems on the fragment images of the layer input and the attention output
-    hipMemsetAsync(xf, 0, img * 2, st); hipMemsetAsync(af, 0, img * 2, st);
-    if ((rc = launch_xf_pack(st, x0, 0, xf, nullptr, M, d, MB))) break;
-    if ((rc = launch_xf_pack(st, a, 1, af, nullptr, M, d, MB))) break;
-    auto base = [&](const void* x, const f16* Wp, const float* bias, int flags) {
-      GemvP g; memset(&g, 0, sizeof(g));
-      g.x = x; g.Wp = Wp; g.bias = bias; g.M = M; g.N = d; g.K = d; g.flags = flags; g.xmb = MB; g.rows = 16;
-      return g;
-    };
-    GemvP g3[3];
-    g3[0] = base(af, p_out, bo, GV_RESID);
-    g3[0].y = x1; g3[0].ymb = MB; g3[0].stat_out = stat;
-    g3[1] = base(xf, p_cqo, b_cqo, GV_OUT_F32);
-    g3[1].y = q; g3[1].wks = 2 * d / 32; g3[1].wk0 = 0;
-    g3[2] = base(af, p_cqo, nullptr, GV_OUT_F32);
-    g3[2].y = q2; g3[2].wks = 2 * d / 32; g3[2].wk0 = d / 32;
-    rc = launch_gemv_frag3(st, g3, 3);
-  } while (0);
-  hipError_t e = hipStreamSynchronize(st);
-  if (rc) return rc;
-  if (e != hipSuccess) { set_error("wis_op_gemv_out_cq: %s", hipGetErrorString(e)); return WIS_E_HIP; }
-  return WIS_OK;
-}
-
-}  // extern "C"
+#include "taps.hip"      // the debug / measurement taps and the single-kernel entry points
 
 // word-level alignment (wis_align, wis_op_dtw, wis_op_align_matrix): its kernels and driver, in this translation unit
 #include "align.hip"

@@ -1,0 +1,584 @@
+// taps.hip — debug, tuning and measurement taps (wis_debug_*, wis_bench_weight_stream, wis_dev_*, wis_op_*).  Included by model.hip: the taps run the
+// product's own static helpers (dec_forward, the stage builders, prep_projection), not copies of them.
+extern "C" {
+
+int wis_debug_encode(wis_model_t* m, const float* input, int input_kind, int B, float* enc_out) {
+  if (!m || !input || !enc_out) { set_error("wis_debug_encode: bad argument"); return WIS_E_ARG; }
+  WIS_ENTER(m, "wis_debug_encode")
+  WIS_HIP_CHECK(hipSetDevice(m->device));
+  WIS_RET(check_batch(m, B, 1));
+  WIS_RET(stage_input(m, input, input_kind, B));
+  WIS_RET(run_encoder(m, B));
+  const int64_t n = (int64_t)B * m->cfg.n_audio_ctx * m->cfg.d_model;
+  hipLaunchKernelGGL(f16_to_f32_kernel, dim3(blocks_for(n)), dim3(256), 0, m->st, m->mem, m->x, n);   // x is free after the encoder
+  WIS_HIP_CHECK(hipMemcpyAsync(enc_out, m->x, (size_t)n * 4, hipMemcpyDeviceToHost, m->st));
+  WIS_HIP_CHECK(hipStreamSynchronize(m->st));
+  return WIS_OK;
+}
+
+int wis_debug_logits(wis_model_t* m, const float* input, int input_kind, int B, const int32_t* dec_in, int T, float* logits) {
+  if (!m || !input || !dec_in || !logits || T < 1 || T > m->cfg.n_text_ctx) { set_error("wis_debug_logits: bad argument"); return WIS_E_ARG; }
+  WIS_ENTER(m, "wis_debug_logits")
+  WIS_HIP_CHECK(hipSetDevice(m->device));
+  WIS_RET(check_batch(m, B, 1));
+  WIS_RET(stage_input(m, input, input_kind, B));
+  WIS_RET(run_encoder(m, B));
+  WIS_RET(run_cross_kv(m, B));
+  const int V = m->cfg.n_vocab;
+  for (int t = 0; t < T; ++t) {
+    std::vector<int> tok(B);
+    for (int b = 0; b < B; ++b) tok[b] = dec_in[b * T + t];
+    for (int attempt = 0; attempt < 2; ++attempt) {      // (a pass whose granule hand-off gave up is repeated in the ticket form)
+      SpinClaim claim(m, B);
+      WIS_RET(single_row_setup(m, B, tok, t));
+      WIS_RET(dec_forward(m, B, 1, B, true, 1, 0));
+      for (int b = 0; b < B; ++b)
+        WIS_HIP_CHECK(hipMemcpyAsync(logits + ((size_t)b * T + t) * V, m->logits + (size_t)b * m->n_vocab_pad, (size_t)V * 4, hipMemcpyDeviceToHost, m->st));
+      bool gave_up = false;
+      WIS_RET(spin_gave_up(m, &gave_up));
+      if (!gave_up) break;
+    }
+  }
+  return WIS_OK;
+}
+
+int wis_debug_logits_rows(wis_model_t* m, const float* input, int input_kind, int B, const int32_t* dec_in, int T, int R, float* logits) {
+  if (!m || !input || !dec_in || !logits || T < 1 || T > m->cfg.n_text_ctx || R < 1 || R > 16) { set_error("wis_debug_logits_rows: bad argument (1 <= R <= 16)"); return WIS_E_ARG; }
+  WIS_ENTER(m, "wis_debug_logits_rows")
+  WIS_HIP_CHECK(hipSetDevice(m->device));
+  WIS_RET(check_batch(m, B, 1));
+  if (B * R > MAX_ROWS) { set_error("wis_debug_logits_rows: B*R = %d exceeds %d decoder rows per pass", B * R, MAX_ROWS); return WIS_E_STATE; }
+  WIS_RET(stage_input(m, input, input_kind, B));
+  WIS_RET(run_encoder(m, B));
+  WIS_RET(run_cross_kv(m, B));
+  const int V = m->cfg.n_vocab;
+  // teacher-forced in blocks of R positions: the rows (b, i) of a pass sit at positions t0 + i of utterance b's KV slot (causal by
+  // position, like the merged prompt pass of wis_generate), so a pass has B * R rows - with B * R > 8 it takes the batched-row
+  // route (dec_forward_frag: fragment images, partial-sum LayerNorm statistics) that wis_debug_logits' one row per utterance never
+  // reaches at small B
+  for (int t0 = 0; t0 < T; t0 += R) {
+    const int rows = std::min(R, T - t0), M = B * rows;
+    std::vector<int> tok(M), pos(M), slot(M), ls(M);
+    for (int b = 0; b < B; ++b) for (int i = 0; i < rows; ++i) { const int r = b * rows + i; tok[r] = dec_in[b * T + t0 + i]; pos[r] = t0 + i; slot[r] = b; ls[r] = b; }
+    for (int r = 0; r < M; ++r) if (tok[r] < 0 || tok[r] >= V) { set_error("wis_debug_logits_rows: token %d out of range", tok[r]); return WIS_E_ARG; }
+    for (int attempt = 0; attempt < 2; ++attempt) {      // (a pass whose granule hand-off gave up is repeated in the ticket form)
+      SpinClaim claim(m, B);
+      WIS_RET(upload_rows(m, tok, pos, slot, ls));
+      WIS_RET(dec_forward(m, M, rows, B, true, 1, 0));
+      for (int b = 0; b < B; ++b) for (int i = 0; i < rows; ++i)
+        WIS_HIP_CHECK(hipMemcpyAsync(logits + ((size_t)b * T + t0 + i) * V, m->logits + (size_t)(b * rows + i) * m->n_vocab_pad, (size_t)V * 4, hipMemcpyDeviceToHost, m->st));
+      bool gave_up = false;
+      WIS_RET(spin_gave_up(m, &gave_up));
+      if (!gave_up) break;
+    }
+  }
+  return WIS_OK;
+}
+
+int wis_debug_tree_logits(wis_model_t* m, const float* input, int input_kind, const int32_t* prompt, int P, int beam,
+                          const int32_t* tok, const int32_t* org, int n_steps, float* logits) {
+  if (!m || !input || !prompt || !tok || !org || !logits || P < 1 || P > 16 || beam < 1 || beam > MAX_R || n_steps < 1 || n_steps > std::min(32, MAX_ROWS / std::max(beam, 1))) {
+    set_error("wis_debug_tree_logits: bad argument (1 <= n_steps <= min(32, %d / beam))", MAX_ROWS); return WIS_E_ARG;
+  }
+  WIS_ENTER(m, "wis_debug_tree_logits")
+  WIS_HIP_CHECK(hipSetDevice(m->device));
+  WIS_RET(check_batch(m, 1, beam));
+  const wis_config_t& c = m->cfg; hipStream_t st = m->st;
+  const int k = beam, V = c.n_vocab;
+  for (int i = 0; i < n_steps * k; ++i) if (tok[i] < 0 || tok[i] >= V || org[i] < 0 || org[i] >= k) { set_error("wis_debug_tree_logits: token / origin out of range"); return WIS_E_ARG; }
+  WIS_RET(stage_input(m, input, input_kind, 1));
+  WIS_RET(run_encoder(m, 1));
+  WIS_RET(run_cross_kv(m, 1));
+  m->spin_now = false;
+  // the prompt: rows at positions 0 .. P-1 of slot 0, then every slot gets a copy (what the first step's kv_reorder does)
+  std::vector<int> ptok(P), ppos(P), pslot(P, 0), pls(P, 0);
+  for (int i = 0; i < P; ++i) { ptok[i] = prompt[i]; ppos[i] = i; }
+  WIS_RET(upload_rows(m, ptok, ppos, pslot, pls));
+  WIS_RET(dec_forward(m, P, P, 1, false, beam, 0));
+  auto& hs = m->h_pin->tree_seed;
+  for (int j = 0; j < MAX_R; ++j) hs.parent[j] = 0;
+  hs.step = 1; hs.done = 0;
+  WIS_HIP_CHECK(hipMemcpyAsync(m->bs.parent, hs.parent, (size_t)k * 4, hipMemcpyHostToDevice, st));
+  WIS_HIP_CHECK(hipMemcpyAsync(m->bs.step_u, &hs.step, 4, hipMemcpyHostToDevice, st));
+  WIS_HIP_CHECK(hipMemcpyAsync(m->bs.done, &hs.done, 4, hipMemcpyHostToDevice, st));
+  WIS_RET(launch_kv_reorder(st, m->kc_all, m->vc_all, m->kv_layer_stride, c.n_dec_layers, m->bs, 1, beam, P, c.n_text_ctx, c.d_model));
+  // one window: steps 1 .. n_steps, rows from trajectory entries 0 .. n_steps - 1
+  std::vector<int> hd((size_t)n_steps * MAX_R * 2, 0);
+  pack_traj(hd.data(), tok, org, n_steps, k);
+  std::vector<int> wt, wp, wsl, wls;
+  int* ha = m->h_pin->anc;
+  const int Mpad = fill_tree_window(hd.data(), 1, n_steps, k, P, wt, wp, wsl, wls, ha);
+  WIS_RET(upload_rows(m, wt, wp, wsl, wls, false, &m->h_pin->win_rows));
+  WIS_HIP_CHECK(hipMemcpyAsync(m->d_anc, ha, (size_t)Mpad * ANC_W * 4, hipMemcpyHostToDevice, st));
+  const TreeWin tw{m->d_anc, P, ANC_W};
+  WIS_RET(dec_forward(m, Mpad, 16, Mpad / 16, true, 1, 0, &tw));
+  WIS_HIP_CHECK(hipMemcpy2DAsync(logits, (size_t)V * 4, m->logits, (size_t)m->n_vocab_pad * 4, (size_t)V * 4, (size_t)n_steps * k, hipMemcpyDeviceToHost, st));
+  WIS_HIP_CHECK(hipStreamSynchronize(st));
+  return WIS_OK;
+}
+
+int wis_debug_phase_cycles(wis_model_t* m, int B, int beam, int pos, uint64_t* out) {
+  if (!m || !out) { set_error("wis_debug_phase_cycles: bad argument"); return WIS_E_ARG; }
+  if (!WIS_TAPS) { set_error("tuning taps are not compiled in (rebuild with WIS_EXTRA_HIPFLAGS=-DWIS_TAPS=1)"); return WIS_E_UNSUPPORTED; }
+  WIS_ENTER(m, "wis_debug_phase_cycles")
+  WIS_HIP_CHECK(hipSetDevice(m->device));
+  WIS_RET(check_batch(m, B, beam));
+  SpinClaim claim(m, B);      // the hand-off form wis_generate would take for this batch now (and not whatever the last call left behind)
+  const int Mrows = B * beam, ctx = m->cfg.n_text_ctx;
+  if (pos < 0 || pos >= ctx) { set_error("bad pos"); return WIS_E_ARG; }
+  WIS_HIP_CHECK(hipStreamSynchronize(m->st));
+  WIS_RET(single_row_setup(m, Mrows, std::vector<int>(Mrows, 100), pos));
+  WIS_HIP_CHECK(hipMemsetAsync(m->d_prof, 0, 8 * 16 * 8, m->st));
+  WIS_RET(dec_forward(m, Mrows, beam, B, false, beam, 1));   // warm
+  m->prof_on = true;
+  int rc = dec_forward(m, Mrows, beam, B, false, beam, 1);
+  m->prof_on = false;
+  WIS_RET(rc);
+  // API order: QKV gemv, out-proj gemv, cross-attn, self-attn, FFN1 gemv, FFN2 gemv  <-  rows 0, 2, 4, 1, 6, 7
+  // (more than 8 rows - the batched-row kernels, round 6: the fourth slot carries the cross-attention output projection (row 5); the attention
+  // kernels' stamps are the one-utterance forms' and stay empty there)
+  static const int rows_small[6] = {0, 2, 4, 1, 6, 7}, rows_frag[6] = {0, 2, 4, 5, 6, 7};
+  const int* rows = Mrows > 8 ? rows_frag : rows_small;
+  for (int i = 0; i < 6; ++i)
+    WIS_HIP_CHECK(hipMemcpyAsync(out + i * 16, m->d_prof + rows[i] * 16, 16 * 8, hipMemcpyDeviceToHost, m->st));
+  bool gave_up = false;
+  WIS_RET(spin_gave_up(m, &gave_up));      // (synchronises the stream; a raised flag is consumed here, not by the next wis_generate)
+  if (gave_up) { set_error("wis_debug_phase_cycles: the granule hand-off gave up during the tap; stamps are not valid"); return WIS_E_STATE; }
+  return WIS_OK;
+}
+
+int wis_debug_sampling_cycles(wis_model_t* m, uint64_t* out) {
+  if (!m || !out) { set_error("wis_debug_sampling_cycles: bad argument"); return WIS_E_ARG; }
+  if (!WIS_TAPS) { set_error("tuning taps are not compiled in (rebuild with WIS_EXTRA_HIPFLAGS=-DWIS_TAPS=1)"); return WIS_E_UNSUPPORTED; }
+  WIS_HIP_CHECK(hipSetDevice(m->device));
+  WIS_HIP_CHECK(hipMemcpy(out, m->d_prof + (size_t)m->cfg.n_dec_layers * 8 * 16, 2 * 16 * 8, hipMemcpyDeviceToHost));
+  return WIS_OK;
+}
+
+int wis_debug_timeline(wis_model_t* m, int B, int beam, int pos, int use_graph, uint64_t* out, int n_out) {
+  if (!m || !out) { set_error("wis_debug_timeline: bad argument"); return WIS_E_ARG; }
+  if (!WIS_TAPS) { set_error("tuning taps are not compiled in (rebuild with WIS_EXTRA_HIPFLAGS=-DWIS_TAPS=1)"); return WIS_E_UNSUPPORTED; }
+  WIS_ENTER(m, "wis_debug_timeline")
+  WIS_HIP_CHECK(hipSetDevice(m->device));
+  WIS_RET(check_batch(m, B, beam));
+  SpinClaim claim(m, B);
+  const int Mrows = B * beam, ctx = m->cfg.n_text_ctx, nk = m->cfg.n_dec_layers * 8;
+  if (pos < 0 || pos >= ctx || n_out < nk) { set_error("wis_debug_timeline: bad pos / out size (need %d rows)", nk); return WIS_E_ARG; }
+  WIS_HIP_CHECK(hipStreamSynchronize(m->st));
+  WIS_RET(single_row_setup(m, Mrows, std::vector<int>(Mrows, 100), pos));
+  std::vector<unsigned long long> init((size_t)nk * 16, 0ull);
+  for (int k = 0; k < nk; ++k) init[(size_t)k * 16 + 14] = ~0ull;
+  m->prof_on = true; m->prof_all = true;
+  int rc = WIS_OK;
+  hipGraph_t g = nullptr; hipGraphExec_t gx = nullptr;
+  do {
+    if (use_graph) {
+      if (hipStreamBeginCapture(m->st, hipStreamCaptureModeThreadLocal) != hipSuccess) { set_error("capture failed"); rc = WIS_E_HIP; break; }
+      rc = dec_forward(m, Mrows, beam, B, true, beam, 1);
+      if (hipStreamEndCapture(m->st, &g) != hipSuccess || rc) { if (!rc) { set_error("end capture failed"); rc = WIS_E_HIP; } break; }
+      if (hipGraphInstantiate(&gx, g, nullptr, nullptr, 0) != hipSuccess) { set_error("instantiate failed"); rc = WIS_E_HIP; break; }
+    }
+    for (int it = 0; it < 3 && !rc; ++it) {   // the last iteration is the one reported
+      if (hipMemcpyAsync(m->d_prof, init.data(), init.size() * 8, hipMemcpyHostToDevice, m->st) != hipSuccess) { rc = WIS_E_HIP; break; }
+      hipStreamSynchronize(m->st);
+      if (use_graph) { if (hipGraphLaunch(gx, m->st) != hipSuccess) { set_error("graph launch failed"); rc = WIS_E_HIP; } }
+      else rc = dec_forward(m, Mrows, beam, B, true, beam, 1);
+      hipStreamSynchronize(m->st);
+    }
+  } while (0);
+  m->prof_on = false; m->prof_all = false;
+  if (gx) hipGraphExecDestroy(gx);
+  if (g) hipGraphDestroy(g);
+  WIS_RET(rc);
+  { bool gave_up = false; WIS_RET(spin_gave_up(m, &gave_up)); if (gave_up) { set_error("wis_debug_timeline: the granule hand-off gave up during the tap"); return WIS_E_STATE; } }
+  std::vector<unsigned long long> h((size_t)nk * 16);
+  WIS_HIP_CHECK(hipMemcpy(h.data(), m->d_prof, h.size() * 8, hipMemcpyDeviceToHost));
+  for (int k = 0; k < nk; ++k) { out[2 * k] = h[(size_t)k * 16 + 14]; out[2 * k + 1] = h[(size_t)k * 16 + 15]; }
+  return WIS_OK;
+}
+
+int wis_bench_weight_stream(wis_model_t* m, int M, int passes, float* total_ms, int* launches_per_pass, double* bytes_per_pass) {
+  if (!m || M < 1 || M > MAX_ROWS || passes < 1 || !total_ms) { set_error("wis_bench_weight_stream: bad argument"); return WIS_E_ARG; }
+  WIS_ENTER(m, "wis_bench_weight_stream")
+  WIS_HIP_CHECK(hipSetDevice(m->device));
+  const int d = m->cfg.d_model; hipStream_t st = m->st;
+  int launches = 0; double bytes = 0;
+  const StepRoute rt = small_route(m, M);      // dec_forward's route at this row count
+  const bool frag = rt.frag, ln16 = rt.ln16;
+  // one projection alone, by the step's route, on zero rows (K = d: the layer input, K = 4d: the FFN hidden rows), into the logits buffer.  (ln16: every
+  // LayerNorm-folded matrix reads the f16 rows here, cross-Q too - the step runs cross-Q inside the fused stage and has no such launch of its own)
+  auto stream = [&](const DecProj& p, bool count) -> int {
+    if (count) { ++launches; bytes += (double)p.N * p.K * (m->w8 ? 1 : 2); }
+    const bool ln = p.csum != nullptr;
+    if (frag) {
+      GemvP g = gemv_frag(p, p.K == d ? m->dxf : m->dhxf, M, (ln ? GV_LN : 0) | GV_OUT_F32);
+      g.y = m->logits; g.stat_in = m->dstat;
+      return launch_gemv_frag(st, g);
+    }
+    if (ln && ln16) return launch_gemv(st, gemv_small(p, m->dxh, m->logits, M, GV_LN16 | GV_OUT_F32));
+    return launch_gemv(st, gemv_small(p, ln ? (const void*)m->dx : (const void*)m->dh, m->logits, M, (ln ? GV_LN : 0) | GV_OUT_F32));
+  };
+  auto pass = [&](bool count) -> int {      // every layer's six matrices in step order, then the vocabulary projection
+    for (const DecLayerW& w : m->dec) for (const DecProj* p : w.streamed()) WIS_RET(stream(*p, count));
+    return stream(m->proj, count);
+  };
+  if (frag) {       // zero rows: fragment image of zeros (allocation state), partial sums of zeros
+    WIS_HIP_CHECK(hipMemsetAsync(m->dxf, 0, (size_t)(d / 32) * (MAX_ROWS / 16) * 64 * 8 * 2, st));
+    WIS_HIP_CHECK(hipMemsetAsync(m->dhxf, 0, (size_t)(4 * d / 32) * (MAX_ROWS / 16) * 64 * 8 * 2, st));
+    WIS_HIP_CHECK(hipMemsetAsync(m->dstat, 0, (size_t)MAX_ROWS * (d / 16) * 2 * 4, st));
+  }
+  WIS_HIP_CHECK(hipMemsetAsync(m->dx, 0, (size_t)MAX_ROWS * d * 4, st));
+  WIS_HIP_CHECK(hipMemsetAsync(m->dh, 0, (size_t)MAX_ROWS * 4 * d * 2, st));
+  if (ln16) {
+    WIS_HIP_CHECK(hipMemsetAsync(m->dxh, 0, (size_t)MAX_ROWS * d * 2, st));
+    WIS_HIP_CHECK(hipMemsetAsync(m->dstat, 0, (size_t)MAX_ROWS * (d / 16) * 2 * 4, st));
+  }
+  WIS_RET(pass(true));   // warm-up pass (also counts launches / bytes)
+  // the timed passes run the way the product runs these kernels: captured once into a HIP graph and replayed (wis_generate replays
+  // its decode step as a graph); WIS_NO_GRAPH=1 (profilers that cannot follow a capture) falls back to eager launches
+  hipGraph_t graph = nullptr; hipGraphExec_t gexec = nullptr;
+  if (m->use_graph) {
+    WIS_HIP_CHECK(hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal));
+    const int rc = pass(false);
+    const hipError_t e = hipStreamEndCapture(st, &graph);
+    if (rc || e != hipSuccess) { if (graph) hipGraphDestroy(graph); if (rc) return rc; set_error("weight-stream tap: graph capture failed: %s", hipGetErrorString(e)); return WIS_E_HIP; }
+    if (hipGraphInstantiate(&gexec, graph, nullptr, nullptr, 0) != hipSuccess) { hipGraphDestroy(graph); set_error("weight-stream tap: graph instantiate failed"); return WIS_E_HIP; }
+    hipGraphDestroy(graph);
+    if (hipGraphLaunch(gexec, st) != hipSuccess) { hipGraphExecDestroy(gexec); set_error("weight-stream tap: graph launch failed"); return WIS_E_HIP; }      // untimed first replay
+  }
+  int rc2 = WIS_OK;
+  hipError_t e2 = hipEventRecord(m->ev[6], st);
+  for (int i = 0; i < passes && !rc2 && e2 == hipSuccess; ++i) { if (gexec) e2 = hipGraphLaunch(gexec, st); else rc2 = pass(false); }
+  if (e2 == hipSuccess) e2 = hipEventRecord(m->ev[7], st);
+  if (e2 == hipSuccess) e2 = hipStreamSynchronize(st);
+  if (gexec) hipGraphExecDestroy(gexec);
+  WIS_RET(rc2);
+  WIS_HIP_CHECK(e2);
+  WIS_HIP_CHECK(hipEventElapsedTime(total_ms, m->ev[6], m->ev[7]));
+  if (launches_per_pass) *launches_per_pass = launches;
+  if (bytes_per_pass) *bytes_per_pass = bytes;
+  return WIS_OK;
+}
+
+// ---- raw device helpers + single-kernel entry points -----------------------------------
+int wis_dev_alloc(int device, size_t bytes, void** out) {
+  DeviceCtx* c; WIS_RET(get_ctx(device, &c));
+  WIS_HIP_CHECK(hipMalloc(out, bytes ? bytes : 16)); return WIS_OK;
+}
+int wis_dev_free(int device, void* p) { DeviceCtx* c; WIS_RET(get_ctx(device, &c)); WIS_HIP_CHECK(hipFree(p)); return WIS_OK; }
+int wis_dev_h2d(int device, void* dst, const void* src, size_t bytes) { DeviceCtx* c; WIS_RET(get_ctx(device, &c)); WIS_HIP_CHECK(hipMemcpy(dst, src, bytes, hipMemcpyHostToDevice)); return WIS_OK; }
+int wis_dev_d2h(int device, void* dst, const void* src, size_t bytes) { DeviceCtx* c; WIS_RET(get_ctx(device, &c)); WIS_HIP_CHECK(hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost)); return WIS_OK; }
+int wis_dev_sync(int device) { DeviceCtx* c; WIS_RET(get_ctx(device, &c)); WIS_HIP_CHECK(hipDeviceSynchronize()); return WIS_OK; }
+int wis_dev_copy_peer(int dst_device, void* dst, int src_device, const void* src, size_t bytes) {
+  if (!dst || !src) { set_error("wis_dev_copy_peer: bad argument"); return WIS_E_ARG; }
+  DeviceCtx* c; WIS_RET(get_ctx(src_device, &c)); WIS_RET(get_ctx(dst_device, &c));      // both devices exist; current = dst
+  if (src_device != dst_device) {
+    int can = 0;
+    if (hipDeviceCanAccessPeer(&can, dst_device, src_device) == hipSuccess && can) {
+      hipError_t e = hipDeviceEnablePeerAccess(src_device, 0);                            // direct xGMI path; already-enabled is fine
+      if (e != hipSuccess && e != hipErrorPeerAccessAlreadyEnabled) (void)hipGetLastError();
+    }
+  }
+  WIS_HIP_CHECK(hipMemcpyPeer(dst, dst_device, src, src_device, bytes));
+  return WIS_OK;
+}
+
+int wis_op_gemm(int device, const void* A, int lda, const void* W, const float* bias, const float* residual, void* C, int M, int N, int K, int flags) {
+  DeviceCtx* c; WIS_RET(get_ctx(device, &c));
+  std::lock_guard<std::mutex> op_lock(ctx_op_mutex(c));
+  hipStream_t st = ctx_stream(c);
+  if (flags & 8) {   // split-K = 2 path of the encoder's FFN2: requires bias, residual and fp32 output
+    if (!bias || !residual || (flags & 7) != (2 | 4)) { set_error("wis_op_gemm: split-K needs bias, residual, flags 2|4|8"); return WIS_E_ARG; }
+    float* scratch = nullptr;
+    WIS_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&scratch), (size_t)2 * M * N * 4));
+    int rc = launch_gemm_splitk_resid(st, gemm_plain(reinterpret_cast<const f16*>(A), lda, reinterpret_cast<const f16*>(W), M, N, K), 2, scratch, bias, residual,
+                                      reinterpret_cast<float*>(C));
+    hipError_t e = hipStreamSynchronize(st);
+    hipFree(scratch);
+    if (rc) return rc;
+    if (e != hipSuccess) { set_error("wis_op_gemm: %s", hipGetErrorString(e)); return WIS_E_HIP; }
+    return WIS_OK;
+  }
+  WIS_RET(launch_gemm_generic(st, gemm_plain(reinterpret_cast<const f16*>(A), lda, reinterpret_cast<const f16*>(W), M, N, K), bias, residual, C, flags));
+  WIS_HIP_CHECK(hipGetLastError());
+  WIS_HIP_CHECK(hipStreamSynchronize(st));
+  return WIS_OK;
+}
+int wis_op_layernorm(int device, const float* x, const float* gamma, const float* beta, void* y, int M, int d) {
+  DeviceCtx* c; WIS_RET(get_ctx(device, &c));
+  std::lock_guard<std::mutex> op_lock(ctx_op_mutex(c));
+  WIS_RET(launch_layernorm(ctx_stream(c), x, gamma, beta, reinterpret_cast<f16*>(y), M, d));
+  WIS_HIP_CHECK(hipGetLastError());
+  WIS_HIP_CHECK(hipStreamSynchronize(ctx_stream(c)));
+  return WIS_OK;
+}
+int wis_op_enc_attention(int device, const void* qk, const void* vt, void* out, int B, int T, int Tpad, int H) {
+  DeviceCtx* c; WIS_RET(get_ctx(device, &c));
+  std::lock_guard<std::mutex> op_lock(ctx_op_mutex(c));
+  // same rule as the encoder: the split-key form (two workgroups per query tile and head, in-launch merge) at small grids
+  hipStream_t st = ctx_stream(c);
+  float* part = nullptr; unsigned* counters = nullptr;
+  const size_t ncnt = (size_t)B * H * cdiv(T, 128);
+  int rc = WIS_OK;
+  if (hipMalloc(reinterpret_cast<void**>(&part), enc_attention_part_floats(B, T, H) * 4) != hipSuccess ||
+      hipMalloc(reinterpret_cast<void**>(&counters), ncnt * 4) != hipSuccess) { set_error("wis_op_enc_attention: out of device memory"); rc = WIS_E_NOMEM; }
+  f16* qk2 = nullptr;      // the lazy-reference loop wants log2(e) on Q as well (the engine folds it into the projection): a scaled private copy
+  if (!rc && enc_attn_lazy()) {
+    const size_t n = (size_t)B * T * 2 * H * 64;
+    if (hipMalloc(reinterpret_cast<void**>(&qk2), n * 2) != hipSuccess) { set_error("wis_op_enc_attention: out of device memory"); rc = WIS_E_NOMEM; }
+    else {
+      hipMemcpyAsync(qk2, qk, n * 2, hipMemcpyDeviceToDevice, st);
+      launch_scale_q_log2e(st, qk2, (int64_t)B * T, H * 64);
+    }
+  }
+  if (!rc) {
+    hipMemsetAsync(counters, 0, ncnt * 4, st);
+    rc = launch_enc_attention(st, qk2 ? qk2 : reinterpret_cast<const f16*>(qk), reinterpret_cast<const f16*>(vt), reinterpret_cast<f16*>(out), B, T, Tpad, H, part, counters, ncnt);
+  }
+  hipError_t e = hipStreamSynchronize(st);
+  hipFree(part); hipFree(counters); hipFree(qk2);
+  if (rc) return rc;
+  if (e != hipSuccess) { set_error("wis_op_enc_attention: %s", hipGetErrorString(e)); return WIS_E_HIP; }
+  return WIS_OK;
+}
+int wis_op_gemv(int device, const void* x, const float* gamma, const float* beta, const void* W, const float* bias, void* y, int M, int N, int K, int flags) {
+  DeviceCtx* c; WIS_RET(get_ctx(device, &c));
+  std::lock_guard<std::mutex> op_lock(ctx_op_mutex(c));
+  hipStream_t st = ctx_stream(c);
+  if (flags & GV_QKV) { set_error("wis_op_gemv: flag 16 is internal"); return WIS_E_ARG; }
+  const int Npad = cdiv(N, gemv_rows_for(N, K)) * gemv_rows_for(N, K);
+  // (tap flags: 32 = quantise the matrix to 8 bits per weight first; 64 = GV_LN16: x is the F16 copy of the rows, LayerNorm folded)
+  const bool w8 = flags & 32, ln16 = (flags & GV_LN16) != 0, ln = (flags & GV_LN) || ln16;
+  flags &= ~32;
+  if (ln16 && ((flags & GV_LN) || M > 8 || w8)) { set_error("wis_op_gemv: flag 64 (LayerNorm fold on f16 rows): <= 8 rows, f16 weights, without flag 8"); return WIS_E_ARG; }
+  if (ln && (!gamma || !beta)) { set_error("wis_op_gemv: flags 8 / 64 need gamma and beta"); return WIS_E_ARG; }
+  // the same preparation the model loader does: optional LayerNorm fold into a private copy of W / bias, then packing
+  f16 *wp = nullptr, *wtmp = nullptr, *xfr = nullptr; float *wsc = nullptr, *b2 = nullptr, *cs = nullptr, *stt = nullptr;
+  int rc = WIS_OK;
+  do {
+    if (hipMalloc(reinterpret_cast<void**>(&wp), (size_t)Npad * K * 2) != hipSuccess || hipMalloc(reinterpret_cast<void**>(&wtmp), (size_t)N * K * 2) != hipSuccess ||
+        hipMalloc(reinterpret_cast<void**>(&b2), (size_t)Npad * 4) != hipSuccess || hipMalloc(reinterpret_cast<void**>(&cs), (size_t)Npad * 4) != hipSuccess ||
+        (w8 && hipMalloc(reinterpret_cast<void**>(&wsc), (size_t)Npad * 4) != hipSuccess)) { set_error("wis_op_gemv: out of device memory"); rc = WIS_E_NOMEM; break; }
+    hipMemcpyAsync(wtmp, W, (size_t)N * K * 2, hipMemcpyDeviceToDevice, st);
+    hipMemsetAsync(b2, 0, (size_t)Npad * 4, st); hipMemsetAsync(cs, 0, (size_t)Npad * 4, st);
+    if (bias) hipMemcpyAsync(b2, bias, (size_t)N * 4, hipMemcpyDeviceToDevice, st);
+    const int rows = gemv_rows_for(N, K);
+    if ((rc = prep_projection(st, wtmp, N, Npad, K, 0, 1.f, ln ? gamma : nullptr, beta, b2, cs, wp, wsc, rows))) break;      // (wsc: allocated for the 8-bit form only)
+    GemvP g; memset(&g, 0, sizeof(g));
+    g.x = x; g.csum = ln ? cs : nullptr; g.Wp = wp; g.wscale = wsc; g.bias = (bias || ln) ? b2 : nullptr; g.y = y; g.M = M; g.N = N; g.K = K; g.flags = flags; g.rows = rows;
+    if (M > 8) {
+      // the product's batched route (dec_forward_frag): activations as a fragment image, LayerNorm statistics as row partials
+      const int MBf = cdiv(M, 16);
+      if (hipMalloc(reinterpret_cast<void**>(&xfr), (size_t)(K / 32) * MBf * 64 * 8 * 2) != hipSuccess ||
+          (ln && hipMalloc(reinterpret_cast<void**>(&stt), (size_t)M * (K / 16) * 2 * 4) != hipSuccess)) { set_error("wis_op_gemv: out of device memory"); rc = WIS_E_NOMEM; break; }
+      hipMemsetAsync(xfr, 0, (size_t)(K / 32) * MBf * 64 * 8 * 2, st);
+      if ((rc = launch_xf_pack(st, x, ln ? 0 : 1, xfr, ln ? stt : nullptr, M, K, MBf))) break;
+      g.x = xfr; g.xmb = MBf; g.stat_in = stt;
+      float* kp = nullptr; unsigned* kc = nullptr;
+      if (!ln && K >= 4096 && (K / 32) % 16 == 0) {      // the product's rule for the K = 4d projection: four K slices per n-tile, merged in the launch
+        const size_t nt = (size_t)cdiv(N, 16);
+        if (hipMalloc(reinterpret_cast<void**>(&kp), nt * 4 * MBf * 64 * 16) != hipSuccess || hipMalloc(reinterpret_cast<void**>(&kc), nt * 4) != hipSuccess) {
+          hipFree(kp); set_error("wis_op_gemv: out of device memory"); rc = WIS_E_NOMEM; break; }
+        hipMemsetAsync(kc, 0, nt * 4, st);
+        g.ksplit = 4; g.kpart = kp; g.kcnt = kc;
+        if (!(flags & GV_RESID)) rc = launch_gemv_frag(st, g);      // a first launch on the same tickets: they must re-arm themselves
+      }
+      if (!rc) rc = launch_gemv_frag(st, g);
+      hipStreamSynchronize(st);
+      hipFree(kp); hipFree(kc);
+      break;
+    }
+    rc = launch_gemv(st, g);
+  } while (0);
+  hipError_t e = hipStreamSynchronize(st);
+  hipFree(wp); hipFree(wtmp); hipFree(b2); hipFree(cs); hipFree(wsc); hipFree(xfr); hipFree(stt);
+  if (rc) return rc;
+  if (e != hipSuccess) { set_error("wis_op_gemv: %s", hipGetErrorString(e)); return WIS_E_HIP; }
+  return WIS_OK;
+}
+
+int wis_op_dec_self_attn(int device, const float* q, const void* kc, const void* vc, const int32_t* pos, void* out,
+                         int M, int H, int ctx, int rpu, int sstride, int rmul) {
+  DeviceCtx* c; WIS_RET(get_ctx(device, &c));
+  std::lock_guard<std::mutex> op_lock(ctx_op_mutex(c));
+  if (!q || !kc || !vc || !pos || !out || M < 1 || H < 1 || rpu < 1) { set_error("wis_op_dec_self_attn: bad argument"); return WIS_E_ARG; }
+  SelfAttnP sa;
+  sa.q = q; sa.kc = reinterpret_cast<const f16*>(kc); sa.vc = reinterpret_cast<const f16*>(vc); sa.pos = pos; sa.out = reinterpret_cast<f16*>(out);
+  sa.M = M; sa.H = H; sa.d = 64 * H; sa.ctx = ctx; sa.rpu = rpu; sa.sstride = sstride; sa.rmul = rmul;
+  WIS_RET(launch_dec_self_attn(ctx_stream(c), sa));
+  WIS_HIP_CHECK(hipGetLastError());
+  WIS_HIP_CHECK(hipStreamSynchronize(ctx_stream(c)));
+  return WIS_OK;
+}
+int wis_op_dec_self_attn_ex(int device, const float* q, const void* kc, const void* vc, const int32_t* pos, void* out,
+                            int M, int H, int ctx, int rpu, int sstride, int rmul, int nb, int out_mb,
+                            const int32_t* anc, int w0, int aw, const int32_t* base) {
+  DeviceCtx* c; WIS_RET(get_ctx(device, &c));
+  std::lock_guard<std::mutex> op_lock(ctx_op_mutex(c));
+  if (!q || !kc || !vc || !pos || !out || M < 1 || H < 1 || rpu < 1 || (nb != 2 && nb != 4 && nb != 8) || (out_mb && out_mb < cdiv(M, 16)) || (base && !anc)) {
+    set_error("wis_op_dec_self_attn_ex: bad argument"); return WIS_E_ARG; }
+  hipStream_t st = ctx_stream(c);
+  const int d = 64 * H;
+  if (out_mb) WIS_HIP_CHECK(hipMemsetAsync(out, 0, (size_t)(d / 32) * out_mb * 64 * 8 * 2, st));      // the fragment image's rows beyond M stay zero
+  SelfAttnP sa;
+  sa.q = q; sa.kc = reinterpret_cast<const f16*>(kc); sa.vc = reinterpret_cast<const f16*>(vc); sa.pos = pos; sa.out = reinterpret_cast<f16*>(out);
+  sa.M = M; sa.H = H; sa.d = d; sa.ctx = ctx; sa.rpu = rpu; sa.sstride = sstride; sa.rmul = rmul; sa.out_mb = out_mb; sa.anc = anc; sa.w0 = w0; sa.aw = aw; sa.base = base; sa.nb = nb;
+  WIS_RET(launch_dec_self_attn(st, sa));
+  WIS_HIP_CHECK(hipGetLastError());
+  WIS_HIP_CHECK(hipStreamSynchronize(st));
+  return WIS_OK;
+}
+static int op_dec_cross_attn(int device, const float* q, const float* xres, const float* qcs, const float* qb, const void* kx, const void* vt, void* out,
+                             int B, int R, int H, int T, int chunks, const float* q2 = nullptr, int xres_is_stat = 0, int out_mb = 0, int kv_shared = 0, bool no_spin = false) {
+  DeviceCtx* c; WIS_RET(get_ctx(device, &c));
+  std::lock_guard<std::mutex> op_lock(ctx_op_mutex(c));
+  if (!q || !kx || !vt || !out || B < 1 || H < 1 || T < 1) { set_error("wis_op_dec_cross_attn: bad argument"); return WIS_E_ARG; }
+  hipStream_t st = ctx_stream(c);
+  float* part = nullptr; unsigned* counters = nullptr; unsigned long long* gran = nullptr; unsigned* epoch = nullptr;
+  int rc = WIS_OK;
+  if (out_mb && out_mb < cdiv(B * R, 16)) { set_error("wis_op_dec_cross_attn: %d row blocks for %d rows", out_mb, B * R); return WIS_E_ARG; }
+  const bool small = B * H <= CA_SPIN_MAX_BH && !no_spin;      // the product's rule: the granule hand-off on small grids (launch_dec_cross_attn decides by chunking / rows)
+  if (hipMalloc(reinterpret_cast<void**>(&part), (size_t)B * H * 16 * 16 * 66 * 4) != hipSuccess ||
+      hipMalloc(reinterpret_cast<void**>(&counters), (size_t)B * H * 4) != hipSuccess ||
+      (small && (hipMalloc(reinterpret_cast<void**>(&gran), (size_t)B * H * 6 * 8 * 66 * 8) != hipSuccess || hipMalloc(reinterpret_cast<void**>(&epoch), ((size_t)B * H + 1) * 4) != hipSuccess))) {
+    set_error("wis_op_dec_cross_attn: out of device memory"); rc = WIS_E_NOMEM; }
+  unsigned flag = 0;
+  if (!rc) {
+    hipMemsetAsync(counters, 0, (size_t)B * H * 4, st);
+    if (small) { hipMemsetAsync(gran, 0, (size_t)B * H * 6 * 8 * 66 * 8, st); hipMemsetAsync(epoch, 0, ((size_t)B * H + 1) * 4, st); }
+    if (out_mb) hipMemsetAsync(out, 0, (size_t)(64 * H / 32) * out_mb * 64 * 8 * 2, st);      // the fragment image's rows beyond B * R stay zero
+    CrossAttnP ca;
+    ca.q = q; ca.kx = reinterpret_cast<const f16*>(kx); ca.vt = reinterpret_cast<const f16*>(vt); ca.out = reinterpret_cast<f16*>(out); ca.part = part; ca.counters = counters;
+    ca.B = B; ca.R = R; ca.H = H; ca.d = 64 * H; ca.T = T; ca.Tpad = cdiv(T, 64) * 64; ca.chunks = chunks; ca.out_mb = out_mb; ca.xres = xres; ca.qcs = qcs; ca.qb = qb;
+    ca.gran = gran; ca.epoch = epoch; ca.q2 = q2; ca.xres_is_stat = xres_is_stat; ca.kv_shared = kv_shared;
+    for (int rep = 0; rep < 3 && !rc; ++rep) rc = launch_dec_cross_attn(st, ca);      // three launches: the epochs of the granule form advance from launch to launch
+    if (small && !rc) hipMemcpyAsync(&flag, epoch, 4, hipMemcpyDeviceToHost, st);
+  }
+  hipError_t e = hipStreamSynchronize(st);
+  hipFree(part); hipFree(counters); hipFree(gran); hipFree(epoch);
+  if (rc) return rc;
+  if (flag) { set_error("wis_op_dec_cross_attn: granule hand-off timed out"); return WIS_E_HIP; }
+  if (e != hipSuccess) { set_error("wis_op_dec_cross_attn: %s", hipGetErrorString(e)); return WIS_E_HIP; }
+  return WIS_OK;
+}
+int wis_op_dec_cross_attn(int device, const float* q, const void* kx, const void* vt, void* out, int B, int R, int H, int T, int chunks) {
+  return op_dec_cross_attn(device, q, nullptr, nullptr, nullptr, kx, vt, out, B, R, H, T, chunks);
+}
+int wis_op_dec_cross_attn_folded(int device, const float* q_raw, const float* xres, const float* qcs, const float* qb, const void* kx, const void* vt, void* out,
+                                 int B, int R, int H, int T, int chunks) {
+  if (!xres || !qcs || !qb) { set_error("wis_op_dec_cross_attn_folded: bad argument"); return WIS_E_ARG; }
+  return op_dec_cross_attn(device, q_raw, xres, qcs, qb, kx, vt, out, B, R, H, T, chunks);
+}
+int wis_op_dec_cross_attn_stat(int device, const float* q, const float* q2, const float* stat, const float* qcs, const float* qb, const void* kx, const void* vt, void* out,
+                               int B, int R, int H, int T, int chunks, int out_mb, int kv_shared, int no_spin) {
+  if (stat ? (!qcs || !qb) : (qcs || qb || q2)) { set_error("wis_op_dec_cross_attn_stat: the fold takes partials, column sums and bias together; the plain form none of them"); return WIS_E_ARG; }
+  return op_dec_cross_attn(device, q, stat, qcs, qb, kx, vt, out, B, R, H, T, chunks, q2, stat ? 1 : 0, out_mb, kv_shared, no_spin != 0);
+}
+
+}  // extern "C"
+
+// private device scratch of a tap: freed when the tap returns
+namespace {
+struct TapScratch {
+  std::vector<void*> ptrs;
+  template <class T> bool get(T** p, size_t n_elems) {
+    void* q = nullptr;
+    if (hipMalloc(&q, n_elems * sizeof(T) ? n_elems * sizeof(T) : 16) != hipSuccess) return false;
+    ptrs.push_back(q); *p = reinterpret_cast<T*>(q); return true;
+  }
+  ~TapScratch() { for (void* q : ptrs) hipFree(q); }
+};
+}  // namespace
+
+extern "C" {
+
+int wis_op_gemv_qkv(int device, const float* x, const float* gamma, const float* beta, const void* W, const float* bias, const int32_t* slot, const int32_t* pos,
+                    float* q, void* kc, void* vc, int M, int d, int ctx) {
+  DeviceCtx* c; WIS_RET(get_ctx(device, &c));
+  std::lock_guard<std::mutex> op_lock(ctx_op_mutex(c));
+  if (!x || !gamma || !beta || !W || !bias || !slot || !pos || !q || !kc || !vc || M < 1 || M > MAX_ROWS || d < 128 || d % 128 || ctx < 1) { set_error("wis_op_gemv_qkv: bad argument"); return WIS_E_ARG; }
+  hipStream_t st = ctx_stream(c);
+  const int N = 3 * d, MB = cdiv(M, 16);
+  const float qs = 0.125f;
+  TapScratch ts;
+  f16 *wp = nullptr, *wtmp = nullptr, *xf = nullptr; float *b2 = nullptr, *cs = nullptr, *stt = nullptr;
+  if (!ts.get(&wp, (size_t)N * d) || !ts.get(&wtmp, (size_t)N * d) || !ts.get(&b2, (size_t)N) || !ts.get(&cs, (size_t)N) ||
+      (M > 8 && (!ts.get(&xf, (size_t)(d / 32) * MB * 64 * 8) || !ts.get(&stt, (size_t)M * (d / 16) * 2)))) { set_error("wis_op_gemv_qkv: out of device memory"); return WIS_E_NOMEM; }
+  int rc = WIS_OK;
+  do {
+    // what load_weights does for a layer's DecProj `qkv` (w.qkv): the bias's query part scaled, the LayerNorm folded, the query rows scaled by the packer
+    hipMemcpyAsync(wtmp, W, (size_t)N * d * 2, hipMemcpyDeviceToDevice, st);
+    hipLaunchKernelGGL(convert_kernel, dim3(blocks_for(N)), dim3(256), 0, st, bias, 0, b2, 0, (int64_t)N, (int64_t)1, (int64_t)1, (int64_t)d, qs);
+    hipMemsetAsync(cs, 0, (size_t)N * 4, st);
+    const DecProj qkv{wp, nullptr, b2, cs, N, d, gemv_rows_for(N, d)};
+    if ((rc = prep_projection(st, wtmp, N, N, d, d, qs, gamma, beta, b2, cs, wp, nullptr, qkv.rows))) break;
+    GemvP g;
+    if (M <= 8) g = gemv_small(qkv, x, nullptr, M, GV_LN | GV_QKV);      // dec_forward
+    else {
+      // dec_forward_frag: the rows as a fragment image, their LayerNorm statistics as row partials
+      hipMemsetAsync(xf, 0, (size_t)(d / 32) * MB * 64 * 8 * 2, st);
+      if ((rc = launch_xf_pack(st, x, 0, xf, stt, M, d, MB))) break;
+      g = gemv_frag(qkv, xf, M, GV_LN | GV_QKV);
+      g.stat_in = stt;
+    }
+    g.q = q; g.kc = reinterpret_cast<f16*>(kc); g.vc = reinterpret_cast<f16*>(vc); g.slot = slot; g.pos = pos; g.d = d; g.ctx = ctx;
+    rc = M <= 8 ? launch_gemv(st, g) : launch_gemv_frag(st, g);
+  } while (0);
+  hipError_t e = hipStreamSynchronize(st);
+  if (rc) return rc;
+  if (e != hipSuccess) { set_error("wis_op_gemv_qkv: %s", hipGetErrorString(e)); return WIS_E_HIP; }
+  return WIS_OK;
+}
+
+int wis_op_gemv_out_cq(int device, const void* a, const float* x0, const void* Wo, const float* bo, const void* Wq, const float* bq, const float* gamma, const float* beta,
+                       float* x1, float* stat, float* q, float* q2, float* qcs, float* qb, int M, int d, int force_frag) {
+  DeviceCtx* c; WIS_RET(get_ctx(device, &c));
+  std::lock_guard<std::mutex> op_lock(ctx_op_mutex(c));
+  const bool frag = M > 8 || force_frag;
+  if (!a || !x0 || !Wo || !bo || !Wq || !bq || !gamma || !beta || !x1 || !stat || !q || !qcs || !qb || (frag && !q2) || M < 1 || M > MAX_ROWS || d < 128 || d % 128) {
+    set_error("wis_op_gemv_out_cq: bad argument"); return WIS_E_ARG; }
+  hipStream_t st = ctx_stream(c);
+  const int MB = cdiv(M, 16);
+  const float qs = 0.125f;
+  const size_t img = (size_t)(d / 32) * MB * 64 * 8;
+  TapScratch ts;
+  f16 *wtmp = nullptr, *fcat = nullptr, *fwot = nullptr, *fwqo = nullptr, *p_cqo = nullptr, *p_out = nullptr, *xh = nullptr, *xf = nullptr, *af = nullptr; float* b_cqo = nullptr;
+  if (!ts.get(&wtmp, (size_t)d * d) || !ts.get(&fcat, (size_t)2 * d * d) || !ts.get(&fwot, (size_t)d * d) || !ts.get(&fwqo, (size_t)d * d) || !ts.get(&p_cqo, (size_t)2 * d * d) ||
+      !ts.get(&p_out, (size_t)d * d) || !ts.get(&b_cqo, (size_t)d) || (frag ? (!ts.get(&xf, img) || !ts.get(&af, img)) : !ts.get(&xh, (size_t)M * d))) {
+    set_error("wis_op_gemv_out_cq: out of device memory"); return WIS_E_NOMEM; }
+  int rc = WIS_OK;
+  do {
+    // load_weights, decoder layer: cq (the cross-Q bias scaled, the LayerNorm folded: bias / csum are what the cross-attention kernel takes as qb / qcs), out, then the fold
+    hipMemcpyAsync(wtmp, Wq, (size_t)d * d * 2, hipMemcpyDeviceToDevice, st);
+    hipLaunchKernelGGL(convert_kernel, dim3(blocks_for(d)), dim3(256), 0, st, bq, 0, qb, 0, (int64_t)d, (int64_t)1, (int64_t)1, (int64_t)d, qs);
+    hipMemsetAsync(qcs, 0, (size_t)d * 4, st);
+    DecLayerW w{};
+    w.out = DecProj{p_out, nullptr, bo, nullptr, d, d, gemv_rows_for(d, d)};
+    w.cqo = DecProj{p_cqo, nullptr, b_cqo, nullptr, d, 2 * d, 16};
+    if ((rc = prep_projection(st, wtmp, d, d, d, d, qs, gamma, beta, qb, qcs, nullptr, nullptr, 16))) break;      // (the fold alone: the stage streams w.out and w.cqo)
+    if ((rc = launch_pack_gemv(st, reinterpret_cast<const f16*>(Wo), p_out, d, d, d, 0, 1.f, w.out.rows))) break;
+    if ((rc = build_cq_fold(st, wtmp, Wo, 1, bo, d, qs, fcat, fwot, fwqo, p_cqo, b_cqo))) break;
+    hipMemcpyAsync(x1, x0, (size_t)M * d * 4, hipMemcpyDeviceToDevice, st);      // the residual epilogue works in place
+    if (!frag) {
+      // dec_forward: one dual launch on the f16 rows (the attention output; the f16 copy of the layer input that the embedding / FFN2 epilogues leave)
+      hipLaunchKernelGGL(convert_kernel, dim3(blocks_for((int64_t)M * d)), dim3(256), 0, st, x0, 0, xh, 1, (int64_t)M, (int64_t)d, (int64_t)d, (int64_t)0, 1.f);
+      GemvP ga, gb;
+      out_cq_dual(w, reinterpret_cast<const f16*>(a), xh, x1, stat, q, M, &ga, &gb);
+      rc = launch_gemv_dual(st, ga, gb);
+      break;
+    }
+    // dec_forward_frag: three d x d problems on the fragment images of the layer input and the attention output
+    hipMemsetAsync(xf, 0, img * 2, st); hipMemsetAsync(af, 0, img * 2, st);
+    if ((rc = launch_xf_pack(st, x0, 0, xf, nullptr, M, d, MB))) break;
+    if ((rc = launch_xf_pack(st, a, 1, af, nullptr, M, d, MB))) break;
+    GemvP g3[3];
+    out_cq_frag3(w, af, xf, x1, stat, q, q2, M, g3);
+    rc = launch_gemv_frag3(st, g3, 3);
+  } while (0);
+  hipError_t e = hipStreamSynchronize(st);
+  if (rc) return rc;
+  if (e != hipSuccess) { set_error("wis_op_gemv_out_cq: %s", hipGetErrorString(e)); return WIS_E_HIP; }
+  return WIS_OK;
+}
+
+}  // extern "C"
