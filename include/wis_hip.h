@@ -388,6 +388,35 @@ int wis_op_gemv_out_cq(int device, const void* a_f16, const float* x0, const voi
                        const float* gamma, const float* beta, float* x1, float* stat, float* q, float* q2, float* qcs, float* qb,
                        int M, int d, int force_frag);
 
+/* ---- taps of what the encoder and the cross K/V projection launch (tests/test_gpu_enc_ops.py).  The same rule: arguments and the loader's preparation
+ * only - the GEMM descriptions are the helpers run_encoder itself calls, the tile and kernel are chosen by launch_gemm_* / gemm_pick_tile from the
+ * shape, as in the encoder.  B and T are free (the encoder: T = 3000 / 1500).  All pointers are device memory. */
+/* mel f32 [B][n_mels][3000] -> conv1 input image f16 [B][3002][C] rows 1..3000 (C = 96 for 80 bins, channels 80..95 zero; 128 for 128 bins); rows 0
+ * and 3001 are not written.  Any other n_mels: WIS_E_UNSUPPORTED. */
+int wis_op_mel_to_image(int device, const float* mel, void* img_f16, int B, int n_mels);
+/* the encoder's convs as implicit-im2col GEMMs (kernel 3, padding 1); W [N][Cin][3] f32 or f16 (w_is_f16), packed here as the loader packs it.
+ * which = 1 (stride 1): img f16 [B][T+2][C] (Cin = 80 -> C = 96, K = 320; Cin = 128 -> C = 128, K = 384; anything else WIS_E_UNSUPPORTED) followed
+ *   by 64 readable elements (the zero-weighted columns of the last row read 32 past the image at Cin = 80) -> out f16 [B][T+2][N], GELU(conv + bias)
+ *   at row t + 1; rows 0 and T + 1 of every utterance are not written.  pos unused.
+ * which = 2 (stride 2): img f16 [B][2T+2][Cin] (Cin % 64 == 0) -> out f32 [B*T][N] = GELU(conv + bias) + pos[m % T] (pos f32 [T][N]).
+ * N % 128 == 0. */
+int wis_op_enc_conv(int device, int which, const void* img_f16, const void* W, int w_is_f16, const float* bias, const float* pos, void* out,
+                    int B, int T, int Cin, int N);
+/* the encoder layer's fused QKV projection (d = 64 H): xn f16 [B*T][d], W f16 [3d][d], bias f32 [3d] -> qk f16 [B*T][2d] = [Q | K] rows and the V^T image
+ * vt f16 [B][H][64][Tpad] that wis_op_enc_attention reads (key t at (t & ~12) | ((t & 4) << 1) | ((t & 8) >> 1); Tpad = T rounded up to 64; positions
+ * that belong to no key < T are not written).  T % 4 != 0: WIS_E_ARG (the transposed V tiles store 4 consecutive keys of one utterance). */
+int wis_op_enc_qkv(int device, const void* xn_f16, const void* W_f16, const float* bias, void* qk_f16, void* vt_f16, int B, int T, int H);
+/* every decoder layer's cross-attention K / V projection of the encoder memory in one GEMM: mem f16 [B*T][d], W f16 [L*2d][d] (per layer: d key rows,
+ * then d value rows), bias f32 [L*2d] -> layer l's images at kx + l kx_lstride (f16 [B][H][8][T][8]) and vt + l vt_lstride (f16 [B][H][64][Tpad], keys
+ * >= T not written): what wis_op_dec_cross_attn reads.  Strides in elements, multiples of 8 and at least the image size; T % 4 != 0: WIS_E_ARG. */
+int wis_op_enc_crosskv(int device, const void* mem_f16, const void* W_f16, const float* bias, void* kx_f16, void* vt_f16, int B, int T, int H, int L,
+                       int64_t kx_lstride, int64_t vt_lstride);
+/* the encoder's K-split FFN2 with the fused reduction + LayerNorm: X f32 [M][N] (residual in) += A f16 [M][K] . W f16 [N][K]^T + bias, and
+ * Y f16 [M][N] = LayerNorm(new X) gamma + beta.  splits = 0: what the encoder takes for N = d at M rows (none: WIS_E_UNSUPPORTED); the fused form
+ * exists for 2 and 4 splits and N <= 2048, K % (64 splits) == 0 (otherwise the launch function's error code). */
+int wis_op_gemm_splitk_ln(int device, const void* A_f16, const void* W_f16, const float* bias, float* X, const float* gamma, const float* beta,
+                          void* Y_f16, int M, int N, int K, int splits);
+
 /* ---- speaker verification (replaces the reference's WavLMForXVector embedder, main.py:306-316 / do_sv 797-879): one handle = the
  * WavLM-base-plus-sv x-vector model on one GPU.  Input: mono 16 kHz f32 PCM in host memory, already through the reference's
  * preprocessing (sox gain + trim, the feature extractor's zero-mean / unit-variance normalisation: wis_hip/sv.py); output: the

@@ -73,6 +73,17 @@ __global__ void mel_to_image_kernel(const float* __restrict__ mel, f16* __restri
 // conv1 over the [3002][C] image (C = conv1_channels(n_mels)) as one implicit-im2col GEMM: K = 3C, rounded up to whole 64-deep
 // k-tiles (80 bins: 288 -> 320, the 32 extra columns carry zero weights and read into the next row; 128 bins: 384, no pad)
 static int conv1_k(int n_mels) { return cdiv(3 * conv1_channels(n_mels), 64) * 64; }
+// The convs' GEMM descriptions (run_encoder, and the op taps on shorter images): B utterances of T output rows each; output row t of an
+// utterance starts at row t (conv1, stride 1) / 2 t (conv2, stride 2) of its padded time-major image and runs over three image rows
+static GemmP conv1_gemm(const f16* img, const f16* w, int B, int T, int n_mels, int N) {      // image [B][T + 2][conv1_channels]
+  const int cc = conv1_channels(n_mels);
+  GemmP p; p.klen = 0; p.A = img; p.a_bs = (int64_t)(T + 2) * cc; p.a_rs = cc; p.a_rpb = T; p.W = w; p.M = B * T; p.N = N; p.K = conv1_k(n_mels);
+  return p;
+}
+static GemmP conv2_gemm(const f16* c1, const f16* w, int B, int T, int cin, int N) {      // image [B][2 T + 2][cin]
+  GemmP p; p.klen = 0; p.A = c1; p.a_bs = (int64_t)(2 * T + 2) * cin; p.a_rs = 2 * cin; p.a_rpb = T; p.W = w; p.M = B * T; p.N = N; p.K = 3 * cin;
+  return p;
+}
 // dst[c][r] = src[r][c] as f16 (src f16 or f32, [rows][cols])
 __global__ void transpose_to_f16_kernel(const void* __restrict__ src, int src_f16, f16* __restrict__ dst, int rows, int cols) {
   __shared__ float t[32][33];
@@ -287,6 +298,20 @@ int dalloc(wis_model* m, T** p, size_t n_elems) {
   return WIS_OK;
 }
 inline int blocks_for(int64_t n) { int64_t b = (n + 255) / 256; return (int)(b > 8192 ? 8192 : (b < 1 ? 1 : b)); }
+// the convs' weights [N][cin][3] (f32 or f16) -> the GEMMs' W operand (conv_pack_kernel)
+static void pack_conv1_w(hipStream_t st, const void* src, int src_f16, f16* dst, int N, int n_mels) {
+  const int k1 = conv1_k(n_mels);      // 80 bins: K = 3*96 = 288 padded to 320 = 5 x 64; 128: 384
+  hipLaunchKernelGGL(conv_pack_kernel, dim3(blocks_for((int64_t)N * k1)), dim3(256), 0, st, src, src_f16, dst, N, n_mels, conv1_channels(n_mels), k1);
+}
+static void pack_conv2_w(hipStream_t st, const void* src, int src_f16, f16* dst, int N, int cin) {
+  hipLaunchKernelGGL(conv_pack_kernel, dim3(blocks_for((int64_t)N * 3 * cin)), dim3(256), 0, st, src, src_f16, dst, N, cin, cin, 3 * cin);
+}
+static int launch_mel_to_image(hipStream_t st, const float* mel, f16* img, int B, int n_mels) {
+  if (n_mels == 128) hipLaunchKernelGGL((mel_to_image_kernel<128, 128>), dim3(cdiv(3000, 64), B), dim3(256), 0, st, mel, img);
+  else if (n_mels == 80) hipLaunchKernelGGL((mel_to_image_kernel<80, 96>), dim3(cdiv(3000, 64), B), dim3(256), 0, st, mel, img);
+  else { set_error("mel_to_image: %d mel bins (80 or 128)", n_mels); return WIS_E_UNSUPPORTED; }
+  return WIS_OK;
+}
 
 struct TensorSrc { const void* p; int f16; int64_t rows, cols; };
 
@@ -400,12 +425,11 @@ int load_weights(wis_model* m, const Loader& L) {
     {
       TensorSrc s;
       if ((rc = L.get("encoder/conv1/weight", d, (int64_t)c.n_mels * 3, &s))) break;
-      const int cc = conv1_channels(c.n_mels), k1 = conv1_k(c.n_mels);      // 80 bins: K = 3*96 = 288 padded to 320 = 5 x 64; 128: 384
-      if ((rc = dalloc(m, &m->w_conv1, (size_t)d * k1))) break;
-      hipLaunchKernelGGL(conv_pack_kernel, dim3(blocks_for((int64_t)d * k1)), dim3(256), 0, m->st, s.p, s.f16, m->w_conv1, d, c.n_mels, cc, k1);
+      if ((rc = dalloc(m, &m->w_conv1, (size_t)d * conv1_k(c.n_mels)))) break;
+      pack_conv1_w(m->st, s.p, s.f16, m->w_conv1, d, c.n_mels);
       if ((rc = L.get("encoder/conv2/weight", d, (int64_t)d * 3, &s))) break;
       if ((rc = dalloc(m, &m->w_conv2, (size_t)d * 3 * d))) break;
-      hipLaunchKernelGGL(conv_pack_kernel, dim3(blocks_for((int64_t)d * 3 * d)), dim3(256), 0, m->st, s.p, s.f16, m->w_conv2, d, d, d, 3 * d);
+      pack_conv2_w(m->st, s.p, s.f16, m->w_conv2, d, d);
     }
     if ((rc = to_f32(m, L, "encoder/conv1/bias", d, &m->b_conv1))) break;
     if ((rc = to_f32(m, L, "encoder/conv2/bias", d, &m->b_conv2))) break;
@@ -647,8 +671,7 @@ int stage_input(wis_model* m, const float* input, int kind, int B, hipStream_t o
       WIS_HIP_CHECK(hipMemcpyAsync(m->d_in, input, (size_t)B * m->cfg.n_mels * 3000 * 4, hipMemcpyHostToDevice, st));      // d_in: B x 480000 floats
       dm = m->d_in;
     }
-    if (m->cfg.n_mels == 128) hipLaunchKernelGGL((mel_to_image_kernel<128, 128>), dim3(cdiv(3000, 64), B), dim3(256), 0, st, dm, m->img);
-    else hipLaunchKernelGGL((mel_to_image_kernel<80, 96>), dim3(cdiv(3000, 64), B), dim3(256), 0, st, dm, m->img);
+    WIS_RET(launch_mel_to_image(st, dm, m->img, B, m->cfg.n_mels));
   } else { set_error("bad input_kind %d", kind); return WIS_E_ARG; }
   return WIS_OK;
 }
@@ -659,14 +682,10 @@ int run_encoder(wis_model* m, int B, hipStream_t on = nullptr) {
   const int d = c.d_model, H = c.n_heads, T = c.n_audio_ctx, M = B * T;
   {  // conv1: implicit im2col over the [3002][C] image; 80 bins: C = 96, K = 288 (+32 zero-weighted columns that read into the next
      // row); 128 bins: C = 128, K = 384
-    const int cc = conv1_channels(c.n_mels);
-    GemmP p; p.klen = 0; p.A = m->img; p.a_bs = (int64_t)3002 * cc; p.a_rs = cc; p.a_rpb = 3000; p.W = m->w_conv1; p.M = B * 3000; p.N = d; p.K = conv1_k(c.n_mels);
-    WIS_RET(launch_gemm_conv1(st, p, m->b_conv1, m->c1, 3000));
+    WIS_RET(launch_gemm_conv1(st, conv1_gemm(m->img, m->w_conv1, B, 3000, c.n_mels, d), m->b_conv1, m->c1, 3000));
   }
-  {  // conv2 (stride 2) + GELU + positions -> fp32 residual stream
-    GemmP p; p.klen = 0; p.A = m->c1; p.a_bs = (int64_t)3002 * d; p.a_rs = 2 * d; p.a_rpb = T; p.W = m->w_conv2; p.M = M; p.N = d; p.K = 3 * d;
-    WIS_RET(launch_gemm_conv2(st, p, m->b_conv2, m->enc_pos, m->x, T));
-  }
+  // conv2 (stride 2) + GELU + positions -> fp32 residual stream
+  WIS_RET(launch_gemm_conv2(st, conv2_gemm(m->c1, m->w_conv2, B, T, d, d), m->b_conv2, m->enc_pos, m->x, T));
   // Few row tiles (one utterance of the larger models): FFN2 (N = d, K = 4d) has too few 128x128 tiles for 256 CUs, so K is split
   // over workgroups (240-480 of them) and the reduction launch carries the LayerNorm of whatever consumes the rows next - the next
   // layer's ln1, or ln_post after the last layer.  Measured for large-v2 at M = 1500 with the weights streamed from HBM

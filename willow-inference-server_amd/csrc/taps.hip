@@ -581,4 +581,83 @@ int wis_op_gemv_out_cq(int device, const void* a, const float* x0, const void* W
   return WIS_OK;
 }
 
+// ---- taps of what run_encoder / run_cross_kv launch (tests/test_gpu_enc_ops.py): the product's launch_* functions on the product's GemmP helpers
+// (conv1_gemm, conv2_gemm, gemm_plain) and weight packers, with free B and T; the tile and kernel form are gemm_pick_tile's / launch_gemm_t's choice
+static int tap_finish(hipStream_t st, int rc, const char* who) {      // synchronise before the scratch goes, whatever the launch answered
+  const hipError_t e0 = hipGetLastError(), e = hipStreamSynchronize(st);
+  if (rc) return rc;
+  if (e0 != hipSuccess || e != hipSuccess) { set_error("%s: %s", who, hipGetErrorString(e0 != hipSuccess ? e0 : e)); return WIS_E_HIP; }
+  return WIS_OK;
+}
+int wis_op_mel_to_image(int device, const float* mel, void* img_f16, int B, int n_mels) {
+  DeviceCtx* c; WIS_RET(get_ctx(device, &c));
+  std::lock_guard<std::mutex> op_lock(ctx_op_mutex(c));
+  if (!mel || !img_f16 || B < 1) { set_error("wis_op_mel_to_image: bad argument"); return WIS_E_ARG; }
+  hipStream_t st = ctx_stream(c);
+  return tap_finish(st, launch_mel_to_image(st, mel, reinterpret_cast<f16*>(img_f16), B, n_mels), "wis_op_mel_to_image");
+}
+int wis_op_enc_conv(int device, int which, const void* img_f16, const void* W, int w_is_f16, const float* bias, const float* pos, void* out,
+                    int B, int T, int Cin, int N) {
+  DeviceCtx* c; WIS_RET(get_ctx(device, &c));
+  std::lock_guard<std::mutex> op_lock(ctx_op_mutex(c));
+  if (!img_f16 || !W || !bias || !out || B < 1 || T < 1 || N < 128 || (which != 1 && which != 2) || (which == 2 && !pos) || (int64_t)B * (2 * (int64_t)T + 2) > 0x7fffffff) {
+    set_error("wis_op_enc_conv: bad argument"); return WIS_E_ARG; }
+  if (which == 1 ? !mel_bins_supported(Cin) : (Cin < 64 || Cin % 64)) { set_error("wis_op_enc_conv: conv%d with %d input channels", which, Cin); return WIS_E_UNSUPPORTED; }
+  hipStream_t st = ctx_stream(c);
+  TapScratch ts;
+  f16* wp = nullptr;
+  if (!ts.get(&wp, (size_t)N * (which == 1 ? conv1_k(Cin) : 3 * Cin))) { set_error("wis_op_enc_conv: out of device memory"); return WIS_E_NOMEM; }
+  int rc;
+  if (which == 1) {
+    pack_conv1_w(st, W, w_is_f16, wp, N, Cin);
+    rc = launch_gemm_conv1(st, conv1_gemm(reinterpret_cast<const f16*>(img_f16), wp, B, T, Cin, N), bias, reinterpret_cast<f16*>(out), T);
+  } else {
+    pack_conv2_w(st, W, w_is_f16, wp, N, Cin);
+    rc = launch_gemm_conv2(st, conv2_gemm(reinterpret_cast<const f16*>(img_f16), wp, B, T, Cin, N), bias, pos, reinterpret_cast<float*>(out), T);
+  }
+  return tap_finish(st, rc, "wis_op_enc_conv");
+}
+int wis_op_enc_qkv(int device, const void* xn_f16, const void* W_f16, const float* bias, void* qk_f16, void* vt_f16, int B, int T, int H) {
+  DeviceCtx* c; WIS_RET(get_ctx(device, &c));
+  std::lock_guard<std::mutex> op_lock(ctx_op_mutex(c));
+  if (!xn_f16 || !W_f16 || !bias || !qk_f16 || !vt_f16 || B < 1 || T < 1 || H < 1 || (int64_t)B * T > 0x7fffffff / (3 * 64 * (int64_t)H)) { set_error("wis_op_enc_qkv: bad argument"); return WIS_E_ARG; }
+  if (T % 4) { set_error("wis_op_enc_qkv: T = %d (the transposed V tiles store 4 consecutive keys of one utterance: T %% 4 == 0)", T); return WIS_E_ARG; }
+  hipStream_t st = ctx_stream(c);
+  const int d = 64 * H;
+  const int rc = launch_gemm_qkv(st, gemm_plain(reinterpret_cast<const f16*>(xn_f16), d, reinterpret_cast<const f16*>(W_f16), B * T, 3 * d, d), bias,
+                                 reinterpret_cast<f16*>(qk_f16), reinterpret_cast<f16*>(vt_f16), d, T, cdiv(T, 64) * 64, H);
+  return tap_finish(st, rc, "wis_op_enc_qkv");
+}
+int wis_op_enc_crosskv(int device, const void* mem_f16, const void* W_f16, const float* bias, void* kx_f16, void* vt_f16, int B, int T, int H, int L,
+                       int64_t kx_lstride, int64_t vt_lstride) {
+  DeviceCtx* c; WIS_RET(get_ctx(device, &c));
+  std::lock_guard<std::mutex> op_lock(ctx_op_mutex(c));
+  if (!mem_f16 || !W_f16 || !bias || !kx_f16 || !vt_f16 || B < 1 || T < 1 || H < 1 || L < 1 || (int64_t)L * 2 * 64 * H > 0x7fffffff || (int64_t)B * T > 0x7fffffff / (64 * (int64_t)H)) {
+    set_error("wis_op_enc_crosskv: bad argument"); return WIS_E_ARG; }
+  if (T % 4) { set_error("wis_op_enc_crosskv: T = %d (the transposed V tiles store 4 consecutive keys of one utterance: T %% 4 == 0)", T); return WIS_E_ARG; }
+  const int d = 64 * H, Tpad = cdiv(T, 64) * 64;
+  if (kx_lstride < (int64_t)B * T * d || vt_lstride < (int64_t)B * d * Tpad || kx_lstride % 8 || vt_lstride % 8) {      // (16-byte stores into every layer's image)
+    set_error("wis_op_enc_crosskv: layer strides must be multiples of 8 elements and at least the layer's image"); return WIS_E_ARG; }
+  hipStream_t st = ctx_stream(c);
+  const int rc = launch_gemm_crosskv(st, gemm_plain(reinterpret_cast<const f16*>(mem_f16), d, reinterpret_cast<const f16*>(W_f16), B * T, L * 2 * d, d), bias,
+                                     reinterpret_cast<f16*>(kx_f16), reinterpret_cast<f16*>(vt_f16), d, T, Tpad, H, kx_lstride, vt_lstride);
+  return tap_finish(st, rc, "wis_op_enc_crosskv");
+}
+int wis_op_gemm_splitk_ln(int device, const void* A_f16, const void* W_f16, const float* bias, float* X, const float* gamma, const float* beta, void* Y_f16,
+                          int M, int N, int K, int splits) {
+  DeviceCtx* c; WIS_RET(get_ctx(device, &c));
+  std::lock_guard<std::mutex> op_lock(ctx_op_mutex(c));
+  if (!A_f16 || !W_f16 || !bias || !X || !gamma || !beta || !Y_f16 || M < 1 || N < 128 || K < 64 || splits < 0 || splits > 16 || (int64_t)M * N > 0x7fffffff) {
+    set_error("wis_op_gemm_splitk_ln: bad argument"); return WIS_E_ARG; }
+  if (!splits) splits = enc_splitk(N, M);      // run_encoder's choice for FFN2 at these rows
+  if (!splits) { set_error("wis_op_gemm_splitk_ln: the encoder does not split K at M = %d, N = %d", M, N); return WIS_E_UNSUPPORTED; }
+  hipStream_t st = ctx_stream(c);
+  TapScratch ts;
+  float* scratch = nullptr;
+  if (!ts.get(&scratch, (size_t)splits * M * N)) { set_error("wis_op_gemm_splitk_ln: out of device memory"); return WIS_E_NOMEM; }
+  const int rc = launch_gemm_splitk_resid(st, gemm_plain(reinterpret_cast<const f16*>(A_f16), K, reinterpret_cast<const f16*>(W_f16), M, N, K), splits, scratch, bias, X, X,
+                                          gamma, beta, reinterpret_cast<f16*>(Y_f16));
+  return tap_finish(st, rc, "wis_op_gemm_splitk_ln");
+}
+
 }  // extern "C"

@@ -127,6 +127,11 @@ SYMBOLS = [
     ("wis_op_dec_self_attn_ex", _i, [_i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _i, _i, _vp]),
     ("wis_op_gemv_qkv", _i, [_i] + [_vp] * 10 + [_i] * 3),
     ("wis_op_gemv_out_cq", _i, [_i] + [_vp] * 14 + [_i] * 3),
+    ("wis_op_mel_to_image", _i, [_i, _vp, _vp, _i, _i]),
+    ("wis_op_enc_conv", _i, [_i, _i, _vp, _vp, _i, _vp, _vp, _vp, _i, _i, _i, _i]),
+    ("wis_op_enc_qkv", _i, [_i] + [_vp] * 5 + [_i] * 3),
+    ("wis_op_enc_crosskv", _i, [_i] + [_vp] * 5 + [_i] * 4 + [_i64] * 2),
+    ("wis_op_gemm_splitk_ln", _i, [_i] + [_vp] * 7 + [_i] * 4),
     ("wis_sv_create", _i, [C.POINTER(SvConfig), _vp, _sz, _i, C.POINTER(Tensor), _i, _i, C.POINTER(_vp)]),
     ("wis_sv_destroy", None, [_vp]),
     ("wis_sv_device_bytes", _sz, [_vp]),
