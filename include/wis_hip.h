@@ -338,6 +338,11 @@ int wis_op_enc_attention(int device, const void* qk_f16, const void* vt_f16, voi
  * (x is f32 [M][K], gamma/beta given); without 8, x is f16 [M][K]; 32 = quantise W to per-row int8 first (int8_float16). */
 int wis_op_gemv(int device, const void* x, const float* gamma, const float* beta,
                 const void* W_f16, const float* bias, void* y, int M, int N, int K, int flags);
+/* the one-utterance FFN2 / cross-attention out-projection form of that GEMM (x f16 [M][K], K = 1280 or 5120, M x K / 8 <= 3328, M <= 16) on
+ * sixteen-column (cols = 16) or eight-column (cols = 8) workgroup tiles of the same W; N a multiple of cols.  flags: 1, 2, 4 as above;
+ * y16: optional f16 copy of the rows under flag 2, else null. */
+int wis_op_gemv_cols(int device, const void* x_f16, const void* W_f16, const float* bias, void* y, void* y16,
+                     int M, int N, int K, int flags, int cols);
 
 /* decoder self-attention of ONE new token per row over its cached history (the kernel inside every decode step):
  * q f32 [M][d] (pre-scaled by 1/sqrt(64)), kc / vc f16 [slots][ctx][d] (row m reads positions 0..pos[m] of logical slot

@@ -21,10 +21,10 @@ D = 1280
 # (round 6, round-5 review item 7: the one-utterance kernels are matched by the LEADING template arguments - MB, MODE, SC = k-steps per wave - and the grid,
 # so that a template parameter added behind them does not drop a kernel from the table: round 5's names carried six arguments, the keys four, and
 # `roofline.traffic` came from gemv_dual_kernel alone)
-ALG_B1 = {r"gemv_kernel<1, 2, 40, .* 20480": 8 * D * D,            # FFN2: all 40 fragments of a wave up front
+ALG_B1 = {r"gemv_kernel<1, 2, 40, .* (20480|40960)": 8 * D * D,    # FFN2: every request of a wave up front (160 eight-column workgroups; 80 tiles before)
           r"gemv_kernel<1, 1, 20, .* 40960": 8 * D * D,            # FFN1 on two-tile workgroups
           r"gemv_kernel<1, 1, 10, .* 61440": 6 * D * D,            # QKV
-          r"gemv_kernel<1, 2, 10, .* 20480": 2 * D * D,            # cross-attention output projection
+          r"gemv_kernel<1, 2, 10, .* (20480|40960)": 2 * D * D,    # cross-attention output projection (160 eight-column workgroups; 80 tiles before)
           r"gemv_dual_kernel<10, 20> 40960": 6 * D * D,            # out-projection + the folded cross-Q
           r"gemv_kernel<1, 1, 20, .* 414976": 2 * 51872 * D,       # vocabulary projection (two-tile workgroups)
           r"dec_cross_attn_kernel 30720": 2 * 2 * 1500 * D,
@@ -40,7 +40,7 @@ TEMPLATE_NOTE = ("Template arguments: `gemv_kernel<MB, MODE, SC, RM, W8>` (MODE 
                  "generic ring: FFN2), `gemv_dual_kernel<SCA, SCB>` (out-projection + folded cross-Q in one launch), `gemv_frag_kernel<MB, PF, W8>` (batched rows on fragment images: MB 16-row blocks, "
                  "PF k-steps in flight), `gemv_frag_ms_kernel<MB, PF, W8>` (round 6: the same split by row blocks over workgroups - grid (n-tiles, 1, row-block groups): the d x d projection and FFN2), `dec_cross_attn_kernel<TPW, CM, FOLD, SPIN>` (SPIN = granule hand-off of the chunk partials), `dec_cross_attn_rs_kernel<SPIN, NT, NKW>` (round 6: K waves / V waves; the decode steps' cross-attention), `gemm_8p_kernel<Epi, TR>` (8-phase 256 x 256 LDS-DMA GEMM, "
                  "persistent over tiles; TR = swapped operands for the V images; EpiResid = bias + fp32 residual), `gemm_8pn_kernel<Epi>` (the same on a 128 x 256 tile: FFN1 of one utterance), `gemm_f16_kernel<Epi, BM, BN, WM, WN>` / `gemm_pp_kernel<Epi>` (register-staged tiles / ping-pong 256 x 128), `enc_attn_lazy_kernel<SPLIT>` (r4: lazy softmax reference; `enc_attn_kernel<SPLIT>` is the A/B form behind WIS_ENC_ATTN_LAZY=0), "
-                 "`splitk_reduce_ln_kernel<SPLITS>`, `layernorm_kernel<AFFINE>`.  By-grid table: 20480 threads = 80 tiles (d x d; FFN2 at one utterance), 40960 = FFN2 of the batched path (two K slices), 61440 = QKV, 81920 = FFN1, 829952 = vocabulary projection.")
+                 "`splitk_reduce_ln_kernel<SPLITS>`, `layernorm_kernel<AFFINE>`.  By-grid table: 20480 threads = 80 tiles (the d x d problems of batched rows), 40960 = 160 workgroups (one utterance: FFN2 and the cross-attention out-projection on eight-column tiles, two-tile FFN1, the fused out-projection + cross-Q) or FFN2 of the batched path (two K slices), 61440 = QKV, 81920 = FFN1, 829952 = vocabulary projection.")
 
 
 def read(path):

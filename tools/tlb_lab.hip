@@ -8,9 +8,14 @@
 //   SPAN = 2 / 8 / 24 GB data cold, 1 000 - 12 000 two-MB pages
 // and the same with a RIDER: one wave of every launch also touches one cache line in each 2 MB page of the NEXT launch's region (translations warmed one launch ahead,
 // 5 loads).  Output: us per launch.
+//   tools/bin/tlb_lab ffn2 [launches]
+// The one-utterance FFN2's bytes (13.1 MB per launch, cold: regions rotate through 2 GB) as 80 workgroups x 160 one-KiB wave requests (40 per wave: today's sixteen-column
+// tiles) and as 160 workgroups x 80 (20 per wave: eight-column tiles), every request issued up front, alternating in one process; also the cross-attention out-projection's
+// 3.3 MB as 80 x 40 and 160 x 20.  Output: us per launch of each form, pair by pair.
 #include <hip/hip_runtime.h>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <vector>
 #define CK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { fprintf(stderr, "%s: %s\n", #x, hipGetErrorString(e_)); exit(1); } } while (0)
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
@@ -31,7 +36,46 @@ __global__ __launch_bounds__(256) void stream_read(const u32x4* __restrict__ bas
   if (tid == 0 && blockIdx.x == 0) out[0] = 1;
 }
 
+// `R` one-KiB requests per wave, all up front; the grid decides how many workgroups share the region's bytes
+template <int R>
+__global__ __launch_bounds__(256) void stream_read_r(const u32x4* __restrict__ base, unsigned* out) {
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  const u32x4* p = base + ((size_t)(blockIdx.x * 4 + wave) * R) * 64 + lane;
+  u32x4 v[R];
+#pragma unroll
+  for (int u = 0; u < R; ++u) v[u] = __builtin_nontemporal_load(p + (size_t)u * 64);
+  unsigned s = 0;
+#pragma unroll
+  for (int u = 0; u < R; ++u) s += v[u][0] ^ v[u][1] ^ v[u][2] ^ v[u][3];
+  if (s == 0x12345678u) out[blockIdx.x] = s;
+  if (tid == 0 && blockIdx.x == 0) out[0] = 1;
+}
+template <int R>
+static float chain_r(hipStream_t st, hipEvent_t e0, hipEvent_t e1, const char* buf, size_t stride, size_t nreg, int wgs, int n, unsigned* out) {
+  CK(hipEventRecord(e0, st));
+  for (int i = 0; i < n; ++i) hipLaunchKernelGGL(stream_read_r<R>, dim3(wgs), dim3(256), 0, st, reinterpret_cast<const u32x4*>(buf + (size_t)(i % nreg) * stride), out);
+  CK(hipEventRecord(e1, st)); CK(hipEventSynchronize(e1));
+  float ms; CK(hipEventElapsedTime(&ms, e0, e1));
+  return 1e3f * ms / n;
+}
+static int ffn2_mode(int n) {
+  const size_t STRIDE = 14ull << 20, SPAN = 2ull << 30, nreg = SPAN / STRIDE;      // 13.1 MB regions, 2 MB aligned; 80 x 4 x 40 KiB = 160 x 4 x 20 KiB fit
+  char* buf; CK(hipMalloc(&buf, SPAN)); CK(hipMemset(buf, 0, SPAN));
+  unsigned* out; CK(hipMalloc(&out, 4096));
+  hipStream_t st; CK(hipStreamCreate(&st));
+  hipEvent_t e0, e1; CK(hipEventCreate(&e0)); CK(hipEventCreate(&e1));
+  printf("chains of %d dependent launches over 2 GB of cold regions, every request up front, non-temporal; us per launch\n", n);
+  printf("pair   FFN2 13.1 MB: 80 wg x 4 x 40   160 wg x 4 x 20   |   cross-out 3.3 MB: 80 wg x 4 x 10   160 wg x 4 x 5\n");
+  for (int pair = -1; pair < 8; ++pair) {      // (pair -1 warms the code objects and clocks; not printed)
+    const float a = chain_r<40>(st, e0, e1, buf, STRIDE, nreg, 80, n, out), b = chain_r<20>(st, e0, e1, buf, STRIDE, nreg, 160, n, out);
+    const float c = chain_r<10>(st, e0, e1, buf, STRIDE, nreg, 80, n, out), d = chain_r<5>(st, e0, e1, buf, STRIDE, nreg, 160, n, out);
+    if (pair >= 0) printf("%4d   %30.3f   %15.3f   |   %33.3f   %14.3f\n", pair, a, b, c, d);
+  }
+  return 0;
+}
+
 int main(int argc, char** argv) {
+  if (argc > 1 && !strcmp(argv[1], "ffn2")) return ffn2_mode(argc > 2 ? atoi(argv[2]) : 3000);
   const int n = argc > 1 ? atoi(argv[1]) : 3000;
   size_t freeb = 0, total = 0; CK(hipMemGetInfo(&freeb, &total));
   const size_t cap = 26ull << 30;

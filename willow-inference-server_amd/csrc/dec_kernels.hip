@@ -179,6 +179,36 @@ int launch_pack_gemv(hipStream_t st, const f16* W, f16* Wp, int N, int Npad, int
   return WIS_OK;
 }
 
+// The eight-column image (gemv_body NC = 8): [Npad/8][K/64][64 lanes][8 f16].  Lane l of a wave request carries column 8 nt + (l & 7), k-step
+// 2 kp + ((l >> 3) & 1) of the pair, k-quarter l >> 4 - i.e. A-fragment rows 0-7 hold the even k-step, rows 8-15 the odd one.  Same bytes as the sixteen-column image.
+__global__ void pack_gemv_nc8_kernel(const f16* __restrict__ W, f16* __restrict__ Wp, int N, int Npad, int K) {
+  const int kpairs = K / 64;
+  const size_t total = (size_t)(Npad / 8) * kpairs * 64;
+  for (size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (size_t)gridDim.x * blockDim.x) {
+    const int l = (int)(idx & 63);
+    const size_t t = idx >> 6;
+    const int kp = (int)(t % kpairs), nt = (int)(t / kpairs);
+    const int n = 8 * nt + (l & 7), k = 64 * kp + 32 * ((l >> 3) & 1) + 8 * (l >> 4);
+    f16x8 v;
+    if (n < N) v = *reinterpret_cast<const f16x8*>(W + (size_t)n * K + k);
+    else {
+#pragma unroll
+      for (int j = 0; j < 8; ++j) v[j] = (f16)0.f;
+    }
+    *reinterpret_cast<f16x8*>(Wp + idx * 8) = v;
+  }
+}
+int launch_pack_gemv_nc8(hipStream_t st, const f16* W, f16* Wp, int N, int Npad, int K) {
+  if (K % 64 || Npad % 8 || Npad < N) { set_error("pack_gemv_nc8: bad shape N=%d Npad=%d K=%d", N, Npad, K); return WIS_E_ARG; }
+  const size_t total = (size_t)(Npad / 8) * (K / 64) * 64;
+  int blocks = (int)((total + 255) / 256); if (blocks > 4096) blocks = 4096;
+  hipLaunchKernelGGL(pack_gemv_nc8_kernel, dim3(blocks), dim3(256), 0, st, W, Wp, N, Npad, K);
+  return WIS_OK;
+}
+// the shapes launch_gemv runs on eight-column tiles (GemvP::rows = 8, Wp that image): the single-chunk f16-activation form at
+// K = 1280 and 5120 (SC 10 and 40), as many rows as its register staging holds
+bool gemv_nc8_shape(int M, int N, int K) { return (K == 1280 || K == 5120) && N % 8 == 0 && M >= 1 && M <= 16 && M * (K / 8) <= 13 * 256; }
+
 // 8-byte {tag, value} granules: one relaxed agent-scope (write-through) store each, "the data is the flag" (guide G16 form R2) - the hand-off of the
 // decoder cross-attention's chunk partials (dec_cross_attn_kernel SPIN).  Lesson of the three in-launch hand-offs that were tried for the step's other
 // stages and lost (retired experiments): an in-launch hand-off is two fabric round trips (granule store -> L2 -> poll), like a kernel boundary.
@@ -210,15 +240,24 @@ constexpr unsigned CA_SPIN_LIMIT = 1u << 17;      // sweeps before the combiner 
 // NT (r5; MB = 1, single chunk, compile-time SC only): n-tiles per workgroup.  2: waves 0-1 own tile 2 nt, waves 2-3 tile 2 nt + 1, half of
 // K each (SC = K / 64 fragments per wave, all requested up front) - half as many workgroups stage the activation rows, each with twice
 // the weight bytes in flight: N = 4d of the one-utterance step is 160 workgroups (one per CU) instead of 320 on 256 CUs.
-template <int MB, int MODE, int SC, int RM, bool W8, int NT = 1>
+// NC (MODE 2, MB = 1, NT = 1, even compile-time SC, f16 weights): output columns per workgroup.  8: the eight-column image (pack_gemv_nc8_kernel) - a wave
+// request is still one full KiB, eight columns x TWO k-steps (lanes with bit 3 clear carry the even k-step of the pair in A-fragment rows 0-7, lanes with
+// bit 3 set the odd one in rows 8-15), so a workgroup issues HALF the requests of a sixteen-column tile and N / 8 workgroups share the matrix: the
+// one-utterance FFN2 and cross-attention out-projection run on 160 workgroups instead of 80.  Per request two MFMAs: the registers as they landed against
+// the even k-step's activations, then the same registers rotated by eight lanes within each row of 16 (DPP row_ror:8: the odd k-step's weights arrive in
+// rows 0-7) against the odd k-step's.  Rows 0-7 of the accumulator thus see the wave's k-steps in today's order, each through the same MFMA, and the
+// cross-wave reduction is unchanged: bit-identical outputs.  Rows 8-15 of the accumulator are by-products nobody reads.
+template <int MB, int MODE, int SC, int RM, bool W8, int NT = 1, int NC = 16>
 __device__ __forceinline__ void gemv_body(const GemvP& p, const int KC, const int nt, char* smem) {
   static_assert(NT == 1 || (NT == 2 && MB == 1 && SC > 0), "two-tile workgroups: <= 16 rows, every fragment prefetched");
+  static_assert(NC == 16 || (NC == 8 && MB == 1 && NT == 1 && MODE == 2 && SC > 0 && SC % 2 == 0 && !W8), "eight-column tiles: f16 activations and weights, k-steps in pairs, all prefetched");
   typedef typename WFrag<W8>::T WT;
-  constexpr int GV_PF = SC > 0 ? SC : 16;
+  constexpr int GV_PF = SC > 0 ? (NC == 8 ? SC / 2 : SC) : 16;
   // full MFMA A fragments.  4- / 8-row tiles were measured twice: packed that way (round 1) and as HALF tiles of the ordinary image (round 6: 160 workgroups
   // addressing rows 8 h .. 8 h + 7 of every fragment for the one-utterance FFN2, 1.2152 / 1.2137 vs 1.2152 / 1.2159 ms per step, session r6L) - no gain: a
   // wave's request costs the CU's address path the same ~50 cycles whether 64 or 32 of its lanes are active, and the stream is those requests
-  constexpr int rows = 16;
+  // (NC = 8 is not that form: its requests stay FULL - eight columns x two k-steps -, so a workgroup issues half as many)
+  constexpr int rows = NC;
   const int M = p.M, K = p.K;
   const int xstr = KC + 8;
   f16* xs = reinterpret_cast<f16*>(smem);
@@ -233,7 +272,9 @@ __device__ __forceinline__ void gemv_body(const GemvP& p, const int KC, const in
   // fragment (tile, k-step) = 4*rows 16-byte pieces: piece (kq, row) at kq*rows + row; lanes with row >= rows stay zero
   const bool wact = (lane & 15) < rows;
   const int wstep = 4 * rows;                     // pieces per k-step
-  const WT* wp4 = reinterpret_cast<const WT*>(p.Wp) + (size_t)(nt * NT + wt) * ksteps * wstep + (lane >> 4) * rows + (lane & 15);
+  // (NC == 8: request `u` of the wave = k-steps ksl0 + 2u, + 1 of tile nt, 64 pieces)
+  const WT* wp4 = NC == 8 ? reinterpret_cast<const WT*>(p.Wp) + ((size_t)nt * (ksteps >> 1) + (ksl0 >> 1)) * 64 + lane
+                          : reinterpret_cast<const WT*>(p.Wp) + (size_t)(nt * NT + wt) * ksteps * wstep + (lane >> 4) * rows + (lane & 15);
   const WT wzero = WFrag<W8>::zero();
   const int k4n = K >> 2;                        // float4 per row
   // LayerNorm-folded path (MODE 1; host-selected, M <= 8, K <= 2048): the raw fp32 rows live in registers, thread owns float4
@@ -305,7 +346,10 @@ __device__ __forceinline__ void gemv_body(const GemvP& p, const int KC, const in
   }
   // weight prefetch for chunk 0 (independent of x)
   WT wf[GV_PF];
-  {
+  if constexpr (NC == 8) {
+#pragma unroll
+    for (int u = 0; u < GV_PF; ++u) wf[u] = __builtin_nontemporal_load(wp4 + (size_t)u * 64);
+  } else {
     const WT* wq = wp4 + (size_t)ksl0 * wstep;
 #pragma unroll
     for (int u = 0; u < GV_PF; ++u) { wf[u] = wzero; if ((SC > 0 || u < S) && wact) wf[u] = __builtin_nontemporal_load(wq + (size_t)u * wstep); }
@@ -405,7 +449,20 @@ __device__ __forceinline__ void gemv_body(const GemvP& p, const int KC, const in
     }
     __syncthreads();
     stamp(pf, 3);
-    if (SC > 0) {
+    if constexpr (NC == 8) {
+#pragma unroll
+      for (int u = 0; u < GV_PF; ++u) {
+        const f16x8 a0 = WFrag<W8>::cvt(wf[u]);
+        const f16x8 x0 = *reinterpret_cast<const f16x8*>(xs + xrow[0] + (ksl0 + 2 * u) * 32);
+        acc[0] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a0, x0, acc[0], 0, 0, 0);
+        u32x4 wr;      // row_ror:8 - lane l takes lane l ^ 8's registers
+#pragma unroll
+        for (int e = 0; e < 4; ++e) wr[e] = (unsigned)__builtin_amdgcn_update_dpp(0, (int)wf[u][e], 0x128, 0xf, 0xf, false);
+        const f16x8 a1 = *reinterpret_cast<const f16x8*>(&wr);
+        const f16x8 x1 = *reinterpret_cast<const f16x8*>(xs + xrow[0] + (ksl0 + 2 * u + 1) * 32);
+        acc[0] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a1, x1, acc[0], 0, 0, 0);
+      }
+    } else if (SC > 0) {
 #pragma unroll
       for (int u = 0; u < GV_PF; ++u) {
         const f16x8 a = WFrag<W8>::cvt(wf[u]);
@@ -542,11 +599,11 @@ __device__ __forceinline__ void gemv_body(const GemvP& p, const int KC, const in
 #define WIS_GV_LEAD(q) (q).x, (q).x2, (q).Wp, (q).M, (q).N, (q).K, (q).xsplit
 #define WIS_GV_LEAD_DECL(s) const void* s##x, const void* s##x2, const f16* s##Wp, int s##M, int s##N, int s##K, int s##xsplit
 #define WIS_GV_LEAD_APPLY(q, s) (q).x = s##x; (q).x2 = s##x2; (q).Wp = s##Wp; (q).M = s##M; (q).N = s##N; (q).K = s##K; (q).xsplit = s##xsplit
-template <int MB, int MODE, int SC, int RM, bool W8, int NT = 1>
+template <int MB, int MODE, int SC, int RM, bool W8, int NT = 1, int NC = 16>
 __global__ __launch_bounds__(256) void gemv_kernel(WIS_GV_LEAD_DECL(l_), int KC, GemvP p) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   WIS_GV_LEAD_APPLY(p, l_);
-  gemv_body<MB, MODE, SC, RM, W8, NT>(p, KC, blockIdx.x, smem);
+  gemv_body<MB, MODE, SC, RM, W8, NT, NC>(p, KC, blockIdx.x, smem);
 }
 // Two skinny GEMMs in ONE launch (workgroups [0, nA) run problem A, the rest problem B; both f16-activation, single-chunk,
 // <= 16 rows): the decoder's attention output projection together with the cross-attention query projection folded THROUGH it
@@ -620,6 +677,16 @@ int launch_gemv(hipStream_t st, const GemvP& p) {
   // already, and 120 fat workgroups measured SLOWER (1.292 ms) - fatter workgroups pay only where they remove a second round.
   if (mode == 1 && sc == 10 && p.M > 3 && p.M <= 5 && !p.wscale && rows == 16 && p.N % 32 == 0 && !(p.flags & (GV_RESID | GV_QKV)) && p.N >= 4096) {
     hipLaunchKernelGGL((gemv_kernel<1, 1, 20, 5, false, 2>), dim3(p.N / 32), block, lds, st, WIS_GV_LEAD(pp), KC, pp);
+    return WIS_OK;
+  }
+  // rows = 8: Wp is the eight-column image (gemv_body NC = 8) - twice the workgroups, half the weight requests each.  Plain and residual
+  // epilogues only: the LayerNorm partials of stat_out are per sixteen columns
+  if (rows != 16 && rows != 8) { set_error("gemv: %d-row weight tiles have no kernel", rows); return WIS_E_UNSUPPORTED; }
+  if (rows == 8) {
+    if (mode != 2 || p.wscale || p.stat_out || (p.flags & GV_QKV) || !gemv_nc8_shape(p.M, p.N, p.K)) {
+      set_error("gemv: the eight-column image serves f16 rows and weights at K = 1280 / 5120 without row partials (M=%d N=%d K=%d flags=%d)", p.M, p.N, p.K, p.flags); return WIS_E_UNSUPPORTED; }
+    if (sck == 40) hipLaunchKernelGGL((gemv_kernel<1, 2, 40, 1, false, 1, 8>), dim3(p.N / 8), block, lds, st, WIS_GV_LEAD(pp), KC, pp);
+    else hipLaunchKernelGGL((gemv_kernel<1, 2, 10, 1, false, 1, 8>), dim3(p.N / 8), block, lds, st, WIS_GV_LEAD(pp), KC, pp);
     return WIS_OK;
   }
   if (mode == 1) { if (p.M <= 3) WIS_GV_SC(1, 3); else if (p.M <= 5) WIS_GV_SC(1, 5); else WIS_GV_SC(1, 8); }

@@ -65,7 +65,7 @@ struct GemvP {
   // GV_QKV epilogue: n < d -> q (f32 [M][d]); d <= n < 2d -> K cache; n >= 2d -> V cache
   float* q; f16* kc; f16* vc; const int* slot; const int* pos; int d; int ctx;   // cache [slots][ctx][d]
   unsigned long long* prof;      // optional phase stamps (workgroup 0)
-  int rows;                      // weight rows per workgroup tile (16 / 8 / 4; 0 => 16): must match the packing
+  int rows;                      // output columns per workgroup (0 => 16): 16 = Wp in A-fragment order, 8 (launch_gemv, gemv_nc8_shape only) = Wp the eight-column image of launch_pack_gemv_nc8
   const void* x2; int xsplit;    // f16 activations only: columns >= xsplit are read from x2 (row-major [M][K - xsplit]); x then is [M][xsplit]
   f16* y16;                      // GV_RESID: optional f16 row-major copy of the produced rows
   // ---- batched rows (launch_gemv_frag, M > 8): activations live in HBM in MFMA B-fragment order ("xf", xf_index below)
@@ -108,6 +108,9 @@ int launch_pack_gemv8(hipStream_t st, const f16* W, unsigned char* Wp, float* sc
 // pack W [N][K] f16 row-major -> Wp [Npad/rows][K/32][4][rows][8]; matrix rows >= N are zero; scale matrix rows
 // [0, n_scale) by `scale` (folds the 1/sqrt(dh) query scaling into the projection)
 int launch_pack_gemv(hipStream_t st, const f16* W, f16* Wp, int N, int Npad, int K, int n_scale, float scale, int rows = 16);
+// pack W [N][K] f16 row-major -> the eight-column image [Npad/8][K/64][64][8] (dec_kernels.hip pack_gemv_nc8_kernel); Npad % 8 == 0, K % 64 == 0
+int launch_pack_gemv_nc8(hipStream_t st, const f16* W, f16* Wp, int N, int Npad, int K);
+bool gemv_nc8_shape(int M, int N, int K);      // launch_gemv serves GemvP::rows = 8 at these shapes
 int gemv_rows_for(int N, int K);     // tile height used for an [N][K] decoder matrix
 
 int launch_dec_embed(hipStream_t st, const f16* emb, const f16* pos_emb, const int* tok, const int* pos, float* x, int M, int d, f16* xh = nullptr);

@@ -126,6 +126,7 @@ struct DecProj {
   const float* csum;      // column sums of the LayerNorm-folded weights (dec_kernels.hip fold_ln_kernel): non-null exactly when the projection follows a LayerNorm
   int N, K;               // launch shape (the vocabulary projection: N = n_vocab_pad)
   int rows;               // weight rows per workgroup tile the matrix was packed for (gemv_rows_for)
+  const f16* Wp8 = nullptr;      // the same f16 matrix as an eight-column image (add_nc8_image), or null: the route of <= 8 rows streams this one where gemv_nc8_shape holds
 };
 struct DecLayerW {
   float *ln1_g, *ln1_b, *ln2_g, *ln2_b, *ln3_g, *ln3_b;
@@ -389,6 +390,18 @@ int load_proj(wis_model* m, const Loader& L, const std::string& name, int N, int
   return WIS_OK;
 }
 
+// A second, eight-column image of a projection whose f16 row-major matrix is still in `tmp` (right behind its load_proj): the step of <= 8 rows runs it on
+// N / 8 workgroups (dec_kernels.hip gemv_body NC = 8).  The batched route keeps reading the sixteen-column image, so both exist: N * K * 2 bytes more.
+// Nothing is added where the kernel form does not apply (8-bit weights, other widths than large's).
+static int add_nc8_image(wis_model* m, const f16* tmp, DecProj* p) {
+  if (m->w8 || !gemv_nc8_shape(1, p->N, p->K)) return WIS_OK;
+  f16* wp8 = nullptr;
+  WIS_RET(dalloc(m, &wp8, (size_t)p->N * p->K));
+  WIS_RET(launch_pack_gemv_nc8(m->st, tmp, wp8, p->N, p->N, p->K));
+  p->Wp8 = wp8;
+  return WIS_OK;
+}
+
 // The cross-Q fold's matrix and bias (load_weights below; the wis_op_gemv_out_cq tap builds its operands with the same code): wq_gamma = f16(Wq o gamma)
 // [d][d] as fold_ln_kernel left it, wo / bo = the self-attention output projection (f16 or f32 [d][d]; fp32 [d]) ->
 //   p_cqo = packed [W'q | W'q Wo] ([d][2d], W'q = wq_gamma * qs, the product rounded to f16 like every other stored weight),  b_cqo = W'q bo.
@@ -514,10 +527,12 @@ int load_weights(wis_model* m, const Loader& L) {
       if ((rc = to_f16_mat(m, L, p + "attention/linear_1/weight", 2 * d, d, &w.w_ckv))) break;
       if ((rc = to_f32(m, L, p + "attention/linear_1/bias", 2 * d, &w.b_ckv))) break;
       if ((rc = load_proj(m, L, p + "attention/linear_2", d, d, tmp, 0, 1.f, nullptr, nullptr, &w.cout))) break;
+      if ((rc = add_nc8_image(m, tmp, &w.cout))) break;
       if ((rc = to_f32(m, L, p + "ffn/layer_norm/gamma", d, &w.ln3_g))) break;
       if ((rc = to_f32(m, L, p + "ffn/layer_norm/beta", d, &w.ln3_b))) break;
       if ((rc = load_proj(m, L, p + "ffn/linear_0", 4 * d, d, tmp, 0, 1.f, w.ln3_g, w.ln3_b, &w.f1))) break;
       if ((rc = load_proj(m, L, p + "ffn/linear_1", d, 4 * d, tmp, 0, 1.f, nullptr, nullptr, &w.f2))) break;
+      if ((rc = add_nc8_image(m, tmp, &w.f2))) break;
     }
   } while (0);
   hipError_t e = hipStreamSynchronize(m->st);
@@ -809,6 +824,8 @@ int align_capture_q(wis_model* m, int l, int M);      // align.hip
 static GemvP gemv_small(const DecProj& p, const void* x, void* y, int M, int flags) {
   GemvP g; memset(&g, 0, sizeof(g));
   g.x = x; g.csum = p.csum; g.Wp = p.Wp; g.wscale = p.scale; g.bias = p.bias; g.y = y; g.M = M; g.N = p.N; g.K = p.K; g.flags = flags; g.rows = p.rows;
+  // eight-column tiles where the projection has that image (FFN2, cross-attention out-projection of large models): f16 rows, plain or residual epilogue
+  if (p.Wp8 && !(flags & ~(GV_RESID | GV_OUT_F32 | GV_GELU)) && gemv_nc8_shape(M, p.N, p.K)) { g.Wp = p.Wp8; g.rows = 8; }
   return g;
 }
 // launch_gemv_frag (batched rows) on the rows' fragment image; the caller adds the stage's own: output, statistics, QKV cache members, prof, FFN2's K split

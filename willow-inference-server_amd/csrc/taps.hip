@@ -397,6 +397,30 @@ int wis_op_gemv(int device, const void* x, const float* gamma, const float* beta
   return WIS_OK;
 }
 
+// The single-chunk f16-activation form of launch_gemv (the one-utterance FFN2 and cross-attention out-projection: K = 5120 / 1280) on sixteen-column
+// tiles (cols = 16: the fragment image) or eight-column tiles (cols = 8: launch_pack_gemv_nc8's image) of the same row-major W [N][K].  flags: GV_RESID
+// (y fp32 [M][N] in place, y16 an optional f16 copy), GV_OUT_F32, GV_GELU or none (y f16).  Nothing but the M x N outputs is written.
+int wis_op_gemv_cols(int device, const void* x, const void* W, const float* bias, void* y, void* y16, int M, int N, int K, int flags, int cols) {
+  DeviceCtx* c; WIS_RET(get_ctx(device, &c));
+  std::lock_guard<std::mutex> op_lock(ctx_op_mutex(c));
+  hipStream_t st = ctx_stream(c);
+  if (!x || !W || !y || (cols != 8 && cols != 16) || N < 1 || N % cols || (flags & ~(GV_RESID | GV_OUT_F32 | GV_GELU)) || (y16 && !(flags & GV_RESID))) { set_error("wis_op_gemv_cols: bad argument"); return WIS_E_ARG; }
+  if (!gemv_nc8_shape(M, N, K)) { set_error("wis_op_gemv_cols: M=%d N=%d K=%d is not a shape of the eight-column form", M, N, K); return WIS_E_UNSUPPORTED; }
+  f16* wp = nullptr;
+  if (hipMalloc(reinterpret_cast<void**>(&wp), (size_t)N * K * 2) != hipSuccess) { set_error("wis_op_gemv_cols: out of device memory"); return WIS_E_NOMEM; }
+  int rc = cols == 8 ? launch_pack_gemv_nc8(st, reinterpret_cast<const f16*>(W), wp, N, N, K) : launch_pack_gemv(st, reinterpret_cast<const f16*>(W), wp, N, N, K, 0, 1.f, 16);
+  if (!rc) {
+    GemvP g; memset(&g, 0, sizeof(g));
+    g.x = x; g.Wp = wp; g.bias = bias; g.y = y; g.y16 = reinterpret_cast<f16*>(y16); g.M = M; g.N = N; g.K = K; g.flags = flags; g.rows = cols;
+    rc = launch_gemv(st, g);
+  }
+  hipError_t e = hipStreamSynchronize(st);
+  hipFree(wp);
+  if (rc) return rc;
+  if (e != hipSuccess) { set_error("wis_op_gemv_cols: %s", hipGetErrorString(e)); return WIS_E_HIP; }
+  return WIS_OK;
+}
+
 int wis_op_dec_self_attn(int device, const float* q, const void* kc, const void* vc, const int32_t* pos, void* out,
                          int M, int H, int ctx, int rpu, int sstride, int rmul) {
   DeviceCtx* c; WIS_RET(get_ctx(device, &c));
