@@ -422,6 +422,28 @@ int wis_op_enc_crosskv(int device, const void* mem_f16, const void* W_f16, const
 int wis_op_gemm_splitk_ln(int device, const void* A_f16, const void* W_f16, const float* bias, float* X, const float* gamma, const float* beta,
                           void* Y_f16, int M, int N, int K, int splits);
 
+/* ---- taps of what runs behind the logits (tests/test_gpu_sample_ops.py): the product's launch functions on caller-supplied device memory. */
+/* the cache permutation after a beam step, in place: kc / vc f16, layer l at + l layer_stride_elems, [slots][ctx][d] each (d % 8 == 0); for every
+ * utterance b with done[b] == 0, slot b beam + j becomes a copy of slot parent[b beam + j] (a slot of the same utterance) at positions
+ * < P - 1 + step_u[b] (<= ctx: the caller's duty), all L layers, K and V; nothing else is written.  beam = 1: nothing runs. */
+int wis_op_kv_reorder(int device, void* kc_f16, void* vc_f16, int64_t layer_stride_elems, int L, const int32_t* parent, const int32_t* step_u,
+                      const int32_t* done, int B, int beam, int P, int ctx, int d);
+/* the cache gather after a verified draft window (one utterance), in place: vstate i32 [32 + 8 x 32]: [2] = window steps nwin (<= 32, w0 + nwin <= ctx:
+ * the caller's duty), [16 + j] = the slot that holds beam j's positions < w0, [32 + 32 j + u] = the slot that holds its position w0 + u; slot j (< beam)
+ * becomes that history.  done[0] == 1 or nwin <= 0: nothing is written (done[0] == 2, a parked search, still gathers). */
+int wis_op_kv_gather(int device, void* kc_f16, void* vc_f16, int64_t layer_stride_elems, int L, const int32_t* vstate, const int32_t* done,
+                     int beam, int w0, int ctx, int d);
+/* out[b] = softmax(logits row b rs + r0 over ids [0, V))[ns]; logits f32, row stride ld >= V.  ns outside [0, V): WIS_E_ARG. */
+int wis_op_no_speech(int device, const float* logits, int ld, int B, int rs, int r0, int V, int ns, float* out);
+/* probs f32 [B][n_lang] = softmax over the n_lang listed ids of logits row b (row stride ld) */
+int wis_op_lang_probs(int device, const float* logits, int ld, const int32_t* lang_ids, int n_lang, float* probs, int B);
+/* the teacher-forced greedy pick: logit statistics (suppress_blank on, no fixed length, n_cand = 2) of B x beam rows, then the k = 1 pick of each.
+ * Row (b, j) reads logits row b lr_b + (rowmap ? rowmap[j] : j) lr_j + lr_off (row stride n_vocab_pad) at step step_u[b]: bias_begin (f32 [n_vocab])
+ * is added at step 0 only, bias_all (f32 [n_vocab] or NULL) always.  tok_out i32 / lp_out f32 [B x beam]: token (lowest id among equal maxima) and
+ * its log-probability.  rowmap i32 [beam] or NULL.  Scratch is the tap's own. */
+int wis_op_greedy_rows(int device, const float* logits, int n_vocab, int n_vocab_pad, int eot, const float* bias_all, const float* bias_begin,
+                       const int32_t* step_u, int B, int beam, int lr_b, int lr_j, int lr_off, const int32_t* rowmap, int32_t* tok_out, float* lp_out);
+
 /* ---- speaker verification (replaces the reference's WavLMForXVector embedder, main.py:306-316 / do_sv 797-879): one handle = the
  * WavLM-base-plus-sv x-vector model on one GPU.  Input: mono 16 kHz f32 PCM in host memory, already through the reference's
  * preprocessing (sox gain + trim, the feature extractor's zero-mean / unit-variance normalisation: wis_hip/sv.py); output: the

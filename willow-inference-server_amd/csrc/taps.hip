@@ -684,4 +684,58 @@ int wis_op_gemm_splitk_ln(int device, const void* A_f16, const void* W_f16, cons
   return tap_finish(st, rc, "wis_op_gemm_splitk_ln");
 }
 
+// ---- taps of what runs behind the logits (tests/test_gpu_sample_ops.py): the cache movers of a beam step and of a verified draft window, and the three
+// softmax readers, through the product's launch_* functions on caller-supplied device memory
+int wis_op_kv_reorder(int device, void* kc_f16, void* vc_f16, int64_t layer_stride_elems, int L, const int32_t* parent, const int32_t* step_u, const int32_t* done,
+                      int B, int beam, int P, int ctx, int d) {
+  DeviceCtx* c; WIS_RET(get_ctx(device, &c));
+  std::lock_guard<std::mutex> op_lock(ctx_op_mutex(c));
+  if (!kc_f16 || !vc_f16 || !parent || !step_u || !done || L < 1 || B < 1 || beam < 1 || P < 1 || ctx < 1 || d < 8 || d % 8 || layer_stride_elems < (int64_t)B * beam * ctx * d || layer_stride_elems % 8) {
+    set_error("wis_op_kv_reorder: bad argument"); return WIS_E_ARG; }
+  hipStream_t st = ctx_stream(c);
+  BeamState bs; memset(&bs, 0, sizeof(bs));
+  bs.parent = const_cast<int*>(parent); bs.step_u = const_cast<int*>(step_u); bs.done = const_cast<int*>(done);
+  return tap_finish(st, launch_kv_reorder(st, reinterpret_cast<f16*>(kc_f16), reinterpret_cast<f16*>(vc_f16), (size_t)layer_stride_elems, L, bs, B, beam, P, ctx, d), "wis_op_kv_reorder");
+}
+int wis_op_kv_gather(int device, void* kc_f16, void* vc_f16, int64_t layer_stride_elems, int L, const int32_t* vstate, const int32_t* done, int beam, int w0, int ctx, int d) {
+  DeviceCtx* c; WIS_RET(get_ctx(device, &c));
+  std::lock_guard<std::mutex> op_lock(ctx_op_mutex(c));
+  if (!kc_f16 || !vc_f16 || !vstate || !done || L < 1 || beam < 1 || beam > MAX_R || w0 < 0 || w0 >= ctx || d < 8 || d % 8 || layer_stride_elems < (int64_t)beam * ctx * d || layer_stride_elems % 8) {
+    set_error("wis_op_kv_gather: bad argument"); return WIS_E_ARG; }
+  hipStream_t st = ctx_stream(c);
+  return tap_finish(st, launch_kv_gather(st, reinterpret_cast<f16*>(kc_f16), reinterpret_cast<f16*>(vc_f16), (size_t)layer_stride_elems, L, vstate, done, beam, w0, ctx, d), "wis_op_kv_gather");
+}
+int wis_op_no_speech(int device, const float* logits, int ld, int B, int rs, int r0, int V, int ns, float* out) {
+  DeviceCtx* c; WIS_RET(get_ctx(device, &c));
+  std::lock_guard<std::mutex> op_lock(ctx_op_mutex(c));
+  if (!logits || !out || B < 1 || rs < 1 || r0 < 0 || r0 >= rs || V < 1 || ld < V) { set_error("wis_op_no_speech: bad argument"); return WIS_E_ARG; }
+  hipStream_t st = ctx_stream(c);
+  return tap_finish(st, launch_no_speech(st, logits, ld, B, rs, r0, V, ns, out), "wis_op_no_speech");
+}
+int wis_op_lang_probs(int device, const float* logits, int ld, const int32_t* lang_ids, int n_lang, float* probs, int B) {
+  DeviceCtx* c; WIS_RET(get_ctx(device, &c));
+  std::lock_guard<std::mutex> op_lock(ctx_op_mutex(c));
+  if (!logits || !lang_ids || !probs || B < 1 || n_lang < 1 || ld < 1) { set_error("wis_op_lang_probs: bad argument"); return WIS_E_ARG; }
+  hipStream_t st = ctx_stream(c);
+  return tap_finish(st, launch_lang_probs(st, logits, ld, lang_ids, n_lang, probs, B), "wis_op_lang_probs");
+}
+int wis_op_greedy_rows(int device, const float* logits, int n_vocab, int n_vocab_pad, int eot, const float* bias_all, const float* bias_begin, const int32_t* step_u,
+                       int B, int beam, int lr_b, int lr_j, int lr_off, const int32_t* rowmap, int32_t* tok_out, float* lp_out) {
+  DeviceCtx* c; WIS_RET(get_ctx(device, &c));
+  std::lock_guard<std::mutex> op_lock(ctx_op_mutex(c));
+  if (!logits || !bias_begin || !step_u || !tok_out || !lp_out || B < 1 || beam < 1 || beam > MAX_R || n_vocab < STAT_SUB || n_vocab_pad < n_vocab || eot < 0 || eot >= n_vocab ||
+      lr_b < 0 || lr_j < 0 || lr_off < 0) { set_error("wis_op_greedy_rows: bad argument"); return WIS_E_ARG; }
+  hipStream_t st = ctx_stream(c);
+  const int rows = B * beam;
+  SampleCfg sc; memset(&sc, 0, sizeof(sc));
+  sc.n_vocab = n_vocab; sc.n_vocab_pad = n_vocab_pad; sc.eot = eot; sc.beam = beam; sc.n_cand = 2; sc.suppress_blank = 1; sc.greedy = 1;
+  TapScratch ts;
+  float *smax = nullptr, *ssum = nullptr, *sval = nullptr; int* sidx = nullptr;
+  if (!ts.get(&smax, (size_t)rows * STAT_SUB) || !ts.get(&ssum, (size_t)rows * STAT_SUB) || !ts.get(&sval, (size_t)rows * STAT_SUB * sc.n_cand) ||
+      !ts.get(&sidx, (size_t)rows * STAT_SUB * sc.n_cand)) { set_error("wis_op_greedy_rows: out of device memory"); return WIS_E_NOMEM; }
+  int rc = launch_logit_stats(st, logits, bias_all, bias_begin, step_u, smax, ssum, sval, sidx, B, sc, lr_b, lr_j, lr_off, nullptr, rowmap);
+  if (!rc) rc = launch_greedy_pick(st, smax, ssum, sval, sidx, rows, sc, tok_out, lp_out);
+  return tap_finish(st, rc, "wis_op_greedy_rows");
+}
+
 }  // extern "C"

@@ -133,6 +133,11 @@ SYMBOLS = [
     ("wis_op_enc_qkv", _i, [_i] + [_vp] * 5 + [_i] * 3),
     ("wis_op_enc_crosskv", _i, [_i] + [_vp] * 5 + [_i] * 4 + [_i64] * 2),
     ("wis_op_gemm_splitk_ln", _i, [_i] + [_vp] * 7 + [_i] * 4),
+    ("wis_op_kv_reorder", _i, [_i, _vp, _vp, _i64, _i, _vp, _vp, _vp, _i, _i, _i, _i, _i]),
+    ("wis_op_kv_gather", _i, [_i, _vp, _vp, _i64, _i, _vp, _vp, _i, _i, _i, _i]),
+    ("wis_op_no_speech", _i, [_i, _vp, _i, _i, _i, _i, _i, _i, _vp]),
+    ("wis_op_lang_probs", _i, [_i, _vp, _i, _vp, _i, _vp, _i]),
+    ("wis_op_greedy_rows", _i, [_i, _vp, _i, _i, _i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
     ("wis_sv_create", _i, [C.POINTER(SvConfig), _vp, _sz, _i, C.POINTER(Tensor), _i, _i, C.POINTER(_vp)]),
     ("wis_sv_destroy", None, [_vp]),
     ("wis_sv_device_bytes", _sz, [_vp]),
