@@ -332,6 +332,15 @@ int wis_op_layernorm(int device, const float* x, const float* gamma, const float
  * out f16 [B*T][d] */
 int wis_op_enc_attention(int device, const void* qk_f16, const void* vt_f16, void* out_f16,
                          int B, int T, int Tpad, int H);
+/* the same attention with the kernel named: form bit 0 = the lazy-reference loop (enc_attn_lazy_kernel: Q must already carry
+ * log2(e) / sqrt(64), as the engine's query projection delivers it; the tap makes no scaled copy), clear = enc_attn_kernel (Q carries
+ * 1 / sqrt(64)); bit 1 = the split-key pair (two workgroups per query tile and head, merged in the launch), WIS_E_ARG when
+ * cdiv(T, 64) < 4.  wis_op_enc_attention above chooses as the encoder does (and scales a private copy of Q for the lazy loop).
+ * Both entries, and the encoder: the V^T positions of keys >= T up to Tpad must hold FINITE values.  Those keys get weight exactly 0,
+ * but the P.V product still multiplies them (0 x NaN or 0 x inf would poison the whole row); the engine zeroes the image once at
+ * allocation and nothing writes those positions afterwards.  K rows >= T are never read (the loaders clamp to row T - 1). */
+int wis_op_enc_attention_ex(int device, const void* qk_f16, const void* vt_f16, void* out_f16,
+                            int B, int T, int Tpad, int H, int form);
 /* skinny GEMM used by the decoder: y[M][N] = epi(LN?(x)[M][K] . W[N][K]^T + bias); W is the
  * plain row-major f16 matrix (packed internally for the call).
  * flags: 1 = GELU, 2 = residual add in place into y f32, 4 = y f32 (else f16), 8 = fuse LayerNorm

@@ -37,7 +37,7 @@ namespace wis {
 
 
 // =======================================================================================
-// LayerNorm: fp32 [M][d] -> f16 [M][d]; one 64-lane wave per row, two-pass in registers.
+// LayerNorm: fp32 [M][d] -> f16 [M][d]; one 64-lane wave per row, two-pass in registers (the mean itself in two steps).
 #define WIS_PIN4(r) asm volatile("" :: "v"((r).x), "v"((r).y), "v"((r).z), "v"((r).w))
 template <bool AFFINE>
 __global__ __launch_bounds__(256) void layernorm_kernel(const float* __restrict__ x, const float* __restrict__ gamma,
@@ -66,7 +66,21 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const float* __restrict_
 #pragma unroll
     for (int i = 0; i < 8; ++i) { WIS_PIN4(g[i]); WIS_PIN4(be[i]); }
   }
-  const float mean = wave_sum(s) / (float)d;
+  // The mean in two steps.  mean0, the quotient of the plain sum, is off by a few ulp(mean): the lane sums pass through partial sums of
+  // up to 32 values, and on a row with a common offset (|mean| >> sigma) an ulp of the mean is not small beside the deviations - at
+  // |mean| = 1000, sigma = 1 it put 1e-4 on every output of the row.  The row is therefore centred on mean0 (x - mean0 is exact or
+  // nearly so exactly where it matters: x and mean0 within a factor of 2) and the mean of the CENTRED values, which is mean - mean0 to
+  // within an ulp of sigma, is taken off as well: `mean` below is that small remainder, and v holds x - mean0.
+  const float mean0 = wave_sum(s) / (float)d;
+  float s1 = 0.f;
+#pragma unroll
+  for (int i = 0; i < 8; ++i) {
+    const int idx = lane + 64 * i;
+    v[i].x -= mean0; v[i].y -= mean0; v[i].z -= mean0; v[i].w -= mean0;
+    const float t = (v[i].x + v[i].y) + (v[i].z + v[i].w);
+    s1 += idx < n4 ? t : 0.f;
+  }
+  const float mean = wave_sum(s1) / (float)d;
   float q = 0.f;
 #pragma unroll
   for (int i = 0; i < 8; ++i) {
@@ -1187,7 +1201,7 @@ __global__ void splitk_reduce_kernel(const float* __restrict__ part, int splits,
 // The same reduction with the LayerNorm that consumes the new residual rows fused in: one wave per row, the row stays in registers
 // between "x = sum of partials + bias + residual" (written back in fp32) and "y = LN(x) gamma + beta" (f16, the A operand of the
 // next projection) - one launch and one 7.7 MB read of x less per use.  Same summation order as splitk_reduce_kernel and the same
-// two-pass statistics as layernorm_kernel.  Loads are unconditional (clamped column index, masked result): a guarded load per
+// two-pass statistics layernorm_kernel had before its mean got a second step (the rows here are residual-stream rows, |mean| ~ sigma).  Loads are unconditional (clamped column index, masked result): a guarded load per
 // float4 compiles into a branch and a wait each.
 template <int SPLITS>
 __global__ __launch_bounds__(256) void splitk_reduce_ln_kernel(const float* __restrict__ part, int64_t zstride, const float* __restrict__ bias,
@@ -1745,12 +1759,12 @@ void launch_scale_q_log2e(hipStream_t st, f16* qk, int64_t rows, int d) {
 // part / counters: ENC_PART_FLOATS floats per workgroup and one zeroed counter per (utterance, head, query tile); given and with
 // at most 256 unsplit workgroups (one utterance of large-v2; round 3 split up to 600) the key range is split over two workgroups
 size_t enc_attention_part_floats(int B, int T, int H) { return (size_t)B * H * cdiv(T, 128) * 2 * ENC_PART_FLOATS; }
-int launch_enc_attention(hipStream_t st, const f16* qk, const f16* vt, f16* out, int B, int T, int Tpad, int H, float* part, unsigned* counters, size_t part_cap) {
+// the launch itself, loop and form given (the tap wis_op_enc_attention_ex names them; the encoder's choice is launch_enc_attention below).
+// split needs part / counters for cdiv(T, 128) * H * B pairs and at least four key tiles (two per workgroup of a pair).
+int launch_enc_attention_form(hipStream_t st, const f16* qk, const f16* vt, f16* out, int B, int T, int Tpad, int H, float* part, unsigned* counters, bool lazy, bool split) {
   if (Tpad < cdiv(T, AKT) * AKT || Tpad % 8) { set_error("enc_attention: Tpad=%d too small for T=%d", Tpad, T); return WIS_E_ARG; }
-  static const int env = getenv("WIS_ENC_ATTN_SPLIT") ? atoi(getenv("WIS_ENC_ATTN_SPLIT")) : -1;      // tuning: 0 never, 1 whenever possible
-  const int wgs = cdiv(T, 128) * H * B;
-  const bool split = part && counters && (size_t)wgs <= part_cap && cdiv(T, AKT) >= 4 && (env >= 0 ? env == 1 : wgs <= 256);      // never beyond the scratch it was given; split only while the unsplit grid leaves CUs empty (r4, sustained launches of the lazy loop, large-v2: one utterance = 240 workgroups 24.4 us unsplit / 23.6 split; two = 480: 35.8 / 41.9; three 49.7 / 57.6)
-  if (enc_attn_lazy()) {
+  if (split && (!part || !counters || cdiv(T, AKT) < 4)) { set_error("enc_attention: the split-key form needs scratch and >= 4 key tiles (T=%d)", T); return WIS_E_ARG; }
+  if (lazy) {
     if (split) hipLaunchKernelGGL((enc_attn_lazy_kernel<true>), dim3(2 * cdiv(T, 128), H, B), dim3(256), 0, st, qk, vt, out, T, Tpad, H, H * 64, part, counters);
     else hipLaunchKernelGGL((enc_attn_lazy_kernel<false>), dim3(cdiv(T, 128), H, B), dim3(256), 0, st, qk, vt, out, T, Tpad, H, H * 64, part, counters);
     return WIS_OK;
@@ -1758,6 +1772,12 @@ int launch_enc_attention(hipStream_t st, const f16* qk, const f16* vt, f16* out,
   if (split) hipLaunchKernelGGL((enc_attn_kernel<true>), dim3(2 * cdiv(T, 128), H, B), dim3(256), 0, st, qk, vt, out, T, Tpad, H, H * 64, part, counters);
   else hipLaunchKernelGGL((enc_attn_kernel<false>), dim3(cdiv(T, 128), H, B), dim3(256), 0, st, qk, vt, out, T, Tpad, H, H * 64, part, counters);
   return WIS_OK;
+}
+int launch_enc_attention(hipStream_t st, const f16* qk, const f16* vt, f16* out, int B, int T, int Tpad, int H, float* part, unsigned* counters, size_t part_cap) {
+  static const int env = getenv("WIS_ENC_ATTN_SPLIT") ? atoi(getenv("WIS_ENC_ATTN_SPLIT")) : -1;      // tuning: 0 never, 1 whenever possible
+  const int wgs = cdiv(T, 128) * H * B;
+  const bool split = part && counters && (size_t)wgs <= part_cap && cdiv(T, AKT) >= 4 && (env >= 0 ? env == 1 : wgs <= 256);      // never beyond the scratch it was given; split only while the unsplit grid leaves CUs empty (r4, sustained launches of the lazy loop, large-v2: one utterance = 240 workgroups 24.4 us unsplit / 23.6 split; two = 480: 35.8 / 41.9; three 49.7 / 57.6)
+  return launch_enc_attention_form(st, qk, vt, out, B, T, Tpad, H, part, counters, enc_attn_lazy(), split);
 }
 
 }  // namespace wis

@@ -32,6 +32,10 @@ int launch_gemm_crosskv(hipStream_t st, const GemmP& p, const float* bias, f16* 
 // split-key form is only taken when the launch fits that capacity
 int launch_enc_attention(hipStream_t st, const f16* qk, const f16* vt, f16* out, int B, int T, int Tpad, int H, float* part = nullptr, unsigned* counters = nullptr,
                          size_t part_cap = 0);
+// the same launch with the loop (lazy: enc_attn_lazy_kernel, Q pre-multiplied by log2(e) / sqrt(64); else enc_attn_kernel, Q by 1 / sqrt(64)) and
+// the form (split: two workgroups per query tile and head; needs part / counters for every pair and cdiv(T, 64) >= 4) named by the caller
+int launch_enc_attention_form(hipStream_t st, const f16* qk, const f16* vt, f16* out, int B, int T, int Tpad, int H, float* part, unsigned* counters,
+                              bool lazy, bool split);
 size_t enc_attention_part_floats(int B, int T, int H);
 // true: the lazy-reference loop (enc_attn_lazy_kernel), which expects Q pre-multiplied by log2(e) / sqrt(64); fixed per process
 bool enc_attn_lazy();

@@ -341,6 +341,30 @@ int wis_op_enc_attention(int device, const void* qk, const void* vt, void* out, 
   if (e != hipSuccess) { set_error("wis_op_enc_attention: %s", hipGetErrorString(e)); return WIS_E_HIP; }
   return WIS_OK;
 }
+int wis_op_enc_attention_ex(int device, const void* qk, const void* vt, void* out, int B, int T, int Tpad, int H, int form) {
+  DeviceCtx* c; WIS_RET(get_ctx(device, &c));
+  std::lock_guard<std::mutex> op_lock(ctx_op_mutex(c));
+  if (form & ~3) { set_error("wis_op_enc_attention_ex: form=%d (bit 0: lazy loop, bit 1: split-key pair)", form); return WIS_E_ARG; }
+  const bool lazy = form & 1, split = form & 2;
+  if (B < 1 || T < 1 || H < 1) { set_error("wis_op_enc_attention_ex: B=%d T=%d H=%d", B, T, H); return WIS_E_ARG; }
+  if (split && cdiv(T, 64) < 4) { set_error("wis_op_enc_attention_ex: the split-key pair needs at least four key tiles (T=%d)", T); return WIS_E_ARG; }
+  // Q is read as given (the lazy loop's log2(e) / 8 is the caller's, as the engine's query projection delivers it): no scaled copy
+  hipStream_t st = ctx_stream(c);
+  float* part = nullptr; unsigned* counters = nullptr;
+  const size_t ncnt = (size_t)B * H * cdiv(T, 128);
+  int rc = WIS_OK;
+  if (split) {
+    if (hipMalloc(reinterpret_cast<void**>(&part), enc_attention_part_floats(B, T, H) * 4) != hipSuccess ||
+        hipMalloc(reinterpret_cast<void**>(&counters), ncnt * 4) != hipSuccess) { set_error("wis_op_enc_attention_ex: out of device memory"); rc = WIS_E_NOMEM; }
+    else hipMemsetAsync(counters, 0, ncnt * 4, st);
+  }
+  if (!rc) rc = launch_enc_attention_form(st, reinterpret_cast<const f16*>(qk), reinterpret_cast<const f16*>(vt), reinterpret_cast<f16*>(out), B, T, Tpad, H, part, counters, lazy, split);
+  hipError_t e = hipStreamSynchronize(st);
+  hipFree(part); hipFree(counters);
+  if (rc) return rc;
+  if (e != hipSuccess) { set_error("wis_op_enc_attention_ex: %s", hipGetErrorString(e)); return WIS_E_HIP; }
+  return WIS_OK;
+}
 int wis_op_gemv(int device, const void* x, const float* gamma, const float* beta, const void* W, const float* bias, void* y, int M, int N, int K, int flags) {
   DeviceCtx* c; WIS_RET(get_ctx(device, &c));
   std::lock_guard<std::mutex> op_lock(ctx_op_mutex(c));

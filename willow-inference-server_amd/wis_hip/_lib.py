@@ -119,6 +119,7 @@ SYMBOLS = [
     ("wis_op_gemm", _i, [_i, _vp, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _i]),
     ("wis_op_layernorm", _i, [_i, _vp, _vp, _vp, _vp, _i, _i]),
     ("wis_op_enc_attention", _i, [_i, _vp, _vp, _vp, _i, _i, _i, _i]),
+    ("wis_op_enc_attention_ex", _i, [_i, _vp, _vp, _vp, _i, _i, _i, _i, _i]),
     ("wis_op_gemv", _i, [_i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i]),
     ("wis_op_gemv_cols", _i, [_i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i]),
     ("wis_op_dec_self_attn", _i, [_i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i]),
