@@ -165,6 +165,18 @@ typedef struct {
                                             < 0: no cap */
   int32_t no_speech_prob;   /* 1: keep P(<|nospeech|>) of the softmax over the raw logits at <|startoftranscript|> per utterance
                                (wis_last_no_speech_prob) */
+  /* The two CTranslate2 4.1.0 processors against a hypothesis that loops (RepetitionPenalty, NoRepeatNgram; restated, not pinned against
+   * CTranslate2).  A live beam's HISTORY is what this search has generated for it so far, after the last beam step's reordering; the start
+   * sequence and a decoder prefix are not counted (CTranslate2 also counts the last start token: the default suppress list masks that token
+   * in every prompt form the server builds, so the two agree there and differ only with suppress_default = 0).  EOT never enters a history
+   * that continues, so neither rule touches EOT; fixed_new_tokens keeps its override.  Both are no-ops at the first step (all beams sample
+   * from the one prompt row).  Order: repetition_penalty on the raw logits, then the masks (suppress lists, n-gram bans), then the timestamp
+   * rules - whose text / timestamp decision therefore sees penalised, banned values.  wis_generate / wis_debug_search; drafts answer
+   * WIS_E_UNSUPPORTED.  A negative or non-finite penalty, a negative n-gram size: WIS_E_ARG, nothing enqueued. */
+  float   repetition_penalty;     /* p > 0: for every DISTINCT token t of the history, logit x of t becomes x * p if x < 0, else x / p (fp32, a true
+                                     division; once however often t occurs).  1 - and 0, what a caller that never knew the field passes - : off */
+  int32_t no_repeat_ngram_size;   /* n >= 1: with a history h of L >= n tokens, every i in [0, L - n] with h[i .. i+n-2] == h[L-n+1 .. L-1] masks
+                                     h[i+n-1] (n = 1: every history token).  0: off */
 } wis_gen_opts_t;
 
 /* out_ids: [B][max_new] (max_new = resolved max_new_tokens), out_len: [B], out_score: [B]

@@ -2463,6 +2463,56 @@ int launch_ts_rules(hipStream_t st, const float* logits, const float* bias_all, 
   return WIS_OK;
 }
 
+// =======================================================================================
+// repetition_penalty / no_repeat_ngram_size (CTranslate2 4.1.0 RepetitionPenalty / NoRepeatNgram, restated), the pre-pass at the head of the
+// sampling tail when either option is on.  grid B*beam (one workgroup per live row), block 256.  The row's generated history is
+// bs.alive[m][0 .. min(step_u[b], max_new)) - max_new <= 256 = one token per thread, as in ts_rules_kernel - and the row of m->logits the
+// step samples from is PATCHED IN PLACE, so every kernel behind this one reads a row that already carries both rules:
+//   penalty p: every DISTINCT history token t gets one read-modify-write, x < 0 ? x * p : x / p (fp32, a true division) - the thread that
+//              holds the first occurrence of t does it, so a token that occurs three times is penalised once;
+//   n-gram n:  thread i <= L - n compares h[i .. i+n-2] with the last n - 1 tokens and stores -inf at h[i+n-1] on a match (n = 1: every
+//              history token; L < n: nothing).  The bans are stored behind a barrier: a token both penalised and banned ends as -inf.
+// Nothing happens at step 0 (every beam samples from ONE shared prompt row there, and no history exists), for a finished (or parked)
+// utterance, or on the measurement convention's forced-EOT step (only EOT survives that step, and EOT is in no history that continues).
+__global__ __launch_bounds__(256) void rep_rules_kernel(float* __restrict__ logits, const int* __restrict__ step_u, const int* __restrict__ done,
+                                                        const int* __restrict__ alive, SampleCfg cfg, float penalty, int ngram,
+                                                        int lr_b, int lr_j, int lr_off) {
+  __shared__ int4 sh4[64];
+  int* sh = reinterpret_cast<int*>(sh4);
+  const int tid = threadIdx.x, m = blockIdx.x, b = m / cfg.beam, jb = m - b * cfg.beam;
+  if (done[b]) return;
+  int L = step_u[b];
+  L = L < cfg.max_new ? L : cfg.max_new;
+  if (L <= 0 || (cfg.fixed_new > 0 && L >= cfg.fixed_new)) return;
+  const int V = cfg.n_vocab;
+  int tk = tid < L ? alive[(size_t)m * cfg.max_new + tid] : -1;
+  tk = (tk >= 0 && tk < V) ? tk : -1;      // (nothing outside the row is ever addressed)
+  sh[tid] = tk;
+  __syncthreads();
+  float* row = logits + (size_t)(b * lr_b + jb * lr_j + lr_off) * cfg.n_vocab_pad;
+  if (penalty != 1.f) {
+    bool dup = false;      // an earlier position holds the same token (broadcast LDS reads, four positions each)
+    for (int i = 0; i < L; i += 4) {
+      const int4 h = sh4[i >> 2];
+      dup = dup | ((h.x == tk) & (i < tid)) | ((h.y == tk) & (i + 1 < tid)) | ((h.z == tk) & (i + 2 < tid)) | ((h.w == tk) & (i + 3 < tid));
+    }
+    if (tk >= 0 && !dup) { const float x = row[tk]; row[tk] = x < 0.f ? x * penalty : __fdiv_rn(x, penalty); }
+  }
+  if (ngram >= 1 && L >= ngram) {
+    __syncthreads();       // the penalty's stores are ahead of the bans (workgroup-scope release / acquire)
+    bool hit = tid <= L - ngram;
+    const int i0 = hit ? tid : 0, tail = L - ngram + 1;
+    for (int q = 0; q < ngram - 1; ++q) hit = hit & (sh[i0 + q] == sh[tail + q]);
+    const int t = sh[i0 + ngram - 1];
+    if (hit && t >= 0) row[t] = -INFINITY;
+  }
+}
+int launch_rep_rules(hipStream_t st, float* logits, const BeamState& bs, int B, const SampleCfg& cfg, float penalty, int ngram, int lr_b, int lr_j, int lr_off) {
+  if (cfg.max_new > 256 || !(penalty > 0.f) || ngram < 0) { set_error("rep_rules: config out of range"); return WIS_E_UNSUPPORTED; }
+  hipLaunchKernelGGL(rep_rules_kernel, dim3(B * cfg.beam), dim3(256), 0, st, logits, bs.step_u, bs.done, bs.alive, cfg, penalty, ngram, lr_b, lr_j, lr_off);
+  return WIS_OK;
+}
+
 // no_speech_prob (openai-whisper probs_at_sot, CTranslate2 return_no_speech_prob): softmax over the full vocabulary of the raw logits of
 // the decoder row that read <|startoftranscript|>, at <|nospeech|>.  grid B, block 256; row of utterance b = logits + (b * rs + r0) * ld
 __global__ __launch_bounds__(256) void no_speech_kernel(const float* __restrict__ logits, int ld, int rs, int r0, int V, int ns, float* __restrict__ out) {

@@ -15,7 +15,17 @@ struct SampleCtx {
   int B, P, beam;
   SampleCfg sc; const float* bias_all;
   bool ts; int ts_max_init;      // Whisper's timestamp rules (prompts without <|notimestamps|>): a pre-pass ahead of the sampling statistics of every step
+  float rep_pen = 1.f; int rep_ngram = 0;      // repetition_penalty / no_repeat_ngram_size (1 / 0: off): a pre-pass that patches the logits rows, ahead of everything else
+  bool rep() const { return rep_pen != 1.f || rep_ngram != 0; }
 };
+// repetition_penalty / no_repeat_ngram_size of a call, resolved (0 in the C struct means "off" for both) - or refused
+static int resolve_rep_opts(const wis_gen_opts_t* o, SampleCtx* g) {
+  const float p = o->repetition_penalty; const int n = o->no_repeat_ngram_size;
+  if (!std::isfinite(p) || p < 0.f) { set_error("repetition_penalty %g: a finite value > 0 (1 or 0: off)", (double)p); return WIS_E_ARG; }
+  if (n < 0) { set_error("no_repeat_ngram_size %d: >= 0 (0: off)", n); return WIS_E_ARG; }
+  g->rep_pen = p == 0.f ? 1.f : p; g->rep_ngram = n;
+  return WIS_OK;
+}
 // everything a stage needs to know about the call: built once (make_gen_ctx), read-only afterwards
 struct GenCtx : SampleCtx {
   const float* input; const int32_t* prompt; const wis_gen_opts_t* o;
@@ -44,6 +54,7 @@ static int make_gen_ctx(wis_model* m, const float* input, int B, const int32_t* 
   if (P - 1 + max_new > c.n_text_ctx) max_new = c.n_text_ctx - (P - 1);
   g.max_new = max_new;
   for (int i = 0; i < B * P; ++i) if (prompt[i] < 0 || prompt[i] >= c.n_vocab) { set_error("prompt token %d out of range", prompt[i]); return WIS_E_ARG; }
+  WIS_RET(resolve_rep_opts(o, &g));
   g.t0 = std::chrono::steady_clock::now();
   g.sc = make_sample_cfg(m, o, beam, max_new, &g.patience);
   g.bias_all = o->suppress_default ? m->bias_all : nullptr;
@@ -54,6 +65,7 @@ static int make_gen_ctx(wis_model* m, const float* input, int B, const int32_t* 
   g.ts = o->timestamps != 0;
   g.ts_max_init = o->max_initial_timestamp_index < 0 ? -1 : o->max_initial_timestamp_index;
   if (g.ts && draft != nullptr) { set_error("timestamps: not available for drafted decodes (wis_generate_draft / wis_generate_draft_beam)"); return WIS_E_UNSUPPORTED; }
+  if (g.rep() && draft != nullptr) { set_error("repetition_penalty / no_repeat_ngram_size: not available for drafted decodes (wis_generate_draft / wis_generate_draft_beam)"); return WIS_E_UNSUPPORTED; }
   int sot_row = -1;
   if (o->no_speech_prob && !drafting) {
     for (int i = 0; i < P; ++i) if (prompt[i] == c.sot) { sot_row = i; break; }
@@ -115,7 +127,7 @@ static int front_half(const GenCtx& g) {
   return WIS_OK;
 }
 
-// The sampling tail of a decoder pass: timestamp rules -> candidate statistics -> beam step -> cache reorder.  The logits row of (b, j) is
+// The sampling tail of a decoder pass: [repetition rules ->] [timestamp rules ->] candidate statistics -> beam step -> cache reorder.  The logits row of (b, j) is
 // b*rows.b + j*rows.j + rows.off: a step samples beam j from row b*beam + j {beam, 1, 0}, the pass that carries the prompt samples every beam from the
 // last prompt row {P, 0, P - 1}.  TAIL_TAPS: the tap build's stamp rows of the two sampling kernels (the product build carries none).
 // TAIL_NO_CACHE: a search over given logits has no cache to reorder (wis_debug_search).
@@ -125,6 +137,7 @@ static int sampling_tail(const SampleCtx& g, LogitRows rows, int flags) {
   wis_model* m = g.m; hipStream_t st = g.st; const wis_config_t& c = m->cfg;
   const int lr_b = rows.b, lr_j = rows.j, lr_off = rows.off;
   unsigned long long* prof = (WIS_TAPS && (flags & TAIL_TAPS)) ? m->d_prof + (size_t)c.n_dec_layers * 8 * 16 : nullptr;
+  if (g.rep()) WIS_RET(launch_rep_rules(st, m->logits, m->bs, g.B, g.sc, g.rep_pen, g.rep_ngram, lr_b, lr_j, lr_off));
   if (g.ts) WIS_RET(launch_ts_rules(st, m->logits, g.bias_all, m->bias_begin, m->bs, g.B, g.sc, c.no_timestamps, g.ts_max_init, lr_b, lr_j, lr_off, m->ts_desc));
   WIS_RET(launch_logit_stats(st, m->logits, g.bias_all, m->bias_begin, m->bs.step_u, m->st_max, m->st_sum, m->st_val, m->st_idx, g.B, g.sc, lr_b, lr_j, lr_off, prof ? prof + 16 : nullptr,
                              nullptr, g.ts ? m->ts_desc : nullptr));
@@ -385,6 +398,7 @@ struct StepGraph {
     key.suppress_default = g.o->suppress_default; key.early_exit = sc.allow_early_exit; key.lp = sc.length_penalty; key.patience = g.patience; key.spin = m->spin_now ? 1 : 0;
     key.sa_nb = nb;
     key.timestamps = g.ts ? 1 : 0; key.max_init = g.ts ? g.ts_max_init : 0;
+    key.rep_pen = g.rep_pen == 1.f ? 0.f : g.rep_pen; key.rep_ngram = g.rep_ngram;      // (off: the zeroes of a key that never knew the fields)
     auto it = m->graphs.find(key);
     if (it != m->graphs.end()) { *out = it->second; return WIS_OK; }
     hipGraph_t graph = nullptr; hipGraphExec_t ge = nullptr;
@@ -635,6 +649,7 @@ int wis_generate_draft(wis_model_t* m, const float* input, const int32_t* prompt
                        const int32_t* draft, int n_draft, int32_t* out_ids, int32_t* out_len, float* out_score, int32_t* accepted) {
   if (!m || !input || !prompt || !o || !out_ids || !out_len || (n_draft > 0 && !draft) || n_draft < 0) { set_error("wis_generate_draft: bad argument"); return WIS_E_ARG; }
   if (o->timestamps) { set_error("wis_generate_draft: timestamps are not available for drafted decodes"); return WIS_E_UNSUPPORTED; }
+  if ((o->repetition_penalty != 0.f && o->repetition_penalty != 1.f) || o->no_repeat_ngram_size != 0) { set_error("wis_generate_draft: repetition_penalty / no_repeat_ngram_size are not available for drafted decodes"); return WIS_E_UNSUPPORTED; }
   WIS_ENTER(m, "wis_generate_draft")
   int acc = 0;
   WIS_RET(generate_with_retry("wis_generate_draft", m, input, 1, prompt, P, o, out_ids, out_len, out_score, draft, n_draft, &acc));
@@ -646,6 +661,7 @@ int wis_generate_draft_beam(wis_model_t* m, const float* input, const int32_t* p
                             const int32_t* draft_tok, const int32_t* draft_org, int n_steps, int32_t* out_ids, int32_t* out_len, float* out_score, int32_t* accepted_steps) {
   if (!m || !input || !prompt || !o || !out_ids || !out_len || n_steps < 0 || (n_steps > 0 && (!draft_tok || !draft_org))) { set_error("wis_generate_draft_beam: bad argument"); return WIS_E_ARG; }
   if (o->timestamps) { set_error("wis_generate_draft_beam: timestamps are not available for drafted decodes"); return WIS_E_UNSUPPORTED; }
+  if ((o->repetition_penalty != 0.f && o->repetition_penalty != 1.f) || o->no_repeat_ngram_size != 0) { set_error("wis_generate_draft_beam: repetition_penalty / no_repeat_ngram_size are not available for drafted decodes"); return WIS_E_UNSUPPORTED; }
   WIS_ENTER(m, "wis_generate_draft_beam")
   int acc = 0;
   WIS_RET(generate_with_retry("wis_generate_draft_beam", m, input, 1, prompt, P, o, out_ids, out_len, out_score, n_steps > 0 ? draft_tok : nullptr, n_steps, &acc,

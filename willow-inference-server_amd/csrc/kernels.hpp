@@ -171,6 +171,11 @@ constexpr int TS_DESC_INTS = 8;
 struct BeamState;
 int launch_ts_rules(hipStream_t st, const float* logits, const float* bias_all, const float* bias_begin, const BeamState& bs, int B,
                     const SampleCfg& cfg, int no_ts, int max_init, int lr_b, int lr_j, int lr_off, int* ts_desc);
+// repetition_penalty / no_repeat_ngram_size (dec_kernels.hip rep_rules_kernel): per live row, the row of `logits` the step samples from is
+// patched in place from the row's generated history - one penalty per distinct history token, -inf per banned n-gram completion - ahead of
+// every other kernel of the tail; rows as launch_logit_stats reads them.  penalty 1 / ngram 0: that rule is off (the caller launches
+// nothing when both are)
+int launch_rep_rules(hipStream_t st, float* logits, const BeamState& bs, int B, const SampleCfg& cfg, float penalty, int ngram, int lr_b, int lr_j, int lr_off);
 // probability of <|nospeech|> under the full-vocabulary softmax of each utterance's <|startoftranscript|> row (b * rs + r0)
 int launch_no_speech(hipStream_t st, const float* logits, int ld, int B, int rs, int r0, int V, int ns, float* out);
 struct BeamState {

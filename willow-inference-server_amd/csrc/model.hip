@@ -140,6 +140,7 @@ struct DecLayerW {
 struct GraphKey {
   int B, beam, P, max_new, fixed_new, suppress_blank, suppress_default, early_exit, spin, sa_nb; float lp, patience;
   int timestamps, max_init;      // the timestamp form of the step (ts_rules_kernel ahead of logit_stats_kernel<true>) and its first-timestamp cap
+  float rep_pen; int rep_ngram;  // rep_rules_kernel at the head of the tail (both 0: off, no such launch)
   bool operator<(const GraphKey& o) const { return memcmp(this, &o, sizeof(GraphKey)) < 0; }
 };
 
@@ -1257,9 +1258,10 @@ int wis_debug_search(wis_model_t* m, const float* logits, int n_steps, int B, co
   if (max_new > n_steps) { set_error("wis_debug_search: %d steps of logits for max_new_tokens %d", n_steps, max_new); return WIS_E_ARG; }
   hipStream_t st = m->st;
   const int Mrows = B * beam, V = c.n_vocab;
-  WIS_RET(init_beam_state(m, B, beam));
   float patience;
   SampleCtx g;      // a search over given logits: a one-token prompt
+  WIS_RET(resolve_rep_opts(o, &g));
+  WIS_RET(init_beam_state(m, B, beam));
   g.m = m; g.st = st; g.B = B; g.P = 1; g.beam = beam;
   g.sc = make_sample_cfg(m, o, beam, max_new, &patience);
   g.bias_all = o->suppress_default ? m->bias_all : nullptr;

@@ -41,7 +41,7 @@ class GenOpts(C.Structure):
     _fields_ = [("input_kind", C.c_int32), ("beam_size", C.c_int32), ("max_new_tokens", C.c_int32), ("length_penalty", C.c_float),
                 ("patience", C.c_float), ("suppress_blank", C.c_int32), ("suppress_default", C.c_int32),
                 ("fixed_new_tokens", C.c_int32), ("queue_depth", C.c_int32), ("timestamps", C.c_int32), ("max_initial_timestamp_index", C.c_int32),
-                ("no_speech_prob", C.c_int32)]
+                ("no_speech_prob", C.c_int32), ("repetition_penalty", C.c_float), ("no_repeat_ngram_size", C.c_int32)]
 
 
 class Timing(C.Structure):

@@ -195,19 +195,21 @@ def _last_trajectory(r, b, beam):
 
 
 def _generate_chunk(r, mel, prompts, P, beam, max_new, lp, patience, suppress_blank, suppress_default, fixed_new, kind, device_ptr=None, draft=None, want_traj=False,
-                    timestamps=False, max_initial_timestamp_index=50, no_speech_prob=False):
+                    timestamps=False, max_initial_timestamp_index=50, no_speech_prob=False, repetition_penalty=1.0, no_repeat_ngram_size=0):
     """mel: host ndarray [B, ...] - or, with device_ptr, just the batch size B of features already resident on r.device.
     draft (one utterance): token ids of an earlier hypothesis (beam 1: wis_generate_draft) or the trajectory (tok [n][beam], org [n][beam]) of
     an earlier beam search (wis_generate_draft_beam) - verified in multi-row passes before ordinary steps go on.
     want_traj: every result carries `.trajectory`, what a later call takes as its draft.
     timestamps: Whisper's timestamp rules every step (max_initial_timestamp_index None: no cap on the first timestamp);
-    no_speech_prob: every result carries P(<|nospeech|>) at <|startoftranscript|> (wis_last_no_speech_prob)."""
+    no_speech_prob: every result carries P(<|nospeech|>) at <|startoftranscript|> (wis_last_no_speech_prob).
+    repetition_penalty / no_repeat_ngram_size: CTranslate2's two options against looping hypotheses (include/wis_hip.h; 1 / 0: off)."""
     B = int(mel) if device_ptr is not None else mel.shape[0]
     o = _lib.GenOpts(kind, beam, max_new, lp, patience, int(bool(suppress_blank)), int(bool(suppress_default)), int(fixed_new), 0)
     if timestamps:
         o.timestamps = 1
         o.max_initial_timestamp_index = -1 if max_initial_timestamp_index is None else int(max_initial_timestamp_index)
     o.no_speech_prob = int(bool(no_speech_prob))
+    o.repetition_penalty, o.no_repeat_ngram_size = float(repetition_penalty), int(no_repeat_ngram_size)
     pr = np.ascontiguousarray(np.asarray(prompts, np.int32).reshape(B, P))
     ids = np.zeros((B, max_new), np.int32)
     lens = np.zeros(B, np.int32)
@@ -263,6 +265,33 @@ def timestamp_prompt(prompt, special=None):
     return all(eot <= t < nts for t in p[p.index(sot):])
 
 
+def _check_repetition(repetition_penalty, no_repeat_ngram_size, drafted=False):
+    """-> (penalty, n-gram size) as the engine takes them; a value CTranslate2 would not take, or either option together with a draft, is a
+    request error (ValueError -> HTTP 400 in wis_hip.server)."""
+    try:
+        p = float(repetition_penalty)
+        n = int(no_repeat_ngram_size)
+        if n != float(no_repeat_ngram_size):
+            raise ValueError
+    except (TypeError, ValueError, OverflowError):
+        raise ValueError(f"repetition_penalty {repetition_penalty!r} / no_repeat_ngram_size {no_repeat_ngram_size!r}: a number and an integer") from None
+    if not (p > 0 and p != float("inf")):
+        raise ValueError(f"repetition_penalty {repetition_penalty!r} must be a finite number > 0 (1: off)")
+    if n < 0:
+        raise ValueError(f"no_repeat_ngram_size {no_repeat_ngram_size!r} must be >= 0 (0: off)")
+    if drafted and (p != 1.0 or n != 0):
+        raise ValueError("repetition_penalty / no_repeat_ngram_size cannot be combined with draft_tokens / draft_trajectory")
+    return p, n
+
+
+def _rep_key(key, p, n):
+    """The batcher key of a call with either option on: the draft / timestamp slots padded to their fixed positions (_run_batch), then the two
+    values.  Both off: the key as it is."""
+    if p == 1.0 and n == 0:
+        return key
+    return (key + (None, False, False, 50, False)[len(key) - 9:])[:14] + (p, n)
+
+
 def _check_patience(beam_size, patience):
     """CTranslate2 searches until round(beam_size * patience) hypotheses have finished; the engine stores MAX_HYPOTHESES - beam_size + 1.
     A patience beyond that is a request error (it used to be clamped silently: a shorter search than CTranslate2's, other ids)."""
@@ -284,6 +313,8 @@ def _run_batch(replica, key, rows):
     want_traj = bool(key[10]) if len(key) > 10 else False
     ts, mi, nsp = key[11:14] if len(key) > 11 else (False, 50, False)      # Whisper.generate's timestamp tail
     tsk = dict(timestamps=ts, max_initial_timestamp_index=mi, no_speech_prob=nsp) if len(key) > 11 else {}
+    if len(key) > 14:      # ... and its repetition tail
+        tsk.update(repetition_penalty=key[14], no_repeat_ngram_size=key[15])
     dr = (draft[1] if draft and len(rows) == 1 else None)
     prompts = [p for _, p in rows]
     if kind == _lib.WIS_IN_MEL_DEV:
@@ -440,9 +471,15 @@ class Whisper:
         Timestamps: a Whisper start sequence without <|notimestamps|> (<|startoftranscript|>, language, task - `timestamp_prompt`) decodes
         under Whisper's timestamp rules (first timestamp at most <|0.00|> + max_initial_timestamp_index; None: no cap); drafts cannot be
         combined with them.  A prompt that carries text after its start sequence (a decoder prefix) keeps the plain search.  return_no_speech_prob=True fills
-        `no_speech_prob` (P(<|nospeech|>) at <|startoftranscript|>)."""
-        if num_hypotheses != 1 or repetition_penalty != 1 or no_repeat_ngram_size != 0 or sampling_topk != 1:
-            raise NotImplementedError("only the decoding options WIS uses are implemented (defaults of CTranslate2 4.1.0)")
+        `no_speech_prob` (P(<|nospeech|>) at <|startoftranscript|>).
+        `repetition_penalty` (> 0; 1: off) and `no_repeat_ngram_size` (>= 0; 0: off) are CTranslate2's: every distinct token the search has generated
+        for a beam has its logit divided (multiplied when negative) by the penalty, and a token that would complete an n-gram the beam already holds is
+        masked (include/wis_hip.h states both).  A bad value, or either option together with a draft, is a ValueError; calls with different values never
+        share a device batch."""
+        if num_hypotheses != 1 or sampling_topk != 1:
+            raise NotImplementedError("num_hypotheses and sampling_topk are not implemented (the other decoding options of CTranslate2 4.1.0 are)")
+        drafted = bool(draft_tokens is not None and len(draft_tokens) or draft_trajectory is not None and len(draft_trajectory[0]))
+        rep_p, rep_n = _check_repetition(repetition_penalty, no_repeat_ngram_size, drafted)
         mel = self._features(features, input_kind)
         B = mel.shape[0]
         if len(prompts) != B:
@@ -471,6 +508,7 @@ class Whisper:
         if timestamps or return_no_speech_prob:      # (the tail keeps the draft slots at fixed positions: _run_batch reads key[11:14])
             mi = None if max_initial_timestamp_index is None else int(max_initial_timestamp_index)
             key = (key + (None, False))[:11] + (timestamps, mi if timestamps else 50, bool(return_no_speech_prob))
+        key = _rep_key(key, rep_p, rep_n)
         rows = [(np.ascontiguousarray(mel[b]), [int(t) for t in prompts[b]]) for b in range(B)]
         return self._batcher.submit(key, rows)
 
@@ -511,7 +549,8 @@ class Whisper:
         raise ValueError(f"no replica on device {device}")
 
     def generate_from_device(self, device, mel_device_ptr, prompt, *, beam_size=5, max_length=448, length_penalty=1, patience=1,
-                             suppress_blank=True, fixed_new_tokens=0, replica=None, draft_tokens=None, draft_trajectory=None, return_trajectory=False):
+                             suppress_blank=True, fixed_new_tokens=0, replica=None, draft_tokens=None, draft_trajectory=None, return_trajectory=False,
+                             repetition_penalty=1, no_repeat_ngram_size=0):
         """One utterance whose log-mel features ALREADY live in HBM on `device` (f32 [n_mels][3000] at `mel_device_ptr`, e.g. an
         audio.MelStream after finish()): WIS_IN_MEL_DEV - nothing is staged through the host.  Goes through the micro-batcher bound
         to that DEVICE: any replica of the GPU can read the features, so concurrent windows of several streaming sessions on one GPU
@@ -529,7 +568,9 @@ class Whisper:
         key = (P, int(beam_size), max_new, float(length_penalty), float(patience), bool(suppress_blank), True, int(fixed_new_tokens),
                int(_lib.WIS_IN_MEL_DEV))
         _check_patience(beam_size, patience)
-        key = key + self._draft_key(1, beam_size, draft_tokens, draft_trajectory, return_trajectory)
+        drafted = bool(draft_tokens is not None and len(draft_tokens) or draft_trajectory is not None and len(draft_trajectory[0]))
+        rep_p, rep_n = _check_repetition(repetition_penalty, no_repeat_ngram_size, drafted)
+        key = _rep_key(key + self._draft_key(1, beam_size, draft_tokens, draft_trajectory, return_trajectory), rep_p, rep_n)
         return self._batcher.submit(key, [(int(mel_device_ptr), [int(t) for t in prompt])], affinity=("device", device))[0]
 
     def _generate_chunk(self, r, mel, prompts, P, beam, max_new, lp, patience, suppress_blank, suppress_default, fixed_new, kind):

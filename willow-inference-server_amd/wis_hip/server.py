@@ -150,7 +150,18 @@ def create_app(models=None, settings=None, max_workers=None, sv=None):
         # the engine's beam ceiling is a property of the request, not a server fault (the reference accepts any int, main.py:1180)
         if not 1 <= beam <= s.max_beam:
             raise BadRequest(f"beam_size {beam} outside 1..{s.max_beam}")
-        return dict(model=model, beam_size=beam,
+        # CTranslate2's two options against looping hypotheses: absent = the settings' values; unparsable or out of range = 400
+        rp, ng = q.get("repetition_penalty"), q.get("no_repeat_ngram_size")
+        try:
+            rp = float(rp) if rp not in (None, "") else None
+            ng = int(ng) if ng not in (None, "") else None
+        except ValueError:
+            raise BadRequest(f"Invalid repetition_penalty {rp!r} / no_repeat_ngram_size {ng!r}")
+        if rp is not None and not (0 < rp < float("inf")):
+            raise BadRequest(f"repetition_penalty {rp} must be a finite number > 0")
+        if ng is not None and ng < 0:
+            raise BadRequest(f"no_repeat_ngram_size {ng} must be >= 0")
+        return dict(model=model, beam_size=beam, repetition_penalty=rp, no_repeat_ngram_size=ng,
                     detect_language=_as_bool(q.get("detect_language"), s.detect_language), force_language=q.get("force_language") or None,
                     translate=_as_bool(q.get("translate"), False), timestamps=_as_bool(q.get("timestamps"), False),
                     word_timestamps=_as_bool(q.get("word_timestamps"), False))
@@ -160,6 +171,7 @@ def create_app(models=None, settings=None, max_workers=None, sv=None):
         kw = {"timestamps": True} if p["timestamps"] else {}      # (segment times: one 30 s window; longer audio is a 400)
         if p["word_timestamps"]:                                  # (word times imply segment times; no vocabulary / long audio is a 400)
             kw = {"word_timestamps": True}
+        kw.update({k: p[k] for k in ("repetition_penalty", "no_repeat_ngram_size") if p[k] is not None})      # (absent: do_whisper takes the settings' values)
         return await loop.run_in_executor(pool, lambda: do_whisper(audio_file, p["model"], p["beam_size"], "transcribe", p["detect_language"],
                                                                    p["force_language"], p["translate"], models=get_models(), **kw))
 

@@ -77,6 +77,11 @@ class APISettings:
     # measurement convention for seeded synthetic weights, which never emit EOT: decode exactly this many tokens
     # (EOT masked until then, then forced).  0 = off: the product default, natural termination
     fixed_new_tokens: int = 0
+    # CTranslate2's two decoding options against a hypothesis that loops, as every request without the query parameters of the same names
+    # decodes: every distinct token a beam has generated has its logit divided (multiplied when negative) by the penalty; a token that would
+    # complete an n-gram the beam already holds is masked.  1.0 / 0 = off (CTranslate2's defaults)
+    repetition_penalty: float = 1.0
+    no_repeat_ngram_size: int = 0
     # --- speaker verification (`voice_auth`, support_sv): not reference fields, the reference hard-codes both paths (main.py:308-312,
     # 839).  The model directory is a Hugging Face WavLMForXVector checkpoint (or "synthetic:wavlm-base-plus-sv[:SEED]"); the speakers
     # directory holds one NAME.npy embedding per enrolled speaker (python -m wis_hip.sv enroll NAME AUDIO)

@@ -77,9 +77,14 @@ class _IncrementalFront:
 
 class StreamingSession:
     def __init__(self, model, beam_size=None, task="transcribe", detect_language=False, force_language=None, models=None,
-                 fixed_new_tokens=0, incremental=True, speculate_every_s=None):
+                 fixed_new_tokens=0, incremental=True, speculate_every_s=None, repetition_penalty=None, no_repeat_ngram_size=None):
         self.models = models or default_models()
         s = self.models.settings
+        # CTranslate2's repetition_penalty / no_repeat_ngram_size (None: the settings' values) go to every window decode that runs WITHOUT a
+        # draft - eager windows, interim hypotheses, a final decode with nothing to verify.  A decode that verifies a draft keeps the plain
+        # search, as it always has: the engine has no drafted form of the two rules
+        self._rep = dict(repetition_penalty=getattr(s, "repetition_penalty", 1.0) if repetition_penalty is None else repetition_penalty,
+                         no_repeat_ngram_size=getattr(s, "no_repeat_ngram_size", 0) if no_repeat_ngram_size is None else no_repeat_ngram_size)
         self.model_name, self.task = model, task
         self.beam_size = s.beam_size if beam_size is None else beam_size
         self.detect_language, self.force_language = detect_language, force_language
@@ -223,6 +228,8 @@ class StreamingSession:
         kw = dict(draft or {})
         if want_traj:
             kw["return_trajectory"] = True
+        if "draft_tokens" not in kw and "draft_trajectory" not in kw:
+            kw.update(getattr(self, "_rep", {}))
         if stream is not None:
             try:
                 stream.finish(to_host=False)

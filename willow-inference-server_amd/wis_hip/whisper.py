@@ -317,8 +317,10 @@ def chunkit(lst, num):
 
 
 def do_whisper(audio_file, model, beam_size=None, task="transcribe", detect_language=False, force_language=None, translate=False,
-               models=None, fixed_new_tokens=None, timestamps=False, word_timestamps=False):
-    """word_timestamps=True implies timestamps=True: after the search the window's text tokens are aligned with the audio in one
+               models=None, fixed_new_tokens=None, timestamps=False, word_timestamps=False, repetition_penalty=None, no_repeat_ngram_size=None):
+    """repetition_penalty / no_repeat_ngram_size: CTranslate2's options of those names (None: the settings' values, 1.0 and 0 = off), handed
+    to every `generate` call of the request - chunked windows, the timestamped pass, the translation pass.
+    word_timestamps=True implies timestamps=True: after the search the window's text tokens are aligned with the audio in one
     `Whisper.align` call (cross-attention of the alignment heads + DTW on the GPU) and every segment gains
     `words: [{word, start, end, probability}]`, grouped as openai-whisper's split_to_word_tokens + merge_punctuations group them.
     Out of scope: the pause / median-duration heuristics of openai-whisper's add_word_timestamps, audio over 30 s, and `translate`
@@ -329,6 +331,8 @@ def do_whisper(audio_file, model, beam_size=None, task="transcribe", detect_lang
     if fixed_new_tokens is None:
         fixed_new_tokens = s.fixed_new_tokens
     beam_size = s.beam_size if beam_size is None else beam_size
+    rep = dict(repetition_penalty=getattr(s, "repetition_penalty", 1.0) if repetition_penalty is None else repetition_penalty,
+               no_repeat_ngram_size=getattr(s, "no_repeat_ngram_size", 0) if no_repeat_ngram_size is None else no_repeat_ngram_size)
     whisper_model = models.get(model)
     special = model_special_tokens(whisper_model)
     n_mels = getattr(whisper_model, "n_mels", audio.N_MELS)
@@ -391,7 +395,7 @@ def do_whisper(audio_file, model, beam_size=None, task="transcribe", detect_lang
     for batch in chunkit(features, s.concurrent_gpu_chunks):
         feats = ctranslate2.StorageView.from_array(np.ascontiguousarray(batch))
         results.extend(whisper_model.generate(feats, [prompt] * len(batch), beam_size=beam_size, return_scores=False,
-                                              fixed_new_tokens=fixed_new_tokens, input_kind=kind))
+                                              fixed_new_tokens=fixed_new_tokens, input_kind=kind, **rep))
     assert len(results) == total_chunk_count, "Result length doesn't match expected total_chunk_count"
     if use_chunking:
         tokens = audio.find_longest_common_sequence([(results[i].sequences_ids[0], strides[i]) for i in range(total_chunk_count)],
@@ -419,7 +423,7 @@ def do_whisper(audio_file, model, beam_size=None, task="transcribe", detect_lang
     if translate and total_chunk_count <= s.concurrent_gpu_chunks:       # main.py:729-748 (its `len(int)` bug aside: short audio only)
         tprompt = [special.sot, special.language_token_id(language), special.translate, special.notimestamps]
         feats = ctranslate2.StorageView.from_array(np.ascontiguousarray(features))
-        tres = whisper_model.generate(feats, [tprompt] * total_chunk_count, beam_size=beam_size, fixed_new_tokens=fixed_new_tokens, input_kind=kind)
+        tres = whisper_model.generate(feats, [tprompt] * total_chunk_count, beam_size=beam_size, fixed_new_tokens=fixed_new_tokens, input_kind=kind, **rep)
         translation = tokenizer.decode(tres[0].sequences_ids[0]).strip()
         out_translation_tokens = tres[0].sequences_ids[0]
     else:
