@@ -519,49 +519,32 @@ int wis_align_last_timing(wis_model_t* m, float* ms) {
 }
 
 int wis_op_dtw(int device, const float* x, int N, int M, int32_t* text_idx, int32_t* time_idx, int32_t* len) {
-  DeviceCtx* c; WIS_RET(get_ctx(device, &c));
-  std::lock_guard<std::mutex> op_lock(ctx_op_mutex(c));
+  Tap t(device, "wis_op_dtw"); WIS_RET(t.rc);
   if (!x || !text_idx || !time_idx || !len || N < 1 || M < 1) { set_error("wis_op_dtw: bad argument"); return WIS_E_ARG; }
-  hipStream_t st = ctx_stream(c);
   unsigned* trace = nullptr; int* rev = nullptr;
-  if (hipMalloc(reinterpret_cast<void**>(&trace), (size_t)(N + 1) * dtw_wpr(M) * 4) != hipSuccess || hipMalloc(reinterpret_cast<void**>(&rev), (size_t)2 * (N + M) * 4) != hipSuccess) {
-    hipFree(trace); set_error("wis_op_dtw: out of device memory"); return WIS_E_NOMEM; }
+  WIS_RET(t.get(&trace, (size_t)(N + 1) * dtw_wpr(M))); WIS_RET(t.get(&rev, (size_t)2 * (N + M)));
   // text_idx / time_idx hold up to N + M - 1 entries
-  int rc = launch_align_dtw(st, x, 0, M, nullptr, nullptr, N, M, 1, trace, rev, text_idx, time_idx, len, N + M - 1);
-  hipError_t e = hipStreamSynchronize(st);
-  hipFree(trace); hipFree(rev);
-  if (rc) return rc;
-  if (e != hipSuccess) { set_error("wis_op_dtw: %s", hipGetErrorString(e)); return WIS_E_HIP; }
-  return WIS_OK;
+  return t.finish(launch_align_dtw(t.st, x, 0, M, nullptr, nullptr, N, M, 1, trace, rev, text_idx, time_idx, len, N + M - 1));
 }
 
 int wis_op_align_matrix(int device, const float* q, const void* kx_f16, int T_tokens, int n_heads_sel, int T, int frames, int width, float* out) {
-  DeviceCtx* c; WIS_RET(get_ctx(device, &c));
-  std::lock_guard<std::mutex> op_lock(ctx_op_mutex(c));
+  Tap t(device, "wis_op_align_matrix"); WIS_RET(t.rc);
   if (!q || !kx_f16 || !out || T_tokens < 1 || n_heads_sel < 1 || T < 1 || frames < 1 || frames > T) { set_error("wis_op_align_matrix: bad argument"); return WIS_E_ARG; }
-  hipStream_t st = ctx_stream(c);
+  hipStream_t st = t.st;
   // q fp32 [n_heads_sel][T_tokens][64] (finished queries), kx_f16 [n_heads_sel][8][T][8] (the cross-attention K image), out fp32 [T_tokens][frames]
   const int n = T_tokens, G = align_chunk_heads(n_heads_sel, 1, n, T);
   f16* qsel = nullptr; long long* koff = nullptr; int* meta = nullptr; float *W = nullptr, *acc = nullptr;
   std::vector<long long> hk(n_heads_sel);
   for (int s = 0; s < n_heads_sel; ++s) hk[s] = (long long)s * T * 64;
   const int hm[2] = {n, frames};
-  int rc = WIS_OK;
-  if (hipMalloc(reinterpret_cast<void**>(&qsel), (size_t)n_heads_sel * n * 128) != hipSuccess || hipMalloc(reinterpret_cast<void**>(&koff), (size_t)n_heads_sel * 8) != hipSuccess ||
-      hipMalloc(reinterpret_cast<void**>(&meta), 8) != hipSuccess || hipMalloc(reinterpret_cast<void**>(&W), (size_t)G * n * T * 4) != hipSuccess ||
-      hipMalloc(reinterpret_cast<void**>(&acc), (size_t)n * T * 4) != hipSuccess) { set_error("wis_op_align_matrix: out of device memory"); rc = WIS_E_NOMEM; }
-  if (!rc) {
-    hipMemcpyAsync(koff, hk.data(), (size_t)n_heads_sel * 8, hipMemcpyHostToDevice, st);
-    hipMemcpyAsync(meta, hm, 8, hipMemcpyHostToDevice, st);
-    hipLaunchKernelGGL(align_q16_kernel, dim3(n, n_heads_sel), dim3(64), 0, st, q, qsel, n, n);
-    rc = launch_align_matrix(st, qsel, reinterpret_cast<const f16*>(kx_f16), koff, 0, meta, meta + 1, W, acc, 1, n_heads_sel, n, n, frames, T, width);
-    if (!rc && hipMemcpy2DAsync(out, (size_t)frames * 4, acc, (size_t)T * 4, (size_t)frames * 4, n, hipMemcpyDeviceToDevice, st) != hipSuccess) { set_error("wis_op_align_matrix: copy failed"); rc = WIS_E_HIP; }
-  }
-  hipError_t e = hipStreamSynchronize(st);
-  hipFree(qsel); hipFree(koff); hipFree(meta); hipFree(W); hipFree(acc);
-  if (rc) return rc;
-  if (e != hipSuccess) { set_error("wis_op_align_matrix: %s", hipGetErrorString(e)); return WIS_E_HIP; }
-  return WIS_OK;
+  WIS_RET(t.get(&qsel, (size_t)n_heads_sel * n * 64)); WIS_RET(t.get(&koff, (size_t)n_heads_sel)); WIS_RET(t.get(&meta, 2));
+  WIS_RET(t.get(&W, (size_t)G * n * T)); WIS_RET(t.get(&acc, (size_t)n * T));
+  hipMemcpyAsync(koff, hk.data(), (size_t)n_heads_sel * 8, hipMemcpyHostToDevice, st);
+  hipMemcpyAsync(meta, hm, 8, hipMemcpyHostToDevice, st);
+  hipLaunchKernelGGL(align_q16_kernel, dim3(n, n_heads_sel), dim3(64), 0, st, q, qsel, n, n);
+  WIS_RET(launch_align_matrix(st, qsel, reinterpret_cast<const f16*>(kx_f16), koff, 0, meta, meta + 1, W, acc, 1, n_heads_sel, n, n, frames, T, width));
+  if (hipMemcpy2DAsync(out, (size_t)frames * 4, acc, (size_t)T * 4, (size_t)frames * 4, n, hipMemcpyDeviceToDevice, st) != hipSuccess) { set_error("wis_op_align_matrix: copy failed"); return WIS_E_HIP; }
+  return t.finish(WIS_OK);
 }
 
 }  // extern "C"

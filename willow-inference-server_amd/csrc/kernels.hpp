@@ -103,6 +103,8 @@ int launch_gemv_frag3(hipStream_t st, const GemvP* p, int n);
 __host__ __device__ static inline size_t xf_index(int m, int k, int MB) {
   return ((size_t)((k >> 5) * MB + (m >> 4)) * 64 + (m & 15) + 16 * ((k >> 3) & 3)) * 8 + (k & 7);
 }
+// f16 elements of a fragment image of K columns and MB row blocks (host code: allocation and memset sizes)
+constexpr size_t xf_elems(int K, int MB) { return (size_t)(K / 32) * MB * 64 * 8; }
 // x (fp32 or f16, row-major [M][K]) -> fragment image (+ optional per-16-column partial sums): test taps and the weight-stream tap
 int launch_xf_pack(hipStream_t st, const void* x, int x_f16, f16* xf, float* stat, int M, int K, int MB);
 int launch_dec_embed_xf(hipStream_t st, const f16* emb, const f16* pos_emb, const int* tok, const int* pos, float* x, f16* xf, float* stat, int M, int d, int MB);

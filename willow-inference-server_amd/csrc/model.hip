@@ -598,11 +598,11 @@ int alloc_buffers(wis_model* m) {
   WIS_RET(dalloc(m, &m->dln, (size_t)MAX_ROWS * d));
   WIS_RET(dalloc(m, &m->dxh, (size_t)MAX_ROWS * d));
   {  // fragment images (kernels.hpp xf_index): [K/32][3 row blocks][64][8] f16; zeroed once (rows >= M are never written)
-    const size_t blk = (size_t)(MAX_ROWS / 16) * 64 * 8;
-    WIS_RET(dalloc(m, &m->dxf, (size_t)(d / 32) * blk)); WIS_RET(dalloc(m, &m->daoxf, (size_t)(d / 32) * blk)); WIS_RET(dalloc(m, &m->dhxf, (size_t)(4 * d / 32) * blk));
+    const size_t img = xf_elems(d, MAX_ROWS / 16), img4 = xf_elems(4 * d, MAX_ROWS / 16);
+    WIS_RET(dalloc(m, &m->dxf, img)); WIS_RET(dalloc(m, &m->daoxf, img)); WIS_RET(dalloc(m, &m->dhxf, img4));
     WIS_RET(dalloc(m, &m->dstat, (size_t)MAX_ROWS * (d / 16) * 2));
-    WIS_HIP_CHECK(hipMemsetAsync(m->dxf, 0, (size_t)(d / 32) * blk * 2, m->st)); WIS_HIP_CHECK(hipMemsetAsync(m->daoxf, 0, (size_t)(d / 32) * blk * 2, m->st));
-    WIS_HIP_CHECK(hipMemsetAsync(m->dhxf, 0, (size_t)(4 * d / 32) * blk * 2, m->st));
+    WIS_HIP_CHECK(hipMemsetAsync(m->dxf, 0, img * 2, m->st)); WIS_HIP_CHECK(hipMemsetAsync(m->daoxf, 0, img * 2, m->st));
+    WIS_HIP_CHECK(hipMemsetAsync(m->dhxf, 0, img4 * 2, m->st));
   }
   WIS_RET(dalloc(m, &m->logits, (size_t)MAX_ROWS * m->n_vocab_pad));
   // (row groups of the cross-attention: utterances - or, verifying a beam-search draft, up to MAX_ROWS / 16 groups of 16 tree rows of ONE utterance)
@@ -1094,7 +1094,7 @@ struct BusyGuard {
 };
 #define WIS_ENTER(m, what)                                                                                      \
   BusyGuard _busy(m);                                                                                           \
-  if (!_busy.ok) { set_error(what ": another call is running on this handle (one call at a time per replica)"); return WIS_E_STATE; }
+  if (!_busy.ok) { set_error("%s: another call is running on this handle (one call at a time per replica)", what); return WIS_E_STATE; }
 
 }  // namespace
 

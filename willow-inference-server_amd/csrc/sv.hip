@@ -752,60 +752,38 @@ int wis_debug_sv_taps(wis_sv_t* s, const float* pcm, int64_t n, int tap, int lay
 // ---- single-kernel taps (tests): device pointers in, the production launch helper on the device's op stream, synchronised --------
 int wis_op_sv_conv0(int device, const float* pcm, int64_t n, const float* w0, const float* gamma, const float* beta, void* y) {
   if (!pcm || !w0 || !gamma || !beta || !y || n < CONV_K[0] || n > (int64_t)16000 * 60) { set_error("wis_op_sv_conv0: bad argument"); return WIS_E_ARG; }
-  DeviceCtx* c; WIS_RET(get_ctx(device, &c));
-  std::lock_guard<std::mutex> op_lock(ctx_op_mutex(c));
-  hipStream_t st = ctx_stream(c);
+  Tap t(device, "wis_op_sv_conv0"); WIS_RET(t.rc);
   const int T0 = (int)((n - CONV_K[0]) / CONV_S[0] + 1);
   float *part = nullptr, *ss = nullptr;
-  if (hipMalloc(reinterpret_cast<void**>(&part), (size_t)cdiv(T0, CHUNK0) * C0 * 2 * 4) != hipSuccess ||
-      hipMalloc(reinterpret_cast<void**>(&ss), (size_t)2 * C0 * 4) != hipSuccess) {
-    hipFree(part); set_error("wis_op_sv_conv0: out of device memory"); return WIS_E_NOMEM;
-  }
-  sv_launch_conv0(st, pcm, w0, gamma, beta, part, ss, reinterpret_cast<f16*>(y), T0);
-  hipError_t e = hipGetLastError();
-  if (e == hipSuccess) e = hipStreamSynchronize(st);
-  hipFree(part); hipFree(ss);
-  if (e != hipSuccess) { set_error("wis_op_sv_conv0: %s", hipGetErrorString(e)); return WIS_E_HIP; }
-  return WIS_OK;
+  WIS_RET(t.get(&part, (size_t)cdiv(T0, CHUNK0) * C0 * 2)); WIS_RET(t.get(&ss, (size_t)2 * C0));
+  sv_launch_conv0(t.st, pcm, w0, gamma, beta, part, ss, reinterpret_cast<f16*>(y), T0);
+  return t.finish(WIS_OK);
 }
 int wis_op_sv_posconv(int device, const float* x, const void* W, const float* bias, float* out, int T) {
   if (!x || !W || !bias || !out || T < 1) { set_error("wis_op_sv_posconv: bad argument"); return WIS_E_ARG; }
-  DeviceCtx* c; WIS_RET(get_ctx(device, &c));
-  std::lock_guard<std::mutex> op_lock(ctx_op_mutex(c));
-  sv_launch_posconv(ctx_stream(c), x, reinterpret_cast<const f16*>(W), bias, out, T);
-  WIS_HIP_CHECK(hipGetLastError());
-  WIS_HIP_CHECK(hipStreamSynchronize(ctx_stream(c)));
-  return WIS_OK;
+  Tap t(device, "wis_op_sv_posconv"); WIS_RET(t.rc);
+  sv_launch_posconv(t.st, x, reinterpret_cast<const f16*>(W), bias, out, T);
+  return t.finish(WIS_OK);
 }
 int wis_op_sv_attention(int device, const void* qkv, const float* xin, const float* gw, const float* gb, const float* gconst, const float* tab,
                         int L, void* out, int T) {
   if (!qkv || !xin || !gw || !gb || !gconst || !tab || !out || T < 1 || L < T) { set_error("wis_op_sv_attention: bad argument"); return WIS_E_ARG; }
-  DeviceCtx* c; WIS_RET(get_ctx(device, &c));
-  std::lock_guard<std::mutex> op_lock(ctx_op_mutex(c));
-  sv_launch_attn(ctx_stream(c), reinterpret_cast<const f16*>(qkv), xin, gw, gb, gconst, tab, L, reinterpret_cast<f16*>(out), T);
-  WIS_HIP_CHECK(hipGetLastError());
-  WIS_HIP_CHECK(hipStreamSynchronize(ctx_stream(c)));
-  return WIS_OK;
+  Tap t(device, "wis_op_sv_attention"); WIS_RET(t.rc);
+  sv_launch_attn(t.st, reinterpret_cast<const f16*>(qkv), xin, gw, gb, gconst, tab, L, reinterpret_cast<f16*>(out), T);
+  return t.finish(WIS_OK);
 }
 int wis_op_sv_layernorm(int device, const void* x, int in_f16, const float* gamma, const float* beta, void* y16, float* y32, float* ws, void* ws16,
                         float wl, int wmode, int M, int d) {
   if (!x || !gamma || !beta || !y16 || wmode < 0 || wmode > 2 || (wmode && !ws) || M < 1) { set_error("wis_op_sv_layernorm: bad argument"); return WIS_E_ARG; }
-  DeviceCtx* c; WIS_RET(get_ctx(device, &c));
-  std::lock_guard<std::mutex> op_lock(ctx_op_mutex(c));
-  if (in_f16) WIS_RET(sv_ln<true>(ctx_stream(c), x, gamma, beta, reinterpret_cast<f16*>(y16), y32, ws, reinterpret_cast<f16*>(ws16), wl, wmode, M, d));
-  else WIS_RET(sv_ln<false>(ctx_stream(c), x, gamma, beta, reinterpret_cast<f16*>(y16), y32, ws, reinterpret_cast<f16*>(ws16), wl, wmode, M, d));
-  WIS_HIP_CHECK(hipGetLastError());
-  WIS_HIP_CHECK(hipStreamSynchronize(ctx_stream(c)));
-  return WIS_OK;
+  Tap t(device, "wis_op_sv_layernorm"); WIS_RET(t.rc);
+  return t.finish(in_f16 ? sv_ln<true>(t.st, x, gamma, beta, reinterpret_cast<f16*>(y16), y32, ws, reinterpret_cast<f16*>(ws16), wl, wmode, M, d)
+                         : sv_ln<false>(t.st, x, gamma, beta, reinterpret_cast<f16*>(y16), y32, ws, reinterpret_cast<f16*>(ws16), wl, wmode, M, d));
 }
 int wis_op_sv_xvector_tail(int device, const float* z, int ldz, int T, int n, const float* w_fe, const float* b_fe, float* stats, float* emb) {
   if (!z || !w_fe || !b_fe || !stats || !emb || T < 2 || n < 1 || n > ldz) { set_error("wis_op_sv_xvector_tail: bad argument"); return WIS_E_ARG; }
-  DeviceCtx* c; WIS_RET(get_ctx(device, &c));
-  std::lock_guard<std::mutex> op_lock(ctx_op_mutex(c));
-  sv_launch_xvector_tail(ctx_stream(c), z, ldz, T, n, w_fe, b_fe, stats, emb);
-  WIS_HIP_CHECK(hipGetLastError());
-  WIS_HIP_CHECK(hipStreamSynchronize(ctx_stream(c)));
-  return WIS_OK;
+  Tap t(device, "wis_op_sv_xvector_tail"); WIS_RET(t.rc);
+  sv_launch_xvector_tail(t.st, z, ldz, T, n, w_fe, b_fe, stats, emb);
+  return t.finish(WIS_OK);
 }
 
 }  // extern "C"

@@ -1,5 +1,54 @@
 // taps.hip — debug, tuning and measurement taps (wis_debug_*, wis_bench_weight_stream, wis_dev_*, wis_op_*).  Included by model.hip: the taps run the
 // product's own static helpers (dec_forward, the stage builders, prep_projection), not copies of them.
+//
+// How to write a tap (a wis_op_* entry point: one product launch_* function on caller-supplied device memory; here, in align.hip and in sv.hip):
+//   Tap t(device, "wis_op_name"); WIS_RET(t.rc);        get_ctx + the device's op mutex; t.st is the stream all taps of a device share
+//   argument checks: set_error("wis_op_name: ...") and return (after the Tap here and in align.hip, in front of it in sv.hip: a call that is
+//                                                       wrong in its device and in an argument keeps the answer it always got)
+//   WIS_RET(t.get(&p, n_elems[, true]));                private device scratch (true: zeroed on t.st); sets the out-of-memory message itself
+//   WIS_RET(launch_...(t.st, ...));                     any step but the last: returning early is always safe
+//   return t.finish(launch_...(t.st, ...));             the last launch: collects the launch error, synchronises, gives the verdict
+// The Tap's destructor synchronises the stream when finish() was not reached, frees the scratch and only then lets go of the mutex, so no
+// return path frees memory under work in flight and none needs a clean-up of its own: no hipMalloc / hipFree / hipStreamSynchronize in a tap.
+namespace {
+struct Tap {
+  const char* const name;      // the entry point the caller used: prefix of the messages
+  hipStream_t st = nullptr;
+  int rc;                      // entry verdict (get_ctx's code)
+  Tap(int device, const char* who) : name(who) {
+    DeviceCtx* c = nullptr;
+    if ((rc = get_ctx(device, &c)) != WIS_OK) return;
+    lock = std::unique_lock<std::mutex>(ctx_op_mutex(c));
+    st = ctx_stream(c);
+  }
+  Tap(const Tap&) = delete;
+  Tap& operator=(const Tap&) = delete;
+  template <class T> int get(T** p, size_t n_elems, bool zeroed = false) {
+    const size_t bytes = n_elems * sizeof(T) ? n_elems * sizeof(T) : 16;
+    void* q = nullptr;
+    if (hipMalloc(&q, bytes) != hipSuccess) { (void)hipGetLastError(); set_error("%s: out of device memory", name); return WIS_E_NOMEM; }
+    scratch.push_back(q); *p = reinterpret_cast<T*>(q);
+    if (zeroed) hipMemsetAsync(q, 0, bytes, st);
+    return WIS_OK;
+  }
+  int finish(int launch_rc) {      // launch_rc wins; otherwise a HIP error of the launches or of the stream becomes WIS_E_HIP
+    const hipError_t e0 = hipGetLastError(), e = hipStreamSynchronize(st);
+    synced = true;
+    if (launch_rc) return launch_rc;
+    if (e0 != hipSuccess || e != hipSuccess) { set_error("%s: %s", name, hipGetErrorString(e0 != hipSuccess ? e0 : e)); return WIS_E_HIP; }
+    return WIS_OK;
+  }
+  ~Tap() {      // (the members go after this body: the frees happen under the lock)
+    if (lock.owns_lock() && !synced) hipStreamSynchronize(st);
+    for (void* q : scratch) hipFree(q);
+  }
+ private:
+  std::unique_lock<std::mutex> lock;
+  std::vector<void*> scratch;
+  bool synced = false;
+};
+}  // namespace
+
 extern "C" {
 
 int wis_debug_encode(wis_model_t* m, const float* input, int input_kind, int B, float* enc_out) {
@@ -16,51 +65,24 @@ int wis_debug_encode(wis_model_t* m, const float* input, int input_kind, int B, 
   return WIS_OK;
 }
 
-int wis_debug_logits(wis_model_t* m, const float* input, int input_kind, int B, const int32_t* dec_in, int T, float* logits) {
-  if (!m || !input || !dec_in || !logits || T < 1 || T > m->cfg.n_text_ctx) { set_error("wis_debug_logits: bad argument"); return WIS_E_ARG; }
-  WIS_ENTER(m, "wis_debug_logits")
+// teacher-forced logits in blocks of R positions (wis_debug_logits: R = 1); `who` is the entry point the caller used
+static int debug_logits_rows(const char* who, wis_model_t* m, const float* input, int input_kind, int B, const int32_t* dec_in, int T, int R, float* logits) {
+  WIS_ENTER(m, who)
   WIS_HIP_CHECK(hipSetDevice(m->device));
   WIS_RET(check_batch(m, B, 1));
+  if (B * R > MAX_ROWS) { set_error("%s: B*R = %d exceeds %d decoder rows per pass", who, B * R, MAX_ROWS); return WIS_E_STATE; }
   WIS_RET(stage_input(m, input, input_kind, B));
   WIS_RET(run_encoder(m, B));
   WIS_RET(run_cross_kv(m, B));
   const int V = m->cfg.n_vocab;
-  for (int t = 0; t < T; ++t) {
-    std::vector<int> tok(B);
-    for (int b = 0; b < B; ++b) tok[b] = dec_in[b * T + t];
-    for (int attempt = 0; attempt < 2; ++attempt) {      // (a pass whose granule hand-off gave up is repeated in the ticket form)
-      SpinClaim claim(m, B);
-      WIS_RET(single_row_setup(m, B, tok, t));
-      WIS_RET(dec_forward(m, B, 1, B, true, 1, 0));
-      for (int b = 0; b < B; ++b)
-        WIS_HIP_CHECK(hipMemcpyAsync(logits + ((size_t)b * T + t) * V, m->logits + (size_t)b * m->n_vocab_pad, (size_t)V * 4, hipMemcpyDeviceToHost, m->st));
-      bool gave_up = false;
-      WIS_RET(spin_gave_up(m, &gave_up));
-      if (!gave_up) break;
-    }
-  }
-  return WIS_OK;
-}
-
-int wis_debug_logits_rows(wis_model_t* m, const float* input, int input_kind, int B, const int32_t* dec_in, int T, int R, float* logits) {
-  if (!m || !input || !dec_in || !logits || T < 1 || T > m->cfg.n_text_ctx || R < 1 || R > 16) { set_error("wis_debug_logits_rows: bad argument (1 <= R <= 16)"); return WIS_E_ARG; }
-  WIS_ENTER(m, "wis_debug_logits_rows")
-  WIS_HIP_CHECK(hipSetDevice(m->device));
-  WIS_RET(check_batch(m, B, 1));
-  if (B * R > MAX_ROWS) { set_error("wis_debug_logits_rows: B*R = %d exceeds %d decoder rows per pass", B * R, MAX_ROWS); return WIS_E_STATE; }
-  WIS_RET(stage_input(m, input, input_kind, B));
-  WIS_RET(run_encoder(m, B));
-  WIS_RET(run_cross_kv(m, B));
-  const int V = m->cfg.n_vocab;
-  // teacher-forced in blocks of R positions: the rows (b, i) of a pass sit at positions t0 + i of utterance b's KV slot (causal by
-  // position, like the merged prompt pass of wis_generate), so a pass has B * R rows - with B * R > 8 it takes the batched-row
-  // route (dec_forward_frag: fragment images, partial-sum LayerNorm statistics) that wis_debug_logits' one row per utterance never
-  // reaches at small B
+  // the rows (b, i) of a pass sit at positions t0 + i of utterance b's KV slot (causal by position, like the merged prompt pass of
+  // wis_generate), so a pass has B * R rows - with B * R > 8 it takes the batched-row route (dec_forward_frag: fragment images,
+  // partial-sum LayerNorm statistics) that one row per utterance never reaches at small B
   for (int t0 = 0; t0 < T; t0 += R) {
     const int rows = std::min(R, T - t0), M = B * rows;
     std::vector<int> tok(M), pos(M), slot(M), ls(M);
     for (int b = 0; b < B; ++b) for (int i = 0; i < rows; ++i) { const int r = b * rows + i; tok[r] = dec_in[b * T + t0 + i]; pos[r] = t0 + i; slot[r] = b; ls[r] = b; }
-    for (int r = 0; r < M; ++r) if (tok[r] < 0 || tok[r] >= V) { set_error("wis_debug_logits_rows: token %d out of range", tok[r]); return WIS_E_ARG; }
+    for (int r = 0; r < M; ++r) if (tok[r] < 0 || tok[r] >= V) { set_error("%s: token %d out of range", who, tok[r]); return WIS_E_ARG; }
     for (int attempt = 0; attempt < 2; ++attempt) {      // (a pass whose granule hand-off gave up is repeated in the ticket form)
       SpinClaim claim(m, B);
       WIS_RET(upload_rows(m, tok, pos, slot, ls));
@@ -73,6 +95,14 @@ int wis_debug_logits_rows(wis_model_t* m, const float* input, int input_kind, in
     }
   }
   return WIS_OK;
+}
+int wis_debug_logits(wis_model_t* m, const float* input, int input_kind, int B, const int32_t* dec_in, int T, float* logits) {
+  if (!m || !input || !dec_in || !logits || T < 1 || T > m->cfg.n_text_ctx) { set_error("wis_debug_logits: bad argument"); return WIS_E_ARG; }
+  return debug_logits_rows("wis_debug_logits", m, input, input_kind, B, dec_in, T, 1, logits);
+}
+int wis_debug_logits_rows(wis_model_t* m, const float* input, int input_kind, int B, const int32_t* dec_in, int T, int R, float* logits) {
+  if (!m || !input || !dec_in || !logits || T < 1 || T > m->cfg.n_text_ctx || R < 1 || R > 16) { set_error("wis_debug_logits_rows: bad argument (1 <= R <= 16)"); return WIS_E_ARG; }
+  return debug_logits_rows("wis_debug_logits_rows", m, input, input_kind, B, dec_in, T, R, logits);
 }
 
 int wis_debug_tree_logits(wis_model_t* m, const float* input, int input_kind, const int32_t* prompt, int P, int beam,
@@ -223,8 +253,8 @@ int wis_bench_weight_stream(wis_model_t* m, int M, int passes, float* total_ms, 
     return stream(m->proj, count);
   };
   if (frag) {       // zero rows: fragment image of zeros (allocation state), partial sums of zeros
-    WIS_HIP_CHECK(hipMemsetAsync(m->dxf, 0, (size_t)(d / 32) * (MAX_ROWS / 16) * 64 * 8 * 2, st));
-    WIS_HIP_CHECK(hipMemsetAsync(m->dhxf, 0, (size_t)(4 * d / 32) * (MAX_ROWS / 16) * 64 * 8 * 2, st));
+    WIS_HIP_CHECK(hipMemsetAsync(m->dxf, 0, xf_elems(d, MAX_ROWS / 16) * 2, st));
+    WIS_HIP_CHECK(hipMemsetAsync(m->dhxf, 0, xf_elems(4 * d, MAX_ROWS / 16) * 2, st));
     WIS_HIP_CHECK(hipMemsetAsync(m->dstat, 0, (size_t)MAX_ROWS * (d / 16) * 2 * 4, st));
   }
   WIS_HIP_CHECK(hipMemsetAsync(m->dx, 0, (size_t)MAX_ROWS * d * 4, st));
@@ -284,93 +314,51 @@ int wis_dev_copy_peer(int dst_device, void* dst, int src_device, const void* src
 }
 
 int wis_op_gemm(int device, const void* A, int lda, const void* W, const float* bias, const float* residual, void* C, int M, int N, int K, int flags) {
-  DeviceCtx* c; WIS_RET(get_ctx(device, &c));
-  std::lock_guard<std::mutex> op_lock(ctx_op_mutex(c));
-  hipStream_t st = ctx_stream(c);
+  Tap t(device, "wis_op_gemm"); WIS_RET(t.rc);
+  const GemmP g = gemm_plain(reinterpret_cast<const f16*>(A), lda, reinterpret_cast<const f16*>(W), M, N, K);
   if (flags & 8) {   // split-K = 2 path of the encoder's FFN2: requires bias, residual and fp32 output
     if (!bias || !residual || (flags & 7) != (2 | 4)) { set_error("wis_op_gemm: split-K needs bias, residual, flags 2|4|8"); return WIS_E_ARG; }
     float* scratch = nullptr;
-    WIS_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&scratch), (size_t)2 * M * N * 4));
-    int rc = launch_gemm_splitk_resid(st, gemm_plain(reinterpret_cast<const f16*>(A), lda, reinterpret_cast<const f16*>(W), M, N, K), 2, scratch, bias, residual,
-                                      reinterpret_cast<float*>(C));
-    hipError_t e = hipStreamSynchronize(st);
-    hipFree(scratch);
-    if (rc) return rc;
-    if (e != hipSuccess) { set_error("wis_op_gemm: %s", hipGetErrorString(e)); return WIS_E_HIP; }
-    return WIS_OK;
+    WIS_RET(t.get(&scratch, (size_t)2 * M * N));
+    return t.finish(launch_gemm_splitk_resid(t.st, g, 2, scratch, bias, residual, reinterpret_cast<float*>(C)));
   }
-  WIS_RET(launch_gemm_generic(st, gemm_plain(reinterpret_cast<const f16*>(A), lda, reinterpret_cast<const f16*>(W), M, N, K), bias, residual, C, flags));
-  WIS_HIP_CHECK(hipGetLastError());
-  WIS_HIP_CHECK(hipStreamSynchronize(st));
-  return WIS_OK;
+  return t.finish(launch_gemm_generic(t.st, g, bias, residual, C, flags));
 }
 int wis_op_layernorm(int device, const float* x, const float* gamma, const float* beta, void* y, int M, int d) {
-  DeviceCtx* c; WIS_RET(get_ctx(device, &c));
-  std::lock_guard<std::mutex> op_lock(ctx_op_mutex(c));
-  WIS_RET(launch_layernorm(ctx_stream(c), x, gamma, beta, reinterpret_cast<f16*>(y), M, d));
-  WIS_HIP_CHECK(hipGetLastError());
-  WIS_HIP_CHECK(hipStreamSynchronize(ctx_stream(c)));
-  return WIS_OK;
+  Tap t(device, "wis_op_layernorm"); WIS_RET(t.rc);
+  return t.finish(launch_layernorm(t.st, x, gamma, beta, reinterpret_cast<f16*>(y), M, d));
 }
 int wis_op_enc_attention(int device, const void* qk, const void* vt, void* out, int B, int T, int Tpad, int H) {
-  DeviceCtx* c; WIS_RET(get_ctx(device, &c));
-  std::lock_guard<std::mutex> op_lock(ctx_op_mutex(c));
+  Tap t(device, "wis_op_enc_attention"); WIS_RET(t.rc);
   // same rule as the encoder: the split-key form (two workgroups per query tile and head, in-launch merge) at small grids
-  hipStream_t st = ctx_stream(c);
   float* part = nullptr; unsigned* counters = nullptr;
   const size_t ncnt = (size_t)B * H * cdiv(T, 128);
-  int rc = WIS_OK;
-  if (hipMalloc(reinterpret_cast<void**>(&part), enc_attention_part_floats(B, T, H) * 4) != hipSuccess ||
-      hipMalloc(reinterpret_cast<void**>(&counters), ncnt * 4) != hipSuccess) { set_error("wis_op_enc_attention: out of device memory"); rc = WIS_E_NOMEM; }
+  WIS_RET(t.get(&part, enc_attention_part_floats(B, T, H))); WIS_RET(t.get(&counters, ncnt, true));
   f16* qk2 = nullptr;      // the lazy-reference loop wants log2(e) on Q as well (the engine folds it into the projection): a scaled private copy
-  if (!rc && enc_attn_lazy()) {
+  if (enc_attn_lazy()) {
     const size_t n = (size_t)B * T * 2 * H * 64;
-    if (hipMalloc(reinterpret_cast<void**>(&qk2), n * 2) != hipSuccess) { set_error("wis_op_enc_attention: out of device memory"); rc = WIS_E_NOMEM; }
-    else {
-      hipMemcpyAsync(qk2, qk, n * 2, hipMemcpyDeviceToDevice, st);
-      launch_scale_q_log2e(st, qk2, (int64_t)B * T, H * 64);
-    }
+    WIS_RET(t.get(&qk2, n));
+    hipMemcpyAsync(qk2, qk, n * 2, hipMemcpyDeviceToDevice, t.st);
+    launch_scale_q_log2e(t.st, qk2, (int64_t)B * T, H * 64);
   }
-  if (!rc) {
-    hipMemsetAsync(counters, 0, ncnt * 4, st);
-    rc = launch_enc_attention(st, qk2 ? qk2 : reinterpret_cast<const f16*>(qk), reinterpret_cast<const f16*>(vt), reinterpret_cast<f16*>(out), B, T, Tpad, H, part, counters, ncnt);
-  }
-  hipError_t e = hipStreamSynchronize(st);
-  hipFree(part); hipFree(counters); hipFree(qk2);
-  if (rc) return rc;
-  if (e != hipSuccess) { set_error("wis_op_enc_attention: %s", hipGetErrorString(e)); return WIS_E_HIP; }
-  return WIS_OK;
+  return t.finish(launch_enc_attention(t.st, qk2 ? qk2 : reinterpret_cast<const f16*>(qk), reinterpret_cast<const f16*>(vt), reinterpret_cast<f16*>(out), B, T, Tpad, H, part, counters, ncnt));
 }
 int wis_op_enc_attention_ex(int device, const void* qk, const void* vt, void* out, int B, int T, int Tpad, int H, int form) {
-  DeviceCtx* c; WIS_RET(get_ctx(device, &c));
-  std::lock_guard<std::mutex> op_lock(ctx_op_mutex(c));
+  Tap t(device, "wis_op_enc_attention_ex"); WIS_RET(t.rc);
   if (form & ~3) { set_error("wis_op_enc_attention_ex: form=%d (bit 0: lazy loop, bit 1: split-key pair)", form); return WIS_E_ARG; }
   const bool lazy = form & 1, split = form & 2;
   if (B < 1 || T < 1 || H < 1) { set_error("wis_op_enc_attention_ex: B=%d T=%d H=%d", B, T, H); return WIS_E_ARG; }
   if (split && cdiv(T, 64) < 4) { set_error("wis_op_enc_attention_ex: the split-key pair needs at least four key tiles (T=%d)", T); return WIS_E_ARG; }
   // Q is read as given (the lazy loop's log2(e) / 8 is the caller's, as the engine's query projection delivers it): no scaled copy
-  hipStream_t st = ctx_stream(c);
   float* part = nullptr; unsigned* counters = nullptr;
-  const size_t ncnt = (size_t)B * H * cdiv(T, 128);
-  int rc = WIS_OK;
-  if (split) {
-    if (hipMalloc(reinterpret_cast<void**>(&part), enc_attention_part_floats(B, T, H) * 4) != hipSuccess ||
-        hipMalloc(reinterpret_cast<void**>(&counters), ncnt * 4) != hipSuccess) { set_error("wis_op_enc_attention_ex: out of device memory"); rc = WIS_E_NOMEM; }
-    else hipMemsetAsync(counters, 0, ncnt * 4, st);
-  }
-  if (!rc) rc = launch_enc_attention_form(st, reinterpret_cast<const f16*>(qk), reinterpret_cast<const f16*>(vt), reinterpret_cast<f16*>(out), B, T, Tpad, H, part, counters, lazy, split);
-  hipError_t e = hipStreamSynchronize(st);
-  hipFree(part); hipFree(counters);
-  if (rc) return rc;
-  if (e != hipSuccess) { set_error("wis_op_enc_attention_ex: %s", hipGetErrorString(e)); return WIS_E_HIP; }
-  return WIS_OK;
+  if (split) { WIS_RET(t.get(&part, enc_attention_part_floats(B, T, H))); WIS_RET(t.get(&counters, (size_t)B * H * cdiv(T, 128), true)); }
+  return t.finish(launch_enc_attention_form(t.st, reinterpret_cast<const f16*>(qk), reinterpret_cast<const f16*>(vt), reinterpret_cast<f16*>(out), B, T, Tpad, H, part, counters, lazy, split));
 }
 int wis_op_gemv(int device, const void* x, const float* gamma, const float* beta, const void* W, const float* bias, void* y, int M, int N, int K, int flags) {
-  DeviceCtx* c; WIS_RET(get_ctx(device, &c));
-  std::lock_guard<std::mutex> op_lock(ctx_op_mutex(c));
-  hipStream_t st = ctx_stream(c);
+  Tap t(device, "wis_op_gemv"); WIS_RET(t.rc);
+  hipStream_t st = t.st;
   if (flags & GV_QKV) { set_error("wis_op_gemv: flag 16 is internal"); return WIS_E_ARG; }
-  const int Npad = cdiv(N, gemv_rows_for(N, K)) * gemv_rows_for(N, K);
+  const int rows = gemv_rows_for(N, K), Npad = cdiv(N, rows) * rows;
   // (tap flags: 32 = quantise the matrix to 8 bits per weight first; 64 = GV_LN16: x is the F16 copy of the rows, LayerNorm folded)
   const bool w8 = flags & 32, ln16 = (flags & GV_LN16) != 0, ln = (flags & GV_LN) || ln16;
   flags &= ~32;
@@ -378,136 +366,87 @@ int wis_op_gemv(int device, const void* x, const float* gamma, const float* beta
   if (ln && (!gamma || !beta)) { set_error("wis_op_gemv: flags 8 / 64 need gamma and beta"); return WIS_E_ARG; }
   // the same preparation the model loader does: optional LayerNorm fold into a private copy of W / bias, then packing
   f16 *wp = nullptr, *wtmp = nullptr, *xfr = nullptr; float *wsc = nullptr, *b2 = nullptr, *cs = nullptr, *stt = nullptr;
-  int rc = WIS_OK;
-  do {
-    if (hipMalloc(reinterpret_cast<void**>(&wp), (size_t)Npad * K * 2) != hipSuccess || hipMalloc(reinterpret_cast<void**>(&wtmp), (size_t)N * K * 2) != hipSuccess ||
-        hipMalloc(reinterpret_cast<void**>(&b2), (size_t)Npad * 4) != hipSuccess || hipMalloc(reinterpret_cast<void**>(&cs), (size_t)Npad * 4) != hipSuccess ||
-        (w8 && hipMalloc(reinterpret_cast<void**>(&wsc), (size_t)Npad * 4) != hipSuccess)) { set_error("wis_op_gemv: out of device memory"); rc = WIS_E_NOMEM; break; }
-    hipMemcpyAsync(wtmp, W, (size_t)N * K * 2, hipMemcpyDeviceToDevice, st);
-    hipMemsetAsync(b2, 0, (size_t)Npad * 4, st); hipMemsetAsync(cs, 0, (size_t)Npad * 4, st);
-    if (bias) hipMemcpyAsync(b2, bias, (size_t)N * 4, hipMemcpyDeviceToDevice, st);
-    const int rows = gemv_rows_for(N, K);
-    if ((rc = prep_projection(st, wtmp, N, Npad, K, 0, 1.f, ln ? gamma : nullptr, beta, b2, cs, wp, wsc, rows))) break;      // (wsc: allocated for the 8-bit form only)
-    GemvP g; memset(&g, 0, sizeof(g));
-    g.x = x; g.csum = ln ? cs : nullptr; g.Wp = wp; g.wscale = wsc; g.bias = (bias || ln) ? b2 : nullptr; g.y = y; g.M = M; g.N = N; g.K = K; g.flags = flags; g.rows = rows;
-    if (M > 8) {
-      // the product's batched route (dec_forward_frag): activations as a fragment image, LayerNorm statistics as row partials
-      const int MBf = cdiv(M, 16);
-      if (hipMalloc(reinterpret_cast<void**>(&xfr), (size_t)(K / 32) * MBf * 64 * 8 * 2) != hipSuccess ||
-          (ln && hipMalloc(reinterpret_cast<void**>(&stt), (size_t)M * (K / 16) * 2 * 4) != hipSuccess)) { set_error("wis_op_gemv: out of device memory"); rc = WIS_E_NOMEM; break; }
-      hipMemsetAsync(xfr, 0, (size_t)(K / 32) * MBf * 64 * 8 * 2, st);
-      if ((rc = launch_xf_pack(st, x, ln ? 0 : 1, xfr, ln ? stt : nullptr, M, K, MBf))) break;
-      g.x = xfr; g.xmb = MBf; g.stat_in = stt;
-      float* kp = nullptr; unsigned* kc = nullptr;
-      if (!ln && K >= 4096 && (K / 32) % 16 == 0) {      // the product's rule for the K = 4d projection: four K slices per n-tile, merged in the launch
-        const size_t nt = (size_t)cdiv(N, 16);
-        if (hipMalloc(reinterpret_cast<void**>(&kp), nt * 4 * MBf * 64 * 16) != hipSuccess || hipMalloc(reinterpret_cast<void**>(&kc), nt * 4) != hipSuccess) {
-          hipFree(kp); set_error("wis_op_gemv: out of device memory"); rc = WIS_E_NOMEM; break; }
-        hipMemsetAsync(kc, 0, nt * 4, st);
-        g.ksplit = 4; g.kpart = kp; g.kcnt = kc;
-        if (!(flags & GV_RESID)) rc = launch_gemv_frag(st, g);      // a first launch on the same tickets: they must re-arm themselves
-      }
-      if (!rc) rc = launch_gemv_frag(st, g);
-      hipStreamSynchronize(st);
-      hipFree(kp); hipFree(kc);
-      break;
-    }
-    rc = launch_gemv(st, g);
-  } while (0);
-  hipError_t e = hipStreamSynchronize(st);
-  hipFree(wp); hipFree(wtmp); hipFree(b2); hipFree(cs); hipFree(wsc); hipFree(xfr); hipFree(stt);
-  if (rc) return rc;
-  if (e != hipSuccess) { set_error("wis_op_gemv: %s", hipGetErrorString(e)); return WIS_E_HIP; }
-  return WIS_OK;
+  WIS_RET(t.get(&wp, (size_t)Npad * K)); WIS_RET(t.get(&wtmp, (size_t)N * K)); WIS_RET(t.get(&b2, (size_t)Npad, true)); WIS_RET(t.get(&cs, (size_t)Npad, true));
+  if (w8) WIS_RET(t.get(&wsc, (size_t)Npad));      // (allocated for the 8-bit form only)
+  hipMemcpyAsync(wtmp, W, (size_t)N * K * 2, hipMemcpyDeviceToDevice, st);
+  if (bias) hipMemcpyAsync(b2, bias, (size_t)N * 4, hipMemcpyDeviceToDevice, st);
+  WIS_RET(prep_projection(st, wtmp, N, Npad, K, 0, 1.f, ln ? gamma : nullptr, beta, b2, cs, wp, wsc, rows));
+  GemvP g; memset(&g, 0, sizeof(g));
+  g.x = x; g.csum = ln ? cs : nullptr; g.Wp = wp; g.wscale = wsc; g.bias = (bias || ln) ? b2 : nullptr; g.y = y; g.M = M; g.N = N; g.K = K; g.flags = flags; g.rows = rows;
+  if (M <= 8) return t.finish(launch_gemv(st, g));
+  // the product's batched route (dec_forward_frag): activations as a fragment image, LayerNorm statistics as row partials
+  const int MBf = cdiv(M, 16);
+  WIS_RET(t.get(&xfr, xf_elems(K, MBf), true));
+  if (ln) WIS_RET(t.get(&stt, (size_t)M * (K / 16) * 2));
+  WIS_RET(launch_xf_pack(st, x, ln ? 0 : 1, xfr, ln ? stt : nullptr, M, K, MBf));
+  g.x = xfr; g.xmb = MBf; g.stat_in = stt;
+  if (!ln && K >= 4096 && (K / 32) % 16 == 0) {      // the product's rule for the K = 4d projection: four K slices per n-tile, merged in the launch
+    const size_t nt = (size_t)cdiv(N, 16);
+    WIS_RET(t.get(&g.kpart, nt * 4 * MBf * 64 * 4)); WIS_RET(t.get(&g.kcnt, nt, true));
+    g.ksplit = 4;
+    if (!(flags & GV_RESID)) WIS_RET(launch_gemv_frag(st, g));      // a first launch on the same tickets: they must re-arm themselves
+  }
+  return t.finish(launch_gemv_frag(st, g));
 }
 
 // The single-chunk f16-activation form of launch_gemv (the one-utterance FFN2 and cross-attention out-projection: K = 5120 / 1280) on sixteen-column
 // tiles (cols = 16: the fragment image) or eight-column tiles (cols = 8: launch_pack_gemv_nc8's image) of the same row-major W [N][K].  flags: GV_RESID
 // (y fp32 [M][N] in place, y16 an optional f16 copy), GV_OUT_F32, GV_GELU or none (y f16).  Nothing but the M x N outputs is written.
 int wis_op_gemv_cols(int device, const void* x, const void* W, const float* bias, void* y, void* y16, int M, int N, int K, int flags, int cols) {
-  DeviceCtx* c; WIS_RET(get_ctx(device, &c));
-  std::lock_guard<std::mutex> op_lock(ctx_op_mutex(c));
-  hipStream_t st = ctx_stream(c);
+  Tap t(device, "wis_op_gemv_cols"); WIS_RET(t.rc);
   if (!x || !W || !y || (cols != 8 && cols != 16) || N < 1 || N % cols || (flags & ~(GV_RESID | GV_OUT_F32 | GV_GELU)) || (y16 && !(flags & GV_RESID))) { set_error("wis_op_gemv_cols: bad argument"); return WIS_E_ARG; }
   if (!gemv_nc8_shape(M, N, K)) { set_error("wis_op_gemv_cols: M=%d N=%d K=%d is not a shape of the eight-column form", M, N, K); return WIS_E_UNSUPPORTED; }
   f16* wp = nullptr;
-  if (hipMalloc(reinterpret_cast<void**>(&wp), (size_t)N * K * 2) != hipSuccess) { set_error("wis_op_gemv_cols: out of device memory"); return WIS_E_NOMEM; }
-  int rc = cols == 8 ? launch_pack_gemv_nc8(st, reinterpret_cast<const f16*>(W), wp, N, N, K) : launch_pack_gemv(st, reinterpret_cast<const f16*>(W), wp, N, N, K, 0, 1.f, 16);
-  if (!rc) {
-    GemvP g; memset(&g, 0, sizeof(g));
-    g.x = x; g.Wp = wp; g.bias = bias; g.y = y; g.y16 = reinterpret_cast<f16*>(y16); g.M = M; g.N = N; g.K = K; g.flags = flags; g.rows = cols;
-    rc = launch_gemv(st, g);
-  }
-  hipError_t e = hipStreamSynchronize(st);
-  hipFree(wp);
-  if (rc) return rc;
-  if (e != hipSuccess) { set_error("wis_op_gemv_cols: %s", hipGetErrorString(e)); return WIS_E_HIP; }
-  return WIS_OK;
+  WIS_RET(t.get(&wp, (size_t)N * K));
+  WIS_RET(cols == 8 ? launch_pack_gemv_nc8(t.st, reinterpret_cast<const f16*>(W), wp, N, N, K) : launch_pack_gemv(t.st, reinterpret_cast<const f16*>(W), wp, N, N, K, 0, 1.f, 16));
+  GemvP g; memset(&g, 0, sizeof(g));
+  g.x = x; g.Wp = wp; g.bias = bias; g.y = y; g.y16 = reinterpret_cast<f16*>(y16); g.M = M; g.N = N; g.K = K; g.flags = flags; g.rows = cols;
+  return t.finish(launch_gemv(t.st, g));
 }
 
-int wis_op_dec_self_attn(int device, const float* q, const void* kc, const void* vc, const int32_t* pos, void* out,
-                         int M, int H, int ctx, int rpu, int sstride, int rmul) {
-  DeviceCtx* c; WIS_RET(get_ctx(device, &c));
-  std::lock_guard<std::mutex> op_lock(ctx_op_mutex(c));
-  if (!q || !kc || !vc || !pos || !out || M < 1 || H < 1 || rpu < 1) { set_error("wis_op_dec_self_attn: bad argument"); return WIS_E_ARG; }
+// wis_op_dec_self_attn is the nb = 8, row-major, no-tree case of wis_op_dec_self_attn_ex; `who` is the entry point the caller used
+static int op_dec_self_attn(const char* who, int device, const float* q, const void* kc, const void* vc, const int32_t* pos, void* out,
+                            int M, int H, int ctx, int rpu, int sstride, int rmul, int nb, int out_mb, const int32_t* anc, int w0, int aw, const int32_t* base) {
+  Tap t(device, who); WIS_RET(t.rc);
+  if (!q || !kc || !vc || !pos || !out || M < 1 || H < 1 || rpu < 1 || (nb != 2 && nb != 4 && nb != 8) || (out_mb && out_mb < cdiv(M, 16)) || (base && !anc)) {
+    set_error("%s: bad argument", who); return WIS_E_ARG; }
+  const int d = 64 * H;
+  if (out_mb) WIS_HIP_CHECK(hipMemsetAsync(out, 0, xf_elems(d, out_mb) * 2, t.st));      // the fragment image's rows beyond M stay zero
   SelfAttnP sa;
   sa.q = q; sa.kc = reinterpret_cast<const f16*>(kc); sa.vc = reinterpret_cast<const f16*>(vc); sa.pos = pos; sa.out = reinterpret_cast<f16*>(out);
-  sa.M = M; sa.H = H; sa.d = 64 * H; sa.ctx = ctx; sa.rpu = rpu; sa.sstride = sstride; sa.rmul = rmul;
-  WIS_RET(launch_dec_self_attn(ctx_stream(c), sa));
-  WIS_HIP_CHECK(hipGetLastError());
-  WIS_HIP_CHECK(hipStreamSynchronize(ctx_stream(c)));
-  return WIS_OK;
+  sa.M = M; sa.H = H; sa.d = d; sa.ctx = ctx; sa.rpu = rpu; sa.sstride = sstride; sa.rmul = rmul; sa.out_mb = out_mb; sa.anc = anc; sa.w0 = w0; sa.aw = aw; sa.base = base; sa.nb = nb;
+  return t.finish(launch_dec_self_attn(t.st, sa));
+}
+int wis_op_dec_self_attn(int device, const float* q, const void* kc, const void* vc, const int32_t* pos, void* out,
+                         int M, int H, int ctx, int rpu, int sstride, int rmul) {
+  return op_dec_self_attn("wis_op_dec_self_attn", device, q, kc, vc, pos, out, M, H, ctx, rpu, sstride, rmul, 8, 0, nullptr, 0, 0, nullptr);
 }
 int wis_op_dec_self_attn_ex(int device, const float* q, const void* kc, const void* vc, const int32_t* pos, void* out,
                             int M, int H, int ctx, int rpu, int sstride, int rmul, int nb, int out_mb,
                             const int32_t* anc, int w0, int aw, const int32_t* base) {
-  DeviceCtx* c; WIS_RET(get_ctx(device, &c));
-  std::lock_guard<std::mutex> op_lock(ctx_op_mutex(c));
-  if (!q || !kc || !vc || !pos || !out || M < 1 || H < 1 || rpu < 1 || (nb != 2 && nb != 4 && nb != 8) || (out_mb && out_mb < cdiv(M, 16)) || (base && !anc)) {
-    set_error("wis_op_dec_self_attn_ex: bad argument"); return WIS_E_ARG; }
-  hipStream_t st = ctx_stream(c);
-  const int d = 64 * H;
-  if (out_mb) WIS_HIP_CHECK(hipMemsetAsync(out, 0, (size_t)(d / 32) * out_mb * 64 * 8 * 2, st));      // the fragment image's rows beyond M stay zero
-  SelfAttnP sa;
-  sa.q = q; sa.kc = reinterpret_cast<const f16*>(kc); sa.vc = reinterpret_cast<const f16*>(vc); sa.pos = pos; sa.out = reinterpret_cast<f16*>(out);
-  sa.M = M; sa.H = H; sa.d = d; sa.ctx = ctx; sa.rpu = rpu; sa.sstride = sstride; sa.rmul = rmul; sa.out_mb = out_mb; sa.anc = anc; sa.w0 = w0; sa.aw = aw; sa.base = base; sa.nb = nb;
-  WIS_RET(launch_dec_self_attn(st, sa));
-  WIS_HIP_CHECK(hipGetLastError());
-  WIS_HIP_CHECK(hipStreamSynchronize(st));
-  return WIS_OK;
+  return op_dec_self_attn("wis_op_dec_self_attn_ex", device, q, kc, vc, pos, out, M, H, ctx, rpu, sstride, rmul, nb, out_mb, anc, w0, aw, base);
 }
 static int op_dec_cross_attn(int device, const float* q, const float* xres, const float* qcs, const float* qb, const void* kx, const void* vt, void* out,
                              int B, int R, int H, int T, int chunks, const float* q2 = nullptr, int xres_is_stat = 0, int out_mb = 0, int kv_shared = 0, bool no_spin = false) {
-  DeviceCtx* c; WIS_RET(get_ctx(device, &c));
-  std::lock_guard<std::mutex> op_lock(ctx_op_mutex(c));
+  Tap t(device, "wis_op_dec_cross_attn"); WIS_RET(t.rc);
   if (!q || !kx || !vt || !out || B < 1 || H < 1 || T < 1) { set_error("wis_op_dec_cross_attn: bad argument"); return WIS_E_ARG; }
-  hipStream_t st = ctx_stream(c);
-  float* part = nullptr; unsigned* counters = nullptr; unsigned long long* gran = nullptr; unsigned* epoch = nullptr;
-  int rc = WIS_OK;
   if (out_mb && out_mb < cdiv(B * R, 16)) { set_error("wis_op_dec_cross_attn: %d row blocks for %d rows", out_mb, B * R); return WIS_E_ARG; }
+  hipStream_t st = t.st;
   const bool small = B * H <= CA_SPIN_MAX_BH && !no_spin;      // the product's rule: the granule hand-off on small grids (launch_dec_cross_attn decides by chunking / rows)
-  if (hipMalloc(reinterpret_cast<void**>(&part), (size_t)B * H * 16 * 16 * 66 * 4) != hipSuccess ||
-      hipMalloc(reinterpret_cast<void**>(&counters), (size_t)B * H * 4) != hipSuccess ||
-      (small && (hipMalloc(reinterpret_cast<void**>(&gran), (size_t)B * H * 6 * 8 * 66 * 8) != hipSuccess || hipMalloc(reinterpret_cast<void**>(&epoch), ((size_t)B * H + 1) * 4) != hipSuccess))) {
-    set_error("wis_op_dec_cross_attn: out of device memory"); rc = WIS_E_NOMEM; }
+  CrossAttnP ca;
+  WIS_RET(t.get(&ca.part, (size_t)B * H * 16 * 16 * 66)); WIS_RET(t.get(&ca.counters, (size_t)B * H, true));
+  if (small) { WIS_RET(t.get(&ca.gran, (size_t)B * H * 6 * 8 * 66, true)); WIS_RET(t.get(&ca.epoch, (size_t)B * H + 1, true)); }
+  if (out_mb) hipMemsetAsync(out, 0, xf_elems(64 * H, out_mb) * 2, st);      // the fragment image's rows beyond B * R stay zero
+  ca.q = q; ca.kx = reinterpret_cast<const f16*>(kx); ca.vt = reinterpret_cast<const f16*>(vt); ca.out = reinterpret_cast<f16*>(out);
+  ca.B = B; ca.R = R; ca.H = H; ca.d = 64 * H; ca.T = T; ca.Tpad = cdiv(T, 64) * 64; ca.chunks = chunks; ca.out_mb = out_mb; ca.xres = xres; ca.qcs = qcs; ca.qb = qb;
+  ca.q2 = q2; ca.xres_is_stat = xres_is_stat; ca.kv_shared = kv_shared;
+  int rc = WIS_OK;
+  for (int rep = 0; rep < 3 && !rc; ++rep) rc = launch_dec_cross_attn(st, ca);      // three launches: the epochs of the granule form advance from launch to launch
   unsigned flag = 0;
-  if (!rc) {
-    hipMemsetAsync(counters, 0, (size_t)B * H * 4, st);
-    if (small) { hipMemsetAsync(gran, 0, (size_t)B * H * 6 * 8 * 66 * 8, st); hipMemsetAsync(epoch, 0, ((size_t)B * H + 1) * 4, st); }
-    if (out_mb) hipMemsetAsync(out, 0, (size_t)(64 * H / 32) * out_mb * 64 * 8 * 2, st);      // the fragment image's rows beyond B * R stay zero
-    CrossAttnP ca;
-    ca.q = q; ca.kx = reinterpret_cast<const f16*>(kx); ca.vt = reinterpret_cast<const f16*>(vt); ca.out = reinterpret_cast<f16*>(out); ca.part = part; ca.counters = counters;
-    ca.B = B; ca.R = R; ca.H = H; ca.d = 64 * H; ca.T = T; ca.Tpad = cdiv(T, 64) * 64; ca.chunks = chunks; ca.out_mb = out_mb; ca.xres = xres; ca.qcs = qcs; ca.qb = qb;
-    ca.gran = gran; ca.epoch = epoch; ca.q2 = q2; ca.xres_is_stat = xres_is_stat; ca.kv_shared = kv_shared;
-    for (int rep = 0; rep < 3 && !rc; ++rep) rc = launch_dec_cross_attn(st, ca);      // three launches: the epochs of the granule form advance from launch to launch
-    if (small && !rc) hipMemcpyAsync(&flag, epoch, 4, hipMemcpyDeviceToHost, st);
-  }
-  hipError_t e = hipStreamSynchronize(st);
-  hipFree(part); hipFree(counters); hipFree(gran); hipFree(epoch);
-  if (rc) return rc;
-  if (flag) { set_error("wis_op_dec_cross_attn: granule hand-off timed out"); return WIS_E_HIP; }
-  if (e != hipSuccess) { set_error("wis_op_dec_cross_attn: %s", hipGetErrorString(e)); return WIS_E_HIP; }
-  return WIS_OK;
+  if (small && !rc) hipMemcpyAsync(&flag, ca.epoch, 4, hipMemcpyDeviceToHost, st);
+  const int verdict = t.finish(rc);      // (synchronises: flag has arrived)
+  if (!rc && flag) { set_error("wis_op_dec_cross_attn: granule hand-off timed out"); return WIS_E_HIP; }
+  return verdict;
 }
 int wis_op_dec_cross_attn(int device, const float* q, const void* kx, const void* vt, void* out, int B, int R, int H, int T, int chunks) {
   return op_dec_cross_attn(device, q, nullptr, nullptr, nullptr, kx, vt, out, B, R, H, T, chunks);
@@ -523,243 +462,168 @@ int wis_op_dec_cross_attn_stat(int device, const float* q, const float* q2, cons
   return op_dec_cross_attn(device, q, stat, qcs, qb, kx, vt, out, B, R, H, T, chunks, q2, stat ? 1 : 0, out_mb, kv_shared, no_spin != 0);
 }
 
-}  // extern "C"
-
-// private device scratch of a tap: freed when the tap returns
-namespace {
-struct TapScratch {
-  std::vector<void*> ptrs;
-  template <class T> bool get(T** p, size_t n_elems) {
-    void* q = nullptr;
-    if (hipMalloc(&q, n_elems * sizeof(T) ? n_elems * sizeof(T) : 16) != hipSuccess) return false;
-    ptrs.push_back(q); *p = reinterpret_cast<T*>(q); return true;
-  }
-  ~TapScratch() { for (void* q : ptrs) hipFree(q); }
-};
-}  // namespace
-
-extern "C" {
-
 int wis_op_gemv_qkv(int device, const float* x, const float* gamma, const float* beta, const void* W, const float* bias, const int32_t* slot, const int32_t* pos,
                     float* q, void* kc, void* vc, int M, int d, int ctx) {
-  DeviceCtx* c; WIS_RET(get_ctx(device, &c));
-  std::lock_guard<std::mutex> op_lock(ctx_op_mutex(c));
+  Tap t(device, "wis_op_gemv_qkv"); WIS_RET(t.rc);
   if (!x || !gamma || !beta || !W || !bias || !slot || !pos || !q || !kc || !vc || M < 1 || M > MAX_ROWS || d < 128 || d % 128 || ctx < 1) { set_error("wis_op_gemv_qkv: bad argument"); return WIS_E_ARG; }
-  hipStream_t st = ctx_stream(c);
+  hipStream_t st = t.st;
   const int N = 3 * d, MB = cdiv(M, 16);
   const float qs = 0.125f;
-  TapScratch ts;
   f16 *wp = nullptr, *wtmp = nullptr, *xf = nullptr; float *b2 = nullptr, *cs = nullptr, *stt = nullptr;
-  if (!ts.get(&wp, (size_t)N * d) || !ts.get(&wtmp, (size_t)N * d) || !ts.get(&b2, (size_t)N) || !ts.get(&cs, (size_t)N) ||
-      (M > 8 && (!ts.get(&xf, (size_t)(d / 32) * MB * 64 * 8) || !ts.get(&stt, (size_t)M * (d / 16) * 2)))) { set_error("wis_op_gemv_qkv: out of device memory"); return WIS_E_NOMEM; }
-  int rc = WIS_OK;
-  do {
-    // what load_weights does for a layer's DecProj `qkv` (w.qkv): the bias's query part scaled, the LayerNorm folded, the query rows scaled by the packer
-    hipMemcpyAsync(wtmp, W, (size_t)N * d * 2, hipMemcpyDeviceToDevice, st);
-    hipLaunchKernelGGL(convert_kernel, dim3(blocks_for(N)), dim3(256), 0, st, bias, 0, b2, 0, (int64_t)N, (int64_t)1, (int64_t)1, (int64_t)d, qs);
-    hipMemsetAsync(cs, 0, (size_t)N * 4, st);
-    const DecProj qkv{wp, nullptr, b2, cs, N, d, gemv_rows_for(N, d)};
-    if ((rc = prep_projection(st, wtmp, N, N, d, d, qs, gamma, beta, b2, cs, wp, nullptr, qkv.rows))) break;
-    GemvP g;
-    if (M <= 8) g = gemv_small(qkv, x, nullptr, M, GV_LN | GV_QKV);      // dec_forward
-    else {
-      // dec_forward_frag: the rows as a fragment image, their LayerNorm statistics as row partials
-      hipMemsetAsync(xf, 0, (size_t)(d / 32) * MB * 64 * 8 * 2, st);
-      if ((rc = launch_xf_pack(st, x, 0, xf, stt, M, d, MB))) break;
-      g = gemv_frag(qkv, xf, M, GV_LN | GV_QKV);
-      g.stat_in = stt;
-    }
-    g.q = q; g.kc = reinterpret_cast<f16*>(kc); g.vc = reinterpret_cast<f16*>(vc); g.slot = slot; g.pos = pos; g.d = d; g.ctx = ctx;
-    rc = M <= 8 ? launch_gemv(st, g) : launch_gemv_frag(st, g);
-  } while (0);
-  hipError_t e = hipStreamSynchronize(st);
-  if (rc) return rc;
-  if (e != hipSuccess) { set_error("wis_op_gemv_qkv: %s", hipGetErrorString(e)); return WIS_E_HIP; }
-  return WIS_OK;
+  WIS_RET(t.get(&wp, (size_t)N * d)); WIS_RET(t.get(&wtmp, (size_t)N * d)); WIS_RET(t.get(&b2, (size_t)N)); WIS_RET(t.get(&cs, (size_t)N, true));
+  if (M > 8) { WIS_RET(t.get(&xf, xf_elems(d, MB), true)); WIS_RET(t.get(&stt, (size_t)M * (d / 16) * 2)); }
+  // what load_weights does for a layer's DecProj `qkv` (w.qkv): the bias's query part scaled, the LayerNorm folded, the query rows scaled by the packer
+  hipMemcpyAsync(wtmp, W, (size_t)N * d * 2, hipMemcpyDeviceToDevice, st);
+  hipLaunchKernelGGL(convert_kernel, dim3(blocks_for(N)), dim3(256), 0, st, bias, 0, b2, 0, (int64_t)N, (int64_t)1, (int64_t)1, (int64_t)d, qs);
+  const DecProj qkv{wp, nullptr, b2, cs, N, d, gemv_rows_for(N, d)};
+  WIS_RET(prep_projection(st, wtmp, N, N, d, d, qs, gamma, beta, b2, cs, wp, nullptr, qkv.rows));
+  GemvP g;
+  if (M <= 8) g = gemv_small(qkv, x, nullptr, M, GV_LN | GV_QKV);      // dec_forward
+  else {
+    // dec_forward_frag: the rows as a fragment image, their LayerNorm statistics as row partials
+    WIS_RET(launch_xf_pack(st, x, 0, xf, stt, M, d, MB));
+    g = gemv_frag(qkv, xf, M, GV_LN | GV_QKV);
+    g.stat_in = stt;
+  }
+  g.q = q; g.kc = reinterpret_cast<f16*>(kc); g.vc = reinterpret_cast<f16*>(vc); g.slot = slot; g.pos = pos; g.d = d; g.ctx = ctx;
+  return t.finish(M <= 8 ? launch_gemv(st, g) : launch_gemv_frag(st, g));
 }
 
 int wis_op_gemv_out_cq(int device, const void* a, const float* x0, const void* Wo, const float* bo, const void* Wq, const float* bq, const float* gamma, const float* beta,
                        float* x1, float* stat, float* q, float* q2, float* qcs, float* qb, int M, int d, int force_frag) {
-  DeviceCtx* c; WIS_RET(get_ctx(device, &c));
-  std::lock_guard<std::mutex> op_lock(ctx_op_mutex(c));
+  Tap t(device, "wis_op_gemv_out_cq"); WIS_RET(t.rc);
   const bool frag = M > 8 || force_frag;
   if (!a || !x0 || !Wo || !bo || !Wq || !bq || !gamma || !beta || !x1 || !stat || !q || !qcs || !qb || (frag && !q2) || M < 1 || M > MAX_ROWS || d < 128 || d % 128) {
     set_error("wis_op_gemv_out_cq: bad argument"); return WIS_E_ARG; }
-  hipStream_t st = ctx_stream(c);
+  hipStream_t st = t.st;
   const int MB = cdiv(M, 16);
   const float qs = 0.125f;
-  const size_t img = (size_t)(d / 32) * MB * 64 * 8;
-  TapScratch ts;
   f16 *wtmp = nullptr, *fcat = nullptr, *fwot = nullptr, *fwqo = nullptr, *p_cqo = nullptr, *p_out = nullptr, *xh = nullptr, *xf = nullptr, *af = nullptr; float* b_cqo = nullptr;
-  if (!ts.get(&wtmp, (size_t)d * d) || !ts.get(&fcat, (size_t)2 * d * d) || !ts.get(&fwot, (size_t)d * d) || !ts.get(&fwqo, (size_t)d * d) || !ts.get(&p_cqo, (size_t)2 * d * d) ||
-      !ts.get(&p_out, (size_t)d * d) || !ts.get(&b_cqo, (size_t)d) || (frag ? (!ts.get(&xf, img) || !ts.get(&af, img)) : !ts.get(&xh, (size_t)M * d))) {
-    set_error("wis_op_gemv_out_cq: out of device memory"); return WIS_E_NOMEM; }
-  int rc = WIS_OK;
-  do {
-    // load_weights, decoder layer: cq (the cross-Q bias scaled, the LayerNorm folded: bias / csum are what the cross-attention kernel takes as qb / qcs), out, then the fold
-    hipMemcpyAsync(wtmp, Wq, (size_t)d * d * 2, hipMemcpyDeviceToDevice, st);
-    hipLaunchKernelGGL(convert_kernel, dim3(blocks_for(d)), dim3(256), 0, st, bq, 0, qb, 0, (int64_t)d, (int64_t)1, (int64_t)1, (int64_t)d, qs);
-    hipMemsetAsync(qcs, 0, (size_t)d * 4, st);
-    DecLayerW w{};
-    w.out = DecProj{p_out, nullptr, bo, nullptr, d, d, gemv_rows_for(d, d)};
-    w.cqo = DecProj{p_cqo, nullptr, b_cqo, nullptr, d, 2 * d, 16};
-    if ((rc = prep_projection(st, wtmp, d, d, d, d, qs, gamma, beta, qb, qcs, nullptr, nullptr, 16))) break;      // (the fold alone: the stage streams w.out and w.cqo)
-    if ((rc = launch_pack_gemv(st, reinterpret_cast<const f16*>(Wo), p_out, d, d, d, 0, 1.f, w.out.rows))) break;
-    if ((rc = build_cq_fold(st, wtmp, Wo, 1, bo, d, qs, fcat, fwot, fwqo, p_cqo, b_cqo))) break;
-    hipMemcpyAsync(x1, x0, (size_t)M * d * 4, hipMemcpyDeviceToDevice, st);      // the residual epilogue works in place
-    if (!frag) {
-      // dec_forward: one dual launch on the f16 rows (the attention output; the f16 copy of the layer input that the embedding / FFN2 epilogues leave)
-      hipLaunchKernelGGL(convert_kernel, dim3(blocks_for((int64_t)M * d)), dim3(256), 0, st, x0, 0, xh, 1, (int64_t)M, (int64_t)d, (int64_t)d, (int64_t)0, 1.f);
-      GemvP ga, gb;
-      out_cq_dual(w, reinterpret_cast<const f16*>(a), xh, x1, stat, q, M, &ga, &gb);
-      rc = launch_gemv_dual(st, ga, gb);
-      break;
-    }
-    // dec_forward_frag: three d x d problems on the fragment images of the layer input and the attention output
-    hipMemsetAsync(xf, 0, img * 2, st); hipMemsetAsync(af, 0, img * 2, st);
-    if ((rc = launch_xf_pack(st, x0, 0, xf, nullptr, M, d, MB))) break;
-    if ((rc = launch_xf_pack(st, a, 1, af, nullptr, M, d, MB))) break;
-    GemvP g3[3];
-    out_cq_frag3(w, af, xf, x1, stat, q, q2, M, g3);
-    rc = launch_gemv_frag3(st, g3, 3);
-  } while (0);
-  hipError_t e = hipStreamSynchronize(st);
-  if (rc) return rc;
-  if (e != hipSuccess) { set_error("wis_op_gemv_out_cq: %s", hipGetErrorString(e)); return WIS_E_HIP; }
-  return WIS_OK;
+  WIS_RET(t.get(&wtmp, (size_t)d * d)); WIS_RET(t.get(&fcat, (size_t)2 * d * d)); WIS_RET(t.get(&fwot, (size_t)d * d)); WIS_RET(t.get(&fwqo, (size_t)d * d));
+  WIS_RET(t.get(&p_cqo, (size_t)2 * d * d)); WIS_RET(t.get(&p_out, (size_t)d * d)); WIS_RET(t.get(&b_cqo, (size_t)d));
+  if (frag) { WIS_RET(t.get(&xf, xf_elems(d, MB), true)); WIS_RET(t.get(&af, xf_elems(d, MB), true)); }
+  else WIS_RET(t.get(&xh, (size_t)M * d));
+  // load_weights, decoder layer: cq (the cross-Q bias scaled, the LayerNorm folded: bias / csum are what the cross-attention kernel takes as qb / qcs), out, then the fold
+  hipMemcpyAsync(wtmp, Wq, (size_t)d * d * 2, hipMemcpyDeviceToDevice, st);
+  hipLaunchKernelGGL(convert_kernel, dim3(blocks_for(d)), dim3(256), 0, st, bq, 0, qb, 0, (int64_t)d, (int64_t)1, (int64_t)1, (int64_t)d, qs);
+  hipMemsetAsync(qcs, 0, (size_t)d * 4, st);
+  DecLayerW w{};
+  w.out = DecProj{p_out, nullptr, bo, nullptr, d, d, gemv_rows_for(d, d)};
+  w.cqo = DecProj{p_cqo, nullptr, b_cqo, nullptr, d, 2 * d, 16};
+  WIS_RET(prep_projection(st, wtmp, d, d, d, d, qs, gamma, beta, qb, qcs, nullptr, nullptr, 16));      // (the fold alone: the stage streams w.out and w.cqo)
+  WIS_RET(launch_pack_gemv(st, reinterpret_cast<const f16*>(Wo), p_out, d, d, d, 0, 1.f, w.out.rows));
+  WIS_RET(build_cq_fold(st, wtmp, Wo, 1, bo, d, qs, fcat, fwot, fwqo, p_cqo, b_cqo));
+  hipMemcpyAsync(x1, x0, (size_t)M * d * 4, hipMemcpyDeviceToDevice, st);      // the residual epilogue works in place
+  if (!frag) {
+    // dec_forward: one dual launch on the f16 rows (the attention output; the f16 copy of the layer input that the embedding / FFN2 epilogues leave)
+    hipLaunchKernelGGL(convert_kernel, dim3(blocks_for((int64_t)M * d)), dim3(256), 0, st, x0, 0, xh, 1, (int64_t)M, (int64_t)d, (int64_t)d, (int64_t)0, 1.f);
+    GemvP ga, gb;
+    out_cq_dual(w, reinterpret_cast<const f16*>(a), xh, x1, stat, q, M, &ga, &gb);
+    return t.finish(launch_gemv_dual(st, ga, gb));
+  }
+  // dec_forward_frag: three d x d problems on the fragment images of the layer input and the attention output
+  WIS_RET(launch_xf_pack(st, x0, 0, xf, nullptr, M, d, MB));
+  WIS_RET(launch_xf_pack(st, a, 1, af, nullptr, M, d, MB));
+  GemvP g3[3];
+  out_cq_frag3(w, af, xf, x1, stat, q, q2, M, g3);
+  return t.finish(launch_gemv_frag3(st, g3, 3));
 }
 
 // ---- taps of what run_encoder / run_cross_kv launch (tests/test_gpu_enc_ops.py): the product's launch_* functions on the product's GemmP helpers
 // (conv1_gemm, conv2_gemm, gemm_plain) and weight packers, with free B and T; the tile and kernel form are gemm_pick_tile's / launch_gemm_t's choice
-static int tap_finish(hipStream_t st, int rc, const char* who) {      // synchronise before the scratch goes, whatever the launch answered
-  const hipError_t e0 = hipGetLastError(), e = hipStreamSynchronize(st);
-  if (rc) return rc;
-  if (e0 != hipSuccess || e != hipSuccess) { set_error("%s: %s", who, hipGetErrorString(e0 != hipSuccess ? e0 : e)); return WIS_E_HIP; }
-  return WIS_OK;
-}
 int wis_op_mel_to_image(int device, const float* mel, void* img_f16, int B, int n_mels) {
-  DeviceCtx* c; WIS_RET(get_ctx(device, &c));
-  std::lock_guard<std::mutex> op_lock(ctx_op_mutex(c));
+  Tap t(device, "wis_op_mel_to_image"); WIS_RET(t.rc);
   if (!mel || !img_f16 || B < 1) { set_error("wis_op_mel_to_image: bad argument"); return WIS_E_ARG; }
-  hipStream_t st = ctx_stream(c);
-  return tap_finish(st, launch_mel_to_image(st, mel, reinterpret_cast<f16*>(img_f16), B, n_mels), "wis_op_mel_to_image");
+  return t.finish(launch_mel_to_image(t.st, mel, reinterpret_cast<f16*>(img_f16), B, n_mels));
 }
 int wis_op_enc_conv(int device, int which, const void* img_f16, const void* W, int w_is_f16, const float* bias, const float* pos, void* out,
                     int B, int T, int Cin, int N) {
-  DeviceCtx* c; WIS_RET(get_ctx(device, &c));
-  std::lock_guard<std::mutex> op_lock(ctx_op_mutex(c));
+  Tap t(device, "wis_op_enc_conv"); WIS_RET(t.rc);
   if (!img_f16 || !W || !bias || !out || B < 1 || T < 1 || N < 128 || (which != 1 && which != 2) || (which == 2 && !pos) || (int64_t)B * (2 * (int64_t)T + 2) > 0x7fffffff) {
     set_error("wis_op_enc_conv: bad argument"); return WIS_E_ARG; }
   if (which == 1 ? !mel_bins_supported(Cin) : (Cin < 64 || Cin % 64)) { set_error("wis_op_enc_conv: conv%d with %d input channels", which, Cin); return WIS_E_UNSUPPORTED; }
-  hipStream_t st = ctx_stream(c);
-  TapScratch ts;
   f16* wp = nullptr;
-  if (!ts.get(&wp, (size_t)N * (which == 1 ? conv1_k(Cin) : 3 * Cin))) { set_error("wis_op_enc_conv: out of device memory"); return WIS_E_NOMEM; }
-  int rc;
+  WIS_RET(t.get(&wp, (size_t)N * (which == 1 ? conv1_k(Cin) : 3 * Cin)));
   if (which == 1) {
-    pack_conv1_w(st, W, w_is_f16, wp, N, Cin);
-    rc = launch_gemm_conv1(st, conv1_gemm(reinterpret_cast<const f16*>(img_f16), wp, B, T, Cin, N), bias, reinterpret_cast<f16*>(out), T);
-  } else {
-    pack_conv2_w(st, W, w_is_f16, wp, N, Cin);
-    rc = launch_gemm_conv2(st, conv2_gemm(reinterpret_cast<const f16*>(img_f16), wp, B, T, Cin, N), bias, pos, reinterpret_cast<float*>(out), T);
+    pack_conv1_w(t.st, W, w_is_f16, wp, N, Cin);
+    return t.finish(launch_gemm_conv1(t.st, conv1_gemm(reinterpret_cast<const f16*>(img_f16), wp, B, T, Cin, N), bias, reinterpret_cast<f16*>(out), T));
   }
-  return tap_finish(st, rc, "wis_op_enc_conv");
+  pack_conv2_w(t.st, W, w_is_f16, wp, N, Cin);
+  return t.finish(launch_gemm_conv2(t.st, conv2_gemm(reinterpret_cast<const f16*>(img_f16), wp, B, T, Cin, N), bias, pos, reinterpret_cast<float*>(out), T));
 }
 int wis_op_enc_qkv(int device, const void* xn_f16, const void* W_f16, const float* bias, void* qk_f16, void* vt_f16, int B, int T, int H) {
-  DeviceCtx* c; WIS_RET(get_ctx(device, &c));
-  std::lock_guard<std::mutex> op_lock(ctx_op_mutex(c));
+  Tap t(device, "wis_op_enc_qkv"); WIS_RET(t.rc);
   if (!xn_f16 || !W_f16 || !bias || !qk_f16 || !vt_f16 || B < 1 || T < 1 || H < 1 || (int64_t)B * T > 0x7fffffff / (3 * 64 * (int64_t)H)) { set_error("wis_op_enc_qkv: bad argument"); return WIS_E_ARG; }
   if (T % 4) { set_error("wis_op_enc_qkv: T = %d (the transposed V tiles store 4 consecutive keys of one utterance: T %% 4 == 0)", T); return WIS_E_ARG; }
-  hipStream_t st = ctx_stream(c);
   const int d = 64 * H;
-  const int rc = launch_gemm_qkv(st, gemm_plain(reinterpret_cast<const f16*>(xn_f16), d, reinterpret_cast<const f16*>(W_f16), B * T, 3 * d, d), bias,
-                                 reinterpret_cast<f16*>(qk_f16), reinterpret_cast<f16*>(vt_f16), d, T, cdiv(T, 64) * 64, H);
-  return tap_finish(st, rc, "wis_op_enc_qkv");
+  return t.finish(launch_gemm_qkv(t.st, gemm_plain(reinterpret_cast<const f16*>(xn_f16), d, reinterpret_cast<const f16*>(W_f16), B * T, 3 * d, d), bias,
+                                  reinterpret_cast<f16*>(qk_f16), reinterpret_cast<f16*>(vt_f16), d, T, cdiv(T, 64) * 64, H));
 }
 int wis_op_enc_crosskv(int device, const void* mem_f16, const void* W_f16, const float* bias, void* kx_f16, void* vt_f16, int B, int T, int H, int L,
                        int64_t kx_lstride, int64_t vt_lstride) {
-  DeviceCtx* c; WIS_RET(get_ctx(device, &c));
-  std::lock_guard<std::mutex> op_lock(ctx_op_mutex(c));
+  Tap t(device, "wis_op_enc_crosskv"); WIS_RET(t.rc);
   if (!mem_f16 || !W_f16 || !bias || !kx_f16 || !vt_f16 || B < 1 || T < 1 || H < 1 || L < 1 || (int64_t)L * 2 * 64 * H > 0x7fffffff || (int64_t)B * T > 0x7fffffff / (64 * (int64_t)H)) {
     set_error("wis_op_enc_crosskv: bad argument"); return WIS_E_ARG; }
   if (T % 4) { set_error("wis_op_enc_crosskv: T = %d (the transposed V tiles store 4 consecutive keys of one utterance: T %% 4 == 0)", T); return WIS_E_ARG; }
   const int d = 64 * H, Tpad = cdiv(T, 64) * 64;
   if (kx_lstride < (int64_t)B * T * d || vt_lstride < (int64_t)B * d * Tpad || kx_lstride % 8 || vt_lstride % 8) {      // (16-byte stores into every layer's image)
     set_error("wis_op_enc_crosskv: layer strides must be multiples of 8 elements and at least the layer's image"); return WIS_E_ARG; }
-  hipStream_t st = ctx_stream(c);
-  const int rc = launch_gemm_crosskv(st, gemm_plain(reinterpret_cast<const f16*>(mem_f16), d, reinterpret_cast<const f16*>(W_f16), B * T, L * 2 * d, d), bias,
-                                     reinterpret_cast<f16*>(kx_f16), reinterpret_cast<f16*>(vt_f16), d, T, Tpad, H, kx_lstride, vt_lstride);
-  return tap_finish(st, rc, "wis_op_enc_crosskv");
+  return t.finish(launch_gemm_crosskv(t.st, gemm_plain(reinterpret_cast<const f16*>(mem_f16), d, reinterpret_cast<const f16*>(W_f16), B * T, L * 2 * d, d), bias,
+                                      reinterpret_cast<f16*>(kx_f16), reinterpret_cast<f16*>(vt_f16), d, T, Tpad, H, kx_lstride, vt_lstride));
 }
 int wis_op_gemm_splitk_ln(int device, const void* A_f16, const void* W_f16, const float* bias, float* X, const float* gamma, const float* beta, void* Y_f16,
                           int M, int N, int K, int splits) {
-  DeviceCtx* c; WIS_RET(get_ctx(device, &c));
-  std::lock_guard<std::mutex> op_lock(ctx_op_mutex(c));
+  Tap t(device, "wis_op_gemm_splitk_ln"); WIS_RET(t.rc);
   if (!A_f16 || !W_f16 || !bias || !X || !gamma || !beta || !Y_f16 || M < 1 || N < 128 || K < 64 || splits < 0 || splits > 16 || (int64_t)M * N > 0x7fffffff) {
     set_error("wis_op_gemm_splitk_ln: bad argument"); return WIS_E_ARG; }
   if (!splits) splits = enc_splitk(N, M);      // run_encoder's choice for FFN2 at these rows
   if (!splits) { set_error("wis_op_gemm_splitk_ln: the encoder does not split K at M = %d, N = %d", M, N); return WIS_E_UNSUPPORTED; }
-  hipStream_t st = ctx_stream(c);
-  TapScratch ts;
   float* scratch = nullptr;
-  if (!ts.get(&scratch, (size_t)splits * M * N)) { set_error("wis_op_gemm_splitk_ln: out of device memory"); return WIS_E_NOMEM; }
-  const int rc = launch_gemm_splitk_resid(st, gemm_plain(reinterpret_cast<const f16*>(A_f16), K, reinterpret_cast<const f16*>(W_f16), M, N, K), splits, scratch, bias, X, X,
-                                          gamma, beta, reinterpret_cast<f16*>(Y_f16));
-  return tap_finish(st, rc, "wis_op_gemm_splitk_ln");
+  WIS_RET(t.get(&scratch, (size_t)splits * M * N));
+  return t.finish(launch_gemm_splitk_resid(t.st, gemm_plain(reinterpret_cast<const f16*>(A_f16), K, reinterpret_cast<const f16*>(W_f16), M, N, K), splits, scratch, bias, X, X,
+                                           gamma, beta, reinterpret_cast<f16*>(Y_f16)));
 }
 
 // ---- taps of what runs behind the logits (tests/test_gpu_sample_ops.py): the cache movers of a beam step and of a verified draft window, and the three
 // softmax readers, through the product's launch_* functions on caller-supplied device memory
 int wis_op_kv_reorder(int device, void* kc_f16, void* vc_f16, int64_t layer_stride_elems, int L, const int32_t* parent, const int32_t* step_u, const int32_t* done,
                       int B, int beam, int P, int ctx, int d) {
-  DeviceCtx* c; WIS_RET(get_ctx(device, &c));
-  std::lock_guard<std::mutex> op_lock(ctx_op_mutex(c));
+  Tap t(device, "wis_op_kv_reorder"); WIS_RET(t.rc);
   if (!kc_f16 || !vc_f16 || !parent || !step_u || !done || L < 1 || B < 1 || beam < 1 || P < 1 || ctx < 1 || d < 8 || d % 8 || layer_stride_elems < (int64_t)B * beam * ctx * d || layer_stride_elems % 8) {
     set_error("wis_op_kv_reorder: bad argument"); return WIS_E_ARG; }
-  hipStream_t st = ctx_stream(c);
   BeamState bs; memset(&bs, 0, sizeof(bs));
   bs.parent = const_cast<int*>(parent); bs.step_u = const_cast<int*>(step_u); bs.done = const_cast<int*>(done);
-  return tap_finish(st, launch_kv_reorder(st, reinterpret_cast<f16*>(kc_f16), reinterpret_cast<f16*>(vc_f16), (size_t)layer_stride_elems, L, bs, B, beam, P, ctx, d), "wis_op_kv_reorder");
+  return t.finish(launch_kv_reorder(t.st, reinterpret_cast<f16*>(kc_f16), reinterpret_cast<f16*>(vc_f16), (size_t)layer_stride_elems, L, bs, B, beam, P, ctx, d));
 }
 int wis_op_kv_gather(int device, void* kc_f16, void* vc_f16, int64_t layer_stride_elems, int L, const int32_t* vstate, const int32_t* done, int beam, int w0, int ctx, int d) {
-  DeviceCtx* c; WIS_RET(get_ctx(device, &c));
-  std::lock_guard<std::mutex> op_lock(ctx_op_mutex(c));
+  Tap t(device, "wis_op_kv_gather"); WIS_RET(t.rc);
   if (!kc_f16 || !vc_f16 || !vstate || !done || L < 1 || beam < 1 || beam > MAX_R || w0 < 0 || w0 >= ctx || d < 8 || d % 8 || layer_stride_elems < (int64_t)beam * ctx * d || layer_stride_elems % 8) {
     set_error("wis_op_kv_gather: bad argument"); return WIS_E_ARG; }
-  hipStream_t st = ctx_stream(c);
-  return tap_finish(st, launch_kv_gather(st, reinterpret_cast<f16*>(kc_f16), reinterpret_cast<f16*>(vc_f16), (size_t)layer_stride_elems, L, vstate, done, beam, w0, ctx, d), "wis_op_kv_gather");
+  return t.finish(launch_kv_gather(t.st, reinterpret_cast<f16*>(kc_f16), reinterpret_cast<f16*>(vc_f16), (size_t)layer_stride_elems, L, vstate, done, beam, w0, ctx, d));
 }
 int wis_op_no_speech(int device, const float* logits, int ld, int B, int rs, int r0, int V, int ns, float* out) {
-  DeviceCtx* c; WIS_RET(get_ctx(device, &c));
-  std::lock_guard<std::mutex> op_lock(ctx_op_mutex(c));
+  Tap t(device, "wis_op_no_speech"); WIS_RET(t.rc);
   if (!logits || !out || B < 1 || rs < 1 || r0 < 0 || r0 >= rs || V < 1 || ld < V) { set_error("wis_op_no_speech: bad argument"); return WIS_E_ARG; }
-  hipStream_t st = ctx_stream(c);
-  return tap_finish(st, launch_no_speech(st, logits, ld, B, rs, r0, V, ns, out), "wis_op_no_speech");
+  return t.finish(launch_no_speech(t.st, logits, ld, B, rs, r0, V, ns, out));
 }
 int wis_op_lang_probs(int device, const float* logits, int ld, const int32_t* lang_ids, int n_lang, float* probs, int B) {
-  DeviceCtx* c; WIS_RET(get_ctx(device, &c));
-  std::lock_guard<std::mutex> op_lock(ctx_op_mutex(c));
+  Tap t(device, "wis_op_lang_probs"); WIS_RET(t.rc);
   if (!logits || !lang_ids || !probs || B < 1 || n_lang < 1 || ld < 1) { set_error("wis_op_lang_probs: bad argument"); return WIS_E_ARG; }
-  hipStream_t st = ctx_stream(c);
-  return tap_finish(st, launch_lang_probs(st, logits, ld, lang_ids, n_lang, probs, B), "wis_op_lang_probs");
+  return t.finish(launch_lang_probs(t.st, logits, ld, lang_ids, n_lang, probs, B));
 }
 int wis_op_greedy_rows(int device, const float* logits, int n_vocab, int n_vocab_pad, int eot, const float* bias_all, const float* bias_begin, const int32_t* step_u,
                        int B, int beam, int lr_b, int lr_j, int lr_off, const int32_t* rowmap, int32_t* tok_out, float* lp_out) {
-  DeviceCtx* c; WIS_RET(get_ctx(device, &c));
-  std::lock_guard<std::mutex> op_lock(ctx_op_mutex(c));
+  Tap t(device, "wis_op_greedy_rows"); WIS_RET(t.rc);
   if (!logits || !bias_begin || !step_u || !tok_out || !lp_out || B < 1 || beam < 1 || beam > MAX_R || n_vocab < STAT_SUB || n_vocab_pad < n_vocab || eot < 0 || eot >= n_vocab ||
       lr_b < 0 || lr_j < 0 || lr_off < 0) { set_error("wis_op_greedy_rows: bad argument"); return WIS_E_ARG; }
-  hipStream_t st = ctx_stream(c);
   const int rows = B * beam;
   SampleCfg sc; memset(&sc, 0, sizeof(sc));
   sc.n_vocab = n_vocab; sc.n_vocab_pad = n_vocab_pad; sc.eot = eot; sc.beam = beam; sc.n_cand = 2; sc.suppress_blank = 1; sc.greedy = 1;
-  TapScratch ts;
   float *smax = nullptr, *ssum = nullptr, *sval = nullptr; int* sidx = nullptr;
-  if (!ts.get(&smax, (size_t)rows * STAT_SUB) || !ts.get(&ssum, (size_t)rows * STAT_SUB) || !ts.get(&sval, (size_t)rows * STAT_SUB * sc.n_cand) ||
-      !ts.get(&sidx, (size_t)rows * STAT_SUB * sc.n_cand)) { set_error("wis_op_greedy_rows: out of device memory"); return WIS_E_NOMEM; }
-  int rc = launch_logit_stats(st, logits, bias_all, bias_begin, step_u, smax, ssum, sval, sidx, B, sc, lr_b, lr_j, lr_off, nullptr, rowmap);
-  if (!rc) rc = launch_greedy_pick(st, smax, ssum, sval, sidx, rows, sc, tok_out, lp_out);
-  return tap_finish(st, rc, "wis_op_greedy_rows");
+  WIS_RET(t.get(&smax, (size_t)rows * STAT_SUB)); WIS_RET(t.get(&ssum, (size_t)rows * STAT_SUB));
+  WIS_RET(t.get(&sval, (size_t)rows * STAT_SUB * sc.n_cand)); WIS_RET(t.get(&sidx, (size_t)rows * STAT_SUB * sc.n_cand));
+  WIS_RET(launch_logit_stats(t.st, logits, bias_all, bias_begin, step_u, smax, ssum, sval, sidx, B, sc, lr_b, lr_j, lr_off, nullptr, rowmap));
+  return t.finish(launch_greedy_pick(t.st, smax, ssum, sval, sidx, rows, sc, tok_out, lp_out));
 }
 
 }  // extern "C"
