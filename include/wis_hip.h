@@ -177,6 +177,28 @@ typedef struct {
                                      division; once however often t occurs).  1 - and 0, what a caller that never knew the field passes - : off */
   int32_t no_repeat_ngram_size;   /* n >= 1: with a history h of L >= n tokens, every i in [0, L - n] with h[i .. i+n-2] == h[L-n+1 .. L-1] masks
                                      h[i+n-1] (n = 1: every history token).  0: off */
+  /* Random sampling and n-best results (CTranslate2 4.1.0 RandomSampler / GreedySearch and num_hypotheses; restated, not pinned against
+   * CTranslate2).  Appended fields: 0 is what a caller that never knew them passes, and means today's search.
+   * THE SAMPLING RULE.  Sampling applies at beam_size 1.  The logits processors run first, in the order above (repetition rules, suppress lists,
+   * timestamp rules, fixed_new_tokens); call the result x, masked ids at -inf.  The allowed set K is every unmasked id (whole vocabulary) or the k
+   * largest x (top-k; value descending, then id ascending).  The token is drawn from softmax(x[K] / T); its contribution to the hypothesis score is
+   * (x[t] - logsumexp(x over ALL unmasked ids)) / T, the temperature-scaled log-probability; the final score is normalised as the greedy path's
+   * (/ len^length_penalty).  num_hypotheses = n decodes n independent samples per utterance (n decoder rows that share the utterance's cross K / V, where
+   * n beams would sit: B n <= 96 rows, n <= max_beam); results come back in sample order, unsorted.
+   * The draw is a Gumbel-max: t = argmax over K of (x[t] / T + g(t)) in fp32 (a true division, one addition), ties to the lower id, with noise that
+   * is specified bit for bit:  w = Philox4x32-10(counter = (token id, step index, sample index j within the utterance, 0), key = (seed_lo, seed_hi))[0],
+   * u = ((w >> 9) + 0.5) 2^-23  (inside (5.96e-8, 0.99999994) for every w; the 24-bit form rounds to 1 for w = 0xFFFFFFFF),  g = -log(-log(u)) with
+   * an accurate logf.  The seed is per UTTERANCE (wis_generate_n: seeds [B]) and the counter carries the sample index, not the device row: an
+   * utterance's samples do not depend on its slot in the device batch.  A finished sample keeps its result; its row is fed <|endoftext|> until the
+   * utterance's last sample has finished.
+   * Errors: sampling with beam_size > 1, num_hypotheses > 1 at beam_size 1 without sampling, num_hypotheses > beam_size in a beam search, a
+   * temperature that is not finite and > 0, num_hypotheses outside 1 .. 8: WIS_E_ARG; sampling_topk > 16: WIS_E_UNSUPPORTED; drafted decodes with
+   * any of the three on: WIS_E_UNSUPPORTED.  Nothing is enqueued by a refused call.  wis_generate / wis_debug_search return one hypothesis:
+   * num_hypotheses > 1 there is WIS_E_ARG (wis_generate_n / wis_debug_search_n). */
+  int32_t sampling_topk;          /* 0 or 1: off (arg-max).  -1: sample from the whole vocabulary.  2 .. 16: from the k best.  Larger: WIS_E_UNSUPPORTED */
+  float   sampling_temperature;   /* T; 0 means 1 */
+  int32_t num_hypotheses;         /* n; 0 means 1.  Beam search (no sampling): the n best finished hypotheses by normalised score, best first, the first
+                                     registered among equal scores; CTranslate2's early exit then needs n finished hypotheses */
 } wis_gen_opts_t;
 
 /* out_ids: [B][max_new] (max_new = resolved max_new_tokens), out_len: [B], out_score: [B]
@@ -187,6 +209,11 @@ typedef struct {
  * replica from one worker thread and coalesces concurrent requests into device batches. */
 int wis_generate(wis_model_t* m, const float* input, int B, const int32_t* prompt, int P,
                  const wis_gen_opts_t* opts, int32_t* out_ids, int32_t* out_len, float* out_score);
+/* wis_generate with n = opts->num_hypotheses results per utterance: out_ids [B][n][max_new], out_len [B][n], out_score [B][n] or NULL.
+ * seeds: uint64 [B], one per utterance, or NULL = all 0 (read by sampled decodes only).  They are written to device memory at the start of
+ * the call - never a kernel argument of a captured step: one step graph serves every seed. */
+int wis_generate_n(wis_model_t* m, const float* input, int B, const int32_t* prompt, int P, const wis_gen_opts_t* opts, const uint64_t* seeds,
+                   int32_t* out_ids, int32_t* out_len, float* out_score);
 
 /* ---- 8(f)3, BASELINE configs[4]: the FINAL decode of a recording that was heard while it arrived (one utterance, beam_size 1 - the
  * reference's default, settings.py:14).  `draft`: the token ids of an earlier hypothesis for (most of) the same audio, e.g. the last
@@ -282,6 +309,12 @@ int wis_debug_tree_logits(wis_model_t* m, const float* input, int input_kind, co
  * out_parent [n_steps][B*beam] or NULL (KV slot every live beam continues from after each step: what kv_reorder_kernel applies). */
 int wis_debug_search(wis_model_t* m, const float* logits, int n_steps, int B, const wis_gen_opts_t* opts,
                      int32_t* out_ids, int32_t* out_len, float* out_score, int32_t* out_finish_step, int32_t* out_parent);
+/* the same with n = opts->num_hypotheses results per utterance and the sampling options: logits f32 [n_steps][B*R][n_vocab], R = rows per utterance
+ * (beam_size in a beam search, n in a sampled one).  Sampled: sample j of utterance b reads row s*B*n + b*n + j, step 0 row b*n for every sample.
+ * out_ids [B][n][max_new], out_len / out_score [B][n]; out_finish_step [B]; out_parent [n_steps][B*R].  seeds [B] or NULL as wis_generate_n.
+ * noise (tests; NULL: Philox): uint32 [n_steps][B*n][n_vocab] (host) - the word w of (step, row, token id) in place of the Philox word. */
+int wis_debug_search_n(wis_model_t* m, const float* logits, int n_steps, int B, const wis_gen_opts_t* opts, const uint64_t* seeds, const uint32_t* noise,
+                       int32_t* out_ids, int32_t* out_len, float* out_score, int32_t* out_finish_step, int32_t* out_parent);
 
 /* the decoder cross-attention's granule hand-off (small grids; dec_kernels.hip SPIN): retries = calls on this handle that were run
  * again in the ticket form because a combiner's bounded spin ran out (a request never fails for it; expected 0 - the granule form is

@@ -2270,15 +2270,39 @@ __device__ __forceinline__ bool better(float av, int ai, float bv, int bi) { ret
 __device__ __forceinline__ bool better_b(float av, int ai, float bv, int bi) { return (av > bv) | ((av == bv) & (ai < bi)); }
 __device__ __forceinline__ void take_better(float& v, int& i, float ov, int oi) { const bool t = better_b(ov, oi, v, i); v = t ? ov : v; i = t ? oi : i; }
 
+// ---- the noise of a sampled decode (include/wis_hip.h states it bit for bit; tests/sample_ref.py restates it in numpy)
+// word 0 of Philox4x32-10 (Salmon et al., "Parallel random numbers: as easy as 1, 2, 3") over counter (c0, c1, c2, c3), key (k0, k1)
+__device__ __forceinline__ unsigned philox4x32_10_w0(unsigned c0, unsigned c1, unsigned c2, unsigned c3, unsigned k0, unsigned k1) {
+#pragma unroll
+  for (int r = 0; r < 10; ++r) {
+    const unsigned h0 = __umulhi(0xD2511F53u, c0), l0 = 0xD2511F53u * c0;
+    const unsigned h1 = __umulhi(0xCD9E8D57u, c2), l1 = 0xCD9E8D57u * c2;
+    c0 = h1 ^ c1 ^ k0; c1 = l1; c2 = h0 ^ c3 ^ k1; c3 = l0;
+    k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
+  }
+  return c0;
+}
+// u = ((w >> 9) + 0.5) 2^-23 (exact in fp32, strictly inside (0, 1)), g = -log(-log(u)) with the accurate logf: the winners of a Gumbel-max are
+// the u closest to 1, where log(u) is tiny and the fast __logf loses its relative accuracy
+__device__ __forceinline__ float gumbel_of_word(unsigned w) {
+  const float u = ((float)(w >> 9) + 0.5f) * 1.1920928955078125e-07f;
+  return -logf(-logf(u));
+}
+// the perturbed value of token id `tk` with processed logit x: x / T + g, fp32, a true division (-inf stays -inf)
+__device__ __forceinline__ float gumbel_perturb(float x, unsigned w, float T) { return __fadd_rn(__fdiv_rn(x, T), gumbel_of_word(w)); }
+
 // TS: the timestamp form - three more [lo, hi) ranges of the row are masked, as ts_rules_kernel left them for the row in ts_desc
 // (the plain form takes ts_desc = nullptr and compiles to what it was before the template parameter existed)
-template <bool TS>
+// SAMP: whole-vocabulary sampling - maximum and sum of exponentials of the UNPERTURBED row as ever (the score needs them), then every value is
+// perturbed (x / T + Gumbel noise) and the wave reports its single best perturbed entry: st_val[.][0] = the perturbed value, [1] = that entry's
+// unperturbed logit, st_idx[.][0] = its id (cfg.n_cand = 2 is the layout; the other instantiations never read sp)
+template <bool TS, bool SAMP = false>
 __global__ __launch_bounds__(256) void logit_stats_kernel(const float* __restrict__ logits, const float* __restrict__ bias_all,
                                                           const float* __restrict__ bias_begin, const int* __restrict__ step_u,
                                                           float* __restrict__ st_max, float* __restrict__ st_sum,
                                                           float* __restrict__ st_val, int* __restrict__ st_idx, SampleCfg cfg,
                                                           int lr_b, int lr_j, int lr_off, unsigned long long* prof, const int* __restrict__ rowmap,
-                                                          const int* __restrict__ ts_desc) {
+                                                          const int* __restrict__ ts_desc, SampleP sp) {
   constexpr int PT = 16;   // values per lane: supports n_vocab <= 64 * 64 * 16
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int sc = blockIdx.x * 4 + wave, m = blockIdx.y, b = m / cfg.beam;
@@ -2332,6 +2356,37 @@ __global__ __launch_bounds__(256) void logit_stats_kernel(const float* __restric
   sum = wave_sum(sum);
   if (lane == 0) { st_max[m * STAT_SUB + sc] = mx; st_sum[m * STAT_SUB + sc] = sum; }
   stamp(pf, 2);
+  if constexpr (SAMP) {
+    // one Philox block per value, all independent; the noise words of a test table are requested straight-line like the row itself
+    const unsigned long long seed = sp.seeds[b];
+    const unsigned k0 = (unsigned)seed, k1 = (unsigned)(seed >> 32);
+    unsigned nw[PT];
+    if (sp.noise) {
+#pragma unroll
+      for (int i = 0; i < PT; ++i) { const int nidx = lo + lane + 64 * i; nw[i] = sp.noise[(size_t)m * cfg.n_vocab + (nidx < hi ? nidx : hi - 1)]; }
+    } else {
+#pragma unroll
+      for (int i = 0; i < PT; ++i) nw[i] = philox4x32_10_w0((unsigned)(lo + lane + 64 * i), (unsigned)step, (unsigned)jb, 0u, k0, k1);
+    }
+    u64 t[PT];
+#pragma unroll
+    for (int i = 0; i < PT; ++i) { const int nidx = lo + lane + 64 * i; t[i] = nidx < hi ? sel_key(gumbel_perturb(vals[i], nw[i], sp.T), nidx) : 0ull; keys[i] = t[i]; }
+#pragma unroll
+    for (int w = PT / 2; w >= 1; w >>= 1)
+#pragma unroll
+      for (int i = 0; i < w; ++i) t[i] = key_max(t[i], t[i + w]);
+    const u64 best = wave_max_key(t[0]);
+    float xw = -INFINITY;      // the winner's unperturbed logit: one lane holds the key (ids are distinct)
+#pragma unroll
+    for (int i = 0; i < PT; ++i) xw = ((keys[i] == best) & (best != 0ull)) ? vals[i] : xw;
+    xw = wave_max(xw);
+    if (lane == 0) {
+      st_val[((size_t)m * STAT_SUB + sc) * 2] = best ? key_value(best) : -INFINITY;
+      st_val[((size_t)m * STAT_SUB + sc) * 2 + 1] = xw;
+      st_idx[((size_t)m * STAT_SUB + sc) * 2] = best ? key_index(best) : 0x7fffffff;
+    }
+    return;
+  }
   // top-n_cand of the sub-chunk in (value desc, index asc) order: n_cand rounds of a wave arg-best over the lanes' best
   // not-yet-picked value
   // n_cand rounds: lane-local best key strictly below the previous pick (independent tests, a 4-level max tree - a scan that
@@ -2357,12 +2412,21 @@ __global__ __launch_bounds__(256) void logit_stats_kernel(const float* __restric
 }
 int launch_logit_stats(hipStream_t st, const float* logits, const float* bias_all, const float* bias_begin, const int* step_u,
                        float* st_max, float* st_sum, float* st_val, int* st_idx, int B, const SampleCfg& cfg, int lr_b, int lr_j, int lr_off,
-                       unsigned long long* prof, const int* rowmap, const int* ts_desc) {
+                       unsigned long long* prof, const int* rowmap, const int* ts_desc, const SampleP* sp) {
   if (cdiv(cfg.n_vocab, STAT_SUB) > 16 * 64) { set_error("logit_stats: vocab too large"); return WIS_E_UNSUPPORTED; }
-  if (ts_desc) hipLaunchKernelGGL(logit_stats_kernel<true>, dim3(STAT_SUB / 4, B * cfg.beam), dim3(256), 0, st, logits, bias_all, bias_begin, step_u,
-                                  st_max, st_sum, st_val, st_idx, cfg, lr_b, lr_j, lr_off, prof, rowmap, ts_desc);
-  else hipLaunchKernelGGL(logit_stats_kernel<false>, dim3(STAT_SUB / 4, B * cfg.beam), dim3(256), 0, st, logits, bias_all, bias_begin, step_u,
-                          st_max, st_sum, st_val, st_idx, cfg, lr_b, lr_j, lr_off, prof, rowmap, nullptr);
+  const SampleP none;
+  if (sp && sp->topk < 0) {
+    if (rowmap || cfg.n_cand != 2 || !sp->seeds || !(sp->T > 0.f)) { set_error("logit_stats: sampling form misconfigured"); return WIS_E_ARG; }
+    if (ts_desc) hipLaunchKernelGGL((logit_stats_kernel<true, true>), dim3(STAT_SUB / 4, B * cfg.beam), dim3(256), 0, st, logits, bias_all, bias_begin, step_u,
+                                    st_max, st_sum, st_val, st_idx, cfg, lr_b, lr_j, lr_off, prof, rowmap, ts_desc, *sp);
+    else hipLaunchKernelGGL((logit_stats_kernel<false, true>), dim3(STAT_SUB / 4, B * cfg.beam), dim3(256), 0, st, logits, bias_all, bias_begin, step_u,
+                            st_max, st_sum, st_val, st_idx, cfg, lr_b, lr_j, lr_off, prof, rowmap, nullptr, *sp);
+    return WIS_OK;
+  }
+  if (ts_desc) hipLaunchKernelGGL((logit_stats_kernel<true, false>), dim3(STAT_SUB / 4, B * cfg.beam), dim3(256), 0, st, logits, bias_all, bias_begin, step_u,
+                                  st_max, st_sum, st_val, st_idx, cfg, lr_b, lr_j, lr_off, prof, rowmap, ts_desc, none);
+  else hipLaunchKernelGGL((logit_stats_kernel<false, false>), dim3(STAT_SUB / 4, B * cfg.beam), dim3(256), 0, st, logits, bias_all, bias_begin, step_u,
+                          st_max, st_sum, st_val, st_idx, cfg, lr_b, lr_j, lr_off, prof, rowmap, nullptr, none);
   return WIS_OK;
 }
 
@@ -2591,7 +2655,7 @@ __device__ __forceinline__ void publish_step(const BeamState& bs) {
 template <int PSL>
 __global__ __launch_bounds__(256) void beam_step_kernel(const float* __restrict__ st_max, const float* __restrict__ st_sum,
                                                         const float* __restrict__ st_val, const int* __restrict__ st_idx,
-                                                        BeamState bs, RowMeta rm, int P, int ctx, SampleCfg cfg, unsigned long long* prof) {
+                                                        BeamState bs, RowMeta rm, int P, int ctx, SampleCfg cfg, unsigned long long* prof, int n_best) {
   constexpr int HPT = (MAX_R * 256 + 255) / 256;                    // history tokens per thread (8)
   __shared__ float lse[MAX_R], s_cum[MAX_R];
   __shared__ float cand_v[MAX_CAND]; __shared__ int cand_word[MAX_CAND]; __shared__ int cand_org[MAX_CAND];
@@ -2737,27 +2801,39 @@ __global__ __launch_bounds__(256) void beam_step_kernel(const float* __restrict_
     __syncthreads();
     __threadfence_block();
     if (tid == 0) {
-      // finalize_result: score / len^length_penalty, best first
+      // finalize_result: score / len^length_penalty, best first: the n_best best, the first registered among equal scores (result i of the
+      // utterance at b n_best + i; n_best = 1 is the one result at b)
       const int nh = bs.n_hyp[b];
-      int best = 0; float bsc = -INFINITY;
-      for (int i = 0; i < nh; ++i) {
-        float s = bs.hyp_score[b * cfg.max_hyp + i];
-        const int n = bs.hyp_len[b * cfg.max_hyp + i];
-        if (cfg.length_penalty != 0.f) s /= powf((float)n, cfg.length_penalty);
-        if (s > bsc) { bsc = s; best = i; }
+      unsigned taken = 0u;
+      for (int r = 0; r < n_best; ++r) {
+        int best = -1; float bsc = -INFINITY;
+        for (int i = 0; i < nh; ++i) {
+          if ((taken >> i) & 1u) continue;
+          if (best < 0) best = i;
+          float s = bs.hyp_score[b * cfg.max_hyp + i];
+          const int n = bs.hyp_len[b * cfg.max_hyp + i];
+          if (cfg.length_penalty != 0.f) s /= powf((float)n, cfg.length_penalty);
+          if (s > bsc) { bsc = s; best = i; }
+        }
+        cand_org[r] = best;
+        const int len = best >= 0 ? bs.hyp_len[b * cfg.max_hyp + best] : 0;
+        if (best >= 0) taken |= 1u << best;
+        bs.out_len[b * n_best + r] = len;
+        bs.out_score[b * n_best + r] = bsc;
+        hp_out_len(bs.host)[b * n_best + r] = len;      // the host's copy of the result (fenced below, before the step is published)
+        hp_out_score(bs.host)[b * n_best + r] = bsc;
       }
-      cand_org[0] = best;
-      bs.out_len[b] = bs.hyp_len[b * cfg.max_hyp + best];
-      bs.out_score[b] = bsc;
       bs.done[b] = 1;
-      hp_out_len(bs.host)[b] = bs.hyp_len[b * cfg.max_hyp + best];      // the host's copy of the result (fenced below, before the step is published)
-      hp_out_score(bs.host)[b] = bsc;
     }
     __syncthreads();
-    const int best = cand_org[0], n = bs.hyp_len[b * cfg.max_hyp + best];
-    const int* src = bs.hyp_tok + ((size_t)b * cfg.max_hyp + best) * cfg.max_new;
-    int* hids = hp_out_ids(bs.host) + (size_t)b * cfg.max_new;
-    for (int t = tid; t < n; t += 256) { const int v = src[t]; bs.out_ids[(size_t)b * cfg.max_new + t] = v; hids[t] = v; }
+    for (int r = 0; r < n_best; ++r) {
+      const int best = cand_org[r];
+      if (best < 0) continue;
+      const int n = bs.hyp_len[b * cfg.max_hyp + best];
+      const int* src = bs.hyp_tok + ((size_t)b * cfg.max_hyp + best) * cfg.max_new;
+      int* hids = hp_out_ids(bs.host) + (size_t)(b * n_best + r) * cfg.max_new;
+      for (int t = tid; t < n; t += 256) { const int v = src[t]; bs.out_ids[(size_t)(b * n_best + r) * cfg.max_new + t] = v; hids[t] = v; }
+    }
     __threadfence_system();
     __syncthreads();
     if (tid == 0) { atomicAdd(bs.all_done, 1); publish_step(bs); }
@@ -2786,10 +2862,144 @@ __global__ __launch_bounds__(256) void beam_step_kernel(const float* __restrict_
   stamp(pf, 8);
 }
 int launch_beam_step(hipStream_t st, const float* st_max, const float* st_sum, const float* st_val, const int* st_idx,
-                     const BeamState& bs, const RowMeta& rm, int B, int P, int ctx, const SampleCfg& cfg, unsigned long long* prof) {
+                     const BeamState& bs, const RowMeta& rm, int B, int P, int ctx, const SampleCfg& cfg, unsigned long long* prof, int n_best) {
   if (cfg.beam > MAX_R || cfg.n_cand > MAX_CAND || cfg.max_new > 256 || ctx > 512 || cfg.n_vocab > (1 << 20)) { set_error("beam_step: config out of range"); return WIS_E_UNSUPPORTED; }
-  if (cfg.beam * STAT_SUB * cfg.n_cand <= 16 * 256) hipLaunchKernelGGL(beam_step_kernel<16>, dim3(B), dim3(256), 0, st, st_max, st_sum, st_val, st_idx, bs, rm, P, ctx, cfg, prof);
-  else hipLaunchKernelGGL(beam_step_kernel<32>, dim3(B), dim3(256), 0, st, st_max, st_sum, st_val, st_idx, bs, rm, P, ctx, cfg, prof);
+  if (n_best < 1 || n_best > cfg.beam || B * n_best > HP_MAXB) { set_error("beam_step: %d results per utterance at beam %d", n_best, cfg.beam); return WIS_E_ARG; }
+  if (cfg.beam * STAT_SUB * cfg.n_cand <= 16 * 256) hipLaunchKernelGGL(beam_step_kernel<16>, dim3(B), dim3(256), 0, st, st_max, st_sum, st_val, st_idx, bs, rm, P, ctx, cfg, prof, n_best);
+  else hipLaunchKernelGGL(beam_step_kernel<32>, dim3(B), dim3(256), 0, st, st_max, st_sum, st_val, st_idx, bs, rm, P, ctx, cfg, prof, n_best);
+  return WIS_OK;
+}
+
+// =======================================================================================
+// The step of a SAMPLED decode, in beam_step_kernel's place (include/wis_hip.h states the rule).  grid B, block 256: an utterance's cfg.beam = n
+// rows are its n independent samples; wave w draws rows w and w + 4, no barrier inside a wave's work.
+//   whole vocabulary (TOPK false): logit_stats_kernel<., true> left each sub-chunk's best PERTURBED entry; the draw is the arg-best of the 64.
+//   top-k (TOPK true): the pool is unperturbed, k candidates per sub-chunk (16 entries per lane at most); k selection rounds (wave maximum of the
+//     lane-local bests, retire) give the row's top-k in sel_key order, each is perturbed as it is selected (every lane computes the same Philox
+//     block: the round's winner is wave-uniform), the best perturbed one is the draw.
+// Then one thread per row: score += (x[t] - lse) / T, the token joins bs.alive, a row that drew EOT (or the last step) freezes its result
+// (bs.out_len / out_score; its tokens are alive[row][0 .. len)) and raises its own done flag - from then on the row is fed EOT, and EOT is what
+// its history collects (the processors of a later step read valid ids there).  All n rows done: the results go to the host block (result j at
+// row b n + j), bs.done[b] = 1.  Every path ends in publish_step, as beam_step_kernel's do.
+template <bool TOPK>
+__global__ __launch_bounds__(256) void sample_step_kernel(const float* __restrict__ st_max, const float* __restrict__ st_sum,
+                                                          const float* __restrict__ st_val, const int* __restrict__ st_idx,
+                                                          BeamState bs, RowMeta rm, int P, SampleCfg cfg, SampleP sp) {
+  __shared__ int s_tok[MAX_R]; __shared__ float s_sc[MAX_R]; __shared__ int s_len[MAX_R]; __shared__ int s_ndone;
+  const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int n = cfg.beam, NC = cfg.n_cand, V = cfg.n_vocab, r0 = b * n;
+  const int done_b = bs.done[b];
+  const int step = bs.step_u[b];
+  if (done_b) { if (tid == 0) publish_step(bs); return; }
+  const unsigned long long seed = sp.seeds[b];
+  const unsigned k0 = (unsigned)seed, k1 = (unsigned)(seed >> 32);
+  if (tid == 0) s_ndone = 0;
+#pragma unroll
+  for (int j2 = 0; j2 < 2; ++j2) {
+    const int j = wave + 4 * j2;
+    if (j >= n) continue;                      // (wave-uniform)
+    const int mrow = r0 + j;
+    const float smx = st_max[mrow * STAT_SUB + lane], ssm = st_sum[mrow * STAT_SUB + lane];
+    int tok; float xw;
+    if constexpr (!TOPK) {
+      const size_t e = ((size_t)mrow * STAT_SUB + lane) * 2;
+      const float pv = st_val[e], xv = st_val[e + 1];
+      int ix = st_idx[e]; ix = ix > V - 1 ? V - 1 : ix;
+      const u64 mine = sel_key(pv, ix);
+      const u64 best = wave_max_key(mine);
+      tok = key_index(best);
+      xw = wave_max(mine == best ? xv : -INFINITY);
+    } else {
+      constexpr int PSL = MAX_CAND;            // 64 sub-chunks x NC <= 16 candidates = 16 entries per lane
+      const int total = STAT_SUB * NC;
+      u64 pk[PSL]; u64 lbest = 0ull;
+#pragma unroll
+      for (int u = 0; u < PSL; ++u) {
+        const int e = lane + 64 * u, ce = e < total ? e : total - 1;       // clamped address, masked by select
+        const float v = st_val[(size_t)mrow * total + ce]; int ix = st_idx[(size_t)mrow * total + ce];
+        ix = ix > V - 1 ? V - 1 : ix;
+        pk[u] = e < total ? sel_key(v, ix) : 0ull;
+        lbest = key_max(lbest, pk[u]);
+      }
+      u64 pbest = 0ull; xw = -INFINITY;
+      for (int rnd = 0; rnd < NC; ++rnd) {
+        const u64 wb = wave_max_key(lbest);
+        const float x = key_value(wb); int t = wb ? key_index(wb) : 0; t = t < 0 ? 0 : (t > V - 1 ? V - 1 : t);      // (nothing outside the row's noise is ever addressed)
+        const unsigned w = sp.noise ? sp.noise[(size_t)mrow * V + t] : philox4x32_10_w0((unsigned)t, (unsigned)step, (unsigned)j, 0u, k0, k1);
+        const u64 cand = wb ? sel_key(gumbel_perturb(x, w, sp.T), t) : 0ull;
+        xw = cand > pbest ? x : xw; pbest = key_max(pbest, cand);
+#pragma unroll
+        for (int u = 0; u < PSL; ++u) pk[u] = pk[u] == wb ? 0ull : pk[u];
+        u64 tt[PSL];
+#pragma unroll
+        for (int u = 0; u < PSL; ++u) tt[u] = pk[u];
+#pragma unroll
+        for (int w2 = PSL / 2; w2 >= 1; w2 >>= 1)
+#pragma unroll
+          for (int u = 0; u < w2; ++u) tt[u] = key_max(tt[u], tt[u + w2]);
+        lbest = tt[0];
+      }
+      tok = pbest ? key_index(pbest) : V - 1;
+    }
+    const float M_ = wave_max(smx);
+    const float S = wave_sum(smx > -INFINITY ? ssm * __expf(smx - M_) : 0.f);
+    const float lse = M_ + logf(S);
+    if (lane == 0) { s_tok[j] = tok; s_sc[j] = __fdiv_rn(xw - lse, sp.T); }
+  }
+  __syncthreads();
+  const bool is_last = step + 1 >= cfg.max_new;
+  const int npos = P - 1 + step + 1;           // cache positions valid after this step
+  if (tid < n) {
+    const int row = r0 + tid;
+    int rd = bs.row_done[row];
+    int tok = cfg.eot;
+    if (!rd) {
+      tok = s_tok[tid];
+      const float cum = bs.cum[row] + s_sc[tid];
+      bs.cum[row] = cum;
+      const bool eos = tok == cfg.eot;
+      if (eos || is_last) {
+        const int len = eos ? step : step + 1;   // EOS is not part of the hypothesis
+        float s = cum;
+        if (cfg.length_penalty != 0.f) s /= powf((float)len, cfg.length_penalty);
+        bs.out_len[row] = len; bs.out_score[row] = s; bs.row_done[row] = 1; rd = 1;
+      }
+    }
+    bs.alive[(size_t)row * cfg.max_new + step] = tok;      // (step < max_new: the max_new-th step ends every row)
+    bs.parent[row] = (step == 0) ? r0 : row;             // the merged prefill + first step left the prompt's K/V in the utterance's first slot
+    { int* tr = bs.traj + ((size_t)(b * 256 + step) * MAX_R + tid) * 2; tr[0] = tok; tr[1] = tid; }
+    rm.tok[row] = rd ? cfg.eot : tok;
+    rm.pos[row] = npos;
+    rm.slot[row] = row;
+    s_len[tid] = bs.out_len[row];
+    if (rd) atomicAdd(&s_ndone, 1);
+  }
+  __syncthreads();
+  if (s_ndone >= n) {
+    for (int j = 0; j < n; ++j) {
+      const int row = r0 + j, len = s_len[j];
+      const int* src = bs.alive + (size_t)row * cfg.max_new;
+      int* hids = hp_out_ids(bs.host) + (size_t)row * cfg.max_new;
+      for (int t = tid; t < len; t += 256) { const int v = src[t]; bs.out_ids[(size_t)row * cfg.max_new + t] = v; hids[t] = v; }
+      if (tid == 0) { hp_out_len(bs.host)[row] = len; hp_out_score(bs.host)[row] = bs.out_score[row]; }
+    }
+    if (tid == 0) bs.done[b] = 1;
+    __threadfence_system();
+    __syncthreads();
+    if (tid == 0) { atomicAdd(bs.all_done, 1); publish_step(bs); }
+    return;
+  }
+  if (tid == 0) bs.step_u[b] = step + 1;
+  __syncthreads();
+  if (tid == 0) publish_step(bs);
+}
+int launch_sample_step(hipStream_t st, const float* st_max, const float* st_sum, const float* st_val, const int* st_idx,
+                       const BeamState& bs, const RowMeta& rm, int B, int P, const SampleCfg& cfg, const SampleP& sp) {
+  const bool whole = sp.topk < 0;
+  if (cfg.beam < 1 || cfg.beam > MAX_R || B * cfg.beam > HP_MAXB || cfg.max_new > 256 || cfg.n_vocab > (1 << 20) || !sp.seeds || !(sp.T > 0.f) ||
+      (whole ? cfg.n_cand != 2 : (sp.topk < 2 || sp.topk > MAX_CAND || cfg.n_cand != sp.topk))) { set_error("sample_step: config out of range"); return WIS_E_UNSUPPORTED; }
+  if (whole) hipLaunchKernelGGL(sample_step_kernel<false>, dim3(B), dim3(256), 0, st, st_max, st_sum, st_val, st_idx, bs, rm, P, cfg, sp);
+  else hipLaunchKernelGGL(sample_step_kernel<true>, dim3(B), dim3(256), 0, st, st_max, st_sum, st_val, st_idx, bs, rm, P, cfg, sp);
   return WIS_OK;
 }
 

@@ -17,7 +17,36 @@ struct SampleCtx {
   bool ts; int ts_max_init;      // Whisper's timestamp rules (prompts without <|notimestamps|>): a pre-pass ahead of the sampling statistics of every step
   float rep_pen = 1.f; int rep_ngram = 0;      // repetition_penalty / no_repeat_ngram_size (1 / 0: off): a pre-pass that patches the logits rows, ahead of everything else
   bool rep() const { return rep_pen != 1.f || rep_ngram != 0; }
+  SampleP sp;                    // random sampling (topk 0: off): sample_step_kernel stands in beam_step_kernel's place, `beam` counts the utterance's samples
+  int n_res = 1;                 // results per utterance (num_hypotheses)
+  bool sampling() const { return sp.topk != 0; }
 };
+// sampling_topk / sampling_temperature / num_hypotheses of a call, resolved (0 in the C struct: off / 1 / 1) - or refused.  *rows = decoder rows per
+// utterance: the beams of a search, the samples of a sampled decode.  single: an entry point whose outputs hold one hypothesis per utterance
+static int resolve_sample_opts(const wis_gen_opts_t* o, bool single, bool drafted, SampleCtx* g, int* rows) {
+  const int k = o->sampling_topk, beam = o->beam_size < 1 ? 1 : o->beam_size;
+  const float T = o->sampling_temperature;
+  const int n = o->num_hypotheses == 0 ? 1 : o->num_hypotheses;
+  const bool on = !(k == 0 || k == 1);
+  if (drafted && (on || (T != 0.f && T != 1.f) || n != 1)) { set_error("sampling_topk / sampling_temperature / num_hypotheses: not available for drafted decodes"); return WIS_E_UNSUPPORTED; }
+  if (k < -1) { set_error("sampling_topk %d: -1 (whole vocabulary), 0 or 1 (off), 2 .. %d", k, MAX_CAND); return WIS_E_ARG; }
+  if (k > MAX_CAND) { set_error("sampling_topk %d: the engine samples from the whole vocabulary (-1) or from at most %d candidates", k, MAX_CAND); return WIS_E_UNSUPPORTED; }
+  if (!std::isfinite(T) || T < 0.f) { set_error("sampling_temperature %g: a finite value > 0 (0: 1)", (double)T); return WIS_E_ARG; }
+  if (n < 1 || n > MAX_R) { set_error("num_hypotheses %d outside [1, %d]", n, MAX_R); return WIS_E_ARG; }
+  if (on && beam > 1) { set_error("sampling applies at beam_size 1 (got beam_size %d)", beam); return WIS_E_ARG; }
+  if (!on && n > beam) { set_error("num_hypotheses %d: a search at beam_size %d returns at most %d (more at beam_size 1 needs sampling)", n, beam, beam); return WIS_E_ARG; }
+  if (single && n > 1) { set_error("num_hypotheses %d: this entry point returns one hypothesis per utterance (wis_generate_n / wis_debug_search_n)", n); return WIS_E_ARG; }
+  g->sp = SampleP();
+  g->sp.topk = on ? k : 0; g->sp.T = T == 0.f ? 1.f : T;
+  g->n_res = n;
+  *rows = on ? n : beam;
+  return WIS_OK;
+}
+// ... and what they change in the sampling kernels' configuration (make_sample_cfg ran for `rows` rows per utterance)
+static void apply_sample_opts(wis_model* m, SampleCtx* g) {
+  if (g->sampling()) { g->sc.n_cand = g->sp.topk < 0 ? 2 : g->sp.topk; g->sp.seeds = m->d_seeds; }
+  else if (g->n_res > 1 && WIS_EARLY_EXIT_NUM_HYPOTHESES) g->sc.early_exit_hyps = g->n_res;      // CTranslate2: hypotheses.size() >= num_hypotheses
+}
 // repetition_penalty / no_repeat_ngram_size of a call, resolved (0 in the C struct means "off" for both) - or refused
 static int resolve_rep_opts(const wis_gen_opts_t* o, SampleCtx* g) {
   const float p = o->repetition_penalty; const int n = o->no_repeat_ngram_size;
@@ -30,6 +59,7 @@ static int resolve_rep_opts(const wis_gen_opts_t* o, SampleCtx* g) {
 struct GenCtx : SampleCtx {
   const float* input; const int32_t* prompt; const wis_gen_opts_t* o;
   const int32_t *draft, *draft_org; int n_draft;
+  const uint64_t* seeds;         // sampled decode: one Philox key per utterance, or null (all 0)
   int max_new; float patience;
   std::chrono::steady_clock::time_point t0;      // total_ms counts from here: the shape is resolved, nothing is enqueued yet
   int sot_row;                   // no_speech_prob: the prompt row that reads <|startoftranscript|> (the same in every utterance of the batch); -1: not asked
@@ -41,13 +71,16 @@ struct GenCtx : SampleCtx {
 // the trajectory of an earlier SEARCH (wis_last_trajectory)
 // None of the checks depends on device state: a refused call has enqueued nothing.
 static int make_gen_ctx(wis_model* m, const float* input, int B, const int32_t* prompt, int P, const wis_gen_opts_t* o,
-                        const int32_t* draft, int n_draft, const int32_t* draft_org, GenCtx* out) {
+                        const int32_t* draft, int n_draft, const int32_t* draft_org, const uint64_t* seeds, bool single, GenCtx* out) {
   const wis_config_t& c = m->cfg;
   GenCtx& g = *out;
   g.m = m; g.st = m->st; g.input = input; g.prompt = prompt; g.o = o; g.draft = draft; g.draft_org = draft_org; g.n_draft = n_draft; g.B = B; g.P = P;
-  const int beam = g.beam = o->beam_size < 1 ? 1 : o->beam_size;
+  g.seeds = seeds;
+  int rows = 1;
+  WIS_RET(resolve_sample_opts(o, single, draft != nullptr, &g, &rows));
+  const int beam = g.beam = rows;
   WIS_RET(check_batch(m, B, beam));
-  WIS_RET(check_patience(beam, o->patience));
+  if (!g.sampling()) WIS_RET(check_patience(beam, o->patience));
   if (P < 1 || P > 16 || B * P > MAX_ROWS) { set_error("prompt length %d unsupported (1..16, B*P <= %d)", P, MAX_ROWS); return WIS_E_UNSUPPORTED; }
   int max_new = o->max_new_tokens > 0 ? o->max_new_tokens : std::min(c.n_text_ctx / 2, c.n_text_ctx - P);
   if (max_new > MAX_STEPS) max_new = MAX_STEPS;
@@ -57,6 +90,7 @@ static int make_gen_ctx(wis_model* m, const float* input, int B, const int32_t* 
   WIS_RET(resolve_rep_opts(o, &g));
   g.t0 = std::chrono::steady_clock::now();
   g.sc = make_sample_cfg(m, o, beam, max_new, &g.patience);
+  apply_sample_opts(m, &g);
   g.bias_all = o->suppress_default ? m->bias_all : nullptr;
   const bool drafting = g.drafting = draft != nullptr && n_draft > 0;
   const bool beam_draft = g.beam_draft = drafting && draft_org != nullptr;
@@ -84,7 +118,8 @@ static int make_gen_ctx(wis_model* m, const float* input, int B, const int32_t* 
 // (the prefill's ~230 launches are issued while the encoder runs instead of after two stream drains)
 static int stage_search(const GenCtx& g) {
   wis_model* m = g.m; const int B = g.B, P = g.P, beam = g.beam;
-  WIS_RET(init_beam_state(m, B, beam));
+  WIS_RET(init_beam_state(m, B, beam, g.sampling(), g.sampling() ? beam : g.n_res));
+  if (g.sampling()) WIS_RET(upload_seeds(m, g.seeds, B));
   m->last_B = B; m->last_beam = beam;
   if (!g.drafting || g.beam_draft) {
     std::vector<int> tok(B * P), pos(B * P), slot(B * P), ls(B * P);
@@ -139,9 +174,15 @@ static int sampling_tail(const SampleCtx& g, LogitRows rows, int flags) {
   unsigned long long* prof = (WIS_TAPS && (flags & TAIL_TAPS)) ? m->d_prof + (size_t)c.n_dec_layers * 8 * 16 : nullptr;
   if (g.rep()) WIS_RET(launch_rep_rules(st, m->logits, m->bs, g.B, g.sc, g.rep_pen, g.rep_ngram, lr_b, lr_j, lr_off));
   if (g.ts) WIS_RET(launch_ts_rules(st, m->logits, g.bias_all, m->bias_begin, m->bs, g.B, g.sc, c.no_timestamps, g.ts_max_init, lr_b, lr_j, lr_off, m->ts_desc));
+  if (g.sampling()) {      // statistics (whole vocabulary: perturbed) -> sample step; every row continues itself: the cache moves only behind the prompt pass
+    WIS_RET(launch_logit_stats(st, m->logits, g.bias_all, m->bias_begin, m->bs.step_u, m->st_max, m->st_sum, m->st_val, m->st_idx, g.B, g.sc, lr_b, lr_j, lr_off, nullptr,
+                               nullptr, g.ts ? m->ts_desc : nullptr, &g.sp));
+    WIS_RET(launch_sample_step(st, m->st_max, m->st_sum, m->st_val, m->st_idx, m->bs, m->rm, g.B, g.P, g.sc, g.sp));
+  } else {
   WIS_RET(launch_logit_stats(st, m->logits, g.bias_all, m->bias_begin, m->bs.step_u, m->st_max, m->st_sum, m->st_val, m->st_idx, g.B, g.sc, lr_b, lr_j, lr_off, prof ? prof + 16 : nullptr,
                              nullptr, g.ts ? m->ts_desc : nullptr));
-  WIS_RET(launch_beam_step(st, m->st_max, m->st_sum, m->st_val, m->st_idx, m->bs, m->rm, g.B, g.P, c.n_text_ctx, g.sc, prof));
+  WIS_RET(launch_beam_step(st, m->st_max, m->st_sum, m->st_val, m->st_idx, m->bs, m->rm, g.B, g.P, c.n_text_ctx, g.sc, prof, g.n_res));
+  }
   if (!(flags & TAIL_NO_CACHE)) WIS_RET(launch_kv_reorder(st, m->kc_all, m->vc_all, m->kv_layer_stride, c.n_dec_layers, m->bs, g.B, g.beam, g.P, c.n_text_ctx, c.d_model));
   return WIS_OK;
 }
@@ -389,7 +430,7 @@ struct StepGraph {
   }
   int one_step() const {
     WIS_RET(dec_forward(g.m, g.B * g.beam, g.beam, g.B, true, g.beam, 1));
-    return sampling_tail(g, {g.beam, 1, 0}, TAIL_TAPS);
+    return sampling_tail(g, {g.beam, 1, 0}, TAIL_TAPS | (g.sampling() ? TAIL_NO_CACHE : 0));      // (a sample's row continues itself: nothing to reorder after the first step)
   }
   int graph_for(int nb, hipGraphExec_t* out) const {
     wis_model* m = g.m; const SampleCfg& sc = g.sc;
@@ -399,6 +440,7 @@ struct StepGraph {
     key.sa_nb = nb;
     key.timestamps = g.ts ? 1 : 0; key.max_init = g.ts ? g.ts_max_init : 0;
     key.rep_pen = g.rep_pen == 1.f ? 0.f : g.rep_pen; key.rep_ngram = g.rep_ngram;      // (off: the zeroes of a key that never knew the fields)
+    key.samp_topk = g.sp.topk; key.samp_T = g.sampling() ? g.sp.T : 0.f; key.n_hyp = g.n_res > 1 ? g.n_res : 0;      // (the seeds are device memory: no part of the key)
     auto it = m->graphs.find(key);
     if (it != m->graphs.end()) { *out = it->second; return WIS_OK; }
     hipGraph_t graph = nullptr; hipGraphExec_t ge = nullptr;
@@ -533,9 +575,9 @@ static void results_from_verification(const GenCtx& g, const Seed& sd, int32_t* 
 static int results_from_record(const GenCtx& g, int32_t* out_ids, int32_t* out_len, float* out_score) {
   const wis_model* m = g.m; const int max_new = g.max_new;
   const int* hl = hp_out_len(m->h_prog); const float* hs = hp_out_score(m->h_prog); const int* hi = hp_out_ids(m->h_prog);
-  for (int b = 0; b < g.B; ++b) {
+  for (int b = 0; b < g.B * g.n_res; ++b) {      // (result i of utterance u at u n_res + i)
     int n = hl[b];
-    if (n < 0 || n > max_new) { set_error("decode result of utterance %d has length %d outside [0, %d]", b, n, max_new); return WIS_E_STATE; }
+    if (n < 0 || n > max_new) { set_error("decode result %d of utterance %d has length %d outside [0, %d]", b % g.n_res, b / g.n_res, n, max_new); return WIS_E_STATE; }
     out_len[b] = n;
     for (int t = 0; t < max_new; ++t) out_ids[(size_t)b * max_new + t] = t < n ? hi[(size_t)b * max_new + t] : 0;
     if (out_score) out_score[b] = hs[b];
@@ -576,14 +618,15 @@ static void record_timing(const GenCtx& g, const LoopResult& lr) {
 // accepted: draft tokens (wis_generate_draft) / steps (wis_generate_draft_beam) verified
 static int generate_impl(wis_model_t* m, const float* input, int B, const int32_t* prompt, int P,
                  const wis_gen_opts_t* o, int32_t* out_ids, int32_t* out_len, float* out_score, bool* retry,
-                 const int32_t* draft = nullptr, int n_draft = 0, int* accepted = nullptr, const int32_t* draft_org = nullptr) {
+                 const int32_t* draft = nullptr, int n_draft = 0, int* accepted = nullptr, const int32_t* draft_org = nullptr,
+                 const uint64_t* seeds = nullptr, bool single = true) {
   *retry = false;
   if (accepted) *accepted = 0;
   m->nsp_B = 0;
   WIS_HIP_CHECK(hipSetDevice(m->device));
   SpinClaim claim(m, B);
   GenCtx g;
-  WIS_RET(make_gen_ctx(m, input, B, prompt, P, o, draft, n_draft, draft_org, &g));
+  WIS_RET(make_gen_ctx(m, input, B, prompt, P, o, draft, n_draft, draft_org, seeds, single, &g));
   hipStream_t st = g.st;
   WIS_RET(stage_search(g));
   WIS_RET(front_half(g));
@@ -616,7 +659,7 @@ static int generate_impl(wis_model_t* m, const float* input, int B, const int32_
   }
   if (sd.spec_done) { results_from_verification(g, sd, out_ids, out_len, out_score); lr.from_host = true; lr.decode_ms_dev = 0.f; }
   else if (lr.from_host) WIS_RET(results_from_record(g, out_ids, out_len, out_score));
-  else WIS_RET(results_from_device(m, B, g.max_new, out_ids, out_len, out_score));
+  else WIS_RET(results_from_device(m, B * g.n_res, g.max_new, out_ids, out_len, out_score));
   record_timing(g, lr);
   if (lr.steps > lr.needed) { claim.defer(st); m->overrun_left = true; }      // an over-run step is still queued: its combiners keep their share of the spin budget until it has run
   if (g.sot_row >= 0) m->nsp_B = B;
@@ -626,10 +669,11 @@ static int generate_impl(wis_model_t* m, const float* input, int B, const int32_
 // runs the call, and once more if the granule hand-off gave up: the second run takes the ticket hand-off (spin_off is set), which cannot time out
 static int generate_with_retry(const char* who, wis_model_t* m, const float* input, int B, const int32_t* prompt, int P, const wis_gen_opts_t* o,
                                int32_t* out_ids, int32_t* out_len, float* out_score,
-                               const int32_t* draft = nullptr, int n_draft = 0, int* accepted = nullptr, const int32_t* draft_org = nullptr) {
+                               const int32_t* draft = nullptr, int n_draft = 0, int* accepted = nullptr, const int32_t* draft_org = nullptr,
+                               const uint64_t* seeds = nullptr, bool single = true) {
   bool retry = false;
   for (int attempt = 0; attempt < 2; ++attempt) {
-    WIS_RET(generate_impl(m, input, B, prompt, P, o, out_ids, out_len, out_score, &retry, draft, n_draft, accepted, draft_org));
+    WIS_RET(generate_impl(m, input, B, prompt, P, o, out_ids, out_len, out_score, &retry, draft, n_draft, accepted, draft_org, seeds, single));
     if (!retry) return WIS_OK;
   }
   set_error("%s: hand-off flag raised without the granule path", who);
@@ -645,11 +689,19 @@ int wis_generate(wis_model_t* m, const float* input, int B, const int32_t* promp
   return generate_with_retry("wis_generate", m, input, B, prompt, P, o, out_ids, out_len, out_score);
 }
 
+int wis_generate_n(wis_model_t* m, const float* input, int B, const int32_t* prompt, int P, const wis_gen_opts_t* o, const uint64_t* seeds,
+                   int32_t* out_ids, int32_t* out_len, float* out_score) {
+  if (!m || !input || !prompt || !o || !out_ids || !out_len) { set_error("wis_generate_n: bad argument"); return WIS_E_ARG; }
+  WIS_ENTER(m, "wis_generate_n")
+  return generate_with_retry("wis_generate_n", m, input, B, prompt, P, o, out_ids, out_len, out_score, nullptr, 0, nullptr, nullptr, seeds, false);
+}
+
 int wis_generate_draft(wis_model_t* m, const float* input, const int32_t* prompt, int P, const wis_gen_opts_t* o,
                        const int32_t* draft, int n_draft, int32_t* out_ids, int32_t* out_len, float* out_score, int32_t* accepted) {
   if (!m || !input || !prompt || !o || !out_ids || !out_len || (n_draft > 0 && !draft) || n_draft < 0) { set_error("wis_generate_draft: bad argument"); return WIS_E_ARG; }
   if (o->timestamps) { set_error("wis_generate_draft: timestamps are not available for drafted decodes"); return WIS_E_UNSUPPORTED; }
   if ((o->repetition_penalty != 0.f && o->repetition_penalty != 1.f) || o->no_repeat_ngram_size != 0) { set_error("wis_generate_draft: repetition_penalty / no_repeat_ngram_size are not available for drafted decodes"); return WIS_E_UNSUPPORTED; }
+  if ((o->sampling_topk != 0 && o->sampling_topk != 1) || (o->sampling_temperature != 0.f && o->sampling_temperature != 1.f) || (o->num_hypotheses != 0 && o->num_hypotheses != 1)) { set_error("wis_generate_draft: sampling_topk / sampling_temperature / num_hypotheses are not available for drafted decodes"); return WIS_E_UNSUPPORTED; }
   WIS_ENTER(m, "wis_generate_draft")
   int acc = 0;
   WIS_RET(generate_with_retry("wis_generate_draft", m, input, 1, prompt, P, o, out_ids, out_len, out_score, draft, n_draft, &acc));
@@ -662,6 +714,7 @@ int wis_generate_draft_beam(wis_model_t* m, const float* input, const int32_t* p
   if (!m || !input || !prompt || !o || !out_ids || !out_len || n_steps < 0 || (n_steps > 0 && (!draft_tok || !draft_org))) { set_error("wis_generate_draft_beam: bad argument"); return WIS_E_ARG; }
   if (o->timestamps) { set_error("wis_generate_draft_beam: timestamps are not available for drafted decodes"); return WIS_E_UNSUPPORTED; }
   if ((o->repetition_penalty != 0.f && o->repetition_penalty != 1.f) || o->no_repeat_ngram_size != 0) { set_error("wis_generate_draft_beam: repetition_penalty / no_repeat_ngram_size are not available for drafted decodes"); return WIS_E_UNSUPPORTED; }
+  if ((o->sampling_topk != 0 && o->sampling_topk != 1) || (o->sampling_temperature != 0.f && o->sampling_temperature != 1.f) || (o->num_hypotheses != 0 && o->num_hypotheses != 1)) { set_error("wis_generate_draft_beam: sampling_topk / sampling_temperature / num_hypotheses are not available for drafted decodes"); return WIS_E_UNSUPPORTED; }
   WIS_ENTER(m, "wis_generate_draft_beam")
   int acc = 0;
   WIS_RET(generate_with_retry("wis_generate_draft_beam", m, input, 1, prompt, P, o, out_ids, out_len, out_score, n_steps > 0 ? draft_tok : nullptr, n_steps, &acc,

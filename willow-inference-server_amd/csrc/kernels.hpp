@@ -161,11 +161,21 @@ struct SampleCfg {
 #define WIS_EARLY_EXIT_NUM_HYPOTHESES 1
 #endif
 constexpr int STAT_SUB = 64;      // sub-chunks per logits row (one wave each): statistics and top-n_cand candidates per sub-chunk
+// Random sampling (include/wis_hip.h states the rule): what the sampling kernels take besides SampleCfg.  An utterance's cfg.beam rows are its
+// samples.  topk < 0: the whole vocabulary - the statistics kernel perturbs every value and leaves per sub-chunk {best perturbed value, that entry's
+// unperturbed logit} in st_val and its id in st_idx (cfg.n_cand = 2 is the layout); topk >= 2: the pool stays unperturbed (cfg.n_cand = topk per
+// sub-chunk), the sample step selects and perturbs.  topk = 0: off.
+struct SampleP {
+  int topk = 0; float T = 1.f;
+  const unsigned long long* seeds = nullptr;      // device [B]: Philox key per utterance (written at the start of the call: never a captured value)
+  const unsigned* noise = nullptr;                // device [rows][n_vocab] (wis_debug_search_n's table) in place of the Philox words, or null
+};
 int launch_logit_stats(hipStream_t st, const float* logits, const float* bias_all, const float* bias_begin, const int* step_u,
                        float* st_max, float* st_sum, float* st_val, int* st_idx, int B, const SampleCfg& cfg,
                        int lr_b, int lr_j, int lr_off, unsigned long long* prof = nullptr,    // logits row of (b, j) = b*lr_b + j*lr_j + lr_off
                        const int* rowmap = nullptr,       // ... or b*lr_b + rowmap[j]*lr_j + lr_off (device table: draft verification of a beam search)
-                       const int* ts_desc = nullptr);     // timestamp form: the ranges launch_ts_rules left per row are masked too
+                       const int* ts_desc = nullptr,      // timestamp form: the ranges launch_ts_rules left per row are masked too
+                       const SampleP* sp = nullptr);      // whole-vocabulary sampling (sp->topk < 0): the perturbed form
 // Whisper's timestamp rules for prompts without <|notimestamps|> (dec_kernels.hip ts_rules_kernel): per live row, the masked ranges
 // of the step (+ the decision flag, the step) -> ts_desc [B*beam][TS_DESC_INTS]; rows as launch_logit_stats reads them.
 // max_init < 0: no cap on the first timestamp
@@ -196,6 +206,7 @@ struct BeamState {
   unsigned* tick;                 // device [4]: {workgroups of beam_step_kernel that ended since init, call generation, step at which all_done reached B, -}
   const unsigned* giveup;         // word 0 of the cross-attention hand-off's epoch block (a combiner's bounded spin ran out)
   unsigned long long* host;       // device address of the HOST-mapped (fine-grained) progress block, layout HP_* below
+  int* row_done;                  // [B*beam] sampled decodes: the sample of this row has finished (its result stands, the row is fed EOT)
   int* traj;                      // [B][256 steps][MAX_R][2]: (token, beam slot it continued from) of every live beam after each step - the search's
                                   // trajectory, what a later call verifies as its DRAFT (wis_last_trajectory / wis_generate_draft_beam)
 };
@@ -206,7 +217,7 @@ enum { HP_REC = 0,          // (generation << 48) | (steps completed << 32) | (g
        HP_STAMP = 2,        // ... at the end of the latest beam step
        HP_DONE_STEP = 3,    // steps completed when the last utterance finished (0 until then)
        HP_DONE_STAMP = 4,   // constant clock at that moment
-       HP_WORDS = 8,        // results follow: int out_len[HP_MAXB], float out_score[HP_MAXB], int out_ids[HP_MAXB][256]
+       HP_WORDS = 8,        // results follow: int out_len[HP_MAXB], float out_score[HP_MAXB], int out_ids[HP_MAXB][256]; result i of utterance b at b n + i (n results per utterance)
        HP_MAXB = MAX_ROWS };
 constexpr size_t HP_BYTES = HP_WORDS * 8 + (size_t)HP_MAXB * 8 + (size_t)HP_MAXB * 256 * 4;
 __host__ __device__ inline int* hp_out_len(unsigned long long* hp) { return reinterpret_cast<int*>(hp + HP_WORDS); }
@@ -215,7 +226,12 @@ __host__ __device__ inline int* hp_out_ids(unsigned long long* hp) { return rein
 // after a beam step: every live beam's KV rows (all layers, positions < P - 1 + step) become a copy of its parent's
 int launch_kv_reorder(hipStream_t st, f16* kc, f16* vc, size_t layer_stride, int L, const BeamState& bs, int B, int beam, int P, int ctx, int d);
 int launch_beam_step(hipStream_t st, const float* st_max, const float* st_sum, const float* st_val, const int* st_idx,
-                     const BeamState& bs, const RowMeta& rm, int B, int P, int ctx, const SampleCfg& cfg, unsigned long long* prof = nullptr);
+                     const BeamState& bs, const RowMeta& rm, int B, int P, int ctx, const SampleCfg& cfg, unsigned long long* prof = nullptr,
+                     int n_best = 1);      // results per utterance: the n_best best finished hypotheses at b n_best + i (bs.out_*, the host block)
+// the sampled decode's step (dec_kernels.hip sample_step_kernel), in beam_step's place: per sample row the Gumbel-max draw from what
+// launch_logit_stats left, score, history, per-row done flag; the utterance ends when all its rows have (or at max_new)
+int launch_sample_step(hipStream_t st, const float* st_max, const float* st_sum, const float* st_val, const int* st_idx,
+                       const BeamState& bs, const RowMeta& rm, int B, int P, const SampleCfg& cfg, const SampleP& sp);
 // draft verification at beam > 1 (one utterance; dec_kernels.hip draft_match_kernel / kv_gather_kernel): behind a replayed beam step, match the live set
 // it produced with the draft's entry for the step AS A SET (draft = [n_draft][MAX_R][2] in BeamState::traj's layout); vstate ints: 0 steps verified,
 // 2 window steps applied, 8.. the draft node each live beam is matched to (logit_stats rowmap), 16.. / 32.. the slots holding each beam's history

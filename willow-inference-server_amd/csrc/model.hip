@@ -141,6 +141,7 @@ struct GraphKey {
   int B, beam, P, max_new, fixed_new, suppress_blank, suppress_default, early_exit, spin, sa_nb; float lp, patience;
   int timestamps, max_init;      // the timestamp form of the step (ts_rules_kernel ahead of logit_stats_kernel<true>) and its first-timestamp cap
   float rep_pen; int rep_ngram;  // rep_rules_kernel at the head of the tail (both 0: off, no such launch)
+  int samp_topk; float samp_T; int n_hyp;      // sampled decode (sample_step_kernel in beam_step_kernel's place) / results per utterance; all 0: off, one result
   bool operator<(const GraphKey& o) const { return memcmp(this, &o, sizeof(GraphKey)) < 0; }
 };
 
@@ -180,6 +181,7 @@ struct PinnedScratch {
   int giveup;                                  // spin_gave_up: the give-up flag read back
   RowStage rows, win_rows;                     // the search's rows (every caller's default); the rows of a draft-verification window
   float beam_cum[MAX_ROWS]; unsigned beam_tick[4];      // init_beam_state
+  unsigned long long seeds[MAX_ROWS];          // upload_seeds: the Philox key of every utterance of a sampled decode
   unsigned reseed_tick[4];                     // reseed_tick: bs.tick behind a draft verification
   // wis_generate_draft: step index of the verified rows, their picks read back; then the search state `steps` ordinary steps would have left
   int vstep[MAX_ROWS], pick_tok[MAX_ROWS]; float pick_lp[MAX_ROWS];
@@ -239,6 +241,7 @@ struct wis_model {
   RowMeta rm; BeamState bs;
   RowMeta rm_win;               // row metadata of a draft-verification window (wis_generate_draft_beam): the search's own rows (rm, written by beam_step_kernel) stay untouched
   float *st_max, *st_sum, *st_val; int* st_idx;
+  unsigned long long* d_seeds = nullptr;      // sampled decodes: Philox key per utterance [MAX_ROWS], written at the start of every call (SampleP::seeds)
   int* ts_desc = nullptr;       // timestamp rules: masked ranges per live row [MAX_ROWS][TS_DESC_INTS] (ts_rules_kernel -> logit_stats_kernel<true>)
   float* d_nsp = nullptr;       // no_speech_prob per utterance of the last wis_generate that asked for it
   int nsp_B = 0;                // ... its batch size; 0: the last call did not ask (wis_last_no_speech_prob answers WIS_E_STATE)
@@ -635,6 +638,7 @@ int alloc_buffers(wis_model* m) {
   WIS_RET(dalloc(m, &m->bs.cum, slots));
   WIS_RET(dalloc(m, &m->bs.alive, (size_t)slots * max_new));
   WIS_RET(dalloc(m, &m->bs.parent, (size_t)slots));
+  WIS_RET(dalloc(m, &m->bs.row_done, (size_t)slots)); WIS_RET(dalloc(m, &m->d_seeds, (size_t)MAX_ROWS));
   WIS_RET(dalloc(m, &m->bs.hyp_score, (size_t)Bm * max_hyp)); WIS_RET(dalloc(m, &m->bs.hyp_len, (size_t)Bm * max_hyp));
   WIS_RET(dalloc(m, &m->bs.hyp_tok, (size_t)Bm * max_hyp * max_new));
   WIS_RET(dalloc(m, &m->bs.all_done, 4));
@@ -643,7 +647,7 @@ int alloc_buffers(wis_model* m) {
   WIS_RET(dalloc(m, &m->bs.traj, (size_t)Bm * MAX_STEPS * MAX_R * 2));
   WIS_RET(dalloc(m, &m->d_draft, sizeof(PinnedScratch::draft) / sizeof(int))); WIS_RET(dalloc(m, &m->d_anc, sizeof(PinnedScratch::anc) / sizeof(int))); WIS_RET(dalloc(m, &m->d_vstate, DRAFT_VS_INTS)); WIS_RET(dalloc(m, &m->d_base, MAX_ROWS));
   WIS_HIP_CHECK(hipMemsetAsync(m->bs.tick, 0, 16, m->st));
-  WIS_RET(dalloc(m, &m->bs.out_ids, (size_t)Bm * max_new)); WIS_RET(dalloc(m, &m->bs.out_len, Bm)); WIS_RET(dalloc(m, &m->bs.out_score, Bm));
+  WIS_RET(dalloc(m, &m->bs.out_ids, (size_t)slots * max_new)); WIS_RET(dalloc(m, &m->bs.out_len, slots)); WIS_RET(dalloc(m, &m->bs.out_score, slots));      // (up to max_beam results per utterance)
   WIS_RET(dalloc(m, &m->st_max, (size_t)MAX_ROWS * STAT_SUB)); WIS_RET(dalloc(m, &m->st_sum, (size_t)MAX_ROWS * STAT_SUB));
   WIS_RET(dalloc(m, &m->st_val, (size_t)MAX_ROWS * STAT_SUB * MAX_CAND)); WIS_RET(dalloc(m, &m->st_idx, (size_t)MAX_ROWS * STAT_SUB * MAX_CAND));
   WIS_RET(dalloc(m, &m->ts_desc, (size_t)MAX_ROWS * TS_DESC_INTS)); WIS_RET(dalloc(m, &m->d_nsp, (size_t)MAX_ROWS));
@@ -1012,12 +1016,13 @@ int dec_forward(wis_model* m, int M, int R, int B, bool want_logits, int sstride
 }
 
 // search state of a device batch: beams tiled up front with scores [0, -inf, ...] (CT2 GPU path), counters cleared
-static int init_beam_state(wis_model* m, int B, int beam) {
+// (samples: the rows of an utterance are independent samples - every one starts live, with its own done flag; n_res results per utterance)
+static int init_beam_state(wis_model* m, int B, int beam, bool samples = false, int n_res = 1) {
   hipStream_t st = m->st;
   const int Mrows = B * beam;
   // staged in pinned memory of its own (PinnedScratch::beam_cum / beam_tick): the copies run when the stream gets there, nothing waits for them here
   float* cum = m->h_pin->beam_cum;
-  for (int r = 0; r < Mrows; ++r) cum[r] = (r % beam == 0) ? 0.f : -INFINITY;
+  for (int r = 0; r < Mrows; ++r) cum[r] = (r % beam == 0 || samples) ? 0.f : -INFINITY;
   unsigned* tk = m->h_pin->beam_tick;
   m->gen = (m->gen % 0xFFFFu) + 1u;      // 1 .. 65535: never the 0 of a cleared record
   tk[0] = 0; tk[1] = m->gen; tk[2] = 0; tk[3] = 0;
@@ -1027,7 +1032,15 @@ static int init_beam_state(wis_model* m, int B, int beam) {
   WIS_HIP_CHECK(hipMemsetAsync(m->bs.done, 0, (size_t)B * 4, st));
   WIS_HIP_CHECK(hipMemsetAsync(m->bs.n_hyp, 0, (size_t)B * 4, st));
   WIS_HIP_CHECK(hipMemsetAsync(m->bs.all_done, 0, 16, st));
-  WIS_HIP_CHECK(hipMemsetAsync(m->bs.out_len, 0, (size_t)B * 4, st));
+  WIS_HIP_CHECK(hipMemsetAsync(m->bs.out_len, 0, (size_t)B * n_res * 4, st));
+  if (samples) WIS_HIP_CHECK(hipMemsetAsync(m->bs.row_done, 0, (size_t)Mrows * 4, st));
+  return WIS_OK;
+}
+// the utterances' Philox keys of a sampled decode (seeds NULL: all 0), staged like the search counters
+static int upload_seeds(wis_model* m, const uint64_t* seeds, int B) {
+  unsigned long long* h = m->h_pin->seeds;
+  for (int b = 0; b < B; ++b) h[b] = seeds ? (unsigned long long)seeds[b] : 0ull;
+  WIS_HIP_CHECK(hipMemcpyAsync(m->d_seeds, h, (size_t)B * 8, hipMemcpyHostToDevice, m->st));
   return WIS_OK;
 }
 // decoding options -> what the sampling kernels take (CTranslate2 4.1.0 BeamSearch defaults where WIS passes none, main.py:687-693)
@@ -1043,7 +1056,7 @@ static SampleCfg make_sample_cfg(const wis_model* m, const wis_gen_opts_t* o, in
   sc.max_candidates = (int)lroundf((float)beam * patience); if (sc.max_candidates < 1) sc.max_candidates = 1;
   // CT2: allow_early_exit = patience == 1 && length_penalty == 0 && coverage_penalty == 0
   sc.allow_early_exit = (patience == 1.f && o->length_penalty == 0.f) ? 1 : 0;
-  sc.early_exit_hyps = WIS_EARLY_EXIT_NUM_HYPOTHESES ? 1 : sc.max_candidates;      // num_hypotheses is 1 at this boundary (kernels.hpp)
+  sc.early_exit_hyps = WIS_EARLY_EXIT_NUM_HYPOTHESES ? 1 : sc.max_candidates;      // num_hypotheses = 1; resolve_sample_opts (generate.hip) puts a caller's n here
   *patience_out = patience;
   return sc;
 }
@@ -1245,31 +1258,38 @@ int wis_last_trajectory(wis_model_t* m, int b, int32_t* tok, int32_t* org, int c
   return WIS_OK;
 }
 
-int wis_debug_search(wis_model_t* m, const float* logits, int n_steps, int B, const wis_gen_opts_t* o,
-                     int32_t* out_ids, int32_t* out_len, float* out_score, int32_t* out_finish_step, int32_t* out_parent) {
-  if (!m || !logits || !o || !out_ids || !out_len || n_steps < 1 || n_steps > MAX_STEPS) { set_error("wis_debug_search: bad argument"); return WIS_E_ARG; }
-  WIS_ENTER(m, "wis_debug_search")
+// wis_debug_search / wis_debug_search_n: the sampling tail over a caller's logits table (single: one hypothesis per utterance)
+static int debug_search_impl(const char* who, wis_model_t* m, const float* logits, int n_steps, int B, const wis_gen_opts_t* o, const uint64_t* seeds, const uint32_t* noise,
+                             bool single, int32_t* out_ids, int32_t* out_len, float* out_score, int32_t* out_finish_step, int32_t* out_parent) {
   WIS_HIP_CHECK(hipSetDevice(m->device));
   const wis_config_t& c = m->cfg;
-  const int beam = o->beam_size < 1 ? 1 : o->beam_size;
+  SampleCtx g;      // a search over given logits: a one-token prompt
+  int beam = 1;     // rows per utterance: beams, or the samples of a sampled decode
+  WIS_RET(resolve_sample_opts(o, single, false, &g, &beam));
   WIS_RET(check_batch(m, B, beam));
-  WIS_RET(check_patience(beam, o->patience));
+  if (!g.sampling()) WIS_RET(check_patience(beam, o->patience));
   const int max_new = o->max_new_tokens > 0 ? std::min(o->max_new_tokens, MAX_STEPS) : n_steps;
-  if (max_new > n_steps) { set_error("wis_debug_search: %d steps of logits for max_new_tokens %d", n_steps, max_new); return WIS_E_ARG; }
+  if (max_new > n_steps) { set_error("%s: %d steps of logits for max_new_tokens %d", who, n_steps, max_new); return WIS_E_ARG; }
   hipStream_t st = m->st;
   const int Mrows = B * beam, V = c.n_vocab;
   float patience;
-  SampleCtx g;      // a search over given logits: a one-token prompt
   WIS_RET(resolve_rep_opts(o, &g));
-  WIS_RET(init_beam_state(m, B, beam));
+  if (noise && !g.sampling()) { set_error("%s: a noise table without sampling", who); return WIS_E_ARG; }
+  struct DevBlock { void* p = nullptr; ~DevBlock() { if (p) hipFree(p); } } d_noise;      // one step of the noise table [Mrows][V]
+  if (noise && hipMalloc(&d_noise.p, (size_t)Mrows * V * 4) != hipSuccess) { (void)hipGetLastError(); set_error("%s: out of device memory", who); return WIS_E_NOMEM; }
+  WIS_RET(init_beam_state(m, B, beam, g.sampling(), g.sampling() ? beam : g.n_res));
+  if (g.sampling()) WIS_RET(upload_seeds(m, seeds, B));
   g.m = m; g.st = st; g.B = B; g.P = 1; g.beam = beam;
   g.sc = make_sample_cfg(m, o, beam, max_new, &patience);
+  apply_sample_opts(m, &g);
+  g.sp.noise = static_cast<const unsigned*>(d_noise.p);
   g.bias_all = o->suppress_default ? m->bias_all : nullptr;
   g.ts = o->timestamps != 0;
   g.ts_max_init = o->max_initial_timestamp_index < 0 ? -1 : o->max_initial_timestamp_index;
   std::vector<int> done(B, 0), fin(B, -1), par(Mrows);
   for (int s = 0; s < max_new; ++s) {
     WIS_HIP_CHECK(hipMemcpy2DAsync(m->logits, (size_t)m->n_vocab_pad * 4, logits + (size_t)s * Mrows * V, (size_t)V * 4, (size_t)V * 4, Mrows, hipMemcpyHostToDevice, st));
+    if (noise) WIS_HIP_CHECK(hipMemcpyAsync(d_noise.p, noise + (size_t)s * Mrows * V, (size_t)Mrows * V * 4, hipMemcpyHostToDevice, st));
     // step 0 samples every beam of an utterance from ONE row (wis_generate: the last prompt row; here row b*beam), later steps row b*beam + j
     WIS_RET(sampling_tail(g, {beam, s == 0 ? 0 : 1, 0}, TAIL_NO_CACHE));
     WIS_HIP_CHECK(hipMemcpyAsync(done.data(), m->bs.done, (size_t)B * 4, hipMemcpyDeviceToHost, st));
@@ -1280,10 +1300,24 @@ int wis_debug_search(wis_model_t* m, const float* logits, int n_steps, int B, co
     if (out_parent) for (int r = 0; r < Mrows; ++r) out_parent[(size_t)s * Mrows + r] = par[r];
     if (all) break;
   }
-  for (int b = 0; b < B; ++b) if (fin[b] < 0) { set_error("wis_debug_search: utterance %d did not finish within %d steps", b, max_new); return WIS_E_STATE; }
-  WIS_RET(results_from_device(m, B, max_new, out_ids, out_len, out_score));
+  for (int b = 0; b < B; ++b) if (fin[b] < 0) { set_error("%s: utterance %d did not finish within %d steps", who, b, max_new); return WIS_E_STATE; }
+  WIS_RET(results_from_device(m, B * g.n_res, max_new, out_ids, out_len, out_score));
   if (out_finish_step) for (int b = 0; b < B; ++b) out_finish_step[b] = fin[b];
   return WIS_OK;
+}
+
+int wis_debug_search(wis_model_t* m, const float* logits, int n_steps, int B, const wis_gen_opts_t* o,
+                     int32_t* out_ids, int32_t* out_len, float* out_score, int32_t* out_finish_step, int32_t* out_parent) {
+  if (!m || !logits || !o || !out_ids || !out_len || n_steps < 1 || n_steps > MAX_STEPS) { set_error("wis_debug_search: bad argument"); return WIS_E_ARG; }
+  WIS_ENTER(m, "wis_debug_search")
+  return debug_search_impl("wis_debug_search", m, logits, n_steps, B, o, nullptr, nullptr, true, out_ids, out_len, out_score, out_finish_step, out_parent);
+}
+
+int wis_debug_search_n(wis_model_t* m, const float* logits, int n_steps, int B, const wis_gen_opts_t* o, const uint64_t* seeds, const uint32_t* noise,
+                       int32_t* out_ids, int32_t* out_len, float* out_score, int32_t* out_finish_step, int32_t* out_parent) {
+  if (!m || !logits || !o || !out_ids || !out_len || n_steps < 1 || n_steps > MAX_STEPS) { set_error("wis_debug_search_n: bad argument"); return WIS_E_ARG; }
+  WIS_ENTER(m, "wis_debug_search_n")
+  return debug_search_impl("wis_debug_search_n", m, logits, n_steps, B, o, seeds, noise, false, out_ids, out_len, out_score, out_finish_step, out_parent);
 }
 
 int wis_debug_handoff(wis_model_t* m, int raise_flag, int* retries, int* spin_disabled) {

@@ -41,7 +41,8 @@ class GenOpts(C.Structure):
     _fields_ = [("input_kind", C.c_int32), ("beam_size", C.c_int32), ("max_new_tokens", C.c_int32), ("length_penalty", C.c_float),
                 ("patience", C.c_float), ("suppress_blank", C.c_int32), ("suppress_default", C.c_int32),
                 ("fixed_new_tokens", C.c_int32), ("queue_depth", C.c_int32), ("timestamps", C.c_int32), ("max_initial_timestamp_index", C.c_int32),
-                ("no_speech_prob", C.c_int32), ("repetition_penalty", C.c_float), ("no_repeat_ngram_size", C.c_int32)]
+                ("no_speech_prob", C.c_int32), ("repetition_penalty", C.c_float), ("no_repeat_ngram_size", C.c_int32),
+                ("sampling_topk", C.c_int32), ("sampling_temperature", C.c_float), ("num_hypotheses", C.c_int32)]
 
 
 class Timing(C.Structure):
@@ -85,6 +86,7 @@ SYMBOLS = [
     ("wis_model_device_bytes", _sz, [_vp]),
     ("wis_model_clone", _i, [_vp, C.POINTER(_vp)]),
     ("wis_generate", _i, [_vp, _vp, _i, C.POINTER(C.c_int32), _i, C.POINTER(GenOpts), C.POINTER(C.c_int32), C.POINTER(C.c_int32), _fp]),
+    ("wis_generate_n", _i, [_vp, _vp, _i, C.POINTER(C.c_int32), _i, C.POINTER(GenOpts), C.POINTER(C.c_uint64), C.POINTER(C.c_int32), C.POINTER(C.c_int32), _fp]),
     ("wis_generate_draft", _i, [_vp, _vp, C.POINTER(C.c_int32), _i, C.POINTER(GenOpts), C.POINTER(C.c_int32), _i, C.POINTER(C.c_int32), C.POINTER(C.c_int32), _fp,
                                 C.POINTER(C.c_int32)]),
     ("wis_generate_draft_beam", _i, [_vp, _vp, C.POINTER(C.c_int32), _i, C.POINTER(GenOpts), C.POINTER(C.c_int32), C.POINTER(C.c_int32), _i, C.POINTER(C.c_int32),
@@ -104,6 +106,8 @@ SYMBOLS = [
     ("wis_op_align_matrix", _i, [_i, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
     ("wis_debug_tree_logits", _i, [_vp, _vp, _i, C.POINTER(C.c_int32), _i, _i, C.POINTER(C.c_int32), C.POINTER(C.c_int32), _i, _fp]),
     ("wis_debug_search", _i, [_vp, _vp, _i, _i, C.POINTER(GenOpts), C.POINTER(C.c_int32), C.POINTER(C.c_int32), _fp, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    ("wis_debug_search_n", _i, [_vp, _vp, _i, _i, C.POINTER(GenOpts), C.POINTER(C.c_uint64), C.POINTER(C.c_uint32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), _fp,
+                                C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     ("wis_debug_handoff", _i, [_vp, _i, C.POINTER(_i), C.POINTER(_i)]),
     ("wis_last_timing", _i, [_vp, C.POINTER(Timing)]),
     ("wis_debug_phase_cycles", _i, [_vp, _i, _i, _i, C.POINTER(C.c_uint64)]),

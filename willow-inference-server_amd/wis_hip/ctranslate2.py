@@ -23,6 +23,30 @@ from . import _lib, weights as W
 from .batching import MicroBatcher
 
 
+# ---- random sampling: where the seed of an unseeded request comes from (CTranslate2 has ctranslate2.set_random_seed)
+_seed_lock = threading.Lock()
+_seed_state = None      # None: every unseeded request draws 64 bits from os.urandom; [seed, counter] after set_random_seed
+
+
+def set_random_seed(seed):
+    """ctranslate2.set_random_seed: from now on the requests that pass no `sampling_seed` draw theirs from a deterministic counter over `seed`
+    (the n-th unseeded utterance after this call always gets the same seed).  None: back to os.urandom."""
+    global _seed_state
+    with _seed_lock:
+        _seed_state = None if seed is None else [int(seed) & 0xFFFFFFFFFFFFFFFF, 0]
+
+
+def _next_seed():
+    with _seed_lock:
+        if _seed_state is None:
+            return int.from_bytes(os.urandom(8), "little")
+        _seed_state[1] += 1
+        z = (_seed_state[0] + 0x9E3779B97F4A7C15 * _seed_state[1]) & 0xFFFFFFFFFFFFFFFF      # splitmix64 of (seed, counter)
+    z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & 0xFFFFFFFFFFFFFFFF
+    z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & 0xFFFFFFFFFFFFFFFF
+    return z ^ (z >> 31)
+
+
 def get_supported_compute_types(device="cuda", device_index=0):
     buf = C.create_string_buffer(64)
     _lib.check(_lib.load().wis_supported_compute_types(device_index, buf, 64))
@@ -195,14 +219,17 @@ def _last_trajectory(r, b, beam):
 
 
 def _generate_chunk(r, mel, prompts, P, beam, max_new, lp, patience, suppress_blank, suppress_default, fixed_new, kind, device_ptr=None, draft=None, want_traj=False,
-                    timestamps=False, max_initial_timestamp_index=50, no_speech_prob=False, repetition_penalty=1.0, no_repeat_ngram_size=0):
+                    timestamps=False, max_initial_timestamp_index=50, no_speech_prob=False, repetition_penalty=1.0, no_repeat_ngram_size=0,
+                    sampling_topk=0, sampling_temperature=1.0, num_hypotheses=1, seeds=None):
     """mel: host ndarray [B, ...] - or, with device_ptr, just the batch size B of features already resident on r.device.
     draft (one utterance): token ids of an earlier hypothesis (beam 1: wis_generate_draft) or the trajectory (tok [n][beam], org [n][beam]) of
     an earlier beam search (wis_generate_draft_beam) - verified in multi-row passes before ordinary steps go on.
     want_traj: every result carries `.trajectory`, what a later call takes as its draft.
     timestamps: Whisper's timestamp rules every step (max_initial_timestamp_index None: no cap on the first timestamp);
     no_speech_prob: every result carries P(<|nospeech|>) at <|startoftranscript|> (wis_last_no_speech_prob).
-    repetition_penalty / no_repeat_ngram_size: CTranslate2's two options against looping hypotheses (include/wis_hip.h; 1 / 0: off)."""
+    repetition_penalty / no_repeat_ngram_size: CTranslate2's two options against looping hypotheses (include/wis_hip.h; 1 / 0: off).
+    sampling_topk (the ENGINE's value: 0 off, -1 whole vocabulary, 2 .. 16), sampling_temperature, num_hypotheses, seeds (one uint64 per utterance):
+    random sampling and n results per utterance (wis_generate_n); every result then carries num_hypotheses sequences and scores."""
     B = int(mel) if device_ptr is not None else mel.shape[0]
     o = _lib.GenOpts(kind, beam, max_new, lp, patience, int(bool(suppress_blank)), int(bool(suppress_default)), int(fixed_new), 0)
     if timestamps:
@@ -210,10 +237,14 @@ def _generate_chunk(r, mel, prompts, P, beam, max_new, lp, patience, suppress_bl
         o.max_initial_timestamp_index = -1 if max_initial_timestamp_index is None else int(max_initial_timestamp_index)
     o.no_speech_prob = int(bool(no_speech_prob))
     o.repetition_penalty, o.no_repeat_ngram_size = float(repetition_penalty), int(no_repeat_ngram_size)
+    n = int(num_hypotheses)
+    multi = bool(sampling_topk) or n > 1
+    if multi:
+        o.sampling_topk, o.sampling_temperature, o.num_hypotheses = int(sampling_topk), float(sampling_temperature), n
     pr = np.ascontiguousarray(np.asarray(prompts, np.int32).reshape(B, P))
-    ids = np.zeros((B, max_new), np.int32)
-    lens = np.zeros(B, np.int32)
-    scores = np.zeros(B, np.float32)
+    ids = np.zeros((B, n, max_new), np.int32)
+    lens = np.zeros((B, n), np.int32)
+    scores = np.zeros((B, n), np.float32)
     src = C.c_void_p(device_ptr) if device_ptr is not None else _lib.ptr(mel)
     i32p, lib = C.POINTER(C.c_int32), _lib.load()
     acc = None
@@ -229,13 +260,17 @@ def _generate_chunk(r, mel, prompts, P, beam, max_new, lp, patience, suppress_bl
         acc = C.c_int32(0)
         _lib.check(lib.wis_generate_draft(r.handle, src, pr.ctypes.data_as(i32p), P, C.byref(o), d.ctypes.data_as(i32p), int(d.shape[0]),
                                           ids.ctypes.data_as(i32p), lens.ctypes.data_as(i32p), scores.ctypes.data_as(C.POINTER(C.c_float)), C.byref(acc)))
+    elif multi:
+        sd = np.ascontiguousarray(np.asarray([0] * B if seeds is None else [int(x) & 0xFFFFFFFFFFFFFFFF for x in seeds], np.uint64))
+        _lib.check(lib.wis_generate_n(r.handle, src, B, pr.ctypes.data_as(i32p), P, C.byref(o), sd.ctypes.data_as(C.POINTER(C.c_uint64)), ids.ctypes.data_as(i32p),
+                                      lens.ctypes.data_as(i32p), scores.ctypes.data_as(C.POINTER(C.c_float))))
     else:
         _lib.check(lib.wis_generate(r.handle, src, B, pr.ctypes.data_as(i32p), P, C.byref(o), ids.ctypes.data_as(i32p), lens.ctypes.data_as(i32p),
                                     scores.ctypes.data_as(C.POINTER(C.c_float))))
     nsp = np.zeros(B, np.float32)
     if no_speech_prob:
         _lib.check(lib.wis_last_no_speech_prob(r.handle, B, nsp.ctypes.data_as(C.POINTER(C.c_float))))
-    out = [WhisperGenerationResult([ids[b, :lens[b]].tolist()], [float(scores[b])], float(nsp[b])) for b in range(B)]
+    out = [WhisperGenerationResult([ids[b, j, :lens[b, j]].tolist() for j in range(n)], [float(scores[b, j]) for j in range(n)], float(nsp[b])) for b in range(B)]
     if acc is not None:
         out[0].accepted_draft_tokens = int(acc.value)      # tokens (beam 1) or search steps (beam > 1) of the draft the final decode kept
     if want_traj:
@@ -250,6 +285,7 @@ MAX_BEAM = 8               # csrc/kernels.hpp MAX_R: rows per utterance (beam si
 MAX_REPLICAS_PER_DEVICE = 4   # default ceiling for inter_threads -> replicas per GPU (measured on MI355X, bench.py "concurrent_device_batches": 118 / 152 / 165 / 173 / 160 utterances/s with 1..5 batches of 8 in flight)
 MAX_PROMPT = 16            # wis_generate: prompt tokens per utterance
 MAX_HYPOTHESES = 24        # csrc/kernels.hpp MAX_HYP: finished hypotheses an utterance's search can hold
+MAX_SAMPLING_TOPK = 16     # csrc/kernels.hpp MAX_CAND: the largest sampling_topk short of the whole vocabulary
 
 
 def timestamp_prompt(prompt, special=None):
@@ -292,6 +328,53 @@ def _rep_key(key, p, n):
     return (key + (None, False, False, 50, False)[len(key) - 9:])[:14] + (p, n)
 
 
+_KEY_TAIL = (None, False, False, 50, False, 1.0, 0)      # a plain key's slots 9 .. 15: draft, trajectory, timestamps, its cap, no_speech_prob, repetition tail
+
+
+class UnsupportedOption(ValueError, NotImplementedError):
+    """A decoding option (or combination) this shim does not serve.  A ValueError like every other request error (HTTP 400 in wis_hip.server);
+    also the NotImplementedError that `sampling_topk` / `num_hypotheses` raised before they existed, for the calls that stay unserved."""
+
+
+def _check_sampling(beam_size, num_hypotheses, sampling_topk, sampling_temperature, drafted=False):
+    """-> (top-k, temperature, n) as the ENGINE takes them (include/wis_hip.h: top-k 0 off, -1 the whole vocabulary, 2 .. 16); CTranslate2's
+    sampling_topk counts 1 as off and 0 as the whole vocabulary.  Validated as the C side validates: a bad value is a ValueError.
+    This face samples from the WHOLE vocabulary only (sampling_topk=0, what the temperature fallback calls): a top-k of 2 .. 16 is served by the
+    engine (wis_generate_n / wis_debug_search_n) but answered UnsupportedOption here, as is num_hypotheses beyond what the search can return."""
+    try:
+        k, n, T = int(sampling_topk), int(num_hypotheses), float(sampling_temperature)
+        if k != float(sampling_topk) or n != float(num_hypotheses):
+            raise ValueError
+    except (TypeError, ValueError, OverflowError):
+        raise ValueError(f"sampling_topk {sampling_topk!r} / num_hypotheses {num_hypotheses!r} / sampling_temperature {sampling_temperature!r}: two integers and a number") from None
+    if k < 0 or k > MAX_SAMPLING_TOPK:
+        raise ValueError(f"sampling_topk {k} outside 0 (the whole vocabulary), 1 (off), 2..{MAX_SAMPLING_TOPK}")
+    if not (T > 0 and T != float("inf")):
+        raise ValueError(f"sampling_temperature {sampling_temperature!r} must be a finite number > 0")
+    if not 1 <= n <= MAX_BEAM:
+        raise ValueError(f"num_hypotheses {n} outside 1..{MAX_BEAM}")
+    on = k != 1
+    if k >= 2:
+        raise UnsupportedOption(f"sampling_topk {k}: this face samples from the whole vocabulary (sampling_topk=0); the engine's top-k of 2..{MAX_SAMPLING_TOPK} "
+                                "is reachable through wis_generate_n")
+    if on and int(beam_size) != 1:
+        raise ValueError(f"random sampling (sampling_topk {k}) needs beam_size 1, got {beam_size}")
+    if not on and n > int(beam_size):
+        raise UnsupportedOption(f"num_hypotheses {n} > beam_size {beam_size}" + (" (more than one hypothesis at beam_size 1 needs sampling_topk=0)" if int(beam_size) == 1 else ""))
+    if drafted and (on or n != 1):
+        raise ValueError("sampling_topk / num_hypotheses cannot be combined with draft_tokens / draft_trajectory")
+    return (0 if not on else (-1 if k == 0 else k)), (T if on else 1.0), n
+
+
+def _sample_key(key, topk, T, n):
+    """The batcher key of a sampled or n-best call: every earlier slot padded to its fixed position (_run_batch), then (top-k, temperature, n) -
+    calls with different sampling values never share a device batch; their seeds travel with the rows, so calls with different seeds do.
+    All off: the key as it is."""
+    if topk == 0 and n == 1:
+        return key
+    return (key + _KEY_TAIL[len(key) - 9:])[:16] + (topk, T, n)
+
+
 def _check_patience(beam_size, patience):
     """CTranslate2 searches until round(beam_size * patience) hypotheses have finished; the engine stores MAX_HYPOTHESES - beam_size + 1.
     A patience beyond that is a request error (it used to be clamped silently: a shorter search than CTranslate2's, other ids)."""
@@ -304,7 +387,8 @@ def _capacity(max_batch, key):
     """Utterances per device batch: the decoder handles <= MAX_DECODER_ROWS rows per pass - utterances x beam while decoding,
     utterances x P in the merged prefill + first step (wis_generate enforces B * P <= MAX_ROWS and B * beam <= MAX_ROWS)."""
     P, beam = key[0], key[1]
-    return max(1, min(max_batch, MAX_DECODER_ROWS // max(beam, 1), MAX_DECODER_ROWS // max(P, 1)))
+    rows = max(beam, key[18] if len(key) > 18 else 1, 1)      # decoder rows per utterance: its beams, or its num_hypotheses samples
+    return max(1, min(max_batch, MAX_DECODER_ROWS // rows, MAX_DECODER_ROWS // max(P, 1)))
 
 
 def _run_batch(replica, key, rows):
@@ -315,8 +399,10 @@ def _run_batch(replica, key, rows):
     tsk = dict(timestamps=ts, max_initial_timestamp_index=mi, no_speech_prob=nsp) if len(key) > 11 else {}
     if len(key) > 14:      # ... and its repetition tail
         tsk.update(repetition_penalty=key[14], no_repeat_ngram_size=key[15])
+    if len(key) > 16:      # ... and its sampling tail; the rows then carry their seeds
+        tsk.update(sampling_topk=key[16], sampling_temperature=key[17], num_hypotheses=key[18], seeds=[(r[2] if len(r) > 2 else 0) for r in rows])
     dr = (draft[1] if draft and len(rows) == 1 else None)
-    prompts = [p for _, p in rows]
+    prompts = [r[1] for r in rows]
     if kind == _lib.WIS_IN_MEL_DEV:
         # features that already live in this replica's HBM (streaming sessions: audio.MelStream.finish): one utterance goes in
         # by pointer, several are gathered device-to-device into the replica's staging block - nothing visits the host
@@ -328,12 +414,12 @@ def _run_batch(replica, key, rows):
                 if replica.stage is None or replica.stage.nbytes < len(rows) * mb:
                     replica.stage = _lib.DevBuf(max(len(rows), 8) * mb, replica.device)
                 lib = _lib.load()
-                for i, (src, _) in enumerate(rows):
+                for i, src in enumerate(r[0] for r in rows):
                     _lib.check(lib.wis_dev_copy_peer(replica.device, C.c_void_p(replica.stage.ptr.value + i * mb), replica.device, C.c_void_p(int(src)), mb))
                 ptr = replica.stage.ptr.value
             return _generate_chunk(replica, len(rows), prompts, P, beam, max_new, lp, patience, suppress_blank, suppress_default, fixed_new, kind, device_ptr=ptr,
                                    draft=dr, want_traj=want_traj, **tsk)
-    mel = np.ascontiguousarray(np.stack([m for m, _ in rows]))
+    mel = np.ascontiguousarray(np.stack([r[0] for r in rows]))
     with replica.lock:
         return _generate_chunk(replica, mel, prompts, P, beam, max_new, lp, patience, suppress_blank, suppress_default, fixed_new, kind,
                                draft=dr, want_traj=want_traj, **tsk)
@@ -463,7 +549,7 @@ class Whisper:
                  repetition_penalty=1, no_repeat_ngram_size=0, max_length=448, return_scores=False, return_no_speech_prob=False,
                  max_initial_timestamp_index=50, suppress_blank=True, suppress_tokens=(-1,), sampling_topk=1,
                  sampling_temperature=1, fixed_new_tokens=0, input_kind=_lib.WIS_IN_MEL_HOST, draft_tokens=None, draft_trajectory=None,
-                 return_trajectory=False):
+                 return_trajectory=False, sampling_seed=None):
         """`draft_tokens` (one utterance, beam_size 1): the ids of an earlier hypothesis for this audio - wis_generate_draft verifies them in
         multi-row passes and decodes on behind the accepted prefix; the result is the greedy decode of THESE features either way.
         `draft_trajectory` (one utterance, beam_size > 1): `(tok, org)` as an earlier result's `.trajectory` gives it (`return_trajectory=True`) -
@@ -475,10 +561,17 @@ class Whisper:
         `repetition_penalty` (> 0; 1: off) and `no_repeat_ngram_size` (>= 0; 0: off) are CTranslate2's: every distinct token the search has generated
         for a beam has its logit divided (multiplied when negative) by the penalty, and a token that would complete an n-gram the beam already holds is
         masked (include/wis_hip.h states both).  A bad value, or either option together with a draft, is a ValueError; calls with different values never
-        share a device batch."""
-        if num_hypotheses != 1 or sampling_topk != 1:
-            raise NotImplementedError("num_hypotheses and sampling_topk are not implemented (the other decoding options of CTranslate2 4.1.0 are)")
+        share a device batch.
+        Random sampling (`beam_size=1`, `sampling_topk=0` = the whole vocabulary, `sampling_temperature`; a top-k of 2..16 is the engine's, not yet this face's) and `num_hypotheses` are CTranslate2's
+        (include/wis_hip.h states the rule): with sampling, `num_hypotheses=n` decodes n independent samples per utterance (results in sample order,
+        unsorted) - openai-whisper's temperature fallback is `beam_size=1, num_hypotheses=best_of, sampling_topk=0, sampling_temperature=t`; in a beam
+        search it returns the n best finished hypotheses, best first.  `sampling_seed` (an extension of this shim): an int for the call or one per
+        utterance; None draws from os.urandom, or from a deterministic counter after `ctranslate2.set_random_seed`.  The same seed gives the same
+        samples, whatever else shares the device batch."""
         drafted = bool(draft_tokens is not None and len(draft_tokens) or draft_trajectory is not None and len(draft_trajectory[0]))
+        s_k, s_T, s_n = _check_sampling(beam_size, num_hypotheses, sampling_topk, sampling_temperature, drafted)
+        if max(int(beam_size), s_n) > self.max_beam:
+            raise ValueError(f"num_hypotheses {s_n} outside 1..{self.max_beam} (setting max_beam: decoder rows per utterance)")
         rep_p, rep_n = _check_repetition(repetition_penalty, no_repeat_ngram_size, drafted)
         mel = self._features(features, input_kind)
         B = mel.shape[0]
@@ -508,8 +601,18 @@ class Whisper:
         if timestamps or return_no_speech_prob:      # (the tail keeps the draft slots at fixed positions: _run_batch reads key[11:14])
             mi = None if max_initial_timestamp_index is None else int(max_initial_timestamp_index)
             key = (key + (None, False))[:11] + (timestamps, mi if timestamps else 50, bool(return_no_speech_prob))
-        key = _rep_key(key, rep_p, rep_n)
+        key = _sample_key(_rep_key(key, rep_p, rep_n), s_k, s_T, s_n)
         rows = [(np.ascontiguousarray(mel[b]), [int(t) for t in prompts[b]]) for b in range(B)]
+        if s_k != 0:
+            if sampling_seed is None:
+                seeds = [_next_seed() for _ in range(B)]
+            elif np.isscalar(sampling_seed):
+                seeds = [int(sampling_seed)] * B
+            else:
+                seeds = [int(x) for x in sampling_seed]
+                if len(seeds) != B:
+                    raise ValueError(f"sampling_seed: {len(seeds)} seeds for {B} utterances")
+            rows = [r + (sd & 0xFFFFFFFFFFFFFFFF,) for r, sd in zip(rows, seeds)]
         return self._batcher.submit(key, rows)
 
     @staticmethod
@@ -550,7 +653,7 @@ class Whisper:
 
     def generate_from_device(self, device, mel_device_ptr, prompt, *, beam_size=5, max_length=448, length_penalty=1, patience=1,
                              suppress_blank=True, fixed_new_tokens=0, replica=None, draft_tokens=None, draft_trajectory=None, return_trajectory=False,
-                             repetition_penalty=1, no_repeat_ngram_size=0):
+                             repetition_penalty=1, no_repeat_ngram_size=0, num_hypotheses=1, sampling_topk=1, sampling_temperature=1, sampling_seed=None):
         """One utterance whose log-mel features ALREADY live in HBM on `device` (f32 [n_mels][3000] at `mel_device_ptr`, e.g. an
         audio.MelStream after finish()): WIS_IN_MEL_DEV - nothing is staged through the host.  Goes through the micro-batcher bound
         to that DEVICE: any replica of the GPU can read the features, so concurrent windows of several streaming sessions on one GPU
@@ -570,8 +673,14 @@ class Whisper:
         _check_patience(beam_size, patience)
         drafted = bool(draft_tokens is not None and len(draft_tokens) or draft_trajectory is not None and len(draft_trajectory[0]))
         rep_p, rep_n = _check_repetition(repetition_penalty, no_repeat_ngram_size, drafted)
-        key = _rep_key(key + self._draft_key(1, beam_size, draft_tokens, draft_trajectory, return_trajectory), rep_p, rep_n)
-        return self._batcher.submit(key, [(int(mel_device_ptr), [int(t) for t in prompt])], affinity=("device", device))[0]
+        s_k, s_T, s_n = _check_sampling(beam_size, num_hypotheses, sampling_topk, sampling_temperature, drafted)
+        if max(int(beam_size), s_n) > self.max_beam:
+            raise ValueError(f"num_hypotheses {s_n} outside 1..{self.max_beam}")
+        key = _sample_key(_rep_key(key + self._draft_key(1, beam_size, draft_tokens, draft_trajectory, return_trajectory), rep_p, rep_n), s_k, s_T, s_n)
+        row = (int(mel_device_ptr), [int(t) for t in prompt])
+        if s_k != 0:
+            row = row + ((_next_seed() if sampling_seed is None else int(sampling_seed)) & 0xFFFFFFFFFFFFFFFF,)
+        return self._batcher.submit(key, [row], affinity=("device", device))[0]
 
     def _generate_chunk(self, r, mel, prompts, P, beam, max_new, lp, patience, suppress_blank, suppress_default, fixed_new, kind):
         """One `wis_generate` call on replica r (the caller serialises access to r)."""

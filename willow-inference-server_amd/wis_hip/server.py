@@ -161,7 +161,22 @@ def create_app(models=None, settings=None, max_workers=None, sv=None):
             raise BadRequest(f"repetition_penalty {rp} must be a finite number > 0")
         if ng is not None and ng < 0:
             raise BadRequest(f"no_repeat_ngram_size {ng} must be >= 0")
-        return dict(model=model, beam_size=beam, repetition_penalty=rp, no_repeat_ngram_size=ng,
+        # openai-whisper's temperature fallback: temperatures=0,0.2,0.4 and best_of= per request (absent: the settings' values); a bad value = 400
+        temps, best_of = q.get("temperatures"), q.get("best_of")
+        if temps in (None, ""):
+            temps = None
+        if best_of in (None, ""):
+            best_of = None
+        if temps is not None or best_of is not None:
+            from .whisper import parse_temperatures
+            try:
+                t_, n_ = parse_temperatures(temps if temps is not None else (), best_of if best_of is not None else 1)
+            except ValueError as e:
+                raise BadRequest(f"Invalid temperatures / best_of: {e}")
+            temps, best_of = (t_ if temps is not None else None), (n_ if best_of is not None else None)
+            if best_of is not None and best_of > s.max_beam:
+                raise BadRequest(f"best_of {best_of} outside 1..{s.max_beam}")
+        return dict(model=model, beam_size=beam, repetition_penalty=rp, no_repeat_ngram_size=ng, temperatures=temps, best_of=best_of,
                     detect_language=_as_bool(q.get("detect_language"), s.detect_language), force_language=q.get("force_language") or None,
                     translate=_as_bool(q.get("translate"), False), timestamps=_as_bool(q.get("timestamps"), False),
                     word_timestamps=_as_bool(q.get("word_timestamps"), False))
@@ -171,7 +186,7 @@ def create_app(models=None, settings=None, max_workers=None, sv=None):
         kw = {"timestamps": True} if p["timestamps"] else {}      # (segment times: one 30 s window; longer audio is a 400)
         if p["word_timestamps"]:                                  # (word times imply segment times; no vocabulary / long audio is a 400)
             kw = {"word_timestamps": True}
-        kw.update({k: p[k] for k in ("repetition_penalty", "no_repeat_ngram_size") if p[k] is not None})      # (absent: do_whisper takes the settings' values)
+        kw.update({k: p[k] for k in ("repetition_penalty", "no_repeat_ngram_size", "temperatures", "best_of") if p[k] is not None})      # (absent: do_whisper takes the settings' values)
         return await loop.run_in_executor(pool, lambda: do_whisper(audio_file, p["model"], p["beam_size"], "transcribe", p["detect_language"],
                                                                    p["force_language"], p["translate"], models=get_models(), **kw))
 

@@ -82,6 +82,15 @@ class APISettings:
     # complete an n-gram the beam already holds is masked.  1.0 / 0 = off (CTranslate2's defaults)
     repetition_penalty: float = 1.0
     no_repeat_ngram_size: int = 0
+    # openai-whisper's temperature fallback (decode_with_fallback), as every request without the query parameters of the same names decodes: a
+    # window whose result loops (zlib compression ratio of its text above `compression_ratio_threshold`) or scores badly (average log-probability
+    # below `logprob_threshold`) is decoded again at each later temperature - a sampled decode of `best_of` samples, the one with the best average
+    # log-probability kept.  Temperature 0 is the ordinary search.  An empty list = no fallback (the product default); openai-whisper's own
+    # schedule is 0,0.2,0.4,0.6,0.8,1.0 with the thresholds below.  A threshold <= -1e30 / >= 1e30 switches that test off
+    temperatures: list = field(default_factory=list)
+    best_of: int = 5
+    compression_ratio_threshold: float = 2.4
+    logprob_threshold: float = -1.0
     # --- speaker verification (`voice_auth`, support_sv): not reference fields, the reference hard-codes both paths (main.py:308-312,
     # 839).  The model directory is a Hugging Face WavLMForXVector checkpoint (or "synthetic:wavlm-base-plus-sv[:SEED]"); the speakers
     # directory holds one NAME.npy embedding per enrolled speaker (python -m wis_hip.sv enroll NAME AUDIO)

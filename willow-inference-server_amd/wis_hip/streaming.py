@@ -77,7 +77,8 @@ class _IncrementalFront:
 
 class StreamingSession:
     def __init__(self, model, beam_size=None, task="transcribe", detect_language=False, force_language=None, models=None,
-                 fixed_new_tokens=0, incremental=True, speculate_every_s=None, repetition_penalty=None, no_repeat_ngram_size=None):
+                 fixed_new_tokens=0, incremental=True, speculate_every_s=None, repetition_penalty=None, no_repeat_ngram_size=None,
+                 sampling_topk=None, sampling_temperature=None, sampling_seed=None):
         self.models = models or default_models()
         s = self.models.settings
         # CTranslate2's repetition_penalty / no_repeat_ngram_size (None: the settings' values) go to every window decode that runs WITHOUT a
@@ -85,6 +86,12 @@ class StreamingSession:
         # search, as it always has: the engine has no drafted form of the two rules
         self._rep = dict(repetition_penalty=getattr(s, "repetition_penalty", 1.0) if repetition_penalty is None else repetition_penalty,
                          no_repeat_ngram_size=getattr(s, "no_repeat_ngram_size", 0) if no_repeat_ngram_size is None else no_repeat_ngram_size)
+        # ... and so does random sampling (CTranslate2's sampling_topk / sampling_temperature, beam_size 1; None: off): the engine has no drafted
+        # form of it either, and a generate call refuses the combination
+        if sampling_topk is not None and int(sampling_topk) != 1:
+            self._rep.update(sampling_topk=int(sampling_topk), sampling_temperature=1.0 if sampling_temperature is None else float(sampling_temperature))
+            if sampling_seed is not None:
+                self._rep["sampling_seed"] = int(sampling_seed)
         self.model_name, self.task = model, task
         self.beam_size = s.beam_size if beam_size is None else beam_size
         self.detect_language, self.force_language = detect_language, force_language
@@ -230,6 +237,8 @@ class StreamingSession:
             kw["return_trajectory"] = True
         if "draft_tokens" not in kw and "draft_trajectory" not in kw:
             kw.update(getattr(self, "_rep", {}))
+            if "sampling_topk" in kw:
+                beam = 1      # (random sampling applies at beam_size 1)
         if stream is not None:
             try:
                 stream.finish(to_host=False)

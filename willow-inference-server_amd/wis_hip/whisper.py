@@ -316,9 +316,63 @@ def chunkit(lst, num):
         yield lst[i:i + num]
 
 
+def compression_ratio(text):
+    """openai-whisper's: bytes of the text over bytes of its zlib image (a looping transcript compresses well: > 2.4 is its retry mark)."""
+    import zlib
+    raw = text.encode("utf-8")
+    return len(raw) / len(zlib.compress(raw)) if raw else 0.0
+
+
+def parse_temperatures(temperatures, best_of):
+    """-> (tuple of temperatures, best_of), validated: finite values >= 0, best_of 1 .. the engine's rows per utterance.  ValueError otherwise."""
+    try:
+        ts = tuple(float(t) for t in (temperatures.split(",") if isinstance(temperatures, str) else (temperatures or ())) if str(t).strip() != "")
+        n = int(best_of)
+        if n != float(best_of):
+            raise ValueError
+    except (TypeError, ValueError, OverflowError):
+        raise ValueError(f"temperatures {temperatures!r} / best_of {best_of!r}: a list of numbers and an integer") from None
+    if any(not (0 <= t < float("inf")) for t in ts):
+        raise ValueError(f"temperatures {temperatures!r}: finite values >= 0")
+    if not 1 <= n <= ctranslate2.MAX_BEAM:
+        raise ValueError(f"best_of {best_of!r} outside 1..{ctranslate2.MAX_BEAM}")
+    return ts, n
+
+
+def decode_with_fallback(decode, temperatures, best_of=5, compression_ratio_threshold=None, logprob_threshold=None, text_of=None):
+    """openai-whisper's decode_with_fallback as a pure host function.  decode(temperature, n) -> [(tokens, score), ...]: the ordinary search at
+    temperature 0 (n = 1), n samples at a later one; `score` is the engine's (cumulative log-probability, the end token's included, over the
+    token count), so the average log-probability is score * len / (len + 1) as openai-whisper counts it.  Of a temperature's candidates the one
+    with the best average log-probability is kept (the first among equals).  It needs a retry when its text's zlib compression ratio is above
+    `compression_ratio_threshold` (only with `text_of`, tokens -> text: without a tokenizer vocabulary there is no text to compress) or its average
+    log-probability is below `logprob_threshold`; None switches a test off.  The first acceptable result ends the schedule; the last one stands.
+    -> dict(tokens, score, avg_logprob, compression_ratio (None without text_of), temperature, attempts)"""
+    out = None
+    for i, t in enumerate(temperatures):
+        cands = decode(t, 1 if t == 0 else best_of)
+        best = None
+        for tokens, score in cands:
+            avg = score * len(tokens) / (len(tokens) + 1)
+            if best is None or avg > best[2]:
+                best = (list(tokens), score, avg)
+        ratio = compression_ratio(text_of(best[0])) if text_of is not None else None
+        out = dict(tokens=best[0], score=best[1], avg_logprob=best[2], compression_ratio=ratio, temperature=t, attempts=i + 1)
+        retry = (compression_ratio_threshold is not None and ratio is not None and ratio > compression_ratio_threshold) or \
+                (logprob_threshold is not None and not best[2] >= logprob_threshold)
+        if not retry:
+            break
+    return out
+
+
 def do_whisper(audio_file, model, beam_size=None, task="transcribe", detect_language=False, force_language=None, translate=False,
-               models=None, fixed_new_tokens=None, timestamps=False, word_timestamps=False, repetition_penalty=None, no_repeat_ngram_size=None):
-    """repetition_penalty / no_repeat_ngram_size: CTranslate2's options of those names (None: the settings' values, 1.0 and 0 = off), handed
+               models=None, fixed_new_tokens=None, timestamps=False, word_timestamps=False, repetition_penalty=None, no_repeat_ngram_size=None,
+               temperatures=None, best_of=None, compression_ratio_threshold=None, logprob_threshold=None):
+    """temperatures / best_of / compression_ratio_threshold / logprob_threshold: openai-whisper's temperature fallback (decode_with_fallback; None:
+    the settings' values, and the settings' default - no temperatures - is no fallback).  The first temperature's decode is judged, and while it
+    loops or scores badly the window is decoded again at the next: 0 is the search at `beam_size`, anything else `generate(beam_size=1,
+    num_hypotheses=best_of, sampling_topk=0, sampling_temperature=t)`.  The compression ratio needs the decoded TEXT, so it needs the
+    checkpoint's tokenizer vocabulary: without one only the log-probability threshold applies.  One 30 s window (longer audio: ValueError).
+    repetition_penalty / no_repeat_ngram_size: CTranslate2's options of those names (None: the settings' values, 1.0 and 0 = off), handed
     to every `generate` call of the request - chunked windows, the timestamped pass, the translation pass.
     word_timestamps=True implies timestamps=True: after the search the window's text tokens are aligned with the audio in one
     `Whisper.align` call (cross-attention of the alignment heads + DTW on the GPU) and every segment gains
@@ -333,6 +387,10 @@ def do_whisper(audio_file, model, beam_size=None, task="transcribe", detect_lang
     beam_size = s.beam_size if beam_size is None else beam_size
     rep = dict(repetition_penalty=getattr(s, "repetition_penalty", 1.0) if repetition_penalty is None else repetition_penalty,
                no_repeat_ngram_size=getattr(s, "no_repeat_ngram_size", 0) if no_repeat_ngram_size is None else no_repeat_ngram_size)
+    temps, best_of = parse_temperatures(getattr(s, "temperatures", ()) if temperatures is None else temperatures,
+                                        getattr(s, "best_of", 5) if best_of is None else best_of)
+    cr_thr = getattr(s, "compression_ratio_threshold", 2.4) if compression_ratio_threshold is None else compression_ratio_threshold
+    lp_thr = getattr(s, "logprob_threshold", -1.0) if logprob_threshold is None else logprob_threshold
     whisper_model = models.get(model)
     special = model_special_tokens(whisper_model)
     n_mels = getattr(whisper_model, "n_mels", audio.N_MELS)
@@ -353,6 +411,8 @@ def do_whisper(audio_file, model, beam_size=None, task="transcribe", detect_lang
         beam_size = s.long_beam_size
     if timestamps and audio_duration > 30 * 1000:
         raise ValueError("timestamps are available for audio of up to 30 s (one window)")
+    if temps and audio_duration > 30 * 1000:
+        raise ValueError("the temperature fallback is available for audio of up to 30 s (one window)")
     use_chunking = audio_duration > 30 * 1000 and s.support_chunking
     strides = []
     if use_chunking:
@@ -392,7 +452,23 @@ def do_whisper(audio_file, model, beam_size=None, task="transcribe", detect_lang
 
     # STEP 3 — run the model, `concurrent_gpu_chunks` windows per generate call
     results = []
-    for batch in chunkit(features, s.concurrent_gpu_chunks):
+    if temps:      # one window, openai-whisper's decode_with_fallback around it
+        feats = ctranslate2.StorageView.from_array(np.ascontiguousarray(features[0:1]))
+
+        def decode(t, n):
+            if t == 0:
+                r = whisper_model.generate(feats, [prompt], beam_size=beam_size, return_scores=True, fixed_new_tokens=fixed_new_tokens, input_kind=kind, **rep)[0]
+            else:
+                r = whisper_model.generate(feats, [prompt], beam_size=1, num_hypotheses=n, sampling_topk=0, sampling_temperature=t, return_scores=True,
+                                           fixed_new_tokens=fixed_new_tokens, input_kind=kind, **rep)[0]
+            return list(zip(r.sequences_ids, r.scores))
+        text_of = None
+        if getattr(tokenizer, "has_vocabulary", False):      # (no vocabulary: no text to compress - the log-probability threshold alone decides)
+            text_of = lambda toks: tokenizer.decode([t for t in toks if t < special.timestamp_begin])
+        fb = decode_with_fallback(decode, temps, best_of, None if cr_thr is None or cr_thr >= 1e30 else cr_thr, None if lp_thr is None or lp_thr <= -1e30 else lp_thr, text_of)
+        results.append(ctranslate2.WhisperGenerationResult([fb["tokens"]], [fb["score"]]))
+        results[0].fallback = fb
+    for batch in ([] if temps else chunkit(features, s.concurrent_gpu_chunks)):
         feats = ctranslate2.StorageView.from_array(np.ascontiguousarray(batch))
         results.extend(whisper_model.generate(feats, [prompt] * len(batch), beam_size=beam_size, return_scores=False,
                                               fixed_new_tokens=fixed_new_tokens, input_kind=kind, **rep))
@@ -435,4 +511,5 @@ def do_whisper(audio_file, model, beam_size=None, task="transcribe", detect_lang
     out.tokens = tokens
     out.translation_tokens = out_translation_tokens
     out.segments = segments
+    out.fallback = getattr(results[0], "fallback", None)      # temperature fallback: what the kept decode was (decode_with_fallback)
     return out
