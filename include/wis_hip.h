@@ -56,6 +56,31 @@ int  wis_audio_decode(const void* bytes, size_t n_bytes, float** pcm_out,
                       int64_t* n_samples_out, int* sample_rate_out, int* md5_status_out);
 void wis_audio_free(float* pcm);
 
+/* ---- a1, second half: sample-rate conversion to 16 kHz (the resampling librosa.load(audio_file, sr=16000) does, main.py:579 and
+ * :815; x-audio-sample-rate on /api/willow), csrc/resample.hip.  up = 16000 / g, down = sr_in / g, g = gcd(sr_in, 16000); the
+ * prototype low-pass h has n_taps = 64 max(up, down) + 1 taps: Kaiser-windowed sinc, 32 zero crossings each side at the lower
+ * rate, beta 14.769656459379492, cut-off 0.945 of the lower Nyquist, taps summing to `up`; n_out = ceil(n_in up / down) and
+ * y[m] = sum over k in [0, n_in) of x[k] h[m down - k up + 32 max(up, down)], zeros outside the signal on both sides
+ * (wis_hip.audio._resample_filter / resample define the same filter and the same sum on the host).
+ * A ratio is served on the device while n_taps <= 2^20 (every rate from 8 to 96 kHz that shares a sensible divisor with 16 kHz);
+ * above that the entries answer WIS_E_UNSUPPORTED and the caller resamples on the host.
+ *
+ * wis_resample_plan: host only, no GPU.  Any out pointer may be NULL.  taps_per_phase = ceil(n_taps / up): the terms of every
+ * output's sum.  sr_in <= 0 or n_in < 0: WIS_E_ARG; above the tap cap: WIS_E_UNSUPPORTED (the values are still written). */
+int wis_resample_plan(int sr_in, int64_t n_in, int* up, int* down, int64_t* n_out, int* taps_per_phase, int64_t* n_taps);
+/* the fp64 prototype the engine rounds to f32 for its device tables: h[0 .. 64 max(up, down)], cap = room in h (fewer than
+ * n_taps: WIS_E_ARG).  Host only, no GPU. */
+int wis_resample_filter(int up, int down, double* h, int64_t cap);
+/* host PCM at sr_in in, host PCM at 16 kHz out: out[0 .. *n_out).  *n_out is written whenever the arguments name a length;
+ * out_cap < *n_out: WIS_E_ARG and `out` is not touched.  sr_in == 16000 copies the input (no GPU needed); n_in == 0 gives
+ * *n_out = 0.  The bits of out[m] depend on the signal, the ratio and m alone: long inputs run in segments over a bounded
+ * workspace and the result does not depend on where the segments fall.  Re-entrant like wis_logmel_n: every call has a stream
+ * and a workspace of its own. */
+int wis_resample(int device, const float* pcm, int64_t n_in, int sr_in, float* out, int64_t out_cap, int64_t* n_out);
+/* the same with the segment length forced: segment_samples input samples per segment (0: the built-in length) */
+int wis_resample_ex(int device, const float* pcm, int64_t n_in, int sr_in, float* out, int64_t out_cap, int64_t* n_out,
+                    int64_t segment_samples);
+
 /* ---- a2+a3: log-mel front-end (replaces wis.audio.log_mel_spectrogram(pad_or_trim(x)),
  * wis/audio.py:28-51,72-103; call sites main.py:606-614).
  * pcm: n_win windows, window w has n_samples[w] valid samples starting at pcm + w*stride
@@ -475,6 +500,13 @@ int wis_op_enc_crosskv(int device, const void* mem_f16, const void* W_f16, const
  * exists for 2 and 4 splits and N <= 2048, K % (64 splits) == 0 (otherwise the launch function's error code). */
 int wis_op_gemm_splitk_ln(int device, const void* A_f16, const void* W_f16, const float* bias, float* X, const float* gamma, const float* beta,
                           void* Y_f16, int M, int N, int K, int splits);
+
+/* ---- the resampler's kernel alone (tests/test_gpu_resample_ops.py): outputs m0 .. m0 + count - 1 (out f32 [count]) of a signal of
+ * n_in_total samples at the reduced ratio up / down to 16 kHz, from the slice x_slice f32 [n_slice] = samples k_base .. k_base +
+ * n_slice - 1 of that signal (device pointers).  The slice must hold every sample of the signal those outputs read (else
+ * WIS_E_ARG); samples outside [0, n_in_total) are zeros.  k_base and m0 are 64-bit: positions past 2^31 are ordinary. */
+int wis_op_resample_segment(int device, const float* x_slice, int64_t n_slice, int64_t k_base, int64_t n_in_total, int64_t m0, int64_t count,
+                            int up, int down, float* out);
 
 /* ---- taps of what runs behind the logits (tests/test_gpu_sample_ops.py): the product's launch functions on caller-supplied device memory. */
 /* the cache permutation after a beam step, in place: kc / vc f16, layer l at + l layer_stride_elems, [slots][ctx][d] each (d % 8 == 0); for every

@@ -19,7 +19,7 @@ LIB = os.path.join(LIBDIR, "libwis_hip.so")
 
 HIP_SOURCES = ["logmel.hip", "enc_kernels.hip", "dec_kernels.hip", "model.hip"]
 C_SOURCES = ["audio_io.c"]
-HEADERS = ["common.hpp", "kernels.hpp", "sv.hip", "align.hip", "generate.hip", "taps.hip", os.path.join(ROOT, "include", "wis_hip.h")]      # sv.hip, align.hip, generate.hip, taps.hip: included by model.hip
+HEADERS = ["common.hpp", "kernels.hpp", "sv.hip", "align.hip", "generate.hip", "taps.hip", "resample.hip", os.path.join(ROOT, "include", "wis_hip.h")]      # sv.hip, align.hip, generate.hip, taps.hip: included by model.hip; resample.hip: by logmel.hip
 EXPORTS = os.path.join(CSRC, "exports.map")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 # -amdgpu-mfma-vgpr-form: MFMA accumulators live in VGPRs (gfx90a+ unified register file) instead of AGPRs.  hipcc's default put

@@ -176,6 +176,16 @@ int get_ctx(int device, DeviceCtx** out);
 hipStream_t ctx_stream(DeviceCtx* c);
 std::mutex& ctx_op_mutex(DeviceCtx* c);   // serialises the single-kernel taps (wis_op_*) that share ctx_stream
 
+// sample-rate conversion to 16 kHz (csrc/resample.hip): the context keeps the device's tap tables, one per (up, down), built at first
+// use, and the free list of the workspaces wis_resample runs on
+struct ResampleCtx;
+ResampleCtx* resample_ctx_new();
+ResampleCtx* ctx_resample(DeviceCtx* c);
+// outputs m0 .. m0 + count - 1 of a signal of n_in_total samples from the slice d_x = samples k_base .. k_base + n_slice - 1 (device
+// pointers, on `st`); WIS_E_ARG when the slice does not hold every sample of the signal those outputs read
+int resample_segment(DeviceCtx* c, hipStream_t st, const float* d_x, int64_t n_slice, int64_t k_base, int64_t n_in_total, int64_t m0, int64_t count,
+                     int up, int down, float* d_out);
+
 // log-mel on `stream`: pcm (device) -> mel f32 [n_win][n_mels][3000] (device, may be null) and/or
 // conv1 input f16 [n_win][3002][conv1_channels(n_mels)] (device, may be null; rows 0 and 3001 and the pad cols 80..95 zero).
 // d_logspec f32 [n_win][n_mels][3000] and d_gmax u32 [n_win] are the caller's own scratch (never shared between in-flight calls).

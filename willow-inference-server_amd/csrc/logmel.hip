@@ -59,6 +59,7 @@ struct DeviceCtx {
   std::mutex ws_mu;
   std::vector<struct LogmelWs*> ws_free;
   std::mutex op_mu;           // serialises the single-kernel test taps (wis_op_*), which share `stream`
+  ResampleCtx* rs = nullptr;  // wis_resample's tap tables and workspaces (csrc/resample.hip)
 };
 
 // everything one wis_logmel call touches on the device; owned by exactly one caller between acquire and release
@@ -97,6 +98,7 @@ static void ws_release(DeviceCtx* c, LogmelWs* w) {
   c->ws_free.push_back(w);
 }
 std::mutex& ctx_op_mutex(DeviceCtx* c) { return c->op_mu; }
+ResampleCtx* ctx_resample(DeviceCtx* c) { return c->rs; }
 
 static std::mutex g_ctx_mu;
 static DeviceCtx* g_ctx[64] = {nullptr};
@@ -136,7 +138,7 @@ int get_ctx(int device, DeviceCtx** out) {
     set_error("no HIP device %d (found %d): libwis_hip has no CPU fallback", device, n); return WIS_E_HIP;
   }
   WIS_HIP_CHECK(hipSetDevice(device));
-  DeviceCtx* c = new DeviceCtx(); c->device = device;
+  DeviceCtx* c = new DeviceCtx(); c->device = device; c->rs = resample_ctx_new();
   WIS_HIP_CHECK(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
   // DFT matrix, fp64 with exact angle reduction; window folded in (torch.hann_window(400),
   // periodic: 0.5 - 0.5 cos(2 pi n / 400), wis/audio.py:97).
@@ -486,3 +488,6 @@ extern "C" void wis_melstream_destroy(wis_melstream_t* s) {
   if (s->h_nsamp) hipHostFree(s->h_nsamp);
   delete s;
 }
+
+// ---------------------------------------------------------------------------------------
+#include "resample.hip"      // the other half of the audio front end: uploads at another rate than 16 kHz (wis_resample)

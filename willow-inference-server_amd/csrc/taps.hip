@@ -626,4 +626,12 @@ int wis_op_greedy_rows(int device, const float* logits, int n_vocab, int n_vocab
   return t.finish(launch_greedy_pick(t.st, smax, ssum, sval, sidx, rows, sc, tok_out, lp_out));
 }
 
+// ---- the resampler's kernel alone (tests/test_gpu_resample_ops.py): one launch of csrc/resample.hip on a caller-supplied slice of a longer signal
+int wis_op_resample_segment(int device, const float* x_slice, int64_t n_slice, int64_t k_base, int64_t n_in_total, int64_t m0, int64_t count,
+                            int up, int down, float* out) {
+  Tap t(device, "wis_op_resample_segment"); WIS_RET(t.rc);
+  DeviceCtx* c = nullptr; WIS_RET(get_ctx(device, &c));
+  return t.finish(resample_segment(c, t.st, x_slice, n_slice, k_base, n_in_total, m0, count, up, down, out));
+}
+
 }  // extern "C"

@@ -72,6 +72,11 @@ SYMBOLS = [
     ("wis_audio_decode", _i, [_vp, _sz, C.POINTER(_fp), C.POINTER(_i64), C.POINTER(_i), C.POINTER(_i)]),
     ("wis_audio_free", None, [_fp]),
     ("wis_logmel", _i, [_i, _vp, _i64, C.POINTER(_i64), _i, _i, _vp, _i]),
+    ("wis_resample_plan", _i, [_i, _i64, C.POINTER(_i), C.POINTER(_i), C.POINTER(_i64), C.POINTER(_i), C.POINTER(_i64)]),
+    ("wis_resample_filter", _i, [_i, _i, C.POINTER(C.c_double), _i64]),
+    ("wis_resample", _i, [_i, _vp, _i64, _i, _vp, _i64, C.POINTER(_i64)]),
+    ("wis_resample_ex", _i, [_i, _vp, _i64, _i, _vp, _i64, C.POINTER(_i64), _i64]),
+    ("wis_op_resample_segment", _i, [_i, _vp, _i64, _i64, _i64, _i64, _i64, _i, _i, _vp]),
     ("wis_melstream_create", _i, [_i, C.POINTER(_vp)]),
     ("wis_logmel_n", _i, [_i, _i, _vp, _i64, C.POINTER(_i64), _i, _i, _vp, _i]),
     ("wis_melstream_create_n", _i, [_i, _i, C.POINTER(_vp)]),

@@ -7,7 +7,8 @@ arithmetic moved to the GPU:
 (`wis_logmel`); it raises if libwis_hip.so or a GPU is missing (no CPU fallback).  `pad_or_trim`,
 `chunk_iter` and `find_longest_common_sequence` are integer/host logic and keep the reference's
 semantics exactly (wis/audio.py:28-51, 119-134, 139-159).  `load_audio` replaces the
-`librosa.load(audio_file, sr=16000, mono=True)` call of main.py:579 (container decode in C, channel mix, resampling to 16 kHz).
+`librosa.load(audio_file, sr=16000, mono=True)` call of main.py:579 (container decode in C, channel mix, resampling to 16 kHz:
+on the host in numpy, or with `device=` on that GPU through `wis_resample`, csrc/resample.hip).
 """
 import ctypes as C
 import threading
@@ -33,10 +34,11 @@ stride_left = stride_length_s[0] * SAMPLE_RATE
 stride_right = stride_length_s[1] * SAMPLE_RATE
 
 
-def load_audio(audio_file):
+def load_audio(audio_file, device=None):
     """FLAC / WAV path, bytes or file-like -> (float32 mono PCM in [-1, 1), sample_rate).
 
-    Container decode is host C code inside libwis_hip.so (wis_audio_decode); FLAC streams are MD5-verified."""
+    Container decode is host C code inside libwis_hip.so (wis_audio_decode); FLAC streams are MD5-verified.
+    `device`: the GPU that resamples a container at another rate than 16 kHz (see `resample`); None = on the host."""
     if isinstance(audio_file, (bytes, bytearray, memoryview)):
         data = bytes(audio_file)
     elif hasattr(audio_file, "read"):
@@ -54,7 +56,7 @@ def load_audio(audio_file):
     finally:
         lib.wis_audio_free(p)
     if sr.value != SAMPLE_RATE:         # librosa.load(..., sr=16000) resamples whatever the container holds (main.py:579)
-        pcm = resample(pcm, sr.value, SAMPLE_RATE)
+        pcm = resample(pcm, sr.value, SAMPLE_RATE, device=device)
     return pcm, SAMPLE_RATE
 
 
@@ -69,16 +71,38 @@ def _resample_filter(up, down, half_width=32, beta=14.769656459379492, rolloff=0
     return h * (up / h.sum())
 
 
-def resample(pcm, sr_in, sr_out=SAMPLE_RATE):
-    """Band-limited sample-rate conversion sr_in -> sr_out (host, numpy fp64 accumulation; polyphase Kaiser-windowed sinc,
-    64 zero crossings, stop band below -100 dB).  Replaces the resampling half of `librosa.load(audio_file, sr=16000)`
+def resample_gpu(pcm, sr_in, device=0, segment_samples=0):
+    """`wis_resample` (csrc/resample.hip): float32 PCM at sr_in -> float32 PCM at 16 kHz on GPU `device`, the filter and the sum of
+    `resample` in f32.  segment_samples: input samples per segment (0 = the engine's).  Raises WisError: code -7 (WIS_E_UNSUPPORTED)
+    for a ratio the device does not serve."""
+    x = np.ascontiguousarray(pcm, np.float32).reshape(-1)
+    lib = _lib.load()
+    n_out = C.c_int64()
+    _lib.check(lib.wis_resample_plan(int(sr_in), x.shape[0], None, None, C.byref(n_out), None, None))
+    out = np.empty(n_out.value, np.float32)
+    _lib.check(lib.wis_resample_ex(int(device), _lib.ptr(x), x.shape[0], int(sr_in), _lib.ptr(out), out.shape[0], C.byref(n_out), int(segment_samples)))
+    return out[:n_out.value]
+
+
+def resample(pcm, sr_in, sr_out=SAMPLE_RATE, device=None):
+    """Band-limited sample-rate conversion sr_in -> sr_out (polyphase Kaiser-windowed sinc, 64 zero crossings, stop band below
+    -100 dB).  Replaces the resampling half of `librosa.load(audio_file, sr=16000)`
     (main.py:579; librosa's default there is soxr_hq - a different filter of the same class, so the result agrees with it to
     pass-band ripple / transition-band shape, not bit for bit: the reference fixtures are all 16 kHz and never take this path).
-    Output length = ceil(n * sr_out / sr_in), as librosa."""
-    x = np.ascontiguousarray(pcm, np.float64).reshape(-1)
+    Output length = ceil(n * sr_out / sr_in), as librosa.
+    `device=None`: on the host, numpy with fp64 accumulation.  With a device and sr_out = 16000 the same sum runs on that GPU in f32
+    (`resample_gpu`; equal to the host result to f32 rounding of the taps and of the sum, not bit for bit); a ratio the device does not
+    serve (a prototype of more than 2^20 taps) and any other sr_out take the host path."""
     sr_in, sr_out = int(sr_in), int(sr_out)
     if sr_in <= 0 or sr_out <= 0:
         raise ValueError(f"bad sample rate {sr_in} -> {sr_out}")
+    if device is not None and sr_out == SAMPLE_RATE and sr_in != sr_out and np.size(pcm):
+        try:
+            return resample_gpu(pcm, sr_in, device)
+        except _lib.WisError as e:
+            if e.code != -7:        # WIS_E_UNSUPPORTED: the host serves every ratio
+                raise
+    x = np.ascontiguousarray(pcm, np.float64).reshape(-1)
     if sr_in == sr_out or x.shape[0] == 0:
         return x.astype(np.float32)
     g = math.gcd(sr_in, sr_out)

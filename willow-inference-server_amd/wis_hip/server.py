@@ -203,7 +203,8 @@ def create_app(models=None, settings=None, max_workers=None, sv=None):
     async def run_sv(audio_file):
         from .sv import do_sv
         loop = asyncio.get_running_loop()
-        return await loop.run_in_executor(pool, lambda: do_sv(audio_file, s.sv_threshold, get_sv(), s.sv_speakers_dir))
+        return await loop.run_in_executor(pool, lambda: do_sv(audio_file, s.sv_threshold, get_sv(), s.sv_speakers_dir,
+                                                               resample_on_gpu=getattr(s, "resample_on_gpu", False)))
 
     @app.get("/api/ping")
     async def ping():

@@ -48,6 +48,10 @@ class APISettings:
     # log-mel on the replica's GPU inside generate (PCM in, mel never leaves HBM) instead of the reference's
     # mel -> host -> StorageView round trip; results are identical (same kernels)
     fuse_logmel: bool = True
+    # an upload at another rate than 16 kHz (main.py:579: librosa.load(audio_file, sr=16000)) is resampled on one of the model's own GPUs
+    # (wis_resample, csrc/resample.hip) instead of in numpy on the request thread; False: the host resampler.  The two agree to f32
+    # rounding, not bit for bit
+    resample_on_gpu: bool = True
     max_batch: int = 8
     # replicas per GPU sharing one weight copy, each with its own stream / activations / KV caches: `ctranslate2_threads` (the
     # reference's inter_threads) device batches run concurrently per GPU, up to this many

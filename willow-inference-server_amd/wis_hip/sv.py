@@ -228,6 +228,7 @@ class SpeakerVerifier:
         check_arch(cfg)
         self.do_normalize = bool(pre.get("do_normalize", True))
         self.max_samples = int(max_samples)
+        self.device = int(device)
         lib = _lib.load()
         _lib.require_gpu()
         arena, tv, keep = build_arena(engine_tensors(sd))
@@ -302,12 +303,21 @@ def score(emb, speakers, threshold):
     return dict(sorted(res.items(), key=lambda kv: kv[1], reverse=True))
 
 
-def do_sv(audio_file, threshold, verifier, speakers_dir="speakers/voice_auth"):
+def _resample_device(verifier, resample_on_gpu):
+    """the GPU that resamples a recording for `verifier`: the verifier's own (None = on the host); resample_on_gpu None = the settings' value"""
+    if resample_on_gpu is None:
+        from .settings import get_api_settings
+        resample_on_gpu = getattr(get_api_settings(), "resample_on_gpu", False)
+    return getattr(verifier, "device", None) if resample_on_gpu else None
+
+
+def do_sv(audio_file, threshold, verifier, speakers_dir="speakers/voice_auth", resample_on_gpu=None):
     """main.py:797-879: embed the request, compare with every enrolled speaker.  Audio too short for the model scores nothing
-    (the reference's NaN similarity), so the request ends as unauthorised."""
+    (the reference's NaN similarity), so the request ends as unauthorised.  A recording at another rate than 16 kHz is resampled
+    on the verifier's GPU (resample_on_gpu; None: the settings' value)."""
     from . import audio
     try:
-        pcm, _ = audio.load_audio(audio_file)
+        pcm, _ = audio.load_audio(audio_file, device=_resample_device(verifier, resample_on_gpu))
     except Exception as e:
         raise ValueError(f"invalid audio: {e}") from e
     try:
@@ -320,13 +330,13 @@ def do_sv(audio_file, threshold, verifier, speakers_dir="speakers/voice_auth"):
     return score(emb, load_speakers(speakers_dir), threshold)
 
 
-def enroll(name, audio_file, speakers_dir="speakers/voice_auth", verifier=None, model_path=None):
+def enroll(name, audio_file, speakers_dir="speakers/voice_auth", verifier=None, model_path=None, resample_on_gpu=None):
     """Write speakers_dir/NAME.npy: the L2-normalised embedding of the recording (what do_sv compares requests with)."""
     from . import audio
     if not re.fullmatch(r"[A-Za-z0-9_.\- ]+", name) or name.startswith("."):
         raise ValueError(f"invalid speaker name {name!r}")
     v = verifier or SpeakerVerifier(model_path or os.environ.get("SV_MODEL_PATH", "./models/microsoft-wavlm-base-plus-sv"))
-    pcm, _ = audio.load_audio(audio_file)
+    pcm, _ = audio.load_audio(audio_file, device=_resample_device(v, resample_on_gpu))
     emb = v.embed(pcm)
     emb = (emb / max(float(np.linalg.norm(emb)), 1e-12)).astype(np.float32)
     os.makedirs(speakers_dir, exist_ok=True)
@@ -347,7 +357,7 @@ def main(argv=None):
     e.add_argument("--dir", default=s.sv_speakers_dir)
     e.add_argument("--model", default=s.sv_model_path)
     a = ap.parse_args(argv)
-    print(enroll(a.name, a.audio, a.dir, model_path=a.model))
+    print(enroll(a.name, a.audio, a.dir, model_path=a.model, resample_on_gpu=getattr(s, "resample_on_gpu", False)))
 
 
 if __name__ == "__main__":

@@ -400,8 +400,10 @@ def do_whisper(audio_file, model, beam_size=None, task="transcribe", detect_lang
     if isinstance(audio_file, np.ndarray):
         pcm, sr = audio_file.astype(np.float32), 16000
     else:
+        # a container at another rate is resampled on one of the model's own GPUs (never on a device the server was not configured to use)
+        rs_dev = whisper_model._replicas[0].device if getattr(s, "resample_on_gpu", False) and getattr(whisper_model, "_replicas", None) else None
         try:
-            pcm, sr = audio.load_audio(audio_file)
+            pcm, sr = audio.load_audio(audio_file, device=rs_dev)
         except Exception as e:
             raise InvalidAudio(str(e)) from e
     if pcm.shape[0] == 0:
