@@ -51,7 +51,11 @@ int         wis_supported_compute_types(int device, char* out, size_t out_cap);
 
 /* ---- a1: container decode (replaces librosa.load(audio_file, sr=16000, mono=True),
  * main.py:579).  FLAC or RIFF/WAVE bytes -> malloc'ed mono f32 PCM; free with
- * wis_audio_free.  md5_status_out: 1 verified, -1 no signature present (WAV / unsigned). */
+ * wis_audio_free.  md5_status_out: 1 verified, -1 no signature present (WAV / unsigned).
+ * The bytes are untrusted: WIS_E_FORMAT for anything malformed (a sample rate of 0 and bytes
+ * before or behind the stream included), WIS_E_CHECKSUM for a FLAC signature that is present
+ * and wrong, WIS_E_NOMEM; on an error *pcm_out is not written.  Supported features:
+ * INTEGRATION.md section 5. */
 int  wis_audio_decode(const void* bytes, size_t n_bytes, float** pcm_out,
                       int64_t* n_samples_out, int* sample_rate_out, int* md5_status_out);
 void wis_audio_free(float* pcm);

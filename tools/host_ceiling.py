@@ -2,6 +2,7 @@
 batch and answer when the engine costs the host nothing?
 
     python tools/host_ceiling.py [--gpus 8] [--replicas 4] [--clients 256] [--seconds 4]
+    python tools/host_ceiling.py --decode-clip tests/golden/clips/30sec.flac          # the container decode alone, ms per file
 
 The engine call (`wis_hip.ctranslate2._generate_chunk`, i.e. wis_generate behind ctypes with the GIL released) is replaced by a sleep
 of 30 ms + 4 ms per utterance of the device batch - what a large-v2 beam-5 batch of 3.84 s utterances costs on an MI355X (62 ms for
@@ -126,6 +127,26 @@ def multi_process(a):
     return n / span, (float(np.mean(sizes)) if sizes else 0.0)
 
 
+def decode_clip(path, runs, reps):
+    """the container decode alone (wis_audio_decode through ctypes, csrc/audio_io.c): `runs` timings of `reps` decodes of one file each,
+    milliseconds per decode.  WIS_LIB_PATH selects another build of the library (a parent commit's, to compare)."""
+    import ctypes as C
+    from wis_hip import _lib
+    lib = _lib.load()
+    data = open(path, "rb").read()
+    ms = []
+    for _ in range(runs + 1):
+        t0 = time.perf_counter()
+        for _ in range(reps):
+            p, n, sr, md = C.POINTER(C.c_float)(), C.c_int64(), C.c_int(), C.c_int()
+            _lib.check(lib.wis_audio_decode(data, len(data), C.byref(p), C.byref(n), C.byref(sr), C.byref(md)))
+            lib.wis_audio_free(p)
+        ms.append(1e3 * (time.perf_counter() - t0) / reps)
+    ms = ms[1:]          # (the first run warms the caches)
+    print(f"{os.path.basename(path)}: {n.value} samples at {sr.value} Hz, {len(data)} bytes; ms per decode over {runs} runs of {reps}: "
+          + " ".join(f"{v:.3f}" for v in ms) + f"; min {min(ms):.3f} median {float(np.median(ms)):.3f} max {max(ms):.3f}  ({_lib.LIB_PATH})")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=8)
@@ -137,7 +158,12 @@ def main():
     ap.add_argument("--client-procs", type=int, default=2, help="load-generator processes (--processes mode)")
     ap.add_argument("--client-worker", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--port", type=int, default=0, help=argparse.SUPPRESS)
+    ap.add_argument("--decode-clip", metavar="FILE", help="time the container decode of FILE alone (no server): --decode-runs timings of --decode-reps decodes")
+    ap.add_argument("--decode-runs", type=int, default=5)
+    ap.add_argument("--decode-reps", type=int, default=50)
     a = ap.parse_args()
+    if a.decode_clip:
+        return decode_clip(a.decode_clip, a.decode_runs, a.decode_reps)
     if a.client_worker:
         return client_worker("127.0.0.1", a.port, a.clients, a.seconds)
     if a.processes > 0:

@@ -4,14 +4,26 @@
 // (reference main.py:579-581): FLAC or RIFF/WAVE bytes -> mono float32 PCM in [-1,1)
 // (int sample / 2^(bps-1), channels averaged), plus the sample rate.  Resampling is NOT
 // done here: the reference's fixtures and the Willow device stream are 16 kHz already;
-// any other rate is reported to the caller, which resamples to 16 kHz on the host
-// (wis_hip.audio.resample: polyphase Kaiser-windowed sinc).
+// any other rate is reported to the caller, which resamples to 16 kHz
+// (wis_hip.audio.resample on the host, wis_resample on the GPU).
 //
 // Host-only plain C; no dependency.  The FLAC side implements the full subframe set
 // (CONSTANT / VERBATIM / FIXED 0-4 / LPC 1-32, Rice methods 0 and 1 with escape
-// partitions, wasted bits, all four channel assignments, 4..32 bps) and verifies the
-// frame CRC-16 and the STREAMINFO MD5 of the decoded signal, which is the
-// known-answer test for the three reference clips.
+// partitions, wasted bits, all four channel assignments - a side channel is one bit wider
+// than the stream, 33 bits at 32 - and 4..32 bps) and verifies the frame CRC-16 and the
+// STREAMINFO MD5 of the decoded signal, which is the known-answer test for the three
+// reference clips.
+//
+// The bytes come from strangers (tests/test_audio_formats_cpu.py, tests/test_audio_hostile_cpu.py,
+// tools/audio_io_harness.c).  What that costs the decoder:
+//  - no header field sizes an allocation: STREAMINFO's total is a hint below a fixed cap, the
+//    output grows geometrically with what has actually been decoded;
+//  - every reconstructed sample is checked against the range of its subframe before the next
+//    prediction uses it, so the predictor sums stay far inside 64 bits (32 coefficients of 15
+//    bits x samples of 33 bits < 2^53) and a stream that leaves the range is a format error
+//    (the frame's CRC-16 can only be checked after the whole frame has been predicted);
+//  - a frame that names its own sample size or rate must name STREAMINFO's (the scale factor
+//    and the MD5 byte width come from there), and the bytes must end with the last frame.
 #include <stdint.h>
 #include <stdlib.h>
 #include <string.h>
@@ -53,6 +65,7 @@ static void md5_block(md5_t* m, const uint8_t* p) {
 static void md5_init(md5_t* m) { m->a = 0x67452301; m->b = 0xefcdab89; m->c = 0x98badcfe; m->d = 0x10325476; m->len = 0; m->fill = 0; }
 static void md5_update(md5_t* m, const uint8_t* p, size_t n) {
   m->len += n;
+  if (m->fill == 0) for (; n >= 64; p += 64, n -= 64) md5_block(m, p);  // whole blocks straight from the caller's buffer
   while (n) {
     size_t k = 64 - m->fill; if (k > n) k = n;
     memcpy(m->buf + m->fill, p, k); m->fill += (uint32_t)k; p += k; n -= k;
@@ -94,6 +107,11 @@ static inline int32_t br_sbits(br_t* b, int n) {
   uint32_t v = br_bits(b, n);
   if (n < 32 && (v >> (n - 1))) v |= ~0u << n;
   return (int32_t)v;
+}
+static inline int64_t br_sample(br_t* b, int n) {  // a signed sample of 1..33 bits (33: the side channel of a 32-bit stream)
+  if (n <= 32) return br_sbits(b, n);
+  const int64_t top = br_bits(b, 1) ? -((int64_t)1 << 32) : 0;
+  return top + (int64_t)br_bits(b, 32);
 }
 static inline uint32_t br_unary(br_t* b) {  // count zeros before a one
   uint32_t q = 0;
@@ -150,6 +168,7 @@ static int flac_residual(br_t* b, int64_t* out, int blocksize, int order) {
       for (int i = 0; i < cnt; ++i) {
         uint32_t q = br_unary(b);
         uint32_t r = k ? br_bits(b, k) : 0;
+        if (q > (0xffffffffu >> k)) return -1;  // a residual is a 32-bit number
         uint32_t u = (q << k) | r;
         out[idx++] = (int32_t)(u >> 1) ^ -(int32_t)(u & 1);
       }
@@ -159,37 +178,41 @@ static int flac_residual(br_t* b, int64_t* out, int blocksize, int order) {
   return 0;
 }
 
+// One subframe of `bps` bits (1..33).  Every sample leaves here inside [-2^(bps-1), 2^(bps-1)): warm-up, constant and verbatim samples
+// by the width they are read with, predicted ones by the check in RANGE - which is also what keeps the sums below from overflowing.
+#define RANGE(v) do { if ((v) < lo || (v) > hi) return -1; } while (0)
 static int flac_subframe(br_t* b, int64_t* out, int blocksize, int bps) {
   if (br_bits(b, 1)) return -1;  // padding bit must be 0
   int type = (int)br_bits(b, 6);
   int wasted = 0;
-  if (br_bits(b, 1)) { wasted = 1 + (int)br_unary(b); bps -= wasted; }
+  if (br_bits(b, 1)) {
+    uint32_t w = br_unary(b);
+    if (w >= (uint32_t)bps - 1) return -1;  // at least one bit is left
+    wasted = 1 + (int)w; bps -= wasted;
+  }
   if (bps <= 0) return -1;
+  const int64_t hi = ((int64_t)1 << (bps - 1)) - 1, lo = -hi - 1;
   if (type == 0) {  // CONSTANT
-    int64_t v = br_sbits(b, bps > 32 ? 32 : bps);
+    int64_t v = br_sample(b, bps);
     for (int i = 0; i < blocksize; ++i) out[i] = v;
   } else if (type == 1) {  // VERBATIM
-    for (int i = 0; i < blocksize; ++i) out[i] = br_sbits(b, bps > 32 ? 32 : bps);
+    for (int i = 0; i < blocksize; ++i) out[i] = br_sample(b, bps);
   } else if (type >= 8 && type <= 12) {  // FIXED
     int order = type - 8;
     if (order > blocksize) return -1;
-    for (int i = 0; i < order; ++i) out[i] = br_sbits(b, bps > 32 ? 32 : bps);
+    for (int i = 0; i < order; ++i) out[i] = br_sample(b, bps);
     if (flac_residual(b, out, blocksize, order)) return -1;
-    for (int i = order; i < blocksize; ++i) {
-      int64_t p = 0;
-      switch (order) {
-        case 1: p = out[i-1]; break;
-        case 2: p = 2*out[i-1] - out[i-2]; break;
-        case 3: p = 3*out[i-1] - 3*out[i-2] + out[i-3]; break;
-        case 4: p = 4*out[i-1] - 6*out[i-2] + 4*out[i-3] - out[i-4]; break;
-        default: break;
-      }
-      out[i] += p;
+    switch (order) {
+      case 0: for (int i = 0; i < blocksize; ++i) { RANGE(out[i]); } break;
+      case 1: for (int i = 1; i < blocksize; ++i) { int64_t v = out[i] + out[i-1]; RANGE(v); out[i] = v; } break;
+      case 2: for (int i = 2; i < blocksize; ++i) { int64_t v = out[i] + 2*out[i-1] - out[i-2]; RANGE(v); out[i] = v; } break;
+      case 3: for (int i = 3; i < blocksize; ++i) { int64_t v = out[i] + 3*out[i-1] - 3*out[i-2] + out[i-3]; RANGE(v); out[i] = v; } break;
+      default: for (int i = 4; i < blocksize; ++i) { int64_t v = out[i] + 4*out[i-1] - 6*out[i-2] + 4*out[i-3] - out[i-4]; RANGE(v); out[i] = v; } break;
     }
   } else if (type >= 32) {  // LPC
     int order = (type & 31) + 1;
     if (order > blocksize) return -1;
-    for (int i = 0; i < order; ++i) out[i] = br_sbits(b, bps > 32 ? 32 : bps);
+    for (int i = 0; i < order; ++i) out[i] = br_sample(b, bps);
     int prec = (int)br_bits(b, 4) + 1;
     if (prec == 16) return -1;
     int shift = br_sbits(b, 5);
@@ -200,7 +223,9 @@ static int flac_subframe(br_t* b, int64_t* out, int blocksize, int bps) {
     for (int i = order; i < blocksize; ++i) {
       int64_t s = 0;
       for (int j = 0; j < order; ++j) s += (int64_t)coef[j] * out[i-1-j];
-      out[i] += s >> shift;
+      const int64_t v = out[i] + (s >> shift);
+      RANGE(v);
+      out[i] = v;
     }
   } else {
     return -1;  // reserved
@@ -208,6 +233,7 @@ static int flac_subframe(br_t* b, int64_t* out, int blocksize, int bps) {
   if (wasted) for (int i = 0; i < blocksize; ++i) out[i] *= ((int64_t)1 << wasted);
   return b->err ? -1 : 0;
 }
+#undef RANGE
 
 // Decodes a whole FLAC stream.  Returns 0 or a negative WIS_E_* code.
 static int flac_decode(const uint8_t* data, size_t n, float** pcm_out, int64_t* n_out, int* sr_out, int* md5_ok) {
@@ -234,9 +260,10 @@ static int flac_decode(const uint8_t* data, size_t n, float** pcm_out, int64_t* 
     }
     off += blen;
   }
-  if (!have_si || ch < 1 || ch > 8 || bps < 4 || bps > 32 || max_bs < 16) return WIS_E_FORMAT;
+  if (!have_si || ch < 1 || ch > 8 || bps < 4 || bps > 32 || max_bs < 16 || sr < 1) return WIS_E_FORMAT;
 
-  size_t cap = total ? (size_t)total : (size_t)1 << 20;
+  // STREAMINFO's total is a 36-bit number anybody can write: a hint up to 2^22 samples (16 MiB), beyond that the buffer grows with the decoded audio
+  size_t cap = (total && total < ((uint64_t)1 << 22)) ? (size_t)total : (size_t)1 << 20;
   float* pcm = (float*)malloc(cap * sizeof(float) + 16);
   int64_t* sub = (int64_t*)malloc((size_t)ch * 65536 * sizeof(int64_t));
   if (!pcm || !sub) { free(pcm); free(sub); return WIS_E_NOMEM; }
@@ -245,13 +272,13 @@ static int flac_decode(const uint8_t* data, size_t n, float** pcm_out, int64_t* 
   const float scale = 1.0f / (float)((int64_t)1 << (bps - 1));
   const int bytes_ps = (bps + 7) / 8;
 
-  while (off + 2 <= n) {
-    if (!(data[off] == 0xff && (data[off+1] & 0xfe) == 0xf8)) { rc = WIS_E_FORMAT; break; }
+  while (off < n) {
+    if (off + 2 > n || !(data[off] == 0xff && (data[off+1] & 0xfe) == 0xf8)) { rc = WIS_E_FORMAT; break; }
     br_t b = {data + off, n - off, 0, 0};
     br_bits(&b, 15); br_bits(&b, 1);
     int bs_code = (int)br_bits(&b, 4), sr_code = (int)br_bits(&b, 4);
     int ch_code = (int)br_bits(&b, 4), bps_code = (int)br_bits(&b, 3);
-    br_bits(&b, 1);
+    if (br_bits(&b, 1)) { rc = WIS_E_FORMAT; break; }  // reserved
     // UTF-8 style coded frame/sample number
     uint32_t lead = br_bits(&b, 8); int extra = 0;
     if (lead & 0x80) { while (lead & (0x80u >> extra)) ++extra; if (extra < 2 || extra > 7) { rc = WIS_E_FORMAT; break; } --extra; }
@@ -263,9 +290,15 @@ static int flac_decode(const uint8_t* data, size_t n, float** pcm_out, int64_t* 
     else if (bs_code == 7) blocksize = (int)br_bits(&b, 16) + 1;
     else if (bs_code >= 8) blocksize = 256 << (bs_code - 8);
     else { rc = WIS_E_FORMAT; break; }
-    if (sr_code == 12) br_bits(&b, 8); else if (sr_code == 13 || sr_code == 14) br_bits(&b, 16);
+    static const int sr_tab[12] = {0, 88200, 176400, 192000, 8000, 16000, 22050, 24000, 32000, 44100, 48000, 96000};
+    int fsr = sr_code < 12 ? sr_tab[sr_code] : sr_code == 12 ? (int)br_bits(&b, 8) * 1000 : sr_code == 13 ? (int)br_bits(&b, 16)
+            : sr_code == 14 ? (int)br_bits(&b, 16) * 10 : -1;
     static const int bps_tab[8] = {0, 8, 12, -1, 16, 20, 24, 32};
-    int fbps = bps_tab[bps_code]; if (fbps == 0) fbps = bps; if (fbps < 0) { rc = WIS_E_FORMAT; break; }
+    int fbps = bps_tab[bps_code];
+    // 0 = "see STREAMINFO"; a frame that names its own rate or sample size names STREAMINFO's, where the scale and the MD5 width come from
+    if (fsr == 0) fsr = sr;
+    if (fbps == 0) fbps = bps;
+    if (fsr != sr || fbps != bps) { rc = WIS_E_FORMAT; break; }
     size_t hdr_bytes = b.pos >> 3;
     uint32_t c8 = br_bits(&b, 8);
     if (b.err || crc8(data + off, hdr_bytes) != c8) { rc = WIS_E_FORMAT; break; }
@@ -283,12 +316,18 @@ static int flac_decode(const uint8_t* data, size_t n, float** pcm_out, int64_t* 
     if (b.err || crc16(data + off, body) != c16) { rc = WIS_E_FORMAT; break; }
     off += body + 2;
     int64_t* s0 = sub; int64_t* s1 = sub + 65536;
-    if (ch_code == 8)       for (int i = 0; i < blocksize; ++i) s1[i] = s0[i] - s1[i];
-    else if (ch_code == 9)  for (int i = 0; i < blocksize; ++i) s0[i] = s0[i] + s1[i];
-    else if (ch_code == 10) for (int i = 0; i < blocksize; ++i) {
-      int64_t mid = s0[i], side = s1[i];
-      mid = (mid << 1) | (side & 1);
-      s0[i] = (mid + side) >> 1; s1[i] = (mid - side) >> 1;
+    if (ch_code >= 8) {  // undo the stereo decorrelation; what comes out is a left and a right sample of the stream's width, or the file is refused
+      const int64_t hi = ((int64_t)1 << (bps - 1)) - 1, lo = -hi - 1;
+      int64_t bad = 0;
+      if (ch_code == 8)      for (int i = 0; i < blocksize; ++i) { int64_t r = s0[i] - s1[i]; bad |= (r < lo) | (r > hi); s1[i] = r; }
+      else if (ch_code == 9) for (int i = 0; i < blocksize; ++i) { int64_t l = s0[i] + s1[i]; bad |= (l < lo) | (l > hi); s0[i] = l; }
+      else for (int i = 0; i < blocksize; ++i) {
+        int64_t side = s1[i], mid = s0[i] * 2 + (side & 1);
+        int64_t l = (mid + side) >> 1, r = (mid - side) >> 1;
+        bad |= (l < lo) | (l > hi) | (r < lo) | (r > hi);
+        s0[i] = l; s1[i] = r;
+      }
+      if (bad) { rc = WIS_E_FORMAT; break; }
     }
     if (nsamp + (size_t)blocksize > cap) {
       cap = (nsamp + blocksize) * 2;
@@ -296,17 +335,19 @@ static int flac_decode(const uint8_t* data, size_t n, float** pcm_out, int64_t* 
       if (!np_) { rc = WIS_E_NOMEM; break; }
       pcm = np_;
     }
+    uint8_t le[4096]; size_t nle = 0;  // the interleaved little-endian samples the signature is taken of, handed to MD5 in runs of blocks
     for (int i = 0; i < blocksize; ++i) {
       // mono mix = mean over channels in float, matching librosa's to_mono on /2^(bps-1) floats
       float acc = 0.f;
       for (int c = 0; c < nch; ++c) {
         int64_t v = sub[(size_t)c * 65536 + i];
-        uint8_t le[4]; for (int k = 0; k < bytes_ps; ++k) le[k] = (uint8_t)((uint64_t)v >> (8*k));
-        md5_update(&md5, le, (size_t)bytes_ps);
+        for (int k = 0; k < bytes_ps; ++k) le[nle++] = (uint8_t)((uint64_t)v >> (8*k));
         acc += (float)v * scale;
       }
       pcm[nsamp + i] = nch == 1 ? acc : acc / (float)nch;
+      if (nle + 32 > sizeof le) { md5_update(&md5, le, nle); nle = 0; }  // (32: the widest sample frame, 8 channels of 4 bytes)
     }
+    md5_update(&md5, le, nle);
     nsamp += (size_t)blocksize;
   }
   free(sub);
@@ -332,10 +373,10 @@ static int wav_decode(const uint8_t* d, size_t n, float** pcm_out, int64_t* n_ou
     if (!memcmp(d + off, "fmt ", 4) && len >= 16) {
       fmt = body[0] | (body[1] << 8); ch = body[2] | (body[3] << 8); sr = (int)rd32(body + 4); bits = body[14] | (body[15] << 8);
       if (fmt == 0xfffe && len >= 26) fmt = body[24] | (body[25] << 8);  // WAVE_FORMAT_EXTENSIBLE sub-format
-    } else if (!memcmp(d + off, "data", 4)) { data = body; dlen = len; break; }
+    } else if (!memcmp(d + off, "data", 4)) { data = body; dlen = len ? len : avail; break; }  // ... or 0: the audio is the rest of the file
     off += 8 + (size_t)len + (len & 1);
   }
-  if (!data || ch < 1 || !(fmt == 1 || fmt == 3)) return WIS_E_FORMAT;
+  if (!data || ch < 1 || sr < 1 || !(fmt == 1 || fmt == 3)) return WIS_E_FORMAT;
   if (fmt == 3 && bits != 32) return WIS_E_FORMAT;
   if (fmt == 1 && bits != 8 && bits != 16 && bits != 24 && bits != 32) return WIS_E_FORMAT;
   int bps = bits / 8; size_t frames = dlen / ((size_t)bps * ch);
