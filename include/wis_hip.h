@@ -475,6 +475,24 @@ int wis_op_gemv_qkv(int device, const float* x, const float* gamma, const float*
 int wis_op_gemv_out_cq(int device, const void* a_f16, const float* x0, const void* Wo_f16, const float* bo, const void* Wq_f16, const float* bq,
                        const float* gamma, const float* beta, float* x1, float* stat, float* q, float* q2, float* qcs, float* qb,
                        int M, int d, int force_frag);
+/* ONE projection stage of the batched decode route (9 .. 96 rows), assembled by the builders the decoder forward itself uses; W f16 [N][K] row-major and
+ * bias f32 [N] are prepared as the loader does (w8 != 0: quantised to per-row int8 first; stages 1 / 2: the LayerNorm gamma / beta folded in).
+ *   stage 0  residual: y f32 [M][N] += x W^T + bias in place; y_xf (optional) the produced rows' f16 fragment image of ceil(M / 16) row blocks
+ *            ([N/32][blocks][64][8], rows >= M untouched); stat_out (optional) f32 [M][N/16][2] = per 16 columns (sum, sum of squares about the tile mean)
+ *   stage 1  LayerNorm-folded + GELU, f16 rows into the fragment image y_xf (FFN1); y unused
+ *   stage 2  LayerNorm-folded, y f32 [M][N] (cross-Q, vocabulary)
+ * x, x_is_image = 0: row-major [M][K], f16 for stage 0, f32 for stages 1 / 2 (the tap builds image and partials as wis_op_gemv does; xmb = 0).
+ * x_is_image = 1: a ready f16 fragment image of xmb row blocks (0: ceil(M / 16)) and, for stages 1 / 2, stat_in f32 [M][K/16][2]: what an earlier stage 0
+ * call or wis_op_dec_embed left in y_xf / stat_out - the hand-off between the stages of a layer.
+ * ksplit: -1 = what the decoder forward asks for (stage 0: its FFN2 rule, two K slices where K / 128 is even - honoured by the launcher at one row block;
+ * else none), 1 .. 8 = that many slices; with slices the launch runs twice on one set of tickets (stage 0: the residual rows put back in between). */
+int wis_op_gemv_frag_stage(int device, int stage, const void* x, int x_is_image, int xmb, const float* stat_in, const float* gamma, const float* beta,
+                           const void* W_f16, const float* bias, int w8, float* y, void* y_xf_f16, float* stat_out, int M, int N, int K, int ksplit);
+/* the decoder's embedding launches: x f32 [M][d] = emb[tok[m]] + pos_emb[pos[m]] (f16 tables [n_vocab][d], [n_ctx][d]; tok / pos HOST arrays, checked).
+ * xf given (with stat): the batched form - x, the rows' f16 fragment image of ceil(M / 16) row blocks and partials f32 [M][d/16][2] in one pass (xh null);
+ * else the form of <= 8 rows: x and, if xh is given, its f16 copy [M][d] (stat null). */
+int wis_op_dec_embed(int device, const void* emb_f16, const void* pos_f16, const int32_t* tok, const int32_t* pos, float* x, void* xh_f16, void* xf_f16,
+                     float* stat, int M, int d, int n_vocab, int n_ctx);
 
 /* ---- taps of what the encoder and the cross K/V projection launch (tests/test_gpu_enc_ops.py).  The same rule: arguments and the loader's preparation
  * only - the GEMM descriptions are the helpers run_encoder itself calls, the tile and kernel are chosen by launch_gemm_* / gemm_pick_tile from the

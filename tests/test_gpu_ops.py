@@ -177,7 +177,10 @@ def test_enc_attention(lib, B, T, H):
                                          # 49-96 rows (up to 16 utterances x beam 5): four to six row blocks, six-deep fragment ring
                                          (64, 1280, 1280, 8 | 4), (80, 5120, 1280, 8 | 1), (80, 1280, 5120, 2), (96, 3840, 1280, 8 | 4), (80, 1280, 1280, 32 | 2),
                                          (72, 768, 384, 8 | 4),
-                                         # K = 4d over four workgroups per n-tile with the in-launch merge (two launches on one set of tickets where nothing accumulates)
+                                         # K = 4d on f16 rows asks for the step's K split (two slices), but from 17 rows on and up to 85 n-tiles launch_gemv_frag runs the
+                                         # M split instead: these three land on gemv_frag_ms_kernel<1 | 2 | 1> (3, 3 and 2 row-block groups, no K split, no merge).  Of this
+                                         # list only (16, 1280, 4096, 2) above splits K: gemv_frag_kernel<1, 8>, two slices merged in the launch.  The merge at two and at
+                                         # four slices, with its tickets re-armed between two launches: tests/test_gpu_dec_frag_ops.py
                                          (40, 1280, 5120, 4), (96, 1280, 5120, 0), (24, 1024, 4096, 1),
                                          # two n-tiles per workgroup (more than 256 n-tiles behind a folded LayerNorm): int8 weights, the vocabulary shape, ragged rows
                                          (40, 5120, 1280, 32 | 8 | 1), (80, 51872, 1280, 8 | 4), (33, 8192, 1280, 8 | 4),

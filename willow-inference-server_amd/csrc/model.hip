@@ -546,6 +546,7 @@ int load_weights(wis_model* m, const Loader& L) {
   return WIS_OK;
 }
 
+static int frag_ksplit_setting();      // (beside dec_forward_frag)
 int alloc_buffers(wis_model* m) {
   const wis_config_t& c = m->cfg;
   const int d = c.d_model, H = c.n_heads, Bm = c.max_batch, T = c.n_audio_ctx, L = c.n_dec_layers;
@@ -614,10 +615,8 @@ int alloc_buffers(wis_model* m) {
   WIS_RET(dalloc(m, &m->counters, (size_t)Bg * H));
   WIS_HIP_CHECK(hipMemsetAsync(m->counters, 0, (size_t)Bg * H * 4, m->st));
   {
-    // measured (decode ms per utterance batch, 17 steps): 8 utterances 40.7 unsplit / 38.6 two slices / 38.9 four; 12: 46.7 two / 46.9 four;
-    // 16: 60.9 unsplit / 58.7 two / 59.5 four
-    static const int env_ks = getenv("WIS_FRAG_KSPLIT") ? atoi(getenv("WIS_FRAG_KSPLIT")) : 2;      // 1: no split (A/B switch)
-    m->gf_ksplit = env_ks >= 1 && env_ks <= 8 ? env_ks : 2;
+    // (K split of the batched FFN2: frag_ksplit_setting / ffn2_ksplit, beside dec_forward_frag)
+    m->gf_ksplit = frag_ksplit_setting();
     const size_t nt = (size_t)cdiv(d, 16);
     WIS_RET(dalloc(m, &m->gf_part, nt * m->gf_ksplit * (MAX_ROWS / 16) * 64 * 4));
     WIS_RET(dalloc(m, &m->gf_cnt, nt));
@@ -862,6 +861,42 @@ static void out_cq_frag3(const DecLayerW& w, const f16* af, const f16* xf, float
   g3[2].K = d; g3[2].bias = nullptr; g3[2].y = q2; g3[2].wks = w.cqo.K / 32; g3[2].wk0 = d / 32;
 }
 
+// The other stages of the batched route, as dec_forward_frag and the wis_op_gemv_frag_stage tap launch them (ymb = the rows' own row blocks):
+//   frag_resid        y += W x + b in place (cross-attention out-projection, FFN2; the self-attention out-projection when the fold is off), the rows' f16
+//                     fragment image and per-16-column LayerNorm partials for the projection that follows (either may be null)
+//   frag_ln_f32       the LayerNorm-folded projection into fp32 rows (cross-Q when the fold is off, the vocabulary): statistics from the producer's partials
+//   frag_ln_gelu_xf   FFN1: LayerNorm-folded, GELU, the f16 rows straight into FFN2's fragment image
+static GemvP frag_resid(const DecProj& p, const f16* xf, float* y, f16* y_xf, float* stat_out, int M) {
+  GemvP g = gemv_frag(p, xf, M, GV_RESID);
+  g.y = y; g.y_xf = y_xf; g.ymb = g.xmb; g.stat_out = stat_out;
+  return g;
+}
+static GemvP frag_ln_f32(const DecProj& p, const f16* xf, const float* stat_in, float* y, int M) {
+  GemvP g = gemv_frag(p, xf, M, GV_LN | GV_OUT_F32);
+  g.stat_in = stat_in; g.y = y;
+  return g;
+}
+static GemvP frag_ln_gelu_xf(const DecProj& p, const f16* xf, const float* stat_in, f16* y_xf, int M) {
+  GemvP g = gemv_frag(p, xf, M, GV_LN | GV_GELU);
+  g.stat_in = stat_in; g.y = y_xf; g.ymb = g.xmb;
+  return g;
+}
+// K slices of the batched FFN2 (GemvP::ksplit).  Measured (decode ms per utterance batch, 17 steps): 8 utterances 40.7 unsplit / 38.6 two slices / 38.9 four;
+// 12: 46.7 two / 46.9 four; 16: 60.9 unsplit / 58.7 two / 59.5 four.  WIS_FRAG_KSPLIT=1: no split (A/B switch).  ffn2_ksplit: the slices a K-deep FFN2 takes -
+// the setting where the k-steps divide into slices of whole wave quarters, else 1 (launch_gemv_frag still prefers its M split from two row blocks on)
+static int frag_ksplit_setting() {
+  static const int env_ks = getenv("WIS_FRAG_KSPLIT") ? atoi(getenv("WIS_FRAG_KSPLIT")) : 2;
+  return env_ks >= 1 && env_ks <= 8 ? env_ks : 2;
+}
+static int ffn2_ksplit(int K) {
+  const int ks = frag_ksplit_setting();
+  return ks > 1 && (K / 32) % (4 * ks) == 0 ? ks : 1;
+}
+// part: [N/16][ks][xmb][64] float4 slice sums; cnt: [N/16] tickets, zeroed once
+static void frag_set_ksplit(GemvP& g, int ks, float* part, unsigned* cnt) {
+  if (ks > 1) { g.ksplit = ks; g.kpart = part; g.kcnt = cnt; }
+}
+
 static int dec_forward_frag(wis_model* m, int M, int R, int B, bool want_logits, int sstride, int rmul, int chunks, const TreeWin* tw = nullptr) {
   const wis_config_t& c = m->cfg; hipStream_t st = m->st;
   const int d = c.d_model, H = c.n_heads, T = c.n_audio_ctx, ctx = c.n_text_ctx, MB = cdiv(M, 16);
@@ -900,11 +935,9 @@ static int dec_forward_frag(wis_model* m, int M, int R, int B, bool want_logits,
       cf.gran = m->spin_now ? m->ca_gran : nullptr; cf.q2 = m->dq2; cf.xres_is_stat = 1;
       WIS_RET(launch_dec_cross_attn(st, cf));
     } else {
-    g = gemv_frag(w.out, m->daoxf, M, GV_RESID);
-    g.y = m->dx; g.y_xf = m->dxf; g.ymb = MB; g.stat_out = m->dstat;
+    g = frag_resid(w.out, m->daoxf, m->dx, m->dxf, m->dstat, M);
     WIS_RET(launch_gemv_frag(st, g));
-    g = gemv_frag(w.cq, m->dxf, M, GV_LN | GV_OUT_F32);
-    g.stat_in = m->dstat; g.y = m->dq;
+    g = frag_ln_f32(w.cq, m->dxf, m->dstat, m->dq, M);
     WIS_RET(launch_gemv_frag(st, g));
     // (wis_align decodes a batch in groups of utterances: the group's first utterance picks the K / V block the rows' b = 0 reads; 0 otherwise)
     const size_t ku = (size_t)m->al.kv_ub0 * H * T * 64, vu = (size_t)m->al.kv_ub0 * H * 64 * m->Tpad;
@@ -913,20 +946,19 @@ static int dec_forward_frag(wis_model* m, int M, int R, int B, bool want_logits,
     WIS_RET(launch_dec_cross_attn(st, cp));
     if (m->al.capture) WIS_RET(align_capture_q(m, l, M));      // wis_align: m->dq holds this layer's finished cross-Q until the next layer's QKV projection
     }
-    g = gemv_frag(w.cout, m->daoxf, M, GV_RESID);
-    g.y = m->dx; g.y_xf = m->dxf; g.ymb = MB; g.stat_out = m->dstat; g.prof = pr ? pr + 80 : nullptr;
+    g = frag_resid(w.cout, m->daoxf, m->dx, m->dxf, m->dstat, M);
+    g.prof = pr ? pr + 80 : nullptr;
     WIS_RET(launch_gemv_frag(st, g));
-    g = gemv_frag(w.f1, m->dxf, M, GV_LN | GV_GELU);
-    g.stat_in = m->dstat; g.y = m->dhxf; g.ymb = MB; g.prof = pr ? pr + 96 : nullptr;
+    g = frag_ln_gelu_xf(w.f1, m->dxf, m->dstat, m->dhxf, M);
+    g.prof = pr ? pr + 96 : nullptr;
     WIS_RET(launch_gemv_frag(st, g));
-    g = gemv_frag(w.f2, m->dhxf, M, GV_RESID);
-    g.y = m->dx; g.y_xf = m->dxf; g.ymb = MB; g.stat_out = m->dstat; g.prof = pr ? pr + 112 : nullptr;
-    if (m->gf_ksplit > 1 && (4 * d / 32) % (4 * m->gf_ksplit) == 0) { g.ksplit = m->gf_ksplit; g.kpart = m->gf_part; g.kcnt = m->gf_cnt; }      // K = 4d over `ksplit` workgroups per n-tile
+    g = frag_resid(w.f2, m->dhxf, m->dx, m->dxf, m->dstat, M);
+    g.prof = pr ? pr + 112 : nullptr;
+    frag_set_ksplit(g, ffn2_ksplit(w.f2.K), m->gf_part, m->gf_cnt);      // K = 4d over `ksplit` workgroups per n-tile
     WIS_RET(launch_gemv_frag(st, g));
   }
   if (want_logits) {
-    GemvP g = gemv_frag(m->proj, m->dxf, M, GV_LN | GV_OUT_F32);
-    g.stat_in = m->dstat; g.y = m->logits;
+    GemvP g = frag_ln_f32(m->proj, m->dxf, m->dstat, m->logits, M);
     WIS_RET(launch_gemv_frag(st, g));
   }
   return WIS_OK;

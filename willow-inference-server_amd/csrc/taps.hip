@@ -380,13 +380,78 @@ int wis_op_gemv(int device, const void* x, const float* gamma, const float* beta
   if (ln) WIS_RET(t.get(&stt, (size_t)M * (K / 16) * 2));
   WIS_RET(launch_xf_pack(st, x, ln ? 0 : 1, xfr, ln ? stt : nullptr, M, K, MBf));
   g.x = xfr; g.xmb = MBf; g.stat_in = stt;
-  if (!ln && K >= 4096 && (K / 32) % 16 == 0) {      // the product's rule for the K = 4d projection: four K slices per n-tile, merged in the launch
+  // a K = 4d projection on f16 rows (FFN2) asks for dec_forward_frag's K split (ffn2_ksplit: two slices unless WIS_FRAG_KSPLIT says otherwise).  As in the
+  // step, launch_gemv_frag honours it only at one row block (<= 16 rows: gemv_frag_kernel, grid.y = slices, merged in the launch); from 17 rows on and up to
+  // 85 n-tiles it runs gemv_frag_ms_kernel (row-block groups, no K split) instead.  Other slice counts: wis_op_gemv_frag_stage.
+  const int ks = (!ln && K >= 4096) ? ffn2_ksplit(K) : 1;
+  if (ks > 1) {
     const size_t nt = (size_t)cdiv(N, 16);
-    WIS_RET(t.get(&g.kpart, nt * 4 * MBf * 64 * 4)); WIS_RET(t.get(&g.kcnt, nt, true));
-    g.ksplit = 4;
+    float* part = nullptr; unsigned* cnt = nullptr;
+    WIS_RET(t.get(&part, nt * ks * MBf * 64 * 4)); WIS_RET(t.get(&cnt, nt, true));
+    frag_set_ksplit(g, ks, part, cnt);
     if (!(flags & GV_RESID)) WIS_RET(launch_gemv_frag(st, g));      // a first launch on the same tickets: they must re-arm themselves
   }
   return t.finish(launch_gemv_frag(st, g));
+}
+
+// One projection stage of the batched route, assembled by dec_forward_frag's own builders (model.hip frag_resid / frag_ln_gelu_xf / frag_ln_f32) on a matrix
+// prepared as the loader prepares it; launch_gemv_frag picks the kernel.  include/wis_hip.h has the contract.  Nothing but the stage's outputs is written.
+int wis_op_gemv_frag_stage(int device, int stage, const void* x, int x_is_image, int xmb, const float* stat_in, const float* gamma, const float* beta,
+                           const void* W_f16, const float* bias, int w8, float* y, void* y_xf, float* stat_out, int M, int N, int K, int ksplit) {
+  Tap t(device, "wis_op_gemv_frag_stage"); WIS_RET(t.rc);
+  hipStream_t st = t.st;
+  const bool ln = stage == 1 || stage == 2;
+  if (stage < 0 || stage > 2 || !x || !W_f16 || !bias || (ln && (!gamma || !beta)) || (stage != 1 && !y) || (stage == 1 && !y_xf) || (x_is_image && ln && !stat_in) ||
+      M < 1 || M > 8 * MAX_ROWS || N < 4 || K < 32 || K % 32 || ksplit < -1 || ksplit == 0 || ksplit > 8 || xmb < 0 || (xmb && !x_is_image)) {
+    set_error("wis_op_gemv_frag_stage: bad argument"); return WIS_E_ARG;
+  }
+  const int Npad = cdiv(N, 16) * 16, MB = xmb ? xmb : cdiv(M, 16);
+  f16 *wp = nullptr, *wtmp = nullptr, *xfr = nullptr; float *wsc = nullptr, *b2 = nullptr, *cs = nullptr, *stt = nullptr;
+  WIS_RET(t.get(&wp, (size_t)Npad * K)); WIS_RET(t.get(&wtmp, (size_t)N * K)); WIS_RET(t.get(&b2, (size_t)Npad, true)); WIS_RET(t.get(&cs, (size_t)Npad, true));
+  if (w8) WIS_RET(t.get(&wsc, (size_t)Npad));
+  hipMemcpyAsync(wtmp, W_f16, (size_t)N * K * 2, hipMemcpyDeviceToDevice, st);
+  hipMemcpyAsync(b2, bias, (size_t)N * 4, hipMemcpyDeviceToDevice, st);
+  WIS_RET(prep_projection(st, wtmp, N, Npad, K, 0, 1.f, ln ? gamma : nullptr, beta, b2, cs, wp, wsc, 16));
+  const DecProj proj{wp, wsc, b2, ln ? cs : nullptr, N, K, 16};
+  const f16* xf = reinterpret_cast<const f16*>(x);
+  if (!x_is_image) {      // row-major rows (fp32 behind a LayerNorm, else f16) -> fragment image (+ partials), as wis_op_gemv does
+    WIS_RET(t.get(&xfr, xf_elems(K, MB), true));
+    if (ln) WIS_RET(t.get(&stt, (size_t)M * (K / 16) * 2));
+    WIS_RET(launch_xf_pack(st, x, ln ? 0 : 1, xfr, stt, M, K, MB));
+    xf = xfr; stat_in = stt;
+  }
+  GemvP g = stage == 0 ? frag_resid(proj, xf, y, reinterpret_cast<f16*>(y_xf), stat_out, M)
+          : stage == 1 ? frag_ln_gelu_xf(proj, xf, stat_in, reinterpret_cast<f16*>(y_xf), M) : frag_ln_f32(proj, xf, stat_in, y, M);
+  if (xmb) g.xmb = xmb;      // (a ready image of another row-block count: launch_gemv_frag's answer)
+  const int ks = ksplit < 0 ? (stage == 0 ? ffn2_ksplit(K) : 1) : ksplit;
+  if (ks > 1) {
+    // two launches on one set of tickets (they must re-arm themselves); the residual rows are put back in between
+    const size_t nt = (size_t)cdiv(N, 16);
+    float *part = nullptr, *y0 = nullptr; unsigned* cnt = nullptr;
+    WIS_RET(t.get(&part, nt * ks * MB * 64 * 4)); WIS_RET(t.get(&cnt, nt, true));
+    frag_set_ksplit(g, ks, part, cnt);
+    if (stage == 0) { WIS_RET(t.get(&y0, (size_t)M * N)); hipMemcpyAsync(y0, y, (size_t)M * N * 4, hipMemcpyDeviceToDevice, st); }
+    WIS_RET(launch_gemv_frag(st, g));
+    if (stage == 0) hipMemcpyAsync(y, y0, (size_t)M * N * 4, hipMemcpyDeviceToDevice, st);
+  }
+  return t.finish(launch_gemv_frag(st, g));
+}
+
+// The two embedding launches of the step on the caller's tables: launch_dec_embed_xf (xf given: x, the rows' fragment image of ceil(M / 16) row blocks and
+// their partials - the batched route) or launch_dec_embed (x and, optionally, the f16 copy xh).  tok / pos are HOST arrays, range-checked here.
+int wis_op_dec_embed(int device, const void* emb_f16, const void* pos_f16, const int32_t* tok, const int32_t* pos, float* x, void* xh_f16, void* xf_f16, float* stat,
+                     int M, int d, int n_vocab, int n_ctx) {
+  Tap t(device, "wis_op_dec_embed"); WIS_RET(t.rc);
+  if (!emb_f16 || !pos_f16 || !tok || !pos || !x || M < 1 || M > MAX_ROWS || d < 32 || d % 32 || n_vocab < 1 || n_ctx < 1 || (xf_f16 ? (!stat || xh_f16 != nullptr) : stat != nullptr)) {
+    set_error("wis_op_dec_embed: bad argument"); return WIS_E_ARG;
+  }
+  for (int r = 0; r < M; ++r) if (tok[r] < 0 || tok[r] >= n_vocab || pos[r] < 0 || pos[r] >= n_ctx) { set_error("wis_op_dec_embed: row %d: token %d / position %d out of range", r, tok[r], pos[r]); return WIS_E_ARG; }
+  int *d_tok = nullptr, *d_pos = nullptr;
+  WIS_RET(t.get(&d_tok, (size_t)M)); WIS_RET(t.get(&d_pos, (size_t)M));
+  WIS_HIP_CHECK(hipMemcpy(d_tok, tok, (size_t)M * 4, hipMemcpyHostToDevice)); WIS_HIP_CHECK(hipMemcpy(d_pos, pos, (size_t)M * 4, hipMemcpyHostToDevice));
+  const f16 *e = reinterpret_cast<const f16*>(emb_f16), *pe = reinterpret_cast<const f16*>(pos_f16);
+  if (xf_f16) return t.finish(launch_dec_embed_xf(t.st, e, pe, d_tok, d_pos, x, reinterpret_cast<f16*>(xf_f16), stat, M, d, cdiv(M, 16)));
+  return t.finish(launch_dec_embed(t.st, e, pe, d_tok, d_pos, x, M, d, reinterpret_cast<f16*>(xh_f16)));
 }
 
 // The single-chunk f16-activation form of launch_gemv (the one-utterance FFN2 and cross-attention out-projection: K = 5120 / 1280) on sixteen-column
