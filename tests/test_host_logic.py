@@ -44,10 +44,132 @@ def test_library_exports_only_the_c_abi_and_passes_the_isa_lint(lib):
     mod = importlib.util.module_from_spec(spec)
     spec.loader.exec_module(mod)
     objs = sorted(glob.glob(os.path.join(ROOT, "willow-inference-server_amd", "build", "*.hip.o")))
-    assert len(objs) == 4
+    assert [os.path.basename(o) for o in objs] == sorted(s + ".o" for s in _build_py().HIP_SOURCES)      # one object per source, and no stale one beside them
     bad, rows = mod.lint(objs)
     assert len(rows) > 150 and not bad and not [r for r in rows if r[6]]
     assert sum(1 for r in rows if r[4]) > 100          # (the scan really saw the MFMA kernels)
+
+
+def _build_py():
+    """a fresh instance of willow-inference-server_amd/build.py (a test may repoint its directories)"""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("wis_build_t", os.path.join(ROOT, "willow-inference-server_amd", "build.py"))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    return mod
+
+
+# what generate.hip, taps.hip and align.hip call across objects (csrc/model.hpp), and the process-wide state behind it
+SHARED_FUNCTIONS = ["check_batch", "stage_input", "run_encoder", "run_cross_kv", "upload_rows", "single_row_setup", "dec_forward", "dec_forward_frag", "small_route",
+                    "spin_gave_up", "init_beam_state", "upload_seeds", "make_sample_cfg", "check_patience", "prep_projection", "build_cq_fold", "gemv_small", "gemv_frag",
+                    "out_cq_dual", "out_cq_frag3", "frag_resid", "frag_ln_f32", "frag_ln_gelu_xf", "ffn2_ksplit", "frag_set_ksplit", "conv1_k", "conv1_gemm", "conv2_gemm",
+                    "pack_conv1_w", "pack_conv2_w", "launch_mel_to_image", "enc_splitk", "blocks_for", "align_capture_q"]
+SHARED_STATE = ["g_spin_bh", "g_spin_mu", "g_spin_deferred", "g_active_calls"]
+
+
+def test_shared_state_and_functions_are_defined_in_exactly_one_object(lib):
+    """A `static` variable, or a function with a `static` local, copied into a header is one copy per object: three spin budgets
+    (g_spin_*) would let three callers each take all of it.  `nm` over the objects the library was linked from: every piece of
+    process-wide state, every shared function model.hpp declares without a body, and every function that owns a read-once
+    getenv() local has its definition in exactly one of them.  (Mangled names: nm's demangler gives up on a signature with an
+    _Float16 in it, and those are the ones that must not be missed.)"""
+    import glob
+    import subprocess
+    csrc = os.path.join(ROOT, "willow-inference-server_amd", "csrc")
+    syms = {}      # object -> [(type, mangled name)]
+    for o in sorted(glob.glob(os.path.join(ROOT, "willow-inference-server_amd", "build", "*.hip.o"))):
+        out = subprocess.run(["nm", "--defined-only", o], capture_output=True, text=True, check=True).stdout
+        syms[os.path.basename(o)] = [tuple(ln.split()[1:]) for ln in out.splitlines() if len(ln.split()) == 3]
+    assert len(syms) > 4
+
+    def objects_with(pred):
+        return sorted(o for o, ss in syms.items() if any(pred(t, n) for t, n in ss))
+
+    for var in SHARED_STATE:
+        assert len(objects_with(lambda t, n: t in "BbDd" and n == "_ZN3wis%d%sE" % (len(var), var))) == 1, var
+    # the shared functions: declared without a body -> one definition; a body in a header -> no static local in it
+    strip = lambda src: re.sub(r"//[^\n]*", "", src)
+    hdrs = {h: strip(open(os.path.join(csrc, h)).read()) for h in ("model.hpp", "common.hpp")}
+    for fn in SHARED_FUNCTIONS:
+        defined = objects_with(lambda t, n: t in "Tt" and re.match(r"_ZN3wisL?%d%sE" % (len(fn), fn), n))      # (L: a file-local one)
+        if re.search(r"\b%s\s*\([^;{}]*\)\s*;" % fn, hdrs["model.hpp"]):
+            assert len(defined) == 1, (fn, defined)
+            continue
+        body = next((m.group(1) for h in hdrs.values() for m in [re.search(r"\b%s\s*\([^;{}]*\)\s*\{([^}]*)\}" % fn, h)] if m), None)
+        if body is not None:
+            assert "static" not in body, fn                # (an inline copy per object: harmless only without state of its own)
+        else:
+            # not shared after all (dec_forward_frag): file-local in one source, so at most one out-of-line body (none where the compiler
+            # inlined it into its caller; its getenv local is pinned to that one object below)
+            n_bodies = sum(len(re.findall(r"\b%s\s*\([^;{}]*\)\s*\{" % fn, strip(open(os.path.join(csrc, f)).read()))) for f in os.listdir(csrc))
+            assert n_bodies == 1 and len(defined) <= 1, (fn, n_bodies, defined)
+    # the read-once switches: `static const T name = ... getenv(...)` - none in a header, and each one's storage (_ZZ<owner>E<name>), with
+    # its owner's out-of-line body (_Z<owner>) where the compiler kept one, in the object of the source that spells it
+    n_locals = 0
+    for f in sorted(os.listdir(csrc)):
+        if not f.endswith((".hip", ".hpp")):
+            continue
+        names = re.findall(r"\bstatic\s+const\s+\w+\s+(\w+)\s*=[^;]*\bgetenv\b", strip(open(os.path.join(csrc, f)).read()))
+        assert not (names and f.endswith(".hpp")), (f, names)
+        for var in names:
+            n_locals += 1
+            local = re.compile(r"_ZZ(.+)E%d%s(_\d+)?$" % (len(var), var))
+            owners = {local.match(n).group(1) for ss in syms.values() for t, n in ss if t in "BbDd" and local.match(n)}
+            assert owners, (f, var)
+            for owner in owners:      # (one per instantiation where the owner is a template: all in the source's own object)
+                holds = objects_with(lambda t, n: t in "BbDd" and local.match(n) and local.match(n).group(1) == owner)
+                assert holds == [f + ".o"], (f, var, holds)
+                assert objects_with(lambda t, n: t in "TtWw" and n == "_Z" + owner) in ([], holds), (f, var, owner)
+    assert n_locals >= 10      # (the scan saw them: SpinClaim, frag_ksplit_setting, small_route, the two forwards, generate.hip's five, ...)
+
+
+def test_build_dependencies_follow_the_include_lines():
+    """build.py digests a source with the closure of its quoted #include lines, nothing else: a tap edit cannot reach the kernel objects."""
+    bp = _build_py()
+    base = lambda paths: {os.path.basename(p) for p in paths}
+    taps, gen, sv = base(bp.include_closure("taps.hip")), base(bp.include_closure("generate.hip")), base(bp.include_closure("sv.hip"))
+    assert {"model.hpp", "tap.hpp", "kernels.hpp", "common.hpp", "wis_hip.h"} <= taps and not [f for f in taps if f.endswith(".hip")]
+    assert "model.hpp" not in sv and "tap.hpp" in sv
+    order = [os.path.basename(p) for p in bp.include_closure("taps.hip")]
+    assert order == sorted(order)          # hashed in an order that does not depend on where csrc/ and include/ lie
+    for kern in ("enc_kernels.hip", "dec_kernels.hip"):
+        own = base(bp.include_closure(kern))
+        assert own == {"common.hpp", "kernels.hpp", "wis_hip.h"}, (kern, own)
+        assert not own & ((taps | gen) - own) and not own & {"model.hpp", "tap.hpp"}
+    # no orphans: every file under csrc/ is compiled, included by something that is, or the linker's version script
+    listed = set(bp.HIP_SOURCES + bp.C_SOURCES) | {os.path.basename(bp.EXPORTS)}
+    reached = set().union(*(base(bp.include_closure(s)) for s in bp.HIP_SOURCES + bp.C_SOURCES))
+    assert sorted(set(os.listdir(bp.CSRC)) - listed - reached) == []
+    assert not [s for s in bp.HIP_SOURCES if s in reached]          # no source is another source's include
+
+
+def test_incremental_rebuild_compiles_only_what_includes_the_edit(lib, tmp_path):
+    """On a copy of csrc/ with the tree's objects beside it: nothing to do; a comment appended to taps.hip recompiles taps.hip alone;
+    then nothing again.  An object without a source (a build directory older than the split) is gone before the link."""
+    import contextlib
+    import shutil
+    bp = _build_py()
+    shutil.copytree(bp.CSRC, tmp_path / "csrc")
+    shutil.copytree(bp.OBJDIR, tmp_path / "build", ignore=lambda d, names: [n for n in names if os.path.isdir(os.path.join(d, n))])
+    os.makedirs(tmp_path / "lib")
+    shutil.copy2(bp.LIB, tmp_path / "lib")
+    bp.CSRC, bp.OBJDIR, bp.LIBDIR = str(tmp_path / "csrc"), str(tmp_path / "build"), str(tmp_path / "lib")
+    bp.LIB, bp.EXPORTS, bp.INCLUDE_DIRS[0] = os.path.join(bp.LIBDIR, "libwis_hip.so"), os.path.join(bp.CSRC, "exports.map"), bp.CSRC
+    bp.lint_objects = lambda objs: 0          # (the lint of the tree's objects is test_library_exports_only_the_c_abi_and_passes_the_isa_lint)
+
+    def compiled():
+        out = io.StringIO()
+        with contextlib.redirect_stdout(out):
+            bp.build()
+        return sorted(ln.split()[-1] for ln in out.getvalue().splitlines() if ln.startswith("[build] compiling"))
+
+    shutil.copy2(tmp_path / "build" / "model.hip.o", tmp_path / "build" / "old_unity.hip.o")
+    assert compiled() == []
+    assert not (tmp_path / "build" / "old_unity.hip.o").exists()
+    with open(tmp_path / "csrc" / "taps.hip", "a") as f:
+        f.write("// a comment\n")
+    assert compiled() == ["taps.hip"]
+    assert compiled() == []
 
 
 @pytest.mark.parametrize("clip,md5,n", [("3sec", "ad790df21d4d9d223d3f34227b5cfedd", 61440),

@@ -7,7 +7,8 @@ already, addresses and symbol names are dropped) and matched BY STREAM + resourc
 dropping a template parameter changes the mangled name and nothing else.  Kernels of the new build without such a partner are paired with
 the old kernel of the closest demangled name and printed with both sets of figures.
 
-Limits: `s_nop` padding is not part of a stream, so kernels that differ only in it count as equal; the pairing of a changed kernel with an old
+Limits: `s_nop` padding is not part of a stream, so kernels that differ only in it count as equal (neither is the `...` llvm-objdump prints
+for a run of zero bytes: the alignment gap behind a kernel's `s_endpgm`, which depends on what the code object holds next); the pairing of a changed kernel with an old
 one is by name similarity alone (it can pair unrelated kernels, and it fails if more kernels changed than old ones are left over) - read the
 "was" line of every pair."""
 import collections
@@ -47,7 +48,7 @@ def kernels(co):
                 out[name] = []
             continue
         t = re.sub(r"\s+", " ", ln.partition("//")[0]).strip()
-        if name and t and not t.startswith("s_nop") and not t.startswith("s_code_end"):
+        if name and t and not t.startswith("s_nop") and not t.startswith("s_code_end") and t != "...":
             out[name].append(t)
     return {n: meta[n] + (tuple(ins),) for n, ins in out.items()}
 

@@ -5,8 +5,10 @@
 The .so lands in willow-inference-server_amd/lib/ (git-ignored, but shipped to the GPU box by gpurun).
 hipcc cross-compiles without a GPU, so this also runs in the CPU-only build container.
 """
+import concurrent.futures
 import hashlib
 import os
+import re
 import subprocess
 import sys
 
@@ -17,9 +19,10 @@ LIBDIR = os.path.join(HERE, "lib")
 OBJDIR = os.path.join(HERE, "build")
 LIB = os.path.join(LIBDIR, "libwis_hip.so")
 
-HIP_SOURCES = ["logmel.hip", "enc_kernels.hip", "dec_kernels.hip", "model.hip"]
+# one object per source; the longest compiles first (they start first when the pool is narrower than the list)
+HIP_SOURCES = ["dec_kernels.hip", "enc_kernels.hip", "model.hip", "sv.hip", "generate.hip", "taps.hip", "align.hip", "logmel.hip", "resample.hip"]
 C_SOURCES = ["audio_io.c"]
-HEADERS = ["common.hpp", "kernels.hpp", "sv.hip", "align.hip", "generate.hip", "taps.hip", "resample.hip", os.path.join(ROOT, "include", "wis_hip.h")]      # sv.hip, align.hip, generate.hip, taps.hip: included by model.hip; resample.hip: by logmel.hip
+INCLUDE_DIRS = [CSRC, os.path.join(ROOT, "include")]
 EXPORTS = os.path.join(CSRC, "exports.map")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 # -amdgpu-mfma-vgpr-form: MFMA accumulators live in VGPRs (gfx90a+ unified register file) instead of AGPRs.  hipcc's default put
@@ -50,6 +53,20 @@ C_FLAGS = ["-O2", "-fPIC", "-std=c11", "-I" + os.path.join(ROOT, "include")]
 SOURCE_FLAGS = {}
 
 
+def include_closure(src):
+    """the files a source's quoted #include lines pull in, followed recursively through csrc/ and include/ (the source itself not included)"""
+    seen, todo = [], [os.path.join(CSRC, src)]
+    while todo:
+        with open(todo.pop(), errors="replace") as f:
+            names = re.findall(r'^\s*#\s*include\s+"([^"]+)"', f.read(), flags=re.M)
+        for name in names:
+            path = next((p for p in (os.path.join(d, name) for d in INCLUDE_DIRS) if os.path.exists(p)), None)
+            if path and path not in seen:
+                seen.append(path)
+                todo.append(path)
+    return sorted(seen, key=os.path.basename)      # (by name, not by path: a digest must not depend on where the tree lies)
+
+
 def _digest(paths):
     h = hashlib.sha256()
     for p in paths:
@@ -75,24 +92,39 @@ def build(force=False, verbose=True, variant=None, extra_flags=()):
     lib = os.path.join(LIBDIR, f"libwis_hip_{variant}.so") if variant else LIB
     os.makedirs(LIBDIR, exist_ok=True)
     os.makedirs(objdir, exist_ok=True)
-    hdrs = [h if os.path.isabs(h) else os.path.join(CSRC, h) for h in HEADERS]
-    objs = []
+    objs, stale = [], []
     hip_flags = HIP_FLAGS + list(extra_flags)
     for src in HIP_SOURCES + C_SOURCES:
         path = os.path.join(CSRC, src)
         obj = os.path.join(objdir, src + ".o")
         stamp = obj + ".sha"
-        dig = _digest([path] + hdrs) + "|" + " ".join(extra_flags)
+        dig = _digest([path] + include_closure(src)) + "|" + " ".join(extra_flags)
         if force or not os.path.exists(obj) or not os.path.exists(stamp) or open(stamp).read() != dig:
-            if verbose:
-                print("[build] compiling", src, flush=True)
-            if src.endswith(".c"):
-                _run(["gcc"] + C_FLAGS + ["-c", path, "-o", obj])
-            else:
-                _run([HIPCC] + hip_flags + SOURCE_FLAGS.get(src, []) + ["-c", path, "-o", obj])
-            with open(stamp, "w") as f:
-                f.write(dig)
+            stale.append((src, path, obj, stamp, dig))
         objs.append(obj)
+
+    def compile_one(job):
+        src, path, obj, stamp, dig = job
+        if verbose:
+            print("[build] compiling", src, flush=True)
+        if src.endswith(".c"):
+            _run(["gcc"] + C_FLAGS + ["-c", path, "-o", obj])
+        else:
+            _run([HIPCC] + hip_flags + SOURCE_FLAGS.get(src, []) + ["-c", path, "-o", obj])
+        with open(stamp, "w") as f:
+            f.write(dig)
+
+    if stale:
+        # the out-of-date sources side by side: at most 16 at a time, fewer where MAX_JOBS says so (never sized by the machine's CPU count)
+        jobs = min(16, len(stale), max(1, int(os.environ.get("MAX_JOBS") or 16)))
+        with concurrent.futures.ThreadPoolExecutor(max_workers=jobs) as pool:
+            for done in [pool.submit(compile_one, job) for job in stale]:
+                done.result()          # the first failing compile, in source order, raises its RuntimeError here
+    # objects of sources the library no longer has (a tree built before a source was split or renamed): neither linked nor linted
+    keep = {os.path.basename(o) for o in objs}
+    for f in os.listdir(objdir):
+        if f.endswith((".o", ".sha")) and (f[:-4] if f.endswith(".sha") else f) not in keep:
+            os.remove(os.path.join(objdir, f))
     newest = max(os.path.getmtime(o) for o in objs)
     newest = max(newest, os.path.getmtime(EXPORTS))
     if force or not os.path.exists(lib) or os.path.getmtime(lib) < newest:

@@ -1,5 +1,5 @@
 // align.hip — word-level timestamps: cross-attention alignment and dynamic time warping (wis_align).
-// Compiled as part of model.hip's translation unit (included before sv.hip), like sv.hip.
+// An object of its own on model.hpp's interface (the decoder pass, the handle) and tap.hpp's scaffold (the two wis_op_* taps at the end).
 //
 // What openai-whisper's find_alignment / CTranslate2's Whisper.align compute, on the GPU:
 //   1. the text is teacher-forced through the batched-row decoder route in passes of 16 positions (dec_forward_frag, un-folded
@@ -26,6 +26,8 @@
 
 #include "common.hpp"
 #include "kernels.hpp"
+#include "model.hpp"
+#include "tap.hpp"
 
 using namespace wis;
 
@@ -364,13 +366,15 @@ int align_prepare(wis_model* m) {
   a.nsel = nsel; a.ready = true;
   return WIS_OK;
 }
-// dec_forward_frag's hook: the finished cross-Q of layer l's rows lies in m->dq
-int align_capture_q(wis_model* m, int l, int M) {
+}  // namespace
+// dec_forward_frag's hook (model.hpp): the finished cross-Q of layer l's rows lies in m->dq
+int wis::align_capture_q(wis_model* m, int l, int M) {
   const AlignState& a = m->al;
   const int s0 = a.layer_s0[l], n = a.layer_s0[l + 1] - s0;
   if (n > 0) hipLaunchKernelGGL(align_capture_kernel, dim3(M, n), dim3(64), 0, m->st, m->dq, a.qsel, a.d_sel_head, s0, a.nsel, m->cfg.d_model, a.cap_ub0, a.cap_t0, a.cap_P, m->cfg.n_text_ctx);
   return WIS_OK;
 }
+namespace {
 
 // the whole alignment up to the matrix (want_dtw: and the paths / probabilities).  Results stay in m->al (acc, path, probs).
 int align_run(wis_model* m, const float* input, int input_kind, int B, const int32_t* start_seq, int P, const int32_t* text, const int32_t* text_len,

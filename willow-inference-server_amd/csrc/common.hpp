@@ -38,6 +38,8 @@ typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 __host__ __device__ static inline int cdiv(int a, int b) { return (a + b - 1) / b; }
+// workgroups of 256 threads for a grid-stride loop over n elements (at most 8192)
+inline int blocks_for(int64_t n) { int64_t b = (n + 255) / 256; return (int)(b > 8192 ? 8192 : (b < 1 ? 1 : b)); }
 
 // ---- device-side helpers ---------------------------------------------------------------
 // 64-lane reductions: four DPP steps inside each 16-lane row (quad_perm xor1, xor2, row_half_mirror, row_mirror)

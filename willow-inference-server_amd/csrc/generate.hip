@@ -1,5 +1,6 @@
-// generate.hip — the generate driver (wis_generate, wis_generate_draft, wis_generate_draft_beam) as a sequence of stages.
-// Compiled as part of model.hip's translation unit (included behind the model lifecycle), like align.hip and sv.hip.
+// generate.hip — the generate driver (wis_generate, wis_generate_n, wis_generate_draft, wis_generate_draft_beam) as a sequence of stages, and the
+// two taps that are made of its file-local helpers (wis_debug_search*: the sampling tail alone; wis_debug_tree_logits: a draft window alone).
+// An object of its own on model.hpp's interface; everything below but the entry points is file-local.
 //
 //   make_gen_ctx      every argument check, the resolved shape and sampling options of the call
 //   stage_search      search counters, prompt rows, progress block: staged before anything the encoder produces
@@ -8,6 +9,22 @@
 //   StepGraph         the decode step as a cached HIP graph (three self-attention lengths)
 //   run_burst / run_paced      the two step loops
 //   results_*         three forms of result read-back, then the timing record
+#include <math.h>
+#include <stdlib.h>
+#include <string.h>
+#include <time.h>
+#include <algorithm>
+#include <chrono>
+#include <cmath>
+#include <vector>
+
+#include "common.hpp"
+#include "kernels.hpp"
+#include "model.hpp"
+
+using namespace wis;
+
+namespace {
 
 // what the sampling tail reads of a call (wis_debug_search builds one for a search over given logits)
 struct SampleCtx {
@@ -487,6 +504,12 @@ static int check_terminated(const GenCtx& g, LoopResult* lr, int dn_, int gu_) {
   return WIS_OK;
 }
 
+static inline void cpu_relax() {
+#if !defined(__HIP_DEVICE_COMPILE__) && defined(__x86_64__)
+  __builtin_ia32_pause();
+#endif
+}
+
 // With the measurement convention the step count is known (fixed_new tokens + the forced EOT): every step goes out in one burst, nothing to
 // find out from the device before the last one
 static int run_burst(const GenCtx& g, const StepGraph& sg, int limit, LoopResult* lr) {
@@ -680,6 +703,56 @@ static int generate_with_retry(const char* who, wis_model_t* m, const float* inp
   return WIS_E_STATE;
 }
 
+// wis_debug_search / wis_debug_search_n: the sampling tail over a caller's logits table (single: one hypothesis per utterance)
+static int debug_search_impl(const char* who, wis_model_t* m, const float* logits, int n_steps, int B, const wis_gen_opts_t* o, const uint64_t* seeds, const uint32_t* noise,
+                             bool single, int32_t* out_ids, int32_t* out_len, float* out_score, int32_t* out_finish_step, int32_t* out_parent) {
+  WIS_HIP_CHECK(hipSetDevice(m->device));
+  const wis_config_t& c = m->cfg;
+  SampleCtx g;      // a search over given logits: a one-token prompt
+  int beam = 1;     // rows per utterance: beams, or the samples of a sampled decode
+  WIS_RET(resolve_sample_opts(o, single, false, &g, &beam));
+  WIS_RET(check_batch(m, B, beam));
+  if (!g.sampling()) WIS_RET(check_patience(beam, o->patience));
+  const int max_new = o->max_new_tokens > 0 ? std::min(o->max_new_tokens, MAX_STEPS) : n_steps;
+  if (max_new > n_steps) { set_error("%s: %d steps of logits for max_new_tokens %d", who, n_steps, max_new); return WIS_E_ARG; }
+  hipStream_t st = m->st;
+  const int Mrows = B * beam, V = c.n_vocab;
+  float patience;
+  WIS_RET(resolve_rep_opts(o, &g));
+  if (noise && !g.sampling()) { set_error("%s: a noise table without sampling", who); return WIS_E_ARG; }
+  struct DevBlock { void* p = nullptr; ~DevBlock() { if (p) hipFree(p); } } d_noise;      // one step of the noise table [Mrows][V]
+  if (noise && hipMalloc(&d_noise.p, (size_t)Mrows * V * 4) != hipSuccess) { (void)hipGetLastError(); set_error("%s: out of device memory", who); return WIS_E_NOMEM; }
+  WIS_RET(init_beam_state(m, B, beam, g.sampling(), g.sampling() ? beam : g.n_res));
+  if (g.sampling()) WIS_RET(upload_seeds(m, seeds, B));
+  g.m = m; g.st = st; g.B = B; g.P = 1; g.beam = beam;
+  g.sc = make_sample_cfg(m, o, beam, max_new, &patience);
+  apply_sample_opts(m, &g);
+  g.sp.noise = static_cast<const unsigned*>(d_noise.p);
+  g.bias_all = o->suppress_default ? m->bias_all : nullptr;
+  g.ts = o->timestamps != 0;
+  g.ts_max_init = o->max_initial_timestamp_index < 0 ? -1 : o->max_initial_timestamp_index;
+  std::vector<int> done(B, 0), fin(B, -1), par(Mrows);
+  for (int s = 0; s < max_new; ++s) {
+    WIS_HIP_CHECK(hipMemcpy2DAsync(m->logits, (size_t)m->n_vocab_pad * 4, logits + (size_t)s * Mrows * V, (size_t)V * 4, (size_t)V * 4, Mrows, hipMemcpyHostToDevice, st));
+    if (noise) WIS_HIP_CHECK(hipMemcpyAsync(d_noise.p, noise + (size_t)s * Mrows * V, (size_t)Mrows * V * 4, hipMemcpyHostToDevice, st));
+    // step 0 samples every beam of an utterance from ONE row (wis_generate: the last prompt row; here row b*beam), later steps row b*beam + j
+    WIS_RET(sampling_tail(g, {beam, s == 0 ? 0 : 1, 0}, TAIL_NO_CACHE));
+    WIS_HIP_CHECK(hipMemcpyAsync(done.data(), m->bs.done, (size_t)B * 4, hipMemcpyDeviceToHost, st));
+    WIS_HIP_CHECK(hipMemcpyAsync(par.data(), m->bs.parent, (size_t)Mrows * 4, hipMemcpyDeviceToHost, st));
+    WIS_HIP_CHECK(hipStreamSynchronize(st));
+    bool all = true;
+    for (int b = 0; b < B; ++b) { if (done[b] && fin[b] < 0) fin[b] = s; all = all && done[b]; }
+    if (out_parent) for (int r = 0; r < Mrows; ++r) out_parent[(size_t)s * Mrows + r] = par[r];
+    if (all) break;
+  }
+  for (int b = 0; b < B; ++b) if (fin[b] < 0) { set_error("%s: utterance %d did not finish within %d steps", who, b, max_new); return WIS_E_STATE; }
+  WIS_RET(results_from_device(m, B * g.n_res, max_new, out_ids, out_len, out_score));
+  if (out_finish_step) for (int b = 0; b < B; ++b) out_finish_step[b] = fin[b];
+  return WIS_OK;
+}
+
+}  // namespace
+
 extern "C" {
 
 int wis_generate(wis_model_t* m, const float* input, int B, const int32_t* prompt, int P,
@@ -720,6 +793,63 @@ int wis_generate_draft_beam(wis_model_t* m, const float* input, const int32_t* p
   WIS_RET(generate_with_retry("wis_generate_draft_beam", m, input, 1, prompt, P, o, out_ids, out_len, out_score, n_steps > 0 ? draft_tok : nullptr, n_steps, &acc,
                               n_steps > 0 ? draft_org : nullptr));
   if (accepted_steps) *accepted_steps = acc;
+  return WIS_OK;
+}
+
+int wis_debug_search(wis_model_t* m, const float* logits, int n_steps, int B, const wis_gen_opts_t* o,
+                     int32_t* out_ids, int32_t* out_len, float* out_score, int32_t* out_finish_step, int32_t* out_parent) {
+  if (!m || !logits || !o || !out_ids || !out_len || n_steps < 1 || n_steps > MAX_STEPS) { set_error("wis_debug_search: bad argument"); return WIS_E_ARG; }
+  WIS_ENTER(m, "wis_debug_search")
+  return debug_search_impl("wis_debug_search", m, logits, n_steps, B, o, nullptr, nullptr, true, out_ids, out_len, out_score, out_finish_step, out_parent);
+}
+
+int wis_debug_search_n(wis_model_t* m, const float* logits, int n_steps, int B, const wis_gen_opts_t* o, const uint64_t* seeds, const uint32_t* noise,
+                       int32_t* out_ids, int32_t* out_len, float* out_score, int32_t* out_finish_step, int32_t* out_parent) {
+  if (!m || !logits || !o || !out_ids || !out_len || n_steps < 1 || n_steps > MAX_STEPS) { set_error("wis_debug_search_n: bad argument"); return WIS_E_ARG; }
+  WIS_ENTER(m, "wis_debug_search_n")
+  return debug_search_impl("wis_debug_search_n", m, logits, n_steps, B, o, seeds, noise, false, out_ids, out_len, out_score, out_finish_step, out_parent);
+}
+
+// the rows of ONE draft window of a given beam trajectory through the tree pass (seed_beam_draft's first window, without the replay): their logits
+int wis_debug_tree_logits(wis_model_t* m, const float* input, int input_kind, const int32_t* prompt, int P, int beam,
+                          const int32_t* tok, const int32_t* org, int n_steps, float* logits) {
+  if (!m || !input || !prompt || !tok || !org || !logits || P < 1 || P > 16 || beam < 1 || beam > MAX_R || n_steps < 1 || n_steps > std::min(32, MAX_ROWS / std::max(beam, 1))) {
+    set_error("wis_debug_tree_logits: bad argument (1 <= n_steps <= min(32, %d / beam))", MAX_ROWS); return WIS_E_ARG;
+  }
+  WIS_ENTER(m, "wis_debug_tree_logits")
+  WIS_HIP_CHECK(hipSetDevice(m->device));
+  WIS_RET(check_batch(m, 1, beam));
+  const wis_config_t& c = m->cfg; hipStream_t st = m->st;
+  const int k = beam, V = c.n_vocab;
+  for (int i = 0; i < n_steps * k; ++i) if (tok[i] < 0 || tok[i] >= V || org[i] < 0 || org[i] >= k) { set_error("wis_debug_tree_logits: token / origin out of range"); return WIS_E_ARG; }
+  WIS_RET(stage_input(m, input, input_kind, 1));
+  WIS_RET(run_encoder(m, 1));
+  WIS_RET(run_cross_kv(m, 1));
+  m->spin_now = false;
+  // the prompt: rows at positions 0 .. P-1 of slot 0, then every slot gets a copy (what the first step's kv_reorder does)
+  std::vector<int> ptok(P), ppos(P), pslot(P, 0), pls(P, 0);
+  for (int i = 0; i < P; ++i) { ptok[i] = prompt[i]; ppos[i] = i; }
+  WIS_RET(upload_rows(m, ptok, ppos, pslot, pls));
+  WIS_RET(dec_forward(m, P, P, 1, false, beam, 0));
+  auto& hs = m->h_pin->tree_seed;
+  for (int j = 0; j < MAX_R; ++j) hs.parent[j] = 0;
+  hs.step = 1; hs.done = 0;
+  WIS_HIP_CHECK(hipMemcpyAsync(m->bs.parent, hs.parent, (size_t)k * 4, hipMemcpyHostToDevice, st));
+  WIS_HIP_CHECK(hipMemcpyAsync(m->bs.step_u, &hs.step, 4, hipMemcpyHostToDevice, st));
+  WIS_HIP_CHECK(hipMemcpyAsync(m->bs.done, &hs.done, 4, hipMemcpyHostToDevice, st));
+  WIS_RET(launch_kv_reorder(st, m->kc_all, m->vc_all, m->kv_layer_stride, c.n_dec_layers, m->bs, 1, beam, P, c.n_text_ctx, c.d_model));
+  // one window: steps 1 .. n_steps, rows from trajectory entries 0 .. n_steps - 1
+  std::vector<int> hd((size_t)n_steps * MAX_R * 2, 0);
+  pack_traj(hd.data(), tok, org, n_steps, k);
+  std::vector<int> wt, wp, wsl, wls;
+  int* ha = m->h_pin->anc;
+  const int Mpad = fill_tree_window(hd.data(), 1, n_steps, k, P, wt, wp, wsl, wls, ha);
+  WIS_RET(upload_rows(m, wt, wp, wsl, wls, false, &m->h_pin->win_rows));
+  WIS_HIP_CHECK(hipMemcpyAsync(m->d_anc, ha, (size_t)Mpad * ANC_W * 4, hipMemcpyHostToDevice, st));
+  const TreeWin tw{m->d_anc, P, ANC_W};
+  WIS_RET(dec_forward(m, Mpad, 16, Mpad / 16, true, 1, 0, &tw));
+  WIS_HIP_CHECK(hipMemcpy2DAsync(logits, (size_t)V * 4, m->logits, (size_t)m->n_vocab_pad * 4, (size_t)V * 4, (size_t)n_steps * k, hipMemcpyDeviceToHost, st));
+  WIS_HIP_CHECK(hipStreamSynchronize(st));
   return WIS_OK;
 }
 

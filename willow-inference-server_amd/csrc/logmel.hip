@@ -488,6 +488,3 @@ extern "C" void wis_melstream_destroy(wis_melstream_t* s) {
   if (s->h_nsamp) hipHostFree(s->h_nsamp);
   delete s;
 }
-
-// ---------------------------------------------------------------------------------------
-#include "resample.hip"      // the other half of the audio front end: uploads at another rate than 16 kHz (wis_resample)

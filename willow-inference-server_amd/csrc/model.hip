@@ -1,5 +1,6 @@
-// model.hip — model lifecycle, weight re-packing, the generate / detect_language drivers and
-// the C-ABI entry points of libwis_hip.so (include/wis_hip.h).
+// model.hip — model lifecycle, weight re-packing, the encoder and decoder passes, the search-state helpers and wis_detect_language:
+// the definitions behind model.hpp.  The other drivers are objects of their own on that interface: generate.hip (wis_generate*, the
+// sampling tail), taps.hip (debug / measurement taps, wis_op_*), align.hip (wis_align).
 //
 // Replaces the ctranslate2.models.Whisper object the reference builds at main.py:341-444 and
 // drives at main.py:535-537, 638-639, 685-693.  One handle = one replica on one GPU: weights are
@@ -11,12 +12,8 @@
 #include <math.h>
 #include <stdlib.h>
 #include <string.h>
-#include <time.h>
 #include <algorithm>
-#include <array>
 #include <atomic>
-#include <chrono>
-#include <map>
 #include <mutex>
 #include <memory>
 #include <string>
@@ -24,6 +21,7 @@
 
 #include "common.hpp"
 #include "kernels.hpp"
+#include "model.hpp"
 
 using namespace wis;
 
@@ -72,15 +70,15 @@ __global__ void mel_to_image_kernel(const float* __restrict__ mel, f16* __restri
 }
 // conv1 over the [3002][C] image (C = conv1_channels(n_mels)) as one implicit-im2col GEMM: K = 3C, rounded up to whole 64-deep
 // k-tiles (80 bins: 288 -> 320, the 32 extra columns carry zero weights and read into the next row; 128 bins: 384, no pad)
-static int conv1_k(int n_mels) { return cdiv(3 * conv1_channels(n_mels), 64) * 64; }
+int conv1_k(int n_mels) { return cdiv(3 * conv1_channels(n_mels), 64) * 64; }
 // The convs' GEMM descriptions (run_encoder, and the op taps on shorter images): B utterances of T output rows each; output row t of an
 // utterance starts at row t (conv1, stride 1) / 2 t (conv2, stride 2) of its padded time-major image and runs over three image rows
-static GemmP conv1_gemm(const f16* img, const f16* w, int B, int T, int n_mels, int N) {      // image [B][T + 2][conv1_channels]
+GemmP conv1_gemm(const f16* img, const f16* w, int B, int T, int n_mels, int N) {      // image [B][T + 2][conv1_channels]
   const int cc = conv1_channels(n_mels);
   GemmP p; p.klen = 0; p.A = img; p.a_bs = (int64_t)(T + 2) * cc; p.a_rs = cc; p.a_rpb = T; p.W = w; p.M = B * T; p.N = N; p.K = conv1_k(n_mels);
   return p;
 }
-static GemmP conv2_gemm(const f16* c1, const f16* w, int B, int T, int cin, int N) {      // image [B][2 T + 2][cin]
+GemmP conv2_gemm(const f16* c1, const f16* w, int B, int T, int cin, int N) {      // image [B][2 T + 2][cin]
   GemmP p; p.klen = 0; p.A = c1; p.a_bs = (int64_t)(2 * T + 2) * cin; p.a_rs = 2 * cin; p.a_rpb = T; p.W = w; p.M = B * T; p.N = N; p.K = 3 * cin;
   return p;
 }
@@ -110,183 +108,22 @@ __global__ void matvec_rows_kernel(const f16* __restrict__ W, int ld, const floa
 __global__ void f16_to_f32_kernel(const f16* __restrict__ s, float* __restrict__ d, int64_t n) {
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) d[i] = (float)s[i];
 }
-}  // namespace wis
 
-// ---------------------------------------------------------------------------------------
-struct EncLayerW {
-  float *ln1_g, *ln1_b, *ln2_g, *ln2_b;
-  f16 *w_qkv, *w_out, *w_f1, *w_f2;
-  float *b_qkv, *b_out, *b_f1, *b_f2;
-};
-// One decoder projection as the step streams it (load_weights: load_proj; the taps fill one from their own scratch)
-struct DecProj {
-  const f16* Wp;          // MFMA-fragment packed matrix; the 8-bit image when `scale` is given
-  const float* scale;     // int8_float16: dequantisation scale per output row, else null
-  const float* bias;      // LayerNorm-folded projections: b + W . beta
-  const float* csum;      // column sums of the LayerNorm-folded weights (dec_kernels.hip fold_ln_kernel): non-null exactly when the projection follows a LayerNorm
-  int N, K;               // launch shape (the vocabulary projection: N = n_vocab_pad)
-  int rows;               // weight rows per workgroup tile the matrix was packed for (gemv_rows_for)
-  const f16* Wp8 = nullptr;      // the same f16 matrix as an eight-column image (add_nc8_image), or null: the route of <= 8 rows streams this one where gemv_nc8_shape holds
-};
-struct DecLayerW {
-  float *ln1_g, *ln1_b, *ln2_g, *ln2_b, *ln3_g, *ln3_b;
-  DecProj qkv, out, cq, cout, f1, f2;
-  DecProj cqo;                                       // cross-Q folded THROUGH the out-projection: packed [W'q | W'q Wo] ([d][2d]) and W'q bo (out_cq_dual / out_cq_frag3)
-  f16* w_ckv; float* b_ckv;                          // row-major [2d][d] (encoder-side GEMM)
-  // the six matrices a decode step streams per layer, in step order
-  std::array<const DecProj*, 6> streamed() const { return {&qkv, &out, &cq, &cout, &f1, &f2}; }
-};
-
-struct GraphKey {
-  int B, beam, P, max_new, fixed_new, suppress_blank, suppress_default, early_exit, spin, sa_nb; float lp, patience;
-  int timestamps, max_init;      // the timestamp form of the step (ts_rules_kernel ahead of logit_stats_kernel<true>) and its first-timestamp cap
-  float rep_pen; int rep_ngram;  // rep_rules_kernel at the head of the tail (both 0: off, no such launch)
-  int samp_topk; float samp_T; int n_hyp;      // sampled decode (sample_step_kernel in beam_step_kernel's place) / results per utterance; all 0: off, one result
-  bool operator<(const GraphKey& o) const { return memcmp(this, &o, sizeof(GraphKey)) < 0; }
-};
-
-// the device slabs that hold a model's converted weights: shared by every replica cloned from it on the same GPU (wis_model_clone),
-// freed when the last of them is destroyed
-struct WeightSlabs {
-  int device; std::vector<void*> slabs; size_t bytes = 0;
-  ~WeightSlabs() { hipSetDevice(device); for (void* p : slabs) hipFree(p); }
-};
-
-// word-level alignment (csrc/align.hip): the handle's alignment heads and the scratch its first wis_align allocates
-struct AlignState {
-  std::vector<int> heads;                 // (layer, head) pairs of wis_model_set_alignment_heads; empty: every head of the upper half of the decoder
-  bool ready = false;                     // the selection below matches `heads`
-  bool capture = false;                   // a wis_align decoder pass is running: dec_forward_frag hands every layer's finished cross-Q to align_capture_q
-  int nsel = 0, sel_cap = 0; size_t sel_bytes = 0;
-  std::vector<int> layer_s0;              // selected heads of layer l: [layer_s0[l], layer_s0[l + 1]) of the (layer, head)-sorted selection
-  int* d_sel_head = nullptr; long long* d_koff = nullptr;      // per selected head: its head index, the element offset of its K image in kx_all (utterance 0)
-  f16* qsel = nullptr;                    // captured queries [max_batch][nsel][n_text_ctx][64]
-  float *W = nullptr, *acc = nullptr;     // one chunk of heads' probabilities; the matrix [max_batch][tokens][n_audio_ctx]
-  unsigned* trace = nullptr; int *rev = nullptr, *path = nullptr, *d_meta = nullptr; float* probs = nullptr;
-  int cap_ub0 = 0, cap_t0 = 0, cap_P = 0, last_nmax = 0;
-  int kv_ub0 = 0;                         // first utterance of the group a wis_align decoder pass runs (dec_forward_frag offsets the cross K / V by it); 0 outside
-  hipEvent_t ev[5 + 128] = {}; int n_ev = 0;      // phase boundaries of the last call (wis_align_last_timing); ev[5..]: (weights, filter) pairs of the first 64 head chunks
-  bool ev_partial = false;                // the last call had more head chunks than event pairs: the weights / filter split is not reported
-};
-
-constexpr int ANC_W = 32;      // ancestor-table entries per row = the most steps a window holds (beam 2 / 3: 32 steps = 64 / 96 rows)
-constexpr int MAX_STEPS = 256;      // decode steps a search can take (the cap on max_new; BeamState::traj and the draft hold this many entries)
-
-// The handle's pinned host staging block.  Every area is a member of its own: a copy out of one may still be pending on the stream when
-// the host fills the next (the prompt rows against a window's rows, init_beam_state's staging against the rows'), and nothing here is
-// large enough to be worth sharing.  Extents follow the device buffers they stage (alloc_buffers).
-struct RowStage { int tok[MAX_ROWS], pos[MAX_ROWS], slot[MAX_ROWS], lslot[MAX_ROWS]; };      // upload_rows -> RowMeta
-struct PinnedScratch {
-  int64_t nsamp[MAX_ROWS];                     // stage_input: samples per utterance
-  int giveup;                                  // spin_gave_up: the give-up flag read back
-  RowStage rows, win_rows;                     // the search's rows (every caller's default); the rows of a draft-verification window
-  float beam_cum[MAX_ROWS]; unsigned beam_tick[4];      // init_beam_state
-  unsigned long long seeds[MAX_ROWS];          // upload_seeds: the Philox key of every utterance of a sampled decode
-  unsigned reseed_tick[4];                     // reseed_tick: bs.tick behind a draft verification
-  // wis_generate_draft: step index of the verified rows, their picks read back; then the search state `steps` ordinary steps would have left
-  int vstep[MAX_ROWS], pick_tok[MAX_ROWS]; float pick_lp[MAX_ROWS];
-  int hist[MAX_STEPS];
-  struct { int step, tok, pos, slot; float cum; } seed;
-  // wis_generate_draft_beam: the draft in BeamState::traj's layout, the host image of the verification state, done / step_u read back per
-  // window, the window rows' ancestor table and base slots, the per-window reset of the path bookkeeping (vs[2], then vs[DRAFT_VS_BASE + j])
-  int draft[MAX_STEPS * MAX_R * 2];
-  int vstate[DRAFT_VS_INTS]; int win_done, win_step;
-  int anc[MAX_ROWS * ANC_W], base[MAX_ROWS];
-  int path_reset[1 + MAX_R];
-  struct { int parent[MAX_R], step, done; } tree_seed;      // wis_debug_tree_logits: the search state behind the prompt pass
-  int al_frames[2 * MAX_ROWS], al_tgt[MAX_ROWS], al_dst[MAX_ROWS];      // wis_align: {tokens, frames} per utterance; target token / matrix row per pass row
-};
-static_assert(MAX_ROWS % 16 == 0, "a verification window is padded to whole groups of 16 rows: min(ANC_W, MAX_ROWS / beam) steps x beam rows must still fit MAX_ROWS");
-static_assert(sizeof(PinnedScratch::draft) == sizeof(int) * MAX_STEPS * MAX_R * 2, "the draft area holds one {token, origin} pair per step and beam slot");
-static_assert(sizeof(PinnedScratch::anc) == sizeof(int) * MAX_ROWS * ANC_W, "ANC_W ancestor slots per window row");
-// (the device buffers these two are copied to - d_draft, d_anc - are allocated by the staging areas' own extents: alloc_buffers)
-static_assert(DRAFT_VS_PERM + MAX_R <= 16 && DRAFT_VS_BASE + MAX_R <= 32 && DRAFT_VS_INTS >= 32, "the verification state's head (32 ints up, 16 back) holds the matching and the base slots");
-
-struct wis_model {
-  wis_config_t cfg;
-  int device;
-  DeviceCtx* ctx;
-  hipStream_t st;
-  std::shared_ptr<WeightSlabs> wslabs;      // weights (read-only after load): possibly shared with clones
-  std::vector<void*> allocs;    // this replica's own slabs (activations, caches, state), carved by dalloc()
-  char* slab_cur = nullptr; size_t slab_left = 0;
-  size_t bytes = 0;
-  // weights
-  f16 *w_conv1, *w_conv2; float *b_conv1, *b_conv2, *enc_pos, *enc_ln_g, *enc_ln_b;
-  std::vector<EncLayerW> enc;
-  std::vector<DecLayerW> dec;
-  f16 *emb, *dec_pos; float *dec_ln_g, *dec_ln_b;
-  DecProj proj;                 // the tied vocabulary projection behind the final LayerNorm (N = n_vocab_pad; it has no bias of its own: bias = W . beta)
-  float *bias_all, *bias_begin; int* d_lang_ids;
-  int n_vocab_pad;
-  // activations
-  int Tpad;
-  f16 *img, *c1, *xn, *qk, *vt, *ao, *hbuf, *mem;
-  float* x; float* skbuf; float* enc_part = nullptr; unsigned* enc_cnt = nullptr;
-  std::vector<f16*> kx, vx;             // per decoder layer cross K / V
-  std::vector<f16*> kc, vc;             // per decoder layer self KV cache [slots][ctx][d] (views into kc_all / vc_all)
-  f16 *kc_all = nullptr, *vc_all = nullptr; size_t kv_layer_stride = 0;
-  f16 *kx_all = nullptr, *vx_all = nullptr, *w_ckv_all = nullptr; float* b_ckv_all = nullptr;   // cross K/V: one block each, all layers
-  size_t kx_lstride = 0, vx_lstride = 0;
-  // decode state
-  float *dx, *dq, *logits, *part; f16 *dao, *dh, *dln; unsigned* counters;
-  float* dq2 = nullptr;         // batched fold: second half of the cross-attention q_raw (dec_forward_frag)
-  int sa_nb = 8;      // 8-position blocks the step's self-attention asks for per pass (generate.hip StepGraph: by the step index; 8 outside the step loops)
-  float* gf_part = nullptr; unsigned* gf_cnt = nullptr; int gf_ksplit = 1;      // K split of the batched FFN2 skinny GEMM: slice sums, tickets (GemvP::ksplit)
-  unsigned long long* ca_gran = nullptr; unsigned* ca_epoch = nullptr;      // granule hand-off of the decoder cross-attention (small grids): slots, flag + epochs
-  bool spin_off = false;        // sticky: a combiner's bounded spin ran out once on this handle - it keeps to the ticket hand-off from then on
-  int handoff_retries = 0;      // calls repeated because a combiner's spin ran out (wis_debug_handoff: expected to stay 0)
-  bool spin_now = true;         // this call's decision (SpinClaim): dec_forward passes the granule buffers only when set
-  f16 *dxf = nullptr, *daoxf = nullptr, *dhxf = nullptr; float* dstat = nullptr;   // batched rows: fragment images of x / attention out / FFN hidden, row partial sums
-  RowMeta rm; BeamState bs;
-  RowMeta rm_win;               // row metadata of a draft-verification window (wis_generate_draft_beam): the search's own rows (rm, written by beam_step_kernel) stay untouched
-  float *st_max, *st_sum, *st_val; int* st_idx;
-  unsigned long long* d_seeds = nullptr;      // sampled decodes: Philox key per utterance [MAX_ROWS], written at the start of every call (SampleP::seeds)
-  int* ts_desc = nullptr;       // timestamp rules: masked ranges per live row [MAX_ROWS][TS_DESC_INTS] (ts_rules_kernel -> logit_stats_kernel<true>)
-  float* d_nsp = nullptr;       // no_speech_prob per utterance of the last wis_generate that asked for it
-  int nsp_B = 0;                // ... its batch size; 0: the last call did not ask (wis_last_no_speech_prob answers WIS_E_STATE)
-  float* d_in; int64_t* d_nsamp; float* d_probs;
-  int* vstep = nullptr; int* pick_tok = nullptr; float* pick_lp = nullptr;      // wis_generate_draft: per-row step index, picked token / log-probability of the teacher-forced rows
-  int* d_draft = nullptr; int* d_anc = nullptr; int* d_vstate = nullptr; int* d_base = nullptr;        // wis_generate_draft_beam: the draft trajectory [MAX_STEPS][MAX_R][2], the window rows' ancestor slots [MAX_ROWS][ANC_W], the verification state, the rows' base slots
-  float* lm_logspec = nullptr; unsigned* lm_gmax = nullptr;   // log-mel scratch of THIS replica (never shared with other callers)
-  PinnedScratch* h_pin = nullptr;      // pinned host staging (one block, named areas)
-  unsigned long long* h_prog = nullptr;      // host-mapped progress block of the beam search (kernels.hpp HP_*): the decode loop polls it
-  unsigned gen = 0;                          // generation of the current search (records of an earlier call's over-run step are ignored)
-  int last_B = 0, last_beam = 0;             // shape of the last generate call (wis_last_trajectory)
-  bool overrun_left = false;                 // the last call returned with an over-run decode step still queued (its give-up flag, if any, is not the next call's)
-  hipEvent_t ev[8];
-  hipStream_t st_enc = nullptr;             // wis_generate's front half (log-mel, encoder) runs here: it overlaps the previous call's over-run decode step on `st`
-  hipEvent_t ev_enc = nullptr, ev_ckv = nullptr;      // encoder output ready (st_enc -> st); cross-K/V projection done reading it (st -> the next call's st_enc)
-  wis_timing_t timing;
-  std::map<GraphKey, hipGraphExec_t> graphs;
-  bool use_graph;
-  bool w8 = false;              // decoder weights stored as 8-bit packed fragments
-  bool cq_fold = false;         // f16 decoder weights: the fused out-projection + cross-Q stage is available (p_cqo)
-  f16* dxh = nullptr;           // f16 row-major copy of the layer input rows (written by the embedding / FFN2 epilogues)
-  unsigned long long* d_prof;   // [L*8][16] stamp rows, one per layer kernel (wis_debug_phase_cycles / wis_debug_timeline)
-  bool prof_on; bool prof_all;
-  size_t enc_part_cap = 0;      // (utterance, head, query tile) triples the split-key encoder attention buffers were sized for
-  std::atomic_flag busy = ATOMIC_FLAG_INIT;   // one compute call at a time per handle (BusyGuard)
-  AlignState al;
-};
-
-namespace {
-
+// K-splits of the encoder's FFN2 at M rows (0 = one workgroup per output tile over the whole K): split while the 128x128 tiles
+// are too few for 256 CUs; four ways while that still leaves <= 512 workgroups, else two (the split length stays a multiple of
+// the 64-deep k-tile for every Whisper width)
+int enc_splitk(int d, int M) {
+  const int tiles = (d / 128) * cdiv(M, 128);
+  if (tiles >= 200) return 0;
+  return (tiles <= 128 && (4 * d) % (4 * 64) == 0) ? 4 : 2;
+}
 // Bump allocator over large slabs: the ~700 tensors and buffers of a replica come from a handful of hipMalloc calls, so the
 // small per-layer parameters (biases, LayerNorm vectors: 2.5-10 KB) sit next to their matrices inside the same large-page
 // fragments instead of each owning a 4 KB page - every decode kernel touches 3-5 of them on its critical path, and a
 // translation miss there costs more than the kernel's whole weight stream.
 constexpr size_t SLAB_BYTES = (size_t)1 << 30;
-// K-splits of the encoder's FFN2 at M rows (0 = one workgroup per output tile over the whole K): split while the 128x128 tiles
-// are too few for 256 CUs; four ways while that still leaves <= 512 workgroups, else two (the split length stays a multiple of
-// the 64-deep k-tile for every Whisper width)
-static int enc_splitk(int d, int M) {
-  const int tiles = (d / 128) * cdiv(M, 128);
-  if (tiles >= 200) return 0;
-  return (tiles <= 128 && (4 * d) % (4 * 64) == 0) ? 4 : 2;
-}
 template <class T>
-int dalloc(wis_model* m, T** p, size_t n_elems) {
+static int dalloc(wis_model* m, T** p, size_t n_elems) {
   size_t b = n_elems * sizeof(T); if (b == 0) b = 16;
   const size_t align = b >= ((size_t)1 << 20) ? ((size_t)1 << 16) : 256;
   size_t pad = (align - (reinterpret_cast<uintptr_t>(m->slab_cur) & (align - 1))) & (align - 1);
@@ -302,22 +139,29 @@ int dalloc(wis_model* m, T** p, size_t n_elems) {
   m->slab_cur += b; m->slab_left -= b; m->bytes += b + pad;
   return WIS_OK;
 }
-inline int blocks_for(int64_t n) { int64_t b = (n + 255) / 256; return (int)(b > 8192 ? 8192 : (b < 1 ? 1 : b)); }
+// the two utility kernels as the other objects launch them (model.hpp)
+void launch_convert(hipStream_t st, const void* src, int src_f16, void* dst, int dst_f16, int64_t rows, int64_t cols, int64_t dst_ld, int64_t n_scale, float scale) {
+  hipLaunchKernelGGL(convert_kernel, dim3(blocks_for(rows * cols)), dim3(256), 0, st, src, src_f16, dst, dst_f16, rows, cols, dst_ld, n_scale, scale);
+}
+void launch_f16_to_f32(hipStream_t st, const f16* s, float* d, int64_t n) {
+  hipLaunchKernelGGL(f16_to_f32_kernel, dim3(blocks_for(n)), dim3(256), 0, st, s, d, n);
+}
 // the convs' weights [N][cin][3] (f32 or f16) -> the GEMMs' W operand (conv_pack_kernel)
-static void pack_conv1_w(hipStream_t st, const void* src, int src_f16, f16* dst, int N, int n_mels) {
+void pack_conv1_w(hipStream_t st, const void* src, int src_f16, f16* dst, int N, int n_mels) {
   const int k1 = conv1_k(n_mels);      // 80 bins: K = 3*96 = 288 padded to 320 = 5 x 64; 128: 384
   hipLaunchKernelGGL(conv_pack_kernel, dim3(blocks_for((int64_t)N * k1)), dim3(256), 0, st, src, src_f16, dst, N, n_mels, conv1_channels(n_mels), k1);
 }
-static void pack_conv2_w(hipStream_t st, const void* src, int src_f16, f16* dst, int N, int cin) {
+void pack_conv2_w(hipStream_t st, const void* src, int src_f16, f16* dst, int N, int cin) {
   hipLaunchKernelGGL(conv_pack_kernel, dim3(blocks_for((int64_t)N * 3 * cin)), dim3(256), 0, st, src, src_f16, dst, N, cin, cin, 3 * cin);
 }
-static int launch_mel_to_image(hipStream_t st, const float* mel, f16* img, int B, int n_mels) {
+int launch_mel_to_image(hipStream_t st, const float* mel, f16* img, int B, int n_mels) {
   if (n_mels == 128) hipLaunchKernelGGL((mel_to_image_kernel<128, 128>), dim3(cdiv(3000, 64), B), dim3(256), 0, st, mel, img);
   else if (n_mels == 80) hipLaunchKernelGGL((mel_to_image_kernel<80, 96>), dim3(cdiv(3000, 64), B), dim3(256), 0, st, mel, img);
   else { set_error("mel_to_image: %d mel bins (80 or 128)", n_mels); return WIS_E_UNSUPPORTED; }
   return WIS_OK;
 }
 
+namespace {
 struct TensorSrc { const void* p; int f16; int64_t rows, cols; };
 
 struct Loader {
@@ -339,14 +183,15 @@ struct Loader {
     return WIS_OK;
   }
 };
+}  // namespace
 
-int to_f32(wis_model* m, const Loader& L, const std::string& name, int64_t n, float** out, int64_t n_scale = 0, float scale = 1.f) {
+static int to_f32(wis_model* m, const Loader& L, const std::string& name, int64_t n, float** out, int64_t n_scale = 0, float scale = 1.f) {
   TensorSrc s; WIS_RET(L.get(name, n, 1, &s));
   if (!*out) WIS_RET(dalloc(m, out, (size_t)n));          // *out preset: a view into a block the caller allocated
   hipLaunchKernelGGL(convert_kernel, dim3(blocks_for(n)), dim3(256), 0, m->st, s.p, s.f16, *out, 0, n, (int64_t)1, (int64_t)1, n_scale, scale);
   return WIS_OK;
 }
-int to_f16_mat(wis_model* m, const Loader& L, const std::string& name, int64_t rows, int64_t cols, f16** out, int64_t n_scale = 0, float scale = 1.f) {
+static int to_f16_mat(wis_model* m, const Loader& L, const std::string& name, int64_t rows, int64_t cols, f16** out, int64_t n_scale = 0, float scale = 1.f) {
   TensorSrc s; WIS_RET(L.get(name, rows, cols, &s));
   if (!*out) WIS_RET(dalloc(m, out, (size_t)rows * cols));
   hipLaunchKernelGGL(convert_kernel, dim3(blocks_for(rows * cols)), dim3(256), 0, m->st, s.p, s.f16, *out, 1, rows, cols, cols, n_scale, scale);
@@ -369,7 +214,7 @@ int prep_projection(hipStream_t st, f16* W, int N, int Npad, int K, int n_scale,
 }
 // checkpoint matrix -> packed projection through the f16 image `tmp` (build_cq_fold reads the folded weights there); allocations in slab order: column
 // sums, then the 8-bit image and its scales or the f16 image.  out->N is the logical N; *npad_out the packed image's rows
-int to_packed(wis_model* m, const Loader& L, const std::string& name, int N, int K, f16* tmp, int n_scale, float scale, const float* ln_gamma, const float* ln_beta,
+static int to_packed(wis_model* m, const Loader& L, const std::string& name, int N, int K, f16* tmp, int n_scale, float scale, const float* ln_gamma, const float* ln_beta,
               float* bias, DecProj* out, int* npad_out = nullptr) {
   TensorSrc s; WIS_RET(L.get(name, N, K, &s));
   const int rows = gemv_rows_for(N, K);
@@ -386,7 +231,7 @@ int to_packed(wis_model* m, const Loader& L, const std::string& name, int N, int
 }
 // `name`/weight + `name`/bias of the checkpoint as a DecProj.  A LayerNorm-folded projection converts its bias first (the fold adds W . beta to it), the
 // others the matrix first: that is the order of the allocations, i.e. the slab layout (SLAB_BYTES) - keep it.
-int load_proj(wis_model* m, const Loader& L, const std::string& name, int N, int K, f16* tmp, int n_scale, float scale, const float* ln_gamma, const float* ln_beta, DecProj* out) {
+static int load_proj(wis_model* m, const Loader& L, const std::string& name, int N, int K, f16* tmp, int n_scale, float scale, const float* ln_gamma, const float* ln_beta, DecProj* out) {
   float* bias = nullptr;
   if (ln_gamma) WIS_RET(to_f32(m, L, name + "/bias", N, &bias, n_scale, scale));
   WIS_RET(to_packed(m, L, name + "/weight", N, K, tmp, n_scale, scale, ln_gamma, ln_beta, bias, out));
@@ -421,7 +266,7 @@ int build_cq_fold(hipStream_t st, const f16* wq_gamma, const void* wo, int wo_f1
   return WIS_OK;
 }
 
-int load_weights(wis_model* m, const Loader& L) {
+static int load_weights(wis_model* m, const Loader& L) {
   const wis_config_t& c = m->cfg;
   const int d = c.d_model, V = c.n_vocab;
   const float qs = 0.125f;   // 1/sqrt(64), folded into the query projections (exact: power of two)
@@ -546,8 +391,23 @@ int load_weights(wis_model* m, const Loader& L) {
   return WIS_OK;
 }
 
-static int frag_ksplit_setting();      // (beside dec_forward_frag)
-int alloc_buffers(wis_model* m) {
+// K slices of the batched FFN2 (GemvP::ksplit).  Measured (decode ms per utterance batch, 17 steps): 8 utterances 40.7 unsplit / 38.6 two slices / 38.9 four;
+// 12: 46.7 two / 46.9 four; 16: 60.9 unsplit / 58.7 two / 59.5 four.  WIS_FRAG_KSPLIT=1: no split (A/B switch).  ffn2_ksplit: the slices a K-deep FFN2 takes -
+// the setting where the k-steps divide into slices of whole wave quarters, else 1 (launch_gemv_frag still prefers its M split from two row blocks on)
+static int frag_ksplit_setting() {
+  static const int env_ks = getenv("WIS_FRAG_KSPLIT") ? atoi(getenv("WIS_FRAG_KSPLIT")) : 2;
+  return env_ks >= 1 && env_ks <= 8 ? env_ks : 2;
+}
+int ffn2_ksplit(int K) {
+  const int ks = frag_ksplit_setting();
+  return ks > 1 && (K / 32) % (4 * ks) == 0 ? ks : 1;
+}
+// part: [N/16][ks][xmb][64] float4 slice sums; cnt: [N/16] tickets, zeroed once
+void frag_set_ksplit(GemvP& g, int ks, float* part, unsigned* cnt) {
+  if (ks > 1) { g.ksplit = ks; g.kpart = part; g.kcnt = cnt; }
+}
+
+static int alloc_buffers(wis_model* m) {
   const wis_config_t& c = m->cfg;
   const int d = c.d_model, H = c.n_heads, Bm = c.max_batch, T = c.n_audio_ctx, L = c.n_dec_layers;
   const int slots = Bm * c.max_beam, ctx = c.n_text_ctx;
@@ -615,7 +475,7 @@ int alloc_buffers(wis_model* m) {
   WIS_RET(dalloc(m, &m->counters, (size_t)Bg * H));
   WIS_HIP_CHECK(hipMemsetAsync(m->counters, 0, (size_t)Bg * H * 4, m->st));
   {
-    // (K split of the batched FFN2: frag_ksplit_setting / ffn2_ksplit, beside dec_forward_frag)
+    // (K split of the batched FFN2: frag_ksplit_setting / ffn2_ksplit above)
     m->gf_ksplit = frag_ksplit_setting();
     const size_t nt = (size_t)cdiv(d, 16);
     WIS_RET(dalloc(m, &m->gf_part, nt * m->gf_ksplit * (MAX_ROWS / 16) * 64 * 4));
@@ -672,7 +532,7 @@ int alloc_buffers(wis_model* m) {
 }
 
 // ---- input -> conv1 image --------------------------------------------------------------
-int stage_input(wis_model* m, const float* input, int kind, int B, hipStream_t on = nullptr) {
+int stage_input(wis_model* m, const float* input, int kind, int B, hipStream_t on) {
   hipStream_t st = on ? on : m->st;
   if (kind == WIS_IN_PCM_HOST || kind == WIS_IN_PCM_DEV) {
     const float* dp = input;
@@ -696,7 +556,7 @@ int stage_input(wis_model* m, const float* input, int kind, int B, hipStream_t o
 }
 
 // ---- encoder + cross K/V ---------------------------------------------------------------
-int run_encoder(wis_model* m, int B, hipStream_t on = nullptr) {
+int run_encoder(wis_model* m, int B, hipStream_t on) {
   const wis_config_t& c = m->cfg; hipStream_t st = on ? on : m->st;
   const int d = c.d_model, H = c.n_heads, T = c.n_audio_ctx, M = B * T;
   {  // conv1: implicit im2col over the [3002][C] image; 80 bins: C = 96, K = 288 (+32 zero-weighted columns that read into the next
@@ -751,19 +611,16 @@ int run_cross_kv(wis_model* m, int B) {
 // with one handle, always did: the published decode numbers were for a path the server did not run.)  Whatever happens, a spin
 // that runs out never fails a request: the flag travels with every step's progress record / is read after every tap pass, the handle
 // switches to the ticket form for good and the call is run again (wis_generate / wis_detect_language / the logits taps).
-static inline void cpu_relax() {
-#if !defined(__HIP_DEVICE_COMPILE__) && defined(__x86_64__)
-  __builtin_ia32_pause();
-#endif
-}
-static std::atomic<int> g_spin_bh[64];
+// The budget is process-wide state: it is defined here and nowhere else, and generate.hip, taps.hip and align.hip claim from it through
+// SpinClaim (declared in model.hpp, its members defined below).
+std::atomic<int> g_spin_bh[64];
 // claims whose call has returned while ONE over-run decode step of it may still be running on the handle's stream (a search that ended on
 // EOT does not wait for the step queued behind the one that finished it): the combiners of that step still spin, so its share of the
 // budget is released only when the event recorded behind it has completed - checked by whoever claims next on the device (advisor, round 5:
 // released at return, the budget could be over-subscribed for the length of one step)
 struct DeferredClaim { hipEvent_t ev; int n; };
-static std::mutex g_spin_mu;
-static std::vector<DeferredClaim> g_spin_deferred[64];
+std::mutex g_spin_mu;
+std::vector<DeferredClaim> g_spin_deferred[64];
 static void spin_collect(int device) {
   std::lock_guard<std::mutex> lk(g_spin_mu);
   auto& v = g_spin_deferred[device & 63];
@@ -772,35 +629,30 @@ static void spin_collect(int device) {
     else ++i;
   }
 }
-struct SpinClaim {
-  wis_model* m; int n = 0;
-  SpinClaim(wis_model* mm, int B) : m(mm) {
-    static const bool env_share = getenv("WIS_CA_SPIN_SHARED") != nullptr;      // test switch: ignore the budget (exercises the shared-GPU hazard on purpose)
-    m->spin_now = false;
-    spin_collect(m->device);
-    if (m->spin_off) return;
-    if (env_share) { m->spin_now = true; return; }
-    const int need = B * m->cfg.n_heads;
-    std::atomic<int>& a = g_spin_bh[m->device & 63];
-    int cur = a.load(std::memory_order_relaxed);
-    while (cur + need <= CA_SPIN_MAX_BH)
-      if (a.compare_exchange_weak(cur, cur + need, std::memory_order_relaxed)) { n = need; m->spin_now = true; return; }
-  }
-  ~SpinClaim() { if (n) g_spin_bh[m->device & 63].fetch_sub(n, std::memory_order_relaxed); }
-  // the call returns with work of its own still queued on `st`: hand the claim to the deferred list behind an event on that stream
-  void defer(hipStream_t st) {
-    if (!n) return;
-    if (hipEventRecord(m->ev[6], st) != hipSuccess) return;      // (then the destructor releases as before)
-    std::lock_guard<std::mutex> lk(g_spin_mu);
-    auto& v = g_spin_deferred[m->device & 63];
-    for (auto& d : v) if (d.ev == m->ev[6]) { d.n += n; n = 0; return; }      // (re-recorded: the earlier share now waits for the later record too)
-    v.push_back({m->ev[6], n}); n = 0;
-  }
-  SpinClaim(const SpinClaim&) = delete;
-  SpinClaim& operator=(const SpinClaim&) = delete;
-};
+SpinClaim::SpinClaim(wis_model* mm, int B) : m(mm) {
+  static const bool env_share = getenv("WIS_CA_SPIN_SHARED") != nullptr;      // test switch: ignore the budget (exercises the shared-GPU hazard on purpose)
+  m->spin_now = false;
+  spin_collect(m->device);
+  if (m->spin_off) return;
+  if (env_share) { m->spin_now = true; return; }
+  const int need = B * m->cfg.n_heads;
+  std::atomic<int>& a = g_spin_bh[m->device & 63];
+  int cur = a.load(std::memory_order_relaxed);
+  while (cur + need <= CA_SPIN_MAX_BH)
+    if (a.compare_exchange_weak(cur, cur + need, std::memory_order_relaxed)) { n = need; m->spin_now = true; return; }
+}
+SpinClaim::~SpinClaim() { if (n) g_spin_bh[m->device & 63].fetch_sub(n, std::memory_order_relaxed); }
+// the call returns with work of its own still queued on `st`: hand the claim to the deferred list behind an event on that stream
+void SpinClaim::defer(hipStream_t st) {
+  if (!n) return;
+  if (hipEventRecord(m->ev[6], st) != hipSuccess) return;      // (then the destructor releases as before)
+  std::lock_guard<std::mutex> lk(g_spin_mu);
+  auto& v = g_spin_deferred[m->device & 63];
+  for (auto& d : v) if (d.ev == m->ev[6]) { d.n += n; n = 0; return; }      // (re-recorded: the earlier share now waits for the later record too)
+  v.push_back({m->ev[6], n}); n = 0;
+}
 // reads and clears the give-up flag (word 0 of the epoch block); true = a combiner gave up: results of the pass are garbage
-static int spin_gave_up(wis_model* m, bool* gave_up) {
+int spin_gave_up(wis_model* m, bool* gave_up) {
   int* h = &m->h_pin->giveup;
   WIS_HIP_CHECK(hipMemcpyAsync(h, m->ca_epoch, 4, hipMemcpyDeviceToHost, m->st));
   WIS_HIP_CHECK(hipStreamSynchronize(m->st));
@@ -818,14 +670,11 @@ static int spin_gave_up(wis_model* m, bool* gave_up) {
 // Batched rows (8 < M <= 48): every activation a projection reads lives in HBM as an MFMA fragment image, LayerNorm statistics
 // travel as per-16-column partial sums from the residual epilogues (kernels.hpp launch_gemv_frag): 8 launches per layer, no
 // LayerNorm launch, no per-workgroup LDS staging of the activations.
-// tw (draft verification at beam > 1): the M rows are nodes of ONE utterance's beam tree - self-attention by ancestor table (anc [M][aw], first
-// window position w0), cross-attention as B = M / 16 groups of R = 16 rows that all read utterance 0's K / V
-struct TreeWin { const int* anc; int w0, aw; const int* base = nullptr; };
-int align_capture_q(wis_model* m, int l, int M);      // align.hip
+// tw: a tree window (model.hpp TreeWin)
 
 // ---- the step's projection stages: the ONLY places that assemble a GemvP from a projection (both forwards, the weight-stream tap, the op taps); raw
 // operand pointers, so a tap passes its own scratch; every member they do not name stays zero.  launch_gemv (<= 8 rows): x fp32 under GV_LN, else f16
-static GemvP gemv_small(const DecProj& p, const void* x, void* y, int M, int flags) {
+GemvP gemv_small(const DecProj& p, const void* x, void* y, int M, int flags) {
   GemvP g; memset(&g, 0, sizeof(g));
   g.x = x; g.csum = p.csum; g.Wp = p.Wp; g.wscale = p.scale; g.bias = p.bias; g.y = y; g.M = M; g.N = p.N; g.K = p.K; g.flags = flags; g.rows = p.rows;
   // eight-column tiles where the projection has that image (FFN2, cross-attention out-projection of large models): f16 rows, plain or residual epilogue
@@ -833,7 +682,7 @@ static GemvP gemv_small(const DecProj& p, const void* x, void* y, int M, int fla
   return g;
 }
 // launch_gemv_frag (batched rows) on the rows' fragment image; the caller adds the stage's own: output, statistics, QKV cache members, prof, FFN2's K split
-static GemvP gemv_frag(const DecProj& p, const void* xf, int M, int flags) {
+GemvP gemv_frag(const DecProj& p, const void* xf, int M, int flags) {
   GemvP g; memset(&g, 0, sizeof(g));
   g.x = xf; g.csum = p.csum; g.Wp = p.Wp; g.wscale = p.scale; g.bias = p.bias; g.M = M; g.N = p.N; g.K = p.K; g.flags = flags; g.xmb = cdiv(M, 16); g.rows = 16;
   return g;
@@ -841,7 +690,7 @@ static GemvP gemv_frag(const DecProj& p, const void* xf, int M, int flags) {
 // The fused out-projection + cross-Q stage (cq_fold; w.cqo = packed [W'q | W'q Wo], W'q bo), <= 8 rows, ONE launch_gemv_dual (which sets `rows`):
 //   ga: x1 = x0 + Wo a + bo in place, x1's LayerNorm partials to `stat` (the cross-attention's prologue merges them: decode step 1.352 -> 1.330 ms)
 //   gb: q_raw = W'q x0 + (W'q Wo) a + W'q bo from the f16 layer input xh and the attention output a; the cross-attention kernel applies rs, mu of x1 and b'
-static void out_cq_dual(const DecLayerW& w, const f16* a, const f16* xh, float* x1, float* stat, float* q, int M, GemvP* ga, GemvP* gb) {
+void out_cq_dual(const DecLayerW& w, const f16* a, const f16* xh, float* x1, float* stat, float* q, int M, GemvP* ga, GemvP* gb) {
   const int d = w.out.K;
   memset(ga, 0, sizeof(*ga));
   ga->x = a; ga->Wp = w.out.Wp; ga->bias = w.out.bias; ga->y = x1; ga->M = M; ga->N = d; ga->K = d; ga->flags = GV_RESID; ga->stat_out = stat;
@@ -851,7 +700,7 @@ static void out_cq_dual(const DecLayerW& w, const f16* a, const f16* xh, float* 
 // The same stage on batched rows, ONE launch_gemv_frag3 of three d x d problems: x1 = x0 + Wo a + bo (+ partials; x1's fragment image has no reader, so
 // x0's image xf stays valid), q = W'q x0 + W'q bo and q2 = (W'q Wo) a - the two k-step halves of w.cqo.  The cross-attention kernel finishes
 // q = rs (q + q2 - mu c) + b': the folded cross-Q projection as a launch of its own (6.4 us per layer at 8 utterances) is gone.
-static void out_cq_frag3(const DecLayerW& w, const f16* af, const f16* xf, float* x1, float* stat, float* q, float* q2, int M, GemvP g3[3]) {
+void out_cq_frag3(const DecLayerW& w, const f16* af, const f16* xf, float* x1, float* stat, float* q, float* q2, int M, GemvP g3[3]) {
   const int d = w.out.K;
   g3[0] = gemv_frag(w.out, af, M, GV_RESID);
   g3[0].wscale = nullptr; g3[0].y = x1; g3[0].ymb = g3[0].xmb; g3[0].stat_out = stat;
@@ -866,37 +715,21 @@ static void out_cq_frag3(const DecLayerW& w, const f16* af, const f16* xf, float
 //                     fragment image and per-16-column LayerNorm partials for the projection that follows (either may be null)
 //   frag_ln_f32       the LayerNorm-folded projection into fp32 rows (cross-Q when the fold is off, the vocabulary): statistics from the producer's partials
 //   frag_ln_gelu_xf   FFN1: LayerNorm-folded, GELU, the f16 rows straight into FFN2's fragment image
-static GemvP frag_resid(const DecProj& p, const f16* xf, float* y, f16* y_xf, float* stat_out, int M) {
+GemvP frag_resid(const DecProj& p, const f16* xf, float* y, f16* y_xf, float* stat_out, int M) {
   GemvP g = gemv_frag(p, xf, M, GV_RESID);
   g.y = y; g.y_xf = y_xf; g.ymb = g.xmb; g.stat_out = stat_out;
   return g;
 }
-static GemvP frag_ln_f32(const DecProj& p, const f16* xf, const float* stat_in, float* y, int M) {
+GemvP frag_ln_f32(const DecProj& p, const f16* xf, const float* stat_in, float* y, int M) {
   GemvP g = gemv_frag(p, xf, M, GV_LN | GV_OUT_F32);
   g.stat_in = stat_in; g.y = y;
   return g;
 }
-static GemvP frag_ln_gelu_xf(const DecProj& p, const f16* xf, const float* stat_in, f16* y_xf, int M) {
+GemvP frag_ln_gelu_xf(const DecProj& p, const f16* xf, const float* stat_in, f16* y_xf, int M) {
   GemvP g = gemv_frag(p, xf, M, GV_LN | GV_GELU);
   g.stat_in = stat_in; g.y = y_xf; g.ymb = g.xmb;
   return g;
 }
-// K slices of the batched FFN2 (GemvP::ksplit).  Measured (decode ms per utterance batch, 17 steps): 8 utterances 40.7 unsplit / 38.6 two slices / 38.9 four;
-// 12: 46.7 two / 46.9 four; 16: 60.9 unsplit / 58.7 two / 59.5 four.  WIS_FRAG_KSPLIT=1: no split (A/B switch).  ffn2_ksplit: the slices a K-deep FFN2 takes -
-// the setting where the k-steps divide into slices of whole wave quarters, else 1 (launch_gemv_frag still prefers its M split from two row blocks on)
-static int frag_ksplit_setting() {
-  static const int env_ks = getenv("WIS_FRAG_KSPLIT") ? atoi(getenv("WIS_FRAG_KSPLIT")) : 2;
-  return env_ks >= 1 && env_ks <= 8 ? env_ks : 2;
-}
-static int ffn2_ksplit(int K) {
-  const int ks = frag_ksplit_setting();
-  return ks > 1 && (K / 32) % (4 * ks) == 0 ? ks : 1;
-}
-// part: [N/16][ks][xmb][64] float4 slice sums; cnt: [N/16] tickets, zeroed once
-static void frag_set_ksplit(GemvP& g, int ks, float* part, unsigned* cnt) {
-  if (ks > 1) { g.ksplit = ks; g.kpart = part; g.kcnt = cnt; }
-}
-
 static int dec_forward_frag(wis_model* m, int M, int R, int B, bool want_logits, int sstride, int rmul, int chunks, const TreeWin* tw = nullptr) {
   const wis_config_t& c = m->cfg; hipStream_t st = m->st;
   const int d = c.d_model, H = c.n_heads, T = c.n_audio_ctx, ctx = c.n_text_ctx, MB = cdiv(M, 16);
@@ -970,8 +803,7 @@ static int dec_forward_frag(wis_model* m, int M, int R, int B, bool want_logits,
 //   ln16   WIS_B1_LN=f16 (off by default: statistics of rounded rows cost parity at large-v2): the LayerNorm-folded projections (QKV,
 //          FFN1, the vocabulary) read the f16 copy of the rows their producers leave (GV_LN16, 12.8 KB against 25.6 KB at five rows) and take the statistics
 //          from it.  (Statistics from the producers' per-16-column partials measured slower, 1.357 against 1.345 ms per step.)
-struct StepRoute { bool frag, fold, ln16; };
-static StepRoute small_route(const wis_model* m, int M) {
+StepRoute small_route(const wis_model* m, int M) {
   static const bool ln_f16 = [] { const char* e = getenv("WIS_B1_LN"); return e && !strcmp(e, "f16"); }();
   const int d = m->cfg.d_model;
   const bool frag = M > 8, ln_ok = !frag && m->cq_fold && d % 64 == 0 && M * (d / 8) <= 13 * 256;
@@ -981,7 +813,7 @@ static StepRoute small_route(const wis_model* m, int M) {
 // The step of <= 8 rows: LDS-staged skinny GEMMs (launch_gemv) with the LayerNorm folded into their prologue; more rows and tree windows take
 // dec_forward_frag.  One launch per stage: running the self-attention inside the QKV projection's launch (granule hand-off) was built, bit-identical and
 // slower (1.280 against 1.250 ms per step) - an in-launch hand-off is two fabric round trips, like a kernel boundary (retired experiments).
-int dec_forward(wis_model* m, int M, int R, int B, bool want_logits, int sstride, int rmul, const TreeWin* tw = nullptr) {
+int dec_forward(wis_model* m, int M, int R, int B, bool want_logits, int sstride, int rmul, const TreeWin* tw) {
   const wis_config_t& c = m->cfg; hipStream_t st = m->st;
   const int d = c.d_model, H = c.n_heads, T = c.n_audio_ctx, ctx = c.n_text_ctx;
   static const int env_chunks = getenv("WIS_CROSS_CHUNKS") ? atoi(getenv("WIS_CROSS_CHUNKS")) : 0;
@@ -1049,7 +881,7 @@ int dec_forward(wis_model* m, int M, int R, int B, bool want_logits, int sstride
 
 // search state of a device batch: beams tiled up front with scores [0, -inf, ...] (CT2 GPU path), counters cleared
 // (samples: the rows of an utterance are independent samples - every one starts live, with its own done flag; n_res results per utterance)
-static int init_beam_state(wis_model* m, int B, int beam, bool samples = false, int n_res = 1) {
+int init_beam_state(wis_model* m, int B, int beam, bool samples, int n_res) {
   hipStream_t st = m->st;
   const int Mrows = B * beam;
   // staged in pinned memory of its own (PinnedScratch::beam_cum / beam_tick): the copies run when the stream gets there, nothing waits for them here
@@ -1069,14 +901,14 @@ static int init_beam_state(wis_model* m, int B, int beam, bool samples = false, 
   return WIS_OK;
 }
 // the utterances' Philox keys of a sampled decode (seeds NULL: all 0), staged like the search counters
-static int upload_seeds(wis_model* m, const uint64_t* seeds, int B) {
+int upload_seeds(wis_model* m, const uint64_t* seeds, int B) {
   unsigned long long* h = m->h_pin->seeds;
   for (int b = 0; b < B; ++b) h[b] = seeds ? (unsigned long long)seeds[b] : 0ull;
   WIS_HIP_CHECK(hipMemcpyAsync(m->d_seeds, h, (size_t)B * 8, hipMemcpyHostToDevice, m->st));
   return WIS_OK;
 }
 // decoding options -> what the sampling kernels take (CTranslate2 4.1.0 BeamSearch defaults where WIS passes none, main.py:687-693)
-static SampleCfg make_sample_cfg(const wis_model* m, const wis_gen_opts_t* o, int beam, int max_new, float* patience_out) {
+SampleCfg make_sample_cfg(const wis_model* m, const wis_gen_opts_t* o, int beam, int max_new, float* patience_out) {
   const wis_config_t& c = m->cfg;
   SampleCfg sc; memset(&sc, 0, sizeof(sc));
   sc.n_vocab = c.n_vocab; sc.n_vocab_pad = m->n_vocab_pad; sc.eot = c.eot; sc.beam = beam; sc.n_cand = 2 * beam; sc.max_new = max_new;
@@ -1095,7 +927,7 @@ static SampleCfg make_sample_cfg(const wis_model* m, const wis_gen_opts_t* o, in
 
 // A patience the hypothesis storage cannot honour is an argument error, not a silently shorter search (CTranslate2 would keep
 // searching until round(beam x patience) hypotheses exist and return different ids)
-static int check_patience(int beam, float patience) {
+int check_patience(int beam, float patience) {
   const float p = patience > 0.f ? patience : 1.f;
   const long want = lroundf((float)beam * p);
   if (want > MAX_HYP - beam + 1) {
@@ -1106,7 +938,7 @@ static int check_patience(int beam, float patience) {
   return WIS_OK;
 }
 
-int upload_rows(wis_model* m, const std::vector<int>& tok, const std::vector<int>& pos, const std::vector<int>& slot, const std::vector<int>& lslot, bool wait = true, RowStage* stage = nullptr) {
+int upload_rows(wis_model* m, const std::vector<int>& tok, const std::vector<int>& pos, const std::vector<int>& slot, const std::vector<int>& lslot, bool wait, RowStage* stage) {
   const size_t n = tok.size();
   RowStage* h = stage ? stage : &m->h_pin->rows;      // (a caller that uploads twice without a wait in between passes a second staging area)
   memcpy(h->tok, tok.data(), n * 4); memcpy(h->pos, pos.data(), n * 4); memcpy(h->slot, slot.data(), n * 4); memcpy(h->lslot, lslot.data(), n * 4);
@@ -1127,21 +959,16 @@ int check_batch(wis_model* m, int B, int beam) {
   return WIS_OK;
 }
 
-// A handle runs ONE compute call at a time (its activations, KV caches and stream are single-instance; the Python shim feeds every
-// replica from one worker thread).  A second thread entering the same handle is refused with WIS_E_STATE instead of silently
-// corrupting the first call's state - SURVEY 8(b) asks for thread safety at the boundary: concurrency comes from replicas and the
-// micro-batcher, never from two calls inside one replica.
-static std::atomic<int> g_active_calls[64];      // compute calls running per device (all handles): front_half's stream choice (generate.hip)
-struct BusyGuard {
-  wis_model* m; bool ok;
-  explicit BusyGuard(wis_model* mm) : m(mm), ok(!mm->busy.test_and_set(std::memory_order_acquire)) { if (ok) g_active_calls[m->device & 63].fetch_add(1, std::memory_order_relaxed); }
-  ~BusyGuard() { if (ok) { g_active_calls[m->device & 63].fetch_sub(1, std::memory_order_relaxed); m->busy.clear(std::memory_order_release); } }
-};
-#define WIS_ENTER(m, what)                                                                                      \
-  BusyGuard _busy(m);                                                                                           \
-  if (!_busy.ok) { set_error("%s: another call is running on this handle (one call at a time per replica)", what); return WIS_E_STATE; }
+// n rows at one position, row r in KV slot r of its own (R = 1 rows of n utterances; the tuning taps' B * beam rows of token 100)
+int single_row_setup(wis_model* m, int n, const std::vector<int>& tok, int pos) {
+  std::vector<int> ps(n, pos), slot(n), ls(n);
+  for (int r = 0; r < n; ++r) { slot[r] = r; ls[r] = r; }
+  return upload_rows(m, tok, ps, slot, ls);
+}
 
-}  // namespace
+std::atomic<int> g_active_calls[64];      // compute calls running per device, every handle and entry point (model.hpp BusyGuard); read by front_half's stream choice (generate.hip)
+
+}  // namespace wis
 
 // =======================================================================================
 extern "C" {
@@ -1255,12 +1082,6 @@ int wis_model_clone(wis_model_t* parent, wis_model_t** out) {
   return WIS_OK;
 }
 
-}  // extern "C" (reopened below: the generate driver is made of static helpers)
-
-#include "generate.hip"      // the generate driver and its three entry points
-
-extern "C" {
-
 int wis_last_no_speech_prob(wis_model_t* m, int B, float* out) {
   if (!m || !out || B < 1) { set_error("wis_last_no_speech_prob: bad argument"); return WIS_E_ARG; }
   WIS_ENTER(m, "wis_last_no_speech_prob")
@@ -1290,68 +1111,6 @@ int wis_last_trajectory(wis_model_t* m, int b, int32_t* tok, int32_t* org, int c
   return WIS_OK;
 }
 
-// wis_debug_search / wis_debug_search_n: the sampling tail over a caller's logits table (single: one hypothesis per utterance)
-static int debug_search_impl(const char* who, wis_model_t* m, const float* logits, int n_steps, int B, const wis_gen_opts_t* o, const uint64_t* seeds, const uint32_t* noise,
-                             bool single, int32_t* out_ids, int32_t* out_len, float* out_score, int32_t* out_finish_step, int32_t* out_parent) {
-  WIS_HIP_CHECK(hipSetDevice(m->device));
-  const wis_config_t& c = m->cfg;
-  SampleCtx g;      // a search over given logits: a one-token prompt
-  int beam = 1;     // rows per utterance: beams, or the samples of a sampled decode
-  WIS_RET(resolve_sample_opts(o, single, false, &g, &beam));
-  WIS_RET(check_batch(m, B, beam));
-  if (!g.sampling()) WIS_RET(check_patience(beam, o->patience));
-  const int max_new = o->max_new_tokens > 0 ? std::min(o->max_new_tokens, MAX_STEPS) : n_steps;
-  if (max_new > n_steps) { set_error("%s: %d steps of logits for max_new_tokens %d", who, n_steps, max_new); return WIS_E_ARG; }
-  hipStream_t st = m->st;
-  const int Mrows = B * beam, V = c.n_vocab;
-  float patience;
-  WIS_RET(resolve_rep_opts(o, &g));
-  if (noise && !g.sampling()) { set_error("%s: a noise table without sampling", who); return WIS_E_ARG; }
-  struct DevBlock { void* p = nullptr; ~DevBlock() { if (p) hipFree(p); } } d_noise;      // one step of the noise table [Mrows][V]
-  if (noise && hipMalloc(&d_noise.p, (size_t)Mrows * V * 4) != hipSuccess) { (void)hipGetLastError(); set_error("%s: out of device memory", who); return WIS_E_NOMEM; }
-  WIS_RET(init_beam_state(m, B, beam, g.sampling(), g.sampling() ? beam : g.n_res));
-  if (g.sampling()) WIS_RET(upload_seeds(m, seeds, B));
-  g.m = m; g.st = st; g.B = B; g.P = 1; g.beam = beam;
-  g.sc = make_sample_cfg(m, o, beam, max_new, &patience);
-  apply_sample_opts(m, &g);
-  g.sp.noise = static_cast<const unsigned*>(d_noise.p);
-  g.bias_all = o->suppress_default ? m->bias_all : nullptr;
-  g.ts = o->timestamps != 0;
-  g.ts_max_init = o->max_initial_timestamp_index < 0 ? -1 : o->max_initial_timestamp_index;
-  std::vector<int> done(B, 0), fin(B, -1), par(Mrows);
-  for (int s = 0; s < max_new; ++s) {
-    WIS_HIP_CHECK(hipMemcpy2DAsync(m->logits, (size_t)m->n_vocab_pad * 4, logits + (size_t)s * Mrows * V, (size_t)V * 4, (size_t)V * 4, Mrows, hipMemcpyHostToDevice, st));
-    if (noise) WIS_HIP_CHECK(hipMemcpyAsync(d_noise.p, noise + (size_t)s * Mrows * V, (size_t)Mrows * V * 4, hipMemcpyHostToDevice, st));
-    // step 0 samples every beam of an utterance from ONE row (wis_generate: the last prompt row; here row b*beam), later steps row b*beam + j
-    WIS_RET(sampling_tail(g, {beam, s == 0 ? 0 : 1, 0}, TAIL_NO_CACHE));
-    WIS_HIP_CHECK(hipMemcpyAsync(done.data(), m->bs.done, (size_t)B * 4, hipMemcpyDeviceToHost, st));
-    WIS_HIP_CHECK(hipMemcpyAsync(par.data(), m->bs.parent, (size_t)Mrows * 4, hipMemcpyDeviceToHost, st));
-    WIS_HIP_CHECK(hipStreamSynchronize(st));
-    bool all = true;
-    for (int b = 0; b < B; ++b) { if (done[b] && fin[b] < 0) fin[b] = s; all = all && done[b]; }
-    if (out_parent) for (int r = 0; r < Mrows; ++r) out_parent[(size_t)s * Mrows + r] = par[r];
-    if (all) break;
-  }
-  for (int b = 0; b < B; ++b) if (fin[b] < 0) { set_error("%s: utterance %d did not finish within %d steps", who, b, max_new); return WIS_E_STATE; }
-  WIS_RET(results_from_device(m, B * g.n_res, max_new, out_ids, out_len, out_score));
-  if (out_finish_step) for (int b = 0; b < B; ++b) out_finish_step[b] = fin[b];
-  return WIS_OK;
-}
-
-int wis_debug_search(wis_model_t* m, const float* logits, int n_steps, int B, const wis_gen_opts_t* o,
-                     int32_t* out_ids, int32_t* out_len, float* out_score, int32_t* out_finish_step, int32_t* out_parent) {
-  if (!m || !logits || !o || !out_ids || !out_len || n_steps < 1 || n_steps > MAX_STEPS) { set_error("wis_debug_search: bad argument"); return WIS_E_ARG; }
-  WIS_ENTER(m, "wis_debug_search")
-  return debug_search_impl("wis_debug_search", m, logits, n_steps, B, o, nullptr, nullptr, true, out_ids, out_len, out_score, out_finish_step, out_parent);
-}
-
-int wis_debug_search_n(wis_model_t* m, const float* logits, int n_steps, int B, const wis_gen_opts_t* o, const uint64_t* seeds, const uint32_t* noise,
-                       int32_t* out_ids, int32_t* out_len, float* out_score, int32_t* out_finish_step, int32_t* out_parent) {
-  if (!m || !logits || !o || !out_ids || !out_len || n_steps < 1 || n_steps > MAX_STEPS) { set_error("wis_debug_search_n: bad argument"); return WIS_E_ARG; }
-  WIS_ENTER(m, "wis_debug_search_n")
-  return debug_search_impl("wis_debug_search_n", m, logits, n_steps, B, o, seeds, noise, false, out_ids, out_len, out_score, out_finish_step, out_parent);
-}
-
 int wis_debug_handoff(wis_model_t* m, int raise_flag, int* retries, int* spin_disabled) {
   if (!m) { set_error("wis_debug_handoff: bad argument"); return WIS_E_ARG; }
   WIS_ENTER(m, "wis_debug_handoff")
@@ -1369,13 +1128,6 @@ int wis_debug_handoff(wis_model_t* m, int raise_flag, int* retries, int* spin_di
 int wis_last_timing(const wis_model_t* m, wis_timing_t* t) {
   if (!m || !t) { set_error("wis_last_timing: bad argument"); return WIS_E_ARG; }
   *t = m->timing; return WIS_OK;
-}
-
-// n rows at one position, row r in KV slot r of its own (R = 1 rows of n utterances; the tuning taps' B * beam rows of token 100)
-static int single_row_setup(wis_model* m, int n, const std::vector<int>& tok, int pos) {
-  std::vector<int> ps(n, pos), slot(n), ls(n);
-  for (int r = 0; r < n; ++r) { slot[r] = r; ls[r] = r; }
-  return upload_rows(m, tok, ps, slot, ls);
 }
 
 int wis_detect_language(wis_model_t* m, const float* input, int input_kind, int B, float* lang_probs) {
@@ -1402,10 +1154,3 @@ int wis_detect_language(wis_model_t* m, const float* input, int input_kind, int 
 }
 
 }  // extern "C"
-
-#include "taps.hip"      // the debug / measurement taps and the single-kernel entry points
-
-// word-level alignment (wis_align, wis_op_dtw, wis_op_align_matrix): its kernels and driver, in this translation unit
-#include "align.hip"
-// speaker verification (wis_sv_*): its kernels and driver, in this translation unit
-#include "sv.hip"

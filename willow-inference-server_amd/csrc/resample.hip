@@ -1,4 +1,4 @@
-// resample.hip — included by logmel.hip (one translation unit for the audio front end).  Sample-rate conversion of an upload to 16 kHz on gfx950: the resampling half of
+// resample.hip — an object of its own beside logmel.hip (the audio front end's other half; the device context is logmel.hip's, common.hpp).  Sample-rate conversion of an upload to 16 kHz on gfx950: the resampling half of
 // `librosa.load(audio_file, sr=16000)` (reference main.py:579, :815; `x-audio-sample-rate` on /api/willow).
 //
 // The filter and the output are the ones wis_hip/audio.py defines (_resample_filter, resample):

@@ -1,5 +1,5 @@
 // sv.hip — speaker verification: the WavLM-base-plus-sv x-vector embedder (HF WavLMForXVector, post-LN encoder, weighted layer sum).
-// Compiled as part of model.hip's translation unit (included at its end): the library is built from four HIP objects.
+// An object of its own: it shares no state with the Whisper handle (model.hpp), only the encoder's launch_* functions and tap.hpp's scaffold.
 //
 // PCM (host, already trimmed / gain-normalised / feature-extractor-normalised by wis_hip/sv.py) -> 512-float embedding (host).  Every
 // step from the first convolution to the statistics pooling runs on the GPU:
@@ -23,6 +23,7 @@
 
 #include "common.hpp"
 #include "kernels.hpp"
+#include "tap.hpp"
 
 using namespace wis;
 
@@ -325,8 +326,6 @@ __global__ void sv_convert_kernel(const void* __restrict__ src, int src_f16, voi
   }
 }
 
-inline int sv_blocks_for(int64_t n) { int64_t b = (n + 255) / 256; return (int)(b > 8192 ? 8192 : (b < 1 ? 1 : b)); }
-
 }  // namespace
 
 // ---- host side ----------------------------------------------------------------------------------------------------------------------
@@ -401,7 +400,7 @@ int sv_load(wis_sv* s, const SvLoader& Ld, const std::string& name, int64_t ne, 
     WIS_RET(sv_alloc(s, dst, (size_t)(alloc_ne > ne ? alloc_ne : ne)));
     if (alloc_ne > ne) WIS_HIP_CHECK(hipMemsetAsync(*dst, 0, (size_t)alloc_ne * sizeof(T), s->st));
   }
-  hipLaunchKernelGGL(sv_convert_kernel, dim3(sv_blocks_for(ne)), dim3(256), 0, s->st, p, f16, static_cast<void*>(*dst), (int)(sizeof(T) == 2), ne, scale);
+  hipLaunchKernelGGL(sv_convert_kernel, dim3(blocks_for(ne)), dim3(256), 0, s->st, p, f16, static_cast<void*>(*dst), (int)(sizeof(T) == 2), ne, scale);
   return WIS_OK;
 }
 
@@ -480,7 +479,7 @@ int sv_load_weights(wis_sv* s, const SvLoader& Ld) {
     WIS_RET(sv_alloc(s, &dbk, (size_t)n));
     WIS_RET(sv_alloc(s, &s->tab, (size_t)H * n));
     WIS_HIP_CHECK(hipMemcpyAsync(dbk, bk.data(), (size_t)n * 4, hipMemcpyHostToDevice, s->st));
-    hipLaunchKernelGGL(sv_bias_table_kernel, dim3(sv_blocks_for((int64_t)H * n)), dim3(256), 0, s->st, E, dbk, s->tab, L);
+    hipLaunchKernelGGL(sv_bias_table_kernel, dim3(blocks_for((int64_t)H * n)), dim3(256), 0, s->st, E, dbk, s->tab, L);
     WIS_HIP_CHECK(hipStreamSynchronize(s->st));       // (bk leaves scope)
   }
   // softmax(layer_weights) on the host: the per-layer LayerNorm launches take it as an argument
@@ -619,10 +618,10 @@ int sv_forward(wis_sv* s, int64_t n, int stop_hidden) {
     if (i + 1 < NTD) {
       const int kn = TD_K[i + 1], dn = TD_DIL[i + 1], tn = t - (kn - 1) * dn;
       if (dn == 1) {       // plain ReLU image; the next GEMM reads it with lda = C (k taps overlap)
-        hipLaunchKernelGGL(sv_relu_gather_kernel, dim3(sv_blocks_for((int64_t)t * TD_DIM[i])), dim3(256), 0, st, s->z, N, s->gbuf, t, TD_DIM[i], 1, 1);
+        hipLaunchKernelGGL(sv_relu_gather_kernel, dim3(blocks_for((int64_t)t * TD_DIM[i])), dim3(256), 0, st, s->z, N, s->gbuf, t, TD_DIM[i], 1, 1);
         lda = TD_DIM[i];
       } else {
-        hipLaunchKernelGGL(sv_relu_gather_kernel, dim3(sv_blocks_for((int64_t)tn * kn * TD_DIM[i])), dim3(256), 0, st, s->z, N, s->gbuf, tn, TD_DIM[i], kn, dn);
+        hipLaunchKernelGGL(sv_relu_gather_kernel, dim3(blocks_for((int64_t)tn * kn * TD_DIM[i])), dim3(256), 0, st, s->z, N, s->gbuf, tn, TD_DIM[i], kn, dn);
         lda = kn * TD_DIM[i];
       }
       a = s->gbuf;

@@ -1,53 +1,15 @@
-// taps.hip — debug, tuning and measurement taps (wis_debug_*, wis_bench_weight_stream, wis_dev_*, wis_op_*).  Included by model.hip: the taps run the
-// product's own static helpers (dec_forward, the stage builders, prep_projection), not copies of them.
-//
-// How to write a tap (a wis_op_* entry point: one product launch_* function on caller-supplied device memory; here, in align.hip and in sv.hip):
-//   Tap t(device, "wis_op_name"); WIS_RET(t.rc);        get_ctx + the device's op mutex; t.st is the stream all taps of a device share
-//   argument checks: set_error("wis_op_name: ...") and return (after the Tap here and in align.hip, in front of it in sv.hip: a call that is
-//                                                       wrong in its device and in an argument keeps the answer it always got)
-//   WIS_RET(t.get(&p, n_elems[, true]));                private device scratch (true: zeroed on t.st); sets the out-of-memory message itself
-//   WIS_RET(launch_...(t.st, ...));                     any step but the last: returning early is always safe
-//   return t.finish(launch_...(t.st, ...));             the last launch: collects the launch error, synchronises, gives the verdict
-// The Tap's destructor synchronises the stream when finish() was not reached, frees the scratch and only then lets go of the mutex, so no
-// return path frees memory under work in flight and none needs a clean-up of its own: no hipMalloc / hipFree / hipStreamSynchronize in a tap.
-namespace {
-struct Tap {
-  const char* const name;      // the entry point the caller used: prefix of the messages
-  hipStream_t st = nullptr;
-  int rc;                      // entry verdict (get_ctx's code)
-  Tap(int device, const char* who) : name(who) {
-    DeviceCtx* c = nullptr;
-    if ((rc = get_ctx(device, &c)) != WIS_OK) return;
-    lock = std::unique_lock<std::mutex>(ctx_op_mutex(c));
-    st = ctx_stream(c);
-  }
-  Tap(const Tap&) = delete;
-  Tap& operator=(const Tap&) = delete;
-  template <class T> int get(T** p, size_t n_elems, bool zeroed = false) {
-    const size_t bytes = n_elems * sizeof(T) ? n_elems * sizeof(T) : 16;
-    void* q = nullptr;
-    if (hipMalloc(&q, bytes) != hipSuccess) { (void)hipGetLastError(); set_error("%s: out of device memory", name); return WIS_E_NOMEM; }
-    scratch.push_back(q); *p = reinterpret_cast<T*>(q);
-    if (zeroed) hipMemsetAsync(q, 0, bytes, st);
-    return WIS_OK;
-  }
-  int finish(int launch_rc) {      // launch_rc wins; otherwise a HIP error of the launches or of the stream becomes WIS_E_HIP
-    const hipError_t e0 = hipGetLastError(), e = hipStreamSynchronize(st);
-    synced = true;
-    if (launch_rc) return launch_rc;
-    if (e0 != hipSuccess || e != hipSuccess) { set_error("%s: %s", name, hipGetErrorString(e0 != hipSuccess ? e0 : e)); return WIS_E_HIP; }
-    return WIS_OK;
-  }
-  ~Tap() {      // (the members go after this body: the frees happen under the lock)
-    if (lock.owns_lock() && !synced) hipStreamSynchronize(st);
-    for (void* q : scratch) hipFree(q);
-  }
- private:
-  std::unique_lock<std::mutex> lock;
-  std::vector<void*> scratch;
-  bool synced = false;
-};
-}  // namespace
+// taps.hip — debug, tuning and measurement taps (wis_debug_*, wis_bench_weight_stream, wis_dev_*, wis_op_*).  An object of its own: the taps run the
+// product's own helpers (dec_forward, the stage builders, prep_projection: model.hpp), not copies of them.  tap.hpp says how to write a wis_op_* tap.
+#include <string.h>
+#include <algorithm>
+#include <vector>
+
+#include "common.hpp"
+#include "kernels.hpp"
+#include "model.hpp"
+#include "tap.hpp"
+
+using namespace wis;
 
 extern "C" {
 
@@ -59,7 +21,7 @@ int wis_debug_encode(wis_model_t* m, const float* input, int input_kind, int B, 
   WIS_RET(stage_input(m, input, input_kind, B));
   WIS_RET(run_encoder(m, B));
   const int64_t n = (int64_t)B * m->cfg.n_audio_ctx * m->cfg.d_model;
-  hipLaunchKernelGGL(f16_to_f32_kernel, dim3(blocks_for(n)), dim3(256), 0, m->st, m->mem, m->x, n);   // x is free after the encoder
+  launch_f16_to_f32(m->st, m->mem, m->x, n);   // x is free after the encoder
   WIS_HIP_CHECK(hipMemcpyAsync(enc_out, m->x, (size_t)n * 4, hipMemcpyDeviceToHost, m->st));
   WIS_HIP_CHECK(hipStreamSynchronize(m->st));
   return WIS_OK;
@@ -103,48 +65,6 @@ int wis_debug_logits(wis_model_t* m, const float* input, int input_kind, int B, 
 int wis_debug_logits_rows(wis_model_t* m, const float* input, int input_kind, int B, const int32_t* dec_in, int T, int R, float* logits) {
   if (!m || !input || !dec_in || !logits || T < 1 || T > m->cfg.n_text_ctx || R < 1 || R > 16) { set_error("wis_debug_logits_rows: bad argument (1 <= R <= 16)"); return WIS_E_ARG; }
   return debug_logits_rows("wis_debug_logits_rows", m, input, input_kind, B, dec_in, T, R, logits);
-}
-
-int wis_debug_tree_logits(wis_model_t* m, const float* input, int input_kind, const int32_t* prompt, int P, int beam,
-                          const int32_t* tok, const int32_t* org, int n_steps, float* logits) {
-  if (!m || !input || !prompt || !tok || !org || !logits || P < 1 || P > 16 || beam < 1 || beam > MAX_R || n_steps < 1 || n_steps > std::min(32, MAX_ROWS / std::max(beam, 1))) {
-    set_error("wis_debug_tree_logits: bad argument (1 <= n_steps <= min(32, %d / beam))", MAX_ROWS); return WIS_E_ARG;
-  }
-  WIS_ENTER(m, "wis_debug_tree_logits")
-  WIS_HIP_CHECK(hipSetDevice(m->device));
-  WIS_RET(check_batch(m, 1, beam));
-  const wis_config_t& c = m->cfg; hipStream_t st = m->st;
-  const int k = beam, V = c.n_vocab;
-  for (int i = 0; i < n_steps * k; ++i) if (tok[i] < 0 || tok[i] >= V || org[i] < 0 || org[i] >= k) { set_error("wis_debug_tree_logits: token / origin out of range"); return WIS_E_ARG; }
-  WIS_RET(stage_input(m, input, input_kind, 1));
-  WIS_RET(run_encoder(m, 1));
-  WIS_RET(run_cross_kv(m, 1));
-  m->spin_now = false;
-  // the prompt: rows at positions 0 .. P-1 of slot 0, then every slot gets a copy (what the first step's kv_reorder does)
-  std::vector<int> ptok(P), ppos(P), pslot(P, 0), pls(P, 0);
-  for (int i = 0; i < P; ++i) { ptok[i] = prompt[i]; ppos[i] = i; }
-  WIS_RET(upload_rows(m, ptok, ppos, pslot, pls));
-  WIS_RET(dec_forward(m, P, P, 1, false, beam, 0));
-  auto& hs = m->h_pin->tree_seed;
-  for (int j = 0; j < MAX_R; ++j) hs.parent[j] = 0;
-  hs.step = 1; hs.done = 0;
-  WIS_HIP_CHECK(hipMemcpyAsync(m->bs.parent, hs.parent, (size_t)k * 4, hipMemcpyHostToDevice, st));
-  WIS_HIP_CHECK(hipMemcpyAsync(m->bs.step_u, &hs.step, 4, hipMemcpyHostToDevice, st));
-  WIS_HIP_CHECK(hipMemcpyAsync(m->bs.done, &hs.done, 4, hipMemcpyHostToDevice, st));
-  WIS_RET(launch_kv_reorder(st, m->kc_all, m->vc_all, m->kv_layer_stride, c.n_dec_layers, m->bs, 1, beam, P, c.n_text_ctx, c.d_model));
-  // one window: steps 1 .. n_steps, rows from trajectory entries 0 .. n_steps - 1
-  std::vector<int> hd((size_t)n_steps * MAX_R * 2, 0);
-  pack_traj(hd.data(), tok, org, n_steps, k);
-  std::vector<int> wt, wp, wsl, wls;
-  int* ha = m->h_pin->anc;
-  const int Mpad = fill_tree_window(hd.data(), 1, n_steps, k, P, wt, wp, wsl, wls, ha);
-  WIS_RET(upload_rows(m, wt, wp, wsl, wls, false, &m->h_pin->win_rows));
-  WIS_HIP_CHECK(hipMemcpyAsync(m->d_anc, ha, (size_t)Mpad * ANC_W * 4, hipMemcpyHostToDevice, st));
-  const TreeWin tw{m->d_anc, P, ANC_W};
-  WIS_RET(dec_forward(m, Mpad, 16, Mpad / 16, true, 1, 0, &tw));
-  WIS_HIP_CHECK(hipMemcpy2DAsync(logits, (size_t)V * 4, m->logits, (size_t)m->n_vocab_pad * 4, (size_t)V * 4, (size_t)n_steps * k, hipMemcpyDeviceToHost, st));
-  WIS_HIP_CHECK(hipStreamSynchronize(st));
-  return WIS_OK;
 }
 
 int wis_debug_phase_cycles(wis_model_t* m, int B, int beam, int pos, uint64_t* out) {
@@ -539,7 +459,7 @@ int wis_op_gemv_qkv(int device, const float* x, const float* gamma, const float*
   if (M > 8) { WIS_RET(t.get(&xf, xf_elems(d, MB), true)); WIS_RET(t.get(&stt, (size_t)M * (d / 16) * 2)); }
   // what load_weights does for a layer's DecProj `qkv` (w.qkv): the bias's query part scaled, the LayerNorm folded, the query rows scaled by the packer
   hipMemcpyAsync(wtmp, W, (size_t)N * d * 2, hipMemcpyDeviceToDevice, st);
-  hipLaunchKernelGGL(convert_kernel, dim3(blocks_for(N)), dim3(256), 0, st, bias, 0, b2, 0, (int64_t)N, (int64_t)1, (int64_t)1, (int64_t)d, qs);
+  launch_convert(st, bias, 0, b2, 0, N, 1, 1, d, qs);
   const DecProj qkv{wp, nullptr, b2, cs, N, d, gemv_rows_for(N, d)};
   WIS_RET(prep_projection(st, wtmp, N, N, d, d, qs, gamma, beta, b2, cs, wp, nullptr, qkv.rows));
   GemvP g;
@@ -570,7 +490,7 @@ int wis_op_gemv_out_cq(int device, const void* a, const float* x0, const void* W
   else WIS_RET(t.get(&xh, (size_t)M * d));
   // load_weights, decoder layer: cq (the cross-Q bias scaled, the LayerNorm folded: bias / csum are what the cross-attention kernel takes as qb / qcs), out, then the fold
   hipMemcpyAsync(wtmp, Wq, (size_t)d * d * 2, hipMemcpyDeviceToDevice, st);
-  hipLaunchKernelGGL(convert_kernel, dim3(blocks_for(d)), dim3(256), 0, st, bq, 0, qb, 0, (int64_t)d, (int64_t)1, (int64_t)1, (int64_t)d, qs);
+  launch_convert(st, bq, 0, qb, 0, d, 1, 1, d, qs);
   hipMemsetAsync(qcs, 0, (size_t)d * 4, st);
   DecLayerW w{};
   w.out = DecProj{p_out, nullptr, bo, nullptr, d, d, gemv_rows_for(d, d)};
@@ -581,7 +501,7 @@ int wis_op_gemv_out_cq(int device, const void* a, const float* x0, const void* W
   hipMemcpyAsync(x1, x0, (size_t)M * d * 4, hipMemcpyDeviceToDevice, st);      // the residual epilogue works in place
   if (!frag) {
     // dec_forward: one dual launch on the f16 rows (the attention output; the f16 copy of the layer input that the embedding / FFN2 epilogues leave)
-    hipLaunchKernelGGL(convert_kernel, dim3(blocks_for((int64_t)M * d)), dim3(256), 0, st, x0, 0, xh, 1, (int64_t)M, (int64_t)d, (int64_t)d, (int64_t)0, 1.f);
+    launch_convert(st, x0, 0, xh, 1, M, d, d, 0, 1.f);
     GemvP ga, gb;
     out_cq_dual(w, reinterpret_cast<const f16*>(a), xh, x1, stat, q, M, &ga, &gb);
     return t.finish(launch_gemv_dual(st, ga, gb));
