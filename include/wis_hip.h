@@ -235,7 +235,12 @@ typedef struct {
  * (SURVEY 8b): any number of threads may call into DIFFERENT handles; a handle itself runs one
  * compute call at a time (single-instance activations / KV caches) - a second thread entering a
  * busy handle gets WIS_E_STATE at once, nothing is corrupted.  The shim's micro-batcher feeds each
- * replica from one worker thread and coalesces concurrent requests into device batches. */
+ * replica from one worker thread and coalesces concurrent requests into device batches.
+ * prompt: i32 [B][P], one common length P in 1 .. n_text_ctx / 2 + 4 (228; beyond: WIS_E_UNSUPPORTED).  P <= 16 (with B P <= 96) runs as one
+ * merged prefill + first step pass.  Longer prompts - text behind <|startofprev|>, a prefix behind the start sequence - are prefilled in windows of
+ * 16 positions, their K / V is kept once per utterance and read there by every beam, and one captured step serves every length; the drafted entry
+ * points (wis_generate_draft, wis_generate_draft_beam) answer them with WIS_E_UNSUPPORTED.  max_new_tokens = 0 resolves to
+ * min(n_text_ctx / 2, n_text_ctx - P). */
 int wis_generate(wis_model_t* m, const float* input, int B, const int32_t* prompt, int P,
                  const wis_gen_opts_t* opts, int32_t* out_ids, int32_t* out_len, float* out_score);
 /* wis_generate with n = opts->num_hypotheses results per utterance: out_ids [B][n][max_new], out_len [B][n], out_score [B][n] or NULL.
@@ -350,6 +355,11 @@ int wis_debug_search_n(wis_model_t* m, const float* logits, int n_steps, int B, 
  * only taken while B * heads * live handles on the GPU <= 192), spin_disabled = the handle has switched to the ticket form for good.
  * raise_flag != 0 raises the give-up flag by hand, so that the NEXT compute call exercises the repeat path (tests). */
 int wis_debug_handoff(wis_model_t* m, int raise_flag, int* retries, int* spin_disabled);
+/* captured decode-step graphs the handle holds (one per shape and option set; prompts of more than 16 tokens share one whatever their length) */
+int wis_debug_graph_count(wis_model_t* m, int* count);
+/* the self-attention form of the long-prompt route's decode step on this handle: 1 = dec_self_attn_long_kernel, 0 = the TREE form of dec_self_attn_kernel
+ * (what WIS_SA_LONG=0 selects for the process), -1 = back to the switch.  For A/B measurements in one process (tools/prompt_bench.py). */
+int wis_debug_sa_long(wis_model_t* m, int form);
 
 /* ---- timing taps: wall/device ms of the stages of the LAST wis_generate on this handle */
 typedef struct {
@@ -462,6 +472,12 @@ int wis_op_dec_cross_attn_stat(int device, const float* q, const float* q2, cons
 int wis_op_dec_self_attn_ex(int device, const float* q, const void* kc_f16, const void* vc_f16, const int32_t* pos, void* out_f16,
                             int M, int H, int ctx, int rpu, int sstride, int rmul, int nb, int out_mb,
                             const int32_t* anc, int w0, int aw, const int32_t* base);
+/* the decode step's self-attention behind a prompt of more than 16 tokens (the long-prompt route): B utterances of k <= 8 rows, row m = b k + j.  Row m
+ * reads positions < plen[b] from slot b k - the prompt prefix, kept once per utterance - and positions plen[b] .. pos[m] from its own slot b k + j; nothing
+ * else is read unmasked (reads beyond a row's length come from clamped positions of those two slots).  q f32 [B k][d], kc / vc f16 [B k][ctx][d], pos i32
+ * [B k] (>= plen[b] - 1), plen i32 [B] in [1, 256] (device memory, as pos) -> out f16 [B k][d], or the fragment image of out_mb row blocks as above. */
+int wis_op_dec_self_attn_long(int device, const float* q, const void* kc_f16, const void* vc_f16, const int32_t* pos, const int32_t* plen, void* out_f16,
+                              int B, int k, int H, int ctx, int out_mb);
 /* the self-attention QKV projection behind its LayerNorm with the scatter epilogue (GV_LN | GV_QKV), prepared as the loader prepares it (LayerNorm
  * fold, 1/8 on the query rows, packing): x f32 [M][d], W f16 [3d][d], bias f32 [3d] -> q f32 [M][d]; row m's key / value rows go to
  * kc / vc f16 [slots][ctx][d] at (slot[m], pos[m]).  M <= 8: the LDS-staged form; more rows: fragment image + row partials (launch_gemv_frag). */
@@ -536,6 +552,11 @@ int wis_op_resample_segment(int device, const float* x_slice, int64_t n_slice, i
  * < P - 1 + step_u[b] (<= ctx: the caller's duty), all L layers, K and V; nothing else is written.  beam = 1: nothing runs. */
 int wis_op_kv_reorder(int device, void* kc_f16, void* vc_f16, int64_t layer_stride_elems, int L, const int32_t* parent, const int32_t* step_u,
                       const int32_t* done, int B, int beam, int P, int ctx, int d);
+/* wis_op_kv_reorder behind a long prompt: plen i32 [B] (device memory) in P's place, and a lower bound - for every utterance b with done[b] == 0, slot
+ * b beam + j becomes a copy of slot parent[b beam + j] at positions [plen[b], plen[b] - 1 + step_u[b]) only; positions < plen[b] of every slot (the prompt
+ * prefix lives in slot b beam alone) and everything else stay as they are. */
+int wis_op_kv_reorder_from(int device, void* kc_f16, void* vc_f16, int64_t layer_stride_elems, int L, const int32_t* parent, const int32_t* step_u,
+                           const int32_t* done, const int32_t* plen, int B, int beam, int ctx, int d);
 /* the cache gather after a verified draft window (one utterance), in place: vstate i32 [32 + 8 x 32]: [2] = window steps nwin (<= 32, w0 + nwin <= ctx:
  * the caller's duty), [16 + j] = the slot that holds beam j's positions < w0, [32 + 32 j + u] = the slot that holds its position w0 + u; slot j (< beam)
  * becomes that history.  done[0] == 1 or nwin <= 0: nothing is written (done[0] == 2, a parked search, still gathers). */

@@ -1419,6 +1419,10 @@ __global__ __launch_bounds__(64) void dec_self_attn_kernel(const float* __restri
 }
 int launch_dec_self_attn(hipStream_t st, const SelfAttnP& p) {
   if (p.ctx > 512 || p.ctx < 64) { set_error("dec_self_attn: ctx=%d outside [64, 512]", p.ctx); return WIS_E_UNSUPPORTED; }
+  if (p.plen) {      // the long-prompt route's decode step: rpu rows per utterance, each in a slot of its own behind the shared prefix
+    if (p.anc || p.rmul != 1 || p.rpu < 1 || p.M % p.rpu != 0) { set_error("dec_self_attn: a shared prompt prefix takes whole utterances of decode rows (M %d, rpu %d, rmul %d)", p.M, p.rpu, p.rmul); return WIS_E_ARG; }
+    return launch_dec_self_attn_long(st, p.q, p.kc, p.vc, p.pos, p.plen, p.M / p.rpu, p.rpu, p.H, p.d, p.ctx, p.sstride, p.out, p.out_mb);
+  }
 #define WIS_SA(TREEv, NBv) hipLaunchKernelGGL((dec_self_attn_kernel<TREEv, NBv>), dim3(p.M, p.H), dim3(64), 0, st, p.q, p.kc, p.vc, p.pos, p.d, p.ctx, p.rpu, p.sstride, p.rmul, p.out, \
                                               p.prof, p.out_mb, p.anc, p.w0, p.aw, p.base)
   if (p.anc) {
@@ -1428,6 +1432,173 @@ int launch_dec_self_attn(hipStream_t st, const SelfAttnP& p) {
   else if (p.nb == 4) WIS_SA(false, 4);
   else WIS_SA(false, 8);
 #undef WIS_SA
+  return WIS_OK;
+}
+
+// =======================================================================================
+// The decode step's self-attention behind a LONG prompt (generate.hip, the long-prompt route).  grid (B, H), block 256 = 4 waves: ONE workgroup serves the
+// k <= MAX_R live rows (m = b k + j) of utterance b at head h.  The prompt's positions [0, plen[b]) lie in the utterance's first slot b * sstride and nowhere
+// else - every K / V chunk of them is loaded ONCE and used against all k queries - and row j's own positions plen[b] .. pos[m] lie in slot b * sstride + j.
+// Lane = (pl = position slot 0..7, c = 16-byte chunk 0..7 of the head), as in dec_self_attn_kernel; the history is split over the waves in blocks of 8
+// positions: prefix block i of wave w holds positions 32 i + 8 w + pl (8 blocks: plen <= SA_LONG_MAX_PLEN = 256), suffix chunk s holds plen + 32 s + 8 w + pl
+// of every row.  A wave issues its 8 + 8 prefix requests - addresses clamped by ctx alone, so they wait for nothing - and the first suffix chunk of all k rows
+// (which needs plen: one scalar round trip) before it consumes anything; only rows with more than 32 generated positions go round a loop, one chunk of
+// all k rows per pass.  Rows j >= k are skipped (k is a kernel argument: uniform branches).  Every (wave, row) keeps a partial (max, sum, acc[8] per lane = 64 columns over the 8 chunk lanes); the four waves' partials meet in LDS.
+// Arithmetic as the plain kernel's: f16 K / V, f32 q, f32 dots and accumulation, __expf, the output rounded to f16 - in another summation order.
+// Reads beyond a row's length come from clamped addresses inside the cache (position <= min(ctx - 1, ...) of a slot the row may read) and are masked.
+__global__ __launch_bounds__(256) void dec_self_attn_long_kernel(const float* __restrict__ q, const f16* __restrict__ kc, const f16* __restrict__ vc,
+                                                                 const int* __restrict__ pos, const int* __restrict__ plen, int d, int ctx, int k, int sstride,
+                                                                 f16* __restrict__ out, int out_mb) {
+  constexpr int PB = SA_LONG_MAX_PLEN / 32;      // prefix blocks per wave
+  __shared__ float red[4][MAX_R][4][64];      // [wave][row][16-lane row of the wave][column]
+  __shared__ float red_m[4][MAX_R], red_l[4][MAX_R];
+  const int b = blockIdx.x, h = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, pl = lane >> 3, c = lane & 7;
+  const int hoff = h * 64 + 8 * c, s0 = b * sstride, m0 = b * k;
+  const int wp = 8 * wave + pl;                  // this lane's position inside a 32-position block row
+  // ---- requests: prefix K / V (no dependence), the control words, q of every row, the first suffix chunk of every row
+  const f16* kbase = kc + (size_t)s0 * ctx * d + hoff;
+  const f16* vbase = vc + (size_t)s0 * ctx * d + hoff;
+  u32x4 kr[PB], vr[PB];
+#pragma unroll
+  for (int i = 0; i < PB; ++i) { const int p = 32 * i + wp, pc = p < ctx ? p : ctx - 1; kr[i] = *reinterpret_cast<const u32x4*>(kbase + (size_t)pc * d); }
+#pragma unroll
+  for (int i = 0; i < PB; ++i) { const int p = 32 * i + wp, pc = p < ctx ? p : ctx - 1; vr[i] = *reinterpret_cast<const u32x4*>(vbase + (size_t)pc * d); }
+  const int pn = plen[b];
+  int last[MAX_R];                               // last position of row j (pos[m]); rows >= k repeat row k - 1 and are never written
+#pragma unroll
+  for (int j = 0; j < MAX_R; ++j) last[j] = pos[m0 + (j < k ? j : k - 1)];
+  float qv[MAX_R][8];
+#pragma unroll
+  for (int j = 0; j < MAX_R; ++j) {
+    if (j >= k) continue;                        // (uniform: rows beyond the utterance's k cost neither requests nor arithmetic)
+    const float* qp = q + (size_t)(m0 + j) * d + hoff;
+    const float4 q0 = *reinterpret_cast<const float4*>(qp), q1 = *reinterpret_cast<const float4*>(qp + 4);
+    qv[j][0] = q0.x; qv[j][1] = q0.y; qv[j][2] = q0.z; qv[j][3] = q0.w; qv[j][4] = q1.x; qv[j][5] = q1.y; qv[j][6] = q1.z; qv[j][7] = q1.w;
+  }
+  u32x4 ks[MAX_R], vs[MAX_R];
+  int maxlast = 0;
+#pragma unroll
+  for (int j = 0; j < MAX_R; ++j) {
+    if (j >= k) continue;
+    const int p = pn + wp, pc = p < last[j] ? (p > 0 ? p : 0) : last[j];      // (a row without a suffix reads its position pos[m] = plen - 1 of its own slot: inside the cache, masked)
+    const size_t off = ((size_t)(s0 + j) * ctx + pc) * d + hoff;
+    ks[j] = *reinterpret_cast<const u32x4*>(kc + off);
+    vs[j] = *reinterpret_cast<const u32x4*>(vc + off);
+    maxlast = last[j] > maxlast ? last[j] : maxlast;
+  }
+  // ---- prefix: every block's scores of row j, one softmax partial per (wave, row)
+  float m_run[MAX_R], l_run[MAX_R], acc[MAX_R][8];
+#pragma unroll
+  for (int j = 0; j < MAX_R; ++j) {
+    if (j >= k) continue;
+    float sc[PB]; float mx = -INFINITY;
+#pragma unroll
+    for (int i = 0; i < PB; ++i) {
+      const int p = 32 * i + wp;
+      const bool ok = p < pn && p <= last[j];
+      float dot = 0.f;
+      if (ok) {
+        const f16x8 kv = *reinterpret_cast<const f16x8*>(&kr[i]);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) dot = fmaf((float)kv[e], qv[j][e], dot);
+      }
+      dot += dpp_f<0xB1>(dot); dot += dpp_f<0x4E>(dot); dot += dpp_f<0x141>(dot);   // sum over the 8 chunk lanes
+      sc[i] = ok ? dot : -INFINITY;
+      mx = fmaxf(mx, sc[i]);
+    }
+    mx = wave_max(mx);
+    const float ms = mx == -INFINITY ? 0.f : mx;      // (a wave whose share of the prompt is empty: every weight 0, no NaN)
+    float lsum = 0.f;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) acc[j][e] = 0.f;
+#pragma unroll
+    for (int i = 0; i < PB; ++i) {
+      const float pw = __expf(sc[i] - ms);            // 0 for masked positions
+      lsum += pw;
+      if (32 * i + wp < pn && 32 * i + wp <= last[j]) {
+        const f16x8 vv = *reinterpret_cast<const f16x8*>(&vr[i]);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) acc[j][e] = fmaf(pw, (float)vv[e], acc[j][e]);
+      }
+    }
+    m_run[j] = mx; l_run[j] = wave_sum(lsum) * 0.125f;   // every position is replicated on its 8 chunk lanes
+  }
+  // ---- suffix: one chunk of 32 positions of every row per pass (the first one is already on its way; later ones are requested and consumed in the same
+  // pass, not prefetched: requesting chunk c + 1 ahead of consuming chunk c was built - together with the skipped rows it spills to scratch (1160 bytes
+  // per lane), without them it keeps 168 AGPRs of spill moves in the loop; measured instead: profiles/prompt_ab.md, the 128-token rows)
+  int p0 = pn;
+  do {
+    if (p0 > pn) {
+#pragma unroll
+      for (int j = 0; j < MAX_R; ++j) {
+        if (j >= k) continue;
+        const int p = p0 + wp, pc = p < last[j] ? p : last[j];
+        const size_t off = ((size_t)(s0 + j) * ctx + pc) * d + hoff;
+        ks[j] = *reinterpret_cast<const u32x4*>(kc + off);
+        vs[j] = *reinterpret_cast<const u32x4*>(vc + off);
+      }
+    }
+#pragma unroll
+    for (int j = 0; j < MAX_R; ++j) {
+      if (j >= k) continue;
+      const bool ok = p0 + wp <= last[j];
+      float dot = 0.f;
+      if (ok) {
+        const f16x8 kv = *reinterpret_cast<const f16x8*>(&ks[j]);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) dot = fmaf((float)kv[e], qv[j][e], dot);
+      }
+      dot += dpp_f<0xB1>(dot); dot += dpp_f<0x4E>(dot); dot += dpp_f<0x141>(dot);
+      const float sc = ok ? dot : -INFINITY;
+      const float m_new = fmaxf(m_run[j], wave_max(sc));
+      const float ms = m_new == -INFINITY ? 0.f : m_new;
+      const float alpha = __expf(m_run[j] - ms), pw = __expf(sc - ms);
+#pragma unroll
+      for (int e = 0; e < 8; ++e) acc[j][e] *= alpha;
+      if (ok) {
+        const f16x8 vv = *reinterpret_cast<const f16x8*>(&vs[j]);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) acc[j][e] = fmaf(pw, (float)vv[e], acc[j][e]);
+      }
+      l_run[j] = l_run[j] * alpha + wave_sum(pw) * 0.125f;
+      m_run[j] = m_new;
+    }
+    p0 += 32;
+  } while (p0 <= maxlast);
+  // ---- merge: acc over the wave's 8 position slots (xor 8 inside the 16-lane row by DPP, the four rows through LDS), then the four waves' partials
+#pragma unroll
+  for (int j = 0; j < MAX_R; ++j) {
+    if (j >= k) continue;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) acc[j][e] += dpp_f<0x128>(acc[j][e]);     // row_ror:8
+    if (j < k && (lane & 8) == 0) {
+#pragma unroll
+      for (int e = 0; e < 8; ++e) red[wave][j][lane >> 4][8 * c + e] = acc[j][e];
+    }
+    if (j < k && lane == 0) { red_m[wave][j] = m_run[j]; red_l[wave][j] = l_run[j]; }
+  }
+  __syncthreads();
+#pragma unroll
+  for (int j2 = 0; j2 < MAX_R / 4; ++j2) {
+    const int j = wave + 4 * j2;
+    if (j >= k) continue;                // (uniform; no barrier behind this point)
+    const float m0_ = red_m[0][j], m1_ = red_m[1][j], m2_ = red_m[2][j], m3_ = red_m[3][j];
+    const float M_ = fmaxf(fmaxf(m0_, m1_), fmaxf(m2_, m3_));      // finite: position 0 belongs to every row
+    const float w0_ = __expf(m0_ - M_), w1_ = __expf(m1_ - M_), w2_ = __expf(m2_ - M_), w3_ = __expf(m3_ - M_);
+    const float L_ = (red_l[0][j] * w0_ + red_l[1][j] * w1_) + (red_l[2][j] * w2_ + red_l[3][j] * w3_);
+    float ow[4];
+#pragma unroll
+    for (int w = 0; w < 4; ++w) ow[w] = (red[w][j][0][lane] + red[w][j][1][lane]) + (red[w][j][2][lane] + red[w][j][3][lane]);
+    const float o = (ow[0] * w0_ + ow[1] * w1_) + (ow[2] * w2_ + ow[3] * w3_);
+    const int m = m0 + j;
+    out[out_mb ? xf_index(m, h * 64 + lane, out_mb) : (size_t)m * d + h * 64 + lane] = (f16)(o / L_);
+  }
+}
+int launch_dec_self_attn_long(hipStream_t st, const float* q, const f16* kc, const f16* vc, const int* pos, const int* plen, int B, int k, int H, int d, int ctx, int sstride,
+                              f16* out, int out_mb) {
+  if (ctx > 512 || ctx < 64) { set_error("dec_self_attn_long: ctx=%d outside [64, 512]", ctx); return WIS_E_UNSUPPORTED; }
+  if (k < 1 || k > MAX_R || sstride < k || d != H * 64 || !plen) { set_error("dec_self_attn_long: %d rows per utterance (1..%d) in %d slots, d = %d at %d heads", k, MAX_R, sstride, d, H); return WIS_E_ARG; }
+  hipLaunchKernelGGL(dec_self_attn_long_kernel, dim3(B, H), dim3(256), 0, st, q, kc, vc, pos, plen, d, ctx, k, sstride, out, out_mb);
   return WIS_OK;
 }
 
@@ -2652,10 +2823,15 @@ __device__ __forceinline__ void publish_step(const BeamState& bs) {
   __hip_atomic_store(bs.host + HP_REC, rec, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
 }
 
-template <int PSL>
+// The prompt length of a step kernel: a kernel argument (PT = int: the shipped instantiations), or one device word per utterance (PT = const int*: the
+// long-prompt route - one captured step serves every prompt length, as the Philox seeds are read)
+__device__ __forceinline__ int prompt_len(int P, int) { return P; }
+__device__ __forceinline__ int prompt_len(const int* plen, int b) { return plen[b]; }
+
+template <int PSL, class PT>
 __global__ __launch_bounds__(256) void beam_step_kernel(const float* __restrict__ st_max, const float* __restrict__ st_sum,
                                                         const float* __restrict__ st_val, const int* __restrict__ st_idx,
-                                                        BeamState bs, RowMeta rm, int P, int ctx, SampleCfg cfg, unsigned long long* prof, int n_best) {
+                                                        BeamState bs, RowMeta rm, PT P, int ctx, SampleCfg cfg, unsigned long long* prof, int n_best) {
   constexpr int HPT = (MAX_R * 256 + 255) / 256;                    // history tokens per thread (8)
   __shared__ float lse[MAX_R], s_cum[MAX_R];
   __shared__ float cand_v[MAX_CAND]; __shared__ int cand_word[MAX_CAND]; __shared__ int cand_org[MAX_CAND];
@@ -2790,7 +2966,7 @@ __global__ __launch_bounds__(256) void beam_step_kernel(const float* __restrict_
 
   stamp(pf, 5);
   const int hist = step;                 // tokens already in alive[] (sh_alive holds the whole rows)
-  const int npos = P - 1 + step + 1;     // cache positions valid after this step
+  const int npos = prompt_len(P, b) - 1 + step + 1;     // cache positions valid after this step
   // finished hypotheses of this step
   for (int hh = 0; hh < n_newhyp; ++hh) {
     const int kk = hyp_src[hh], org = cand_org[kk], n = hyp_n[hh];
@@ -2862,11 +3038,16 @@ __global__ __launch_bounds__(256) void beam_step_kernel(const float* __restrict_
   stamp(pf, 8);
 }
 int launch_beam_step(hipStream_t st, const float* st_max, const float* st_sum, const float* st_val, const int* st_idx,
-                     const BeamState& bs, const RowMeta& rm, int B, int P, int ctx, const SampleCfg& cfg, unsigned long long* prof, int n_best) {
+                     const BeamState& bs, const RowMeta& rm, int B, int P, int ctx, const SampleCfg& cfg, unsigned long long* prof, int n_best, const int* plen) {
   if (cfg.beam > MAX_R || cfg.n_cand > MAX_CAND || cfg.max_new > 256 || ctx > 512 || cfg.n_vocab > (1 << 20)) { set_error("beam_step: config out of range"); return WIS_E_UNSUPPORTED; }
   if (n_best < 1 || n_best > cfg.beam || B * n_best > HP_MAXB) { set_error("beam_step: %d results per utterance at beam %d", n_best, cfg.beam); return WIS_E_ARG; }
-  if (cfg.beam * STAT_SUB * cfg.n_cand <= 16 * 256) hipLaunchKernelGGL(beam_step_kernel<16>, dim3(B), dim3(256), 0, st, st_max, st_sum, st_val, st_idx, bs, rm, P, ctx, cfg, prof, n_best);
-  else hipLaunchKernelGGL(beam_step_kernel<32>, dim3(B), dim3(256), 0, st, st_max, st_sum, st_val, st_idx, bs, rm, P, ctx, cfg, prof, n_best);
+  const bool small = cfg.beam * STAT_SUB * cfg.n_cand <= 16 * 256;
+  if (plen) {
+    if (small) hipLaunchKernelGGL((beam_step_kernel<16, const int*>), dim3(B), dim3(256), 0, st, st_max, st_sum, st_val, st_idx, bs, rm, plen, ctx, cfg, prof, n_best);
+    else hipLaunchKernelGGL((beam_step_kernel<32, const int*>), dim3(B), dim3(256), 0, st, st_max, st_sum, st_val, st_idx, bs, rm, plen, ctx, cfg, prof, n_best);
+  }
+  else if (small) hipLaunchKernelGGL((beam_step_kernel<16, int>), dim3(B), dim3(256), 0, st, st_max, st_sum, st_val, st_idx, bs, rm, P, ctx, cfg, prof, n_best);
+  else hipLaunchKernelGGL((beam_step_kernel<32, int>), dim3(B), dim3(256), 0, st, st_max, st_sum, st_val, st_idx, bs, rm, P, ctx, cfg, prof, n_best);
   return WIS_OK;
 }
 
@@ -2881,10 +3062,10 @@ int launch_beam_step(hipStream_t st, const float* st_max, const float* st_sum, c
 // (bs.out_len / out_score; its tokens are alive[row][0 .. len)) and raises its own done flag - from then on the row is fed EOT, and EOT is what
 // its history collects (the processors of a later step read valid ids there).  All n rows done: the results go to the host block (result j at
 // row b n + j), bs.done[b] = 1.  Every path ends in publish_step, as beam_step_kernel's do.
-template <bool TOPK>
+template <bool TOPK, class PT>
 __global__ __launch_bounds__(256) void sample_step_kernel(const float* __restrict__ st_max, const float* __restrict__ st_sum,
                                                           const float* __restrict__ st_val, const int* __restrict__ st_idx,
-                                                          BeamState bs, RowMeta rm, int P, SampleCfg cfg, SampleP sp) {
+                                                          BeamState bs, RowMeta rm, PT P, SampleCfg cfg, SampleP sp) {
   __shared__ int s_tok[MAX_R]; __shared__ float s_sc[MAX_R]; __shared__ int s_len[MAX_R]; __shared__ int s_ndone;
   const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int n = cfg.beam, NC = cfg.n_cand, V = cfg.n_vocab, r0 = b * n;
@@ -2948,7 +3129,7 @@ __global__ __launch_bounds__(256) void sample_step_kernel(const float* __restric
   }
   __syncthreads();
   const bool is_last = step + 1 >= cfg.max_new;
-  const int npos = P - 1 + step + 1;           // cache positions valid after this step
+  const int npos = prompt_len(P, b) - 1 + step + 1;           // cache positions valid after this step
   if (tid < n) {
     const int row = r0 + tid;
     int rd = bs.row_done[row];
@@ -2994,12 +3175,16 @@ __global__ __launch_bounds__(256) void sample_step_kernel(const float* __restric
   if (tid == 0) publish_step(bs);
 }
 int launch_sample_step(hipStream_t st, const float* st_max, const float* st_sum, const float* st_val, const int* st_idx,
-                       const BeamState& bs, const RowMeta& rm, int B, int P, const SampleCfg& cfg, const SampleP& sp) {
+                       const BeamState& bs, const RowMeta& rm, int B, int P, const SampleCfg& cfg, const SampleP& sp, const int* plen) {
   const bool whole = sp.topk < 0;
   if (cfg.beam < 1 || cfg.beam > MAX_R || B * cfg.beam > HP_MAXB || cfg.max_new > 256 || cfg.n_vocab > (1 << 20) || !sp.seeds || !(sp.T > 0.f) ||
       (whole ? cfg.n_cand != 2 : (sp.topk < 2 || sp.topk > MAX_CAND || cfg.n_cand != sp.topk))) { set_error("sample_step: config out of range"); return WIS_E_UNSUPPORTED; }
-  if (whole) hipLaunchKernelGGL(sample_step_kernel<false>, dim3(B), dim3(256), 0, st, st_max, st_sum, st_val, st_idx, bs, rm, P, cfg, sp);
-  else hipLaunchKernelGGL(sample_step_kernel<true>, dim3(B), dim3(256), 0, st, st_max, st_sum, st_val, st_idx, bs, rm, P, cfg, sp);
+  if (plen) {
+    if (whole) hipLaunchKernelGGL((sample_step_kernel<false, const int*>), dim3(B), dim3(256), 0, st, st_max, st_sum, st_val, st_idx, bs, rm, plen, cfg, sp);
+    else hipLaunchKernelGGL((sample_step_kernel<true, const int*>), dim3(B), dim3(256), 0, st, st_max, st_sum, st_val, st_idx, bs, rm, plen, cfg, sp);
+  }
+  else if (whole) hipLaunchKernelGGL((sample_step_kernel<false, int>), dim3(B), dim3(256), 0, st, st_max, st_sum, st_val, st_idx, bs, rm, P, cfg, sp);
+  else hipLaunchKernelGGL((sample_step_kernel<true, int>), dim3(B), dim3(256), 0, st, st_max, st_sum, st_val, st_idx, bs, rm, P, cfg, sp);
   return WIS_OK;
 }
 
@@ -3097,14 +3282,18 @@ int launch_kv_gather(hipStream_t st, f16* kc, f16* vc, size_t layer_stride, int 
 // stores - reads and writes of an address meet only inside one thread, so the permutation is safe in place.  Moving
 // beam x positions x d bytes per step (16 MB at position 20, large-v2) buys the self-attention kernel a K/V address that
 // depends on nothing it has to load: one fabric round trip per layer instead of two.
+// FROM (the long-prompt route, launch_kv_reorder_from): P is a device word per utterance, and only positions [P, P - 1 + step) move - the prompt's positions
+// stay in the utterance's first slot (dec_self_attn_long_kernel reads them there), never copied, never reordered
+template <bool FROM, class PT>
 __global__ __launch_bounds__(256) void kv_reorder_kernel(f16* __restrict__ kc, f16* __restrict__ vc, size_t lstride, const int* __restrict__ parent,
-                                                         const int* __restrict__ step_u, const int* __restrict__ done, int k, int P, int ctx, int d) {
+                                                         const int* __restrict__ step_u, const int* __restrict__ done, int k, PT P, int ctx, int d) {
   const int b = blockIdx.z, lk = blockIdx.y, tid = threadIdx.x;
   if (k < 2) return;
   const int r0 = b * k;
   // the three control words are requested together (a `done` test in front of the `parent` loads in front of the `step` load is
   // three dependent round trips before the first cache row moves)
   const int dn = done[b], st = step_u[b];
+  const int Pb = prompt_len(P, b);
   int par[MAX_R];
 #pragma unroll
   for (int j = 0; j < MAX_R; ++j) par[j] = parent[r0 + (j < k ? j : 0)];
@@ -3112,10 +3301,10 @@ __global__ __launch_bounds__(256) void kv_reorder_kernel(f16* __restrict__ kc, f
 #pragma unroll
   for (int j = 0; j < MAX_R; ++j) { if (j < k) ident = ident & (par[j] == r0 + j); else par[j] = r0 + j; }
   if (dn | (int)ident) return;
-  const int npos = P - 1 + st;                  // beam_step already counted this step: positions 0 .. npos-1 hold history
+  const int npos = Pb - 1 + st;                 // beam_step already counted this step: positions 0 .. npos-1 hold history
   f16* cache = ((lk & 1) ? vc : kc) + (size_t)(lk >> 1) * lstride;
   const int c8 = d >> 3;
-  for (int p = blockIdx.x; p < npos; p += gridDim.x) {
+  for (int p = (FROM ? Pb : 0) + blockIdx.x; p < npos; p += gridDim.x) {
     for (int ch = tid; ch < c8; ch += 256) {
       u32x4 v[MAX_R];
 #pragma unroll
@@ -3129,7 +3318,13 @@ __global__ __launch_bounds__(256) void kv_reorder_kernel(f16* __restrict__ kc, f
 int launch_kv_reorder(hipStream_t st, f16* kc, f16* vc, size_t layer_stride, int L, const BeamState& bs, int B, int beam, int P, int ctx, int d) {
   if (beam < 2) return WIS_OK;        // greedy: a row always continues itself
   if (beam > MAX_R) { set_error("kv_reorder: beam %d > %d", beam, MAX_R); return WIS_E_UNSUPPORTED; }
-  hipLaunchKernelGGL(kv_reorder_kernel, dim3(8, 2 * L, B), dim3(256), 0, st, kc, vc, layer_stride, bs.parent, bs.step_u, bs.done, beam, P, ctx, d);
+  hipLaunchKernelGGL((kv_reorder_kernel<false, int>), dim3(8, 2 * L, B), dim3(256), 0, st, kc, vc, layer_stride, bs.parent, bs.step_u, bs.done, beam, P, ctx, d);
+  return WIS_OK;
+}
+int launch_kv_reorder_from(hipStream_t st, f16* kc, f16* vc, size_t layer_stride, int L, const BeamState& bs, int B, int beam, const int* plen, int ctx, int d) {
+  if (beam < 2) return WIS_OK;
+  if (beam > MAX_R || !plen) { set_error("kv_reorder_from: beam %d > %d, or no prompt lengths", beam, MAX_R); return WIS_E_UNSUPPORTED; }
+  hipLaunchKernelGGL((kv_reorder_kernel<true, const int*>), dim3(8, 2 * L, B), dim3(256), 0, st, kc, vc, layer_stride, bs.parent, bs.step_u, bs.done, beam, plen, ctx, d);
   return WIS_OK;
 }
 

@@ -5,7 +5,7 @@
 //   make_gen_ctx      every argument check, the resolved shape and sampling options of the call
 //   stage_search      search counters, prompt rows, progress block: staged before anything the encoder produces
 //   front_half        log-mel, encoder, cross-K/V (on a stream of its own while the handle is alone on the GPU)
-//   seed_*            three ways to "the search stands after `steps` passes": merged prefill, greedy draft, beam-draft windows
+//   seed_*            four ways to "the search stands after `steps` passes": merged prefill, windowed prefill of a long prompt, greedy draft, beam-draft windows
 //   StepGraph         the decode step as a cached HIP graph (three self-attention lengths)
 //   run_burst / run_paced      the two step loops
 //   results_*         three forms of result read-back, then the timing record
@@ -37,7 +37,10 @@ struct SampleCtx {
   SampleP sp;                    // random sampling (topk 0: off): sample_step_kernel stands in beam_step_kernel's place, `beam` counts the utterance's samples
   int n_res = 1;                 // results per utterance (num_hypotheses)
   bool sampling() const { return sp.topk != 0; }
+  const int* plen = nullptr;     // the long-prompt route (P > SHORT_PROMPT): the step kernels read the prompt length from this device word per utterance, P stays out of the step graph
 };
+// prompts up to here take the merged prefill + first step in one pass and keep P as a kernel argument of the step; longer ones the long-prompt route (seed_prefill_long)
+constexpr int SHORT_PROMPT = 16;
 // sampling_topk / sampling_temperature / num_hypotheses of a call, resolved (0 in the C struct: off / 1 / 1) - or refused.  *rows = decoder rows per
 // utterance: the beams of a search, the samples of a sampled decode.  single: an entry point whose outputs hold one hypothesis per utterance
 static int resolve_sample_opts(const wis_gen_opts_t* o, bool single, bool drafted, SampleCtx* g, int* rows) {
@@ -81,6 +84,8 @@ struct GenCtx : SampleCtx {
   std::chrono::steady_clock::time_point t0;      // total_ms counts from here: the shape is resolved, nothing is enqueued yet
   int sot_row;                   // no_speech_prob: the prompt row that reads <|startoftranscript|> (the same in every utterance of the batch); -1: not asked
   bool drafting, beam_draft;
+  bool long_p;                   // the long-prompt route
+  int Pl;                        // ... its last window: the prompt rows P - Pl .. P - 1 run as the merged prefill + first step
 };
 
 // draft / n_draft: wis_generate_draft (one utterance, beam 1): the tokens of an earlier hypothesis to verify first
@@ -98,7 +103,12 @@ static int make_gen_ctx(wis_model* m, const float* input, int B, const int32_t* 
   const int beam = g.beam = rows;
   WIS_RET(check_batch(m, B, beam));
   if (!g.sampling()) WIS_RET(check_patience(beam, o->patience));
-  if (P < 1 || P > 16 || B * P > MAX_ROWS) { set_error("prompt length %d unsupported (1..16, B*P <= %d)", P, MAX_ROWS); return WIS_E_UNSUPPORTED; }
+  const int max_prompt = std::min(c.n_text_ctx / 2 + 4, SA_LONG_MAX_PLEN);      // openai-whisper's n_ctx / 2 - 1 prompt tokens behind <|startofprev|>, the start sequence; the step's self-attention covers a prefix of SA_LONG_MAX_PLEN positions
+  if (P < 1 || P > max_prompt) { set_error("prompt length %d unsupported (1..%d)", P, max_prompt); return WIS_E_UNSUPPORTED; }
+  if (P <= SHORT_PROMPT && B * P > MAX_ROWS) { set_error("prompt length %d unsupported (1..16, B*P <= %d)", P, MAX_ROWS); return WIS_E_UNSUPPORTED; }
+  if (P > SHORT_PROMPT && draft != nullptr) { set_error("prompts of more than %d tokens: not available for drafted decodes (wis_generate_draft / wis_generate_draft_beam)", SHORT_PROMPT); return WIS_E_UNSUPPORTED; }
+  g.long_p = P > SHORT_PROMPT; g.Pl = std::min(16, MAX_ROWS / B);
+  g.plen = g.long_p ? m->d_plen : nullptr;
   int max_new = o->max_new_tokens > 0 ? o->max_new_tokens : std::min(c.n_text_ctx / 2, c.n_text_ctx - P);
   if (max_new > MAX_STEPS) max_new = MAX_STEPS;
   if (P - 1 + max_new > c.n_text_ctx) max_new = c.n_text_ctx - (P - 1);
@@ -138,6 +148,16 @@ static int stage_search(const GenCtx& g) {
   WIS_RET(init_beam_state(m, B, beam, g.sampling(), g.sampling() ? beam : g.n_res));
   if (g.sampling()) WIS_RET(upload_seeds(m, g.seeds, B));
   m->last_B = B; m->last_beam = beam;
+  if (g.long_p) {      // (its prompt rows go up window by window: seed_prefill_long)
+    int* hp = m->h_pin->plen;
+    for (int b = 0; b < B; ++b) hp[b] = P;
+    WIS_HIP_CHECK(hipMemcpyAsync(m->d_plen, hp, (size_t)B * 4, hipMemcpyHostToDevice, g.st));
+    if (!sa_long_kernel(m)) {      // the TREE form's tables: row r = b beam + j owns slot r, its utterance's prefix lies in slot b beam
+      int* ht = m->h_pin->sa_tab;
+      for (int r = 0; r < B * beam; ++r) { ht[r] = r; ht[MAX_ROWS + r] = r / beam * beam; }
+      WIS_HIP_CHECK(hipMemcpyAsync(m->d_sa_tab, ht, sizeof(m->h_pin->sa_tab), hipMemcpyHostToDevice, g.st));
+    }
+  } else
   if (!g.drafting || g.beam_draft) {
     std::vector<int> tok(B * P), pos(B * P), slot(B * P), ls(B * P);
     for (int b = 0; b < B; ++b) for (int i = 0; i < P; ++i) { tok[b * P + i] = g.prompt[b * P + i]; pos[b * P + i] = i; slot[b * P + i] = b * beam; ls[b * P + i] = b * beam; }
@@ -194,12 +214,13 @@ static int sampling_tail(const SampleCtx& g, LogitRows rows, int flags) {
   if (g.sampling()) {      // statistics (whole vocabulary: perturbed) -> sample step; every row continues itself: the cache moves only behind the prompt pass
     WIS_RET(launch_logit_stats(st, m->logits, g.bias_all, m->bias_begin, m->bs.step_u, m->st_max, m->st_sum, m->st_val, m->st_idx, g.B, g.sc, lr_b, lr_j, lr_off, nullptr,
                                nullptr, g.ts ? m->ts_desc : nullptr, &g.sp));
-    WIS_RET(launch_sample_step(st, m->st_max, m->st_sum, m->st_val, m->st_idx, m->bs, m->rm, g.B, g.P, g.sc, g.sp));
+    WIS_RET(launch_sample_step(st, m->st_max, m->st_sum, m->st_val, m->st_idx, m->bs, m->rm, g.B, g.P, g.sc, g.sp, g.plen));
   } else {
   WIS_RET(launch_logit_stats(st, m->logits, g.bias_all, m->bias_begin, m->bs.step_u, m->st_max, m->st_sum, m->st_val, m->st_idx, g.B, g.sc, lr_b, lr_j, lr_off, prof ? prof + 16 : nullptr,
                              nullptr, g.ts ? m->ts_desc : nullptr));
-  WIS_RET(launch_beam_step(st, m->st_max, m->st_sum, m->st_val, m->st_idx, m->bs, m->rm, g.B, g.P, c.n_text_ctx, g.sc, prof, g.n_res));
+  WIS_RET(launch_beam_step(st, m->st_max, m->st_sum, m->st_val, m->st_idx, m->bs, m->rm, g.B, g.P, c.n_text_ctx, g.sc, prof, g.n_res, g.plen));
   }
+  if (!(flags & TAIL_NO_CACHE) && g.plen) return launch_kv_reorder_from(st, m->kc_all, m->vc_all, m->kv_layer_stride, c.n_dec_layers, m->bs, g.B, g.beam, g.plen, c.n_text_ctx, c.d_model);
   if (!(flags & TAIL_NO_CACHE)) WIS_RET(launch_kv_reorder(st, m->kc_all, m->vc_all, m->kv_layer_stride, c.n_dec_layers, m->bs, g.B, g.beam, g.P, c.n_text_ctx, c.d_model));
   return WIS_OK;
 }
@@ -243,6 +264,47 @@ static int seed_prefill(const GenCtx& g) {
   // every prompt row has its logits after this pass: the <|startoftranscript|> row's are what no_speech_prob reads (raw, no processors)
   if (g.sot_row >= 0) WIS_RET(launch_no_speech(g.st, m->logits, m->n_vocab_pad, B, P, g.sot_row, c.n_vocab, c.no_speech, m->d_nsp));
   return sampling_tail(g, {P, 0, P - 1}, TAIL_TAPS);
+}
+
+// ---- the long-prompt route (P > SHORT_PROMPT): WINDOWED prefill.  Prompt positions 0 .. P - Pl - 1 are teacher-forced without logits in passes of 16
+// consecutive positions per utterance over groups of at most MAX_ROWS / 16 utterances - the un-folded batched-row route wis_align forces its text through,
+// with the self-attention in the TREE row-group form (every row's history in ONE slot: an ancestor table of width 1 that names the utterance's first slot
+// b * beam, where the rows' K / V go) - and the last Pl = min(16, MAX_ROWS / B) prompt rows run as the merged prefill + first step of seed_prefill, at
+// positions P - Pl .. P - 1: that pass has logits, the sampling tail reads its last row.  no_speech_prob reads the <|startoftranscript|> row: the window
+// that holds it runs with logits too.  The prompt's K / V stays in slot b * beam for the whole search: the step's self-attention reads it there for all of
+// the utterance's rows (dec_self_attn_long_kernel), a decode row keeps only the positions from P on in its own slot, and the cache reorder moves only those -
+// behind this pass there is nothing to move.
+static int seed_prefill_long(const GenCtx& g) {
+  wis_model* m = g.m; hipStream_t st = g.st; const wis_config_t& c = m->cfg; PinnedScratch* hp = m->h_pin;
+  const int B = g.B, P = g.P, beam = g.beam, Pl = g.Pl, Np = P - Pl, G = MAX_ROWS / 16;
+  for (int ub0 = 0; ub0 < B; ub0 += G) {
+    const int nb = std::min(G, B - ub0), M = nb * 16;
+    for (int r = 0; r < M; ++r) hp->base[r] = hp->anc[r] = (ub0 + r / 16) * beam;
+    WIS_HIP_CHECK(hipMemcpyAsync(m->d_anc, hp->anc, (size_t)M * 4, hipMemcpyHostToDevice, st));
+    WIS_HIP_CHECK(hipMemcpyAsync(m->d_base, hp->base, (size_t)M * 4, hipMemcpyHostToDevice, st));
+    for (int t0 = 0; t0 < Np; t0 += 16) {
+      const int n = std::min(16, Np - t0);      // (a short last window is padded with copies of its last row: the same K / V to the same place)
+      std::vector<int> tok(M), pos(M), slot(M), ls(M);
+      for (int r = 0; r < M; ++r) {
+        const int u = ub0 + r / 16, i = std::min(r % 16, n - 1);
+        tok[r] = g.prompt[u * P + t0 + i]; pos[r] = t0 + i; slot[r] = ls[r] = u * beam;
+      }
+      WIS_RET(upload_rows(m, tok, pos, slot, ls));      // (waits: the staging areas are free for the next window)
+      const bool nsp = g.sot_row >= t0 && g.sot_row < t0 + n;
+      TreeWin tw{m->d_anc, t0, 1}; tw.base = m->d_base; tw.own_kv = true;
+      m->al.kv_ub0 = ub0;
+      const int rc = dec_forward(m, M, 16, nb, nsp, 1, 0, &tw);
+      m->al.kv_ub0 = 0;
+      WIS_RET(rc);
+      if (nsp) WIS_RET(launch_no_speech(st, m->logits, m->n_vocab_pad, nb, 16, g.sot_row - t0, c.n_vocab, c.no_speech, m->d_nsp + ub0));
+    }
+  }
+  std::vector<int> tok(B * Pl), pos(B * Pl), slot(B * Pl), ls(B * Pl);
+  for (int b = 0; b < B; ++b) for (int i = 0; i < Pl; ++i) { tok[b * Pl + i] = g.prompt[b * P + Np + i]; pos[b * Pl + i] = Np + i; slot[b * Pl + i] = ls[b * Pl + i] = b * beam; }
+  WIS_RET(upload_rows(m, tok, pos, slot, ls, false));
+  WIS_RET(dec_forward(m, B * Pl, Pl, B, true, beam, 0));
+  if (g.sot_row >= Np) WIS_RET(launch_no_speech(st, m->logits, m->n_vocab_pad, B, Pl, g.sot_row - Np, c.n_vocab, c.no_speech, m->d_nsp));
+  return sampling_tail(g, {Pl, 0, Pl - 1}, TAIL_TAPS | TAIL_NO_CACHE);
 }
 
 // The decoder rows of window steps s0 .. s0 + Rw - 1 of a beam trajectory (hd: [step][MAX_R][2] = token, origin; one utterance, k beams), step-major:
@@ -443,16 +505,19 @@ struct StepGraph {
   int nb_for(int passes_done) const {
     static const bool sa_short = !(getenv("WIS_SA_NB") && atoi(getenv("WIS_SA_NB")) == 0);
     const int len = g.P + passes_done;
-    return !sa_short ? 8 : (len <= 16 ? 2 : (len <= 32 ? 4 : 8));
+    return (!sa_short || g.long_p) ? 8 : (len <= 16 ? 2 : (len <= 32 ? 4 : 8));
   }
   int one_step() const {
-    WIS_RET(dec_forward(g.m, g.B * g.beam, g.beam, g.B, true, g.beam, 1));
+    g.m->sa_plen = g.plen; g.m->sa_w0 = g.P;      // (the long-prompt route: the pass's self-attention over the shared prefix)
+    const int rc = dec_forward(g.m, g.B * g.beam, g.beam, g.B, true, g.beam, 1);
+    g.m->sa_plen = nullptr;
+    WIS_RET(rc);
     return sampling_tail(g, {g.beam, 1, 0}, TAIL_TAPS | (g.sampling() ? TAIL_NO_CACHE : 0));      // (a sample's row continues itself: nothing to reorder after the first step)
   }
   int graph_for(int nb, hipGraphExec_t* out) const {
     wis_model* m = g.m; const SampleCfg& sc = g.sc;
     GraphKey key; memset(&key, 0, sizeof(key));
-    key.B = g.B; key.beam = g.beam; key.P = g.P; key.max_new = g.max_new; key.fixed_new = sc.fixed_new; key.suppress_blank = sc.suppress_blank;
+    key.B = g.B; key.beam = g.beam; key.P = (g.long_p && sa_long_kernel(m)) ? -1 : g.P /* one sentinel for the whole long-prompt route (its TREE form keeps w0 = P as a kernel argument) */; key.max_new = g.max_new; key.fixed_new = sc.fixed_new; key.suppress_blank = sc.suppress_blank;
     key.suppress_default = g.o->suppress_default; key.early_exit = sc.allow_early_exit; key.lp = sc.length_penalty; key.patience = g.patience; key.spin = m->spin_now ? 1 : 0;
     key.sa_nb = nb;
     key.timestamps = g.ts ? 1 : 0; key.max_init = g.ts ? g.ts_max_init : 0;
@@ -655,7 +720,8 @@ static int generate_impl(wis_model_t* m, const float* input, int B, const int32_
   WIS_RET(front_half(g));
 
   Seed sd;
-  if (!g.drafting) WIS_RET(seed_prefill(g));
+  if (g.long_p) WIS_RET(seed_prefill_long(g));
+  else if (!g.drafting) WIS_RET(seed_prefill(g));
   else {
     TicketScope ticket(m);
     WIS_RET(g.beam_draft ? seed_beam_draft(g, &sd) : seed_greedy_draft(g, &sd));

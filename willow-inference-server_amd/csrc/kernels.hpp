@@ -130,8 +130,15 @@ struct SelfAttnP {
   unsigned long long* prof = nullptr; int out_mb = 0; const int* anc = nullptr; int w0 = 0, aw = 0;
   const int* base = nullptr;      // (optional): slot of the positions before w0, per row
   int nb = 8;                     // 8-position blocks per pass (2 / 4 / 8; plain form only)
+  const int* plen = nullptr;      // (optional; the long-prompt route's decode step): device word per utterance - the length of the prompt prefix its rpu rows share in slot
+                                  // (m / rpu) * sstride; the pass runs dec_self_attn_long_kernel (one workgroup per (utterance, head)) in the plain kernel's place
 };
 int launch_dec_self_attn(hipStream_t st, const SelfAttnP& p);
+// The decode step's self-attention behind a long prompt (dec_kernels.hip dec_self_attn_long_kernel): utterance b's k <= MAX_R rows (m = b k + j) read positions
+// < plen[b] from slot b * sstride - once for all k rows - and positions plen[b] .. pos[m] from their own slot b * sstride + j.  plen[b] in [1, SA_LONG_MAX_PLEN]
+constexpr int SA_LONG_MAX_PLEN = 256;
+int launch_dec_self_attn_long(hipStream_t st, const float* q, const f16* kc, const f16* vc, const int* pos, const int* plen, int B, int k, int H, int d, int ctx, int sstride,
+                              f16* out, int out_mb);
 // cross attention of R rows per utterance over the utterance's T encoder keys.
 //   q f32 [B*R][d] (pre-scaled), kx f16 [B][H][8][T][8], vt f16 [B][H][64][Tpad] (zero padded) -> out f16 [B*R][d]
 // gran / epoch (optional): the granule hand-off of small grids (dec_kernels.hip, SPIN): gran = 8-byte slots [B*H][6][8][66], epoch =
@@ -225,13 +232,19 @@ __host__ __device__ inline float* hp_out_score(unsigned long long* hp) { return 
 __host__ __device__ inline int* hp_out_ids(unsigned long long* hp) { return reinterpret_cast<int*>(hp + HP_WORDS) + 2 * HP_MAXB; }
 // after a beam step: every live beam's KV rows (all layers, positions < P - 1 + step) become a copy of its parent's
 int launch_kv_reorder(hipStream_t st, f16* kc, f16* vc, size_t layer_stride, int L, const BeamState& bs, int B, int beam, int P, int ctx, int d);
+// ... behind a long prompt: the prompt's positions [0, plen[b]) stay in the utterance's first slot for the whole search and are never moved - only positions
+// [plen[b], plen[b] - 1 + step) of every live beam become a copy of its parent's.  plen: device word per utterance
+int launch_kv_reorder_from(hipStream_t st, f16* kc, f16* vc, size_t layer_stride, int L, const BeamState& bs, int B, int beam, const int* plen, int ctx, int d);
+// plen (launch_beam_step, launch_sample_step; the long-prompt route): the prompt length comes from this device word per utterance, P is ignored - a second
+// instantiation of the kernel, so that one captured step serves every prompt length
 int launch_beam_step(hipStream_t st, const float* st_max, const float* st_sum, const float* st_val, const int* st_idx,
                      const BeamState& bs, const RowMeta& rm, int B, int P, int ctx, const SampleCfg& cfg, unsigned long long* prof = nullptr,
-                     int n_best = 1);      // results per utterance: the n_best best finished hypotheses at b n_best + i (bs.out_*, the host block)
+                     int n_best = 1,       // results per utterance: the n_best best finished hypotheses at b n_best + i (bs.out_*, the host block)
+                     const int* plen = nullptr);
 // the sampled decode's step (dec_kernels.hip sample_step_kernel), in beam_step's place: per sample row the Gumbel-max draw from what
 // launch_logit_stats left, score, history, per-row done flag; the utterance ends when all its rows have (or at max_new)
 int launch_sample_step(hipStream_t st, const float* st_max, const float* st_sum, const float* st_val, const int* st_idx,
-                       const BeamState& bs, const RowMeta& rm, int B, int P, const SampleCfg& cfg, const SampleP& sp);
+                       const BeamState& bs, const RowMeta& rm, int B, int P, const SampleCfg& cfg, const SampleP& sp, const int* plen = nullptr);
 // draft verification at beam > 1 (one utterance; dec_kernels.hip draft_match_kernel / kv_gather_kernel): behind a replayed beam step, match the live set
 // it produced with the draft's entry for the step AS A SET (draft = [n_draft][MAX_R][2] in BeamState::traj's layout); vstate ints: 0 steps verified,
 // 2 window steps applied, 8.. the draft node each live beam is matched to (logit_stats rowmap), 16.. / 32.. the slots holding each beam's history

@@ -497,7 +497,7 @@ static int alloc_buffers(wis_model* m) {
   WIS_RET(dalloc(m, &m->bs.cum, slots));
   WIS_RET(dalloc(m, &m->bs.alive, (size_t)slots * max_new));
   WIS_RET(dalloc(m, &m->bs.parent, (size_t)slots));
-  WIS_RET(dalloc(m, &m->bs.row_done, (size_t)slots)); WIS_RET(dalloc(m, &m->d_seeds, (size_t)MAX_ROWS));
+  WIS_RET(dalloc(m, &m->bs.row_done, (size_t)slots)); WIS_RET(dalloc(m, &m->d_seeds, (size_t)MAX_ROWS)); WIS_RET(dalloc(m, &m->d_plen, (size_t)MAX_ROWS)); WIS_RET(dalloc(m, &m->d_sa_tab, (size_t)2 * MAX_ROWS));
   WIS_RET(dalloc(m, &m->bs.hyp_score, (size_t)Bm * max_hyp)); WIS_RET(dalloc(m, &m->bs.hyp_len, (size_t)Bm * max_hyp));
   WIS_RET(dalloc(m, &m->bs.hyp_tok, (size_t)Bm * max_hyp * max_new));
   WIS_RET(dalloc(m, &m->bs.all_done, 4));
@@ -730,6 +730,18 @@ GemvP frag_ln_gelu_xf(const DecProj& p, const f16* xf, const float* stat_in, f16
   g.stat_in = stat_in; g.y = y_xf; g.ymb = g.xmb;
   return g;
 }
+// WIS_SA_LONG=0: A/B switch and fallback of the long-prompt route's step self-attention
+bool sa_long_kernel(const wis_model* m) {
+  static const bool sa_long_on = !(getenv("WIS_SA_LONG") && atoi(getenv("WIS_SA_LONG")) == 0);
+  return m->sa_long_form >= 0 ? m->sa_long_form != 0 : sa_long_on;
+}
+// the decode step of the long-prompt route (wis_model::sa_plen set around it): the rows read their utterance's prompt prefix in its first slot - through
+// dec_self_attn_long_kernel, or as a TREE of width 1 (base = the utterance's first slot, the one ancestor = the row's own slot, w0 = the prompt length)
+static void sa_shared_prefix(const wis_model* m, SelfAttnP* sa) {
+  if (!m->sa_plen) return;
+  if (sa_long_kernel(m)) { sa->plen = m->sa_plen; return; }
+  sa->anc = m->d_sa_tab; sa->base = m->d_sa_tab + MAX_ROWS; sa->w0 = m->sa_w0; sa->aw = 1;
+}
 static int dec_forward_frag(wis_model* m, int M, int R, int B, bool want_logits, int sstride, int rmul, int chunks, const TreeWin* tw = nullptr) {
   const wis_config_t& c = m->cfg; hipStream_t st = m->st;
   const int d = c.d_model, H = c.n_heads, T = c.n_audio_ctx, ctx = c.n_text_ctx, MB = cdiv(M, 16);
@@ -742,6 +754,7 @@ static int dec_forward_frag(wis_model* m, int M, int R, int B, bool want_logits,
   // what every layer's attention launches share; the layer adds its caches / K, V images (and its stamp row)
   SelfAttnP sa;
   sa.q = m->dq; sa.pos = m->rm.pos; sa.out = m->daoxf; sa.M = M; sa.H = H; sa.d = d; sa.ctx = ctx; sa.rpu = R; sa.sstride = sstride; sa.rmul = rmul; sa.out_mb = MB; sa.nb = m->sa_nb;
+  if (!tw) sa_shared_prefix(m, &sa);
   if (tw) { sa.anc = tw->anc; sa.w0 = tw->w0; sa.aw = tw->aw; sa.base = tw->base; }
   CrossAttnP ca;
   ca.q = m->dq; ca.out = m->daoxf; ca.part = m->part; ca.counters = m->counters; ca.B = B; ca.R = R; ca.H = H; ca.d = d; ca.T = T; ca.Tpad = m->Tpad; ca.chunks = chunks; ca.out_mb = MB;
@@ -775,7 +788,7 @@ static int dec_forward_frag(wis_model* m, int M, int R, int B, bool want_logits,
     // (wis_align decodes a batch in groups of utterances: the group's first utterance picks the K / V block the rows' b = 0 reads; 0 otherwise)
     const size_t ku = (size_t)m->al.kv_ub0 * H * T * 64, vu = (size_t)m->al.kv_ub0 * H * 64 * m->Tpad;
     CrossAttnP cp = ca;
-    cp.kx = m->kx[l] + ku; cp.vt = m->vx[l] + vu; cp.gran = (m->spin_now && !tw) ? m->ca_gran : nullptr; cp.kv_shared = tw ? 1 : 0;
+    cp.kx = m->kx[l] + ku; cp.vt = m->vx[l] + vu; cp.gran = (m->spin_now && !tw) ? m->ca_gran : nullptr; cp.kv_shared = (tw && !tw->own_kv) ? 1 : 0;
     WIS_RET(launch_dec_cross_attn(st, cp));
     if (m->al.capture) WIS_RET(align_capture_q(m, l, M));      // wis_align: m->dq holds this layer's finished cross-Q until the next layer's QKV projection
     }
@@ -829,6 +842,7 @@ int dec_forward(wis_model* m, int M, int R, int B, bool want_logits, int sstride
   WIS_RET(launch_dec_embed(st, m->emb, m->dec_pos, m->rm.tok, m->rm.pos, m->dx, M, d, fold ? m->dxh : nullptr));
   SelfAttnP sa;
   sa.q = m->dq; sa.pos = m->rm.pos; sa.out = m->dao; sa.M = M; sa.H = H; sa.d = d; sa.ctx = ctx; sa.rpu = R; sa.sstride = sstride; sa.rmul = rmul; sa.nb = m->sa_nb;
+  sa_shared_prefix(m, &sa);
   CrossAttnP ca;
   ca.q = m->dq; ca.out = m->dao; ca.part = m->part; ca.counters = m->counters; ca.B = B; ca.R = R; ca.H = H; ca.d = d; ca.T = T; ca.Tpad = m->Tpad; ca.chunks = chunks;
   ca.gran = m->spin_now ? m->ca_gran : nullptr; ca.epoch = m->ca_epoch;
@@ -1111,6 +1125,18 @@ int wis_last_trajectory(wis_model_t* m, int b, int32_t* tok, int32_t* org, int c
   return WIS_OK;
 }
 
+int wis_debug_sa_long(wis_model_t* m, int form) {
+  if (!m || form < -1 || form > 1) { set_error("wis_debug_sa_long: bad argument"); return WIS_E_ARG; }
+  WIS_ENTER(m, "wis_debug_sa_long")
+  m->sa_long_form = form;
+  return WIS_OK;
+}
+int wis_debug_graph_count(wis_model_t* m, int* count) {
+  if (!m || !count) { set_error("wis_debug_graph_count: bad argument"); return WIS_E_ARG; }
+  WIS_ENTER(m, "wis_debug_graph_count")
+  *count = (int)m->graphs.size();
+  return WIS_OK;
+}
 int wis_debug_handoff(wis_model_t* m, int raise_flag, int* retries, int* spin_disabled) {
   if (!m) { set_error("wis_debug_handoff: bad argument"); return WIS_E_ARG; }
   WIS_ENTER(m, "wis_debug_handoff")

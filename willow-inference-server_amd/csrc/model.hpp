@@ -66,7 +66,7 @@ struct AlignState {
   float *W = nullptr, *acc = nullptr;     // one chunk of heads' probabilities; the matrix [max_batch][tokens][n_audio_ctx]
   unsigned* trace = nullptr; int *rev = nullptr, *path = nullptr, *d_meta = nullptr; float* probs = nullptr;
   int cap_ub0 = 0, cap_t0 = 0, cap_P = 0, last_nmax = 0;
-  int kv_ub0 = 0;                         // first utterance of the group a wis_align decoder pass runs (dec_forward_frag offsets the cross K / V by it); 0 outside
+  int kv_ub0 = 0;                         // first utterance of the group a wis_align decoder pass (or a long prompt's prefill window) runs (dec_forward_frag offsets the cross K / V by it); 0 outside
   hipEvent_t ev[5 + 128] = {}; int n_ev = 0;      // phase boundaries of the last call (wis_align_last_timing); ev[5..]: (weights, filter) pairs of the first 64 head chunks
   bool ev_partial = false;                // the last call had more head chunks than event pairs: the weights / filter split is not reported
 };
@@ -84,6 +84,8 @@ struct PinnedScratch {
   RowStage rows, win_rows;                     // the search's rows (every caller's default); the rows of a draft-verification window
   float beam_cum[MAX_ROWS]; unsigned beam_tick[4];      // init_beam_state
   unsigned long long seeds[MAX_ROWS];          // upload_seeds: the Philox key of every utterance of a sampled decode
+  int sa_tab[2 * MAX_ROWS];                    // stage_search, WIS_SA_LONG=0: wis_model::d_sa_tab
+  int plen[MAX_ROWS];                          // stage_search: the prompt length of every utterance (wis_model::d_plen)
   unsigned reseed_tick[4];                     // reseed_tick: bs.tick behind a draft verification
   // wis_generate_draft: step index of the verified rows, their picks read back; then the search state `steps` ordinary steps would have left
   int vstep[MAX_ROWS], pick_tok[MAX_ROWS]; float pick_lp[MAX_ROWS];
@@ -136,6 +138,11 @@ struct wis_model {
   // decode state
   float *dx, *dq, *logits, *part; wis::f16 *dao, *dh, *dln; unsigned* counters;
   float* dq2 = nullptr;         // batched fold: second half of the cross-attention q_raw (dec_forward_frag)
+  const int* sa_plen = nullptr;      // set around the decode step of the long-prompt route (generate.hip StepGraph): the pass's self-attention reads the prompt prefix shared in the utterance's first slot (SelfAttnP::plen)
+  int sa_long_form = -1;      // wis_debug_sa_long: 1 / 0 pick the step's self-attention form on this handle whatever WIS_SA_LONG says (-1: the switch decides)
+  int sa_w0 = 0; int* d_sa_tab = nullptr;      // WIS_SA_LONG=0 (A/B form, fallback): the same read pattern through dec_self_attn_kernel<TREE> - w0 = the prompt length (a kernel
+                                               // argument: this form keeps one step graph per prompt length), [0, MAX_ROWS) the rows' own slots, [MAX_ROWS, 2 MAX_ROWS) their utterance's first slot
+  int* d_plen = nullptr;             // prompt length per utterance [MAX_ROWS], written at the start of every call (stage_search): what the long-prompt route's step kernels read in P's place
   int sa_nb = 8;      // 8-position blocks the step's self-attention asks for per pass (generate.hip StepGraph: by the step index; 8 outside the step loops)
   float* gf_part = nullptr; unsigned* gf_cnt = nullptr; int gf_ksplit = 1;      // K split of the batched FFN2 skinny GEMM: slice sums, tickets (GemvP::ksplit)
   unsigned long long* ca_gran = nullptr; unsigned* ca_epoch = nullptr;      // granule hand-off of the decoder cross-attention (small grids): slots, flag + epochs
@@ -230,9 +237,11 @@ int spin_gave_up(wis_model* m, bool* gave_up);
 // ---- the decoder pass ------------------------------------------------------------------------------------------------------------------
 // tw (draft verification at beam > 1): the M rows are nodes of ONE utterance's beam tree - self-attention by ancestor table (anc [M][aw], first
 // window position w0), cross-attention as B = M / 16 groups of R = 16 rows that all read utterance 0's K / V
-struct TreeWin { const int* anc; int w0, aw; const int* base = nullptr; };
+// own_kv: the B groups are B utterances (the windowed prefill of a long prompt) - group b reads the cross K / V of utterance AlignState::kv_ub0 + b
+struct TreeWin { const int* anc; int w0, aw; const int* base = nullptr; bool own_kv = false; };
 struct StepRoute { bool frag, fold, ln16; };      // (small_route, model.hip)
 StepRoute small_route(const wis_model* m, int M);
+bool sa_long_kernel(const wis_model* m);      // false under WIS_SA_LONG=0 (or wis_debug_sa_long(m, 0)): the long-prompt route's step runs the TREE form of dec_self_attn_kernel instead of dec_self_attn_long_kernel
 int dec_forward(wis_model* m, int M, int R, int B, bool want_logits, int sstride, int rmul, const TreeWin* tw = nullptr);
 int upload_rows(wis_model* m, const std::vector<int>& tok, const std::vector<int>& pos, const std::vector<int>& slot, const std::vector<int>& lslot, bool wait = true, RowStage* stage = nullptr);
 int single_row_setup(wis_model* m, int n, const std::vector<int>& tok, int pos);

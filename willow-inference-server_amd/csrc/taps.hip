@@ -411,6 +411,18 @@ int wis_op_dec_self_attn_ex(int device, const float* q, const void* kc, const vo
                             const int32_t* anc, int w0, int aw, const int32_t* base) {
   return op_dec_self_attn("wis_op_dec_self_attn_ex", device, q, kc, vc, pos, out, M, H, ctx, rpu, sstride, rmul, nb, out_mb, anc, w0, aw, base);
 }
+// the long-prompt route's step kernel (launch_dec_self_attn_long, through the launch function the decoder forward calls: SelfAttnP::plen)
+int wis_op_dec_self_attn_long(int device, const float* q, const void* kc, const void* vc, const int32_t* pos, const int32_t* plen, void* out,
+                              int B, int k, int H, int ctx, int out_mb) {
+  Tap t(device, "wis_op_dec_self_attn_long"); WIS_RET(t.rc);
+  if (!q || !kc || !vc || !pos || !plen || !out || B < 1 || H < 1 || k < 1 || k > MAX_R || (out_mb && out_mb < cdiv(B * k, 16))) { set_error("wis_op_dec_self_attn_long: bad argument"); return WIS_E_ARG; }
+  const int d = 64 * H;
+  if (out_mb) WIS_HIP_CHECK(hipMemsetAsync(out, 0, xf_elems(d, out_mb) * 2, t.st));      // the fragment image's rows beyond B k stay zero
+  SelfAttnP sa;
+  sa.q = q; sa.kc = reinterpret_cast<const f16*>(kc); sa.vc = reinterpret_cast<const f16*>(vc); sa.pos = pos; sa.out = reinterpret_cast<f16*>(out);
+  sa.M = B * k; sa.H = H; sa.d = d; sa.ctx = ctx; sa.rpu = k; sa.sstride = k; sa.rmul = 1; sa.out_mb = out_mb; sa.plen = plen;
+  return t.finish(launch_dec_self_attn(t.st, sa));
+}
 static int op_dec_cross_attn(int device, const float* q, const float* xres, const float* qcs, const float* qb, const void* kx, const void* vt, void* out,
                              int B, int R, int H, int T, int chunks, const float* q2 = nullptr, int xres_is_stat = 0, int out_mb = 0, int kv_shared = 0, bool no_spin = false) {
   Tap t(device, "wis_op_dec_cross_attn"); WIS_RET(t.rc);
@@ -579,6 +591,15 @@ int wis_op_kv_reorder(int device, void* kc_f16, void* vc_f16, int64_t layer_stri
   BeamState bs; memset(&bs, 0, sizeof(bs));
   bs.parent = const_cast<int*>(parent); bs.step_u = const_cast<int*>(step_u); bs.done = const_cast<int*>(done);
   return t.finish(launch_kv_reorder(t.st, reinterpret_cast<f16*>(kc_f16), reinterpret_cast<f16*>(vc_f16), (size_t)layer_stride_elems, L, bs, B, beam, P, ctx, d));
+}
+int wis_op_kv_reorder_from(int device, void* kc_f16, void* vc_f16, int64_t layer_stride_elems, int L, const int32_t* parent, const int32_t* step_u, const int32_t* done,
+                           const int32_t* plen, int B, int beam, int ctx, int d) {
+  Tap t(device, "wis_op_kv_reorder_from"); WIS_RET(t.rc);
+  if (!kc_f16 || !vc_f16 || !parent || !step_u || !done || !plen || L < 1 || B < 1 || beam < 1 || ctx < 1 || d < 8 || d % 8 || layer_stride_elems < (int64_t)B * beam * ctx * d || layer_stride_elems % 8) {
+    set_error("wis_op_kv_reorder_from: bad argument"); return WIS_E_ARG; }
+  BeamState bs; memset(&bs, 0, sizeof(bs));
+  bs.parent = const_cast<int*>(parent); bs.step_u = const_cast<int*>(step_u); bs.done = const_cast<int*>(done);
+  return t.finish(launch_kv_reorder_from(t.st, reinterpret_cast<f16*>(kc_f16), reinterpret_cast<f16*>(vc_f16), (size_t)layer_stride_elems, L, bs, B, beam, plen, ctx, d));
 }
 int wis_op_kv_gather(int device, void* kc_f16, void* vc_f16, int64_t layer_stride_elems, int L, const int32_t* vstate, const int32_t* done, int beam, int w0, int ctx, int d) {
   Tap t(device, "wis_op_kv_gather"); WIS_RET(t.rc);

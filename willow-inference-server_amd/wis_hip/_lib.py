@@ -114,6 +114,8 @@ SYMBOLS = [
     ("wis_debug_search_n", _i, [_vp, _vp, _i, _i, C.POINTER(GenOpts), C.POINTER(C.c_uint64), C.POINTER(C.c_uint32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), _fp,
                                 C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     ("wis_debug_handoff", _i, [_vp, _i, C.POINTER(_i), C.POINTER(_i)]),
+    ("wis_debug_graph_count", _i, [_vp, C.POINTER(_i)]),
+    ("wis_debug_sa_long", _i, [_vp, _i]),
     ("wis_last_timing", _i, [_vp, C.POINTER(Timing)]),
     ("wis_debug_phase_cycles", _i, [_vp, _i, _i, _i, C.POINTER(C.c_uint64)]),
     ("wis_debug_timeline", _i, [_vp, _i, _i, _i, _i, C.POINTER(C.c_uint64), _i]),
@@ -146,6 +148,8 @@ SYMBOLS = [
     ("wis_op_enc_crosskv", _i, [_i] + [_vp] * 5 + [_i] * 4 + [_i64] * 2),
     ("wis_op_gemm_splitk_ln", _i, [_i] + [_vp] * 7 + [_i] * 4),
     ("wis_op_kv_reorder", _i, [_i, _vp, _vp, _i64, _i, _vp, _vp, _vp, _i, _i, _i, _i, _i]),
+    ("wis_op_kv_reorder_from", _i, [_i, _vp, _vp, _i64, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _i]),
+    ("wis_op_dec_self_attn_long", _i, [_i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i]),
     ("wis_op_kv_gather", _i, [_i, _vp, _vp, _i64, _i, _vp, _vp, _i, _i, _i, _i]),
     ("wis_op_no_speech", _i, [_i, _vp, _i, _i, _i, _i, _i, _i, _vp]),
     ("wis_op_lang_probs", _i, [_i, _vp, _i, _vp, _i, _vp, _i]),

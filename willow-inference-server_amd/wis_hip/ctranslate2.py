@@ -283,7 +283,9 @@ def _generate_chunk(r, mel, prompts, P, beam, max_new, lp, patience, suppress_bl
 MAX_DECODER_ROWS = 96      # csrc/kernels.hpp MAX_ROWS: decoder rows per device pass
 MAX_BEAM = 8               # csrc/kernels.hpp MAX_R: rows per utterance (beam size)
 MAX_REPLICAS_PER_DEVICE = 4   # default ceiling for inter_threads -> replicas per GPU (measured on MI355X, bench.py "concurrent_device_batches": 118 / 152 / 165 / 173 / 160 utterances/s with 1..5 batches of 8 in flight)
-MAX_PROMPT = 16            # wis_generate: prompt tokens per utterance
+SHORT_PROMPT = 16          # csrc/generate.hip SHORT_PROMPT: prompts up to here run as ONE merged prefill + first step pass (B * P decoder rows)
+MAX_PROMPT = 228           # wis_generate: prompt tokens per utterance (n_text_ctx / 2 + 4: openai-whisper's 223 prompt tokens behind <|startofprev|>, the start sequence);
+                           # more than SHORT_PROMPT take the long-prompt route (windowed prefill, shared prompt prefix)
 MAX_HYPOTHESES = 24        # csrc/kernels.hpp MAX_HYP: finished hypotheses an utterance's search can hold
 MAX_SAMPLING_TOPK = 16     # csrc/kernels.hpp MAX_CAND: the largest sampling_topk short of the whole vocabulary
 
@@ -385,9 +387,13 @@ def _check_patience(beam_size, patience):
 
 def _capacity(max_batch, key):
     """Utterances per device batch: the decoder handles <= MAX_DECODER_ROWS rows per pass - utterances x beam while decoding,
-    utterances x P in the merged prefill + first step (wis_generate enforces B * P <= MAX_ROWS and B * beam <= MAX_ROWS)."""
+    utterances x P in the merged prefill + first step (wis_generate enforces B * P <= MAX_ROWS and B * beam <= MAX_ROWS).
+    A prompt of more than SHORT_PROMPT tokens is prefilled in windows whose last one shrinks with the batch (min(16, MAX_ROWS // B) rows per
+    utterance): the capacity no longer divides by P."""
     P, beam = key[0], key[1]
     rows = max(beam, key[18] if len(key) > 18 else 1, 1)      # decoder rows per utterance: its beams, or its num_hypotheses samples
+    if P > SHORT_PROMPT:
+        return max(1, min(max_batch, MAX_DECODER_ROWS // rows))
     return max(1, min(max_batch, MAX_DECODER_ROWS // rows, MAX_DECODER_ROWS // max(P, 1)))
 
 
@@ -583,8 +589,11 @@ class Whisper:
         # the engine's capacity limits are request errors (ValueError -> HTTP 400 in wis_hip.server), not internal ones
         if not 1 <= int(beam_size) <= self.max_beam:
             raise ValueError(f"beam_size {beam_size} outside 1..{self.max_beam} (setting max_beam; engine ceiling {MAX_BEAM})")
-        if not 1 <= P <= MAX_PROMPT:
-            raise ValueError(f"prompt length {P} outside 1..{MAX_PROMPT}")
+        max_prompt = min(MAX_PROMPT, int((getattr(self, "arch", None) or {}).get("n_text_ctx", 448)) // 2 + 4)
+        if not 1 <= P <= max_prompt:
+            raise ValueError(f"prompt length {P} outside 1..{max_prompt}")
+        if P > SHORT_PROMPT and drafted:
+            raise ValueError(f"a prompt of more than {SHORT_PROMPT} tokens cannot be combined with draft_tokens / draft_trajectory")
         _check_patience(beam_size, patience)
         ts_rows = [timestamp_prompt(p, getattr(self, "special", None)) for p in prompts]
         timestamps = any(ts_rows)
@@ -665,6 +674,10 @@ class Whisper:
         if r.device != device:
             raise ValueError(f"replica lives on device {r.device}, the features on {device}")
         P = len(prompt)
+        if not 1 <= P <= MAX_PROMPT:
+            raise ValueError(f"prompt length {P} outside 1..{MAX_PROMPT}")
+        if P > SHORT_PROMPT and (draft_tokens is not None and len(draft_tokens) or draft_trajectory is not None and len(draft_trajectory[0])):
+            raise ValueError(f"a prompt of more than {SHORT_PROMPT} tokens cannot be combined with draft_tokens / draft_trajectory")
         max_new = min(max_length // 2, max_length - P)
         if not 1 <= int(beam_size) <= self.max_beam:
             raise ValueError(f"beam_size {beam_size} outside 1..{self.max_beam}")

@@ -176,7 +176,24 @@ def create_app(models=None, settings=None, max_workers=None, sv=None):
             temps, best_of = (t_ if temps is not None else None), (n_ if best_of is not None else None)
             if best_of is not None and best_of > s.max_beam:
                 raise BadRequest(f"best_of {best_of} outside 1..{s.max_beam}")
-        return dict(model=model, beam_size=beam, repetition_penalty=rp, no_repeat_ngram_size=ng, temperatures=temps, best_of=best_of,
+        # openai-whisper's initial_prompt= / prefix=: text, or "ids:1,2,3" for token ids; absent or empty = the settings' values; unparsable = 400
+        prompts = {}
+        for name in ("initial_prompt", "prefix"):
+            v = q.get(name)
+            if v in (None, ""):
+                prompts[name] = None
+            elif len(v) > 4096:
+                raise BadRequest(f"{name}: {len(v)} characters (at most 4096)")
+            elif v.startswith("ids:"):
+                try:
+                    prompts[name] = [int(t) for t in v[4:].split(",") if t.strip() != ""]
+                except ValueError:
+                    raise BadRequest(f"Invalid {name} {v!r}: ids:<comma-separated token ids>")
+                if any(t < 0 for t in prompts[name]):
+                    raise BadRequest(f"Invalid {name} {v!r}: token ids are >= 0")
+            else:
+                prompts[name] = v
+        return dict(model=model, beam_size=beam, repetition_penalty=rp, **prompts, no_repeat_ngram_size=ng, temperatures=temps, best_of=best_of,
                     detect_language=_as_bool(q.get("detect_language"), s.detect_language), force_language=q.get("force_language") or None,
                     translate=_as_bool(q.get("translate"), False), timestamps=_as_bool(q.get("timestamps"), False),
                     word_timestamps=_as_bool(q.get("word_timestamps"), False))
@@ -186,7 +203,7 @@ def create_app(models=None, settings=None, max_workers=None, sv=None):
         kw = {"timestamps": True} if p["timestamps"] else {}      # (segment times: one 30 s window; longer audio is a 400)
         if p["word_timestamps"]:                                  # (word times imply segment times; no vocabulary / long audio is a 400)
             kw = {"word_timestamps": True}
-        kw.update({k: p[k] for k in ("repetition_penalty", "no_repeat_ngram_size", "temperatures", "best_of") if p[k] is not None})      # (absent: do_whisper takes the settings' values)
+        kw.update({k: p[k] for k in ("repetition_penalty", "no_repeat_ngram_size", "temperatures", "best_of", "initial_prompt", "prefix") if p[k] is not None})      # (absent: do_whisper takes the settings' values)
         return await loop.run_in_executor(pool, lambda: do_whisper(audio_file, p["model"], p["beam_size"], "transcribe", p["detect_language"],
                                                                    p["force_language"], p["translate"], models=get_models(), **kw))
 

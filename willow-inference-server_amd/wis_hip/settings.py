@@ -86,6 +86,10 @@ class APISettings:
     # complete an n-gram the beam already holds is masked.  1.0 / 0 = off (CTranslate2's defaults)
     repetition_penalty: float = 1.0
     no_repeat_ngram_size: int = 0
+    # prompted decoding (openai-whisper's options of these names; empty: off): text the decoder is conditioned on behind <|startofprev|> (names,
+    # vocabulary, style), and text the transcript is made to start with
+    initial_prompt: str = ""
+    prefix: str = ""
     # openai-whisper's temperature fallback (decode_with_fallback), as every request without the query parameters of the same names decodes: a
     # window whose result loops (zlib compression ratio of its text above `compression_ratio_threshold`) or scores badly (average log-probability
     # below `logprob_threshold`) is decoded again at each later temperature - a sampled decode of `best_of` samples, the one with the best average

@@ -217,6 +217,12 @@ class _Tokenizer:
             return self._tok.decode(ids, skip_special_tokens=False)
         return " ".join(str(t) for t in ids)
 
+    def encode(self, text):
+        """text -> token ids, no special tokens added (a prompt's text); needs the checkpoint's vocabulary"""
+        if self._tok is None:
+            raise ValueError("a text prompt needs the checkpoint's tokenizer vocabulary (tokenizer.json next to the model); pass token ids instead")
+        return [int(t) for t in self._tok.encode(text, add_special_tokens=False).ids]
+
     @staticmethod
     def language_token_id(code):
         return W.LANG_IDS[LANGUAGE_CODES.index(code)]
@@ -364,10 +370,53 @@ def decode_with_fallback(decode, temperatures, best_of=5, compression_ratio_thre
     return out
 
 
+MAX_PREFIX_TOKENS = 64      # a decoder prefix is a few words, never half the context
+
+
+def prompt_ids(value, tokenizer, special, what):
+    """`initial_prompt` / `prefix` of do_whisper -> text token ids.  A string is encoded as " " + text.strip() with the checkpoint's tokenizer
+    (openai-whisper's convention; no vocabulary: ValueError), a list of ids is taken as it is (text ids, below <|endoftext|>).  None / empty: []."""
+    if value is None or (isinstance(value, (str, list, tuple)) and len(value) == 0):
+        return []
+    if isinstance(value, str):
+        if not value.strip():
+            return []
+        if not getattr(tokenizer, "has_vocabulary", False):
+            raise ValueError(f"{what}: a text prompt needs the checkpoint's tokenizer vocabulary (tokenizer.json next to the model); pass token ids instead")
+        return tokenizer.encode(" " + value.strip())
+    try:
+        ids = [int(t) for t in value]
+        if any(isinstance(t, (bool, float)) for t in value):
+            raise TypeError
+    except (TypeError, ValueError):
+        raise ValueError(f"{what}: a string or a list of token ids") from None
+    if any(not 0 <= t < special.eot for t in ids):
+        raise ValueError(f"{what}: token ids must be text tokens (0 .. {special.eot - 1})")
+    return ids
+
+
+def assemble_prompt(start, special, initial_prompt_ids=(), prefix_ids=(), n_text_ctx=448):
+    """openai-whisper's decoder prompt: [<|startofprev|>] + initial_prompt_ids[-(n_ctx / 2 - 1):] + start sequence + prefix_ids.  The engine takes
+    n_ctx / 2 + 4 tokens (228): with a prefix the prompt part is cut further from the left.  A prefix of more than MAX_PREFIX_TOKENS is a ValueError."""
+    prefix_ids, initial_prompt_ids = list(prefix_ids), list(initial_prompt_ids)
+    if len(prefix_ids) > MAX_PREFIX_TOKENS:
+        raise ValueError(f"prefix: {len(prefix_ids)} tokens (at most {MAX_PREFIX_TOKENS})")
+    if not initial_prompt_ids:
+        return list(start) + prefix_ids
+    keep = min(n_text_ctx // 2 - 1, n_text_ctx // 2 + 4 - 1 - len(start) - len(prefix_ids))
+    return [special.startofprev] + initial_prompt_ids[-keep:] + list(start) + prefix_ids
+
+
 def do_whisper(audio_file, model, beam_size=None, task="transcribe", detect_language=False, force_language=None, translate=False,
                models=None, fixed_new_tokens=None, timestamps=False, word_timestamps=False, repetition_penalty=None, no_repeat_ngram_size=None,
-               temperatures=None, best_of=None, compression_ratio_threshold=None, logprob_threshold=None):
-    """temperatures / best_of / compression_ratio_threshold / logprob_threshold: openai-whisper's temperature fallback (decode_with_fallback; None:
+               temperatures=None, best_of=None, compression_ratio_threshold=None, logprob_threshold=None, initial_prompt=None, prefix=None):
+    """initial_prompt / prefix: openai-whisper's options of those names, each a string or a list of token ids (None: the settings' values; empty:
+    off).  The decoder prompt becomes [<|startofprev|>] + prompt ids + start sequence + prefix ids (assemble_prompt; the prompt is cut from the left
+    to what the engine takes, 228 tokens in all).  Every window of a long recording gets the same prompt; language detection, the translation pass and
+    the word alignment stay unprompted; the repetition options and the temperature fallback combine with both options, timestamps / word_timestamps
+    with initial_prompt only: together with a prefix they are a ValueError (the engine's timestamp rules read the generated history, which a prefix
+    is not part of).  `text` is what the engine GENERATED: the prefix is not repeated in it.
+    temperatures / best_of / compression_ratio_threshold / logprob_threshold: openai-whisper's temperature fallback (decode_with_fallback; None:
     the settings' values, and the settings' default - no temperatures - is no fallback).  The first temperature's decode is judged, and while it
     loops or scores badly the window is decoded again at the next: 0 is the search at `beam_size`, anything else `generate(beam_size=1,
     num_hypotheses=best_of, sampling_topk=0, sampling_temperature=t)`.  The compression ratio needs the decoded TEXT, so it needs the
@@ -436,6 +485,12 @@ def do_whisper(audio_file, model, beam_size=None, task="transcribe", detect_lang
         features, kind = audio.log_mel_spectrogram(windows, n_mels=n_mels, device=dev).numpy(), ctranslate2._lib.WIS_IN_MEL_HOST
     total_chunk_count = features.shape[0]
     tokenizer = models.tokenizer_for(model)
+    ip_ids = prompt_ids(getattr(s, "initial_prompt", "") if initial_prompt is None else initial_prompt, tokenizer, special, "initial_prompt")
+    px_ids = prompt_ids(getattr(s, "prefix", "") if prefix is None else prefix, tokenizer, special, "prefix")
+    if timestamps and px_ids:
+        # text behind the start sequence makes the prompt a plain-search prompt for the engine (ctranslate2.timestamp_prompt): its timestamp rules
+        # read the GENERATED history, which a prefix is not part of - refused rather than decoded without the rules
+        raise ValueError("prefix cannot be combined with timestamps / word_timestamps (initial_prompt can)")
     if word_timestamps and not getattr(tokenizer, "has_vocabulary", False):
         raise ValueError("word_timestamps need the checkpoint's tokenizer vocabulary (tokenizer.json next to the model)")
 
@@ -450,7 +505,9 @@ def do_whisper(audio_file, model, beam_size=None, task="transcribe", detect_lang
     if not check_language(language, special):
         raise ValueError(f"unsupported language {language!r}")
     task_id = special.translate if task == "translate" else special.transcribe
-    prompt = [special.sot, special.language_token_id(language), task_id] + ([] if timestamps else [special.notimestamps])
+    start = [special.sot, special.language_token_id(language), task_id] + ([] if timestamps else [special.notimestamps])
+    prompt = assemble_prompt(start, special, ip_ids, px_ids,
+                             int((getattr(whisper_model, "arch", None) or {}).get("n_text_ctx", 448)))
 
     # STEP 3 — run the model, `concurrent_gpu_chunks` windows per generate call
     results = []
@@ -488,7 +545,7 @@ def do_whisper(audio_file, model, beam_size=None, task="transcribe", detect_lang
         if word_timestamps:
             text_tokens = [t for sg in segments for t in sg["tokens"]]
             num_frames = max(2, min(3000, -(-pcm.shape[0] // audio.HOP_LENGTH)))
-            al = whisper_model.align(ctranslate2.StorageView.from_array(np.ascontiguousarray(features[0:1])), prompt[:3], [text_tokens], [num_frames],
+            al = whisper_model.align(ctranslate2.StorageView.from_array(np.ascontiguousarray(features[0:1])), start[:3], [text_tokens], [num_frames],
                                      input_kind=kind)[0]
             words_from_alignment(segments, al.alignments, al.text_token_probs, tokenizer, language, special, duration)
             for sg in segments:
