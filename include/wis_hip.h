@@ -546,6 +546,19 @@ int wis_op_gemm_splitk_ln(int device, const void* A_f16, const void* W_f16, cons
 int wis_op_resample_segment(int device, const float* x_slice, int64_t n_slice, int64_t k_base, int64_t n_in_total, int64_t m0, int64_t count,
                             int up, int down, float* out);
 
+/* ---- the log-mel front end's kernels on caller-supplied device memory, their scratch exposed (tests/test_gpu_logmel_ops.py).  d_pcm: n_win windows,
+ * window w at d_pcm + w stride with n_samples[w] valid samples (n_samples is a HOST array and reaches the kernel unclamped: values below 0 or above
+ * 480000 are the kernel's to handle; samples behind n_samples[w] are never read as signal).  d_logspec f32 [n_win][n_mels][3000] is the log10 mel
+ * spectrum before the floor, d_gmax u32 [n_win] the order-preserving key of each window's maximum.
+ * (tile0, n_tiles) == (0, 188): the whole window as the model's input stage runs it - d_mel f32 [n_win][n_mels][3000] and / or the conv1 image
+ *   d_img_f16 [n_win][3002][C] (C = 96 for 80 bins, 128 for 128; rows 0 and 3001 are not written), either may be null.
+ * any other range: d_gmax is zeroed and the 16-frame tiles [tile0, tile0 + n_tiles) alone are computed, as a streaming session does: no other frame of
+ *   d_logspec is written, d_gmax is the maximum over the range, and there is no finalize pass - d_mel and d_img_f16 must be null (WIS_E_ARG); a range
+ *   outside [0, 188] is WIS_E_ARG.
+ * n_mels other than 80 / 128: WIS_E_UNSUPPORTED. */
+int wis_op_logmel(int device, int n_mels, const float* d_pcm, int64_t stride, const int64_t* n_samples, int n_win, int tile0, int n_tiles,
+                  float* d_logspec, unsigned* d_gmax, float* d_mel, void* d_img_f16);
+
 /* ---- taps of what runs behind the logits (tests/test_gpu_sample_ops.py): the product's launch functions on caller-supplied device memory. */
 /* the cache permutation after a beam step, in place: kc / vc f16, layer l at + l layer_stride_elems, [slots][ctx][d] each (d % 8 == 0); for every
  * utterance b with done[b] == 0, slot b beam + j becomes a copy of slot parent[b beam + j] (a slot of the same utterance) at positions

@@ -14,7 +14,7 @@
 // kernel; the global max is a per-window atomicMax on an order-preserving key, applied by a
 // small finalize kernel that also emits the conv1 input image (time-major f16, zero padded)
 // so the mel never has to leave HBM.  All-silent 16-frame tiles (the zero padding behind a
-// short utterance) skip the DFT: the DFT of zeros is exactly zero, so results are identical.
+// short utterance) skip the DFT: the DFT of zeros is exactly zero and a clamped entry is the constant -10.0f, so results are identical.
 #include <math.h>
 #include <stdarg.h>
 #include <mutex>
@@ -268,7 +268,10 @@ __global__ __launch_bounds__(256) void logmel_stft_kernel(
       const float* pr = s_p + f * PSTR;
       for (int k = lo; k < hi; ++k) v = fmaf(fm[k], pr[k], v);
     }
-    const float lg = log10f(fmaxf(v, 1e-10f));
+    // a clamped entry is -10.0f exactly, the correctly rounded log10 of the clamp constant.  log10f(1e-10f) evaluated on the device is one ulp
+    // below it, while the compiler folds the same expression to -10.0f on the all-silent path: written out, a silent frame has one value
+    // whether or not its tile took the shortcut
+    const float lg = v > 1e-10f ? log10f(v) : -10.0f;
     if (f0 + f < NFRAMES) {
       logspec[((size_t)w * NM + m) * NFRAMES + f0 + f] = lg;
       lmax = fmaxf(lmax, lg);

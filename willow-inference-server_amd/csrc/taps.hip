@@ -640,4 +640,22 @@ int wis_op_resample_segment(int device, const float* x_slice, int64_t n_slice, i
   return t.finish(resample_segment(c, t.st, x_slice, n_slice, k_base, n_in_total, m0, count, up, down, out));
 }
 
+// ---- the log-mel front end on caller-supplied device memory, its scratch exposed (tests/test_gpu_logmel_ops.py): the whole window as stage_input runs it
+// (logmel_device), or a range of 16-frame tiles alone as a streaming session runs it (logmel_frames, no finalize).  n_samples goes to the device as given:
+// the clamp to the window is the kernel's
+int wis_op_logmel(int device, int n_mels, const float* d_pcm, int64_t stride, const int64_t* n_samples, int n_win, int tile0, int n_tiles,
+                  float* d_logspec, unsigned* d_gmax, float* d_mel, void* d_img_f16) {
+  Tap t(device, "wis_op_logmel"); WIS_RET(t.rc);
+  if (!d_pcm || !n_samples || !d_logspec || !d_gmax || n_win < 1 || stride < 0) { set_error("wis_op_logmel: bad argument"); return WIS_E_ARG; }
+  DeviceCtx* c = nullptr; WIS_RET(get_ctx(device, &c));
+  const bool whole = tile0 == 0 && n_tiles == cdiv(WIS_N_FRAMES, 16);
+  if (!whole && (d_mel || d_img_f16)) { set_error("wis_op_logmel: a tile range has no finalize pass: d_mel and d_img_f16 must be null"); return WIS_E_ARG; }
+  int64_t* d_ns = nullptr;
+  WIS_RET(t.get(&d_ns, (size_t)n_win));
+  WIS_HIP_CHECK(hipMemcpy(d_ns, n_samples, (size_t)n_win * 8, hipMemcpyHostToDevice));
+  if (whole) return t.finish(logmel_device(c, t.st, d_logspec, d_gmax, d_pcm, stride, d_ns, n_win, d_mel, reinterpret_cast<f16*>(d_img_f16), n_mels));
+  WIS_HIP_CHECK(hipMemsetAsync(d_gmax, 0, (size_t)n_win * 4, t.st));
+  return t.finish(logmel_frames(c, t.st, d_logspec, d_gmax, d_pcm, stride, d_ns, n_win, tile0, n_tiles, n_mels));
+}
+
 }  // extern "C"

@@ -77,6 +77,7 @@ SYMBOLS = [
     ("wis_resample", _i, [_i, _vp, _i64, _i, _vp, _i64, C.POINTER(_i64)]),
     ("wis_resample_ex", _i, [_i, _vp, _i64, _i, _vp, _i64, C.POINTER(_i64), _i64]),
     ("wis_op_resample_segment", _i, [_i, _vp, _i64, _i64, _i64, _i64, _i64, _i, _i, _vp]),
+    ("wis_op_logmel", _i, [_i, _i, _vp, _i64, C.POINTER(_i64), _i, _i, _i, _vp, _vp, _vp, _vp]),
     ("wis_melstream_create", _i, [_i, C.POINTER(_vp)]),
     ("wis_logmel_n", _i, [_i, _i, _vp, _i64, C.POINTER(_i64), _i, _i, _vp, _i]),
     ("wis_melstream_create_n", _i, [_i, _i, C.POINTER(_vp)]),
