@@ -117,6 +117,38 @@ int64_t wis_melstream_samples(const wis_melstream_t* s);       /* samples receiv
 int  wis_melstream_tiles_done(const wis_melstream_t* s);       /* 16-frame tiles already transformed (0..188) */
 void wis_melstream_destroy(wis_melstream_t* s);
 
+/* ---- whole-recording log-mel for long-form transcription (openai-whisper's transcribe(): one log-mel over the recording with 30 s
+ * of zeros appended, sliced mel[:, seek : seek + 3000]).  One handle = one recording's log10 spectrum in HBM on one device.
+ * Definition: the recording of n_samples samples continues with zeros on the right without end; its left edge is reflect-padded by
+ * 200 samples (torch.stft's centre padding); there is no reflection on the right.  Frame t covers the samples 160 t - 200 ..
+ * 160 t + 199, for t = 0 .. n_samples / 160 + 2999.  lg[m][t] = log10(max(mel, 1e-10)) with the DFT table, the filter bank and
+ * the order of every sum of wis_logmel_n (the same per-tile code: the bits of a frame depend on its 400 samples alone - not on the
+ * recording's length, on the upload segment or launch that produced it, or on the window that reads it).  A frame that touches no
+ * sample has lg = -10.0f exactly.  gmax = the maximum of lg over all those frames, so never below -10.  A window's entry for the
+ * frame g = seek + f, f < 3000, is (max(lg[m][g], gmax - 8) + 4) / 4: the floor is the RECORDING's, not the window's.
+ * Only the frames up to the last one that touches a sample, rounded up to a 16-frame tile, are stored (4 n_mels bytes per frame:
+ * 230 MB for two hours at 80 bins); the window kernel supplies -10.0f beyond them.  While n_samples <= 479800 the window at seek 0
+ * equals wis_logmel_n of the same samples bit for bit.  From 479801 samples on frame 3000 touches a sample: it enters gmax here and is no
+ * frame of wis_logmel_n, so the floors differ if that frame holds the maximum; above 479958 wis_logmel_n's right-hand reflection reads real
+ * samples as well.
+ * Host PCM is uploaded in segments over a bounded staging buffer.  n_samples above WIS_LONGMEL_MAX_SAMPLES (4 hours), n_mels
+ * other than 80 or 128, a NULL pcm with n_samples > 0: WIS_E_ARG, and *out is NULL. */
+#define WIS_LONGMEL_MAX_SAMPLES 230400000LL
+typedef struct wis_longmel wis_longmel_t;
+int  wis_longmel_create(int device, int n_mels, const float* pcm, int64_t n_samples, int pcm_on_device, wis_longmel_t** out);
+/* the same with the upload segment forced: segment_samples host samples per segment (0: the built-in length; below 2800, one
+ * tile's span: WIS_E_ARG).  Ignored for device PCM. */
+int  wis_longmel_create_ex(int device, int n_mels, const float* pcm, int64_t n_samples, int pcm_on_device, int64_t segment_samples,
+                           wis_longmel_t** out);
+int64_t wis_longmel_frames(const wis_longmel_t* h);            /* content frames = n_samples / 160, floor (NULL: 0) */
+int  wis_longmel_max(wis_longmel_t* h, float* gmax_out);       /* gmax, the value behind the ordered key (tests) */
+/* mel_out f32 [n_win][n_mels][3000] (host or device): window w = frames seek_frames[w] .. seek_frames[w] + 2999, one launch for all
+ * of them; a device mel_out is WIS_IN_MEL_DEV input of wis_generate on the same device.  Every seek in [0, frames + 2999], n_win up
+ * to 1024; otherwise, and for a NULL handle, WIS_E_ARG with nothing launched.  Returns with nothing in flight.  Calls on one handle
+ * are serialised; different handles are independent (own stream and buffers). */
+int  wis_longmel_window(wis_longmel_t* h, const int64_t* seek_frames, int n_win, float* mel_out, int mel_on_device);
+void wis_longmel_destroy(wis_longmel_t* h);
+
 /* ---- a6: model lifecycle (replaces ctranslate2.models.Whisper(path, device=..,
  * compute_type=.., device_index=[..]), main.py:341-444).  One handle = one replica on one
  * GPU; the Python shim creates one per listed device_index entry. */

@@ -17,7 +17,9 @@
 // short utterance) skip the DFT: the DFT of zeros is exactly zero and a clamped entry is the constant -10.0f, so results are identical.
 #include <math.h>
 #include <stdarg.h>
+#include <string.h>
 #include <mutex>
+#include <type_traits>
 #include <vector>
 
 #include "common.hpp"
@@ -191,27 +193,39 @@ __device__ __forceinline__ float fkey_inv(unsigned k) {
   return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k);
 }
 
-// grid (188, n_win), block 256; NM = mel bins (80 or 128): only the filterbank stage and the logspec layout depend on it
-template <int NM>
-__global__ __launch_bounds__(256) void logmel_stft_kernel(
-    const float* __restrict__ pcm, int64_t stride, const int64_t* __restrict__ nsamp,
+// One 16-frame tile, the body of both STFT kernels; block 256; NM = mel bins (80 or 128): only the filterbank stage and the logspec
+// layout depend on it.  LONG = false is the 30 s window (pad_or_trim, reflection at both window edges, rows of 3000 frames); LONG = true is
+// a whole recording (wis_longmel_*): 64-bit sample positions, a run-time length nv, reflection at the left edge only, zeros behind the
+// last sample, and x holds the samples [base, base + avail) of the recording (one upload segment).  Everything after the staging is the
+// same code, so a frame's bits depend on its 400 samples alone.  lrow: row 0 of this window's log-spectrum, rows `pitch` apart, frames
+// below nstore are written.
+template <int NM, bool LONG>
+__device__ __forceinline__ void stft_tile(
+    const float* __restrict__ x, int64_t nv, int64_t base, int64_t avail, int64_t tile,
     const float* __restrict__ dft, const float* __restrict__ filt, const int* __restrict__ frange,
-    float* __restrict__ logspec, unsigned* __restrict__ gmax, int tile0) {
+    float* __restrict__ lrow, int64_t pitch, int64_t nstore, unsigned* __restrict__ gmax) {
   __shared__ float s_x[SPAN_LDS];
   __shared__ float s_p[FT * PSTR];
   __shared__ float s_red[4];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int w = blockIdx.y, f0 = (blockIdx.x + tile0) * FT;   // tile0: first 16-frame tile of this launch (streaming sessions)
-  const float* x = pcm + (int64_t)w * stride;
-  int64_t nv = nsamp[w]; if (nv > NSAMP) nv = NSAMP;   // pad_or_trim (wis/audio.py:28-51)
+  typedef typename std::conditional<LONG, int64_t, int>::type pos_t;
+  const pos_t f0 = (pos_t)tile * FT;
 
   // stage the 2800-sample span with torch.stft's centre/reflect padding of the 480000 window
   int nz = 0;
   for (int t = tid; t < SPAN; t += 256) {
-    int g = HOP * f0 - NFFT / 2 + t;
-    if (g < 0) g = -g;
-    if (g >= NSAMP) g = 2 * (NSAMP - 1) - g;
-    float v = (g >= 0 && g < nv) ? x[g] : 0.f;
+    float v;
+    if constexpr (LONG) {
+      int64_t g = (int64_t)HOP * f0 - NFFT / 2 + t;
+      if (g < 0) g = -g;                                   // the left edge only: the recording continues with zeros on the right
+      const int64_t o = g - base;
+      v = (g < nv && o >= 0 && o < avail) ? x[o] : 0.f;
+    } else {
+      int g = HOP * f0 - NFFT / 2 + t;
+      if (g < 0) g = -g;
+      if (g >= NSAMP) g = 2 * (NSAMP - 1) - g;
+      v = (g >= 0 && g < nv) ? x[g] : 0.f;
+    }
     nz |= (v != 0.f);
     s_x[SKEW(t)] = v;
   }
@@ -272,8 +286,8 @@ __global__ __launch_bounds__(256) void logmel_stft_kernel(
     // below it, while the compiler folds the same expression to -10.0f on the all-silent path: written out, a silent frame has one value
     // whether or not its tile took the shortcut
     const float lg = v > 1e-10f ? log10f(v) : -10.0f;
-    if (f0 + f < NFRAMES) {
-      logspec[((size_t)w * NM + m) * NFRAMES + f0 + f] = lg;
+    if (f0 + f < nstore) {
+      lrow[(size_t)m * pitch + f0 + f] = lg;
       lmax = fmaxf(lmax, lg);
     }
   }
@@ -282,8 +296,44 @@ __global__ __launch_bounds__(256) void logmel_stft_kernel(
   __syncthreads();
   if (tid == 0) {
     const float mx = fmaxf(fmaxf(s_red[0], s_red[1]), fmaxf(s_red[2], s_red[3]));
-    atomicMax(gmax + w, fkey(mx));
+    atomicMax(gmax, fkey(mx));
   }
+}
+
+// grid (n_tiles, n_win), block 256: the tiles tile0 .. of every 30 s window (tile0: first 16-frame tile of this launch, streaming sessions)
+template <int NM>
+__global__ __launch_bounds__(256) void logmel_stft_kernel(
+    const float* __restrict__ pcm, int64_t stride, const int64_t* __restrict__ nsamp,
+    const float* __restrict__ dft, const float* __restrict__ filt, const int* __restrict__ frange,
+    float* __restrict__ logspec, unsigned* __restrict__ gmax, int tile0) {
+  const int w = blockIdx.y;
+  int64_t nv = nsamp[w]; if (nv > NSAMP) nv = NSAMP;   // pad_or_trim (wis/audio.py:28-51)
+  stft_tile<NM, false>(pcm + (int64_t)w * stride, nv, 0, NSAMP, blockIdx.x + tile0, dft, filt, frange,
+                       logspec + (size_t)w * NM * NFRAMES, NFRAMES, NFRAMES, gmax + w);
+}
+
+// grid (n_tiles), block 256: the tiles tile0 .. of one recording of n samples, read from the slice x = samples [base, base + avail);
+// logspec f32 [NM][stored], stored a multiple of 16 that covers every tile launched
+template <int NM>
+__global__ __launch_bounds__(256) void longmel_stft_kernel(
+    const float* __restrict__ x, int64_t n, int64_t base, int64_t avail,
+    const float* __restrict__ dft, const float* __restrict__ filt, const int* __restrict__ frange,
+    float* __restrict__ logspec, int64_t stored, unsigned* __restrict__ gmax, int64_t tile0) {
+  stft_tile<NM, true>(x, n, base, avail, tile0 + blockIdx.x, dft, filt, frange, logspec, stored, stored, gmax);
+}
+
+// grid (ceil(3000 / 256), NM, n_win), block 256: window w = frames seek[w] .. seek[w] + 2999 of the recording, clamped against the
+// recording's maximum and scaled as logmel_finalize_kernel does; a frame beyond the stored range touches no sample: -10.0f
+template <int NM>
+__global__ __launch_bounds__(256) void longmel_window_kernel(
+    const float* __restrict__ logspec, int64_t stored, const unsigned* __restrict__ gmax, const int64_t* __restrict__ seek,
+    float* __restrict__ mel) {
+  const int f = blockIdx.x * 256 + threadIdx.x, m = blockIdx.y, w = blockIdx.z;
+  if (f >= NFRAMES) return;
+  const float floor_ = fkey_inv(gmax[0]) - 8.0f;
+  const int64_t g = seek[w] + f;
+  const float lg = g < stored ? logspec[(size_t)m * stored + g] : -10.0f;
+  mel[((size_t)w * NM + m) * NFRAMES + f] = (fmaxf(lg, floor_) + 4.0f) / 4.0f;
 }
 
 // grid (ceil(3000/64), n_win), block 256: clamp to max-8, scale, write f32 [NM][3000] and/or
@@ -490,4 +540,149 @@ extern "C" void wis_melstream_destroy(wis_melstream_t* s) {
   hipFree(s->d_pcm); hipFree(s->d_nsamp); hipFree(s->d_logspec); hipFree(s->d_gmax); hipFree(s->d_mel);
   if (s->h_nsamp) hipHostFree(s->h_nsamp);
   delete s;
+}
+
+// ---------------------------------------------------------------------------------------
+// Whole-recording log-mel (include/wis_hip.h: wis_longmel_*).  The log10 spectrum of every frame that touches a sample stays in HBM
+// with the recording's maximum; a window is a gather + clamp + scale at any frame offset.
+struct wis_longmel {
+  int device = 0;
+  int n_mels = NMEL;
+  DeviceCtx* ctx = nullptr;
+  hipStream_t stream = nullptr;
+  float* d_logspec = nullptr;      // [n_mels][stored]
+  unsigned* d_gmax = nullptr;
+  int64_t n = 0, content = 0, stored = 0;
+  std::mutex mu;                   // the window scratch below serves one call at a time
+  int64_t* d_seek = nullptr; int cap = 0;                             // windows
+  float* d_out = nullptr; int out_cap = 0;                            // windows of the host-return path alone
+};
+namespace {
+constexpr int64_t LM_SEGMENT = (int64_t)1 << 22;       // samples per upload segment (wis_longmel_create; wis_longmel_create_ex overrides)
+constexpr int64_t LM_TILE = (int64_t)FT * HOP;         // 2560 samples between two tiles
+constexpr int LM_MAX_WIN = 1024;
+unsigned host_fkey(float x) {
+  unsigned b; memcpy(&b, &x, 4);
+  return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
+}
+int longmel_tiles(wis_longmel* h, const float* d_x, int64_t base, int64_t avail, int64_t tile0, int64_t n_tiles) {
+  DeviceCtx* c = h->ctx;
+  if (h->n_mels == NMEL)
+    hipLaunchKernelGGL(longmel_stft_kernel<NMEL>, dim3((unsigned)n_tiles), dim3(256), 0, h->stream,
+                       d_x, h->n, base, avail, c->d_dft, c->d_filt, c->d_frange, h->d_logspec, h->stored, h->d_gmax, tile0);
+  else
+    hipLaunchKernelGGL(longmel_stft_kernel<NMEL_MAX>, dim3((unsigned)n_tiles), dim3(256), 0, h->stream,
+                       d_x, h->n, base, avail, c->d_dft, c->d_filt128, c->d_frange128, h->d_logspec, h->stored, h->d_gmax, tile0);
+  WIS_HIP_CHECK(hipGetLastError());
+  return WIS_OK;
+}
+}  // namespace
+
+extern "C" int wis_longmel_create_ex(int device, int n_mels, const float* pcm, int64_t n_samples, int pcm_on_device, int64_t segment_samples,
+                                     wis_longmel_t** out) {
+  if (!out) { set_error("wis_longmel_create: bad argument"); return WIS_E_ARG; }
+  *out = nullptr;
+  if (!mel_bins_supported(n_mels)) { set_error("wis_longmel_create: %d mel bins (80 or 128)", n_mels); return WIS_E_ARG; }
+  if (n_samples < 0 || (!pcm && n_samples > 0) || segment_samples < 0 || (segment_samples && segment_samples < SPAN)) {
+    set_error("wis_longmel_create: bad argument"); return WIS_E_ARG;
+  }
+  if (n_samples > WIS_LONGMEL_MAX_SAMPLES) {
+    set_error("wis_longmel_create: %lld samples, over the cap of %lld (4 h)", (long long)n_samples, (long long)WIS_LONGMEL_MAX_SAMPLES); return WIS_E_ARG;
+  }
+  DeviceCtx* c; WIS_RET(get_ctx(device, &c));
+  wis_longmel* h = new wis_longmel();
+  h->device = device; h->ctx = c; h->n_mels = n_mels; h->n = n_samples; h->content = n_samples / HOP;
+  // frame t touches a sample while 160 t - 200 <= n - 1; stored: one past the last such frame, rounded up to a tile
+  const int64_t touched = n_samples > 0 ? (n_samples + NFFT / 2 - 1) / HOP + 1 : 0;
+  h->stored = (touched + FT - 1) / FT * FT;
+  const int64_t n_tiles = h->stored / FT;
+  const int64_t seg = segment_samples ? segment_samples : LM_SEGMENT;
+  const int64_t per = (seg - (SPAN - LM_TILE)) / LM_TILE;          // tiles whose spans fit one segment (>= 1: seg >= 2800)
+  float* d_stage = nullptr;
+  auto body = [&]() -> int {
+    if (hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess || hipMalloc(&h->d_gmax, 4) != hipSuccess ||
+        (h->stored && hipMalloc(&h->d_logspec, (size_t)n_mels * h->stored * 4) != hipSuccess)) {
+      set_error("wis_longmel_create: out of device memory for %lld frames", (long long)h->stored); return WIS_E_NOMEM;
+    }
+    const unsigned key0 = host_fkey(-10.0f);                       // the frames behind the stored range: the maximum is never below them
+    WIS_HIP_CHECK(hipMemcpy(h->d_gmax, &key0, 4, hipMemcpyHostToDevice));     // (synchronous: done before the first tile is launched, and key0 is a local)
+    if (n_tiles && pcm_on_device) WIS_RET(longmel_tiles(h, pcm, 0, n_samples, 0, n_tiles));
+    else if (n_tiles) {
+      const int64_t stage = seg < n_samples ? seg : n_samples;
+      if (hipMalloc(&d_stage, (size_t)stage * 4) != hipSuccess) { set_error("wis_longmel_create: out of device memory for a segment of %lld samples", (long long)stage); return WIS_E_NOMEM; }
+      for (int64_t t0 = 0; t0 < n_tiles; t0 += per) {
+        const int64_t t1 = t0 + per < n_tiles ? t0 + per : n_tiles;
+        int64_t lo = LM_TILE * t0 - NFFT / 2, hi = LM_TILE * (t1 - 1) + SPAN - NFFT / 2;     // the samples those tiles read
+        if (lo < 0) lo = 0;                                        // (the reflected ones are samples 1 .. 200 of the same segment)
+        if (hi > n_samples) hi = n_samples;
+        if (hi - lo > stage) { set_error("wis_longmel_create: segment of %lld samples over a staging buffer of %lld", (long long)(hi - lo), (long long)stage); return WIS_E_STATE; }
+        if (hi > lo) WIS_HIP_CHECK(hipMemcpyAsync(d_stage, pcm + lo, (size_t)(hi - lo) * 4, hipMemcpyHostToDevice, h->stream));
+        WIS_RET(longmel_tiles(h, d_stage, lo, hi > lo ? hi - lo : 0, t0, t1 - t0));
+      }
+    }
+    WIS_HIP_CHECK(hipStreamSynchronize(h->stream));                // the caller's PCM and the staging buffer are free again
+    return WIS_OK;
+  };
+  const int rc = body();
+  if (rc != WIS_OK && h->stream) hipStreamSynchronize(h->stream);  // nothing may still be in flight when the buffers go
+  hipFree(d_stage);
+  if (rc != WIS_OK) { wis_longmel_destroy(h); return rc; }
+  *out = h;
+  return WIS_OK;
+}
+extern "C" int wis_longmel_create(int device, int n_mels, const float* pcm, int64_t n_samples, int pcm_on_device, wis_longmel_t** out) {
+  return wis_longmel_create_ex(device, n_mels, pcm, n_samples, pcm_on_device, 0, out);
+}
+extern "C" int64_t wis_longmel_frames(const wis_longmel_t* h) { return h ? h->content : 0; }
+extern "C" int wis_longmel_max(wis_longmel_t* h, float* gmax_out) {
+  if (!h || !gmax_out) { set_error("wis_longmel_max: bad argument"); return WIS_E_ARG; }
+  WIS_HIP_CHECK(hipSetDevice(h->device));
+  unsigned k = 0;
+  WIS_HIP_CHECK(hipMemcpy(&k, h->d_gmax, 4, hipMemcpyDeviceToHost));
+  const unsigned b = (k & 0x80000000u) ? (k & 0x7fffffffu) : ~k;
+  memcpy(gmax_out, &b, 4);
+  return WIS_OK;
+}
+extern "C" int wis_longmel_window(wis_longmel_t* h, const int64_t* seek_frames, int n_win, float* mel_out, int mel_on_device) {
+  if (!h || !seek_frames || !mel_out || n_win < 0 || n_win > LM_MAX_WIN) { set_error("wis_longmel_window: bad argument"); return WIS_E_ARG; }
+  for (int w = 0; w < n_win; ++w)
+    if (seek_frames[w] < 0 || seek_frames[w] > h->content + NFRAMES - 1) {
+      set_error("wis_longmel_window: seek %lld outside the recording's frames [0, %lld]", (long long)seek_frames[w], (long long)(h->content + NFRAMES - 1));
+      return WIS_E_ARG;
+    }
+  if (n_win == 0) return WIS_OK;
+  WIS_HIP_CHECK(hipSetDevice(h->device));
+  std::lock_guard<std::mutex> lk(h->mu);
+  if (n_win > h->cap) {
+    hipFree(h->d_seek); h->d_seek = nullptr; h->cap = 0;
+    if (hipMalloc(&h->d_seek, (size_t)n_win * 8) != hipSuccess) { set_error("wis_longmel_window: out of device memory for %d seeks", n_win); return WIS_E_NOMEM; }
+    h->cap = n_win;
+  }
+  if (!mel_on_device && n_win > h->out_cap) {      // a device mel_out is written in place: only the host path stages
+    hipFree(h->d_out); h->d_out = nullptr; h->out_cap = 0;
+    if (hipMalloc(&h->d_out, (size_t)n_win * h->n_mels * NFRAMES * 4) != hipSuccess) { set_error("wis_longmel_window: out of device memory for %d windows", n_win); return WIS_E_NOMEM; }
+    h->out_cap = n_win;
+  }
+  auto body = [&]() -> int {
+    WIS_HIP_CHECK(hipMemcpyAsync(h->d_seek, seek_frames, (size_t)n_win * 8, hipMemcpyHostToDevice, h->stream));
+    float* dm = mel_on_device ? mel_out : h->d_out;
+    const dim3 grid(cdiv(NFRAMES, 256), h->n_mels, n_win);
+    if (h->n_mels == NMEL)
+      hipLaunchKernelGGL(longmel_window_kernel<NMEL>, grid, dim3(256), 0, h->stream, h->d_logspec, h->stored, h->d_gmax, h->d_seek, dm);
+    else
+      hipLaunchKernelGGL(longmel_window_kernel<NMEL_MAX>, grid, dim3(256), 0, h->stream, h->d_logspec, h->stored, h->d_gmax, h->d_seek, dm);
+    WIS_HIP_CHECK(hipGetLastError());
+    if (!mel_on_device) WIS_HIP_CHECK(hipMemcpyAsync(mel_out, dm, (size_t)n_win * h->n_mels * NFRAMES * 4, hipMemcpyDeviceToHost, h->stream));
+    return WIS_OK;
+  };
+  const int rc = body();
+  if (hipStreamSynchronize(h->stream) != hipSuccess && rc == WIS_OK) { set_error("wis_longmel_window: stream synchronize failed"); return WIS_E_HIP; }
+  return rc;                                                       // the caller's seeks and buffers are free again, on every path
+}
+extern "C" void wis_longmel_destroy(wis_longmel_t* h) {
+  if (!h) return;
+  hipSetDevice(h->device);
+  if (h->stream) { hipStreamSynchronize(h->stream); hipStreamDestroy(h->stream); }
+  hipFree(h->d_logspec); hipFree(h->d_gmax); hipFree(h->d_seek); hipFree(h->d_out);
+  delete h;
 }

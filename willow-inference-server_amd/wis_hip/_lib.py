@@ -87,6 +87,12 @@ SYMBOLS = [
     ("wis_melstream_samples", _i64, [_vp]),
     ("wis_melstream_tiles_done", _i, [_vp]),
     ("wis_melstream_destroy", None, [_vp]),
+    ("wis_longmel_create", _i, [_i, _i, _vp, _i64, _i, C.POINTER(_vp)]),
+    ("wis_longmel_create_ex", _i, [_i, _i, _vp, _i64, _i, _i64, C.POINTER(_vp)]),
+    ("wis_longmel_frames", _i64, [_vp]),
+    ("wis_longmel_max", _i, [_vp, _fp]),
+    ("wis_longmel_window", _i, [_vp, C.POINTER(_i64), _i, _vp, _i]),
+    ("wis_longmel_destroy", None, [_vp]),
     ("wis_model_create", _i, [C.POINTER(Config), _vp, _sz, _i, C.POINTER(Tensor), _i, _i, C.POINTER(_vp)]),
     ("wis_model_destroy", None, [_vp]),
     ("wis_model_device_bytes", _sz, [_vp]),

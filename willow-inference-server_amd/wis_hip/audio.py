@@ -263,6 +263,78 @@ class MelStream:
             pass
 
 
+LONGMEL_MAX_SAMPLES = 230400000      # include/wis_hip.h WIS_LONGMEL_MAX_SAMPLES: 4 hours
+
+
+class LongMel:
+    """The log-mel of ONE whole recording on one GPU (C-ABI wis_longmel_*, include/wis_hip.h states the definition): openai-whisper's
+    `log_mel_spectrogram(audio, padding=N_SAMPLES)` kept in HBM, `window(seek)` its `mel[:, seek : seek + 3000]` - reflection at the
+    recording's left edge only, zeros behind its end, the floor of the RECORDING's maximum.  `frames`: content frames (samples // 160).
+    `window(seek)`: the device address of f32 [n_mels, 3000] for frame offset `seek` (this object's own buffer: valid until the next
+    `window` call or `close`; what `Whisper.generate_from_device` / `align_from_device` take); `window(seeks, to_host=True)`: a numpy
+    array [n_mels, 3000] for an int, [n, n_mels, 3000] for a list, one launch for all of them.  segment_samples: host samples per
+    upload segment (0 = the engine's; tests).  `close()` frees the device memory; using the object afterwards is a ValueError."""
+
+    def __init__(self, pcm, n_mels=N_MELS, device=0, segment_samples=0):
+        if n_mels not in MEL_BINS:
+            raise ValueError(f"Unsupported n_mels: {n_mels} (80 or 128)")
+        x = np.ascontiguousarray(pcm, np.float32).reshape(-1)
+        if x.shape[0] > LONGMEL_MAX_SAMPLES:
+            raise ValueError(f"recording of {x.shape[0]} samples is over the long-form cap of {LONGMEL_MAX_SAMPLES} (4 hours)")
+        _lib.require_gpu()
+        self.device, self.n_mels = int(device), int(n_mels)
+        self._h, self._buf = C.c_void_p(), None
+        _lib.check(_lib.load().wis_longmel_create_ex(self.device, self.n_mels, _lib.ptr(x) if x.shape[0] else None, x.shape[0], 0, int(segment_samples),
+                                                     C.byref(self._h)))
+        self.frames = int(_lib.load().wis_longmel_frames(self._h))
+
+    def window(self, seek, to_host=False):
+        if not self._h:
+            raise ValueError("LongMel is closed")
+        single = np.isscalar(seek)
+        seeks = [int(seek)] if single else [int(t) for t in seek]
+        arr = (C.c_int64 * max(len(seeks), 1))(*seeks)
+        if to_host:
+            out = np.empty((len(seeks), self.n_mels, N_FRAMES), np.float32)
+            _lib.check(_lib.load().wis_longmel_window(self._h, arr, len(seeks), _lib.ptr(out), 0))
+            return out[0] if single else out
+        if not single:
+            raise ValueError("a device window is one seek (several go to the host: to_host=True)")
+        if self._buf is None:
+            self._buf = _lib.DevBuf(self.n_mels * N_FRAMES * 4, self.device)
+        _lib.check(_lib.load().wis_longmel_window(self._h, arr, 1, self._buf.ptr, 1))
+        return self._buf.ptr.value
+
+    @property
+    def max(self):
+        """the recording's maximum log10 mel energy (never below -10): the floor of every window is this minus 8"""
+        if not self._h:
+            raise ValueError("LongMel is closed")
+        v = C.c_float()
+        _lib.check(_lib.load().wis_longmel_max(self._h, C.byref(v)))
+        return float(v.value)
+
+    def close(self):
+        h, self._h = self._h, None
+        buf, self._buf = self._buf, None
+        if buf is not None:
+            buf.free()
+        if h:
+            _lib.load().wis_longmel_destroy(h)
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 def chunk_iter(inputs):
     """22 s windows with 4 s of context each side, stepping 14 s; yields (chunk, (len, left, right))."""
     assert isinstance(inputs, np.ndarray), "chunk_iter only takes numpy array"

@@ -662,12 +662,16 @@ class Whisper:
 
     def generate_from_device(self, device, mel_device_ptr, prompt, *, beam_size=5, max_length=448, length_penalty=1, patience=1,
                              suppress_blank=True, fixed_new_tokens=0, replica=None, draft_tokens=None, draft_trajectory=None, return_trajectory=False,
-                             repetition_penalty=1, no_repeat_ngram_size=0, num_hypotheses=1, sampling_topk=1, sampling_temperature=1, sampling_seed=None):
+                             repetition_penalty=1, no_repeat_ngram_size=0, num_hypotheses=1, sampling_topk=1, sampling_temperature=1, sampling_seed=None,
+                             return_scores=False, return_no_speech_prob=False, max_initial_timestamp_index=50):
         """One utterance whose log-mel features ALREADY live in HBM on `device` (f32 [n_mels][3000] at `mel_device_ptr`, e.g. an
         audio.MelStream after finish()): WIS_IN_MEL_DEV - nothing is staged through the host.  Goes through the micro-batcher bound
         to that DEVICE: any replica of the GPU can read the features, so concurrent windows of several streaming sessions on one GPU
         coalesce into one device batch like REST requests do, whatever replica each session holds (round 4 bound a window to the
-        session's own replica: sessions pinned to different replicas of a GPU never shared a batch)."""
+        session's own replica: sessions pinned to different replicas of a GPU never shared a batch).
+        As in `generate`: a start sequence without <|notimestamps|> (`timestamp_prompt`) decodes under Whisper's timestamp rules with
+        `max_initial_timestamp_index`, `return_no_speech_prob=True` fills `no_speech_prob`, and drafts cannot be combined with either;
+        `return_scores` is accepted for symmetry (the scores are always filled)."""
         # `replica`: the replica the caller holds (a streaming session pins itself to the least-loaded one, acquire_replica: the load
         # accounting that spreads sessions over GPUs); it only has to live on the features' device
         r = replica if replica is not None else self.replica_on(device)
@@ -689,7 +693,16 @@ class Whisper:
         s_k, s_T, s_n = _check_sampling(beam_size, num_hypotheses, sampling_topk, sampling_temperature, drafted)
         if max(int(beam_size), s_n) > self.max_beam:
             raise ValueError(f"num_hypotheses {s_n} outside 1..{self.max_beam}")
-        key = _sample_key(_rep_key(key + self._draft_key(1, beam_size, draft_tokens, draft_trajectory, return_trajectory), rep_p, rep_n), s_k, s_T, s_n)
+        timestamps = timestamp_prompt(prompt, getattr(self, "special", None))
+        if timestamps and drafted:
+            raise ValueError("timestamps (a prompt without <|notimestamps|>) cannot be combined with draft_tokens / draft_trajectory")
+        if return_no_speech_prob and drafted:
+            raise ValueError("return_no_speech_prob cannot be combined with draft_tokens / draft_trajectory")
+        key = key + self._draft_key(1, beam_size, draft_tokens, draft_trajectory, return_trajectory)
+        if timestamps or return_no_speech_prob:      # (the same tail as generate's: _run_batch reads key[11:14])
+            mi = None if max_initial_timestamp_index is None else int(max_initial_timestamp_index)
+            key = (key + (None, False))[:11] + (timestamps, mi if timestamps else 50, bool(return_no_speech_prob))
+        key = _sample_key(_rep_key(key, rep_p, rep_n), s_k, s_T, s_n)
         row = (int(mel_device_ptr), [int(t) for t in prompt])
         if s_k != 0:
             row = row + ((_next_seed() if sampling_seed is None else int(sampling_seed)) & 0xFFFFFFFFFFFFFFFF,)

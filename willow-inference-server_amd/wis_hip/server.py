@@ -113,6 +113,8 @@ def create_app(models=None, settings=None, max_workers=None, sv=None):
     """sv: the speaker verifier (an object with `embed(pcm)`, e.g. wis_hip.sv.SpeakerVerifier); None = created on first use from
     `sv_model_path` when `support_sv` is set"""
     s = settings or (models.settings if models is not None else get_api_settings())
+    if getattr(s, "long_form", "chunk") not in ("chunk", "seek"):      # (a bad setting fails the start, not every request)
+        raise ValueError(f"setting long_form {s.long_form!r}: seek or chunk")
     state = {"models": models, "sv": sv}
     sv_lock = __import__("threading").Lock()
     # enough threads that a full device batch per GPU replica can be waiting in the micro-batcher at once
@@ -193,17 +195,37 @@ def create_app(models=None, settings=None, max_workers=None, sv=None):
                     raise BadRequest(f"Invalid {name} {v!r}: token ids are >= 0")
             else:
                 prompts[name] = v
+        # recordings over 30 s: long_form=seek | chunk, condition_on_previous_text=, no_speech_threshold= (absent: the settings' values); a bad value = 400
+        lf = q.get("long_form") or None
+        if lf is not None and lf not in ("seek", "chunk"):
+            raise BadRequest(f"Invalid long_form {lf!r}: seek or chunk")
+        cond = q.get("condition_on_previous_text")
+        if cond in (None, ""):
+            cond = None
+        elif cond.strip().lower() in ("1", "true", "yes", "on", "0", "false", "no", "off"):
+            cond = _as_bool(cond, True)
+        else:
+            raise BadRequest(f"Invalid condition_on_previous_text {cond!r}: true or false")
+        nst = q.get("no_speech_threshold")
+        try:
+            nst = float(nst) if nst not in (None, "") else None
+        except ValueError:
+            raise BadRequest(f"Invalid no_speech_threshold {nst!r}")
+        if nst is not None and nst != nst:
+            raise BadRequest("Invalid no_speech_threshold: not a number")
         return dict(model=model, beam_size=beam, repetition_penalty=rp, **prompts, no_repeat_ngram_size=ng, temperatures=temps, best_of=best_of,
+                    long_form=lf, condition_on_previous_text=cond, no_speech_threshold=nst,
                     detect_language=_as_bool(q.get("detect_language"), s.detect_language), force_language=q.get("force_language") or None,
                     translate=_as_bool(q.get("translate"), False), timestamps=_as_bool(q.get("timestamps"), False),
                     word_timestamps=_as_bool(q.get("word_timestamps"), False))
 
     async def run_whisper(audio_file, p):
         loop = asyncio.get_running_loop()
-        kw = {"timestamps": True} if p["timestamps"] else {}      # (segment times: one 30 s window; longer audio is a 400)
-        if p["word_timestamps"]:                                  # (word times imply segment times; no vocabulary / long audio is a 400)
+        kw = {"timestamps": True} if p["timestamps"] else {}      # (segment times; audio over 30 s is a 400 unless long_form=seek)
+        if p["word_timestamps"]:                                  # (word times imply segment times; no vocabulary is a 400, and so is audio over 30 s without long_form=seek)
             kw = {"word_timestamps": True}
-        kw.update({k: p[k] for k in ("repetition_penalty", "no_repeat_ngram_size", "temperatures", "best_of", "initial_prompt", "prefix") if p[k] is not None})      # (absent: do_whisper takes the settings' values)
+        kw.update({k: p[k] for k in ("repetition_penalty", "no_repeat_ngram_size", "temperatures", "best_of", "initial_prompt", "prefix", "long_form",
+                                         "condition_on_previous_text", "no_speech_threshold") if p[k] is not None})      # (absent: do_whisper takes the settings' values)
         return await loop.run_in_executor(pool, lambda: do_whisper(audio_file, p["model"], p["beam_size"], "transcribe", p["detect_language"],
                                                                    p["force_language"], p["translate"], models=get_models(), **kw))
 

@@ -99,6 +99,13 @@ class APISettings:
     best_of: int = 5
     compression_ratio_threshold: float = 2.4
     logprob_threshold: float = -1.0
+    # recordings over 30 s, as every request without the query parameters of the same names is served: "chunk" = the reference's fixed 22 s windows
+    # merged by longest common sequence (no timestamps, no fallback); "seek" = openai-whisper's transcribe() loop over one whole-recording log-mel
+    # (wis_hip.longform): every window decoded under the timestamp rules, the next one starting at the last closed timestamp, conditioned on the
+    # text so far (`condition_on_previous_text`), windows whose no-speech probability is above `no_speech_threshold` skipped (>= 1e30: never)
+    long_form: str = "chunk"
+    condition_on_previous_text: bool = True
+    no_speech_threshold: float = 0.6
     # --- speaker verification (`voice_auth`, support_sv): not reference fields, the reference hard-codes both paths (main.py:308-312,
     # 839).  The model directory is a Hugging Face WavLMForXVector checkpoint (or "synthetic:wavlm-base-plus-sv[:SEED]"); the speakers
     # directory holds one NAME.npy embedding per enrolled speaker (python -m wis_hip.sv enroll NAME AUDIO)

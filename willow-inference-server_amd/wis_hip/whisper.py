@@ -9,7 +9,8 @@ including the reference's behaviours: >= long_beam_size_threshold ms switches to
 find_longest_common_sequence (main.py:588-611, 677-711).
 
 `timestamps=True` decodes without <|notimestamps|> (CTranslate2 then applies Whisper's timestamp rules) and attaches
-`.segments` = [{start, end, text}] (segments_from_tokens); `text` stays free of timestamp tokens.  One 30 s window only.
+`.segments` = [{start, end, text}] (segments_from_tokens); `text` stays free of timestamp tokens.  One 30 s window - or, with
+long_form="seek", a recording of any length through openai-whisper's seek loop (wis_hip.longform) over one whole-recording log-mel.
 
 No tokenizer files exist offline (the reference loads HF WhisperProcessor from the model dir, main.py:329-334):
 prompt ids are the fixed multilingual ids; `text` is produced by an optional tokenizer
@@ -42,6 +43,7 @@ class WhisperResult(tuple):
     tokens = None
     translation_tokens = None
     segments = None
+    seek = None          # long_form="seek": one record per decoded window (longform.transcribe)
 
 
 def model_special_tokens(model):
@@ -409,8 +411,17 @@ def assemble_prompt(start, special, initial_prompt_ids=(), prefix_ids=(), n_text
 
 def do_whisper(audio_file, model, beam_size=None, task="transcribe", detect_language=False, force_language=None, translate=False,
                models=None, fixed_new_tokens=None, timestamps=False, word_timestamps=False, repetition_penalty=None, no_repeat_ngram_size=None,
-               temperatures=None, best_of=None, compression_ratio_threshold=None, logprob_threshold=None, initial_prompt=None, prefix=None):
-    """initial_prompt / prefix: openai-whisper's options of those names, each a string or a list of token ids (None: the settings' values; empty:
+               temperatures=None, best_of=None, compression_ratio_threshold=None, logprob_threshold=None, initial_prompt=None, prefix=None,
+               long_form=None, condition_on_previous_text=None, no_speech_threshold=None):
+    """long_form ("chunk" | "seek"; None: the setting, "chunk"): how a recording over 30 s is served.  "chunk": the reference's fixed windows merged by
+    longest common sequence - no timestamps, no fallback (ValueError).  "seek": openai-whisper's transcribe() loop (wis_hip.longform) over one
+    whole-recording log-mel kept on one of the model's GPUs (audio.LongMel) - timestamps, word_timestamps, the temperature fallback, initial_prompt
+    and the repetition options all apply per window; condition_on_previous_text (None: the setting, True) and no_speech_threshold (None: the setting,
+    0.6; >= 1e30: never skip) are the loop's.  Every word of word_timestamps lies inside its segment (held at the segment's bounds where the
+    alignment puts it outside).  translate=True runs the loop a second time with the translate task: unprompted, one search per window, the
+    repetition options and the skip rule applied; it carries no segments.  Recordings of up to 30 s are not affected by the option.  The result's `.seek` then holds the loop's
+    per-window record.
+    initial_prompt / prefix: openai-whisper's options of those names, each a string or a list of token ids (None: the settings' values; empty:
     off).  The decoder prompt becomes [<|startofprev|>] + prompt ids + start sequence + prefix ids (assemble_prompt; the prompt is cut from the left
     to what the engine takes, 228 tokens in all).  Every window of a long recording gets the same prompt; language detection, the translation pass and
     the word alignment stay unprompted; the repetition options and the temperature fallback combine with both options, timestamps / word_timestamps
@@ -440,6 +451,9 @@ def do_whisper(audio_file, model, beam_size=None, task="transcribe", detect_lang
                                         getattr(s, "best_of", 5) if best_of is None else best_of)
     cr_thr = getattr(s, "compression_ratio_threshold", 2.4) if compression_ratio_threshold is None else compression_ratio_threshold
     lp_thr = getattr(s, "logprob_threshold", -1.0) if logprob_threshold is None else logprob_threshold
+    long_form = getattr(s, "long_form", "chunk") if long_form is None else long_form
+    if long_form not in ("chunk", "seek"):
+        raise ValueError(f"long_form {long_form!r}: seek or chunk")
     whisper_model = models.get(model)
     special = model_special_tokens(whisper_model)
     n_mels = getattr(whisper_model, "n_mels", audio.N_MELS)
@@ -460,6 +474,12 @@ def do_whisper(audio_file, model, beam_size=None, task="transcribe", detect_lang
     audio_duration = int(pcm.shape[0] / sr * 1000)
     if audio_duration >= s.long_beam_size_threshold:
         beam_size = s.long_beam_size
+    if long_form == "seek" and audio_duration > 30 * 1000:
+        cond = getattr(s, "condition_on_previous_text", True) if condition_on_previous_text is None else bool(condition_on_previous_text)
+        nst = getattr(s, "no_speech_threshold", 0.6) if no_speech_threshold is None else no_speech_threshold
+        return _do_whisper_seek(models, model, whisper_model, special, pcm, audio_duration, beam_size, task, detect_language, force_language, translate,
+                                fixed_new_tokens, timestamps, word_timestamps, rep, temps, best_of, cr_thr, lp_thr, initial_prompt, prefix, cond,
+                                None if nst is None or nst >= 1e30 else float(nst), first_time_start)
     if timestamps and audio_duration > 30 * 1000:
         raise ValueError("timestamps are available for audio of up to 30 s (one window)")
     if temps and audio_duration > 30 * 1000:
@@ -571,4 +591,96 @@ def do_whisper(audio_file, model, beam_size=None, task="transcribe", detect_lang
     out.translation_tokens = out_translation_tokens
     out.segments = segments
     out.fallback = getattr(results[0], "fallback", None)      # temperature fallback: what the kept decode was (decode_with_fallback)
+    return out
+
+
+def _do_whisper_seek(models, model, whisper_model, special, pcm, audio_duration, beam_size, task, detect_language, force_language, translate,
+                     fixed_new_tokens, timestamps, word_timestamps, rep, temps, best_of, cr_thr, lp_thr, initial_prompt, prefix, cond, no_speech_threshold,
+                     first_time_start):
+    """do_whisper for a recording over 30 s with long_form="seek": the whole-recording log-mel on one of the model's GPUs for the length of the
+    request, longform.transcribe around generate_from_device / align_from_device."""
+    from . import longform
+    s = models.settings
+    tokenizer = models.tokenizer_for(model)
+    ip_ids = prompt_ids(getattr(s, "initial_prompt", "") if initial_prompt is None else initial_prompt, tokenizer, special, "initial_prompt")
+    px_ids = prompt_ids(getattr(s, "prefix", "") if prefix is None else prefix, tokenizer, special, "prefix")
+    if px_ids:      # (the loop always decodes under the timestamp rules, which read the generated history: a prefix is not part of it)
+        raise ValueError("prefix cannot be combined with timestamps / word_timestamps (initial_prompt can), and long_form=seek always decodes with timestamps")
+    if word_timestamps and not getattr(tokenizer, "has_vocabulary", False):
+        raise ValueError("word_timestamps need the checkpoint's tokenizer vocabulary (tokenizer.json next to the model)")
+    n_mels = getattr(whisper_model, "n_mels", audio.N_MELS)
+    n_text_ctx = int((getattr(whisper_model, "arch", None) or {}).get("n_text_ctx", 448))
+    replica = whisper_model.acquire_replica()
+    long_mel = None
+    try:
+        long_mel = audio.LongMel(pcm, n_mels=n_mels, device=replica.device)
+        language = s.language
+        if detect_language and not force_language:
+            first = np.ascontiguousarray(long_mel.window(0, to_host=True)[None])
+            lang_token, _probability = whisper_model.detect_language(ctranslate2.StorageView.from_array(first))[0][0]
+            language = lang_token.strip("<|>")
+        elif force_language:
+            language = force_language
+        if not check_language(language, special):
+            raise ValueError(f"unsupported language {language!r}")
+        start = [special.sot, special.language_token_id(language), special.translate if task == "translate" else special.transcribe]
+
+        def decode(window, prompt, t, n):
+            kw = dict(beam_size=beam_size) if t == 0 else dict(beam_size=1, num_hypotheses=n, sampling_topk=0, sampling_temperature=t)
+            r = whisper_model.generate_from_device(replica.device, window, prompt, replica=replica, fixed_new_tokens=fixed_new_tokens, return_scores=True,
+                                                   return_no_speech_prob=True, **kw, **rep)
+            return list(zip(r.sequences_ids, r.scores)), r.no_speech_prob
+
+        def on_window(window, seek, segment_size, segs):
+            text_tokens = [t for sg in segs for t in sg["tokens"] if t < special.eot]
+            if not text_tokens:
+                for sg in segs:
+                    sg["words"] = []
+                return
+            al = whisper_model.align_from_device(replica.device, window, start, [text_tokens], max(2, segment_size), replica=replica)[0]
+            timed = [dict(tokens=[t for t in sg["tokens"] if t < special.eot]) for sg in segs]
+            words_from_alignment(timed, al.alignments, al.text_token_probs, tokenizer, language, special, segment_size * longform.FRAME_S)
+            off = round(seek * longform.FRAME_S, 2)
+            # a word lies inside its segment: the alignment places a word by the cross-attention alone, the segment's bounds are the decoder's
+            # timestamp tokens, and where the two disagree the word is held at the bound (openai-whisper moves the segment's bounds to its words
+            # instead; here the segments stay what the timestamps said - monotone, inside the recording, the same with and without words)
+            for sg, tm in zip(segs, timed):
+                inside = lambda t: round(min(max(t + off, sg["start"]), sg["end"]), 2)
+                sg["words"] = [dict(w, start=inside(w["start"]), end=inside(w["end"])) for w in tm["words"]]
+        text_of = None
+        if getattr(tokenizer, "has_vocabulary", False):
+            text_of = lambda toks: tokenizer.decode([t for t in toks if t < special.eot])
+        res = longform.transcribe(long_mel, decode, start=start, special=special, initial_prompt_ids=ip_ids, n_text_ctx=n_text_ctx, temperatures=temps, best_of=best_of,
+                                  compression_ratio_threshold=None if cr_thr is None or cr_thr >= 1e30 else cr_thr,
+                                  logprob_threshold=None if lp_thr is None or lp_thr <= -1e30 else lp_thr, no_speech_threshold=no_speech_threshold,
+                                  condition_on_previous_text=cond, text_of=text_of, on_window=on_window if word_timestamps else None)
+        translation = translation_tokens = None
+        if translate:
+            # the translation pass: the same loop with the translate task - unprompted, one search per window (no fallback), the repetition
+            # options applied as to every decode of the request, the same skip rule as the transcription; it carries no segments
+            tres = longform.transcribe(long_mel, decode, start=start[:2] + [special.translate], special=special, n_text_ctx=n_text_ctx,
+                                       logprob_threshold=None if lp_thr is None or lp_thr <= -1e30 else lp_thr,
+                                       no_speech_threshold=no_speech_threshold, condition_on_previous_text=cond)
+            translation_tokens = [t for sg in tres["segments"] for t in sg["tokens"] if t < special.eot]
+            translation = tokenizer.decode(translation_tokens).strip()
+    finally:
+        if long_mel is not None:
+            long_mel.close()
+        whisper_model.release_replica(replica)
+    tokens, segments = [], []
+    for sg in res["segments"]:
+        text_tokens = [t for t in sg["tokens"] if t < special.eot]
+        tokens.extend(sg["tokens"])
+        out_sg = {"start": sg["start"], "end": sg["end"], "text": tokenizer.decode(text_tokens).strip()}
+        if word_timestamps:
+            out_sg["words"] = sg.get("words", [])
+        segments.append(out_sg)
+    text = " ".join(sg["text"] for sg in segments if sg["text"]).strip()
+    infer_time_milliseconds = (time.perf_counter() - first_time_start) * 1000
+    out = WhisperResult((language, text, infer_time_milliseconds, translation, math.floor(audio_duration / infer_time_milliseconds), audio_duration))
+    out.tokens = tokens
+    out.translation_tokens = translation_tokens
+    out.segments = segments if timestamps else None
+    out.fallback = res["fallback"] if temps else None
+    out.seek = res["windows"]
     return out
