@@ -177,7 +177,8 @@ def test_settings_default_is_the_reference_layout_and_fails_loudly(tmp_path, mon
 def test_batch_capacity_uses_the_prefill_row_count():
     """wis_generate prefills all P prompt rows (B * P <= MAX_ROWS); the batcher's capacity must use the same bound
     (96 rows since round 3: 16 utterances x beam 5)."""
-    from wis_hip.ctranslate2 import MAX_DECODER_ROWS, _capacity
+    from wis_hip.ctranslate2 import MAX_DECODER_ROWS, DecodeOptions, _capacity as capacity
+    _capacity = lambda max_batch, key: capacity(max_batch, DecodeOptions(key[0], key[1], 224))      # key: (prompt length, beam size)
     assert MAX_DECODER_ROWS == 96
     assert _capacity(32, (4, 1)) == 24 and _capacity(32, (4, 3)) == 24 and _capacity(32, (4, 5)) == 19 and _capacity(16, (4, 5)) == 16 and _capacity(8, (4, 5)) == 8
     assert _capacity(96, (1, 1)) == 96 and _capacity(16, (16, 1)) == 6

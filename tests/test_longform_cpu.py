@@ -390,30 +390,33 @@ def test_generate_from_device_timestamp_tail(monkeypatch):
     model = app.state.wis["models"]._models["large"]
     calls, keys = [], []
     inner, submit = ct2._generate_chunk, model._batcher.submit
-    monkeypatch.setattr(ct2, "_generate_chunk", lambda *a, **kw: (calls.append(kw), inner(*a, **kw))[1])
+    monkeypatch.setattr(ct2, "_generate_chunk", lambda r, mel, prompts, opts, **kw: (calls.append(opts._asdict()), inner(r, mel, prompts, opts, **kw))[1])
     model._batcher.submit = lambda key, rows, **kw: (keys.append(key), submit(key, rows, **kw))[1]
     try:
-        plain = (4, 1, 224, 1.0, 1.0, True, True, 0, _lib.WIS_IN_MEL_DEV)
+        plain = ct2.DecodeOptions(prompt_len=4, beam_size=1, max_new_tokens=224, length_penalty=1.0, patience=1.0, suppress_blank=True, suppress_default=True,
+                                  fixed_new_tokens=0, input_kind=_lib.WIS_IN_MEL_DEV, draft=None, return_trajectory=False, timestamps=False,
+                                  max_initial_timestamp_index=50, no_speech_prob=False, repetition_penalty=1.0, no_repeat_ngram_size=0, sampling_topk=0,
+                                  sampling_temperature=1.0, num_hypotheses=1)
         model.generate_from_device(0, 4096, START + [W.NO_TIMESTAMPS], beam_size=1)
         assert keys[-1] == plain                                            # <|notimestamps|>: the key and the call they always were
         model.generate_from_device(0, 4096, START, beam_size=1, return_scores=True)
-        assert keys[-1] == (3, 1, 224, 1.0, 1.0, True, True, 0, _lib.WIS_IN_MEL_DEV, None, False, True, 50, False)
+        assert keys[-1] == plain._replace(prompt_len=3, timestamps=True)
         assert calls[-1]["timestamps"] is True and calls[-1]["max_initial_timestamp_index"] == 50 and calls[-1]["no_speech_prob"] is False
         model.generate_from_device(0, 4096, START, beam_size=1, max_initial_timestamp_index=None, return_no_speech_prob=True)
-        assert keys[-1][11:] == (True, None, True) and calls[-1]["max_initial_timestamp_index"] is None and calls[-1]["no_speech_prob"] is True
+        assert keys[-1] == plain._replace(prompt_len=3, timestamps=True, max_initial_timestamp_index=None, no_speech_prob=True) and calls[-1]["max_initial_timestamp_index"] is None and calls[-1]["no_speech_prob"] is True
         model.generate_from_device(0, 4096, START + [W.NO_TIMESTAMPS], beam_size=1, return_no_speech_prob=True, max_initial_timestamp_index=7)
-        assert keys[-1][:9] == plain and keys[-1][9:] == (None, False, False, 50, True) and calls[-1]["timestamps"] is False
-        # the same tail as generate's: the repetition and sampling slots keep their places behind it
+        assert keys[-1] == plain._replace(no_speech_prob=True) and calls[-1]["timestamps"] is False
+        # the same record as generate's: the repetition and sampling fields beside the timestamp ones
         model.generate_from_device(0, 4096, [SOP, 11, 12] + START, beam_size=1, no_repeat_ngram_size=3, return_no_speech_prob=True)
-        assert keys[-1][0] == 6 and keys[-1][11:] == (True, 50, True, 1.0, 3)
+        assert keys[-1] == plain._replace(prompt_len=6, timestamps=True, no_speech_prob=True, no_repeat_ngram_size=3)
         model.generate_from_device(0, 4096, START, beam_size=1, num_hypotheses=3, sampling_topk=0, sampling_temperature=0.4, sampling_seed=1, return_no_speech_prob=True)
-        assert keys[-1][11:] == (True, 50, True, 1.0, 0, -1, 0.4, 3) and calls[-1]["num_hypotheses"] == 3
+        assert keys[-1] == plain._replace(prompt_len=3, timestamps=True, no_speech_prob=True, sampling_topk=-1, sampling_temperature=0.4, num_hypotheses=3) and calls[-1]["num_hypotheses"] == 3
         feats = ct2.StorageView.from_array(np.zeros((1, 80, 3000), np.float32))
         model.generate(feats, [START], beam_size=1, return_no_speech_prob=True)
-        assert keys[-1][9:] == (None, False, True, 50, True)                # generate's tail for the same options
+        assert keys[-1] == plain._replace(prompt_len=3, input_kind=_lib.WIS_IN_MEL_HOST, timestamps=True, no_speech_prob=True)      # generate's record for the same options
         # a prefix behind the start sequence keeps the plain search, as in generate; drafts stay refused with these options
         model.generate_from_device(0, 4096, START + [400], beam_size=1)
-        assert keys[-1] == plain and calls[-1].get("timestamps", False) is False
+        assert keys[-1] == plain and calls[-1]["timestamps"] is False
         n = len(keys)
         with pytest.raises(ValueError, match="draft"):
             model.generate_from_device(0, 4096, START, beam_size=1, draft_tokens=[400])

@@ -87,12 +87,12 @@ def fake_app(monkeypatch):
     import fake_engine_app
     app = fake_engine_app.create_app()
     model = app.state.wis["models"]._models["large"]
-    calls = []      # (prompts, P, keyword arguments) of every engine call
+    calls = []      # (prompts, P, the DecodeOptions by field name) of every engine call
     inner = ct2._generate_chunk
 
-    def spy(r, mel, prompts, P, *a, **kw):
-        calls.append(([list(p) for p in prompts], P, kw))
-        return inner(r, mel, prompts, P, *a, **kw)
+    def spy(r, mel, prompts, opts, **kw):
+        calls.append(([list(p) for p in prompts], opts.prompt_len, opts._asdict()))
+        return inner(r, mel, prompts, opts, **kw)
     monkeypatch.setattr(ct2, "_generate_chunk", spy)
     yield app, calls, model
     model.close()
@@ -203,15 +203,15 @@ def test_rest_parameters_and_400s(fake_app):
 
 # ---- the micro-batcher ------------------------------------------------------------------------------------------------------------------------
 def test_capacity_does_not_divide_by_a_long_prompt():
-    from wis_hip.ctranslate2 import MAX_DECODER_ROWS, MAX_PROMPT, SHORT_PROMPT, _capacity
+    from wis_hip.ctranslate2 import MAX_DECODER_ROWS, MAX_PROMPT, SHORT_PROMPT, DecodeOptions, _capacity as capacity
+    _capacity = lambda max_batch, key: capacity(max_batch, DecodeOptions(key[0], key[1], 224))      # key: (prompt length, beam size)
     assert (MAX_DECODER_ROWS, SHORT_PROMPT, MAX_PROMPT) == (96, 16, 228)
     # up to 16 tokens: what tests/test_loaders.py pins (rows of the merged prefill + first step)
     assert _capacity(32, (4, 1)) == 24 and _capacity(32, (4, 5)) == 19 and _capacity(16, (16, 1)) == 6 and _capacity(96, (1, 1)) == 96
     # beyond: the decode rows alone (the last prefill window shrinks with the batch)
     for P in (17, 33, 100, 228):
         assert _capacity(32, (P, 1)) == 32 and _capacity(96, (P, 1)) == 96 and _capacity(32, (P, 5)) == 19 and _capacity(16, (P, 5)) == 16 and _capacity(32, (P, 8)) == 12
-    key = (100, 1, 224, 1.0, 1.0, True, True, 0, 0) + (None, False, False, 50, False, 1.0, 0) + (0, 0.7, 5)      # a sampled decode: five rows per utterance
-    assert _capacity(32, key) == 19
+    assert capacity(32, DecodeOptions(100, 1, 224, sampling_topk=-1, sampling_temperature=0.7, num_hypotheses=5)) == 19      # a sampled decode: five rows per utterance
 
 
 def test_prompt_length_separates_device_batches_and_long_drafts_are_refused(fake_app):
@@ -227,9 +227,13 @@ def test_prompt_length_separates_device_batches_and_long_drafts_are_refused(fake
     g([PREV] + [7] * 36 + START)
     g([PREV] + [7] * 37 + START)
     g([PREV] + [9] * 36 + START)
-    assert [k[0] for k in keys] == [4, 41, 42, 41] and keys[1] == keys[3] and len({keys[0], keys[1], keys[2]}) == 3
-    assert keys[0] == (4, 1, 224, 1.0, 1.0, True, True, 0, _lib.WIS_IN_PCM_HOST)                    # today's key is what it was
-    assert [k[2] for k in keys] == [224] * 4 and g([PREV] + [7] * 223 + START)[0] is not None and keys[-1][:3] == (228, 1, 220)
+    assert [k.prompt_len for k in keys] == [4, 41, 42, 41] and keys[1] == keys[3] and len({keys[0], keys[1], keys[2]}) == 3
+    todays = ct2.DecodeOptions(prompt_len=4, beam_size=1, max_new_tokens=224, length_penalty=1.0, patience=1.0, suppress_blank=True, suppress_default=True,
+                               fixed_new_tokens=0, input_kind=_lib.WIS_IN_PCM_HOST, draft=None, return_trajectory=False, timestamps=False,
+                               max_initial_timestamp_index=50, no_speech_prob=False, repetition_penalty=1.0, no_repeat_ngram_size=0, sampling_topk=0,
+                               sampling_temperature=1.0, num_hypotheses=1)
+    assert keys[0] == todays and keys[1] == todays._replace(prompt_len=41) and keys[2] == todays._replace(prompt_len=42)      # nothing but the length differs
+    assert [k.max_new_tokens for k in keys] == [224] * 4 and g([PREV] + [7] * 223 + START)[0] is not None and keys[-1] == todays._replace(prompt_len=228, max_new_tokens=220)
     n0 = len(calls)
     with pytest.raises(ValueError, match="prompt length 229"):
         g([PREV] + [7] * 224 + START)

@@ -121,9 +121,9 @@ def fake_app(monkeypatch):
     calls = []
     inner = ct2._generate_chunk
 
-    def spy(*a, **kw):
-        calls.append(kw)
-        return inner(*a, **kw)
+    def spy(r, mel, prompts, opts, **kw):      # every engine call: its DecodeOptions by field name
+        calls.append(opts._asdict())
+        return inner(r, mel, prompts, opts, **kw)
     monkeypatch.setattr(ct2, "_generate_chunk", spy)
     yield app, calls, model
     model.close()
@@ -160,9 +160,9 @@ def test_query_parameters_reach_the_engine_call_and_bad_values_are_400(fake_app)
             n0 = len(calls)
             r = await c.post("/api/asr?model=large&translate=true&repetition_penalty=1.3", content=body, headers=hdr)
             assert r.status_code == 200 and len(calls) == n0 + 2 and all(k.get("repetition_penalty") == pytest.approx(1.3) for k in calls[n0:]), calls[n0:]
-            # ... and a request without them decodes as it always has: the engine call carries neither
+            # ... and a request without them decodes as it always has: both are off in the engine call
             r = await c.post("/api/asr?model=large", content=body, headers=hdr)
-            assert r.status_code == 200 and "repetition_penalty" not in calls[-1] and "no_repeat_ngram_size" not in calls[-1], calls[-1]
+            assert r.status_code == 200 and calls[-1]["repetition_penalty"] == 1.0 and calls[-1]["no_repeat_ngram_size"] == 0, calls[-1]
             n0 = len(calls)
             for q in ("repetition_penalty=abc", "repetition_penalty=0", "repetition_penalty=-1", "repetition_penalty=nan", "repetition_penalty=inf",
                       "no_repeat_ngram_size=-1", "no_repeat_ngram_size=1.5", "no_repeat_ngram_size=x"):
@@ -183,13 +183,13 @@ def test_settings_are_the_defaults_of_do_whisper(fake_app):
     models = app.state.wis["models"]
     pcm = np.zeros(16000, np.float32)
     do_whisper(pcm, "large", 1, models=models)
-    assert "repetition_penalty" not in calls[-1]
+    assert calls[-1]["repetition_penalty"] == 1.0 and calls[-1]["no_repeat_ngram_size"] == 0
     models.settings.repetition_penalty, models.settings.no_repeat_ngram_size = 1.2, 4
     try:
         do_whisper(pcm, "large", 1, models=models)
         assert calls[-1]["repetition_penalty"] == pytest.approx(1.2) and calls[-1]["no_repeat_ngram_size"] == 4
         do_whisper(pcm, "large", 1, models=models, repetition_penalty=1.0, no_repeat_ngram_size=0)      # the arguments win
-        assert "repetition_penalty" not in calls[-1]
+        assert calls[-1]["repetition_penalty"] == 1.0 and calls[-1]["no_repeat_ngram_size"] == 0
         do_whisper(pcm, "large", 1, models=models, timestamps=True)                                     # the timestamped pass
         assert calls[-1]["no_repeat_ngram_size"] == 4 and calls[-1]["timestamps"] is True
         with pytest.raises(ValueError):
@@ -212,7 +212,10 @@ def test_batcher_keys(fake_app):
     g()
     g(repetition_penalty=1, no_repeat_ngram_size=0)
     g(repetition_penalty=1.0)
-    todays = (4, 1, 224, 1.0, 1.0, True, True, 0, _lib.WIS_IN_PCM_HOST)
+    todays = ct2.DecodeOptions(prompt_len=4, beam_size=1, max_new_tokens=224, length_penalty=1.0, patience=1.0, suppress_blank=True, suppress_default=True,
+                               fixed_new_tokens=0, input_kind=_lib.WIS_IN_PCM_HOST, draft=None, return_trajectory=False, timestamps=False,
+                               max_initial_timestamp_index=50, no_speech_prob=False, repetition_penalty=1.0, no_repeat_ngram_size=0, sampling_topk=0,
+                               sampling_temperature=1.0, num_hypotheses=1)
     assert keys == [todays] * 3, keys
     g(repetition_penalty=1.1)
     g(repetition_penalty=1.2)
@@ -220,15 +223,15 @@ def test_batcher_keys(fake_app):
     g(repetition_penalty=1.1, no_repeat_ngram_size=3)
     g(repetition_penalty=1.1)
     assert len(set(keys[3:7])) == 4 and todays not in keys[3:] and keys[7] == keys[3], keys[3:]
-    assert all(k[:9] == todays and len(k) == 16 and k[14:] == (p, n) for k, (p, n) in zip(keys[3:7], ((1.1, 0), (1.2, 0), (1.0, 3), (1.1, 3)))), keys[3:7]
-    # with the timestamp tail and with a returned trajectory the earlier slots keep their places
+    assert all(k == todays._replace(repetition_penalty=p, no_repeat_ngram_size=n) for k, (p, n) in zip(keys[3:7], ((1.1, 0), (1.2, 0), (1.0, 3), (1.1, 3)))), keys[3:7]
+    # with the timestamp options and with a returned trajectory every other field keeps its value
     g(return_no_speech_prob=True, no_repeat_ngram_size=2)
-    assert keys[-1][11:] == (False, 50, True, 1.0, 2) and calls[-1]["no_speech_prob"] is True and calls[-1]["no_repeat_ngram_size"] == 2
+    assert keys[-1] == todays._replace(no_speech_prob=True, no_repeat_ngram_size=2) and calls[-1]["no_speech_prob"] is True and calls[-1]["no_repeat_ngram_size"] == 2
     g(return_trajectory=True, repetition_penalty=1.5)
-    assert keys[-1][9:] == (None, True, False, 50, False, 1.5, 0) and calls[-1]["want_traj"] is True and calls[-1]["repetition_penalty"] == 1.5
+    assert keys[-1] == todays._replace(return_trajectory=True, repetition_penalty=1.5) and calls[-1]["return_trajectory"] is True and calls[-1]["repetition_penalty"] == 1.5
     ts_prompt = prompt[:3]
     model.generate(pcm, [ts_prompt], beam_size=1, input_kind=_lib.WIS_IN_PCM_HOST, no_repeat_ngram_size=3)
-    assert keys[-1][11:] == (True, 50, False, 1.0, 3) and calls[-1]["timestamps"] is True
+    assert keys[-1] == todays._replace(prompt_len=3, timestamps=True, no_repeat_ngram_size=3) and calls[-1]["timestamps"] is True
     # drafts
     n0 = len(keys)
     for kw in (dict(repetition_penalty=1.1), dict(no_repeat_ngram_size=2)):
@@ -245,15 +248,15 @@ def test_batcher_keys(fake_app):
             g(**kw)
     assert len(keys) == n0
     g(draft_tokens=[400, 401])                     # a draft with the defaults is today's drafted call
-    assert len(keys[-1]) == 11 and keys[-1][10] is False
+    assert keys[-1].draft.tokens == (400, 401) and keys[-1] == todays._replace(draft=keys[-1].draft)      # nothing but the draft differs
     for kw in (dict(sampling_topk=5), dict(num_hypotheses=2)):
         with pytest.raises(NotImplementedError):
             g(**kw)
     # the device-resident form takes the options too
     model.generate_from_device(0, 4096, prompt, beam_size=1, repetition_penalty=1.1, no_repeat_ngram_size=3)
-    assert keys[-1][:9] == todays[:8] + (_lib.WIS_IN_MEL_DEV,) and keys[-1][14:] == (1.1, 3) and calls[-1]["repetition_penalty"] == 1.1
+    assert keys[-1] == todays._replace(input_kind=_lib.WIS_IN_MEL_DEV, repetition_penalty=1.1, no_repeat_ngram_size=3) and calls[-1]["repetition_penalty"] == 1.1
     model.generate_from_device(0, 4096, prompt, beam_size=1)
-    assert keys[-1] == todays[:8] + (_lib.WIS_IN_MEL_DEV,)
+    assert keys[-1] == todays._replace(input_kind=_lib.WIS_IN_MEL_DEV)
 
 
 def test_streaming_session_passes_the_options_only_without_a_draft():

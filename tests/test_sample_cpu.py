@@ -121,9 +121,9 @@ def fake_app(monkeypatch):
     calls = []
     inner = ct2._generate_chunk
 
-    def spy(*a, **kw):
-        calls.append(dict(kw, B=(int(a[1]) if kw.get("device_ptr") is not None else a[1].shape[0])))
-        return inner(*a, **kw)
+    def spy(r, mel, prompts, opts, **kw):      # every engine call: its DecodeOptions by field name, the seeds, the batch size
+        calls.append(dict(opts._asdict(), **kw, B=(int(mel) if kw.get("device_ptr") is not None else mel.shape[0])))
+        return inner(r, mel, prompts, opts, **kw)
     monkeypatch.setattr(ct2, "_generate_chunk", spy)
     yield app, calls, model
     model.close()
@@ -140,20 +140,23 @@ def test_batcher_key_capacity_and_seeds(fake_app):
     g = lambda **kw: model.generate(pcm, [prompt] * 2, input_kind=_lib.WIS_IN_PCM_HOST, **kw)
     g(beam_size=1)
     g(beam_size=1, sampling_topk=1, num_hypotheses=1, sampling_temperature=0.5)
-    todays = (4, 1, 224, 1.0, 1.0, True, True, 0, _lib.WIS_IN_PCM_HOST)
-    assert keys == [todays] * 2 and all(len(r) == 2 for rows in rows_seen for r in rows) and "sampling_topk" not in calls[-1]
+    todays = ct2.DecodeOptions(prompt_len=4, beam_size=1, max_new_tokens=224, length_penalty=1.0, patience=1.0, suppress_blank=True, suppress_default=True,
+                               fixed_new_tokens=0, input_kind=_lib.WIS_IN_PCM_HOST, draft=None, return_trajectory=False, timestamps=False,
+                               max_initial_timestamp_index=50, no_speech_prob=False, repetition_penalty=1.0, no_repeat_ngram_size=0, sampling_topk=0,
+                               sampling_temperature=1.0, num_hypotheses=1)
+    assert keys == [todays] * 2 and all(r[2] == 0 for rows in rows_seen for r in rows) and calls[-1]["sampling_topk"] == 0 and calls[-1]["num_hypotheses"] == 1
     g(beam_size=1, sampling_topk=0, sampling_temperature=0.6, num_hypotheses=5, sampling_seed=7)
-    assert keys[-1] == todays + (None, False, False, 50, False, 1.0, 0, -1, 0.6, 5) and [r[2] for r in rows_seen[-1]] == [7, 7]
+    assert keys[-1] == todays._replace(sampling_topk=-1, sampling_temperature=0.6, num_hypotheses=5) and [r[2] for r in rows_seen[-1]] == [7, 7]
     assert (calls[-1]["sampling_topk"], calls[-1]["sampling_temperature"], calls[-1]["num_hypotheses"], calls[-1]["seeds"]) == (-1, 0.6, 5, [7, 7])
     g(beam_size=1, sampling_topk=0, sampling_temperature=0.6, num_hypotheses=5, sampling_seed=[8, 9])          # another seed: the same key
     assert keys[-1] == keys[-2] and calls[-1]["seeds"] == [8, 9]
     g(beam_size=1, sampling_topk=0, sampling_temperature=0.6, num_hypotheses=5, repetition_penalty=1.1)
     g(beam_size=1, sampling_topk=0, sampling_temperature=0.8, num_hypotheses=5)
     g(beam_size=1, sampling_topk=0, sampling_temperature=0.6, num_hypotheses=4)
-    assert len(set(keys[-4:])) == 4 and keys[-3][14:] == (1.1, 0, -1, 0.6, 5)                                  # other values: other device batches
+    assert len(set(keys[-4:])) == 4 and keys[-3] == todays._replace(repetition_penalty=1.1, sampling_topk=-1, sampling_temperature=0.6, num_hypotheses=5)      # other values: other device batches
     assert len(set(calls[-1]["seeds"])) == 2                                                                 # unseeded: one draw per utterance
     g(beam_size=5, num_hypotheses=3)
-    assert keys[-1][16:] == (0, 1.0, 3) and calls[-1]["num_hypotheses"] == 3 and calls[-1]["sampling_topk"] == 0
+    assert keys[-1] == todays._replace(beam_size=5, num_hypotheses=3) and calls[-1]["num_hypotheses"] == 3 and calls[-1]["sampling_topk"] == 0
     with pytest.raises(ValueError):
         g(beam_size=1, sampling_topk=0, sampling_seed=[1, 2, 3])
     with pytest.raises(ValueError):
@@ -163,11 +166,11 @@ def test_batcher_key_capacity_and_seeds(fake_app):
                        sampling_topk=0, draft_tokens=[400, 401])
     # capacity: max(beam, n) rows per utterance
     cap = lambda key: ct2._capacity(64, key)
-    assert cap(todays) == 24 and cap(todays + (None, False, False, 50, False, 1.0, 0, -1, 0.6, 5)) == 19 and cap(todays + (None,) * 7 + (-1, 1.0, 8)) == 12
-    assert cap((4, 5) + todays[2:]) == 19 and cap((4, 5) + todays[2:] + (None,) * 7 + (0, 1.0, 3)) == 19
+    assert cap(todays) == 24 and cap(todays._replace(sampling_topk=-1, sampling_temperature=0.6, num_hypotheses=5)) == 19 and cap(todays._replace(sampling_topk=-1, num_hypotheses=8)) == 12
+    assert cap(todays._replace(beam_size=5)) == 19 and cap(todays._replace(beam_size=5, num_hypotheses=3)) == 19
     # the device-resident form
     model.generate_from_device(0, 4096, prompt, beam_size=1, sampling_topk=0, sampling_temperature=0.4, sampling_seed=3)
-    assert keys[-1][16:] == (-1, 0.4, 1) and rows_seen[-1][0][2] == 3 and calls[-1]["seeds"] == [3]
+    assert keys[-1] == todays._replace(input_kind=_lib.WIS_IN_MEL_DEV, sampling_topk=-1, sampling_temperature=0.4) and rows_seen[-1][0][2] == 3 and calls[-1]["seeds"] == [3]
 
 
 # ---- the temperature fallback --------------------------------------------------------------------------------------------------------------------------
@@ -228,14 +231,14 @@ def test_do_whisper_fallback_and_the_servers_400s(fake_app):
     models = app.state.wis["models"]
     pcm = np.zeros(16000, np.float32)
     do_whisper(pcm, "large", 1, models=models)                                           # the default: no fallback, today's single call
-    assert len(calls) == 1 and "sampling_topk" not in calls[-1]
+    assert len(calls) == 1 and calls[-1]["sampling_topk"] == 0 and calls[-1]["num_hypotheses"] == 1
     # the fake engine answers score -0.5 over 16 tokens: acceptable at once
     r = do_whisper(pcm, "large", 1, models=models, temperatures=(0, 0.4), best_of=3)
-    assert len(calls) == 2 and "sampling_topk" not in calls[-1] and r.fallback["temperature"] == 0 and r.fallback["attempts"] == 1
+    assert len(calls) == 2 and calls[-1]["sampling_topk"] == 0 and calls[-1]["num_hypotheses"] == 1 and r.fallback["temperature"] == 0 and r.fallback["attempts"] == 1
     # a log-probability threshold nothing meets: every temperature is tried, the later ones sampled with best_of samples at beam 1
     r = do_whisper(pcm, "large", 5, models=models, temperatures=(0, 0.4, 0.8), best_of=3, logprob_threshold=-0.1)
-    assert len(calls) == 5 and [(c.get("sampling_topk", 0), c.get("sampling_temperature"), c.get("num_hypotheses", 1)) for c in calls[2:]] == \
-        [(0, None, 1), (-1, 0.4, 3), (-1, 0.8, 3)]
+    assert len(calls) == 5 and [(c["sampling_topk"], c["sampling_temperature"], c["num_hypotheses"]) for c in calls[2:]] == \
+        [(0, 1.0, 1), (-1, 0.4, 3), (-1, 0.8, 3)]
     assert r.fallback["attempts"] == 3 and r.fallback["temperature"] == 0.8 and r.tokens == [400 + i for i in range(16)]
     with pytest.raises(ValueError):
         do_whisper(np.zeros(16000 * 31, np.float32), "large", 1, models=models, temperatures=(0, 0.4))

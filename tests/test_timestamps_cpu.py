@@ -98,10 +98,10 @@ def _stub_whisper(monkeypatch):
     from wis_hip import ctranslate2 as ct2
     calls = []
 
-    def fake_chunk(r, mel, prompts, P, beam, max_new, lp, patience, suppress_blank, suppress_default, fixed_new, kind, device_ptr=None, draft=None,
-                   want_traj=False, timestamps=False, max_initial_timestamp_index=50, no_speech_prob=False):
-        calls.append(dict(B=len(prompts), timestamps=timestamps, mi=max_initial_timestamp_index, nsp=no_speech_prob, draft=draft))
-        return [ct2.WhisperGenerationResult([[TB, 5, TB + 3]], [0.0], 0.25 if no_speech_prob else 0.0) for _ in prompts]
+    def fake_chunk(r, mel, prompts, opts, device_ptr=None, seeds=None):
+        calls.append(dict(B=len(prompts), timestamps=opts.timestamps, mi=opts.max_initial_timestamp_index, nsp=opts.no_speech_prob,
+                          draft=opts.draft and opts.draft.tokens))
+        return [ct2.WhisperGenerationResult([[TB, 5, TB + 3]], [0.0], 0.25 if opts.no_speech_prob else 0.0) for _ in prompts]
     monkeypatch.setattr(ct2, "_generate_chunk", fake_chunk)
 
     class R:
@@ -127,11 +127,15 @@ def test_generate_sets_timestamp_options_from_the_prompt(monkeypatch):
     assert calls[-1]["nsp"] is True and calls[-1]["timestamps"] is False and r[0].no_speech_prob == 0.25
     # the micro-batcher never mixes these in one device batch: every option set has a key of its own
     assert len(set(keys)) == len(keys) == 4
-    assert keys[0] == (4, 1, 224, 1.0, 1.0, True, True, 0, 0)            # timestamps off: the key it always was
+    todays = ct2.DecodeOptions(prompt_len=4, beam_size=1, max_new_tokens=224, length_penalty=1.0, patience=1.0, suppress_blank=True, suppress_default=True,
+                       fixed_new_tokens=0, input_kind=0, draft=None, return_trajectory=False, timestamps=False,
+                       max_initial_timestamp_index=50, no_speech_prob=False, repetition_penalty=1.0, no_repeat_ngram_size=0, sampling_topk=0,
+                       sampling_temperature=1.0, num_hypotheses=1)
+    assert keys[0] == todays            # timestamps off: the key it always was
     # a prompt with a decoder prefix after its start sequence keeps the plain search (and its drafts), as before
     prefixed = [50258, 50259, 50359, 40763]
     m.generate(feats, [prefixed], beam_size=1)
-    assert calls[-1]["timestamps"] is False and keys[-1] == (4, 1, 224, 1.0, 1.0, True, True, 0, 0)
+    assert calls[-1]["timestamps"] is False and keys[-1] == todays
     m.generate(feats, [prefixed], beam_size=1, draft_tokens=[1, 2, 3])
     assert calls[-1]["timestamps"] is False and calls[-1]["draft"] == (1, 2, 3)
     assert not ct2.timestamp_prompt([50258, 50259, 50359, 50363]) and not ct2.timestamp_prompt([50259, 50359])

@@ -30,7 +30,7 @@ def create_app():
         os.makedirs(stats_dir, exist_ok=True)
         log = open(os.path.join(stats_dir, f"worker_{os.environ.get('WIS_WORKER_INDEX', '0')}.txt"), "a", buffering=1)
 
-    def fake_chunk(r, mel, prompts, P, beam, max_new, lp, patience, suppress_blank, suppress_default, fixed_new, kind, device_ptr=None, **_kw):
+    def fake_chunk(r, mel, prompts, opts, device_ptr=None, seeds=None):
         B = int(mel) if device_ptr is not None else mel.shape[0]
         sizes.append(B)
         if log is not None:

@@ -176,7 +176,7 @@ def main():
 
     sizes = []
 
-    def fake_chunk(r, mel, prompts, P, beam, max_new, lp, patience, suppress_blank, suppress_default, fixed_new, kind, device_ptr=None, **_kw):
+    def fake_chunk(r, mel, prompts, opts, device_ptr=None, seeds=None):
         B = int(mel) if device_ptr is not None else mel.shape[0]
         sizes.append(B)
         time.sleep(0.030 + 0.004 * B)

@@ -16,6 +16,7 @@ offline).
 import ctypes as C
 import os
 import threading
+from typing import NamedTuple, Optional
 
 import numpy as np
 
@@ -110,7 +111,7 @@ def special_tokens_for(a, special=None, lang_ids=None):
     return W.special_tokens(a["n_vocab"], ov)
 
 
-def make_config(a, max_batch, max_beam, suppress_ids=None, suppress_begin=None, lang_ids=None, n_vocab=None, weight_bits=16, special=None):
+def make_config(a, max_batch, max_beam, *, suppress_ids=None, suppress_begin=None, lang_ids=None, n_vocab=None, weight_bits=16, special=None):
     """special: a weights.SpecialTokens (default: the table of the vocabulary a["n_vocab"]); the 51865 defaults are the module constants."""
     st = special if isinstance(special, W.SpecialTokens) else special_tokens_for(a, special, lang_ids)
     sup = np.asarray(st.default_suppress_ids() if suppress_ids is None else suppress_ids, np.int32)
@@ -218,66 +219,106 @@ def _last_trajectory(r, b, beam):
     return tok[:n.value].copy(), org[:n.value].copy()
 
 
-def _generate_chunk(r, mel, prompts, P, beam, max_new, lp, patience, suppress_blank, suppress_default, fixed_new, kind, device_ptr=None, draft=None, want_traj=False,
-                    timestamps=False, max_initial_timestamp_index=50, no_speech_prob=False, repetition_penalty=1.0, no_repeat_ngram_size=0,
-                    sampling_topk=0, sampling_temperature=1.0, num_hypotheses=1, seeds=None):
-    """mel: host ndarray [B, ...] - or, with device_ptr, just the batch size B of features already resident on r.device.
-    draft (one utterance): token ids of an earlier hypothesis (beam 1: wis_generate_draft) or the trajectory (tok [n][beam], org [n][beam]) of
-    an earlier beam search (wis_generate_draft_beam) - verified in multi-row passes before ordinary steps go on.
-    want_traj: every result carries `.trajectory`, what a later call takes as its draft.
-    timestamps: Whisper's timestamp rules every step (max_initial_timestamp_index None: no cap on the first timestamp);
-    no_speech_prob: every result carries P(<|nospeech|>) at <|startoftranscript|> (wis_last_no_speech_prob).
-    repetition_penalty / no_repeat_ngram_size: CTranslate2's two options against looping hypotheses (include/wis_hip.h; 1 / 0: off).
-    sampling_topk (the ENGINE's value: 0 off, -1 whole vocabulary, 2 .. 16), sampling_temperature, num_hypotheses, seeds (one uint64 per utterance):
-    random sampling and n results per utterance (wis_generate_n); every result then carries num_hypotheses sequences and scores."""
-    B = int(mel) if device_ptr is not None else mel.shape[0]
-    o = _lib.GenOpts(kind, beam, max_new, lp, patience, int(bool(suppress_blank)), int(bool(suppress_default)), int(fixed_new), 0)
-    if timestamps:
+class _Draft:
+    """The draft of one utterance: `tokens` (the ids of an earlier hypothesis, beam 1) or `trajectory` ((tok, org) int32 [steps][beam] of an earlier
+    beam search).  Compared and hashed by identity: the DecodeOptions of a drafted utterance equal no other call's, so it never shares a device
+    batch, and the arrays are never compared or hashed."""
+    __slots__ = ("tokens", "trajectory")
+
+    def __init__(self, tokens=None, trajectory=None):
+        self.tokens, self.trajectory = tokens, trajectory
+
+
+class DecodeOptions(NamedTuple):
+    """Everything but features, prompt and seed that one engine call needs - and the micro-batcher's key: two utterances share a device batch
+    exactly when their records are equal (a NamedTuple: the batcher compares keys under its lock, and tuple == runs in C).  The record is
+    canonical - an option that is off holds its default (max_initial_timestamp_index is 50 unless timestamps is on, sampling_temperature 1.0
+    unless something is sampled); Whisper._decode_options builds it from a call's arguments.
+    draft: None or a _Draft (one utterance, verified in multi-row passes before ordinary steps go on).  return_trajectory: every result carries
+    `.trajectory`, what a later call takes as its draft.  timestamps: Whisper's timestamp rules every step (max_initial_timestamp_index None: no
+    cap on the first timestamp).  no_speech_prob: every result carries P(<|nospeech|>) at <|startoftranscript|>.  repetition_penalty /
+    no_repeat_ngram_size: CTranslate2's two options against looping hypotheses (include/wis_hip.h; 1 / 0: off).  sampling_topk (the ENGINE's
+    value, as _check_sampling returns it: 0 off, -1 the whole vocabulary, 2 .. 16), sampling_temperature, num_hypotheses: random sampling and n
+    results per utterance; every result then carries num_hypotheses sequences and scores."""
+    prompt_len: int
+    beam_size: int
+    max_new_tokens: int
+    length_penalty: float = 1.0
+    patience: float = 1.0
+    suppress_blank: bool = True
+    suppress_default: bool = True
+    fixed_new_tokens: int = 0
+    input_kind: int = _lib.WIS_IN_MEL_HOST
+    draft: Optional[_Draft] = None
+    return_trajectory: bool = False
+    timestamps: bool = False
+    max_initial_timestamp_index: Optional[int] = 50
+    no_speech_prob: bool = False
+    repetition_penalty: float = 1.0
+    no_repeat_ngram_size: int = 0
+    sampling_topk: int = 0
+    sampling_temperature: float = 1.0
+    num_hypotheses: int = 1
+
+
+def _gen_opts(opts):
+    """The engine's wis_gen_opts_t of a DecodeOptions."""
+    o = _lib.GenOpts(opts.input_kind, opts.beam_size, opts.max_new_tokens, opts.length_penalty, opts.patience, int(bool(opts.suppress_blank)),
+                     int(bool(opts.suppress_default)), int(opts.fixed_new_tokens), 0)
+    if opts.timestamps:
         o.timestamps = 1
-        o.max_initial_timestamp_index = -1 if max_initial_timestamp_index is None else int(max_initial_timestamp_index)
-    o.no_speech_prob = int(bool(no_speech_prob))
-    o.repetition_penalty, o.no_repeat_ngram_size = float(repetition_penalty), int(no_repeat_ngram_size)
-    n = int(num_hypotheses)
-    multi = bool(sampling_topk) or n > 1
-    if multi:
-        o.sampling_topk, o.sampling_temperature, o.num_hypotheses = int(sampling_topk), float(sampling_temperature), n
+        o.max_initial_timestamp_index = -1 if opts.max_initial_timestamp_index is None else int(opts.max_initial_timestamp_index)
+    o.no_speech_prob = int(bool(opts.no_speech_prob))
+    o.repetition_penalty, o.no_repeat_ngram_size = float(opts.repetition_penalty), int(opts.no_repeat_ngram_size)
+    if opts.sampling_topk != 0 or opts.num_hypotheses > 1:
+        o.sampling_topk, o.sampling_temperature, o.num_hypotheses = int(opts.sampling_topk), float(opts.sampling_temperature), int(opts.num_hypotheses)
+    return o
+
+
+def _generate_chunk(r, mel, prompts, opts, *rest, device_ptr=None, seeds=None):
+    """One engine call on replica r (the caller serialises access to r).  mel: host ndarray [B, ...] - or, with device_ptr, just the batch size B
+    of features already resident on r.device.  opts: a DecodeOptions (its first nine fields may also be spelled out positionally: prompt length,
+    beam, ...).  seeds: one uint64 per utterance (sampled calls).  opts.draft goes to wis_generate_draft_beam / wis_generate_draft, a sampled or
+    n-best call to wis_generate_n, everything else to wis_generate."""
+    if rest:
+        opts = DecodeOptions(opts, *rest)
+    B = int(mel) if device_ptr is not None else mel.shape[0]
+    P, beam, n, draft = opts.prompt_len, opts.beam_size, int(opts.num_hypotheses), opts.draft
+    o = _gen_opts(opts)
     pr = np.ascontiguousarray(np.asarray(prompts, np.int32).reshape(B, P))
-    ids = np.zeros((B, n, max_new), np.int32)
+    ids = np.zeros((B, n, opts.max_new_tokens), np.int32)
     lens = np.zeros((B, n), np.int32)
     scores = np.zeros((B, n), np.float32)
     src = C.c_void_p(device_ptr) if device_ptr is not None else _lib.ptr(mel)
     i32p, lib = C.POINTER(C.c_int32), _lib.load()
+    out_ptrs = (ids.ctypes.data_as(i32p), lens.ctypes.data_as(i32p), scores.ctypes.data_as(C.POINTER(C.c_float)))
     acc = None
-    if draft is not None and len(draft) == 2 and isinstance(draft[0], np.ndarray):      # (tok, org): a beam search's trajectory
-        dt, do = (np.ascontiguousarray(np.asarray(a, np.int32)) for a in draft)
+    if draft is not None and draft.trajectory is not None:
+        dt, do = (np.ascontiguousarray(np.asarray(a, np.int32)) for a in draft.trajectory)
         if dt.ndim != 2 or dt.shape != do.shape or dt.shape[1] != beam:
             raise ValueError(f"draft trajectory must be two [steps][{beam}] arrays, got {dt.shape} / {do.shape}")
         acc = C.c_int32(0)
         _lib.check(lib.wis_generate_draft_beam(r.handle, src, pr.ctypes.data_as(i32p), P, C.byref(o), dt.ctypes.data_as(i32p), do.ctypes.data_as(i32p), int(dt.shape[0]),
-                                               ids.ctypes.data_as(i32p), lens.ctypes.data_as(i32p), scores.ctypes.data_as(C.POINTER(C.c_float)), C.byref(acc)))
-    elif draft is not None and len(draft):
-        d = np.ascontiguousarray(np.asarray(draft, np.int32))
+                                               *out_ptrs, C.byref(acc)))
+    elif draft is not None and draft.tokens:
+        d = np.ascontiguousarray(np.asarray(draft.tokens, np.int32))
         acc = C.c_int32(0)
-        _lib.check(lib.wis_generate_draft(r.handle, src, pr.ctypes.data_as(i32p), P, C.byref(o), d.ctypes.data_as(i32p), int(d.shape[0]),
-                                          ids.ctypes.data_as(i32p), lens.ctypes.data_as(i32p), scores.ctypes.data_as(C.POINTER(C.c_float)), C.byref(acc)))
-    elif multi:
+        _lib.check(lib.wis_generate_draft(r.handle, src, pr.ctypes.data_as(i32p), P, C.byref(o), d.ctypes.data_as(i32p), int(d.shape[0]), *out_ptrs, C.byref(acc)))
+    elif opts.sampling_topk != 0 or n > 1:
         sd = np.ascontiguousarray(np.asarray([0] * B if seeds is None else [int(x) & 0xFFFFFFFFFFFFFFFF for x in seeds], np.uint64))
-        _lib.check(lib.wis_generate_n(r.handle, src, B, pr.ctypes.data_as(i32p), P, C.byref(o), sd.ctypes.data_as(C.POINTER(C.c_uint64)), ids.ctypes.data_as(i32p),
-                                      lens.ctypes.data_as(i32p), scores.ctypes.data_as(C.POINTER(C.c_float))))
+        _lib.check(lib.wis_generate_n(r.handle, src, B, pr.ctypes.data_as(i32p), P, C.byref(o), sd.ctypes.data_as(C.POINTER(C.c_uint64)), *out_ptrs))
     else:
-        _lib.check(lib.wis_generate(r.handle, src, B, pr.ctypes.data_as(i32p), P, C.byref(o), ids.ctypes.data_as(i32p), lens.ctypes.data_as(i32p),
-                                    scores.ctypes.data_as(C.POINTER(C.c_float))))
+        _lib.check(lib.wis_generate(r.handle, src, B, pr.ctypes.data_as(i32p), P, C.byref(o), *out_ptrs))
     nsp = np.zeros(B, np.float32)
-    if no_speech_prob:
+    if opts.no_speech_prob:
         _lib.check(lib.wis_last_no_speech_prob(r.handle, B, nsp.ctypes.data_as(C.POINTER(C.c_float))))
     out = [WhisperGenerationResult([ids[b, j, :lens[b, j]].tolist() for j in range(n)], [float(scores[b, j]) for j in range(n)], float(nsp[b])) for b in range(B)]
     if acc is not None:
         out[0].accepted_draft_tokens = int(acc.value)      # tokens (beam 1) or search steps (beam > 1) of the draft the final decode kept
-    if want_traj:
+    if opts.return_trajectory:
         for b in range(B):
             out[b].trajectory = _last_trajectory(r, b, beam)
     return out
-
 
 
 MAX_DECODER_ROWS = 96      # csrc/kernels.hpp MAX_ROWS: decoder rows per device pass
@@ -322,17 +363,6 @@ def _check_repetition(repetition_penalty, no_repeat_ngram_size, drafted=False):
     return p, n
 
 
-def _rep_key(key, p, n):
-    """The batcher key of a call with either option on: the draft / timestamp slots padded to their fixed positions (_run_batch), then the two
-    values.  Both off: the key as it is."""
-    if p == 1.0 and n == 0:
-        return key
-    return (key + (None, False, False, 50, False)[len(key) - 9:])[:14] + (p, n)
-
-
-_KEY_TAIL = (None, False, False, 50, False, 1.0, 0)      # a plain key's slots 9 .. 15: draft, trajectory, timestamps, its cap, no_speech_prob, repetition tail
-
-
 class UnsupportedOption(ValueError, NotImplementedError):
     """A decoding option (or combination) this shim does not serve.  A ValueError like every other request error (HTTP 400 in wis_hip.server);
     also the NotImplementedError that `sampling_topk` / `num_hypotheses` raised before they existed, for the calls that stay unserved."""
@@ -368,15 +398,6 @@ def _check_sampling(beam_size, num_hypotheses, sampling_topk, sampling_temperatu
     return (0 if not on else (-1 if k == 0 else k)), (T if on else 1.0), n
 
 
-def _sample_key(key, topk, T, n):
-    """The batcher key of a sampled or n-best call: every earlier slot padded to its fixed position (_run_batch), then (top-k, temperature, n) -
-    calls with different sampling values never share a device batch; their seeds travel with the rows, so calls with different seeds do.
-    All off: the key as it is."""
-    if topk == 0 and n == 1:
-        return key
-    return (key + _KEY_TAIL[len(key) - 9:])[:16] + (topk, T, n)
-
-
 def _check_patience(beam_size, patience):
     """CTranslate2 searches until round(beam_size * patience) hypotheses have finished; the engine stores MAX_HYPOTHESES - beam_size + 1.
     A patience beyond that is a request error (it used to be clamped silently: a shorter search than CTranslate2's, other ids)."""
@@ -385,31 +406,34 @@ def _check_patience(beam_size, patience):
         raise ValueError(f"patience {patience} at beam_size {beam_size} is beyond the engine's hypothesis storage (patience <= {(MAX_HYPOTHESES - int(beam_size) + 1) / int(beam_size):.3g} at this beam)")
 
 
-def _capacity(max_batch, key):
+def _seeds(opts, sampling_seed, B):
+    """One seed per utterance of a call: `sampling_seed` (an int for the call, or one per utterance), or fresh ones; 0 when nothing is sampled."""
+    if opts.sampling_topk == 0:
+        return [0] * B
+    if sampling_seed is None:
+        return [_next_seed() for _ in range(B)]
+    seeds = [int(sampling_seed)] * B if np.isscalar(sampling_seed) else [int(x) for x in sampling_seed]
+    if len(seeds) != B:
+        raise ValueError(f"sampling_seed: {len(seeds)} seeds for {B} utterances")
+    return [sd & 0xFFFFFFFFFFFFFFFF for sd in seeds]
+
+
+def _capacity(max_batch, opts):
     """Utterances per device batch: the decoder handles <= MAX_DECODER_ROWS rows per pass - utterances x beam while decoding,
     utterances x P in the merged prefill + first step (wis_generate enforces B * P <= MAX_ROWS and B * beam <= MAX_ROWS).
     A prompt of more than SHORT_PROMPT tokens is prefilled in windows whose last one shrinks with the batch (min(16, MAX_ROWS // B) rows per
     utterance): the capacity no longer divides by P."""
-    P, beam = key[0], key[1]
-    rows = max(beam, key[18] if len(key) > 18 else 1, 1)      # decoder rows per utterance: its beams, or its num_hypotheses samples
+    P = opts.prompt_len
+    rows = max(opts.beam_size, opts.num_hypotheses, 1)      # decoder rows per utterance: its beams, or its num_hypotheses samples
     if P > SHORT_PROMPT:
         return max(1, min(max_batch, MAX_DECODER_ROWS // rows))
     return max(1, min(max_batch, MAX_DECODER_ROWS // rows, MAX_DECODER_ROWS // max(P, 1)))
 
 
-def _run_batch(replica, key, rows):
-    P, beam, max_new, lp, patience, suppress_blank, suppress_default, fixed_new, kind = key[:9]
-    draft = key[9] if len(key) > 9 else None          # (a drafted utterance has a key of its own: it never shares a device batch)
-    want_traj = bool(key[10]) if len(key) > 10 else False
-    ts, mi, nsp = key[11:14] if len(key) > 11 else (False, 50, False)      # Whisper.generate's timestamp tail
-    tsk = dict(timestamps=ts, max_initial_timestamp_index=mi, no_speech_prob=nsp) if len(key) > 11 else {}
-    if len(key) > 14:      # ... and its repetition tail
-        tsk.update(repetition_penalty=key[14], no_repeat_ngram_size=key[15])
-    if len(key) > 16:      # ... and its sampling tail; the rows then carry their seeds
-        tsk.update(sampling_topk=key[16], sampling_temperature=key[17], num_hypotheses=key[18], seeds=[(r[2] if len(r) > 2 else 0) for r in rows])
-    dr = (draft[1] if draft and len(rows) == 1 else None)
-    prompts = [r[1] for r in rows]
-    if kind == _lib.WIS_IN_MEL_DEV:
+def _run_batch(replica, opts, rows):
+    """One device batch: rows = [(features, prompt, seed)] of utterances whose DecodeOptions are equal (seed 0 when nothing is sampled)."""
+    prompts, seeds = [r[1] for r in rows], [r[2] for r in rows]
+    if opts.input_kind == _lib.WIS_IN_MEL_DEV:
         # features that already live in this replica's HBM (streaming sessions: audio.MelStream.finish): one utterance goes in
         # by pointer, several are gathered device-to-device into the replica's staging block - nothing visits the host
         with replica.lock:
@@ -423,12 +447,10 @@ def _run_batch(replica, key, rows):
                 for i, src in enumerate(r[0] for r in rows):
                     _lib.check(lib.wis_dev_copy_peer(replica.device, C.c_void_p(replica.stage.ptr.value + i * mb), replica.device, C.c_void_p(int(src)), mb))
                 ptr = replica.stage.ptr.value
-            return _generate_chunk(replica, len(rows), prompts, P, beam, max_new, lp, patience, suppress_blank, suppress_default, fixed_new, kind, device_ptr=ptr,
-                                   draft=dr, want_traj=want_traj, **tsk)
+            return _generate_chunk(replica, len(rows), prompts, opts, device_ptr=ptr, seeds=seeds)
     mel = np.ascontiguousarray(np.stack([r[0] for r in rows]))
     with replica.lock:
-        return _generate_chunk(replica, mel, prompts, P, beam, max_new, lp, patience, suppress_blank, suppress_default, fixed_new, kind,
-                               draft=dr, want_traj=want_traj, **tsk)
+        return _generate_chunk(replica, mel, prompts, opts, seeds=seeds)
 
 
 class Whisper:
@@ -476,7 +498,7 @@ class Whisper:
         self.max_batch, self.max_beam = max_batch, max_beam
         self._pick = threading.Lock()
         # concurrent generate() calls coalesce into device batches, one worker per GPU replica (wis_hip/batching.py)
-        self._batcher = MicroBatcher(self._replicas, _run_batch, lambda key: _capacity(max_batch, key))
+        self._batcher = MicroBatcher(self._replicas, _run_batch, lambda opts: _capacity(max_batch, opts))
 
     @classmethod
     def from_handles(cls, handles, arch, max_batch=8, max_beam=5, decode_config=None):
@@ -490,7 +512,7 @@ class Whisper:
         self._set_alignment_heads(self.decode_config.get("alignment_heads"))
         self.max_batch, self.max_beam = max_batch, max_beam
         self._pick = threading.Lock()
-        self._batcher = MicroBatcher(self._replicas, _run_batch, lambda key: _capacity(max_batch, key))
+        self._batcher = MicroBatcher(self._replicas, _run_batch, lambda opts: _capacity(max_batch, opts))
         return self
 
     @staticmethod
@@ -574,19 +596,33 @@ class Whisper:
         search it returns the n best finished hypotheses, best first.  `sampling_seed` (an extension of this shim): an int for the call or one per
         utterance; None draws from os.urandom, or from a deterministic counter after `ctranslate2.set_random_seed`.  The same seed gives the same
         samples, whatever else shares the device batch."""
+        opts, mel = self._decode_options(features, prompts, input_kind=input_kind, beam_size=beam_size, patience=patience, num_hypotheses=num_hypotheses,
+                                         length_penalty=length_penalty, repetition_penalty=repetition_penalty, no_repeat_ngram_size=no_repeat_ngram_size,
+                                         max_length=max_length, return_no_speech_prob=return_no_speech_prob, max_initial_timestamp_index=max_initial_timestamp_index,
+                                         suppress_blank=suppress_blank, suppress_default=list(suppress_tokens) == [-1], sampling_topk=sampling_topk,
+                                         sampling_temperature=sampling_temperature, fixed_new_tokens=fixed_new_tokens, draft_tokens=draft_tokens,
+                                         draft_trajectory=draft_trajectory, return_trajectory=return_trajectory)
+        seeds = _seeds(opts, sampling_seed, len(prompts))
+        return self._batcher.submit(opts, [(np.ascontiguousarray(mel[b]), [int(t) for t in prompts[b]], seeds[b]) for b in range(len(prompts))])
+
+    def _decode_options(self, features, prompts, *, input_kind, beam_size, patience, num_hypotheses, length_penalty, repetition_penalty, no_repeat_ngram_size,
+                        max_length, return_no_speech_prob, max_initial_timestamp_index, suppress_blank, suppress_default, sampling_topk, sampling_temperature,
+                        fixed_new_tokens, draft_tokens, draft_trajectory, return_trajectory):
+        """Every check of a decode call, for `generate` (features: host arrays, one prompt each) and `generate_from_device` (features None: ONE
+        utterance already on the device) -> (its DecodeOptions, the checked host features or None).  The engine's capacity limits are request
+        errors (ValueError -> HTTP 400 in wis_hip.server), not internal ones."""
         drafted = bool(draft_tokens is not None and len(draft_tokens) or draft_trajectory is not None and len(draft_trajectory[0]))
         s_k, s_T, s_n = _check_sampling(beam_size, num_hypotheses, sampling_topk, sampling_temperature, drafted)
         if max(int(beam_size), s_n) > self.max_beam:
             raise ValueError(f"num_hypotheses {s_n} outside 1..{self.max_beam} (setting max_beam: decoder rows per utterance)")
         rep_p, rep_n = _check_repetition(repetition_penalty, no_repeat_ngram_size, drafted)
-        mel = self._features(features, input_kind)
-        B = mel.shape[0]
+        mel = None if features is None else self._features(features, input_kind)
+        B = 1 if mel is None else mel.shape[0]
         if len(prompts) != B:
             raise ValueError("one prompt per batch item")
         P = len(prompts[0])
         if any(len(p) != P for p in prompts):
             raise ValueError("all prompts must have the same length")
-        # the engine's capacity limits are request errors (ValueError -> HTTP 400 in wis_hip.server), not internal ones
         if not 1 <= int(beam_size) <= self.max_beam:
             raise ValueError(f"beam_size {beam_size} outside 1..{self.max_beam} (setting max_beam; engine ceiling {MAX_BEAM})")
         max_prompt = min(MAX_PROMPT, int((getattr(self, "arch", None) or {}).get("n_text_ctx", 448)) // 2 + 4)
@@ -599,44 +635,22 @@ class Whisper:
         timestamps = any(ts_rows)
         if timestamps and not all(ts_rows):
             raise ValueError("prompts of one call must all ask for timestamps (a start sequence without <|notimestamps|>) or none")
-        if timestamps and (draft_tokens is not None and len(draft_tokens) or draft_trajectory is not None and len(draft_trajectory[0])):
+        if timestamps and drafted:
             raise ValueError("timestamps (a prompt without <|notimestamps|>) cannot be combined with draft_tokens / draft_trajectory")
-        if return_no_speech_prob and (draft_tokens is not None and len(draft_tokens) or draft_trajectory is not None and len(draft_trajectory[0])):
+        if return_no_speech_prob and drafted:
             raise ValueError("return_no_speech_prob cannot be combined with draft_tokens / draft_trajectory")
-        max_new = min(max_length // 2, max_length - P)
-        key = (P, int(beam_size), max_new, float(length_penalty), float(patience), bool(suppress_blank), list(suppress_tokens) == [-1],
-               int(fixed_new_tokens), int(input_kind))
-        key = key + self._draft_key(B, beam_size, draft_tokens, draft_trajectory, return_trajectory)
-        if timestamps or return_no_speech_prob:      # (the tail keeps the draft slots at fixed positions: _run_batch reads key[11:14])
-            mi = None if max_initial_timestamp_index is None else int(max_initial_timestamp_index)
-            key = (key + (None, False))[:11] + (timestamps, mi if timestamps else 50, bool(return_no_speech_prob))
-        key = _sample_key(_rep_key(key, rep_p, rep_n), s_k, s_T, s_n)
-        rows = [(np.ascontiguousarray(mel[b]), [int(t) for t in prompts[b]]) for b in range(B)]
-        if s_k != 0:
-            if sampling_seed is None:
-                seeds = [_next_seed() for _ in range(B)]
-            elif np.isscalar(sampling_seed):
-                seeds = [int(sampling_seed)] * B
-            else:
-                seeds = [int(x) for x in sampling_seed]
-                if len(seeds) != B:
-                    raise ValueError(f"sampling_seed: {len(seeds)} seeds for {B} utterances")
-            rows = [r + (sd & 0xFFFFFFFFFFFFFFFF,) for r, sd in zip(rows, seeds)]
-        return self._batcher.submit(key, rows)
-
-    @staticmethod
-    def _draft_key(B, beam_size, draft_tokens, draft_trajectory, return_trajectory):
-        """The batcher-key tail of a drafted / trajectory-returning utterance: a draft makes the key unique (it never shares a device batch)."""
-        d = None
+        draft = None      # (a draft for several utterances, or of another beam size, cannot be followed: a plain call)
         if B == 1 and int(beam_size) == 1 and draft_tokens is not None and len(draft_tokens):
-            d = (object(), tuple(int(t) for t in draft_tokens))
+            draft = _Draft(tokens=tuple(int(t) for t in draft_tokens))
         elif B == 1 and int(beam_size) > 1 and draft_trajectory is not None and len(draft_trajectory[0]):
             tok, org = (np.ascontiguousarray(np.asarray(a, np.int32)) for a in draft_trajectory)
-            if tok.ndim == 2 and tok.shape[1] == int(beam_size) and tok.shape == org.shape:      # (a draft of another beam size cannot be followed: plain call)
-                d = (object(), (tok, org))
-        if d is None and not return_trajectory:
-            return ()
-        return (d, bool(return_trajectory))
+            if tok.ndim == 2 and tok.shape[1] == int(beam_size) and tok.shape == org.shape:
+                draft = _Draft(trajectory=(tok, org))
+        mi = None if max_initial_timestamp_index is None else int(max_initial_timestamp_index)
+        opts = DecodeOptions(P, int(beam_size), min(max_length // 2, max_length - P), float(length_penalty), float(patience), bool(suppress_blank),
+                             bool(suppress_default), int(fixed_new_tokens), int(input_kind), draft, bool(return_trajectory), timestamps,
+                             mi if timestamps else 50, bool(return_no_speech_prob), rep_p, rep_n, s_k, s_T, s_n)
+        return opts, mel
 
     def load(self, device=None):
         """(utterances queued, device batches running[, on `device`]) in this model's micro-batcher"""
@@ -677,40 +691,18 @@ class Whisper:
         r = replica if replica is not None else self.replica_on(device)
         if r.device != device:
             raise ValueError(f"replica lives on device {r.device}, the features on {device}")
-        P = len(prompt)
-        if not 1 <= P <= MAX_PROMPT:
-            raise ValueError(f"prompt length {P} outside 1..{MAX_PROMPT}")
-        if P > SHORT_PROMPT and (draft_tokens is not None and len(draft_tokens) or draft_trajectory is not None and len(draft_trajectory[0])):
-            raise ValueError(f"a prompt of more than {SHORT_PROMPT} tokens cannot be combined with draft_tokens / draft_trajectory")
-        max_new = min(max_length // 2, max_length - P)
-        if not 1 <= int(beam_size) <= self.max_beam:
-            raise ValueError(f"beam_size {beam_size} outside 1..{self.max_beam}")
-        key = (P, int(beam_size), max_new, float(length_penalty), float(patience), bool(suppress_blank), True, int(fixed_new_tokens),
-               int(_lib.WIS_IN_MEL_DEV))
-        _check_patience(beam_size, patience)
-        drafted = bool(draft_tokens is not None and len(draft_tokens) or draft_trajectory is not None and len(draft_trajectory[0]))
-        rep_p, rep_n = _check_repetition(repetition_penalty, no_repeat_ngram_size, drafted)
-        s_k, s_T, s_n = _check_sampling(beam_size, num_hypotheses, sampling_topk, sampling_temperature, drafted)
-        if max(int(beam_size), s_n) > self.max_beam:
-            raise ValueError(f"num_hypotheses {s_n} outside 1..{self.max_beam}")
-        timestamps = timestamp_prompt(prompt, getattr(self, "special", None))
-        if timestamps and drafted:
-            raise ValueError("timestamps (a prompt without <|notimestamps|>) cannot be combined with draft_tokens / draft_trajectory")
-        if return_no_speech_prob and drafted:
-            raise ValueError("return_no_speech_prob cannot be combined with draft_tokens / draft_trajectory")
-        key = key + self._draft_key(1, beam_size, draft_tokens, draft_trajectory, return_trajectory)
-        if timestamps or return_no_speech_prob:      # (the same tail as generate's: _run_batch reads key[11:14])
-            mi = None if max_initial_timestamp_index is None else int(max_initial_timestamp_index)
-            key = (key + (None, False))[:11] + (timestamps, mi if timestamps else 50, bool(return_no_speech_prob))
-        key = _sample_key(_rep_key(key, rep_p, rep_n), s_k, s_T, s_n)
-        row = (int(mel_device_ptr), [int(t) for t in prompt])
-        if s_k != 0:
-            row = row + ((_next_seed() if sampling_seed is None else int(sampling_seed)) & 0xFFFFFFFFFFFFFFFF,)
-        return self._batcher.submit(key, [row], affinity=("device", device))[0]
+        opts, _ = self._decode_options(None, [prompt], input_kind=_lib.WIS_IN_MEL_DEV, beam_size=beam_size, patience=patience,
+                                       num_hypotheses=num_hypotheses, length_penalty=length_penalty, repetition_penalty=repetition_penalty,
+                                       no_repeat_ngram_size=no_repeat_ngram_size, max_length=max_length, return_no_speech_prob=return_no_speech_prob,
+                                       max_initial_timestamp_index=max_initial_timestamp_index, suppress_blank=suppress_blank, suppress_default=True,
+                                       sampling_topk=sampling_topk, sampling_temperature=sampling_temperature, fixed_new_tokens=fixed_new_tokens,
+                                       draft_tokens=draft_tokens, draft_trajectory=draft_trajectory, return_trajectory=return_trajectory)
+        row = (int(mel_device_ptr), [int(t) for t in prompt], _seeds(opts, sampling_seed, 1)[0])
+        return self._batcher.submit(opts, [row], affinity=("device", device))[0]
 
     def _generate_chunk(self, r, mel, prompts, P, beam, max_new, lp, patience, suppress_blank, suppress_default, fixed_new, kind):
         """One `wis_generate` call on replica r (the caller serialises access to r)."""
-        return _generate_chunk(r, mel, prompts, P, beam, max_new, lp, patience, suppress_blank, suppress_default, fixed_new, kind)
+        return _generate_chunk(r, mel, prompts, DecodeOptions(P, beam, max_new, lp, patience, suppress_blank, suppress_default, fixed_new, kind))
 
     def _set_alignment_heads(self, heads):
         """[[layer, head], ...] from the checkpoint (config.json / generation_config.json); None or empty: every head of the upper
@@ -733,14 +725,14 @@ class Whisper:
         takes them).  `features` on the device: `StorageView`s are host arrays in this shim; a device
         pointer goes through `align_from_device`."""
         mel = self._features(features, input_kind)
-        return self._align(mel, _lib.ptr, input_kind, mel.shape[0], start_sequence, text_tokens, num_frames, median_filter_width)
+        return self._align(mel, _lib.ptr, input_kind, mel.shape[0], start_sequence, text_tokens, num_frames, width=median_filter_width)
 
     def align_from_device(self, device, mel_device_ptr, start_sequence, text_tokens, num_frames, *, median_filter_width=7, replica=None):
         """`align` on one [n_mels][3000] fp32 window already in `device`'s memory (what generate_from_device takes)."""
         r = replica or self.replica_on(device)
-        return self._align(None, None, _lib.WIS_IN_MEL_DEV, 1, start_sequence, text_tokens, num_frames, median_filter_width, dev=(r, mel_device_ptr))
+        return self._align(None, None, _lib.WIS_IN_MEL_DEV, 1, start_sequence, text_tokens, num_frames, width=median_filter_width, dev=(r, mel_device_ptr))
 
-    def _align(self, mel, to_ptr, kind, B, start_sequence, text_tokens, num_frames, width, dev=None):
+    def _align(self, mel, to_ptr, kind, B, start_sequence, text_tokens, num_frames, *, width, dev=None):
         if B < 1 or len(text_tokens) != B:
             raise ValueError(f"align: {len(text_tokens)} token lists for a batch of {B}")
         nf = [int(num_frames)] * B if np.isscalar(num_frames) else [int(x) for x in num_frames]

@@ -21,6 +21,7 @@ import math
 import os
 import threading
 import time
+from types import SimpleNamespace
 
 import numpy as np
 
@@ -409,6 +410,55 @@ def assemble_prompt(start, special, initial_prompt_ids=(), prefix_ids=(), n_text
     return [special.startofprev] + initial_prompt_ids[-keep:] + list(start) + prefix_ids
 
 
+def _threshold(value, sign=1):
+    """A threshold of the temperature fallback / the seek loop as they take it: None when it is off (None, or >= 1e30; sign -1: <= -1e30)."""
+    return None if value is None or sign * value >= 1e30 else value
+
+
+def _n_text_ctx(whisper_model):
+    return int((getattr(whisper_model, "arch", None) or {}).get("n_text_ctx", 448))
+
+
+def _request_prompt_ids(q, tokenizer, special, seek=False):
+    """(initial_prompt ids, prefix ids) of a request, and its two refusals.  seek: the loop always decodes under the timestamp rules."""
+    ip_ids = prompt_ids(q.initial_prompt, tokenizer, special, "initial_prompt")
+    px_ids = prompt_ids(q.prefix, tokenizer, special, "prefix")
+    if px_ids and (q.timestamps or seek):
+        # text behind the start sequence makes the prompt a plain-search prompt for the engine (ctranslate2.timestamp_prompt): its timestamp rules
+        # read the GENERATED history, which a prefix is not part of - refused rather than decoded without the rules
+        raise ValueError("prefix cannot be combined with timestamps / word_timestamps (initial_prompt can)"
+                         + (", and long_form=seek always decodes with timestamps" if seek else ""))
+    if q.word_timestamps and not getattr(tokenizer, "has_vocabulary", False):
+        raise ValueError("word_timestamps need the checkpoint's tokenizer vocabulary (tokenizer.json next to the model)")
+    return ip_ids, px_ids
+
+
+def _request_language(q, settings, special, detect):
+    """The request's language: detected (detect() -> detect_language's result for the first window), forced, or the setting; one of the model's."""
+    language = settings.language
+    if q.detect_language and not q.force_language:
+        lang_token, _probability = detect()[0][0]
+        language = lang_token.strip("<|>")
+    elif q.force_language:
+        language = q.force_language
+    if not check_language(language, special):
+        raise ValueError(f"unsupported language {language!r}")
+    return language
+
+
+def _search(q, t, n):
+    """generate's search arguments at temperature t of the fallback: the search at the request's beam size at 0, n samples at beam 1 otherwise."""
+    return dict(beam_size=q.beam_size) if t == 0 else dict(beam_size=1, num_hypotheses=n, sampling_topk=0, sampling_temperature=t)
+
+
+def _text_of(tokenizer, below):
+    """tokens -> the text whose compression ratio the fallback judges (ids from `below` up dropped); None without a vocabulary: no text to
+    compress, the log-probability threshold alone decides."""
+    if not getattr(tokenizer, "has_vocabulary", False):
+        return None
+    return lambda toks: tokenizer.decode([t for t in toks if t < below])
+
+
 def do_whisper(audio_file, model, beam_size=None, task="transcribe", detect_language=False, force_language=None, translate=False,
                models=None, fixed_new_tokens=None, timestamps=False, word_timestamps=False, repetition_penalty=None, no_repeat_ngram_size=None,
                temperatures=None, best_of=None, compression_ratio_threshold=None, logprob_threshold=None, initial_prompt=None, prefix=None,
@@ -439,24 +489,25 @@ def do_whisper(audio_file, model, beam_size=None, task="transcribe", detect_lang
     `words: [{word, start, end, probability}]`, grouped as openai-whisper's split_to_word_tokens + merge_punctuations group them.
     Out of scope: the pause / median-duration heuristics of openai-whisper's add_word_timestamps, audio over 30 s, and `translate`
     (the translation pass carries no words).  A model without a tokenizer vocabulary raises ValueError."""
-    timestamps = timestamps or word_timestamps
     models = models or default_models()
     s = models.settings
-    if fixed_new_tokens is None:
-        fixed_new_tokens = s.fixed_new_tokens
-    beam_size = s.beam_size if beam_size is None else beam_size
-    rep = dict(repetition_penalty=getattr(s, "repetition_penalty", 1.0) if repetition_penalty is None else repetition_penalty,
-               no_repeat_ngram_size=getattr(s, "no_repeat_ngram_size", 0) if no_repeat_ngram_size is None else no_repeat_ngram_size)
-    temps, best_of = parse_temperatures(getattr(s, "temperatures", ()) if temperatures is None else temperatures,
-                                        getattr(s, "best_of", 5) if best_of is None else best_of)
-    cr_thr = getattr(s, "compression_ratio_threshold", 2.4) if compression_ratio_threshold is None else compression_ratio_threshold
-    lp_thr = getattr(s, "logprob_threshold", -1.0) if logprob_threshold is None else logprob_threshold
-    long_form = getattr(s, "long_form", "chunk") if long_form is None else long_form
-    if long_form not in ("chunk", "seek"):
-        raise ValueError(f"long_form {long_form!r}: seek or chunk")
+    opt = lambda value, name, default: getattr(s, name, default) if value is None else value      # None means the setting
+    temps, best_of = parse_temperatures(opt(temperatures, "temperatures", ()), opt(best_of, "best_of", 5))
+    q = SimpleNamespace(      # the request, resolved once: what the 30 s path and _do_whisper_seek both read
+        task=task, detect_language=detect_language, force_language=force_language, translate=translate, timestamps=timestamps or word_timestamps, word_timestamps=word_timestamps,
+        beam_size=s.beam_size if beam_size is None else beam_size, fixed_new_tokens=s.fixed_new_tokens if fixed_new_tokens is None else fixed_new_tokens,
+        rep=dict(repetition_penalty=opt(repetition_penalty, "repetition_penalty", 1.0), no_repeat_ngram_size=opt(no_repeat_ngram_size, "no_repeat_ngram_size", 0)),
+        temps=temps, best_of=best_of,
+        compression_ratio_threshold=_threshold(opt(compression_ratio_threshold, "compression_ratio_threshold", 2.4)),
+        logprob_threshold=_threshold(opt(logprob_threshold, "logprob_threshold", -1.0), -1),
+        long_form=opt(long_form, "long_form", "chunk"), condition_on_previous_text=bool(opt(condition_on_previous_text, "condition_on_previous_text", True)),
+        no_speech_threshold=_threshold(opt(no_speech_threshold, "no_speech_threshold", 0.6)),
+        initial_prompt=opt(initial_prompt, "initial_prompt", ""), prefix=opt(prefix, "prefix", ""))
+    if q.long_form not in ("chunk", "seek"):
+        raise ValueError(f"long_form {q.long_form!r}: seek or chunk")
+    timestamps, rep, fixed_new_tokens = q.timestamps, q.rep, q.fixed_new_tokens
     whisper_model = models.get(model)
     special = model_special_tokens(whisper_model)
-    n_mels = getattr(whisper_model, "n_mels", audio.N_MELS)
     first_time_start = time.perf_counter()
 
     # STEP 1 — load audio and extract features
@@ -473,13 +524,9 @@ def do_whisper(audio_file, model, beam_size=None, task="transcribe", detect_lang
         raise InvalidAudio("empty audio")
     audio_duration = int(pcm.shape[0] / sr * 1000)
     if audio_duration >= s.long_beam_size_threshold:
-        beam_size = s.long_beam_size
-    if long_form == "seek" and audio_duration > 30 * 1000:
-        cond = getattr(s, "condition_on_previous_text", True) if condition_on_previous_text is None else bool(condition_on_previous_text)
-        nst = getattr(s, "no_speech_threshold", 0.6) if no_speech_threshold is None else no_speech_threshold
-        return _do_whisper_seek(models, model, whisper_model, special, pcm, audio_duration, beam_size, task, detect_language, force_language, translate,
-                                fixed_new_tokens, timestamps, word_timestamps, rep, temps, best_of, cr_thr, lp_thr, initial_prompt, prefix, cond,
-                                None if nst is None or nst >= 1e30 else float(nst), first_time_start)
+        q.beam_size = s.long_beam_size
+    if q.long_form == "seek" and audio_duration > 30 * 1000:
+        return _do_whisper_seek(q, models, model, whisper_model, pcm, audio_duration, first_time_start)
     if timestamps and audio_duration > 30 * 1000:
         raise ValueError("timestamps are available for audio of up to 30 s (one window)")
     if temps and audio_duration > 30 * 1000:
@@ -502,32 +549,17 @@ def do_whisper(audio_file, model, beam_size=None, task="transcribe", detect_lang
         # the reference's two-step form (main.py:606-614, 685): features to the host, then StorageView.from_array
         # (on one of the model's own GPUs - never on a device the server was not configured to use)
         dev = whisper_model._replicas[0].device if getattr(whisper_model, "_replicas", None) else None
-        features, kind = audio.log_mel_spectrogram(windows, n_mels=n_mels, device=dev).numpy(), ctranslate2._lib.WIS_IN_MEL_HOST
+        features, kind = audio.log_mel_spectrogram(windows, n_mels=getattr(whisper_model, "n_mels", audio.N_MELS), device=dev).numpy(), ctranslate2._lib.WIS_IN_MEL_HOST
     total_chunk_count = features.shape[0]
     tokenizer = models.tokenizer_for(model)
-    ip_ids = prompt_ids(getattr(s, "initial_prompt", "") if initial_prompt is None else initial_prompt, tokenizer, special, "initial_prompt")
-    px_ids = prompt_ids(getattr(s, "prefix", "") if prefix is None else prefix, tokenizer, special, "prefix")
-    if timestamps and px_ids:
-        # text behind the start sequence makes the prompt a plain-search prompt for the engine (ctranslate2.timestamp_prompt): its timestamp rules
-        # read the GENERATED history, which a prefix is not part of - refused rather than decoded without the rules
-        raise ValueError("prefix cannot be combined with timestamps / word_timestamps (initial_prompt can)")
-    if word_timestamps and not getattr(tokenizer, "has_vocabulary", False):
-        raise ValueError("word_timestamps need the checkpoint's tokenizer vocabulary (tokenizer.json next to the model)")
+    ip_ids, px_ids = _request_prompt_ids(q, tokenizer, special)
 
     # STEP 2 — language
-    language = s.language
-    if detect_language and not force_language:
-        results = whisper_model.detect_language(ctranslate2.StorageView.from_array(np.ascontiguousarray(features[0:1])), input_kind=kind)
-        lang_token, _probability = results[0][0]
-        language = lang_token.strip("<|>")
-    elif force_language:
-        language = force_language
-    if not check_language(language, special):
-        raise ValueError(f"unsupported language {language!r}")
+    language = _request_language(q, s, special, lambda: whisper_model.detect_language(
+        ctranslate2.StorageView.from_array(np.ascontiguousarray(features[0:1])), input_kind=kind))
     task_id = special.translate if task == "translate" else special.transcribe
     start = [special.sot, special.language_token_id(language), task_id] + ([] if timestamps else [special.notimestamps])
-    prompt = assemble_prompt(start, special, ip_ids, px_ids,
-                             int((getattr(whisper_model, "arch", None) or {}).get("n_text_ctx", 448)))
+    prompt = assemble_prompt(start, special, ip_ids, px_ids, _n_text_ctx(whisper_model))
 
     # STEP 3 — run the model, `concurrent_gpu_chunks` windows per generate call
     results = []
@@ -535,21 +567,14 @@ def do_whisper(audio_file, model, beam_size=None, task="transcribe", detect_lang
         feats = ctranslate2.StorageView.from_array(np.ascontiguousarray(features[0:1]))
 
         def decode(t, n):
-            if t == 0:
-                r = whisper_model.generate(feats, [prompt], beam_size=beam_size, return_scores=True, fixed_new_tokens=fixed_new_tokens, input_kind=kind, **rep)[0]
-            else:
-                r = whisper_model.generate(feats, [prompt], beam_size=1, num_hypotheses=n, sampling_topk=0, sampling_temperature=t, return_scores=True,
-                                           fixed_new_tokens=fixed_new_tokens, input_kind=kind, **rep)[0]
+            r = whisper_model.generate(feats, [prompt], return_scores=True, fixed_new_tokens=fixed_new_tokens, input_kind=kind, **_search(q, t, n), **rep)[0]
             return list(zip(r.sequences_ids, r.scores))
-        text_of = None
-        if getattr(tokenizer, "has_vocabulary", False):      # (no vocabulary: no text to compress - the log-probability threshold alone decides)
-            text_of = lambda toks: tokenizer.decode([t for t in toks if t < special.timestamp_begin])
-        fb = decode_with_fallback(decode, temps, best_of, None if cr_thr is None or cr_thr >= 1e30 else cr_thr, None if lp_thr is None or lp_thr <= -1e30 else lp_thr, text_of)
+        fb = decode_with_fallback(decode, temps, best_of, q.compression_ratio_threshold, q.logprob_threshold, _text_of(tokenizer, special.timestamp_begin))
         results.append(ctranslate2.WhisperGenerationResult([fb["tokens"]], [fb["score"]]))
         results[0].fallback = fb
     for batch in ([] if temps else chunkit(features, s.concurrent_gpu_chunks)):
         feats = ctranslate2.StorageView.from_array(np.ascontiguousarray(batch))
-        results.extend(whisper_model.generate(feats, [prompt] * len(batch), beam_size=beam_size, return_scores=False,
+        results.extend(whisper_model.generate(feats, [prompt] * len(batch), beam_size=q.beam_size, return_scores=False,
                                               fixed_new_tokens=fixed_new_tokens, input_kind=kind, **rep))
     assert len(results) == total_chunk_count, "Result length doesn't match expected total_chunk_count"
     if use_chunking:
@@ -578,7 +603,7 @@ def do_whisper(audio_file, model, beam_size=None, task="transcribe", detect_lang
     if translate and total_chunk_count <= s.concurrent_gpu_chunks:       # main.py:729-748 (its `len(int)` bug aside: short audio only)
         tprompt = [special.sot, special.language_token_id(language), special.translate, special.notimestamps]
         feats = ctranslate2.StorageView.from_array(np.ascontiguousarray(features))
-        tres = whisper_model.generate(feats, [tprompt] * total_chunk_count, beam_size=beam_size, fixed_new_tokens=fixed_new_tokens, input_kind=kind, **rep)
+        tres = whisper_model.generate(feats, [tprompt] * total_chunk_count, beam_size=q.beam_size, fixed_new_tokens=fixed_new_tokens, input_kind=kind, **rep)
         translation = tokenizer.decode(tres[0].sequences_ids[0]).strip()
         out_translation_tokens = tres[0].sequences_ids[0]
     else:
@@ -594,41 +619,25 @@ def do_whisper(audio_file, model, beam_size=None, task="transcribe", detect_lang
     return out
 
 
-def _do_whisper_seek(models, model, whisper_model, special, pcm, audio_duration, beam_size, task, detect_language, force_language, translate,
-                     fixed_new_tokens, timestamps, word_timestamps, rep, temps, best_of, cr_thr, lp_thr, initial_prompt, prefix, cond, no_speech_threshold,
-                     first_time_start):
-    """do_whisper for a recording over 30 s with long_form="seek": the whole-recording log-mel on one of the model's GPUs for the length of the
-    request, longform.transcribe around generate_from_device / align_from_device."""
+def _do_whisper_seek(q, models, model, whisper_model, pcm, audio_duration, first_time_start):
+    """do_whisper for a recording over 30 s with long_form="seek" (q: the request as do_whisper resolved it): the whole-recording log-mel on one of
+    the model's GPUs for the length of the request, longform.transcribe around generate_from_device / align_from_device."""
     from . import longform
-    s = models.settings
+    special = model_special_tokens(whisper_model)
     tokenizer = models.tokenizer_for(model)
-    ip_ids = prompt_ids(getattr(s, "initial_prompt", "") if initial_prompt is None else initial_prompt, tokenizer, special, "initial_prompt")
-    px_ids = prompt_ids(getattr(s, "prefix", "") if prefix is None else prefix, tokenizer, special, "prefix")
-    if px_ids:      # (the loop always decodes under the timestamp rules, which read the generated history: a prefix is not part of it)
-        raise ValueError("prefix cannot be combined with timestamps / word_timestamps (initial_prompt can), and long_form=seek always decodes with timestamps")
-    if word_timestamps and not getattr(tokenizer, "has_vocabulary", False):
-        raise ValueError("word_timestamps need the checkpoint's tokenizer vocabulary (tokenizer.json next to the model)")
-    n_mels = getattr(whisper_model, "n_mels", audio.N_MELS)
-    n_text_ctx = int((getattr(whisper_model, "arch", None) or {}).get("n_text_ctx", 448))
+    ip_ids, _ = _request_prompt_ids(q, tokenizer, special, seek=True)
+    n_text_ctx = _n_text_ctx(whisper_model)
     replica = whisper_model.acquire_replica()
     long_mel = None
     try:
-        long_mel = audio.LongMel(pcm, n_mels=n_mels, device=replica.device)
-        language = s.language
-        if detect_language and not force_language:
-            first = np.ascontiguousarray(long_mel.window(0, to_host=True)[None])
-            lang_token, _probability = whisper_model.detect_language(ctranslate2.StorageView.from_array(first))[0][0]
-            language = lang_token.strip("<|>")
-        elif force_language:
-            language = force_language
-        if not check_language(language, special):
-            raise ValueError(f"unsupported language {language!r}")
-        start = [special.sot, special.language_token_id(language), special.translate if task == "translate" else special.transcribe]
+        long_mel = audio.LongMel(pcm, n_mels=getattr(whisper_model, "n_mels", audio.N_MELS), device=replica.device)
+        language = _request_language(q, models.settings, special, lambda: whisper_model.detect_language(
+            ctranslate2.StorageView.from_array(np.ascontiguousarray(long_mel.window(0, to_host=True)[None]))))
+        start = [special.sot, special.language_token_id(language), special.translate if q.task == "translate" else special.transcribe]
 
         def decode(window, prompt, t, n):
-            kw = dict(beam_size=beam_size) if t == 0 else dict(beam_size=1, num_hypotheses=n, sampling_topk=0, sampling_temperature=t)
-            r = whisper_model.generate_from_device(replica.device, window, prompt, replica=replica, fixed_new_tokens=fixed_new_tokens, return_scores=True,
-                                                   return_no_speech_prob=True, **kw, **rep)
+            r = whisper_model.generate_from_device(replica.device, window, prompt, replica=replica, fixed_new_tokens=q.fixed_new_tokens, return_scores=True,
+                                                   return_no_speech_prob=True, **_search(q, t, n), **q.rep)
             return list(zip(r.sequences_ids, r.scores)), r.no_speech_prob
 
         def on_window(window, seek, segment_size, segs):
@@ -647,20 +656,16 @@ def _do_whisper_seek(models, model, whisper_model, special, pcm, audio_duration,
             for sg, tm in zip(segs, timed):
                 inside = lambda t: round(min(max(t + off, sg["start"]), sg["end"]), 2)
                 sg["words"] = [dict(w, start=inside(w["start"]), end=inside(w["end"])) for w in tm["words"]]
-        text_of = None
-        if getattr(tokenizer, "has_vocabulary", False):
-            text_of = lambda toks: tokenizer.decode([t for t in toks if t < special.eot])
-        res = longform.transcribe(long_mel, decode, start=start, special=special, initial_prompt_ids=ip_ids, n_text_ctx=n_text_ctx, temperatures=temps, best_of=best_of,
-                                  compression_ratio_threshold=None if cr_thr is None or cr_thr >= 1e30 else cr_thr,
-                                  logprob_threshold=None if lp_thr is None or lp_thr <= -1e30 else lp_thr, no_speech_threshold=no_speech_threshold,
-                                  condition_on_previous_text=cond, text_of=text_of, on_window=on_window if word_timestamps else None)
+        loop = dict(special=special, n_text_ctx=n_text_ctx, logprob_threshold=q.logprob_threshold, no_speech_threshold=q.no_speech_threshold,
+                    condition_on_previous_text=q.condition_on_previous_text)
+        res = longform.transcribe(long_mel, decode, start=start, initial_prompt_ids=ip_ids, temperatures=q.temps, best_of=q.best_of,
+                                  compression_ratio_threshold=q.compression_ratio_threshold, text_of=_text_of(tokenizer, special.eot),
+                                  on_window=on_window if q.word_timestamps else None, **loop)
         translation = translation_tokens = None
-        if translate:
+        if q.translate:
             # the translation pass: the same loop with the translate task - unprompted, one search per window (no fallback), the repetition
             # options applied as to every decode of the request, the same skip rule as the transcription; it carries no segments
-            tres = longform.transcribe(long_mel, decode, start=start[:2] + [special.translate], special=special, n_text_ctx=n_text_ctx,
-                                       logprob_threshold=None if lp_thr is None or lp_thr <= -1e30 else lp_thr,
-                                       no_speech_threshold=no_speech_threshold, condition_on_previous_text=cond)
+            tres = longform.transcribe(long_mel, decode, start=start[:2] + [special.translate], **loop)
             translation_tokens = [t for sg in tres["segments"] for t in sg["tokens"] if t < special.eot]
             translation = tokenizer.decode(translation_tokens).strip()
     finally:
@@ -672,7 +677,7 @@ def _do_whisper_seek(models, model, whisper_model, special, pcm, audio_duration,
         text_tokens = [t for t in sg["tokens"] if t < special.eot]
         tokens.extend(sg["tokens"])
         out_sg = {"start": sg["start"], "end": sg["end"], "text": tokenizer.decode(text_tokens).strip()}
-        if word_timestamps:
+        if q.word_timestamps:
             out_sg["words"] = sg.get("words", [])
         segments.append(out_sg)
     text = " ".join(sg["text"] for sg in segments if sg["text"]).strip()
@@ -680,7 +685,7 @@ def _do_whisper_seek(models, model, whisper_model, special, pcm, audio_duration,
     out = WhisperResult((language, text, infer_time_milliseconds, translation, math.floor(audio_duration / infer_time_milliseconds), audio_duration))
     out.tokens = tokens
     out.translation_tokens = translation_tokens
-    out.segments = segments if timestamps else None
-    out.fallback = res["fallback"] if temps else None
+    out.segments = segments if q.timestamps else None
+    out.fallback = res["fallback"] if q.temps else None
     out.seek = res["windows"]
     return out
