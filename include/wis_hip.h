@@ -202,6 +202,9 @@ int  wis_model_clone(wis_model_t* parent, wis_model_t** out);
 #define WIS_IN_MEL_DEV  1   /* same, device memory */
 #define WIS_IN_PCM_HOST 2   /* f32 [B][480000] host: log-mel runs on the GPU, mel never leaves HBM */
 #define WIS_IN_PCM_DEV  3
+/* encoder OUTPUT handed back in (wis_encode below): the entry point skips the log-mel and the encoder and starts at the cross-K/V projection */
+#define WIS_IN_ENC_DEV  4   /* f16 [B][n_audio_ctx][d_model], device memory on the handle's device: the bits wis_encode left there */
+#define WIS_IN_ENC_HOST 5   /* the same values as f32 in host memory (f16 -> f32 -> f16 is exact: a host round trip loses nothing) */
 
 typedef struct {
   int32_t input_kind;       /* WIS_IN_* */
@@ -317,6 +320,28 @@ int wis_last_no_speech_prob(wis_model_t* m, int B, float* out);
 /* ---- a14: language detection (replaces whisper_model.detect_language(features),
  * main.py:637-643): probabilities over cfg.lang_ids, [B][n_lang]. */
 int wis_detect_language(wis_model_t* m, const float* input, int input_kind, int B, float* lang_probs);
+
+/* ---- one encoder pass for every decode of a window (replaces ctranslate2.models.Whisper.encode(features, to_cpu)).
+ * input / input_kind: one of the four WIS_IN_MEL_* / WIS_IN_PCM_* forms, B <= max_batch windows.  Runs the log-mel (PCM kinds) and the
+ * encoder, then leaves the encoder's output - B * n_audio_ctx * d_model halves - in enc_out_dev_f16, a block of the CALLER's on the
+ * handle's device; enc_out_host_or_null != NULL additionally receives the same values as f32 [B][n_audio_ctx][d_model] in host memory.
+ * The handle's stream is synchronised before the call returns: the block can be read from any stream of that device afterwards, by this
+ * handle, by a clone, or by any other handle of the same model on that device.
+ * wis_generate* (opts->input_kind), wis_detect_language, wis_align, wis_debug_align_matrix and the logits taps take the block back as
+ * WIS_IN_ENC_DEV (any B consecutive utterances of it: a pointer offset of whole utterances is fine) or its host copy as WIS_IN_ENC_HOST and
+ * then compute, bit for bit, what they compute from the features at the same B - the cross-K/V projection and everything behind it
+ * are the same launches on the same values.
+ * WHERE THE BLOCK IS READ.  WIS_IN_ENC_DEV: the cross-K/V GEMM reads the caller's block IN PLACE as its A operand, no copy.  Every
+ * A-operand loader of the encoder GEMM clamps its row index to M - 1 = B * n_audio_ctx - 1 (the guard is on the stores), and K = d_model
+ * is a whole number of k-tiles, so nothing beyond the B * n_audio_ctx * d_model halves is touched - the GEMM does not rely on the size of
+ * the handle's own encoder buffer.  The address handed in must be 16-byte aligned (the loaders read A in 16-byte pieces; a device allocation
+ * is, and so is any offset of whole utterances inside one: n_audio_ctx * d_model halves are a multiple of 16 bytes) - nothing checks it.
+ * The block must stay allocated until the call that reads it has returned (the GEMM has run by then).
+ * WIS_IN_ENC_HOST: host -> device, f32 -> f16 into the handle's own encoder buffer, then the same GEMM.
+ * wis_last_timing after a wis_generate from encoder output reports logmel_ms = encoder_ms = 0: the stages did not run.
+ * Refused before anything is enqueued: enc_out_dev_f16 or input NULL (WIS_E_ARG), input_kind WIS_IN_ENC_* (WIS_E_UNSUPPORTED: that is
+ * encoder output already) or unknown (WIS_E_ARG), B outside [1, max_batch] (WIS_E_ARG); wis_last_error names the argument. */
+int wis_encode(wis_model_t* m, const float* input, int input_kind, int B, void* enc_out_dev_f16, float* enc_out_host_or_null);
 
 /* ---- parity taps (teacher-forced); not used by the product path -------------------- */
 /* encoder output [B][1500][d] f32 */

@@ -38,7 +38,17 @@ def create_app():
         time.sleep(base + per * B)
         return [ct2.WhisperGenerationResult([[400 + i for i in range(16)]], [-0.5]) for _ in range(B)]
 
+    def fake_encode(r, features, input_kind, device_ptr=None):
+        """Whisper.encode without an engine: a HOST-only view of the right shape (zeros), which generate / detect_language / align then
+        recognise as encoder output (WIS_IN_ENC_HOST) - the call sequence is real, the values are not."""
+        import numpy as np
+        B = int(features) if device_ptr is not None else features.shape[0]
+        T, d = r.enc_shape
+        time.sleep(base * 0.2)
+        return ct2.StorageView(np.zeros((B, T, d), np.float32))
+
     ct2._generate_chunk = fake_chunk
+    ct2._encode_chunk = fake_encode
     _lib.device_count = lambda: 1
     s = APISettings()
     s.whisper_model_path = "synthetic:{size}"

@@ -401,9 +401,7 @@ int align_run(wis_model* m, const float* input, int input_kind, int B, const int
   hipStream_t st = m->st;
   a.n_ev = 0;
   hipEventRecord(a.ev[0], st);
-  WIS_RET(stage_input(m, input, input_kind, B));
-  WIS_RET(run_encoder(m, B));
-  WIS_RET(run_cross_kv(m, B));
+  WIS_RET(run_front(m, input, input_kind, B));
   hipEventRecord(a.ev[1], st);
   int* dN = a.d_meta; int* dF = a.d_meta + B; int* d_tgt = a.d_meta + 3 * c.max_batch; int* d_dst = d_tgt + MAX_ROWS;
   {

@@ -186,15 +186,9 @@ static int front_half(const GenCtx& g) {
   static const bool two_streams = getenv("WIS_TWO_STREAMS") != nullptr;    // A/B switch: the second stream whatever else runs
   const bool alone = g_active_calls[m->device & 63].load(std::memory_order_relaxed) <= 1;
   hipStream_t se = (one_stream || !(alone || two_streams)) ? st : m->st_enc;
+  if (input_is_encoded(g.o->input_kind)) se = st;      // encoder output handed in (wis_encode): nothing to run beside the over-run step
   if (se != st) WIS_HIP_CHECK(hipStreamWaitEvent(se, m->ev_ckv, 0));
-  WIS_HIP_CHECK(hipEventRecord(m->ev[0], se));
-  WIS_RET(stage_input(m, g.input, g.o->input_kind, B, se));
-  WIS_HIP_CHECK(hipEventRecord(m->ev[1], se));
-  WIS_RET(run_encoder(m, B, se));
-  WIS_HIP_CHECK(hipEventRecord(m->ev[2], se));
-  if (se != st) { WIS_HIP_CHECK(hipEventRecord(m->ev_enc, se)); WIS_HIP_CHECK(hipStreamWaitEvent(st, m->ev_enc, 0)); }
-  WIS_RET(run_cross_kv(m, B));
-  WIS_HIP_CHECK(hipEventRecord(m->ev[3], st));
+  WIS_RET(run_front(m, g.input, g.o->input_kind, B, se, true));
   WIS_HIP_CHECK(hipEventRecord(m->ev_ckv, st));
   return WIS_OK;
 }
@@ -695,6 +689,7 @@ static void record_timing(const GenCtx& g, const LoopResult& lr) {
   float ms;
   hipEventElapsedTime(&ms, m->ev[0], m->ev[1]); m->timing.logmel_ms = ms;
   hipEventElapsedTime(&ms, m->ev[1], m->ev[2]); m->timing.encoder_ms = ms;
+  if (m->front_skipped) m->timing.logmel_ms = m->timing.encoder_ms = 0.f;      // encoder output was handed in: the stages did not run
   hipEventElapsedTime(&ms, m->ev[2], m->ev[3]); m->timing.crosskv_ms = ms;
   hipEventElapsedTime(&ms, m->ev[3], m->ev[4]); m->timing.prefill_ms = ms;
   if (lr.from_host) m->timing.decode_ms = lr.decode_ms_dev; else { hipEventElapsedTime(&ms, m->ev[4], m->ev[5]); m->timing.decode_ms = ms; }
@@ -888,9 +883,7 @@ int wis_debug_tree_logits(wis_model_t* m, const float* input, int input_kind, co
   const wis_config_t& c = m->cfg; hipStream_t st = m->st;
   const int k = beam, V = c.n_vocab;
   for (int i = 0; i < n_steps * k; ++i) if (tok[i] < 0 || tok[i] >= V || org[i] < 0 || org[i] >= k) { set_error("wis_debug_tree_logits: token / origin out of range"); return WIS_E_ARG; }
-  WIS_RET(stage_input(m, input, input_kind, 1));
-  WIS_RET(run_encoder(m, 1));
-  WIS_RET(run_cross_kv(m, 1));
+  WIS_RET(run_front(m, input, input_kind, 1));
   m->spin_now = false;
   // the prompt: rows at positions 0 .. P-1 of slot 0, then every slot gets a copy (what the first step's kv_reorder does)
   std::vector<int> ptok(P), ppos(P), pslot(P, 0), pls(P, 0);

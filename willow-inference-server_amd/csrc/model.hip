@@ -39,6 +39,17 @@ __global__ void convert_kernel(const void* __restrict__ src, int src_f16, void* 
     if (dst_f16) reinterpret_cast<f16*>(dst)[r * dst_ld + c] = (f16)v; else reinterpret_cast<float*>(dst)[r * dst_ld + c] = v;
   }
 }
+// encoder output handed back in through the host (WIS_IN_ENC_HOST): f32 -> f16, eight values per thread and trip (two 16-byte loads, one
+// 16-byte store; n8 = B T d / 8, d a multiple of 64).  Values that were f16 before the host saw them convert back exactly.
+__global__ __launch_bounds__(256) void enc_f32_to_f16_kernel(const float4* __restrict__ s, f16x8* __restrict__ d, int64_t n8) {
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n8; i += (int64_t)gridDim.x * 256) {
+    const float4 a = s[2 * i], b = s[2 * i + 1];
+    f16x8 o;
+    o[0] = (f16)a.x; o[1] = (f16)a.y; o[2] = (f16)a.z; o[3] = (f16)a.w;
+    o[4] = (f16)b.x; o[5] = (f16)b.y; o[6] = (f16)b.z; o[7] = (f16)b.w;
+    d[i] = o;
+  }
+}
 // conv weight [out][in][3] -> f16 [out][row_len], element (o, k*cpad + c) = W[o][c][k]; channel padding and the row tail
 // [3*cpad, row_len) are zero (row_len = K rounded up to the GEMM's 64-deep k-tile)
 __global__ void conv_pack_kernel(const void* __restrict__ src, int src_f16, f16* __restrict__ dst, int out, int in, int cpad, int row_len) {
@@ -594,12 +605,36 @@ int run_encoder(wis_model* m, int B, hipStream_t on) {
   if (!split) WIS_RET(launch_layernorm(st, m->x, m->enc_ln_g, m->enc_ln_b, m->mem, M, d));
   return WIS_OK;
 }
-int run_cross_kv(wis_model* m, int B) {
+int run_cross_kv(wis_model* m, int B, const f16* mem) {
   const wis_config_t& c = m->cfg;
   const int d = c.d_model, T = c.n_audio_ctx;
   // every decoder layer's K/V projection of the encoder memory in one GEMM (weights, biases and outputs are single blocks)
-  return launch_gemm_crosskv(m->st, gemm_plain(m->mem, d, m->w_ckv_all, B * T, c.n_dec_layers * 2 * d, d), m->b_ckv_all, m->kx_all, m->vx_all, d, T, m->Tpad,
+  return launch_gemm_crosskv(m->st, gemm_plain(mem ? mem : m->mem, d, m->w_ckv_all, B * T, c.n_dec_layers * 2 * d, d), m->b_ckv_all, m->kx_all, m->vx_all, d, T, m->Tpad,
                              c.n_heads, (int64_t)m->kx_lstride, (int64_t)m->vx_lstride);
+}
+// input -> cross K / V (model.hpp has the contract).  The caller has checked B (check_batch) and that `input` is not null.
+int run_front(wis_model* m, const float* input, int kind, int B, hipStream_t enc, bool timed) {
+  hipStream_t st = m->st;
+  const bool given = input_is_encoded(kind);
+  hipStream_t se = (enc && !given) ? enc : st;
+  const f16* mem = nullptr;
+  m->front_skipped = given;
+  if (timed) WIS_HIP_CHECK(hipEventRecord(m->ev[0], se));
+  if (!given) WIS_RET(stage_input(m, input, kind, B, se));
+  if (timed) WIS_HIP_CHECK(hipEventRecord(m->ev[1], se));
+  if (!given) WIS_RET(run_encoder(m, B, se));
+  if (timed) WIS_HIP_CHECK(hipEventRecord(m->ev[2], se));
+  if (se != st) { WIS_HIP_CHECK(hipEventRecord(m->ev_enc, se)); WIS_HIP_CHECK(hipStreamWaitEvent(st, m->ev_enc, 0)); }
+  if (kind == WIS_IN_ENC_DEV) mem = reinterpret_cast<const f16*>(input);
+  if (kind == WIS_IN_ENC_HOST) {
+    const int64_t n = (int64_t)B * m->cfg.n_audio_ctx * m->cfg.d_model;
+    if (n % 8) { set_error("WIS_IN_ENC_HOST: d_model %d is not a multiple of 8", m->cfg.d_model); return WIS_E_UNSUPPORTED; }
+    WIS_HIP_CHECK(hipMemcpyAsync(m->x, input, (size_t)n * 4, hipMemcpyHostToDevice, st));      // x [max_batch T][d] f32: the residual stream, free outside the encoder
+    hipLaunchKernelGGL(enc_f32_to_f16_kernel, dim3(blocks_for(n / 8)), dim3(256), 0, st, reinterpret_cast<const float4*>(m->x), reinterpret_cast<f16x8*>(m->mem), n / 8);
+  }
+  WIS_RET(run_cross_kv(m, B, mem));
+  if (timed) WIS_HIP_CHECK(hipEventRecord(m->ev[3], st));
+  return WIS_OK;
 }
 
 // ---- granule hand-off of the cross-attention: when it may be used -------------------------------
@@ -1162,9 +1197,7 @@ int wis_detect_language(wis_model_t* m, const float* input, int input_kind, int 
   WIS_ENTER(m, "wis_detect_language")
   WIS_HIP_CHECK(hipSetDevice(m->device));
   WIS_RET(check_batch(m, B, 1));
-  WIS_RET(stage_input(m, input, input_kind, B));
-  WIS_RET(run_encoder(m, B));
-  WIS_RET(run_cross_kv(m, B));
+  WIS_RET(run_front(m, input, input_kind, B));
   std::vector<int> tok(B, m->cfg.sot);
   for (int attempt = 0; attempt < 2; ++attempt) {
     SpinClaim claim(m, B);
@@ -1176,6 +1209,28 @@ int wis_detect_language(wis_model_t* m, const float* input, int input_kind, int 
     WIS_RET(spin_gave_up(m, &gave_up));      // (synchronises the stream)
     if (!gave_up) break;
   }
+  return WIS_OK;
+}
+
+// the encoder alone, its output left in a block of the caller's (include/wis_hip.h): what the WIS_IN_ENC_* kinds of the other entry points take back
+int wis_encode(wis_model_t* m, const float* input, int input_kind, int B, void* enc_out_dev_f16, float* enc_out_host_or_null) {
+  if (!m) { set_error("wis_encode: the model handle is null"); return WIS_E_ARG; }
+  if (!input) { set_error("wis_encode: input is null"); return WIS_E_ARG; }
+  if (!enc_out_dev_f16) { set_error("wis_encode: enc_out_dev_f16 is null (the caller provides the device block)"); return WIS_E_ARG; }
+  if (input_is_encoded(input_kind)) { set_error("wis_encode: input_kind %d is encoder output already (WIS_IN_MEL_* / WIS_IN_PCM_* are encoded)", input_kind); return WIS_E_UNSUPPORTED; }
+  if (input_kind < WIS_IN_MEL_HOST || input_kind > WIS_IN_PCM_DEV) { set_error("wis_encode: bad input_kind %d", input_kind); return WIS_E_ARG; }
+  if (B < 1 || B > m->cfg.max_batch) { set_error("wis_encode: B = %d outside [1, max_batch=%d]", B, m->cfg.max_batch); return WIS_E_ARG; }
+  WIS_ENTER(m, "wis_encode")
+  WIS_HIP_CHECK(hipSetDevice(m->device));
+  WIS_RET(stage_input(m, input, input_kind, B));
+  WIS_RET(run_encoder(m, B));
+  const int64_t n = (int64_t)B * m->cfg.n_audio_ctx * m->cfg.d_model;
+  WIS_HIP_CHECK(hipMemcpyAsync(enc_out_dev_f16, m->mem, (size_t)n * 2, hipMemcpyDeviceToDevice, m->st));
+  if (enc_out_host_or_null) {
+    launch_f16_to_f32(m->st, m->mem, m->x, n);   // x is free after the encoder
+    WIS_HIP_CHECK(hipMemcpyAsync(enc_out_host_or_null, m->x, (size_t)n * 4, hipMemcpyDeviceToHost, m->st));
+  }
+  WIS_HIP_CHECK(hipStreamSynchronize(m->st));
   return WIS_OK;
 }
 

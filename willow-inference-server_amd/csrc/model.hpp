@@ -170,6 +170,7 @@ struct wis_model {
   hipStream_t st_enc = nullptr;             // wis_generate's front half (log-mel, encoder) runs here: it overlaps the previous call's over-run decode step on `st`
   hipEvent_t ev_enc = nullptr, ev_ckv = nullptr;      // encoder output ready (st_enc -> st); cross-K/V projection done reading it (st -> the next call's st_enc)
   wis_timing_t timing;
+  bool front_skipped = false;               // the last run_front was handed encoder output: no log-mel, no encoder ran (wis_last_timing: 0 ms for both)
   std::map<wis::GraphKey, hipGraphExec_t> graphs;
   bool use_graph;
   bool w8 = false;              // decoder weights stored as 8-bit packed fragments
@@ -203,7 +204,16 @@ struct BusyGuard {
 int check_batch(wis_model* m, int B, int beam);
 int stage_input(wis_model* m, const float* input, int kind, int B, hipStream_t on = nullptr);
 int run_encoder(wis_model* m, int B, hipStream_t on = nullptr);
-int run_cross_kv(wis_model* m, int B);
+int run_cross_kv(wis_model* m, int B, const f16* mem = nullptr);      // mem: the GEMM's A operand [B T][d] (null: the handle's own m->mem)
+// The front half of every entry point that reads audio: input -> cross K / V of B utterances on m->st.
+//   WIS_IN_MEL_* / WIS_IN_PCM_*: stage_input + run_encoder on `enc` (null: m->st), then run_cross_kv on m->st behind them (enc != m->st:
+//   through ev_enc) - what every call site enqueued before the helper existed, launch for launch.
+//   WIS_IN_ENC_DEV: no log-mel, no encoder; the cross-K/V GEMM reads the caller's block in place (include/wis_hip.h wis_encode says why it may).
+//   WIS_IN_ENC_HOST: the f32 values go up into m->x (free outside the encoder), enc_f32_to_f16_kernel writes m->mem, then the same GEMM.
+//   Both run on m->st whatever `enc` says: there is no encoder to run beside the previous call's over-run step.
+// timed (wis_generate): ev[0] .. ev[3] around log-mel / encoder / cross-K/V for wis_last_timing; m->front_skipped says the first two did not run.
+inline bool input_is_encoded(int kind) { return kind == WIS_IN_ENC_DEV || kind == WIS_IN_ENC_HOST; }
+int run_front(wis_model* m, const float* input, int kind, int B, hipStream_t enc = nullptr, bool timed = false);
 // what run_encoder launches, for the op taps on shorter images: conv1's K (3 C rounded up to whole 64-deep k-tiles), the convs' GEMM
 // descriptions and weight packers, the mel -> image transpose, the FFN2 K split at M rows
 int conv1_k(int n_mels);

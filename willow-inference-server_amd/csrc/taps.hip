@@ -33,9 +33,7 @@ static int debug_logits_rows(const char* who, wis_model_t* m, const float* input
   WIS_HIP_CHECK(hipSetDevice(m->device));
   WIS_RET(check_batch(m, B, 1));
   if (B * R > MAX_ROWS) { set_error("%s: B*R = %d exceeds %d decoder rows per pass", who, B * R, MAX_ROWS); return WIS_E_STATE; }
-  WIS_RET(stage_input(m, input, input_kind, B));
-  WIS_RET(run_encoder(m, B));
-  WIS_RET(run_cross_kv(m, B));
+  WIS_RET(run_front(m, input, input_kind, B));
   const int V = m->cfg.n_vocab;
   // the rows (b, i) of a pass sit at positions t0 + i of utterance b's KV slot (causal by position, like the merged prompt pass of
   // wis_generate), so a pass has B * R rows - with B * R > 8 it takes the batched-row route (dec_forward_frag: fragment images,

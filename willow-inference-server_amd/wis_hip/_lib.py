@@ -14,6 +14,7 @@ LIB_PATH = os.environ.get("WIS_LIB_PATH") or os.path.join(os.path.dirname(_HERE)
 
 WIS_OK = 0
 WIS_IN_MEL_HOST, WIS_IN_MEL_DEV, WIS_IN_PCM_HOST, WIS_IN_PCM_DEV = 0, 1, 2, 3
+WIS_IN_ENC_DEV, WIS_IN_ENC_HOST = 4, 5      # encoder output handed back in (wis_encode): f16 on the handle's device / the same values as f32 on the host
 WIS_DT_F32, WIS_DT_F16 = 0, 1
 N_SAMPLES, N_FRAMES, N_MELS = 480000, 3000, 80
 
@@ -106,6 +107,7 @@ SYMBOLS = [
     ("wis_last_trajectory", _i, [_vp, _i, C.POINTER(C.c_int32), C.POINTER(C.c_int32), _i, C.POINTER(C.c_int32)]),
     ("wis_last_no_speech_prob", _i, [_vp, _i, _fp]),
     ("wis_detect_language", _i, [_vp, _vp, _i, _i, _fp]),
+    ("wis_encode", _i, [_vp, _vp, _i, _i, _vp, _fp]),
     ("wis_debug_encode", _i, [_vp, _vp, _i, _i, _fp]),
     ("wis_debug_logits", _i, [_vp, _vp, _i, _i, C.POINTER(C.c_int32), _i, _fp]),
     ("wis_debug_logits_rows", _i, [_vp, _vp, _i, _i, C.POINTER(C.c_int32), _i, _i, _fp]),

@@ -4,6 +4,7 @@
     ctranslate2.StorageView.from_array(ndarray f32 [B, n_mels, 3000])   (n_mels 80, or 128 for large-v3 / large-v3-turbo)
     model.generate(features, [prompt] * B, beam_size=int, return_scores=False) -> results[i].sequences_ids[0]
     model.detect_language(features) -> [[("<|xx|>", prob), ...], ...]
+    model.encode(features, to_cpu=False) -> StorageView of the encoder output, which generate / detect_language / align take in place of features
     ctranslate2.get_supported_compute_types(device)
 
 (reference main.py:341-444, 454, 535-537, 638-639, 685-693, 707, 713).  The arithmetic runs in the
@@ -16,6 +17,7 @@ offline).
 import ctypes as C
 import os
 import threading
+import weakref
 from typing import NamedTuple, Optional
 
 import numpy as np
@@ -55,10 +57,14 @@ def get_supported_compute_types(device="cuda", device_index=0):
 
 
 class StorageView:
-    """Zero-copy wrapper of a host ndarray (ctranslate2.StorageView.from_array, main.py:638,685)."""
+    """Zero-copy wrapper of a host ndarray (ctranslate2.StorageView.from_array, main.py:638,685) - or, as `Whisper.encode` returns it, a view of
+    encoder output in device memory: f16 [B, n_audio_ctx, d_model] inside a `_lib.DevBuf` that every view of it shares and the last one frees.
+    `view[i:j]` (utterances, step 1) is another view into the same block: a pointer offset, no copy.  A device view has no `.array`;
+    `to_cpu()` reads it back as a host view of the same values in f32 (exact), which `generate` / `detect_language` / `align` take as well."""
 
-    def __init__(self, array):
+    def __init__(self, array, *, _block=None, _offset=0, _shape=None, _owner=None):
         self.array = array
+        self._block, self._offset, self._dev_shape, self._owner = _block, int(_offset), _shape, _owner
 
     @classmethod
     def from_array(cls, array):
@@ -67,9 +73,66 @@ class StorageView:
             raise ValueError("StorageView.from_array expects a C-contiguous float32 array")
         return cls(a)
 
+    @classmethod
+    def _on_device(cls, block, shape, owner=None, offset=0):
+        """a view of f16 `shape` at byte `offset` of the _lib.DevBuf `block`; owner: the Whisper model that encoded it"""
+        return cls(None, _block=block, _offset=offset, _shape=[int(x) for x in shape], _owner=weakref.ref(owner) if owner is not None else None)
+
+    @property
+    def device(self):
+        return "cpu" if self._block is None else "cuda"
+
+    @property
+    def device_index(self):
+        return 0 if self._block is None else int(self._block.device)
+
+    @property
+    def dtype(self):
+        return "float32" if self._block is None else "float16"
+
     @property
     def shape(self):
-        return list(self.array.shape)
+        return list(self.array.shape) if self._block is None else list(self._dev_shape)
+
+    @property
+    def device_ptr(self):
+        """address of the view's first element in device memory (device views only)"""
+        if self._block is None or not self._block.ptr:
+            raise ValueError("StorageView: not a live device view")
+        return int(self._block.ptr.value) + self._offset
+
+    def __len__(self):
+        return self.shape[0]
+
+    def __getitem__(self, key):
+        if self._block is None:
+            return StorageView(np.ascontiguousarray(self.array[key]))
+        if isinstance(key, (int, np.integer)):
+            k = int(key) + (self._dev_shape[0] if key < 0 else 0)
+            key = slice(k, k + 1)
+        if not isinstance(key, slice):
+            raise TypeError("a device StorageView is sliced by utterance: view[i:j]")
+        i, j, step = key.indices(self._dev_shape[0])
+        if step != 1:
+            raise ValueError("a device StorageView is sliced with step 1 (a pointer offset, no copy)")
+        j = max(i, j)
+        row = 2 * int(np.prod(self._dev_shape[1:], dtype=np.int64))
+        v = StorageView(None, _block=self._block, _offset=self._offset + i * row, _shape=[j - i] + self._dev_shape[1:])
+        v._owner = self._owner
+        return v
+
+    def to_cpu(self):
+        """host view of the same values (f32; f16 -> f32 is exact)"""
+        if self._block is None:
+            return self
+        h = np.empty(self._dev_shape, np.float16)
+        if h.size:
+            _lib.check(_lib.load().wis_dev_d2h(self._block.device, _lib.ptr(h), C.c_void_p(self.device_ptr), h.nbytes))
+        return StorageView(h.astype(np.float32))
+
+    def __array__(self, dtype=None, copy=None):
+        a = self.to_cpu().array
+        return a if dtype is None else a.astype(dtype, copy=False)
 
 
 class WhisperGenerationResult:
@@ -95,9 +158,11 @@ class WhisperAlignmentResult:
 
 
 class _Replica:
-    def __init__(self, handle, device, n_mels=W.N_MELS):
+    def __init__(self, handle, device, n_mels=W.N_MELS, enc_shape=(W.N_AUDIO_CTX, 0)):
         self.handle, self.device = handle, device
         self.mel_bytes = n_mels * 3000 * 4      # one utterance's features
+        self.enc_shape = (int(enc_shape[0]), int(enc_shape[1]))      # one utterance's encoder output [n_audio_ctx, d_model], f16
+        self.enc_bytes = self.enc_shape[0] * self.enc_shape[1] * 2
         self.lock = threading.Lock()
         self.inflight = 0
         self.stage = None           # device block for batches of device-resident features (lazy)
@@ -321,6 +386,48 @@ def _generate_chunk(r, mel, prompts, opts, *rest, device_ptr=None, seeds=None):
     return out
 
 
+class EncodeKey(NamedTuple):
+    """The micro-batcher's key of `Whisper.encode` rows: windows of concurrent requests share one encoder batch when their input kind is the
+    same.  A type of its own, so it never equals a DecodeOptions - an encode row never lands in a decode batch or the other way round."""
+    input_kind: int = _lib.WIS_IN_MEL_HOST
+
+    def __eq__(self, other):
+        return type(other) is EncodeKey and tuple.__eq__(self, other)
+
+    def __ne__(self, other):
+        return not self == other
+
+    __hash__ = tuple.__hash__
+
+
+_ENCODED_KINDS = (_lib.WIS_IN_ENC_DEV, _lib.WIS_IN_ENC_HOST)
+
+
+def _encode_chunk(r, features, input_kind, device_ptr=None):
+    """One wis_encode call on replica r (the caller serialises access to r) -> a device StorageView [B, n_audio_ctx, d_model] that owns its block.
+    features: host ndarray [B, ...] - or, with device_ptr, just the batch size B of features already resident on r.device."""
+    B = int(features) if device_ptr is not None else features.shape[0]
+    T, d = r.enc_shape
+    block = _lib.DevBuf(B * r.enc_bytes, r.device)
+    src = C.c_void_p(device_ptr) if device_ptr is not None else _lib.ptr(features)
+    _lib.check(_lib.load().wis_encode(r.handle, src, int(input_kind), B, block.ptr, None))
+    return StorageView._on_device(block, [B, T, d])
+
+
+def _gather_device_rows(replica, ptrs, row_bytes):
+    """-> the address of len(ptrs) consecutive rows on replica.device (the caller holds replica.lock): the rows themselves when they already lie
+    back to back (one utterance; the slices of one encode), else a device-to-device copy into the replica's staging block - nothing visits the host"""
+    if all(ptrs[i + 1] == ptrs[i] + row_bytes for i in range(len(ptrs) - 1)):
+        return ptrs[0]
+    rb = max(replica.mel_bytes, replica.enc_bytes, int(row_bytes))      # the block serves every row kind; never smaller than the rows written now
+    if replica.stage is None or replica.stage.nbytes < len(ptrs) * rb:
+        replica.stage = _lib.DevBuf(max(len(ptrs), 8) * rb, replica.device)
+    lib = _lib.load()
+    for i, src in enumerate(ptrs):
+        _lib.check(lib.wis_dev_copy_peer(replica.device, C.c_void_p(replica.stage.ptr.value + i * row_bytes), replica.device, C.c_void_p(src), row_bytes))
+    return replica.stage.ptr.value
+
+
 MAX_DECODER_ROWS = 96      # csrc/kernels.hpp MAX_ROWS: decoder rows per device pass
 MAX_BEAM = 8               # csrc/kernels.hpp MAX_R: rows per utterance (beam size)
 MAX_REPLICAS_PER_DEVICE = 4   # default ceiling for inter_threads -> replicas per GPU (measured on MI355X, bench.py "concurrent_device_batches": 118 / 152 / 165 / 173 / 160 utterances/s with 1..5 batches of 8 in flight)
@@ -422,7 +529,9 @@ def _capacity(max_batch, opts):
     """Utterances per device batch: the decoder handles <= MAX_DECODER_ROWS rows per pass - utterances x beam while decoding,
     utterances x P in the merged prefill + first step (wis_generate enforces B * P <= MAX_ROWS and B * beam <= MAX_ROWS).
     A prompt of more than SHORT_PROMPT tokens is prefilled in windows whose last one shrinks with the batch (min(16, MAX_ROWS // B) rows per
-    utterance): the capacity no longer divides by P."""
+    utterance): the capacity no longer divides by P.  An EncodeKey (Whisper.encode rows): the encoder takes max_batch windows."""
+    if isinstance(opts, EncodeKey):
+        return max(1, int(max_batch))
     P = opts.prompt_len
     rows = max(opts.beam_size, opts.num_hypotheses, 1)      # decoder rows per utterance: its beams, or its num_hypotheses samples
     if P > SHORT_PROMPT:
@@ -431,22 +540,22 @@ def _capacity(max_batch, opts):
 
 
 def _run_batch(replica, opts, rows):
-    """One device batch: rows = [(features, prompt, seed)] of utterances whose DecodeOptions are equal (seed 0 when nothing is sampled)."""
-    prompts, seeds = [r[1] for r in rows], [r[2] for r in rows]
-    if opts.input_kind == _lib.WIS_IN_MEL_DEV:
-        # features that already live in this replica's HBM (streaming sessions: audio.MelStream.finish): one utterance goes in
-        # by pointer, several are gathered device-to-device into the replica's staging block - nothing visits the host
+    """One device batch: rows = [(features, prompt, seed[, what keeps a device address alive])] of utterances whose DecodeOptions are equal (seed 0 when nothing is sampled) - or,
+    under an EncodeKey, rows = [features] of windows to encode together: every row gets its one-utterance slice of the batch's view."""
+    if isinstance(opts, EncodeKey):
         with replica.lock:
-            if len(rows) == 1:
-                ptr = int(rows[0][0])
+            if opts.input_kind == _lib.WIS_IN_MEL_DEV:
+                view = _encode_chunk(replica, len(rows), opts.input_kind, device_ptr=_gather_device_rows(replica, [int(r) for r in rows], replica.mel_bytes))
             else:
-                mb = replica.mel_bytes
-                if replica.stage is None or replica.stage.nbytes < len(rows) * mb:
-                    replica.stage = _lib.DevBuf(max(len(rows), 8) * mb, replica.device)
-                lib = _lib.load()
-                for i, src in enumerate(r[0] for r in rows):
-                    _lib.check(lib.wis_dev_copy_peer(replica.device, C.c_void_p(replica.stage.ptr.value + i * mb), replica.device, C.c_void_p(int(src)), mb))
-                ptr = replica.stage.ptr.value
+                view = _encode_chunk(replica, np.ascontiguousarray(np.stack(rows)), opts.input_kind)
+        return [view[i:i + 1] for i in range(len(rows))]
+    prompts, seeds = [r[1] for r in rows], [r[2] for r in rows]
+    if opts.input_kind in (_lib.WIS_IN_MEL_DEV, _lib.WIS_IN_ENC_DEV):
+        # features (streaming sessions: audio.MelStream.finish) or encoder output (Whisper.encode) that already live in this replica's HBM: one
+        # utterance goes in by pointer, several are gathered device-to-device into the replica's staging block - nothing visits the host
+        rb = replica.mel_bytes if opts.input_kind == _lib.WIS_IN_MEL_DEV else replica.enc_bytes
+        with replica.lock:
+            ptr = _gather_device_rows(replica, [int(r[0]) for r in rows], rb)
             return _generate_chunk(replica, len(rows), prompts, opts, device_ptr=ptr, seeds=seeds)
     mel = np.ascontiguousarray(np.stack([r[0] for r in rows]))
     with replica.lock:
@@ -484,7 +593,8 @@ class Whisper:
         arena, index = W.build_arena(weights)
         kw = dict(suppress_ids=cfg.get("suppress_ids"), suppress_begin=cfg.get("suppress_ids_begin"), lang_ids=cfg.get("lang_ids"),
                   weight_bits=8 if self.compute_type == "int8_float16" else 16, special=self.special)
-        self._replicas = [_Replica(h, d, arch["n_mels"]) for h, d in zip(create_replicas(arch, arena, index, devs, max_batch, max_beam, **kw), devs)]
+        enc_shape = (arch["n_audio_ctx"], arch["d_model"])
+        self._replicas = [_Replica(h, d, arch["n_mels"], enc_shape) for h, d in zip(create_replicas(arch, arena, index, devs, max_batch, max_beam, **kw), devs)]
         # CTranslate2's `inter_threads` = batches a model runs in parallel (reference main.py:341-355 passes ctranslate2_threads).  Here:
         # replicas PER GPU that share one weight copy (wis_model_clone) and run their device batches concurrently on their own
         # streams - a decode chain is latency-bound and leaves most of the chip idle, a second batch in flight fills it.  The count is
@@ -493,7 +603,7 @@ class Whisper:
         per_dev = max(1, min(int(inter_threads) if inter_threads else 1, per_dev))
         for r in list(self._replicas):
             for _ in range(per_dev - 1):
-                self._replicas.append(_Replica(clone_handle(r.handle), r.device, arch["n_mels"]))
+                self._replicas.append(_Replica(clone_handle(r.handle), r.device, arch["n_mels"], r.enc_shape))
         self._set_alignment_heads(cfg.get("alignment_heads"))
         self.max_batch, self.max_beam = max_batch, max_beam
         self._pick = threading.Lock()
@@ -508,7 +618,7 @@ class Whisper:
         self.compute_type = "float16"
         self.arch, self.decode_config = arch, decode_config or {}
         self.special = special_tokens_for(arch, self.decode_config.get("special"), self.decode_config.get("lang_ids"))
-        self._replicas = [_Replica(h, d, arch["n_mels"]) for h, d in handles]
+        self._replicas = [_Replica(h, d, arch["n_mels"], (arch["n_audio_ctx"], arch["d_model"])) for h, d in handles]
         self._set_alignment_heads(self.decode_config.get("alignment_heads"))
         self.max_batch, self.max_beam = max_batch, max_beam
         self._pick = threading.Lock()
@@ -573,6 +683,119 @@ class Whisper:
             raise ValueError("the Python face takes host arrays (WIS_IN_MEL_HOST or WIS_IN_PCM_HOST)")
         return a
 
+    @property
+    def _enc_shape(self):
+        a = getattr(self, "arch", None) or {}
+        return int(a.get("n_audio_ctx", W.N_AUDIO_CTX)), int(a.get("d_model", 0))
+
+    def _check_open(self):
+        if "_batcher" not in self.__dict__:
+            raise ValueError("this Whisper model is closed")
+
+    def _encoded(self, features):
+        """Encoder output recognised by what it is.  -> None: `features` are features.  (WIS_IN_ENC_DEV, device, [address per utterance],
+        [the block behind each address]): a device-resident StorageView of `encode` (or a list of them, utterances in order); whoever queues an
+        address keeps its block referenced beside it until the engine call has returned.  (WIS_IN_ENC_HOST, f32 array [B, n_audio_ctx, d_model]):
+        a host view or array of that shape - [B, n_mels, 3000] cannot be mistaken for it.  A device view that this model cannot decode - another
+        width, another GPU than any replica's, a closed model's - is a ValueError before the engine is reached."""
+        T, d = self._enc_shape
+        views = list(features) if isinstance(features, (list, tuple)) and len(features) and all(isinstance(v, StorageView) for v in features) else [features]
+        if any(isinstance(v, StorageView) and v.device == "cuda" for v in views):
+            if not all(isinstance(v, StorageView) and v.device == "cuda" for v in views):
+                raise ValueError("device-resident and host StorageViews cannot be mixed in one call")
+            self._check_open()
+            dev = views[0].device_index
+            ptrs, blocks = [], []
+            for v in views:
+                if len(v.shape) != 3 or tuple(v.shape[1:]) != (T, d):
+                    raise ValueError(f"encoder output must be [batch, {T}, {d}] for this model (d_model {d}), got {v.shape}")
+                owner = v._owner() if v._owner is not None else self
+                if owner is None or "_batcher" not in owner.__dict__:
+                    raise ValueError("this encoder output belongs to a Whisper model that has been closed")
+                if v.device_index != dev:
+                    raise ValueError(f"encoder output on devices {dev} and {v.device_index} in one call")
+                row = 2 * T * d
+                ptrs.extend(v.device_ptr + b * row for b in range(v.shape[0]))
+                blocks.extend([v._block] * v.shape[0])
+            if not any(r.device == dev for r in self._replicas):
+                raise ValueError(f"encoder output lives on device {dev}, where this model has no replica")
+            return _lib.WIS_IN_ENC_DEV, dev, ptrs, blocks
+        if len(views) != 1:
+            return None
+        a = features.array if isinstance(features, StorageView) else features
+        if isinstance(a, np.ndarray) and a.ndim == 3 and d > 0 and tuple(a.shape[1:]) == (T, d):
+            return _lib.WIS_IN_ENC_HOST, np.ascontiguousarray(a, np.float32)
+        return None
+
+    def _encoder_input(self, features, input_kind):
+        """_encoded for a call that also takes `input_kind`: the argument keeps meaning what it means for host feature arrays (any other value
+        than the default leaves the features to _features, which refuses device kinds as ever); WIS_IN_ENC_* insists on encoder output."""
+        if input_kind != _lib.WIS_IN_MEL_HOST and input_kind not in _ENCODED_KINDS:
+            return None
+        enc = self._encoded(features)
+        if enc is None and input_kind in _ENCODED_KINDS:
+            T, d = self._enc_shape
+            raise ValueError(f"input_kind {input_kind}: encoder output is a view `encode` returned or a float32 array [batch, {T}, {d}]")
+        if enc is not None:
+            self._check_open()
+        return enc
+
+    def _device_replica(self, device):
+        """the least-loaded replica on `device`, counted as in use until _release"""
+        with self._pick:
+            r = min((x for x in self._replicas if x.device == device), key=lambda x: x.inflight)
+            r.inflight += 1
+        return r
+
+    def encode(self, features, to_cpu=False, *, input_kind=_lib.WIS_IN_MEL_HOST, device=None):
+        """CTranslate2's `Whisper.encode(features, to_cpu=False)`: the encoder's output for every window of `features`, once, for every later
+        pass over them - `generate`, `detect_language` and `align` take the result in place of the features and then skip the log-mel and the
+        encoder (bit for bit what they compute from the features in a batch of the same size).  to_cpu=False: a device-resident StorageView
+        (device "cuda", dtype "float16", shape [B, n_audio_ctx, d_model]) that owns its block of device memory - freed with the last view of it -
+        and decodes on its own GPU only; to_cpu=True: the same values as a host view of f32.
+        `input_kind` (an extension of this shim): host mel windows, host PCM windows (WIS_IN_PCM_HOST), or - with `device`, the GPU they live on -
+        log-mel windows already in device memory (WIS_IN_MEL_DEV, what the seek loop's whole-recording log-mel hands out; `features`: one device
+        address or a list of them, one f32 [n_mels][3000] window each, which the caller keeps allocated until the call returns).
+        The windows go through the micro-batcher under a key of their own (EncodeKey): concurrent requests share encoder batches of up to
+        max_batch windows, as their decodes do.  Windows encoded in one engine call come back as they lie; more than max_batch, or windows that
+        shared batches with other requests, are gathered device-to-device into one block."""
+        self._check_open()
+        kind = int(input_kind)
+        if kind == _lib.WIS_IN_MEL_DEV:
+            if device is None:
+                raise ValueError("encode: features in device memory need `device`")
+            rows = [int(features)] if np.isscalar(features) else [int(p) for p in features]
+            dev = int(device)
+            if not any(r.device == dev for r in self._replicas):
+                raise ValueError(f"no replica on device {dev}")
+        elif kind in (_lib.WIS_IN_MEL_HOST, _lib.WIS_IN_PCM_HOST):
+            a = self._features(features, kind)
+            rows = [np.ascontiguousarray(a[b]) for b in range(a.shape[0])]
+            with self._pick:      # every window of the call on ONE GPU (the result is one block): the least loaded one
+                dev = min(self._replicas, key=lambda x: x.inflight).device if device is None else int(device)
+        else:
+            raise ValueError(f"encode: input_kind {input_kind} (host mel or PCM windows, or mel windows in device memory; encoder output is not encoded again)")
+        if not rows:
+            raise ValueError("encode: no windows")
+        parts = self._batcher.submit(EncodeKey(kind), rows, affinity=("device", dev))
+        for p in parts:
+            if p._owner is None:
+                p._owner = weakref.ref(self)
+        T, d = self._enc_shape
+        if parts[0].device != "cuda":      # (a host-only stand-in for the engine)
+            out = parts[0] if len(parts) == 1 else StorageView(np.ascontiguousarray(np.concatenate([p.array for p in parts])))
+            return out
+        row = 2 * T * d
+        if all(p._block is parts[0]._block and p._offset == parts[0]._offset + i * row for i, p in enumerate(parts)):
+            out = StorageView._on_device(parts[0]._block, [len(parts), T, d], self, parts[0]._offset)      # one engine call: as it lies
+        else:
+            block = _lib.DevBuf(len(parts) * row, dev)
+            lib = _lib.load()
+            for i, p in enumerate(parts):
+                _lib.check(lib.wis_dev_copy_peer(dev, C.c_void_p(block.ptr.value + i * row), dev, C.c_void_p(p.device_ptr), row))
+            out = StorageView._on_device(block, [len(parts), T, d], self)
+        return out.to_cpu() if to_cpu else out
+
     def generate(self, features, prompts, *, asynchronous=False, beam_size=5, patience=1, num_hypotheses=1, length_penalty=1,
                  repetition_penalty=1, no_repeat_ngram_size=0, max_length=448, return_scores=False, return_no_speech_prob=False,
                  max_initial_timestamp_index=50, suppress_blank=True, suppress_tokens=(-1,), sampling_topk=1,
@@ -595,17 +818,29 @@ class Whisper:
         unsorted) - openai-whisper's temperature fallback is `beam_size=1, num_hypotheses=best_of, sampling_topk=0, sampling_temperature=t`; in a beam
         search it returns the n best finished hypotheses, best first.  `sampling_seed` (an extension of this shim): an int for the call or one per
         utterance; None draws from os.urandom, or from a deterministic counter after `ctranslate2.set_random_seed`.  The same seed gives the same
-        samples, whatever else shares the device batch."""
-        opts, mel = self._decode_options(features, prompts, input_kind=input_kind, beam_size=beam_size, patience=patience, num_hypotheses=num_hypotheses,
+        samples, whatever else shares the device batch.
+        `features` may be what `encode` returned (a device-resident view, a slice or a list of them, or its host copy of shape [B, n_audio_ctx,
+        d_model]): the call then starts at the cross-K/V projection (WIS_IN_ENC_DEV / WIS_IN_ENC_HOST in the options' input_kind; `input_kind`
+        itself keeps describing host feature arrays).  A device view decodes on its own GPU."""
+        enc = self._encoder_input(features, input_kind)
+        if enc is not None:
+            n_utt = len(enc[2]) if enc[0] == _lib.WIS_IN_ENC_DEV else enc[1].shape[0]
+        opts, mel = self._decode_options(features if enc is None else None, prompts, input_kind=input_kind if enc is None else enc[0], n_utt=1 if enc is None else n_utt,
+                                         beam_size=beam_size, patience=patience, num_hypotheses=num_hypotheses,
                                          length_penalty=length_penalty, repetition_penalty=repetition_penalty, no_repeat_ngram_size=no_repeat_ngram_size,
                                          max_length=max_length, return_no_speech_prob=return_no_speech_prob, max_initial_timestamp_index=max_initial_timestamp_index,
                                          suppress_blank=suppress_blank, suppress_default=list(suppress_tokens) == [-1], sampling_topk=sampling_topk,
                                          sampling_temperature=sampling_temperature, fixed_new_tokens=fixed_new_tokens, draft_tokens=draft_tokens,
                                          draft_trajectory=draft_trajectory, return_trajectory=return_trajectory)
         seeds = _seeds(opts, sampling_seed, len(prompts))
+        if enc is not None and enc[0] == _lib.WIS_IN_ENC_DEV:
+            # every row carries the block its address points into: the rows themselves keep the device memory allocated until _run_batch has returned
+            return self._batcher.submit(opts, [(enc[2][b], [int(t) for t in prompts[b]], seeds[b], enc[3][b]) for b in range(len(prompts))], affinity=("device", enc[1]))
+        if enc is not None:
+            mel = enc[1]
         return self._batcher.submit(opts, [(np.ascontiguousarray(mel[b]), [int(t) for t in prompts[b]], seeds[b]) for b in range(len(prompts))])
 
-    def _decode_options(self, features, prompts, *, input_kind, beam_size, patience, num_hypotheses, length_penalty, repetition_penalty, no_repeat_ngram_size,
+    def _decode_options(self, features, prompts, *, input_kind, n_utt=1, beam_size, patience, num_hypotheses, length_penalty, repetition_penalty, no_repeat_ngram_size,
                         max_length, return_no_speech_prob, max_initial_timestamp_index, suppress_blank, suppress_default, sampling_topk, sampling_temperature,
                         fixed_new_tokens, draft_tokens, draft_trajectory, return_trajectory):
         """Every check of a decode call, for `generate` (features: host arrays, one prompt each) and `generate_from_device` (features None: ONE
@@ -617,7 +852,7 @@ class Whisper:
             raise ValueError(f"num_hypotheses {s_n} outside 1..{self.max_beam} (setting max_beam: decoder rows per utterance)")
         rep_p, rep_n = _check_repetition(repetition_penalty, no_repeat_ngram_size, drafted)
         mel = None if features is None else self._features(features, input_kind)
-        B = 1 if mel is None else mel.shape[0]
+        B = int(n_utt) if mel is None else mel.shape[0]      # (features None: utterances already on the device, or encoder output the caller resolved)
         if len(prompts) != B:
             raise ValueError("one prompt per batch item")
         P = len(prompts[0])
@@ -723,7 +958,18 @@ class Whisper:
         `.text_token_probs`.  Signature and result are restated from CTranslate2's documentation; the real library cannot be
         installed here to pin them against.  `input_kind` is an extension of this shim (host mel windows or host PCM windows, as `generate`
         takes them).  `features` on the device: `StorageView`s are host arrays in this shim; a device
-        pointer goes through `align_from_device`."""
+        pointer goes through `align_from_device`.  Encoder output (`encode`'s view, a slice of it, or its host copy) is taken in place of
+        the features, as in `generate`."""
+        enc = self._encoder_input(features, input_kind)
+        if enc is not None and enc[0] == _lib.WIS_IN_ENC_DEV:
+            r = self._device_replica(enc[1])
+            try:
+                return self._align(None, None, _lib.WIS_IN_ENC_DEV, len(enc[2]), start_sequence, text_tokens, num_frames, width=median_filter_width,
+                                   dev=(r, enc[2], r.enc_bytes))
+            finally:
+                self._release(r)
+        if enc is not None:
+            return self._align(enc[1], _lib.ptr, _lib.WIS_IN_ENC_HOST, enc[1].shape[0], start_sequence, text_tokens, num_frames, width=median_filter_width)
         mel = self._features(features, input_kind)
         return self._align(mel, _lib.ptr, input_kind, mel.shape[0], start_sequence, text_tokens, num_frames, width=median_filter_width)
 
@@ -761,7 +1007,10 @@ class Whisper:
                     cap = n_ctx + n_audio
                     pt, pf = np.zeros((b, cap), np.int32), np.zeros((b, cap), np.int32)
                     pl, probs = np.zeros(b, np.int32), np.zeros((b, n_ctx), np.float32)
-                    src = dev[1] if dev else to_ptr(np.ascontiguousarray(mel[s:s + b]))
+                    if dev and len(dev) > 2:      # (replica, [address per utterance], bytes per utterance): encoder output on the replica's GPU
+                        src = C.c_void_p(_gather_device_rows(r, dev[1][s:s + b], dev[2]))
+                    else:
+                        src = dev[1] if dev else to_ptr(np.ascontiguousarray(mel[s:s + b]))
                     _lib.check(_lib.load().wis_align(r.handle, src, kind, b, i32(start), len(start), i32(flat), i32(lens), i32(frames), int(width),
                                                      i32(pt), i32(pf), i32(pl), probs.ctypes.data_as(C.POINTER(C.c_float))))
                     for u in range(b):
@@ -773,18 +1022,28 @@ class Whisper:
         return out
 
     def detect_language(self, features, input_kind=_lib.WIS_IN_MEL_HOST):
-        mel = self._features(features, input_kind)
-        B = mel.shape[0]
+        """`features`: host feature windows, or encoder output as `generate` takes it (`encode`'s view, a slice of it, its host copy)."""
+        enc = self._encoder_input(features, input_kind)
+        ptrs = None
+        if enc is not None and enc[0] == _lib.WIS_IN_ENC_DEV:
+            input_kind, ptrs, B = _lib.WIS_IN_ENC_DEV, enc[2], len(enc[2])
+        else:
+            mel = self._features(features, input_kind) if enc is None else enc[1]
+            input_kind, B = (input_kind if enc is None else _lib.WIS_IN_ENC_HOST), mel.shape[0]
         n_lang, codes = len(self.special.lang_ids), self.special.lang_codes
         out = []
-        r = self._acquire()
+        r = self._acquire() if ptrs is None else self._device_replica(enc[1])
         try:
             with r.lock:
                 for s in range(0, B, self.max_batch):
-                    m = mel[s:s + self.max_batch]
-                    probs = np.zeros((m.shape[0], n_lang), np.float32)
-                    m = np.ascontiguousarray(m)
-                    _lib.check(_lib.load().wis_detect_language(r.handle, _lib.ptr(m), input_kind, m.shape[0],
+                    if ptrs is not None:
+                        b = len(ptrs[s:s + self.max_batch])
+                        src = C.c_void_p(_gather_device_rows(r, ptrs[s:s + b], r.enc_bytes))
+                    else:
+                        m = np.ascontiguousarray(mel[s:s + self.max_batch])
+                        b, src = m.shape[0], _lib.ptr(m)
+                    probs = np.zeros((b, n_lang), np.float32)
+                    _lib.check(_lib.load().wis_detect_language(r.handle, src, input_kind, b,
                                                                probs.ctypes.data_as(C.POINTER(C.c_float))))
                     for row in probs:
                         order = np.argsort(-row, kind="stable")

@@ -67,10 +67,12 @@ def split_window(tokens, timestamp_begin, time_offset, segment_size):
 
 
 def transcribe(long_mel, decode, *, start, special, initial_prompt_ids=(), n_text_ctx=448, temperatures=(), best_of=5, compression_ratio_threshold=None,
-               logprob_threshold=None, no_speech_threshold=0.6, condition_on_previous_text=True, text_of=None, on_window=None):
+               logprob_threshold=None, no_speech_threshold=0.6, condition_on_previous_text=True, text_of=None, on_window=None, encode=None):
     """The loop of the module text.  long_mel: `.frames` and `.window(seek)`; start: the start sequence WITHOUT <|notimestamps|>; special: the
     model's SpecialTokens (timestamp_begin, eot, startofprev); text_of: tokens -> text for the fallback's compression ratio (None: off);
     on_window(window, seek, segment_size, segments): called for every kept window while `window` is still valid (word alignment).
+    encode(window, seek): called once per window; what it returns (the window's encoder output, say) is what `decode` and `on_window` get as
+    `window` - every decode of the fallback and the alignment then read one encoder pass.
     -> dict(segments=[{start, end, tokens, ...}], windows=[one dict per decoded window: seek, segment_size, prompt, tokens, temperature,
     avg_logprob, no_speech_prob, skipped, advance], fallback=the last kept decode's decode_with_fallback result)"""
     tb, eot = special.timestamp_begin, special.eot
@@ -83,6 +85,8 @@ def transcribe(long_mel, decode, *, start, special, initial_prompt_ids=(), n_tex
         time_offset = round(seek * FRAME_S, 2)
         prompt = assemble_prompt(start, special, list(initial_prompt_ids) + history, (), n_text_ctx)
         window = long_mel.window(seek)
+        if encode is not None:
+            window = encode(window, seek)
         nsp = [0.0]
 
         def step(t, n):

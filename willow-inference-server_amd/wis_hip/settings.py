@@ -48,6 +48,9 @@ class APISettings:
     # log-mel on the replica's GPU inside generate (PCM in, mel never leaves HBM) instead of the reference's
     # mel -> host -> StorageView round trip; results are identical (same kernels)
     fuse_logmel: bool = True
+    # a request that reads a window more than once (language detection, translate, word_timestamps, a temperature fallback) encodes its windows
+    # once (Whisper.encode) and every pass starts from the encoder's output; a request that reads its windows once is served the same either way
+    encode_once: bool = False
     # an upload at another rate than 16 kHz (main.py:579: librosa.load(audio_file, sr=16000)) is resampled on one of the model's own GPUs
     # (wis_resample, csrc/resample.hip) instead of in numpy on the request thread; False: the host resampler.  The two agree to f32
     # rounding, not bit for bit

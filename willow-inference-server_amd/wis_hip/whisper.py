@@ -553,10 +553,28 @@ def do_whisper(audio_file, model, beam_size=None, task="transcribe", detect_lang
     total_chunk_count = features.shape[0]
     tokenizer = models.tokenizer_for(model)
     ip_ids, px_ids = _request_prompt_ids(q, tokenizer, special)
+    ccg = s.concurrent_gpu_chunks
+    translating = translate and total_chunk_count <= ccg
+    # encode_once: a request that reads a window more than once - language detection, the temperature fallback, the word alignment, the
+    # translation pass - encodes its windows ONCE (Whisper.encode, in the groups the decode uses) and hands the views to every pass; a request that
+    # reads its windows once is served as ever: no encode call, the same input kind, the same batch key
+    reads = int(bool(q.detect_language and not q.force_language)) + max(1, len(temps)) + int(bool(word_timestamps)) + int(bool(translating))
+    views = None
+    if getattr(s, "encode_once", False) and reads > 1:
+        views = [whisper_model.encode(ctranslate2.StorageView.from_array(np.ascontiguousarray(batch)), input_kind=kind) for batch in chunkit(features, ccg)]
+
+    def windows_of(lo, hi):
+        """(what generate / detect_language / align take for windows lo .. hi - 1 (inside one decode group), their input_kind argument)"""
+        if views is None:
+            return ctranslate2.StorageView.from_array(np.ascontiguousarray(features[lo:hi])), dict(input_kind=kind)
+        g = lo // ccg
+        return views[g][lo - g * ccg:hi - g * ccg], {}
 
     # STEP 2 — language
-    language = _request_language(q, s, special, lambda: whisper_model.detect_language(
-        ctranslate2.StorageView.from_array(np.ascontiguousarray(features[0:1])), input_kind=kind))
+    def detect():
+        f, k = windows_of(0, 1)
+        return whisper_model.detect_language(f, **k)
+    language = _request_language(q, s, special, detect)
     task_id = special.translate if task == "translate" else special.transcribe
     start = [special.sot, special.language_token_id(language), task_id] + ([] if timestamps else [special.notimestamps])
     prompt = assemble_prompt(start, special, ip_ids, px_ids, _n_text_ctx(whisper_model))
@@ -564,18 +582,19 @@ def do_whisper(audio_file, model, beam_size=None, task="transcribe", detect_lang
     # STEP 3 — run the model, `concurrent_gpu_chunks` windows per generate call
     results = []
     if temps:      # one window, openai-whisper's decode_with_fallback around it
-        feats = ctranslate2.StorageView.from_array(np.ascontiguousarray(features[0:1]))
+        feats, fkind = windows_of(0, 1)
 
         def decode(t, n):
-            r = whisper_model.generate(feats, [prompt], return_scores=True, fixed_new_tokens=fixed_new_tokens, input_kind=kind, **_search(q, t, n), **rep)[0]
+            r = whisper_model.generate(feats, [prompt], return_scores=True, fixed_new_tokens=fixed_new_tokens, **fkind, **_search(q, t, n), **rep)[0]
             return list(zip(r.sequences_ids, r.scores))
         fb = decode_with_fallback(decode, temps, best_of, q.compression_ratio_threshold, q.logprob_threshold, _text_of(tokenizer, special.timestamp_begin))
         results.append(ctranslate2.WhisperGenerationResult([fb["tokens"]], [fb["score"]]))
         results[0].fallback = fb
-    for batch in ([] if temps else chunkit(features, s.concurrent_gpu_chunks)):
-        feats = ctranslate2.StorageView.from_array(np.ascontiguousarray(batch))
-        results.extend(whisper_model.generate(feats, [prompt] * len(batch), beam_size=q.beam_size, return_scores=False,
-                                              fixed_new_tokens=fixed_new_tokens, input_kind=kind, **rep))
+    for lo in ([] if temps else range(0, total_chunk_count, ccg)):
+        hi = min(lo + ccg, total_chunk_count)
+        feats, fkind = windows_of(lo, hi)
+        results.extend(whisper_model.generate(feats, [prompt] * (hi - lo), beam_size=q.beam_size, return_scores=False,
+                                              fixed_new_tokens=fixed_new_tokens, **fkind, **rep))
     assert len(results) == total_chunk_count, "Result length doesn't match expected total_chunk_count"
     if use_chunking:
         tokens = audio.find_longest_common_sequence([(results[i].sequences_ids[0], strides[i]) for i in range(total_chunk_count)],
@@ -590,8 +609,8 @@ def do_whisper(audio_file, model, beam_size=None, task="transcribe", detect_lang
         if word_timestamps:
             text_tokens = [t for sg in segments for t in sg["tokens"]]
             num_frames = max(2, min(3000, -(-pcm.shape[0] // audio.HOP_LENGTH)))
-            al = whisper_model.align(ctranslate2.StorageView.from_array(np.ascontiguousarray(features[0:1])), start[:3], [text_tokens], [num_frames],
-                                     input_kind=kind)[0]
+            feats, fkind = windows_of(0, 1)
+            al = whisper_model.align(feats, start[:3], [text_tokens], [num_frames], **fkind)[0]
             words_from_alignment(segments, al.alignments, al.text_token_probs, tokenizer, language, special, duration)
             for sg in segments:
                 del sg["tokens"]
@@ -600,10 +619,10 @@ def do_whisper(audio_file, model, beam_size=None, task="transcribe", detect_lang
         text = tokenizer.decode(tokens).strip()
 
     translation = None
-    if translate and total_chunk_count <= s.concurrent_gpu_chunks:       # main.py:729-748 (its `len(int)` bug aside: short audio only)
+    if translating:       # main.py:729-748 (its `len(int)` bug aside: short audio only)
         tprompt = [special.sot, special.language_token_id(language), special.translate, special.notimestamps]
-        feats = ctranslate2.StorageView.from_array(np.ascontiguousarray(features))
-        tres = whisper_model.generate(feats, [tprompt] * total_chunk_count, beam_size=q.beam_size, fixed_new_tokens=fixed_new_tokens, input_kind=kind, **rep)
+        feats, fkind = windows_of(0, total_chunk_count)
+        tres = whisper_model.generate(feats, [tprompt] * total_chunk_count, beam_size=q.beam_size, fixed_new_tokens=fixed_new_tokens, **fkind, **rep)
         translation = tokenizer.decode(tres[0].sequences_ids[0]).strip()
         out_translation_tokens = tres[0].sequences_ids[0]
     else:
@@ -631,13 +650,37 @@ def _do_whisper_seek(q, models, model, whisper_model, pcm, audio_duration, first
     long_mel = None
     try:
         long_mel = audio.LongMel(pcm, n_mels=getattr(whisper_model, "n_mels", audio.N_MELS), device=replica.device)
-        language = _request_language(q, models.settings, special, lambda: whisper_model.detect_language(
-            ctranslate2.StorageView.from_array(np.ascontiguousarray(long_mel.window(0, to_host=True)[None]))))
+        # encode_once: a window the transcription loop reads more than once (the fallback's temperatures, the word alignment) is encoded once
+        # (Whisper.encode from the window's device features) and its decodes and the alignment read the view; language detection shares the
+        # first window's view with the loop.  A loop that reads its windows once is served as ever
+        once = bool(getattr(models.settings, "encode_once", False))
+        detecting = bool(q.detect_language and not q.force_language)
+        multi = once and (q.word_timestamps or len(q.temps) > 1)
+        first = {}      # the view of the window at seek 0, while language detection and the loop's first window share it
+
+        def encoded(window):
+            return whisper_model.encode(window, input_kind=ctranslate2._lib.WIS_IN_MEL_DEV, device=replica.device)
+
+        def encode(window, seek):
+            if seek == 0 and first:
+                return first.pop(0)
+            return encoded(window) if multi else window
+
+        def detect():
+            if not once:
+                return whisper_model.detect_language(ctranslate2.StorageView.from_array(np.ascontiguousarray(long_mel.window(0, to_host=True)[None])))
+            first[0] = encoded(long_mel.window(0))
+            return whisper_model.detect_language(first[0])
+        language = _request_language(q, models.settings, special, detect)
         start = [special.sot, special.language_token_id(language), special.translate if q.task == "translate" else special.transcribe]
 
         def decode(window, prompt, t, n):
-            r = whisper_model.generate_from_device(replica.device, window, prompt, replica=replica, fixed_new_tokens=q.fixed_new_tokens, return_scores=True,
-                                                   return_no_speech_prob=True, **_search(q, t, n), **q.rep)
+            if isinstance(window, ctranslate2.StorageView):
+                r = whisper_model.generate(window, [prompt], fixed_new_tokens=q.fixed_new_tokens, return_scores=True, return_no_speech_prob=True,
+                                           **_search(q, t, n), **q.rep)[0]
+            else:
+                r = whisper_model.generate_from_device(replica.device, window, prompt, replica=replica, fixed_new_tokens=q.fixed_new_tokens, return_scores=True,
+                                                       return_no_speech_prob=True, **_search(q, t, n), **q.rep)
             return list(zip(r.sequences_ids, r.scores)), r.no_speech_prob
 
         def on_window(window, seek, segment_size, segs):
@@ -646,7 +689,10 @@ def _do_whisper_seek(q, models, model, whisper_model, pcm, audio_duration, first
                 for sg in segs:
                     sg["words"] = []
                 return
-            al = whisper_model.align_from_device(replica.device, window, start, [text_tokens], max(2, segment_size), replica=replica)[0]
+            if isinstance(window, ctranslate2.StorageView):
+                al = whisper_model.align(window, start, [text_tokens], max(2, segment_size))[0]
+            else:
+                al = whisper_model.align_from_device(replica.device, window, start, [text_tokens], max(2, segment_size), replica=replica)[0]
             timed = [dict(tokens=[t for t in sg["tokens"] if t < special.eot]) for sg in segs]
             words_from_alignment(timed, al.alignments, al.text_token_probs, tokenizer, language, special, segment_size * longform.FRAME_S)
             off = round(seek * longform.FRAME_S, 2)
@@ -660,7 +706,8 @@ def _do_whisper_seek(q, models, model, whisper_model, pcm, audio_duration, first
                     condition_on_previous_text=q.condition_on_previous_text)
         res = longform.transcribe(long_mel, decode, start=start, initial_prompt_ids=ip_ids, temperatures=q.temps, best_of=q.best_of,
                                   compression_ratio_threshold=q.compression_ratio_threshold, text_of=_text_of(tokenizer, special.eot),
-                                  on_window=on_window if q.word_timestamps else None, **loop)
+                                  on_window=on_window if q.word_timestamps else None, encode=encode if once and (multi or first) else None, **loop)
+        first.clear()
         translation = translation_tokens = None
         if q.translate:
             # the translation pass: the same loop with the translate task - unprompted, one search per window (no fallback), the repetition
