@@ -491,6 +491,10 @@ int wis_op_gemv(int device, const void* x, const float* gamma, const float* beta
 /* the one-utterance FFN2 / cross-attention out-projection form of that GEMM (x f16 [M][K], K = 1280 or 5120, M x K / 8 <= 3328, M <= 16) on
  * sixteen-column (cols = 16) or eight-column (cols = 8) workgroup tiles of the same W; N a multiple of cols.  flags: 1, 2, 4 as above;
  * y16: optional f16 copy of the rows under flag 2, else null. */
+/* cols = 5: the stage as the decode step assembles it for a projection that carries the sixteen-column image and, where the model loader would add one,
+ * the five-column image (FFN2: K = 5120, f16 rows, N a multiple of 5, N / 5 workgroups in one dispatch round on the device).  The step's own predicate
+ * picks the kernel: a shape it refuses runs on sixteen-column tiles (N a multiple of 4 then; any M <= 16 and K % 128 == 0 that launch_gemv serves).
+ * flags with cols = 5: additionally 32 = quantise W to per-row int8 first (no five-column image then). */
 int wis_op_gemv_cols(int device, const void* x_f16, const void* W_f16, const float* bias, void* y, void* y16,
                      int M, int N, int K, int flags, int cols);
 

@@ -209,6 +209,51 @@ int launch_pack_gemv_nc8(hipStream_t st, const f16* W, f16* Wp, int N, int Npad,
 // K = 1280 and 5120 (SC 10 and 40), as many rows as its register staging holds
 bool gemv_nc8_shape(int M, int N, int K) { return (K == 1280 || K == 5120) && N % 8 == 0 && M >= 1 && M <= 16 && M * (K / 8) <= 13 * 256; }
 
+// The five-column image (gemv_nc5_kernel): [N/5 slabs][K/32/kw wave K-ranges][ceil(kw/3) requests][64 lanes][8 f16].  A wave request is one
+// full KiB, five columns x THREE k-steps: lane l carries A-fragment row l & 15 and k-quarter l >> 4; rows 0-4 hold the slab's columns for k-step 3u of the
+// K-range, rows 5-9 for 3u + 1, rows 10-14 for 3u + 2, row 15 is zero.  The last request of a K-range carries the one or two k-steps left over (kw = 40: one,
+// kw = 20: two), the unused rows zero.  16/15 of the sixteen-column image's bytes, plus the ragged last requests: 12 % more at kw = 40.
+__global__ void pack_gemv_nc5_kernel(const f16* __restrict__ W, f16* __restrict__ Wp, int N, int K, int kw) {
+  const int rq = (kw + 2) / 3, nr = K / 32 / kw;
+  const size_t total = (size_t)(N / 5) * nr * rq * 64;
+  for (size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (size_t)gridDim.x * blockDim.x) {
+    const int l = (int)(idx & 63);
+    size_t t = idx >> 6;
+    const int u = (int)(t % rq); t /= rq;
+    const int rg = (int)(t % nr), slab = (int)(t / nr);
+    const int row = l & 15, j = row / 5, ksl = 3 * u + j;
+    const int n = 5 * slab + (row - 5 * j), k = 32 * (rg * kw + ksl) + 8 * (l >> 4);
+    f16x8 v;
+    if (row < 15 && ksl < kw) v = *reinterpret_cast<const f16x8*>(W + (size_t)n * K + k);
+    else {
+#pragma unroll
+      for (int e = 0; e < 8; ++e) v[e] = (f16)0.f;
+    }
+    *reinterpret_cast<f16x8*>(Wp + idx * 8) = v;
+  }
+}
+size_t gemv_nc5_elems(int N, int K, int kw) { return (size_t)(N / 5) * (K / 32 / kw) * ((kw + 2) / 3) * 512; }
+int launch_pack_gemv_nc5(hipStream_t st, const f16* W, f16* Wp, int N, int K, int kw) {
+  if (N < 5 || N % 5 || K % 32 || kw < 1 || (K / 32) % kw) { set_error("pack_gemv_nc5: bad shape N=%d K=%d kw=%d", N, K, kw); return WIS_E_ARG; }
+  const size_t total = gemv_nc5_elems(N, K, kw) / 8;
+  int blocks = (int)((total + 255) / 256); if (blocks > 4096) blocks = 4096;
+  hipLaunchKernelGGL(pack_gemv_nc5_kernel, dim3(blocks), dim3(256), 0, st, W, Wp, N, K, kw);
+  return WIS_OK;
+}
+// the launches launch_gemv runs on five-column slabs (GemvP::rows = 5, Wp that image with kw = 40): K = 5120, f16 rows (FFN2; four waves split K), plain /
+// residual epilogues, as many rows as the register staging holds, N / 5 workgroups in ONE dispatch round on this device - a part with fewer CUs than workgroups
+// keeps the other forms (a second round costs more than the requests saved)
+static int device_cu_count() {
+  static int cus[64];
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 0;
+  if (!cus[dev]) { int v = 0; if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) v = 0; cus[dev] = v > 0 ? v : -1; }
+  return cus[dev] > 0 ? cus[dev] : 0;
+}
+bool gemv_nc5_shape(int M, int N, int K, int flags) {
+  return K == 5120 && M >= 1 && M * (K / 8) <= 13 * 256 && N >= 5 && N % 5 == 0 && !(flags & ~(GV_RESID | GV_OUT_F32 | GV_GELU)) && N / 5 <= device_cu_count();
+}
+
 // 8-byte {tag, value} granules: one relaxed agent-scope (write-through) store each, "the data is the flag" (guide G16 form R2) - the hand-off of the
 // decoder cross-attention's chunk partials (dec_cross_attn_kernel SPIN).  Lesson of the three in-launch hand-offs that were tried for the step's other
 // stages and lost (retired experiments): an in-launch hand-off is two fabric round trips (granule store -> L2 -> poll), like a kernel boundary.
@@ -246,7 +291,10 @@ constexpr unsigned CA_SPIN_LIMIT = 1u << 17;      // sweeps before the combiner 
 // one-utterance FFN2 and cross-attention out-projection run on 160 workgroups instead of 80.  Per request two MFMAs: the registers as they landed against
 // the even k-step's activations, then the same registers rotated by eight lanes within each row of 16 (DPP row_ror:8: the odd k-step's weights arrive in
 // rows 0-7) against the odd k-step's.  Rows 0-7 of the accumulator thus see the wave's k-steps in today's order, each through the same MFMA, and the
-// cross-wave reduction is unchanged: bit-identical outputs.  Rows 8-15 of the accumulator are by-products nobody reads.
+// cross-wave reduction is unchanged: bit-identical outputs.  Rows 8-15 of the accumulator are by-products nobody reads.  Today the cross-attention
+// out-projection (K = d) runs this form; FFN2 (K = 4d) moved on to FIVE-column slabs, three k-steps per request, N / 5 = 256 workgroups at large's width -
+// a kernel of its own below (gemv_nc5_kernel), so that this body keeps its instructions.  FFN1 on such slabs (four per workgroup in NT = 2's place) measured
+// slower and stays on NT = 2.
 template <int MB, int MODE, int SC, int RM, bool W8, int NT = 1, int NC = 16>
 __device__ __forceinline__ void gemv_body(const GemvP& p, const int KC, const int nt, char* smem) {
   static_assert(NT == 1 || (NT == 2 && MB == 1 && SC > 0), "two-tile workgroups: <= 16 rows, every fragment prefetched");
@@ -636,8 +684,115 @@ int launch_gemv_dual(hipStream_t st, const GemvP& pa, const GemvP& pb) {
   return WIS_OK;
 }
 
+// ---- five-column slabs (the one-utterance FFN2 on 256 workgroups; image: pack_gemv_nc5_kernel) -------------------------------------------------------
+// The NC = 8 idea with three k-steps per request.  Per request three MFMAs: the registers as they landed against the activations of k-step 3u, the same
+// registers rotated left by five lanes within each row of 16 (rows 5-9 arrive in rows 0-4) against 3u + 1, rotated left by ten against 3u + 2.  Rows 0-4 of
+// an accumulator see their k-steps in the sixteen-column order, each through the same MFMA; rows 5-15 are by-products nobody reads.
+// DPP row_ror:n hands lane l the registers of lane (l - n) & 15 of its row: left by five is row_ror:11, left by ten row_ror:6.
+// The requests go out in index order and request u's rotations stay behind request u - 1's MFMAs (only LDS reads and scalar work may cross): vmcnt retires
+// in order, so the wave waits for ONE more request at a time and its MFMAs run while the rest of the stream is in flight.  Left alone, hipcc issued the loads
+// out of order and hoisted the rotations - the wave then waited for the whole stream in front of its fifth request, and read each B operand from LDS one MFMA ahead.  (The same schedule on the eight-column
+// kernel gained at K = 4d and lost 0.5 us per launch at K = d in the eager trace: that body is left as it was.)
+#define GV_IN_ORDER() __builtin_amdgcn_sched_barrier(0x104)
+template <int CTRL>
+__device__ __forceinline__ f16x8 nc5_rot(const u32x4& w) {
+  u32x4 r;
+#pragma unroll
+  for (int e = 0; e < 4; ++e) r[e] = (unsigned)__builtin_amdgcn_update_dpp(0, (int)w[e], CTRL, 0xf, 0xf, false);
+  return *reinterpret_cast<const f16x8*>(&r);
+}
+// Five columns are 20 / 10 bytes of a row: the epilogue's lanes address them at element, not vector, alignment (gfx950 takes global accesses at any alignment).
+// Lanes with k-quarter 0 hold local columns 0-3 of the accumulator, lanes with k-quarter 1 local column 4 in element 0: the latter move it to element 3 and
+// address the four columns that END at the slab's last one (`5 slab + kq`), so one request per operand serves both groups and nothing past the row is read.
+__device__ __forceinline__ f32x4 ld4_f32(const float* p) { f32x4 v; __builtin_memcpy(&v, p, 16); return v; }
+// (component by component: a sum of ext-vector values lowers to packed-f32 instructions, which no kernel with MFMAs may contain - tools/isa_lint.py)
+__device__ __forceinline__ f32x4 add4_f32(const f32x4& a, const f32x4& b) { return f32x4{a[0] + b[0], a[1] + b[1], a[2] + b[2], a[3] + b[3]}; }
+__device__ __forceinline__ void st_nc5_f32(float* p, const f32x4& v, int kq) { if (kq) p[3] = v[3]; else __builtin_memcpy(p, &v, 16); }
+__device__ __forceinline__ void st_nc5_f16(f16* p, const f32x4& v, int kq) {
+  const f16x4 h = {(f16)v[0], (f16)v[1], (f16)v[2], (f16)v[3]};
+  if (kq) p[3] = h[3]; else __builtin_memcpy(p, &h, 8);
+}
+// FFN2's form: gemv_body MODE 2 (f16 rows, staged from registers) on slab blockIdx.x; the four waves take a K quarter of SC k-steps each - ceil(SC / 3)
+// requests, all up front -, meet in LDS and wave 0 finishes the five columns as gemv_body finishes sixteen: per element the same sums in the same order.
+template <int SC>
+__global__ __launch_bounds__(256) void gemv_nc5_kernel(WIS_GV_LEAD_DECL(l_), int KC, GemvP p) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  WIS_GV_LEAD_APPLY(p, l_);
+  (void)KC;
+  constexpr int K = SC * 128, RQ = (SC + 2) / 3, xstr = K + 8, c8 = K / 8, NXH = 13;
+  const int M = p.M;
+  f16* xs = reinterpret_cast<f16*>(smem);
+  float* red = reinterpret_cast<float*>(smem + (((size_t)M * xstr * 2 + 15) & ~(size_t)15));
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, slab = blockIdx.x;
+  unsigned long long* pf = (slab == 0 && tid == 0) ? p.prof : nullptr;
+  if (tid == 0) tl_begin(p.prof);
+  stamp(pf, 0);
+  u32x4 xh[NXH];
+  const int nx = M * c8;
+  const u32x4* x8 = reinterpret_cast<const u32x4*>(p.x);
+#pragma unroll
+  for (int i = 0; i < NXH; ++i) { const int idx = tid + 256 * i; if (idx < nx) xh[i] = x8[idx]; }
+  const u32x4* wp4 = reinterpret_cast<const u32x4*>(p.Wp) + ((size_t)slab * 4 + wave) * RQ * 64 + lane;
+  u32x4 wf[RQ];
+#pragma unroll
+  for (int u = 0; u < RQ; ++u) { wf[u] = __builtin_nontemporal_load(wp4 + (size_t)u * 64); GV_IN_ORDER(); }
+  stamp(pf, 1);
+#pragma unroll
+  for (int i = 0; i < NXH; ++i) {
+    const int idx = tid + 256 * i;
+    if (idx < nx) { const int row = idx / c8, k8 = idx - row * c8; *reinterpret_cast<u32x4*>(xs + (size_t)row * xstr + k8 * 8) = xh[i]; }
+  }
+  __syncthreads();
+  stamp(pf, 3);
+  f32x4 acc = f32x4{0.f, 0.f, 0.f, 0.f};
+  const int m = lane & 15, kq = lane >> 4;
+  const f16* xw = xs + (m < M ? m : M - 1) * xstr + 8 * kq + wave * SC * 32;
+  // the wave's B operands, all SC k-steps, into registers while its weights are in flight (one workgroup per CU: the register file is this wave's): read
+  // one MFMA ahead, each LDS round trip sat between two MFMAs of a wave whose weights had all landed
+  f16x8 xb[SC];
+#pragma unroll
+  for (int k = 0; k < SC; ++k) xb[k] = *reinterpret_cast<const f16x8*>(xw + k * 32);
+  __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+  for (int u = 0; u < RQ; ++u) {
+    acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(*reinterpret_cast<const f16x8*>(&wf[u]), xb[3 * u], acc, 0, 0, 0);
+    if (3 * u + 1 < SC) acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(nc5_rot<0x12B>(wf[u]), xb[3 * u + 1 < SC ? 3 * u + 1 : 0], acc, 0, 0, 0);
+    if (3 * u + 2 < SC) acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(nc5_rot<0x126>(wf[u]), xb[3 * u + 2 < SC ? 3 * u + 2 : 0], acc, 0, 0, 0);
+    GV_IN_ORDER();
+  }
+  stamp(pf, 4);
+  // epilogue operands, requested behind the stream and covered by the reduction barrier, as in gemv_body
+  const bool ep_ok = wave == 0 && m < M && kq < 2;
+  const size_t o = (size_t)m * p.N + 5 * slab + kq;
+  f32x4 ep_bias = f32x4{0.f, 0.f, 0.f, 0.f}, ep_res = ep_bias;
+  if (ep_ok) {
+    if (p.bias) ep_bias = ld4_f32(p.bias + 5 * slab + kq);
+    if (p.flags & GV_RESID) ep_res = ld4_f32(reinterpret_cast<const float*>(p.y) + o);
+  }
+  *reinterpret_cast<f32x4*>(red + ((size_t)wave * 64 + lane) * 4) = acc;
+  __syncthreads();
+  stamp(pf, 5);
+  if (wave == 0) {
+    f32x4 s = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int w = 0; w < 4; ++w) s = add4_f32(s, *reinterpret_cast<const f32x4*>(red + ((size_t)w * 64 + lane) * 4));
+    if (ep_ok) {
+      if (kq) s[3] = s[0];
+      s = add4_f32(s, ep_bias);
+      if (p.flags & GV_GELU) { s[0] = gelu_erf(s[0]); s[1] = gelu_erf(s[1]); s[2] = gelu_erf(s[2]); s[3] = gelu_erf(s[3]); }
+      if (p.flags & GV_RESID) {
+        const f32x4 r = add4_f32(ep_res, s);
+        st_nc5_f32(reinterpret_cast<float*>(p.y) + o, r, kq);
+        if (p.y16) st_nc5_f16(p.y16 + o, r, kq);
+      } else if (p.flags & GV_OUT_F32) st_nc5_f32(reinterpret_cast<float*>(p.y) + o, s, kq);
+      else st_nc5_f16(reinterpret_cast<f16*>(p.y) + o, s, kq);
+    }
+  }
+  stamp(pf, 6);
+  if (tid == 0) tl_end(p.prof);
+}
 int launch_gemv(hipStream_t st, const GemvP& p) {
-  if (p.M < 1 || p.M > 16 || p.K % 128 || p.N % 4) { set_error("gemv: M=%d N=%d K=%d unsupported (the LDS-staged form holds one 16-row block; more rows take launch_gemv_frag)", p.M, p.N, p.K); return WIS_E_UNSUPPORTED; }
+  if (p.M < 1 || p.M > 16 || p.K % 128 || (p.N % 4 && p.rows != 5)) { set_error("gemv: M=%d N=%d K=%d unsupported (the LDS-staged form holds one 16-row block; more rows take launch_gemv_frag)", p.M, p.N, p.K); return WIS_E_UNSUPPORTED; }
   // largest K-chunk (multiple of 128 dividing K) whose f16 image of M rows fits 64 KiB of LDS (several workgroups per CU)
   int KC = p.K;
   const size_t aux = (size_t)4 * 64 * 16 + MAX_ROWS * 8 + 4 * 16 * 4 + 16;   // red + stats + sred (+ alignment)
@@ -668,6 +823,13 @@ int launch_gemv(hipStream_t st, const GemvP& p) {
   }
   const int sck = KC / 128;
   const int sc = (KC == p.K && (sck == 3 || sck == 4 || sck == 6 || sck == 8 || sck == 10)) ? sck : 0;
+  // rows = 5: Wp is the five-column image (gemv_nc5_kernel), one slab per workgroup
+  if (rows == 5) {
+    if (mode != 2 || p.wscale || p.stat_out || p.x2 || !gemv_nc5_shape(p.M, p.N, p.K, p.flags)) {
+      set_error("gemv: the five-column image serves f16 rows and weights at K = 5120 without row partials, one dispatch round (M=%d N=%d K=%d flags=%d)", p.M, p.N, p.K, p.flags); return WIS_E_UNSUPPORTED; }
+    hipLaunchKernelGGL((gemv_nc5_kernel<40>), dim3(p.N / 5), block, lds, st, WIS_GV_LEAD(pp), KC, pp);
+    return WIS_OK;
+  }
 #define WIS_GV1(MODEv, SCv, RMv, W8v) hipLaunchKernelGGL((gemv_kernel<1, MODEv, SCv, RMv, W8v>), grid, block, lds, st, WIS_GV_LEAD(pp), KC, pp)
 #define WIS_GV(MODEv, SCv, RMv) do { if (p.wscale) WIS_GV1(MODEv, SCv, RMv, true); else WIS_GV1(MODEv, SCv, RMv, false); } while (0)
 #define WIS_GV_SC(MODEv, RMv) do { switch (sc) { case 3: WIS_GV(MODEv, 3, RMv); break; case 4: WIS_GV(MODEv, 4, RMv); break; case 6: WIS_GV(MODEv, 6, RMv); break; \

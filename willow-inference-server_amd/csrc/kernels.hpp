@@ -69,7 +69,7 @@ struct GemvP {
   // GV_QKV epilogue: n < d -> q (f32 [M][d]); d <= n < 2d -> K cache; n >= 2d -> V cache
   float* q; f16* kc; f16* vc; const int* slot; const int* pos; int d; int ctx;   // cache [slots][ctx][d]
   unsigned long long* prof;      // optional phase stamps (workgroup 0)
-  int rows;                      // output columns per workgroup (0 => 16): 16 = Wp in A-fragment order, 8 (launch_gemv, gemv_nc8_shape only) = Wp the eight-column image of launch_pack_gemv_nc8
+  int rows;                      // output columns per workgroup (0 => 16): 16 = Wp in A-fragment order, 8 (launch_gemv, gemv_nc8_shape only) = Wp the eight-column image of launch_pack_gemv_nc8, 5 (launch_gemv, gemv_nc5_shape only) = Wp the five-column image of launch_pack_gemv_nc5
   const void* x2; int xsplit;    // f16 activations only: columns >= xsplit are read from x2 (row-major [M][K - xsplit]); x then is [M][xsplit]
   f16* y16;                      // GV_RESID: optional f16 row-major copy of the produced rows
   // ---- batched rows (launch_gemv_frag, M > 8): activations live in HBM in MFMA B-fragment order ("xf", xf_index below)
@@ -117,6 +117,12 @@ int launch_pack_gemv(hipStream_t st, const f16* W, f16* Wp, int N, int Npad, int
 // pack W [N][K] f16 row-major -> the eight-column image [Npad/8][K/64][64][8] (dec_kernels.hip pack_gemv_nc8_kernel); Npad % 8 == 0, K % 64 == 0
 int launch_pack_gemv_nc8(hipStream_t st, const f16* W, f16* Wp, int N, int Npad, int K);
 bool gemv_nc8_shape(int M, int N, int K);      // launch_gemv serves GemvP::rows = 8 at these shapes
+// pack W [N][K] f16 row-major -> the five-column image [N/5][K/32/kw][ceil(kw/3)][64][8] (dec_kernels.hip pack_gemv_nc5_kernel) of gemv_nc5_elems f16 elements;
+// kw = k-steps per wave K-range (a divisor of K / 32): 40 for the form launch_gemv runs (FFN2, K = 5120: a K quarter per wave); N % 5 == 0
+size_t gemv_nc5_elems(int N, int K, int kw);
+int launch_pack_gemv_nc5(hipStream_t st, const f16* W, f16* Wp, int N, int K, int kw);
+// launch_gemv serves GemvP::rows = 5 at these shapes and stage flags: one dispatch round of five-column slabs on the current device
+bool gemv_nc5_shape(int M, int N, int K, int flags);
 int gemv_rows_for(int N, int K);     // tile height used for an [N][K] decoder matrix
 
 int launch_dec_embed(hipStream_t st, const f16* emb, const f16* pos_emb, const int* tok, const int* pos, float* x, int M, int d, f16* xh = nullptr);

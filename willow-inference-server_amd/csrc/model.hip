@@ -261,6 +261,17 @@ static int add_nc8_image(wis_model* m, const f16* tmp, DecProj* p) {
   p->Wp8 = wp8;
   return WIS_OK;
 }
+// ... or a five-column image (dec_kernels.hip gemv_nc5_kernel: FFN2 on N / 5 workgroups, one per CU at large's width), where the pass of <= 8 rows would run it
+// on this device: gemv_nc5_elems * 2 bytes (the matrix's bytes plus about 12 %: a zero row in sixteen and a ragged last request per wave).  *added: it exists.
+static int add_nc5_image(wis_model* m, const f16* tmp, DecProj* p, bool* added) {
+  *added = false;
+  if (m->w8 || !gemv_nc5_shape(1, p->N, p->K, GV_RESID)) return WIS_OK;
+  f16* wp5 = nullptr;
+  WIS_RET(dalloc(m, &wp5, gemv_nc5_elems(p->N, p->K, 40)));
+  WIS_RET(launch_pack_gemv_nc5(m->st, tmp, wp5, p->N, p->K, 40));
+  p->Wp5 = wp5; *added = true;
+  return WIS_OK;
+}
 
 // The cross-Q fold's matrix and bias (load_weights below; the wis_op_gemv_out_cq tap builds its operands with the same code): wq_gamma = f16(Wq o gamma)
 // [d][d] as fold_ln_kernel left it, wo / bo = the self-attention output projection (f16 or f32 [d][d]; fp32 [d]) ->
@@ -390,9 +401,12 @@ static int load_weights(wis_model* m, const Loader& L) {
       if ((rc = add_nc8_image(m, tmp, &w.cout))) break;
       if ((rc = to_f32(m, L, p + "ffn/layer_norm/gamma", d, &w.ln3_g))) break;
       if ((rc = to_f32(m, L, p + "ffn/layer_norm/beta", d, &w.ln3_b))) break;
+      bool nc5 = false;
       if ((rc = load_proj(m, L, p + "ffn/linear_0", 4 * d, d, tmp, 0, 1.f, w.ln3_g, w.ln3_b, &w.f1))) break;
       if ((rc = load_proj(m, L, p + "ffn/linear_1", d, 4 * d, tmp, 0, 1.f, nullptr, nullptr, &w.f2))) break;
-      if ((rc = add_nc8_image(m, tmp, &w.f2))) break;
+      if ((rc = add_nc5_image(m, tmp, &w.f2, &nc5))) break;
+      // (the five-column image serves every pass FFN2's eight-column image would: at K = 4d both end at the rows the register staging holds)
+      if (!nc5 && (rc = add_nc8_image(m, tmp, &w.f2))) break;
     }
   } while (0);
   hipError_t e = hipStreamSynchronize(m->st);
@@ -714,6 +728,8 @@ GemvP gemv_small(const DecProj& p, const void* x, void* y, int M, int flags) {
   g.x = x; g.csum = p.csum; g.Wp = p.Wp; g.wscale = p.scale; g.bias = p.bias; g.y = y; g.M = M; g.N = p.N; g.K = p.K; g.flags = flags; g.rows = p.rows;
   // eight-column tiles where the projection has that image (FFN2, cross-attention out-projection of large models): f16 rows, plain or residual epilogue
   if (p.Wp8 && !(flags & ~(GV_RESID | GV_OUT_F32 | GV_GELU)) && gemv_nc8_shape(M, p.N, p.K)) { g.Wp = p.Wp8; g.rows = 8; }
+  // five-column slabs where the projection has that image (FFN2 of large models): one workgroup on every CU, f16 rows, plain or residual epilogue
+  if (p.Wp5 && !p.scale && !p.csum && gemv_nc5_shape(M, p.N, p.K, flags)) { g.Wp = p.Wp5; g.rows = 5; }
   return g;
 }
 // launch_gemv_frag (batched rows) on the rows' fragment image; the caller adds the stage's own: output, statistics, QKV cache members, prof, FFN2's K split

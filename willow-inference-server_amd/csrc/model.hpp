@@ -29,6 +29,7 @@ struct DecProj {
   int N, K;               // launch shape (the vocabulary projection: N = n_vocab_pad)
   int rows;               // weight rows per workgroup tile the matrix was packed for (gemv_rows_for)
   const f16* Wp8 = nullptr;      // the same f16 matrix as an eight-column image (add_nc8_image), or null: the route of <= 8 rows streams this one where gemv_nc8_shape holds
+  const f16* Wp5 = nullptr;      // the same f16 matrix as a five-column image (add_nc5_image: FFN2, in place of Wp8), or null: streamed where gemv_nc5_shape holds
 };
 struct DecLayerW {
   float *ln1_g, *ln1_b, *ln2_g, *ln2_b, *ln3_g, *ln3_b;

@@ -375,9 +375,36 @@ int wis_op_dec_embed(int device, const void* emb_f16, const void* pos_f16, const
 // The single-chunk f16-activation form of launch_gemv (the one-utterance FFN2 and cross-attention out-projection: K = 5120 / 1280) on sixteen-column
 // tiles (cols = 16: the fragment image) or eight-column tiles (cols = 8: launch_pack_gemv_nc8's image) of the same row-major W [N][K].  flags: GV_RESID
 // (y fp32 [M][N] in place, y16 an optional f16 copy), GV_OUT_F32, GV_GELU or none (y f16).  Nothing but the M x N outputs is written.
+// cols = 5: the stage as the step assembles it (gemv_small) for a projection that carries the sixteen-column image (tap flag 32: the matrix quantised to 8 bits
+// first, as wis_op_gemv's) and - packed by the loader's launcher, where the loader would add one - the five-column image: gemv_small's predicate picks the
+// form, so a shape it refuses (N no multiple of five, more rows than the register staging holds, 8-bit weights) runs the sixteen-column kernel.
+static int op_gemv_cols5(Tap& t, const void* x, const void* W, const float* bias, void* y, void* y16, int M, int N, int K, int flags, bool w8) {
+  const int Npad = cdiv(N, 16) * 16;
+  f16 *wp = nullptr, *wrow = nullptr, *wp5 = nullptr; float *wsc = nullptr, *b2 = nullptr;
+  WIS_RET(t.get(&wp, (size_t)Npad * K)); WIS_RET(t.get(&wrow, (size_t)N * K)); WIS_RET(t.get(&b2, (size_t)Npad, true));
+  if (w8) WIS_RET(t.get(&wsc, (size_t)Npad));
+  hipMemcpyAsync(wrow, W, (size_t)N * K * 2, hipMemcpyDeviceToDevice, t.st);
+  if (bias) hipMemcpyAsync(b2, bias, (size_t)N * 4, hipMemcpyDeviceToDevice, t.st);
+  WIS_RET(prep_projection(t.st, wrow, N, Npad, K, 0, 1.f, nullptr, nullptr, b2, nullptr, wp, wsc, 16));
+  DecProj proj{wp, wsc, bias ? b2 : nullptr, nullptr, N, K, 16};
+  if (!w8 && gemv_nc5_shape(1, N, K, flags)) {
+    WIS_RET(t.get(&wp5, gemv_nc5_elems(N, K, 40)));
+    WIS_RET(launch_pack_gemv_nc5(t.st, wrow, wp5, N, K, 40));
+    proj.Wp5 = wp5;
+  }
+  GemvP g = gemv_small(proj, x, y, M, flags);
+  g.y16 = reinterpret_cast<f16*>(y16);
+  return t.finish(launch_gemv(t.st, g));
+}
 int wis_op_gemv_cols(int device, const void* x, const void* W, const float* bias, void* y, void* y16, int M, int N, int K, int flags, int cols) {
   Tap t(device, "wis_op_gemv_cols"); WIS_RET(t.rc);
-  if (!x || !W || !y || (cols != 8 && cols != 16) || N < 1 || N % cols || (flags & ~(GV_RESID | GV_OUT_F32 | GV_GELU)) || (y16 && !(flags & GV_RESID))) { set_error("wis_op_gemv_cols: bad argument"); return WIS_E_ARG; }
+  const bool w8 = cols == 5 && (flags & 32);      // (tap flag, cols = 5 only)
+  if (w8) flags &= ~32;
+  if (!x || !W || !y || (cols != 5 && cols != 8 && cols != 16) || N < 1 || (cols != 5 && N % cols) || (flags & ~(GV_RESID | GV_OUT_F32 | GV_GELU)) || (y16 && !(flags & GV_RESID))) { set_error("wis_op_gemv_cols: bad argument"); return WIS_E_ARG; }
+  if (cols == 5) {
+    if (M < 1 || M > 16 || K < 128 || K % 128) { set_error("wis_op_gemv_cols: M=%d K=%d", M, K); return WIS_E_ARG; }
+    return op_gemv_cols5(t, x, W, bias, y, y16, M, N, K, flags, w8);
+  }
   if (!gemv_nc8_shape(M, N, K)) { set_error("wis_op_gemv_cols: M=%d N=%d K=%d is not a shape of the eight-column form", M, N, K); return WIS_E_UNSUPPORTED; }
   f16* wp = nullptr;
   WIS_RET(t.get(&wp, (size_t)N * K));
