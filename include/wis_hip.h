@@ -283,6 +283,24 @@ int wis_generate(wis_model_t* m, const float* input, int B, const int32_t* promp
  * the call - never a kernel argument of a captured step: one step graph serves every seed. */
 int wis_generate_n(wis_model_t* m, const float* input, int B, const int32_t* prompt, int P, const wis_gen_opts_t* opts, const uint64_t* seeds,
                    int32_t* out_ids, int32_t* out_len, float* out_score);
+/* wis_generate_n for prompts of DIFFERENT lengths in one device batch.  prompt: the B prompts back to back (sum of plen[b] ids), in utterance order;
+ * plen i32 [B], each in 1 .. min(228, n_text_ctx / 2 + 4) (anything else: WIS_E_UNSUPPORTED).  seeds and the outputs as in wis_generate_n
+ * (num_hypotheses results per utterance, out_ids rows of the resolved max_new).
+ *   - All lengths equal: the call IS wis_generate_n(..., P, ...) - the same launches, the same bits, for every P.
+ *   - Otherwise every utterance takes the long-prompt route, whatever its own length (1 .. 16 included): its prompt's K / V is kept once in its first
+ *     slot, the step kernels read its length from a device word, and the step graphs are the ones a uniform long-prompt call of the same (B, beam,
+ *     options, max_new) captures - either kind of call replays what the other captured.  The prefix windows of 16 positions carry only the utterances
+ *     that still have prompt left, in runs of consecutive utterances: any order of lengths is correct, the longest prompts first needs the fewest
+ *     passes.  The last pass is right-aligned (row i of utterance b reads position plen[b] - Pl + i, Pl = min(16, 96 / B)).
+ *   - max_new_tokens = 0 resolves to min(n_text_ctx / 2, n_text_ctx - max plen); an explicit value with max plen + max_new_tokens > n_text_ctx
+ *     is WIS_E_ARG.  One max_new serves the batch.
+ *   - no_speech_prob: every prompt must hold <|startoftranscript|> (else WIS_E_ARG); the row is found per utterance.
+ *   - Timestamps, the repetition options, sampling and n-best, fixed_new_tokens and the suppress options apply as in the uniform call.
+ *   - WIS_E_UNSUPPORTED while the TREE form of the step's self-attention is selected (WIS_SA_LONG=0 / wis_debug_sa_long(m, 0): its prompt length
+ *     is a kernel argument).  There is no drafted form, and wis_last_trajectory answers WIS_E_STATE after a ragged call (the rows of utterances
+ *     of different prompt lengths do not line up with what a drafted call replays). */
+int wis_generate_ragged(wis_model_t* m, const float* input, int B, const int32_t* prompt, const int32_t* plen, const wis_gen_opts_t* opts,
+                        const uint64_t* seeds, int32_t* out_ids, int32_t* out_len, float* out_score);
 
 /* ---- 8(f)3, BASELINE configs[4]: the FINAL decode of a recording that was heard while it arrived (one utterance, beam_size 1 - the
  * reference's default, settings.py:14).  `draft`: the token ids of an earlier hypothesis for (most of) the same audio, e.g. the last
@@ -638,6 +656,9 @@ int wis_op_kv_gather(int device, void* kc_f16, void* vc_f16, int64_t layer_strid
                      int beam, int w0, int ctx, int d);
 /* out[b] = softmax(logits row b rs + r0 over ids [0, V))[ns]; logits f32, row stride ld >= V.  ns outside [0, V): WIS_E_ARG. */
 int wis_op_no_speech(int device, const float* logits, int ld, int B, int rs, int r0, int V, int ns, float* out);
+/* the same with one row per utterance (wis_generate_ragged): rows i32 [B] in device memory; out[b] = softmax(logits row b rs + rows[b])[ns] where rows[b]
+ * lies in [0, rs), and out[b] is left as it is otherwise (the utterance is not in this pass). */
+int wis_op_no_speech_rows(int device, const float* logits, int ld, int B, int rs, const int32_t* rows, int V, int ns, float* out);
 /* probs f32 [B][n_lang] = softmax over the n_lang listed ids of logits row b (row stride ld) */
 int wis_op_lang_probs(int device, const float* logits, int ld, const int32_t* lang_ids, int n_lang, float* probs, int B);
 /* the teacher-forced greedy pick: logit statistics (suppress_blank on, no fixed length, n_cand = 2) of B x beam rows, then the k = 1 pick of each.

@@ -2929,6 +2929,28 @@ int launch_no_speech(hipStream_t st, const float* logits, int ld, int B, int rs,
   hipLaunchKernelGGL(no_speech_kernel, dim3(B), dim3(256), 0, st, logits, ld, rs, r0, V, ns, out);
   return WIS_OK;
 }
+// ... of a batch whose prompts differ in length (wis_generate_ragged): the <|startoftranscript|> row is another one in every utterance, and not every
+// utterance has it in this pass.  rows: device word per utterance - its row of the pass's rs (row of utterance b = logits + (b * rs + rows[b]) * ld), or a
+// value outside [0, rs): out[b] is left alone (the workgroup returns as a whole).  The arithmetic, reduction order included, is no_speech_kernel's.
+__global__ __launch_bounds__(256) void no_speech_rows_kernel(const float* __restrict__ logits, int ld, int rs, const int* __restrict__ rows, int V, int ns, float* __restrict__ out) {
+  __shared__ float red[4];
+  const int b = blockIdx.x, tid = threadIdx.x;
+  const int r0 = rows[b];
+  if (r0 < 0 || r0 >= rs) return;
+  const float* row = logits + (size_t)(b * rs + r0) * ld;
+  float mx = -INFINITY;
+  for (int i = tid; i < V; i += 256) mx = fmaxf(mx, row[i]);
+  mx = block_max_256(mx, red);
+  float s = 0.f;
+  for (int i = tid; i < V; i += 256) s += expf(row[i] - mx);
+  s = block_sum_256(s, red);
+  if (tid == 0) out[b] = expf(row[ns] - mx) / s;
+}
+int launch_no_speech_rows(hipStream_t st, const float* logits, int ld, int B, int rs, const int* rows, int V, int ns, float* out) {
+  if (ns < 0 || ns >= V || !rows || rs < 1) { set_error("no_speech_rows: token %d outside the vocabulary, or no row table", ns); return WIS_E_ARG; }
+  hipLaunchKernelGGL(no_speech_rows_kernel, dim3(B), dim3(256), 0, st, logits, ld, rs, rows, V, ns, out);
+  return WIS_OK;
+}
 
 // Greedy pick of teacher-forced rows (wis_generate_draft: the final decode of a streamed recording verifies the last interim hypothesis
 // in a few multi-row passes instead of one pass per token).  One wave per logits row over what logit_stats_kernel left for it: the

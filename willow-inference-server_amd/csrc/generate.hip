@@ -1,11 +1,11 @@
-// generate.hip — the generate driver (wis_generate, wis_generate_n, wis_generate_draft, wis_generate_draft_beam) as a sequence of stages, and the
+// generate.hip — the generate driver (wis_generate, wis_generate_n, wis_generate_ragged, wis_generate_draft, wis_generate_draft_beam) as a sequence of stages, and the
 // two taps that are made of its file-local helpers (wis_debug_search*: the sampling tail alone; wis_debug_tree_logits: a draft window alone).
 // An object of its own on model.hpp's interface; everything below but the entry points is file-local.
 //
 //   make_gen_ctx      every argument check, the resolved shape and sampling options of the call
 //   stage_search      search counters, prompt rows, progress block: staged before anything the encoder produces
 //   front_half        log-mel, encoder, cross-K/V (on a stream of its own while the handle is alone on the GPU)
-//   seed_*            four ways to "the search stands after `steps` passes": merged prefill, windowed prefill of a long prompt, greedy draft, beam-draft windows
+//   seed_*            five ways to "the search stands after `steps` passes": merged prefill, windowed prefill of a long prompt (one length, or one per utterance), greedy draft, beam-draft windows
 //   StepGraph         the decode step as a cached HIP graph (three self-attention lengths)
 //   run_burst / run_paced      the two step loops
 //   results_*         three forms of result read-back, then the timing record
@@ -86,14 +86,19 @@ struct GenCtx : SampleCtx {
   bool drafting, beam_draft;
   bool long_p;                   // the long-prompt route
   int Pl;                        // ... its last window: the prompt rows P - Pl .. P - 1 run as the merged prefill + first step
+  bool ragged = false;           // wis_generate_ragged with lengths that differ: every utterance on the long-prompt route, P = the LONGEST prompt (what max_new and the context check take)
+  std::vector<int> plens, poff;  // ... the utterances' own lengths (what d_plen holds), where each one's ids start in `prompt`
+  std::vector<int> sot_rows;     // ... no_speech_prob: the <|startoftranscript|> position of every utterance (empty: not asked; sot_row stays -1)
+  bool nsp() const { return sot_row >= 0 || !sot_rows.empty(); }
 };
 
 // draft / n_draft: wis_generate_draft (one utterance, beam 1): the tokens of an earlier hypothesis to verify first
 // draft_org (beam > 1, wis_generate_draft_beam): draft = [n_draft][beam] tokens, draft_org = [n_draft][beam] the beam slot each continued from -
 // the trajectory of an earlier SEARCH (wis_last_trajectory)
+// plen_v (wis_generate_ragged, lengths that differ): the length of every utterance's prompt, `prompt` holds them back to back; P is not read
 // None of the checks depends on device state: a refused call has enqueued nothing.
 static int make_gen_ctx(wis_model* m, const float* input, int B, const int32_t* prompt, int P, const wis_gen_opts_t* o,
-                        const int32_t* draft, int n_draft, const int32_t* draft_org, const uint64_t* seeds, bool single, GenCtx* out) {
+                        const int32_t* draft, int n_draft, const int32_t* draft_org, const uint64_t* seeds, bool single, const int32_t* plen_v, GenCtx* out) {
   const wis_config_t& c = m->cfg;
   GenCtx& g = *out;
   g.m = m; g.st = m->st; g.input = input; g.prompt = prompt; g.o = o; g.draft = draft; g.draft_org = draft_org; g.n_draft = n_draft; g.B = B; g.P = P;
@@ -104,16 +109,29 @@ static int make_gen_ctx(wis_model* m, const float* input, int B, const int32_t* 
   WIS_RET(check_batch(m, B, beam));
   if (!g.sampling()) WIS_RET(check_patience(beam, o->patience));
   const int max_prompt = std::min(c.n_text_ctx / 2 + 4, SA_LONG_MAX_PLEN);      // openai-whisper's n_ctx / 2 - 1 prompt tokens behind <|startofprev|>, the start sequence; the step's self-attention covers a prefix of SA_LONG_MAX_PLEN positions
+  int n_prompt = B * P;
+  if (plen_v) {
+    g.ragged = true; g.plens.assign(plen_v, plen_v + B); g.poff.resize(B);
+    n_prompt = P = 0;
+    for (int b = 0; b < B; ++b) {
+      if (plen_v[b] < 1 || plen_v[b] > max_prompt) { set_error("prompt length %d of utterance %d unsupported (1..%d)", plen_v[b], b, max_prompt); return WIS_E_UNSUPPORTED; }
+      g.poff[b] = n_prompt; n_prompt += plen_v[b]; P = std::max(P, (int)plen_v[b]);
+    }
+    g.P = P;
+    if (!sa_long_kernel(m)) { set_error("prompts of different lengths need dec_self_attn_long_kernel (the TREE form of the step's self-attention, WIS_SA_LONG=0, keeps the prompt length as a kernel argument)"); return WIS_E_UNSUPPORTED; }
+    if (draft != nullptr) { set_error("prompts of different lengths: not available for drafted decodes"); return WIS_E_UNSUPPORTED; }
+    if (o->max_new_tokens > 0 && P + o->max_new_tokens > c.n_text_ctx) { set_error("max_new_tokens %d behind a prompt of %d tokens exceeds the decoder's %d positions", o->max_new_tokens, P, c.n_text_ctx); return WIS_E_ARG; }
+  }
   if (P < 1 || P > max_prompt) { set_error("prompt length %d unsupported (1..%d)", P, max_prompt); return WIS_E_UNSUPPORTED; }
-  if (P <= SHORT_PROMPT && B * P > MAX_ROWS) { set_error("prompt length %d unsupported (1..16, B*P <= %d)", P, MAX_ROWS); return WIS_E_UNSUPPORTED; }
+  if (!g.ragged && P <= SHORT_PROMPT && B * P > MAX_ROWS) { set_error("prompt length %d unsupported (1..16, B*P <= %d)", P, MAX_ROWS); return WIS_E_UNSUPPORTED; }
   if (P > SHORT_PROMPT && draft != nullptr) { set_error("prompts of more than %d tokens: not available for drafted decodes (wis_generate_draft / wis_generate_draft_beam)", SHORT_PROMPT); return WIS_E_UNSUPPORTED; }
-  g.long_p = P > SHORT_PROMPT; g.Pl = std::min(16, MAX_ROWS / B);
+  g.long_p = P > SHORT_PROMPT || g.ragged; g.Pl = std::min(16, MAX_ROWS / B);
   g.plen = g.long_p ? m->d_plen : nullptr;
   int max_new = o->max_new_tokens > 0 ? o->max_new_tokens : std::min(c.n_text_ctx / 2, c.n_text_ctx - P);
   if (max_new > MAX_STEPS) max_new = MAX_STEPS;
   if (P - 1 + max_new > c.n_text_ctx) max_new = c.n_text_ctx - (P - 1);
   g.max_new = max_new;
-  for (int i = 0; i < B * P; ++i) if (prompt[i] < 0 || prompt[i] >= c.n_vocab) { set_error("prompt token %d out of range", prompt[i]); return WIS_E_ARG; }
+  for (int i = 0; i < n_prompt; ++i) if (prompt[i] < 0 || prompt[i] >= c.n_vocab) { set_error("prompt token %d out of range", prompt[i]); return WIS_E_ARG; }
   WIS_RET(resolve_rep_opts(o, &g));
   g.t0 = std::chrono::steady_clock::now();
   g.sc = make_sample_cfg(m, o, beam, max_new, &g.patience);
@@ -128,6 +146,13 @@ static int make_gen_ctx(wis_model* m, const float* input, int B, const int32_t* 
   if (g.ts && draft != nullptr) { set_error("timestamps: not available for drafted decodes (wis_generate_draft / wis_generate_draft_beam)"); return WIS_E_UNSUPPORTED; }
   if (g.rep() && draft != nullptr) { set_error("repetition_penalty / no_repeat_ngram_size: not available for drafted decodes (wis_generate_draft / wis_generate_draft_beam)"); return WIS_E_UNSUPPORTED; }
   int sot_row = -1;
+  if (o->no_speech_prob && g.ragged) {
+    g.sot_rows.assign(B, -1);
+    for (int b = 0; b < B; ++b) {
+      for (int i = 0; i < g.plens[b]; ++i) if (prompt[g.poff[b] + i] == c.sot) { g.sot_rows[b] = i; break; }
+      if (g.sot_rows[b] < 0) { set_error("no_speech_prob: the prompt of utterance %d holds no <|startoftranscript|>", b); return WIS_E_ARG; }
+    }
+  } else
   if (o->no_speech_prob && !drafting) {
     for (int i = 0; i < P; ++i) if (prompt[i] == c.sot) { sot_row = i; break; }
     for (int b = 1; b < B && sot_row >= 0; ++b) if (prompt[b * P + sot_row] != c.sot) sot_row = -1;
@@ -147,10 +172,10 @@ static int stage_search(const GenCtx& g) {
   wis_model* m = g.m; const int B = g.B, P = g.P, beam = g.beam;
   WIS_RET(init_beam_state(m, B, beam, g.sampling(), g.sampling() ? beam : g.n_res));
   if (g.sampling()) WIS_RET(upload_seeds(m, g.seeds, B));
-  m->last_B = B; m->last_beam = beam;
+  m->last_B = B; m->last_beam = beam; m->last_ragged = g.ragged;
   if (g.long_p) {      // (its prompt rows go up window by window: seed_prefill_long)
     int* hp = m->h_pin->plen;
-    for (int b = 0; b < B; ++b) hp[b] = P;
+    for (int b = 0; b < B; ++b) hp[b] = g.ragged ? g.plens[b] : P;
     WIS_HIP_CHECK(hipMemcpyAsync(m->d_plen, hp, (size_t)B * 4, hipMemcpyHostToDevice, g.st));
     if (!sa_long_kernel(m)) {      // the TREE form's tables: row r = b beam + j owns slot r, its utterance's prefix lies in slot b beam
       int* ht = m->h_pin->sa_tab;
@@ -268,7 +293,9 @@ static int seed_prefill(const GenCtx& g) {
 // that holds it runs with logits too.  The prompt's K / V stays in slot b * beam for the whole search: the step's self-attention reads it there for all of
 // the utterance's rows (dec_self_attn_long_kernel), a decode row keeps only the positions from P on in its own slot, and the cache reorder moves only those -
 // behind this pass there is nothing to move.
+static int seed_prefill_ragged(const GenCtx& g);
 static int seed_prefill_long(const GenCtx& g) {
+  if (g.ragged) return seed_prefill_ragged(g);
   wis_model* m = g.m; hipStream_t st = g.st; const wis_config_t& c = m->cfg; PinnedScratch* hp = m->h_pin;
   const int B = g.B, P = g.P, beam = g.beam, Pl = g.Pl, Np = P - Pl, G = MAX_ROWS / 16;
   for (int ub0 = 0; ub0 < B; ub0 += G) {
@@ -298,6 +325,73 @@ static int seed_prefill_long(const GenCtx& g) {
   WIS_RET(upload_rows(m, tok, pos, slot, ls, false));
   WIS_RET(dec_forward(m, B * Pl, Pl, B, true, beam, 0));
   if (g.sot_row >= Np) WIS_RET(launch_no_speech(st, m->logits, m->n_vocab_pad, B, Pl, g.sot_row - Np, c.n_vocab, c.no_speech, m->d_nsp));
+  return sampling_tail(g, {Pl, 0, Pl - 1}, TAIL_TAPS | TAIL_NO_CACHE);
+}
+
+// ---- the same for prompts of DIFFERENT lengths (wis_generate_ragged): every utterance u on the long-prompt route, whatever its length P_u.  Its prefix
+// positions are 0 .. Np_u - 1, Np_u = max(0, P_u - Pl); the pass of window t0 carries only the utterances with Np_u > t0 (a short last window of an
+// utterance padded with copies of its last row, as above).  The row-group cross-attention finds a group's K / V by kv_ub0 + group, so a pass covers a
+// RUN of consecutive utterances, in groups of at most MAX_ROWS / 16: one pass per maximal run - any order of lengths is right, the longest first needs the
+// fewest passes (every run is then a head of the batch).  The last pass is right-aligned: row i of utterance u is position P_u - Pl + i, and where
+// P_u < Pl the rows in front are copies of its first row (the same K / V to the same place); the sampling tail reads row Pl - 1 as ever.
+// no_speech_prob: the <|startoftranscript|> row differs per utterance, and so does the pass that holds it - a pass runs with logits when any of its
+// utterances has its row there, and no_speech_rows_kernel takes the rows from device memory (-1: not in this pass).
+static int seed_prefill_ragged(const GenCtx& g) {
+  wis_model* m = g.m; hipStream_t st = g.st; const wis_config_t& c = m->cfg; PinnedScratch* hp = m->h_pin;
+  const int B = g.B, beam = g.beam, Pl = g.Pl, G = MAX_ROWS / 16;
+  const bool want_nsp = !g.sot_rows.empty();
+  auto prefix = [&](int u) { return std::max(0, g.plens[u] - Pl); };
+  int np_max = 0;
+  for (int u = 0; u < B; ++u) np_max = std::max(np_max, prefix(u));
+  for (int t0 = 0; t0 < np_max; t0 += 16) {
+    for (int u0 = 0; u0 < B;) {
+      if (prefix(u0) <= t0) { ++u0; continue; }
+      int u1 = u0;
+      while (u1 < B && u1 - u0 < G && prefix(u1) > t0) ++u1;
+      const int nb = u1 - u0, M = nb * 16;
+      for (int r = 0; r < M; ++r) hp->base[r] = hp->anc[r] = (u0 + r / 16) * beam;
+      WIS_HIP_CHECK(hipMemcpyAsync(m->d_anc, hp->anc, (size_t)M * 4, hipMemcpyHostToDevice, st));
+      WIS_HIP_CHECK(hipMemcpyAsync(m->d_base, hp->base, (size_t)M * 4, hipMemcpyHostToDevice, st));
+      std::vector<int> tok(M), pos(M), slot(M), ls(M);
+      for (int r = 0; r < M; ++r) {
+        const int u = u0 + r / 16, n = std::min(16, prefix(u) - t0), i = std::min(r % 16, n - 1);
+        tok[r] = g.prompt[g.poff[u] + t0 + i]; pos[r] = t0 + i; slot[r] = ls[r] = u * beam;
+      }
+      bool nsp = false;
+      if (want_nsp) {
+        for (int b = 0; b < nb; ++b) {
+          const int u = u0 + b, s_ = g.sot_rows[u] - t0;
+          hp->nsp_rows[b] = (s_ >= 0 && s_ < std::min(16, prefix(u) - t0)) ? s_ : -1;
+          nsp = nsp || hp->nsp_rows[b] >= 0;
+        }
+        if (nsp) WIS_HIP_CHECK(hipMemcpyAsync(m->d_nsp_rows, hp->nsp_rows, (size_t)nb * 4, hipMemcpyHostToDevice, st));
+      }
+      WIS_RET(upload_rows(m, tok, pos, slot, ls));      // (waits: the staging areas - the rows', the tables', the no-speech rows' - are free for the next pass)
+      TreeWin tw{m->d_anc, t0, 1}; tw.base = m->d_base; tw.own_kv = true;
+      m->al.kv_ub0 = u0;
+      const int rc = dec_forward(m, M, 16, nb, nsp, 1, 0, &tw);
+      m->al.kv_ub0 = 0;
+      WIS_RET(rc);
+      if (nsp) WIS_RET(launch_no_speech_rows(st, m->logits, m->n_vocab_pad, nb, 16, m->d_nsp_rows, c.n_vocab, c.no_speech, m->d_nsp + u0));
+      u0 = u1;
+    }
+  }
+  std::vector<int> tok(B * Pl), pos(B * Pl), slot(B * Pl), ls(B * Pl);
+  for (int b = 0; b < B; ++b) for (int i = 0; i < Pl; ++i) {
+    const int p = std::max(g.plens[b] - Pl + i, 0);
+    tok[b * Pl + i] = g.prompt[g.poff[b] + p]; pos[b * Pl + i] = p; slot[b * Pl + i] = ls[b * Pl + i] = b * beam;
+  }
+  bool nsp = false;
+  if (want_nsp) {
+    for (int b = 0; b < B; ++b) {
+      hp->nsp_rows[b] = g.sot_rows[b] >= prefix(b) ? g.sot_rows[b] - g.plens[b] + Pl : -1;
+      nsp = nsp || hp->nsp_rows[b] >= 0;
+    }
+    if (nsp) WIS_HIP_CHECK(hipMemcpyAsync(m->d_nsp_rows, hp->nsp_rows, (size_t)B * 4, hipMemcpyHostToDevice, st));
+  }
+  WIS_RET(upload_rows(m, tok, pos, slot, ls, false));
+  WIS_RET(dec_forward(m, B * Pl, Pl, B, true, beam, 0));
+  if (nsp) WIS_RET(launch_no_speech_rows(st, m->logits, m->n_vocab_pad, B, Pl, m->d_nsp_rows, c.n_vocab, c.no_speech, m->d_nsp));
   return sampling_tail(g, {Pl, 0, Pl - 1}, TAIL_TAPS | TAIL_NO_CACHE);
 }
 
@@ -702,14 +796,14 @@ static void record_timing(const GenCtx& g, const LoopResult& lr) {
 static int generate_impl(wis_model_t* m, const float* input, int B, const int32_t* prompt, int P,
                  const wis_gen_opts_t* o, int32_t* out_ids, int32_t* out_len, float* out_score, bool* retry,
                  const int32_t* draft = nullptr, int n_draft = 0, int* accepted = nullptr, const int32_t* draft_org = nullptr,
-                 const uint64_t* seeds = nullptr, bool single = true) {
+                 const uint64_t* seeds = nullptr, bool single = true, const int32_t* plen_v = nullptr) {
   *retry = false;
   if (accepted) *accepted = 0;
   m->nsp_B = 0;
   WIS_HIP_CHECK(hipSetDevice(m->device));
   SpinClaim claim(m, B);
   GenCtx g;
-  WIS_RET(make_gen_ctx(m, input, B, prompt, P, o, draft, n_draft, draft_org, seeds, single, &g));
+  WIS_RET(make_gen_ctx(m, input, B, prompt, P, o, draft, n_draft, draft_org, seeds, single, plen_v, &g));
   hipStream_t st = g.st;
   WIS_RET(stage_search(g));
   WIS_RET(front_half(g));
@@ -746,7 +840,7 @@ static int generate_impl(wis_model_t* m, const float* input, int B, const int32_
   else WIS_RET(results_from_device(m, B * g.n_res, g.max_new, out_ids, out_len, out_score));
   record_timing(g, lr);
   if (lr.steps > lr.needed) { claim.defer(st); m->overrun_left = true; }      // an over-run step is still queued: its combiners keep their share of the spin budget until it has run
-  if (g.sot_row >= 0) m->nsp_B = B;
+  if (g.nsp()) m->nsp_B = B;
   return WIS_OK;
 }
 
@@ -754,10 +848,10 @@ static int generate_impl(wis_model_t* m, const float* input, int B, const int32_
 static int generate_with_retry(const char* who, wis_model_t* m, const float* input, int B, const int32_t* prompt, int P, const wis_gen_opts_t* o,
                                int32_t* out_ids, int32_t* out_len, float* out_score,
                                const int32_t* draft = nullptr, int n_draft = 0, int* accepted = nullptr, const int32_t* draft_org = nullptr,
-                               const uint64_t* seeds = nullptr, bool single = true) {
+                               const uint64_t* seeds = nullptr, bool single = true, const int32_t* plen_v = nullptr) {
   bool retry = false;
   for (int attempt = 0; attempt < 2; ++attempt) {
-    WIS_RET(generate_impl(m, input, B, prompt, P, o, out_ids, out_len, out_score, &retry, draft, n_draft, accepted, draft_org, seeds, single));
+    WIS_RET(generate_impl(m, input, B, prompt, P, o, out_ids, out_len, out_score, &retry, draft, n_draft, accepted, draft_org, seeds, single, plen_v));
     if (!retry) return WIS_OK;
   }
   set_error("%s: hand-off flag raised without the granule path", who);
@@ -828,6 +922,17 @@ int wis_generate_n(wis_model_t* m, const float* input, int B, const int32_t* pro
   if (!m || !input || !prompt || !o || !out_ids || !out_len) { set_error("wis_generate_n: bad argument"); return WIS_E_ARG; }
   WIS_ENTER(m, "wis_generate_n")
   return generate_with_retry("wis_generate_n", m, input, B, prompt, P, o, out_ids, out_len, out_score, nullptr, 0, nullptr, nullptr, seeds, false);
+}
+
+// prompts of different lengths in one device batch; equal lengths are wis_generate_n, launch for launch
+int wis_generate_ragged(wis_model_t* m, const float* input, int B, const int32_t* prompt, const int32_t* plen, const wis_gen_opts_t* o, const uint64_t* seeds,
+                        int32_t* out_ids, int32_t* out_len, float* out_score) {
+  if (!m || !input || !prompt || !plen || !o || !out_ids || !out_len || B < 1) { set_error("wis_generate_ragged: bad argument"); return WIS_E_ARG; }
+  WIS_ENTER(m, "wis_generate_ragged")
+  bool uniform = true;
+  for (int b = 1; b < B && b < MAX_ROWS; ++b) uniform = uniform && plen[b] == plen[0];      // (a batch beyond MAX_ROWS is refused by the uniform call's check_batch)
+  if (uniform) return generate_with_retry("wis_generate_ragged", m, input, B, prompt, plen[0], o, out_ids, out_len, out_score, nullptr, 0, nullptr, nullptr, seeds, false);
+  return generate_with_retry("wis_generate_ragged", m, input, B, prompt, 0, o, out_ids, out_len, out_score, nullptr, 0, nullptr, nullptr, seeds, false, plen);
 }
 
 int wis_generate_draft(wis_model_t* m, const float* input, const int32_t* prompt, int P, const wis_gen_opts_t* o,

@@ -203,6 +203,8 @@ int launch_ts_rules(hipStream_t st, const float* logits, const float* bias_all, 
 int launch_rep_rules(hipStream_t st, float* logits, const BeamState& bs, int B, const SampleCfg& cfg, float penalty, int ngram, int lr_b, int lr_j, int lr_off);
 // probability of <|nospeech|> under the full-vocabulary softmax of each utterance's <|startoftranscript|> row (b * rs + r0)
 int launch_no_speech(hipStream_t st, const float* logits, int ld, int B, int rs, int r0, int V, int ns, float* out);
+// ... with the row of every utterance in device memory (rows [B]; a value outside [0, rs): utterance b is not in this pass, out[b] stays as it is)
+int launch_no_speech_rows(hipStream_t st, const float* logits, int ld, int B, int rs, const int* rows, int V, int ns, float* out);
 struct BeamState {
   int* step_u;      // [B] generated-token count so far
   int* done;        // [B]

@@ -534,7 +534,7 @@ static int alloc_buffers(wis_model* m) {
   WIS_RET(dalloc(m, &m->bs.out_ids, (size_t)slots * max_new)); WIS_RET(dalloc(m, &m->bs.out_len, slots)); WIS_RET(dalloc(m, &m->bs.out_score, slots));      // (up to max_beam results per utterance)
   WIS_RET(dalloc(m, &m->st_max, (size_t)MAX_ROWS * STAT_SUB)); WIS_RET(dalloc(m, &m->st_sum, (size_t)MAX_ROWS * STAT_SUB));
   WIS_RET(dalloc(m, &m->st_val, (size_t)MAX_ROWS * STAT_SUB * MAX_CAND)); WIS_RET(dalloc(m, &m->st_idx, (size_t)MAX_ROWS * STAT_SUB * MAX_CAND));
-  WIS_RET(dalloc(m, &m->ts_desc, (size_t)MAX_ROWS * TS_DESC_INTS)); WIS_RET(dalloc(m, &m->d_nsp, (size_t)MAX_ROWS));
+  WIS_RET(dalloc(m, &m->ts_desc, (size_t)MAX_ROWS * TS_DESC_INTS)); WIS_RET(dalloc(m, &m->d_nsp, (size_t)MAX_ROWS)); WIS_RET(dalloc(m, &m->d_nsp_rows, (size_t)MAX_ROWS));
   WIS_RET(dalloc(m, &m->d_in, (size_t)Bm * WIS_N_SAMPLES));
   WIS_RET(dalloc(m, &m->d_nsamp, Bm));
   WIS_RET(dalloc(m, &m->lm_logspec, (size_t)Bm * c.n_mels * WIS_N_FRAMES));
@@ -1162,6 +1162,7 @@ int wis_last_trajectory(wis_model_t* m, int b, int32_t* tok, int32_t* org, int c
   if (!m || !tok || !org || !n_steps || cap_steps < 0) { set_error("wis_last_trajectory: bad argument"); return WIS_E_ARG; }
   WIS_ENTER(m, "wis_last_trajectory")
   WIS_HIP_CHECK(hipSetDevice(m->device));
+  if (m->last_ragged) { set_error("wis_last_trajectory: the last call's prompts differed in length (wis_generate_ragged): its rows do not line up with a drafted call's"); return WIS_E_STATE; }
   if (b < 0 || b >= m->last_B) { set_error("wis_last_trajectory: utterance %d outside the last call's batch of %d", b, m->last_B); return WIS_E_ARG; }
   const int k = m->last_beam;
   int n = 0;

@@ -87,6 +87,7 @@ struct PinnedScratch {
   unsigned long long seeds[MAX_ROWS];          // upload_seeds: the Philox key of every utterance of a sampled decode
   int sa_tab[2 * MAX_ROWS];                    // stage_search, WIS_SA_LONG=0: wis_model::d_sa_tab
   int plen[MAX_ROWS];                          // stage_search: the prompt length of every utterance (wis_model::d_plen)
+  int nsp_rows[MAX_ROWS];                      // wis_generate_ragged: the <|startoftranscript|> row of every utterance of a prefill pass (wis_model::d_nsp_rows)
   unsigned reseed_tick[4];                     // reseed_tick: bs.tick behind a draft verification
   // wis_generate_draft: step index of the verified rows, their picks read back; then the search state `steps` ordinary steps would have left
   int vstep[MAX_ROWS], pick_tok[MAX_ROWS]; float pick_lp[MAX_ROWS];
@@ -158,6 +159,7 @@ struct wis_model {
   int* ts_desc = nullptr;       // timestamp rules: masked ranges per live row [MAX_ROWS][TS_DESC_INTS] (ts_rules_kernel -> logit_stats_kernel<true>)
   float* d_nsp = nullptr;       // no_speech_prob per utterance of the last wis_generate that asked for it
   int nsp_B = 0;                // ... its batch size; 0: the last call did not ask (wis_last_no_speech_prob answers WIS_E_STATE)
+  int* d_nsp_rows = nullptr;    // wis_generate_ragged: per utterance of a prefill pass, the pass row that read <|startoftranscript|> or -1 [MAX_ROWS] (launch_no_speech_rows)
   float* d_in; int64_t* d_nsamp; float* d_probs;
   int* vstep = nullptr; int* pick_tok = nullptr; float* pick_lp = nullptr;      // wis_generate_draft: per-row step index, picked token / log-probability of the teacher-forced rows
   int* d_draft = nullptr; int* d_anc = nullptr; int* d_vstate = nullptr; int* d_base = nullptr;        // wis_generate_draft_beam: the draft trajectory [MAX_STEPS][MAX_R][2], the window rows' ancestor slots [MAX_ROWS][ANC_W], the verification state, the rows' base slots
@@ -166,6 +168,7 @@ struct wis_model {
   unsigned long long* h_prog = nullptr;      // host-mapped progress block of the beam search (kernels.hpp HP_*): the decode loop polls it
   unsigned gen = 0;                          // generation of the current search (records of an earlier call's over-run step are ignored)
   int last_B = 0, last_beam = 0;             // shape of the last generate call (wis_last_trajectory)
+  bool last_ragged = false;                  // ... its prompts differed in length (wis_generate_ragged): wis_last_trajectory answers WIS_E_STATE
   bool overrun_left = false;                 // the last call returned with an over-run decode step still queued (its give-up flag, if any, is not the next call's)
   hipEvent_t ev[8];
   hipStream_t st_enc = nullptr;             // wis_generate's front half (log-mel, encoder) runs here: it overlaps the previous call's over-run decode step on `st`

@@ -637,6 +637,11 @@ int wis_op_no_speech(int device, const float* logits, int ld, int B, int rs, int
   if (!logits || !out || B < 1 || rs < 1 || r0 < 0 || r0 >= rs || V < 1 || ld < V) { set_error("wis_op_no_speech: bad argument"); return WIS_E_ARG; }
   return t.finish(launch_no_speech(t.st, logits, ld, B, rs, r0, V, ns, out));
 }
+int wis_op_no_speech_rows(int device, const float* logits, int ld, int B, int rs, const int32_t* rows, int V, int ns, float* out) {
+  Tap t(device, "wis_op_no_speech_rows"); WIS_RET(t.rc);
+  if (!logits || !rows || !out || B < 1 || rs < 1 || V < 1 || ld < V) { set_error("wis_op_no_speech_rows: bad argument"); return WIS_E_ARG; }
+  return t.finish(launch_no_speech_rows(t.st, logits, ld, B, rs, rows, V, ns, out));
+}
 int wis_op_lang_probs(int device, const float* logits, int ld, const int32_t* lang_ids, int n_lang, float* probs, int B) {
   Tap t(device, "wis_op_lang_probs"); WIS_RET(t.rc);
   if (!logits || !lang_ids || !probs || B < 1 || n_lang < 1 || ld < 1) { set_error("wis_op_lang_probs: bad argument"); return WIS_E_ARG; }

@@ -100,6 +100,8 @@ SYMBOLS = [
     ("wis_model_clone", _i, [_vp, C.POINTER(_vp)]),
     ("wis_generate", _i, [_vp, _vp, _i, C.POINTER(C.c_int32), _i, C.POINTER(GenOpts), C.POINTER(C.c_int32), C.POINTER(C.c_int32), _fp]),
     ("wis_generate_n", _i, [_vp, _vp, _i, C.POINTER(C.c_int32), _i, C.POINTER(GenOpts), C.POINTER(C.c_uint64), C.POINTER(C.c_int32), C.POINTER(C.c_int32), _fp]),
+    ("wis_generate_ragged", _i, [_vp, _vp, _i, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(GenOpts), C.POINTER(C.c_uint64), C.POINTER(C.c_int32),
+                                 C.POINTER(C.c_int32), _fp]),
     ("wis_generate_draft", _i, [_vp, _vp, C.POINTER(C.c_int32), _i, C.POINTER(GenOpts), C.POINTER(C.c_int32), _i, C.POINTER(C.c_int32), C.POINTER(C.c_int32), _fp,
                                 C.POINTER(C.c_int32)]),
     ("wis_generate_draft_beam", _i, [_vp, _vp, C.POINTER(C.c_int32), _i, C.POINTER(GenOpts), C.POINTER(C.c_int32), C.POINTER(C.c_int32), _i, C.POINTER(C.c_int32),
@@ -161,6 +163,7 @@ SYMBOLS = [
     ("wis_op_dec_self_attn_long", _i, [_i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i]),
     ("wis_op_kv_gather", _i, [_i, _vp, _vp, _i64, _i, _vp, _vp, _i, _i, _i, _i]),
     ("wis_op_no_speech", _i, [_i, _vp, _i, _i, _i, _i, _i, _i, _vp]),
+    ("wis_op_no_speech_rows", _i, [_i, _vp, _i, _i, _i, _vp, _i, _i, _vp]),
     ("wis_op_lang_probs", _i, [_i, _vp, _i, _vp, _i, _vp, _i]),
     ("wis_op_greedy_rows", _i, [_i, _vp, _i, _i, _i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
     ("wis_sv_create", _i, [C.POINTER(SvConfig), _vp, _sz, _i, C.POINTER(Tensor), _i, _i, C.POINTER(_vp)]),

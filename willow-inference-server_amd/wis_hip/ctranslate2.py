@@ -304,7 +304,9 @@ class DecodeOptions(NamedTuple):
     cap on the first timestamp).  no_speech_prob: every result carries P(<|nospeech|>) at <|startoftranscript|>.  repetition_penalty /
     no_repeat_ngram_size: CTranslate2's two options against looping hypotheses (include/wis_hip.h; 1 / 0: off).  sampling_topk (the ENGINE's
     value, as _check_sampling returns it: 0 off, -1 the whole vocabulary, 2 .. 16), sampling_temperature, num_hypotheses: random sampling and n
-    results per utterance; every result then carries num_hypotheses sequences and scores."""
+    results per utterance; every result then carries num_hypotheses sequences and scores.
+    prompt_len RAGGED_PROMPT (-1) is the POOLED key: the rows of the batch carry prompts of any length 1 .. MAX_PROMPT, max_new_tokens was resolved
+    from the longest the call may hold, and the batch decodes through wis_generate_ragged."""
     prompt_len: int
     beam_size: int
     max_new_tokens: int
@@ -326,6 +328,15 @@ class DecodeOptions(NamedTuple):
     num_hypotheses: int = 1
 
 
+RAGGED_PROMPT = -1         # DecodeOptions.prompt_len of the pooled key: prompts of different lengths in one device batch (wis_generate_ragged)
+
+
+def _longest_first(prompts):
+    """-> the rows' indices, longest prompt first (a stable sort: equal lengths keep their order) - the order in which wis_generate_ragged's
+    windowed prefill needs the fewest passes"""
+    return sorted(range(len(prompts)), key=lambda i: -len(prompts[i]))
+
+
 def _gen_opts(opts):
     """The engine's wis_gen_opts_t of a DecodeOptions."""
     o = _lib.GenOpts(opts.input_kind, opts.beam_size, opts.max_new_tokens, opts.length_penalty, opts.patience, int(bool(opts.suppress_blank)),
@@ -344,13 +355,38 @@ def _generate_chunk(r, mel, prompts, opts, *rest, device_ptr=None, seeds=None):
     """One engine call on replica r (the caller serialises access to r).  mel: host ndarray [B, ...] - or, with device_ptr, just the batch size B
     of features already resident on r.device.  opts: a DecodeOptions (its first nine fields may also be spelled out positionally: prompt length,
     beam, ...).  seeds: one uint64 per utterance (sampled calls).  opts.draft goes to wis_generate_draft_beam / wis_generate_draft, a sampled or
-    n-best call to wis_generate_n, everything else to wis_generate."""
+    n-best call to wis_generate_n, everything else to wis_generate.  Under the pooled key (prompt_len RAGGED_PROMPT) the rows go to
+    wis_generate_ragged longest prompt first and the results come back in the rows' own order (features on the device lie where they lie: their
+    rows keep their order, which the engine serves as well - _run_batch sorts those before it gathers them)."""
     if rest:
         opts = DecodeOptions(opts, *rest)
     B = int(mel) if device_ptr is not None else mel.shape[0]
     P, beam, n, draft = opts.prompt_len, opts.beam_size, int(opts.num_hypotheses), opts.draft
     o = _gen_opts(opts)
-    pr = np.ascontiguousarray(np.asarray(prompts, np.int32).reshape(B, P))
+    order = None
+    if P == RAGGED_PROMPT:
+        if draft is not None or opts.return_trajectory:
+            raise ValueError("prompts of different lengths cannot be combined with drafts or return_trajectory")
+        prompts = [[int(t) for t in p] for p in prompts]
+        P0 = len(prompts[0])
+        if P0 <= SHORT_PROMPT and B * P0 > MAX_DECODER_ROWS and all(len(p) == P0 for p in prompts):
+            # a pooled batch that happens to hold ONE short length is the default call to the engine (the merged prefill, B * P rows): more
+            # utterances than that pass takes go in several such calls
+            step, row_bytes, out = MAX_DECODER_ROWS // P0, (r.mel_bytes if opts.input_kind == _lib.WIS_IN_MEL_DEV else r.enc_bytes) if device_ptr is not None else 0, []
+            for lo in range(0, B, step):
+                hi = min(B, lo + step)
+                out += _generate_chunk(r, hi - lo if device_ptr is not None else mel[lo:hi], prompts[lo:hi], opts._replace(prompt_len=P0),
+                                       device_ptr=None if device_ptr is None else device_ptr + lo * row_bytes, seeds=None if seeds is None else seeds[lo:hi])
+            return out
+        if device_ptr is None:
+            order = _longest_first(prompts)
+            prompts, mel = [prompts[i] for i in order], np.ascontiguousarray(mel[order])
+            if seeds is not None:
+                seeds = [seeds[i] for i in order]
+        plen = np.ascontiguousarray(np.asarray([len(p) for p in prompts], np.int32))
+        pr = np.ascontiguousarray(np.asarray([t for p in prompts for t in p], np.int32))
+    else:
+        pr = np.ascontiguousarray(np.asarray(prompts, np.int32).reshape(B, P))
     ids = np.zeros((B, n, opts.max_new_tokens), np.int32)
     lens = np.zeros((B, n), np.int32)
     scores = np.zeros((B, n), np.float32)
@@ -358,7 +394,10 @@ def _generate_chunk(r, mel, prompts, opts, *rest, device_ptr=None, seeds=None):
     i32p, lib = C.POINTER(C.c_int32), _lib.load()
     out_ptrs = (ids.ctypes.data_as(i32p), lens.ctypes.data_as(i32p), scores.ctypes.data_as(C.POINTER(C.c_float)))
     acc = None
-    if draft is not None and draft.trajectory is not None:
+    if P == RAGGED_PROMPT:
+        sd = np.ascontiguousarray(np.asarray([0] * B if seeds is None else [int(x) & 0xFFFFFFFFFFFFFFFF for x in seeds], np.uint64))
+        _lib.check(lib.wis_generate_ragged(r.handle, src, B, pr.ctypes.data_as(i32p), plen.ctypes.data_as(i32p), C.byref(o), sd.ctypes.data_as(C.POINTER(C.c_uint64)), *out_ptrs))
+    elif draft is not None and draft.trajectory is not None:
         dt, do = (np.ascontiguousarray(np.asarray(a, np.int32)) for a in draft.trajectory)
         if dt.ndim != 2 or dt.shape != do.shape or dt.shape[1] != beam:
             raise ValueError(f"draft trajectory must be two [steps][{beam}] arrays, got {dt.shape} / {do.shape}")
@@ -383,6 +422,11 @@ def _generate_chunk(r, mel, prompts, opts, *rest, device_ptr=None, seeds=None):
     if opts.return_trajectory:
         for b in range(B):
             out[b].trajectory = _last_trajectory(r, b, beam)
+    if order is not None:
+        back = [None] * B
+        for at, i in enumerate(order):
+            back[i] = out[at]
+        out = back
     return out
 
 
@@ -534,7 +578,7 @@ def _capacity(max_batch, opts):
         return max(1, int(max_batch))
     P = opts.prompt_len
     rows = max(opts.beam_size, opts.num_hypotheses, 1)      # decoder rows per utterance: its beams, or its num_hypotheses samples
-    if P > SHORT_PROMPT:
+    if P > SHORT_PROMPT or P == RAGGED_PROMPT:      # (the pooled key: every utterance takes the long-prompt route)
         return max(1, min(max_batch, MAX_DECODER_ROWS // rows))
     return max(1, min(max_batch, MAX_DECODER_ROWS // rows, MAX_DECODER_ROWS // max(P, 1)))
 
@@ -549,6 +593,17 @@ def _run_batch(replica, opts, rows):
             else:
                 view = _encode_chunk(replica, np.ascontiguousarray(np.stack(rows)), opts.input_kind)
         return [view[i:i + 1] for i in range(len(rows))]
+    if opts.prompt_len == RAGGED_PROMPT and opts.input_kind in (_lib.WIS_IN_MEL_DEV, _lib.WIS_IN_ENC_DEV):
+        # rows on the device are gathered in the order they go to the engine: longest prompt first here, the results back in the rows' own order
+        order = _longest_first([r[1] for r in rows])
+        rows = [rows[i] for i in order]
+        with replica.lock:
+            ptr = _gather_device_rows(replica, [int(r[0]) for r in rows], replica.mel_bytes if opts.input_kind == _lib.WIS_IN_MEL_DEV else replica.enc_bytes)
+            res = _generate_chunk(replica, len(rows), [r[1] for r in rows], opts, device_ptr=ptr, seeds=[r[2] for r in rows])
+        back = [None] * len(rows)
+        for at, i in enumerate(order):
+            back[i] = res[at]
+        return back
     prompts, seeds = [r[1] for r in rows], [r[2] for r in rows]
     if opts.input_kind in (_lib.WIS_IN_MEL_DEV, _lib.WIS_IN_ENC_DEV):
         # features (streaming sessions: audio.MelStream.finish) or encoder output (Whisper.encode) that already live in this replica's HBM: one
@@ -800,7 +855,7 @@ class Whisper:
                  repetition_penalty=1, no_repeat_ngram_size=0, max_length=448, return_scores=False, return_no_speech_prob=False,
                  max_initial_timestamp_index=50, suppress_blank=True, suppress_tokens=(-1,), sampling_topk=1,
                  sampling_temperature=1, fixed_new_tokens=0, input_kind=_lib.WIS_IN_MEL_HOST, draft_tokens=None, draft_trajectory=None,
-                 return_trajectory=False, sampling_seed=None):
+                 return_trajectory=False, sampling_seed=None, ragged_prompts=False):
         """`draft_tokens` (one utterance, beam_size 1): the ids of an earlier hypothesis for this audio - wis_generate_draft verifies them in
         multi-row passes and decodes on behind the accepted prefix; the result is the greedy decode of THESE features either way.
         `draft_trajectory` (one utterance, beam_size > 1): `(tok, org)` as an earlier result's `.trajectory` gives it (`return_trajectory=True`) -
@@ -821,7 +876,12 @@ class Whisper:
         samples, whatever else shares the device batch.
         `features` may be what `encode` returned (a device-resident view, a slice or a list of them, or its host copy of shape [B, n_audio_ctx,
         d_model]): the call then starts at the cross-K/V projection (WIS_IN_ENC_DEV / WIS_IN_ENC_HOST in the options' input_kind; `input_kind`
-        itself keeps describing host feature arrays).  A device view decodes on its own GPU."""
+        itself keeps describing host feature arrays).  A device view decodes on its own GPU.
+        `ragged_prompts=True` (an extension of this shim; CTranslate2 takes such calls as they are): the prompts of the call may differ in length
+        (1 .. 228 tokens each) and still decode in one device batch (wis_generate_ragged) - all with timestamps or none, `max_new_tokens` from the
+        longest prompt, no drafts, no `return_trajectory`.  Equal prompts decode exactly as without the keyword.  The setting `batch_ragged_prompts`
+        pools every call whose prompts are longer than 16 tokens under one batch key in the same way, so that prompted requests of concurrent callers
+        share device batches."""
         enc = self._encoder_input(features, input_kind)
         if enc is not None:
             n_utt = len(enc[2]) if enc[0] == _lib.WIS_IN_ENC_DEV else enc[1].shape[0]
@@ -831,7 +891,8 @@ class Whisper:
                                          max_length=max_length, return_no_speech_prob=return_no_speech_prob, max_initial_timestamp_index=max_initial_timestamp_index,
                                          suppress_blank=suppress_blank, suppress_default=list(suppress_tokens) == [-1], sampling_topk=sampling_topk,
                                          sampling_temperature=sampling_temperature, fixed_new_tokens=fixed_new_tokens, draft_tokens=draft_tokens,
-                                         draft_trajectory=draft_trajectory, return_trajectory=return_trajectory)
+                                         draft_trajectory=draft_trajectory, return_trajectory=return_trajectory, ragged_prompts=ragged_prompts,
+                                         pool_long_prompts=getattr(self, "batch_ragged_prompts", False))
         seeds = _seeds(opts, sampling_seed, len(prompts))
         if enc is not None and enc[0] == _lib.WIS_IN_ENC_DEV:
             # every row carries the block its address points into: the rows themselves keep the device memory allocated until _run_batch has returned
@@ -842,10 +903,12 @@ class Whisper:
 
     def _decode_options(self, features, prompts, *, input_kind, n_utt=1, beam_size, patience, num_hypotheses, length_penalty, repetition_penalty, no_repeat_ngram_size,
                         max_length, return_no_speech_prob, max_initial_timestamp_index, suppress_blank, suppress_default, sampling_topk, sampling_temperature,
-                        fixed_new_tokens, draft_tokens, draft_trajectory, return_trajectory):
+                        fixed_new_tokens, draft_tokens, draft_trajectory, return_trajectory, ragged_prompts=False, pool_long_prompts=False):
         """Every check of a decode call, for `generate` (features: host arrays, one prompt each) and `generate_from_device` (features None: ONE
         utterance already on the device) -> (its DecodeOptions, the checked host features or None).  The engine's capacity limits are request
-        errors (ValueError -> HTTP 400 in wis_hip.server), not internal ones."""
+        errors (ValueError -> HTTP 400 in wis_hip.server), not internal ones.  ragged_prompts: the prompts may differ in length (the key then
+        carries RAGGED_PROMPT).  pool_long_prompts (the setting batch_ragged_prompts): a call whose prompts are longer than SHORT_PROMPT gets the
+        pooled key whatever their lengths."""
         drafted = bool(draft_tokens is not None and len(draft_tokens) or draft_trajectory is not None and len(draft_trajectory[0]))
         s_k, s_T, s_n = _check_sampling(beam_size, num_hypotheses, sampling_topk, sampling_temperature, drafted)
         if max(int(beam_size), s_n) > self.max_beam:
@@ -856,13 +919,22 @@ class Whisper:
         if len(prompts) != B:
             raise ValueError("one prompt per batch item")
         P = len(prompts[0])
-        if any(len(p) != P for p in prompts):
+        if ragged_prompts and drafted:
+            raise ValueError("ragged_prompts cannot be combined with draft_tokens / draft_trajectory")
+        if ragged_prompts and return_trajectory:
+            raise ValueError("ragged_prompts cannot be combined with return_trajectory")
+        ragged = bool(ragged_prompts) and any(len(p) != P for p in prompts)      # (equal prompts: the call is the default one)
+        if ragged:
+            P = max(len(p) for p in prompts)      # (max_new_tokens comes from the longest prompt of the call)
+        elif any(len(p) != P for p in prompts):
             raise ValueError("all prompts must have the same length")
         if not 1 <= int(beam_size) <= self.max_beam:
             raise ValueError(f"beam_size {beam_size} outside 1..{self.max_beam} (setting max_beam; engine ceiling {MAX_BEAM})")
         max_prompt = min(MAX_PROMPT, int((getattr(self, "arch", None) or {}).get("n_text_ctx", 448)) // 2 + 4)
         if not 1 <= P <= max_prompt:
             raise ValueError(f"prompt length {P} outside 1..{max_prompt}")
+        if ragged and min(len(p) for p in prompts) < 1:
+            raise ValueError(f"prompt length 0 outside 1..{max_prompt}")
         if P > SHORT_PROMPT and drafted:
             raise ValueError(f"a prompt of more than {SHORT_PROMPT} tokens cannot be combined with draft_tokens / draft_trajectory")
         _check_patience(beam_size, patience)
@@ -882,7 +954,8 @@ class Whisper:
             if tok.ndim == 2 and tok.shape[1] == int(beam_size) and tok.shape == org.shape:
                 draft = _Draft(trajectory=(tok, org))
         mi = None if max_initial_timestamp_index is None else int(max_initial_timestamp_index)
-        opts = DecodeOptions(P, int(beam_size), min(max_length // 2, max_length - P), float(length_penalty), float(patience), bool(suppress_blank),
+        pooled = ragged or (bool(pool_long_prompts) and P > SHORT_PROMPT and not drafted and not return_trajectory)
+        opts = DecodeOptions(RAGGED_PROMPT if pooled else P, int(beam_size), min(max_length // 2, max_length - P), float(length_penalty), float(patience), bool(suppress_blank),
                              bool(suppress_default), int(fixed_new_tokens), int(input_kind), draft, bool(return_trajectory), timestamps,
                              mi if timestamps else 50, bool(return_no_speech_prob), rep_p, rep_n, s_k, s_T, s_n)
         return opts, mel

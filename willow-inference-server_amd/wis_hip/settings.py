@@ -93,6 +93,10 @@ class APISettings:
     # vocabulary, style), and text the transcript is made to start with
     initial_prompt: str = ""
     prefix: str = ""
+    # prompted requests (more than 16 prompt tokens) share device batches whatever their prompt lengths: their micro-batcher key carries the pooled
+    # prompt length -1 and the batch decodes through wis_generate_ragged, longest prompt first.  max_new_tokens stays in the key.  False: the key
+    # carries the exact prompt length, as ever - two requests whose prompts differ by a token never meet in a device batch
+    batch_ragged_prompts: bool = False
     # openai-whisper's temperature fallback (decode_with_fallback), as every request without the query parameters of the same names decodes: a
     # window whose result loops (zlib compression ratio of its text above `compression_ratio_threshold`) or scores badly (average log-probability
     # below `logprob_threshold`) is decoded again at each later temperature - a sampled decode of `best_of` samples, the one with the best average

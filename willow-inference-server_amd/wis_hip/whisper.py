@@ -276,6 +276,8 @@ class WhisperModels:
                 import logging
                 logging.getLogger("wis_hip").info("whisper %s loaded: beam_size 1..%d served (max_beam), device batches of up to %d utterances, %d replica(s)",
                                                   size, max_beam, self.settings.max_batch, len(self._models[size]._replicas))
+            # (the batcher's pooled key for prompted requests is the model's to build: it reads the setting where it builds its keys)
+            self._models[size].batch_ragged_prompts = bool(getattr(self.settings, "batch_ragged_prompts", False))
             return self._models[size]
 
     def tokenizer_for(self, size):
