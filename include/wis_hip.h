@@ -449,6 +449,9 @@ int wis_last_timing(const wis_model_t* m, wis_timing_t* t);
  * batched-row kernels, the fourth row is the cross-attention output projection; the cross-attention row carries two stamp sets, entries 0-5 and 7-13:
  * the first K wave and the first V wave of workgroup (0, 0, 0)) */
 int wis_debug_phase_cycles(wis_model_t* m, int B, int beam, int pos, uint64_t* out);
+/* ... and, behind such a call at <= 8 rows with the cross-Q fold on, the stamps of the fused out-projection + cross-Q launch's OTHER arm (the folded
+ * cross-Q, workgroup 0 of its side of the grid) -> out[16]; the out-proj row above is the out-projection arm */
+int wis_debug_phase_cycles_cq_arm(wis_model_t* m, uint64_t* out);
 
 /* ---- tuning tap: device timeline of one decode forward (B x beam rows at text position `pos`): for each of the
  * n_dec_layers * 8 layer kernels (QKV, self-attn, out-proj, cross-Q, cross-attn, cross-out, FFN1, FFN2) the 100 MHz

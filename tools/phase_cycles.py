@@ -48,3 +48,9 @@ for pos in (10,):
                 for name, c in zip(PH, ph):
                     print(f"| {name} | {c} | {100.0 * c / max(1, st[-1] - st[0]):.0f} % |")
                 print(f"| total | {st[-1] - st[0]} | |\n")
+    if B * 5 <= 8:      # the fused out-projection + cross-Q launch: "gemv out-proj" above is its out-projection arm, this its folded cross-Q arm (both workgroup 0 of their side)
+        arm = np.zeros(16, np.uint64)
+        _lib.check(lib.wis_debug_phase_cycles_cq_arm(h, arm.ctypes.data_as(C.POINTER(C.c_uint64))))
+        st = [int(v) for v in arm[:14] if v]
+        if st:
+            print(f"{'gemv cross-Q arm':16s} pos {pos}: total {st[-1] - st[0]:6d} cyc; phases {[st[j + 1] - st[j] for j in range(len(st) - 1)]}")

@@ -655,7 +655,8 @@ __global__ __launch_bounds__(256) void gemv_kernel(WIS_GV_LEAD_DECL(l_), int KC,
 }
 // Two skinny GEMMs in ONE launch (workgroups [0, nA) run problem A, the rest problem B; both f16-activation, single-chunk,
 // <= 16 rows): the decoder's attention output projection together with the cross-attention query projection folded THROUGH it
-// (model.hip fused_out_cq): one dependent stage instead of two.
+// (model.hip out_cq_dual): one dependent stage instead of two.  At d = 384 and 1280 and <= 8 rows the stage runs a kernel of its own
+// (gemv_out_cq_kernel below, out_cq_shape); this one serves the other widths and 9 .. 16 rows.
 template <int SCA, int SCB>
 __global__ __launch_bounds__(256) void gemv_dual_kernel(int nA, int M, const void* ax, const f16* aWp, const void* bx, const void* bx2, const f16* bWp, int bxsplit,
                                                         GemvP pa, GemvP pb) {
@@ -664,6 +665,8 @@ __global__ __launch_bounds__(256) void gemv_dual_kernel(int nA, int M, const voi
   if ((int)blockIdx.x < nA) { pa.x = ax; pa.x2 = nullptr; pa.Wp = aWp; pa.M = M; pa.K = SCA * 128; gemv_body<1, 2, SCA, 1, false>(pa, SCA * 128, blockIdx.x, smem); }
   else { pb.x = bx; pb.x2 = bx2; pb.Wp = bWp; pb.M = M; pb.K = SCB * 128; pb.xsplit = bxsplit; gemv_body<1, 2, SCB, 1, false>(pb, SCB * 128, (int)blockIdx.x - nA, smem); }
 }
+static bool out_cq_shape(const GemvP& pa, const GemvP& pb);      // the stage's own kernel (gemv_out_cq_kernel, below) and the pairs it serves
+static void launch_out_cq(hipStream_t st, dim3 grid, dim3 block, size_t lds, int nA, const GemvP& a, const GemvP& b);
 int launch_gemv_dual(hipStream_t st, const GemvP& pa, const GemvP& pb) {
   if (pa.M != pb.M || pa.M < 1 || pa.M > 16 || pa.x2 || pa.wscale || pb.wscale || (pa.flags & (GV_LN | GV_QKV)) || (pb.flags & (GV_LN | GV_QKV))) { set_error("gemv_dual: unsupported pair"); return WIS_E_UNSUPPORTED; }
   if (pa.M * (pa.K / 8) > 13 * 256 || pb.M * (pb.K / 8) > 13 * 256 || pa.K % 128 || pb.K % 128) { set_error("gemv_dual: rows do not fit the register staging (M=%d K=%d/%d)", pa.M, pa.K, pb.K); return WIS_E_UNSUPPORTED; }
@@ -672,10 +675,14 @@ int launch_gemv_dual(hipStream_t st, const GemvP& pa, const GemvP& pb) {
   const int Kmax = pa.K > pb.K ? pa.K : pb.K;
   const size_t lds = (((size_t)pa.M * (Kmax + 8) * 2 + 15) & ~(size_t)15) + aux;
   if (lds > 65536) { set_error("gemv_dual: LDS"); return WIS_E_UNSUPPORTED; }
-  const int nA = cdiv(pa.N, 16), nB = cdiv(pb.N, 16);
+  // pb.rows = 8: problem B's Wp is the eight-column image (out_cq_dual, where out_cq_nc8_shape holds) - twice the workgroups on B's side
+  const bool b8 = pb.rows == 8;
+  if (b8 && !(out_cq_shape(pa, pb) && out_cq_nc8_shape(pa.M, pa.K))) { set_error("gemv_dual: the eight-column image serves the out-projection + cross-Q pair of large's width, <= 8 rows (M=%d K=%d/%d)", pa.M, pa.K, pb.K); return WIS_E_UNSUPPORTED; }
+  const int nA = cdiv(pa.N, 16), nB = b8 ? pb.N / 8 : cdiv(pb.N, 16);
   dim3 grid(nA + nB), block(256);
-  GemvP a = pa, b = pb; a.rows = 16; b.rows = 16;
-  if (sa == 10 && sb == 20) hipLaunchKernelGGL((gemv_dual_kernel<10, 20>), grid, block, lds, st, nA, a.M, a.x, a.Wp, b.x, b.x2, b.Wp, b.xsplit, a, b);
+  GemvP a = pa, b = pb; a.rows = 16; b.rows = b8 ? 8 : 16;
+  if (out_cq_shape(pa, pb)) launch_out_cq(st, grid, block, lds, nA, a, b);
+  else if (sa == 10 && sb == 20) hipLaunchKernelGGL((gemv_dual_kernel<10, 20>), grid, block, lds, st, nA, a.M, a.x, a.Wp, b.x, b.x2, b.Wp, b.xsplit, a, b);
   else if (sa == 8 && sb == 16) hipLaunchKernelGGL((gemv_dual_kernel<8, 16>), grid, block, lds, st, nA, a.M, a.x, a.Wp, b.x, b.x2, b.Wp, b.xsplit, a, b);
   else if (sa == 6 && sb == 12) hipLaunchKernelGGL((gemv_dual_kernel<6, 12>), grid, block, lds, st, nA, a.M, a.x, a.Wp, b.x, b.x2, b.Wp, b.xsplit, a, b);
   else if (sa == 4 && sb == 8) hipLaunchKernelGGL((gemv_dual_kernel<4, 8>), grid, block, lds, st, nA, a.M, a.x, a.Wp, b.x, b.x2, b.Wp, b.xsplit, a, b);
@@ -790,6 +797,146 @@ __global__ __launch_bounds__(256) void gemv_nc5_kernel(WIS_GV_LEAD_DECL(l_), int
   }
   stamp(pf, 6);
   if (tid == 0) tl_end(p.prof);
+}
+
+// ---- the fused out-projection + folded cross-Q stage of <= 8 rows: a kernel of its own (launch_gemv_dual selects it) ------------------------------------
+// gemv_dual_kernel's two arms on the same sixteen-column images, the same k order per wave, the same cross-wave sum and epilogue arithmetic: the same bits.
+// What differs is when a wave asks for what.  In gemv_dual_kernel<10, 20> the guarded activation requests (`if (idx < nx) xh[i] = ...`, thirteen slots for
+// rows that fill five) compiled to thirteen branches with a wait for everything outstanding behind each load: three dependent memory round trips, four in
+// wave 0, before the first weight byte was requested.  Here a thread's pieces number what eight rows need (NXH), every one is requested unconditionally at a
+// clamped index - a thread beyond the rows asks for the last piece and drops it - and the arm's weight requests follow in index order with no branch and no
+// wait in between.  Arm B (K = 2d, the longer stream) takes gemv_nc5_kernel's schedule: the wave's B operands go from LDS into registers once behind the
+// staging barrier, and the MFMAs consume the requests in index order while the rest of the stream is in flight (left alone, hipcc waited for 19 of the 20
+// requests behind the fourth MFMA and read each B operand from LDS in front of its MFMA).  Arm A keeps gemv_body's loop.
+// SC = d / 128: k-steps per wave of arm A; arm B's waves take 2 SC.
+// NC (arm B): output columns per workgroup.  8: Wp is the eight-column image (pack_gemv_nc8_kernel) - a request is eight columns x two k-steps, two MFMAs
+// through row_ror:8 as in gemv_body NC = 8, SW / 2 requests per wave, d / 8 workgroups.
+template <int SC, bool ARM_B, int NC = 16>
+__device__ __forceinline__ void out_cq_arm(const GemvP& p, const int nt, char* smem) {
+  static_assert(NC == 16 || (NC == 8 && ARM_B), "eight-column tiles: arm B");
+  constexpr int SW = ARM_B ? 2 * SC : SC, K = SW * 128, xstr = K + 8, c8 = K / 8, s8 = c8 / 2;
+  constexpr int RQ = NC == 8 ? SW / 2 : SW;      // weight requests per wave
+  constexpr int NXH = (8 * c8 + 255) / 256;      // 16-byte pieces per thread at eight rows
+  const int M = p.M;
+  f16* xs = reinterpret_cast<f16*>(smem);
+  float* red = reinterpret_cast<float*>(smem + (((size_t)M * xstr * 2 + 15) & ~(size_t)15));
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  unsigned long long* pf = (nt == 0 && tid == 0) ? p.prof : nullptr;
+  if (tid == 0) tl_begin(p.prof);
+  stamp(pf, 0);
+  // activation rows (written by the previous launch): arm A's are the attention output, arm B's the row-wise concatenation [x | x2] at column d
+  const int nx = M * c8;
+  const u32x4* x8 = reinterpret_cast<const u32x4*>(p.x);
+  const u32x4* y8 = reinterpret_cast<const u32x4*>(p.x2);
+  u32x4 xh[NXH];
+#pragma unroll
+  for (int i = 0; i < NXH; ++i) {
+    const int idx = min(tid + 256 * i, nx - 1);
+    if (ARM_B) {
+      const int row = idx / c8, col = idx - row * c8;
+      const u32x4* src = col < s8 ? x8 + (row * s8 + col) : y8 + (row * s8 + (col - s8));
+      xh[i] = *src;
+    } else xh[i] = x8[idx];
+  }
+  GV_IN_ORDER();
+  // the wave's weight fragments: k-steps wave SW .. wave SW + SW - 1 of tile nt, all requested up front (either image: RQ KiB-requests per tile and wave)
+  const u32x4* wq = reinterpret_cast<const u32x4*>(p.Wp) + ((size_t)nt * 4 + wave) * RQ * 64 + lane;
+  u32x4 wf[RQ];
+#pragma unroll
+  for (int u = 0; u < RQ; ++u) { wf[u] = __builtin_nontemporal_load(wq + (size_t)u * 64); GV_IN_ORDER(); }
+  stamp(pf, 1);
+#pragma unroll
+  for (int i = 0; i < NXH; ++i) {
+    const int idx = tid + 256 * i;
+    if (idx < nx) { const int row = idx / c8, k8 = idx - row * c8; *reinterpret_cast<u32x4*>(xs + (size_t)row * xstr + k8 * 8) = xh[i]; }
+  }
+  __syncthreads();
+  stamp(pf, 3);
+  f32x4 acc = f32x4{0.f, 0.f, 0.f, 0.f};
+  const f16* xw = xs + ((lane & 15) < M ? (lane & 15) : M - 1) * xstr + 8 * (lane >> 4) + wave * SW * 32;
+  if (ARM_B) {
+    f16x8 xb[SW];
+#pragma unroll
+    for (int k = 0; k < SW; ++k) xb[k] = *reinterpret_cast<const f16x8*>(xw + k * 32);
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int u = 0; u < RQ; ++u) {
+      if (NC == 8) {      // rows 0-7 of the accumulator see k-steps 2 u, 2 u + 1 in order; rows 8-15 are by-products nobody reads
+        acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(*reinterpret_cast<const f16x8*>(&wf[u]), xb[2 * u], acc, 0, 0, 0);
+        acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(nc5_rot<0x128>(wf[u]), xb[NC == 8 ? 2 * u + 1 : 0], acc, 0, 0, 0);
+      } else acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(*reinterpret_cast<const f16x8*>(&wf[u]), xb[u], acc, 0, 0, 0);
+      GV_IN_ORDER();
+    }
+  } else {
+#pragma unroll
+    for (int u = 0; u < SW; ++u)
+      acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(*reinterpret_cast<const f16x8*>(&wf[u]), *reinterpret_cast<const f16x8*>(xw + u * 32), acc, 0, 0, 0);
+  }
+  stamp(pf, 4);
+  // epilogue operands, requested behind the stream and covered by the reduction barrier, as in gemv_body; wave 0 finishes the tile
+  const int ep_m = lane & 15, ep_n = NC * nt + 4 * (lane >> 4);
+  const bool ep_ok = tid < 64 && ep_m < M && ep_n < p.N && 4 * (lane >> 4) < NC;
+  float4 ep_bias = make_float4(0.f, 0.f, 0.f, 0.f), ep_res = ep_bias;
+  if (ep_ok) {
+    if (p.bias) ep_bias = *reinterpret_cast<const float4*>(p.bias + ep_n);
+    if (!ARM_B) ep_res = *reinterpret_cast<const float4*>(reinterpret_cast<const float*>(p.y) + (size_t)ep_m * p.N + ep_n);
+  }
+  *reinterpret_cast<float4*>(red + ((size_t)wave * 64 + lane) * 4) = make_float4(acc[0], acc[1], acc[2], acc[3]);
+  __syncthreads();
+  stamp(pf, 5);
+  if (tid < 64) {
+    float4 s = make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll
+    for (int w = 0; w < 4; ++w) {
+      const float4 t = *reinterpret_cast<const float4*>(red + ((size_t)w * 64 + lane) * 4);
+      s.x += t.x; s.y += t.y; s.z += t.z; s.w += t.w;
+    }
+    float4 rsum = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (ep_ok) {
+      s.x += ep_bias.x; s.y += ep_bias.y; s.z += ep_bias.z; s.w += ep_bias.w;
+      const size_t o = (size_t)ep_m * p.N + ep_n;
+      if (ARM_B) {      // GV_OUT_F32: the raw folded query
+        *reinterpret_cast<float4*>(reinterpret_cast<float*>(p.y) + o) = s;
+      } else {          // GV_RESID: x1 in place
+        const float4 r = make_float4(ep_res.x + s.x, ep_res.y + s.y, ep_res.z + s.z, ep_res.w + s.w);
+        rsum = r;
+        *reinterpret_cast<float4*>(reinterpret_cast<float*>(p.y) + o) = r;
+      }
+    }
+    // LayerNorm partials of x1 per (row, 16-column tile): (sum, M2 about the tile mean), gemv_body's arithmetic - the cross-attention merges d / 16 pairs per row
+    if (!ARM_B && p.stat_out) {
+      float t1 = ep_ok ? (rsum.x + rsum.y) + (rsum.z + rsum.w) : 0.f;
+      t1 += __shfl_xor(t1, 16); t1 += __shfl_xor(t1, 32);
+      float t2 = 0.f;
+      if (ep_ok) { const float ml = t1 * 0.0625f, a_ = rsum.x - ml, b_ = rsum.y - ml, c_ = rsum.z - ml, e_ = rsum.w - ml; t2 = (a_ * a_ + b_ * b_) + (c_ * c_ + e_ * e_); }
+      t2 += __shfl_xor(t2, 16); t2 += __shfl_xor(t2, 32);
+      if ((lane >> 4) == 0 && ep_m < M && 16 * nt < p.N) *reinterpret_cast<float2*>(p.stat_out + ((size_t)ep_m * (p.N >> 4) + nt) * 2) = make_float2(t1, t2);
+    }
+  }
+  stamp(pf, 6);
+  if (tid == 0) tl_end(p.prof);
+}
+// (the argument list of gemv_dual_kernel: what the first loads need leads as scalars)
+template <int SC, int NCB>
+__global__ __launch_bounds__(256) void gemv_out_cq_kernel(int nA, int M, const void* ax, const f16* aWp, const void* bx, const void* bx2, const f16* bWp, int bxsplit,
+                                                          GemvP pa, GemvP pb) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  (void)bxsplit;      // (= d: the launcher checked it)
+  if ((int)blockIdx.x < nA) { pa.x = ax; pa.x2 = nullptr; pa.Wp = aWp; pa.M = M; out_cq_arm<SC, false>(pa, blockIdx.x, smem); }
+  else { pb.x = bx; pb.x2 = bx2; pb.Wp = bWp; pb.M = M; out_cq_arm<SC, true, NCB>(pb, (int)blockIdx.x - nA, smem); }
+}
+// arm B on eight-column tiles: large's width, a CU for each of the d / 16 + d / 8 workgroups (one dispatch round, as gemv_nc5_shape)
+bool out_cq_nc8_shape(int M, int d) { return d == 1280 && M >= 1 && M <= 8 && d / 16 + d / 8 <= device_cu_count(); }
+// the pairs the kernel above serves (launch_gemv_dual has checked the rest): the stage as out_cq_dual assembles it - residual out-projection d x d beside the
+// raw cross-Q d x 2d on [x | x2] split at d, f16 weights, whole sixteen-column tiles, <= 8 rows - at the widths it is instantiated for
+static bool out_cq_shape(const GemvP& pa, const GemvP& pb) {
+  return pa.M <= 8 && pa.flags == GV_RESID && pb.flags == GV_OUT_F32 && pb.K == 2 * pa.K && pb.x2 && pb.xsplit == pa.K && !pa.y16 && !pb.y16 && !pb.stat_out &&
+         pa.N % 16 == 0 && pb.N % 16 == 0 && (pa.K == 1280 || pa.K == 384);
+}
+static void launch_out_cq(hipStream_t st, dim3 grid, dim3 block, size_t lds, int nA, const GemvP& a, const GemvP& b) {
+  if (b.rows == 8) hipLaunchKernelGGL((gemv_out_cq_kernel<10, 8>), grid, block, lds, st, nA, a.M, a.x, a.Wp, b.x, b.x2, b.Wp, b.xsplit, a, b);
+  else if (a.K == 1280) hipLaunchKernelGGL((gemv_out_cq_kernel<10, 16>), grid, block, lds, st, nA, a.M, a.x, a.Wp, b.x, b.x2, b.Wp, b.xsplit, a, b);
+  else hipLaunchKernelGGL((gemv_out_cq_kernel<3, 16>), grid, block, lds, st, nA, a.M, a.x, a.Wp, b.x, b.x2, b.Wp, b.xsplit, a, b);
 }
 int launch_gemv(hipStream_t st, const GemvP& p) {
   if (p.M < 1 || p.M > 16 || p.K % 128 || (p.N % 4 && p.rows != 5)) { set_error("gemv: M=%d N=%d K=%d unsupported (the LDS-staged form holds one 16-row block; more rows take launch_gemv_frag)", p.M, p.N, p.K); return WIS_E_UNSUPPORTED; }

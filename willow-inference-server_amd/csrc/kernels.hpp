@@ -69,7 +69,7 @@ struct GemvP {
   // GV_QKV epilogue: n < d -> q (f32 [M][d]); d <= n < 2d -> K cache; n >= 2d -> V cache
   float* q; f16* kc; f16* vc; const int* slot; const int* pos; int d; int ctx;   // cache [slots][ctx][d]
   unsigned long long* prof;      // optional phase stamps (workgroup 0)
-  int rows;                      // output columns per workgroup (0 => 16): 16 = Wp in A-fragment order, 8 (launch_gemv, gemv_nc8_shape only) = Wp the eight-column image of launch_pack_gemv_nc8, 5 (launch_gemv, gemv_nc5_shape only) = Wp the five-column image of launch_pack_gemv_nc5
+  int rows;                      // output columns per workgroup (0 => 16): 16 = Wp in A-fragment order, 8 (launch_gemv, gemv_nc8_shape only) = Wp the eight-column image of launch_pack_gemv_nc8, 5 (launch_gemv, gemv_nc5_shape only) = Wp the five-column image of launch_pack_gemv_nc5; launch_gemv_dual: problem B's 8 under out_cq_nc8_shape, else ignored
   const void* x2; int xsplit;    // f16 activations only: columns >= xsplit are read from x2 (row-major [M][K - xsplit]); x then is [M][xsplit]
   f16* y16;                      // GV_RESID: optional f16 row-major copy of the produced rows
   // ---- batched rows (launch_gemv_frag, M > 8): activations live in HBM in MFMA B-fragment order ("xf", xf_index below)
@@ -91,6 +91,9 @@ struct GemvP {
 int launch_gemv(hipStream_t st, const GemvP& p);
 // two f16-activation skinny GEMMs in one launch
 int launch_gemv_dual(hipStream_t st, const GemvP& pa, const GemvP& pb);
+// launch_gemv_dual serves pb.rows = 8 (problem B's Wp the eight-column image of launch_pack_gemv_nc8) for the out-projection + cross-Q pair at these shapes:
+// large's width, <= 8 rows, d / 16 + d / 8 workgroups in one dispatch round on this device
+bool out_cq_nc8_shape(int M, int d);
 // Batched decode rows (8 < M <= 96).  The skinny GEMM reads its activations as ready-made MFMA B fragments straight from L2
 // (written in that order by the producing kernel: no per-workgroup LDS staging, no staging barrier, many workgroups per CU), and
 // the pre-LN LayerNorm needs no launch of its own: every residual epilogue leaves per-16-column partial sums of the rows it

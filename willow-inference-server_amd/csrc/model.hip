@@ -393,6 +393,13 @@ static int load_weights(wis_model* m, const Loader& L) {
         if ((rc = dalloc(m, &b_cqo, (size_t)d))) break;
         if ((rc = build_cq_fold(m->st, tmp, so.p, so.f16, w.out.bias, d, qs, fcat, fwot, fwqo, p_cqo, b_cqo))) break;
         w.cqo = DecProj{p_cqo, nullptr, b_cqo, nullptr, d, 2 * d, 16};
+        // ... and its eight-column image for the pass of <= 8 rows (fcat still holds the row-major [d][2d]); the batched route keeps reading the other
+        if (!m->w8 && out_cq_nc8_shape(1, d)) {
+          f16* p8 = nullptr;
+          if ((rc = dalloc(m, &p8, (size_t)d * 2 * d))) break;
+          if ((rc = launch_pack_gemv_nc8(m->st, fcat, p8, d, d, 2 * d))) break;
+          w.cqo.Wp8 = p8;
+        }
       }
       w.w_ckv = m->w_ckv_all + (size_t)l * 2 * d * d; w.b_ckv = m->b_ckv_all + (size_t)l * 2 * d;
       if ((rc = to_f16_mat(m, L, p + "attention/linear_1/weight", 2 * d, d, &w.w_ckv))) break;
@@ -738,7 +745,8 @@ GemvP gemv_frag(const DecProj& p, const void* xf, int M, int flags) {
   g.x = xf; g.csum = p.csum; g.Wp = p.Wp; g.wscale = p.scale; g.bias = p.bias; g.M = M; g.N = p.N; g.K = p.K; g.flags = flags; g.xmb = cdiv(M, 16); g.rows = 16;
   return g;
 }
-// The fused out-projection + cross-Q stage (cq_fold; w.cqo = packed [W'q | W'q Wo], W'q bo), <= 8 rows, ONE launch_gemv_dual (which sets `rows`):
+// The fused out-projection + cross-Q stage (cq_fold; w.cqo = packed [W'q | W'q Wo], W'q bo), <= 8 rows, ONE launch_gemv_dual (`rows` of gb: 8 = w.cqo's
+// eight-column image, where the loader added one and out_cq_nc8_shape holds for these rows - 160 workgroups on the cross-Q's side instead of 80; else 0):
 //   ga: x1 = x0 + Wo a + bo in place, x1's LayerNorm partials to `stat` (the cross-attention's prologue merges them: decode step 1.352 -> 1.330 ms)
 //   gb: q_raw = W'q x0 + (W'q Wo) a + W'q bo from the f16 layer input xh and the attention output a; the cross-attention kernel applies rs, mu of x1 and b'
 void out_cq_dual(const DecLayerW& w, const f16* a, const f16* xh, float* x1, float* stat, float* q, int M, GemvP* ga, GemvP* gb) {
@@ -747,6 +755,7 @@ void out_cq_dual(const DecLayerW& w, const f16* a, const f16* xh, float* x1, flo
   ga->x = a; ga->Wp = w.out.Wp; ga->bias = w.out.bias; ga->y = x1; ga->M = M; ga->N = d; ga->K = d; ga->flags = GV_RESID; ga->stat_out = stat;
   memset(gb, 0, sizeof(*gb));
   gb->x = xh; gb->x2 = a; gb->xsplit = d; gb->Wp = w.cqo.Wp; gb->bias = w.cqo.bias; gb->y = q; gb->M = M; gb->N = d; gb->K = w.cqo.K; gb->flags = GV_OUT_F32;
+  if (w.cqo.Wp8 && out_cq_nc8_shape(M, d)) { gb->Wp = w.cqo.Wp8; gb->rows = 8; }
 }
 // The same stage on batched rows, ONE launch_gemv_frag3 of three d x d problems: x1 = x0 + Wo a + bo (+ partials; x1's fragment image has no reader, so
 // x0's image xf stays valid), q = W'q x0 + W'q bo and q2 = (W'q Wo) a - the two k-step halves of w.cqo.  The cross-attention kernel finishes
@@ -913,6 +922,7 @@ int dec_forward(wis_model* m, int M, int R, int B, bool want_logits, int sstride
       GemvP ga, gb;
       out_cq_dual(w, m->dao, m->dxh, m->dx, m->dstat, m->dq, M, &ga, &gb);
       ga.prof = pr ? pr + 32 : nullptr;
+      gb.prof = pr ? pr + 48 : nullptr;      // (arm B stamps the cross-Q row, which the fold leaves free)
       WIS_RET(launch_gemv_dual(st, ga, gb));
       CrossAttnP cf = ca;      // the folded query: statistics of x1 from the out-projection's row partials
       cf.xres = m->dstat; cf.qcs = w.cq.csum; cf.qb = w.cq.bias; cf.xres_is_stat = 1;

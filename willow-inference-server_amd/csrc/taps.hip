@@ -95,6 +95,14 @@ int wis_debug_phase_cycles(wis_model_t* m, int B, int beam, int pos, uint64_t* o
   return WIS_OK;
 }
 
+int wis_debug_phase_cycles_cq_arm(wis_model_t* m, uint64_t* out) {
+  if (!m || !out) { set_error("wis_debug_phase_cycles_cq_arm: bad argument"); return WIS_E_ARG; }
+  if (!WIS_TAPS) { set_error("tuning taps are not compiled in (rebuild with WIS_EXTRA_HIPFLAGS=-DWIS_TAPS=1)"); return WIS_E_UNSUPPORTED; }
+  WIS_HIP_CHECK(hipSetDevice(m->device));
+  WIS_HIP_CHECK(hipMemcpy(out, m->d_prof + 3 * 16, 16 * 8, hipMemcpyDeviceToHost));      // (row 3, the cross-Q row: dec_forward hands it to the launch's arm B)
+  return WIS_OK;
+}
+
 int wis_debug_sampling_cycles(wis_model_t* m, uint64_t* out) {
   if (!m || !out) { set_error("wis_debug_sampling_cycles: bad argument"); return WIS_E_ARG; }
   if (!WIS_TAPS) { set_error("tuning taps are not compiled in (rebuild with WIS_EXTRA_HIPFLAGS=-DWIS_TAPS=1)"); return WIS_E_UNSUPPORTED; }
@@ -535,6 +543,12 @@ int wis_op_gemv_out_cq(int device, const void* a, const float* x0, const void* W
   WIS_RET(prep_projection(st, wtmp, d, d, d, d, qs, gamma, beta, qb, qcs, nullptr, nullptr, 16));      // (the fold alone: the stage streams w.out and w.cqo)
   WIS_RET(launch_pack_gemv(st, reinterpret_cast<const f16*>(Wo), p_out, d, d, d, 0, 1.f, w.out.rows));
   WIS_RET(build_cq_fold(st, wtmp, Wo, 1, bo, d, qs, fcat, fwot, fwqo, p_cqo, b_cqo));
+  if (out_cq_nc8_shape(1, d)) {      // ... and the eight-column image where the loader adds one (out_cq_dual picks it)
+    f16* p8 = nullptr;
+    WIS_RET(t.get(&p8, (size_t)2 * d * d));
+    WIS_RET(launch_pack_gemv_nc8(st, fcat, p8, d, d, 2 * d));
+    w.cqo.Wp8 = p8;
+  }
   hipMemcpyAsync(x1, x0, (size_t)M * d * 4, hipMemcpyDeviceToDevice, st);      // the residual epilogue works in place
   if (!frag) {
     // dec_forward: one dual launch on the f16 rows (the attention output; the f16 copy of the layer input that the embedding / FFN2 epilogues leave)
