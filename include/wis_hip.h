@@ -573,6 +573,11 @@ int wis_op_gemv_qkv(int device, const float* x, const float* gamma, const float*
 int wis_op_gemv_out_cq(int device, const void* a_f16, const float* x0, const void* Wo_f16, const float* bo, const void* Wq_f16, const float* bq,
                        const float* gamma, const float* beta, float* x1, float* stat, float* q, float* q2, float* qcs, float* qb,
                        int M, int d, int force_frag);
+/* the wave reductions of the LayerNorm-folded projections' tail, side by side: ONE wave takes x f32 [N][64] (value i of lane l at x[i][l]) and runs
+ * wave_sum on each of the N values and then wave_sums<N> on the same registers, in one launch -> out_old / out_new f32 [N][64], every lane's result of
+ * either (all 64 words of a value are equal, and out_new equals out_old bit for bit: the tree is the contract).  N = 6, 10 or 16: the 2 RM sums of
+ * the three row-register forms of gemv_kernel MODE 1; any other N is WIS_E_ARG. */
+int wis_op_wave_sums(int device, const float* x, int N, float* out_old, float* out_new);
 /* ONE projection stage of the batched decode route (9 .. 96 rows), assembled by the builders the decoder forward itself uses; W f16 [N][K] row-major and
  * bias f32 [N] are prepared as the loader does (w8 != 0: quantised to per-row int8 first; stages 1 / 2: the LayerNorm gamma / beta folded in).
  *   stage 0  residual: y f32 [M][N] += x W^T + bias in place; y_xf (optional) the produced rows' f16 fragment image of ceil(M / 16) row blocks

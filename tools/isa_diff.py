@@ -9,8 +9,8 @@ the old kernel of the closest demangled name and printed with both sets of figur
 
 Limits: `s_nop` padding is not part of a stream, so kernels that differ only in it count as equal (neither is the `...` llvm-objdump prints
 for a run of zero bytes: the alignment gap behind a kernel's `s_endpgm`, which depends on what the code object holds next); the pairing of a changed kernel with an old
-one is by name similarity alone (it can pair unrelated kernels, and it fails if more kernels changed than old ones are left over) - read the
-"was" line of every pair."""
+one is by name similarity alone (it can pair unrelated kernels) - read the "was" line of every pair.  A kernel of the new build for which no old
+kernel of the same template name is left over is printed as new, with its own figures."""
 import collections
 import difflib
 import os
@@ -93,11 +93,18 @@ def main(old_dir, new_dir):
         else:
             changed.append(n)
     left = sorted(n for ns in pool.values() for n in ns)
-    print(f"kernels: {len(old)} old, {len(new)} new; {len(equal)} instruction-equal with equal VGPRs / SGPRs / LDS / scratch "
-          f"({sum(1 for a, b in equal if a != b)} of them under a new name), {len(changed)} changed, {len(left) - len(changed)} gone")
     gone = list(left)
+    # (a kernel the old build has no like of - no old kernel left over that shares the name in front of the template arguments - is new)
+    fresh = [n for n in changed if not any(short(g).split("<")[0] == short(n).split("<")[0] for g in gone)]
+    print(f"kernels: {len(old)} old, {len(new)} new; {len(equal)} instruction-equal with equal VGPRs / SGPRs / LDS / scratch "
+          f"({sum(1 for a, b in equal if a != b)} of them under a new name), {len(changed) - len(fresh)} changed, {len(fresh)} added, "
+          f"{len(left) - len(changed) + len(fresh)} gone")
     print("\n## changed (old -> new): instructions, VGPRs, SGPRs, LDS bytes, scratch bytes, waves per SIMD by registers")
     for n in changed:
+        if n in fresh:
+            b = new[n]
+            print(f"{short(n)}\n    new: instr {len(b[4])}, VGPR {b[0]}, SGPR {b[1]}, LDS {b[2]}, scratch {b[3]}")
+            continue
         cand = difflib.get_close_matches(short(n), [short(g) for g in gone], n=1, cutoff=0.0)
         o = next(g for g in gone if short(g) == cand[0])
         gone.remove(o)

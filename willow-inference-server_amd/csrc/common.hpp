@@ -60,6 +60,34 @@ __device__ __forceinline__ float wave_sum(float v) {
   const float a = readlane_f(v, 0), b = readlane_f(v, 16), c = readlane_f(v, 32), d = readlane_f(v, 48);
   return (a + b) + (c + d);
 }
+// N sums at once, each the very word wave_sum returns for it (on every lane): the same balanced pairwise tree - xor 1, xor 2, the other quad, the
+// other half row, then (row 0 + row 1) + (row 2 + row 3) - with the N chains interleaved step by step, so that no DPP add waits for the one in front
+// of it (wave_sum alone is a serial chain with an s_nop behind every link), and the four rows closed with gfx950's row swaps instead of four
+// v_readlane into SGPRs per value: v_permlane16_swap of a register with its copy leaves rows (0, 0, 2, 2) in one and (1, 1, 3, 3) in the other,
+// v_permlane32_swap the lower half twice and the upper half twice.  Row 0's lanes add (r0 + r1) and then (r0 + r1) + (r2 + r3) with the operands
+// in wave_sum's order; the other rows add the same words in the other order, which float addition does not see.  (xrow_sum in dec_kernels.hip
+// swaps the halves first: (r0 + r2) + (r1 + r3), another sum.)
+template <int N>
+__device__ __forceinline__ void wave_sums(float (&v)[N]) {
+#pragma unroll
+  for (int i = 0; i < N; ++i) v[i] += dpp_f<0xB1>(v[i]);    // quad_perm [1,0,3,2]
+#pragma unroll
+  for (int i = 0; i < N; ++i) v[i] += dpp_f<0x4E>(v[i]);    // quad_perm [2,3,0,1]
+#pragma unroll
+  for (int i = 0; i < N; ++i) v[i] += dpp_f<0x141>(v[i]);   // row_half_mirror
+#pragma unroll
+  for (int i = 0; i < N; ++i) v[i] += dpp_f<0x140>(v[i]);   // row_mirror
+#pragma unroll
+  for (int i = 0; i < N; ++i) {
+    const auto s = __builtin_amdgcn_permlane16_swap(__float_as_uint(v[i]), __float_as_uint(v[i]), false, false);
+    v[i] = __uint_as_float(s[0]) + __uint_as_float(s[1]);
+  }
+#pragma unroll
+  for (int i = 0; i < N; ++i) {
+    const auto s = __builtin_amdgcn_permlane32_swap(__float_as_uint(v[i]), __float_as_uint(v[i]), false, false);
+    v[i] = __uint_as_float(s[0]) + __uint_as_float(s[1]);
+  }
+}
 __device__ __forceinline__ float wave_max(float v) {
   v = fmaxf(v, dpp_f<0xB1>(v));
   v = fmaxf(v, dpp_f<0x4E>(v));

@@ -408,14 +408,18 @@ __device__ __forceinline__ void gemv_body(const GemvP& p, const int KC, const in
   const int ep_m = NT == 2 ? (lane & 15) : (tid >> 6) * 16 + (lane & 15), ep_n = rows * (nt * NT + (NT == 2 ? (tid >> 6) & 1 : 0)) + 4 * (lane >> 4);
   const bool ep_ok = ep_act && ep_m < M && ep_n < p.N && 4 * (lane >> 4) < rows;
   float4 ep_bias = make_float4(0.f, 0.f, 0.f, 0.f), ep_cs = ep_bias, ep_res = ep_bias, ep_sc = make_float4(1.f, 1.f, 1.f, 1.f);
-  int ep_slot = 0, ep_pos = 0;
+  // (MODE 1 leaves slot and position unset where the K / V arm that reads them does not run: zeroing their registers on the other paths made hipcc wait
+  // there for the requests it believes may be in flight into them - s_waitcnt vmcnt(0) in front of the reductions, for bias and column sums as well)
+  int ep_slot, ep_pos;
+  if constexpr (MODE != 1) { ep_slot = 0; ep_pos = 0; }
+#define WIS_FL (MODE == 1 ? fl : p.flags)      /* (the other modes read the struct where they always did: their instructions stay) */
 #define WIS_EP_LOADS()                                                                                              \
   if (ep_ok) {                                                                                                      \
     if (p.bias) ep_bias = *reinterpret_cast<const float4*>(p.bias + ep_n);                                          \
     if (fast) ep_cs = *reinterpret_cast<const float4*>(p.csum + ep_n);                                              \
     if (W8) ep_sc = *reinterpret_cast<const float4*>(p.wscale + ep_n);                                              \
-    if (p.flags & GV_QKV) { if (ep_n >= p.d) { ep_slot = p.slot[ep_m]; ep_pos = p.pos[ep_m]; } }                    \
-    else if (p.flags & GV_RESID) ep_res = *reinterpret_cast<const float4*>(reinterpret_cast<const float*>(p.y) + (size_t)ep_m * p.N + ep_n); \
+    if (WIS_FL & GV_QKV) { if (ep_n >= p.d) { ep_slot = p.slot[ep_m]; ep_pos = p.pos[ep_m]; } }                    \
+    else if (WIS_FL & GV_RESID) ep_res = *reinterpret_cast<const float4*>(reinterpret_cast<const float*>(p.y) + (size_t)ep_m * p.N + ep_n); \
   }
   stamp(pf, 1);
   float sa[RMAX], sb[RMAX];
@@ -473,6 +477,11 @@ __device__ __forceinline__ void gemv_body(const GemvP& p, const int KC, const in
   for (int mb = 0; mb < MB; ++mb) { int r = mb * 16 + (lane & 15); xrow[mb] = (r < M ? r : M - 1) * xstr + 8 * (lane >> 4); }
 
   const int c8n = KC / 8;
+  // p.flags sits in the by-value struct, which is not preloaded, and hipcc sank its scalar load BEHIND the MFMA loop, with the wait in front of the first
+  // epilogue operand request.  MODE 1: held in an SGPR from here on, so it is fetched with the operand pointers in front of the loop and waited for at its head.
+  int fl = 0;
+  if constexpr (MODE == 1) { fl = p.flags; asm volatile("" : "+s"(fl)); }
+  if constexpr (MODE == 1) __builtin_assume(K >= 128);      // (the loop runs: without this hipcc guards registers of the weight ring behind it with vmcnt waits for a path that skips it)
   for (int kc0 = 0; kc0 < K; kc0 += KC) {
     const WT* wq = wp4 + (size_t)(kc0 / 32 + ksl0) * wstep;
     const bool more = MB > 1 && kc0 + KC < K;     // (dead: MB == 1)
@@ -551,7 +560,21 @@ __device__ __forceinline__ void gemv_body(const GemvP& p, const int KC, const in
   // covered by the reductions and the barrier below; requested BEFORE the activations they delayed them and cost more than they saved)
   WIS_EP_LOADS()
 #undef WIS_EP_LOADS
-  if (fast) {   // LayerNorm statistics of the folded form: reduced here, behind the MFMAs, published with the accumulators
+  if constexpr (MODE == 1) {   // LayerNorm statistics of the folded form: reduced here, behind the MFMAs, published with the accumulators
+    // (the wave's 2 RM sums through one interleaved tree - wave_sum's own, word for word - and lane 0 publishes them behind ONE branch with wide LDS
+    // stores; one wave_sum per value was ~190 dependent instructions, five exec-masked branches and five ds_write_b64 in front of the barrier, with
+    // the MFMA loop over and nothing to run beside them)
+    float t[2 * RMAX];
+#pragma unroll
+    for (int r = 0; r < RMAX; ++r) { t[2 * r] = sa[r]; t[2 * r + 1] = sb[r]; }
+    wave_sums(t);
+    if (lane == 0) {
+      float* o = sred + wave * 16;
+#pragma unroll
+      for (int i = 0; i + 4 <= 2 * RMAX; i += 4) *reinterpret_cast<float4*>(o + i) = make_float4(t[i], t[i + 1], t[i + 2], t[i + 3]);
+      if constexpr ((2 * RMAX) % 4 != 0) *reinterpret_cast<float2*>(o + 2 * RMAX - 2) = make_float2(t[2 * RMAX - 2], t[2 * RMAX - 1]);
+    }
+  } else if (fast) {
 #pragma unroll
     for (int r = 0; r < RMAX; ++r) {
       const float ta = wave_sum(sa[r]), tb = wave_sum(sb[r]);
@@ -595,25 +618,33 @@ __device__ __forceinline__ void gemv_body(const GemvP& p, const int KC, const in
         s.x = rs * (s.x - mu * ep_cs.x); s.y = rs * (s.y - mu * ep_cs.y); s.z = rs * (s.z - mu * ep_cs.z); s.w = rs * (s.w - mu * ep_cs.w);
       }
       s.x += ep_bias.x; s.y += ep_bias.y; s.z += ep_bias.z; s.w += ep_bias.w;
-      if (p.flags & GV_QKV) {
+      if (WIS_FL & GV_QKV) {
         const int d = p.d;
         if (n < d) {
           *reinterpret_cast<float4*>(p.q + (size_t)m * d + n) = s;
         } else {
           const bool isk = n < 2 * d;
-          f16* dst = (isk ? p.kc : p.vc) + ((size_t)ep_slot * p.ctx + ep_pos) * d + (n - (isk ? d : 2 * d));
+          // (MODE 1: slot and position widen by ZERO - both are non-negative -, which is no instruction; widened by sign, hipcc shifted each at its load,
+          // behind an s_waitcnt vmcnt, so wave 0 of a K / V tile sat out the operands' round trip in front of the statistics reduction.  64-bit as before:
+          // slot * ctx * d passes 2^31 elements at large's cache sizes.)
+          f16* dst;
+          if constexpr (MODE == 1) {
+            asm volatile("" : "+v"(ep_slot), "+v"(ep_pos));      // (the 32-bit words as they landed, opaque up to here: nothing of the widening moves up to the requests)
+            dst = (isk ? p.kc : p.vc) + ((size_t)(unsigned)ep_slot * (size_t)p.ctx + (size_t)(unsigned)ep_pos) * d + (n - (isk ? d : 2 * d));
+          } else
+          dst = (isk ? p.kc : p.vc) + ((size_t)ep_slot * p.ctx + ep_pos) * d + (n - (isk ? d : 2 * d));
           const f16x4 o = {(f16)s.x, (f16)s.y, (f16)s.z, (f16)s.w};
           *reinterpret_cast<f16x4*>(dst) = o;
         }
       } else {
-        if (p.flags & GV_GELU) { s.x = gelu_erf(s.x); s.y = gelu_erf(s.y); s.z = gelu_erf(s.z); s.w = gelu_erf(s.w); }
+        if (WIS_FL & GV_GELU) { s.x = gelu_erf(s.x); s.y = gelu_erf(s.y); s.z = gelu_erf(s.z); s.w = gelu_erf(s.w); }
         const size_t o = (size_t)m * p.N + n;
-        if (p.flags & GV_RESID) {
+        if (WIS_FL & GV_RESID) {
           const float4 r = make_float4(ep_res.x + s.x, ep_res.y + s.y, ep_res.z + s.z, ep_res.w + s.w);
           rsum = r;
           *reinterpret_cast<float4*>(reinterpret_cast<float*>(p.y) + o) = r;
           if (p.y16) { const f16x4 h = {(f16)r.x, (f16)r.y, (f16)r.z, (f16)r.w}; *reinterpret_cast<f16x4*>(p.y16 + o) = h; }   // f16 copy: next layer's folded cross-Q input
-        } else if (p.flags & GV_OUT_F32) {
+        } else if (WIS_FL & GV_OUT_F32) {
           *reinterpret_cast<float4*>(reinterpret_cast<float*>(p.y) + o) = s;
         } else {
           const f16x4 h = {(f16)s.x, (f16)s.y, (f16)s.z, (f16)s.w};
@@ -625,7 +656,7 @@ __device__ __forceinline__ void gemv_body(const GemvP& p, const int KC, const in
     // query): per (row, 16-column tile) the pair (sum, M2 about the tile mean), as gemv_frag_kernel's residual epilogue leaves them - the
     // four lanes of a row (kq = 0..3) hold four columns each; whole waves take part in the shuffles.  The consumer merges d / 16 pairs per
     // row instead of re-reading and re-summing the whole rows in every one of its workgroups.
-    if ((p.flags & GV_RESID) && p.stat_out) {
+    if ((WIS_FL & GV_RESID) && p.stat_out) {
       float t1 = ep_ok ? (rsum.x + rsum.y) + (rsum.z + rsum.w) : 0.f;
       t1 += __shfl_xor(t1, 16); t1 += __shfl_xor(t1, 32);
       float t2 = 0.f;
@@ -638,6 +669,7 @@ __device__ __forceinline__ void gemv_body(const GemvP& p, const int KC, const in
   stamp(pf, 6);
   if (tid == 0) tl_end(p.prof);
 #undef WIS_ROW_OF
+#undef WIS_FL
 }
 // Kernel arguments: what the kernel needs BEFORE its first vector load (activation / weight base addresses, the shape) leads the
 // argument list as plain scalars, the rest follows as the struct.  With -amdgpu-kernarg-preload-count (build.py) the command
@@ -939,7 +971,7 @@ static void launch_out_cq(hipStream_t st, dim3 grid, dim3 block, size_t lds, int
   else hipLaunchKernelGGL((gemv_out_cq_kernel<3, 16>), grid, block, lds, st, nA, a.M, a.x, a.Wp, b.x, b.x2, b.Wp, b.xsplit, a, b);
 }
 int launch_gemv(hipStream_t st, const GemvP& p) {
-  if (p.M < 1 || p.M > 16 || p.K % 128 || (p.N % 4 && p.rows != 5)) { set_error("gemv: M=%d N=%d K=%d unsupported (the LDS-staged form holds one 16-row block; more rows take launch_gemv_frag)", p.M, p.N, p.K); return WIS_E_UNSUPPORTED; }
+  if (p.M < 1 || p.M > 16 || p.K < 128 || p.K % 128 || (p.N % 4 && p.rows != 5)) { set_error("gemv: M=%d N=%d K=%d unsupported (the LDS-staged form holds one 16-row block; more rows take launch_gemv_frag)", p.M, p.N, p.K); return WIS_E_UNSUPPORTED; }
   // largest K-chunk (multiple of 128 dividing K) whose f16 image of M rows fits 64 KiB of LDS (several workgroups per CU)
   int KC = p.K;
   const size_t aux = (size_t)4 * 64 * 16 + MAX_ROWS * 8 + 4 * 16 * 4 + 16;   // red + stats + sred (+ alignment)

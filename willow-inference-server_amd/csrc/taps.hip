@@ -11,6 +11,21 @@
 
 using namespace wis;
 
+// wis_op_wave_sums: one wave, wave_sum per value and wave_sums<N> on the same registers (the only kernel this object has: the helper is inlined
+// into gemv_body and has no launch of its own)
+template <int N>
+__global__ __launch_bounds__(64) void wave_sums_tap_kernel(const float* __restrict__ x, float* __restrict__ out_old, float* __restrict__ out_new) {
+  const int lane = threadIdx.x;
+  float v[N], w[N];
+#pragma unroll
+  for (int i = 0; i < N; ++i) v[i] = x[i * 64 + lane];
+#pragma unroll
+  for (int i = 0; i < N; ++i) w[i] = wave_sum(v[i]);
+  wave_sums(v);
+#pragma unroll
+  for (int i = 0; i < N; ++i) { out_old[i * 64 + lane] = w[i]; out_new[i * 64 + lane] = v[i]; }
+}
+
 extern "C" {
 
 int wis_debug_encode(wis_model_t* m, const float* input, int input_kind, int B, float* enc_out) {
@@ -517,6 +532,15 @@ int wis_op_gemv_qkv(int device, const float* x, const float* gamma, const float*
   }
   g.q = q; g.kc = reinterpret_cast<f16*>(kc); g.vc = reinterpret_cast<f16*>(vc); g.slot = slot; g.pos = pos; g.d = d; g.ctx = ctx;
   return t.finish(M <= 8 ? launch_gemv(st, g) : launch_gemv_frag(st, g));
+}
+
+int wis_op_wave_sums(int device, const float* x, int N, float* out_old, float* out_new) {
+  Tap t(device, "wis_op_wave_sums"); WIS_RET(t.rc);
+  if (!x || !out_old || !out_new || (N != 6 && N != 10 && N != 16)) { set_error("wis_op_wave_sums: N=%d (6, 10 or 16 values per lane)", N); return WIS_E_ARG; }
+  if (N == 6) hipLaunchKernelGGL((wave_sums_tap_kernel<6>), dim3(1), dim3(64), 0, t.st, x, out_old, out_new);
+  else if (N == 10) hipLaunchKernelGGL((wave_sums_tap_kernel<10>), dim3(1), dim3(64), 0, t.st, x, out_old, out_new);
+  else hipLaunchKernelGGL((wave_sums_tap_kernel<16>), dim3(1), dim3(64), 0, t.st, x, out_old, out_new);
+  return t.finish(WIS_OK);
 }
 
 int wis_op_gemv_out_cq(int device, const void* a, const float* x0, const void* Wo, const float* bo, const void* Wq, const float* bq, const float* gamma, const float* beta,

@@ -152,6 +152,7 @@ SYMBOLS = [
     ("wis_op_dec_self_attn_ex", _i, [_i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _i, _i, _vp]),
     ("wis_op_gemv_qkv", _i, [_i] + [_vp] * 10 + [_i] * 3),
     ("wis_op_gemv_out_cq", _i, [_i] + [_vp] * 14 + [_i] * 3),
+    ("wis_op_wave_sums", _i, [_i, _vp, _i, _vp, _vp]),
     ("wis_op_gemv_frag_stage", _i, [_i, _i, _vp, _i, _i] + [_vp] * 5 + [_i] + [_vp] * 3 + [_i] * 4),
     ("wis_op_dec_embed", _i, [_i, _vp, _vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32), _vp, _vp, _vp, _vp, _i, _i, _i, _i]),
     ("wis_op_mel_to_image", _i, [_i, _vp, _vp, _i, _i]),
