@@ -263,6 +263,26 @@ typedef struct {
   float   sampling_temperature;   /* T; 0 means 1 */
   int32_t num_hypotheses;         /* n; 0 means 1.  Beam search (no sampling): the n best finished hypotheses by normalised score, best first, the first
                                      registered among equal scores; CTranslate2's early exit then needs n finished hypotheses */
+  /* Phrase-constrained decoding.  Appended field: 0 is what a caller that never knew it passes, and means today's search.
+   * THE PHRASE RULE.  The handle holds a PHRASE SET (wis_model_set_phrases): token sequences of 1 .. 32 ids, every id a text token (< eot) outside the
+   * model's suppress_ids, no first id in suppress_ids_begin - so no allowed token is masked by the suppress lists and no row ends up all -inf.  The
+   * set is a trie.  A live row's NODE is found by walking the row's generated history (the repetition rules' history: what this search has generated
+   * for the beam so far, after the last beam step's reordering; no start sequence, no prompt, no <|startofprev|> text) from the root.
+   *   - The history is a path of the trie: every id of [0, n_vocab) except the node's children - and <|endoftext|> when the node ends a phrase - is
+   *     stored as -inf; the kept ids keep their values bit for bit.
+   *   - The history is no path (only a slot whose cumulative score is already -inf can hold one: every finite continuation was masked): the row
+   *     is left as it is.
+   *   - The first step: every beam samples from the one shared prompt row, every history is empty; that row is masked to the root's children.
+   *   - Finished utterances: nothing.  Ids in [n_vocab, n_vocab_pad) and every other row are never written.
+   * Order: the repetition penalty and bans first, then this mask, then everything else of the tail (a mask commutes with the suppress lists; an
+   * n-gram ban CAN take a node's last child - that slot's row is then all -inf and the slot dies, as any such row's does).  A
+   * hypothesis' score is the model's log-probability renormalised over what the set allows at each step; a beam search with num_hypotheses = n
+   * ranks the n best phrases (results whose score is -inf are fillers: the set reached fewer phrases than the search wanted).
+   * max_new_tokens = 0 resolves to min(the usual value, longest phrase + 1) - the bound that ends a search whose set holds fewer phrases than the
+   * beam needs hypotheses; an explicit value below longest phrase + 1: WIS_E_ARG.  With timestamps, fixed_new_tokens > 0, sampling, or through the
+   * drafted entry points: WIS_E_UNSUPPORTED; on with no set installed: WIS_E_STATE; a value other than 0 / 1: WIS_E_ARG.  Nothing is enqueued
+   * by a refused call.  wis_generate, wis_generate_n, wis_generate_ragged, wis_debug_search, wis_debug_search_n. */
+  int32_t phrases;                /* 1: constrain the search by the handle's phrase set.  0: off */
 } wis_gen_opts_t;
 
 /* out_ids: [B][max_new] (max_new = resolved max_new_tokens), out_len: [B], out_score: [B]
@@ -372,6 +392,20 @@ int wis_debug_logits(wis_model_t* m, const float* input, int input_kind, int B,
  * concurrent requests) instead of the <= 8-row route; B*R <= 96 (MAX_ROWS) */
 int wis_debug_logits_rows(wis_model_t* m, const float* input, int input_kind, int B,
                           const int32_t* dec_in, int T, int R, float* logits);
+/* ---- phrase-constrained decoding (wis_gen_opts_t::phrases states the rule) ------------------------------------------------------
+ * Installs a phrase set on a handle, as a flat trie of n_records 16-byte records, one per EDGE:
+ *   trie[4 i + 0] token of the edge            trie[4 i + 1] index of the first record of the child's own children (0: it has none)
+ *   trie[4 i + 2] number of those children     trie[4 i + 3] 1: the child ends a phrase, else 0
+ * Record 0 is the root's pseudo-edge {-1, 1, children of the root, 0}.  The children of one node are contiguous, in strictly ascending token
+ * order, and the blocks lie in TREE ORDER: walking the records by index, every node's children start where the previous node's ended
+ * (breadth-first), and the last block ends at n_records.  Every leaf ends a phrase.  A walk costs one dependent 16-byte load round per
+ * history token.  The whole table is validated on the host before anything reaches the device - ranges, tree order, sorted children, the
+ * token rules of the phrase rule, leaves - and anything malformed is WIS_E_ARG with the set that was installed before left in place.
+ * Limits: 65535 records, 4096 children per node, 32 tokens per phrase; beyond them WIS_E_UNSUPPORTED.  n_records = 0 removes the set.
+ * The device buffer has a fixed capacity and never moves: installing another set is a copy, captured decode steps stay valid (the resolved
+ * max_new_tokens is part of a captured step's key, as ever: sets whose longest phrases are equally long share their steps).  A clone
+ * (wis_model_clone) has a buffer of its own and starts without a set.  Not part of wis_config_t. */
+int wis_model_set_phrases(wis_model_t* m, const int32_t* trie, int n_records);
 /* ---- word-level timestamps: cross-attention alignment + dynamic time warping (csrc/align.hip) --------------------------------
  * The alignment heads of a handle: n (layer, head) pairs; n == 0 restores openai-whisper's default, every head of the upper half
  * of the decoder layers (layer >= n_dec_layers / 2).  Clones made afterwards inherit them.  Not part of wis_config_t. */
@@ -675,6 +709,13 @@ int wis_op_lang_probs(int device, const float* logits, int ld, const int32_t* la
  * its log-probability.  rowmap i32 [beam] or NULL.  Scratch is the tap's own. */
 int wis_op_greedy_rows(int device, const float* logits, int n_vocab, int n_vocab_pad, int eot, const float* bias_all, const float* bias_begin,
                        const int32_t* step_u, int B, int beam, int lr_b, int lr_j, int lr_off, const int32_t* rowmap, int32_t* tok_out, float* lp_out);
+/* the phrase mask of one step (phrase_rules_kernel), in place, all pointers device memory: logits f32 rows of stride n_vocab_pad - row (b, j) is
+ * b lr_b + j lr_j + lr_off, lr_j = 0: the utterance's beams share one row and its first workgroup masks it -, trie i32 [n_rec][4] (the layout of
+ * wis_model_set_phrases; NOT validated here: the kernel itself refuses every child range and token outside the table / the vocabulary, such a
+ * row stays as it is), alive i32 [B x beam][max_new] histories of which the first min(step_u[b], max_new) entries count, step_u / done i32 [B].
+ * 1 <= n_rec <= 65535, 0 <= eot < n_vocab <= n_vocab_pad, 1 <= max_new <= 256, beam <= 8, B x beam <= 96: anything else WIS_E_ARG. */
+int wis_op_phrase_rules(int device, float* logits, int n_vocab, int n_vocab_pad, int eot, const int32_t* trie, int n_rec, const int32_t* alive,
+                        const int32_t* step_u, const int32_t* done, int B, int beam, int max_new, int lr_b, int lr_j, int lr_off);
 
 /* ---- speaker verification (replaces the reference's WavLMForXVector embedder, main.py:306-316 / do_sv 797-879): one handle = the
  * WavLM-base-plus-sv x-vector model on one GPU.  Input: mono 16 kHz f32 PCM in host memory, already through the reference's

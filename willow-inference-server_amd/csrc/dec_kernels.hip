@@ -3708,4 +3708,80 @@ int launch_lang_probs(hipStream_t st, const float* logits, int ld, const int* la
   return WIS_OK;
 }
 
+// =======================================================================================
+// Phrase-constrained decoding (include/wis_hip.h states the rule), the pre-pass behind rep_rules_kernel when wis_gen_opts_t::phrases is on.
+// (The last kernel of the file: every other kernel of the code object lies where it lay before this one existed.)
+// grid B*beam (one workgroup per live row), block 256.  WALK: the row's generated history bs.alive[m][0 .. min(step_u[b], max_new)) is followed
+// from the root of the flat trie (one int4 record per edge: {token, first child record, children, child ends a phrase}; record 0 = the root's
+// pseudo-edge; a node's children are contiguous and ascending by token) - per history token the workgroup scans the node's children 256 per
+// round, the thread that finds the token publishes the child's record in LDS (two slots, alternating: two barriers per token).  A history that
+// leaves the trie (or is longer than PHRASE_MAX_DEPTH) leaves the row as it is.  MASK: every thread reads its share of the node's children's
+// values (and <|endoftext|>'s when the node ends a phrase) into LDS, barrier, ids [0, n_vocab) are filled with -inf (float4 stores between a
+// scalar head and tail: the row's alignment is whatever ld makes it), barrier, the kept values go back bit for bit.  Ids >= n_vocab are never
+// written.  Rows that share ONE logits row (lr_j == 0: the pass that carries the prompt, every history empty) are masked by the utterance's
+// first workgroup alone.  The host validates a set before it reaches the device (model.hip wis_model_set_phrases); the kernel checks every
+// child range and token against n_rec / n_vocab again, so no table - a tap caller's included - can make it address outside its buffers.
+__global__ __launch_bounds__(256) void phrase_rules_kernel(float* __restrict__ logits, const int* __restrict__ step_u, const int* __restrict__ done,
+                                                           const int* __restrict__ alive, const int4* __restrict__ trie, int n_rec, SampleCfg cfg,
+                                                           int lr_b, int lr_j, int lr_off) {
+  __shared__ int4 s_rec[2];
+  __shared__ int s_tok[PHRASE_MAX_CHILDREN];
+  __shared__ float s_val[PHRASE_MAX_CHILDREN];
+  __shared__ float s_eot;
+  const int tid = threadIdx.x, m = blockIdx.x, b = m / cfg.beam, jb = m - b * cfg.beam;
+  if (done[b] || n_rec < 1) return;
+  if (lr_j == 0 && jb != 0) return;
+  int L = step_u[b];
+  L = L < cfg.max_new ? L : cfg.max_new;
+  if (L < 0 || L > PHRASE_MAX_DEPTH) return;
+  const int V = cfg.n_vocab;
+  int4 node = trie[0];
+  for (int i = 0; i < L; ++i) {
+    const int first = node.y, n = node.z;
+    if (first < 1 || n < 1 || n > PHRASE_MAX_CHILDREN || first > n_rec - n) return;      // a leaf, or no record range of this table
+    const int tk = alive[(size_t)m * cfg.max_new + i];
+    if (tid == 0) s_rec[i & 1] = make_int4(-1, 0, 0, 0);
+    __syncthreads();
+    for (int c = tid; c < n; c += 256) {
+      const int4 r = trie[first + c];
+      if (r.x == tk && tk >= 0) s_rec[i & 1] = r;      // (ascending tokens: at most one child matches)
+    }
+    __syncthreads();
+    node = s_rec[i & 1];
+    if (node.x < 0) return;      // the history is no path of the trie: the row stays as it is
+  }
+  const int first = node.y, n = node.z, ends = node.w;
+  const bool kids = n >= 1;
+  if (kids && (first < 1 || n > PHRASE_MAX_CHILDREN || first > n_rec - n)) return;
+  if (!kids && !ends) return;      // (a validated set has no such node)
+  float* row = logits + (size_t)(b * lr_b + jb * lr_j + lr_off) * cfg.n_vocab_pad;
+  if (kids)
+    for (int c = tid; c < n; c += 256) {
+      int t = trie[first + c].x;
+      t = (t >= 0 && t < V) ? t : -1;
+      s_tok[c] = t;
+      s_val[c] = t >= 0 ? row[t] : 0.f;
+    }
+  const bool keep_eot = ends != 0 && cfg.eot >= 0 && cfg.eot < V;
+  if (keep_eot && tid == 0) s_eot = row[cfg.eot];
+  __syncthreads();      // every kept value is read - it lies in LDS - before the fill
+  int head = (int)((4u - (unsigned)((reinterpret_cast<uintptr_t>(row) >> 2) & 3u)) & 3u);
+  head = head < V ? head : V;
+  const int n4 = (V - head) >> 2, tail0 = head + 4 * n4;
+  if (tid < head) row[tid] = -INFINITY;
+  float4* row4 = reinterpret_cast<float4*>(row + head);
+  const float4 ninf4 = make_float4(-INFINITY, -INFINITY, -INFINITY, -INFINITY);
+  for (int i = tid; i < n4; i += 256) row4[i] = ninf4;
+  if (tid < V - tail0) row[tail0 + tid] = -INFINITY;
+  __syncthreads();      // the fill is ahead of the values that go back (workgroup-scope release / acquire, as in rep_rules_kernel)
+  if (kids)
+    for (int c = tid; c < n; c += 256) { const int t = s_tok[c]; if (t >= 0) row[t] = s_val[c]; }
+  if (keep_eot && tid == 0) row[cfg.eot] = s_eot;
+}
+int launch_phrase_rules(hipStream_t st, float* logits, const BeamState& bs, int B, const SampleCfg& cfg, const int4* trie, int n_rec, int lr_b, int lr_j, int lr_off) {
+  if (!trie || n_rec < 1 || n_rec > PHRASE_MAX_RECORDS || cfg.max_new < 1 || cfg.n_vocab < 1 || cfg.n_vocab_pad < cfg.n_vocab) { set_error("phrase_rules: config out of range"); return WIS_E_UNSUPPORTED; }
+  hipLaunchKernelGGL(phrase_rules_kernel, dim3(B * cfg.beam), dim3(256), 0, st, logits, bs.step_u, bs.done, bs.alive, trie, n_rec, cfg, lr_b, lr_j, lr_off);
+  return WIS_OK;
+}
+
 }  // namespace wis

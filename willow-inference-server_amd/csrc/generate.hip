@@ -34,6 +34,7 @@ struct SampleCtx {
   bool ts; int ts_max_init;      // Whisper's timestamp rules (prompts without <|notimestamps|>): a pre-pass ahead of the sampling statistics of every step
   float rep_pen = 1.f; int rep_ngram = 0;      // repetition_penalty / no_repeat_ngram_size (1 / 0: off): a pre-pass that patches the logits rows, ahead of everything else
   bool rep() const { return rep_pen != 1.f || rep_ngram != 0; }
+  bool phrases = false;          // wis_gen_opts_t::phrases: the handle's phrase set masks every live row behind the repetition rules (phrase_rules_kernel)
   SampleP sp;                    // random sampling (topk 0: off): sample_step_kernel stands in beam_step_kernel's place, `beam` counts the utterance's samples
   int n_res = 1;                 // results per utterance (num_hypotheses)
   bool sampling() const { return sp.topk != 0; }
@@ -73,6 +74,24 @@ static int resolve_rep_opts(const wis_gen_opts_t* o, SampleCtx* g) {
   if (!std::isfinite(p) || p < 0.f) { set_error("repetition_penalty %g: a finite value > 0 (1 or 0: off)", (double)p); return WIS_E_ARG; }
   if (n < 0) { set_error("no_repeat_ngram_size %d: >= 0 (0: off)", n); return WIS_E_ARG; }
   g->rep_pen = p == 0.f ? 1.f : p; g->rep_ngram = n;
+  return WIS_OK;
+}
+// wis_gen_opts_t::phrases of a call, resolved - or refused; *max_new: the call's usual value in, what the constrained search takes out
+// (max_new_tokens = 0: at most the longest phrase + 1, the step that can only take <|endoftext|>; an explicit value below that is refused)
+static int resolve_phrase_opts(const wis_model* m, const wis_gen_opts_t* o, bool drafted, SampleCtx* g, int* max_new) {
+  g->phrases = false;
+  if (o->phrases == 0) return WIS_OK;
+  if (o->phrases != 1) { set_error("phrases %d: 0 (off) or 1 (the handle's phrase set)", o->phrases); return WIS_E_ARG; }
+  if (drafted) { set_error("phrases: not available for drafted decodes (wis_generate_draft / wis_generate_draft_beam)"); return WIS_E_UNSUPPORTED; }
+  if (o->timestamps) { set_error("phrases: not available with timestamps (a phrase holds text tokens only)"); return WIS_E_UNSUPPORTED; }
+  if (o->fixed_new_tokens > 0) { set_error("phrases: not available with fixed_new_tokens (a phrase ends where the set says)"); return WIS_E_UNSUPPORTED; }
+  if (g->sampling()) { set_error("phrases: not available for sampled decodes (sampling_topk 0 or 1)"); return WIS_E_UNSUPPORTED; }
+  if (m->phr_n < 1) { set_error("phrases: the handle has no phrase set (wis_model_set_phrases)"); return WIS_E_STATE; }
+  const int need = m->phr_depth + 1;
+  if (o->max_new_tokens > 0 && o->max_new_tokens < need) { set_error("max_new_tokens %d: the phrase set's longest phrase needs %d (its %d tokens and <|endoftext|>)", o->max_new_tokens, need, m->phr_depth); return WIS_E_ARG; }
+  if (*max_new < need) { set_error("phrases: the longest phrase (%d tokens) does not fit the %d steps this call can take", m->phr_depth, *max_new); return WIS_E_ARG; }
+  if (o->max_new_tokens == 0 && *max_new > need) *max_new = need;
+  g->phrases = true;
   return WIS_OK;
 }
 // everything a stage needs to know about the call: built once (make_gen_ctx), read-only afterwards
@@ -130,6 +149,7 @@ static int make_gen_ctx(wis_model* m, const float* input, int B, const int32_t* 
   int max_new = o->max_new_tokens > 0 ? o->max_new_tokens : std::min(c.n_text_ctx / 2, c.n_text_ctx - P);
   if (max_new > MAX_STEPS) max_new = MAX_STEPS;
   if (P - 1 + max_new > c.n_text_ctx) max_new = c.n_text_ctx - (P - 1);
+  WIS_RET(resolve_phrase_opts(m, o, draft != nullptr, &g, &max_new));
   g.max_new = max_new;
   for (int i = 0; i < n_prompt; ++i) if (prompt[i] < 0 || prompt[i] >= c.n_vocab) { set_error("prompt token %d out of range", prompt[i]); return WIS_E_ARG; }
   WIS_RET(resolve_rep_opts(o, &g));
@@ -218,7 +238,7 @@ static int front_half(const GenCtx& g) {
   return WIS_OK;
 }
 
-// The sampling tail of a decoder pass: [repetition rules ->] [timestamp rules ->] candidate statistics -> beam step -> cache reorder.  The logits row of (b, j) is
+// The sampling tail of a decoder pass: [repetition rules ->] [phrase mask ->] [timestamp rules ->] candidate statistics -> beam step -> cache reorder.  The logits row of (b, j) is
 // b*rows.b + j*rows.j + rows.off: a step samples beam j from row b*beam + j {beam, 1, 0}, the pass that carries the prompt samples every beam from the
 // last prompt row {P, 0, P - 1}.  TAIL_TAPS: the tap build's stamp rows of the two sampling kernels (the product build carries none).
 // TAIL_NO_CACHE: a search over given logits has no cache to reorder (wis_debug_search).
@@ -229,6 +249,7 @@ static int sampling_tail(const SampleCtx& g, LogitRows rows, int flags) {
   const int lr_b = rows.b, lr_j = rows.j, lr_off = rows.off;
   unsigned long long* prof = (WIS_TAPS && (flags & TAIL_TAPS)) ? m->d_prof + (size_t)c.n_dec_layers * 8 * 16 : nullptr;
   if (g.rep()) WIS_RET(launch_rep_rules(st, m->logits, m->bs, g.B, g.sc, g.rep_pen, g.rep_ngram, lr_b, lr_j, lr_off));
+  if (g.phrases) WIS_RET(launch_phrase_rules(st, m->logits, m->bs, g.B, g.sc, m->d_trie, m->phr_n, lr_b, lr_j, lr_off));
   if (g.ts) WIS_RET(launch_ts_rules(st, m->logits, g.bias_all, m->bias_begin, m->bs, g.B, g.sc, c.no_timestamps, g.ts_max_init, lr_b, lr_j, lr_off, m->ts_desc));
   if (g.sampling()) {      // statistics (whole vocabulary: perturbed) -> sample step; every row continues itself: the cache moves only behind the prompt pass
     WIS_RET(launch_logit_stats(st, m->logits, g.bias_all, m->bias_begin, m->bs.step_u, m->st_max, m->st_sum, m->st_val, m->st_idx, g.B, g.sc, lr_b, lr_j, lr_off, nullptr,
@@ -611,6 +632,7 @@ struct StepGraph {
     key.timestamps = g.ts ? 1 : 0; key.max_init = g.ts ? g.ts_max_init : 0;
     key.rep_pen = g.rep_pen == 1.f ? 0.f : g.rep_pen; key.rep_ngram = g.rep_ngram;      // (off: the zeroes of a key that never knew the fields)
     key.samp_topk = g.sp.topk; key.samp_T = g.sampling() ? g.sp.T : 0.f; key.n_hyp = g.n_res > 1 ? g.n_res : 0;      // (the seeds are device memory: no part of the key)
+    key.phrases = g.phrases ? 1 : 0;      // (the set is device memory behind a pointer that never changes: installing another needs no new graph)
     auto it = m->graphs.find(key);
     if (it != m->graphs.end()) { *out = it->second; return WIS_OK; }
     hipGraph_t graph = nullptr; hipGraphExec_t ge = nullptr;
@@ -868,7 +890,8 @@ static int debug_search_impl(const char* who, wis_model_t* m, const float* logit
   WIS_RET(resolve_sample_opts(o, single, false, &g, &beam));
   WIS_RET(check_batch(m, B, beam));
   if (!g.sampling()) WIS_RET(check_patience(beam, o->patience));
-  const int max_new = o->max_new_tokens > 0 ? std::min(o->max_new_tokens, MAX_STEPS) : n_steps;
+  int max_new = o->max_new_tokens > 0 ? std::min(o->max_new_tokens, MAX_STEPS) : n_steps;
+  WIS_RET(resolve_phrase_opts(m, o, false, &g, &max_new));
   if (max_new > n_steps) { set_error("%s: %d steps of logits for max_new_tokens %d", who, n_steps, max_new); return WIS_E_ARG; }
   hipStream_t st = m->st;
   const int Mrows = B * beam, V = c.n_vocab;
@@ -939,6 +962,7 @@ int wis_generate_draft(wis_model_t* m, const float* input, const int32_t* prompt
                        const int32_t* draft, int n_draft, int32_t* out_ids, int32_t* out_len, float* out_score, int32_t* accepted) {
   if (!m || !input || !prompt || !o || !out_ids || !out_len || (n_draft > 0 && !draft) || n_draft < 0) { set_error("wis_generate_draft: bad argument"); return WIS_E_ARG; }
   if (o->timestamps) { set_error("wis_generate_draft: timestamps are not available for drafted decodes"); return WIS_E_UNSUPPORTED; }
+  if (o->phrases) { set_error("wis_generate_draft: phrases are not available for drafted decodes"); return WIS_E_UNSUPPORTED; }
   if ((o->repetition_penalty != 0.f && o->repetition_penalty != 1.f) || o->no_repeat_ngram_size != 0) { set_error("wis_generate_draft: repetition_penalty / no_repeat_ngram_size are not available for drafted decodes"); return WIS_E_UNSUPPORTED; }
   if ((o->sampling_topk != 0 && o->sampling_topk != 1) || (o->sampling_temperature != 0.f && o->sampling_temperature != 1.f) || (o->num_hypotheses != 0 && o->num_hypotheses != 1)) { set_error("wis_generate_draft: sampling_topk / sampling_temperature / num_hypotheses are not available for drafted decodes"); return WIS_E_UNSUPPORTED; }
   WIS_ENTER(m, "wis_generate_draft")
@@ -952,6 +976,7 @@ int wis_generate_draft_beam(wis_model_t* m, const float* input, const int32_t* p
                             const int32_t* draft_tok, const int32_t* draft_org, int n_steps, int32_t* out_ids, int32_t* out_len, float* out_score, int32_t* accepted_steps) {
   if (!m || !input || !prompt || !o || !out_ids || !out_len || n_steps < 0 || (n_steps > 0 && (!draft_tok || !draft_org))) { set_error("wis_generate_draft_beam: bad argument"); return WIS_E_ARG; }
   if (o->timestamps) { set_error("wis_generate_draft_beam: timestamps are not available for drafted decodes"); return WIS_E_UNSUPPORTED; }
+  if (o->phrases) { set_error("wis_generate_draft_beam: phrases are not available for drafted decodes"); return WIS_E_UNSUPPORTED; }
   if ((o->repetition_penalty != 0.f && o->repetition_penalty != 1.f) || o->no_repeat_ngram_size != 0) { set_error("wis_generate_draft_beam: repetition_penalty / no_repeat_ngram_size are not available for drafted decodes"); return WIS_E_UNSUPPORTED; }
   if ((o->sampling_topk != 0 && o->sampling_topk != 1) || (o->sampling_temperature != 0.f && o->sampling_temperature != 1.f) || (o->num_hypotheses != 0 && o->num_hypotheses != 1)) { set_error("wis_generate_draft_beam: sampling_topk / sampling_temperature / num_hypotheses are not available for drafted decodes"); return WIS_E_UNSUPPORTED; }
   WIS_ENTER(m, "wis_generate_draft_beam")

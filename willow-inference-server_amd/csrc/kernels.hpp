@@ -204,6 +204,12 @@ int launch_ts_rules(hipStream_t st, const float* logits, const float* bias_all, 
 // every other kernel of the tail; rows as launch_logit_stats reads them.  penalty 1 / ngram 0: that rule is off (the caller launches
 // nothing when both are)
 int launch_rep_rules(hipStream_t st, float* logits, const BeamState& bs, int B, const SampleCfg& cfg, float penalty, int ngram, int lr_b, int lr_j, int lr_off);
+// phrase-constrained decoding (dec_kernels.hip phrase_rules_kernel): per live row whose generated history is a path of the flat trie, every id
+// of [0, n_vocab) but the node's children (and <|endoftext|> at a phrase end) is stored as -inf in the row of `logits` the step samples from;
+// behind launch_rep_rules, ahead of everything else of the tail; rows as launch_logit_stats reads them.  trie: device, n_rec int4 records
+// {token, first child record, children, child ends a phrase}, record 0 the root's pseudo-edge (include/wis_hip.h has the layout's rules)
+constexpr int PHRASE_MAX_RECORDS = 65535, PHRASE_MAX_CHILDREN = 4096, PHRASE_MAX_DEPTH = 32;
+int launch_phrase_rules(hipStream_t st, float* logits, const BeamState& bs, int B, const SampleCfg& cfg, const int4* trie, int n_rec, int lr_b, int lr_j, int lr_off);
 // probability of <|nospeech|> under the full-vocabulary softmax of each utterance's <|startoftranscript|> row (b * rs + r0)
 int launch_no_speech(hipStream_t st, const float* logits, int ld, int B, int rs, int r0, int V, int ns, float* out);
 // ... with the row of every utterance in device memory (rows [B]; a value outside [0, rs): utterance b is not in this pass, out[b] stays as it is)

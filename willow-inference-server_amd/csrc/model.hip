@@ -548,6 +548,7 @@ static int alloc_buffers(wis_model* m) {
   WIS_RET(dalloc(m, &m->lm_gmax, Bm));
   WIS_RET(dalloc(m, &m->d_probs, (size_t)Bm * (c.n_lang > 0 ? c.n_lang : 1)));
   WIS_RET(dalloc(m, &m->d_prof, ((size_t)c.n_dec_layers * 8 + 2) * 16));   // + sampling kernels (tap builds)
+  WIS_RET(dalloc(m, &m->d_trie, (size_t)PHRASE_MAX_RECORDS));      // (the last buffer carved: every other one lies where it lay before the phrase set existed)
   WIS_HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&m->h_pin), sizeof(PinnedScratch), hipHostMallocDefault));
   // fine-grained (coherent) host memory mapped into the device: beam_step_kernel's system-scope stores land here while the
   // stream is still running
@@ -1096,6 +1097,9 @@ int wis_model_create(const wis_config_t* cfg, const void* arena, size_t arena_by
       if ((rc = dalloc(m, &m->d_lang_ids, (size_t)(cfg->n_lang > 0 ? cfg->n_lang : 1)))) break;
       if (cfg->n_lang > 0) hipMemcpy(m->d_lang_ids, cfg->lang_ids, (size_t)cfg->n_lang * 4, hipMemcpyHostToDevice);
     }
+    m->tok_flags.assign((size_t)cfg->n_vocab, 0);      // (what wis_model_set_phrases validates a set against)
+    for (int i = 0; i < cfg->n_suppress; ++i) if (cfg->suppress_ids[i] >= 0 && cfg->suppress_ids[i] < cfg->n_vocab) m->tok_flags[cfg->suppress_ids[i]] |= 1;
+    for (int i = 0; i < cfg->n_suppress_begin; ++i) if (cfg->suppress_ids_begin[i] >= 0 && cfg->suppress_ids_begin[i] < cfg->n_vocab) m->tok_flags[cfg->suppress_ids_begin[i]] |= 2;
     m->cfg.suppress_ids = nullptr; m->cfg.suppress_ids_begin = nullptr; m->cfg.lang_ids = nullptr;   // caller-owned memory is not retained
     // everything carved so far is the (read-only) weight set: it moves into a shareable block; the buffers start on fresh slabs
     m->wslabs = std::make_shared<WeightSlabs>();
@@ -1145,6 +1149,7 @@ int wis_model_clone(wis_model_t* parent, wis_model_t** out) {
   m->w8 = parent->w8; m->cq_fold = parent->cq_fold;
   m->use_graph = parent->use_graph;
   m->al.heads = parent->al.heads;      // (the clone allocates its own align scratch on its first wis_align)
+  m->tok_flags = parent->tok_flags;      // (a clone has a phrase buffer of its own and starts without a set)
   memset(&m->timing, 0, sizeof(m->timing));
   int rc = WIS_OK;
   do {
@@ -1184,6 +1189,55 @@ int wis_last_trajectory(wis_model_t* m, int b, int32_t* tok, int32_t* org, int c
   if (n) WIS_HIP_CHECK(hipMemcpy(raw.data(), m->bs.traj + (size_t)b * MAX_STEPS * MAX_R * 2, raw.size() * 4, hipMemcpyDeviceToHost));
   for (int s = 0; s < n; ++s) for (int j = 0; j < k; ++j) { tok[s * k + j] = raw[((size_t)s * MAX_R + j) * 2]; org[s * k + j] = raw[((size_t)s * MAX_R + j) * 2 + 1]; }
   *n_steps = n;
+  return WIS_OK;
+}
+
+// Installs a phrase set (include/wis_hip.h has the layout and its rules).  EVERYTHING is checked here, on the host, before a byte reaches the
+// device: the records are walked in index order with one running cursor - a node's children must start exactly where the previous node's
+// ended - so every record but the root is the child of exactly one earlier record, no range leaves the table and no walk can cycle.
+int wis_model_set_phrases(wis_model_t* m, const int32_t* trie, int n_records) {
+  if (!m || n_records < 0 || (n_records > 0 && !trie)) { set_error("wis_model_set_phrases: bad argument"); return WIS_E_ARG; }
+  WIS_ENTER(m, "wis_model_set_phrases")
+  if (n_records == 0) { m->phr_n = 0; m->phr_depth = 0; return WIS_OK; }
+  if (n_records > PHRASE_MAX_RECORDS) { set_error("wis_model_set_phrases: %d records (at most %d)", n_records, PHRASE_MAX_RECORDS); return WIS_E_UNSUPPORTED; }
+  const wis_config_t& c = m->cfg;
+  const int n = n_records;
+  auto bad = [](const char* what, int i) { set_error("wis_model_set_phrases: record %d: %s", i, what); return WIS_E_ARG; };
+  std::vector<int> depth((size_t)n, 0);
+  int cursor = 1, deepest = 0;
+  for (int i = 0; i < n; ++i) {
+    const int32_t tok = trie[4 * i], first = trie[4 * i + 1], nc = trie[4 * i + 2], ends = trie[4 * i + 3];
+    if (i >= cursor) return bad("not the child of an earlier record (tree order)", i);
+    if (ends != 0 && ends != 1) return bad("the phrase-end flag is 0 or 1", i);
+    if (i == 0) {
+      if (tok != -1 || ends != 0 || nc < 1) return bad("the root's pseudo-edge is {-1, 1, children >= 1, 0}", i);
+    } else {
+      if (tok < 0 || tok >= c.eot || tok >= c.n_vocab) return bad("the token is no text token (0 <= id < <|endoftext|>)", i);
+      if (m->tok_flags[tok] & 1) return bad("the token is in the model's suppress_ids", i);
+      if (depth[i] == 1 && (m->tok_flags[tok] & 2)) return bad("a phrase's first token is in the model's suppress_ids_begin", i);
+    }
+    if (nc < 0) return bad("a negative number of children", i);
+    if (nc > PHRASE_MAX_CHILDREN) { set_error("wis_model_set_phrases: record %d: %d children (at most %d per node)", i, nc, PHRASE_MAX_CHILDREN); return WIS_E_UNSUPPORTED; }
+    if (nc == 0) {
+      if (first != 0) return bad("a leaf's first-child index is 0", i);
+      if (!ends) return bad("a leaf that ends no phrase", i);
+      continue;
+    }
+    if (first != cursor || nc > n - cursor) return bad("the children do not follow the previous node's (tree order), or leave the table", i);
+    if (depth[i] + 1 > PHRASE_MAX_DEPTH) { set_error("wis_model_set_phrases: record %d: a phrase of more than %d tokens", i, PHRASE_MAX_DEPTH); return WIS_E_UNSUPPORTED; }
+    for (int k = 0; k < nc; ++k) {
+      depth[cursor + k] = depth[i] + 1;
+      if (k > 0 && trie[4 * (cursor + k)] <= trie[4 * (cursor + k - 1)]) return bad("children not in strictly ascending token order", cursor + k);
+    }
+    deepest = std::max(deepest, depth[i] + 1);
+    cursor += nc;
+  }
+  if (cursor != n) { set_error("wis_model_set_phrases: %d records, the tree holds %d", n, cursor); return WIS_E_ARG; }
+  WIS_HIP_CHECK(hipSetDevice(m->device));
+  m->phr_n = 0;      // (a failed copy leaves no set behind)
+  WIS_HIP_CHECK(hipMemcpyAsync(m->d_trie, trie, (size_t)n * 16, hipMemcpyHostToDevice, m->st));      // behind whatever step of an earlier call is still queued
+  WIS_HIP_CHECK(hipStreamSynchronize(m->st));
+  m->phr_n = n; m->phr_depth = deepest;
   return WIS_OK;
 }
 

@@ -45,6 +45,7 @@ struct GraphKey {
   int timestamps, max_init;      // the timestamp form of the step (ts_rules_kernel ahead of logit_stats_kernel<true>) and its first-timestamp cap
   float rep_pen; int rep_ngram;  // rep_rules_kernel at the head of the tail (both 0: off, no such launch)
   int samp_topk; float samp_T; int n_hyp;      // sampled decode (sample_step_kernel in beam_step_kernel's place) / results per utterance; all 0: off, one result
+  int phrases;                   // phrase_rules_kernel behind rep_rules_kernel (0: off, no such launch; the set itself is device memory: no part of the key)
   bool operator<(const GraphKey& o) const { return memcmp(this, &o, sizeof(GraphKey)) < 0; }
 };
 
@@ -185,6 +186,11 @@ struct wis_model {
   size_t enc_part_cap = 0;      // (utterance, head, query tile) triples the split-key encoder attention buffers were sized for
   std::atomic_flag busy = ATOMIC_FLAG_INIT;   // one compute call at a time per handle (BusyGuard)
   wis::AlignState al;
+  // phrase-constrained decoding (wis_model_set_phrases): the handle's set as a flat trie in a buffer of FIXED capacity (PHRASE_MAX_RECORDS records,
+  // allocated with the other buffers: the pointer a captured step carries never changes, installing a set is a copy), its record count (0: no set)
+  // and its longest phrase; tok_flags: per token id, bit 0 = in the model's suppress_ids, bit 1 = in suppress_ids_begin (what a set is validated against)
+  int4* d_trie = nullptr; int phr_n = 0, phr_depth = 0;
+  std::vector<unsigned char> tok_flags;
 };
 
 namespace wis {

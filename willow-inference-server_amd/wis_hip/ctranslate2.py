@@ -166,6 +166,7 @@ class _Replica:
         self.lock = threading.Lock()
         self.inflight = 0
         self.stage = None           # device block for batches of device-resident features (lazy)
+        self.phrase_digest = None   # digest of the phrase set installed on the handle (wis_model_set_phrases), None: none yet
 
 
 def special_tokens_for(a, special=None, lang_ids=None):
@@ -328,6 +329,49 @@ class DecodeOptions(NamedTuple):
     num_hypotheses: int = 1
 
 
+class ConstrainedOptions(DecodeOptions):
+    """The DecodeOptions of a phrase-constrained call (`generate(..., phrases=...)`): the same record - `_fields` and every value a plain call
+    with these arguments would have, max_new_tokens capped at the longest phrase + 1 - that carries the call's phrase set beside it:
+    `phrase_trie` (int32 [n][4], weights.build_phrase_trie) and `phrase_digest` (its SHA-256).  The digest takes part in equality and hash, the
+    type too: two calls share a device batch exactly when their options AND their phrase sets are equal, and a constrained record never equals a
+    plain one.  The batch runner installs the set on the replica when the replica's current digest differs (_generate_chunk)."""
+
+    def __new__(cls, base, trie, digest):
+        self = tuple.__new__(cls, base)
+        self.phrase_trie, self.phrase_digest = trie, digest
+        return self
+
+    def __eq__(self, other):
+        return type(other) is ConstrainedOptions and tuple.__eq__(self, other) and self.phrase_digest == other.phrase_digest
+
+    def __ne__(self, other):
+        return not self == other
+
+    def __hash__(self):
+        return hash((tuple.__hash__(self), self.phrase_digest))
+
+    def _replace(self, **kw):
+        return ConstrainedOptions(DecodeOptions(*self)._replace(**kw), self.phrase_trie, self.phrase_digest)
+
+    def __reduce__(self):
+        return (ConstrainedOptions, (DecodeOptions(*self), self.phrase_trie, self.phrase_digest))
+
+
+def _phrase_set(phrases, special, decode_config):
+    """-> (trie, digest, longest phrase) of a call's `phrases` ([[token ids], ...]), validated against the MODEL's lists (what the engine checks
+    again): a ValueError names the offending phrase."""
+    import hashlib
+    try:
+        phrases = [list(ph) for ph in phrases]
+    except TypeError:
+        raise ValueError(f"phrases {phrases!r}: a list of token id lists") from None
+    sup = decode_config.get("suppress_ids")
+    beg = decode_config.get("suppress_ids_begin")
+    trie = W.build_phrase_trie(phrases, eot=special.eot, suppress_ids=special.default_suppress_ids() if sup is None else sup,
+                               suppress_begin=[220, special.eot] if beg is None else beg)
+    return trie, hashlib.sha256(trie.tobytes()).hexdigest(), max(len(ph) for ph in phrases)
+
+
 RAGGED_PROMPT = -1         # DecodeOptions.prompt_len of the pooled key: prompts of different lengths in one device batch (wis_generate_ragged)
 
 
@@ -348,6 +392,7 @@ def _gen_opts(opts):
     o.repetition_penalty, o.no_repeat_ngram_size = float(opts.repetition_penalty), int(opts.no_repeat_ngram_size)
     if opts.sampling_topk != 0 or opts.num_hypotheses > 1:
         o.sampling_topk, o.sampling_temperature, o.num_hypotheses = int(opts.sampling_topk), float(opts.sampling_temperature), int(opts.num_hypotheses)
+    o.phrases = int(getattr(opts, "phrase_trie", None) is not None)
     return o
 
 
@@ -363,6 +408,11 @@ def _generate_chunk(r, mel, prompts, opts, *rest, device_ptr=None, seeds=None):
     B = int(mel) if device_ptr is not None else mel.shape[0]
     P, beam, n, draft = opts.prompt_len, opts.beam_size, int(opts.num_hypotheses), opts.draft
     o = _gen_opts(opts)
+    trie = getattr(opts, "phrase_trie", None)
+    if trie is not None and r.phrase_digest != opts.phrase_digest:      # (installing a set is a copy: no new step graph)
+        r.phrase_digest = None
+        _lib.check(_lib.load().wis_model_set_phrases(r.handle, trie.ctypes.data_as(C.POINTER(C.c_int32)), len(trie)))
+        r.phrase_digest = opts.phrase_digest
     order = None
     if P == RAGGED_PROMPT:
         if draft is not None or opts.return_trajectory:
@@ -416,7 +466,9 @@ def _generate_chunk(r, mel, prompts, opts, *rest, device_ptr=None, seeds=None):
     nsp = np.zeros(B, np.float32)
     if opts.no_speech_prob:
         _lib.check(lib.wis_last_no_speech_prob(r.handle, B, nsp.ctypes.data_as(C.POINTER(C.c_float))))
-    out = [WhisperGenerationResult([ids[b, j, :lens[b, j]].tolist() for j in range(n)], [float(scores[b, j]) for j in range(n)], float(nsp[b])) for b in range(B)]
+    # (a constrained search whose set reaches fewer than n phrases fills up with -inf hypotheses: those are dropped)
+    keep = [[j for j in range(n) if trie is None or scores[b, j] != -np.inf] for b in range(B)]
+    out = [WhisperGenerationResult([ids[b, j, :lens[b, j]].tolist() for j in keep[b]], [float(scores[b, j]) for j in keep[b]], float(nsp[b])) for b in range(B)]
     if acc is not None:
         out[0].accepted_draft_tokens = int(acc.value)      # tokens (beam 1) or search steps (beam > 1) of the draft the final decode kept
     if opts.return_trajectory:
@@ -855,7 +907,7 @@ class Whisper:
                  repetition_penalty=1, no_repeat_ngram_size=0, max_length=448, return_scores=False, return_no_speech_prob=False,
                  max_initial_timestamp_index=50, suppress_blank=True, suppress_tokens=(-1,), sampling_topk=1,
                  sampling_temperature=1, fixed_new_tokens=0, input_kind=_lib.WIS_IN_MEL_HOST, draft_tokens=None, draft_trajectory=None,
-                 return_trajectory=False, sampling_seed=None, ragged_prompts=False):
+                 return_trajectory=False, sampling_seed=None, ragged_prompts=False, phrases=None):
         """`draft_tokens` (one utterance, beam_size 1): the ids of an earlier hypothesis for this audio - wis_generate_draft verifies them in
         multi-row passes and decodes on behind the accepted prefix; the result is the greedy decode of THESE features either way.
         `draft_trajectory` (one utterance, beam_size > 1): `(tok, org)` as an earlier result's `.trajectory` gives it (`return_trajectory=True`) -
@@ -881,7 +933,12 @@ class Whisper:
         (1 .. 228 tokens each) and still decode in one device batch (wis_generate_ragged) - all with timestamps or none, `max_new_tokens` from the
         longest prompt, no drafts, no `return_trajectory`.  Equal prompts decode exactly as without the keyword.  The setting `batch_ragged_prompts`
         pools every call whose prompts are longer than 16 tokens under one batch key in the same way, so that prompted requests of concurrent callers
-        share device batches."""
+        share device batches.
+        `phrases=[[token ids], ...]` (an extension of this shim): the search is restricted to the caller's phrase list - every result is one of the
+        phrases, scored by the model's log-probabilities renormalised over what the list allows at each step (include/wis_hip.h states the rule);
+        `num_hypotheses=n` in a beam search returns the n best phrases, best first (fewer when the search reached fewer).  A phrase holds 1 .. 32 text
+        tokens outside the model's suppress lists (weights.build_phrase_trie; a ValueError names the phrase).  Not with timestamps, sampling,
+        `fixed_new_tokens` or drafts (ValueError).  Calls share a device batch exactly when their options and their phrase sets are equal."""
         enc = self._encoder_input(features, input_kind)
         if enc is not None:
             n_utt = len(enc[2]) if enc[0] == _lib.WIS_IN_ENC_DEV else enc[1].shape[0]
@@ -892,7 +949,7 @@ class Whisper:
                                          suppress_blank=suppress_blank, suppress_default=list(suppress_tokens) == [-1], sampling_topk=sampling_topk,
                                          sampling_temperature=sampling_temperature, fixed_new_tokens=fixed_new_tokens, draft_tokens=draft_tokens,
                                          draft_trajectory=draft_trajectory, return_trajectory=return_trajectory, ragged_prompts=ragged_prompts,
-                                         pool_long_prompts=getattr(self, "batch_ragged_prompts", False))
+                                         pool_long_prompts=getattr(self, "batch_ragged_prompts", False), phrases=phrases)
         seeds = _seeds(opts, sampling_seed, len(prompts))
         if enc is not None and enc[0] == _lib.WIS_IN_ENC_DEV:
             # every row carries the block its address points into: the rows themselves keep the device memory allocated until _run_batch has returned
@@ -903,12 +960,12 @@ class Whisper:
 
     def _decode_options(self, features, prompts, *, input_kind, n_utt=1, beam_size, patience, num_hypotheses, length_penalty, repetition_penalty, no_repeat_ngram_size,
                         max_length, return_no_speech_prob, max_initial_timestamp_index, suppress_blank, suppress_default, sampling_topk, sampling_temperature,
-                        fixed_new_tokens, draft_tokens, draft_trajectory, return_trajectory, ragged_prompts=False, pool_long_prompts=False):
+                        fixed_new_tokens, draft_tokens, draft_trajectory, return_trajectory, ragged_prompts=False, pool_long_prompts=False, phrases=None):
         """Every check of a decode call, for `generate` (features: host arrays, one prompt each) and `generate_from_device` (features None: ONE
         utterance already on the device) -> (its DecodeOptions, the checked host features or None).  The engine's capacity limits are request
         errors (ValueError -> HTTP 400 in wis_hip.server), not internal ones.  ragged_prompts: the prompts may differ in length (the key then
         carries RAGGED_PROMPT).  pool_long_prompts (the setting batch_ragged_prompts): a call whose prompts are longer than SHORT_PROMPT gets the
-        pooled key whatever their lengths."""
+        pooled key whatever their lengths.  phrases: the call's phrase list -> a ConstrainedOptions; None: the plain record, as it has always been built."""
         drafted = bool(draft_tokens is not None and len(draft_tokens) or draft_trajectory is not None and len(draft_trajectory[0]))
         s_k, s_T, s_n = _check_sampling(beam_size, num_hypotheses, sampling_topk, sampling_temperature, drafted)
         if max(int(beam_size), s_n) > self.max_beam:
@@ -958,6 +1015,19 @@ class Whisper:
         opts = DecodeOptions(RAGGED_PROMPT if pooled else P, int(beam_size), min(max_length // 2, max_length - P), float(length_penalty), float(patience), bool(suppress_blank),
                              bool(suppress_default), int(fixed_new_tokens), int(input_kind), draft, bool(return_trajectory), timestamps,
                              mi if timestamps else 50, bool(return_no_speech_prob), rep_p, rep_n, s_k, s_T, s_n)
+        if phrases is not None:
+            if timestamps:
+                raise ValueError("phrases cannot be combined with timestamps (a start sequence without <|notimestamps|>)")
+            if drafted:
+                raise ValueError("phrases cannot be combined with draft_tokens / draft_trajectory")
+            if s_k != 0:
+                raise ValueError("phrases cannot be combined with sampling (sampling_topk 1)")
+            if int(fixed_new_tokens) > 0:
+                raise ValueError("phrases cannot be combined with fixed_new_tokens")
+            trie, digest, longest = _phrase_set(phrases, self.special, getattr(self, "decode_config", None) or {})
+            if opts.max_new_tokens < longest + 1:
+                raise ValueError(f"max_length {max_length} leaves {opts.max_new_tokens} steps behind a prompt of {P} tokens: the longest phrase needs {longest + 1}")
+            opts = ConstrainedOptions(opts._replace(max_new_tokens=longest + 1), trie, digest)
         return opts, mel
 
     def load(self, device=None):
@@ -985,7 +1055,7 @@ class Whisper:
     def generate_from_device(self, device, mel_device_ptr, prompt, *, beam_size=5, max_length=448, length_penalty=1, patience=1,
                              suppress_blank=True, fixed_new_tokens=0, replica=None, draft_tokens=None, draft_trajectory=None, return_trajectory=False,
                              repetition_penalty=1, no_repeat_ngram_size=0, num_hypotheses=1, sampling_topk=1, sampling_temperature=1, sampling_seed=None,
-                             return_scores=False, return_no_speech_prob=False, max_initial_timestamp_index=50):
+                             return_scores=False, return_no_speech_prob=False, max_initial_timestamp_index=50, phrases=None):
         """One utterance whose log-mel features ALREADY live in HBM on `device` (f32 [n_mels][3000] at `mel_device_ptr`, e.g. an
         audio.MelStream after finish()): WIS_IN_MEL_DEV - nothing is staged through the host.  Goes through the micro-batcher bound
         to that DEVICE: any replica of the GPU can read the features, so concurrent windows of several streaming sessions on one GPU
@@ -993,7 +1063,7 @@ class Whisper:
         session's own replica: sessions pinned to different replicas of a GPU never shared a batch).
         As in `generate`: a start sequence without <|notimestamps|> (`timestamp_prompt`) decodes under Whisper's timestamp rules with
         `max_initial_timestamp_index`, `return_no_speech_prob=True` fills `no_speech_prob`, and drafts cannot be combined with either;
-        `return_scores` is accepted for symmetry (the scores are always filled)."""
+        `return_scores` is accepted for symmetry (the scores are always filled); `phrases` restricts the search to a phrase list, as in `generate`."""
         # `replica`: the replica the caller holds (a streaming session pins itself to the least-loaded one, acquire_replica: the load
         # accounting that spreads sessions over GPUs); it only has to live on the features' device
         r = replica if replica is not None else self.replica_on(device)
@@ -1004,7 +1074,7 @@ class Whisper:
                                        no_repeat_ngram_size=no_repeat_ngram_size, max_length=max_length, return_no_speech_prob=return_no_speech_prob,
                                        max_initial_timestamp_index=max_initial_timestamp_index, suppress_blank=suppress_blank, suppress_default=True,
                                        sampling_topk=sampling_topk, sampling_temperature=sampling_temperature, fixed_new_tokens=fixed_new_tokens,
-                                       draft_tokens=draft_tokens, draft_trajectory=draft_trajectory, return_trajectory=return_trajectory)
+                                       draft_tokens=draft_tokens, draft_trajectory=draft_trajectory, return_trajectory=return_trajectory, phrases=phrases)
         row = (int(mel_device_ptr), [int(t) for t in prompt], _seeds(opts, sampling_seed, 1)[0])
         return self._batcher.submit(opts, [row], affinity=("device", device))[0]
 

@@ -115,6 +115,10 @@ def create_app(models=None, settings=None, max_workers=None, sv=None):
     s = settings or (models.settings if models is not None else get_api_settings())
     if getattr(s, "long_form", "chunk") not in ("chunk", "seek"):      # (a bad setting fails the start, not every request)
         raise ValueError(f"setting long_form {s.long_form!r}: seek or chunk")
+    if getattr(s, "phrases_file", ""):      # (an unreadable phrase list fails the start too)
+        from .whisper import load_phrases_file
+        if not load_phrases_file(s.phrases_file):
+            raise ValueError(f"setting phrases_file {s.phrases_file!r}: the file holds no phrase")
     state = {"models": models, "sv": sv}
     sv_lock = __import__("threading").Lock()
     # enough threads that a full device batch per GPU replica can be waiting in the micro-batcher at once
@@ -195,6 +199,33 @@ def create_app(models=None, settings=None, max_workers=None, sv=None):
                     raise BadRequest(f"Invalid {name} {v!r}: token ids are >= 0")
             else:
                 prompts[name] = v
+        # phrase-constrained decoding: phrases=a|b|c (text; an entry "ids:1,2,3" is token ids) and phrase_nbest=n; absent or empty = the setting's list
+        # (phrases_file) and 1; unparsable = 400
+        phrases, nbest = q.get("phrases"), q.get("phrase_nbest")
+        if phrases in (None, ""):
+            phrases = None
+        elif len(phrases) > 65536:
+            raise BadRequest(f"phrases: {len(phrases)} characters (at most 65536)")
+        else:
+            entries = []
+            for v in phrases.split("|"):
+                if v.strip() == "":
+                    raise BadRequest(f"Invalid phrases {phrases!r}: an empty entry")
+                if v.startswith("ids:"):
+                    try:
+                        v = [int(t) for t in v[4:].split(",") if t.strip() != ""]
+                    except ValueError:
+                        raise BadRequest(f"Invalid phrases entry {v!r}: ids:<comma-separated token ids>")
+                    if not v or any(t < 0 for t in v):
+                        raise BadRequest("Invalid phrases: an ids: entry holds token ids >= 0, at least one")
+                entries.append(v)
+            phrases = entries
+        try:
+            nbest = int(nbest) if nbest not in (None, "") else None
+        except ValueError:
+            raise BadRequest(f"Invalid phrase_nbest {nbest!r}")
+        if nbest is not None and not 1 <= nbest <= s.max_beam:
+            raise BadRequest(f"phrase_nbest {nbest} outside 1..{s.max_beam}")
         # recordings over 30 s: long_form=seek | chunk, condition_on_previous_text=, no_speech_threshold= (absent: the settings' values); a bad value = 400
         lf = q.get("long_form") or None
         if lf is not None and lf not in ("seek", "chunk"):
@@ -214,7 +245,7 @@ def create_app(models=None, settings=None, max_workers=None, sv=None):
         if nst is not None and nst != nst:
             raise BadRequest("Invalid no_speech_threshold: not a number")
         return dict(model=model, beam_size=beam, repetition_penalty=rp, **prompts, no_repeat_ngram_size=ng, temperatures=temps, best_of=best_of,
-                    long_form=lf, condition_on_previous_text=cond, no_speech_threshold=nst,
+                    long_form=lf, condition_on_previous_text=cond, no_speech_threshold=nst, phrases=phrases, phrase_nbest=nbest,
                     detect_language=_as_bool(q.get("detect_language"), s.detect_language), force_language=q.get("force_language") or None,
                     translate=_as_bool(q.get("translate"), False), timestamps=_as_bool(q.get("timestamps"), False),
                     word_timestamps=_as_bool(q.get("word_timestamps"), False))
@@ -225,7 +256,7 @@ def create_app(models=None, settings=None, max_workers=None, sv=None):
         if p["word_timestamps"]:                                  # (word times imply segment times; no vocabulary is a 400, and so is audio over 30 s without long_form=seek)
             kw = {"word_timestamps": True}
         kw.update({k: p[k] for k in ("repetition_penalty", "no_repeat_ngram_size", "temperatures", "best_of", "initial_prompt", "prefix", "long_form",
-                                         "condition_on_previous_text", "no_speech_threshold") if p[k] is not None})      # (absent: do_whisper takes the settings' values)
+                                         "condition_on_previous_text", "no_speech_threshold", "phrases", "phrase_nbest") if p[k] is not None})      # (absent: do_whisper takes the settings' values)
         return await loop.run_in_executor(pool, lambda: do_whisper(audio_file, p["model"], p["beam_size"], "transcribe", p["detect_language"],
                                                                    p["force_language"], p["translate"], models=get_models(), **kw))
 
@@ -271,6 +302,8 @@ def create_app(models=None, settings=None, max_workers=None, sv=None):
             out["translation"] = translation
         if p["timestamps"] or p["word_timestamps"]:
             out["segments"] = res.segments
+        if getattr(res, "matches", None) is not None:      # a phrase-constrained request: the ranked phrases
+            out["matches"] = res.matches
         return JSONResponse(content=out)
 
     @app.post("/api/willow")
@@ -331,6 +364,8 @@ def create_app(models=None, settings=None, max_workers=None, sv=None):
             out["translation"] = translation
         if p["timestamps"] or p["word_timestamps"]:
             out["segments"] = res.segments
+        if getattr(res, "matches", None) is not None:      # a phrase-constrained request: the ranked phrases
+            out["matches"] = res.matches
         if voice_auth:
             out["voice_auth"] = sv_results
             out["speaker_status"] = speaker_status

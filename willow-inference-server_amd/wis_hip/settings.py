@@ -93,6 +93,10 @@ class APISettings:
     # vocabulary, style), and text the transcript is made to start with
     initial_prompt: str = ""
     prefix: str = ""
+    # phrase-constrained decoding: a file with one phrase per line (# starts a comment line); every request without a `phrases` query parameter is then
+    # restricted to that list and answers with its best phrase (`matches` in the response, `phrase_nbest` of them).  Empty = off.  A file that cannot
+    # be read fails the server's start
+    phrases_file: str = ""
     # prompted requests (more than 16 prompt tokens) share device batches whatever their prompt lengths: their micro-batcher key carries the pooled
     # prompt length -1 and the batch decodes through wis_generate_ragged, longest prompt first.  max_new_tokens stays in the key.  False: the key
     # carries the exact prompt length, as ever - two requests whose prompts differ by a token never meet in a device batch

@@ -607,3 +607,59 @@ def convert_hf_to_ct2_dir(hf_dir, out_dir):
         if os.path.exists(os.path.join(hf_dir, fn)):
             shutil.copy(os.path.join(hf_dir, fn), os.path.join(out_dir, fn))
     return a
+
+
+# ---- phrase-constrained decoding: the flat trie wis_model_set_phrases takes (include/wis_hip.h has the layout) -----------------------------
+PHRASE_MAX_RECORDS, PHRASE_MAX_CHILDREN, PHRASE_MAX_TOKENS = 65535, 4096, 32      # csrc/kernels.hpp PHRASE_MAX_*
+
+
+def build_phrase_trie(phrases, *, eot=EOT, suppress_ids=SUPPRESS_IDS, suppress_begin=SUPPRESS_IDS_BEGIN):
+    """[[token ids], ...] -> int32 [n][4], one record per trie edge: {token, first record of the child's children, number of children, child
+    ends a phrase}; record 0 is the root's pseudo-edge {-1, 1, children of the root, 0}; the children of a node are contiguous and ascending by
+    token, the blocks lie breadth-first.  Deterministic: the table depends on the SET of phrases only (duplicates merge, the order of the list
+    does not matter).  A phrase that is a prefix of another marks an interior node as a phrase end.  A phrase the engine would refuse - empty,
+    longer than 32 tokens, an id that is no text token (< eot) or is in suppress_ids, a first id in suppress_begin - is a ValueError that names
+    it; so are more than 4096 children of one node and more than 65535 records."""
+    sup, beg = set(int(t) for t in suppress_ids), set(int(t) for t in suppress_begin)
+    root = {}      # node = {token: [children dict, ends]}
+    n_phrases = 0
+    for ph in phrases:
+        try:
+            ids = [int(t) for t in ph]
+            if any(t != x for t, x in zip(ids, ph)):
+                raise ValueError
+        except (TypeError, ValueError):
+            raise ValueError(f"phrase {ph!r}: a list of token ids") from None
+        if not 1 <= len(ids) <= PHRASE_MAX_TOKENS:
+            raise ValueError(f"phrase {ids!r}: {len(ids)} tokens (1..{PHRASE_MAX_TOKENS})")
+        for i, t in enumerate(ids):
+            if not 0 <= t < eot:
+                raise ValueError(f"phrase {ids!r}: id {t} is no text token (0 <= id < {eot})")
+            if t in sup:
+                raise ValueError(f"phrase {ids!r}: id {t} is in the model's suppress_ids")
+            if i == 0 and t in beg:
+                raise ValueError(f"phrase {ids!r}: first id {t} is in the model's suppress_ids_begin")
+        node = root
+        for i, t in enumerate(ids):
+            ent = node.setdefault(t, [{}, 0])
+            if i == len(ids) - 1:
+                ent[1] = 1
+            node = ent[0]
+        n_phrases += 1
+    if not n_phrases:
+        raise ValueError("an empty phrase list")
+    recs, queue, at = [[-1, 0, 0, 0]], [(0, root)], 0
+    while at < len(queue):      # breadth-first: the children of record i are appended when i is visited
+        i, kids = queue[at]
+        at += 1
+        if not kids:
+            continue
+        if len(kids) > PHRASE_MAX_CHILDREN:
+            raise ValueError(f"{len(kids)} different tokens continue one prefix (at most {PHRASE_MAX_CHILDREN})")
+        recs[i][1], recs[i][2] = len(recs), len(kids)
+        for t in sorted(kids):
+            queue.append((len(recs), kids[t][0]))
+            recs.append([t, 0, 0, kids[t][1]])
+        if len(recs) > PHRASE_MAX_RECORDS:
+            raise ValueError(f"the phrase set needs more than {PHRASE_MAX_RECORDS} trie records")
+    return np.ascontiguousarray(np.asarray(recs, np.int32).reshape(-1, 4))

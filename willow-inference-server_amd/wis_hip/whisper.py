@@ -400,6 +400,43 @@ def prompt_ids(value, tokenizer, special, what):
     return ids
 
 
+MAX_PHRASES = 20000      # entries of a request's phrase list (the engine's own limit is 65535 trie records)
+
+
+def load_phrases_file(path):
+    """The setting `phrases_file`: one phrase per line (blank lines and lines that start with # are skipped).  Empty path: no list.  A file that
+    cannot be read raises (OSError): the server's start fails, not every request."""
+    if not path:
+        return []
+    key = (path, os.stat(path).st_mtime_ns)      # (read once per version of the file, not once per request)
+    if _phrases_file_cache.get("key") != key:
+        with open(path, "r", encoding="utf-8") as f:
+            _phrases_file_cache.update(key=key, phrases=[ln.strip() for ln in f if ln.strip() and not ln.lstrip().startswith("#")])
+    return list(_phrases_file_cache["phrases"])
+
+
+_phrases_file_cache = {}
+
+
+def phrase_ids(phrases, tokenizer, special):
+    """do_whisper's `phrases` -> ([token ids per phrase], {ids tuple: the caller's text for it}).  An entry is a string - encoded as
+    " " + text.strip() with the checkpoint's tokenizer, like a prompt (no vocabulary: ValueError) - or a list of text token ids."""
+    if isinstance(phrases, (str, bytes)) or not hasattr(phrases, "__iter__"):
+        raise ValueError("phrases: a list of strings or token id lists")
+    phrases = list(phrases)
+    if not 1 <= len(phrases) <= MAX_PHRASES:
+        raise ValueError(f"phrases: {len(phrases)} entries (1..{MAX_PHRASES})")
+    out, names = [], {}
+    for i, ph in enumerate(phrases):
+        ids = prompt_ids(ph, tokenizer, special, f"phrases[{i}]")
+        if not ids:
+            raise ValueError(f"phrases[{i}]: an empty phrase")
+        out.append(ids)
+        if isinstance(ph, str):
+            names.setdefault(tuple(ids), ph.strip())
+    return out, names
+
+
 def assemble_prompt(start, special, initial_prompt_ids=(), prefix_ids=(), n_text_ctx=448):
     """openai-whisper's decoder prompt: [<|startofprev|>] + initial_prompt_ids[-(n_ctx / 2 - 1):] + start sequence + prefix_ids.  The engine takes
     n_ctx / 2 + 4 tokens (228): with a prefix the prompt part is cut further from the left.  A prefix of more than MAX_PREFIX_TOKENS is a ValueError."""
@@ -464,8 +501,15 @@ def _text_of(tokenizer, below):
 def do_whisper(audio_file, model, beam_size=None, task="transcribe", detect_language=False, force_language=None, translate=False,
                models=None, fixed_new_tokens=None, timestamps=False, word_timestamps=False, repetition_penalty=None, no_repeat_ngram_size=None,
                temperatures=None, best_of=None, compression_ratio_threshold=None, logprob_threshold=None, initial_prompt=None, prefix=None,
-               long_form=None, condition_on_previous_text=None, no_speech_threshold=None):
-    """long_form ("chunk" | "seek"; None: the setting, "chunk"): how a recording over 30 s is served.  "chunk": the reference's fixed windows merged by
+               long_form=None, condition_on_previous_text=None, no_speech_threshold=None, phrases=None, phrase_nbest=1):
+    """phrases (None: the setting's list, `phrases_file`; empty: off): the transcript is restricted to a phrase list - strings (tokenised as
+    " " + text.strip() with the checkpoint's tokenizer; no vocabulary: ValueError) or lists of text token ids.  The search can only produce
+    one of the phrases (include/wis_hip.h states the rule); `text` is the best one, and the result gains
+    `matches = [{"text", "score"}]`, best first: the `phrase_nbest` best phrases of the beam search (at most beam_size; fewer when the search
+    reached fewer) with the engine's length-normalised log-probability, renormalised over what the list allows at each step.  initial_prompt and
+    the repetition options combine with it; prefix, timestamps, word_timestamps, temperatures, long_form=seek and a recording over 30 s are a
+    ValueError.  Language detection is unaffected; the translation pass stays unconstrained, as it stays unprompted.
+    long_form ("chunk" | "seek"; None: the setting, "chunk"): how a recording over 30 s is served.  "chunk": the reference's fixed windows merged by
     longest common sequence - no timestamps, no fallback (ValueError).  "seek": openai-whisper's transcribe() loop (wis_hip.longform) over one
     whole-recording log-mel kept on one of the model's GPUs (audio.LongMel) - timestamps, word_timestamps, the temperature fallback, initial_prompt
     and the repetition options all apply per window; condition_on_previous_text (None: the setting, True) and no_speech_threshold (None: the setting,
@@ -504,7 +548,20 @@ def do_whisper(audio_file, model, beam_size=None, task="transcribe", detect_lang
         logprob_threshold=_threshold(opt(logprob_threshold, "logprob_threshold", -1.0), -1),
         long_form=opt(long_form, "long_form", "chunk"), condition_on_previous_text=bool(opt(condition_on_previous_text, "condition_on_previous_text", True)),
         no_speech_threshold=_threshold(opt(no_speech_threshold, "no_speech_threshold", 0.6)),
-        initial_prompt=opt(initial_prompt, "initial_prompt", ""), prefix=opt(prefix, "prefix", ""))
+        initial_prompt=opt(initial_prompt, "initial_prompt", ""), prefix=opt(prefix, "prefix", ""),
+        phrases=load_phrases_file(getattr(s, "phrases_file", "")) if phrases is None else phrases, phrase_nbest=phrase_nbest)
+    constrained = not (q.phrases is None or (hasattr(q.phrases, "__len__") and len(q.phrases) == 0))
+    if constrained:
+        try:
+            q.phrase_nbest = int(phrase_nbest)
+            if q.phrase_nbest != float(phrase_nbest) or q.phrase_nbest < 1:
+                raise ValueError
+        except (TypeError, ValueError, OverflowError):
+            raise ValueError(f"phrase_nbest {phrase_nbest!r}: an integer >= 1") from None
+        for on, what in ((q.prefix, "prefix"), (q.timestamps, "timestamps / word_timestamps"), (temps, "temperatures"), (q.long_form == "seek", "long_form=seek"),
+                         (q.fixed_new_tokens, "fixed_new_tokens")):
+            if on:
+                raise ValueError(f"phrases cannot be combined with {what}")
     if q.long_form not in ("chunk", "seek"):
         raise ValueError(f"long_form {q.long_form!r}: seek or chunk")
     timestamps, rep, fixed_new_tokens = q.timestamps, q.rep, q.fixed_new_tokens
@@ -531,6 +588,8 @@ def do_whisper(audio_file, model, beam_size=None, task="transcribe", detect_lang
         return _do_whisper_seek(q, models, model, whisper_model, pcm, audio_duration, first_time_start)
     if timestamps and audio_duration > 30 * 1000:
         raise ValueError("timestamps are available for audio of up to 30 s (one window)")
+    if constrained and audio_duration > 30 * 1000:
+        raise ValueError("phrases are available for audio of up to 30 s (one window)")
     if temps and audio_duration > 30 * 1000:
         raise ValueError("the temperature fallback is available for audio of up to 30 s (one window)")
     use_chunking = audio_duration > 30 * 1000 and s.support_chunking
@@ -555,6 +614,12 @@ def do_whisper(audio_file, model, beam_size=None, task="transcribe", detect_lang
     total_chunk_count = features.shape[0]
     tokenizer = models.tokenizer_for(model)
     ip_ids, px_ids = _request_prompt_ids(q, tokenizer, special)
+    phr = {}
+    if constrained:
+        if q.phrase_nbest > q.beam_size:
+            raise ValueError(f"phrase_nbest {q.phrase_nbest}: a search at beam_size {q.beam_size} returns at most {q.beam_size} phrases")
+        phr_ids, phr_names = phrase_ids(q.phrases, tokenizer, special)
+        phr = dict(phrases=phr_ids, num_hypotheses=q.phrase_nbest)
     ccg = s.concurrent_gpu_chunks
     translating = translate and total_chunk_count <= ccg
     # encode_once: a request that reads a window more than once - language detection, the temperature fallback, the word alignment, the
@@ -596,7 +661,7 @@ def do_whisper(audio_file, model, beam_size=None, task="transcribe", detect_lang
         hi = min(lo + ccg, total_chunk_count)
         feats, fkind = windows_of(lo, hi)
         results.extend(whisper_model.generate(feats, [prompt] * (hi - lo), beam_size=q.beam_size, return_scores=False,
-                                              fixed_new_tokens=fixed_new_tokens, **fkind, **rep))
+                                              fixed_new_tokens=fixed_new_tokens, **fkind, **rep, **phr))
     assert len(results) == total_chunk_count, "Result length doesn't match expected total_chunk_count"
     if use_chunking:
         tokens = audio.find_longest_common_sequence([(results[i].sequences_ids[0], strides[i]) for i in range(total_chunk_count)],
@@ -637,6 +702,10 @@ def do_whisper(audio_file, model, beam_size=None, task="transcribe", detect_lang
     out.translation_tokens = out_translation_tokens
     out.segments = segments
     out.fallback = getattr(results[0], "fallback", None)      # temperature fallback: what the kept decode was (decode_with_fallback)
+    out.matches = None
+    if constrained:      # the caller's own spelling of a phrase it gave as text, the decoded ids otherwise
+        out.matches = [dict(text=phr_names.get(tuple(ids)) or tokenizer.decode(ids).strip(), score=float(sc))
+                       for ids, sc in zip(results[0].sequences_ids, results[0].scores)]
     return out
 
 
