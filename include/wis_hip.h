@@ -283,6 +283,29 @@ typedef struct {
    * drafted entry points: WIS_E_UNSUPPORTED; on with no set installed: WIS_E_STATE; a value other than 0 / 1: WIS_E_ARG.  Nothing is enqueued
    * by a refused call.  wis_generate, wis_generate_n, wis_generate_ragged, wis_debug_search, wis_debug_search_n. */
   int32_t phrases;                /* 1: constrain the search by the handle's phrase set.  0: off */
+  /* The in-grammar mass of a phrase-constrained search.  Appended field: 0 is what a caller that never knew it passes, and changes nothing - the same
+   * launches, captured steps and buffers as before the field existed.
+   * THE PHRASE MASS RULE.  A live row of utterance b (cumulative score above -inf; at the first step the one shared prompt row) whose history is a
+   * path of the trie ending at record r (record 0: the root).  x: the row as the repetition rules left it.  u[t], t in [0, n_vocab): x[t] under exactly
+   * the masks the sampling statistics apply to the row of a call without timestamps, in fp32:
+   *     u[t] = x[t] + (suppress_default ? bias_all[t] : 0),  then  u[t] = u[t] + bias_begin[t]  at the first step (no token generated yet) when suppress_blank is on
+   * (bias_all: -inf at the model's suppress_ids, else 0; bias_begin: -inf at suppress_ids_begin, else 0).  A: the node's children, plus <|endoftext|>
+   * when the node ends a phrase.  M = max u; num = sum over A of exp(u[t] - M); den = the same sum over [0, n_vocab) (an entry equal to M counts as
+   * exactly 1, also when M is +inf);
+   *     logmass[b][r] = min(0, log(num) - log(den)),   -inf when M is -inf or num is 0 (every allowed entry is -inf, or M is +inf and none is);
+   * (the engine sums the allowed entries about their own maximum, so a share below fp32's exp range is still a number, not an underflow to -inf)
+   * never NaN for a row without NaN in [0, n_vocab) (with a NaN there: unspecified).  Ids in [n_vocab, n_vocab_pad) never enter.  It is the log of the
+   * share of the model's probability that the set allows at that step, computed where the mask is applied (num and den are reduced in one fixed order,
+   * csrc/dec_kernels.hip phrase_rules_mass_kernel; a row whose finite entries are all allowed gives exactly 0), and the masked row is bit for bit the row
+   * of a call with the option off - so are ids and scores.
+   * Nothing is accumulated per beam: a live row's node is a function of its history, distinct live beams of an utterance hold distinct histories, and a
+   * node at depth L is visited at step L alone - so the step's value is stored per (utterance, record), and a RESULT's phrase_logmass is the fp32
+   * sum, in path order from the root, of logmass[b][r] over the len + 1 nodes of its own path; -inf for a filler result (score -inf) and for a result
+   * that is no phrase of the set.  The sum equals log P_unconstrained(phrase, <|endoftext|>) - log P_constrained(phrase, <|endoftext|>): what a second,
+   * unconstrained decode would have been compared for.  A slot the search did not write is NaN (the slots of the installed set are filled with NaN
+   * when the call starts), and a NaN slot propagates into the sum.
+   * 1 needs phrases = 1 (else WIS_E_ARG); a value other than 0 / 1: WIS_E_ARG.  wis_last_phrase_mass reads the sums.  The entry points of `phrases`. */
+  int32_t phrase_mass;            /* 1: compute the in-grammar mass of every result (wis_last_phrase_mass).  0: off */
 } wis_gen_opts_t;
 
 /* out_ids: [B][max_new] (max_new = resolved max_new_tokens), out_len: [B], out_score: [B]
@@ -354,6 +377,10 @@ int wis_last_trajectory(wis_model_t* m, int b, int32_t* tok, int32_t* org, int c
  * (otherwise WIS_E_STATE): softmax(logits at the <|startoftranscript|> prompt position)[cfg.no_speech] over the whole vocabulary,
  * no logits processor applied (openai-whisper probs_at_sot).  Synchronises the handle's stream. */
 int wis_last_no_speech_prob(wis_model_t* m, int B, float* out);
+/* phrase_logmass (wis_gen_opts_t::phrase_mass states the rule) of the n results of each of the first B utterances of the LAST search on this handle
+ * (wis_generate, wis_generate_n, wis_generate_ragged, wis_debug_search, wis_debug_search_n), which must have set opts->phrase_mass (otherwise
+ * WIS_E_STATE): out [B][n], n = that call's results per utterance (anything else: WIS_E_ARG).  Synchronises the handle's stream. */
+int wis_last_phrase_mass(wis_model_t* m, int B, int n, float* out);
 
 /* ---- a14: language detection (replaces whisper_model.detect_language(features),
  * main.py:637-643): probabilities over cfg.lang_ids, [B][n_lang]. */
@@ -716,6 +743,17 @@ int wis_op_greedy_rows(int device, const float* logits, int n_vocab, int n_vocab
  * 1 <= n_rec <= 65535, 0 <= eot < n_vocab <= n_vocab_pad, 1 <= max_new <= 256, beam <= 8, B x beam <= 96: anything else WIS_E_ARG. */
 int wis_op_phrase_rules(int device, float* logits, int n_vocab, int n_vocab_pad, int eot, const int32_t* trie, int n_rec, const int32_t* alive,
                         const int32_t* step_u, const int32_t* done, int B, int beam, int max_new, int lr_b, int lr_j, int lr_off);
+/* the phrase mask with the in-grammar mass (phrase_rules_mass_kernel; wis_gen_opts_t::phrase_mass states the rule): wis_op_phrase_rules' arguments and
+ * its mask, bit for bit, plus bias_all f32 [n_vocab] or NULL (no list), bias_begin f32 [n_vocab] (added when step_u[b] == 0 and suppress_blank != 0) and
+ * logmass f32 [B][n_rec]: the row's value is stored at logmass[b n_rec + record index of the row's node], every other slot keeps its bits (finished
+ * utterances, histories off the trie, beams j > 0 of a shared row write nothing; every other row counts as live).  n_vocab <= 65536. */
+int wis_op_phrase_mass(int device, float* logits, int n_vocab, int n_vocab_pad, int eot, const int32_t* trie, int n_rec, const int32_t* alive,
+                       const int32_t* step_u, const int32_t* done, int B, int beam, int max_new, int lr_b, int lr_j, int lr_off,
+                       const float* bias_all, const float* bias_begin, int suppress_blank, float* logmass);
+/* the sums along finished results (phrase_mass_gather_kernel): ids i32 [B n][id_ld], len i32 [B n], score f32 [B n] or NULL (a result whose score is not
+ * above -inf is a filler), trie i32 [n_rec][4], logmass f32 [B][n_rec] -> out f32 [B n].  All device memory; B n <= 96, 1 <= id_ld <= 256. */
+int wis_op_phrase_mass_gather(int device, const int32_t* ids, const int32_t* len, const float* score, const int32_t* trie, int n_rec,
+                              const float* logmass, int B, int n, int id_ld, float* out);
 
 /* ---- speaker verification (replaces the reference's WavLMForXVector embedder, main.py:306-316 / do_sv 797-879): one handle = the
  * WavLM-base-plus-sv x-vector model on one GPU.  Input: mono 16 kHz f32 PCM in host memory, already through the reference's

@@ -129,7 +129,7 @@ def table():
     return t
 
 
-APPENDED_FIELDS = ("phrases",)      # wis_gen_opts_t fields younger than tests/golden/decode_calls.json
+APPENDED_FIELDS = ("phrases", "phrase_mass")      # wis_gen_opts_t fields younger than tests/golden/decode_calls.json
 
 
 class RecordingLib:

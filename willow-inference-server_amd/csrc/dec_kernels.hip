@@ -3784,4 +3784,187 @@ int launch_phrase_rules(hipStream_t st, float* logits, const BeamState& bs, int 
   return WIS_OK;
 }
 
+// =======================================================================================
+// The phrase mask WITH the in-grammar mass (include/wis_hip.h, THE PHRASE MASS RULE): phrase_rules_kernel's place in the tail when
+// wis_gen_opts_t::phrase_mass is on.  (Behind phrase_rules_kernel, the walk duplicated, not shared: that kernel's code stays what it was.)
+// Same grid, same walk, same early-outs, same lr_j == 0 rule, the same mask stored the same way - the row it leaves is phrase_rules_kernel's bit
+// for bit.  The walk also publishes the INDEX of the record it arrived at (s_at, beside s_rec); the root is record 0.  Between the gather of the
+// kept values and the fill, ONE pass over u[t] = row[t] + (bias_all ? bias_all[t] : 0) (+ bias_begin[t] at step 0 with suppress_blank: the form
+// logit_stats_kernel gives a row of a call without timestamps) yields M = max u and den = sum exp(u - M) over [0, n_vocab), and MA, num: the same two
+// over the allowed ids alone (an LDS bitmap of the node's children and <|endoftext|> at a phrase end, set while the kept values are gathered); the
+// mass is (MA - M) + log(num) - log(den) - the rule's log(sum over A of exp(u - M)) - log(den) with the allowed sum taken about its OWN maximum, so
+// a share far below fp32's exp range (allowed logits 100 under the row's best) is still a number, not an underflow.
+// THE REDUCTION ORDER (tests/phrase_mass_ref.py derives its fp32 bound from it):
+//   thread tid owns the ids t = tid (mod 256), ascending, in chunks of 8 (ids base + 256 j + tid, base = 0, 2048, ..; ids >= n_vocab count as -inf).
+//   Online, per chunk, for (m, sd) over all ids: cm = max(m, the chunk's 8 values); mm = cm, or 0 when cm is -inf; sd = sd E(m, mm); then for
+//   j = 0 .. 7 in order sd += E(v[j], mm); m = cm.   E(a, b) = 1 when a == b, else __expf(a - b) (so exp(-inf) = 0, never -inf - -inf; a +inf
+//   maximum counts its own entries as 1 each).  (ma, sn) likewise over the allowed ids (a value that is not allowed counts as -inf and adds 0).
+//   Then M = the maximum of the 256 m (exact), every thread scales its sd by E(m, M or 0 when -inf); the 256 values are summed by wave_sum (a
+//   balanced pairwise tree over the 64 lanes) and the four waves' sums as (w0 + w1) + (w2 + w3); MA and num likewise.  The two reductions take the
+//   same operations in the same order, so a row whose finite entries are all allowed gives MA == M, num == den and a mass of exactly 0.
+//   logmass = -inf when M or MA is -inf, else min(0, (MA == M ? 0 : MA - M) + (logf(num) - logf(den))).
+// Thread 0 stores the one float at logmass[b lm_ld + record index] (a vector store), only for a row whose cumulative score is finite (cum null: a tap
+// caller's rows all count): a dead slot (cum -inf) can repeat a live beam's history, and its row is not the model's row for that history.  A row that
+// returns early stores nothing.  n_vocab <= PHRASE_MASS_MAX_VOCAB (the bitmap; launch_logit_stats has the same limit).
+constexpr int PHRASE_MASS_MAX_VOCAB = 65536;
+__device__ __forceinline__ float mass_term(float a, float b) { return a == b ? 1.f : __expf(a - b); }
+__global__ __launch_bounds__(256) void phrase_rules_mass_kernel(float* __restrict__ logits, const int* __restrict__ step_u, const int* __restrict__ done,
+                                                                const int* __restrict__ alive, const int4* __restrict__ trie, int n_rec, SampleCfg cfg,
+                                                                int lr_b, int lr_j, int lr_off, const float* __restrict__ bias_all,
+                                                                const float* __restrict__ bias_begin, const float* __restrict__ cum,
+                                                                float* __restrict__ logmass, int lm_ld) {
+  __shared__ int4 s_rec[2];
+  __shared__ int s_at[2];
+  __shared__ int s_tok[PHRASE_MAX_CHILDREN];
+  __shared__ float s_val[PHRASE_MAX_CHILDREN];
+  __shared__ float s_eot;
+  __shared__ unsigned s_bits[PHRASE_MASS_MAX_VOCAB / 32];
+  __shared__ float s_red[4][4];
+  const int tid = threadIdx.x, m = blockIdx.x, b = m / cfg.beam, jb = m - b * cfg.beam;
+  if (done[b] || n_rec < 1) return;
+  if (lr_j == 0 && jb != 0) return;
+  const int step = step_u[b];
+  int L = step;
+  L = L < cfg.max_new ? L : cfg.max_new;
+  if (L < 0 || L > PHRASE_MAX_DEPTH) return;
+  const int V = cfg.n_vocab;
+  if (V > PHRASE_MASS_MAX_VOCAB || lm_ld < n_rec) return;      // (the launcher refuses both)
+  int4 node = trie[0];
+  int at = 0;
+  for (int i = 0; i < L; ++i) {
+    const int first = node.y, n = node.z;
+    if (first < 1 || n < 1 || n > PHRASE_MAX_CHILDREN || first > n_rec - n) return;      // a leaf, or no record range of this table
+    const int tk = alive[(size_t)m * cfg.max_new + i];
+    if (tid == 0) s_rec[i & 1] = make_int4(-1, 0, 0, 0);
+    __syncthreads();
+    for (int c = tid; c < n; c += 256) {
+      const int4 r = trie[first + c];
+      if (r.x == tk && tk >= 0) { s_rec[i & 1] = r; s_at[i & 1] = first + c; }      // (ascending tokens: at most one child matches)
+    }
+    __syncthreads();
+    node = s_rec[i & 1];
+    if (node.x < 0) return;      // the history is no path of the trie: the row stays as it is, no slot is written
+    at = s_at[i & 1];      // in [1, n_rec): first + c < first + n <= n_rec
+  }
+  const int first = node.y, n = node.z, ends = node.w;
+  const bool kids = n >= 1;
+  if (kids && (first < 1 || n > PHRASE_MAX_CHILDREN || first > n_rec - n)) return;
+  if (!kids && !ends) return;      // (a validated set has no such node)
+  float* row = logits + (size_t)(b * lr_b + jb * lr_j + lr_off) * cfg.n_vocab_pad;
+  const bool want = !cum || cum[m] > -INFINITY;      // (workgroup-uniform)
+  if (want) {
+    for (int w = tid; w < ((V + 31) >> 5); w += 256) s_bits[w] = 0u;
+    __syncthreads();
+  }
+  if (kids)
+    for (int c = tid; c < n; c += 256) {
+      int t = trie[first + c].x;
+      t = (t >= 0 && t < V) ? t : -1;
+      s_tok[c] = t;
+      s_val[c] = t >= 0 ? row[t] : 0.f;
+      if (want && t >= 0) atomicOr(&s_bits[t >> 5], 1u << (t & 31));
+    }
+  const bool keep_eot = ends != 0 && cfg.eot >= 0 && cfg.eot < V;
+  if (keep_eot && tid == 0) { s_eot = row[cfg.eot]; if (want) atomicOr(&s_bits[cfg.eot >> 5], 1u << (cfg.eot & 31)); }
+  __syncthreads();      // every kept value is read - it lies in LDS -, the bitmap is whole
+  if (want) {
+    const bool begin = (step == 0) && cfg.suppress_blank;
+    float mx = -INFINITY, sd = 0.f, ma = -INFINITY, sn = 0.f;
+    for (int base = 0; base < V; base += 8 * 256) {
+      float v[8]; bool ok[8];
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {      // clamped addresses, masks by select: the eight requests of a stream leave before anything is waited for
+        const int idx = base + 256 * j + tid, c = idx < V ? idx : V - 1;
+        float x = row[c] + (bias_all ? bias_all[c] : 0.f);
+        x = begin ? x + bias_begin[c] : x;
+        v[j] = idx < V ? x : -INFINITY;
+        ok[j] = (idx < V) & (((s_bits[c >> 5] >> (c & 31)) & 1u) != 0u);
+      }
+      float cm = mx, ca = ma;
+#pragma unroll
+      for (int j = 0; j < 8; ++j) { cm = fmaxf(cm, v[j]); ca = fmaxf(ca, ok[j] ? v[j] : -INFINITY); }
+      const float mm = cm == -INFINITY ? 0.f : cm, am = ca == -INFINITY ? 0.f : ca;
+      sd *= mass_term(mx, mm); sn *= mass_term(ma, am);
+#pragma unroll
+      for (int j = 0; j < 8; ++j) { sd += mass_term(v[j], mm); sn += ok[j] ? mass_term(v[j], am) : 0.f; }
+      mx = cm; ma = ca;
+    }
+    const int lane = tid & 63, wave = tid >> 6;
+    const float wm = wave_max(mx), wa = wave_max(ma);
+    if (lane == 0) { s_red[0][wave] = wm; s_red[1][wave] = wa; }
+    __syncthreads();
+    const float M = fmaxf(fmaxf(s_red[0][0], s_red[0][1]), fmaxf(s_red[0][2], s_red[0][3]));
+    const float MA = fmaxf(fmaxf(s_red[1][0], s_red[1][1]), fmaxf(s_red[1][2], s_red[1][3]));
+    sd = wave_sum(sd * mass_term(mx, M == -INFINITY ? 0.f : M)); sn = wave_sum(sn * mass_term(ma, MA == -INFINITY ? 0.f : MA));
+    if (lane == 0) { s_red[2][wave] = sd; s_red[3][wave] = sn; }
+    __syncthreads();
+    if (tid == 0) {
+      const float den = (s_red[2][0] + s_red[2][1]) + (s_red[2][2] + s_red[2][3]);
+      const float num = (s_red[3][0] + s_red[3][1]) + (s_red[3][2] + s_red[3][3]);
+      float lm = -INFINITY;      // (M or MA -inf: nothing, or nothing allowed, is finite; otherwise the sums are >= 1: their maximum's own term)
+      if (M > -INFINITY && MA > -INFINITY) lm = fminf(0.f, (MA == M ? 0.f : MA - M) + (logf(num) - logf(den)));
+      logmass[(size_t)b * lm_ld + at] = lm;
+    }
+  }
+  __syncthreads();      // every read of the row is done before the fill
+  int head = (int)((4u - (unsigned)((reinterpret_cast<uintptr_t>(row) >> 2) & 3u)) & 3u);
+  head = head < V ? head : V;
+  const int n4 = (V - head) >> 2, tail0 = head + 4 * n4;
+  if (tid < head) row[tid] = -INFINITY;
+  float4* row4 = reinterpret_cast<float4*>(row + head);
+  const float4 ninf4 = make_float4(-INFINITY, -INFINITY, -INFINITY, -INFINITY);
+  for (int i = tid; i < n4; i += 256) row4[i] = ninf4;
+  if (tid < V - tail0) row[tail0 + tid] = -INFINITY;
+  __syncthreads();      // the fill is ahead of the values that go back
+  if (kids)
+    for (int c = tid; c < n; c += 256) { const int t = s_tok[c]; if (t >= 0) row[t] = s_val[c]; }
+  if (keep_eot && tid == 0) row[cfg.eot] = s_eot;
+}
+int launch_phrase_rules_mass(hipStream_t st, float* logits, const BeamState& bs, int B, const SampleCfg& cfg, const int4* trie, int n_rec, int lr_b, int lr_j, int lr_off,
+                             const float* bias_all, const float* bias_begin, float* logmass, int lm_ld) {
+  if (!trie || n_rec < 1 || n_rec > PHRASE_MAX_RECORDS || cfg.max_new < 1 || cfg.n_vocab < 1 || cfg.n_vocab_pad < cfg.n_vocab || cfg.n_vocab > PHRASE_MASS_MAX_VOCAB ||
+      !bias_begin || !logmass || lm_ld < n_rec) { set_error("phrase_rules_mass: config out of range"); return WIS_E_UNSUPPORTED; }
+  hipLaunchKernelGGL(phrase_rules_mass_kernel, dim3(B * cfg.beam), dim3(256), 0, st, logits, bs.step_u, bs.done, bs.alive, trie, n_rec, cfg, lr_b, lr_j, lr_off,
+                     bias_all, bias_begin, bs.cum, logmass, lm_ld);
+  return WIS_OK;
+}
+
+// The in-grammar mass of finished results (THE PHRASE MASS RULE): one wave per (utterance, result), launched once behind the search.  Result r = b n + i:
+// ids[r id_ld .. + len[r]) is walked from the root - 64 children per round, the matching lane found by ballot - and the slots
+// logmass[b lm_ld + record] of the len + 1 nodes of the path, the root first, are added in path order in fp32 (a NaN slot - one the search never
+// wrote - propagates).  -inf: a filler (score not above -inf), a length outside [0, PHRASE_MAX_DEPTH], a token that is no child, a record range
+// outside the table, a path that does not end a phrase.  score may be null.  Lane 0 stores out[r].
+__global__ __launch_bounds__(64) void phrase_mass_gather_kernel(const int* __restrict__ ids, const int* __restrict__ len, const float* __restrict__ score,
+                                                                const int4* __restrict__ trie, int n_rec, const float* __restrict__ logmass, int lm_ld,
+                                                                int n, int id_ld, float* __restrict__ out) {
+  const int r = blockIdx.x, b = r / n, lane = threadIdx.x;
+  const int L = len[r];
+  bool path = n_rec >= 1 && lm_ld >= n_rec && L >= 0 && L <= PHRASE_MAX_DEPTH && L <= id_ld && !(score && !(score[r] > -INFINITY));
+  float acc = 0.f;
+  if (path) {
+    int4 node = trie[0];
+    acc = logmass[(size_t)b * lm_ld];
+    for (int i = 0; i < L && path; ++i) {
+      const int first = node.y, nn = node.z, tk = ids[(size_t)r * id_ld + i];
+      int found = -1;
+      if (first >= 1 && nn >= 1 && nn <= PHRASE_MAX_CHILDREN && first <= n_rec - nn && tk >= 0)
+        for (int c0 = 0; c0 < nn && found < 0; c0 += 64) {
+          const int c = c0 + lane;
+          const unsigned long long hit = __ballot(c < nn && trie[first + (c < nn ? c : 0)].x == tk);
+          if (hit) found = first + c0 + (__ffsll((long long)hit) - 1);
+        }
+      path = found >= 0;
+      if (path) { node = trie[found]; acc += logmass[(size_t)b * lm_ld + found]; }
+    }
+    path = path && node.w != 0;
+  }
+  if (lane == 0) out[r] = path ? acc : -INFINITY;
+}
+int launch_phrase_mass_gather(hipStream_t st, const int* ids, const int* len, const float* score, const int4* trie, int n_rec, const float* logmass, int lm_ld,
+                              int B, int n, int id_ld, float* out) {
+  if (!ids || !len || !trie || !logmass || !out || n_rec < 1 || n_rec > PHRASE_MAX_RECORDS || lm_ld < n_rec || B < 1 || n < 1 || id_ld < 1) { set_error("phrase_mass_gather: config out of range"); return WIS_E_UNSUPPORTED; }
+  hipLaunchKernelGGL(phrase_mass_gather_kernel, dim3(B * n), dim3(64), 0, st, ids, len, score, trie, n_rec, logmass, lm_ld, n, id_ld, out);
+  return WIS_OK;
+}
+
 }  // namespace wis

@@ -35,6 +35,7 @@ struct SampleCtx {
   float rep_pen = 1.f; int rep_ngram = 0;      // repetition_penalty / no_repeat_ngram_size (1 / 0: off): a pre-pass that patches the logits rows, ahead of everything else
   bool rep() const { return rep_pen != 1.f || rep_ngram != 0; }
   bool phrases = false;          // wis_gen_opts_t::phrases: the handle's phrase set masks every live row behind the repetition rules (phrase_rules_kernel)
+  bool phr_mass = false;         // wis_gen_opts_t::phrase_mass: phrase_rules_mass_kernel in that kernel's place - the same mask, and the node's in-grammar mass
   SampleP sp;                    // random sampling (topk 0: off): sample_step_kernel stands in beam_step_kernel's place, `beam` counts the utterance's samples
   int n_res = 1;                 // results per utterance (num_hypotheses)
   bool sampling() const { return sp.topk != 0; }
@@ -79,7 +80,9 @@ static int resolve_rep_opts(const wis_gen_opts_t* o, SampleCtx* g) {
 // wis_gen_opts_t::phrases of a call, resolved - or refused; *max_new: the call's usual value in, what the constrained search takes out
 // (max_new_tokens = 0: at most the longest phrase + 1, the step that can only take <|endoftext|>; an explicit value below that is refused)
 static int resolve_phrase_opts(const wis_model* m, const wis_gen_opts_t* o, bool drafted, SampleCtx* g, int* max_new) {
-  g->phrases = false;
+  g->phrases = false; g->phr_mass = false;
+  if (o->phrase_mass != 0 && o->phrase_mass != 1) { set_error("phrase_mass %d: 0 (off) or 1 (the in-grammar mass of every result)", o->phrase_mass); return WIS_E_ARG; }
+  if (o->phrase_mass && o->phrases == 0) { set_error("phrase_mass: needs phrases = 1 (the mass is that of the handle's phrase set)"); return WIS_E_ARG; }
   if (o->phrases == 0) return WIS_OK;
   if (o->phrases != 1) { set_error("phrases %d: 0 (off) or 1 (the handle's phrase set)", o->phrases); return WIS_E_ARG; }
   if (drafted) { set_error("phrases: not available for drafted decodes (wis_generate_draft / wis_generate_draft_beam)"); return WIS_E_UNSUPPORTED; }
@@ -91,7 +94,28 @@ static int resolve_phrase_opts(const wis_model* m, const wis_gen_opts_t* o, bool
   if (o->max_new_tokens > 0 && o->max_new_tokens < need) { set_error("max_new_tokens %d: the phrase set's longest phrase needs %d (its %d tokens and <|endoftext|>)", o->max_new_tokens, need, m->phr_depth); return WIS_E_ARG; }
   if (*max_new < need) { set_error("phrases: the longest phrase (%d tokens) does not fit the %d steps this call can take", m->phr_depth, *max_new); return WIS_E_ARG; }
   if (o->max_new_tokens == 0 && *max_new > need) *max_new = need;
-  g->phrases = true;
+  g->phrases = true; g->phr_mass = o->phrase_mass == 1;
+  return WIS_OK;
+}
+// A call with phrase_mass on, before anything of it is enqueued: the handle's logmass buffer (allocated here once, as the align scratch is on the first
+// wis_align; it never moves), and NaN in the slots of the installed set for each of the call's utterances - a slot the search does not write
+// reads as NaN afterwards, never as an earlier call's value (bytes 0xFF: a NaN in every float)
+static int phrase_mass_begin(wis_model* m, int B, hipStream_t st) {
+  if (!m->d_logmass) {
+    void* q = nullptr;
+    const size_t bytes = ((size_t)m->cfg.max_batch * PHRASE_MASS_LD + MAX_ROWS) * 4;
+    if (hipMalloc(&q, bytes) != hipSuccess) { (void)hipGetLastError(); set_error("phrase_mass: out of device memory (%zu bytes)", bytes); return WIS_E_NOMEM; }
+    m->allocs.push_back(q); m->bytes += bytes;
+    m->d_logmass = static_cast<float*>(q); m->d_phr_mass = m->d_logmass + (size_t)m->cfg.max_batch * PHRASE_MASS_LD;
+  }
+  WIS_HIP_CHECK(hipMemset2DAsync(m->d_logmass, (size_t)PHRASE_MASS_LD * 4, 0xFF, (size_t)m->phr_n * 4, (size_t)B, st));
+  return WIS_OK;
+}
+// ... and behind its search: the sums along the results' paths (n results per utterance, where the beam step left them), left in device memory for
+// wis_last_phrase_mass
+static int phrase_mass_end(wis_model* m, int B, int n, int max_new, hipStream_t st) {
+  WIS_RET(launch_phrase_mass_gather(st, m->bs.out_ids, m->bs.out_len, m->bs.out_score, m->d_trie, m->phr_n, m->d_logmass, PHRASE_MASS_LD, B, n, max_new, m->d_phr_mass));
+  m->phr_mass_B = B; m->phr_mass_n = n;
   return WIS_OK;
 }
 // everything a stage needs to know about the call: built once (make_gen_ctx), read-only afterwards
@@ -249,7 +273,8 @@ static int sampling_tail(const SampleCtx& g, LogitRows rows, int flags) {
   const int lr_b = rows.b, lr_j = rows.j, lr_off = rows.off;
   unsigned long long* prof = (WIS_TAPS && (flags & TAIL_TAPS)) ? m->d_prof + (size_t)c.n_dec_layers * 8 * 16 : nullptr;
   if (g.rep()) WIS_RET(launch_rep_rules(st, m->logits, m->bs, g.B, g.sc, g.rep_pen, g.rep_ngram, lr_b, lr_j, lr_off));
-  if (g.phrases) WIS_RET(launch_phrase_rules(st, m->logits, m->bs, g.B, g.sc, m->d_trie, m->phr_n, lr_b, lr_j, lr_off));
+  if (g.phrases && !g.phr_mass) WIS_RET(launch_phrase_rules(st, m->logits, m->bs, g.B, g.sc, m->d_trie, m->phr_n, lr_b, lr_j, lr_off));
+  if (g.phrases && g.phr_mass) WIS_RET(launch_phrase_rules_mass(st, m->logits, m->bs, g.B, g.sc, m->d_trie, m->phr_n, lr_b, lr_j, lr_off, g.bias_all, m->bias_begin, m->d_logmass, PHRASE_MASS_LD));
   if (g.ts) WIS_RET(launch_ts_rules(st, m->logits, g.bias_all, m->bias_begin, m->bs, g.B, g.sc, c.no_timestamps, g.ts_max_init, lr_b, lr_j, lr_off, m->ts_desc));
   if (g.sampling()) {      // statistics (whole vocabulary: perturbed) -> sample step; every row continues itself: the cache moves only behind the prompt pass
     WIS_RET(launch_logit_stats(st, m->logits, g.bias_all, m->bias_begin, m->bs.step_u, m->st_max, m->st_sum, m->st_val, m->st_idx, g.B, g.sc, lr_b, lr_j, lr_off, nullptr,
@@ -632,7 +657,7 @@ struct StepGraph {
     key.timestamps = g.ts ? 1 : 0; key.max_init = g.ts ? g.ts_max_init : 0;
     key.rep_pen = g.rep_pen == 1.f ? 0.f : g.rep_pen; key.rep_ngram = g.rep_ngram;      // (off: the zeroes of a key that never knew the fields)
     key.samp_topk = g.sp.topk; key.samp_T = g.sampling() ? g.sp.T : 0.f; key.n_hyp = g.n_res > 1 ? g.n_res : 0;      // (the seeds are device memory: no part of the key)
-    key.phrases = g.phrases ? 1 : 0;      // (the set is device memory behind a pointer that never changes: installing another needs no new graph)
+    key.phrases = g.phrases ? (g.phr_mass ? 2 : 1) : 0;      // (the set is device memory behind a pointer that never changes: installing another needs no new graph)
     auto it = m->graphs.find(key);
     if (it != m->graphs.end()) { *out = it->second; return WIS_OK; }
     hipGraph_t graph = nullptr; hipGraphExec_t ge = nullptr;
@@ -821,12 +846,13 @@ static int generate_impl(wis_model_t* m, const float* input, int B, const int32_
                  const uint64_t* seeds = nullptr, bool single = true, const int32_t* plen_v = nullptr) {
   *retry = false;
   if (accepted) *accepted = 0;
-  m->nsp_B = 0;
+  m->nsp_B = 0; m->phr_mass_B = 0;
   WIS_HIP_CHECK(hipSetDevice(m->device));
   SpinClaim claim(m, B);
   GenCtx g;
   WIS_RET(make_gen_ctx(m, input, B, prompt, P, o, draft, n_draft, draft_org, seeds, single, plen_v, &g));
   hipStream_t st = g.st;
+  if (g.phr_mass) WIS_RET(phrase_mass_begin(m, B, st));
   WIS_RET(stage_search(g));
   WIS_RET(front_half(g));
 
@@ -863,6 +889,7 @@ static int generate_impl(wis_model_t* m, const float* input, int B, const int32_
   record_timing(g, lr);
   if (lr.steps > lr.needed) { claim.defer(st); m->overrun_left = true; }      // an over-run step is still queued: its combiners keep their share of the spin budget until it has run
   if (g.nsp()) m->nsp_B = B;
+  if (g.phr_mass) WIS_RET(phrase_mass_end(m, B, g.n_res, g.max_new, st));      // (behind an over-run step too: a finished utterance's rows write no slot)
   return WIS_OK;
 }
 
@@ -884,6 +911,7 @@ static int generate_with_retry(const char* who, wis_model_t* m, const float* inp
 static int debug_search_impl(const char* who, wis_model_t* m, const float* logits, int n_steps, int B, const wis_gen_opts_t* o, const uint64_t* seeds, const uint32_t* noise,
                              bool single, int32_t* out_ids, int32_t* out_len, float* out_score, int32_t* out_finish_step, int32_t* out_parent) {
   WIS_HIP_CHECK(hipSetDevice(m->device));
+  m->phr_mass_B = 0;
   const wis_config_t& c = m->cfg;
   SampleCtx g;      // a search over given logits: a one-token prompt
   int beam = 1;     // rows per utterance: beams, or the samples of a sampled decode
@@ -894,6 +922,7 @@ static int debug_search_impl(const char* who, wis_model_t* m, const float* logit
   WIS_RET(resolve_phrase_opts(m, o, false, &g, &max_new));
   if (max_new > n_steps) { set_error("%s: %d steps of logits for max_new_tokens %d", who, n_steps, max_new); return WIS_E_ARG; }
   hipStream_t st = m->st;
+  if (g.phr_mass) WIS_RET(phrase_mass_begin(m, B, st));
   const int Mrows = B * beam, V = c.n_vocab;
   float patience;
   WIS_RET(resolve_rep_opts(o, &g));
@@ -925,6 +954,7 @@ static int debug_search_impl(const char* who, wis_model_t* m, const float* logit
   }
   for (int b = 0; b < B; ++b) if (fin[b] < 0) { set_error("%s: utterance %d did not finish within %d steps", who, b, max_new); return WIS_E_STATE; }
   WIS_RET(results_from_device(m, B * g.n_res, max_new, out_ids, out_len, out_score));
+  if (g.phr_mass) WIS_RET(phrase_mass_end(m, B, g.n_res, max_new, st));
   if (out_finish_step) for (int b = 0; b < B; ++b) out_finish_step[b] = fin[b];
   return WIS_OK;
 }

@@ -210,6 +210,15 @@ int launch_rep_rules(hipStream_t st, float* logits, const BeamState& bs, int B, 
 // {token, first child record, children, child ends a phrase}, record 0 the root's pseudo-edge (include/wis_hip.h has the layout's rules)
 constexpr int PHRASE_MAX_RECORDS = 65535, PHRASE_MAX_CHILDREN = 4096, PHRASE_MAX_DEPTH = 32;
 int launch_phrase_rules(hipStream_t st, float* logits, const BeamState& bs, int B, const SampleCfg& cfg, const int4* trie, int n_rec, int lr_b, int lr_j, int lr_off);
+// ... with the in-grammar mass (dec_kernels.hip phrase_rules_mass_kernel, in launch_phrase_rules' place when wis_gen_opts_t::phrase_mass is on): the
+// same mask, and per live row with a finite cumulative score (bs.cum; null: every row) one float at logmass[b lm_ld + the node's record index] - the
+// log of the share of the row's softmax, under the bias lists launch_logit_stats applies, that the node allows.  lm_ld >= n_rec floats per utterance
+int launch_phrase_rules_mass(hipStream_t st, float* logits, const BeamState& bs, int B, const SampleCfg& cfg, const int4* trie, int n_rec, int lr_b, int lr_j, int lr_off,
+                             const float* bias_all, const float* bias_begin, float* logmass, int lm_ld);
+// ... and, behind the search, per result r = b n + i (ids [B n][id_ld], len / score [B n]; score may be null) the sum of the slots along its path -> out [B n]
+int launch_phrase_mass_gather(hipStream_t st, const int* ids, const int* len, const float* score, const int4* trie, int n_rec, const float* logmass, int lm_ld,
+                              int B, int n, int id_ld, float* out);
+constexpr int PHRASE_MASS_LD = 65536;      // floats per utterance of a handle's logmass buffer (>= PHRASE_MAX_RECORDS)
 // probability of <|nospeech|> under the full-vocabulary softmax of each utterance's <|startoftranscript|> row (b * rs + r0)
 int launch_no_speech(hipStream_t st, const float* logits, int ld, int B, int rs, int r0, int V, int ns, float* out);
 // ... with the row of every utterance in device memory (rows [B]; a value outside [0, rs): utterance b is not in this pass, out[b] stays as it is)

@@ -1173,6 +1173,17 @@ int wis_last_no_speech_prob(wis_model_t* m, int B, float* out) {
   return WIS_OK;
 }
 
+int wis_last_phrase_mass(wis_model_t* m, int B, int n, float* out) {
+  if (!m || !out || B < 1 || n < 1) { set_error("wis_last_phrase_mass: bad argument"); return WIS_E_ARG; }
+  WIS_ENTER(m, "wis_last_phrase_mass")
+  if (m->phr_mass_B == 0) { set_error("wis_last_phrase_mass: the last search on this handle did not set phrase_mass"); return WIS_E_STATE; }
+  if (B > m->phr_mass_B || n != m->phr_mass_n) { set_error("wis_last_phrase_mass: %d utterances x %d results asked, the last call had %d x %d", B, n, m->phr_mass_B, m->phr_mass_n); return WIS_E_ARG; }
+  WIS_HIP_CHECK(hipSetDevice(m->device));
+  WIS_HIP_CHECK(hipMemcpyAsync(out, m->d_phr_mass, (size_t)B * n * 4, hipMemcpyDeviceToHost, m->st));
+  WIS_HIP_CHECK(hipStreamSynchronize(m->st));
+  return WIS_OK;
+}
+
 int wis_last_trajectory(wis_model_t* m, int b, int32_t* tok, int32_t* org, int cap_steps, int32_t* n_steps) {
   if (!m || !tok || !org || !n_steps || cap_steps < 0) { set_error("wis_last_trajectory: bad argument"); return WIS_E_ARG; }
   WIS_ENTER(m, "wis_last_trajectory")

@@ -45,7 +45,7 @@ struct GraphKey {
   int timestamps, max_init;      // the timestamp form of the step (ts_rules_kernel ahead of logit_stats_kernel<true>) and its first-timestamp cap
   float rep_pen; int rep_ngram;  // rep_rules_kernel at the head of the tail (both 0: off, no such launch)
   int samp_topk; float samp_T; int n_hyp;      // sampled decode (sample_step_kernel in beam_step_kernel's place) / results per utterance; all 0: off, one result
-  int phrases;                   // phrase_rules_kernel behind rep_rules_kernel (0: off, no such launch; the set itself is device memory: no part of the key)
+  int phrases;                   // phrase_rules_kernel behind rep_rules_kernel (0: off, no such launch; 2: phrase_rules_mass_kernel in its place; the set itself is device memory: no part of the key)
   bool operator<(const GraphKey& o) const { return memcmp(this, &o, sizeof(GraphKey)) < 0; }
 };
 
@@ -190,6 +190,11 @@ struct wis_model {
   // allocated with the other buffers: the pointer a captured step carries never changes, installing a set is a copy), its record count (0: no set)
   // and its longest phrase; tok_flags: per token id, bit 0 = in the model's suppress_ids, bit 1 = in suppress_ids_begin (what a set is validated against)
   int4* d_trie = nullptr; int phr_n = 0, phr_depth = 0;
+  // wis_gen_opts_t::phrase_mass: per (utterance, trie record) the log in-grammar mass of the step that visited the node, [max_batch][PHRASE_MASS_LD] f32,
+  // then [MAX_ROWS] f32 for the gathered sums per result; allocated on the handle's first call with the option on (generate.hip phrase_mass_begin) and
+  // never moved - captured steps hold the address; a clone has its own.  phr_mass_B / _n: batch and results per utterance of the last call when that
+  // call computed the mass, else 0 (wis_last_phrase_mass answers WIS_E_STATE)
+  float* d_logmass = nullptr; float* d_phr_mass = nullptr; int phr_mass_B = 0, phr_mass_n = 0;
   std::vector<unsigned char> tok_flags;
 };
 

@@ -714,6 +714,29 @@ int wis_op_phrase_rules(int device, float* logits, int n_vocab, int n_vocab_pad,
   return t.finish(launch_phrase_rules(t.st, logits, bs, B, sc, reinterpret_cast<const int4*>(trie), n_rec, lr_b, lr_j, lr_off));
 }
 
+// ... with the in-grammar mass, and the gather of finished results' sums (tests/test_gpu_phrase_mass_ops.py); every row counts as live (no cum)
+int wis_op_phrase_mass(int device, float* logits, int n_vocab, int n_vocab_pad, int eot, const int32_t* trie, int n_rec, const int32_t* alive,
+                       const int32_t* step_u, const int32_t* done, int B, int beam, int max_new, int lr_b, int lr_j, int lr_off,
+                       const float* bias_all, const float* bias_begin, int suppress_blank, float* logmass) {
+  Tap t(device, "wis_op_phrase_mass"); WIS_RET(t.rc);
+  if (!logits || !trie || !alive || !step_u || !done || !bias_begin || !logmass || n_rec < 1 || n_rec > PHRASE_MAX_RECORDS || n_vocab < 1 || n_vocab > 65536 ||
+      n_vocab_pad < n_vocab || eot < 0 || eot >= n_vocab || B < 1 || beam < 1 || beam > MAX_R || B * beam > MAX_ROWS || max_new < 1 || max_new > MAX_STEPS ||
+      lr_b < 0 || lr_j < 0 || lr_off < 0) {
+    set_error("wis_op_phrase_mass: bad argument"); return WIS_E_ARG; }
+  SampleCfg sc; memset(&sc, 0, sizeof(sc));
+  sc.n_vocab = n_vocab; sc.n_vocab_pad = n_vocab_pad; sc.eot = eot; sc.beam = beam; sc.max_new = max_new; sc.suppress_blank = suppress_blank ? 1 : 0;
+  BeamState bs; memset(&bs, 0, sizeof(bs));
+  bs.alive = const_cast<int*>(alive); bs.step_u = const_cast<int*>(step_u); bs.done = const_cast<int*>(done);
+  return t.finish(launch_phrase_rules_mass(t.st, logits, bs, B, sc, reinterpret_cast<const int4*>(trie), n_rec, lr_b, lr_j, lr_off, bias_all, bias_begin, logmass, n_rec));
+}
+int wis_op_phrase_mass_gather(int device, const int32_t* ids, const int32_t* len, const float* score, const int32_t* trie, int n_rec,
+                              const float* logmass, int B, int n, int id_ld, float* out) {
+  Tap t(device, "wis_op_phrase_mass_gather"); WIS_RET(t.rc);
+  if (!ids || !len || !trie || !logmass || !out || n_rec < 1 || n_rec > PHRASE_MAX_RECORDS || B < 1 || n < 1 || B * n > MAX_ROWS || id_ld < 1 || id_ld > MAX_STEPS) {
+    set_error("wis_op_phrase_mass_gather: bad argument"); return WIS_E_ARG; }
+  return t.finish(launch_phrase_mass_gather(t.st, ids, len, score, reinterpret_cast<const int4*>(trie), n_rec, logmass, n_rec, B, n, id_ld, out));
+}
+
 // ---- the resampler's kernel alone (tests/test_gpu_resample_ops.py): one launch of csrc/resample.hip on a caller-supplied slice of a longer signal
 int wis_op_resample_segment(int device, const float* x_slice, int64_t n_slice, int64_t k_base, int64_t n_in_total, int64_t m0, int64_t count,
                             int up, int down, float* out) {

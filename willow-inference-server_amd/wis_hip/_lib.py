@@ -43,7 +43,8 @@ class GenOpts(C.Structure):
                 ("patience", C.c_float), ("suppress_blank", C.c_int32), ("suppress_default", C.c_int32),
                 ("fixed_new_tokens", C.c_int32), ("queue_depth", C.c_int32), ("timestamps", C.c_int32), ("max_initial_timestamp_index", C.c_int32),
                 ("no_speech_prob", C.c_int32), ("repetition_penalty", C.c_float), ("no_repeat_ngram_size", C.c_int32),
-                ("sampling_topk", C.c_int32), ("sampling_temperature", C.c_float), ("num_hypotheses", C.c_int32), ("phrases", C.c_int32)]
+                ("sampling_topk", C.c_int32), ("sampling_temperature", C.c_float), ("num_hypotheses", C.c_int32), ("phrases", C.c_int32),
+                ("phrase_mass", C.c_int32)]
 
 
 class Timing(C.Structure):
@@ -115,6 +116,7 @@ SYMBOLS = [
     ("wis_debug_logits_rows", _i, [_vp, _vp, _i, _i, C.POINTER(C.c_int32), _i, _i, _fp]),
     ("wis_model_set_alignment_heads", _i, [_vp, C.POINTER(C.c_int32), _i]),
     ("wis_model_set_phrases", _i, [_vp, C.POINTER(C.c_int32), _i]),
+    ("wis_last_phrase_mass", _i, [_vp, _i, _i, _fp]),
     ("wis_align", _i, [_vp, _vp, _i, _i, C.POINTER(C.c_int32), _i, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), _i,
                        C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), _fp]),
     ("wis_debug_align_matrix", _i, [_vp, _vp, _i, _i, C.POINTER(C.c_int32), _i, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), _i, _fp]),
@@ -170,6 +172,8 @@ SYMBOLS = [
     ("wis_op_lang_probs", _i, [_i, _vp, _i, _vp, _i, _vp, _i]),
     ("wis_op_greedy_rows", _i, [_i, _vp, _i, _i, _i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
     ("wis_op_phrase_rules", _i, [_i, _vp, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i]),
+    ("wis_op_phrase_mass", _i, [_i, _vp, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _i, _vp]),
+    ("wis_op_phrase_mass_gather", _i, [_i, _vp, _vp, _vp, _vp, _i, _vp, _i, _i, _i, _vp]),
     ("wis_sv_create", _i, [C.POINTER(SvConfig), _vp, _sz, _i, C.POINTER(Tensor), _i, _i, C.POINTER(_vp)]),
     ("wis_sv_destroy", None, [_vp]),
     ("wis_sv_device_bytes", _sz, [_vp]),

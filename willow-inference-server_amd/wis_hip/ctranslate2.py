@@ -136,11 +136,12 @@ class StorageView:
 
 
 class WhisperGenerationResult:
-    def __init__(self, sequences_ids, scores, no_speech_prob=0.0):
+    def __init__(self, sequences_ids, scores, no_speech_prob=0.0, phrase_logmass=None):
         self.sequences_ids = sequences_ids
         self.sequences = [[str(t) for t in s] for s in sequences_ids]
         self.scores = scores
         self.no_speech_prob = no_speech_prob
+        self.phrase_logmass = phrase_logmass      # generate(..., phrases=..., return_phrase_mass=True): one float per hypothesis, else None
 
     def __repr__(self):
         return f"WhisperGenerationResult(sequences_ids={self.sequences_ids}, scores={self.scores})"
@@ -334,27 +335,30 @@ class ConstrainedOptions(DecodeOptions):
     with these arguments would have, max_new_tokens capped at the longest phrase + 1 - that carries the call's phrase set beside it:
     `phrase_trie` (int32 [n][4], weights.build_phrase_trie) and `phrase_digest` (its SHA-256).  The digest takes part in equality and hash, the
     type too: two calls share a device batch exactly when their options AND their phrase sets are equal, and a constrained record never equals a
-    plain one.  The batch runner installs the set on the replica when the replica's current digest differs (_generate_chunk)."""
+    plain one.  The batch runner installs the set on the replica when the replica's current digest differs (_generate_chunk).
+    `phrase_mass` (return_phrase_mass=True: the engine also computes every result's in-grammar mass, wis_gen_opts_t::phrase_mass) is carried the
+    same way and takes part in equality and hash: calls that differ in it never share a device batch."""
 
-    def __new__(cls, base, trie, digest):
+    def __new__(cls, base, trie, digest, phrase_mass=False):
         self = tuple.__new__(cls, base)
-        self.phrase_trie, self.phrase_digest = trie, digest
+        self.phrase_trie, self.phrase_digest, self.phrase_mass = trie, digest, bool(phrase_mass)
         return self
 
     def __eq__(self, other):
-        return type(other) is ConstrainedOptions and tuple.__eq__(self, other) and self.phrase_digest == other.phrase_digest
+        return (type(other) is ConstrainedOptions and tuple.__eq__(self, other) and self.phrase_digest == other.phrase_digest
+                and self.phrase_mass == other.phrase_mass)
 
     def __ne__(self, other):
         return not self == other
 
     def __hash__(self):
-        return hash((tuple.__hash__(self), self.phrase_digest))
+        return hash((tuple.__hash__(self), self.phrase_digest, self.phrase_mass))
 
     def _replace(self, **kw):
-        return ConstrainedOptions(DecodeOptions(*self)._replace(**kw), self.phrase_trie, self.phrase_digest)
+        return ConstrainedOptions(DecodeOptions(*self)._replace(**kw), self.phrase_trie, self.phrase_digest, self.phrase_mass)
 
     def __reduce__(self):
-        return (ConstrainedOptions, (DecodeOptions(*self), self.phrase_trie, self.phrase_digest))
+        return (ConstrainedOptions, (DecodeOptions(*self), self.phrase_trie, self.phrase_digest, self.phrase_mass))
 
 
 def _phrase_set(phrases, special, decode_config):
@@ -393,6 +397,7 @@ def _gen_opts(opts):
     if opts.sampling_topk != 0 or opts.num_hypotheses > 1:
         o.sampling_topk, o.sampling_temperature, o.num_hypotheses = int(opts.sampling_topk), float(opts.sampling_temperature), int(opts.num_hypotheses)
     o.phrases = int(getattr(opts, "phrase_trie", None) is not None)
+    o.phrase_mass = int(bool(getattr(opts, "phrase_mass", False)))
     return o
 
 
@@ -469,6 +474,11 @@ def _generate_chunk(r, mel, prompts, opts, *rest, device_ptr=None, seeds=None):
     # (a constrained search whose set reaches fewer than n phrases fills up with -inf hypotheses: those are dropped)
     keep = [[j for j in range(n) if trie is None or scores[b, j] != -np.inf] for b in range(B)]
     out = [WhisperGenerationResult([ids[b, j, :lens[b, j]].tolist() for j in keep[b]], [float(scores[b, j]) for j in keep[b]], float(nsp[b])) for b in range(B)]
+    if getattr(opts, "phrase_mass", False):      # the in-grammar mass of every result, in the engine's (unsorted) batch order like everything above
+        mass = np.zeros((B, n), np.float32)
+        _lib.check(lib.wis_last_phrase_mass(r.handle, B, n, mass.ctypes.data_as(C.POINTER(C.c_float))))
+        for b in range(B):
+            out[b].phrase_logmass = [float(mass[b, j]) for j in keep[b]]
     if acc is not None:
         out[0].accepted_draft_tokens = int(acc.value)      # tokens (beam 1) or search steps (beam > 1) of the draft the final decode kept
     if opts.return_trajectory:
@@ -907,7 +917,7 @@ class Whisper:
                  repetition_penalty=1, no_repeat_ngram_size=0, max_length=448, return_scores=False, return_no_speech_prob=False,
                  max_initial_timestamp_index=50, suppress_blank=True, suppress_tokens=(-1,), sampling_topk=1,
                  sampling_temperature=1, fixed_new_tokens=0, input_kind=_lib.WIS_IN_MEL_HOST, draft_tokens=None, draft_trajectory=None,
-                 return_trajectory=False, sampling_seed=None, ragged_prompts=False, phrases=None):
+                 return_trajectory=False, sampling_seed=None, ragged_prompts=False, phrases=None, return_phrase_mass=False):
         """`draft_tokens` (one utterance, beam_size 1): the ids of an earlier hypothesis for this audio - wis_generate_draft verifies them in
         multi-row passes and decodes on behind the accepted prefix; the result is the greedy decode of THESE features either way.
         `draft_trajectory` (one utterance, beam_size > 1): `(tok, org)` as an earlier result's `.trajectory` gives it (`return_trajectory=True`) -
@@ -938,7 +948,11 @@ class Whisper:
         phrases, scored by the model's log-probabilities renormalised over what the list allows at each step (include/wis_hip.h states the rule);
         `num_hypotheses=n` in a beam search returns the n best phrases, best first (fewer when the search reached fewer).  A phrase holds 1 .. 32 text
         tokens outside the model's suppress lists (weights.build_phrase_trie; a ValueError names the phrase).  Not with timestamps, sampling,
-        `fixed_new_tokens` or drafts (ValueError).  Calls share a device batch exactly when their options and their phrase sets are equal."""
+        `fixed_new_tokens` or drafts (ValueError).  Calls share a device batch exactly when their options and their phrase sets are equal.
+        `return_phrase_mass=True` (with `phrases`; without: ValueError) fills `phrase_logmass`, one float per returned hypothesis: the log of the share
+        of the model's probability that the list allowed, summed over the phrase's steps and its <|endoftext|> - log P_unconstrained(phrase) -
+        log P_constrained(phrase), near 0 when the audio says the phrase, strongly negative when the mask forced it (include/wis_hip.h, THE PHRASE
+        MASS RULE).  Ids and scores are those of the call without it."""
         enc = self._encoder_input(features, input_kind)
         if enc is not None:
             n_utt = len(enc[2]) if enc[0] == _lib.WIS_IN_ENC_DEV else enc[1].shape[0]
@@ -949,7 +963,8 @@ class Whisper:
                                          suppress_blank=suppress_blank, suppress_default=list(suppress_tokens) == [-1], sampling_topk=sampling_topk,
                                          sampling_temperature=sampling_temperature, fixed_new_tokens=fixed_new_tokens, draft_tokens=draft_tokens,
                                          draft_trajectory=draft_trajectory, return_trajectory=return_trajectory, ragged_prompts=ragged_prompts,
-                                         pool_long_prompts=getattr(self, "batch_ragged_prompts", False), phrases=phrases)
+                                         pool_long_prompts=getattr(self, "batch_ragged_prompts", False), phrases=phrases,
+                                         return_phrase_mass=return_phrase_mass)
         seeds = _seeds(opts, sampling_seed, len(prompts))
         if enc is not None and enc[0] == _lib.WIS_IN_ENC_DEV:
             # every row carries the block its address points into: the rows themselves keep the device memory allocated until _run_batch has returned
@@ -960,7 +975,8 @@ class Whisper:
 
     def _decode_options(self, features, prompts, *, input_kind, n_utt=1, beam_size, patience, num_hypotheses, length_penalty, repetition_penalty, no_repeat_ngram_size,
                         max_length, return_no_speech_prob, max_initial_timestamp_index, suppress_blank, suppress_default, sampling_topk, sampling_temperature,
-                        fixed_new_tokens, draft_tokens, draft_trajectory, return_trajectory, ragged_prompts=False, pool_long_prompts=False, phrases=None):
+                        fixed_new_tokens, draft_tokens, draft_trajectory, return_trajectory, ragged_prompts=False, pool_long_prompts=False, phrases=None,
+                        return_phrase_mass=False):
         """Every check of a decode call, for `generate` (features: host arrays, one prompt each) and `generate_from_device` (features None: ONE
         utterance already on the device) -> (its DecodeOptions, the checked host features or None).  The engine's capacity limits are request
         errors (ValueError -> HTTP 400 in wis_hip.server), not internal ones.  ragged_prompts: the prompts may differ in length (the key then
@@ -1015,6 +1031,8 @@ class Whisper:
         opts = DecodeOptions(RAGGED_PROMPT if pooled else P, int(beam_size), min(max_length // 2, max_length - P), float(length_penalty), float(patience), bool(suppress_blank),
                              bool(suppress_default), int(fixed_new_tokens), int(input_kind), draft, bool(return_trajectory), timestamps,
                              mi if timestamps else 50, bool(return_no_speech_prob), rep_p, rep_n, s_k, s_T, s_n)
+        if return_phrase_mass and phrases is None:
+            raise ValueError("return_phrase_mass needs phrases (the mass is that of the call's phrase list)")
         if phrases is not None:
             if timestamps:
                 raise ValueError("phrases cannot be combined with timestamps (a start sequence without <|notimestamps|>)")
@@ -1027,7 +1045,7 @@ class Whisper:
             trie, digest, longest = _phrase_set(phrases, self.special, getattr(self, "decode_config", None) or {})
             if opts.max_new_tokens < longest + 1:
                 raise ValueError(f"max_length {max_length} leaves {opts.max_new_tokens} steps behind a prompt of {P} tokens: the longest phrase needs {longest + 1}")
-            opts = ConstrainedOptions(opts._replace(max_new_tokens=longest + 1), trie, digest)
+            opts = ConstrainedOptions(opts._replace(max_new_tokens=longest + 1), trie, digest, bool(return_phrase_mass))
         return opts, mel
 
     def load(self, device=None):
@@ -1055,7 +1073,8 @@ class Whisper:
     def generate_from_device(self, device, mel_device_ptr, prompt, *, beam_size=5, max_length=448, length_penalty=1, patience=1,
                              suppress_blank=True, fixed_new_tokens=0, replica=None, draft_tokens=None, draft_trajectory=None, return_trajectory=False,
                              repetition_penalty=1, no_repeat_ngram_size=0, num_hypotheses=1, sampling_topk=1, sampling_temperature=1, sampling_seed=None,
-                             return_scores=False, return_no_speech_prob=False, max_initial_timestamp_index=50, phrases=None):
+                             return_scores=False, return_no_speech_prob=False, max_initial_timestamp_index=50, phrases=None,
+                             return_phrase_mass=False):
         """One utterance whose log-mel features ALREADY live in HBM on `device` (f32 [n_mels][3000] at `mel_device_ptr`, e.g. an
         audio.MelStream after finish()): WIS_IN_MEL_DEV - nothing is staged through the host.  Goes through the micro-batcher bound
         to that DEVICE: any replica of the GPU can read the features, so concurrent windows of several streaming sessions on one GPU
@@ -1063,7 +1082,8 @@ class Whisper:
         session's own replica: sessions pinned to different replicas of a GPU never shared a batch).
         As in `generate`: a start sequence without <|notimestamps|> (`timestamp_prompt`) decodes under Whisper's timestamp rules with
         `max_initial_timestamp_index`, `return_no_speech_prob=True` fills `no_speech_prob`, and drafts cannot be combined with either;
-        `return_scores` is accepted for symmetry (the scores are always filled); `phrases` restricts the search to a phrase list, as in `generate`."""
+        `return_scores` is accepted for symmetry (the scores are always filled); `phrases` restricts the search to a phrase list and
+        `return_phrase_mass` fills `phrase_logmass`, as in `generate`."""
         # `replica`: the replica the caller holds (a streaming session pins itself to the least-loaded one, acquire_replica: the load
         # accounting that spreads sessions over GPUs); it only has to live on the features' device
         r = replica if replica is not None else self.replica_on(device)
@@ -1074,7 +1094,8 @@ class Whisper:
                                        no_repeat_ngram_size=no_repeat_ngram_size, max_length=max_length, return_no_speech_prob=return_no_speech_prob,
                                        max_initial_timestamp_index=max_initial_timestamp_index, suppress_blank=suppress_blank, suppress_default=True,
                                        sampling_topk=sampling_topk, sampling_temperature=sampling_temperature, fixed_new_tokens=fixed_new_tokens,
-                                       draft_tokens=draft_tokens, draft_trajectory=draft_trajectory, return_trajectory=return_trajectory, phrases=phrases)
+                                       draft_tokens=draft_tokens, draft_trajectory=draft_trajectory, return_trajectory=return_trajectory, phrases=phrases,
+                                       return_phrase_mass=return_phrase_mass)
         row = (int(mel_device_ptr), [int(t) for t in prompt], _seeds(opts, sampling_seed, 1)[0])
         return self._batcher.submit(opts, [row], affinity=("device", device))[0]
 

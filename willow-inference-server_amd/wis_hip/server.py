@@ -22,6 +22,7 @@ WebRTC (`/api/rtc/asr`), TTS, nginx auth and the static sites are not re-hosted 
 import asyncio
 import io
 import logging
+import math
 import os
 import wave
 from concurrent.futures import ThreadPoolExecutor
@@ -101,6 +102,12 @@ def parse_multipart(body, content_type, field="audio_file"):
 
 class BadRequest(ValueError):
     """A request parameter the engine cannot serve -> HTTP 400 with the message."""
+
+
+def _json_matches(matches):
+    """do_whisper's `matches` for a JSON body: a logmass / in_grammar that is no finite number (-inf: the list allowed nothing of the model's
+    probability; NaN: a step the search never scored) is sent as null."""
+    return [{k: (None if isinstance(v, float) and not math.isfinite(v) else v) for k, v in m.items()} for m in matches]
 
 
 def _as_bool(v, default):
@@ -226,6 +233,27 @@ def create_app(models=None, settings=None, max_workers=None, sv=None):
             raise BadRequest(f"Invalid phrase_nbest {nbest!r}")
         if nbest is not None and not 1 <= nbest <= s.max_beam:
             raise BadRequest(f"phrase_nbest {nbest} outside 1..{s.max_beam}")
+        # the out-of-grammar signal: phrase_mass=true | false, phrase_threshold=0.2 (a number in [0, 1]), phrase_fallback=true | false; absent or empty =
+        # the settings' values; anything else = 400
+        pm = {}
+        for name in ("phrase_mass", "phrase_fallback"):
+            v = q.get(name)
+            if v in (None, ""):
+                pm[name] = None
+            elif str(v).strip().lower() in ("1", "true", "yes", "on"):
+                pm[name] = True
+            elif str(v).strip().lower() in ("0", "false", "no", "off"):
+                pm[name] = False
+            else:
+                raise BadRequest(f"Invalid {name} {v!r}: true or false")
+        pthr = q.get("phrase_threshold")
+        try:
+            pthr = float(pthr) if pthr not in (None, "") else None
+        except ValueError:
+            raise BadRequest(f"Invalid phrase_threshold {pthr!r}")
+        if pthr is not None and not 0.0 <= pthr <= 1.0:      # (a NaN fails both comparisons)
+            raise BadRequest(f"phrase_threshold {pthr!r} outside [0, 1]")
+        pm["phrase_threshold"] = pthr
         # recordings over 30 s: long_form=seek | chunk, condition_on_previous_text=, no_speech_threshold= (absent: the settings' values); a bad value = 400
         lf = q.get("long_form") or None
         if lf is not None and lf not in ("seek", "chunk"):
@@ -245,7 +273,7 @@ def create_app(models=None, settings=None, max_workers=None, sv=None):
         if nst is not None and nst != nst:
             raise BadRequest("Invalid no_speech_threshold: not a number")
         return dict(model=model, beam_size=beam, repetition_penalty=rp, **prompts, no_repeat_ngram_size=ng, temperatures=temps, best_of=best_of,
-                    long_form=lf, condition_on_previous_text=cond, no_speech_threshold=nst, phrases=phrases, phrase_nbest=nbest,
+                    long_form=lf, condition_on_previous_text=cond, no_speech_threshold=nst, phrases=phrases, phrase_nbest=nbest, **pm,
                     detect_language=_as_bool(q.get("detect_language"), s.detect_language), force_language=q.get("force_language") or None,
                     translate=_as_bool(q.get("translate"), False), timestamps=_as_bool(q.get("timestamps"), False),
                     word_timestamps=_as_bool(q.get("word_timestamps"), False))
@@ -256,7 +284,8 @@ def create_app(models=None, settings=None, max_workers=None, sv=None):
         if p["word_timestamps"]:                                  # (word times imply segment times; no vocabulary is a 400, and so is audio over 30 s without long_form=seek)
             kw = {"word_timestamps": True}
         kw.update({k: p[k] for k in ("repetition_penalty", "no_repeat_ngram_size", "temperatures", "best_of", "initial_prompt", "prefix", "long_form",
-                                         "condition_on_previous_text", "no_speech_threshold", "phrases", "phrase_nbest") if p[k] is not None})      # (absent: do_whisper takes the settings' values)
+                                         "condition_on_previous_text", "no_speech_threshold", "phrases", "phrase_nbest", "phrase_mass", "phrase_threshold",
+                                         "phrase_fallback") if p[k] is not None})      # (absent: do_whisper takes the settings' values)
         return await loop.run_in_executor(pool, lambda: do_whisper(audio_file, p["model"], p["beam_size"], "transcribe", p["detect_language"],
                                                                    p["force_language"], p["translate"], models=get_models(), **kw))
 
@@ -303,7 +332,9 @@ def create_app(models=None, settings=None, max_workers=None, sv=None):
         if p["timestamps"] or p["word_timestamps"]:
             out["segments"] = res.segments
         if getattr(res, "matches", None) is not None:      # a phrase-constrained request: the ranked phrases
-            out["matches"] = res.matches
+            out["matches"] = _json_matches(res.matches)
+            if getattr(res, "matched", None) is not None:      # (a request with a phrase_threshold)
+                out["matched"] = bool(res.matched)
         return JSONResponse(content=out)
 
     @app.post("/api/willow")
@@ -365,7 +396,9 @@ def create_app(models=None, settings=None, max_workers=None, sv=None):
         if p["timestamps"] or p["word_timestamps"]:
             out["segments"] = res.segments
         if getattr(res, "matches", None) is not None:      # a phrase-constrained request: the ranked phrases
-            out["matches"] = res.matches
+            out["matches"] = _json_matches(res.matches)
+            if getattr(res, "matched", None) is not None:      # (a request with a phrase_threshold)
+                out["matched"] = bool(res.matched)
         if voice_auth:
             out["voice_auth"] = sv_results
             out["speaker_status"] = speaker_status

@@ -97,6 +97,12 @@ class APISettings:
     # restricted to that list and answers with its best phrase (`matches` in the response, `phrase_nbest` of them).  Empty = off.  A file that cannot
     # be read fails the server's start
     phrases_file: str = ""
+    # the out-of-grammar signal of phrase-constrained requests (do_whisper's options of the same names): phrase_mass adds `logmass` / `in_grammar` to every
+    # match; a phrase_threshold in (0, 1] adds `matched` (0 = no threshold - none is shipped: a useful one is calibrated on the deployment's checkpoint
+    # and phrase list); phrase_fallback decodes an unmatched request once more without the list
+    phrase_mass: bool = False
+    phrase_threshold: float = 0.0
+    phrase_fallback: bool = False
     # prompted requests (more than 16 prompt tokens) share device batches whatever their prompt lengths: their micro-batcher key carries the pooled
     # prompt length -1 and the batch decodes through wis_generate_ragged, longest prompt first.  max_new_tokens stays in the key.  False: the key
     # carries the exact prompt length, as ever - two requests whose prompts differ by a token never meet in a device batch

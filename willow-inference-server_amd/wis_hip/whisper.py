@@ -437,6 +437,32 @@ def phrase_ids(phrases, tokenizer, special):
     return out, names
 
 
+def in_grammar(logmass, n_tokens):
+    """exp(logmass / (n_tokens + 1)): the geometric mean, per step, of the share of the model's probability a phrase list allowed along a phrase of
+    n_tokens tokens and its <|endoftext|>; in [0, 1] (-inf -> 0; NaN stays NaN)."""
+    return float(math.exp(float(logmass) / (int(n_tokens) + 1)))
+
+
+def _phrase_mass_opts(opt, constrained, phrase_mass, phrase_threshold, phrase_fallback):
+    """do_whisper's phrase_mass / phrase_threshold / phrase_fallback, resolved against the settings -> (mass on, threshold or 0.0, fallback on)."""
+    if not constrained:
+        for v, name in ((phrase_mass, "phrase_mass"), (phrase_threshold, "phrase_threshold"), (phrase_fallback, "phrase_fallback")):
+            if v:
+                raise ValueError(f"{name} needs phrases")
+        return False, 0.0, False
+    thr = opt(phrase_threshold, "phrase_threshold", 0.0)
+    try:
+        thr = float(0.0 if thr is None else thr)
+    except (TypeError, ValueError):
+        raise ValueError(f"phrase_threshold {phrase_threshold!r}: a number in [0, 1]") from None
+    if not 0.0 <= thr <= 1.0:      # (a NaN fails both comparisons)
+        raise ValueError(f"phrase_threshold {thr!r}: a number in [0, 1] (0: no threshold)")
+    fb = bool(opt(phrase_fallback, "phrase_fallback", False))
+    if fb and thr == 0.0:
+        raise ValueError("phrase_fallback needs a phrase_threshold in (0, 1]")
+    return bool(opt(phrase_mass, "phrase_mass", False)) or thr > 0.0, thr, fb
+
+
 def assemble_prompt(start, special, initial_prompt_ids=(), prefix_ids=(), n_text_ctx=448):
     """openai-whisper's decoder prompt: [<|startofprev|>] + initial_prompt_ids[-(n_ctx / 2 - 1):] + start sequence + prefix_ids.  The engine takes
     n_ctx / 2 + 4 tokens (228): with a prefix the prompt part is cut further from the left.  A prefix of more than MAX_PREFIX_TOKENS is a ValueError."""
@@ -501,7 +527,8 @@ def _text_of(tokenizer, below):
 def do_whisper(audio_file, model, beam_size=None, task="transcribe", detect_language=False, force_language=None, translate=False,
                models=None, fixed_new_tokens=None, timestamps=False, word_timestamps=False, repetition_penalty=None, no_repeat_ngram_size=None,
                temperatures=None, best_of=None, compression_ratio_threshold=None, logprob_threshold=None, initial_prompt=None, prefix=None,
-               long_form=None, condition_on_previous_text=None, no_speech_threshold=None, phrases=None, phrase_nbest=1):
+               long_form=None, condition_on_previous_text=None, no_speech_threshold=None, phrases=None, phrase_nbest=1,
+               phrase_mass=None, phrase_threshold=None, phrase_fallback=None):
     """phrases (None: the setting's list, `phrases_file`; empty: off): the transcript is restricted to a phrase list - strings (tokenised as
     " " + text.strip() with the checkpoint's tokenizer; no vocabulary: ValueError) or lists of text token ids.  The search can only produce
     one of the phrases (include/wis_hip.h states the rule); `text` is the best one, and the result gains
@@ -509,6 +536,15 @@ def do_whisper(audio_file, model, beam_size=None, task="transcribe", detect_lang
     reached fewer) with the engine's length-normalised log-probability, renormalised over what the list allows at each step.  initial_prompt and
     the repetition options combine with it; prefix, timestamps, word_timestamps, temperatures, long_form=seek and a recording over 30 s are a
     ValueError.  Language detection is unaffected; the translation pass stays unconstrained, as it stays unprompted.
+    phrase_mass / phrase_threshold / phrase_fallback (None: the settings of those names - off, 0 = no threshold, off; they act on constrained
+    requests only, and an explicit one without phrases is a ValueError): the out-of-grammar signal.  With phrase_mass every entry of `matches` gains
+    `logmass` - the log of the share of the model's probability the list allowed, summed over the phrase's tokens and its <|endoftext|>
+    (include/wis_hip.h, THE PHRASE MASS RULE: what an unconstrained decode would have been compared for) - and
+    `in_grammar = exp(logmass / (tokens + 1))`, the geometric-mean share per step in [0, 1], comparable across phrase lengths.  A phrase_threshold
+    in (0, 1] implies phrase_mass and the result gains `matched`: in_grammar of the best match >= threshold (outside [0, 1]: ValueError).  There is
+    no default threshold: a useful one has to be calibrated on the deployment's checkpoint and phrase list.  phrase_fallback (needs a threshold:
+    ValueError): when the best phrase is not matched, the same window is decoded once more without the phrase options - through the encoder view
+    when `encode_once` is on - and `text` is that transcript; `matches` stay.
     long_form ("chunk" | "seek"; None: the setting, "chunk"): how a recording over 30 s is served.  "chunk": the reference's fixed windows merged by
     longest common sequence - no timestamps, no fallback (ValueError).  "seek": openai-whisper's transcribe() loop (wis_hip.longform) over one
     whole-recording log-mel kept on one of the model's GPUs (audio.LongMel) - timestamps, word_timestamps, the temperature fallback, initial_prompt
@@ -551,6 +587,7 @@ def do_whisper(audio_file, model, beam_size=None, task="transcribe", detect_lang
         initial_prompt=opt(initial_prompt, "initial_prompt", ""), prefix=opt(prefix, "prefix", ""),
         phrases=load_phrases_file(getattr(s, "phrases_file", "")) if phrases is None else phrases, phrase_nbest=phrase_nbest)
     constrained = not (q.phrases is None or (hasattr(q.phrases, "__len__") and len(q.phrases) == 0))
+    q.phrase_mass, q.phrase_threshold, q.phrase_fallback = _phrase_mass_opts(opt, constrained, phrase_mass, phrase_threshold, phrase_fallback)
     if constrained:
         try:
             q.phrase_nbest = int(phrase_nbest)
@@ -620,12 +657,14 @@ def do_whisper(audio_file, model, beam_size=None, task="transcribe", detect_lang
             raise ValueError(f"phrase_nbest {q.phrase_nbest}: a search at beam_size {q.beam_size} returns at most {q.beam_size} phrases")
         phr_ids, phr_names = phrase_ids(q.phrases, tokenizer, special)
         phr = dict(phrases=phr_ids, num_hypotheses=q.phrase_nbest)
+        if q.phrase_mass:
+            phr["return_phrase_mass"] = True
     ccg = s.concurrent_gpu_chunks
     translating = translate and total_chunk_count <= ccg
     # encode_once: a request that reads a window more than once - language detection, the temperature fallback, the word alignment, the
     # translation pass - encodes its windows ONCE (Whisper.encode, in the groups the decode uses) and hands the views to every pass; a request that
     # reads its windows once is served as ever: no encode call, the same input kind, the same batch key
-    reads = int(bool(q.detect_language and not q.force_language)) + max(1, len(temps)) + int(bool(word_timestamps)) + int(bool(translating))
+    reads = int(bool(q.detect_language and not q.force_language)) + max(1, len(temps)) + int(bool(word_timestamps)) + int(bool(translating)) + int(bool(q.phrase_fallback))
     views = None
     if getattr(s, "encode_once", False) and reads > 1:
         views = [whisper_model.encode(ctranslate2.StorageView.from_array(np.ascontiguousarray(batch)), input_kind=kind) for batch in chunkit(features, ccg)]
@@ -669,6 +708,19 @@ def do_whisper(audio_file, model, beam_size=None, task="transcribe", detect_lang
         tokens = [int(t) for t in tokens]
     else:
         tokens = results[0].sequences_ids[0]
+    matches = matched = None
+    if constrained:      # the caller's own spelling of a phrase it gave as text, the decoded ids otherwise
+        matches = [dict(text=phr_names.get(tuple(ids)) or tokenizer.decode(ids).strip(), score=float(sc))
+                   for ids, sc in zip(results[0].sequences_ids, results[0].scores)]
+        if q.phrase_mass:
+            for mt, ids, lm in zip(matches, results[0].sequences_ids, results[0].phrase_logmass):
+                mt["logmass"], mt["in_grammar"] = float(lm), in_grammar(lm, len(ids))
+        if q.phrase_threshold > 0:
+            matched = bool(matches) and bool(matches[0]["in_grammar"] >= q.phrase_threshold)      # (a NaN share is no match)
+            if not matched and q.phrase_fallback:      # the same window once more, without the phrase options: the plain transcript
+                feats, fkind = windows_of(0, 1)
+                tokens = whisper_model.generate(feats, [prompt], beam_size=q.beam_size, return_scores=False, fixed_new_tokens=fixed_new_tokens,
+                                                **fkind, **rep)[0].sequences_ids[0]
     segments = None
     if timestamps:
         duration = min(audio_duration / 1000.0, WINDOW_S)
@@ -702,10 +754,8 @@ def do_whisper(audio_file, model, beam_size=None, task="transcribe", detect_lang
     out.translation_tokens = out_translation_tokens
     out.segments = segments
     out.fallback = getattr(results[0], "fallback", None)      # temperature fallback: what the kept decode was (decode_with_fallback)
-    out.matches = None
-    if constrained:      # the caller's own spelling of a phrase it gave as text, the decoded ids otherwise
-        out.matches = [dict(text=phr_names.get(tuple(ids)) or tokenizer.decode(ids).strip(), score=float(sc))
-                       for ids, sc in zip(results[0].sequences_ids, results[0].scores)]
+    out.matches = matches
+    out.matched = matched
     return out
 
 
