@@ -461,6 +461,28 @@ int wis_align_last_timing(wis_model_t* m, float* ms);
  * image of those heads), softmax over T keys, cropped to `frames` -> out fp32 [T_tokens][frames] */
 int wis_op_dtw(int device, const float* x, int N, int M, int32_t* text_idx, int32_t* time_idx, int32_t* len);
 int wis_op_align_matrix(int device, const float* q, const void* kx_f16, int T_tokens, int n_heads_sel, int T, int frames, int width, float* out);
+/* the alignment kernels stage by stage, with wis_align's batched index arithmetic in the caller's hands.  N / F / M / koff / target / dst /
+ * sel_head are HOST arrays (the taps check them: anything that would index out of bounds is WIS_E_ARG before a launch); every other pointer is
+ * device memory that the caller fills beforehand (sentinels) and may read back whole.
+ * wis_op_align_stage: B utterances of N[b] <= nmax <= ncap tokens and F[b] <= fmax <= T frames.  stage 0: q fp32 [B][nsel][ncap][64] (rows
+ *   >= N[b] are not read) -> f16 -> scores + softmax over all T keys; head s of utterance b reads its K image ([8][T][8] f16) at kx_f16 +
+ *   koff[s] + b kbstride (elements, multiples of 8, inside k_elems).  stage 1: (w - mean) / std in place on the caller's W.  stage 2: median of
+ *   `width` + head sum of the caller's W into acc [B][nmax][T].  stage 3: the chain as wis_align runs it.  heads_per_chunk = 0: G from the 96 MB
+ *   rule, else G = min(heads_per_chunk, nsel).  Stages 0 - 2 keep chunk c = heads c G .. at W + c B G nmax T, laid out [B][Gc][nmax][T] with Gc
+ *   the chunk's own head count (w_elems >= ceil(nsel / G) B G nmax T); stage 3 reuses the first region for every chunk (w_elems >= B G nmax T).
+ * wis_op_dtw_batch: table b (N[b] x M[b], rows `pitch` >= fmax apart) at x + b xbstride -> text_idx / time_idx [B][cap], len [B]; cap >= nmax + fmax (a path has up to
+ *   N + M - 1 entries, N + M when non-finite costs send it along the borders); nmax > 511 is WIS_E_UNSUPPORTED.
+ * wis_op_align_probs: logits fp32 [rows][vpad] -> probs[dst[r]] = softmax(logits[r][: eot])[target[r]] for rows with target[r] >= 0.
+ * wis_op_align_capture: dq fp32 [M][d], row r = utterance ub0 + r / 16, matrix row t0 + r % 16 - P (rows outside [0, ncap) are skipped); heads
+ *   sel_head[s0 .. s0 + n_layer_heads - 1] of the nsel selected -> qsel f16 [utterance][nsel][ncap][64] (qsel_elems elements). */
+int wis_op_align_stage(int device, int stage, const float* q, const void* kx_f16, long long k_elems, const long long* koff, long long kbstride,
+                       const int32_t* N, const int32_t* F, int B, int nsel, int ncap, int nmax, int fmax, int T, int width, int heads_per_chunk,
+                       float* W, long long w_elems, float* acc, long long acc_elems);
+int wis_op_dtw_batch(int device, const float* x, long long x_elems, long long xbstride, int pitch, const int32_t* N, const int32_t* M, int B, int nmax, int fmax, int cap,
+                     int32_t* text_idx, int32_t* time_idx, int32_t* len);
+int wis_op_align_probs(int device, const float* logits, int rows, int vpad, int eot, const int32_t* target, const int32_t* dst, float* probs, int probs_len);
+int wis_op_align_capture(int device, const float* dq, int M, int d, const int32_t* sel_head, int s0, int n_layer_heads, int nsel, int ub0, int t0, int P, int ncap,
+                         void* qsel_f16, long long qsel_elems);
 /* the decoder pass wis_generate_draft_beam verifies a window with, alone: the tree rows of steps 1 .. n_steps of a beam trajectory (tok / org
  * [n_steps][beam]: per step the live beams' newest tokens and the beam each continued from) behind `prompt`, in ONE pass (tree self-attention by
  * ancestor table, cross-attention as row groups over the utterance's one K / V); logits [n_steps][beam][n_vocab]: row (s, j) = what a step fed

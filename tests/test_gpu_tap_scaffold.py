@@ -30,6 +30,12 @@ def test_refusals_then_a_good_call(lib):
         # the parent commit's wis_op_dtw / wis_op_sv_posconv answer a null pointer with "bad argument", WIS_E_ARG
         ("wis_op_dtw", (0, p, 4, 6, p, p, None), WIS_E_ARG),                                            # null output (len)
         ("wis_op_sv_posconv", (0, p, p, p, None, 8), WIS_E_ARG),                                        # null output
+        # the alignment stage taps: the null pointer is found before any host array (N, F, koff, target, dst, sel_head) is read
+        ("wis_op_align_stage", (0, 3, None, p, 4096, p, 0, p, p, 1, 1, 4, 4, 4, 8, 7, 0, p, 1 << 14, p, 1 << 14), WIS_E_ARG),      # chain without q
+        ("wis_op_align_stage", (0, 2, None, None, 0, None, 0, p, p, 1, 1, 4, 4, 4, 8, 7, 0, p, 1 << 14, None, 0), WIS_E_ARG),      # median without acc
+        ("wis_op_dtw_batch", (0, p, 64, 0, 8, p, p, 1, 4, 6, 16, p, p, None), WIS_E_ARG),               # null output (len)
+        ("wis_op_align_probs", (0, p, 4, 64, 60, p, p, None, 8), WIS_E_ARG),                            # null output (probs)
+        ("wis_op_align_capture", (0, p, 32, 128, p, 0, 1, 1, 0, 0, 4, 16, None, 1 << 14), WIS_E_ARG),   # null output (qsel)
     ]
     for name, args, want in refusals:
         rc = getattr(lib, name)(*args)

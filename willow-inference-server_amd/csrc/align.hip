@@ -1,5 +1,5 @@
 // align.hip — word-level timestamps: cross-attention alignment and dynamic time warping (wis_align).
-// An object of its own on model.hpp's interface (the decoder pass, the handle) and tap.hpp's scaffold (the two wis_op_* taps at the end).
+// An object of its own on model.hpp's interface (the decoder pass, the handle) and tap.hpp's scaffold (the wis_op_* taps at the end).
 //
 // What openai-whisper's find_alignment / CTranslate2's Whisper.align compute, on the GPU:
 //   1. the text is teacher-forced through the batched-row decoder route in passes of 16 positions (dec_forward_frag, un-folded
@@ -274,12 +274,17 @@ int align_chunk_heads(int nsel, int B, int nmax, int T) {
   if (g < 1) g = 1;
   return (int)std::min<size_t>(g, (size_t)nsel);
 }
+// heads_per_chunk = 0: the budget rule; > 0 (the stage tap): that many, so that small shapes run more than one chunk
+int align_heads_per_chunk(int nsel, int B, int nmax, int T, int heads_per_chunk) {
+  return heads_per_chunk > 0 ? std::min(heads_per_chunk, nsel) : align_chunk_heads(nsel, B, nmax, T);
+}
 // the alignment matrix -mean_h median((P_h - mean) / std) of B utterances into acc [B][nmax][T]
 int launch_align_matrix(hipStream_t st, const f16* qsel, const f16* kbase, const long long* koff, long long kbstride, const int* dN, const int* dF,
-                        float* W, float* acc, int B, int nsel, int ncap, int nmax, int fmax, int T, int width, hipEvent_t* ev = nullptr, int nev = 0, int* used_ev = nullptr) {
+                        float* W, float* acc, int B, int nsel, int ncap, int nmax, int fmax, int T, int width, hipEvent_t* ev = nullptr, int nev = 0, int* used_ev = nullptr,
+                        int heads_per_chunk = 0) {
   if (width < 1 || width > AL_MAXW || !(width & 1)) { set_error("align: median_filter_width %d must be odd and within [1, %d]", width, AL_MAXW); return WIS_E_ARG; }
   if (nsel < 1 || nmax < 1 || fmax < 1 || fmax > T) { set_error("align: bad shape (heads %d, tokens %d, frames %d of %d)", nsel, nmax, fmax, T); return WIS_E_ARG; }
-  const int G = align_chunk_heads(nsel, B, nmax, T);
+  const int G = align_heads_per_chunk(nsel, B, nmax, T, heads_per_chunk);
   int e = 0;
   for (int g0 = 0; g0 < nsel; g0 += G) {
     const int Gc = std::min(G, nsel - g0);
@@ -546,6 +551,107 @@ int wis_op_align_matrix(int device, const float* q, const void* kx_f16, int T_to
   hipLaunchKernelGGL(align_q16_kernel, dim3(n, n_heads_sel), dim3(64), 0, st, q, qsel, n, n);
   WIS_RET(launch_align_matrix(st, qsel, reinterpret_cast<const f16*>(kx_f16), koff, 0, meta, meta + 1, W, acc, 1, n_heads_sel, n, n, frames, T, width));
   if (hipMemcpy2DAsync(out, (size_t)frames * 4, acc, (size_t)T * 4, (size_t)frames * 4, n, hipMemcpyDeviceToDevice, st) != hipSuccess) { set_error("wis_op_align_matrix: copy failed"); return WIS_E_HIP; }
+  return t.finish(WIS_OK);
+}
+
+// One stage of the matrix (or the chain) on B ragged utterances, with the shipped call's index arithmetic in the caller's hands: stage 0 scores +
+// softmax, 1 norm, 2 median + head sum, 3 the chain (launch_align_matrix itself).  N / F / koff are host arrays; q fp32 [B][nsel][ncap][64] (rows
+// >= N[b] are never read), K f16 of k_elems elements, W of w_elems and acc of acc_elems floats are device buffers the caller fills beforehand and reads
+// back whole.  Stages 0 - 2 keep chunk c (heads c G .. c G + Gc - 1, laid out [B][Gc][nmax][T]) at W + c B G nmax T; the chain reuses W + 0 as wis_align does.
+int wis_op_align_stage(int device, int stage, const float* q, const void* kx_f16, long long k_elems, const long long* koff, long long kbstride,
+                       const int32_t* N, const int32_t* F, int B, int nsel, int ncap, int nmax, int fmax, int T, int width, int heads_per_chunk,
+                       float* W, long long w_elems, float* acc, long long acc_elems) {
+  Tap t(device, "wis_op_align_stage"); WIS_RET(t.rc);
+  const bool need_q = stage == 0 || stage == 3, need_acc = stage == 2 || stage == 3;
+  if (stage < 0 || stage > 3 || !N || !F || !W || (need_q && (!q || !kx_f16 || !koff)) || (need_acc && !acc)) { set_error("wis_op_align_stage: bad argument"); return WIS_E_ARG; }
+  if (B < 1 || B > 65535 || nsel < 1 || nsel > 65535 || nmax < 1 || nmax > 65535 || ncap < nmax || T < 1 || fmax < 1 || fmax > T || heads_per_chunk < 0 || kbstride < 0) {
+    set_error("wis_op_align_stage: bad shape (B %d, heads %d, tokens %d of %d, frames %d of %d, heads_per_chunk %d)", B, nsel, nmax, ncap, fmax, T, heads_per_chunk); return WIS_E_ARG;
+  }
+  if (width < 1 || width > AL_MAXW || !(width & 1)) { set_error("wis_op_align_stage: median_filter_width %d must be odd and within [1, %d]", width, AL_MAXW); return WIS_E_ARG; }
+  for (int b = 0; b < B; ++b) if (N[b] < 1 || N[b] > nmax || F[b] < 1 || F[b] > fmax) {
+    set_error("wis_op_align_stage: utterance %d: %d tokens of %d, %d frames of %d", b, N[b], nmax, F[b], fmax); return WIS_E_ARG;
+  }
+  const int G = align_heads_per_chunk(nsel, B, nmax, T, heads_per_chunk), nchunks = cdiv(nsel, G);
+  const long long region = (long long)B * G * nmax * T;
+  if (w_elems < (stage == 3 ? 1 : nchunks) * region || (need_acc && acc_elems < (long long)B * nmax * T)) {
+    set_error("wis_op_align_stage: W of %lld floats (needs %lld) or acc of %lld (needs %lld) too small", w_elems, (stage == 3 ? 1 : nchunks) * region, acc_elems, (long long)B * nmax * T); return WIS_E_ARG;
+  }
+  if (need_q) for (int s = 0; s < nsel; ++s) {      // every (utterance, head) image lies inside K, 16-byte aligned
+    const long long last = koff[s] + (long long)(B - 1) * kbstride;
+    if (koff[s] < 0 || (koff[s] & 7) || (kbstride & 7) || last + (long long)T * 64 > k_elems) { set_error("wis_op_align_stage: head %d: K image at %lld (+ %lld per utterance) outside %lld elements or unaligned", s, koff[s], kbstride, k_elems); return WIS_E_ARG; }
+  }
+  hipStream_t st = t.st;
+  f16* qsel = nullptr; long long* d_koff = nullptr; int* meta = nullptr;
+  WIS_RET(t.get(&meta, (size_t)2 * B));
+  hipMemcpyAsync(meta, N, (size_t)B * 4, hipMemcpyHostToDevice, st);
+  hipMemcpyAsync(meta + B, F, (size_t)B * 4, hipMemcpyHostToDevice, st);
+  const int *dN = meta, *dF = meta + B;
+  const f16* kb = reinterpret_cast<const f16*>(kx_f16);
+  if (need_q) {
+    WIS_RET(t.get(&qsel, (size_t)B * nsel * ncap * 64)); WIS_RET(t.get(&d_koff, (size_t)nsel));
+    hipMemcpyAsync(d_koff, koff, (size_t)nsel * 8, hipMemcpyHostToDevice, st);
+    hipLaunchKernelGGL(align_q16_kernel, dim3(ncap, B * nsel), dim3(64), 0, st, q, qsel, ncap, ncap);
+  }
+  if (stage == 3) return t.finish(launch_align_matrix(st, qsel, kb, d_koff, kbstride, dN, dF, W, acc, B, nsel, ncap, nmax, fmax, T, width, nullptr, 0, nullptr, heads_per_chunk));
+  for (int g0 = 0, c = 0; g0 < nsel; g0 += G, ++c) {      // launch_align_matrix's loop, one kernel of it
+    const int Gc = std::min(G, nsel - g0);
+    float* Wc = W + (size_t)c * region;
+    if (stage == 0) hipLaunchKernelGGL(align_scores_kernel, dim3(cdiv(nmax, AL_RW), Gc, B), dim3(64), 0, st, qsel, kb, d_koff, kbstride, dN, dF, Wc, g0, Gc, nsel, ncap, nmax, T);
+    if (stage == 1) hipLaunchKernelGGL(align_norm_kernel, dim3(cdiv(fmax, 64), Gc, B), dim3(256), 0, st, Wc, dN, dF, Gc, nmax, T);
+    if (stage == 2) hipLaunchKernelGGL(align_median_kernel, dim3(cdiv(fmax, 256), nmax, B), dim3(256), 0, st, Wc, acc, dN, dF, Gc, nmax, T, width, g0 == 0 ? 1 : 0, g0 + Gc >= nsel ? 1 : 0, nsel);
+  }
+  return t.finish(WIS_OK);
+}
+
+// B cost tables in one buffer as wis_align lays them out: table b at x + b xbstride, rows `pitch` apart, N[b] x M[b] (host arrays) under common
+// nmax / fmax -> text_idx / time_idx [B][cap], len [B] (device; cap >= nmax + fmax: a path takes N + M - 1 entries, and N + M when non-finite costs send it
+// along the borders, as dtw_cpu's does)
+int wis_op_dtw_batch(int device, const float* x, long long x_elems, long long xbstride, int pitch, const int32_t* N, const int32_t* M, int B, int nmax, int fmax, int cap,
+                     int32_t* text_idx, int32_t* time_idx, int32_t* len) {
+  Tap t(device, "wis_op_dtw_batch"); WIS_RET(t.rc);
+  if (!x || !N || !M || !text_idx || !time_idx || !len || B < 1 || B > 65535 || nmax < 1 || fmax < 1 || pitch < fmax || xbstride < 0 || cap < 1 || (long long)cap < (long long)nmax + fmax) {
+    set_error("wis_op_dtw_batch: bad argument"); return WIS_E_ARG;
+  }
+  for (int b = 0; b < B; ++b) if (N[b] < 1 || N[b] > nmax || M[b] < 1 || M[b] > fmax || (long long)b * xbstride + (long long)(N[b] - 1) * pitch + M[b] > x_elems) {
+    set_error("wis_op_dtw_batch: table %d (%d x %d of %d x %d) outside its buffer of %lld floats", b, N[b], M[b], nmax, fmax, x_elems); return WIS_E_ARG;
+  }
+  if (nmax + 1 > AL_DTW_THREADS) return launch_align_dtw(t.st, x, xbstride, pitch, nullptr, nullptr, nmax, fmax, B, nullptr, nullptr, text_idx, time_idx, len, cap);      // (refuses before it launches)
+  unsigned* trace = nullptr; int* rev = nullptr; int* meta = nullptr;
+  WIS_RET(t.get(&trace, (size_t)B * (nmax + 1) * dtw_wpr(fmax))); WIS_RET(t.get(&rev, (size_t)B * 2 * cap)); WIS_RET(t.get(&meta, (size_t)2 * B));
+  hipMemcpyAsync(meta, N, (size_t)B * 4, hipMemcpyHostToDevice, t.st);
+  hipMemcpyAsync(meta + B, M, (size_t)B * 4, hipMemcpyHostToDevice, t.st);
+  return t.finish(launch_align_dtw(t.st, x, xbstride, pitch, meta, meta + B, nmax, fmax, B, trace, rev, text_idx, time_idx, len, cap));
+}
+
+// align_prob_kernel on caller-supplied logits [rows][vpad] (device): target / dst are host arrays, probs a device buffer of probs_len floats
+int wis_op_align_probs(int device, const float* logits, int rows, int vpad, int eot, const int32_t* target, const int32_t* dst, float* probs, int probs_len) {
+  Tap t(device, "wis_op_align_probs"); WIS_RET(t.rc);
+  if (!logits || !target || !dst || !probs || rows < 1 || vpad < 1 || eot < 1 || eot > vpad || probs_len < 1) { set_error("wis_op_align_probs: bad argument"); return WIS_E_ARG; }
+  for (int r = 0; r < rows; ++r) if (target[r] >= 0 && (target[r] >= vpad || dst[r] < 0 || dst[r] >= probs_len)) {
+    set_error("wis_op_align_probs: row %d: target %d of %d ids or slot %d of %d out of range", r, target[r], vpad, dst[r], probs_len); return WIS_E_ARG;
+  }
+  int* meta = nullptr;
+  WIS_RET(t.get(&meta, (size_t)2 * rows));
+  hipMemcpyAsync(meta, target, (size_t)rows * 4, hipMemcpyHostToDevice, t.st);
+  hipMemcpyAsync(meta + rows, dst, (size_t)rows * 4, hipMemcpyHostToDevice, t.st);
+  hipLaunchKernelGGL(align_prob_kernel, dim3(rows), dim3(256), 0, t.st, logits, vpad, eot, meta, meta + rows, probs);
+  return t.finish(WIS_OK);
+}
+
+// align_capture_kernel on a caller-supplied pass: dq fp32 [M][d] (device), sel_head [nsel] (host), the layer's heads s0 .. s0 + n_layer_heads - 1,
+// qsel f16 [>= ub0 + ceil(M / 16)][nsel][ncap][64] of qsel_elems elements (device)
+int wis_op_align_capture(int device, const float* dq, int M, int d, const int32_t* sel_head, int s0, int n_layer_heads, int nsel, int ub0, int t0, int P, int ncap,
+                         void* qsel_f16, long long qsel_elems) {
+  Tap t(device, "wis_op_align_capture"); WIS_RET(t.rc);
+  if (!dq || !sel_head || !qsel_f16 || M < 1 || M > 65535 || d < 64 || d % 64 || s0 < 0 || n_layer_heads < 1 || nsel < 1 || s0 + n_layer_heads > nsel || ub0 < 0 || t0 < 0 || P < 0 || ncap < 1) {
+    set_error("wis_op_align_capture: bad argument"); return WIS_E_ARG;
+  }
+  for (int s = s0; s < s0 + n_layer_heads; ++s) if (sel_head[s] < 0 || sel_head[s] >= d / 64) { set_error("wis_op_align_capture: head %d outside %d", sel_head[s], d / 64); return WIS_E_ARG; }
+  if ((long long)(ub0 + (M - 1) / 16 + 1) * nsel * ncap * 64 > qsel_elems) { set_error("wis_op_align_capture: utterances up to %d outside qsel of %lld elements", ub0 + (M - 1) / 16, qsel_elems); return WIS_E_ARG; }
+  int* d_sel = nullptr;
+  WIS_RET(t.get(&d_sel, (size_t)nsel));
+  hipMemcpyAsync(d_sel, sel_head, (size_t)nsel * 4, hipMemcpyHostToDevice, t.st);
+  hipLaunchKernelGGL(align_capture_kernel, dim3(M, n_layer_heads), dim3(64), 0, t.st, dq, reinterpret_cast<f16*>(qsel_f16), d_sel, s0, nsel, d, ub0, t0, P, ncap);
   return t.finish(WIS_OK);
 }
 

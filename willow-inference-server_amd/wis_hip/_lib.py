@@ -123,6 +123,10 @@ SYMBOLS = [
     ("wis_align_last_timing", _i, [_vp, _fp]),
     ("wis_op_dtw", _i, [_i, _vp, _i, _i, _vp, _vp, _vp]),
     ("wis_op_align_matrix", _i, [_i, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
+    ("wis_op_align_stage", _i, [_i, _i, _vp, _vp, _i64, _vp, _i64, _vp, _vp] + [_i] * 8 + [_vp, _i64, _vp, _i64]),
+    ("wis_op_dtw_batch", _i, [_i, _vp, _i64, _i64, _i, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp]),
+    ("wis_op_align_probs", _i, [_i, _vp, _i, _i, _i, _vp, _vp, _vp, _i]),
+    ("wis_op_align_capture", _i, [_i, _vp, _i, _i, _vp] + [_i] * 7 + [_vp, _i64]),
     ("wis_debug_tree_logits", _i, [_vp, _vp, _i, C.POINTER(C.c_int32), _i, _i, C.POINTER(C.c_int32), C.POINTER(C.c_int32), _i, _fp]),
     ("wis_debug_search", _i, [_vp, _vp, _i, _i, C.POINTER(GenOpts), C.POINTER(C.c_int32), C.POINTER(C.c_int32), _fp, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     ("wis_debug_search_n", _i, [_vp, _vp, _i, _i, C.POINTER(GenOpts), C.POINTER(C.c_uint64), C.POINTER(C.c_uint32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), _fp,
