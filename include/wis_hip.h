@@ -306,6 +306,34 @@ typedef struct {
    * when the call starts), and a NaN slot propagates into the sum.
    * 1 needs phrases = 1 (else WIS_E_ARG); a value other than 0 / 1: WIS_E_ARG.  wis_last_phrase_mass reads the sums.  The entry points of `phrases`. */
   int32_t phrase_mass;            /* 1: compute the in-grammar mass of every result (wis_last_phrase_mass).  0: off */
+  /* Hotword boosting (contextual biasing): free-form decoding goes on, tokens that start or continue a listed entry get a log-domain bonus.
+   * Appended fields: 0 is what a caller that never knew them passes, and means today's search - the same launches, captured steps and buffers.
+   * THE HOTWORD RULE.  The handle holds a HOTWORD SET (wis_model_set_hotwords), apart from the phrase set: installing one never disturbs the other.
+   * The two share record format, limits and token rules: 16-byte edge records in tree order; at most 65535 records, 4096 children per node, 32
+   * tokens per entry; text tokens only (< eot), outside suppress_ids, no first token in suppress_ids_begin; every leaf ends an entry.
+   * For a live row, h[0 .. L) is the generated history as the repetition rules define it: what this search has generated for the beam so far, after
+   * the last reordering - no start sequence, prompt or prefix -, L = min(steps taken, max_new).
+   *   - For k = 0 .. min(L, 31) the suffix S_k = h[L-k .. L) is ACTIVE when it is a path of the trie from the root.  S_0, the empty suffix, is always
+   *     active and sits at the root.  A history id outside [0, n_vocab) breaks every suffix that contains it.
+   *   - The BOOST SET T is the union, over the active suffixes, of the children of the node each suffix ends at.
+   *   - Every t in T gets exactly ONE fp32 addition, row[t] = row[t] + hotword_boost, round to nearest - however many suffixes name t.  -inf stays
+   *     -inf, NaN stays NaN.  <|endoftext|> is never in T; "ends an entry" flags play no part.
+   *   - Ids in [n_vocab, n_vocab_pad), rows of finished utterances and all other memory are never written.
+   *   - The first step: every beam samples from the one shared prompt row; that row gets the root's children boosted ONCE (the utterance's first
+   *     workgroup alone acts, as under the phrase rule).  The forced-EOT step of fixed_new_tokens: nothing, as under the repetition rules.
+   * Order: the repetition penalty and n-gram bans first, then this addition, then everything else of the tail (an addition commutes with the -inf
+   * masks of the suppress lists: a banned or suppressed hot token stays banned); the timestamp rules' text / timestamp decision sees boosted values.
+   * A hypothesis' score is the log-softmax of the BOOSTED row at each step - not the model's own log-probability.
+   * The rule has NO BACK-OFF: a hypothesis that abandons an entry half-way keeps what it gained (shallow fusion that takes the accumulated bonus
+   * back needs per-beam state that follows the reorder: not part of this rule).
+   * hotwords: a value other than 0 / 1 is WIS_E_ARG.  hotword_boost: finite and > 0 when hotwords = 1, else WIS_E_ARG; ignored when hotwords = 0 (no
+   * default is offered: a useful value depends on the checkpoint).  hotwords = 1 with no set installed: WIS_E_STATE; together with phrases = 1:
+   * WIS_E_ARG; through the drafted entry points: WIS_E_UNSUPPORTED.  (More than 256 new tokens, which the repetition rules answer with
+   * WIS_E_UNSUPPORTED, cannot arise: every entry point caps max_new_tokens at 256.)  Nothing is enqueued by a refused call.  Combines with
+   * timestamps, the repetition options, sampling and num_hypotheses, prompts of any supported length.  wis_generate, wis_generate_n,
+   * wis_generate_ragged, wis_debug_search, wis_debug_search_n. */
+  int32_t hotwords;               /* 1: boost by the handle's hotword set.  0: off */
+  float   hotword_boost;          /* the bonus, in the logits' (natural-log) units */
 } wis_gen_opts_t;
 
 /* out_ids: [B][max_new] (max_new = resolved max_new_tokens), out_len: [B], out_score: [B]
@@ -433,6 +461,12 @@ int wis_debug_logits_rows(wis_model_t* m, const float* input, int input_kind, in
  * max_new_tokens is part of a captured step's key, as ever: sets whose longest phrases are equally long share their steps).  A clone
  * (wis_model_clone) has a buffer of its own and starts without a set.  Not part of wis_config_t. */
 int wis_model_set_phrases(wis_model_t* m, const int32_t* trie, int n_records);
+/* ---- hotword boosting (wis_gen_opts_t::hotwords states THE HOTWORD RULE) ----------------------------------------------------------
+ * Installs a hotword set on a handle: wis_model_set_phrases' table, validator, limits and answers, in a buffer of its own - the phrase set is
+ * not touched, and the other way round.  The "ends an entry" flags are validated and otherwise unused.  The buffer has a fixed capacity and
+ * never moves; the record count and the boost live in device memory beside it, so ONE captured step serves every set and every boost.
+ * n_records = 0 removes the set; a malformed table is WIS_E_ARG with the previous set left in place; a clone starts without a set. */
+int wis_model_set_hotwords(wis_model_t* m, const int32_t* trie, int n_records);
 /* ---- word-level timestamps: cross-attention alignment + dynamic time warping (csrc/align.hip) --------------------------------
  * The alignment heads of a handle: n (layer, head) pairs; n == 0 restores openai-whisper's default, every head of the upper half
  * of the decoder layers (layer >= n_dec_layers / 2).  Clones made afterwards inherit them.  Not part of wis_config_t. */
@@ -776,6 +810,13 @@ int wis_op_phrase_mass(int device, float* logits, int n_vocab, int n_vocab_pad, 
  * above -inf is a filler), trie i32 [n_rec][4], logmass f32 [B][n_rec] -> out f32 [B n].  All device memory; B n <= 96, 1 <= id_ld <= 256. */
 int wis_op_phrase_mass_gather(int device, const int32_t* ids, const int32_t* len, const float* score, const int32_t* trie, int n_rec,
                               const float* logmass, int B, int n, int id_ld, float* out);
+/* the hotword boost of one step (hotword_rules_kernel; THE HOTWORD RULE), in place: wis_op_phrase_rules' arguments, all pointers device memory,
+ * plus fixed_new (> 0: utterances with min(step_u[b], max_new) >= fixed_new are left alone, the forced-EOT step) and the boost (finite, > 0).
+ * UNLIKE that tap the table IS validated - read back and checked on the host by the engine's validator (token rules against eot / n_vocab, no
+ * suppress lists) - and a malformed one is WIS_E_ARG before anything is launched.  n_vocab <= 65536. */
+int wis_op_hotword_rules(int device, float* logits, int n_vocab, int n_vocab_pad, int eot, const int32_t* trie, int n_rec, const int32_t* alive,
+                         const int32_t* step_u, const int32_t* done, int B, int beam, int max_new, int fixed_new, float boost,
+                         int lr_b, int lr_j, int lr_off);
 
 /* ---- speaker verification (replaces the reference's WavLMForXVector embedder, main.py:306-316 / do_sv 797-879): one handle = the
  * WavLM-base-plus-sv x-vector model on one GPU.  Input: mono 16 kHz f32 PCM in host memory, already through the reference's

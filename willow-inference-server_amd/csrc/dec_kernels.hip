@@ -3967,4 +3967,87 @@ int launch_phrase_mass_gather(hipStream_t st, const int* ids, const int* len, co
   return WIS_OK;
 }
 
+// =======================================================================================
+// Hotword boosting (include/wis_hip.h, THE HOTWORD RULE), the pre-pass behind rep_rules_kernel when wis_gen_opts_t::hotwords is on.
+// (The last kernel of the file: every other kernel of the code object lies where it lay before this one existed.)
+// grid B*beam (one workgroup per live row), block 256.  The set is a flat trie in phrase_rules_kernel's record format.
+// HISTORY: the last K = min(L, 31) generated tokens of the row go to LDS (an id outside [0, n_vocab) as -1: it breaks every suffix that holds it).
+// WALK: thread k <= K follows suffix S_k = the last k tokens from the root on its own - the 32 walks are independent; a node's children ascend by
+//   token, so each token is a binary search over the node's child range (<= 12 dependent loads) - and leaves the child range of the node it ends
+//   at in LDS ({0, 0}: the suffix is no path, or ends at a leaf).  S_0 is the root.  Most suffixes die at their first token.
+// BOOST: the workgroup goes through the <= 32 end nodes, 256 children per round; per child token t the thread sets t's bit in an LDS bitmap
+//   (65536 bits = 8 KB, the first n_vocab cleared and used) with atomicOr, and the thread that found the bit clear does row[t] = row[t] + boost - ONE fp32 addition per token of the boost
+//   set however many suffixes name it, and no two threads ever touch the same element.  <|endoftext|> is never boosted; "ends an entry" flags
+//   are not read.  Ids >= n_vocab are never written.
+// ctl = {boost's bits, n_rec} in device memory (the handle's control words: the boost is written ahead of every call's steps, the record count
+// with the set - a captured step carries the address, never either value, so one step graph serves every boost and every set).
+// Rows that share ONE logits row (lr_j == 0: the pass that carries the prompt, every history empty) are boosted by the utterance's first
+// workgroup alone.  Nothing happens for a finished utterance or on the measurement convention's forced-EOT step (as in rep_rules_kernel).
+// The host validates a set before it reaches the device; the kernel checks every child range and token against n_rec / n_vocab again.
+// The SampleCfg fields it reads lead the argument list as scalars behind the pointers (kernarg preload, build.py).
+constexpr int HOTWORD_MAX_VOCAB = 65536, HOTWORD_SUFFIXES = 32;
+__global__ __launch_bounds__(256) void hotword_rules_kernel(float* __restrict__ logits, const int* __restrict__ step_u, const int* __restrict__ done,
+                                                            const int* __restrict__ alive, const int4* __restrict__ trie, const int* __restrict__ ctl,
+                                                            int beam, int max_new, int fixed_new, int n_vocab, int n_vocab_pad, int eot,
+                                                            int lr_b, int lr_j, int lr_off) {
+  __shared__ int s_h[HOTWORD_SUFFIXES];
+  __shared__ int2 s_end[HOTWORD_SUFFIXES];
+  __shared__ unsigned s_bits[HOTWORD_MAX_VOCAB / 32];
+  const int tid = threadIdx.x, m = blockIdx.x, b = m / beam, jb = m - b * beam;
+  const float boost = __int_as_float(ctl[0]);
+  const int n_rec = ctl[1];
+  if (done[b] || n_rec < 1 || n_rec > PHRASE_MAX_RECORDS) return;
+  if (lr_j == 0 && jb != 0) return;
+  int L = step_u[b];
+  L = L < max_new ? L : max_new;
+  if (L < 0 || (fixed_new > 0 && L >= fixed_new)) return;
+  const int V = n_vocab;
+  if (V > HOTWORD_MAX_VOCAB) return;      // (the launcher refuses it)
+  const int K = L < HOTWORD_SUFFIXES - 1 ? L : HOTWORD_SUFFIXES - 1;
+  if (tid < K) {
+    const int tk = alive[(size_t)m * max_new + (L - K + tid)];
+    s_h[tid] = (tk >= 0 && tk < V) ? tk : -1;
+  }
+  for (int i = tid; i < (V + 31) >> 5; i += 256) s_bits[i] = 0u;
+  __syncthreads();
+  if (tid <= K) {
+    int4 node = trie[0];
+    bool live = true;
+    for (int i = K - tid; i < K && live; ++i) {
+      const int first = node.y, n = node.z, tk = s_h[i];
+      live = tk >= 0 && first >= 1 && n >= 1 && n <= PHRASE_MAX_CHILDREN && first <= n_rec - n;
+      if (!live) break;
+      int lo = 0, hi = n;      // the first child whose token is >= tk
+      while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (trie[first + mid].x < tk) lo = mid + 1; else hi = mid;
+      }
+      live = lo < n;
+      if (live) { node = trie[first + lo]; live = node.x == tk; }
+    }
+    const int first = node.y, n = node.z;
+    live = live && first >= 1 && n >= 1 && n <= PHRASE_MAX_CHILDREN && first <= n_rec - n;
+    s_end[tid] = live ? make_int2(first, n) : make_int2(0, 0);
+  }
+  __syncthreads();
+  float* row = logits + (size_t)(b * lr_b + jb * lr_j + lr_off) * n_vocab_pad;
+  for (int k = 0; k <= K; ++k) {
+    const int2 e = s_end[k];
+    for (int c = tid; c < e.y; c += 256) {
+      const int t = trie[e.x + c].x;
+      if (t < 0 || t >= V || t == eot) continue;
+      const unsigned bit = 1u << (t & 31);
+      if (!(atomicOr(&s_bits[t >> 5], bit) & bit)) row[t] = __fadd_rn(row[t], boost);
+    }
+  }
+}
+int launch_hotword_rules(hipStream_t st, float* logits, const BeamState& bs, int B, const SampleCfg& cfg, const int4* trie, const int* ctl,
+                         int lr_b, int lr_j, int lr_off) {
+  if (!trie || !ctl || cfg.max_new < 1 || cfg.max_new > 256 || cfg.n_vocab < 1 || cfg.n_vocab_pad < cfg.n_vocab ||
+      cfg.n_vocab > HOTWORD_MAX_VOCAB) { set_error("hotword_rules: config out of range"); return WIS_E_UNSUPPORTED; }
+  hipLaunchKernelGGL(hotword_rules_kernel, dim3(B * cfg.beam), dim3(256), 0, st, logits, bs.step_u, bs.done, bs.alive, trie, ctl, cfg.beam, cfg.max_new,
+                     cfg.fixed_new, cfg.n_vocab, cfg.n_vocab_pad, cfg.eot, lr_b, lr_j, lr_off);
+  return WIS_OK;
+}
+
 }  // namespace wis

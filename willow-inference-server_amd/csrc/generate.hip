@@ -36,6 +36,8 @@ struct SampleCtx {
   bool rep() const { return rep_pen != 1.f || rep_ngram != 0; }
   bool phrases = false;          // wis_gen_opts_t::phrases: the handle's phrase set masks every live row behind the repetition rules (phrase_rules_kernel)
   bool phr_mass = false;         // wis_gen_opts_t::phrase_mass: phrase_rules_mass_kernel in that kernel's place - the same mask, and the node's in-grammar mass
+  bool hotwords = false;         // wis_gen_opts_t::hotwords: the handle's hotword set boosts every live row behind the repetition rules (hotword_rules_kernel)
+  float hot_boost = 0.f;         // ... by this much: written to the handle's device word ahead of the call's steps (hotword_begin), never a kernel argument
   SampleP sp;                    // random sampling (topk 0: off): sample_step_kernel stands in beam_step_kernel's place, `beam` counts the utterance's samples
   int n_res = 1;                 // results per utterance (num_hypotheses)
   bool sampling() const { return sp.topk != 0; }
@@ -95,6 +97,26 @@ static int resolve_phrase_opts(const wis_model* m, const wis_gen_opts_t* o, bool
   if (*max_new < need) { set_error("phrases: the longest phrase (%d tokens) does not fit the %d steps this call can take", m->phr_depth, *max_new); return WIS_E_ARG; }
   if (o->max_new_tokens == 0 && *max_new > need) *max_new = need;
   g->phrases = true; g->phr_mass = o->phrase_mass == 1;
+  return WIS_OK;
+}
+// wis_gen_opts_t::hotwords / hotword_boost of a call, resolved - or refused (THE HOTWORD RULE has the table; both callers have capped max_new at
+// MAX_STEPS = 256 before this, the most hotword_rules_kernel's history holds)
+static int resolve_hotword_opts(const wis_model* m, const wis_gen_opts_t* o, bool drafted, SampleCtx* g) {
+  g->hotwords = false; g->hot_boost = 0.f;
+  if (o->hotwords == 0) return WIS_OK;
+  if (o->hotwords != 1) { set_error("hotwords %d: 0 (off) or 1 (the handle's hotword set)", o->hotwords); return WIS_E_ARG; }
+  if (!std::isfinite(o->hotword_boost) || !(o->hotword_boost > 0.f)) { set_error("hotword_boost %g: a finite value > 0 with hotwords = 1", (double)o->hotword_boost); return WIS_E_ARG; }
+  if (o->phrases) { set_error("hotwords: not available together with phrases (a constrained search has nothing left to bias)"); return WIS_E_ARG; }
+  if (drafted) { set_error("hotwords: not available for drafted decodes (wis_generate_draft / wis_generate_draft_beam)"); return WIS_E_UNSUPPORTED; }
+  if (m->hot_n < 1) { set_error("hotwords: the handle has no hotword set (wis_model_set_hotwords)"); return WIS_E_STATE; }
+  g->hotwords = true; g->hot_boost = o->hotword_boost;
+  return WIS_OK;
+}
+// A call with hotwords on, before its first step is enqueued: the boost goes to the handle's device word in stream order - behind an earlier
+// call's over-run step, ahead of every step of this one.  The captured steps read the word, so one graph serves every value.
+static int hotword_begin(wis_model* m, float boost, hipStream_t st) {
+  unsigned bits; memcpy(&bits, &boost, 4);
+  WIS_HIP_CHECK(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(m->d_hot_ctl), (int)bits, 1, st));
   return WIS_OK;
 }
 // A call with phrase_mass on, before anything of it is enqueued: the handle's logmass buffer (allocated here once, as the align scratch is on the first
@@ -173,6 +195,7 @@ static int make_gen_ctx(wis_model* m, const float* input, int B, const int32_t* 
   int max_new = o->max_new_tokens > 0 ? o->max_new_tokens : std::min(c.n_text_ctx / 2, c.n_text_ctx - P);
   if (max_new > MAX_STEPS) max_new = MAX_STEPS;
   if (P - 1 + max_new > c.n_text_ctx) max_new = c.n_text_ctx - (P - 1);
+  WIS_RET(resolve_hotword_opts(m, o, draft != nullptr, &g));      // (ahead of the phrase options: hotwords with phrases is refused as such, whatever the phrase set's state)
   WIS_RET(resolve_phrase_opts(m, o, draft != nullptr, &g, &max_new));
   g.max_new = max_new;
   for (int i = 0; i < n_prompt; ++i) if (prompt[i] < 0 || prompt[i] >= c.n_vocab) { set_error("prompt token %d out of range", prompt[i]); return WIS_E_ARG; }
@@ -262,7 +285,7 @@ static int front_half(const GenCtx& g) {
   return WIS_OK;
 }
 
-// The sampling tail of a decoder pass: [repetition rules ->] [phrase mask ->] [timestamp rules ->] candidate statistics -> beam step -> cache reorder.  The logits row of (b, j) is
+// The sampling tail of a decoder pass: [repetition rules ->] [phrase mask | hotword boost ->] [timestamp rules ->] candidate statistics -> beam step -> cache reorder.  The logits row of (b, j) is
 // b*rows.b + j*rows.j + rows.off: a step samples beam j from row b*beam + j {beam, 1, 0}, the pass that carries the prompt samples every beam from the
 // last prompt row {P, 0, P - 1}.  TAIL_TAPS: the tap build's stamp rows of the two sampling kernels (the product build carries none).
 // TAIL_NO_CACHE: a search over given logits has no cache to reorder (wis_debug_search).
@@ -275,6 +298,7 @@ static int sampling_tail(const SampleCtx& g, LogitRows rows, int flags) {
   if (g.rep()) WIS_RET(launch_rep_rules(st, m->logits, m->bs, g.B, g.sc, g.rep_pen, g.rep_ngram, lr_b, lr_j, lr_off));
   if (g.phrases && !g.phr_mass) WIS_RET(launch_phrase_rules(st, m->logits, m->bs, g.B, g.sc, m->d_trie, m->phr_n, lr_b, lr_j, lr_off));
   if (g.phrases && g.phr_mass) WIS_RET(launch_phrase_rules_mass(st, m->logits, m->bs, g.B, g.sc, m->d_trie, m->phr_n, lr_b, lr_j, lr_off, g.bias_all, m->bias_begin, m->d_logmass, PHRASE_MASS_LD));
+  if (g.hotwords) WIS_RET(launch_hotword_rules(st, m->logits, m->bs, g.B, g.sc, m->d_hot, m->d_hot_ctl, lr_b, lr_j, lr_off));
   if (g.ts) WIS_RET(launch_ts_rules(st, m->logits, g.bias_all, m->bias_begin, m->bs, g.B, g.sc, c.no_timestamps, g.ts_max_init, lr_b, lr_j, lr_off, m->ts_desc));
   if (g.sampling()) {      // statistics (whole vocabulary: perturbed) -> sample step; every row continues itself: the cache moves only behind the prompt pass
     WIS_RET(launch_logit_stats(st, m->logits, g.bias_all, m->bias_begin, m->bs.step_u, m->st_max, m->st_sum, m->st_val, m->st_idx, g.B, g.sc, lr_b, lr_j, lr_off, nullptr,
@@ -658,6 +682,7 @@ struct StepGraph {
     key.rep_pen = g.rep_pen == 1.f ? 0.f : g.rep_pen; key.rep_ngram = g.rep_ngram;      // (off: the zeroes of a key that never knew the fields)
     key.samp_topk = g.sp.topk; key.samp_T = g.sampling() ? g.sp.T : 0.f; key.n_hyp = g.n_res > 1 ? g.n_res : 0;      // (the seeds are device memory: no part of the key)
     key.phrases = g.phrases ? (g.phr_mass ? 2 : 1) : 0;      // (the set is device memory behind a pointer that never changes: installing another needs no new graph)
+    key.hotwords = g.hotwords ? 1 : 0;      // (the set, its record count and the boost are device memory behind pointers that never change: one graph serves every set and every boost)
     auto it = m->graphs.find(key);
     if (it != m->graphs.end()) { *out = it->second; return WIS_OK; }
     hipGraph_t graph = nullptr; hipGraphExec_t ge = nullptr;
@@ -853,6 +878,7 @@ static int generate_impl(wis_model_t* m, const float* input, int B, const int32_
   WIS_RET(make_gen_ctx(m, input, B, prompt, P, o, draft, n_draft, draft_org, seeds, single, plen_v, &g));
   hipStream_t st = g.st;
   if (g.phr_mass) WIS_RET(phrase_mass_begin(m, B, st));
+  if (g.hotwords) WIS_RET(hotword_begin(m, g.hot_boost, st));
   WIS_RET(stage_search(g));
   WIS_RET(front_half(g));
 
@@ -919,10 +945,12 @@ static int debug_search_impl(const char* who, wis_model_t* m, const float* logit
   WIS_RET(check_batch(m, B, beam));
   if (!g.sampling()) WIS_RET(check_patience(beam, o->patience));
   int max_new = o->max_new_tokens > 0 ? std::min(o->max_new_tokens, MAX_STEPS) : n_steps;
+  WIS_RET(resolve_hotword_opts(m, o, false, &g));
   WIS_RET(resolve_phrase_opts(m, o, false, &g, &max_new));
   if (max_new > n_steps) { set_error("%s: %d steps of logits for max_new_tokens %d", who, n_steps, max_new); return WIS_E_ARG; }
   hipStream_t st = m->st;
   if (g.phr_mass) WIS_RET(phrase_mass_begin(m, B, st));
+  if (g.hotwords) WIS_RET(hotword_begin(m, g.hot_boost, st));
   const int Mrows = B * beam, V = c.n_vocab;
   float patience;
   WIS_RET(resolve_rep_opts(o, &g));
@@ -993,6 +1021,7 @@ int wis_generate_draft(wis_model_t* m, const float* input, const int32_t* prompt
   if (!m || !input || !prompt || !o || !out_ids || !out_len || (n_draft > 0 && !draft) || n_draft < 0) { set_error("wis_generate_draft: bad argument"); return WIS_E_ARG; }
   if (o->timestamps) { set_error("wis_generate_draft: timestamps are not available for drafted decodes"); return WIS_E_UNSUPPORTED; }
   if (o->phrases) { set_error("wis_generate_draft: phrases are not available for drafted decodes"); return WIS_E_UNSUPPORTED; }
+  if (o->hotwords) { set_error("wis_generate_draft: hotwords are not available for drafted decodes"); return WIS_E_UNSUPPORTED; }
   if ((o->repetition_penalty != 0.f && o->repetition_penalty != 1.f) || o->no_repeat_ngram_size != 0) { set_error("wis_generate_draft: repetition_penalty / no_repeat_ngram_size are not available for drafted decodes"); return WIS_E_UNSUPPORTED; }
   if ((o->sampling_topk != 0 && o->sampling_topk != 1) || (o->sampling_temperature != 0.f && o->sampling_temperature != 1.f) || (o->num_hypotheses != 0 && o->num_hypotheses != 1)) { set_error("wis_generate_draft: sampling_topk / sampling_temperature / num_hypotheses are not available for drafted decodes"); return WIS_E_UNSUPPORTED; }
   WIS_ENTER(m, "wis_generate_draft")
@@ -1007,6 +1036,7 @@ int wis_generate_draft_beam(wis_model_t* m, const float* input, const int32_t* p
   if (!m || !input || !prompt || !o || !out_ids || !out_len || n_steps < 0 || (n_steps > 0 && (!draft_tok || !draft_org))) { set_error("wis_generate_draft_beam: bad argument"); return WIS_E_ARG; }
   if (o->timestamps) { set_error("wis_generate_draft_beam: timestamps are not available for drafted decodes"); return WIS_E_UNSUPPORTED; }
   if (o->phrases) { set_error("wis_generate_draft_beam: phrases are not available for drafted decodes"); return WIS_E_UNSUPPORTED; }
+  if (o->hotwords) { set_error("wis_generate_draft_beam: hotwords are not available for drafted decodes"); return WIS_E_UNSUPPORTED; }
   if ((o->repetition_penalty != 0.f && o->repetition_penalty != 1.f) || o->no_repeat_ngram_size != 0) { set_error("wis_generate_draft_beam: repetition_penalty / no_repeat_ngram_size are not available for drafted decodes"); return WIS_E_UNSUPPORTED; }
   if ((o->sampling_topk != 0 && o->sampling_topk != 1) || (o->sampling_temperature != 0.f && o->sampling_temperature != 1.f) || (o->num_hypotheses != 0 && o->num_hypotheses != 1)) { set_error("wis_generate_draft_beam: sampling_topk / sampling_temperature / num_hypotheses are not available for drafted decodes"); return WIS_E_UNSUPPORTED; }
   WIS_ENTER(m, "wis_generate_draft_beam")

@@ -219,6 +219,13 @@ int launch_phrase_rules_mass(hipStream_t st, float* logits, const BeamState& bs,
 int launch_phrase_mass_gather(hipStream_t st, const int* ids, const int* len, const float* score, const int4* trie, int n_rec, const float* logmass, int lm_ld,
                               int B, int n, int id_ld, float* out);
 constexpr int PHRASE_MASS_LD = 65536;      // floats per utterance of a handle's logmass buffer (>= PHRASE_MAX_RECORDS)
+// hotword boosting (dec_kernels.hip hotword_rules_kernel; include/wis_hip.h, THE HOTWORD RULE): per live row, every token that continues a suffix
+// of the row's generated history along the flat trie (the root's children always) gets ONE fp32 addition of *boost in the row of `logits` the
+// step samples from; behind launch_rep_rules, ahead of everything else of the tail; rows as launch_logit_stats reads them.  trie: device, records
+// in launch_phrase_rules' format; ctl: device, {the boost's fp32 bits, the record count}, read by the kernel (a captured launch carries the
+// address, neither value)
+int launch_hotword_rules(hipStream_t st, float* logits, const BeamState& bs, int B, const SampleCfg& cfg, const int4* trie, const int* ctl,
+                         int lr_b, int lr_j, int lr_off);
 // probability of <|nospeech|> under the full-vocabulary softmax of each utterance's <|startoftranscript|> row (b * rs + r0)
 int launch_no_speech(hipStream_t st, const float* logits, int ld, int B, int rs, int r0, int V, int ns, float* out);
 // ... with the row of every utterance in device memory (rows [B]; a value outside [0, rs): utterance b is not in this pass, out[b] stays as it is)

@@ -548,7 +548,10 @@ static int alloc_buffers(wis_model* m) {
   WIS_RET(dalloc(m, &m->lm_gmax, Bm));
   WIS_RET(dalloc(m, &m->d_probs, (size_t)Bm * (c.n_lang > 0 ? c.n_lang : 1)));
   WIS_RET(dalloc(m, &m->d_prof, ((size_t)c.n_dec_layers * 8 + 2) * 16));   // + sampling kernels (tap builds)
-  WIS_RET(dalloc(m, &m->d_trie, (size_t)PHRASE_MAX_RECORDS));      // (the last buffer carved: every other one lies where it lay before the phrase set existed)
+  WIS_RET(dalloc(m, &m->d_trie, (size_t)PHRASE_MAX_RECORDS));      // (carved behind every buffer that existed before the phrase set did: each lies where it lay)
+  WIS_RET(dalloc(m, &m->d_hot, (size_t)PHRASE_MAX_RECORDS + 1));      // (the last buffer carved, for the same reason; its last record holds the kernel's two control words)
+  m->d_hot_ctl = reinterpret_cast<int*>(m->d_hot + PHRASE_MAX_RECORDS);
+  WIS_HIP_CHECK(hipMemsetAsync(m->d_hot_ctl, 0, 16, m->st));
   WIS_HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&m->h_pin), sizeof(PinnedScratch), hipHostMallocDefault));
   // fine-grained (coherent) host memory mapped into the device: beam_step_kernel's system-scope stores land here while the
   // stream is still running
@@ -1044,6 +1047,46 @@ int single_row_setup(wis_model* m, int n, const std::vector<int>& tok, int pos) 
 
 std::atomic<int> g_active_calls[64];      // compute calls running per device, every handle and entry point (model.hpp BusyGuard); read by front_half's stream choice (generate.hip)
 
+
+// The validator of a flat token trie (include/wis_hip.h has the layout and its rules).  EVERYTHING is checked here, on the host, before a byte
+// reaches the device: the records are walked in index order with one running cursor - a node's children must start exactly where the previous
+// node's ended - so every record but the root is the child of exactly one earlier record, no range leaves the table and no walk can cycle.
+int validate_token_trie(const char* who, const int32_t* trie, int n, int n_vocab, int eot, const unsigned char* tok_flags, int* deepest_out) {
+  if (n > PHRASE_MAX_RECORDS) { set_error("%s: %d records (at most %d)", who, n, PHRASE_MAX_RECORDS); return WIS_E_UNSUPPORTED; }
+  auto bad = [who](const char* what, int i) { set_error("%s: record %d: %s", who, i, what); return WIS_E_ARG; };
+  std::vector<int> depth((size_t)n, 0);
+  int cursor = 1, deepest = 0;
+  for (int i = 0; i < n; ++i) {
+    const int32_t tok = trie[4 * i], first = trie[4 * i + 1], nc = trie[4 * i + 2], ends = trie[4 * i + 3];
+    if (i >= cursor) return bad("not the child of an earlier record (tree order)", i);
+    if (ends != 0 && ends != 1) return bad("the phrase-end flag is 0 or 1", i);
+    if (i == 0) {
+      if (tok != -1 || ends != 0 || nc < 1) return bad("the root's pseudo-edge is {-1, 1, children >= 1, 0}", i);
+    } else {
+      if (tok < 0 || tok >= eot || tok >= n_vocab) return bad("the token is no text token (0 <= id < <|endoftext|>)", i);
+      if (tok_flags && (tok_flags[tok] & 1)) return bad("the token is in the model's suppress_ids", i);
+      if (tok_flags && depth[i] == 1 && (tok_flags[tok] & 2)) return bad("a phrase's first token is in the model's suppress_ids_begin", i);
+    }
+    if (nc < 0) return bad("a negative number of children", i);
+    if (nc > PHRASE_MAX_CHILDREN) { set_error("%s: record %d: %d children (at most %d per node)", who, i, nc, PHRASE_MAX_CHILDREN); return WIS_E_UNSUPPORTED; }
+    if (nc == 0) {
+      if (first != 0) return bad("a leaf's first-child index is 0", i);
+      if (!ends) return bad("a leaf that ends no phrase", i);
+      continue;
+    }
+    if (first != cursor || nc > n - cursor) return bad("the children do not follow the previous node's (tree order), or leave the table", i);
+    if (depth[i] + 1 > PHRASE_MAX_DEPTH) { set_error("%s: record %d: a phrase of more than %d tokens", who, i, PHRASE_MAX_DEPTH); return WIS_E_UNSUPPORTED; }
+    for (int k = 0; k < nc; ++k) {
+      depth[cursor + k] = depth[i] + 1;
+      if (k > 0 && trie[4 * (cursor + k)] <= trie[4 * (cursor + k - 1)]) return bad("children not in strictly ascending token order", cursor + k);
+    }
+    deepest = std::max(deepest, depth[i] + 1);
+    cursor += nc;
+  }
+  if (cursor != n) { set_error("%s: %d records, the tree holds %d", who, n, cursor); return WIS_E_ARG; }
+  if (deepest_out) *deepest_out = deepest;
+  return WIS_OK;
+}
 }  // namespace wis
 
 // =======================================================================================
@@ -1203,52 +1246,35 @@ int wis_last_trajectory(wis_model_t* m, int b, int32_t* tok, int32_t* org, int c
   return WIS_OK;
 }
 
-// Installs a phrase set (include/wis_hip.h has the layout and its rules).  EVERYTHING is checked here, on the host, before a byte reaches the
-// device: the records are walked in index order with one running cursor - a node's children must start exactly where the previous node's
-// ended - so every record but the root is the child of exactly one earlier record, no range leaves the table and no walk can cycle.
+// Installs a phrase set: validated on the host (validate_token_trie), then one copy into the handle's buffer.
 int wis_model_set_phrases(wis_model_t* m, const int32_t* trie, int n_records) {
   if (!m || n_records < 0 || (n_records > 0 && !trie)) { set_error("wis_model_set_phrases: bad argument"); return WIS_E_ARG; }
   WIS_ENTER(m, "wis_model_set_phrases")
   if (n_records == 0) { m->phr_n = 0; m->phr_depth = 0; return WIS_OK; }
-  if (n_records > PHRASE_MAX_RECORDS) { set_error("wis_model_set_phrases: %d records (at most %d)", n_records, PHRASE_MAX_RECORDS); return WIS_E_UNSUPPORTED; }
-  const wis_config_t& c = m->cfg;
   const int n = n_records;
-  auto bad = [](const char* what, int i) { set_error("wis_model_set_phrases: record %d: %s", i, what); return WIS_E_ARG; };
-  std::vector<int> depth((size_t)n, 0);
-  int cursor = 1, deepest = 0;
-  for (int i = 0; i < n; ++i) {
-    const int32_t tok = trie[4 * i], first = trie[4 * i + 1], nc = trie[4 * i + 2], ends = trie[4 * i + 3];
-    if (i >= cursor) return bad("not the child of an earlier record (tree order)", i);
-    if (ends != 0 && ends != 1) return bad("the phrase-end flag is 0 or 1", i);
-    if (i == 0) {
-      if (tok != -1 || ends != 0 || nc < 1) return bad("the root's pseudo-edge is {-1, 1, children >= 1, 0}", i);
-    } else {
-      if (tok < 0 || tok >= c.eot || tok >= c.n_vocab) return bad("the token is no text token (0 <= id < <|endoftext|>)", i);
-      if (m->tok_flags[tok] & 1) return bad("the token is in the model's suppress_ids", i);
-      if (depth[i] == 1 && (m->tok_flags[tok] & 2)) return bad("a phrase's first token is in the model's suppress_ids_begin", i);
-    }
-    if (nc < 0) return bad("a negative number of children", i);
-    if (nc > PHRASE_MAX_CHILDREN) { set_error("wis_model_set_phrases: record %d: %d children (at most %d per node)", i, nc, PHRASE_MAX_CHILDREN); return WIS_E_UNSUPPORTED; }
-    if (nc == 0) {
-      if (first != 0) return bad("a leaf's first-child index is 0", i);
-      if (!ends) return bad("a leaf that ends no phrase", i);
-      continue;
-    }
-    if (first != cursor || nc > n - cursor) return bad("the children do not follow the previous node's (tree order), or leave the table", i);
-    if (depth[i] + 1 > PHRASE_MAX_DEPTH) { set_error("wis_model_set_phrases: record %d: a phrase of more than %d tokens", i, PHRASE_MAX_DEPTH); return WIS_E_UNSUPPORTED; }
-    for (int k = 0; k < nc; ++k) {
-      depth[cursor + k] = depth[i] + 1;
-      if (k > 0 && trie[4 * (cursor + k)] <= trie[4 * (cursor + k - 1)]) return bad("children not in strictly ascending token order", cursor + k);
-    }
-    deepest = std::max(deepest, depth[i] + 1);
-    cursor += nc;
-  }
-  if (cursor != n) { set_error("wis_model_set_phrases: %d records, the tree holds %d", n, cursor); return WIS_E_ARG; }
+  int deepest = 0;
+  WIS_RET(validate_token_trie("wis_model_set_phrases", trie, n, m->cfg.n_vocab, m->cfg.eot, m->tok_flags.data(), &deepest));
   WIS_HIP_CHECK(hipSetDevice(m->device));
   m->phr_n = 0;      // (a failed copy leaves no set behind)
   WIS_HIP_CHECK(hipMemcpyAsync(m->d_trie, trie, (size_t)n * 16, hipMemcpyHostToDevice, m->st));      // behind whatever step of an earlier call is still queued
   WIS_HIP_CHECK(hipStreamSynchronize(m->st));
   m->phr_n = n; m->phr_depth = deepest;
+  return WIS_OK;
+}
+
+// ... and a hotword set (THE HOTWORD RULE): the same table, the same validator, a buffer of its own - neither set disturbs the other
+int wis_model_set_hotwords(wis_model_t* m, const int32_t* trie, int n_records) {
+  if (!m || n_records < 0 || (n_records > 0 && !trie)) { set_error("wis_model_set_hotwords: bad argument"); return WIS_E_ARG; }
+  WIS_ENTER(m, "wis_model_set_hotwords")
+  if (n_records == 0) { m->hot_n = 0; return WIS_OK; }
+  const int n = n_records;
+  WIS_RET(validate_token_trie("wis_model_set_hotwords", trie, n, m->cfg.n_vocab, m->cfg.eot, m->tok_flags.data(), nullptr));
+  WIS_HIP_CHECK(hipSetDevice(m->device));
+  m->hot_n = 0;      // (a failed copy leaves no set behind)
+  WIS_HIP_CHECK(hipMemcpyAsync(m->d_hot, trie, (size_t)n * 16, hipMemcpyHostToDevice, m->st));      // behind whatever step of an earlier call is still queued
+  WIS_HIP_CHECK(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(m->d_hot_ctl + 1), n, 1, m->st));      // (the record count the kernel checks its ranges against)
+  WIS_HIP_CHECK(hipStreamSynchronize(m->st));
+  m->hot_n = n;
   return WIS_OK;
 }
 

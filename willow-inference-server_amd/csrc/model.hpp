@@ -46,6 +46,7 @@ struct GraphKey {
   float rep_pen; int rep_ngram;  // rep_rules_kernel at the head of the tail (both 0: off, no such launch)
   int samp_topk; float samp_T; int n_hyp;      // sampled decode (sample_step_kernel in beam_step_kernel's place) / results per utterance; all 0: off, one result
   int phrases;                   // phrase_rules_kernel behind rep_rules_kernel (0: off, no such launch; 2: phrase_rules_mass_kernel in its place; the set itself is device memory: no part of the key)
+  int hotwords;                  // hotword_rules_kernel behind rep_rules_kernel (0: off, no such launch; the set AND the boost are device memory: no part of the key)
   bool operator<(const GraphKey& o) const { return memcmp(this, &o, sizeof(GraphKey)) < 0; }
 };
 
@@ -196,6 +197,10 @@ struct wis_model {
   // call computed the mass, else 0 (wis_last_phrase_mass answers WIS_E_STATE)
   float* d_logmass = nullptr; float* d_phr_mass = nullptr; int phr_mass_B = 0, phr_mass_n = 0;
   std::vector<unsigned char> tok_flags;
+  // hotword boosting (wis_model_set_hotwords): a second set, apart from the phrase set, in a buffer of its own of the same fixed capacity - the
+  // LAST buffer carved - and its record count (0: no set); d_hot_ctl: the two words {boost bits, record count} behind the table that hotword_rules_kernel
+  // reads - the boost written ahead of every call's steps (as the sampling seeds are), the count with the set: one captured step serves every value
+  int4* d_hot = nullptr; int hot_n = 0; int* d_hot_ctl = nullptr;
 };
 
 namespace wis {
@@ -285,6 +290,9 @@ void frag_set_ksplit(GemvP& g, int ks, float* part, unsigned* cnt);
 // ---- search state ----------------------------------------------------------------------------------------------------------------------
 int init_beam_state(wis_model* m, int B, int beam, bool samples = false, int n_res = 1);
 int upload_seeds(wis_model* m, const uint64_t* seeds, int B);
+// the ONE validator of a flat token trie (wis_model_set_phrases, wis_model_set_hotwords, wis_op_hotword_rules): n >= 1 records of four int32 on the
+// host; tok_flags: the model's suppress bits per token id (null: none known); *deepest: the longest entry.  `who` leads the messages
+int validate_token_trie(const char* who, const int32_t* trie, int n, int n_vocab, int eot, const unsigned char* tok_flags, int* deepest);
 SampleCfg make_sample_cfg(const wis_model* m, const wis_gen_opts_t* o, int beam, int max_new, float* patience_out);
 int check_patience(int beam, float patience);
 

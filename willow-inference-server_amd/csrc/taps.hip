@@ -737,6 +737,31 @@ int wis_op_phrase_mass_gather(int device, const int32_t* ids, const int32_t* len
   return t.finish(launch_phrase_mass_gather(t.st, ids, len, score, reinterpret_cast<const int4*>(trie), n_rec, logmass, n_rec, B, n, id_ld, out));
 }
 
+// the hotword boost of one step on caller-supplied rows, histories and trie (tests/test_gpu_hotword_ops.py); the table is read back and validated
+// on the host before anything is launched
+int wis_op_hotword_rules(int device, float* logits, int n_vocab, int n_vocab_pad, int eot, const int32_t* trie, int n_rec, const int32_t* alive,
+                         const int32_t* step_u, const int32_t* done, int B, int beam, int max_new, int fixed_new, float boost,
+                         int lr_b, int lr_j, int lr_off) {
+  Tap t(device, "wis_op_hotword_rules"); WIS_RET(t.rc);
+  if (!logits || !trie || !alive || !step_u || !done || n_rec < 1 || n_rec > PHRASE_MAX_RECORDS || n_vocab < 1 || n_vocab > 65536 || n_vocab_pad < n_vocab ||
+      eot < 0 || eot >= n_vocab || B < 1 || beam < 1 || beam > MAX_R || B * beam > MAX_ROWS || max_new < 1 || max_new > MAX_STEPS || fixed_new < 0 ||
+      !std::isfinite(boost) || !(boost > 0.f) || lr_b < 0 || lr_j < 0 || lr_off < 0) {
+    set_error("wis_op_hotword_rules: bad argument"); return WIS_E_ARG; }
+  std::vector<int32_t> host((size_t)n_rec * 4);
+  WIS_HIP_CHECK(hipMemcpy(host.data(), trie, host.size() * 4, hipMemcpyDeviceToHost));
+  const int vrc = validate_token_trie("wis_op_hotword_rules", host.data(), n_rec, n_vocab, eot, nullptr, nullptr);
+  if (vrc != WIS_OK) return WIS_E_ARG;      // (a table beyond the limits too: this entry point answers every malformed table alike)
+  int ctl_h[4] = {0, n_rec, 0, 0}; memcpy(&ctl_h[0], &boost, 4);
+  int* ctl = nullptr;
+  WIS_RET(t.get(&ctl, 4));
+  WIS_HIP_CHECK(hipMemcpy(ctl, ctl_h, sizeof(ctl_h), hipMemcpyHostToDevice));
+  SampleCfg sc; memset(&sc, 0, sizeof(sc));
+  sc.n_vocab = n_vocab; sc.n_vocab_pad = n_vocab_pad; sc.eot = eot; sc.beam = beam; sc.max_new = max_new; sc.fixed_new = fixed_new;
+  BeamState bs; memset(&bs, 0, sizeof(bs));
+  bs.alive = const_cast<int*>(alive); bs.step_u = const_cast<int*>(step_u); bs.done = const_cast<int*>(done);
+  return t.finish(launch_hotword_rules(t.st, logits, bs, B, sc, reinterpret_cast<const int4*>(trie), ctl, lr_b, lr_j, lr_off));
+}
+
 // ---- the resampler's kernel alone (tests/test_gpu_resample_ops.py): one launch of csrc/resample.hip on a caller-supplied slice of a longer signal
 int wis_op_resample_segment(int device, const float* x_slice, int64_t n_slice, int64_t k_base, int64_t n_in_total, int64_t m0, int64_t count,
                             int up, int down, float* out) {

@@ -47,6 +47,28 @@ class GenOpts(C.Structure):
                 ("phrase_mass", C.c_int32)]
 
 
+class HotGenOpts(GenOpts):
+    """wis_gen_opts_t in full: GenOpts - the struct as far as phrase_mass, where every field lies where it always lay - and the two fields
+    appended behind it (a ctypes subclass lays its own fields out behind its base's: exactly the C layout)."""
+    _fields_ = [("hotwords", C.c_int32), ("hotword_boost", C.c_float)]
+
+
+class _OptsArg:
+    """The options argument of every entry point that takes a wis_gen_opts_t*.  The engine reads the WHOLE struct, so a GenOpts - given as
+    such or through ctypes.byref - goes to it as a HotGenOpts whose appended fields are zero: what a caller that never knew them passes."""
+
+    @classmethod
+    def from_param(cls, obj):
+        o = getattr(obj, "_obj", obj)      # (ctypes.byref(x) -> x)
+        if isinstance(o, HotGenOpts):
+            return C.byref(o)
+        if not isinstance(o, GenOpts):
+            raise TypeError(f"expected a GenOpts, got {type(o).__name__}")
+        full = HotGenOpts()
+        C.memmove(C.addressof(full), C.addressof(o), C.sizeof(GenOpts))
+        return C.byref(full)               # (the returned object keeps `full` alive for the length of the call)
+
+
 class Timing(C.Structure):
     _fields_ = [("logmel_ms", C.c_float), ("encoder_ms", C.c_float), ("crosskv_ms", C.c_float), ("prefill_ms", C.c_float),
                 ("decode_ms", C.c_float), ("total_ms", C.c_float), ("decode_steps", C.c_int32), ("decode_steps_needed", C.c_int32)]
@@ -99,13 +121,13 @@ SYMBOLS = [
     ("wis_model_destroy", None, [_vp]),
     ("wis_model_device_bytes", _sz, [_vp]),
     ("wis_model_clone", _i, [_vp, C.POINTER(_vp)]),
-    ("wis_generate", _i, [_vp, _vp, _i, C.POINTER(C.c_int32), _i, C.POINTER(GenOpts), C.POINTER(C.c_int32), C.POINTER(C.c_int32), _fp]),
-    ("wis_generate_n", _i, [_vp, _vp, _i, C.POINTER(C.c_int32), _i, C.POINTER(GenOpts), C.POINTER(C.c_uint64), C.POINTER(C.c_int32), C.POINTER(C.c_int32), _fp]),
-    ("wis_generate_ragged", _i, [_vp, _vp, _i, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(GenOpts), C.POINTER(C.c_uint64), C.POINTER(C.c_int32),
+    ("wis_generate", _i, [_vp, _vp, _i, C.POINTER(C.c_int32), _i, _OptsArg, C.POINTER(C.c_int32), C.POINTER(C.c_int32), _fp]),
+    ("wis_generate_n", _i, [_vp, _vp, _i, C.POINTER(C.c_int32), _i, _OptsArg, C.POINTER(C.c_uint64), C.POINTER(C.c_int32), C.POINTER(C.c_int32), _fp]),
+    ("wis_generate_ragged", _i, [_vp, _vp, _i, C.POINTER(C.c_int32), C.POINTER(C.c_int32), _OptsArg, C.POINTER(C.c_uint64), C.POINTER(C.c_int32),
                                  C.POINTER(C.c_int32), _fp]),
-    ("wis_generate_draft", _i, [_vp, _vp, C.POINTER(C.c_int32), _i, C.POINTER(GenOpts), C.POINTER(C.c_int32), _i, C.POINTER(C.c_int32), C.POINTER(C.c_int32), _fp,
+    ("wis_generate_draft", _i, [_vp, _vp, C.POINTER(C.c_int32), _i, _OptsArg, C.POINTER(C.c_int32), _i, C.POINTER(C.c_int32), C.POINTER(C.c_int32), _fp,
                                 C.POINTER(C.c_int32)]),
-    ("wis_generate_draft_beam", _i, [_vp, _vp, C.POINTER(C.c_int32), _i, C.POINTER(GenOpts), C.POINTER(C.c_int32), C.POINTER(C.c_int32), _i, C.POINTER(C.c_int32),
+    ("wis_generate_draft_beam", _i, [_vp, _vp, C.POINTER(C.c_int32), _i, _OptsArg, C.POINTER(C.c_int32), C.POINTER(C.c_int32), _i, C.POINTER(C.c_int32),
                                      C.POINTER(C.c_int32), _fp, C.POINTER(C.c_int32)]),
     ("wis_last_trajectory", _i, [_vp, _i, C.POINTER(C.c_int32), C.POINTER(C.c_int32), _i, C.POINTER(C.c_int32)]),
     ("wis_last_no_speech_prob", _i, [_vp, _i, _fp]),
@@ -117,6 +139,7 @@ SYMBOLS = [
     ("wis_model_set_alignment_heads", _i, [_vp, C.POINTER(C.c_int32), _i]),
     ("wis_model_set_phrases", _i, [_vp, C.POINTER(C.c_int32), _i]),
     ("wis_last_phrase_mass", _i, [_vp, _i, _i, _fp]),
+    ("wis_model_set_hotwords", _i, [_vp, C.POINTER(C.c_int32), _i]),
     ("wis_align", _i, [_vp, _vp, _i, _i, C.POINTER(C.c_int32), _i, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), _i,
                        C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), _fp]),
     ("wis_debug_align_matrix", _i, [_vp, _vp, _i, _i, C.POINTER(C.c_int32), _i, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), _i, _fp]),
@@ -128,8 +151,8 @@ SYMBOLS = [
     ("wis_op_align_probs", _i, [_i, _vp, _i, _i, _i, _vp, _vp, _vp, _i]),
     ("wis_op_align_capture", _i, [_i, _vp, _i, _i, _vp] + [_i] * 7 + [_vp, _i64]),
     ("wis_debug_tree_logits", _i, [_vp, _vp, _i, C.POINTER(C.c_int32), _i, _i, C.POINTER(C.c_int32), C.POINTER(C.c_int32), _i, _fp]),
-    ("wis_debug_search", _i, [_vp, _vp, _i, _i, C.POINTER(GenOpts), C.POINTER(C.c_int32), C.POINTER(C.c_int32), _fp, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
-    ("wis_debug_search_n", _i, [_vp, _vp, _i, _i, C.POINTER(GenOpts), C.POINTER(C.c_uint64), C.POINTER(C.c_uint32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), _fp,
+    ("wis_debug_search", _i, [_vp, _vp, _i, _i, _OptsArg, C.POINTER(C.c_int32), C.POINTER(C.c_int32), _fp, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    ("wis_debug_search_n", _i, [_vp, _vp, _i, _i, _OptsArg, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), _fp,
                                 C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     ("wis_debug_handoff", _i, [_vp, _i, C.POINTER(_i), C.POINTER(_i)]),
     ("wis_debug_graph_count", _i, [_vp, C.POINTER(_i)]),
@@ -178,6 +201,7 @@ SYMBOLS = [
     ("wis_op_phrase_rules", _i, [_i, _vp, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i]),
     ("wis_op_phrase_mass", _i, [_i, _vp, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _i, _vp]),
     ("wis_op_phrase_mass_gather", _i, [_i, _vp, _vp, _vp, _vp, _i, _vp, _i, _i, _i, _vp]),
+    ("wis_op_hotword_rules", _i, [_i, _vp, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, C.c_float, _i, _i, _i]),
     ("wis_sv_create", _i, [C.POINTER(SvConfig), _vp, _sz, _i, C.POINTER(Tensor), _i, _i, C.POINTER(_vp)]),
     ("wis_sv_destroy", None, [_vp]),
     ("wis_sv_device_bytes", _sz, [_vp]),

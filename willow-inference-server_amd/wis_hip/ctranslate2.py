@@ -168,6 +168,7 @@ class _Replica:
         self.inflight = 0
         self.stage = None           # device block for batches of device-resident features (lazy)
         self.phrase_digest = None   # digest of the phrase set installed on the handle (wis_model_set_phrases), None: none yet
+        self.hotword_digest = None  # ... of the hotword set (wis_model_set_hotwords)
 
 
 def special_tokens_for(a, special=None, lang_ids=None):
@@ -361,6 +362,62 @@ class ConstrainedOptions(DecodeOptions):
         return (ConstrainedOptions, (DecodeOptions(*self), self.phrase_trie, self.phrase_digest, self.phrase_mass))
 
 
+class BoostedOptions(DecodeOptions):
+    """The DecodeOptions of a hotword-boosted call (`generate(..., hotwords=..., hotword_boost=b)`): the same record - `_fields` and every value a
+    plain call with these arguments would have - that carries the call's hotword set and boost beside it: `hotword_trie` (int32 [n][4],
+    weights.build_hotword_trie), `hotword_digest` (its SHA-256) and `hotword_boost` (a float).  Digest, boost and type take part in equality and
+    hash: two calls share a device batch exactly when their options, their hotword sets AND their boosts are equal, and a boosted record never
+    equals a plain or a constrained one.  The batch runner installs the set on the replica when the replica's current digest differs."""
+
+    def __new__(cls, base, trie, digest, boost):
+        self = tuple.__new__(cls, base)
+        self.hotword_trie, self.hotword_digest, self.hotword_boost = trie, digest, float(boost)
+        return self
+
+    def __eq__(self, other):
+        return (type(other) is BoostedOptions and tuple.__eq__(self, other) and self.hotword_digest == other.hotword_digest
+                and self.hotword_boost == other.hotword_boost)
+
+    def __ne__(self, other):
+        return not self == other
+
+    def __hash__(self):
+        return hash((tuple.__hash__(self), self.hotword_digest, self.hotword_boost))
+
+    def _replace(self, **kw):
+        return BoostedOptions(DecodeOptions(*self)._replace(**kw), self.hotword_trie, self.hotword_digest, self.hotword_boost)
+
+    def __reduce__(self):
+        return (BoostedOptions, (DecodeOptions(*self), self.hotword_trie, self.hotword_digest, self.hotword_boost))
+
+
+def _check_hotword_boost(boost):
+    """-> the boost as a float: finite and > 0 (a ValueError otherwise; no default is offered: a useful value depends on the checkpoint)"""
+    try:
+        b = float(boost)
+    except (TypeError, ValueError):
+        raise ValueError(f"hotword_boost {boost!r}: a finite number > 0") from None
+    with np.errstate(over="ignore", under="ignore"):
+        b32 = np.float32(b)      # (what the engine takes: a value that is 0 or inf in float32 is refused here, not there)
+    if not (np.isfinite(b) and b > 0 and np.isfinite(b32) and b32 > 0):
+        raise ValueError(f"hotword_boost {boost!r}: a finite number > 0")
+    return b
+
+
+def _hotword_set(hotwords, special, decode_config):
+    """-> (trie, digest) of a call's `hotwords` ([[token ids], ...]), validated against the MODEL's lists as a phrase list is"""
+    import hashlib
+    try:
+        hotwords = [list(hw) for hw in hotwords]
+    except TypeError:
+        raise ValueError(f"hotwords {hotwords!r}: a list of token id lists") from None
+    sup = decode_config.get("suppress_ids")
+    beg = decode_config.get("suppress_ids_begin")
+    trie = W.build_hotword_trie(hotwords, eot=special.eot, suppress_ids=special.default_suppress_ids() if sup is None else sup,
+                                suppress_begin=[220, special.eot] if beg is None else beg)
+    return trie, hashlib.sha256(trie.tobytes()).hexdigest()
+
+
 def _phrase_set(phrases, special, decode_config):
     """-> (trie, digest, longest phrase) of a call's `phrases` ([[token ids], ...]), validated against the MODEL's lists (what the engine checks
     again): a ValueError names the offending phrase."""
@@ -398,6 +455,11 @@ def _gen_opts(opts):
         o.sampling_topk, o.sampling_temperature, o.num_hypotheses = int(opts.sampling_topk), float(opts.sampling_temperature), int(opts.num_hypotheses)
     o.phrases = int(getattr(opts, "phrase_trie", None) is not None)
     o.phrase_mass = int(bool(getattr(opts, "phrase_mass", False)))
+    if getattr(opts, "hotword_trie", None) is not None:      # (only a boosted call builds the full struct: every other call's record is what it was)
+        full = _lib.HotGenOpts()
+        C.memmove(C.addressof(full), C.addressof(o), C.sizeof(_lib.GenOpts))
+        full.hotwords, full.hotword_boost = 1, float(opts.hotword_boost)
+        return full
     return o
 
 
@@ -418,6 +480,11 @@ def _generate_chunk(r, mel, prompts, opts, *rest, device_ptr=None, seeds=None):
         r.phrase_digest = None
         _lib.check(_lib.load().wis_model_set_phrases(r.handle, trie.ctypes.data_as(C.POINTER(C.c_int32)), len(trie)))
         r.phrase_digest = opts.phrase_digest
+    hot = getattr(opts, "hotword_trie", None)
+    if hot is not None and getattr(r, "hotword_digest", None) != opts.hotword_digest:      # (a copy too; the set and the boost are no part of a step graph)
+        r.hotword_digest = None
+        _lib.check(_lib.load().wis_model_set_hotwords(r.handle, hot.ctypes.data_as(C.POINTER(C.c_int32)), len(hot)))
+        r.hotword_digest = opts.hotword_digest
     order = None
     if P == RAGGED_PROMPT:
         if draft is not None or opts.return_trajectory:
@@ -917,7 +984,8 @@ class Whisper:
                  repetition_penalty=1, no_repeat_ngram_size=0, max_length=448, return_scores=False, return_no_speech_prob=False,
                  max_initial_timestamp_index=50, suppress_blank=True, suppress_tokens=(-1,), sampling_topk=1,
                  sampling_temperature=1, fixed_new_tokens=0, input_kind=_lib.WIS_IN_MEL_HOST, draft_tokens=None, draft_trajectory=None,
-                 return_trajectory=False, sampling_seed=None, ragged_prompts=False, phrases=None, return_phrase_mass=False):
+                 return_trajectory=False, sampling_seed=None, ragged_prompts=False, phrases=None, return_phrase_mass=False,
+                 hotwords=None, hotword_boost=None):
         """`draft_tokens` (one utterance, beam_size 1): the ids of an earlier hypothesis for this audio - wis_generate_draft verifies them in
         multi-row passes and decodes on behind the accepted prefix; the result is the greedy decode of THESE features either way.
         `draft_trajectory` (one utterance, beam_size > 1): `(tok, org)` as an earlier result's `.trajectory` gives it (`return_trajectory=True`) -
@@ -952,7 +1020,14 @@ class Whisper:
         `return_phrase_mass=True` (with `phrases`; without: ValueError) fills `phrase_logmass`, one float per returned hypothesis: the log of the share
         of the model's probability that the list allowed, summed over the phrase's steps and its <|endoftext|> - log P_unconstrained(phrase) -
         log P_constrained(phrase), near 0 when the audio says the phrase, strongly negative when the mask forced it (include/wis_hip.h, THE PHRASE
-        MASS RULE).  Ids and scores are those of the call without it."""
+        MASS RULE).  Ids and scores are those of the call without it.
+        `hotwords=[[token ids], ...], hotword_boost=b` (an extension of this shim): contextual biasing - free-form decoding goes on, and every token
+        that starts an entry of the list, or continues one that the hypothesis' last tokens have begun, has `b` added to its logit once per step
+        (include/wis_hip.h, THE HOTWORD RULE).  The scores are log-softmaxes of the BOOSTED rows.  There is no back-off: a hypothesis that leaves an
+        entry half-way keeps what it gained.  An entry holds 1 .. 32 text tokens outside the model's suppress lists; `b` is finite and > 0 and has no
+        default - calibrate it on the checkpoint in use.  Combines with timestamps, the repetition options, sampling, `num_hypotheses` and prompts of
+        any supported length; not with `phrases` or drafts (ValueError).  Calls share a device batch exactly when their options, their hotword lists
+        and their boosts are equal."""
         enc = self._encoder_input(features, input_kind)
         if enc is not None:
             n_utt = len(enc[2]) if enc[0] == _lib.WIS_IN_ENC_DEV else enc[1].shape[0]
@@ -964,7 +1039,7 @@ class Whisper:
                                          sampling_temperature=sampling_temperature, fixed_new_tokens=fixed_new_tokens, draft_tokens=draft_tokens,
                                          draft_trajectory=draft_trajectory, return_trajectory=return_trajectory, ragged_prompts=ragged_prompts,
                                          pool_long_prompts=getattr(self, "batch_ragged_prompts", False), phrases=phrases,
-                                         return_phrase_mass=return_phrase_mass)
+                                         return_phrase_mass=return_phrase_mass, hotwords=hotwords, hotword_boost=hotword_boost)
         seeds = _seeds(opts, sampling_seed, len(prompts))
         if enc is not None and enc[0] == _lib.WIS_IN_ENC_DEV:
             # every row carries the block its address points into: the rows themselves keep the device memory allocated until _run_batch has returned
@@ -976,12 +1051,13 @@ class Whisper:
     def _decode_options(self, features, prompts, *, input_kind, n_utt=1, beam_size, patience, num_hypotheses, length_penalty, repetition_penalty, no_repeat_ngram_size,
                         max_length, return_no_speech_prob, max_initial_timestamp_index, suppress_blank, suppress_default, sampling_topk, sampling_temperature,
                         fixed_new_tokens, draft_tokens, draft_trajectory, return_trajectory, ragged_prompts=False, pool_long_prompts=False, phrases=None,
-                        return_phrase_mass=False):
+                        return_phrase_mass=False, hotwords=None, hotword_boost=None):
         """Every check of a decode call, for `generate` (features: host arrays, one prompt each) and `generate_from_device` (features None: ONE
         utterance already on the device) -> (its DecodeOptions, the checked host features or None).  The engine's capacity limits are request
         errors (ValueError -> HTTP 400 in wis_hip.server), not internal ones.  ragged_prompts: the prompts may differ in length (the key then
         carries RAGGED_PROMPT).  pool_long_prompts (the setting batch_ragged_prompts): a call whose prompts are longer than SHORT_PROMPT gets the
-        pooled key whatever their lengths.  phrases: the call's phrase list -> a ConstrainedOptions; None: the plain record, as it has always been built."""
+        pooled key whatever their lengths.  phrases: the call's phrase list -> a ConstrainedOptions; None: the plain record, as it has always been built.
+        hotwords / hotword_boost: the call's hotword list and bonus -> a BoostedOptions."""
         drafted = bool(draft_tokens is not None and len(draft_tokens) or draft_trajectory is not None and len(draft_trajectory[0]))
         s_k, s_T, s_n = _check_sampling(beam_size, num_hypotheses, sampling_topk, sampling_temperature, drafted)
         if max(int(beam_size), s_n) > self.max_beam:
@@ -1046,6 +1122,18 @@ class Whisper:
             if opts.max_new_tokens < longest + 1:
                 raise ValueError(f"max_length {max_length} leaves {opts.max_new_tokens} steps behind a prompt of {P} tokens: the longest phrase needs {longest + 1}")
             opts = ConstrainedOptions(opts._replace(max_new_tokens=longest + 1), trie, digest, bool(return_phrase_mass))
+        if hotwords is None and hotword_boost is not None:
+            raise ValueError("hotword_boost needs hotwords (the list the boost applies to)")
+        if hotwords is not None:
+            if phrases is not None:
+                raise ValueError("hotwords cannot be combined with phrases (a constrained search has nothing left to bias)")
+            if drafted:
+                raise ValueError("hotwords cannot be combined with draft_tokens / draft_trajectory")
+            if hotword_boost is None:
+                raise ValueError("hotwords need a hotword_boost (finite, > 0; there is no default: calibrate it on the checkpoint in use)")
+            boost = _check_hotword_boost(hotword_boost)
+            trie, digest = _hotword_set(hotwords, self.special, getattr(self, "decode_config", None) or {})
+            opts = BoostedOptions(opts, trie, digest, boost)
         return opts, mel
 
     def load(self, device=None):
@@ -1074,7 +1162,7 @@ class Whisper:
                              suppress_blank=True, fixed_new_tokens=0, replica=None, draft_tokens=None, draft_trajectory=None, return_trajectory=False,
                              repetition_penalty=1, no_repeat_ngram_size=0, num_hypotheses=1, sampling_topk=1, sampling_temperature=1, sampling_seed=None,
                              return_scores=False, return_no_speech_prob=False, max_initial_timestamp_index=50, phrases=None,
-                             return_phrase_mass=False):
+                             return_phrase_mass=False, hotwords=None, hotword_boost=None):
         """One utterance whose log-mel features ALREADY live in HBM on `device` (f32 [n_mels][3000] at `mel_device_ptr`, e.g. an
         audio.MelStream after finish()): WIS_IN_MEL_DEV - nothing is staged through the host.  Goes through the micro-batcher bound
         to that DEVICE: any replica of the GPU can read the features, so concurrent windows of several streaming sessions on one GPU
@@ -1083,7 +1171,7 @@ class Whisper:
         As in `generate`: a start sequence without <|notimestamps|> (`timestamp_prompt`) decodes under Whisper's timestamp rules with
         `max_initial_timestamp_index`, `return_no_speech_prob=True` fills `no_speech_prob`, and drafts cannot be combined with either;
         `return_scores` is accepted for symmetry (the scores are always filled); `phrases` restricts the search to a phrase list and
-        `return_phrase_mass` fills `phrase_logmass`, as in `generate`."""
+        `return_phrase_mass` fills `phrase_logmass`, as in `generate`; `hotwords` / `hotword_boost` bias the search toward a list, as in `generate`."""
         # `replica`: the replica the caller holds (a streaming session pins itself to the least-loaded one, acquire_replica: the load
         # accounting that spreads sessions over GPUs); it only has to live on the features' device
         r = replica if replica is not None else self.replica_on(device)
@@ -1095,7 +1183,7 @@ class Whisper:
                                        max_initial_timestamp_index=max_initial_timestamp_index, suppress_blank=suppress_blank, suppress_default=True,
                                        sampling_topk=sampling_topk, sampling_temperature=sampling_temperature, fixed_new_tokens=fixed_new_tokens,
                                        draft_tokens=draft_tokens, draft_trajectory=draft_trajectory, return_trajectory=return_trajectory, phrases=phrases,
-                                       return_phrase_mass=return_phrase_mass)
+                                       return_phrase_mass=return_phrase_mass, hotwords=hotwords, hotword_boost=hotword_boost)
         row = (int(mel_device_ptr), [int(t) for t in prompt], _seeds(opts, sampling_seed, 1)[0])
         return self._batcher.submit(opts, [row], affinity=("device", device))[0]
 

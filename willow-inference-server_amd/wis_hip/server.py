@@ -126,6 +126,15 @@ def create_app(models=None, settings=None, max_workers=None, sv=None):
         from .whisper import load_phrases_file
         if not load_phrases_file(s.phrases_file):
             raise ValueError(f"setting phrases_file {s.phrases_file!r}: the file holds no phrase")
+    if getattr(s, "hotwords_file", ""):      # (and an unreadable or empty hotword list; a boost of 0 beside it is "off", anything else must be a boost)
+        from .whisper import load_hotwords_file
+        if not load_hotwords_file(s.hotwords_file):
+            raise ValueError(f"setting hotwords_file {s.hotwords_file!r}: the file holds no entry")
+    hb = getattr(s, "hotword_boost", 0.0)
+    if not (isinstance(hb, (int, float)) and math.isfinite(hb) and hb >= 0):
+        raise ValueError(f"setting hotword_boost {hb!r}: a finite number > 0, or 0 for off")
+    if getattr(s, "phrases_file", "") and getattr(s, "hotwords_file", "") and hb > 0:      # (every request would be constrained: the hotword list could never apply)
+        raise ValueError("settings phrases_file and hotwords_file / hotword_boost: a constrained search has nothing left to bias - set one of them")
     state = {"models": models, "sv": sv}
     sv_lock = __import__("threading").Lock()
     # enough threads that a full device batch per GPU replica can be waiting in the micro-batcher at once
@@ -208,25 +217,35 @@ def create_app(models=None, settings=None, max_workers=None, sv=None):
                 prompts[name] = v
         # phrase-constrained decoding: phrases=a|b|c (text; an entry "ids:1,2,3" is token ids) and phrase_nbest=n; absent or empty = the setting's list
         # (phrases_file) and 1; unparsable = 400
-        phrases, nbest = q.get("phrases"), q.get("phrase_nbest")
-        if phrases in (None, ""):
-            phrases = None
-        elif len(phrases) > 65536:
-            raise BadRequest(f"phrases: {len(phrases)} characters (at most 65536)")
-        else:
+        def entry_list(name):
+            raw = q.get(name)
+            if raw in (None, ""):
+                return None
+            if len(raw) > 65536:
+                raise BadRequest(f"{name}: {len(raw)} characters (at most 65536)")
             entries = []
-            for v in phrases.split("|"):
+            for v in raw.split("|"):
                 if v.strip() == "":
-                    raise BadRequest(f"Invalid phrases {phrases!r}: an empty entry")
+                    raise BadRequest(f"Invalid {name} {raw!r}: an empty entry")
                 if v.startswith("ids:"):
                     try:
                         v = [int(t) for t in v[4:].split(",") if t.strip() != ""]
                     except ValueError:
-                        raise BadRequest(f"Invalid phrases entry {v!r}: ids:<comma-separated token ids>")
+                        raise BadRequest(f"Invalid {name} entry {v!r}: ids:<comma-separated token ids>")
                     if not v or any(t < 0 for t in v):
-                        raise BadRequest("Invalid phrases: an ids: entry holds token ids >= 0, at least one")
+                        raise BadRequest(f"Invalid {name}: an ids: entry holds token ids >= 0, at least one")
                 entries.append(v)
-            phrases = entries
+            return entries
+        phrases, nbest = entry_list("phrases"), q.get("phrase_nbest")
+        # hotword boosting: hotwords=a|b|ids:400,401 (entries as in phrases=) and hotword_boost=2.5 (finite, > 0); absent or empty = the settings'
+        # list (hotwords_file) and boost (hotword_boost, 0 = off); a list without any boost, or together with phrases, = 400 (do_whisper's ValueError)
+        hotwords, hboost = entry_list("hotwords"), q.get("hotword_boost")
+        try:
+            hboost = float(hboost) if hboost not in (None, "") else None
+        except ValueError:
+            raise BadRequest(f"Invalid hotword_boost {hboost!r}")
+        if hboost is not None and not (0 < hboost < float("inf")):      # (a NaN fails both comparisons)
+            raise BadRequest(f"hotword_boost {hboost!r} must be a finite number > 0")
         try:
             nbest = int(nbest) if nbest not in (None, "") else None
         except ValueError:
@@ -274,6 +293,7 @@ def create_app(models=None, settings=None, max_workers=None, sv=None):
             raise BadRequest("Invalid no_speech_threshold: not a number")
         return dict(model=model, beam_size=beam, repetition_penalty=rp, **prompts, no_repeat_ngram_size=ng, temperatures=temps, best_of=best_of,
                     long_form=lf, condition_on_previous_text=cond, no_speech_threshold=nst, phrases=phrases, phrase_nbest=nbest, **pm,
+                    hotwords=hotwords, hotword_boost=hboost,
                     detect_language=_as_bool(q.get("detect_language"), s.detect_language), force_language=q.get("force_language") or None,
                     translate=_as_bool(q.get("translate"), False), timestamps=_as_bool(q.get("timestamps"), False),
                     word_timestamps=_as_bool(q.get("word_timestamps"), False))
@@ -285,7 +305,7 @@ def create_app(models=None, settings=None, max_workers=None, sv=None):
             kw = {"word_timestamps": True}
         kw.update({k: p[k] for k in ("repetition_penalty", "no_repeat_ngram_size", "temperatures", "best_of", "initial_prompt", "prefix", "long_form",
                                          "condition_on_previous_text", "no_speech_threshold", "phrases", "phrase_nbest", "phrase_mass", "phrase_threshold",
-                                         "phrase_fallback") if p[k] is not None})      # (absent: do_whisper takes the settings' values)
+                                         "phrase_fallback", "hotwords", "hotword_boost") if p[k] is not None})      # (absent: do_whisper takes the settings' values)
         return await loop.run_in_executor(pool, lambda: do_whisper(audio_file, p["model"], p["beam_size"], "transcribe", p["detect_language"],
                                                                    p["force_language"], p["translate"], models=get_models(), **kw))
 

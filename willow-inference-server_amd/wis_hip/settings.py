@@ -103,6 +103,12 @@ class APISettings:
     phrase_mass: bool = False
     phrase_threshold: float = 0.0
     phrase_fallback: bool = False
+    # hotword boosting (contextual biasing): a file with one entry per line, by phrases_file's rules, and the bonus added to the logit of every token
+    # that starts or continues an entry (do_whisper's hotwords / hotword_boost; a request's own list and boost replace these).  hotword_boost 0.0 = off,
+    # whatever the file holds; no default boost is shipped - a useful one is calibrated on the checkpoint in use.  An unreadable or empty file fails
+    # the server's start
+    hotwords_file: str = ""
+    hotword_boost: float = 0.0
     # prompted requests (more than 16 prompt tokens) share device batches whatever their prompt lengths: their micro-batcher key carries the pooled
     # prompt length -1 and the batch decodes through wis_generate_ragged, longest prompt first.  max_new_tokens stays in the key.  False: the key
     # carries the exact prompt length, as ever - two requests whose prompts differ by a token never meet in a device batch

@@ -663,3 +663,12 @@ def build_phrase_trie(phrases, *, eot=EOT, suppress_ids=SUPPRESS_IDS, suppress_b
         if len(recs) > PHRASE_MAX_RECORDS:
             raise ValueError(f"the phrase set needs more than {PHRASE_MAX_RECORDS} trie records")
     return np.ascontiguousarray(np.asarray(recs, np.int32).reshape(-1, 4))
+
+
+def build_hotword_trie(hotwords, **kw):
+    """A hotword list ([[token ids], ...]) -> the flat trie wis_model_set_hotwords takes: `build_phrase_trie`'s table under its rules and limits
+    (the "ends an entry" flags are filled in and play no part in the boost); its messages speak of hotwords."""
+    try:
+        return build_phrase_trie(hotwords, **kw)
+    except ValueError as e:
+        raise ValueError(str(e).replace("phrase list", "hotword list").replace("phrase set", "hotword set").replace("phrase ", "hotword ")) from None

@@ -437,6 +437,64 @@ def phrase_ids(phrases, tokenizer, special):
     return out, names
 
 
+def load_hotwords_file(path):
+    """The setting `hotwords_file`: one entry per line, by `phrases_file`'s rules (blank lines and # lines skipped; empty path: no list; an
+    unreadable file raises: the server's start fails, not every request)."""
+    if not path:
+        return []
+    key = (path, os.stat(path).st_mtime_ns)
+    if _hotwords_file_cache.get("key") != key:
+        with open(path, "r", encoding="utf-8") as f:
+            _hotwords_file_cache.update(key=key, hotwords=[ln.strip() for ln in f if ln.strip() and not ln.lstrip().startswith("#")])
+    return list(_hotwords_file_cache["hotwords"])
+
+
+_hotwords_file_cache = {}
+
+
+def hotword_ids(hotwords, tokenizer, special):
+    """do_whisper's `hotwords` -> [token ids per entry]: strings are encoded as `phrase_ids` encodes them (" " + text.strip() with the checkpoint's
+    tokenizer; no vocabulary: ValueError), lists of text token ids pass as they are."""
+    if isinstance(hotwords, (str, bytes)) or not hasattr(hotwords, "__iter__"):
+        raise ValueError("hotwords: a list of strings or token id lists")
+    hotwords = list(hotwords)
+    if not 1 <= len(hotwords) <= MAX_PHRASES:
+        raise ValueError(f"hotwords: {len(hotwords)} entries (1..{MAX_PHRASES})")
+    out = []
+    for i, hw in enumerate(hotwords):
+        ids = prompt_ids(hw, tokenizer, special, f"hotwords[{i}]")
+        if not ids:
+            raise ValueError(f"hotwords[{i}]: an empty entry")
+        out.append(ids)
+    return out
+
+
+def _hotword_opts(settings, hotwords, hotword_boost):
+    """do_whisper's hotwords / hotword_boost, resolved against the settings -> (the list, the boost) or (None, 0.0) when the option is off.
+    hotwords None: the setting's list (`hotwords_file`); empty: off.  hotword_boost None: the setting (`hotword_boost`, default 0.0 = off).
+    The settings' list with a boost of 0 is off; a list the REQUEST names needs a boost from somewhere (ValueError); a boost is finite and > 0."""
+    explicit = hotwords is not None
+    if explicit and (isinstance(hotwords, (str, bytes)) or not hasattr(hotwords, "__iter__")):
+        raise ValueError("hotwords: a list of strings or token id lists")
+    lst = list(hotwords) if explicit else load_hotwords_file(getattr(settings, "hotwords_file", ""))
+    boost = getattr(settings, "hotword_boost", 0.0) if hotword_boost is None else hotword_boost
+    try:
+        boost = float(0.0 if boost is None else boost)
+    except (TypeError, ValueError):
+        raise ValueError(f"hotword_boost {hotword_boost!r}: a finite number > 0") from None
+    if hotword_boost is not None and not (math.isfinite(boost) and boost > 0):
+        raise ValueError(f"hotword_boost {hotword_boost!r}: a finite number > 0")
+    if not lst:
+        return None, 0.0
+    if boost == 0.0:
+        if explicit:
+            raise ValueError("hotwords need a hotword_boost (the request's, or the setting): there is no default boost")
+        return None, 0.0
+    if not (math.isfinite(boost) and boost > 0):
+        raise ValueError(f"hotword_boost {boost!r}: a finite number > 0")
+    return lst, boost
+
+
 def in_grammar(logmass, n_tokens):
     """exp(logmass / (n_tokens + 1)): the geometric mean, per step, of the share of the model's probability a phrase list allowed along a phrase of
     n_tokens tokens and its <|endoftext|>; in [0, 1] (-inf -> 0; NaN stays NaN)."""
@@ -498,6 +556,13 @@ def _request_prompt_ids(q, tokenizer, special, seek=False):
     return ip_ids, px_ids
 
 
+def _request_hotwords(q, tokenizer, special):
+    """generate's hotword arguments of a request ({}: the option is off) - handed to every decode of the request"""
+    if q.hotwords is None:
+        return {}
+    return dict(hotwords=hotword_ids(q.hotwords, tokenizer, special), hotword_boost=q.hotword_boost)
+
+
 def _request_language(q, settings, special, detect):
     """The request's language: detected (detect() -> detect_language's result for the first window), forced, or the setting; one of the model's."""
     language = settings.language
@@ -528,8 +593,16 @@ def do_whisper(audio_file, model, beam_size=None, task="transcribe", detect_lang
                models=None, fixed_new_tokens=None, timestamps=False, word_timestamps=False, repetition_penalty=None, no_repeat_ngram_size=None,
                temperatures=None, best_of=None, compression_ratio_threshold=None, logprob_threshold=None, initial_prompt=None, prefix=None,
                long_form=None, condition_on_previous_text=None, no_speech_threshold=None, phrases=None, phrase_nbest=1,
-               phrase_mass=None, phrase_threshold=None, phrase_fallback=None):
-    """phrases (None: the setting's list, `phrases_file`; empty: off): the transcript is restricted to a phrase list - strings (tokenised as
+               phrase_mass=None, phrase_threshold=None, phrase_fallback=None, hotwords=None, hotword_boost=None):
+    """hotwords / hotword_boost (None: the settings' list, `hotwords_file`, and `hotword_boost`, 0.0 = off; an empty list: off): contextual biasing
+    toward a list of entries - strings (tokenised as " " + text.strip() with the checkpoint's tokenizer; no vocabulary: ValueError) or lists of
+    text token ids.  Free-form decoding goes on; every token that starts an entry, or continues one the hypothesis has begun, gets the boost added
+    to its logit (include/wis_hip.h, THE HOTWORD RULE; no back-off; scores are those of the boosted rows).  The option reaches every decode of the
+    request - the translation pass, every temperature of the fallback, every window of long_form=seek and of the chunked form - but not language
+    detection or the word alignment.  There is no default boost: calibrate it on the checkpoint in use; a list named by the request without any
+    boost, a boost that is not finite and > 0, and a request that names hotwords together with phrases are a ValueError; the settings' list
+    does not apply to a constrained request.
+    phrases (None: the setting's list, `phrases_file`; empty: off): the transcript is restricted to a phrase list - strings (tokenised as
     " " + text.strip() with the checkpoint's tokenizer; no vocabulary: ValueError) or lists of text token ids.  The search can only produce
     one of the phrases (include/wis_hip.h states the rule); `text` is the best one, and the result gains
     `matches = [{"text", "score"}]`, best first: the `phrase_nbest` best phrases of the beam search (at most beam_size; fewer when the search
@@ -588,6 +661,11 @@ def do_whisper(audio_file, model, beam_size=None, task="transcribe", detect_lang
         phrases=load_phrases_file(getattr(s, "phrases_file", "")) if phrases is None else phrases, phrase_nbest=phrase_nbest)
     constrained = not (q.phrases is None or (hasattr(q.phrases, "__len__") and len(q.phrases) == 0))
     q.phrase_mass, q.phrase_threshold, q.phrase_fallback = _phrase_mass_opts(opt, constrained, phrase_mass, phrase_threshold, phrase_fallback)
+    q.hotwords, q.hotword_boost = _hotword_opts(s, hotwords, hotword_boost)
+    if constrained and q.hotwords is not None:
+        if hotwords is not None:      # (the request itself names both)
+            raise ValueError("hotwords cannot be combined with phrases (a constrained search has nothing left to bias)")
+        q.hotwords, q.hotword_boost = None, 0.0      # the SETTINGS' hotword list does not apply to a constrained request
     if constrained:
         try:
             q.phrase_nbest = int(phrase_nbest)
@@ -651,6 +729,7 @@ def do_whisper(audio_file, model, beam_size=None, task="transcribe", detect_lang
     total_chunk_count = features.shape[0]
     tokenizer = models.tokenizer_for(model)
     ip_ids, px_ids = _request_prompt_ids(q, tokenizer, special)
+    hot = _request_hotwords(q, tokenizer, special)
     phr = {}
     if constrained:
         if q.phrase_nbest > q.beam_size:
@@ -691,7 +770,7 @@ def do_whisper(audio_file, model, beam_size=None, task="transcribe", detect_lang
         feats, fkind = windows_of(0, 1)
 
         def decode(t, n):
-            r = whisper_model.generate(feats, [prompt], return_scores=True, fixed_new_tokens=fixed_new_tokens, **fkind, **_search(q, t, n), **rep)[0]
+            r = whisper_model.generate(feats, [prompt], return_scores=True, fixed_new_tokens=fixed_new_tokens, **fkind, **_search(q, t, n), **rep, **hot)[0]
             return list(zip(r.sequences_ids, r.scores))
         fb = decode_with_fallback(decode, temps, best_of, q.compression_ratio_threshold, q.logprob_threshold, _text_of(tokenizer, special.timestamp_begin))
         results.append(ctranslate2.WhisperGenerationResult([fb["tokens"]], [fb["score"]]))
@@ -700,7 +779,7 @@ def do_whisper(audio_file, model, beam_size=None, task="transcribe", detect_lang
         hi = min(lo + ccg, total_chunk_count)
         feats, fkind = windows_of(lo, hi)
         results.extend(whisper_model.generate(feats, [prompt] * (hi - lo), beam_size=q.beam_size, return_scores=False,
-                                              fixed_new_tokens=fixed_new_tokens, **fkind, **rep, **phr))
+                                              fixed_new_tokens=fixed_new_tokens, **fkind, **rep, **phr, **hot))
     assert len(results) == total_chunk_count, "Result length doesn't match expected total_chunk_count"
     if use_chunking:
         tokens = audio.find_longest_common_sequence([(results[i].sequences_ids[0], strides[i]) for i in range(total_chunk_count)],
@@ -741,7 +820,7 @@ def do_whisper(audio_file, model, beam_size=None, task="transcribe", detect_lang
     if translating:       # main.py:729-748 (its `len(int)` bug aside: short audio only)
         tprompt = [special.sot, special.language_token_id(language), special.translate, special.notimestamps]
         feats, fkind = windows_of(0, total_chunk_count)
-        tres = whisper_model.generate(feats, [tprompt] * total_chunk_count, beam_size=q.beam_size, fixed_new_tokens=fixed_new_tokens, **fkind, **rep)
+        tres = whisper_model.generate(feats, [tprompt] * total_chunk_count, beam_size=q.beam_size, fixed_new_tokens=fixed_new_tokens, **fkind, **rep, **hot)
         translation = tokenizer.decode(tres[0].sequences_ids[0]).strip()
         out_translation_tokens = tres[0].sequences_ids[0]
     else:
@@ -766,6 +845,7 @@ def _do_whisper_seek(q, models, model, whisper_model, pcm, audio_duration, first
     special = model_special_tokens(whisper_model)
     tokenizer = models.tokenizer_for(model)
     ip_ids, _ = _request_prompt_ids(q, tokenizer, special, seek=True)
+    hot = _request_hotwords(q, tokenizer, special)
     n_text_ctx = _n_text_ctx(whisper_model)
     replica = whisper_model.acquire_replica()
     long_mel = None
@@ -798,10 +878,10 @@ def _do_whisper_seek(q, models, model, whisper_model, pcm, audio_duration, first
         def decode(window, prompt, t, n):
             if isinstance(window, ctranslate2.StorageView):
                 r = whisper_model.generate(window, [prompt], fixed_new_tokens=q.fixed_new_tokens, return_scores=True, return_no_speech_prob=True,
-                                           **_search(q, t, n), **q.rep)[0]
+                                           **_search(q, t, n), **q.rep, **hot)[0]
             else:
                 r = whisper_model.generate_from_device(replica.device, window, prompt, replica=replica, fixed_new_tokens=q.fixed_new_tokens, return_scores=True,
-                                                       return_no_speech_prob=True, **_search(q, t, n), **q.rep)
+                                                       return_no_speech_prob=True, **_search(q, t, n), **q.rep, **hot)
             return list(zip(r.sequences_ids, r.scores)), r.no_speech_prob
 
         def on_window(window, seek, segment_size, segs):
