@@ -690,6 +690,21 @@ int wis_op_gemv_qkv(int device, const float* x, const float* gamma, const float*
 int wis_op_gemv_out_cq(int device, const void* a_f16, const float* x0, const void* Wo_f16, const float* bo, const void* Wq_f16, const float* bq,
                        const float* gamma, const float* beta, float* x1, float* stat, float* q, float* q2, float* qcs, float* qb,
                        int M, int d, int force_frag);
+/* ---- the load-time weight preparation by itself (tests/test_gpu_prep_ops.py; the numpy specification is tests/prep_ref.py): the loader's own
+ * prep_projection on a private copy of W f16 [N][K].  gamma / beta f32 [K] (both or neither): the LayerNorm fold - W' = f16(W * gamma), bias_inout f32 [N]
+ * += W . beta, csum_out = the column sums of what the MFMA will see; rows < n_scale carry qscale (in the f16 image's values, in the 8-bit scales, in both
+ * vectors).  w8 = 0: image_out = Npad K f16 in fragment order [Npad/rows][K/32][4][rows][8], scale_out NULL; w8 = 1 (rows = 16): image_out = Npad K bytes
+ * (q + 128), scale_out f32 [Npad].  W_out_f16 [N][K]: the staging as the fold left it.  csum_out f32 [Npad] (optional without gamma) is set to
+ * WIS_PREP_CSUM_SENTINEL words first where the loader zeroes: the entries nothing wrote still hold it.  What launch_pack_gemv / launch_pack_gemv8 /
+ * prep_projection refuse (K % 32, Npad % rows, Npad < N, rows not 4 / 8 / 16, gamma without bias or csum) is WIS_E_ARG, and nothing is written. */
+#define WIS_PREP_CSUM_SENTINEL 0x7fc5a5a5u
+int wis_op_prep_projection(int device, const void* W_f16, int N, int Npad, int K, int n_scale, float qscale, const float* gamma, const float* beta,
+                           float* bias_inout, int w8, int rows, void* W_out_f16, void* image_out, float* scale_out, float* csum_out);
+/* the cross-Q fold as wis_op_gemv_out_cq and the loader build it: Wq f16 [d][d] folded with gamma / beta and the query scaling 1/8 (no image), then
+ * build_cq_fold with Wo [d][d] (f16 or f32) and bo f32 [d] -> fcat_out f16 [d][2d] = [W'q | f16(W'q Wo)], image_out f16 [d][2d] its sixteen-column fragment
+ * image, b_cqo_out = W'q bo, qb_out = (bq + Wq . beta) / 8, qcs_out = the column sums of f16(Wq * gamma), / 8 (all f32 [d]).  d a multiple of 128. */
+int wis_op_cq_fold(int device, const void* Wq_f16, const float* gamma, const float* beta, const float* bq, const void* Wo, int wo_is_f16, const float* bo, int d,
+                   void* fcat_out_f16, void* image_out_f16, float* b_cqo_out, float* qb_out, float* qcs_out);
 /* the wave reductions of the LayerNorm-folded projections' tail, side by side: ONE wave takes x f32 [N][64] (value i of lane l at x[i][l]) and runs
  * wave_sum on each of the N values and then wave_sums<N> on the same registers, in one launch -> out_old / out_new f32 [N][64], every lane's result of
  * either (all 64 words of a value are equal, and out_new equals out_old bit for bit: the tree is the contract).  N = 6, 10 or 16: the 2 RM sums of

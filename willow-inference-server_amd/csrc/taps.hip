@@ -589,6 +589,47 @@ int wis_op_gemv_out_cq(int device, const void* a, const float* x0, const void* W
   return t.finish(launch_gemv_frag3(st, g3, 3));
 }
 
+// ---- the load-time weight preparation by itself (tests/test_gpu_prep_ops.py): what prep_projection / build_cq_fold hand the step kernels.
+// Everything runs on private memory and reaches the caller's buffers only when the product's own code accepted the shape, so a refused call writes nothing.
+// The private bias / column-sum vectors hold max(N, Npad) entries: fold_ln_kernel writes N of them before the packer has judged Npad.
+int wis_op_prep_projection(int device, const void* W_f16, int N, int Npad, int K, int n_scale, float qscale, const float* gamma, const float* beta, float* bias_inout,
+                           int w8, int rows, void* W_out_f16, void* image_out, float* scale_out, float* csum_out) {
+  Tap t(device, "wis_op_prep_projection"); WIS_RET(t.rc);
+  if (!W_f16 || !W_out_f16 || !image_out || N < 1 || Npad < 1 || K < 1 || n_scale < 0 || n_scale > N || (gamma && !beta) || (w8 ? (!scale_out || rows != 16) : scale_out != nullptr)) {
+    set_error("wis_op_prep_projection: bad argument"); return WIS_E_ARG; }
+  hipStream_t st = t.st;
+  const size_t nv = (size_t)std::max(N, Npad), img_bytes = (size_t)Npad * K * (w8 ? 1 : 2);
+  f16* wtmp = nullptr; unsigned char* img = nullptr; float *wsc = nullptr, *b2 = nullptr, *cs = nullptr;
+  WIS_RET(t.get(&wtmp, (size_t)N * K)); WIS_RET(t.get(&img, img_bytes));
+  if (w8) WIS_RET(t.get(&wsc, (size_t)Npad));
+  if (bias_inout) { WIS_RET(t.get(&b2, nv)); hipMemcpyAsync(b2, bias_inout, (size_t)N * 4, hipMemcpyDeviceToDevice, st); }
+  if (csum_out) { WIS_RET(t.get(&cs, nv)); WIS_HIP_CHECK(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(cs), (int)WIS_PREP_CSUM_SENTINEL, nv, st)); }      // (the loader zeroes these Npad entries)
+  hipMemcpyAsync(wtmp, W_f16, (size_t)N * K * 2, hipMemcpyDeviceToDevice, st);
+  WIS_RET(prep_projection(st, wtmp, N, Npad, K, n_scale, qscale, gamma, beta, b2, cs, img, wsc, rows));
+  hipMemcpyAsync(W_out_f16, wtmp, (size_t)N * K * 2, hipMemcpyDeviceToDevice, st);
+  hipMemcpyAsync(image_out, img, img_bytes, hipMemcpyDeviceToDevice, st);
+  if (w8) hipMemcpyAsync(scale_out, wsc, (size_t)Npad * 4, hipMemcpyDeviceToDevice, st);
+  if (b2) hipMemcpyAsync(bias_inout, b2, (size_t)N * 4, hipMemcpyDeviceToDevice, st);
+  if (cs) hipMemcpyAsync(csum_out, cs, (size_t)Npad * 4, hipMemcpyDeviceToDevice, st);
+  return t.finish(WIS_OK);
+}
+// the cross-Q fold as wis_op_gemv_out_cq (and load_weights) builds it: the cross-Q bias scaled, the LayerNorm folded into Wq without an image, then build_cq_fold
+int wis_op_cq_fold(int device, const void* Wq_f16, const float* gamma, const float* beta, const float* bq, const void* Wo, int wo_is_f16, const float* bo, int d,
+                   void* fcat_out_f16, void* image_out_f16, float* b_cqo_out, float* qb_out, float* qcs_out) {
+  Tap t(device, "wis_op_cq_fold"); WIS_RET(t.rc);
+  if (!Wq_f16 || !gamma || !beta || !bq || !Wo || !bo || !fcat_out_f16 || !image_out_f16 || !b_cqo_out || !qb_out || !qcs_out || d < 128 || d % 128) {
+    set_error("wis_op_cq_fold: bad argument"); return WIS_E_ARG; }
+  hipStream_t st = t.st;
+  const float qs = 0.125f;
+  f16 *wtmp = nullptr, *fwot = nullptr, *fwqo = nullptr;
+  WIS_RET(t.get(&wtmp, (size_t)d * d)); WIS_RET(t.get(&fwot, (size_t)d * d)); WIS_RET(t.get(&fwqo, (size_t)d * d));
+  hipMemcpyAsync(wtmp, Wq_f16, (size_t)d * d * 2, hipMemcpyDeviceToDevice, st);
+  launch_convert(st, bq, 0, qb_out, 0, d, 1, 1, d, qs);
+  hipMemsetAsync(qcs_out, 0, (size_t)d * 4, st);
+  WIS_RET(prep_projection(st, wtmp, d, d, d, d, qs, gamma, beta, qb_out, qcs_out, nullptr, nullptr, 16));
+  return t.finish(build_cq_fold(st, wtmp, Wo, wo_is_f16, bo, d, qs, reinterpret_cast<f16*>(fcat_out_f16), fwot, fwqo, reinterpret_cast<f16*>(image_out_f16), b_cqo_out));
+}
+
 // ---- taps of what run_encoder / run_cross_kv launch (tests/test_gpu_enc_ops.py): the product's launch_* functions on the product's GemmP helpers
 // (conv1_gemm, conv2_gemm, gemm_plain) and weight packers, with free B and T; the tile and kernel form are gemm_pick_tile's / launch_gemm_t's choice
 int wis_op_mel_to_image(int device, const float* mel, void* img_f16, int B, int n_mels) {
