@@ -166,8 +166,23 @@ typedef struct {
   const int32_t* lang_ids;           int32_t n_lang;            /* 50259..50357 */
   int32_t decoder_weight_bits;  /* 0 / 16: f16 decoder weights (compute type "float16"); 8: per-row int8 weights with f16
                                  * activations ("int8_float16", the reference's GPU default main.py:242) - halves the decode
-                                 * weight stream; encoder, embedding lookup and the cross K/V projection stay f16 */
+                                 * weight stream; the embedding lookup stays f16, and so do the encoder and the cross K/V
+                                 * projection unless wis_model_create_ex asks for the int8 encoder (wis_model_ext_t below) */
 } wis_config_t;
+/* Options of wis_model_create_ex that wis_config_t (frozen) has no field for.  size = sizeof(wis_model_ext_t).
+ * encoder_weight_bits: 0 / 16 = the f16 encoder; 8 = the INT8 ENCODER: the four linears of every encoder layer (QKV, attention output, FFN1, FFN2)
+ * and the all-layers cross K/V projection run as int8 x int8 -> int32 GEMMs on the i8 matrix instruction; convolutions, positions, attention, the f32
+ * residual stream, the f16 encoder output and the whole decoder are unchanged.  Independent of decoder_weight_bits.  THE RULE, for weights and
+ * activations alike: a row r of f16 values becomes int8 values and one f32 scale, in f32 arithmetic -
+ *   scale = absmax(r) / 127 (1 for an all-zero row), inv = 1 / scale, q = clip(rint(r * inv), -127, 127), round half to even
+ * (wis_hip.weights.quantize_rows).  Weight rows are quantised at load from the f16 matrix the f16 encoder would multiply by (the query scale folded
+ * into the Q rows first) and that f16 matrix is not kept; activation rows are quantised from the f16-rounded values the f16 encoder would read
+ * (LayerNorm output, attention output, FFN hidden, encoder memory).  A product is (float)(sum_k qa qw) * (scale_a[m] * scale_w[n]), the sum exact in
+ * int32, then the f16 path's epilogue in f32.  Anything else than 0 / 8 / 16, or a size below the struct's: WIS_E_ARG. */
+typedef struct {
+  int32_t size;
+  int32_t encoder_weight_bits;
+} wis_model_ext_t;
 
 #define WIS_DT_F32 0
 #define WIS_DT_F16 1
@@ -187,6 +202,10 @@ typedef struct {
 int  wis_model_create(const wis_config_t* cfg, const void* arena, size_t arena_bytes,
                       int arena_on_device, const wis_tensor_t* tensors, int n_tensors,
                       int device, wis_model_t** out);
+/* wis_model_create with options (ext = NULL: exactly wis_model_create).  Clones share the quantised weights as they share the others. */
+int  wis_model_create_ex(const wis_config_t* cfg, const void* arena, size_t arena_bytes,
+                         int arena_on_device, const wis_tensor_t* tensors, int n_tensors,
+                         int device, wis_model_t** out, const wis_model_ext_t* ext);
 void wis_model_destroy(wis_model_t* m);
 size_t wis_model_device_bytes(const wis_model_t* m);
 /* Another replica on the SAME GPU that shares `parent`'s converted weights (read-only device memory, reference-counted: either
@@ -757,6 +776,24 @@ int wis_op_enc_crosskv(int device, const void* mem_f16, const void* W_f16, const
  * exists for 2 and 4 splits and N <= 2048, K % (64 splits) == 0 (otherwise the launch function's error code). */
 int wis_op_gemm_splitk_ln(int device, const void* A_f16, const void* W_f16, const float* bias, float* X, const float* gamma, const float* beta,
                           void* Y_f16, int M, int N, int K, int splits);
+
+/* ---- the int8 encoder's kernels (wis_model_ext_t has the rule; tests/test_gpu_enc_i8.py), device pointers.
+ * wis_op_quant_rows: x f16 [M][K] -> q i8 [M][K], scale f32 [M] (K % 8 == 0, K <= 5120).
+ * wis_op_layernorm_quant: wis_op_layernorm's rows quantised - q i8 [M][d], scale f32 [M], and y f16 [M][d] (may be null): the bits wis_op_layernorm writes.
+ * wis_op_gemm_i8: C = epi((float)(A . W^T) * (sa[m] * sw[n])), A i8 [M][K], W i8 [N][K], N % 128 == 0, K % 128 == 0.  epi:
+ *   0 generic: + bias (may be null), flags as wis_op_gemm (1 GELU, 2 + residual f32 [M][N], 4 fp32 output), out = C [M][N]
+ *   1 GELU: gelu(. + bias) -> C f16 [M][N]                  2 residual: . + bias + residual -> C f32 [M][N] (residual may be C)
+ *   3 QKV (N = 3 * 64 H, M = B T, T % 4 == 0): [Q | K] rows -> C f16 [M][2d], V^T image -> out2 f16 [B][H][64][Tpad] as wis_op_enc_qkv
+ *   4 cross K/V (N = L * 2 * 64 H): K images -> C, V^T images -> out2, layer strides kx_lstride / vt_lstride as wis_op_enc_crosskv
+ * form: 0 = the tile form the encoder picks at this shape, 1 = 128 x 128, 2 = 64 x 128, 3 = 256 x 256 (N % 256 == 0). */
+int wis_op_quant_rows(int device, const void* x_f16, void* q_i8, float* scale, int M, int K);
+int wis_op_layernorm_quant(int device, const float* x, const float* gamma, const float* beta, void* q_i8, float* scale, void* y_f16, int M, int d);
+int wis_op_gemm_i8(int device, const void* A_i8, const float* sa, const void* W_i8, const float* sw, const float* bias, const float* residual, void* C, void* out2,
+                   int M, int N, int K, int epi, int flags, int form, int B, int T, int H, int L, int64_t kx_lstride, int64_t vt_lstride);
+/* tuning tap (tools/enc_int8_bench.py; no product path calls it): us per launch of one encoder GEMM with the generic f16-output epilogue, `reps` launches between two events after one warm-up: bits 16 = the f16 GEMM
+ * as the encoder picks its tile, bits 8 = the int8 GEMM in `form`; bits 1 = the row quantiser on f16 [M][K], bits 2 = LayerNorm + quantise on f32 [M][K]
+ * (N = K).  Operands are the tap's own (the weight matrix, or the quantisers' input, rotated through ~640 MB so that it streams from HBM). */
+int wis_bench_enc_gemm(int device, int bits, int M, int N, int K, int form, int reps, float* us_out);
 
 /* ---- the resampler's kernel alone (tests/test_gpu_resample_ops.py): outputs m0 .. m0 + count - 1 (out f32 [count]) of a signal of
  * n_in_total samples at the reduced ratio up / down to 16 kHz, from the slice x_slice f32 [n_slice] = samples k_base .. k_base +

@@ -1311,6 +1311,315 @@ int launch_gemm_crosskv(hipStream_t st, const GemmP& p, const float* bias, f16* 
 }
 
 // =======================================================================================
+// The int8 encoder (encoder_weight_bits = 8): W8A8 GEMMs on gfx950's i8 matrix instruction, and the two kernels that make their A operand.
+//
+// THE RULE (include/wis_hip.h states it for callers; wis_hip.weights.quantize_rows is its numpy form).  A row r of f16 values - a weight row at load, an
+// activation row at run time - becomes int8 values and one f32 scale, all arithmetic in f32:
+//   scale = absmax(r) / 127  (1 for an all-zero row),   inv = 1 / scale,   q = clip(rint(r * inv), -127, 127)  (round half to even).
+// Activations are quantised from the f16-ROUNDED values the f16 encoder would have multiplied by, so LayerNorm + quantise in one kernel and LayerNorm
+// followed by the stand-alone quantiser leave the same bytes and the same scales.  A GEMM is then
+//   C[m][n] = epi( (float)(sum_k Aq[m][k] Wq[n][k]) * (sa[m] * sw[n]) + bias[n] ... ),
+// the sum exact in int32 (127 * 127 * 5120 < 2^27), the conversion, the scaling and the epilogue in f32.
+//
+// MI355X mapping:
+//  * v_mfma_i32_32x32x32_i8: 32 k per issue and 16 operand bytes per lane - the f16 form the encoder uses (32x32x16) takes the same 16 bytes for half
+//    the k depth.  The f16 GEMMs are bound by operand staging (the table above: 16-20 bytes per cycle and CU whatever the tile), so a staged byte that
+//    carries twice the multiply-adds is the lever; the matrix pipe's own rate doubles as well.
+//  * the k-tile is 128 deep: a 128-BYTE row of eight 16-byte chunks, the very LDS image of the f16 loader (144-byte pitch, conflict-free
+//    ds_read_b128), so per k-tile a workgroup stages what the f16 kernel stages and issues the same 4 fragment reads per operand row block - for
+//    twice the k.  Register staging, two LDS buffers, one barrier per k-tile; K % 128 == 0 holds for every model width (384 .. 1280, and 4 d).
+//  * the weight tile is the MFMA A operand and the activation tile the B operand, so the 32 x 32 int32 accumulator has the lane layout of the f32 one
+//    (lane: row m = l31, features (r & 3) + 8 (r >> 2) + 4 hi): it is converted and scaled in place - sa[m] once per row block, the sw quad of each
+//    feature quad - and handed to epilogue_32 with the f16 path's functors above, unchanged.
+//  * tile forms (gemm_i8_pick): 256 x 256 on 8 waves from 150 tiles on (the batched encoder: 128 multiply-adds per staged byte), 64 x 128 on 4 waves
+//    while 128 x 128 tiles would number under 200 (one utterance, N = d: out-projection and FFN2 give 240 workgroups), else 128 x 128 on 4 waves (two
+//    workgroups per CU covering each other's waits).  These are the f16 picker's thresholds (gemm_pick_tile): its reasons are tile
+//    counts against 256 CUs and co-residency, which the operand width does not change.  FFN2 of one utterance runs UNSPLIT on the 64 x 128 form with the residual
+//    epilogue: a k-tile is twice as deep, so K = 4 d is the f16 kernel's 2 d in k-tiles, and the fp32 partial tiles and their reduce launch fall away.
+//    Measured (profiles/enc_int8_ab.md; us per launch, d = 1280, f16 as the encoder picks | int8 128x128 | 64x128 | 256x256):
+//      M = 1500    QKV 24.4 | 18.1 | 21.7 | 27.7    out 16.2 | 13.1 | 10.2 | 26.5    FFN1 25.0 | 18.8 | 24.5 | 28.0    FFN2 (unsplit) 52.3 | 38.3 | 28.6 | 68.6
+//      M = 12000   QKV 127 | 100 | 118 | 84.8       out 44.1 | 36.2 | 43.1 | 30.1    FFN1 165 | 130 | 154 | 111        FFN2 129 | 101 | 123 | 72.6
+//    The picked form is the fastest at all eight points.
+typedef int i32x4 __attribute__((ext_vector_type(4)));
+typedef int i32x16 __attribute__((ext_vector_type(16)));
+
+// one value by the rule; inv = 1 / scale
+__device__ __forceinline__ int quant1(float v, float inv) { return (int)fminf(fmaxf(rintf(v * inv), -127.f), 127.f); }
+__device__ __forceinline__ unsigned pack4(int a, int b, int c, int d) { return (unsigned)(a & 255) | ((unsigned)(b & 255) << 8) | ((unsigned)(c & 255) << 16) | ((unsigned)d << 24); }
+
+// =======================================================================================
+// Row quantiser: f16 [M][K] -> i8 [M][K] + f32 scale [M].  One wave per row; the row is read once (16 bytes per lane and round) and stays in registers
+// between the absmax reduction and the write.  NCH rounds of 64 x 8 values: 4 (K <= 2048) or 10 (K <= 5120).
+template <int NCH>
+__global__ __launch_bounds__(256) void quant_rows_kernel(const f16* __restrict__ x, int8_t* __restrict__ q, float* __restrict__ scale, int M, int K) {
+  const int lane = threadIdx.x & 63, row = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (row >= M) return;
+  const int n8 = K >> 3;
+  const f16x8* x8 = reinterpret_cast<const f16x8*>(x + (size_t)row * K);
+  f16x8 v[NCH];
+  float mx = 0.f;
+#pragma unroll
+  for (int i = 0; i < NCH; ++i) {      // unconditional loads (clamped index, masked value): see layernorm_kernel
+    const int idx = lane + 64 * i, ic = idx < n8 ? idx : n8 - 1;
+    f16x8 a = x8[ic];
+    if (idx >= n8) a = f16x8{0, 0, 0, 0, 0, 0, 0, 0};
+    v[i] = a;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) mx = fmaxf(mx, fabsf((float)a[j]));
+  }
+  mx = wave_max(mx);
+  const float sc = mx > 0.f ? mx / 127.0f : 1.0f, inv = 1.0f / sc;
+  if (lane == 0) scale[row] = sc;
+  uint2* q8 = reinterpret_cast<uint2*>(q + (size_t)row * K);
+#pragma unroll
+  for (int i = 0; i < NCH; ++i) {
+    const int idx = lane + 64 * i;
+    uint2 o;
+    o.x = pack4(quant1((float)v[i][0], inv), quant1((float)v[i][1], inv), quant1((float)v[i][2], inv), quant1((float)v[i][3], inv));
+    o.y = pack4(quant1((float)v[i][4], inv), quant1((float)v[i][5], inv), quant1((float)v[i][6], inv), quant1((float)v[i][7], inv));
+    if (idx < n8) q8[idx] = o;
+  }
+}
+int launch_quant_rows(hipStream_t st, const f16* x, int8_t* q, float* scale, int M, int K) {
+  if (M < 1 || K < 8 || K % 8 || K > 5120) { set_error("quant_rows: M=%d K=%d unsupported (K %% 8, K <= 5120)", M, K); return WIS_E_UNSUPPORTED; }
+  if (K <= 2048) hipLaunchKernelGGL((quant_rows_kernel<4>), dim3(cdiv(M, 4)), dim3(256), 0, st, x, q, scale, M, K);
+  else hipLaunchKernelGGL((quant_rows_kernel<10>), dim3(cdiv(M, 4)), dim3(256), 0, st, x, q, scale, M, K);
+  return WIS_OK;
+}
+
+// =======================================================================================
+// LayerNorm + quantise: fp32 [M][d] -> i8 [M][d] + scale [M] (+ the f16 row, where y is given).  layernorm_kernel's arithmetic statement for statement
+// (one wave per row, the mean in two steps, the same expression for every output), so the f16 values quantised here are the bits
+// launch_layernorm writes; the absmax is taken on those f16 values.
+__global__ __launch_bounds__(256) void layernorm_quant_kernel(const float* __restrict__ x, const float* __restrict__ gamma, const float* __restrict__ beta,
+                                                              int8_t* __restrict__ q, float* __restrict__ scale, f16* __restrict__ y, int M, int d) {
+  const int lane = threadIdx.x & 63, row = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (row >= M) return;
+  const int n4 = d >> 2;
+  const float4* x4 = reinterpret_cast<const float4*>(x + (size_t)row * d);
+  float4 v[8], g[8], be[8];
+  const float4* g4 = reinterpret_cast<const float4*>(gamma);
+  const float4* b4 = reinterpret_cast<const float4*>(beta);
+  float s = 0.f;
+#pragma unroll
+  for (int i = 0; i < 8; ++i) {
+    const int idx = lane + 64 * i, ic = idx < n4 ? idx : n4 - 1;
+    float4 a = x4[ic];
+    g[i] = g4[ic]; be[i] = b4[ic];
+    if (idx >= n4) a = make_float4(0.f, 0.f, 0.f, 0.f);
+    v[i] = a;
+    s += (a.x + a.y) + (a.z + a.w);
+  }
+#pragma unroll
+  for (int i = 0; i < 8; ++i) { WIS_PIN4(g[i]); WIS_PIN4(be[i]); }
+  const float mean0 = wave_sum(s) / (float)d;
+  float s1 = 0.f;
+#pragma unroll
+  for (int i = 0; i < 8; ++i) {
+    const int idx = lane + 64 * i;
+    v[i].x -= mean0; v[i].y -= mean0; v[i].z -= mean0; v[i].w -= mean0;
+    const float t = (v[i].x + v[i].y) + (v[i].z + v[i].w);
+    s1 += idx < n4 ? t : 0.f;
+  }
+  const float mean = wave_sum(s1) / (float)d;
+  float qs = 0.f;
+#pragma unroll
+  for (int i = 0; i < 8; ++i) {
+    const int idx = lane + 64 * i;
+    const float a = v[i].x - mean, b = v[i].y - mean, c = v[i].z - mean, e = v[i].w - mean;
+    const float t = (a * a + b * b) + (c * c + e * e);
+    qs += idx < n4 ? t : 0.f;
+  }
+  const float rstd = 1.0f / sqrtf(wave_sum(qs) / (float)d + 1e-5f);
+  f16x4 o[8];
+  float mx = 0.f;
+#pragma unroll
+  for (int i = 0; i < 8; ++i) {
+    const int idx = lane + 64 * i;
+    o[i][0] = (f16)((v[i].x - mean) * rstd * g[i].x + be[i].x);
+    o[i][1] = (f16)((v[i].y - mean) * rstd * g[i].y + be[i].y);
+    o[i][2] = (f16)((v[i].z - mean) * rstd * g[i].z + be[i].z);
+    o[i][3] = (f16)((v[i].w - mean) * rstd * g[i].w + be[i].w);
+    const float t = fmaxf(fmaxf(fabsf((float)o[i][0]), fabsf((float)o[i][1])), fmaxf(fabsf((float)o[i][2]), fabsf((float)o[i][3])));
+    mx = fmaxf(mx, idx < n4 ? t : 0.f);
+  }
+  mx = wave_max(mx);
+  const float sc = mx > 0.f ? mx / 127.0f : 1.0f, inv = 1.0f / sc;
+  if (lane == 0) scale[row] = sc;
+  unsigned* q4 = reinterpret_cast<unsigned*>(q + (size_t)row * d);
+  f16x4* y4 = reinterpret_cast<f16x4*>(y + (size_t)row * d);
+#pragma unroll
+  for (int i = 0; i < 8; ++i) {
+    const int idx = lane + 64 * i;
+    const unsigned w = pack4(quant1((float)o[i][0], inv), quant1((float)o[i][1], inv), quant1((float)o[i][2], inv), quant1((float)o[i][3], inv));
+    if (idx < n4) { q4[idx] = w; if (y) y4[idx] = o[i]; }
+  }
+}
+int launch_layernorm_quant(hipStream_t st, const float* x, const float* gamma, const float* beta, int8_t* q, float* scale, f16* y, int M, int d) {
+  if (M < 1 || d % 4 || d > 2048 || !gamma || !beta) { set_error("layernorm_quant: d=%d unsupported (d %% 4, d <= 2048, gamma and beta given)", d); return WIS_E_UNSUPPORTED; }
+  hipLaunchKernelGGL(layernorm_quant_kernel, dim3(cdiv(M, 4)), dim3(256), 0, st, x, gamma, beta, q, scale, y, M, d);
+  return WIS_OK;
+}
+
+// =======================================================================================
+// GEMM.  Leading scalar arguments (kernarg preload, as the f16 GEMMs take theirs): what the first loads need.
+constexpr int BK8 = 128, LSTR8 = 144;      // 128-deep k-tiles = 128-byte rows; LDS row pitch 144 B
+template <class Epi, int BM_, int BN_, int WM_, int WN_>
+__global__ __launch_bounds__(64 * WM_ * WN_) void gemm_i8_kernel(const int8_t* __restrict__ A, const int8_t* __restrict__ W, int M, int N, int K,
+                                                                   const float* __restrict__ sa, const float* __restrict__ sw, Epi epi) {
+  constexpr int T = 64 * WM_ * WN_;
+  constexpr int TM = BM_ / WM_, TN = BN_ / WN_;
+  constexpr int MI = TM / 32, NI = TN / 32;
+  constexpr int RP = T / 8;                    // tile rows covered by one 16-byte-per-thread pass
+  constexpr int NA = BM_ / RP, NW = BN_ / RP;
+  static_assert((NA == 2 || NA == 4) && (NW == 2 || NW == 4), "loader passes");
+  __shared__ __attribute__((aligned(16))) int8_t sA[2][BM_ * LSTR8];
+  __shared__ __attribute__((aligned(16))) int8_t sW[2][BN_ * LSTR8];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int wm = wave / WN_, wn = wave % WN_, l31 = lane & 31, hi = lane >> 5;
+  // XCD-aware regrouping of the workgroup id, then m-fastest tile coordinates (gemm_f16_kernel)
+  const int nmt = (M + BM_ - 1) / BM_, nwg = nmt * (N / BN_);
+  int wg;
+  {
+    const int orig = blockIdx.x, xcd = orig & 7, q = nwg >> 3, r = nwg & 7;
+    wg = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (orig >> 3);
+  }
+  const int m0 = (wg % nmt) * BM_, n0 = (wg / nmt) * BN_;
+  // loader: 16-byte chunk c -> row c >> 3, byte offset (c & 7) * 16; rows lrow + RP i.  Rows past M read row M - 1 (their results are never stored);
+  // weight rows n0 + .. < N always (N % BN_ == 0).  Named registers, not arrays (the compiler demotes arrays here)
+  const int lrow = tid >> 3, lkc = (tid & 7) * 16;
+  auto arow = [&](int i) -> const int8_t* {
+    int lm = m0 + lrow + RP * i; if (lm > M - 1) lm = M - 1;
+    return A + (int64_t)lm * K + lkc;
+  };
+  const int8_t* ga0 = arow(0); const int8_t* ga1 = arow(1);
+  const int8_t* ga2 = arow(NA > 2 ? 2 : 0); const int8_t* ga3 = arow(NA > 2 ? 3 : 0);
+  const int8_t* gw0 = W + (int64_t)(n0 + lrow) * K + lkc;
+  const int64_t wrp = (int64_t)RP * K;
+  const int soff = lrow * LSTR8 + lkc;
+  uint4 ra0, ra1, ra2, ra3, rw0, rw1, rw2, rw3;
+#define WIS_GLOAD8(kt)                                                                        \
+  ra0 = *reinterpret_cast<const uint4*>(ga0 + (kt) * BK8); ra1 = *reinterpret_cast<const uint4*>(ga1 + (kt) * BK8);   \
+  if (NA > 2) { ra2 = *reinterpret_cast<const uint4*>(ga2 + (kt) * BK8); ra3 = *reinterpret_cast<const uint4*>(ga3 + (kt) * BK8); } \
+  rw0 = *reinterpret_cast<const uint4*>(gw0 + (kt) * BK8); rw1 = *reinterpret_cast<const uint4*>(gw0 + wrp + (kt) * BK8);   \
+  if (NW > 2) { rw2 = *reinterpret_cast<const uint4*>(gw0 + 2 * wrp + (kt) * BK8); rw3 = *reinterpret_cast<const uint4*>(gw0 + 3 * wrp + (kt) * BK8); }
+#define WIS_SSTORE8(buf)                                                                      \
+  *reinterpret_cast<uint4*>(&sA[buf][soff]) = ra0; *reinterpret_cast<uint4*>(&sA[buf][soff + RP * LSTR8]) = ra1;     \
+  if (NA > 2) { *reinterpret_cast<uint4*>(&sA[buf][soff + 2 * RP * LSTR8]) = ra2; *reinterpret_cast<uint4*>(&sA[buf][soff + 3 * RP * LSTR8]) = ra3; } \
+  *reinterpret_cast<uint4*>(&sW[buf][soff]) = rw0; *reinterpret_cast<uint4*>(&sW[buf][soff + RP * LSTR8]) = rw1;     \
+  if (NW > 2) { *reinterpret_cast<uint4*>(&sW[buf][soff + 2 * RP * LSTR8]) = rw2; *reinterpret_cast<uint4*>(&sW[buf][soff + 3 * RP * LSTR8]) = rw3; }
+
+  i32x16 acc[NI][MI];
+#pragma unroll
+  for (int a = 0; a < NI; ++a)
+#pragma unroll
+    for (int b = 0; b < MI; ++b)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) acc[a][b][r] = 0;
+
+  const int nk = K / BK8;
+  // staging order as in gemm_f16_kernel: the 128 x 128 tile (two workgroups per CU) requests at the top and stores at the bottom of an iteration;
+  // the other forms store k-tile k + 1 at the top of iteration k and request k + 2 right behind
+  constexpr bool EARLY = BM_ != 128;
+  WIS_GLOAD8(0) WIS_SSTORE8(0)
+  if (EARLY && nk > 1) { WIS_GLOAD8(1) }
+  __syncthreads();
+  for (int kt = 0; kt < nk; ++kt) {
+    const int cur = kt & 1;
+    if (EARLY) {
+      if (kt + 1 < nk) { WIS_SSTORE8(cur ^ 1) }
+      if (kt + 2 < nk) { WIS_GLOAD8(kt + 2) }
+    } else if (kt + 1 < nk) { WIS_GLOAD8(kt + 1) }
+#pragma unroll
+    for (int kk = 0; kk < BK8 / 32; ++kk) {      // lane (l31, hi) feeds bytes 32 kk + 16 hi .. + 15 of its row to both operands: the same k on both sides
+      i32x4 wf[NI], af[MI];
+#pragma unroll
+      for (int i = 0; i < NI; ++i)
+        wf[i] = *reinterpret_cast<const i32x4*>(&sW[cur][(wn * TN + i * 32 + l31) * LSTR8 + kk * 32 + hi * 16]);
+#pragma unroll
+      for (int i = 0; i < MI; ++i)
+        af[i] = *reinterpret_cast<const i32x4*>(&sA[cur][(wm * TM + i * 32 + l31) * LSTR8 + kk * 32 + hi * 16]);
+#pragma unroll
+      for (int ni = 0; ni < NI; ++ni)
+#pragma unroll
+        for (int mi = 0; mi < MI; ++mi)
+          acc[ni][mi] = __builtin_amdgcn_mfma_i32_32x32x32_i8(wf[ni], af[mi], acc[ni][mi], 0, 0, 0);
+    }
+    if (!EARLY && kt + 1 < nk) { WIS_SSTORE8(cur ^ 1) }
+    __syncthreads();
+  }
+#undef WIS_GLOAD8
+#undef WIS_SSTORE8
+  // D[i = n][j = m]: lane holds m = l31, n = (r & 3) + 8 (r >> 2) + 4 hi.  int32 -> f32 (one rounding from 2^24 on), times sa[m] sw[n] (the product
+  // of the scales first: one rounding; then one for the multiplication), component by component
+  const int mrow = m0 + wm * TM + l31, ncol = n0 + wn * TN + 4 * hi;
+  float sam[MI];
+#pragma unroll
+  for (int mi = 0; mi < MI; ++mi) { int m = mrow + mi * 32; if (m > M - 1) m = M - 1; sam[mi] = sa[m]; }
+  f32x4 s4[NI][4];
+#pragma unroll
+  for (int ni = 0; ni < NI; ++ni)
+#pragma unroll
+    for (int r4 = 0; r4 < 4; ++r4) s4[ni][r4] = ld4(sw + ncol + ni * 32 + 8 * r4);
+  if constexpr (NI * MI > 4) {
+    // the 8-wave tile (128 accumulators per lane): one 32-column x 64-row block at a time, so that a block's residual quads (32 registers) and its
+    // converted values fit beside the accumulators still waiting (no scratch: tools/isa_lint.py)
+#pragma unroll
+    for (int ni = 0; ni < NI; ++ni)
+#pragma unroll
+      for (int mh = 0; mh < MI; mh += 2) {
+        f32x16 fs[1][2];
+#pragma unroll
+        for (int mi = 0; mi < 2; ++mi)
+#pragma unroll
+          for (int r = 0; r < 16; ++r) fs[0][mi][r] = (float)acc[ni][mh + mi][r] * (sam[mh + mi] * s4[ni][r >> 2][r & 3]);
+        epilogue_32<Epi, 1, 2>(epi, fs, mrow + mh * 32, ncol + ni * 32, M);
+      }
+  } else {
+    f32x16 facc[NI][MI];
+#pragma unroll
+    for (int ni = 0; ni < NI; ++ni)
+#pragma unroll
+      for (int mi = 0; mi < MI; ++mi)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) facc[ni][mi][r] = (float)acc[ni][mi][r] * (sam[mi] * s4[ni][r >> 2][r & 3]);
+    epilogue_32<Epi, NI, MI>(epi, facc, mrow, ncol, M);
+  }
+}
+
+// Tile form by shape (the header comment has the reasons)
+int gemm_i8_pick(int M, int N) {
+  if (N % 256 == 0 && (N / 256) * cdiv(M, 256) >= 150) return I8_FORM_256;
+  return ((N / 128) * cdiv(M, 128) < 200 && M > 64) ? I8_FORM_64 : I8_FORM_128;
+}
+template <class Epi>
+static int launch_gemm_i8_t(hipStream_t st, const GemmI8P& p, const Epi& epi, int form) {
+  if (p.M < 1 || p.N < 128 || p.N % 128 || p.K < BK8 || p.K % BK8 || !p.A || !p.W || !p.sa || !p.sw) {
+    set_error("gemm_i8: M=%d N=%d K=%d unsupported (N %% 128, K %% 128)", p.M, p.N, p.K); return WIS_E_UNSUPPORTED; }
+  if (form == I8_FORM_AUTO) form = gemm_i8_pick(p.M, p.N);
+  if (form == I8_FORM_256 && p.N % 256) { set_error("gemm_i8: the 256 x 256 form needs N %% 256 == 0 (N=%d)", p.N); return WIS_E_ARG; }
+  if (form == I8_FORM_256) hipLaunchKernelGGL((gemm_i8_kernel<Epi, 256, 256, 2, 4>), dim3((p.N / 256) * cdiv(p.M, 256)), dim3(512), 0, st, p.A, p.W, p.M, p.N, p.K, p.sa, p.sw, epi);
+  else if (form == I8_FORM_64) hipLaunchKernelGGL((gemm_i8_kernel<Epi, 64, 128, 2, 2>), dim3((p.N / 128) * cdiv(p.M, 64)), dim3(256), 0, st, p.A, p.W, p.M, p.N, p.K, p.sa, p.sw, epi);
+  else if (form == I8_FORM_128) hipLaunchKernelGGL((gemm_i8_kernel<Epi, 128, 128, 2, 2>), dim3((p.N / 128) * cdiv(p.M, 128)), dim3(256), 0, st, p.A, p.W, p.M, p.N, p.K, p.sa, p.sw, epi);
+  else { set_error("gemm_i8: form=%d (0 as the encoder picks, 1 128x128, 2 64x128, 3 256x256)", form); return WIS_E_ARG; }
+  return WIS_OK;
+}
+// flags as launch_gemm_generic takes them (1 GELU, 2 residual, 4 fp32 output); FFN1 and the residual projections get the functors without run-time flags
+int launch_gemm_i8_generic(hipStream_t st, const GemmI8P& p, const float* bias, const float* resid, void* C, int flags, int form) {
+  if (flags == 1 && bias) return launch_gemm_i8_t(st, p, EpiGelu{bias, reinterpret_cast<f16*>(C), p.N}, form);
+  if (flags == (2 | 4) && bias && resid) return launch_gemm_i8_t(st, p, EpiResid{bias, resid, reinterpret_cast<float*>(C), p.N}, form);
+  if ((flags & 2) && !resid) { set_error("gemm_i8: flag 2 without a residual"); return WIS_E_ARG; }
+  return launch_gemm_i8_t(st, p, EpiGeneric{bias, resid, C, p.N, flags}, form);
+}
+int launch_gemm_i8_qkv(hipStream_t st, const GemmI8P& p, const float* bias, f16* qk, f16* vt, int d, int T, int Tpad, int H, int form) {
+  return launch_gemm_i8_t(st, p, EpiQKV{bias, qk, vt, d, T, Tpad, H}, form);
+}
+int launch_gemm_i8_crosskv(hipStream_t st, const GemmI8P& p, const float* bias, f16* kx, f16* vt, int d, int T, int Tpad, int H, int64_t kx_lstride, int64_t vt_lstride, int form) {
+  if (p.N % (2 * d)) { set_error("crosskv: N=%d is not a whole number of layers", p.N); return WIS_E_ARG; }
+  return launch_gemm_i8_t(st, p, EpiCrossKV{bias, kx, vt, d, T, Tpad, H, kx_lstride, vt_lstride}, form);
+}
+
+// =======================================================================================
 // Encoder self-attention (non-causal, dh = 64).  grid (ceil(T/128), H, B), block 256.
 // The loop is bound by the softmax arithmetic, not by the matrix pipe: per 64-key tile a wave issues 16 MFMAs (512 cycles) and, on
 // the vector ALU, 32 maxima, 32 fma + v_exp_f32 (a quarter-rate instruction: 16 cycles per wave) and 32 sums and conversions -

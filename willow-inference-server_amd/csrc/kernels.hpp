@@ -41,6 +41,20 @@ size_t enc_attention_part_floats(int B, int T, int H);
 bool enc_attn_lazy();
 void launch_scale_q_log2e(hipStream_t st, f16* qk, int64_t rows, int d);      // (op-level entry: Q half of a [rows][2d] image times log2(e))
 
+// ---- int8 encoder (enc_kernels.hip states the rule) -----------------------------------------
+// C[m][n] = epi((float)(sum_k A[m][k] W[n][k]) * (sa[m] * sw[n]) ...): A i8 [M][K] with its row scales, W i8 [N][K] with its; N % 128 == 0, K % 128 == 0
+struct GemmI8P { const int8_t* A; const float* sa; const int8_t* W; const float* sw; int M, N, K; };
+enum { I8_FORM_AUTO = 0, I8_FORM_128 = 1, I8_FORM_64 = 2, I8_FORM_256 = 3 };      // tile form: as gemm_i8_pick chooses, 128 x 128, 64 x 128, 256 x 256 (N % 256 == 0)
+int gemm_i8_pick(int M, int N);
+// f16 [M][K] -> i8 [M][K] + f32 scale [M] (K % 8 == 0, K <= 5120)
+int launch_quant_rows(hipStream_t st, const f16* x, int8_t* q, float* scale, int M, int K);
+// launch_layernorm's rows, quantised: i8 [M][d] + scale [M]; y (optional): the f16 rows themselves, the bits launch_layernorm writes
+int launch_layernorm_quant(hipStream_t st, const float* x, const float* gamma, const float* beta, int8_t* q, float* scale, f16* y, int M, int d);
+int launch_gemm_i8_generic(hipStream_t st, const GemmI8P& p, const float* bias, const float* resid, void* C, int flags, int form = I8_FORM_AUTO);
+int launch_gemm_i8_qkv(hipStream_t st, const GemmI8P& p, const float* bias, f16* qk, f16* vt, int d, int T, int Tpad, int H, int form = I8_FORM_AUTO);
+int launch_gemm_i8_crosskv(hipStream_t st, const GemmI8P& p, const float* bias, f16* kx, f16* vt, int d, int T, int Tpad, int H, int64_t kx_lstride, int64_t vt_lstride,
+                           int form = I8_FORM_AUTO);
+
 // ---- decoder ---------------------------------------------------------------------------
 constexpr int MAX_ROWS = 96;      // decoder rows per pass: B*beam (decode) or B*P (merged prefill + first step): 16 utterances x beam 5 + slack; wis_hip/ctranslate2.py MAX_DECODER_ROWS
 constexpr int MAX_R = 8;          // rows per utterance (beam or prompt prefix length)

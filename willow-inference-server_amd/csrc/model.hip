@@ -208,6 +208,15 @@ static int to_f16_mat(wis_model* m, const Loader& L, const std::string& name, in
   hipLaunchKernelGGL(convert_kernel, dim3(blocks_for(rows * cols)), dim3(256), 0, m->st, s.p, s.f16, *out, 1, rows, cols, cols, n_scale, scale);
   return WIS_OK;
 }
+// encoder_weight_bits = 8: checkpoint matrix -> the f16 image the f16 path would keep (staging `tmp`; rows [0, n_scale) times `scale`: the folded query
+// scale) -> int8 rows + one f32 scale per row, by the rule of the int8 encoder (enc_kernels.hip).  *q / *sc preset: views into a block the caller allocated
+static int to_i8_mat(wis_model* m, const Loader& L, const std::string& name, int64_t rows, int64_t cols, f16* tmp, int8_t** q, float** sc, int64_t n_scale = 0, float scale = 1.f) {
+  TensorSrc s; WIS_RET(L.get(name, rows, cols, &s));
+  if (!*q) WIS_RET(dalloc(m, q, (size_t)rows * cols));
+  if (!*sc) WIS_RET(dalloc(m, sc, (size_t)rows));
+  hipLaunchKernelGGL(convert_kernel, dim3(blocks_for(rows * cols)), dim3(256), 0, m->st, s.p, s.f16, tmp, 1, rows, cols, cols, n_scale, scale);
+  return launch_quant_rows(m->st, tmp, *q, *sc, (int)rows, (int)cols);
+}
 // W (f16 [N][K] row-major staging) -> what the skinny GEMMs stream, on the caller's buffers (loader and op taps).  gamma given: fold that LayerNorm
 // (fold_ln_kernel rewrites W; `bias`, loaded, receives W . beta; `csum`, zeroed, the column sums).  out: the f16 fragment image - or, with scale_out, the
 // 8-bit image + row scales, the column sums retaken from what the MFMA will see; null: fold only.  Rows [0, n_scale) (the query part) are scaled by `scale`.
@@ -343,6 +352,20 @@ static int load_weights(wis_model* m, const Loader& L) {
       if ((rc = to_f32(m, L, p + "self_attention/layer_norm/beta", d, &w.ln1_b))) break;
       // (the lazy-reference attention loop takes exp2 of the MFMA result directly: log2(e) rides on the query projection too)
       const float qs_enc = enc_attn_lazy() ? qs * 1.4426950408889634f : qs;
+      if (m->enc_i8) {      // the four linears as int8 rows (biases and LayerNorm vectors as ever); w_* stay null
+        w.w_qkv = w.w_out = w.w_f1 = w.w_f2 = nullptr;
+        if ((rc = to_f32(m, L, p + "self_attention/linear_0/bias", 3 * d, &w.b_qkv, d, qs_enc))) break;
+        if ((rc = to_f32(m, L, p + "self_attention/linear_1/bias", d, &w.b_out))) break;
+        if ((rc = to_f32(m, L, p + "ffn/layer_norm/gamma", d, &w.ln2_g))) break;
+        if ((rc = to_f32(m, L, p + "ffn/layer_norm/beta", d, &w.ln2_b))) break;
+        if ((rc = to_f32(m, L, p + "ffn/linear_0/bias", 4 * d, &w.b_f1))) break;
+        if ((rc = to_f32(m, L, p + "ffn/linear_1/bias", d, &w.b_f2))) break;
+        if ((rc = to_i8_mat(m, L, p + "self_attention/linear_0/weight", 3 * d, d, tmp, &w.q_qkv, &w.s_qkv, d, qs_enc))) break;
+        if ((rc = to_i8_mat(m, L, p + "self_attention/linear_1/weight", d, d, tmp, &w.q_out, &w.s_out))) break;
+        if ((rc = to_i8_mat(m, L, p + "ffn/linear_0/weight", 4 * d, d, tmp, &w.q_f1, &w.s_f1))) break;
+        if ((rc = to_i8_mat(m, L, p + "ffn/linear_1/weight", d, 4 * d, tmp, &w.q_f2, &w.s_f2))) break;
+        continue;
+      }
       if ((rc = to_f16_mat(m, L, p + "self_attention/linear_0/weight", 3 * d, d, &w.w_qkv, d, qs_enc))) break;
       if ((rc = to_f32(m, L, p + "self_attention/linear_0/bias", 3 * d, &w.b_qkv, d, qs_enc))) break;
       if ((rc = to_f16_mat(m, L, p + "self_attention/linear_1/weight", d, d, &w.w_out))) break;
@@ -368,6 +391,10 @@ static int load_weights(wis_model* m, const Loader& L) {
     if ((rc = to_packed(m, L, "decoder/embeddings/weight", V, d, tmp, 0, 1.f, m->dec_ln_g, m->dec_ln_b, b_proj, &m->proj, &m->n_vocab_pad))) break;
     m->proj.N = m->n_vocab_pad;      // launched over the padded vocabulary
     m->dec.resize(c.n_dec_layers);
+    if (m->enc_i8) {      // the same [L * 2d][d] matrix as int8 rows + row scales
+      if ((rc = dalloc(m, &m->q_ckv_all, (size_t)c.n_dec_layers * 2 * d * d))) break;
+      if ((rc = dalloc(m, &m->s_ckv_all, (size_t)c.n_dec_layers * 2 * d))) break;
+    } else
     if ((rc = dalloc(m, &m->w_ckv_all, (size_t)c.n_dec_layers * 2 * d * d))) break;      // one [L * 2d][d] matrix: a single GEMM projects every layer
     if ((rc = dalloc(m, &m->b_ckv_all, (size_t)c.n_dec_layers * 2 * d))) break;
     for (int l = 0; l < c.n_dec_layers && !rc; ++l) {
@@ -401,7 +428,11 @@ static int load_weights(wis_model* m, const Loader& L) {
           w.cqo.Wp8 = p8;
         }
       }
-      w.w_ckv = m->w_ckv_all + (size_t)l * 2 * d * d; w.b_ckv = m->b_ckv_all + (size_t)l * 2 * d;
+      w.w_ckv = m->enc_i8 ? nullptr : m->w_ckv_all + (size_t)l * 2 * d * d; w.b_ckv = m->b_ckv_all + (size_t)l * 2 * d;
+      if (m->enc_i8) {
+        int8_t* q = m->q_ckv_all + (size_t)l * 2 * d * d; float* sc = m->s_ckv_all + (size_t)l * 2 * d;
+        if ((rc = to_i8_mat(m, L, p + "attention/linear_1/weight", 2 * d, d, tmp, &q, &sc))) break;
+      } else
       if ((rc = to_f16_mat(m, L, p + "attention/linear_1/weight", 2 * d, d, &w.w_ckv))) break;
       if ((rc = to_f32(m, L, p + "attention/linear_1/bias", 2 * d, &w.b_ckv))) break;
       if ((rc = load_proj(m, L, p + "attention/linear_2", d, d, tmp, 0, 1.f, nullptr, nullptr, &w.cout))) break;
@@ -552,6 +583,10 @@ static int alloc_buffers(wis_model* m) {
   WIS_RET(dalloc(m, &m->d_hot, (size_t)PHRASE_MAX_RECORDS + 1));      // (the last buffer carved, for the same reason; its last record holds the kernel's two control words)
   m->d_hot_ctl = reinterpret_cast<int*>(m->d_hot + PHRASE_MAX_RECORDS);
   WIS_HIP_CHECK(hipMemsetAsync(m->d_hot_ctl, 0, 16, m->st));
+  if (m->enc_i8) {      // (carved behind everything else: with the option off every buffer lies where it lay)
+    WIS_RET(dalloc(m, &m->aq, (size_t)Bm * T * 4 * d)); WIS_RET(dalloc(m, &m->asc, (size_t)Bm * T));
+    WIS_RET(dalloc(m, &m->memq, (size_t)Bm * T * d)); WIS_RET(dalloc(m, &m->memsc, (size_t)Bm * T));
+  }
   WIS_HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&m->h_pin), sizeof(PinnedScratch), hipHostMallocDefault));
   // fine-grained (coherent) host memory mapped into the device: beam_step_kernel's system-scope stores land here while the
   // stream is still running
@@ -592,6 +627,27 @@ int stage_input(wis_model* m, const float* input, int kind, int B, hipStream_t o
 }
 
 // ---- encoder + cross K/V ---------------------------------------------------------------
+// The layers and ln_post of the int8 encoder (encoder_weight_bits = 8; enc_kernels.hip has the rule): every linear reads the quantised image of the f16
+// activation the f16 path reads - xn behind ln1 / ln2 (LayerNorm and quantiser in one launch), ao behind the attention, hbuf behind FFN1's GELU (the
+// stand-alone quantiser) - from the one buffer aq / asc.  FFN2 runs unsplit with the residual epilogue at every row count.  Attention, the f32
+// residual stream and the f16 memory are the f16 path's.
+static int run_encoder_layers_i8(wis_model* m, int B, hipStream_t st) {
+  const wis_config_t& c = m->cfg;
+  const int d = c.d_model, H = c.n_heads, T = c.n_audio_ctx, M = B * T;
+  for (int l = 0; l < c.n_enc_layers; ++l) {
+    const EncLayerW& w = m->enc[l];
+    WIS_RET(launch_layernorm_quant(st, m->x, w.ln1_g, w.ln1_b, m->aq, m->asc, nullptr, M, d));
+    WIS_RET(launch_gemm_i8_qkv(st, GemmI8P{m->aq, m->asc, w.q_qkv, w.s_qkv, M, 3 * d, d}, w.b_qkv, m->qk, m->vt, d, T, m->Tpad, H));
+    WIS_RET(launch_enc_attention(st, m->qk, m->vt, m->ao, B, T, m->Tpad, H, m->enc_part, m->enc_cnt, m->enc_part_cap));
+    WIS_RET(launch_quant_rows(st, m->ao, m->aq, m->asc, M, d));
+    WIS_RET(launch_gemm_i8_generic(st, GemmI8P{m->aq, m->asc, w.q_out, w.s_out, M, d, d}, w.b_out, m->x, m->x, 2 | 4));
+    WIS_RET(launch_layernorm_quant(st, m->x, w.ln2_g, w.ln2_b, m->aq, m->asc, nullptr, M, d));
+    WIS_RET(launch_gemm_i8_generic(st, GemmI8P{m->aq, m->asc, w.q_f1, w.s_f1, M, 4 * d, d}, w.b_f1, nullptr, m->hbuf, 1));
+    WIS_RET(launch_quant_rows(st, m->hbuf, m->aq, m->asc, M, 4 * d));
+    WIS_RET(launch_gemm_i8_generic(st, GemmI8P{m->aq, m->asc, w.q_f2, w.s_f2, M, d, 4 * d}, w.b_f2, m->x, m->x, 2 | 4));
+  }
+  return launch_layernorm(st, m->x, m->enc_ln_g, m->enc_ln_b, m->mem, M, d);
+}
 int run_encoder(wis_model* m, int B, hipStream_t on) {
   const wis_config_t& c = m->cfg; hipStream_t st = on ? on : m->st;
   const int d = c.d_model, H = c.n_heads, T = c.n_audio_ctx, M = B * T;
@@ -606,6 +662,7 @@ int run_encoder(wis_model* m, int B, hipStream_t on) {
   // layer's ln1, or ln_post after the last layer.  Measured for large-v2 at M = 1500 with the weights streamed from HBM
   // (tools/gemm_lab.hip): 64x128 tiles over the whole K 52 us; 2 splits 42.6 + 6.0 (reduce) + 6.2 (LayerNorm) us; 4 splits + fused
   // reduce-LayerNorm: see profiles/.
+  if (m->enc_i8) return run_encoder_layers_i8(m, B, st);
   const int splits = enc_splitk(d, M);
   const bool split = splits > 0;
   bool xn_ready = false;
@@ -633,6 +690,11 @@ int run_encoder(wis_model* m, int B, hipStream_t on) {
 int run_cross_kv(wis_model* m, int B, const f16* mem) {
   const wis_config_t& c = m->cfg;
   const int d = c.d_model, T = c.n_audio_ctx;
+  if (m->enc_i8) {      // the quantised copy is made from the f16 block, the handle's own or the caller's (WIS_IN_ENC_*)
+    WIS_RET(launch_quant_rows(m->st, mem ? mem : m->mem, m->memq, m->memsc, B * T, d));
+    return launch_gemm_i8_crosskv(m->st, GemmI8P{m->memq, m->memsc, m->q_ckv_all, m->s_ckv_all, B * T, c.n_dec_layers * 2 * d, d}, m->b_ckv_all, m->kx_all, m->vx_all, d, T,
+                                  m->Tpad, c.n_heads, (int64_t)m->kx_lstride, (int64_t)m->vx_lstride);
+  }
   // every decoder layer's K/V projection of the encoder memory in one GEMM (weights, biases and outputs are single blocks)
   return launch_gemm_crosskv(m->st, gemm_plain(mem ? mem : m->mem, d, m->w_ckv_all, B * T, c.n_dec_layers * 2 * d, d), m->b_ckv_all, m->kx_all, m->vx_all, d, T, m->Tpad,
                              c.n_heads, (int64_t)m->kx_lstride, (int64_t)m->vx_lstride);
@@ -1104,7 +1166,15 @@ int wis_supported_compute_types(int device, char* out, size_t cap) {
 
 int wis_model_create(const wis_config_t* cfg, const void* arena, size_t arena_bytes, int arena_on_device,
                      const wis_tensor_t* tensors, int n_tensors, int device, wis_model_t** out) {
+  return wis_model_create_ex(cfg, arena, arena_bytes, arena_on_device, tensors, n_tensors, device, out, nullptr);
+}
+int wis_model_create_ex(const wis_config_t* cfg, const void* arena, size_t arena_bytes, int arena_on_device,
+                        const wis_tensor_t* tensors, int n_tensors, int device, wis_model_t** out, const wis_model_ext_t* ext) {
+  if (ext && (ext->size < (int32_t)sizeof(wis_model_ext_t) || (ext->encoder_weight_bits != 0 && ext->encoder_weight_bits != 8 && ext->encoder_weight_bits != 16))) {
+    set_error("wis_model_create_ex: ext->size %d, encoder_weight_bits %d (0 / 16: f16 encoder, 8: int8 encoder)", ext->size, ext->encoder_weight_bits); return WIS_E_ARG; }
   if (!cfg || !arena || !tensors || !out || n_tensors <= 0) { set_error("wis_model_create: bad argument"); return WIS_E_ARG; }
+  if (ext && ext->encoder_weight_bits == 8 && cfg->d_model > 1280) {      // (the row quantiser holds a row of 4 d <= 5120 values in registers)
+    set_error("wis_model_create_ex: encoder_weight_bits 8 with d_model %d (the int8 encoder serves d_model <= 1280)", cfg->d_model); return WIS_E_UNSUPPORTED; }
   if (cfg->d_model % 128 || cfg->d_model != cfg->n_heads * 64 || cfg->d_model > 2048 || !mel_bins_supported(cfg->n_mels) || cfg->n_enc_layers < 1 || cfg->n_dec_layers < 1 || cfg->n_audio_ctx != 1500 ||
       cfg->n_text_ctx > 512 || cfg->max_batch < 1 || cfg->max_beam < 1 || cfg->max_beam > MAX_R || cfg->n_vocab < 1024) {
     set_error("wis_model_create: unsupported config (d_model %% 128, head_dim 64, n_mels 80 or 128, n_audio_ctx 1500, max_beam <= %d)", MAX_R);
@@ -1114,6 +1184,7 @@ int wis_model_create(const wis_config_t* cfg, const void* arena, size_t arena_by
   wis_model* m = new wis_model();
   m->cfg = *cfg; m->device = device; m->ctx = ctx;
   m->w8 = cfg->decoder_weight_bits == 8;
+  m->enc_i8 = ext && ext->encoder_weight_bits == 8;
   m->cq_fold = !m->w8 && getenv("WIS_NO_CQFOLD") == nullptr;     // (8-bit weights keep the two-stage form: the fold would change what is quantised)
   m->use_graph = getenv("WIS_NO_GRAPH") == nullptr;
   memset(&m->timing, 0, sizeof(m->timing));
@@ -1189,6 +1260,7 @@ int wis_model_clone(wis_model_t* parent, wis_model_t** out) {
   m->emb = parent->emb; m->dec_pos = parent->dec_pos; m->proj = parent->proj; m->dec_ln_g = parent->dec_ln_g; m->dec_ln_b = parent->dec_ln_b;
   m->bias_all = parent->bias_all; m->bias_begin = parent->bias_begin; m->d_lang_ids = parent->d_lang_ids; m->n_vocab_pad = parent->n_vocab_pad;
   m->w_ckv_all = parent->w_ckv_all; m->b_ckv_all = parent->b_ckv_all;
+  m->enc_i8 = parent->enc_i8; m->q_ckv_all = parent->q_ckv_all; m->s_ckv_all = parent->s_ckv_all;
   m->w8 = parent->w8; m->cq_fold = parent->cq_fold;
   m->use_graph = parent->use_graph;
   m->al.heads = parent->al.heads;      // (the clone allocates its own align scratch on its first wis_align)

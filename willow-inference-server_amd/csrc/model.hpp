@@ -19,6 +19,9 @@ struct EncLayerW {
   float *ln1_g, *ln1_b, *ln2_g, *ln2_b;
   f16 *w_qkv, *w_out, *w_f1, *w_f2;
   float *b_qkv, *b_out, *b_f1, *b_f2;
+  // encoder_weight_bits = 8: the four matrices as int8 rows + one f32 scale per row (enc_kernels.hip has the rule); the f16 pointers above are null then
+  int8_t *q_qkv = nullptr, *q_out = nullptr, *q_f1 = nullptr, *q_f2 = nullptr;
+  float *s_qkv = nullptr, *s_out = nullptr, *s_f1 = nullptr, *s_f2 = nullptr;
 };
 // One decoder projection as the step streams it (load_weights: load_proj; the taps fill one from their own scratch)
 struct DecProj {
@@ -139,6 +142,10 @@ struct wis_model {
   wis::f16 *kc_all = nullptr, *vc_all = nullptr; size_t kv_layer_stride = 0;
   wis::f16 *kx_all = nullptr, *vx_all = nullptr, *w_ckv_all = nullptr; float* b_ckv_all = nullptr;   // cross K/V: one block each, all layers
   size_t kx_lstride = 0, vx_lstride = 0;
+  // int8 encoder (wis_model_create_ex, encoder_weight_bits = 8): the all-layers cross K/V matrix as int8 rows + row scales (w_ckv_all is null then); the
+  // quantised A operand of the layer GEMMs and its row scales (xn, ao and hbuf in turn: [max_batch T][4d]); the quantised encoder memory of run_cross_kv
+  bool enc_i8 = false;
+  int8_t *q_ckv_all = nullptr, *aq = nullptr, *memq = nullptr; float *s_ckv_all = nullptr, *asc = nullptr, *memsc = nullptr;
   // decode state
   float *dx, *dq, *logits, *part; wis::f16 *dao, *dh, *dln; unsigned* counters;
   float* dq2 = nullptr;         // batched fold: second half of the cross-attention q_raw (dec_forward_frag)

@@ -685,6 +685,74 @@ int wis_op_gemm_splitk_ln(int device, const void* A_f16, const void* W_f16, cons
                                            gamma, beta, reinterpret_cast<f16*>(Y_f16)));
 }
 
+// ---- the int8 encoder's three kernels (tests/test_gpu_enc_i8.py), through the launch functions run_encoder / run_cross_kv call
+int wis_op_quant_rows(int device, const void* x_f16, void* q_i8, float* scale, int M, int K) {
+  Tap t(device, "wis_op_quant_rows"); WIS_RET(t.rc);
+  if (!x_f16 || !q_i8 || !scale || M < 1) { set_error("wis_op_quant_rows: bad argument"); return WIS_E_ARG; }
+  return t.finish(launch_quant_rows(t.st, reinterpret_cast<const f16*>(x_f16), reinterpret_cast<int8_t*>(q_i8), scale, M, K));
+}
+int wis_op_layernorm_quant(int device, const float* x, const float* gamma, const float* beta, void* q_i8, float* scale, void* y_f16, int M, int d) {
+  Tap t(device, "wis_op_layernorm_quant"); WIS_RET(t.rc);
+  if (!x || !gamma || !beta || !q_i8 || !scale || M < 1) { set_error("wis_op_layernorm_quant: bad argument"); return WIS_E_ARG; }
+  return t.finish(launch_layernorm_quant(t.st, x, gamma, beta, reinterpret_cast<int8_t*>(q_i8), scale, reinterpret_cast<f16*>(y_f16), M, d));
+}
+int wis_op_gemm_i8(int device, const void* A_i8, const float* sa, const void* W_i8, const float* sw, const float* bias, const float* residual, void* C, void* out2,
+                   int M, int N, int K, int epi, int flags, int form, int B, int T, int H, int L, int64_t kx_lstride, int64_t vt_lstride) {
+  Tap t(device, "wis_op_gemm_i8"); WIS_RET(t.rc);
+  if (!A_i8 || !sa || !W_i8 || !sw || !C || M < 1 || N < 128 || K < 128 || form < 0 || form > 3 || epi < 0 || epi > 4 || (int64_t)M * N > 0x7fffffff) {
+    set_error("wis_op_gemm_i8: bad argument"); return WIS_E_ARG; }
+  const GemmI8P g{reinterpret_cast<const int8_t*>(A_i8), sa, reinterpret_cast<const int8_t*>(W_i8), sw, M, N, K};
+  if (epi == 0) return t.finish(launch_gemm_i8_generic(t.st, g, bias, residual, C, flags & 7, form));
+  if (!bias) { set_error("wis_op_gemm_i8: epilogue %d needs a bias", epi); return WIS_E_ARG; }
+  if (epi == 1) return t.finish(launch_gemm_i8_generic(t.st, g, bias, nullptr, C, 1, form));
+  if (epi == 2) {
+    if (!residual) { set_error("wis_op_gemm_i8: the residual epilogue needs a residual"); return WIS_E_ARG; }
+    return t.finish(launch_gemm_i8_generic(t.st, g, bias, residual, C, 2 | 4, form));
+  }
+  const int d = 64 * H, Tpad = cdiv(T, 64) * 64;
+  if (!out2 || B < 1 || T < 1 || T % 4 || H < 1 || K != d || M != B * T) { set_error("wis_op_gemm_i8: epilogue %d needs out2, M = B T, T %% 4 == 0, K = 64 H", epi); return WIS_E_ARG; }
+  if (epi == 3) {
+    if (N != 3 * d) { set_error("wis_op_gemm_i8: QKV has N = 3 d"); return WIS_E_ARG; }
+    return t.finish(launch_gemm_i8_qkv(t.st, g, bias, reinterpret_cast<f16*>(C), reinterpret_cast<f16*>(out2), d, T, Tpad, H, form));
+  }
+  if (L < 1 || N != L * 2 * d || kx_lstride < (int64_t)B * T * d || vt_lstride < (int64_t)B * d * Tpad || kx_lstride % 8 || vt_lstride % 8) {
+    set_error("wis_op_gemm_i8: cross K/V has N = L 2 d and layer strides as wis_op_enc_crosskv"); return WIS_E_ARG; }
+  return t.finish(launch_gemm_i8_crosskv(t.st, g, bias, reinterpret_cast<f16*>(C), reinterpret_cast<f16*>(out2), d, T, Tpad, H, kx_lstride, vt_lstride, form));
+}
+// one encoder GEMM timed on the stream (tools/enc_int8_bench.py): bias + f16 rows, the weight matrix rotated through ~640 MB of copies
+int wis_bench_enc_gemm(int device, int bits, int M, int N, int K, int form, int reps, float* us_out) {
+  Tap t(device, "wis_bench_enc_gemm"); WIS_RET(t.rc);
+  if ((bits != 8 && bits != 16 && bits != 1 && bits != 2) || M < 1 || N < 128 || K < 128 || reps < 1 || !us_out || form < 0 || form > 3 || (bits <= 2 && N != K)) {
+    set_error("wis_bench_enc_gemm: bad argument"); return WIS_E_ARG; }
+  const size_t es = bits == 8 ? 1 : 2, wbytes = bits <= 2 ? (size_t)M * K * 4 : (size_t)N * K * es;
+  const int nrot = (int)std::max<size_t>(1, ((size_t)640 << 20) / wbytes);
+  char *A = nullptr, *W = nullptr; float *sa = nullptr, *sw = nullptr, *bias = nullptr; f16* C = nullptr;
+  WIS_RET(t.get(&A, (size_t)M * K * es)); WIS_RET(t.get(&W, wbytes * nrot));
+  WIS_RET(t.get(&sa, (size_t)M, true)); WIS_RET(t.get(&sw, (size_t)N, true)); WIS_RET(t.get(&bias, (size_t)N, true)); WIS_RET(t.get(&C, (size_t)M * N));
+  WIS_HIP_CHECK(hipMemsetAsync(A, 1, (size_t)M * K * es, t.st)); WIS_HIP_CHECK(hipMemsetAsync(W, 1, wbytes * nrot, t.st));
+  auto one = [&](int i) {
+    const char* w = W + (size_t)(i % nrot) * wbytes;
+    // bits 1 / 2: the quantise launches at [M][K] - the row quantiser on f16 rows, LayerNorm + quantise on f32 rows (sw, bias: gamma, beta; K = N)
+    if (bits == 1) return launch_quant_rows(t.st, reinterpret_cast<const f16*>(w), reinterpret_cast<int8_t*>(C), sa, M, K);
+    if (bits == 2) return launch_layernorm_quant(t.st, reinterpret_cast<const float*>(w), sw, bias, reinterpret_cast<int8_t*>(C), sa, nullptr, M, K);
+    if (bits == 8) return launch_gemm_i8_generic(t.st, GemmI8P{reinterpret_cast<const int8_t*>(A), sa, reinterpret_cast<const int8_t*>(w), sw, M, N, K}, bias, nullptr, C, 0, form);
+    return launch_gemm_generic(t.st, gemm_plain(reinterpret_cast<const f16*>(A), K, reinterpret_cast<const f16*>(w), M, N, K), bias, nullptr, C, 0);
+  };
+  WIS_RET(one(0));
+  hipEvent_t e0 = nullptr, e1 = nullptr;
+  WIS_HIP_CHECK(hipEventCreate(&e0)); WIS_HIP_CHECK(hipEventCreate(&e1));
+  int rc = WIS_OK;
+  hipEventRecord(e0, t.st);
+  for (int i = 1; i <= reps && !rc; ++i) rc = one(i);
+  hipEventRecord(e1, t.st);
+  rc = t.finish(rc);
+  float ms = 0.f;
+  if (!rc && hipEventElapsedTime(&ms, e0, e1) != hipSuccess) { set_error("wis_bench_enc_gemm: no timing"); rc = WIS_E_HIP; }
+  hipEventDestroy(e0); hipEventDestroy(e1);
+  *us_out = ms * 1000.f / reps;
+  return rc;
+}
+
 // ---- taps of what runs behind the logits (tests/test_gpu_sample_ops.py): the cache movers of a beam step and of a verified draft window, and the three
 // softmax readers, through the product's launch_* functions on caller-supplied device memory
 int wis_op_kv_reorder(int device, void* kc_f16, void* vc_f16, int64_t layer_stride_elems, int L, const int32_t* parent, const int32_t* step_u, const int32_t* done,

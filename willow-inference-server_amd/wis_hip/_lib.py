@@ -34,6 +34,11 @@ class Config(C.Structure):
         ("lang_ids", C.POINTER(C.c_int32)), ("n_lang", C.c_int32), ("decoder_weight_bits", C.c_int32)]
 
 
+class ModelExt(C.Structure):
+    """wis_model_ext_t: wis_model_create_ex's options (encoder_weight_bits 0 / 16: f16 encoder, 8: int8 encoder)"""
+    _fields_ = [("size", C.c_int32), ("encoder_weight_bits", C.c_int32)]
+
+
 class Tensor(C.Structure):
     _fields_ = [("name", C.c_char_p), ("dtype", C.c_int32), ("rank", C.c_int32), ("shape", C.c_int64 * 4), ("offset", C.c_uint64)]
 
@@ -118,6 +123,7 @@ SYMBOLS = [
     ("wis_longmel_window", _i, [_vp, C.POINTER(_i64), _i, _vp, _i]),
     ("wis_longmel_destroy", None, [_vp]),
     ("wis_model_create", _i, [C.POINTER(Config), _vp, _sz, _i, C.POINTER(Tensor), _i, _i, C.POINTER(_vp)]),
+    ("wis_model_create_ex", _i, [C.POINTER(Config), _vp, _sz, _i, C.POINTER(Tensor), _i, _i, C.POINTER(_vp), C.POINTER(ModelExt)]),
     ("wis_model_destroy", None, [_vp]),
     ("wis_model_device_bytes", _sz, [_vp]),
     ("wis_model_clone", _i, [_vp, C.POINTER(_vp)]),
@@ -192,6 +198,10 @@ SYMBOLS = [
     ("wis_op_enc_qkv", _i, [_i] + [_vp] * 5 + [_i] * 3),
     ("wis_op_enc_crosskv", _i, [_i] + [_vp] * 5 + [_i] * 4 + [_i64] * 2),
     ("wis_op_gemm_splitk_ln", _i, [_i] + [_vp] * 7 + [_i] * 4),
+    ("wis_op_quant_rows", _i, [_i, _vp, _vp, _vp, _i, _i]),
+    ("wis_op_layernorm_quant", _i, [_i] + [_vp] * 6 + [_i] * 2),
+    ("wis_op_gemm_i8", _i, [_i] + [_vp] * 8 + [_i] * 10 + [_i64] * 2),
+    ("wis_bench_enc_gemm", _i, [_i] * 7 + [_fp]),
     ("wis_op_kv_reorder", _i, [_i, _vp, _vp, _i64, _i, _vp, _vp, _vp, _i, _i, _i, _i, _i]),
     ("wis_op_kv_reorder_from", _i, [_i, _vp, _vp, _i64, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _i]),
     ("wis_op_dec_self_attn_long", _i, [_i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i]),

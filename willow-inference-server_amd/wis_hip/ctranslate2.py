@@ -50,6 +50,9 @@ def _next_seed():
     return z ^ (z >> 31)
 
 
+ENCODER_COMPUTE_TYPES = ("float16", "int8")      # models.Whisper(encoder_compute_type=...)
+
+
 def get_supported_compute_types(device="cuda", device_index=0):
     buf = C.create_string_buffer(64)
     _lib.check(_lib.load().wis_supported_compute_types(device_index, buf, 64))
@@ -217,16 +220,18 @@ def make_tensor_index(index):
     return arr
 
 
-def create_handle(a, arena, index, device, max_batch=8, max_beam=5, arena_device_ptr=None, n_vocab=None, **cfgkw):
-    """arena: uint8 ndarray (host) or None with arena_device_ptr = (ptr, nbytes) already on `device`."""
+def create_handle(a, arena, index, device, max_batch=8, max_beam=5, arena_device_ptr=None, n_vocab=None, encoder_bits=16, **cfgkw):
+    """arena: uint8 ndarray (host) or None with arena_device_ptr = (ptr, nbytes) already on `device`.
+    encoder_bits: 16, or 8 for the int8 encoder (wis_model_create_ex; include/wis_hip.h wis_model_ext_t)."""
     cfg = make_config(a, max_batch, max_beam, n_vocab=n_vocab, **cfgkw)
     tens = make_tensor_index(index)
     h = C.c_void_p()
+    ext = _lib.ModelExt(C.sizeof(_lib.ModelExt), int(encoder_bits))
     if arena_device_ptr is not None:
         p, nbytes = arena_device_ptr
-        rc = _lib.load().wis_model_create(C.byref(cfg), C.c_void_p(p), nbytes, 1, tens, len(index), device, C.byref(h))
+        rc = _lib.load().wis_model_create_ex(C.byref(cfg), C.c_void_p(p), nbytes, 1, tens, len(index), device, C.byref(h), C.byref(ext))
     else:
-        rc = _lib.load().wis_model_create(C.byref(cfg), _lib.ptr(arena), arena.nbytes, 0, tens, len(index), device, C.byref(h))
+        rc = _lib.load().wis_model_create_ex(C.byref(cfg), _lib.ptr(arena), arena.nbytes, 0, tens, len(index), device, C.byref(h), C.byref(ext))
     _lib.check(rc)
     return h
 
@@ -752,9 +757,14 @@ class Whisper:
     is_multilingual = True
 
     def __init__(self, model_path, device="cuda", device_index=0, compute_type="default", inter_threads=1, intra_threads=0,
-                 max_batch=8, max_beam=5, weights=None, arch=None, replicas_per_device=None, **_ignored):
+                 max_batch=8, max_beam=5, weights=None, arch=None, replicas_per_device=None, *, encoder_compute_type="float16", **_ignored):
         if device not in ("cuda", "auto", "hip", "gpu"):
             raise ValueError(f"wis_hip runs on MI355X GPUs only (device={device!r}); there is no CPU path")
+        # the ENCODER's linears and the cross K/V projection: "float16", or "int8" (W8A8 on the i8 matrix instruction; include/wis_hip.h
+        # wis_model_ext_t has the rule).  Independent of compute_type, which is about the decoder's weights
+        if encoder_compute_type not in ENCODER_COMPUTE_TYPES:
+            raise ValueError(f"unsupported encoder_compute_type {encoder_compute_type!r} ({', '.join(ENCODER_COMPUTE_TYPES)})")
+        self.encoder_compute_type = encoder_compute_type
         _lib.require_gpu()
         # "float16" (default / "auto") or "int8_float16" (the reference's GPU default, main.py:242): per-row int8 DECODER
         # weights with f16 activations; everything else stays f16
@@ -776,7 +786,8 @@ class Whisper:
             raise ValueError(f"max_beam={max_beam}: the engine decodes with beam sizes 1..{MAX_BEAM}")
         arena, index = W.build_arena(weights)
         kw = dict(suppress_ids=cfg.get("suppress_ids"), suppress_begin=cfg.get("suppress_ids_begin"), lang_ids=cfg.get("lang_ids"),
-                  weight_bits=8 if self.compute_type == "int8_float16" else 16, special=self.special)
+                  weight_bits=8 if self.compute_type == "int8_float16" else 16, special=self.special,
+                  encoder_bits=8 if encoder_compute_type == "int8" else 16)
         enc_shape = (arch["n_audio_ctx"], arch["d_model"])
         self._replicas = [_Replica(h, d, arch["n_mels"], enc_shape) for h, d in zip(create_replicas(arch, arena, index, devs, max_batch, max_beam, **kw), devs)]
         # CTranslate2's `inter_threads` = batches a model runs in parallel (reference main.py:341-355 passes ctranslate2_threads).  Here:
@@ -799,7 +810,7 @@ class Whisper:
         """Wrap replicas that already exist: [(wis_model handle, device), ...] - e.g. models created from a weight arena an
         RCCL broadcast delivered straight into device memory (`create_handle(arena_device_ptr=...)`, wis_hip/dist.py)."""
         self = cls.__new__(cls)
-        self.compute_type = "float16"
+        self.compute_type = self.encoder_compute_type = "float16"
         self.arch, self.decode_config = arch, decode_config or {}
         self.special = special_tokens_for(arch, self.decode_config.get("special"), self.decode_config.get("lang_ids"))
         self._replicas = [_Replica(h, d, arch["n_mels"], (arch["n_audio_ctx"], arch["d_model"])) for h, d in handles]

@@ -136,6 +136,8 @@ class APISettings:
     sv_speakers_dir: str = "speakers/voice_auth"
     # "float16" or "int8_float16" (the reference picks int8_float16 on GPUs, main.py:242: here it quantises the decoder weights)
     compute_type: str = "float16"
+    # the encoder's linears and the cross K/V projection: "float16", or "int8" (W8A8 GEMMs; off by default, independent of compute_type)
+    encoder_compute_type: str = "float16"
 
     def __post_init__(self):
         env = {k.lower(): v for k, v in os.environ.items()}

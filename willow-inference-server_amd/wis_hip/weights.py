@@ -375,6 +375,10 @@ def write_ct2_model_bin(path, weights, spec="WhisperSpec", revision=3, aliases=N
 # ---- int8_float16: what the engine does to the decoder weights, restated for the oracle -------------------------
 DECODER_LINEARS = ("self_attention/linear_0", "self_attention/linear_1", "attention/linear_0", "attention/linear_2", "ffn/linear_0", "ffn/linear_1")
 
+# the encoder matrices the int8 encoder (models.Whisper(encoder_compute_type="int8")) stores as int8 rows, per encoder layer; with them the
+# cross K/V projection of every decoder layer ("attention/linear_1").  Quantised by quantize_rows from the f16 matrix, the query scale folded first
+ENCODER_LINEARS = ("self_attention/linear_0", "self_attention/linear_1", "ffn/linear_0", "ffn/linear_1")
+
 
 def quantize_rows(w):
     """CTranslate2's per-row int8 scheme as csrc/dec_kernels.hip implements it (float32 arithmetic, round-half-even):
