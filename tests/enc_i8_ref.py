@@ -47,3 +47,86 @@ def encode(w, arch, mel, quant=True, dtype=np.float64, f16=True, lazy=True):
         xn = ln(x, p + "ffn/layer_norm")
         x = x + lin(r16(_gelu(lin(xn, p + "ffn/linear_0"))), p + "ffn/linear_1")
     return ln(x, "encoder/layer_norm")
+
+
+def cross_kv_parts(w, arch, mem):
+    """What the int8 cross-K/V projection multiplies: the memory rows [T][d] (rounded to f16, as the engine keeps them) through quantize_rows ->
+    (qa, sa), and per decoder layer the f16 rows of attention/linear_1 ([K rows | V rows], 2 d of them) through quantize_rows, with the bias ->
+    [(qw, sw, bias)]."""
+    L = arch.get("n_dec_layers", arch["n_layers"])
+    qa, sa = W.quantize_rows(np.asarray(mem).astype(np.float16))
+    layers = []
+    for l in range(L):
+        p = f"decoder/layer_{l}/attention/linear_1/"
+        layers.append((*W.quantize_rows(np.asarray(w[p + "weight"], np.float32).astype(np.float16)), np.asarray(w[p + "bias"], np.float32)))
+    return qa, sa, layers
+
+
+def cross_kv_from(qa, sa, layers, dtype=np.float64, f16=True):
+    """[(K, V)] per layer, [T][d] each: the exact integer product, times sa[m] sw[n], plus the bias, in `dtype`; then rounded to f16 (the engine's K / V
+    images are f16) when `f16`."""
+    d, out = qa.shape[1], []
+    for qw, sw, b in layers:
+        acc = qa.astype(np.float64) @ qw.astype(np.float64).T      # (exact: |acc| <= 127^2 d < 2^53)
+        kv = acc.astype(dtype) * (sa.astype(dtype)[:, None] * sw.astype(dtype)[None, :]) + b.astype(dtype)
+        kv = kv.astype(np.float16).astype(dtype) if f16 else kv
+        out.append((kv[:, :d], kv[:, d:]))
+    return out
+
+
+def cross_kv(w, arch, mem, quant=True, dtype=np.float64, f16=True):
+    """Encoder memory [T][d] -> per decoder layer (K, V), [T][d] each, as run_cross_kv leaves them: by the int8 rule when `quant` (cross_kv_parts,
+    cross_kv_from), else the f16 memory times the f16 weight rows plus the bias in `dtype`; rounded to f16 when `f16`.
+    quant=False, f16=False is the oracle's cross_kv (oracle/whisper_ref.py) in `dtype`."""
+    if quant:
+        return cross_kv_from(*cross_kv_parts(w, arch, mem), dtype=dtype, f16=f16)
+    r16 = (lambda x: np.asarray(x).astype(np.float16).astype(dtype)) if f16 else (lambda x: np.asarray(x).astype(dtype))
+    d, out, m = arch["d_model"], [], r16(mem)
+    for l in range(arch.get("n_dec_layers", arch["n_layers"])):
+        p = f"decoder/layer_{l}/attention/linear_1/"
+        kv = r16(m @ r16(np.asarray(w[p + "weight"], np.float32)).T + np.asarray(w[p + "bias"], np.float32).astype(dtype))
+        out.append((kv[:, :d], kv[:, d:]))
+    return out
+
+
+def decoder_logits(w, arch, ckv, tokens, dtype=np.float64):
+    """Teacher-forced logits [T][n_vocab] behind `tokens` for ONE utterance whose cross K / V are `ckv` (cross_kv's result): the oracle's decoder_step
+    (oracle/whisper_ref.py), one position at a time, on tensors of `dtype`."""
+    import torch
+    from oracle.whisper_ref import WhisperRef
+    td = torch.float64 if dtype == np.float64 else torch.float32
+    ref = WhisperRef(w, arch["d_model"], arch.get("n_dec_layers", arch["n_layers"]), arch["n_heads"], n_vocab=arch["n_vocab"])
+    ref.w = {k: v.to(td) for k, v in ref.w.items() if k.startswith("decoder/")}
+    tck = [(torch.from_numpy(np.ascontiguousarray(k, dtype))[None], torch.from_numpy(np.ascontiguousarray(v, dtype))[None]) for k, v in ckv]
+    cache, rows = [None] * ref.L, []
+    for t, tok in enumerate(tokens):
+        rows.append(ref.decoder_step(np.asarray([[tok]]), t, cache, tck)[0].numpy())
+    return np.stack(rows)
+
+
+def scale_family(M, K, seed):
+    """f16 rows [M][K] for the row quantiser, every row with a scale of its own: absmax one of f16's normal values, drawn without repetition and uniformly
+    over their bit patterns (log-uniform from 2^-14 to 65504), at a random column; half of the other entries at the f16 value nearest (k + 0.5) * scale, k uniform in [0, 126], random sign - the rounding boundaries, where
+    rint(r * inv) and rint(r / scale), or an inv one ulp off, part ways - the rest uniform in +- absmax."""
+    rng = np.random.default_rng(seed)
+    mx = rng.choice(np.arange(0x0400, 0x7C00), M, replace=False).astype(np.uint16).view(np.float16).astype(np.float32)
+    scale = (mx / np.float32(127.0)).astype(np.float32)
+    rows = (rng.uniform(-1, 1, (M, K)) * mx[:, None]).astype(np.float32)
+    ties = (rng.integers(0, 127, (M, K)).astype(np.float32) + np.float32(0.5)) * scale[:, None] * rng.choice(np.float32([-1, 1]), (M, K))
+    rows = np.where(rng.permuted(np.tile(np.arange(K) % 2 == 0, (M, 1)), axis=1), ties, rows).astype(np.float16)
+    rows[np.arange(M), rng.integers(0, K, M)] = mx * rng.choice(np.float32([-1, 1]), M)
+    assert (np.abs(rows.astype(np.float32)).max(1) == mx).all()
+    return rows
+
+
+def ln_scale_family(M, d, seed):
+    """f32 rows [M][d], gamma, beta for LayerNorm + quantise, the scales spread as far as a LayerNorm lets them: it fixes a row's variance, so the
+    absmax of its output lies between about 2.5 (the largest of d normal values) and sqrt(d - 1) gamma (one outlier).  One entry of every row is
+    raised by a factor log-uniform over that range; the rows then get a gain and an offset of their own, which the LayerNorm takes out again.
+    With d = 256 the absmax covers three binades of f16 - some 3000 values, so 4096 rows have about 1900 different scales (the unfused quantiser,
+    which can be handed any row, gets f16's whole range: scale_family)."""
+    rng = np.random.default_rng(seed)
+    x = rng.standard_normal((M, d)).astype(np.float32)
+    x[np.arange(M), rng.integers(0, d, M)] = np.exp(rng.uniform(np.log(2.0), np.log(200.0), M)) * rng.choice([-1.0, 1.0], M)
+    x = (x * np.exp(rng.uniform(-3, 3, (M, 1))) + rng.standard_normal((M, 1))).astype(np.float32)
+    return x, (1 + 0.1 * rng.standard_normal(d)).astype(np.float32), (0.1 * rng.standard_normal(d)).astype(np.float32)

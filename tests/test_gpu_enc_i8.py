@@ -10,16 +10,9 @@ e16 = the f16 engine against the unquantised reference in float64, both measured
 import numpy as np
 import pytest
 
+from enc_i8_taps import EPS, _buf, _gemm, _kept, gemm_case, tiny_rig
+
 pytestmark = pytest.mark.gpu
-EPS, F16_R, GELU_LIP = 2.0 ** -24, 2.0 ** -10, 1.13
-
-
-def _buf(n, dt):
-    return np.full(n * np.dtype(dt).itemsize, 0x5A, np.uint8).view(dt)
-
-
-def _kept(a):
-    return bool((np.ascontiguousarray(a).view(np.uint8) == 0x5A).all())
 
 
 @pytest.mark.parametrize("M", [1, 5])
@@ -54,39 +47,6 @@ def test_quantisers(lib, M, K, fused):
     assert _kept(q[M:]) and _kept(s[M:])
 
 
-def _where(epi, M, N, B, T, H, L):
-    """-> (index of output (m, n) in the concatenation [C | out2], elements of C, elements of out2); 64 / 8 spare elements behind every image"""
-    m, n = np.meshgrid(np.arange(M), np.arange(N), indexing="ij")
-    if epi < 3:
-        return m * N + n, (M + 3) * N, 0
-    d, Tpad, b, t = 64 * H, (T + 63) // 64 * 64, m // T, m % T
-    if epi == 3:      # [Q | K] rows; V^T image [B][H][64][Tpad], key t at bits 2 and 3 of t swapped
-        nn, tp = n - 2 * d, (t & ~12) | ((t & 4) << 1) | ((t & 8) >> 1)
-        return np.where(n < 2 * d, m * 2 * d + n, M * 2 * d + 64 + ((b * H + nn // 64) * 64 + nn % 64) * Tpad + tp), M * 2 * d + 64, B * d * Tpad + 8
-    l, nl, kls, vls = n // (2 * d), n % (2 * d), M * d + 8, B * d * Tpad + 8      # per layer: K image [B][H][8][T][8], V^T image [B][H][64][Tpad]
-    h, dh = (nl % d) // 64, nl % 64
-    kx = l * kls + (((b * H + h) * 8 + dh // 8) * T + t) * 8 + dh % 8
-    return np.where(nl < d, kx, L * kls + 64 + l * vls + ((b * H + h) * 64 + dh) * Tpad + t), L * kls + 64, L * vls
-
-
-def _gemm(lib, epi, form, A, sa, Wq, sw, bias, res, flags, dims):
-    """-> (outputs as float64 [M][N] in GEMM order, the raw buffers' words), after checking that nothing else was written"""
-    from wis_hip._lib import DevBuf, check
-    (M, K), N, (B, T, H, L) = A.shape, Wq.shape[0], dims
-    dt = np.float32 if (epi == 2 or flags & 4) else np.float16
-    idx, nc, nv = _where(epi, M, N, *dims)
-    c = _buf(nc, dt)
-    if epi == 2:
-        c[:M * N] = res.ravel()      # in place: C holds the residual
-    ins = [DevBuf.from_numpy(a) if a is not None else None for a in (A, sa, Wq, sw, bias)]
-    c_d, v_d = DevBuf.from_numpy(c), DevBuf.from_numpy(_buf(max(nv, 1), dt))
-    check(lib.wis_op_gemm_i8(0, *[i and i.ptr for i in ins], c_d.ptr if epi == 2 else None, c_d.ptr, v_d.ptr if nv else None, M, N, K, epi, flags, form, B, T, H, L,
-                             M * 64 * H + 8, B * 64 * H * ((T + 63) // 64 * 64) + 8))
-    buf = np.concatenate([c_d.to_numpy(dt, (nc,)), v_d.to_numpy(dt, (max(nv, 1),))])
-    assert _kept(np.delete(buf, idx.ravel())), "wrote outside its outputs"
-    return buf[idx].astype(np.float64), buf.view(np.uint8)
-
-
 # (epilogue 0 generic / 1 GELU / 2 residual / 3 QKV / 4 cross K/V, form 1 = 128 x 128 / 2 = 64 x 128 / 3 = 256 x 256 / 0 = the encoder's pick, M or (B, T), N or H,
 # K or L): one row more than the form's height (QKV / cross K/V: four, T % 4 == 0) or one row; one and three tiles wide; K of one / two / three k-tiles
 @pytest.mark.parametrize("epi,form,m,n,k", [
@@ -96,23 +56,7 @@ def _gemm(lib, epi, form, A, sa, Wq, sw, bias, res, flags, dims):
     (3, 1, (1, 132), 2, 128), (3, 2, (2, 36), 2, 128), (3, 3, (1, 260), 4, 256),
     (4, 1, (1, 132), 2, 3), (4, 2, (2, 36), 2, 1), (4, 3, (1, 260), 4, 2)])
 def test_gemm_i8(lib, epi, form, m, n, k):
-    from scipy.special import erf
-    dims = (m[0], m[1], n, k) if epi >= 3 else (0, 0, 0, 0)
-    M, N, K = (m[0] * m[1], (3 if epi == 3 else 2 * k) * 64 * n, 64 * n) if epi >= 3 else (m, n, k)
-    rng = np.random.default_rng(epi * 1000 + form * 100 + M + N + K)
-    A, Wq = rng.integers(-127, 128, (M, K), dtype=np.int8), rng.integers(-127, 128, (N, K), dtype=np.int8)
-    sa, sw = rng.uniform(0.002, 0.02, M).astype(np.float32), rng.uniform(0.001, 0.004, N).astype(np.float32)
-    bias, res = rng.standard_normal(N).astype(np.float32), (rng.standard_normal((M, N)).astype(np.float32) if epi == 2 else None)
-    flags = 4 if (epi == 0 and form == 3) else 0      # the generic functor's fp32 output
-    out, raw = _gemm(lib, epi, form, A, sa, Wq, sw, bias, res, flags, dims)
-    assert np.array_equal(raw, _gemm(lib, epi, form, A, sa, Wq, sw, bias, res, flags, dims)[1]), "two runs differ"
-    prod = (A.astype(np.float64) @ Wq.astype(np.float64).T) * (sa.astype(np.float64)[:, None] * sw.astype(np.float64)[None, :])
-    S, pre = np.abs(prod) + np.abs(bias) + (np.abs(res) if epi == 2 else 0), prod + bias + (res if epi == 2 else 0)
-    ref = 0.5 * pre * (1.0 + erf(pre / np.sqrt(2.0))) if epi == 1 else pre
-    bound = (5 if epi == 2 else 4) * EPS * S * (GELU_LIP if epi == 1 else 1.0) + (0.0 if (epi == 2 or flags & 4) else F16_R * np.abs(ref))
-    err = np.abs(out - ref)
-    print(f"gemm_i8 epi {epi} form {form} M{M} N{N} K{K}: worst |out - ref| / bound = {float((err / bound).max()):.3f}")
-    assert np.isfinite(out).all() and (err <= bound).all(), float((err / bound).max())
+    gemm_case(lib, epi, form, m, n, k)      # (tests/enc_i8_taps.py: the bound of the docstring above, the fill pattern, two runs equal)
 
 
 def test_gemm_i8_is_exact_in_the_integer_part(lib):
@@ -132,15 +76,10 @@ def test_gemm_i8_is_exact_in_the_integer_part(lib):
 @pytest.fixture(scope="module")
 def rig(golden_dir):
     import torch  # noqa: F401  (before libwis_hip.so: one HIP runtime per process)
-    from enc_i8_ref import encode
-    from wis_hip import ctranslate2 as ct2, weights as W
-    mel = np.load(golden_dir + "/logmel_3sec.npz")["mel"].astype(np.float32)
-    mels = np.ascontiguousarray(np.stack([mel, np.roll(mel, 53, axis=-1)]))
-    w, a = W.synthetic_weights("tiny", seed=1234, std=0.02, emb_std=0.06, ln_jitter=0.1), W.arch("tiny")
+    from wis_hip import ctranslate2 as ct2
+    w, a, mels, refs = tiny_rig(golden_dir)
     mk = lambda **kw: ct2.Whisper("unused", weights=w, arch=a, max_batch=2, max_beam=1, **kw)
     models = {"plain": mk(), "f16": mk(encoder_compute_type="float16"), "int8": mk(encoder_compute_type="int8")}
-    refs = {k: np.stack([encode(w, a, m, quant=q, dtype=dt) for m in mels]) for k, (q, dt) in
-            {"q64": (True, np.float64), "q32": (True, np.float32), "f64": (False, np.float64)}.items()}
     yield models, mels, refs
     for m in models.values():
         m.close()

@@ -143,6 +143,25 @@ def test_build_dependencies_follow_the_include_lines():
     assert not [s for s in bp.HIP_SOURCES if s in reached]          # no source is another source's include
 
 
+def test_build_stamps_do_not_depend_on_where_the_tree_lies(tmp_path):
+    """A built tree that is copied or moved has nothing to recompile: the stamp of an object digests the file contents and the flags without the
+    tree's own root (the -I flags name it).  build.py loaded from a copy of the sources elsewhere gives the digests of the tree's."""
+    import importlib.util
+    import shutil
+    pkg = os.path.join(ROOT, "willow-inference-server_amd")
+    shutil.copytree(os.path.join(pkg, "csrc"), tmp_path / "moved" / "willow-inference-server_amd" / "csrc")
+    shutil.copytree(os.path.join(ROOT, "include"), tmp_path / "moved" / "include")
+    shutil.copy2(os.path.join(pkg, "build.py"), tmp_path / "moved" / "willow-inference-server_amd")
+    spec = importlib.util.spec_from_file_location("wis_build_moved", str(tmp_path / "moved" / "willow-inference-server_amd" / "build.py"))
+    moved = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(moved)
+    here = _build_py()
+    assert moved.ROOT != here.ROOT and moved.HIP_FLAGS != here.HIP_FLAGS
+    for src in here.HIP_SOURCES + here.C_SOURCES:
+        dig = lambda bp: bp._digest([os.path.join(bp.CSRC, src)] + bp.include_closure(src))
+        assert dig(moved) == dig(here), src
+
+
 def test_incremental_rebuild_compiles_only_what_includes_the_edit(lib, tmp_path):
     """On a copy of csrc/ with the tree's objects beside it: nothing to do; a comment appended to taps.hip recompiles taps.hip alone;
     then nothing again.  An object without a source (a build directory older than the split) is gone before the link."""

@@ -72,7 +72,9 @@ def _digest(paths):
     for p in paths:
         with open(p, "rb") as f:
             h.update(f.read())
-    h.update(" ".join(HIP_FLAGS + C_FLAGS + [f"{k}:{' '.join(v)}" for k, v in sorted(SOURCE_FLAGS.items())]).encode())
+    # the flags name the tree's own directories (-I): without its root, so that a built tree that is copied or moved stays up to date
+    flags = " ".join(HIP_FLAGS + C_FLAGS + [f"{k}:{' '.join(v)}" for k, v in sorted(SOURCE_FLAGS.items())])
+    h.update(flags.replace(ROOT, "<root>").encode())
     return h.hexdigest()
 
 
