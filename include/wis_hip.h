@@ -178,10 +178,24 @@ typedef struct {
  * (wis_hip.weights.quantize_rows).  Weight rows are quantised at load from the f16 matrix the f16 encoder would multiply by (the query scale folded
  * into the Q rows first) and that f16 matrix is not kept; activation rows are quantised from the f16-rounded values the f16 encoder would read
  * (LayerNorm output, attention output, FFN hidden, encoder memory).  A product is (float)(sum_k qa qw) * (scale_a[m] * scale_w[n]), the sum exact in
- * int32, then the f16 path's epilogue in f32.  Anything else than 0 / 8 / 16, or a size below the struct's: WIS_E_ARG. */
+ * int32, then the f16 path's epilogue in f32.  Anything else than 0 / 8 / 16: WIS_E_ARG.
+ * cross_kv_bits: 0 / 16 = the f16 cross-attention K/V images; 8 = INT8 CROSS K/V: what every decode step re-reads per utterance and decoder layer is kept as
+ * int8 values with one f32 scale per (layer, utterance, head, key) and matrix, by THE RULE above: the row is the 64 f16 values of K - and, separately, the 64 of
+ * V - that the f16 engine would have stored for that head and key.  The projection still writes f16 (a few layers at a time, into a staging block) and a kernel
+ * of its own quantises it; the decode step's cross-attention converts the int8 values to f16 in registers (exact) for the same f16 MFMAs, multiplies the f32
+ * score by the key's K scale and the f32 softmax weight by the key's V scale before that weight is rounded to f16.  Images of one layer (Tpad = T rounded up
+ * to 64; keys [T, Tpad) hold zeros and scale 1):
+ *   K   i8 [B][H][4][Tpad][16]   cell (j, t) = K[t][8 j .. 8 j + 7] followed by K[t][32 + 8 j .. 32 + 8 j + 7] of the head
+ *   V   i8 [B][H][64][Tpad]      row dh, byte 64 g + 16 j + 8 e + i = V[64 g + 32 e + 8 j + i][dh]   (g: 64-key group, j < 4, e < 2, i < 8)
+ *   sk, sv  f32 [B][H][Tpad]     the scales of key t's K row and V row
+ * Halves the per-utterance cross K/V memory and the bytes a decode step streams from it.  Independent of decoder_weight_bits and encoder_weight_bits; clones
+ * inherit it.  wis_align / wis_debug_align_matrix read the f16 K image and answer WIS_E_UNSUPPORTED on such a handle; everything else works unchanged.
+ * SIZE: a caller that knows only the first two fields passes size 8 and gets the f16 images; any other size below the struct's, or a value other than
+ * 0 / 8 / 16: WIS_E_ARG. */
 typedef struct {
   int32_t size;
   int32_t encoder_weight_bits;
+  int32_t cross_kv_bits;
 } wis_model_ext_t;
 
 #define WIS_DT_F32 0
@@ -684,6 +698,19 @@ int wis_op_dec_cross_attn_folded(int device, const float* q_raw, const float* xr
 int wis_op_dec_cross_attn_stat(int device, const float* q, const float* q2, const float* stat, const float* qcs, const float* qb,
                                const void* kx_f16, const void* vt_f16, void* out_f16, int B, int R, int H, int T, int chunks,
                                int out_mb, int kv_shared, int no_spin);
+/* ---- the int8 cross K/V (wis_model_ext_t::cross_kv_bits has the rule and the layouts; tests/test_gpu_cross_q8.py), device pointers.
+ * wis_op_cross_kv_quant: the launch run_cross_kv makes behind every group of layers - f16 images kx [B][H][8][T][8] and vt [B][H][64][Tpad] of L layers (layer
+ * strides kx_lstride / vt_lstride in f16 elements) -> kq / vq (layer strides in bytes, multiples of 16), sk / sv (layer stride in floats).
+ * wis_op_dec_cross_attn_q8: wis_op_dec_cross_attn_stat with the int8 images and scales of ONE layer in kx / vt's place (through the same launch function);
+ * 256-key chunks always (`chunks` >= 1 is not otherwise read), T <= 1536, no granule hand-off.  Three launches per call on one set of tickets.
+ * wis_debug_cross_kv: utterance b of layer `layer` of the handle's current cross K/V to the host - an f16 handle fills kx_f16 [H][8][T][8] and vt_f16
+ * [H][64][Tpad]; an int8 handle kq [H][4][Tpad][16], vq [H][64][Tpad], sk and sv [H][Tpad]; the other group must be NULL.  *is_int8 says which. */
+int wis_op_cross_kv_quant(int device, const void* kx_f16, const void* vt_f16, int B, int H, int T, int Tpad, int L, int64_t kx_lstride, int64_t vt_lstride,
+                          void* kq, void* vq, float* sk, float* sv, int64_t kq_lstride, int64_t vq_lstride, int64_t s_lstride);
+int wis_op_dec_cross_attn_q8(int device, const float* q, const float* q2, const float* stat, const float* qcs, const float* qb,
+                             const void* kq, const void* vq, const float* sk, const float* sv, void* out_f16, int B, int R, int H, int T, int chunks,
+                             int out_mb, int kv_shared);
+int wis_debug_cross_kv(wis_model_t* m, int layer, int b, void* kx_f16, void* vt_f16, void* kq, void* vq, float* sk, float* sv, int* is_int8);
 /* wis_op_dec_self_attn with the step's other choices: nb = 2 / 4 / 8 eight-position blocks per pass (the step graphs: 2 up to 16 cached positions,
  * 4 up to 32), out_mb > 0: the fragment image as above, and the TREE form (anc != NULL; draft verification): anc i32 [M][aw] - row m reads positions
  * < w0 from slot base[m] (base NULL: anc[m][0]) and position w0 + t from slot anc[m][min(t, aw - 1)]; rpu / sstride / rmul are unused then. */

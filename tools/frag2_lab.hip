@@ -18,6 +18,7 @@
 // build: hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -mllvm -amdgpu-mfma-vgpr-form -I include -I willow-inference-server_amd/csrc \
 //        -o tools/bin/frag2_lab tools/frag2_lab.hip        (variants of the flags are the experiment: see tools/gpu_session.sh frag2)
 #include "../willow-inference-server_amd/csrc/dec_kernels.hip"
+#include "../willow-inference-server_amd/csrc/cross_q8.hip"      // (launch_dec_cross_attn's int8 K/V branch: dec_kernels.hip calls into it)
 #include <cstdarg>
 #include <cstring>
 #include <vector>

@@ -13,6 +13,7 @@
 // build: hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -mllvm -amdgpu-mfma-vgpr-form -I include -I willow-inference-server_amd/csrc \
 //        -o tools/bin/frag_stress tools/frag_stress.hip          run: tools/bin/frag_stress [launches per stream = 2500]
 #include "../willow-inference-server_amd/csrc/dec_kernels.hip"
+#include "../willow-inference-server_amd/csrc/cross_q8.hip"      // (launch_dec_cross_attn's int8 K/V branch: dec_kernels.hip calls into it)
 #include <cstdarg>
 #include <cstring>
 #include <vector>

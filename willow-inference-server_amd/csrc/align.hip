@@ -482,6 +482,7 @@ int wis_align(wis_model_t* m, const float* input, int input_kind, int B, const i
   if (!m || !input || !start_seq || !text_len || !num_frames || !path_text || !path_time || !path_len || !token_probs || B < 1) { set_error("wis_align: bad argument"); return WIS_E_ARG; }
   WIS_ENTER(m, "wis_align")
   WIS_HIP_CHECK(hipSetDevice(m->device));
+  if (m->ckv_i8) { set_error("wis_align: word alignment reads the f16 cross K image; this handle was created with cross_kv_bits = 8 (cross_kv_compute_type \"int8\")"); return WIS_E_UNSUPPORTED; }
   WIS_RET(align_run(m, input, input_kind, B, start_seq, P, text, text_len, num_frames, median_filter_width, true, "wis_align"));
   const AlignState& a = m->al;
   const int ncap = m->cfg.n_text_ctx, cap = ncap + m->cfg.n_audio_ctx;
@@ -499,6 +500,7 @@ int wis_debug_align_matrix(wis_model_t* m, const float* input, int input_kind, i
   if (!m || !input || !start_seq || !text_len || !num_frames || !out || B < 1) { set_error("wis_debug_align_matrix: bad argument"); return WIS_E_ARG; }
   WIS_ENTER(m, "wis_debug_align_matrix")
   WIS_HIP_CHECK(hipSetDevice(m->device));
+  if (m->ckv_i8) { set_error("wis_debug_align_matrix: word alignment reads the f16 cross K image; this handle was created with cross_kv_bits = 8 (cross_kv_compute_type \"int8\")"); return WIS_E_UNSUPPORTED; }
   WIS_RET(align_run(m, input, input_kind, B, start_seq, P, text, text_len, num_frames, median_filter_width, false, "wis_debug_align_matrix"));
   // out: the utterances' dense [text_len + 1][num_frames / 2] matrices back to back
   const int T = m->cfg.n_audio_ctx; size_t o = 0;

@@ -2021,6 +2021,8 @@ __global__ __launch_bounds__(256) void dec_cross_attn_kernel(const float* __rest
   // per wave as one 16-byte piece per lane and array (clamped, unconditional) and handed out through LDS behind the prologue's barrier.
   // What that buys is REGISTERS: the operands no longer sit in VGPRs beside the K fragments while the requests are in flight, so the V
   // fragments can be requested up front as well and the kernel still fits four workgroups per CU.
+  // (ca_query.hpp holds this STG prologue - requests, Chan merge, staging, finish - as two device functions for dec_cross_attn_q8_kernel: a change to the
+  // arithmetic or the staging layout here is a change there)
   constexpr bool STG = FOLD == 4;
   float4 qa0_, qa1_, qb0_, qb1_, stq, stq2, stc;
   qa0_ = qa1_ = qb0_ = qb1_ = stq = stq2 = stc = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -2731,6 +2733,7 @@ __global__ __launch_bounds__(128 * NKW) void dec_cross_attn_rs_kernel(const floa
 }
 
 int launch_dec_cross_attn(hipStream_t st, const CrossAttnP& p) {
+  if (p.kq8) return launch_dec_cross_attn_q8(st, p);      // the int8 K/V images: a kernel of their own (cross_q8.hip); nothing below is involved
   const int B = p.B, R = p.R, H = p.H, d = p.d, T = p.T, Tpad = p.Tpad, chunks = p.chunks, xres_is_stat = p.xres_is_stat;
   const float* const xres = p.xres;
   if (xres && (!p.qcs || !p.qb || R > 8 || d > (xres_is_stat ? 2048 : 1280))) { set_error("dec_cross_attn: folded query needs column sums, bias, R <= 8 and d <= 1280 (2048 from partials)"); return WIS_E_ARG; }

@@ -175,8 +175,16 @@ struct CrossAttnP {
   unsigned long long* gran = nullptr; unsigned* epoch = nullptr;
   const float* q2 = nullptr; int xres_is_stat = 0;    // batched fold: q = q + q2; xres = row partials [B*R][d/16][2] instead of the rows
   int kv_shared = 0;      // 1: every row group b reads utterance 0's K / V (the B groups are rows of ONE utterance: draft verification)
+  // the int8 K/V images and their per-key scales (cross_q8.hip has the layouts).  kq8 set: launch_dec_cross_attn runs dec_cross_attn_q8_kernel on them - kx, vt, gran
+  // and epoch are not read, the chunks are 256 keys whatever `chunks` says (T <= 1536), the fold is the one from partials (xres_is_stat)
+  const int8_t* kq8 = nullptr; const int8_t* vq8 = nullptr; const float* sk = nullptr; const float* sv = nullptr;
 };
 int launch_dec_cross_attn(hipStream_t st, const CrossAttnP& p);
+int launch_dec_cross_attn_q8(hipStream_t st, const CrossAttnP& p);      // (launch_dec_cross_attn's branch for kq8 != null)
+// f16 cross K/V images of L layers (kx [B][H][8][T][8], vt [B][H][64][Tpad]; layer strides in elements) -> the int8 images and scales by the row rule, one
+// 64-value row per (layer, utterance, head, key) and matrix: kq i8 [B][H][4][Tpad][16], vq i8 [B][H][64][Tpad] (strides in bytes), sk / sv f32 [B][H][Tpad]
+int launch_cross_kv_quant(hipStream_t st, const f16* kx, const f16* vt, int B, int H, int T, int Tpad, int L, int64_t kx_ls, int64_t vt_ls,
+                          int8_t* kq, int8_t* vq, float* sk, float* sv, int64_t kq_ls, int64_t vq_ls, int64_t s_ls);
 
 // sampling: per-(row, chunk) masked max / sum-exp / top-2k of the logits
 struct SampleCfg {

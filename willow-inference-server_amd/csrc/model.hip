@@ -508,12 +508,22 @@ static int alloc_buffers(wis_model* m) {
   WIS_RET(dalloc(m, &m->kc_all, m->kv_layer_stride * L));
   WIS_RET(dalloc(m, &m->vc_all, m->kv_layer_stride * L));
   m->kx_lstride = (size_t)Bm * H * 8 * T * 8; m->vx_lstride = (size_t)Bm * H * 64 * m->Tpad;
-  WIS_RET(dalloc(m, &m->kx_all, m->kx_lstride * L));
-  WIS_RET(dalloc(m, &m->vx_all, m->vx_lstride * L));
-  WIS_HIP_CHECK(hipMemsetAsync(m->vx_all, 0, m->vx_lstride * L * 2, m->st));
+  if (m->ckv_i8) {      // f16 staging for ckv_G layers, the int8 images and scales for all of them (run_cross_kv)
+    m->ckv_G = L < 4 ? L : 4;
+    m->q8_lstride = (size_t)Bm * H * 64 * m->Tpad; m->s8_lstride = (size_t)Bm * H * m->Tpad;
+    WIS_RET(dalloc(m, &m->kx_stage, m->kx_lstride * m->ckv_G));
+    WIS_RET(dalloc(m, &m->vx_stage, m->vx_lstride * m->ckv_G));
+    WIS_HIP_CHECK(hipMemsetAsync(m->vx_stage, 0, m->vx_lstride * m->ckv_G * 2, m->st));
+    WIS_RET(dalloc(m, &m->kq_all, m->q8_lstride * L)); WIS_RET(dalloc(m, &m->vq_all, m->q8_lstride * L));
+    WIS_RET(dalloc(m, &m->sk_all, m->s8_lstride * L)); WIS_RET(dalloc(m, &m->sv_all, m->s8_lstride * L));
+  } else {
+    WIS_RET(dalloc(m, &m->kx_all, m->kx_lstride * L));
+    WIS_RET(dalloc(m, &m->vx_all, m->vx_lstride * L));
+    WIS_HIP_CHECK(hipMemsetAsync(m->vx_all, 0, m->vx_lstride * L * 2, m->st));
+  }
   for (int l = 0; l < L; ++l) {
-    m->kx[l] = m->kx_all + (size_t)l * m->kx_lstride;
-    m->vx[l] = m->vx_all + (size_t)l * m->vx_lstride;
+    m->kx[l] = m->kx_all ? m->kx_all + (size_t)l * m->kx_lstride : nullptr;
+    m->vx[l] = m->vx_all ? m->vx_all + (size_t)l * m->vx_lstride : nullptr;
     m->kc[l] = m->kc_all + (size_t)l * slots * ctx * d;     // one block per cache: kv_reorder_kernel walks the layers by stride
     m->vc[l] = m->vc_all + (size_t)l * slots * ctx * d;
   }
@@ -690,6 +700,24 @@ int run_encoder(wis_model* m, int B, hipStream_t on) {
 int run_cross_kv(wis_model* m, int B, const f16* mem) {
   const wis_config_t& c = m->cfg;
   const int d = c.d_model, T = c.n_audio_ctx;
+  if (m->ckv_i8) {
+    // int8 cross K/V: the same projection, ckv_G decoder layers at a time - a slice of the concatenated weight rows and bias, the f16 images into the
+    // staging blocks - and behind every group ONE launch that turns the group's f16 images into its slice of the int8 images and scales
+    const int L = c.n_dec_layers, H = c.n_heads;
+    if (m->enc_i8) WIS_RET(launch_quant_rows(m->st, mem ? mem : m->mem, m->memq, m->memsc, B * T, d));
+    for (int l0 = 0; l0 < L; l0 += m->ckv_G) {
+      const int G = L - l0 < m->ckv_G ? L - l0 : m->ckv_G;
+      const size_t wrow = (size_t)l0 * 2 * d;      // first weight row (= bias element) of the group
+      if (m->enc_i8) WIS_RET(launch_gemm_i8_crosskv(m->st, GemmI8P{m->memq, m->memsc, m->q_ckv_all + wrow * d, m->s_ckv_all + wrow, B * T, G * 2 * d, d}, m->b_ckv_all + wrow,
+                                                    m->kx_stage, m->vx_stage, d, T, m->Tpad, H, (int64_t)m->kx_lstride, (int64_t)m->vx_lstride));
+      else WIS_RET(launch_gemm_crosskv(m->st, gemm_plain(mem ? mem : m->mem, d, m->w_ckv_all + wrow * d, B * T, G * 2 * d, d), m->b_ckv_all + wrow, m->kx_stage, m->vx_stage,
+                                       d, T, m->Tpad, H, (int64_t)m->kx_lstride, (int64_t)m->vx_lstride));
+      WIS_RET(launch_cross_kv_quant(m->st, m->kx_stage, m->vx_stage, B, H, T, m->Tpad, G, (int64_t)m->kx_lstride, (int64_t)m->vx_lstride,
+                                    m->kq_all + (size_t)l0 * m->q8_lstride, m->vq_all + (size_t)l0 * m->q8_lstride, m->sk_all + (size_t)l0 * m->s8_lstride,
+                                    m->sv_all + (size_t)l0 * m->s8_lstride, (int64_t)m->q8_lstride, (int64_t)m->q8_lstride, (int64_t)m->s8_lstride));
+    }
+    return WIS_OK;
+  }
   if (m->enc_i8) {      // the quantised copy is made from the f16 block, the handle's own or the caller's (WIS_IN_ENC_*)
     WIS_RET(launch_quant_rows(m->st, mem ? mem : m->mem, m->memq, m->memsc, B * T, d));
     return launch_gemm_i8_crosskv(m->st, GemmI8P{m->memq, m->memsc, m->q_ckv_all, m->s_ckv_all, B * T, c.n_dec_layers * 2 * d, d}, m->b_ckv_all, m->kx_all, m->vx_all, d, T,
@@ -868,6 +896,13 @@ static void sa_shared_prefix(const wis_model* m, SelfAttnP* sa) {
   if (sa_long_kernel(m)) { sa->plen = m->sa_plen; return; }
   sa->anc = m->d_sa_tab; sa->base = m->d_sa_tab + MAX_ROWS; sa->w0 = m->sa_w0; sa->aw = 1;
 }
+// layer l's cross K / V into the cross-attention's parameters: the f16 images (ku / vu: element offsets of the utterance the rows' b = 0 reads), or on a handle
+// with cross_kv_bits = 8 the int8 images and scales (kx / vt stay null; wis_align, the one caller with an offset, refuses such a handle)
+static void ca_set_kv(const wis_model* m, int l, CrossAttnP* ca, size_t ku = 0, size_t vu = 0) {
+  if (!m->ckv_i8) { ca->kx = m->kx[l] + ku; ca->vt = m->vx[l] + vu; return; }
+  ca->kq8 = m->kq_all + (size_t)l * m->q8_lstride; ca->vq8 = m->vq_all + (size_t)l * m->q8_lstride;
+  ca->sk = m->sk_all + (size_t)l * m->s8_lstride; ca->sv = m->sv_all + (size_t)l * m->s8_lstride;
+}
 static int dec_forward_frag(wis_model* m, int M, int R, int B, bool want_logits, int sstride, int rmul, int chunks, const TreeWin* tw = nullptr) {
   const wis_config_t& c = m->cfg; hipStream_t st = m->st;
   const int d = c.d_model, H = c.n_heads, T = c.n_audio_ctx, ctx = c.n_text_ctx, MB = cdiv(M, 16);
@@ -903,7 +938,7 @@ static int dec_forward_frag(wis_model* m, int M, int R, int B, bool want_logits,
       g3[0].prof = pr ? pr + 32 : nullptr;
       WIS_RET(launch_gemv_frag3(st, g3, 3));
       CrossAttnP cf = ca;      // the batched fold: q = q + q2, statistics from x1's row partials
-      cf.kx = m->kx[l]; cf.vt = m->vx[l]; cf.prof = pr ? pr + 64 : nullptr; cf.xres = m->dstat; cf.qcs = w.cq.csum; cf.qb = w.cq.bias;
+      ca_set_kv(m, l, &cf); cf.prof = pr ? pr + 64 : nullptr; cf.xres = m->dstat; cf.qcs = w.cq.csum; cf.qb = w.cq.bias;
       cf.gran = m->spin_now ? m->ca_gran : nullptr; cf.q2 = m->dq2; cf.xres_is_stat = 1;
       WIS_RET(launch_dec_cross_attn(st, cf));
     } else {
@@ -914,7 +949,7 @@ static int dec_forward_frag(wis_model* m, int M, int R, int B, bool want_logits,
     // (wis_align decodes a batch in groups of utterances: the group's first utterance picks the K / V block the rows' b = 0 reads; 0 otherwise)
     const size_t ku = (size_t)m->al.kv_ub0 * H * T * 64, vu = (size_t)m->al.kv_ub0 * H * 64 * m->Tpad;
     CrossAttnP cp = ca;
-    cp.kx = m->kx[l] + ku; cp.vt = m->vx[l] + vu; cp.gran = (m->spin_now && !tw) ? m->ca_gran : nullptr; cp.kv_shared = (tw && !tw->own_kv) ? 1 : 0;
+    ca_set_kv(m, l, &cp, ku, vu); cp.gran = (m->spin_now && !tw) ? m->ca_gran : nullptr; cp.kv_shared = (tw && !tw->own_kv) ? 1 : 0;
     WIS_RET(launch_dec_cross_attn(st, cp));
     if (m->al.capture) WIS_RET(align_capture_q(m, l, M));      // wis_align: m->dq holds this layer's finished cross-Q until the next layer's QKV projection
     }
@@ -983,7 +1018,7 @@ int dec_forward(wis_model* m, int M, int R, int B, bool want_logits, int sstride
     WIS_RET(launch_gemv(st, g));
     sa.kc = m->kc[l]; sa.vc = m->vc[l]; sa.prof = pr ? pr + 16 : nullptr;
     WIS_RET(launch_dec_self_attn(st, sa));
-    ca.kx = m->kx[l]; ca.vt = m->vx[l]; ca.prof = pr ? pr + 64 : nullptr;
+    ca_set_kv(m, l, &ca); ca.prof = pr ? pr + 64 : nullptr;
     if (fold) {
       GemvP ga, gb;
       out_cq_dual(w, m->dao, m->dxh, m->dx, m->dstat, m->dq, M, &ga, &gb);
@@ -1170,8 +1205,12 @@ int wis_model_create(const wis_config_t* cfg, const void* arena, size_t arena_by
 }
 int wis_model_create_ex(const wis_config_t* cfg, const void* arena, size_t arena_bytes, int arena_on_device,
                         const wis_tensor_t* tensors, int n_tensors, int device, wis_model_t** out, const wis_model_ext_t* ext) {
-  if (ext && (ext->size < (int32_t)sizeof(wis_model_ext_t) || (ext->encoder_weight_bits != 0 && ext->encoder_weight_bits != 8 && ext->encoder_weight_bits != 16))) {
+  // (size-versioned: a caller built against the struct without cross_kv_bits passes size 8 and gets the f16 cross K/V)
+  if (ext && (ext->size < 8 || (ext->encoder_weight_bits != 0 && ext->encoder_weight_bits != 8 && ext->encoder_weight_bits != 16))) {
     set_error("wis_model_create_ex: ext->size %d, encoder_weight_bits %d (0 / 16: f16 encoder, 8: int8 encoder)", ext->size, ext->encoder_weight_bits); return WIS_E_ARG; }
+  const int ckv_bits = (ext && ext->size >= (int32_t)sizeof(wis_model_ext_t)) ? ext->cross_kv_bits : 0;
+  if (ext && ((ext->size > 8 && ext->size < (int32_t)sizeof(wis_model_ext_t)) || (ckv_bits != 0 && ckv_bits != 8 && ckv_bits != 16))) {
+    set_error("wis_model_create_ex: ext->size %d, cross_kv_bits %d (0 / 16: f16 cross K/V, 8: int8 cross K/V)", ext->size, ckv_bits); return WIS_E_ARG; }
   if (!cfg || !arena || !tensors || !out || n_tensors <= 0) { set_error("wis_model_create: bad argument"); return WIS_E_ARG; }
   if (ext && ext->encoder_weight_bits == 8 && cfg->d_model > 1280) {      // (the row quantiser holds a row of 4 d <= 5120 values in registers)
     set_error("wis_model_create_ex: encoder_weight_bits 8 with d_model %d (the int8 encoder serves d_model <= 1280)", cfg->d_model); return WIS_E_UNSUPPORTED; }
@@ -1185,6 +1224,7 @@ int wis_model_create_ex(const wis_config_t* cfg, const void* arena, size_t arena
   m->cfg = *cfg; m->device = device; m->ctx = ctx;
   m->w8 = cfg->decoder_weight_bits == 8;
   m->enc_i8 = ext && ext->encoder_weight_bits == 8;
+  m->ckv_i8 = ckv_bits == 8;
   m->cq_fold = !m->w8 && getenv("WIS_NO_CQFOLD") == nullptr;     // (8-bit weights keep the two-stage form: the fold would change what is quantised)
   m->use_graph = getenv("WIS_NO_GRAPH") == nullptr;
   memset(&m->timing, 0, sizeof(m->timing));
@@ -1260,6 +1300,7 @@ int wis_model_clone(wis_model_t* parent, wis_model_t** out) {
   m->emb = parent->emb; m->dec_pos = parent->dec_pos; m->proj = parent->proj; m->dec_ln_g = parent->dec_ln_g; m->dec_ln_b = parent->dec_ln_b;
   m->bias_all = parent->bias_all; m->bias_begin = parent->bias_begin; m->d_lang_ids = parent->d_lang_ids; m->n_vocab_pad = parent->n_vocab_pad;
   m->w_ckv_all = parent->w_ckv_all; m->b_ckv_all = parent->b_ckv_all;
+  m->ckv_i8 = parent->ckv_i8;
   m->enc_i8 = parent->enc_i8; m->q_ckv_all = parent->q_ckv_all; m->s_ckv_all = parent->s_ckv_all;
   m->w8 = parent->w8; m->cq_fold = parent->cq_fold;
   m->use_graph = parent->use_graph;

@@ -506,6 +506,51 @@ int wis_op_dec_cross_attn_stat(int device, const float* q, const float* q2, cons
   if (stat ? (!qcs || !qb) : (qcs || qb || q2)) { set_error("wis_op_dec_cross_attn_stat: the fold takes partials, column sums and bias together; the plain form none of them"); return WIS_E_ARG; }
   return op_dec_cross_attn(device, q, stat, qcs, qb, kx, vt, out, B, R, H, T, chunks, q2, stat ? 1 : 0, out_mb, kv_shared, no_spin != 0);
 }
+// ---- the int8 cross K/V (tests/test_gpu_cross_q8.py): the quantiser run_cross_kv launches, the attention through launch_dec_cross_attn, a handle's images
+int wis_op_cross_kv_quant(int device, const void* kx_f16, const void* vt_f16, int B, int H, int T, int Tpad, int L, int64_t kx_lstride, int64_t vt_lstride,
+                          void* kq, void* vq, float* sk, float* sv, int64_t kq_lstride, int64_t vq_lstride, int64_t s_lstride) {
+  Tap t(device, "wis_op_cross_kv_quant"); WIS_RET(t.rc);
+  return t.finish(launch_cross_kv_quant(t.st, reinterpret_cast<const f16*>(kx_f16), reinterpret_cast<const f16*>(vt_f16), B, H, T, Tpad, L, kx_lstride, vt_lstride,
+                                        reinterpret_cast<int8_t*>(kq), reinterpret_cast<int8_t*>(vq), sk, sv, kq_lstride, vq_lstride, s_lstride));
+}
+int wis_op_dec_cross_attn_q8(int device, const float* q, const float* q2, const float* stat, const float* qcs, const float* qb,
+                             const void* kq, const void* vq, const float* sk, const float* sv, void* out, int B, int R, int H, int T, int chunks,
+                             int out_mb, int kv_shared) {
+  Tap t(device, "wis_op_dec_cross_attn_q8"); WIS_RET(t.rc);
+  if (!q || !kq || !vq || !sk || !sv || !out || B < 1 || H < 1 || T < 1 || R < 1) { set_error("wis_op_dec_cross_attn_q8: bad argument"); return WIS_E_ARG; }
+  if (stat ? (!qcs || !qb) : (qcs || qb || q2)) { set_error("wis_op_dec_cross_attn_q8: the fold takes partials, column sums and bias together; the plain form none of them"); return WIS_E_ARG; }
+  if (out_mb && out_mb < cdiv(B * R, 16)) { set_error("wis_op_dec_cross_attn_q8: %d row blocks for %d rows", out_mb, B * R); return WIS_E_ARG; }
+  CrossAttnP ca;
+  WIS_RET(t.get(&ca.part, (size_t)B * H * 16 * 16 * 66)); WIS_RET(t.get(&ca.counters, (size_t)B * H, true));
+  if (out_mb) hipMemsetAsync(out, 0, xf_elems(64 * H, out_mb) * 2, t.st);      // the fragment image's rows beyond B * R stay zero
+  ca.q = q; ca.kq8 = reinterpret_cast<const int8_t*>(kq); ca.vq8 = reinterpret_cast<const int8_t*>(vq); ca.sk = sk; ca.sv = sv; ca.out = reinterpret_cast<f16*>(out);
+  ca.B = B; ca.R = R; ca.H = H; ca.d = 64 * H; ca.T = T; ca.Tpad = cdiv(T, 64) * 64; ca.chunks = chunks; ca.out_mb = out_mb; ca.xres = stat; ca.qcs = qcs; ca.qb = qb;
+  ca.q2 = q2; ca.xres_is_stat = stat ? 1 : 0; ca.kv_shared = kv_shared;
+  int rc = WIS_OK;
+  for (int rep = 0; rep < 3 && !rc; ++rep) rc = launch_dec_cross_attn(t.st, ca);      // three launches on one set of tickets: the winner re-arms them
+  return t.finish(rc);
+}
+int wis_debug_cross_kv(wis_model_t* m, int layer, int b, void* kx_f16, void* vt_f16, void* kq, void* vq, float* sk, float* sv, int* is_int8) {
+  if (!m || !is_int8 || layer < 0 || layer >= m->cfg.n_dec_layers || b < 0 || b >= m->cfg.max_batch) { set_error("wis_debug_cross_kv: bad argument"); return WIS_E_ARG; }
+  WIS_ENTER(m, "wis_debug_cross_kv")
+  WIS_HIP_CHECK(hipSetDevice(m->device));
+  *is_int8 = m->ckv_i8 ? 1 : 0;
+  const size_t H = m->cfg.n_heads, T = m->cfg.n_audio_ctx, Tpad = m->Tpad;
+  if (m->ckv_i8) {
+    if (!kq || !vq || !sk || !sv || kx_f16 || vt_f16) { set_error("wis_debug_cross_kv: an int8 handle fills kq, vq, sk and sv"); return WIS_E_ARG; }
+    const size_t qo = layer * m->q8_lstride + b * H * 64 * Tpad, so = layer * m->s8_lstride + b * H * Tpad;
+    WIS_HIP_CHECK(hipMemcpyAsync(kq, m->kq_all + qo, H * 64 * Tpad, hipMemcpyDeviceToHost, m->st));
+    WIS_HIP_CHECK(hipMemcpyAsync(vq, m->vq_all + qo, H * 64 * Tpad, hipMemcpyDeviceToHost, m->st));
+    WIS_HIP_CHECK(hipMemcpyAsync(sk, m->sk_all + so, H * Tpad * 4, hipMemcpyDeviceToHost, m->st));
+    WIS_HIP_CHECK(hipMemcpyAsync(sv, m->sv_all + so, H * Tpad * 4, hipMemcpyDeviceToHost, m->st));
+  } else {
+    if (!kx_f16 || !vt_f16 || kq || vq || sk || sv) { set_error("wis_debug_cross_kv: an f16 handle fills kx_f16 and vt_f16"); return WIS_E_ARG; }
+    WIS_HIP_CHECK(hipMemcpyAsync(kx_f16, m->kx[layer] + b * H * 64 * T, H * 64 * T * 2, hipMemcpyDeviceToHost, m->st));
+    WIS_HIP_CHECK(hipMemcpyAsync(vt_f16, m->vx[layer] + b * H * 64 * Tpad, H * 64 * Tpad * 2, hipMemcpyDeviceToHost, m->st));
+  }
+  WIS_HIP_CHECK(hipStreamSynchronize(m->st));
+  return WIS_OK;
+}
 
 int wis_op_gemv_qkv(int device, const float* x, const float* gamma, const float* beta, const void* W, const float* bias, const int32_t* slot, const int32_t* pos,
                     float* q, void* kc, void* vc, int M, int d, int ctx) {

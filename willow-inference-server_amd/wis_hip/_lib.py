@@ -35,8 +35,8 @@ class Config(C.Structure):
 
 
 class ModelExt(C.Structure):
-    """wis_model_ext_t: wis_model_create_ex's options (encoder_weight_bits 0 / 16: f16 encoder, 8: int8 encoder)"""
-    _fields_ = [("size", C.c_int32), ("encoder_weight_bits", C.c_int32)]
+    """wis_model_ext_t: wis_model_create_ex's options (encoder_weight_bits 0 / 16: f16 encoder, 8: int8 encoder; cross_kv_bits 0 / 16: f16 cross K/V, 8: int8)"""
+    _fields_ = [("size", C.c_int32), ("encoder_weight_bits", C.c_int32), ("cross_kv_bits", C.c_int32)]
 
 
 class Tensor(C.Structure):
@@ -185,6 +185,9 @@ SYMBOLS = [
     ("wis_op_dec_cross_attn", _i, [_i, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i]),
     ("wis_op_dec_cross_attn_folded", _i, [_i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i]),
     ("wis_op_dec_cross_attn_stat", _i, [_i] + [_vp] * 8 + [_i] * 8),
+    ("wis_op_cross_kv_quant", _i, [_i, _vp, _vp] + [_i] * 5 + [_i64] * 2 + [_vp] * 4 + [_i64] * 3),
+    ("wis_op_dec_cross_attn_q8", _i, [_i] + [_vp] * 10 + [_i] * 7),
+    ("wis_debug_cross_kv", _i, [_vp, _i, _i] + [_vp] * 6 + [C.POINTER(C.c_int)]),
     ("wis_op_dec_self_attn_ex", _i, [_i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _i, _i, _vp]),
     ("wis_op_gemv_qkv", _i, [_i] + [_vp] * 10 + [_i] * 3),
     ("wis_op_gemv_out_cq", _i, [_i] + [_vp] * 14 + [_i] * 3),

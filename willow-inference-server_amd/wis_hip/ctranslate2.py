@@ -51,6 +51,7 @@ def _next_seed():
 
 
 ENCODER_COMPUTE_TYPES = ("float16", "int8")      # models.Whisper(encoder_compute_type=...)
+CROSS_KV_COMPUTE_TYPES = ("float16", "int8")     # models.Whisper(cross_kv_compute_type=...)
 
 
 def get_supported_compute_types(device="cuda", device_index=0):
@@ -220,13 +221,13 @@ def make_tensor_index(index):
     return arr
 
 
-def create_handle(a, arena, index, device, max_batch=8, max_beam=5, arena_device_ptr=None, n_vocab=None, encoder_bits=16, **cfgkw):
+def create_handle(a, arena, index, device, max_batch=8, max_beam=5, arena_device_ptr=None, n_vocab=None, encoder_bits=16, cross_kv_bits=16, **cfgkw):
     """arena: uint8 ndarray (host) or None with arena_device_ptr = (ptr, nbytes) already on `device`.
     encoder_bits: 16, or 8 for the int8 encoder (wis_model_create_ex; include/wis_hip.h wis_model_ext_t)."""
     cfg = make_config(a, max_batch, max_beam, n_vocab=n_vocab, **cfgkw)
     tens = make_tensor_index(index)
     h = C.c_void_p()
-    ext = _lib.ModelExt(C.sizeof(_lib.ModelExt), int(encoder_bits))
+    ext = _lib.ModelExt(C.sizeof(_lib.ModelExt), int(encoder_bits), int(cross_kv_bits))      # (cross_kv_bits 8: the int8 cross K/V images)
     if arena_device_ptr is not None:
         p, nbytes = arena_device_ptr
         rc = _lib.load().wis_model_create_ex(C.byref(cfg), C.c_void_p(p), nbytes, 1, tens, len(index), device, C.byref(h), C.byref(ext))
@@ -757,7 +758,8 @@ class Whisper:
     is_multilingual = True
 
     def __init__(self, model_path, device="cuda", device_index=0, compute_type="default", inter_threads=1, intra_threads=0,
-                 max_batch=8, max_beam=5, weights=None, arch=None, replicas_per_device=None, *, encoder_compute_type="float16", **_ignored):
+                 max_batch=8, max_beam=5, weights=None, arch=None, replicas_per_device=None, *, encoder_compute_type="float16", cross_kv_compute_type="float16",
+                 **_ignored):
         if device not in ("cuda", "auto", "hip", "gpu"):
             raise ValueError(f"wis_hip runs on MI355X GPUs only (device={device!r}); there is no CPU path")
         # the ENCODER's linears and the cross K/V projection: "float16", or "int8" (W8A8 on the i8 matrix instruction; include/wis_hip.h
@@ -765,6 +767,10 @@ class Whisper:
         if encoder_compute_type not in ENCODER_COMPUTE_TYPES:
             raise ValueError(f"unsupported encoder_compute_type {encoder_compute_type!r} ({', '.join(ENCODER_COMPUTE_TYPES)})")
         self.encoder_compute_type = encoder_compute_type
+        # the cross-attention K/V images the decode steps read: "float16", or "int8" (one scale per key; include/wis_hip.h wis_model_ext_t cross_kv_bits)
+        if cross_kv_compute_type not in CROSS_KV_COMPUTE_TYPES:
+            raise ValueError(f"unsupported cross_kv_compute_type {cross_kv_compute_type!r} ({', '.join(CROSS_KV_COMPUTE_TYPES)})")
+        self.cross_kv_compute_type = cross_kv_compute_type
         _lib.require_gpu()
         # "float16" (default / "auto") or "int8_float16" (the reference's GPU default, main.py:242): per-row int8 DECODER
         # weights with f16 activations; everything else stays f16
@@ -787,7 +793,7 @@ class Whisper:
         arena, index = W.build_arena(weights)
         kw = dict(suppress_ids=cfg.get("suppress_ids"), suppress_begin=cfg.get("suppress_ids_begin"), lang_ids=cfg.get("lang_ids"),
                   weight_bits=8 if self.compute_type == "int8_float16" else 16, special=self.special,
-                  encoder_bits=8 if encoder_compute_type == "int8" else 16)
+                  encoder_bits=8 if encoder_compute_type == "int8" else 16, cross_kv_bits=8 if cross_kv_compute_type == "int8" else 16)
         enc_shape = (arch["n_audio_ctx"], arch["d_model"])
         self._replicas = [_Replica(h, d, arch["n_mels"], enc_shape) for h, d in zip(create_replicas(arch, arena, index, devs, max_batch, max_beam, **kw), devs)]
         # CTranslate2's `inter_threads` = batches a model runs in parallel (reference main.py:341-355 passes ctranslate2_threads).  Here:
@@ -810,7 +816,7 @@ class Whisper:
         """Wrap replicas that already exist: [(wis_model handle, device), ...] - e.g. models created from a weight arena an
         RCCL broadcast delivered straight into device memory (`create_handle(arena_device_ptr=...)`, wis_hip/dist.py)."""
         self = cls.__new__(cls)
-        self.compute_type = self.encoder_compute_type = "float16"
+        self.compute_type = self.encoder_compute_type = self.cross_kv_compute_type = "float16"
         self.arch, self.decode_config = arch, decode_config or {}
         self.special = special_tokens_for(arch, self.decode_config.get("special"), self.decode_config.get("lang_ids"))
         self._replicas = [_Replica(h, d, arch["n_mels"], (arch["n_audio_ctx"], arch["d_model"])) for h, d in handles]
@@ -1242,6 +1248,8 @@ class Whisper:
         return self._align(None, None, _lib.WIS_IN_MEL_DEV, 1, start_sequence, text_tokens, num_frames, width=median_filter_width, dev=(r, mel_device_ptr))
 
     def _align(self, mel, to_ptr, kind, B, start_sequence, text_tokens, num_frames, *, width, dev=None):
+        if getattr(self, "cross_kv_compute_type", "float16") == "int8":
+            raise UnsupportedOption('align reads the f16 cross K image: not served by a model created with cross_kv_compute_type="int8"')
         if B < 1 or len(text_tokens) != B:
             raise ValueError(f"align: {len(text_tokens)} token lists for a batch of {B}")
         nf = [int(num_frames)] * B if np.isscalar(num_frames) else [int(x) for x in num_frames]

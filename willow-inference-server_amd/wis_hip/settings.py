@@ -138,6 +138,9 @@ class APISettings:
     compute_type: str = "float16"
     # the encoder's linears and the cross K/V projection: "float16", or "int8" (W8A8 GEMMs; off by default, independent of compute_type)
     encoder_compute_type: str = "float16"
+    # the cross-attention K/V every decode step re-reads: "float16", or "int8" (per-key int8 rows: half the per-utterance cross K/V memory and stream; off by
+    # default, independent of the two above; word_timestamps are refused with it)
+    cross_kv_compute_type: str = "float16"
 
     def __post_init__(self):
         env = {k.lower(): v for k, v in os.environ.items()}

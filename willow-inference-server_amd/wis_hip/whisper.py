@@ -268,6 +268,7 @@ class WhisperModels:
                 max_beam = min(max(int(self.settings.max_beam), int(self.settings.beam_size), int(self.settings.long_beam_size)), ctranslate2.MAX_BEAM)
                 self._models[size] = ctranslate2.models.Whisper(path, device="cuda", compute_type=self.settings.compute_type,
                                                                 encoder_compute_type=self.settings.encoder_compute_type,
+                                                                cross_kv_compute_type=self.settings.cross_kv_compute_type,
                                                                 inter_threads=self.settings.ctranslate2_threads,
                                                                 device_index=self.device_index, max_batch=self.settings.max_batch,
                                                                 replicas_per_device=self.settings.replicas_per_gpu, max_beam=max_beam)
@@ -680,6 +681,8 @@ def do_whisper(audio_file, model, beam_size=None, task="transcribe", detect_lang
                 raise ValueError(f"phrases cannot be combined with {what}")
     if q.long_form not in ("chunk", "seek"):
         raise ValueError(f"long_form {q.long_form!r}: seek or chunk")
+    if q.word_timestamps and getattr(s, "cross_kv_compute_type", "float16") == "int8":
+        raise ValueError("word_timestamps need the f16 cross K/V images (setting cross_kv_compute_type is int8: word alignment is not served)")
     timestamps, rep, fixed_new_tokens = q.timestamps, q.rep, q.fixed_new_tokens
     whisper_model = models.get(model)
     special = model_special_tokens(whisper_model)
