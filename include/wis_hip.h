@@ -181,8 +181,9 @@ typedef struct {
  * int32, then the f16 path's epilogue in f32.  Anything else than 0 / 8 / 16: WIS_E_ARG.
  * cross_kv_bits: 0 / 16 = the f16 cross-attention K/V images; 8 = INT8 CROSS K/V: what every decode step re-reads per utterance and decoder layer is kept as
  * int8 values with one f32 scale per (layer, utterance, head, key) and matrix, by THE RULE above: the row is the 64 f16 values of K - and, separately, the 64 of
- * V - that the f16 engine would have stored for that head and key.  The projection still writes f16 (a few layers at a time, into a staging block) and a kernel
- * of its own quantises it; the decode step's cross-attention converts the int8 values to f16 in registers (exact) for the same f16 MFMAs, multiplies the f32
+ * V - that the f16 engine would have stored for that head and key.  The projection (one launch over all decoder layers) rounds its f32 result to f16 and
+ * quantises it in its own epilogue - the bits of the f16 projection followed by wis_op_cross_kv_quant, without an f16 image in memory (f16 encoder with
+ * d_model % 256 == 0 at two or more utterances: those two launches themselves, over an f16 staging block of four layers, which measured faster); the decode step's cross-attention converts the int8 values to f16 in registers (exact) for the same f16 MFMAs, multiplies the f32
  * score by the key's K scale and the f32 softmax weight by the key's V scale before that weight is rounded to f16.  Images of one layer (Tpad = T rounded up
  * to 64; keys [T, Tpad) hold zeros and scale 1):
  *   K   i8 [B][H][4][Tpad][16]   cell (j, t) = K[t][8 j .. 8 j + 7] followed by K[t][32 + 8 j .. 32 + 8 j + 7] of the head
@@ -699,7 +700,7 @@ int wis_op_dec_cross_attn_stat(int device, const float* q, const float* q2, cons
                                const void* kx_f16, const void* vt_f16, void* out_f16, int B, int R, int H, int T, int chunks,
                                int out_mb, int kv_shared, int no_spin);
 /* ---- the int8 cross K/V (wis_model_ext_t::cross_kv_bits has the rule and the layouts; tests/test_gpu_cross_q8.py), device pointers.
- * wis_op_cross_kv_quant: the launch run_cross_kv makes behind every group of layers - f16 images kx [B][H][8][T][8] and vt [B][H][64][Tpad] of L layers (layer
+ * wis_op_cross_kv_quant: the stand-alone quantiser (run_cross_kv's two-launch path, WIS_CKV_FUSED=0 at create; wis_op_enc_crosskv_q8 is the default) - f16 images kx [B][H][8][T][8] and vt [B][H][64][Tpad] of L layers (layer
  * strides kx_lstride / vt_lstride in f16 elements) -> kq / vq (layer strides in bytes, multiples of 16), sk / sv (layer stride in floats).
  * wis_op_dec_cross_attn_q8: wis_op_dec_cross_attn_stat with the int8 images and scales of ONE layer in kx / vt's place (through the same launch function);
  * 256-key chunks always (`chunks` >= 1 is not otherwise read), T <= 1536, no granule hand-off.  Three launches per call on one set of tickets.
@@ -798,6 +799,13 @@ int wis_op_enc_qkv(int device, const void* xn_f16, const void* W_f16, const floa
  * >= T not written): what wis_op_dec_cross_attn reads.  Strides in elements, multiples of 8 and at least the image size; T % 4 != 0: WIS_E_ARG. */
 int wis_op_enc_crosskv(int device, const void* mem_f16, const void* W_f16, const float* bias, void* kx_f16, void* vt_f16, int B, int T, int H, int L,
                        int64_t kx_lstride, int64_t vt_lstride);
+/* the same projection writing the INT8 images (wis_model_ext_t::cross_kv_bits has the rule and the layouts) from its own epilogue - the launch an int8
+ * cross-K/V handle makes once per encoder block.  A [B*T][d] and W [L*2d][d] are f16 when sa and sw are NULL, else int8 with row scales sa f32 [B*T] and
+ * sw f32 [L*2d] (the int8 encoder's operands); bias f32 [L*2d]; d = 64 H, Tpad a multiple of 64 and >= T.  Outputs of all L layers, layer after layer without
+ * gaps: kq i8 [L][B][H][4][Tpad][16], vq i8 [L][B][H][64][Tpad], sk / sv f32 [L][B][H][Tpad]; keys [T, Tpad) are written as zeros with scale 1.  The bits
+ * are those of wis_op_enc_crosskv (or wis_op_gemm_i8 epilogue 4) followed by wis_op_cross_kv_quant. */
+int wis_op_enc_crosskv_q8(int device, const void* A, const float* sa, const void* W, const float* sw, const float* bias, void* kq, void* vq, float* sk, float* sv,
+                          int B, int T, int Tpad, int H, int d, int L);
 /* the encoder's K-split FFN2 with the fused reduction + LayerNorm: X f32 [M][N] (residual in) += A f16 [M][K] . W f16 [N][K]^T + bias, and
  * Y f16 [M][N] = LayerNorm(new X) gamma + beta.  splits = 0: what the encoder takes for N = d at M rows (none: WIS_E_UNSUPPORTED); the fused form
  * exists for 2 and 4 splits and N <= 2048, K % (64 splits) == 0 (otherwise the launch function's error code). */

@@ -115,6 +115,297 @@ int launch_cross_kv_quant(hipStream_t st, const f16* kx, const f16* vt, int B, i
 }
 
 // =======================================================================================
+// The cross-K/V projection that writes the int8 images itself: C = mem [B T][d] . W [L 2d][d]^T over ALL decoder layers in one launch, and an epilogue that
+// sees whole (key, head) rows.  Block 256 = 4 waves as 2 (key halves) x 2 (heads); a workgroup owns 128 keys of ONE utterance x 128 columns = two heads.
+//   Rows go by (utterance, 128-key block), not by flat M: a wave's 64 keys are one 64-key group of the V image; keys >= T read row T - 1 and leave as zeros
+//   with scale 1 (the quantiser's rule), a wave whose 64 keys start at Tpad or beyond has nothing to write.
+//   Columns go by head: head column hc = n / 64 of the concatenated weight rows is (layer hc / 2H, K head hc % 2H < H, else V head hc % 2H - H), so the tile
+//   may straddle K | V or two layers - every wave has ONE head and picks its epilogue by it (wave-uniform).
+// k-loop: gemm_f16_kernel's 128 x 128 form (register staging, two LDS buffers, one barrier per k-tile, two workgroups per CU), byte-addressed: a staged row
+// is 128 bytes of k - 64 f16 or 128 int8 - at a 144-byte pitch (conflict-free ds_read_b128), so one loader serves both operand widths; a k-tile that ends
+// beyond the row (int8, d = 64) is zero filled.  MODE names the accumulator chain:
+//   CQ_F16_32  v_mfma_f32_32x32x16_f16, 16 k per link, links in k order   = gemm_f16_kernel / gemm_pp_kernel
+//   CQ_F16_16  v_mfma_f32_16x16x32_f16, 32 k per link, links in k order   = gemm_8p_kernel
+//   CQ_I8      v_mfma_i32_32x32x32_i8 (exact), then (float)acc * (sa[m] * sw[n])  = gemm_i8_kernel
+// launch_cross_kv_fused takes the f16 chain launch_gemm_crosskv's kernel runs at the shape (gemm_crosskv_chain), so an output is the same f32 sum.
+// Operand order: K waves D[n][m] (weights as MFMA A: a lane holds one key and 4 consecutive head dimensions), V waves D[m][n] (activations as A: a lane
+// holds one head dimension and 4 consecutive keys), so BOTH write 8-byte f16 quads into the orientation their image needs.
+// Epilogue, per wave and without a workgroup barrier (the k-tile buffers are free behind the loop's last barrier; a wave has 9.5 KB of them to itself):
+//   acc (+ scales) + bias in f32 -> f16 -> wave tile [64][72] f16 (144-byte pitch: rows four banks apart; Q8_TP), keys >= T as zeros
+//   K  tile [key][dh]: lane (key 16 i + l15, quarter j) reads its two 8-value cells (2 x ds_read_b128), the key's absmax is an all-reduce over the four lane
+//      rows (q8_xrow_max: permlane32 / permlane16 swaps), the lane writes its own 16-byte cell of kq - cross_kv_quant_kernel's K half, from LDS
+//   V  tile [dh][key] - the transposition happened in the MFMA: lane (key pair, dh half) takes the absmax of 32 head dimensions of two keys (ds_read_b32),
+//      one permlane32 swap joins the halves, the inverse scales go through 64 floats of LDS, and lane (dh, quarter j) quantises the 16 keys of its 16-byte
+//      piece of vq, each with its own scale - cross_kv_quant_kernel's V half
+enum { CQ_F16_32 = 0, CQ_F16_16 = 1, CQ_I8 = 2 };
+typedef int i32x4 __attribute__((ext_vector_type(4)));
+typedef int i32x16 __attribute__((ext_vector_type(16)));
+typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
+constexpr int CQ_RB = 2 * Q8_TP;               // bytes per staged operand row and per epilogue tile row
+constexpr int CQ_BUF = 256 * CQ_RB;            // one k-tile: 128 activation rows, then 128 weight rows
+constexpr int CQ_WAVE = 64 * CQ_RB + 512;      // a wave's epilogue block: the tile, 64 inverse scales, 64 activation row scales
+__device__ __forceinline__ float q8_x32_max(float v) {      // max over the lane pair (l, l + 32)
+  const auto a = __builtin_amdgcn_permlane32_swap(__float_as_uint(v), __float_as_uint(v), false, false);
+  return fmaxf(__uint_as_float(a[0]), __uint_as_float(a[1]));
+}
+__device__ __forceinline__ void cq_put(char* tile, int x, int y, float a, float b, float c, float d) {
+  const f16x4 o = {(f16)a, (f16)b, (f16)c, (f16)d};
+  *reinterpret_cast<f16x4*>(tile + x * CQ_RB + 2 * y) = o;
+}
+template <int MODE>
+__global__ __launch_bounds__(256) void cross_kv_q8_fused_kernel(const char* __restrict__ A, const char* __restrict__ W, int rowbytes, int T, int Tpad, int H, int nkb, int nmt,
+                                                                int nnt, const float* __restrict__ sa, const float* __restrict__ sw, const float* __restrict__ bias,
+                                                                int8_t* __restrict__ kq, int8_t* __restrict__ vq, float* __restrict__ sk, float* __restrict__ sv,
+                                                                int64_t q_ls, int64_t s_ls) {
+  constexpr bool I8 = MODE == CQ_I8;
+  __shared__ __attribute__((aligned(16))) char smem[2 * CQ_BUF];
+  const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int wm = wave >> 1, wn = wave & 1, l31 = lane & 31, hi = lane >> 5, l15 = lane & 15, kq4 = lane >> 4;
+  // XCD-aware regrouping of the workgroup id, then m-fastest tile coordinates (gemm_f16_kernel)
+  const int nwg = nmt * nnt;
+  int wg;
+  {
+    const int orig = blockIdx.x, xcd = orig & 7, q = nwg >> 3, r = nwg & 7;
+    wg = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (orig >> 3);
+  }
+  const int mt = wg % nmt, nt = wg / nmt;
+  const int b = mt / nkb, t0 = (mt - b * nkb) * 128, n0 = nt * 128;
+  const int hc = 2 * nt + wn, lyr = hc / (2 * H), hw = hc - lyr * 2 * H;
+  const bool isV = hw >= H;
+  const int h = isV ? hw - H : hw;
+
+  // loader: 16-byte chunk c -> row c >> 3, byte offset (c & 7) * 16; rows lrow + 32 i.  Keys >= T read key T - 1 (their results leave as zeros)
+  const int lrow = tid >> 3, lkc = (tid & 7) * 16;
+  auto arow = [&](int i) -> const char* {
+    int t = t0 + lrow + 32 * i; if (t > T - 1) t = T - 1;
+    return A + ((int64_t)b * T + t) * rowbytes;
+  };
+  const char* ga0 = arow(0); const char* ga1 = arow(1); const char* ga2 = arow(2); const char* ga3 = arow(3);
+  const char* gw0 = W + (int64_t)(n0 + lrow) * rowbytes;
+  const int64_t wrp = (int64_t)32 * rowbytes;
+  const int soff = lrow * CQ_RB + lkc;
+  uint4 ra0, ra1, ra2, ra3, rw0, rw1, rw2, rw3;
+  const uint4 z4 = make_uint4(0u, 0u, 0u, 0u);
+#define WIS_CQ_GLOAD(kt) {                                                                                                          \
+    int ko = (kt) * 128 + lkc; const bool past = ko >= rowbytes; if (past) ko = 0;                                                  \
+    ra0 = *reinterpret_cast<const uint4*>(ga0 + ko); ra1 = *reinterpret_cast<const uint4*>(ga1 + ko);                               \
+    ra2 = *reinterpret_cast<const uint4*>(ga2 + ko); ra3 = *reinterpret_cast<const uint4*>(ga3 + ko);                               \
+    rw0 = *reinterpret_cast<const uint4*>(gw0 + ko); rw1 = *reinterpret_cast<const uint4*>(gw0 + wrp + ko);                         \
+    rw2 = *reinterpret_cast<const uint4*>(gw0 + 2 * wrp + ko); rw3 = *reinterpret_cast<const uint4*>(gw0 + 3 * wrp + ko);           \
+    if (past) { ra0 = z4; ra1 = z4; ra2 = z4; ra3 = z4; rw0 = z4; rw1 = z4; rw2 = z4; rw3 = z4; } }
+#define WIS_CQ_SSTORE(buf) {                                                                                                        \
+    char* sa_ = smem + (buf) * CQ_BUF + soff; char* sw_ = sa_ + 128 * CQ_RB;                                                        \
+    *reinterpret_cast<uint4*>(sa_) = ra0; *reinterpret_cast<uint4*>(sa_ + 32 * CQ_RB) = ra1;                                        \
+    *reinterpret_cast<uint4*>(sa_ + 64 * CQ_RB) = ra2; *reinterpret_cast<uint4*>(sa_ + 96 * CQ_RB) = ra3;                           \
+    *reinterpret_cast<uint4*>(sw_) = rw0; *reinterpret_cast<uint4*>(sw_ + 32 * CQ_RB) = rw1;                                        \
+    *reinterpret_cast<uint4*>(sw_ + 64 * CQ_RB) = rw2; *reinterpret_cast<uint4*>(sw_ + 96 * CQ_RB) = rw3; }
+
+  f32x16 accf[2][2]; i32x16 acci[2][2]; f32x4 acc4[4][4];      // [block of p rows][block of q rows]; one of the three per MODE
+#pragma unroll
+  for (int a = 0; a < 2; ++a)
+#pragma unroll
+    for (int c = 0; c < 2; ++c)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) { accf[a][c][r] = 0.f; acci[a][c][r] = 0; }
+#pragma unroll
+  for (int a = 0; a < 4; ++a)
+#pragma unroll
+    for (int c = 0; c < 4; ++c) acc4[a][c] = f32x4{0.f, 0.f, 0.f, 0.f};
+
+  const int nk = (rowbytes + 127) / 128;
+  WIS_CQ_GLOAD(0) WIS_CQ_SSTORE(0)
+  __syncthreads();
+  for (int kt = 0; kt < nk; ++kt) {
+    const int cur = kt & 1;
+    if (kt + 1 < nk) WIS_CQ_GLOAD(kt + 1)
+    // first MFMA operand p (its rows become the quads a lane holds), second operand q (its rows become the lane's own index): K waves p = weights,
+    // q = activations; V waves the other way round - a choice of two LDS base addresses, the loop is the same
+    const char* sAb = smem + cur * CQ_BUF + wm * 64 * CQ_RB;
+    const char* sWb = smem + cur * CQ_BUF + (128 + wn * 64) * CQ_RB;
+    const char* pB = isV ? sAb : sWb;
+    const char* qB = isV ? sWb : sAb;
+    if constexpr (MODE == CQ_F16_16) {
+#pragma unroll
+      for (int kb = 0; kb < 2; ++kb) {      // lane (l15, quarter) feeds k 32 kb + 8 quarter .. + 7 of its row to both operands
+        f16x8 pf[4], qf[4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+          pf[i] = *reinterpret_cast<const f16x8*>(pB + (16 * i + l15) * CQ_RB + kb * 64 + kq4 * 16);
+          qf[i] = *reinterpret_cast<const f16x8*>(qB + (16 * i + l15) * CQ_RB + kb * 64 + kq4 * 16);
+        }
+#pragma unroll
+        for (int pi = 0; pi < 4; ++pi)
+#pragma unroll
+          for (int qi = 0; qi < 4; ++qi) acc4[pi][qi] = __builtin_amdgcn_mfma_f32_16x16x32_f16(pf[pi], qf[qi], acc4[pi][qi], 0, 0, 0);
+      }
+    } else {
+#pragma unroll
+      for (int kk = 0; kk < 4; ++kk) {      // lane (l31, hi) feeds bytes 32 kk + 16 hi .. + 15 of its row to both operands
+        u32x4 pr[2], qr[2];
+#pragma unroll
+        for (int i = 0; i < 2; ++i) {
+          pr[i] = *reinterpret_cast<const u32x4*>(pB + (32 * i + l31) * CQ_RB + kk * 32 + hi * 16);
+          qr[i] = *reinterpret_cast<const u32x4*>(qB + (32 * i + l31) * CQ_RB + kk * 32 + hi * 16);
+        }
+#pragma unroll
+        for (int pi = 0; pi < 2; ++pi)
+#pragma unroll
+          for (int qi = 0; qi < 2; ++qi) {
+            if constexpr (I8) acci[pi][qi] = __builtin_amdgcn_mfma_i32_32x32x32_i8(__builtin_bit_cast(i32x4, pr[pi]), __builtin_bit_cast(i32x4, qr[qi]), acci[pi][qi], 0, 0, 0);
+            else accf[pi][qi] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, pr[pi]), __builtin_bit_cast(f16x8, qr[qi]), accf[pi][qi], 0, 0, 0);
+          }
+      }
+    }
+    if (kt + 1 < nk) WIS_CQ_SSTORE(cur ^ 1)
+    __syncthreads();
+  }
+#undef WIS_CQ_GLOAD
+#undef WIS_CQ_SSTORE
+
+  // ---- epilogue: wave-private from here on (no barrier below this line)
+  const int t0w = t0 + 64 * wm;
+  if (t0w >= Tpad) return;
+  const int ncol = n0 + 64 * wn;      // the wave's first column: bias / weight-scale index
+  char* tile = smem + wave * CQ_WAVE;
+  float* sinv = reinterpret_cast<float*>(tile + 64 * CQ_RB);
+  float* ssa = sinv + 64;
+  if constexpr (I8) {
+    int t = t0w + lane; if (t > T - 1) t = T - 1;
+    ssa[lane] = sa[(int64_t)b * T + t];
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+  }
+  // x = the index a lane holds ONE of (K waves: key, V waves: head dimension), y = the index it holds quads of; tile [x][y]
+  constexpr int NX = MODE == CQ_F16_16 ? 4 : 2, XB = 64 / NX, NQ = MODE == CQ_F16_16 ? 1 : 4;
+  const int xl = MODE == CQ_F16_16 ? l15 : l31, yl = MODE == CQ_F16_16 ? 4 * kq4 : 4 * hi;
+  auto accv = [&](int yb, int xb, int r) -> float {      // block (quads, lane index) = (p, q)
+    if constexpr (MODE == CQ_F16_16) return acc4[yb][xb][r];
+    else if constexpr (I8) return (float)acci[yb][xb][r];
+    else return accf[yb][xb][r];
+  };
+  if (!isV) {
+#pragma unroll
+    for (int mi = 0; mi < NX; ++mi) {
+      const int x = XB * mi + xl;
+      const bool dead = t0w + x >= T;
+      const float sam = I8 ? ssa[x] : 0.f;
+#pragma unroll
+      for (int ni = 0; ni < NX; ++ni)
+#pragma unroll
+        for (int r4 = 0; r4 < NQ; ++r4) {
+          const int y = XB * ni + 8 * r4 + yl;
+          const float4 bq = *reinterpret_cast<const float4*>(bias + ncol + y);
+          float4 sq = make_float4(0.f, 0.f, 0.f, 0.f);
+          if constexpr (I8) sq = *reinterpret_cast<const float4*>(sw + ncol + y);
+          float v0, v1, v2, v3;
+          if constexpr (I8) {
+            v0 = accv(ni, mi, 4 * r4) * (sam * sq.x) + bq.x; v1 = accv(ni, mi, 4 * r4 + 1) * (sam * sq.y) + bq.y;
+            v2 = accv(ni, mi, 4 * r4 + 2) * (sam * sq.z) + bq.z; v3 = accv(ni, mi, 4 * r4 + 3) * (sam * sq.w) + bq.w;
+          } else {
+            v0 = accv(ni, mi, 4 * r4) + bq.x; v1 = accv(ni, mi, 4 * r4 + 1) + bq.y; v2 = accv(ni, mi, 4 * r4 + 2) + bq.z; v3 = accv(ni, mi, 4 * r4 + 3) + bq.w;
+          }
+          if (dead) { v0 = 0.f; v1 = 0.f; v2 = 0.f; v3 = 0.f; }
+          cq_put(tile, x, y, v0, v1, v2, v3);
+        }
+    }
+  } else {
+#pragma unroll
+    for (int ni = 0; ni < NX; ++ni) {
+      const int x = XB * ni + xl;
+      const float bv = bias[ncol + x];
+      const float swv = I8 ? sw[ncol + x] : 0.f;
+#pragma unroll
+      for (int mi = 0; mi < NX; ++mi)
+#pragma unroll
+        for (int r4 = 0; r4 < NQ; ++r4) {
+          const int y = XB * mi + 8 * r4 + yl;
+          float v0, v1, v2, v3;
+          if constexpr (I8) {
+            const float4 s4 = *reinterpret_cast<const float4*>(ssa + y);
+            v0 = accv(mi, ni, 4 * r4) * (s4.x * swv) + bv; v1 = accv(mi, ni, 4 * r4 + 1) * (s4.y * swv) + bv;
+            v2 = accv(mi, ni, 4 * r4 + 2) * (s4.z * swv) + bv; v3 = accv(mi, ni, 4 * r4 + 3) * (s4.w * swv) + bv;
+          } else {
+            v0 = accv(mi, ni, 4 * r4) + bv; v1 = accv(mi, ni, 4 * r4 + 1) + bv; v2 = accv(mi, ni, 4 * r4 + 2) + bv; v3 = accv(mi, ni, 4 * r4 + 3) + bv;
+          }
+          const int tk = t0w + y;
+          if (tk >= T) v0 = 0.f;
+          if (tk + 1 >= T) v1 = 0.f;
+          if (tk + 2 >= T) v2 = 0.f;
+          if (tk + 3 >= T) v3 = 0.f;
+          cq_put(tile, x, y, v0, v1, v2, v3);
+        }
+    }
+  }
+  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");      // wave-private tile: the wave's own LDS writes have landed
+  const size_t bh = (size_t)b * H + h;
+  if (!isV) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const int key = 16 * i + l15, t = t0w + key;
+      const f16x8 ka = *reinterpret_cast<const f16x8*>(tile + key * CQ_RB + 16 * kq4), kc = *reinterpret_cast<const f16x8*>(tile + key * CQ_RB + 64 + 16 * kq4);
+      float mx = 0.f;
+#pragma unroll
+      for (int e = 0; e < 8; ++e) mx = fmaxf(mx, fmaxf(fabsf((float)ka[e]), fabsf((float)kc[e])));
+      mx = q8_xrow_max(mx);
+      const float sc = mx > 0.f ? mx / 127.0f : 1.0f, inv = 1.0f / sc;
+      const u32x4 o = {q8_pack4(ka[0], ka[1], ka[2], ka[3], inv, inv, inv, inv), q8_pack4(ka[4], ka[5], ka[6], ka[7], inv, inv, inv, inv),
+                       q8_pack4(kc[0], kc[1], kc[2], kc[3], inv, inv, inv, inv), q8_pack4(kc[4], kc[5], kc[6], kc[7], inv, inv, inv, inv)};
+      *reinterpret_cast<u32x4*>(kq + lyr * q_ls + ((bh * 4 + kq4) * Tpad + t) * 16) = o;      // t < Tpad: t0w < Tpad, both multiples of 64
+      if (kq4 == 0) sk[lyr * s_ls + bh * Tpad + t] = sc;
+    }
+    return;
+  }
+  {
+    const int kp = lane & 31;      // keys 2 kp, 2 kp + 1; head dimensions 32 hi .. + 31
+    float m0 = 0.f, m1 = 0.f;
+#pragma unroll
+    for (int i = 0; i < 32; ++i) {
+      const f16x2 v = *reinterpret_cast<const f16x2*>(tile + (32 * hi + i) * CQ_RB + 4 * kp);
+      m0 = fmaxf(m0, fabsf((float)v[0])); m1 = fmaxf(m1, fabsf((float)v[1]));
+    }
+    m0 = q8_x32_max(m0); m1 = q8_x32_max(m1);
+    const float s0 = m0 > 0.f ? m0 / 127.0f : 1.0f, s1 = m1 > 0.f ? m1 / 127.0f : 1.0f;
+    if (hi == 0) {
+      *reinterpret_cast<float2*>(sinv + 2 * kp) = make_float2(1.0f / s0, 1.0f / s1);
+      *reinterpret_cast<float2*>(sv + lyr * s_ls + bh * Tpad + t0w + 2 * kp) = make_float2(s0, s1);
+    }
+  }
+  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const int pc = lane + 64 * i, dh = pc >> 2, jj = pc & 3;      // output piece: keys 8 jj .. + 7 and 32 + 8 jj .. + 7 of the group
+    const f16x8 a = *reinterpret_cast<const f16x8*>(tile + dh * CQ_RB + 16 * jj), c = *reinterpret_cast<const f16x8*>(tile + dh * CQ_RB + 64 + 16 * jj);
+    const float4 ia0 = *reinterpret_cast<const float4*>(sinv + 8 * jj), ia1 = *reinterpret_cast<const float4*>(sinv + 8 * jj + 4);
+    const float4 ic0 = *reinterpret_cast<const float4*>(sinv + 32 + 8 * jj), ic1 = *reinterpret_cast<const float4*>(sinv + 36 + 8 * jj);
+    const u32x4 o = {q8_pack4(a[0], a[1], a[2], a[3], ia0.x, ia0.y, ia0.z, ia0.w), q8_pack4(a[4], a[5], a[6], a[7], ia1.x, ia1.y, ia1.z, ia1.w),
+                     q8_pack4(c[0], c[1], c[2], c[3], ic0.x, ic0.y, ic0.z, ic0.w), q8_pack4(c[4], c[5], c[6], c[7], ic1.x, ic1.y, ic1.z, ic1.w)};
+    *reinterpret_cast<u32x4*>(vq + lyr * q_ls + (bh * 64 + dh) * Tpad + t0w + 16 * jj) = o;
+  }
+}
+
+int launch_cross_kv_fused(hipStream_t st, const CrossKvQ8P& p) {
+  const bool i8 = p.sa != nullptr;
+  if (!p.A || !p.W || !p.bias || !p.kq || !p.vq || !p.sk || !p.sv || (p.sa == nullptr) != (p.sw == nullptr) || p.B < 1 || p.T < 1 || p.H < 1 || p.L < 1 || p.d != 64 * p.H ||
+      p.Tpad < p.T || p.Tpad % 64) {
+    set_error("cross_kv_fused: B=%d T=%d Tpad=%d H=%d d=%d L=%d unsupported (d = 64 H, Tpad %% 64, Tpad >= T; int8 operands bring both scale vectors)", p.B, p.T, p.Tpad, p.H,
+              p.d, p.L); return WIS_E_ARG; }
+  const int64_t img = (int64_t)p.B * p.H * 64 * p.Tpad;
+  if (p.q_ls % 16 || p.s_ls % 2 || p.q_ls < img || p.s_ls < (int64_t)p.B * p.H * p.Tpad) {
+    set_error("cross_kv_fused: layer strides %lld / %lld too short or misaligned", (long long)p.q_ls, (long long)p.s_ls); return WIS_E_ARG; }
+  const int nkb = cdiv(p.Tpad, 128), nmt = p.B * nkb, nnt = p.L * p.H;      // (L 2 d / 128 column tiles)
+  if ((int64_t)nmt * nnt > 0x7fffffff || (int64_t)p.B * p.T * p.d > 0x7fffffff) { set_error("cross_kv_fused: B=%d T=%d d=%d L=%d too large", p.B, p.T, p.d, p.L); return WIS_E_ARG; }
+  const dim3 grid(nmt * nnt);
+  const char* A = reinterpret_cast<const char*>(p.A); const char* W = reinterpret_cast<const char*>(p.W);
+#define WIS_CQ_LAUNCH(MODE, RB) hipLaunchKernelGGL((cross_kv_q8_fused_kernel<MODE>), grid, dim3(256), 0, st, A, W, RB, p.T, p.Tpad, p.H, nkb, nmt, nnt, p.sa, p.sw, p.bias, \
+                                                   p.kq, p.vq, p.sk, p.sv, p.q_ls, p.s_ls)
+  if (i8) WIS_CQ_LAUNCH(CQ_I8, p.d);
+  else if (p.chain == 16) WIS_CQ_LAUNCH(CQ_F16_16, 2 * p.d);
+  else if (p.chain == 32) WIS_CQ_LAUNCH(CQ_F16_32, 2 * p.d);
+  else { set_error("cross_kv_fused: f16 operands need the accumulator chain of the shape (16 or 32), got %d", p.chain); return WIS_E_ARG; }
+#undef WIS_CQ_LAUNCH
+  return WIS_OK;
+}
+
+// =======================================================================================
 // Cross-attention of the R (<= 16) query rows of one utterance over a chunk of 256 keys of the int8 images.  grid (chunks, H, B), block 256 = 4 waves.
 //
 // What the f16 kernels showed: a workgroup of this family is bound by how fast the CU's address path takes its wave requests, not by

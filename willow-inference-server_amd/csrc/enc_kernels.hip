@@ -1309,6 +1309,21 @@ int launch_gemm_crosskv(hipStream_t st, const GemmP& p, const float* bias, f16* 
   EpiCrossKV e{bias, kx, vt, d, T, Tpad, H, kx_lstride, vt_lstride};
   return launch_gemm_t(st, p, e);
 }
+// launch_gemm_t's path for EpiCrossKV at this shape, restated for the kernel that has to repeat its sums (cross_q8.hip cross_kv_q8_fused_kernel): the
+// 8-phase kernel takes the 256 x 256 tile when both column sets are 256-aligned (launch_gemm_8p) and there are two k-tiles; everything else is a
+// 32 x 32 x 16 kernel
+int gemm_crosskv_chain(const GemmP& p, int d) {
+  static const bool use_8p = !(getenv("WIS_GEMM_8P") && atoi(getenv("WIS_GEMM_8P")) == 0);
+  int bm, bn; gemm_pick_tile(p, &bm, &bn);
+  const bool p8 = bm == 256 && bn == 256 && use_8p && (p.klen > 0 ? p.klen : p.K) / BK >= 2 && (p.N / 2) % 256 == 0 && d % 256 == 0;
+  return p8 ? 16 : 32;
+}
+int launch_gemm_crosskv_q8(hipStream_t st, const CrossKvQ8P& p0) {
+  CrossKvQ8P p = p0;
+  if (!p.sa && p.A && p.W && p.B > 0 && p.T > 0 && p.d > 0 && p.L > 0)
+    p.chain = gemm_crosskv_chain(gemm_plain(reinterpret_cast<const f16*>(p.A), p.d, reinterpret_cast<const f16*>(p.W), p.B * p.T, p.L * 2 * p.d, p.d), p.d);
+  return launch_cross_kv_fused(st, p);
+}
 
 // =======================================================================================
 // The int8 encoder (encoder_weight_bits = 8): W8A8 GEMMs on gfx950's i8 matrix instruction, and the two kernels that make their A operand.

@@ -185,6 +185,20 @@ int launch_dec_cross_attn_q8(hipStream_t st, const CrossAttnP& p);      // (laun
 // 64-value row per (layer, utterance, head, key) and matrix: kq i8 [B][H][4][Tpad][16], vq i8 [B][H][64][Tpad] (strides in bytes), sk / sv f32 [B][H][Tpad]
 int launch_cross_kv_quant(hipStream_t st, const f16* kx, const f16* vt, int B, int H, int T, int Tpad, int L, int64_t kx_ls, int64_t vt_ls,
                           int8_t* kq, int8_t* vq, float* sk, float* sv, int64_t kq_ls, int64_t vq_ls, int64_t s_ls);
+// the cross K/V projection of ALL L decoder layers that writes those int8 images and scales itself (cross_kv_q8_fused_kernel): A [B T][d] and W [L 2d][d] as
+// f16 (sa = sw = null) or as int8 with row scales sa [B T] and sw [L 2d]; bias f32 [L 2d]; q_ls in bytes (multiple of 16), s_ls in floats (even).
+// The bits are those of launch_gemm_crosskv / launch_gemm_i8_crosskv followed by launch_cross_kv_quant.
+struct CrossKvQ8P {
+  const void* A; const float* sa; const void* W; const float* sw; const float* bias;
+  int8_t *kq, *vq; float *sk, *sv;
+  int B, T, Tpad, H, d, L; int64_t q_ls, s_ls;
+  int chain = 0;      // f16 operands: 16 or 32, gemm_crosskv_chain's answer (launch_gemm_crosskv_q8 fills it in)
+};
+int launch_cross_kv_fused(hipStream_t st, const CrossKvQ8P& p);      // (cross_q8.hip: the kernel's launch, chain given)
+// which accumulator chain launch_gemm_crosskv's kernel runs at this shape: 16 = gemm_8p_kernel (v_mfma_f32_16x16x32_f16, 32 k per link), 32 = the
+// register-staged and ping-pong tiles (v_mfma_f32_32x32x16_f16, 16 k per link).  The fused kernel follows it, link for link.
+int gemm_crosskv_chain(const GemmP& p, int d);
+int launch_gemm_crosskv_q8(hipStream_t st, const CrossKvQ8P& p);     // what run_cross_kv and the tap call: the chain of the shape, then launch_cross_kv_fused
 
 // sampling: per-(row, chunk) masked max / sum-exp / top-2k of the logits
 struct SampleCfg {

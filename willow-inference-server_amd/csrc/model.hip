@@ -470,6 +470,16 @@ void frag_set_ksplit(GemvP& g, int ks, float* part, unsigned* cnt) {
   if (ks > 1) { g.ksplit = ks; g.kpart = part; g.kcnt = cnt; }
 }
 
+// int8 cross K/V: does run_cross_kv take the two-launch path (f16 staging + cross_kv_quant_kernel) at B utterances?  The fused kernel serves every
+// shape with the same bits; it is the slower one where the f16 projection runs the 8-phase 256 x 256 kernel (gemm_crosskv_chain 16: d % 256 == 0 and
+// 150 tiles) on two or more utterances - large-v2, f16 encoder: 0.87 vs 0.78 ms at two, 3.60 vs 3.13 ms at eight (profiles/cross_kv_int8_ab.md) - and the
+// faster one everywhere else that was measured: one utterance (0.46 vs 0.67 ms) and the int8 encoder at every batch size.
+static bool ckv_two_launch(const wis_model* m, int B) {
+  if (!m->ckv_fused) return true;
+  if (m->enc_i8 || B < 2) return false;
+  const int d = m->cfg.d_model;
+  return gemm_crosskv_chain(gemm_plain(nullptr, d, nullptr, B * m->cfg.n_audio_ctx, m->cfg.n_dec_layers * 2 * d, d), d) == 16;
+}
 static int alloc_buffers(wis_model* m) {
   const wis_config_t& c = m->cfg;
   const int d = c.d_model, H = c.n_heads, Bm = c.max_batch, T = c.n_audio_ctx, L = c.n_dec_layers;
@@ -508,12 +518,16 @@ static int alloc_buffers(wis_model* m) {
   WIS_RET(dalloc(m, &m->kc_all, m->kv_layer_stride * L));
   WIS_RET(dalloc(m, &m->vc_all, m->kv_layer_stride * L));
   m->kx_lstride = (size_t)Bm * H * 8 * T * 8; m->vx_lstride = (size_t)Bm * H * 64 * m->Tpad;
-  if (m->ckv_i8) {      // f16 staging for ckv_G layers, the int8 images and scales for all of them (run_cross_kv)
-    m->ckv_G = L < 4 ? L : 4;
+  if (m->ckv_i8) {      // the int8 images and scales of all layers; f16 staging for ckv_G layers only where the two-launch path runs (run_cross_kv)
     m->q8_lstride = (size_t)Bm * H * 64 * m->Tpad; m->s8_lstride = (size_t)Bm * H * m->Tpad;
-    WIS_RET(dalloc(m, &m->kx_stage, m->kx_lstride * m->ckv_G));
-    WIS_RET(dalloc(m, &m->vx_stage, m->vx_lstride * m->ckv_G));
-    WIS_HIP_CHECK(hipMemsetAsync(m->vx_stage, 0, m->vx_lstride * m->ckv_G * 2, m->st));
+    bool staged = false;
+    for (int b = 1; b <= Bm; ++b) staged = staged || ckv_two_launch(m, b);
+    if (staged) {
+      m->ckv_G = L < 4 ? L : 4;
+      WIS_RET(dalloc(m, &m->kx_stage, m->kx_lstride * m->ckv_G));
+      WIS_RET(dalloc(m, &m->vx_stage, m->vx_lstride * m->ckv_G));
+      WIS_HIP_CHECK(hipMemsetAsync(m->vx_stage, 0, m->vx_lstride * m->ckv_G * 2, m->st));
+    }
     WIS_RET(dalloc(m, &m->kq_all, m->q8_lstride * L)); WIS_RET(dalloc(m, &m->vq_all, m->q8_lstride * L));
     WIS_RET(dalloc(m, &m->sk_all, m->s8_lstride * L)); WIS_RET(dalloc(m, &m->sv_all, m->s8_lstride * L));
   } else {
@@ -701,10 +715,16 @@ int run_cross_kv(wis_model* m, int B, const f16* mem) {
   const wis_config_t& c = m->cfg;
   const int d = c.d_model, T = c.n_audio_ctx;
   if (m->ckv_i8) {
-    // int8 cross K/V: the same projection, ckv_G decoder layers at a time - a slice of the concatenated weight rows and bias, the f16 images into the
-    // staging blocks - and behind every group ONE launch that turns the group's f16 images into its slice of the int8 images and scales
     const int L = c.n_dec_layers, H = c.n_heads;
     if (m->enc_i8) WIS_RET(launch_quant_rows(m->st, mem ? mem : m->mem, m->memq, m->memsc, B * T, d));
+    if (!ckv_two_launch(m, B)) {      // int8 cross K/V: ONE launch over all layers; the projection's epilogue applies the rule and writes the images and scales
+      CrossKvQ8P p{mem ? mem : m->mem, nullptr, m->w_ckv_all, nullptr, m->b_ckv_all, m->kq_all, m->vq_all, m->sk_all, m->sv_all, B, T, m->Tpad, H, d, L,
+                   (int64_t)m->q8_lstride, (int64_t)m->s8_lstride};
+      if (m->enc_i8) { p.A = m->memq; p.sa = m->memsc; p.W = m->q_ckv_all; p.sw = m->s_ckv_all; }
+      return launch_gemm_crosskv_q8(m->st, p);
+    }
+    // the two-launch path: the same projection, ckv_G decoder layers at a time - a slice of the concatenated weight rows and bias, the f16 images into the
+    // staging blocks - and behind every group ONE launch that turns the group's f16 images into its slice of the int8 images and scales
     for (int l0 = 0; l0 < L; l0 += m->ckv_G) {
       const int G = L - l0 < m->ckv_G ? L - l0 : m->ckv_G;
       const size_t wrow = (size_t)l0 * 2 * d;      // first weight row (= bias element) of the group
@@ -1225,6 +1245,7 @@ int wis_model_create_ex(const wis_config_t* cfg, const void* arena, size_t arena
   m->w8 = cfg->decoder_weight_bits == 8;
   m->enc_i8 = ext && ext->encoder_weight_bits == 8;
   m->ckv_i8 = ckv_bits == 8;
+  m->ckv_fused = m->ckv_i8 && !(getenv("WIS_CKV_FUSED") && atoi(getenv("WIS_CKV_FUSED")) == 0);
   m->cq_fold = !m->w8 && getenv("WIS_NO_CQFOLD") == nullptr;     // (8-bit weights keep the two-stage form: the fold would change what is quantised)
   m->use_graph = getenv("WIS_NO_GRAPH") == nullptr;
   memset(&m->timing, 0, sizeof(m->timing));
@@ -1300,7 +1321,7 @@ int wis_model_clone(wis_model_t* parent, wis_model_t** out) {
   m->emb = parent->emb; m->dec_pos = parent->dec_pos; m->proj = parent->proj; m->dec_ln_g = parent->dec_ln_g; m->dec_ln_b = parent->dec_ln_b;
   m->bias_all = parent->bias_all; m->bias_begin = parent->bias_begin; m->d_lang_ids = parent->d_lang_ids; m->n_vocab_pad = parent->n_vocab_pad;
   m->w_ckv_all = parent->w_ckv_all; m->b_ckv_all = parent->b_ckv_all;
-  m->ckv_i8 = parent->ckv_i8;
+  m->ckv_i8 = parent->ckv_i8; m->ckv_fused = parent->ckv_fused;
   m->enc_i8 = parent->enc_i8; m->q_ckv_all = parent->q_ckv_all; m->s_ckv_all = parent->s_ckv_all;
   m->w8 = parent->w8; m->cq_fold = parent->cq_fold;
   m->use_graph = parent->use_graph;

@@ -147,9 +147,11 @@ struct wis_model {
   bool enc_i8 = false;
   int8_t *q_ckv_all = nullptr, *aq = nullptr, *memq = nullptr; float *s_ckv_all = nullptr, *asc = nullptr, *memsc = nullptr;
   // int8 cross K/V (wis_model_create_ex, cross_kv_bits = 8; cross_q8.hip has the layouts): all layers' int8 images and per-key scales in one block each; kx_all /
-  // vx_all stay null, kx / vx hold null pointers, and the projection writes ckv_G layers at a time into the f16 staging blocks kx_stage / vx_stage
-  // (kx_lstride / vx_lstride are THEIR layer strides), which cross_kv_quant_kernel turns into the group's slice of the images
-  bool ckv_i8 = false; int ckv_G = 0;
+  // vx_all stay null, kx / vx hold null pointers.  ckv_fused (the default): one launch of cross_kv_q8_fused_kernel writes the images from the projection's
+  // epilogue wherever that is the faster path (model.hip ckv_two_launch: all but two or more utterances on the 8-phase GEMM's shapes), and nothing is staged
+  // on a handle none of whose batch sizes takes the other path.  That other path, and WIS_CKV_FUSED=0 at create (A/B switch; clones inherit): the projection writes ckv_G layers at a time into the f16 staging
+  // blocks kx_stage / vx_stage (kx_lstride / vx_lstride are THEIR layer strides), which cross_kv_quant_kernel turns into the group's slice of the images
+  bool ckv_i8 = false, ckv_fused = false; int ckv_G = 0;
   wis::f16 *kx_stage = nullptr, *vx_stage = nullptr;
   int8_t *kq_all = nullptr, *vq_all = nullptr; float *sk_all = nullptr, *sv_all = nullptr;
   size_t q8_lstride = 0, s8_lstride = 0;      // layer strides of the int8 images (bytes) and of the scale streams (floats)

@@ -717,6 +717,13 @@ int wis_op_enc_crosskv(int device, const void* mem_f16, const void* W_f16, const
   return t.finish(launch_gemm_crosskv(t.st, gemm_plain(reinterpret_cast<const f16*>(mem_f16), d, reinterpret_cast<const f16*>(W_f16), B * T, L * 2 * d, d), bias,
                                       reinterpret_cast<f16*>(kx_f16), reinterpret_cast<f16*>(vt_f16), d, T, Tpad, H, kx_lstride, vt_lstride));
 }
+int wis_op_enc_crosskv_q8(int device, const void* A, const float* sa, const void* W, const float* sw, const float* bias, void* kq, void* vq, float* sk, float* sv,
+                          int B, int T, int Tpad, int H, int d, int L) {
+  Tap t(device, "wis_op_enc_crosskv_q8"); WIS_RET(t.rc);
+  if (!A || !W || !bias || !kq || !vq || !sk || !sv || B < 1 || T < 1 || H < 1 || L < 1 || (int64_t)L * 2 * 64 * H > 0x7fffffff) { set_error("wis_op_enc_crosskv_q8: bad argument"); return WIS_E_ARG; }
+  CrossKvQ8P p{A, sa, W, sw, bias, reinterpret_cast<int8_t*>(kq), reinterpret_cast<int8_t*>(vq), sk, sv, B, T, Tpad, H, d, L, (int64_t)B * H * 64 * Tpad, (int64_t)B * H * Tpad};
+  return t.finish(launch_gemm_crosskv_q8(t.st, p));
+}
 int wis_op_gemm_splitk_ln(int device, const void* A_f16, const void* W_f16, const float* bias, float* X, const float* gamma, const float* beta, void* Y_f16,
                           int M, int N, int K, int splits) {
   Tap t(device, "wis_op_gemm_splitk_ln"); WIS_RET(t.rc);

@@ -200,6 +200,7 @@ SYMBOLS = [
     ("wis_op_enc_conv", _i, [_i, _i, _vp, _vp, _i, _vp, _vp, _vp, _i, _i, _i, _i]),
     ("wis_op_enc_qkv", _i, [_i] + [_vp] * 5 + [_i] * 3),
     ("wis_op_enc_crosskv", _i, [_i] + [_vp] * 5 + [_i] * 4 + [_i64] * 2),
+    ("wis_op_enc_crosskv_q8", _i, [_i] + [_vp] * 9 + [_i] * 6),
     ("wis_op_gemm_splitk_ln", _i, [_i] + [_vp] * 7 + [_i] * 4),
     ("wis_op_quant_rows", _i, [_i, _vp, _vp, _vp, _i, _i]),
     ("wis_op_layernorm_quant", _i, [_i] + [_vp] * 6 + [_i] * 2),
