@@ -596,9 +596,11 @@ typedef struct {
 int wis_last_timing(const wis_model_t* m, wis_timing_t* t);
 
 /* ---- tuning tap: shader-clock stamps of the phases of decoder layer 0's kernels for one decode forward at
- * text position `pos` (out: [6][16] uint64: QKV gemv, out-proj gemv, cross-attn, self-attn, FFN1 gemv, FFN2 gemv; more than 8 rows: the
+ * text position `pos` (out: [8][16] uint64: QKV gemv, out-proj gemv, cross-attn, self-attn, FFN1 gemv, FFN2 gemv; more than 8 rows: the
  * batched-row kernels, the fourth row is the cross-attention output projection; the cross-attention row carries two stamp sets, entries 0-5 and 7-13:
- * the first K wave and the first V wave of workgroup (0, 0, 0)) */
+ * the first K wave and the first V wave of workgroup (0, 0, 0).  Row 6: the cross-attention output projection at any row count.  Row 7: the
+ * cross-attention's combiner workgroup (last chunk, head 0, utterance 0; granule form only) - entries 0-5 its first V wave: entry, V requested, own P.V
+ * done, own partial in LDS (barrier passed), every granule of its items seen, out stored; entry 6 its first K wave arriving at that barrier) */
 int wis_debug_phase_cycles(wis_model_t* m, int B, int beam, int pos, uint64_t* out);
 /* ... and, behind such a call at <= 8 rows with the cross-Q fold on, the stamps of the fused out-projection + cross-Q launch's OTHER arm (the folded
  * cross-Q, workgroup 0 of its side of the grid) -> out[16]; the out-proj row above is the out-projection arm */

@@ -28,7 +28,8 @@ ALG_B1 = {r"gemv_kernel<1, 2, 40, .* (20480|40960)": 8 * D * D,    # FFN2: every
           r"gemv_dual_kernel<10, 20> 40960": 6 * D * D,            # out-projection + the folded cross-Q
           r"gemv_kernel<1, 1, 20, .* 414976": 2 * 51872 * D,       # vocabulary projection (two-tile workgroups)
           r"dec_cross_attn_kernel 30720": 2 * 2 * 1500 * D,
-          r"dec_cross_attn_rs_kernel 30720": 2 * 2 * 1500 * D}       # round 6: the role-split form (K waves / V waves)
+          r"dec_cross_attn_rs_kernel 30720": 2 * 2 * 1500 * D,       # round 6: the role-split form (K waves / V waves)
+          r"dec_cross_attn_b1_kernel 30720": 2 * 2 * 1500 * D}       # ... on a kernel of its own at d = 1280 (the one-utterance step)
 ALG_B8 = {"gemv_frag_kernel<3, 8, false> 40960": 8 * D * D,      # FFN2: two K slices per n-tile (grid.y = 2)
           "gemv_frag_kernel<3, 10, false> 81920": 8 * D * D, "gemv_frag_kernel<3, 10, false> 61440": 6 * D * D,
           "gemv_frag_kernel<3, 10, false> 20480": 2 * D * D, "gemv_frag_kernel<3, 10, false> 829952": 2 * 51872 * D, "dec_cross_attn_kernel 245760": 8 * 2 * 2 * 1500 * D,

@@ -17,7 +17,7 @@ a = W.arch(size)
 w = W.synthetic_weights(size)
 arena, index = W.build_arena(w)
 h = ct2.create_handle(a, arena, index, 0, max_batch=B, max_beam=5)
-out = np.zeros((6, 16), np.uint64)
+out = np.zeros((8, 16), np.uint64)      # rows 6, 7: the cross-attention output projection, the cross-attention's combiner workgroup
 names = ["gemv QKV (LN)", "gemv out-proj", "cross-attn", "self-attn", "gemv FFN1 (LN)", "gemv FFN2"]
 if B * 5 > 8:      # the batched-row kernels (round 6): gemv_frag_kernel<3, 10> QKV, gemv_frag3_kernel (out-projection + the two q halves), -, gemv_frag_kernel d x d,
     # gemv_frag2_kernel (FFN1, two n-tiles per workgroup), gemv_frag_kernel<3, 8> with two K slices (FFN2)
@@ -48,6 +48,21 @@ for pos in (10,):
                 for name, c in zip(PH, ph):
                     print(f"| {name} | {c} | {100.0 * c / max(1, st[-1] - st[0]):.0f} % |")
                 print(f"| total | {st[-1] - st[0]} | |\n")
+    st = [int(v) for v in out[6][:7] if v]
+    if st:
+        print(f"{'gemv cross-out':16s} pos {pos}: total {st[-1] - st[0]:6d} cyc; phases {[st[j + 1] - st[j] for j in range(len(st) - 1)]}")
+    cb = [int(v) for v in out[7][:7]]
+    if all(cb[:6]):      # the combiner of head 0 (last chunk's workgroup, granule form): its first V wave; entry 6: its first K wave reaching the combiner's barrier
+        names_c = ["V requested", "own P.V done", "own partial in LDS (barrier)", "last granule seen", "out stored"]
+        print(f"{'cross-attn combiner':16s} pos {pos}: total {cb[5] - cb[0]:6d} cyc; phases {[cb[j + 1] - cb[j] for j in range(5)]}"
+              )      # (no start offset against workgroup (0, 0, 0): the two run on different CUs, whose s_memtime counters have different origins)
+        print(f"{'':16s} own partial ready -> last granule seen {cb[4] - cb[2]:6d} cyc; -> out stored {cb[5] - cb[2]:6d} cyc"
+              + (f"; its K wave waits {cb[3] - cb[6]:d} cyc at the barrier" if cb[6] else ""))
+        if md:
+            print("\n| cross-attn combiner, first V wave: phase | s_memtime ticks |\n|---|---|")
+            for name, c in zip(names_c, [cb[j + 1] - cb[j] for j in range(5)]):
+                print(f"| {name} | {c} |")
+            print(f"| total | {cb[5] - cb[0]} |\n")
     if B * 5 <= 8:      # the fused out-projection + cross-Q launch: "gemv out-proj" above is its out-projection arm, this its folded cross-Q arm (both workgroup 0 of their side)
         arm = np.zeros(16, np.uint64)
         _lib.check(lib.wis_debug_phase_cycles_cq_arm(h, arm.ctypes.data_as(C.POINTER(C.c_uint64))))

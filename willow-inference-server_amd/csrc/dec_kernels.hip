@@ -2385,6 +2385,7 @@ __global__ __launch_bounds__(256) void dec_cross_attn_kernel(const float* __rest
 // The K waves never wait for a V wave (no workgroup barrier between the first one and the tail), so scores and softmax run while V is
 // still streaming in.  Arithmetic: P and O are dec_cross_attn_kernel's bit for bit (exponentials about the chunk's maximum, P.V steps in key
 // order); the row sum is added in another order (last-bit differences); partial format, combine and its order are the same.
+// (dec_cross_attn_b1_kernel below is a written-out COPY of the <true, true, 2> instantiation for d = 1280: a fix to the arithmetic here belongs there too.)
 // NT: K / V fragments by non-temporal loads - small grids only (every fragment is read once by one workgroup; measured -0.4 % of the one-utterance
 // step, +1.6 % of the step at 8 utterances: session r6D)
 #define WIS_CA_LD(p) (NT ? __builtin_nontemporal_load(p) : *(p))
@@ -2440,6 +2441,12 @@ __global__ __launch_bounds__(128 * NKW) void dec_cross_attn_rs_kernel(const floa
   const int rq = l15 < R ? l15 : R - 1;
   // (tap builds: workgroup (0, 0, 0): its first K wave stamps entries 0-5 of the row, its first V wave entries 7-13)
   unsigned long long* pf = (c == 0 && h == 0 && b == 0 && lane == 0 && prof) ? (wave == 0 ? prof : (wave == NKW ? prof + 7 : nullptr)) : nullptr;
+#if WIS_TAPS
+  // (tap builds, one-utterance grids: the COMBINER of head 0, workgroup (C - 1, 0, 0), the one that ends the launch - its first V wave stamps entries 7-12 of the
+  // NEXT stamp row, the cross-attention output projection's, whose own stamps end at entry 6, and its first K wave entry 13 there, in front of the combiner's barrier)
+  unsigned long long* pfc = (SPIN && NT && C > 1 && c == C - 1 && h == 0 && b == 0 && lane == 0 && prof) ? prof + 16 + 7 : nullptr;
+  if (wave == NKW) stamp(pfc, 0);
+#endif
   if (tid == 0) tl_begin(prof);
   stamp(pf, 0);
   unsigned ep_now = 0;
@@ -2570,6 +2577,9 @@ __global__ __launch_bounds__(128 * NKW) void dec_cross_attn_rs_kernel(const floa
         for (int s4 = 0; s4 < VS; ++s4) vf[blk][VS * j + s4] = WIS_CA_LD(reinterpret_cast<const u32x4*>(vb + (size_t)blk * 16 * Tpad + 32 * (VS * j + s4)));
     __builtin_amdgcn_sched_barrier(0);
     stamp(pf, 1);
+#if WIS_TAPS
+    if (wave == NKW) stamp(pfc, 1);
+#endif
     f32x4 oacc[NB];
 #pragma unroll
     for (int blk = 0; blk < NB; ++blk) oacc[blk] = (f32x4){0.f, 0.f, 0.f, 0.f};
@@ -2593,6 +2603,9 @@ __global__ __launch_bounds__(128 * NKW) void dec_cross_attn_rs_kernel(const floa
 #pragma unroll
       for (int r4 = 0; r4 < 4; ++r4) o_[blk][r4] = oacc[blk][r4];
     stamp(pf, 4);
+#if WIS_TAPS
+    if (wave == NKW) stamp(pfc, 2);
+#endif
   }
 
   // ---- the chunk's partial: (O[64], M, L) per row, published / combined as in dec_cross_attn_kernel (V wave kw owns dh 16 NB kw .. 16 NB (kw + 1) - 1)
@@ -2630,8 +2643,14 @@ __global__ __launch_bounds__(128 * NKW) void dec_cross_attn_rs_kernel(const floa
         for (int r4 = 0; r4 < 4; ++r4) own[l15][dhb + 16 * blk + r4] = o_[blk][r4];
       if (wave == NKW && kq == 0) { own[l15][64] = Mc; own[l15][65] = Lc; }
     }
+#if WIS_TAPS
+    if (wave == 0) stamp(pfc, 6);
+#endif
     __syncthreads();
     stamp(pf, 5);
+#if WIS_TAPS
+    if (wave == NKW) stamp(pfc, 3);
+#endif
     for (int item = tid; item < R * 32; item += NTHR) {
       const int r = item >> 5, dp = item & 31;
       float2 ml[CM], ov[CM];
@@ -2652,6 +2671,9 @@ __global__ __launch_bounds__(128 * NKW) void dec_cross_attn_rs_kernel(const floa
         if (++spins > CA_SPIN_LIMIT) { atomicOr(epoch, 1u); break; }
         __builtin_amdgcn_s_sleep(1);
       }
+#if WIS_TAPS
+      if (wave == NKW) stamp(pfc, 4);      // (the wave's one pass at <= 8 rows: every granule of its items seen)
+#endif
       float M_ = own[r][64];
 #pragma unroll
       for (int cc = 0; cc < CM - 1; ++cc) if (cc < C - 1) M_ = fmaxf(M_, ml[cc].x);
@@ -2674,6 +2696,9 @@ __global__ __launch_bounds__(128 * NKW) void dec_cross_attn_rs_kernel(const floa
     }
     if (tid == 0) __hip_atomic_store(epoch + 1 + b * H + h, tag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     stamp(pf, 6);
+#if WIS_TAPS
+    if (wave == NKW) stamp(pfc, 5);
+#endif
     if (tid == 0) tl_end(prof);
     return;
   }
@@ -2732,6 +2757,271 @@ __global__ __launch_bounds__(128 * NKW) void dec_cross_attn_rs_kernel(const floa
   stamp(pf, 6);
 }
 
+// The one-utterance decode step's launch at d = 1280 on a kernel of its own (profiles/cross_attn_b1_ab.md): dec_cross_attn_rs_kernel<true, true, 2> written out
+// - granule form, non-temporal K / V, 2 + 2 waves, 2 .. 6 chunks, at most one workgroup per CU; no one-chunk form, no ticket form - with what the assembly of that
+// instantiation showed taken out: the combiner asks for the granules of all its chunk slots at once.  Arithmetic, partial format, granule protocol and combine
+// order are dec_cross_attn_rs_kernel's, and so is every output word (tests/test_gpu_cross_attn_b1.py).
+// The first 14 argument dwords are what the K waves' requests need - they arrive preloaded in SGPRs, where the rs kernel fetched TpadF and then qcs / qb from
+// two lines of the kernarg segment, one round trip behind the other, in front of its first K request.
+__global__ __launch_bounds__(256) void dec_cross_attn_b1_kernel(const float* __restrict__ q, const f16* __restrict__ kx, const float* __restrict__ xres,
+                                                              const float* __restrict__ q2, const float* __restrict__ qcs, const float* __restrict__ qb,
+                                                              int RHCC, int dT, const f16* __restrict__ vt, int Tpad, unsigned* epoch, f16* __restrict__ out,
+                                                              unsigned long long* prof, int out_mb, gran_t* gran) {
+  constexpr bool NT = true; constexpr int NKW = 2;
+  constexpr int CM = 6, SQP = 68, NPT = 10, KT = 16 / NKW, KEYS = 256 / NKW, NB = 4 / NKW, VS = 8 / NKW, NTHR = 128 * NKW;      // key tiles / keys per K wave, 16-dh blocks / 32-key steps per flag per V wave
+  // (CM: <= 6 chunks; SQP: staged operand pitch; NPT: row partials per lane, 8 lanes per row, d <= 1280)
+  const int R = RHCC & 0x7F, H = (RHCC >> 8) & 0x3F, C = (RHCC >> 24) & 0xFF, d = dT & 0xFFFF, T = (dT >> 16) & 0xFFFF;
+  __shared__ __attribute__((aligned(16))) f16 sp16[16 * CA_PSTR];
+  __shared__ __attribute__((aligned(16))) float sq[NKW][10 * SQP];      // per K wave: rows 0..7 q_raw (both halves added), 8 column sums, 9 bias
+  __shared__ float srow[NKW][8][2];
+  __shared__ float sml[NKW][16][2];                                    // (chunk max, sum) of the K waves' parts
+  __shared__ float own[16][66];                                        // the combiner's own partial
+  __shared__ float smaxw[NKW][16];                                       // the K waves' row maxima (exchanged behind flagm)
+  __shared__ int flag[NKW], flagm[NKW];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, l15 = lane & 15, kq = lane >> 4;
+  const int c = blockIdx.x, h = blockIdx.y, b = blockIdx.z;
+  const int bkv = ((RHCC >> 7) & 1) ? 0 : b;      // (kv_shared rides in bit 7 of RHCC: the K waves' requests take nothing from behind the preloaded arguments)
+  const int klo = c * 256, n = (klo + 256 <= T) ? 256 : T - klo;
+  const bool kwave = wave < NKW; const int kw = wave & (NKW - 1);
+  const int rq = l15 < R ? l15 : R - 1;
+  // (tap builds: workgroup (0, 0, 0): its first K wave stamps entries 0-5 of the row, its first V wave entries 7-13)
+  unsigned long long* pf = (c == 0 && h == 0 && b == 0 && lane == 0 && prof) ? (wave == 0 ? prof : (wave == NKW ? prof + 7 : nullptr)) : nullptr;
+  // (the COMBINER of head 0, workgroup (C - 1, 0, 0), the one that ends the launch - its first V wave stamps entries 7-12 of the
+  // NEXT stamp row, the cross-attention output projection's, whose own stamps end at entry 6, and its first K wave entry 13 there, in front of the combiner's barrier)
+  unsigned long long* pfc = (WIS_TAPS && c == C - 1 && h == 0 && b == 0 && lane == 0 && prof) ? prof + 16 + 7 : nullptr;
+  if (tid == 0) tl_begin(prof);
+  stamp(pf, 0);
+  if (wave == NKW) stamp(pfc, 0);
+  unsigned ep_now = 0;      // (`epoch` lies behind the preloaded arguments: a wave asks for its head's word where it has time - below)
+  float o_[NB][4]; float Mc = 0.f, Lc = 0.f;      // V waves: the chunk's partial (NB 16-dh blocks of lane column r = l15)
+#pragma unroll
+  for (int i = 0; i < NB; ++i)
+#pragma unroll
+    for (int r4 = 0; r4 < 4; ++r4) o_[i][r4] = 0.f;
+
+  if (kwave) {
+    // ---- requests: the query's operands (one 16-byte piece per lane and array), the row partials (lane = (row, eighth)), the K fragments
+    float4 stq[2], stq2[2];
+#pragma unroll
+    for (int u = 0; u < 2; ++u) {
+      const int sr0 = (lane >> 4) + 4 * u, sr = sr0 < R ? sr0 : R - 1;
+      const size_t so = (size_t)(b * R + sr) * d + h * 64 + 4 * (lane & 15);
+      stq[u] = *reinterpret_cast<const float4*>(q + so);
+      stq2[u] = make_float4(0.f, 0.f, 0.f, 0.f);
+      if (q2) stq2[u] = *reinterpret_cast<const float4*>(q2 + so);      // (uniform)
+    }
+    const float4 stc = *reinterpret_cast<const float4*>(((lane & 16) ? qb : qcs) + h * 64 + 4 * (lane & 15));
+    const int ntile = d >> 4, l8 = lane & 7, prow = (lane >> 3) < R ? (lane >> 3) : R - 1;
+    const float2* sp = reinterpret_cast<const float2*>(xres) + (size_t)(b * R + prow) * ntile;
+    float2 pt[NPT];
+#pragma unroll
+    for (int i = 0; i < NPT; ++i) { const int t = l8 + 8 * i; pt[i] = sp[t < ntile ? t : ntile - 1]; }
+    const f16* kb = kx + (size_t)(bkv * H + h) * 8 * T * 8;
+    u32x4 kf[KT][2];
+#pragma unroll
+    for (int i = 0; i < KT; ++i) {
+      int key = klo + KEYS * kw + 16 * i + l15; if (key > T - 1) key = T - 1;      // clamped; masked below
+#pragma unroll
+      for (int ks = 0; ks < 2; ++ks) kf[i][ks] = WIS_CA_LD(reinterpret_cast<const u32x4*>(kb + ((size_t)(kq + 4 * ks) * T + key) * 8));
+    }
+    __builtin_amdgcn_sched_barrier(0);
+    asm volatile("s_barrier" ::: "memory");      // the K requests are in: the V waves may ask for theirs (raw: no wait for any load)
+    __builtin_amdgcn_sched_barrier(0);           // (and nothing that waits for a load moves above it: hipcc had hoisted the first statistics' wait)
+    stamp(pf, 1);
+    // ---- LayerNorm statistics of the R rows (Chan merge of the per-16-column (sum, M2) pairs about the first tile's mean), in every K wave
+    const float c0 = __shfl(pt[0].x, lane & ~7) * 0.0625f;
+    float a1 = 0.f, a2 = 0.f;
+#pragma unroll
+    for (int i = 0; i < NPT; ++i) {
+      const bool in = l8 + 8 * i < ntile;
+      const float dm = in ? pt[i].x * 0.0625f - c0 : 0.f;
+      a1 += dm; a2 += in ? pt[i].y + 16.0f * dm * dm : 0.f;
+    }
+    a1 += dpp_f<0xB1>(a1); a2 += dpp_f<0xB1>(a2);
+    a1 += dpp_f<0x4E>(a1); a2 += dpp_f<0x4E>(a2);
+    a1 += dpp_f<0x141>(a1); a2 += dpp_f<0x141>(a2);      // the 8 lanes of a row hold its sums
+    float* sqw = sq[kw];
+    if (l8 == 0) {
+      const float invd = 1.0f / (float)d, dmu = a1 * 16.0f * invd;
+      srow[kw][lane >> 3][0] = c0 + dmu; srow[kw][lane >> 3][1] = 1.0f / sqrtf(fmaxf(a2 * invd - dmu * dmu, 0.f) + 1e-5f);
+    }
+#pragma unroll
+    for (int u = 0; u < 2; ++u)
+      *reinterpret_cast<float4*>(&sqw[((lane >> 4) + 4 * u) * SQP + 4 * (lane & 15)]) = make_float4(stq[u].x + stq2[u].x, stq[u].y + stq2[u].y, stq[u].z + stq2[u].z, stq[u].w + stq2[u].w);
+    if (lane < 32) *reinterpret_cast<float4*>(&sqw[(8 + (lane >> 4)) * SQP + 4 * (lane & 15)]) = stc;
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");      // wave-private staging: the wave's own LDS writes have landed
+    const float mu = srow[kw][rq][0], rs = srow[kw][rq][1];
+    const float* sqr = &sqw[rq * SQP + 8 * kq]; const float* scs = &sqw[8 * SQP + 8 * kq]; const float* sbq = &sqw[9 * SQP + 8 * kq];
+    f16x8 qf0, qf1;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      qf0[e] = (f16)(rs * (sqr[e] - mu * scs[e]) + sbq[e]);
+      qf1[e] = (f16)(rs * (sqr[32 + e] - mu * scs[32 + e]) + sbq[32 + e]);
+    }
+    stamp(pf, 2);
+    // ---- scores of this wave's KEYS keys: D[key][r], lane holds r = l15 and keys 16 i + 4 kq + reg; maximum and sums across the four lane rows
+    f32x4 acc[KT];
+    float lmax = -INFINITY;
+#pragma unroll
+    for (int i = 0; i < KT; ++i) {
+      f32x4 a = {0.f, 0.f, 0.f, 0.f};
+      a = __builtin_amdgcn_mfma_f32_16x16x32_f16(*reinterpret_cast<const f16x8*>(&kf[i][0]), qf0, a, 0, 0, 0);
+      a = __builtin_amdgcn_mfma_f32_16x16x32_f16(*reinterpret_cast<const f16x8*>(&kf[i][1]), qf1, a, 0, 0, 0);
+#pragma unroll
+      for (int r4 = 0; r4 < 4; ++r4) {
+        const int kl = KEYS * kw + 16 * i + 4 * kq + r4;
+        a[r4] = (kl < n) ? a[r4] : -INFINITY;
+        lmax = fmaxf(lmax, a[r4]);
+      }
+      acc[i] = a;
+    }
+    stamp(pf, 3);
+    lmax = xrow_max(lmax);
+    // the chunk's maximum = the larger of the two K waves' (the exponentials are taken about the CHUNK's maximum, as dec_cross_attn_kernel takes them:
+    // P and O come out bit for bit as there, only the row sum is added in another order): the one exchange between the two K waves, through LDS
+    // behind a flag word each - no workgroup barrier, the V waves are not involved
+    if (kq == 0) smaxw[kw][l15] = lmax;
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    if (lane == 0) __hip_atomic_store(&flagm[kw], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+#pragma unroll
+    for (int w = 0; w < NKW; ++w)
+      while (__hip_atomic_load(&flagm[w], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) == 0) __builtin_amdgcn_s_sleep(1);
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    float mref = smaxw[0][l15];                               // finite: the chunk holds a key
+#pragma unroll
+    for (int w = 1; w < NKW; ++w) mref = fmaxf(mref, smaxw[w][l15]);
+    float lsum = 0.f;
+#pragma unroll
+    for (int i = 0; i < KT; ++i) {
+      f16x4 ph;
+#pragma unroll
+      for (int r4 = 0; r4 < 4; ++r4) { const float e = __expf(acc[i][r4] - mref); lsum += e; ph[r4] = (f16)e; }
+      *reinterpret_cast<f16x4*>(&sp16[l15 * CA_PSTR + KEYS * kw + 16 * i + 4 * kq]) = ph;
+    }
+    lsum = xrow_sum(lsum);
+    if (kq == 0) { sml[kw][l15][0] = mref; sml[kw][l15][1] = lsum; }
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    if (lane == 0) __hip_atomic_store(&flag[kw], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+    stamp(pf, 4);
+    ep_now = __hip_atomic_load(epoch + 1 + b * H + h, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);      // (its work done; only the combiner's K waves use it)
+  } else {
+    ep_now = __hip_atomic_load(epoch + 1 + b * H + h, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);      // (while it waits for the K waves' requests)
+    if (lane < 2 * NKW && wave == NKW) __hip_atomic_store(lane < NKW ? &flag[lane] : &flagm[lane - NKW], 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+    __builtin_amdgcn_sched_barrier(0);
+    stamp(pf, 0);
+    // ---- V^T fragments of this wave's 16 NB head dimensions, in key order (the first K wave's keys first)
+    const f16* vb = vt + ((size_t)(bkv * H + h) * 64 + 16 * NB * kw + l15) * Tpad + klo + 8 * kq;
+    u32x4 vf[NB][8];
+#pragma unroll
+    for (int j = 0; j < NKW; ++j)
+#pragma unroll
+      for (int blk = 0; blk < NB; ++blk)
+#pragma unroll
+        for (int s4 = 0; s4 < VS; ++s4) vf[blk][VS * j + s4] = WIS_CA_LD(reinterpret_cast<const u32x4*>(vb + (size_t)blk * 16 * Tpad + 32 * (VS * j + s4)));
+    __builtin_amdgcn_sched_barrier(0);
+    stamp(pf, 1);
+    if (wave == NKW) stamp(pfc, 1);
+    f32x4 oacc[NB];
+#pragma unroll
+    for (int blk = 0; blk < NB; ++blk) oacc[blk] = (f32x4){0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int j = 0; j < NKW; ++j) {      // the 32-key steps in key order, as dec_cross_attn_kernel accumulates them; K wave j's keys as soon as its P is there
+      while (__hip_atomic_load(&flag[j], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) == 0) __builtin_amdgcn_s_sleep(1);
+      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+#pragma unroll
+      for (int s4 = 0; s4 < VS; ++s4) {
+        const f16x8 pb = *reinterpret_cast<const f16x8*>(&sp16[rq * CA_PSTR + 32 * (VS * j + s4) + 8 * kq]);
+#pragma unroll
+        for (int blk = 0; blk < NB; ++blk) oacc[blk] = __builtin_amdgcn_mfma_f32_16x16x32_f16(*reinterpret_cast<const f16x8*>(&vf[blk][VS * j + s4]), pb, oacc[blk], 0, 0, 0);
+      }
+      if (j == 0 || j == NKW - 1) stamp(pf, j == 0 ? 2 : 3);
+    }
+    Mc = sml[0][rq][0];
+    Lc = sml[0][rq][1] + sml[1][rq][1];
+#pragma unroll
+    for (int blk = 0; blk < NB; ++blk)
+#pragma unroll
+      for (int r4 = 0; r4 < 4; ++r4) o_[blk][r4] = oacc[blk][r4];
+    stamp(pf, 4);
+    if (wave == NKW) stamp(pfc, 2);
+  }
+
+  // ---- the chunk's partial: (O[64], M, L) per row, published / combined as in dec_cross_attn_kernel (V wave kw owns dh 16 NB kw .. 16 NB (kw + 1) - 1)
+  const int dhb = 16 * NB * kw + 4 * kq;      // + 16 blk
+  const bool pub = !kwave && l15 < R;
+  const unsigned tag = ep_now + 1u;
+  gran_t* gbase = gran + (size_t)(b * H + h) * 6 * 8 * 66;
+  if (c != C - 1) {
+    if (pub) {
+      gran_t* gp = gbase + ((size_t)c * 8 + l15) * 66;
+#pragma unroll
+      for (int blk = 0; blk < NB; ++blk) { st_gran2(gp + dhb + 16 * blk, tag, o_[blk][0], o_[blk][1]); st_gran2(gp + dhb + 16 * blk + 2, tag, o_[blk][2], o_[blk][3]); }
+      if (wave == NKW && kq == 0) st_gran2(gp + 64, tag, Mc, Lc);
+    }
+    stamp(pf, 5);
+    if (tid == 0) tl_end(prof);
+    return;
+  }
+  if (pub) {
+#pragma unroll
+    for (int blk = 0; blk < NB; ++blk)
+#pragma unroll
+      for (int r4 = 0; r4 < 4; ++r4) own[l15][dhb + 16 * blk + r4] = o_[blk][r4];
+    if (wave == NKW && kq == 0) { own[l15][64] = Mc; own[l15][65] = Lc; }
+  }
+  if (wave == 0) stamp(pfc, 6);
+  __syncthreads();
+  stamp(pf, 5);
+  if (wave == NKW) stamp(pfc, 3);
+  for (int item = tid; item < R * 32; item += NTHR) {
+    const int r = item >> 5, dp = item & 31;
+    float2 ml[CM], ov[CM];
+    unsigned spins = 0;
+    for (;;) {
+      bool ok = true;
+#pragma unroll
+      for (int cc = 0; cc < CM - 1; ++cc) {
+        // every chunk slot's four granules asked for at once: a slot this head does not use reads chunk 0's granules again - they count like chunk 0's in `ok`,
+        // which asks nothing new, and nowhere else.  (Guarded by `cc < C - 1`, hipcc gives each slot a branch and a vmcnt(0) of its own: up to five memory
+        // round trips one behind the other in every sweep.)
+        const gran_t* gp = gbase + ((size_t)(cc < C - 1 ? cc : 0) * 8 + r) * 66;
+        const gran_t g0 = ld_gran(gp + 64), g1 = ld_gran(gp + 65), g2 = ld_gran(gp + 2 * dp), g3 = ld_gran(gp + 2 * dp + 1);
+        ok = ok & ((unsigned)(g0 >> 32) == tag) & ((unsigned)(g1 >> 32) == tag) & ((unsigned)(g2 >> 32) == tag) & ((unsigned)(g3 >> 32) == tag);
+        ml[cc] = make_float2(__uint_as_float((unsigned)g0), __uint_as_float((unsigned)g1));
+        ov[cc] = make_float2(__uint_as_float((unsigned)g2), __uint_as_float((unsigned)g3));
+      }
+      if (ok) break;
+      if (++spins > CA_SPIN_LIMIT) { atomicOr(epoch, 1u); break; }
+      __builtin_amdgcn_s_sleep(1);
+    }
+    if (wave == NKW) stamp(pfc, 4);      // (the wave's one pass: every granule of its items seen)
+    float M_ = own[r][64];
+#pragma unroll
+    for (int cc = 0; cc < CM - 1; ++cc) if (cc < C - 1) M_ = fmaxf(M_, ml[cc].x);
+    float L = 0.f, O0 = 0.f, O1 = 0.f;
+#pragma unroll
+    for (int cc = 0; cc < CM - 1; ++cc) {
+      if (cc < C - 1) {
+        const float w = __expf(ml[cc].x - M_);
+        L = fmaf(ml[cc].y, w, L); O0 = fmaf(ov[cc].x, w, O0); O1 = fmaf(ov[cc].y, w, O1);
+      }
+    }
+    {
+      const float w = __expf(own[r][64] - M_);
+      L = fmaf(own[r][65], w, L); O0 = fmaf(own[r][2 * dp], w, O0); O1 = fmaf(own[r][2 * dp + 1], w, O1);
+    }
+    const float inv = 1.0f / L;
+    typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
+    const f16x2 o2 = {(f16)(O0 * inv), (f16)(O1 * inv)};
+    *reinterpret_cast<f16x2*>(out + (out_mb ? xf_index(b * R + r, h * 64 + 2 * dp, out_mb) : (size_t)(b * R + r) * d + h * 64 + 2 * dp)) = o2;
+  }
+  if (tid == 0) __hip_atomic_store(epoch + 1 + b * H + h, tag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  stamp(pf, 6);
+  if (wave == NKW) stamp(pfc, 5);
+  if (tid == 0) tl_end(prof);
+}
+
 int launch_dec_cross_attn(hipStream_t st, const CrossAttnP& p) {
   if (p.kq8) return launch_dec_cross_attn_q8(st, p);      // the int8 K/V images: a kernel of their own (cross_q8.hip); nothing below is involved
   const int B = p.B, R = p.R, H = p.H, d = p.d, T = p.T, Tpad = p.Tpad, chunks = p.chunks, xres_is_stat = p.xres_is_stat;
@@ -2755,6 +3045,11 @@ int launch_dec_cross_attn(hipStream_t st, const CrossAttnP& p) {
     if (ca_rs && (!small || ca_rs >= 2) && CL == 256 && used <= 6 && R <= 8 && d <= 1280) {
 #define WIS_CA_RS(SPINv, NTv) hipLaunchKernelGGL((dec_cross_attn_rs_kernel<SPINv, NTv, 2>), dim3(used, H, B), dim3(256), 0, st, p.q, p.kx, p.vt, xres, p.q2, p.epoch, \
                                                         (R | (H << 8) | (CL << 14) | (used << 24)), (d | (T << 16)), (Tpad | (p.kv_shared ? (1 << 30) : 0)), p.out, p.part, p.counters, p.prof, p.out_mb, p.qcs, p.qb, p.gran)
+      if (spin && small && d == 1280) {      // the one-utterance step of the large models: a kernel of its own, the same bits
+        hipLaunchKernelGGL(dec_cross_attn_b1_kernel, dim3(used, H, B), dim3(256), 0, st, p.q, p.kx, xres, p.q2, p.qcs, p.qb,
+                           (R | (p.kv_shared ? (1 << 7) : 0) | (H << 8) | (CL << 14) | (used << 24)), (d | (T << 16)), p.vt, Tpad, p.epoch, p.out, p.prof, p.out_mb, p.gran);
+        return WIS_OK;
+      }
       if (spin) { if (small) WIS_CA_RS(true, true); else WIS_CA_RS(true, false); }
       else { if (small) WIS_CA_RS(false, true); else WIS_CA_RS(false, false); }
 #undef WIS_CA_RS

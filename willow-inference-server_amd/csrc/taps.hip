@@ -104,9 +104,14 @@ int wis_debug_phase_cycles(wis_model_t* m, int B, int beam, int pos, uint64_t* o
   const int* rows = Mrows > 8 ? rows_frag : rows_small;
   for (int i = 0; i < 6; ++i)
     WIS_HIP_CHECK(hipMemcpyAsync(out + i * 16, m->d_prof + rows[i] * 16, 16 * 8, hipMemcpyDeviceToHost, m->st));
+  // rows 6 and 7 of `out`: the cross-attention output projection (device row 5) and what the cross-attention's COMBINER workgroup left in entries 7-13 of that
+  // device row (dec_cross_attn_rs_kernel, granule form), moved to entries 0-6 of a row of its own
+  WIS_HIP_CHECK(hipMemcpyAsync(out + 6 * 16, m->d_prof + 5 * 16, 16 * 8, hipMemcpyDeviceToHost, m->st));
   bool gave_up = false;
   WIS_RET(spin_gave_up(m, &gave_up));      // (synchronises the stream; a raised flag is consumed here, not by the next wis_generate)
   if (gave_up) { set_error("wis_debug_phase_cycles: the granule hand-off gave up during the tap; stamps are not valid"); return WIS_E_STATE; }
+  for (int i = 0; i < 16; ++i) out[7 * 16 + i] = i < 7 ? out[6 * 16 + 7 + i] : 0;
+  for (int i = 7; i < 14; ++i) out[6 * 16 + i] = 0;
   return WIS_OK;
 }
 
