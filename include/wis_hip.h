@@ -586,6 +586,17 @@ int wis_debug_graph_count(wis_model_t* m, int* count);
 /* the self-attention form of the long-prompt route's decode step on this handle: 1 = dec_self_attn_long_kernel, 0 = the TREE form of dec_self_attn_kernel
  * (what WIS_SA_LONG=0 selects for the process), -1 = back to the switch.  For A/B measurements in one process (tools/prompt_bench.py). */
 int wis_debug_sa_long(wis_model_t* m, int form);
+/* How a prompt of more than 16 tokens is prefilled on this handle (clones inherit it).  mode 0, the default: in windows of 16 positions (one pass over the
+ * decoder weights per window).  mode 1: the prefix - everything before the last min(16, 96 / B) prompt rows - in ONE GEMM-shaped pass (csrc/prefill.hip), the
+ * last rows, the first step and every later step exactly as in mode 0.  Mode 1 applies per call; a call it does not apply to runs as in mode 0:
+ *   - decoder weights int8_float16                       - cross_kv_bits = 8
+ *   - wis_generate_ragged with lengths that differ       - more than 256 prefix rows (B * (P - min(16, 96 / B)) > 256)
+ *   - no_speech_prob with <|startoftranscript|> inside the prefix (it is normally among the last rows)
+ * Prompts of up to 16 tokens, drafts, wis_align and the taps never take the route.  The two modes sum in different orders: ids agree except at near-ties.
+ * WIS_E_ARG for any other mode. */
+int wis_model_set_prefill(wis_model_t* m, int mode);
+/* positions 0 .. n_pos - 1 of one self-attention cache slot of one decoder layer, as the last call left them: k / v f16 [n_pos][d_model] (host) */
+int wis_debug_self_kv(wis_model_t* m, int layer, int slot, int n_pos, void* k_f16, void* v_f16);
 
 /* ---- timing taps: wall/device ms of the stages of the LAST wis_generate on this handle */
 typedef struct {
@@ -726,6 +737,24 @@ int wis_op_dec_self_attn_ex(int device, const float* q, const void* kc_f16, cons
  * [B k] (>= plen[b] - 1), plen i32 [B] in [1, 256] (device memory, as pos) -> out f16 [B k][d], or the fragment image of out_mb row blocks as above. */
 int wis_op_dec_self_attn_long(int device, const float* q, const void* kc_f16, const void* vc_f16, const int32_t* pos, const int32_t* plen, void* out_f16,
                               int B, int k, int H, int ctx, int out_mb);
+/* ---- the one-pass prefix route of a long prompt (wis_model_set_prefill; csrc/prefill.hip): its three kernels on device memory of the caller.  Rows are
+ * M = B Np <= 256, row m = b Np + i = position i of utterance b; every operand is row-major.
+ * wis_op_dec_prefill_proj: y = epi(LN?(x) W^T + bias), W f16 [N][K] prepared as the loader prepares a decoder projection (LayerNorm fold where gamma / beta
+ * are given, the 16-row fragment image; no query scaling), N % 16 == 0, K % 128 == 0.  epi:
+ *   0  QKV: x f32 [M][K], gamma, beta; N = 3 K -> y = the queries f16 [M][K]; the key / value columns of row m go to kc / vc f16 [slots][ctx][K] at slot
+ *      (m / Np) sstride, position m % Np - nothing else of the caches is written
+ *   1  residual: x f16 [M][K], gamma = beta = NULL -> y f32 [M][N] += x W^T + bias in place (out-projection, cross-attention out-projection, FFN2)
+ *   2  LayerNorm-folded: x f32 [M][K], gamma, beta -> y f16 [M][N] (cross-Q)
+ *   3  ... with GELU (FFN1)
+ * kc / vc / Np / sstride / ctx are read for epi 0 only. */
+int wis_op_dec_prefill_proj(int device, int epi, const void* x, const float* gamma, const float* beta, const void* W_f16, const float* bias, void* y,
+                            void* kc_f16, void* vc_f16, int M, int N, int K, int Np, int sstride, int ctx);
+/* causal self-attention of the prefix: q f16 [B Np][64 H] (scaled) - row (b, i) reads positions 0 .. i of slot b sstride of kc / vc f16 [slots][ctx][64 H]
+ * -> out f16 [B Np][64 H].  Np <= min(256, ctx). */
+int wis_op_dec_prefill_self_attn(int device, const void* q_f16, const void* kc_f16, const void* vc_f16, void* out_f16, int B, int Np, int H, int ctx, int sstride);
+/* cross-attention of the prefix: q f16 [B Np][64 H] (scaled) against the f16 cross images kx [B][H][8][T][8], vt [B][H][64][Tpad] (keys >= T are masked,
+ * whatever the tail of vt holds as long as it is finite; Tpad >= T rounded up to 32) -> out f16 [B Np][64 H]. */
+int wis_op_dec_prefill_cross_attn(int device, const void* q_f16, const void* kx_f16, const void* vt_f16, void* out_f16, int B, int Np, int H, int T, int Tpad);
 /* the self-attention QKV projection behind its LayerNorm with the scatter epilogue (GV_LN | GV_QKV), prepared as the loader prepares it (LayerNorm
  * fold, 1/8 on the query rows, packing): x f32 [M][d], W f16 [3d][d], bias f32 [3d] -> q f32 [M][d]; row m's key / value rows go to
  * kc / vc f16 [slots][ctx][d] at (slot[m], pos[m]).  M <= 8: the LDS-staged form; more rows: fragment image + row partials (launch_gemv_frag). */

@@ -364,6 +364,17 @@ static int seed_prefill(const GenCtx& g) {
 // the utterance's rows (dec_self_attn_long_kernel), a decode row keeps only the positions from P on in its own slot, and the cache reorder moves only those -
 // behind this pass there is nothing to move.
 static int seed_prefill_ragged(const GenCtx& g);
+// the last Pl prompt rows behind a prefix whose K / V stands in slot b * beam (either route): merged prefill + first step, then the sampling tail
+static int seed_last_rows(const GenCtx& g) {
+  wis_model* m = g.m; hipStream_t st = g.st; const wis_config_t& c = m->cfg;
+  const int B = g.B, P = g.P, beam = g.beam, Pl = g.Pl, Np = P - Pl;
+  std::vector<int> tok(B * Pl), pos(B * Pl), slot(B * Pl), ls(B * Pl);
+  for (int b = 0; b < B; ++b) for (int i = 0; i < Pl; ++i) { tok[b * Pl + i] = g.prompt[b * P + Np + i]; pos[b * Pl + i] = Np + i; slot[b * Pl + i] = ls[b * Pl + i] = b * beam; }
+  WIS_RET(upload_rows(m, tok, pos, slot, ls, false));
+  WIS_RET(dec_forward(m, B * Pl, Pl, B, true, beam, 0));
+  if (g.sot_row >= Np) WIS_RET(launch_no_speech(st, m->logits, m->n_vocab_pad, B, Pl, g.sot_row - Np, c.n_vocab, c.no_speech, m->d_nsp));
+  return sampling_tail(g, {Pl, 0, Pl - 1}, TAIL_TAPS | TAIL_NO_CACHE);
+}
 static int seed_prefill_long(const GenCtx& g) {
   if (g.ragged) return seed_prefill_ragged(g);
   wis_model* m = g.m; hipStream_t st = g.st; const wis_config_t& c = m->cfg; PinnedScratch* hp = m->h_pin;
@@ -390,12 +401,63 @@ static int seed_prefill_long(const GenCtx& g) {
       if (nsp) WIS_RET(launch_no_speech(st, m->logits, m->n_vocab_pad, nb, 16, g.sot_row - t0, c.n_vocab, c.no_speech, m->d_nsp + ub0));
     }
   }
-  std::vector<int> tok(B * Pl), pos(B * Pl), slot(B * Pl), ls(B * Pl);
-  for (int b = 0; b < B; ++b) for (int i = 0; i < Pl; ++i) { tok[b * Pl + i] = g.prompt[b * P + Np + i]; pos[b * Pl + i] = Np + i; slot[b * Pl + i] = ls[b * Pl + i] = b * beam; }
-  WIS_RET(upload_rows(m, tok, pos, slot, ls, false));
-  WIS_RET(dec_forward(m, B * Pl, Pl, B, true, beam, 0));
-  if (g.sot_row >= Np) WIS_RET(launch_no_speech(st, m->logits, m->n_vocab_pad, B, Pl, g.sot_row - Np, c.n_vocab, c.no_speech, m->d_nsp));
-  return sampling_tail(g, {Pl, 0, Pl - 1}, TAIL_TAPS | TAIL_NO_CACHE);
+  return seed_last_rows(g);
+}
+
+// ---- the long-prompt route with wis_model_set_prefill(m, 1): ONE-PASS prefix.  The same prefix positions 0 .. Np - 1 of every utterance as M = B Np rows
+// through every layer in one GEMM-shaped pass (prefill.hip: row-major activations of the handle's own, the decoder's fragment images read in place), K / V
+// into slot b * beam exactly where the windows put them; no logits, and the last layer stops behind its QKV projection - nothing reads the rest.  The last Pl
+// rows, the sampling tail and everything behind them are seed_prefill_long's, launch for launch.  Where the route does not apply the windowed one runs:
+//   int8_float16 decoder weights (the fragment images are 8-bit)           cross_kv_bits = 8 (the cross images are int8)
+//   wis_generate_ragged with lengths that differ                            B Np > PF_MAX_ROWS = 256 rows
+//   no_speech_prob with the <|startoftranscript|> row inside the prefix (that row needs logits; it is normally among the last Pl)
+static bool onepass_applies(const GenCtx& g) {
+  const wis_model* m = g.m; const int Np = g.P - g.Pl;
+  return m->prefill_mode == 1 && g.long_p && !g.ragged && !m->w8 && !m->ckv_i8 && Np >= 1 && g.B * Np <= PF_MAX_ROWS && !(g.sot_row >= 0 && g.sot_row < Np) &&
+         m->cfg.d_model % 128 == 0 && m->cfg.d_model == 64 * m->cfg.n_heads;
+}
+static int seed_prefill_onepass(const GenCtx& g) {
+  wis_model* m = g.m; hipStream_t st = g.st; const wis_config_t& c = m->cfg; PinnedScratch* hp = m->h_pin;
+  const int B = g.B, P = g.P, beam = g.beam, Pl = g.Pl, Np = P - Pl, M = B * Np, d = c.d_model, H = c.n_heads, L = c.n_dec_layers;
+  if (!m->pf.x) {
+    const size_t R = PF_MAX_ROWS, bytes = R * d * 4 + R * 2 * 4 + R * 4 + R * d * 2 * 7;
+    void* q = nullptr;
+    if (hipMalloc(&q, bytes) != hipSuccess) { (void)hipGetLastError(); set_error("one-pass prefill: out of device memory (%zu bytes)", bytes); return WIS_E_NOMEM; }
+    m->allocs.push_back(q); m->bytes += bytes;
+    m->pf.x = static_cast<float*>(q); m->pf.stat = m->pf.x + R * d; m->pf.tok = reinterpret_cast<int*>(m->pf.stat + R * 2);
+    m->pf.xh = reinterpret_cast<f16*>(m->pf.tok + R); m->pf.q = m->pf.xh + R * d; m->pf.ao = m->pf.q + R * d; m->pf.h = m->pf.ao + R * d;
+  }
+  for (int b = 0; b < B; ++b) for (int i = 0; i < Np; ++i) hp->pf_tok[b * Np + i] = g.prompt[b * P + i];
+  WIS_HIP_CHECK(hipMemcpyAsync(m->pf.tok, hp->pf_tok, (size_t)M * 4, hipMemcpyHostToDevice, st));      // (the call's results are waited for before it returns: the area is free for the next call)
+  WIS_RET(launch_prefill_embed(st, m->emb, m->dec_pos, m->pf.tok, M, Np, d, m->pf.x));
+  auto proj = [&](const DecProj& w, const f16* A, int epi) {
+    PrefillProjP p; memset(&p, 0, sizeof(p));
+    p.A = A; p.Wp = w.Wp; p.bias = w.bias; p.csum = w.csum; p.stat = m->pf.stat; p.M = M; p.N = w.N; p.K = w.K; p.epi = epi;
+    return p;
+  };
+  for (int l = 0; l < L; ++l) {
+    const DecLayerW& w = m->dec[l];
+    WIS_RET(launch_prefill_rowstat(st, m->pf.x, M, d, m->pf.stat, m->pf.xh));
+    PrefillProjP p = proj(w.qkv, m->pf.xh, PF_EPI_QKV);
+    p.y16 = m->pf.q; p.kc = m->kc[l]; p.vc = m->vc[l]; p.d = d; p.ctx = c.n_text_ctx; p.Np = Np; p.sstride = beam;
+    WIS_RET(launch_prefill_proj(st, p));
+    if (l == L - 1) break;      // the pass is for the prefix K / V alone
+    WIS_RET(launch_prefill_self_attn(st, m->pf.q, m->kc[l], m->vc[l], m->pf.ao, B, Np, H, c.n_text_ctx, beam));
+    p = proj(w.out, m->pf.ao, PF_EPI_RESID); p.y32 = m->pf.x;
+    WIS_RET(launch_prefill_proj(st, p));
+    WIS_RET(launch_prefill_rowstat(st, m->pf.x, M, d, m->pf.stat, m->pf.xh));
+    p = proj(w.cq, m->pf.xh, PF_EPI_LN_F16); p.y16 = m->pf.q;
+    WIS_RET(launch_prefill_proj(st, p));
+    WIS_RET(launch_prefill_cross_attn(st, m->pf.q, m->kx[l], m->vx[l], m->pf.ao, B, Np, H, c.n_audio_ctx, m->Tpad));
+    p = proj(w.cout, m->pf.ao, PF_EPI_RESID); p.y32 = m->pf.x;
+    WIS_RET(launch_prefill_proj(st, p));
+    WIS_RET(launch_prefill_rowstat(st, m->pf.x, M, d, m->pf.stat, m->pf.xh));
+    p = proj(w.f1, m->pf.xh, PF_EPI_LN_GELU); p.y16 = m->pf.h;
+    WIS_RET(launch_prefill_proj(st, p));
+    p = proj(w.f2, m->pf.h, PF_EPI_RESID); p.y32 = m->pf.x;
+    WIS_RET(launch_prefill_proj(st, p));
+  }
+  return seed_last_rows(g);
 }
 
 // ---- the same for prompts of DIFFERENT lengths (wis_generate_ragged): every utterance u on the long-prompt route, whatever its length P_u.  Its prefix
@@ -883,7 +945,8 @@ static int generate_impl(wis_model_t* m, const float* input, int B, const int32_
   WIS_RET(front_half(g));
 
   Seed sd;
-  if (g.long_p) WIS_RET(seed_prefill_long(g));
+  if (g.long_p && onepass_applies(g)) WIS_RET(seed_prefill_onepass(g));
+  else if (g.long_p) WIS_RET(seed_prefill_long(g));
   else if (!g.drafting) WIS_RET(seed_prefill(g));
   else {
     TicketScope ticket(m);

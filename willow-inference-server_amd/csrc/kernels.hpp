@@ -326,4 +326,26 @@ int launch_greedy_pick(hipStream_t st, const float* st_max, const float* st_sum,
 // language detection: softmax over lang_ids of the row's logits
 int launch_lang_probs(hipStream_t st, const float* logits, int ld, const int* lang_ids, int n_lang, float* probs, int B);
 
+// ---- the one-pass prefix route of a long prompt (prefill.hip): B Np <= PF_MAX_ROWS rows, row m = b Np + i is position i of utterance b, row-major operands ----
+constexpr int PF_MAX_ROWS = 256;
+enum { PF_EPI_QKV = 0,        // LayerNorm-folded; columns < d -> y16 [M][d] (the queries), the next d -> kc, the last d -> vc at slot (m / Np) sstride, position m % Np
+       PF_EPI_RESID = 1,      // y32 [M][N] += A W^T + bias, in place
+       PF_EPI_LN_F16 = 2,     // LayerNorm-folded -> y16 [M][N] (cross-Q)
+       PF_EPI_LN_GELU = 3 };  // LayerNorm-folded, GELU -> y16 [M][N] (FFN1)
+struct PrefillProjP {
+  const f16* A;                 // [M][K] row-major (a LayerNorm-folded projection: the RAW rows as f16)
+  const f16* Wp;                // the decoder's fragment image of W [N][K] (DecProj::Wp, rows = 16), read in place
+  const float* bias; const float* csum; const float* stat;      // [N]; LayerNorm-folded: column sums [N], {mean, rstd} per row [M][2]
+  float* y32; f16* y16;
+  int M, N, K, epi;
+  f16* kc; f16* vc; int d, ctx, Np, sstride;      // PF_EPI_QKV: the layer's caches [slots][ctx][d]
+};
+int launch_prefill_embed(hipStream_t st, const f16* emb, const f16* pos_emb, const int* tok, int M, int Np, int d, float* x);
+int launch_prefill_rowstat(hipStream_t st, const float* x, int M, int d, float* stat, f16* xh);
+int launch_prefill_proj(hipStream_t st, const PrefillProjP& p);
+// q f16 [B Np][64 H] (scaled) against keys 0 .. i of the same rows, read from cache slot b sstride ([ctx][64 H]) -> out f16 [B Np][64 H]
+int launch_prefill_self_attn(hipStream_t st, const f16* q, const f16* kc, const f16* vc, f16* out, int B, int Np, int H, int ctx, int sstride);
+// q f16 [B Np][64 H] (scaled) against the f16 cross images kx [B][H][8][T][8], vt [B][H][64][Tpad] -> out f16 [B Np][64 H]
+int launch_prefill_cross_attn(hipStream_t st, const f16* q, const f16* kx, const f16* vt, f16* out, int B, int Np, int H, int T, int Tpad);
+
 }  // namespace wis

@@ -1325,6 +1325,7 @@ int wis_model_clone(wis_model_t* parent, wis_model_t** out) {
   m->enc_i8 = parent->enc_i8; m->q_ckv_all = parent->q_ckv_all; m->s_ckv_all = parent->s_ckv_all;
   m->w8 = parent->w8; m->cq_fold = parent->cq_fold;
   m->use_graph = parent->use_graph;
+  m->prefill_mode = parent->prefill_mode;
   m->al.heads = parent->al.heads;      // (the clone allocates its own align scratch on its first wis_align)
   m->tok_flags = parent->tok_flags;      // (a clone has a phrase buffer of its own and starts without a set)
   memset(&m->timing, 0, sizeof(m->timing));
@@ -1416,6 +1417,23 @@ int wis_debug_sa_long(wis_model_t* m, int form) {
   if (!m || form < -1 || form > 1) { set_error("wis_debug_sa_long: bad argument"); return WIS_E_ARG; }
   WIS_ENTER(m, "wis_debug_sa_long")
   m->sa_long_form = form;
+  return WIS_OK;
+}
+int wis_model_set_prefill(wis_model_t* m, int mode) {
+  if (!m || (mode != 0 && mode != 1)) { set_error("wis_model_set_prefill: mode %d (0: windowed, 1: one pass where it applies)", mode); return WIS_E_ARG; }
+  WIS_ENTER(m, "wis_model_set_prefill")
+  m->prefill_mode = mode;
+  return WIS_OK;
+}
+int wis_debug_self_kv(wis_model_t* m, int layer, int slot, int n_pos, void* k_f16, void* v_f16) {
+  if (!m || !k_f16 || !v_f16 || layer < 0 || layer >= m->cfg.n_dec_layers || slot < 0 || slot >= m->cfg.max_batch * m->cfg.max_beam || n_pos < 1 || n_pos > m->cfg.n_text_ctx) {
+    set_error("wis_debug_self_kv: bad argument"); return WIS_E_ARG; }
+  WIS_ENTER(m, "wis_debug_self_kv")
+  WIS_HIP_CHECK(hipSetDevice(m->device));
+  const size_t d = m->cfg.d_model, off = (size_t)slot * m->cfg.n_text_ctx * d;
+  WIS_HIP_CHECK(hipMemcpyAsync(k_f16, m->kc[layer] + off, (size_t)n_pos * d * 2, hipMemcpyDeviceToHost, m->st));
+  WIS_HIP_CHECK(hipMemcpyAsync(v_f16, m->vc[layer] + off, (size_t)n_pos * d * 2, hipMemcpyDeviceToHost, m->st));
+  WIS_HIP_CHECK(hipStreamSynchronize(m->st));
   return WIS_OK;
 }
 int wis_debug_graph_count(wis_model_t* m, int* count) {

@@ -106,6 +106,7 @@ struct PinnedScratch {
   int path_reset[1 + MAX_R];
   struct { int parent[MAX_R], step, done; } tree_seed;      // wis_debug_tree_logits: the search state behind the prompt pass
   int al_frames[2 * MAX_ROWS], al_tgt[MAX_ROWS], al_dst[MAX_ROWS];      // wis_align: {tokens, frames} per utterance; target token / matrix row per pass row
+  int pf_tok[PF_MAX_ROWS];                     // seed_prefill_onepass: the prefix tokens of the pass, row m = b Np + i (wis_model::pf.tok)
 };
 static_assert(MAX_ROWS % 16 == 0, "a verification window is padded to whole groups of 16 rows: min(ANC_W, MAX_ROWS / beam) steps x beam rows must still fit MAX_ROWS");
 static_assert(sizeof(PinnedScratch::draft) == sizeof(int) * MAX_STEPS * MAX_R * 2, "the draft area holds one {token, origin} pair per step and beam slot");
@@ -217,6 +218,12 @@ struct wis_model {
   // LAST buffer carved - and its record count (0: no set); d_hot_ctl: the two words {boost bits, record count} behind the table that hotword_rules_kernel
   // reads - the boost written ahead of every call's steps (as the sampling seeds are), the count with the set: one captured step serves every value
   int4* d_hot = nullptr; int hot_n = 0; int* d_hot_ctl = nullptr;
+  // wis_model_set_prefill: 0 = the windowed prefill of a long prompt (seed_prefill_long), 1 = the one-pass prefix route where it applies (generate.hip
+  // seed_prefill_onepass; clones inherit the mode).  pf: that route's row-major activations for PF_MAX_ROWS rows, one block allocated by the handle's first
+  // such call (as the logmass buffer is) - x fp32 [rows][d], {mean, rstd} [rows][2], the rows' tokens, then f16: the rows' copy xh, q, the attention output
+  // ao [rows][d] each and the FFN hidden h [rows][4 d]
+  int prefill_mode = 0;
+  struct { float* x = nullptr; float* stat = nullptr; int* tok = nullptr; wis::f16 *xh = nullptr, *q = nullptr, *ao = nullptr, *h = nullptr; } pf;
 };
 
 namespace wis {

@@ -476,6 +476,39 @@ int wis_op_dec_self_attn_long(int device, const float* q, const void* kc, const 
   sa.M = B * k; sa.H = H; sa.d = d; sa.ctx = ctx; sa.rpu = k; sa.sstride = k; sa.rmul = 1; sa.out_mb = out_mb; sa.plen = plen;
   return t.finish(launch_dec_self_attn(t.st, sa));
 }
+// ---- the one-pass prefix route's three kernels (prefill.hip; tests/test_gpu_prefill_ops.py)
+int wis_op_dec_prefill_proj(int device, int epi, const void* x, const float* gamma, const float* beta, const void* W_f16, const float* bias, void* y,
+                            void* kc_f16, void* vc_f16, int M, int N, int K, int Np, int sstride, int ctx) {
+  Tap t(device, "wis_op_dec_prefill_proj"); WIS_RET(t.rc);
+  const bool ln = epi != PF_EPI_RESID;
+  if (!x || !W_f16 || !bias || !y || epi < PF_EPI_QKV || epi > PF_EPI_LN_GELU || ln != (gamma != nullptr) || ln != (beta != nullptr) || M < 1 || M > PF_MAX_ROWS || N < 16 || N % 16 ||
+      K < 128 || K % 128 || (epi == PF_EPI_QKV && (!kc_f16 || !vc_f16 || N != 3 * K))) { set_error("wis_op_dec_prefill_proj: bad argument"); return WIS_E_ARG; }
+  hipStream_t st = t.st;
+  f16 *w = nullptr, *wp = nullptr, *xh = nullptr; float *b = nullptr, *csum = nullptr, *stat = nullptr;
+  WIS_RET(t.get(&w, (size_t)N * K)); WIS_RET(t.get(&wp, (size_t)N * K)); WIS_RET(t.get(&b, (size_t)N)); WIS_RET(t.get(&csum, (size_t)N, true));
+  WIS_HIP_CHECK(hipMemcpyAsync(w, W_f16, (size_t)N * K * 2, hipMemcpyDeviceToDevice, st));
+  WIS_HIP_CHECK(hipMemcpyAsync(b, bias, (size_t)N * 4, hipMemcpyDeviceToDevice, st));
+  WIS_RET(prep_projection(st, w, N, N, K, 0, 1.f, gamma, beta, b, csum, wp, nullptr, 16));      // the loader's preparation, without the query scaling
+  PrefillProjP p; memset(&p, 0, sizeof(p));
+  p.A = reinterpret_cast<const f16*>(x); p.Wp = wp; p.bias = b; p.M = M; p.N = N; p.K = K; p.epi = epi;
+  if (ln) {
+    WIS_RET(t.get(&xh, (size_t)M * K)); WIS_RET(t.get(&stat, (size_t)M * 2));
+    WIS_RET(launch_prefill_rowstat(st, reinterpret_cast<const float*>(x), M, K, stat, xh));
+    p.A = xh; p.csum = csum; p.stat = stat; p.y16 = reinterpret_cast<f16*>(y);
+  } else p.y32 = reinterpret_cast<float*>(y);
+  if (epi == PF_EPI_QKV) { p.kc = reinterpret_cast<f16*>(kc_f16); p.vc = reinterpret_cast<f16*>(vc_f16); p.d = K; p.ctx = ctx; p.Np = Np; p.sstride = sstride; }
+  return t.finish(launch_prefill_proj(st, p));
+}
+int wis_op_dec_prefill_self_attn(int device, const void* q_f16, const void* kc_f16, const void* vc_f16, void* out_f16, int B, int Np, int H, int ctx, int sstride) {
+  Tap t(device, "wis_op_dec_prefill_self_attn"); WIS_RET(t.rc);
+  return t.finish(launch_prefill_self_attn(t.st, reinterpret_cast<const f16*>(q_f16), reinterpret_cast<const f16*>(kc_f16), reinterpret_cast<const f16*>(vc_f16),
+                                           reinterpret_cast<f16*>(out_f16), B, Np, H, ctx, sstride));
+}
+int wis_op_dec_prefill_cross_attn(int device, const void* q_f16, const void* kx_f16, const void* vt_f16, void* out_f16, int B, int Np, int H, int T, int Tpad) {
+  Tap t(device, "wis_op_dec_prefill_cross_attn"); WIS_RET(t.rc);
+  return t.finish(launch_prefill_cross_attn(t.st, reinterpret_cast<const f16*>(q_f16), reinterpret_cast<const f16*>(kx_f16), reinterpret_cast<const f16*>(vt_f16),
+                                            reinterpret_cast<f16*>(out_f16), B, Np, H, T, Tpad));
+}
 static int op_dec_cross_attn(int device, const float* q, const float* xres, const float* qcs, const float* qb, const void* kx, const void* vt, void* out,
                              int B, int R, int H, int T, int chunks, const float* q2 = nullptr, int xres_is_stat = 0, int out_mb = 0, int kv_shared = 0, bool no_spin = false) {
   Tap t(device, "wis_op_dec_cross_attn"); WIS_RET(t.rc);

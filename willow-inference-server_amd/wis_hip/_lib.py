@@ -163,6 +163,8 @@ SYMBOLS = [
     ("wis_debug_handoff", _i, [_vp, _i, C.POINTER(_i), C.POINTER(_i)]),
     ("wis_debug_graph_count", _i, [_vp, C.POINTER(_i)]),
     ("wis_debug_sa_long", _i, [_vp, _i]),
+    ("wis_model_set_prefill", _i, [_vp, _i]),
+    ("wis_debug_self_kv", _i, [_vp, _i, _i, _i, _vp, _vp]),
     ("wis_last_timing", _i, [_vp, C.POINTER(Timing)]),
     ("wis_debug_phase_cycles", _i, [_vp, _i, _i, _i, C.POINTER(C.c_uint64)]),
     ("wis_debug_timeline", _i, [_vp, _i, _i, _i, _i, C.POINTER(C.c_uint64), _i]),
@@ -209,6 +211,9 @@ SYMBOLS = [
     ("wis_op_kv_reorder", _i, [_i, _vp, _vp, _i64, _i, _vp, _vp, _vp, _i, _i, _i, _i, _i]),
     ("wis_op_kv_reorder_from", _i, [_i, _vp, _vp, _i64, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _i]),
     ("wis_op_dec_self_attn_long", _i, [_i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i]),
+    ("wis_op_dec_prefill_proj", _i, [_i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i]),
+    ("wis_op_dec_prefill_self_attn", _i, [_i, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i]),
+    ("wis_op_dec_prefill_cross_attn", _i, [_i, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i]),
     ("wis_op_kv_gather", _i, [_i, _vp, _vp, _i64, _i, _vp, _vp, _i, _i, _i, _i]),
     ("wis_op_no_speech", _i, [_i, _vp, _i, _i, _i, _i, _i, _i, _vp]),
     ("wis_op_no_speech_rows", _i, [_i, _vp, _i, _i, _i, _vp, _i, _i, _vp]),

@@ -122,6 +122,8 @@ def create_app(models=None, settings=None, max_workers=None, sv=None):
     s = settings or (models.settings if models is not None else get_api_settings())
     if getattr(s, "long_form", "chunk") not in ("chunk", "seek"):      # (a bad setting fails the start, not every request)
         raise ValueError(f"setting long_form {s.long_form!r}: seek or chunk")
+    if getattr(s, "prompt_prefill", "windowed") not in ("windowed", "one_pass"):
+        raise ValueError(f"setting prompt_prefill {s.prompt_prefill!r}: windowed or one_pass")
     if getattr(s, "phrases_file", ""):      # (an unreadable phrase list fails the start too)
         from .whisper import load_phrases_file
         if not load_phrases_file(s.phrases_file):

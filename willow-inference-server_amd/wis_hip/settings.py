@@ -141,6 +141,10 @@ class APISettings:
     # the cross-attention K/V every decode step re-reads: "float16", or "int8" (per-key int8 rows: half the per-utterance cross K/V memory and stream; off by
     # default, independent of the two above; word_timestamps are refused with it)
     cross_kv_compute_type: str = "float16"
+    # prompts of more than 16 tokens (initial_prompt, the conditioning text of long_form=seek): "windowed" = prefilled 16 positions per pass over the decoder
+    # weights, "one_pass" = the prefix in one GEMM-shaped pass where that applies (f16 decoder weights and cross K/V, at most 256 prefix rows per device batch);
+    # off by default, a property of the model (micro-batches are keyed as before)
+    prompt_prefill: str = "windowed"
 
     def __post_init__(self):
         env = {k.lower(): v for k, v in os.environ.items()}

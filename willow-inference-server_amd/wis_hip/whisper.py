@@ -269,6 +269,7 @@ class WhisperModels:
                 self._models[size] = ctranslate2.models.Whisper(path, device="cuda", compute_type=self.settings.compute_type,
                                                                 encoder_compute_type=self.settings.encoder_compute_type,
                                                                 cross_kv_compute_type=self.settings.cross_kv_compute_type,
+                                                                prompt_prefill=getattr(self.settings, "prompt_prefill", "windowed"),
                                                                 inter_threads=self.settings.ctranslate2_threads,
                                                                 device_index=self.device_index, max_batch=self.settings.max_batch,
                                                                 replicas_per_device=self.settings.replicas_per_gpu, max_beam=max_beam)
