@@ -595,6 +595,13 @@ int wis_debug_sa_long(wis_model_t* m, int form);
  * Prompts of up to 16 tokens, drafts, wis_align and the taps never take the route.  The two modes sum in different orders: ids agree except at near-ties.
  * WIS_E_ARG for any other mode. */
 int wis_model_set_prefill(wis_model_t* m, int mode);
+/* How wis_align (and wis_debug_align_matrix) teacher-forces the known text through the decoder on this handle (clones inherit it).  mode 0, the default: in
+ * windows of 16 positions on the batched-row route (one pass over the decoder weights per window).  mode 1: every position of every utterance as ONE ragged
+ * GEMM-shaped pass over all layers (csrc/align_pass.hip; rows = sum of start + 1 + text tokens, up to max_batch * n_text_ctx), on scratch of its own - the
+ * decoder's caches stay as they were.  Mode 1 applies where the decoder weights and the cross K / V are f16; an int8_float16 handle runs as in mode 0 (and
+ * cross_kv_bits = 8 keeps refusing wis_align).  The two modes sum in different orders: matrices and probabilities agree to rounding, not bit for bit.
+ * WIS_E_ARG for any other mode. */
+int wis_model_set_align_pass(wis_model_t* m, int mode);
 /* positions 0 .. n_pos - 1 of one self-attention cache slot of one decoder layer, as the last call left them: k / v f16 [n_pos][d_model] (host) */
 int wis_debug_self_kv(wis_model_t* m, int layer, int slot, int n_pos, void* k_f16, void* v_f16);
 
@@ -755,6 +762,22 @@ int wis_op_dec_prefill_self_attn(int device, const void* q_f16, const void* kc_f
 /* cross-attention of the prefix: q f16 [B Np][64 H] (scaled) against the f16 cross images kx [B][H][8][T][8], vt [B][H][64][Tpad] (keys >= T are masked,
  * whatever the tail of vt holds as long as it is finite; Tpad >= T rounded up to 32) -> out f16 [B Np][64 H]. */
 int wis_op_dec_prefill_cross_attn(int device, const void* q_f16, const void* kx_f16, const void* vt_f16, void* out_f16, int B, int Np, int H, int T, int Tpad);
+/* ---- the one-pass route of wis_align (wis_model_set_align_pass; csrc/align_pass.hip): its three kernels on device memory of the caller.  Rows are ragged:
+ * off [B + 1] (HOST, off[0] = 0, ascending) - row off[b] + i is position i of utterance b, M = off[B] rows, any M.
+ * wis_op_align_pass_proj: y = epi(LN?(x) W^T + bias), W prepared as for wis_op_dec_prefill_proj; N % 16 == 0, K % 128 == 0.  epi:
+ *   0  LayerNorm-folded: x f32 [M][K], gamma, beta -> y f16 [M][N] (QKV: q | k | v of a row side by side; cross-Q)
+ *   1  residual: x f16 [M][K], gamma = beta = NULL -> y f32 [M][N] += x W^T + bias in place
+ *   2  LayerNorm-folded with GELU -> y f16 [M][N] (FFN1)
+ *   3  LayerNorm-folded -> y f32 [M][N] (the vocabulary projection)
+ * The kernel takes the rows' mean / rstd itself (E[x^2] - mean^2 in f32). */
+int wis_op_align_pass_proj(int device, int epi, const void* x, const float* gamma, const float* beta, const void* W_f16, const float* bias, void* y, int M, int N, int K);
+/* ragged causal self-attention: qkv f16 [M][192 H] (q scaled | k | v) - row (b, i) reads rows (b, 0 .. i) -> out f16 [M][64 H] */
+int wis_op_align_pass_self_attn(int device, const void* qkv_f16, const int32_t* off, void* out_f16, int B, int H);
+/* ragged cross-attention: q f16 [M][64 H] (scaled), utterance b against kx [b] / vt [b] of the f16 cross images ([B][H][8][T][8], [B][H][64][Tpad]) -> out f16
+ * [M][64 H].  head_sel [H] (HOST, or NULL: no capture): index of head h in a selection of nsel heads, or -1; a selected head's 64-wide query slice of the row at
+ * position i, P <= i < P + ncap, is copied to qsel f16 [B][nsel][ncap][64] (qsel_elems elements) at row i - P; nothing else of qsel is written. */
+int wis_op_align_pass_cross_attn(int device, const void* q_f16, const int32_t* off, const void* kx_f16, const void* vt_f16, void* out_f16, int B, int H, int T, int Tpad,
+                                 const int32_t* head_sel, void* qsel_f16, long long qsel_elems, int nsel, int ncap, int P);
 /* the self-attention QKV projection behind its LayerNorm with the scatter epilogue (GV_LN | GV_QKV), prepared as the loader prepares it (LayerNorm
  * fold, 1/8 on the query rows, packing): x f32 [M][d], W f16 [3d][d], bias f32 [3d] -> q f32 [M][d]; row m's key / value rows go to
  * kc / vc f16 [slots][ctx][d] at (slot[m], pos[m]).  M <= 8: the LDS-staged form; more rows: fragment image + row partials (launch_gemv_frag). */

@@ -60,6 +60,50 @@ def align_rows(a, size, clips, res):
         model.close()
 
 
+def ab_rows(a, size, clips, res):
+    """--ab: the windowed and the one-pass teacher-forced decoder (wis_model_set_align_pass 0 / 1) on ONE handle, alternating call by call, at one utterance
+    and at a ragged batch of eight (text lengths n, n / 2, ... cycling down to 5 tokens).  Per mode: the decoder-pass time (GPU events) and the whole call (host
+    clock around the synchronising call), each the median of `rounds` medians of `iters` calls, with the lowest and highest of those medians."""
+    import numpy as np
+    from wis_hip import _lib, audio, ctranslate2 as ct2, weights as W
+    arch = W.arch(size)
+    model = ct2.Whisper("unused", weights=W.synthetic_weights(size), arch=arch, max_batch=8, max_beam=5)
+    lib, h, st = _lib.load(), model._replicas[0].handle, model.special
+    start = [st.sot, st.lang_ids[0], st.transcribe]
+    rng = np.random.default_rng(0)
+    pcm = clips["30sec"]
+    num_frames = min(3000, -(-pcm.shape[0] // audio.HOP_LENGTH))
+    mel = audio.log_mel_spectrogram(audio.pad_or_trim(pcm), n_mels=arch["n_mels"]).numpy()
+    spread = lambda v: {"median": round(float(np.median(v)), 3), "lo": round(float(np.min(v)), 3), "hi": round(float(np.max(v)), 3)}
+    try:
+        for n in [int(t) for t in a.tokens.split(",")]:
+            for B in (1, 8):
+                lens = [n] if B == 1 else [max(5, n >> (b % 4)) for b in range(8)]
+                texts = [rng.integers(0, 50000, size=k).tolist() for k in lens]
+                feats = ct2.StorageView.from_array(np.ascontiguousarray(np.repeat(mel[None], B, axis=0)))
+                med = {0: ([], []), 1: ([], [])}
+                for r in range(a.rounds + 1):      # (round 0 warms both modes up)
+                    t = {0: ([], []), 1: ([], [])}
+                    for i in range(a.warmup if r == 0 else a.iters):
+                        for mode in (0, 1):
+                            _lib.check(lib.wis_model_set_align_pass(h, mode))
+                            t0 = time.perf_counter()
+                            model.align(feats, start, texts, [num_frames] * B)
+                            t1 = time.perf_counter()
+                            ms = (C.c_float * 6)()
+                            _lib.check(lib.wis_align_last_timing(h, ms))
+                            t[mode][0].append(ms[1]), t[mode][1].append((t1 - t0) * 1e3)
+                    if r:
+                        for mode in (0, 1):
+                            med[mode][0].append(np.median(t[mode][0])), med[mode][1].append(np.median(t[mode][1]))
+                res[f"{size}_{n}tok_B{B}"] = {"rows": sum(len(start) + 1 + k for k in lens),
+                                              "windowed": {"decoder_pass_ms": spread(med[0][0]), "align_ms": spread(med[0][1])},
+                                              "one_pass": {"decoder_pass_ms": spread(med[1][0]), "align_ms": spread(med[1][1])}}
+    finally:
+        _lib.check(lib.wis_model_set_align_pass(h, 0))
+        model.close()
+
+
 def do_whisper_rows(a, size, clips, e2e):
     import numpy as np
     label, size = size, ("large" if size == "large-v2" else size)      # (the model registry's name of large-v2)
@@ -92,10 +136,17 @@ def main():
     ap.add_argument("--iters", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--tokens", default="24,223")
+    ap.add_argument("--ab", action="store_true", help="windowed against one-pass on one handle, alternating (large-v2 unless --sizes says otherwise)")
+    ap.add_argument("--rounds", type=int, default=5)
     a = ap.parse_args()
     from wis_hip import audio
     clips = {n: audio.load_audio(os.path.join(ROOT, "tests", "golden", "clips", n + ".flac"))[0] for n in ("3sec", "30sec")}
     res, e2e = {}, {}
+    if a.ab:
+        for size in a.sizes.split(","):
+            ab_rows(a, size, clips, res)
+        print(json.dumps({"metric": "align_pass_ab_ms", "shapes": res}))
+        return
     for size in a.sizes.split(","):
         align_rows(a, size, clips, res)
         do_whisper_rows(a, size, clips, e2e)

@@ -20,7 +20,7 @@ OBJDIR = os.path.join(HERE, "build")
 LIB = os.path.join(LIBDIR, "libwis_hip.so")
 
 # one object per source; the longest compiles first (they start first when the pool is narrower than the list)
-HIP_SOURCES = ["dec_kernels.hip", "enc_kernels.hip", "model.hip", "sv.hip", "generate.hip", "taps.hip", "align.hip", "prefill.hip", "cross_q8.hip", "logmel.hip", "resample.hip"]
+HIP_SOURCES = ["dec_kernels.hip", "enc_kernels.hip", "model.hip", "sv.hip", "generate.hip", "taps.hip", "align.hip", "align_pass.hip", "prefill.hip", "cross_q8.hip", "logmel.hip", "resample.hip"]
 C_SOURCES = ["audio_io.c"]
 INCLUDE_DIRS = [CSRC, os.path.join(ROOT, "include")]
 EXPORTS = os.path.join(CSRC, "exports.map")

@@ -381,6 +381,75 @@ int wis::align_capture_q(wis_model* m, int l, int M) {
 }
 namespace {
 
+// ---- the teacher-forced section as ONE pass (wis_model_set_align_pass(m, 1); kernels in align_pass.hip) -----------------------------------------------------------
+// Every position of every utterance is a row: utterance b holds rows off[b] .. off[b] + P + text_len[b] (start sequence, <|notimestamps|>, text), no padding.
+// Per layer eight launches: QKV (LayerNorm inside) -> ragged self-attention -> out-projection -> cross-Q -> ragged cross-attention (the selected heads' queries
+// go to qsel on the way) -> cross out-projection -> FFN1 -> FFN2.  Probabilities (want_dtw): the vocabulary projection runs over blocks of MAX_ROWS rows into
+// m->logits and align_prob_kernel reads each block - [M][n_vocab] never exists.  Nothing of the decoder's own state is written: no cache slot, no row metadata, no
+// granule hand-off (so no SpinClaim and no retry).
+bool align_pass_applies(const wis_model* m) {
+  return m->align_pass == 1 && !m->w8 && !m->ckv_i8 && m->cfg.d_model % 128 == 0 && m->cfg.d_model == 64 * m->cfg.n_heads;
+}
+int align_one_pass(wis_model* m, int B, const int32_t* start_seq, int P, const int32_t* text, const int32_t* text_len, const std::vector<int>& toff, bool want_dtw) {
+  const wis_config_t& c = m->cfg; AlignState& a = m->al; hipStream_t st = m->st;
+  const int d = c.d_model, H = c.n_heads, L = c.n_dec_layers, ncap = c.n_text_ctx, Bm = c.max_batch, dff = m->dec[0].f1.N;
+  const size_t R = (size_t)Bm * ncap;
+  if (!a.ap.x) {
+    WIS_RET(al_malloc(m, &a.ap.x, R * d)); WIS_RET(al_malloc(m, &a.ap.meta, (size_t)Bm + 1 + (size_t)L * H + 3 * R));
+    WIS_RET(al_malloc(m, &a.ap.qkv, R * 3 * d)); WIS_RET(al_malloc(m, &a.ap.q, R * d)); WIS_RET(al_malloc(m, &a.ap.ao, R * d)); WIS_RET(al_malloc(m, &a.ap.h, R * dff));
+  }
+  // meta: off [Bm + 1] | head_sel [L][H] | tok [M] | tgt [M] | dst [M]
+  int M = 0, Lmax = 0;
+  for (int b = 0; b < B; ++b) { M += P + 1 + text_len[b]; Lmax = std::max(Lmax, P + 1 + text_len[b]); }
+  const size_t o_sel = (size_t)Bm + 1, o_tok = o_sel + (size_t)L * H;
+  std::vector<int>& hm = a.ap_host;
+  hm.assign(o_tok + 3 * (size_t)M, -1);
+  const auto sel = align_selected(m);
+  for (size_t s = 0; s < sel.size(); ++s) hm[o_sel + (size_t)sel[s].first * H + sel[s].second] = (int)s;
+  hm[0] = 0;
+  for (int b = 0, r = 0; b < B; ++b) {
+    const int Lb = P + 1 + text_len[b];
+    for (int p = 0; p < Lb; ++p, ++r) {
+      hm[o_tok + r] = p < P ? start_seq[p] : (p == P ? c.no_timestamps : text[toff[b] + p - P - 1]);
+      const int row = p - P;      // matrix row: predicts text token `row`
+      if (row >= 0 && row < text_len[b]) { hm[o_tok + M + r] = text[toff[b] + row]; hm[o_tok + 2 * (size_t)M + r] = b * ncap + row; }
+      else hm[o_tok + 2 * (size_t)M + r] = 0;
+    }
+    hm[b + 1] = r;
+  }
+  for (int b = B; b < Bm; ++b) hm[b + 1] = M;
+  WIS_HIP_CHECK(hipMemcpyAsync(a.ap.meta, hm.data(), hm.size() * 4, hipMemcpyHostToDevice, st));
+  const int* d_off = a.ap.meta; const int* d_sel = a.ap.meta + o_sel; const int* d_tok = a.ap.meta + o_tok; const int* d_tgt = d_tok + M; const int* d_dst = d_tgt + M;
+  WIS_RET(launch_align_embed(st, m->emb, m->dec_pos, d_tok, d_off, B, M, d, a.ap.x));
+  auto proj = [&](const DecProj& w, const void* A, int epi, void* y, int ldy) {
+    AlignProjP p; memset(&p, 0, sizeof(p));
+    p.A = A; p.Wp = w.Wp; p.bias = w.bias; p.csum = w.csum; p.M = M; p.N = w.N; p.K = w.K; p.epi = epi; p.ldy = ldy;
+    if (epi == AP_EPI_RESID || epi == AP_EPI_LN_F32) p.y32 = static_cast<float*>(y); else p.y16 = static_cast<f16*>(y);
+    return p;
+  };
+  for (int l = 0; l < L; ++l) {
+    const DecLayerW& w = m->dec[l];
+    WIS_RET(launch_align_proj(st, proj(w.qkv, a.ap.x, AP_EPI_LN_F16, a.ap.qkv, 3 * d)));
+    WIS_RET(launch_align_self_attn(st, a.ap.qkv, d_off, a.ap.ao, B, H, Lmax));
+    WIS_RET(launch_align_proj(st, proj(w.out, a.ap.ao, AP_EPI_RESID, a.ap.x, d)));
+    WIS_RET(launch_align_proj(st, proj(w.cq, a.ap.x, AP_EPI_LN_F16, a.ap.q, d)));
+    const bool cap = a.layer_s0[l + 1] > a.layer_s0[l];
+    WIS_RET(launch_align_cross_attn(st, a.ap.q, d_off, m->kx[l], m->vx[l], a.ap.ao, B, H, Lmax, c.n_audio_ctx, m->Tpad, cap ? d_sel + (size_t)l * H : nullptr, a.qsel, a.nsel, ncap, P));
+    if (l == L - 1 && !want_dtw) break;      // only the logits read the rest of the last layer
+    WIS_RET(launch_align_proj(st, proj(w.cout, a.ap.ao, AP_EPI_RESID, a.ap.x, d)));
+    WIS_RET(launch_align_proj(st, proj(w.f1, a.ap.x, AP_EPI_LN_GELU, a.ap.h, dff)));
+    WIS_RET(launch_align_proj(st, proj(w.f2, a.ap.h, AP_EPI_RESID, a.ap.x, d)));
+  }
+  for (int r0 = 0; want_dtw && r0 < M; r0 += MAX_ROWS) {
+    AlignProjP p = proj(m->proj, a.ap.x + (size_t)r0 * d, AP_EPI_LN_F32, m->logits, m->n_vocab_pad);
+    p.M = std::min(MAX_ROWS, M - r0);
+    WIS_RET(launch_align_proj(st, p));
+    hipLaunchKernelGGL(align_prob_kernel, dim3(p.M), dim3(256), 0, st, m->logits, m->n_vocab_pad, c.eot, d_tgt + r0, d_dst + r0, a.probs);
+  }
+  WIS_HIP_CHECK(hipGetLastError());
+  return WIS_OK;
+}
+
 // the whole alignment up to the matrix (want_dtw: and the paths / probabilities).  Results stay in m->al (acc, path, probs).
 int align_run(wis_model* m, const float* input, int input_kind, int B, const int32_t* start_seq, int P, const int32_t* text, const int32_t* text_len,
               const int32_t* num_frames, int width, bool want_dtw, const char* who) {
@@ -417,9 +486,12 @@ int align_run(wis_model* m, const float* input, int input_kind, int B, const int
   // teacher-forced passes of 16 positions over groups of <= MAX_ROWS / 16 utterances: always 16 rows per utterance (a shorter tail is
   // padded with eot inputs at the following positions, which later rows never attend to), so every pass takes the un-folded batched-row
   // route whose finished cross-Q the capture reads
+  // ... unless the handle takes the one-pass route (align_one_pass above): every row of the batch in one ragged pass, the windows below do not run
+  const bool one_pass = align_pass_applies(m);
+  if (one_pass) WIS_RET(align_one_pass(m, B, start_seq, P, text, text_len, off, want_dtw));
   const int Lpad = cdiv(Lmax, 16) * 16, UG = MAX_ROWS / 16;
   auto tok_at = [&](int b, int p) { return p < P ? start_seq[p] : (p == P ? nots : (p - P - 1 < text_len[b] ? text[off[b] + p - P - 1] : eot)); };
-  for (int ub0 = 0; ub0 < B; ub0 += UG) {
+  for (int ub0 = 0; !one_pass && ub0 < B; ub0 += UG) {
     const int nb = std::min(UG, B - ub0), M = nb * 16;
     int glen = 0;
     for (int u = 0; u < nb; ++u) glen = std::max(glen, P + 1 + text_len[ub0 + u]);

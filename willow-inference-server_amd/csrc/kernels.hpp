@@ -348,4 +348,25 @@ int launch_prefill_self_attn(hipStream_t st, const f16* q, const f16* kc, const 
 // q f16 [B Np][64 H] (scaled) against the f16 cross images kx [B][H][8][T][8], vt [B][H][64][Tpad] -> out f16 [B Np][64 H]
 int launch_prefill_cross_attn(hipStream_t st, const f16* q, const f16* kx, const f16* vt, f16* out, int B, int Np, int H, int T, int Tpad);
 
+// ---- the one-pass teacher-forced decoder of wis_align (align_pass.hip): ragged rows, row off[b] + i is position i of utterance b (off [B + 1] on the device), any M ----
+enum { AP_EPI_LN_F16 = 0,     // LayerNorm-folded -> y16 [M][ldy] (QKV into the pass's q | k | v rows, cross-Q)
+       AP_EPI_RESID = 1,      // y32 [M][ldy] += A W^T + bias, in place
+       AP_EPI_LN_GELU = 2,    // LayerNorm-folded, GELU -> y16 [M][ldy] (FFN1)
+       AP_EPI_LN_F32 = 3 };   // LayerNorm-folded -> y32 [M][ldy] (the vocabulary projection behind the final LayerNorm, a block of rows at a time)
+struct AlignProjP {
+  const void* A;                // LayerNorm-folded epilogues: the RAW fp32 rows [M][K] (the kernel rounds them to f16 and takes their mean / rstd itself); AP_EPI_RESID: f16 [M][K]
+  const f16* Wp;                // the decoder's fragment image of W [N][K] (DecProj::Wp), read in place
+  const float* bias; const float* csum;      // [N]; LayerNorm-folded: column sums [N]
+  float* y32; f16* y16; int ldy;
+  int M, N, K, epi;
+};
+int launch_align_embed(hipStream_t st, const f16* emb, const f16* pos_emb, const int* tok, const int* off, int B, int M, int d, float* x);
+int launch_align_proj(hipStream_t st, const AlignProjP& p);
+// qkv f16 [M][192 H] (q scaled | k | v): queries of utterance b against keys 0 .. own position of the same utterance -> out f16 [M][64 H]; Lmax: the longest utterance
+int launch_align_self_attn(hipStream_t st, const f16* qkv, const int* off, f16* out, int B, int H, int Lmax);
+// q f16 [M][64 H] (scaled) against the f16 cross images kx [B][H][8][T][8], vt [B][H][64][Tpad] -> out f16 [M][64 H]; head_sel [H] (device, or null): a head's index in
+// the alignment selection or -1 - a selected head's queries at positions P .. go to qsel [B][nsel][ncap][64] at row position - P (align_capture_kernel's layout)
+int launch_align_cross_attn(hipStream_t st, const f16* q, const int* off, const f16* kx, const f16* vt, f16* out, int B, int H, int Lmax, int T, int Tpad,
+                            const int* head_sel, f16* qsel, int nsel, int ncap, int P);
+
 }  // namespace wis

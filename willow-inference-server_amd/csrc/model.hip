@@ -1326,6 +1326,7 @@ int wis_model_clone(wis_model_t* parent, wis_model_t** out) {
   m->w8 = parent->w8; m->cq_fold = parent->cq_fold;
   m->use_graph = parent->use_graph;
   m->prefill_mode = parent->prefill_mode;
+  m->align_pass = parent->align_pass;
   m->al.heads = parent->al.heads;      // (the clone allocates its own align scratch on its first wis_align)
   m->tok_flags = parent->tok_flags;      // (a clone has a phrase buffer of its own and starts without a set)
   memset(&m->timing, 0, sizeof(m->timing));
@@ -1423,6 +1424,12 @@ int wis_model_set_prefill(wis_model_t* m, int mode) {
   if (!m || (mode != 0 && mode != 1)) { set_error("wis_model_set_prefill: mode %d (0: windowed, 1: one pass where it applies)", mode); return WIS_E_ARG; }
   WIS_ENTER(m, "wis_model_set_prefill")
   m->prefill_mode = mode;
+  return WIS_OK;
+}
+int wis_model_set_align_pass(wis_model_t* m, int mode) {
+  if (!m || (mode != 0 && mode != 1)) { set_error("wis_model_set_align_pass: mode %d (0: windowed, 1: one pass where it applies)", mode); return WIS_E_ARG; }
+  WIS_ENTER(m, "wis_model_set_align_pass")
+  m->align_pass = mode;
   return WIS_OK;
 }
 int wis_debug_self_kv(wis_model_t* m, int layer, int slot, int n_pos, void* k_f16, void* v_f16) {

@@ -75,6 +75,11 @@ struct AlignState {
   int kv_ub0 = 0;                         // first utterance of the group a wis_align decoder pass (or a long prompt's prefill window) runs (dec_forward_frag offsets the cross K / V by it); 0 outside
   hipEvent_t ev[5 + 128] = {}; int n_ev = 0;      // phase boundaries of the last call (wis_align_last_timing); ev[5..]: (weights, filter) pairs of the first 64 head chunks
   bool ev_partial = false;                // the last call had more head chunks than event pairs: the weights / filter split is not reported
+  // the one-pass route (wis_model_set_align_pass(m, 1); align.hip align_one_pass, kernels in align_pass.hip): row-major activations for max_batch * n_text_ctx rows,
+  // allocated by the first such call - x fp32 [rows][d]; meta: the row table, the per-layer head table and the rows' token / target / probability slot; f16: q | k | v
+  // [rows][3 d], q (cross) and the attention output [rows][d], the FFN hidden [rows][4 d].  ap_host: the host image of meta (alive until the call's last copy has run)
+  struct { float* x = nullptr; int* meta = nullptr; f16 *qkv = nullptr, *q = nullptr, *ao = nullptr, *h = nullptr; } ap;
+  std::vector<int> ap_host;
 };
 
 constexpr int ANC_W = 32;      // ancestor-table entries per row = the most steps a window holds (beam 2 / 3: 32 steps = 64 / 96 rows)
@@ -223,6 +228,7 @@ struct wis_model {
   // such call (as the logmass buffer is) - x fp32 [rows][d], {mean, rstd} [rows][2], the rows' tokens, then f16: the rows' copy xh, q, the attention output
   // ao [rows][d] each and the FFN hidden h [rows][4 d]
   int prefill_mode = 0;
+  int align_pass = 0;      // wis_model_set_align_pass: 0 = wis_align teacher-forces the text in windows of 16 positions, 1 = in one ragged pass where it applies (clones inherit)
   struct { float* x = nullptr; float* stat = nullptr; int* tok = nullptr; wis::f16 *xh = nullptr, *q = nullptr, *ao = nullptr, *h = nullptr; } pf;
 };
 

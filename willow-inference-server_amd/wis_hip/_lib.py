@@ -164,6 +164,7 @@ SYMBOLS = [
     ("wis_debug_graph_count", _i, [_vp, C.POINTER(_i)]),
     ("wis_debug_sa_long", _i, [_vp, _i]),
     ("wis_model_set_prefill", _i, [_vp, _i]),
+    ("wis_model_set_align_pass", _i, [_vp, _i]),
     ("wis_debug_self_kv", _i, [_vp, _i, _i, _i, _vp, _vp]),
     ("wis_last_timing", _i, [_vp, C.POINTER(Timing)]),
     ("wis_debug_phase_cycles", _i, [_vp, _i, _i, _i, C.POINTER(C.c_uint64)]),
@@ -214,6 +215,9 @@ SYMBOLS = [
     ("wis_op_dec_prefill_proj", _i, [_i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i]),
     ("wis_op_dec_prefill_self_attn", _i, [_i, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i]),
     ("wis_op_dec_prefill_cross_attn", _i, [_i, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i]),
+    ("wis_op_align_pass_proj", _i, [_i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i]),
+    ("wis_op_align_pass_self_attn", _i, [_i, _vp, C.POINTER(C.c_int32), _vp, _i, _i]),
+    ("wis_op_align_pass_cross_attn", _i, [_i, _vp, C.POINTER(C.c_int32), _vp, _vp, _vp, _i, _i, _i, _i, C.POINTER(C.c_int32), _vp, C.c_longlong, _i, _i, _i]),
     ("wis_op_kv_gather", _i, [_i, _vp, _vp, _i64, _i, _vp, _vp, _i, _i, _i, _i]),
     ("wis_op_no_speech", _i, [_i, _vp, _i, _i, _i, _i, _i, _i, _vp]),
     ("wis_op_no_speech_rows", _i, [_i, _vp, _i, _i, _i, _vp, _i, _i, _vp]),

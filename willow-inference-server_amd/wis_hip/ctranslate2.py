@@ -53,6 +53,7 @@ def _next_seed():
 ENCODER_COMPUTE_TYPES = ("float16", "int8")      # models.Whisper(encoder_compute_type=...)
 CROSS_KV_COMPUTE_TYPES = ("float16", "int8")     # models.Whisper(cross_kv_compute_type=...)
 PROMPT_PREFILLS = ("windowed", "one_pass")       # models.Whisper(prompt_prefill=...): wis_model_set_prefill modes 0 / 1
+ALIGN_FORWARDS = ("windowed", "one_pass")        # models.Whisper(align_forward=...): wis_model_set_align_pass modes 0 / 1
 
 
 def get_supported_compute_types(device="cuda", device_index=0):
@@ -760,7 +761,7 @@ class Whisper:
 
     def __init__(self, model_path, device="cuda", device_index=0, compute_type="default", inter_threads=1, intra_threads=0,
                  max_batch=8, max_beam=5, weights=None, arch=None, replicas_per_device=None, *, encoder_compute_type="float16", cross_kv_compute_type="float16",
-                 prompt_prefill="windowed", **_ignored):
+                 prompt_prefill="windowed", align_forward="windowed", **_ignored):
         if device not in ("cuda", "auto", "hip", "gpu"):
             raise ValueError(f"wis_hip runs on MI355X GPUs only (device={device!r}); there is no CPU path")
         # the ENCODER's linears and the cross K/V projection: "float16", or "int8" (W8A8 on the i8 matrix instruction; include/wis_hip.h
@@ -777,6 +778,11 @@ class Whisper:
         if prompt_prefill not in PROMPT_PREFILLS:
             raise ValueError(f"unsupported prompt_prefill {prompt_prefill!r} ({', '.join(PROMPT_PREFILLS)})")
         self.prompt_prefill = prompt_prefill
+        # how align() teacher-forces the known text: "windowed" (16 positions per pass over the decoder weights), or "one_pass" (every position of every
+        # utterance in one ragged GEMM-shaped pass where it applies; include/wis_hip.h wis_model_set_align_pass).  A property of the model: no decode option
+        if align_forward not in ALIGN_FORWARDS:
+            raise ValueError(f"unsupported align_forward {align_forward!r} ({', '.join(ALIGN_FORWARDS)})")
+        self.align_forward = align_forward
         _lib.require_gpu()
         # "float16" (default / "auto") or "int8_float16" (the reference's GPU default, main.py:242): per-row int8 DECODER
         # weights with f16 activations; everything else stays f16
@@ -808,6 +814,7 @@ class Whisper:
         # bounded by `replicas_per_device` (each replica owns its activations and KV caches: ~0.7 GB per utterance slot for large-v2).
         for r in self._replicas:      # (ahead of the clones: they inherit the mode)
             _lib.check(_lib.load().wis_model_set_prefill(r.handle, PROMPT_PREFILLS.index(prompt_prefill)))
+            _lib.check(_lib.load().wis_model_set_align_pass(r.handle, ALIGN_FORWARDS.index(align_forward)))
         per_dev = MAX_REPLICAS_PER_DEVICE if replicas_per_device is None else int(replicas_per_device)
         per_dev = max(1, min(int(inter_threads) if inter_threads else 1, per_dev))
         for r in list(self._replicas):
@@ -825,7 +832,7 @@ class Whisper:
         RCCL broadcast delivered straight into device memory (`create_handle(arena_device_ptr=...)`, wis_hip/dist.py)."""
         self = cls.__new__(cls)
         self.compute_type = self.encoder_compute_type = self.cross_kv_compute_type = "float16"
-        self.prompt_prefill = "windowed"
+        self.prompt_prefill = self.align_forward = "windowed"
         self.arch, self.decode_config = arch, decode_config or {}
         self.special = special_tokens_for(arch, self.decode_config.get("special"), self.decode_config.get("lang_ids"))
         self._replicas = [_Replica(h, d, arch["n_mels"], (arch["n_audio_ctx"], arch["d_model"])) for h, d in handles]

@@ -124,6 +124,8 @@ def create_app(models=None, settings=None, max_workers=None, sv=None):
         raise ValueError(f"setting long_form {s.long_form!r}: seek or chunk")
     if getattr(s, "prompt_prefill", "windowed") not in ("windowed", "one_pass"):
         raise ValueError(f"setting prompt_prefill {s.prompt_prefill!r}: windowed or one_pass")
+    if getattr(s, "align_forward", "windowed") not in ("windowed", "one_pass"):
+        raise ValueError(f"setting align_forward {s.align_forward!r}: windowed or one_pass")
     if getattr(s, "phrases_file", ""):      # (an unreadable phrase list fails the start too)
         from .whisper import load_phrases_file
         if not load_phrases_file(s.phrases_file):

@@ -145,6 +145,9 @@ class APISettings:
     # weights, "one_pass" = the prefix in one GEMM-shaped pass where that applies (f16 decoder weights and cross K/V, at most 256 prefix rows per device batch);
     # off by default, a property of the model (micro-batches are keyed as before)
     prompt_prefill: str = "windowed"
+    # word_timestamps: how the known text is teacher-forced through the decoder - "windowed" = 16 positions per pass over the decoder weights, "one_pass" = every
+    # position in one ragged GEMM-shaped pass where that applies (f16 decoder weights and cross K/V); off by default, a property of the model
+    align_forward: str = "windowed"
 
     def __post_init__(self):
         env = {k.lower(): v for k, v in os.environ.items()}

@@ -270,6 +270,7 @@ class WhisperModels:
                                                                 encoder_compute_type=self.settings.encoder_compute_type,
                                                                 cross_kv_compute_type=self.settings.cross_kv_compute_type,
                                                                 prompt_prefill=getattr(self.settings, "prompt_prefill", "windowed"),
+                                                                align_forward=getattr(self.settings, "align_forward", "windowed"),
                                                                 inter_threads=self.settings.ctranslate2_threads,
                                                                 device_index=self.device_index, max_batch=self.settings.max_batch,
                                                                 replicas_per_device=self.settings.replicas_per_gpu, max_beam=max_beam)
